@@ -15,10 +15,22 @@ collective): weak scaling.
     python bench.py --gpus N --steps K --warmup W          (N > 1: launches its own N ranks through torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-The timed region (exactly --steps steps between barrier + device sync, MAX over ranks) is repeated --reps
-times and the MEDIAN repetition is reported (all repetitions are listed in `timed_region`).
+The timed region is exactly --steps steps between barrier + device sync, MAX over ranks.  With --reps R it is
+repeated R times and the MEDIAN repetition is reported (all repetitions are listed in `timed_region`); the default
+is one repetition (15 with --full).
 
-Rank 0 prints ONE JSON line.  At N=1 it also carries
+A plain run only sets up, warms up, times the steps, writes the outputs (--dump-outputs DIR) and prints its line:
+`value` (scenes/s), `ms_per_step` and the workload's configuration.
+
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+
+--dump-outputs DIR writes what the last timed step returned to its caller as float32 .npy files under DIR (at most
+64 MB; a fixed, seeded sample of rows where an array would exceed its share): `pred_masks.npy` (every sample's mask
+logits, samples concatenated in batch order), `aux_pred_masks_<layer>.npy` (the earlier decoder layers' logits) and
+`backbone_features.npy` (per-voxel backbone features).  The inputs are seeded, so two builds run with the same
+arguments can be compared file by file.
+
+Rank 0 prints ONE JSON line.  With --full it also carries (roofline at every N, the rest at N=1)
   roofline      the dominant kernel's achieved fp32-MFMA TFLOP/s = algorithmic FLOPs per launch
                 (2 * existing (input,output) pairs * Cin * Cout) / launch duration,
                 measured live with HIP events on the launch stream in an instrumented pass after
@@ -30,7 +42,10 @@ Rank 0 prints ONE JSON line.  At N=1 it also carries
   cpu_baseline  the CPU oracle (restatement of the reference path the way MinkowskiEngine's CPU
                 backend + torch-CPU execute it) timed on this host's cores on the same scene
                 (median of 3), and `parity_vs_oracle` / `max_abs_diff`: the GPU's output for that
-                scene against the oracle's.
+                scene against the oracle's;
+and the phase, decoder-pass, evaluation-round, `value_batch4`, `train_iter`, `iou_at_k` and
+`emulated_fp32_products` passes.  --no-profile, --no-train, --no-cpu-baseline and --steps-only leave parts of
+them out.
 """
 import argparse
 import ctypes as C
@@ -556,6 +571,32 @@ def train_iter_ms(dev, voxels=80_000, batch=4, iters=5, warm=3):
                         f"median of {iters} seeded iterations after {warm} warm-ups and one untimed run of the same draws"}
 
 
+# --dump-outputs: bytes per array (aux_pred_masks: all decoder layers but the last together), 64 MB at most in all
+DUMP_BYTES = {"pred_masks": 36 << 20, "aux_pred_masks": 8 << 20, "backbone_features": 16 << 20}
+
+
+def _rows_within(x, max_bytes, seed=0):
+    """x itself, or a fixed seeded sample of its rows (sorted) when it is larger than max_bytes."""
+    row_bytes = x[0].numel() * x.element_size() if x.shape[0] else 1
+    keep = max(1, max_bytes // row_bytes)
+    if x.shape[0] <= keep:
+        return x
+    idx = np.sort(np.random.default_rng(seed).choice(x.shape[0], keep, replace=False))
+    return x[torch.from_numpy(idx).to(x.device)]
+
+
+def dump_outputs(out, dirname, suffix=""):
+    """--dump-outputs: what one step returned to its caller, as float32 .npy files (the device must be synchronised)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"pred_masks": _rows_within(torch.cat(out["pred_masks"]), DUMP_BYTES["pred_masks"])}
+    aux = out.get("aux_outputs") or []
+    for l, a in enumerate(aux):
+        arrays[f"aux_pred_masks_{l}"] = _rows_within(torch.cat(a["pred_masks"]), DUMP_BYTES["aux_pred_masks"] // len(aux))
+    arrays["backbone_features"] = _rows_within(out["backbone_features"].F, DUMP_BYTES["backbone_features"])
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a.detach().float().cpu().numpy())
+
+
 def make_scene_(voxels, seed):
     from agile3d_amd.synthetic import make_scene
     return make_scene(voxels, seed=seed)
@@ -616,8 +657,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=15,
-                    help="the timed region of --steps steps is repeated this many times; the MEDIAN repetition is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="the timed region of --steps steps is repeated this many times; the MEDIAN repetition is reported "
+                         "(default 1; 15 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline, latency, phase, eval-round, batch-4, training, CPU-baseline, IoU@k and "
+                         "emulated-fp32 passes (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--voxels", type=int, default=80_000)
     ap.add_argument("--objects", type=int, default=5)
     ap.add_argument("--clicks-per-object", type=int, default=2)
@@ -626,14 +673,15 @@ def main():
     ap.add_argument("--no-train", action="store_true", help="skip the training-iteration timing (train_iter)")
     ap.add_argument("--dump-logits", default="", help="write scene 0's logits of the first step to this file (torch.save)")
     ap.add_argument("--steps-only", action="store_true",
-                    help="only the batched steps (warm-up, timed region, instrumented pass): no latency / phase / eval-round "
-                         "/ CPU passes -- the command tools/profile_round.sh traces for profiles/kernel_avg_us.json, so that "
+                    help="with --full: only the batched steps (warm-up, timed region, instrumented pass): no latency / phase / "
+                         "eval-round / CPU passes -- the command tools/profile_round.sh traces for profiles/kernel_avg_us.json, so that "
                          "every launch of a kernel in the trace is a launch of the step the roofline object describes")
     ap.add_argument("--batch", type=int, default=int(os.environ.get("A3D_BENCH_BATCH", "16")),
                     help="scenes per step and rank (one batched SparseTensor, as the reference's collate builds)")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("A3D_BENCH_STREAMS", "4")),
                     help="scenes in flight per GPU: consecutive steps are issued round-robin on this many HIP streams")
     args = ap.parse_args()
+    reps = max(1, args.reps if args.reps is not None else (15 if args.full else 1))
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -728,7 +776,7 @@ def main():
     from agile3d_amd.hostcpu import cpu_throttle_stats
     thr0 = cpu_throttle_stats()
     rep_dt, own_dt = [], []
-    for _ in range(max(1, args.reps)):
+    for _ in range(reps):
         dt_, out = timed_steps(step, args.steps, world, dev, own=own_dt)
         rep_dt.append(dt_)
     thr1 = cpu_throttle_stats()
@@ -739,6 +787,8 @@ def main():
         dist.all_gather_object(gathered, per_rank_ms[0])
         per_rank_ms = [float(x) for x in gathered]
     assert torch.isfinite(out["pred_masks"][0]).all()
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
 
     res = {
         "metric": f"scenes/s ({round(n0 / 1000)}k-voxel, {args.objects * args.clicks_per_object} clicks)",
@@ -773,7 +823,7 @@ def main():
             res["note_multi_rank"] = (f"{world} ranks on {max(1, n_dev)} visible GPU(s): plumbing check of the N > 1 path, "
                                       "not a scaling measurement")
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # (N = 1: everything below; N > 1: rank 0 still measures the roofline object of its own GPU while the other
         # ranks wait at the closing barrier -- the line of every N carries it; latency / phase / CPU passes are N = 1 only)
         # SURVEY 8(d) latency configuration: batch 1, one stream, every scene timed on its own (device sync on
@@ -828,7 +878,7 @@ def main():
             if want:
                 got = 1e3 * d["ms"] / d["launches"]
                 res["roofline"]["rocprof_avg_launch_us"] = want
-                res["roofline"]["rocprof_command"] = ("rocprofv3 --kernel-trace --stats -- python bench.py --steps-only --streams 1"
+                res["roofline"]["rocprof_command"] = ("rocprofv3 --kernel-trace --stats -- python bench.py --full --steps-only --streams 1"
                                                       + ("" if wkey == workload_key(80_000, 16, 20) else
                                                          f" --voxels {args.voxels} --clicks-per-object {args.clicks_per_object} --batch {args.batch}"))
                 res["roofline"]["agrees_with_profiles_within_10pct"] = bool(abs(got - want) <= 0.1 * want)
@@ -966,7 +1016,7 @@ def main():
                     return model.forward_mask(*r, click_idx=cis[:4], click_time_idx=cts[:4])
             for _ in range(args.warmup):
                 step4()
-            rep4 = [timed_steps(step4, args.steps, 1, dev)[0] for _ in range(max(1, min(args.reps, 7)))]
+            rep4 = [timed_steps(step4, args.steps, 1, dev)[0] for _ in range(min(reps, 7))]
             res["value_batch4"] = round(4 * args.steps / float(np.median(rep4)), 2)
             res["value_batch4_note"] = (f"same scenes, 4 per step (round 2's protocol), {args.streams} steps in flight, median of "
                                         f"{len(rep4)} repetitions of {args.steps} steps")
@@ -993,7 +1043,7 @@ def main():
                 res["iou_at_k"] = iou_at_k(dev)
             except Exception as e:   # never lose the headline line over the extra
                 res["iou_at_k"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if rank == 0 and world == 1 and not args.steps_only and not args.no_profile and os.environ.get("A3D_CONV_EMU", "0") == "0":
+    if rank == 0 and args.full and world == 1 and not args.steps_only and not args.no_profile and os.environ.get("A3D_CONV_EMU", "0") == "0":
         # the opt-in emulated-fp32 build of the dominant conv kernel (A3D_CONV_EMU=1: every fp32 product from six bf16 MFMAs,
         # DESIGN.md 4.1) measured next to the headline in its own process -- reported, never `value`
         try:
@@ -1001,7 +1051,7 @@ def main():
             env = dict(os.environ, A3D_CONV_EMU="2")
             import tempfile
             dump = os.path.join(tempfile.gettempdir(), f"a3d_bench_emu_logits_{os.getpid()}.pt")
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps-only", "--reps", "5",
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--steps-only", "--reps", "5",
                                   "--steps", str(args.steps), "--warmup", str(args.warmup), "--batch", str(args.batch),
                                   "--streams", str(args.streams), "--dump-logits", dump], env=env, capture_output=True,
                                  text=True, timeout=600)

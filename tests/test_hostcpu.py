@@ -22,7 +22,10 @@ def test_import_caps_the_pool_to_half_the_quota():
 
 
 def _threads_in_child(env):
-    e = dict(os.environ, **env)
+    # the child's count depends on `env` alone: torch reads MKL_NUM_THREADS after OMP_NUM_THREADS (the later one wins),
+    # and the caller's own settings of the switches under test must not leak in
+    e = {k: v for k, v in os.environ.items() if k not in ("MKL_NUM_THREADS", "A3D_HOST_THREADS", "LOCAL_WORLD_SIZE")}
+    e.update(env)
     out = subprocess.run([sys.executable, "-c", "import torch, agile3d_amd; print(torch.get_num_threads())"], cwd=ROOT, env=e,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
