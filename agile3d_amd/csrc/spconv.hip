@@ -153,14 +153,9 @@ __device__ __forceinline__ void glds16_s(const float* sbase, unsigned voff, unsi
 // the MFMAs -- which would also wait for the LDS-DMA pieces it cannot see.  simm16: vmcnt 0, expcnt 7, lgkmcnt 15.
 __device__ __forceinline__ void wait_all_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
-// BN output columns, CH input channels per stage; PAIR: weight fragments two at a time (16 registers for the B operand
-// instead of 8 BN / 16: the low-register build, 3-4 workgroups per CU)
-// PAIR == 2 (opt-in, A3D_CONV_EMU=1, 96 columns x 32 channels only): fp32 products from SIX bf16 MFMAs -- both operands
-// split into three bf16 planes (x = h + m + l by truncation, every remainder exact), h h + h m + m h + h l + m m + l h on
-// v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  Error: tools/bf16x6_ubench.hip (5.1e-6 against the exact chain's 7.5e-6
-// over 2592 products) and, bounded per shape class on adversarial inputs, tests/test_gpu_conv.py::
-// test_emulated_fp32_products_error_bound (a-priori (2^-20 + 6 (K cin / 32) 2^-24) sum|x||w|; domain |x| >= 2^-100 or 0: the
-// matrix cores drop subnormal bf16 planes); stage loop 1.84x faster; weights packed as three planes.
+// BN output columns, CH input channels per stage; PAIR (0 or 1): 1 = weight fragments two at a time (16 registers for the
+// B operand instead of 8 BN / 16: the low-register build, 3-4 workgroups per CU), 0 = all of a 16-channel step's fragments
+// in registers
 // FUSE: the block's residual projection (BasicBlock.downsample: 1x1 conv + BatchNorm on the block input,
 // resnet_block.py:59-61) as one more "offset" of the block's second conv: every tile ends with cin2 / CH stages that
 // gather the output rows themselves from the block input and multiply them with the 1x1 weight (both BatchNorm scales
@@ -174,12 +169,9 @@ __device__ __forceinline__ void wait_all_vmem() { __builtin_amdgcn_s_waitcnt(0x0
 template <int BN, int CH, int PAIR, bool FUSE = false, int STATS = 0, bool HEAD = false>
 __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) : ((BN <= 96 && CH <= 48) ? 3 : 2))
     k_conv_sk(const SkArgs a) {
-  static_assert(!FUSE || PAIR != 2, "the fused projection runs on the exact-fp32 builds");
   constexpr int RG = 1;   // 16-row groups per wave (two per wave -- 128-row tiles -- was tried and did not pay)
-  constexpr bool EMU = PAIR == 2;
-  static_assert(!EMU || CH == 32, "one 16x16x32 block per stage and column tile");
   constexpr int NCT = BN / 16, NS = CH / 16, NW = 4, kTile = 64 * RG;
-  constexpr int NPIECE = EMU ? 3 * NCT : NS * NCT;   // 1 KB pieces of a stage's weights: 3 bf16 planes per column tile / fp32
+  constexpr int NPIECE = NS * NCT;   // 1 KB pieces of a stage's weights
   constexpr int WV = (NPIECE + NW - 1) / NW;
   constexpr int WF = NPIECE * 256;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -272,11 +264,10 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
 #pragma unroll
   for (int i = 0; i < WV; ++i) {
     const int q = wave + NW * i;
-    wsrc[i] = EMU ? (unsigned)(q * 1024 + lane * 16)
-                  : (unsigned)(((q / NCT) * cout16 + (q % NCT)) * 1024 + lane * 16);
+    wsrc[i] = (unsigned)(((q / NCT) * cout16 + (q % NCT)) * 1024 + lane * 16);
     wdst[i] = (unsigned)q * 1024u;
   }
-  const unsigned lane_a_off = EMU ? 32u * g : 16u * g;   // channels 4g..4g+3 of a 16-channel step (EMU: 8g..8g+7 of the 32)
+  const unsigned lane_a_off = 16u * g;   // channels 4g..4g+3 of a 16-channel step
   const int wrow = 16 * RG * wave + j;   // this lane's row inside the tile for its group 0 (group r: + 16 r)
 
   const int n_u = u_hi - u_lo + 1;
@@ -365,11 +356,10 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
             const int row = proj ? min(r0 + wrow + 16 * r, a.c.n_out) : rows[r];   // n_out = the zero row of in2
             const unsigned roff = (unsigned)row * row_bytes + lane_a_off;
 #pragma unroll
-            for (int Sx = 0; Sx < NS; ++Sx) A[r][Sx] = *(const f32x4*)(ar + roff + (EMU ? 16 : 64) * Sx);
+            for (int Sx = 0; Sx < NS; ++Sx) A[r][Sx] = *(const f32x4*)(ar + roff + 64 * Sx);
           }
         }
-        const float* wst = EMU ? a.c.w + (((size_t)kk * nchunk + cc) * cout16 + ct0) * (3 * 256)
-                               : wbase + ((size_t)kk * cin16 + (size_t)cc * NS) * cout16 * 256;
+        const float* wst = wbase + ((size_t)kk * cin16 + (size_t)cc * NS) * cout16 * 256;
         const unsigned dst = ring_addr + (unsigned)slot * (WF * 4u);
 #pragma unroll
         for (int i = 0; i < WV; ++i)
@@ -378,44 +368,7 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
       auto compute = [&](const f32x4 (&A)[RG][NS], int kk, int slot) {
         if (!((gm >> kk) & 1u)) return;
         const f32x4* Ws = (const f32x4*)(wring + slot * WF) + lane;
-        if constexpr (EMU) {
-          typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-          typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-          // this lane's 8 channels of its row -> three bf16 planes (truncation: v = h + r1, r1 = m + r2, exact in fp32)
-          u32x4 x[3];
-#pragma unroll
-          for (int pq = 0; pq < 4; ++pq) {
-            uint32_t hh[2], mm[2], ll[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              const float v = A[0][pq >> 1][2 * (pq & 1) + e];
-              const uint32_t hb = __float_as_uint(v) & 0xffff0000u;
-              const float r1 = v - __uint_as_float(hb);
-              const uint32_t mb = __float_as_uint(r1) & 0xffff0000u;
-              const float r2 = r1 - __uint_as_float(mb);
-              hh[e] = hb, mm[e] = mb, ll[e] = __float_as_uint(r2) & 0xffff0000u;
-            }
-            x[0][pq] = (hh[0] >> 16) | hh[1];
-            x[1][pq] = (mm[0] >> 16) | mm[1];
-            x[2][pq] = (ll[0] >> 16) | ll[1];
-          }
-          const bf16x8 xh = __builtin_bit_cast(bf16x8, x[0]), xm = __builtin_bit_cast(bf16x8, x[1]),
-                       xl = __builtin_bit_cast(bf16x8, x[2]);
-          const u32x4* Wq = (const u32x4*)Ws;
-#pragma unroll
-          for (int ct = 0; ct < NCT; ++ct) {
-            const bf16x8 wh = __builtin_bit_cast(bf16x8, Wq[(3 * ct + 0) * 64]), wm = __builtin_bit_cast(bf16x8, Wq[(3 * ct + 1) * 64]),
-                         wl = __builtin_bit_cast(bf16x8, Wq[(3 * ct + 2) * 64]);
-            f32x4 c = acc[0][ct];   // smallest terms first
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, xm, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, xh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xm, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh, c, 0, 0, 0);
-            acc[0][ct] = c;
-          }
-        } else if constexpr (PAIR == 0) {
+        if constexpr (PAIR == 0) {
           // the weight fragments of a whole 16-channel step in registers, the next step's read behind this step's MFMAs;
           // consecutive MFMAs go to different accumulators
           f32x4 b[2][NCT];
@@ -1684,45 +1637,6 @@ __global__ void k_pack_weight(const float* __restrict__ w, int K, int cin, int c
   out[e] = w[((size_t)k * cin + 16 * S + 4 * g + t) * cout + 16 * ct + j];
 }
 
-// the same weights as three bf16 planes for the emulated-fp32 build of the 96-column kernel:
-//   Wb[K][cin/32][cout/16][plane h, m, l][lane = 16 g + j][e] = plane(W[k][32 c + 8 g + e][16 ct + j]),  8 bf16 per lane
-__global__ void k_pack_weight_emu(const float* __restrict__ w, int K, int cin, int cout, uint16_t* out) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per weight
-  const size_t total = (size_t)K * cin * cout;
-  if (e >= total) return;
-  const int el = (int)(e & 7), lane = (int)((e >> 3) & 63);
-  size_t rest = e >> 9;
-  const int cout16 = cout >> 4, cin32 = cin >> 5;
-  const int ct = (int)(rest % cout16);
-  rest /= cout16;
-  const int c = (int)(rest % cin32);
-  const int k = (int)(rest / cin32);
-  const int g = lane >> 4, j = lane & 15;
-  const float v = w[((size_t)k * cin + 32 * c + 8 * g + el) * cout + 16 * ct + j];
-  const uint32_t hb = __float_as_uint(v) & 0xffff0000u;
-  const float r1 = v - __uint_as_float(hb);
-  const uint32_t mb = __float_as_uint(r1) & 0xffff0000u;
-  const float r2 = r1 - __uint_as_float(mb);
-  const uint32_t lb = __float_as_uint(r2) & 0xffff0000u;
-  const size_t tile = (((size_t)k * cin32 + c) * cout16 + ct) * 3;   // 1 KB planes
-  out[(tile + 0) * 512 + lane * 8 + el] = (uint16_t)(hb >> 16);
-  out[(tile + 1) * 512 + lane * 8 + el] = (uint16_t)(mb >> 16);
-  out[(tile + 2) * 512 + lane * 8 + el] = (uint16_t)(lb >> 16);
-}
-
-// which layers run the emulated-fp32 build (and have their weights packed for it): opt-in
-static bool conv_emu(int K, int cin, int cout) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("A3D_CONV_EMU");
-    on = e ? atoi(e) : 0;
-  }
-  // on == 1: the 96-column kernels (levels 0 / 1 of the decoder side, 40 % of a step's kernel time); on == 2: every gathered conv
-  if (!on || K <= 1 || cin % 32 != 0) return false;
-  if (cout == 96) return true;
-  return on >= 2 && (cout == 32 || cout == 64 || cout % 128 == 0);
-}
-
 // ------------------------------------------------------------------------------ host: launch
 constexpr int kMaxQueuesPerOp = 1024;  // ints of zeroed per-op state: k_conv_sk ticket [0], failure word [1], hand-off flags [2..2+G)
 constexpr int kSkMaxG = 1020;
@@ -1786,14 +1700,9 @@ static SkPlan plan_sk(int n_rows, int K, int cin, int cout, bool handoff, int fo
     p.nchunk = p.ch ? cin / p.ch : 1;
     p.n_cblk = cout / p.bn;
     p.pair = sk_pair(p.bn, p.ch, n_rows);
-    if (conv_emu(K, cin, cout)) {
-      p.ch = 32;
-      p.nchunk = cin / 32;
-      p.pair = 2;
-    }
     const int mfma_per_stage = p.ch / 4 * (p.bn / 16);
     p.ov = mfma_per_stage >= 128 ? 1 : mfma_per_stage >= 64 ? 2 : 3;   // per-tile overhead in stages (swept in round 2)
-    p.lds = (size_t)2 * p.ch * p.bn * (p.pair == 2 ? 6 : 4) + 64;   // three bf16 planes: 6 bytes per weight
+    p.lds = (size_t)2 * p.ch * p.bn * 4 + 64;
     gmax = 256 * sk_wgs_per_cu(p.bn, p.ch, p.pair, p.lds);
     if (gmax > kSkMaxG) gmax = kSkMaxG;
     const long long est = (long long)p.n_cblk * p.ntile * ((long long)p.nchunk * k_eff + p.ov);
@@ -1848,7 +1757,7 @@ static int deep_mode() {
 static DeepPlan plan_deep(int n_rows, int K, int cin, int cout, int cin2, bool up = false) {
   DeepPlan best;
   memset(&best, 0, sizeof(best));
-  if (!deep_mode() || K < 2 || K > 27 || cin % 32 || cout % 32 || conv_emu(K, cin, cout)) return best;
+  if (!deep_mode() || K < 2 || K > 27 || cin % 32 || cout % 32) return best;
   static float max_us = -1.f;
   if (max_us < 0.f) {
     const char* e = getenv("A3D_DEEP_MAX_US");
@@ -1936,10 +1845,6 @@ static void allow_big_lds() {
   A3D_BIGF(64, 32) A3D_BIGF(64, 64) A3D_BIGF(96, 32) A3D_BIGF(128, 32)
 #undef A3D_BIGF
   A3D_ALLOW_LDS(160 * 1024, (k_conv_sk<96, 32, 1, false, 0, true>));
-  A3D_ALLOW_LDS(160 * 1024, k_conv_sk<96, 32, 2>);
-  A3D_ALLOW_LDS(160 * 1024, k_conv_sk<128, 32, 2>);
-  A3D_ALLOW_LDS(160 * 1024, k_conv_sk<64, 32, 2>);
-  A3D_ALLOW_LDS(160 * 1024, k_conv_sk<32, 32, 2>);
 #define A3D_BIGD(BN_, CH_) \
   A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, false, 3>)); \
   A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, true, 3>)); \
@@ -1972,7 +1877,7 @@ static bool sk_fused_ok(int n_rows, int cin, int cout, int cin2) {
   if (cin2 <= 0) return false;
   SkPlan p = plan_sk(n_rows, 27, cin, cout, true);
   if (p.ch && cin2 % p.ch != 0 && cin2 % 32 == 0) p = plan_sk(n_rows, 27, cin, cout, true, 32);
-  if (!p.ch || p.pair == 2 || cin2 % p.ch != 0) return false;
+  if (!p.ch || cin2 % p.ch != 0) return false;
   return (p.bn == 64 && (p.ch == 32 || p.ch == 64)) || (p.bn == 96 && p.ch == 32) || (p.bn == 128 && p.ch == 32);
 }
 
@@ -1981,7 +1886,6 @@ static bool sk_fused_ok(int n_rows, int cin, int cout, int cin2) {
 // is there a fused-head build for what plan_sk picks here?  (a3d_program_run runs the 1x1 layer on its own otherwise)
 static bool sk_head_ok(int n_rows, int K, int cin, int cout, int head_cout, bool handoff) {
   if (cout != 96 || head_cout <= 0 || head_cout % 16 || head_cout > 256 || cin % 32) return false;
-  if (conv_emu(K, cin, cout)) return false;
   const SkPlan p = plan_sk(n_rows, K, cin, cout, handoff);
   return p.bn == 96 && p.ch == 32 && p.pair == 1;
 }
@@ -1992,8 +1896,8 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
                           hipStream_t st, float* stats = nullptr, int stats_ld = 0, int* stats_rows = nullptr,
                           const BwArgs* bw = nullptr) {
   allow_big_lds();
-  if (stats && (c.scale || c.shift || c.relu || c.cin2 > 0 || conv_emu(c.K, c.cin, c.cout) || !stats_rows || (c.res && !bw))) {
-    set_error("spconv: BatchNorm statistics are taken of a raw convolution (no epilogue, no fused projection, exact fp32)");
+  if (stats && (c.scale || c.shift || c.relu || c.cin2 > 0 || !stats_rows || (c.res && !bw))) {
+    set_error("spconv: BatchNorm statistics are taken of a raw convolution (no epilogue, no fused projection)");
     return A3D_ERR_UNSUPPORTED;
   }
   if (c.cin % 32 != 0 || c.cout % 16 != 0 || !(c.cout % 128 == 0 || c.cout == 32 || c.cout == 64 || c.cout == 96)) {
@@ -2008,7 +1912,7 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
     set_error("spconv: input of %d rows x %d floats exceeds the 4 GB gather window", c.n_in, c.ldi);
     return A3D_ERR_UNSUPPORTED;
   }
-  if (c.cin2 == 0 && conv_wl_supported(c) && !conv_emu(c.K, c.cin, c.cout)) {
+  if (c.cin2 == 0 && conv_wl_supported(c)) {
     if (stats) *stats_rows = 16;
     return launch_conv_wl(c, st, stats, stats_ld, bw);
   }
@@ -2145,10 +2049,10 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
   ProfScope ps(st, A3D_PROF_SPCONV, p.bn, c.K | (c.cin2 << 8) | (c.head_cout << 20), c.cin, c.cout, c.n_out, c.tag_table, c.tag_level,
                p.ch);
   if (c.cin2 > 0) {
-    // fused residual projection: the exact-fp32 builds of the shapes the U-Net's second block convs run on
-    if (c.K != 27 || !c.in2 || p.pair == 2 || c.cin2 % p.ch != 0 || (c.ldi2 & 3) ||
+    // fused residual projection: the shapes the U-Net's second block convs run on
+    if (c.K != 27 || !c.in2 || c.cin2 % p.ch != 0 || (c.ldi2 & 3) ||
         (uint64_t)(c.n_out + 1) * (uint64_t)c.ldi2 * 4ull >= (1ull << 32)) {
-      set_error("spconv: fused projection unsupported here (K=%d cin2=%d stage %d emulated=%d)", c.K, c.cin2, p.ch, p.pair == 2);
+      set_error("spconv: fused projection unsupported here (K=%d cin2=%d stage %d)", c.K, c.cin2, p.ch);
       return A3D_ERR_UNSUPPORTED;
     }
     a.nchunk2 = c.cin2 / p.ch;
@@ -2158,14 +2062,6 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
     A3D_LF(64, 32) A3D_LF(64, 64) A3D_LF(96, 32) A3D_LF(128, 32)
     { set_error("spconv: no fused kernel for BN %d CH %d", p.bn, p.ch); return A3D_ERR_UNSUPPORTED; }
 #undef A3D_LF
-    A3D_LAUNCH_CHECK();
-    return A3D_OK;
-  }
-  if (p.pair == 2) {
-    if (p.bn == 96) k_conv_sk<96, 32, 2><<<p.G, 256, p.lds, st>>>(a);
-    else if (p.bn == 128) k_conv_sk<128, 32, 2><<<p.G, 256, p.lds, st>>>(a);
-    else if (p.bn == 64) k_conv_sk<64, 32, 2><<<p.G, 256, p.lds, st>>>(a);
-    else k_conv_sk<32, 32, 2><<<p.G, 256, p.lds, st>>>(a);
     A3D_LAUNCH_CHECK();
     return A3D_OK;
   }
@@ -2277,11 +2173,7 @@ extern "C" int a3d_pack_conv_weight(const float* w_dev, int kernel_volume, int c
     return A3D_ERR_INVALID;
   }
   const size_t total = (size_t)kernel_volume * cin * cout;
-  if (conv_emu(kernel_volume, cin, cout))
-    k_pack_weight_emu<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(w_dev, kernel_volume, cin, cout,
-                                                                                      (uint16_t*)packed_dev);
-  else
-    k_pack_weight<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(w_dev, kernel_volume, cin, cout, packed_dev);
+  k_pack_weight<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(w_dev, kernel_volume, cin, cout, packed_dev);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -2325,8 +2217,7 @@ extern "C" int a3d_pack_conv_weights_multi(const a3d_pack_job* table_dev, int n_
 }
 
 extern "C" size_t a3d_conv_weight_packed_floats(int kernel_volume, int cin, int cout) {
-  const size_t total = (size_t)kernel_volume * cin * cout;
-  return conv_emu(kernel_volume, cin, cout) ? total + total / 2 : total;   // three bf16 planes = 1.5 floats per weight
+  return (size_t)kernel_volume * cin * cout;
 }
 
 extern "C" size_t a3d_program_workspace_bytes(const a3d_scene* s, const a3d_buf_desc* bufs, int n_bufs,
@@ -2532,8 +2423,8 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
       c1.in2 = nullptr, c1.cin2 = 0, c1.ldi2 = 0, c1.relu = 0;
       rc = launch_conv_sk(c1, pre, partial, L.partial_floats, queues + (size_t)i * kMaxQueuesPerOp, st);
       if (rc != A3D_OK) return rc;
-      if (conv_emu(27, a.cin, a.cout) || a.out_map) {
-        set_error("op %d: fused projection has no fallback in the emulated-fp32 build", i);
+      if (a.out_map) {
+        set_error("op %d: fused projection has no fallback for a row-mapped output", i);
         return A3D_ERR_UNSUPPORTED;
       }
       ConvArgs c2;

@@ -127,11 +127,9 @@ class BackboneProgram:
         bb = model.backbone
         dev = device
 
-        # the residual projections (BasicBlock.downsample) run inside the block's second conv (a3d_op.proj_*): not with the
-        # emulated-fp32 conv products (their weights are packed as bf16 planes), and A3D_FUSE_PROJ=0 keeps the separate
-        # 1x1 launches (tests compare the two)
-        fuse_proj = (os.environ.get("A3D_FUSE_PROJ", "1") != "0" and os.environ.get("A3D_CONV_EMU", "0") == "0"
-                     if fuse_proj is None else fuse_proj)
+        # the residual projections (BasicBlock.downsample) run inside the block's second conv (a3d_op.proj_*);
+        # A3D_FUSE_PROJ=0 keeps the separate 1x1 launches (tests compare the two)
+        fuse_proj = os.environ.get("A3D_FUSE_PROJ", "1") != "0" if fuse_proj is None else fuse_proj
         self.fused_projections = 0
 
         def pack(conv, w=None):

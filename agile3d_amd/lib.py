@@ -272,6 +272,9 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
+    if os.environ.get("A3D_CONV_EMU", "0") != "0":   # refuse rather than run the exact build under the old switch's name
+        raise A3DError("A3D_CONV_EMU: the emulated-fp32 (bf16 x 6) convolution build was removed; unset the variable "
+                       "or set it to 0 (every convolution runs the exact-fp32 build)")
     if not os.path.exists(LIB_PATH):
         raise A3DError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(there is no CPU fallback)")

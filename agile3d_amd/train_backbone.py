@@ -81,7 +81,6 @@ class PackedWeights:
 
     def _build_table(self):
         import numpy as np
-        lib = L.load()
         dt = np.dtype([("src", "<u8"), ("dst", "<u8"), ("K", "<i4"), ("cin", "<i4"), ("cout", "<i4"), ("src_cin", "<i4"),
                        ("src_cout", "<i4"), ("transposed", "<i4"), ("flip", "<i4"), ("c0", "<i4"), ("chunk0", "<i4"),
                        ("pad", "<i4")])
@@ -90,13 +89,11 @@ class PackedWeights:
         for key, (ver, wf, parts, conv, kind) in self._c.items():
             w = conv.kernel3().detach()
             K, cin, cout = w.shape
-            if not w.is_contiguous() or lib.a3d_conv_weight_packed_floats(K, cin, cout) != K * cin * cout:
-                return None          # a weight the one-launch pack does not cover (emulated-fp32 build, strided view)
+            if not w.is_contiguous():
+                return None          # a weight the one-launch pack does not cover (strided view)
             dev = w.device
             jobs = [(w.data_ptr(), wf.data_ptr(), K, cin, cout, cin, cout, 0, 0, 0)]
             for c0, width, pk in parts:
-                if lib.a3d_conv_weight_packed_floats(K, cout, width) != K * cout * width:
-                    return None
                 jobs.append((w.data_ptr(), pk.data_ptr(), K, cout, width, cin, cout, 1, 1 if kind == L.OP_CONV3 else 0, c0))
             for j in jobs:
                 rows.append(j + (chunk, 0))
@@ -180,7 +177,7 @@ class BackboneTape:
     out of the conv kernel's epilogue: no statistics pass over the raw output), concatenations are column slices of one
     buffer (producers write into their slice, nothing is copied), and in the backward every fan-in is summed inside the
     producing kernel's epilogue (the input-gradient convs accumulate into the node's gradient buffer): no torch add /
-    cat / copy on the tape.  ``sync_bn`` and the emulated-fp32 build (A3D_CONV_EMU) keep the layer-at-a-time BatchNorm."""
+    cat / copy on the tape.  ``sync_bn`` keeps the layer-at-a-time BatchNorm."""
 
     def __init__(self, model, scene, feats3: torch.Tensor, sync_bn=None):
         import os
@@ -188,7 +185,7 @@ class BackboneTape:
             raise RuntimeError("BackboneTape runs on the GPU only")
         self.model, self.scene = model, scene
         self.sync_bn = _sync_bn_default() if sync_bn is None else bool(sync_bn)
-        self.fused_bn = not self.sync_bn and os.environ.get("A3D_CONV_EMU", "0") == "0"
+        self.fused_bn = not self.sync_bn
         self.fuse_bwd = os.environ.get("A3D_FUSE_BN_BWD", "1") != "0"     # tests / A-B: the layer-at-a-time BatchNorm backward
         self.feats3 = feats3.to(torch.float32).contiguous()
         self.steps = []          # backward closures, in forward order

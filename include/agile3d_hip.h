@@ -182,9 +182,8 @@ typedef struct {
 /* W[K][cin][cout] (ME layout, models/modules/common.py:137-155) -> MFMA B-fragment order */
 int a3d_pack_conv_weight(const float* w_dev, int kernel_volume, int cin, int cout,
                          float* packed_dev, void* stream);
-/* floats the packed form of a [kernel_volume][cin][cout] weight occupies: kernel_volume * cin * cout, except for the layers
- * the opt-in emulated-fp32 build runs (A3D_CONV_EMU=1: 96-column gathered convolutions, three bf16 planes = 1.5 floats per
- * weight).  Size `packed_dev` of a3d_pack_conv_weight with it. */
+/* floats the packed form of a [kernel_volume][cin][cout] weight occupies: kernel_volume * cin * cout (the packing only
+ * reorders).  Size `packed_dev` of a3d_pack_conv_weight with it. */
 size_t a3d_conv_weight_packed_floats(int kernel_volume, int cin, int cout);
 
 size_t a3d_program_workspace_bytes(const a3d_scene* s, const a3d_buf_desc* bufs, int n_bufs,
@@ -239,7 +238,7 @@ int    a3d_conv_apply(const a3d_scene* s, int kind, int level_in, const float* x
  *     BasicBlock.forward (resnet_block.py:48-64) in training mode: raw_dev [n_out][ld_raw] = the conv's output (kept for
  *     the backward), y_dev as a3d_bn_train_forward's.  The batch statistics come out of the conv kernel's epilogue (per
  *     64-row tile: column sums and squared deviations from the tile mean, merged in fp64 in a fixed order), so the raw
- *     output is not read again for them.  Exact-fp32 builds only (not under A3D_CONV_EMU). */
+ *     output is not read again for them. */
 size_t a3d_conv_state_bytes(void);
 /* Small levels (a layer with a few stages of work per CU: levels 2-4 of one scene; res16unet.py:89-147,242-259) run on
  * k_conv_deep -- static (tile, column block, part) workgroups, both operands by LDS-DMA three stages ahead, a cut tile
@@ -443,8 +442,8 @@ int    a3d_adamw_step_multi(const a3d_mt_tensor* table_dev, int n_tensors, int64
  *   transposed = 0:  W[k][ci][co]      = src[k][ci][co]                         (src is [K][cin][cout])
  *   transposed = 1:  W[k][ci][co]      = src[flip ? K-1-k : k][c0 + co][ci]     (src is [K][src_cin][cin]: the weight of
  *                                        the input-gradient conv, output channels = the slice [c0, c0 + cout) of src's inputs)
- * chunk0 = number of A3D_MT_CHUNK-element chunks of the jobs before it (as a3d_mt_tensor).  Exact-fp32 packs only
- * (a3d_conv_weight_packed_floats(K, cin, cout) == K * cin * cout). */
+ * chunk0 = number of A3D_MT_CHUNK-element chunks of the jobs before it (as a3d_mt_tensor); dst holds K * cin * cout floats
+ * (the same layout as a3d_pack_conv_weight's). */
 typedef struct a3d_pack_job {
   const float* src;
   float* dst;
