@@ -15,6 +15,11 @@
 // and a two-level reduction adds the <= 256 slabs in a fixed order: deterministic.
 // dS is needed in two register layouts (rows x columns and columns x rows, because an MFMA contracts over the lane-group
 // index of BOTH operands): the backward kernels compute it once and transpose it through a wave-private LDS tile.
+// Dropout (DROP = true builds): the probabilities that multiply V are multiplied by Z = keep / (1 - p), the
+// keep bits regenerated per 16 x 16 tile from the counter-based RNG of common.h (one Philox call per lane and tile: the
+// four columns a lane holds in the forward layout; the backward's transposed layout gathers its bits with four shuffles).
+// The softmax statistics stay those of the undropped scores; the backward uses dS = P (Z dP - D), dV += (P Z)^T dO with D
+// the row sums of dO o O of the dropped output.  DROP = false is the code without dropout, unchanged.
 #include "common.h"
 
 namespace a3d {
@@ -45,6 +50,10 @@ __device__ __forceinline__ f32x4 ld4(const float* base, int64_t row, int64_t nro
 #define FL_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 // exp through v_exp_f32 (2^x): one multiply + one transcendental instead of expf's ~15 instructions; |x| <= ~100 here, the
 // argument's rounding moves the result by |x| 2^-24 relative -- inside the 2e-5 the float64 comparison allows (tests)
+// the kernels' dropout argument: DROP = false builds take none (their argument block is that of the code without
+// dropout), DROP = true builds one DropParams
+__device__ __forceinline__ DropParams fl_drop_arg() { return DropParams{}; }
+__device__ __forceinline__ DropParams fl_drop_arg(const DropParams& dp) { return dp; }
 __device__ __forceinline__ float fl_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 // mask bytes [row][col .. col + 3] as one (unaligned) load; `ok`: the four bytes lie inside the row
 __device__ __forceinline__ unsigned ld_mask4(const unsigned char* __restrict__ mask, size_t row, int col, int ncols) {
@@ -66,10 +75,11 @@ __device__ __forceinline__ unsigned ld_mask4(const unsigned char* __restrict__ m
 // registers across all of them (QT = tiles the build holds, nqt <= QT the call's), so the keys and values are read once --
 // the first build walked all chunks once per query tile -- and the next 16-key group's fragments and mask words are in
 // flight while the current group is multiplied.
-template <int QT>
+template <int QT, bool DROP, typename... DP>
 __global__ void __launch_bounds__(512) k_fl_c2s_fwd(const float* __restrict__ qs, const float* __restrict__ K,
                                                     const float* __restrict__ V, const unsigned char* __restrict__ mask,
-                                                    int Lq, int Lk, float* __restrict__ part, int q0) {
+                                                    int Lq, int Lk, float* __restrict__ part, int q0, DP... dps) {
+  const DropParams dp = fl_drop_arg(dps...);
   // q0: first query of this launch (a call with more queries than one build holds runs it once per block of 16 QT)
   const int lane = threadIdx.x & 63, h = threadIdx.x >> 6;
   const int g = lane >> 4, j = lane & 15;
@@ -139,6 +149,11 @@ __global__ void __launch_bounds__(512) k_fl_c2s_fwd(const float* __restrict__ qs
         }
         l[qt] = l[qt] * sc + ps;
         acc[qt] *= sc;
+        if constexpr (DROP) {      // keys 4g + t of query j: one Philox call
+          const unsigned km = drop_keep4(dp, (uint32_t)h * (uint32_t)Lq + (uint32_t)(q0 + qt * 16 + j), (uint32_t)(p0 + 4 * g));
+#pragma unroll
+          for (int t = 0; t < 4; ++t) pw[t] = (km >> t) & 1u ? pw[t] * dp.scale : 0.f;
+        }
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[qt] = FL_MFMA(vf[t], pw[t], acc[qt]);
       }
@@ -235,11 +250,24 @@ __device__ __forceinline__ f32x4 fl_transpose(float* tile, const f32x4& v, int g
   asm volatile("" ::: "memory");
   return *(const f32x4*)(tile + j * kFlTLd + 4 * g);
 }
+// keep bits of the backward's (rows 4g + t, column j) layout of the 16 x 16 tile at logical row r0 / column c0: lane (g, j)
+// draws the Philox block of row r0 + 4g + (j >> 2), columns c0 + 4 (j & 3) .. + 3, and bit t of the result comes from the
+// lane that drew row 4g + t's block holding column j
+__device__ __forceinline__ unsigned fl_keep_tr(const DropParams& dp, uint32_t r0, uint32_t c0, int g, int j) {
+  const int km = (int)drop_keep4(dp, r0 + (uint32_t)(4 * g + (j >> 2)), c0 + (uint32_t)(4 * (j & 3)));
+  unsigned zb = 0u;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) zb |= (((unsigned)__shfl(km, g * 16 + 4 * t + (j >> 2), 64) >> (j & 3)) & 1u) << t;
+  return zb;
+}
+template <bool DROP, typename... DP>
 __global__ void __launch_bounds__(512) k_fl_c2s_bwd(const float* __restrict__ qs, const float* __restrict__ K,
                                                     const float* __restrict__ V, const unsigned char* __restrict__ mask,
                                                     int Lq, int Lk, const float* __restrict__ stats,
                                                     const float* __restrict__ Ds, const float* __restrict__ dO,
-                                                    float* __restrict__ dqp, float* __restrict__ dK, float* __restrict__ dV) {
+                                                    float* __restrict__ dqp, float* __restrict__ dK, float* __restrict__ dV,
+                                                    DP... dps) {
+  const DropParams dp = fl_drop_arg(dps...);
   const int lane = threadIdx.x & 63, h = threadIdx.x >> 6;
   const int g = lane >> 4, j = lane & 15;
   const int nchunk = (Lk + kFlChunk - 1) / kFlChunk;
@@ -307,12 +335,19 @@ __global__ void __launch_bounds__(512) k_fl_c2s_bwd(const float* __restrict__ qs
           dp_qk = FL_MFMA(q.dof[t], vr[gi][t], dp_qk);
         }
         f32x4 p_qk, ds_qk;
+        const unsigned zb = DROP ? fl_keep_tr(dp, (uint32_t)h * (uint32_t)Lq + (uint32_t)(qt * 16), (uint32_t)p0, g, j) : 0u;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const bool blocked = p0 + j >= Lk || qt * 16 + 4 * g + t >= Lq || ((mqk[gi] >> (8 * t)) & 0xffu) != 0u;
           const float p = blocked ? 0.f : fl_exp(s_qk[t] - q.mq[t]) * q.rlq[t];
-          p_qk[t] = p;
-          ds_qk[t] = p * (dp_qk[t] - q.Dq[t]);
+          if constexpr (DROP) {
+            const float z = (zb >> t) & 1u ? dp.scale : 0.f;
+            p_qk[t] = p * z;
+            ds_qk[t] = p * (z * dp_qk[t] - q.Dq[t]);
+          } else {
+            p_qk[t] = p;
+            ds_qk[t] = p * (dp_qk[t] - q.Dq[t]);
+          }
         }
         const f32x4 ds_kq = fl_transpose(tr_l[h][gi], ds_qk, g, j);   // [key 4g+t][query j]
 #pragma unroll
@@ -365,9 +400,11 @@ __global__ void k_fl_reduce_final(const float* __restrict__ tmp, int nslice, int
 // forward: per 16-point group and head, online softmax over the key tiles; stats[n][h][2] = m, l.  The workgroup's four
 // 16-point groups walk the key tiles TOGETHER (their flash states and query fragments stay in registers), so a key
 // tile's fragments are loaded once per chunk -- with the next tile's in flight -- instead of once per group.
+template <bool DROP, typename... DP>
 __global__ void __launch_bounds__(512) k_fl_s2c_fwd(const float* __restrict__ qs, const float* __restrict__ K,
                                                     const float* __restrict__ V, int Lq, int Lk, float* __restrict__ O,
-                                                    float* __restrict__ stats) {
+                                                    float* __restrict__ stats, DP... dps) {
+  const DropParams dp = fl_drop_arg(dps...);
   const int lane = threadIdx.x & 63, h = threadIdx.x >> 6;
   const int g = lane >> 4, j = lane & 15;
   const int nkt = (Lk + 15) / 16;
@@ -419,6 +456,11 @@ __global__ void __launch_bounds__(512) k_fl_s2c_fwd(const float* __restrict__ qs
       }
       l[gi] = l[gi] * sc + ps;
       acc[gi] *= sc;
+      if constexpr (DROP) {        // keys 4g + t of point j: one Philox call
+        const unsigned km = drop_keep4(dp, (uint32_t)h * (uint32_t)Lq + (uint32_t)(pbeg + gi * 16 + j), (uint32_t)(kt * 16 + 4 * g));
+#pragma unroll
+        for (int t = 0; t < 4; ++t) pw[t] = (km >> t) & 1u ? pw[t] * dp.scale : 0.f;
+      }
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc[gi] = FL_MFMA(vf[t], pw[t], acc[gi]);
     }
@@ -442,10 +484,13 @@ __global__ void __launch_bounds__(512) k_fl_s2c_fwd(const float* __restrict__ qs
 // Round 6: the point side of the chunk's four groups (rows and transposed columns of q and dO, statistics, the dO . O row
 // sums) is loaded ONCE per chunk and held across the key tiles, the next key tile's fragments are requested before the
 // current tile's products (both were re-loaded inside the innermost loop, thirteen loads per 28 MFMAs).
+template <bool DROP, typename... DP>
 __global__ void __launch_bounds__(512) k_fl_s2c_bwd(const float* __restrict__ qs, const float* __restrict__ K,
                                                     const float* __restrict__ V, int Lq, int Lk, const float* __restrict__ O,
                                                     const float* __restrict__ stats, const float* __restrict__ dO,
-                                                    float* __restrict__ dQ, float* __restrict__ dkp, float* __restrict__ dvp) {
+                                                    float* __restrict__ dQ, float* __restrict__ dkp, float* __restrict__ dvp,
+                                                    DP... dps) {
+  const DropParams dp = fl_drop_arg(dps...);
   const int lane = threadIdx.x & 63, h = threadIdx.x >> 6;
   const int g = lane >> 4, j = lane & 15;
   const int nkt = (Lk + 15) / 16;
@@ -503,12 +548,19 @@ __global__ void __launch_bounds__(512) k_fl_s2c_bwd(const float* __restrict__ qs
           dp_pk = FL_MFMA(dof[gi][t], vr[t], dp_pk);
         }
         f32x4 p_pk, ds_pk;
+        const unsigned zb = DROP ? fl_keep_tr(dp, (uint32_t)h * (uint32_t)Lq + (uint32_t)p0, (uint32_t)(kt * 16), g, j) : 0u;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const bool off = kt * 16 + j >= Lk || p0 + 4 * g + t >= Lq;
           const float p = off ? 0.f : fl_exp(s_pk[t] - mp[gi][t]) * rlp[gi][t];
-          p_pk[t] = p;
-          ds_pk[t] = p * (dp_pk[t] - Dp[gi][t]);
+          if constexpr (DROP) {
+            const float z = (zb >> t) & 1u ? dp.scale : 0.f;
+            p_pk[t] = p * z;
+            ds_pk[t] = p * (z * dp_pk[t] - Dp[gi][t]);
+          } else {
+            p_pk[t] = p;
+            ds_pk[t] = p * (dp_pk[t] - Dp[gi][t]);
+          }
         }
         const f32x4 ds_kp = fl_transpose(tr_l[h][gi], ds_pk, g, j);   // [key 4g+t][point j]
 #pragma unroll
@@ -574,14 +626,23 @@ static int fl_check(const char* what, const void* a, const void* b, const void* 
   return A3D_OK;
 }
 
-extern "C" int a3d_flash_c2s_forward(const float* q_scaled_dev, const float* k_dev, const float* v_dev,
-                                     const unsigned char* mask_dev, int64_t Lq, int64_t Lk, float* o_dev, float* stats_dev,
-                                     void* workspace_dev, size_t workspace_bytes, void* stream) {
-  int rc = fl_check("a3d_flash_c2s_forward", q_scaled_dev, k_dev, v_dev, Lq, Lk, workspace_dev, workspace_bytes,
-                    a3d_flash_c2s_workspace_bytes(Lq, Lk));
+// the same kernels' launch with (drop) or without the dropout arguments: the DROP = false build keeps the kernel of the code
+// without dropout, argument block included
+template <int QT, bool DROP>
+static void fl_launch_c2s_fwd(int G, hipStream_t st, const float* qs, const float* K, const float* V, const unsigned char* mask,
+                              int Lq, int Lk, float* part, int q0, const DropParams& dp) {
+  if constexpr (DROP) k_fl_c2s_fwd<QT, true><<<G, 512, 0, st>>>(qs, K, V, mask, Lq, Lk, part, q0, dp);
+  else k_fl_c2s_fwd<QT, false><<<G, 512, 0, st>>>(qs, K, V, mask, Lq, Lk, part, q0);
+}
+
+template <bool DROP>
+static int fl_c2s_forward(const char* what, const float* q_scaled_dev, const float* k_dev, const float* v_dev,
+                          const unsigned char* mask_dev, int64_t Lq, int64_t Lk, float* o_dev, float* stats_dev,
+                          void* workspace_dev, size_t workspace_bytes, const DropParams& dp, void* stream) {
+  int rc = fl_check(what, q_scaled_dev, k_dev, v_dev, Lq, Lk, workspace_dev, workspace_bytes, a3d_flash_c2s_workspace_bytes(Lq, Lk));
   if (rc) return rc;
   if (!o_dev || !stats_dev) {
-    set_error("a3d_flash_c2s_forward: null output");
+    set_error("%s: null output", what);
     return A3D_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -590,27 +651,27 @@ extern "C" int a3d_flash_c2s_forward(const float* q_scaled_dev, const float* k_d
   // the build that holds the call's query tiles (or 14 of them per launch)
   for (int q0 = 0; q0 < (int)Lq; q0 += 16 * 14) {
     const int tiles = (int)((Lq - q0 + 15) / 16);
-    if (tiles <= 2) k_fl_c2s_fwd<2><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0);
-    else if (tiles <= 4) k_fl_c2s_fwd<4><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0);
-    else if (tiles <= 6) k_fl_c2s_fwd<6><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0);
-    else if (tiles <= 8) k_fl_c2s_fwd<8><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0);
-    else if (tiles <= 10) k_fl_c2s_fwd<10><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0);
-    else k_fl_c2s_fwd<14><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0);
+    if (tiles <= 2) fl_launch_c2s_fwd<2, DROP>(G, st, q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0, dp);
+    else if (tiles <= 4) fl_launch_c2s_fwd<4, DROP>(G, st, q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0, dp);
+    else if (tiles <= 6) fl_launch_c2s_fwd<6, DROP>(G, st, q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0, dp);
+    else if (tiles <= 8) fl_launch_c2s_fwd<8, DROP>(G, st, q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0, dp);
+    else if (tiles <= 10) fl_launch_c2s_fwd<10, DROP>(G, st, q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0, dp);
+    else fl_launch_c2s_fwd<14, DROP>(G, st, q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, part, q0, dp);
   }
   k_fl_c2s_combine<<<(unsigned)(Lq * FH), 64, 0, st>>>(part, G, (int)Lq, o_dev, stats_dev);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
 
-extern "C" int a3d_flash_c2s_backward(const float* q_scaled_dev, const float* k_dev, const float* v_dev,
-                                      const unsigned char* mask_dev, int64_t Lq, int64_t Lk, const float* o_dev,
-                                      const float* stats_dev, const float* d_o_dev, float* dq_scaled_dev, float* dk_dev,
-                                      float* dv_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  int rc = fl_check("a3d_flash_c2s_backward", q_scaled_dev, k_dev, v_dev, Lq, Lk, workspace_dev, workspace_bytes,
-                    a3d_flash_c2s_workspace_bytes(Lq, Lk));
+template <bool DROP>
+static int fl_c2s_backward(const char* what, const float* q_scaled_dev, const float* k_dev, const float* v_dev,
+                           const unsigned char* mask_dev, int64_t Lq, int64_t Lk, const float* o_dev, const float* stats_dev,
+                           const float* d_o_dev, float* dq_scaled_dev, float* dk_dev, float* dv_dev, void* workspace_dev,
+                           size_t workspace_bytes, const DropParams& dp, void* stream) {
+  int rc = fl_check(what, q_scaled_dev, k_dev, v_dev, Lq, Lk, workspace_dev, workspace_bytes, a3d_flash_c2s_workspace_bytes(Lq, Lk));
   if (rc) return rc;
   if (!o_dev || !stats_dev || !d_o_dev || !dq_scaled_dev || !dk_dev || !dv_dev) {
-    set_error("a3d_flash_c2s_backward: null argument");
+    set_error("%s: null argument", what);
     return A3D_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -619,11 +680,61 @@ extern "C" int a3d_flash_c2s_backward(const float* q_scaled_dev, const float* k_
   float* Ds = (float*)((char*)workspace_dev + align256((size_t)G * FH * Lq * 18 * 4));
   float* tmp = (float*)((char*)Ds + align256((size_t)FH * Lq * 4));
   k_fl_rowdot<<<(unsigned)((Lq * FH + 255) / 256), 256, 0, st>>>(d_o_dev, o_dev, (int)Lq, Ds);
-  k_fl_c2s_bwd<<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, stats_dev, Ds, d_o_dev, dqp, dk_dev,
-                                  dv_dev);
+  if constexpr (DROP)
+    k_fl_c2s_bwd<true><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, stats_dev, Ds, d_o_dev, dqp, dk_dev,
+                                         dv_dev, dp);
+  else
+    k_fl_c2s_bwd<false><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, stats_dev, Ds, d_o_dev, dqp, dk_dev,
+                                    dv_dev);
   fl_reduce(dqp, G, (int)Lq, tmp, dq_scaled_dev, st);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
+}
+
+// the site's logical rows h * Lq + i must fit the RNG's 32-bit row word
+static int fl_drop(const char* what, const a3d_dropout& d, int64_t Lq, DropParams* dp) {
+  if (int rc = drop_params(d, what, dp)) return rc;
+  if ((int64_t)FH * Lq >= (int64_t(1) << 32)) {
+    set_error("%s: too many rows for the dropout counter", what);
+    return A3D_ERR_INVALID;
+  }
+  return A3D_OK;
+}
+
+extern "C" int a3d_flash_c2s_forward(const float* q_scaled_dev, const float* k_dev, const float* v_dev,
+                                     const unsigned char* mask_dev, int64_t Lq, int64_t Lk, float* o_dev, float* stats_dev,
+                                     void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return fl_c2s_forward<false>("a3d_flash_c2s_forward", q_scaled_dev, k_dev, v_dev, mask_dev, Lq, Lk, o_dev, stats_dev,
+                               workspace_dev, workspace_bytes, DropParams{}, stream);
+}
+
+extern "C" int a3d_flash_c2s_forward_dropout(const float* q_scaled_dev, const float* k_dev, const float* v_dev,
+                                             const unsigned char* mask_dev, int64_t Lq, int64_t Lk, float* o_dev,
+                                             float* stats_dev, void* workspace_dev, size_t workspace_bytes, a3d_dropout drop,
+                                             void* stream) {
+  DropParams dp;
+  if (int rc = fl_drop("a3d_flash_c2s_forward_dropout", drop, Lq, &dp)) return rc;
+  return fl_c2s_forward<true>("a3d_flash_c2s_forward_dropout", q_scaled_dev, k_dev, v_dev, mask_dev, Lq, Lk, o_dev, stats_dev,
+                              workspace_dev, workspace_bytes, dp, stream);
+}
+
+extern "C" int a3d_flash_c2s_backward(const float* q_scaled_dev, const float* k_dev, const float* v_dev,
+                                      const unsigned char* mask_dev, int64_t Lq, int64_t Lk, const float* o_dev,
+                                      const float* stats_dev, const float* d_o_dev, float* dq_scaled_dev, float* dk_dev,
+                                      float* dv_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return fl_c2s_backward<false>("a3d_flash_c2s_backward", q_scaled_dev, k_dev, v_dev, mask_dev, Lq, Lk, o_dev, stats_dev,
+                                d_o_dev, dq_scaled_dev, dk_dev, dv_dev, workspace_dev, workspace_bytes, DropParams{}, stream);
+}
+
+extern "C" int a3d_flash_c2s_backward_dropout(const float* q_scaled_dev, const float* k_dev, const float* v_dev,
+                                              const unsigned char* mask_dev, int64_t Lq, int64_t Lk, const float* o_dev,
+                                              const float* stats_dev, const float* d_o_dev, float* dq_scaled_dev, float* dk_dev,
+                                              float* dv_dev, void* workspace_dev, size_t workspace_bytes, a3d_dropout drop,
+                                              void* stream) {
+  DropParams dp;
+  if (int rc = fl_drop("a3d_flash_c2s_backward_dropout", drop, Lq, &dp)) return rc;
+  return fl_c2s_backward<true>("a3d_flash_c2s_backward_dropout", q_scaled_dev, k_dev, v_dev, mask_dev, Lq, Lk, o_dev, stats_dev,
+                               d_o_dev, dq_scaled_dev, dk_dev, dv_dev, workspace_dev, workspace_bytes, dp, stream);
 }
 
 // workspace of the backward: dK and dV slabs [G][8][Lk][16] each + the reduction's slices [16][Lk * 128]
@@ -632,28 +743,33 @@ extern "C" size_t a3d_flash_s2c_workspace_bytes(int64_t Lq, int64_t Lk) {
   return 2 * align256((size_t)fl_grid(Lq) * FH * Lk * FDH * 4) + align256((size_t)kFlSlices * Lk * FD * 4) + 256;
 }
 
-extern "C" int a3d_flash_s2c_forward(const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq, int64_t Lk,
-                                     float* o_dev, float* stats_dev, void* stream) {
-  int rc = fl_check("a3d_flash_s2c_forward", q_scaled_dev, k_dev, v_dev, Lq, Lk, nullptr, 0, 0);
+template <bool DROP>
+static int fl_s2c_forward(const char* what, const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq,
+                          int64_t Lk, float* o_dev, float* stats_dev, const DropParams& dp, void* stream) {
+  int rc = fl_check(what, q_scaled_dev, k_dev, v_dev, Lq, Lk, nullptr, 0, 0);
   if (rc) return rc;
   if (!o_dev || !stats_dev) {
-    set_error("a3d_flash_s2c_forward: null output");
+    set_error("%s: null output", what);
     return A3D_ERR_INVALID;
   }
   const int nchunk = (int)((Lq + kFlChunk - 1) / kFlChunk);
-  k_fl_s2c_fwd<<<nchunk, 512, 0, (hipStream_t)stream>>>(q_scaled_dev, k_dev, v_dev, (int)Lq, (int)Lk, o_dev, stats_dev);
+  if constexpr (DROP)
+    k_fl_s2c_fwd<true><<<nchunk, 512, 0, (hipStream_t)stream>>>(q_scaled_dev, k_dev, v_dev, (int)Lq, (int)Lk, o_dev, stats_dev, dp);
+  else
+    k_fl_s2c_fwd<false><<<nchunk, 512, 0, (hipStream_t)stream>>>(q_scaled_dev, k_dev, v_dev, (int)Lq, (int)Lk, o_dev, stats_dev);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
 
-extern "C" int a3d_flash_s2c_backward(const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq, int64_t Lk,
-                                      const float* o_dev, const float* stats_dev, const float* d_o_dev, float* dq_scaled_dev,
-                                      float* dk_dev, float* dv_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  int rc = fl_check("a3d_flash_s2c_backward", q_scaled_dev, k_dev, v_dev, Lq, Lk, workspace_dev, workspace_bytes,
-                    a3d_flash_s2c_workspace_bytes(Lq, Lk));
+template <bool DROP>
+static int fl_s2c_backward(const char* what, const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq,
+                           int64_t Lk, const float* o_dev, const float* stats_dev, const float* d_o_dev, float* dq_scaled_dev,
+                           float* dk_dev, float* dv_dev, void* workspace_dev, size_t workspace_bytes, const DropParams& dp,
+                           void* stream) {
+  int rc = fl_check(what, q_scaled_dev, k_dev, v_dev, Lq, Lk, workspace_dev, workspace_bytes, a3d_flash_s2c_workspace_bytes(Lq, Lk));
   if (rc) return rc;
   if (!o_dev || !stats_dev || !d_o_dev || !dq_scaled_dev || !dk_dev || !dv_dev) {
-    set_error("a3d_flash_s2c_backward: null argument");
+    set_error("%s: null argument", what);
     return A3D_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -662,10 +778,44 @@ extern "C" int a3d_flash_s2c_backward(const float* q_scaled_dev, const float* k_
   float* dkp = (float*)workspace_dev;
   float* dvp = (float*)((char*)workspace_dev + half);
   float* tmp = (float*)((char*)workspace_dev + 2 * half);
-  k_fl_s2c_bwd<<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, (int)Lq, (int)Lk, o_dev, stats_dev, d_o_dev, dq_scaled_dev, dkp,
-                                  dvp);
+  if constexpr (DROP)
+    k_fl_s2c_bwd<true><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, (int)Lq, (int)Lk, o_dev, stats_dev, d_o_dev, dq_scaled_dev,
+                                         dkp, dvp, dp);
+  else
+    k_fl_s2c_bwd<false><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, (int)Lq, (int)Lk, o_dev, stats_dev, d_o_dev, dq_scaled_dev, dkp,
+                                    dvp);
   fl_reduce(dkp, G, (int)Lk, tmp, dk_dev, st);
   fl_reduce(dvp, G, (int)Lk, tmp, dv_dev, st);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
+}
+
+extern "C" int a3d_flash_s2c_forward(const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq, int64_t Lk,
+                                     float* o_dev, float* stats_dev, void* stream) {
+  return fl_s2c_forward<false>("a3d_flash_s2c_forward", q_scaled_dev, k_dev, v_dev, Lq, Lk, o_dev, stats_dev, DropParams{},
+                               stream);
+}
+
+extern "C" int a3d_flash_s2c_forward_dropout(const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq,
+                                             int64_t Lk, float* o_dev, float* stats_dev, a3d_dropout drop, void* stream) {
+  DropParams dp;
+  if (int rc = fl_drop("a3d_flash_s2c_forward_dropout", drop, Lq, &dp)) return rc;
+  return fl_s2c_forward<true>("a3d_flash_s2c_forward_dropout", q_scaled_dev, k_dev, v_dev, Lq, Lk, o_dev, stats_dev, dp, stream);
+}
+
+extern "C" int a3d_flash_s2c_backward(const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq, int64_t Lk,
+                                      const float* o_dev, const float* stats_dev, const float* d_o_dev, float* dq_scaled_dev,
+                                      float* dk_dev, float* dv_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return fl_s2c_backward<false>("a3d_flash_s2c_backward", q_scaled_dev, k_dev, v_dev, Lq, Lk, o_dev, stats_dev, d_o_dev,
+                                dq_scaled_dev, dk_dev, dv_dev, workspace_dev, workspace_bytes, DropParams{}, stream);
+}
+
+extern "C" int a3d_flash_s2c_backward_dropout(const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq,
+                                              int64_t Lk, const float* o_dev, const float* stats_dev, const float* d_o_dev,
+                                              float* dq_scaled_dev, float* dk_dev, float* dv_dev, void* workspace_dev,
+                                              size_t workspace_bytes, a3d_dropout drop, void* stream) {
+  DropParams dp;
+  if (int rc = fl_drop("a3d_flash_s2c_backward_dropout", drop, Lq, &dp)) return rc;
+  return fl_s2c_backward<true>("a3d_flash_s2c_backward_dropout", q_scaled_dev, k_dev, v_dev, Lq, Lk, o_dev, stats_dev, d_o_dev,
+                               dq_scaled_dev, dk_dev, dv_dev, workspace_dev, workspace_bytes, dp, stream);
 }

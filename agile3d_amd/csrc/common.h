@@ -67,6 +67,48 @@ __device__ inline void grid_barrier_counter(unsigned* bar, unsigned target, int*
 // as this process sees it (a partitioned device exposes a fraction of the CUs), holds `grid` workgroups of `func` (radix.hip)
 bool barrier_grid_fits(const void* func, int block_threads, size_t dyn_lds_bytes, int grid);
 
+// ---- dropout of the training decoder: a counter-based RNG, so that no mask is ever stored --------------------------------
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), key = the 64-bit seed.  The keep decision of element (row,
+// col) of a dropout site is word (col & 3) of philox(ctr = {col >> 2, row, sample, site}, seed) >= thr, thr = floor(p 2^32):
+// one call decides four consecutive columns of one row.  `row` is the logical row h * rows + i of a [heads, rows, cols]
+// tensor (an attention's [8, Lq, Lk] probabilities, or a [rows, cols] activation with heads = 1) and site = 8 * decoder
+// pass + site index: the decision depends on nothing a kernel chooses (layout, tiling, launch split).
+struct DropParams {
+  uint32_t k0, k1;       // seed (low, high word)
+  uint32_t thr;          // keep iff word >= thr
+  uint32_t sample, site;
+  float scale;           // 1 / (1 - p) in fp32
+};
+__host__ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+#ifdef __HIP_DEVICE_COMPILE__
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), hi1 = __umulhi(0xCD9E8D57u, c[2]);
+#else
+    const uint32_t hi0 = (uint32_t)(((uint64_t)0xD2511F53u * c[0]) >> 32), hi1 = (uint32_t)(((uint64_t)0xCD9E8D57u * c[2]) >> 32);
+#endif
+    const uint32_t lo0 = 0xD2511F53u * c[0], lo1 = 0xCD9E8D57u * c[2];
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = lo1;
+    c[2] = n2;
+    c[3] = lo0;
+  }
+}
+// keep bits of columns col4 .. col4 + 3 (col4 % 4 == 0) of logical row `row`: bit t = column col4 + t
+__host__ __device__ __forceinline__ unsigned drop_keep4(const DropParams& dp, uint32_t row, uint32_t col4) {
+  uint32_t c[4] = {col4 >> 2, row, dp.sample, dp.site};
+  philox4x32_10(c, dp.k0, dp.k1);
+  return (unsigned)(c[0] >= dp.thr) | (unsigned)(c[1] >= dp.thr) << 1 | (unsigned)(c[2] >= dp.thr) << 2 |
+         (unsigned)(c[3] >= dp.thr) << 3;
+}
+// a3d_dropout -> DropParams; A3D_ERR_INVALID unless 0 <= p < 1 and 0 <= site_code, sample
+int drop_params(const a3d_dropout& d, const char* what, DropParams* out);
+
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 static inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 

@@ -539,7 +539,7 @@ class Engine:
         """``forward_mask`` of a model in training mode (engine.py:120-122): one DecoderTape per batch sample
         (agile3d.py:192 loops over the samples), logits tied into torch.autograd."""
         from .autograd import DecoderFn, _Holder
-        from .train_decoder import DecoderTape
+        from .train_decoder import DecoderTape, draw_seed
         st = getattr(pcd_features, "_a3d", None)
         if st is None or st.engine_id != id(self):
             raise RuntimeError("forward_mask needs the objects returned by this model's forward_backbone")
@@ -550,10 +550,14 @@ class Engine:
         names, params = [k for k, _ in named], [p for _, p in named]
         n_layers = self.model.num_decoders
         preds = [[] for _ in range(n_layers)]
+        # dropout: one seed per call, sample b's masks keyed by b -- the masks a batched tape of the same seed draws
+        p = getattr(self.model, "dropout", 0.0)
+        seed = draw_seed() if p > 0 else None
         for b, (s, e) in enumerate(st.ranges):
             rows = pcd_features.F[s:e]
             with torch.no_grad():
-                tape = DecoderTape(self.model, rows.detach(), st.posenc[b], click_idx[b], click_time_idx[b])
+                tape = DecoderTape(self.model, rows.detach(), st.posenc[b], click_idx[b], click_time_idx[b], dropout=p, seed=seed,
+                                   sample_base=b)
             if torch.is_grad_enabled():
                 logits = DecoderFn.apply(_Holder(tape=tape, names=names), rows, *params)
             else:

@@ -77,6 +77,12 @@ class DecoderSample(C.Structure):
                 ("kv0_dev", C.c_void_p), ("kv0_state", C.c_int32), ("kv0_blocks", C.c_int32)]
 
 
+class Dropout(C.Structure):
+    """a3d_dropout: the dropout of one site of one batch sample (passed by value)."""
+    _fields_ = [("seed", C.c_uint64), ("p", C.c_float), ("sample", C.c_int32), ("site_code", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
 class ClickSample(C.Structure):
     """a3d_click_sample: one sample of a3d_click_clusters_batch."""
     _fields_ = [("xyz_dev", C.c_void_p), ("pred_dev", C.c_void_p), ("labels_dev", C.c_void_p), ("n", C.c_int64),
@@ -211,6 +217,22 @@ SYMBOLS = {
                                         C.c_void_p]),
     "a3d_flash_s2c_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_dropout_mask": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+                                   C.c_void_p]),
+    "a3d_flash_c2s_forward_dropout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, Dropout, C.c_void_p]),
+    "a3d_flash_c2s_backward_dropout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_size_t, Dropout, C.c_void_p]),
+    "a3d_flash_s2c_forward_dropout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                                C.c_void_p, Dropout, C.c_void_p]),
+    "a3d_flash_s2c_backward_dropout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_size_t, Dropout, C.c_void_p]),
+    "a3d_attn_dropout": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, Dropout, C.c_void_p]),
+    "a3d_dropout_rows_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, Dropout,
+                                           C.c_void_p]),
+    "a3d_dropout_rows_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, Dropout, C.c_void_p]),
     "a3d_sum_squares_workspace_bytes": (C.c_size_t, []),
     "a3d_sum_squares": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_sum_squares_accumulate": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

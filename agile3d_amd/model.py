@@ -9,6 +9,8 @@ Same argument meaning, same return structures, same ``state_dict`` keys.  All ar
 runs in ``libagile3d_hip.so`` (hand-written gfx950 kernels); there is NO CPU fallback --
 calling a forward without the HIP library or on a non-GPU tensor raises.  Both modes of the ``nn.Module`` are
 served: ``eval()`` by the fused inference kernels, ``train()`` by the training path tied into torch.autograd.
+``args.dropout`` (0 <= p < 1) is the decoder's dropout of the training-mode ``forward_mask``; refused:
+``pre_norm=True``, non-Fourier position encodings, ``hlevels != [4]``, ``hidden_dim`` / ``num_heads`` other than 128 / 8.
 """
 from __future__ import annotations
 
@@ -78,11 +80,14 @@ class Agile3d(nn.Module):
             raise NotImplementedError("only the default 'fourier' position encoding is on the hot path")
         if list(args.hlevels) != [4]:
             raise NotImplementedError("only hlevels=[4] (reference default) is on the hot path")
-        if args.dropout != 0.0:
-            raise NotImplementedError("dropout != 0 is outside the hot path (reference default 0.0)")
+        if not 0.0 <= float(args.dropout) < 1.0:
+            raise ValueError(f"dropout must lie in [0, 1), got {args.dropout}")
         if args.hidden_dim != 128 or args.num_heads != 8:
             raise NotImplementedError("kernels are specialised for hidden_dim=128, num_heads=8")
         self.args = args
+        # decoder dropout (attention_block.py): drawn in the training-mode forward_mask only (train_decoder.DecoderTape,
+        # DESIGN.md §4.7); evaluation and the click rounds of a training step run without it, like nn.Dropout in eval()
+        self.dropout = float(args.dropout)
         d, h, ff = args.hidden_dim, args.num_heads, args.dim_feedforward
         self.mask_dim = d
         self.num_heads = h

@@ -10,8 +10,9 @@ activations, so this path is the plain composition of attention_block.py -- nn.L
 kernels), their gradients = ``a3d_linear`` with the transposed weight + ``a3d_linear_wgrad``, LayerNorm, and the
 attention / mask-head primitives of csrc/attn_train.hip with the score matrices materialised.  This module is the
 reverse-mode bookkeeping (which tensor feeds which op; fan-outs are tensor adds, ReLU a mask multiply).  A parity
-executor: every FLOP of consequence is in libagile3d_hip, nothing is tuned yet.  Dropout is 0 in the reference's
-configuration (main.py: --dropout 0.0), so training and evaluation forward agree.
+executor: every FLOP of consequence is in libagile3d_hip, nothing is tuned yet.  Dropout (``dropout=p > 0``, main.py
+--dropout) is applied at the eight sites of every decoder pass with masks regenerated in the kernels from a
+counter-based RNG: one 64-bit seed per tape, the sample index and the site decide every mask, nothing mask-shaped is kept.
 """
 from __future__ import annotations
 
@@ -121,6 +122,15 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# dropout sites of one decoder pass: site code = 8 * pass + site
+SITE_C2S_ATTN, SITE_C2S_OUT, SITE_C2C_ATTN, SITE_C2C_OUT, SITE_FFN_HIDDEN, SITE_FFN_OUT, SITE_S2C_ATTN, SITE_S2C_OUT = range(8)
+
+
+def draw_seed():
+    """One 64-bit dropout seed from torch's default CPU generator (``torch.manual_seed`` makes a run repeatable)."""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) * 2 + int(torch.randint(0, 2, (1,)).item())
+
+
 def _pack(w_in_out):
     cin, cout = w_in_out.shape
     return B.pack_weight(w_in_out.reshape(1, cin, cout)), cin, cout
@@ -223,8 +233,18 @@ class DecoderTape:
     of all samples -- points [N_total, 128] and queries [Q_total, 128] --, attention and the mask head per sample on row
     ranges: a third of the launches and of the host-side bookkeeping of one tape per sample."""
 
-    def __init__(self, model, pcd_features, pos_enc, click_idx, click_time_idx):
+    def __init__(self, model, pcd_features, pos_enc, click_idx, click_time_idx, dropout=0.0, seed=None, sample_base=0):
+        """``dropout``: p of the decoder's dropout sites (0: none, the tape without dropout bit for bit); ``seed``: the 64-bit
+        key of the masks (None: one drawn from torch's default generator when p > 0); the batch samples are numbered
+        ``sample_base``, ``sample_base + 1``, ... in the masks -- a one-sample tape of sample b passes ``sample_base=b``, so
+        that it draws the masks of a batched tape's sample b."""
         self._single = torch.is_tensor(pcd_features)
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
+        self.p = float(dropout)
+        self.seed = (draw_seed() if seed is None else int(seed) & (2 ** 64 - 1)) if self.p > 0 else None
+        self.sample_base = int(sample_base)
+        self._pass = 0
         if self._single:
             pcd_features, pos_enc, click_idx, click_time_idx = [pcd_features], [pos_enc], [click_idx], [click_time_idx]
         if not pcd_features[0].is_cuda:
@@ -255,6 +275,32 @@ class DecoderTape:
         self._grad_written.add(key)
         return (g if rows is None else g[rows[0]:rows[1]]), first
 
+    def _drop(self, b, site):
+        """The a3d_dropout of site ``site`` of the current decoder pass for the tape's sample ``b``."""
+        return L.Dropout(self.seed, self.p, self.sample_base + b, 8 * self._pass + site, 0)
+
+    def _rows_drop(self, x, res, ranges, site, relu=False):
+        """y = res + Z o f(x) per sample on its row range (f = relu or the identity; res may be None)."""
+        lib = L.load()
+        y = torch.empty_like(x)
+        cols = x.shape[1]
+        for b, (r0, r1) in enumerate(ranges):
+            if r1 > r0:
+                L.check(lib.a3d_dropout_rows_forward(_ptr(x[r0:r1]), _ptr(res[r0:r1] if res is not None else None), _ptr(y[r0:r1]),
+                                                     r1 - r0, cols, int(relu), self._drop(b, site), _stream()), "dropout_rows_forward")
+        return y
+
+    def _rows_drop_bwd(self, dy, x_pre, ranges, drops):
+        """dx = Z o dy (o [x_pre > 0]) per sample, with the forward's a3d_dropout structs ``drops``."""
+        lib = L.load()
+        dx = torch.empty_like(dy)
+        cols = dy.shape[1]
+        for (r0, r1), d in zip(ranges, drops):
+            if r1 > r0:
+                L.check(lib.a3d_dropout_rows_backward(_ptr(dy[r0:r1]), _ptr(x_pre[r0:r1] if x_pre is not None else None),
+                                                      _ptr(dx[r0:r1]), r1 - r0, cols, d, _stream()), "dropout_rows_backward")
+        return dx
+
     def add(self, a: _T, b: _T) -> _T:
         if a.needs_grad and not b.needs_grad:
             return _Alias(a.v + b.v, a)
@@ -270,10 +316,12 @@ class DecoderTape:
         self.steps.append(back)
         return y
 
-    def lin(self, x: _T, wname, bname=None, rows=None, res: _T = None) -> _T:
+    def lin(self, x: _T, wname, bname=None, rows=None, res: _T = None, drop=None) -> _T:
         """nn.Linear with weight [out, in] (optionally the row slice ``rows`` of an in_proj matrix).  ``res``: a residual added in
         the GEMM's epilogue -- y = res + x W^T + b as ONE node (the ``tgt + dropout(attn)`` / ``src + ...`` of
-        attention_block.py:96,153,207 without a separate [N, 128] add); its gradient is y's, like an add's."""
+        attention_block.py:96,153,207 without a separate [N, 128] add); its gradient is y's, like an add's.  ``drop`` =
+        (site, row ranges of the samples) with dropout on: y = res + dropout(x W^T + b), the product's mask applied in one
+        pass that also adds the residual, and to dy before the input- and weight-gradient GEMMs."""
         W = self.P[wname].detach()
         b = self.P[bname].detach() if bname else None
         if rows is not None:
@@ -286,12 +334,20 @@ class DecoderTape:
             object.__setattr__(self.model, "_a3d_packed_dec", packs)
         fwd_w, bwd_w = packs.get(self.P[wname], wname, rows)
         bc = b                 # a contiguous slice of the 1-D parameter: always current, nothing to cache
-        y = _T(_linear(x.v, fwd_w, bc, res=res.v.contiguous() if res is not None else None))
+        drops = None
+        if drop is not None and self.p > 0:
+            site, ranges = drop
+            drops = [self._drop(b_, site) for b_ in range(len(ranges))]
+            y = _T(self._rows_drop(_linear(x.v, fwd_w, bc), res.v.contiguous() if res is not None else None, ranges, site))
+        else:
+            y = _T(_linear(x.v, fwd_w, bc, res=res.v.contiguous() if res is not None else None))
 
         def back():
             if y.g is None:
                 return
             dy = y.g.contiguous()
+            if drops is not None:
+                dy = self._rows_drop_bwd(dy, None, drop[1], drops)            # Z o dy: what reaches the product
             if x.needs_grad and x.g is not None and x.own and x.g.is_contiguous():
                 _linear(dy, bwd_w, acc=x.g)                              # x.g += dy @ W in the GEMM's epilogue (no [N, 128] add)
             elif x.needs_grad:
@@ -309,9 +365,19 @@ class DecoderTape:
         self.steps.append(back)
         return y
 
-    def relu(self, x: _T) -> _T:
+    def relu(self, x: _T, drop=None) -> _T:
         mask = x.v > 0
         self.relu_masks.append(mask)
+        if drop is not None and self.p > 0:        # dropout(relu(x)) in one pass each way; relu_masks stays the ReLU's alone
+            site, ranges = drop
+            drops = [self._drop(b_, site) for b_ in range(len(ranges))]
+            y = _T(self._rows_drop(x.v, None, ranges, site, relu=True))
+
+            def back_drop():
+                if y.g is not None:
+                    x.add_grad(self._rows_drop_bwd(y.g.contiguous(), x.v, ranges, drops), fresh=True)
+            self.steps.append(back_drop)
+            return y
         y = _T(x.v * mask)
 
         def back():
@@ -341,7 +407,7 @@ class DecoderTape:
     #   "dense"      scores materialised (csrc/attn_train.hip): the click-to-click self attention, and everything when
     #                FLASH is False (the path the flash kernels are checked against)
     @staticmethod
-    def _dense_fwd(qv, kv, vv, mask, o):
+    def _dense_fwd(qv, kv, vv, mask, o, drop=None):
         lib = L.load()
         Lq, Lk = qv.shape[0], kv.shape[0]
         dev = qv.device
@@ -351,36 +417,47 @@ class DecoderTape:
             Pm = torch.empty((H, Lk, Lq), dtype=torch.float32, device=dev)                      # P^T[h][key][query]
             L.check(lib.a3d_attn_scores(_ptr(kv), _ptr(qv), Lk, Lq, H, DH, scale, None, _ptr(Pm), _stream()), "scores")
             L.check(lib.a3d_softmax_cols(_ptr(Pm), H, Lk, Lq, _stream()), "softmax_cols")         # over the keys
-            _apply(Pm, vv, Lk, Lq, H, DH, 1, 1.0, o)
         else:
             Pm = torch.empty((H, Lq, Lk), dtype=torch.float32, device=dev)
             L.check(lib.a3d_attn_scores(_ptr(qv), _ptr(kv), Lq, Lk, H, DH, scale, _ptr(mask), _ptr(Pm), _stream()), "scores")
             L.check(lib.a3d_softmax_rows(_ptr(Pm), H * Lq, Lk, _stream()), "softmax")
-            _apply(Pm, vv, Lq, Lk, H, DH, 0, 1.0, o)
-        return Pm, transposed
+        Pd = Pm
+        if drop is not None:            # the dropped probabilities multiply V; the softmax backward needs the undropped ones
+            Pd = torch.empty_like(Pm)
+            L.check(lib.a3d_attn_dropout(_ptr(Pm), H, Lq, Lk, int(transposed), _ptr(Pd), drop, _stream()), "attn_dropout")
+        if transposed:
+            _apply(Pd, vv, Lk, Lq, H, DH, 1, 1.0, o)
+        else:
+            _apply(Pd, vv, Lq, Lk, H, DH, 0, 1.0, o)
+        return (Pm, transposed) if drop is None else (Pm, transposed, Pd)
 
     @staticmethod
-    def _dense_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv):
+    def _dense_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv, drop=None):
         lib = L.load()
-        Pm, transposed = saved
+        Pm, transposed = saved[:2]
+        Pd = saved[2] if drop is not None else Pm
         Lq, Lk = qv.shape[0], kv.shape[0]
         scale = 1.0 / (DH ** 0.5)
         dP = torch.empty_like(Pm)
         if transposed:
             L.check(lib.a3d_attn_scores(_ptr(vv), _ptr(do), Lk, Lq, H, DH, 1.0, None, _ptr(dP), _stream()), "scores")
-            _apply(Pm, do, Lk, Lq, H, DH, 0, 1.0, dv)                                        # dv[key] = sum_query P^T dO
+            _apply(Pd, do, Lk, Lq, H, DH, 0, 1.0, dv)                                        # dv[key] = sum_query P^T dO
+            if drop is not None:
+                L.check(lib.a3d_attn_dropout(_ptr(dP), H, Lq, Lk, 1, _ptr(dP), drop, _stream()), "attn_dropout")   # Z o dP
             L.check(lib.a3d_softmax_cols_backward(_ptr(Pm), _ptr(dP), H, Lk, Lq, _stream()), "softmax_cols_bwd")
             _apply(dP, kv, Lk, Lq, H, DH, 1, scale, dq)                                      # dq[query] = sum_key dS^T k
             _apply(dP, qv, Lk, Lq, H, DH, 0, scale, dk)                                      # dk[key] = sum_query dS^T q
         else:
             L.check(lib.a3d_attn_scores(_ptr(do), _ptr(vv), Lq, Lk, H, DH, 1.0, None, _ptr(dP), _stream()), "scores")
-            _apply(Pm, do, Lq, Lk, H, DH, 1, 1.0, dv)
+            _apply(Pd, do, Lq, Lk, H, DH, 1, 1.0, dv)
+            if drop is not None:
+                L.check(lib.a3d_attn_dropout(_ptr(dP), H, Lq, Lk, 0, _ptr(dP), drop, _stream()), "attn_dropout")   # Z o dP
             L.check(lib.a3d_softmax_rows_backward(_ptr(Pm), _ptr(dP), H * Lq, Lk, _stream()), "softmax_bwd")   # dP <- dS
             _apply(dP, kv, Lq, Lk, H, DH, 0, scale, dq)
             _apply(dP, qv, Lq, Lk, H, DH, 1, scale, dk)
 
     @staticmethod
-    def _c2s_fwd(qv, kv, vv, mask, o):
+    def _c2s_fwd(qv, kv, vv, mask, o, drop=None):
         lib = L.load()
         Lq, Lk = qv.shape[0], kv.shape[0]
         dev = qv.device
@@ -388,48 +465,67 @@ class DecoderTape:
         nbytes = lib.a3d_flash_c2s_workspace_bytes(Lq, Lk)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         stats = torch.empty((2, H, Lq), dtype=torch.float32, device=dev)
-        L.check(lib.a3d_flash_c2s_forward(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws),
-                                          nbytes, _stream()), "flash_c2s_forward")
+        if drop is None:
+            L.check(lib.a3d_flash_c2s_forward(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws),
+                                              nbytes, _stream()), "flash_c2s_forward")
+        else:
+            L.check(lib.a3d_flash_c2s_forward_dropout(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats),
+                                                      _ptr(ws), nbytes, drop, _stream()), "flash_c2s_forward_dropout")
         return qs, stats
 
     @staticmethod
-    def _c2s_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv):
+    def _c2s_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv, drop=None):
         lib = L.load()
         qs, stats = saved
         Lq, Lk = qv.shape[0], kv.shape[0]
         nbytes = lib.a3d_flash_c2s_workspace_bytes(Lq, Lk)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=qv.device)
-        L.check(lib.a3d_flash_c2s_backward(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats), _ptr(do),
-                                           _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _stream()), "flash_c2s_backward")
+        if drop is None:
+            L.check(lib.a3d_flash_c2s_backward(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats), _ptr(do),
+                                               _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _stream()), "flash_c2s_backward")
+        else:
+            L.check(lib.a3d_flash_c2s_backward_dropout(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats),
+                                                       _ptr(do), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, drop, _stream()),
+                    "flash_c2s_backward_dropout")
         dq *= 0.25
 
     @staticmethod
-    def _s2c_fwd(qv, kv, vv, mask, o):
+    def _s2c_fwd(qv, kv, vv, mask, o, drop=None):
         # the 1 / sqrt(16) goes on the FEW keys, not on the N queries: q . (k / 4) has the bits of (q / 4) . k (a power of two),
         # and the kernel's dq = dS (k / 4) is then already the gradient of the unscaled queries
         lib = L.load()
         Lq, Lk = qv.shape[0], kv.shape[0]
         ks = kv * 0.25
         stats = torch.empty((Lq, H, 2), dtype=torch.float32, device=qv.device)
-        L.check(lib.a3d_flash_s2c_forward(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), _stream()),
-                "flash_s2c_forward")
+        if drop is None:
+            L.check(lib.a3d_flash_s2c_forward(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), _stream()),
+                    "flash_s2c_forward")
+        else:
+            L.check(lib.a3d_flash_s2c_forward_dropout(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), drop, _stream()),
+                    "flash_s2c_forward_dropout")
         return ks, stats
 
     @staticmethod
-    def _s2c_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv):
+    def _s2c_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv, drop=None):
         lib = L.load()
         ks, stats = saved
         Lq, Lk = qv.shape[0], kv.shape[0]
         nbytes = lib.a3d_flash_s2c_workspace_bytes(Lq, Lk)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=qv.device)
-        L.check(lib.a3d_flash_s2c_backward(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), _ptr(do), _ptr(dq),
-                                           _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _stream()), "flash_s2c_backward")
+        if drop is None:
+            L.check(lib.a3d_flash_s2c_backward(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), _ptr(do), _ptr(dq),
+                                               _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _stream()), "flash_s2c_backward")
+        else:
+            L.check(lib.a3d_flash_s2c_backward_dropout(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), _ptr(do),
+                                                       _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, drop, _stream()),
+                    "flash_s2c_backward_dropout")
         dk *= 0.25
 
-    def attention_seg(self, q: _T, k: _T, v: _T, q_ranges, k_ranges, masks=None) -> _T:
+    def attention_seg(self, q: _T, k: _T, v: _T, q_ranges, k_ranges, masks=None, site=None) -> _T:
         """Attention of every batch sample on ITS rows: sample b's queries are rows q_ranges[b] of ``q``, its keys / values
         rows k_ranges[b] of ``k`` / ``v`` (contiguous row ranges of the batched tensors: views, no copies); masks[b] uint8
-        [Lq_b, Lk_b] (1 = blocked) or None.  One tape step for the whole batch."""
+        [Lq_b, Lk_b] (1 = blocked) or None; ``site``: the dropout site of the probabilities (with dropout on).  One tape step
+        for the whole batch."""
         qv, kv, vv = q.v.contiguous(), k.v.contiguous(), v.v.contiguous()
         out = torch.empty((qv.shape[0], H * DH), dtype=torch.float32, device=qv.device)
         saved = []
@@ -444,8 +540,9 @@ class DecoderTape:
                 kind = "dense"
             fwd = {"s2c": self._s2c_fwd, "c2s": self._c2s_fwd, "dense": self._dense_fwd}[kind]
             o = out[q0:q1]                                  # the sample's rows of the batched result: written in place
-            sv = fwd(qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o)
-            saved.append((kind, o, sv, mask))
+            drop = self._drop(b, site) if site is not None and self.p > 0 else None
+            sv = fwd(qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o) if drop is None else fwd(qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o, drop)
+            saved.append((kind, o, sv, mask, drop))
         y = _T(out)
 
         def back():
@@ -453,24 +550,28 @@ class DecoderTape:
                 return
             do = y.g.contiguous()
             dq, dk, dv = torch.empty_like(qv), torch.empty_like(kv), torch.empty_like(vv)
-            for ((q0, q1), (k0, k1)), (kind, o, sv, mask) in zip(zip(q_ranges, k_ranges), saved):
+            for ((q0, q1), (k0, k1)), (kind, o, sv, mask, drop) in zip(zip(q_ranges, k_ranges), saved):
                 bwd = {"s2c": self._s2c_bwd, "c2s": self._c2s_bwd, "dense": self._dense_bwd}[kind]
-                bwd(qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o, sv, do[q0:q1], dq[q0:q1], dk[k0:k1], dv[k0:k1])
+                args = (qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o, sv, do[q0:q1], dq[q0:q1], dk[k0:k1], dv[k0:k1])
+                bwd(*args) if drop is None else bwd(*args, drop)
             q.add_grad(dq, fresh=True)
             k.add_grad(dk, fresh=True)
             v.add_grad(dv, fresh=True)
         self.steps.append(back)
         return y
 
-    def mha(self, prefix, query: _T, key: _T, value: _T, q_ranges, k_ranges, masks=None, res: _T = None) -> _T:
+    def mha(self, prefix, query: _T, key: _T, value: _T, q_ranges, k_ranges, masks=None, res: _T = None, sites=None) -> _T:
         """nn.MultiheadAttention (attention_block.py:25-26,88-94): in_proj slices (one GEMM each over the rows of the whole
-        batch), attention per sample, out_proj (+ ``res``: the layer's residual, added in out_proj's epilogue)."""
+        batch), attention per sample, out_proj (+ ``res``: the layer's residual, added in out_proj's epilogue).  ``sites``:
+        the dropout sites (probabilities, out_proj output) of this attention."""
         w, b = prefix + "in_proj_weight", prefix + "in_proj_bias"
         q = self.lin(query, w, b, rows=(0, 128))
         k = self.lin(key, w, b, rows=(128, 256))
         v = self.lin(value, w, b, rows=(256, 384))
-        a = self.attention_seg(q, k, v, q_ranges, k_ranges, masks)
-        return self.lin(a, prefix + "out_proj.weight", prefix + "out_proj.bias", res=res)
+        s_attn, s_out = sites if sites is not None else (None, None)
+        a = self.attention_seg(q, k, v, q_ranges, k_ranges, masks, site=s_attn)
+        return self.lin(a, prefix + "out_proj.weight", prefix + "out_proj.bias", res=res,
+                        drop=(s_out, q_ranges) if s_out is not None else None)
 
     def mask_head(self, queries: _T, src: _T, n_ranges, q_ranges, groups):
         """Agile3d.mask_module (agile3d.py:342-384): per-object max over its queries of src . MLP(LN(q)); the MLP runs over
@@ -592,17 +693,22 @@ class DecoderTape:
         self.logits_nodes = []                     # [layer][sample]
         for d in range(self.model.num_decoders):
             li = 0 if self.model.shared_decoder else d
+            self._pass = d                      # the pass's dropout sites: 8 d + site (a shared decoder draws anew per pass)
             src_pos = self.add(src, pos)        # the keys of click-to-scene AND the queries of scene-to-click (src changes after both)
             # every residual (x + sublayer(x), attention_block.py:96,153,207) rides in the sublayer's last GEMM
-            a = self.mha(f"c2s_attention.{li}.0.multihead_attn.", self.add(tgt, qpos), src_pos, src, q_ranges, n_ranges, masks, res=tgt)
+            a = self.mha(f"c2s_attention.{li}.0.multihead_attn.", self.add(tgt, qpos), src_pos, src, q_ranges, n_ranges, masks, res=tgt,
+                         sites=(SITE_C2S_ATTN, SITE_C2S_OUT))
             tgt = self.ln(a, f"c2s_attention.{li}.0.norm.")
             qk = self.add(tgt, qpos)
-            a = self.mha(f"c2c_attention.{li}.0.self_attn.", qk, qk, tgt, q_ranges, q_ranges, res=tgt)
+            a = self.mha(f"c2c_attention.{li}.0.self_attn.", qk, qk, tgt, q_ranges, q_ranges, res=tgt, sites=(SITE_C2C_ATTN, SITE_C2C_OUT))
             tgt = self.ln(a, f"c2c_attention.{li}.0.norm.")
-            h = self.relu(self.lin(tgt, f"ffn_attention.{li}.0.linear1.weight", f"ffn_attention.{li}.0.linear1.bias"))
-            f = self.lin(h, f"ffn_attention.{li}.0.linear2.weight", f"ffn_attention.{li}.0.linear2.bias", res=tgt)
+            h = self.relu(self.lin(tgt, f"ffn_attention.{li}.0.linear1.weight", f"ffn_attention.{li}.0.linear1.bias"),
+                          drop=(SITE_FFN_HIDDEN, q_ranges))
+            f = self.lin(h, f"ffn_attention.{li}.0.linear2.weight", f"ffn_attention.{li}.0.linear2.bias", res=tgt,
+                         drop=(SITE_FFN_OUT, q_ranges))
             tgt = self.ln(f, f"ffn_attention.{li}.0.norm.")
-            a = self.mha(f"s2c_attention.{li}.0.multihead_attn.", src_pos, self.add(tgt, qpos), tgt, n_ranges, q_ranges, res=src)
+            a = self.mha(f"s2c_attention.{li}.0.multihead_attn.", src_pos, self.add(tgt, qpos), tgt, n_ranges, q_ranges, res=src,
+                         sites=(SITE_S2C_ATTN, SITE_S2C_OUT))
             src = self.ln(a, f"s2c_attention.{li}.0.norm.")
             outs = self.mask_head(tgt, src, n_ranges, q_ranges, groups)
             self.logits_nodes.append(outs)

@@ -143,7 +143,7 @@ def _train_one_step(model, criterion, optimizer, batch, device, max_norm):
     # ---- decoder, training mode: ONE tape for the batch (agile3d.py:192 loops over the samples, which only share the
     # weights: row-wise layers run once over all samples' rows, attention and the mask head per sample on row ranges)
     tape = DecoderTape(model, [pcd[s:e] for (s, e) in ranges], [pos_enc[i] for i in range(len(ranges))], click_idx,
-                       click_time_idx)
+                       click_time_idx, dropout=getattr(model, "dropout", 0.0))     # p > 0: one seed drawn for the batch
     n_layers = len(tape.logits)
     outputs = {"pred_masks": list(tape.logits[-1]),
                "aux_outputs": [{"pred_masks": list(tape.logits[l])} for l in range(n_layers - 1)]}

@@ -401,6 +401,51 @@ int a3d_flash_s2c_backward(const float* q_scaled_dev, const float* k_dev, const 
                            const float* o_dev, const float* stats_dev, const float* d_o_dev, float* dq_scaled_dev,
                            float* dk_dev, float* dv_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Dropout of the training decoder (nn.Dropout / nn.MultiheadAttention(dropout=p) of attention_block.py in training mode):
+ * every mask is regenerated where it is used from a counter-based RNG (Philox4x32-10, key = seed), nothing of the shape
+ * of an attention is stored.  Element (h, i, j) of site `site_code` (= 8 * decoder pass + site) of batch
+ * sample `sample` is kept iff word (j & 3) of philox({j >> 2, h * rows + i, sample, site_code}, seed) >= floor(p 2^32);
+ * a kept value is scaled by 1 / (1 - p) (fp32).  0 <= p < 1. */
+typedef struct a3d_dropout {
+  uint64_t seed;
+  float p;
+  int32_t sample;
+  int32_t site_code;
+  int32_t reserved_;
+} a3d_dropout;
+/* the keep mask itself, uint8 [heads][rows][cols] (1 = kept): for tests; the hot path never writes a mask */
+int a3d_dropout_mask(uint64_t seed, int sample, int site_code, float p, int heads, int64_t rows, int64_t cols,
+                     unsigned char* out_dev, void* stream);
+/* the flash attentions with dropout on the probabilities that multiply V (the softmax statistics stay those of the
+ * undropped scores; the backward regenerates the mask: dS = P (Z dP - D), dV = (P Z)^T dO, D = rowsum(dO o O) of the
+ * dropped output); rows of the site = the attention's queries, columns = its keys.  Workspaces as without dropout. */
+int a3d_flash_c2s_forward_dropout(const float* q_scaled_dev, const float* k_dev, const float* v_dev,
+                                  const unsigned char* mask_dev, int64_t Lq, int64_t Lk, float* o_dev, float* stats_dev,
+                                  void* workspace_dev, size_t workspace_bytes, a3d_dropout drop, void* stream);
+int a3d_flash_c2s_backward_dropout(const float* q_scaled_dev, const float* k_dev, const float* v_dev,
+                                   const unsigned char* mask_dev, int64_t Lq, int64_t Lk, const float* o_dev,
+                                   const float* stats_dev, const float* d_o_dev, float* dq_scaled_dev, float* dk_dev,
+                                   float* dv_dev, void* workspace_dev, size_t workspace_bytes, a3d_dropout drop,
+                                   void* stream);
+int a3d_flash_s2c_forward_dropout(const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq,
+                                  int64_t Lk, float* o_dev, float* stats_dev, a3d_dropout drop, void* stream);
+int a3d_flash_s2c_backward_dropout(const float* q_scaled_dev, const float* k_dev, const float* v_dev, int64_t Lq,
+                                   int64_t Lk, const float* o_dev, const float* stats_dev, const float* d_o_dev,
+                                   float* dq_scaled_dev, float* dk_dev, float* dv_dev, void* workspace_dev,
+                                   size_t workspace_bytes, a3d_dropout drop, void* stream);
+/* the materialised path (a3d_attn_scores / softmax / apply): out = Z o P for P [H][Lq][Lk] (transposed = 0) or stored as
+ * [H][Lk][Lq] (transposed = 1; the site's rows are still the Lq queries), in place allowed.  Forward: applied to the
+ * softmax output before a3d_attn_apply; backward: to dP before the softmax backward (dV from the dropped P). */
+int a3d_attn_dropout(const float* P_dev, int H, int64_t Lq, int64_t Lk, int transposed, float* out_dev, a3d_dropout drop,
+                     void* stream);
+/* row-wise sites on [rows][cols] (heads = 1), one batch sample's rows:
+ *   forward:  y = res + Z o f(x), f = relu (relu != 0) or the identity; res_dev may be NULL (then y = Z o f(x))
+ *   backward: dx = Z o dy o (x_pre > 0 if x_pre_dev != NULL) */
+int a3d_dropout_rows_forward(const float* x_dev, const float* res_dev, float* y_dev, int64_t rows, int cols, int relu,
+                             a3d_dropout drop, void* stream);
+int a3d_dropout_rows_backward(const float* dy_dev, const float* x_pre_dev, float* dx_dev, int64_t rows, int cols,
+                              a3d_dropout drop, void* stream);
+
 /* Optimiser step of the reference's training loop: torch.optim.AdamW(lr, weight_decay) (main.py:125-127) after
  * clip_grad_norm_(parameters, max_norm) (engine.py:145-150).  a3d_sum_squares returns sum g^2 of one tensor to the
  * host (the caller adds the tensors, clip coefficient = min(1, max_norm / (sqrt(total) + 1e-6))); a3d_adamw_step is

@@ -43,6 +43,7 @@ def main():
     ap.add_argument("--tape", action="store_true", help="also time a training-mode forward + backward of the backbone")
     ap.add_argument("--step", action="store_true", help="also time complete training iterations")
     ap.add_argument("--only", type=int, default=-1, help="only this case of the table (PMC passes: one shape per kernel name)")
+    ap.add_argument("--dropout", type=float, default=0.0, help="--step: the model's decoder dropout p")
     a = ap.parse_args()
     coords = np.concatenate([make_scene(a.voxels, seed=b, batch_index=b)["coords"] for b in range(a.batch)])
     sc = Scene(torch.from_numpy(coords).cuda())
@@ -64,6 +65,7 @@ def main():
         fl = 2.0 * pairs * cin * cout
         print(f"{name}: pairs {pairs:8d}  dW {1e3 * t_w:8.1f} us {fl / t_w / 1e9:6.1f} TF/s   "
               f"dx (incl. weight repack + buffer copies) {1e3 * t_x:8.1f} us {fl / t_x / 1e9:6.1f} TF/s")
+    return a
 
 
 def tape_time(voxels, batch):
@@ -91,7 +93,7 @@ def tape_time(voxels, batch):
           f"({len(grads)} gradients)")
 
 
-def step_time(voxels, batch):
+def step_time(voxels, batch, dropout=0.0):
     """Complete training iterations (engine.py:38-150) on a synthetic labelled batch."""
     import random
     import time
@@ -100,8 +102,9 @@ def step_time(voxels, batch):
     from agile3d_amd.optim import AdamW
     from agile3d_amd.train_step import train_one_step
     torch.manual_seed(0)
-    args = default_args(bce_loss_coef=1.0, dice_loss_coef=2.0, losses=["bce", "dice"])
+    args = default_args(bce_loss_coef=1.0, dice_loss_coef=2.0, losses=["bce", "dice"], dropout=dropout)
     model = build_model(args).cuda()
+    print(f"decoder dropout p = {dropout}")
     crit = build_mask_criterion(args)
     scenes = [make_scene(voxels, seed=b) for b in range(batch)]
     b = (batched_coordinates([s["coords"][:, 1:] for s in scenes]),
@@ -133,8 +136,8 @@ def step_time(voxels, batch):
 
 
 if __name__ == "__main__":
-    main()
+    opts = main()
     if "--tape" in sys.argv:
         tape_time(80_000, 4)
     if "--step" in sys.argv:
-        step_time(80_000, 4)
+        step_time(80_000, 4, opts.dropout)
