@@ -45,15 +45,26 @@ def time_table(d_model: int = 128, length: int = 200):
 # the activation of the FFN and of the mask MLP: a module attribute so that the gradient comparison of the training path
 # can substitute the 0/1 masks of the implementation under test (see oracle/backbone.py: RELU)
 RELU = torch.relu
+# the reduction of an object's query columns in the mask head (agile3d.py:353,359): a module attribute so that a negative
+# control can replace it
+GROUP_MAX = lambda prods: prods.max(dim=-1, keepdim=True)[0]  # noqa: E731
+
+# dropout sites of one decoder pass, in the order the reference's modules call torch.nn.functional.dropout
+# (attention_block.py over nn.MultiheadAttention): site code = 8 * pass + site
+SITE_C2S_ATTN, SITE_C2S_OUT, SITE_C2C_ATTN, SITE_C2C_OUT, SITE_FFN_HIDDEN, SITE_FFN_OUT, SITE_S2C_ATTN, SITE_S2C_OUT = range(8)
+
+
+def _drop(drop, site, x):
+    return x if drop is None else drop(site, x)
 
 
 def layer_norm(x, sd, prefix):
     return F.layer_norm(x, (x.shape[-1],), sd[prefix + "weight"], sd[prefix + "bias"], LN_EPS)
 
 
-def mha(sd, prefix, query, key, value, attn_mask=None, nhead: int = 8):
-    """nn.MultiheadAttention forward on unbatched [L,E] inputs (dropout 0).  attn_mask: bool
-    [Lq,Lk], True = blocked."""
+def mha(sd, prefix, query, key, value, attn_mask=None, nhead: int = 8, drop=None, site=None):
+    """nn.MultiheadAttention forward on unbatched [L,E] inputs.  attn_mask: bool [Lq,Lk], True = blocked (SURVEY App.
+    C.3).  ``drop(site, x)``: the dropout of the probabilities [h, Lq, Lk] after the softmax (None: none)."""
     E = query.shape[-1]
     W, b = sd[prefix + "in_proj_weight"], sd[prefix + "in_proj_bias"]
     q = query @ W[:E].T + b[:E]
@@ -67,29 +78,30 @@ def mha(sd, prefix, query, key, value, attn_mask=None, nhead: int = 8):
     s = q @ k.transpose(1, 2)  # [h, Lq, Lk]
     if attn_mask is not None:
         s = s.masked_fill(attn_mask.unsqueeze(0), float("-inf"))
-    p = torch.softmax(s, dim=-1)
+    p = _drop(drop, site, torch.softmax(s, dim=-1))
     o = (p @ v).transpose(0, 1).reshape(Lq, E)
     return o @ sd[prefix + "out_proj.weight"].T + sd[prefix + "out_proj.bias"]
 
 
-def cross_attention_layer(sd, prefix, tgt, memory, memory_mask, pos, query_pos):
-    """CrossAttentionLayer.forward_post, attention_block.py:86-98."""
-    tgt2 = mha(sd, prefix + "multihead_attn.", tgt + query_pos, memory + pos, memory, memory_mask)
-    return layer_norm(tgt + tgt2, sd, prefix + "norm.")
+def cross_attention_layer(sd, prefix, tgt, memory, memory_mask, pos, query_pos, drop=None, sites=(None, None)):
+    """CrossAttentionLayer.forward_post, attention_block.py:86-98.  ``sites``: the dropout sites of the probabilities and
+    of the output."""
+    tgt2 = mha(sd, prefix + "multihead_attn.", tgt + query_pos, memory + pos, memory, memory_mask, drop=drop, site=sites[0])
+    return layer_norm(tgt + _drop(drop, sites[1], tgt2), sd, prefix + "norm.")
 
 
-def self_attention_layer(sd, prefix, tgt, query_pos):
+def self_attention_layer(sd, prefix, tgt, query_pos, drop=None):
     """SelfAttentionLayer.forward_post, attention_block.py:28-38."""
     qk = tgt + query_pos
-    tgt2 = mha(sd, prefix + "self_attn.", qk, qk, tgt, None)
-    return layer_norm(tgt + tgt2, sd, prefix + "norm.")
+    tgt2 = mha(sd, prefix + "self_attn.", qk, qk, tgt, None, drop=drop, site=SITE_C2C_ATTN)
+    return layer_norm(tgt + _drop(drop, SITE_C2C_OUT, tgt2), sd, prefix + "norm.")
 
 
-def ffn_layer(sd, prefix, tgt):
+def ffn_layer(sd, prefix, tgt, drop=None):
     """FFNLayer.forward_post, attention_block.py:151-155."""
-    h = RELU(tgt @ sd[prefix + "linear1.weight"].T + sd[prefix + "linear1.bias"])
+    h = _drop(drop, SITE_FFN_HIDDEN, RELU(tgt @ sd[prefix + "linear1.weight"].T + sd[prefix + "linear1.bias"]))
     tgt2 = h @ sd[prefix + "linear2.weight"].T + sd[prefix + "linear2.bias"]
-    return layer_norm(tgt + tgt2, sd, prefix + "norm.")
+    return layer_norm(tgt + _drop(drop, SITE_FFN_OUT, tgt2), sd, prefix + "norm.")
 
 
 def mask_module(sd, fg_q, bg_q, mask_features, fg_split):
@@ -100,8 +112,8 @@ def mask_module(sd, fg_q, bg_q, mask_features, fg_split):
         return h @ sd["mask_embed_head.2.weight"].T + sd["mask_embed_head.2.bias"]
 
     fg_prods = (mask_features @ embed(fg_q).T).split(fg_split, dim=1)
-    fg_masks = torch.cat([p.max(dim=-1, keepdim=True)[0] for p in fg_prods], dim=-1)
-    bg_masks = (mask_features @ embed(bg_q).T).max(dim=-1, keepdim=True)[0]
+    fg_masks = torch.cat([GROUP_MAX(p) for p in fg_prods], dim=-1)
+    bg_masks = GROUP_MAX(mask_features @ embed(bg_q).T)
     out = torch.cat([bg_masks, fg_masks], dim=-1)
     labels = out.argmax(1)
     rows = []
@@ -119,7 +131,8 @@ def mask_module(sd, fg_q, bg_q, mask_features, fg_split):
 
 # ----------------------------------------------------------------------------- forward_mask
 def forward_mask(sd, pcd_features, raw_xyz, pos_enc, click_idx, click_time_idx,
-                 num_decoders: int = 3, return_masks: bool = False, grad: bool = False, force_masks=None):
+                 num_decoders: int = 3, return_masks: bool = False, grad: bool = False, force_masks=None, dropout=None,
+                 query_features=None):
     """Agile3d.forward_mask for ONE batch sample (agile3d.py:192-323).
 
     pcd_features [N,128], raw_xyz [N,3], pos_enc [N,128] (level-4 Fourier encoding),
@@ -127,7 +140,9 @@ def forward_mask(sd, pcd_features, raw_xyz, pos_enc, click_idx, click_time_idx,
     Returns list of ``num_decoders`` logits tensors [N,1+K] (last = 'pred_masks', earlier =
     'aux_outputs').  ``grad=True`` keeps the autograd graph (training-path tests); ``force_masks`` replaces the
     label-derived attention masks of the layers by given ones (they are not differentiated; a test passes the masks of
-    the implementation under test so that both follow the same branch).
+    the implementation under test so that both follow the same branch).  ``dropout(d, site, x)``: x with the dropout of
+    site ``site`` (SITE_*) of decoder pass ``d`` applied (None: training at p = 0, or evaluation).  ``query_features``:
+    the rows the click queries are gathered from (default ``pcd_features``; a negative control passes a detached copy).
     """
     with torch.set_grad_enabled(grad):
         mins, maxs = raw_xyz.min(0)[0], raw_xyz.max(0)[0]
@@ -137,6 +152,7 @@ def forward_mask(sd, pcd_features, raw_xyz, pos_enc, click_idx, click_time_idx,
         fg_times = [t for i in range(1, K + 1) for t in click_time_idx[str(i)]]
         tt = time_table(pcd_features.shape[1], 200)
         B = sd["pos_enc.gauss_B"]
+        qf = pcd_features if query_features is None else query_features
         fg_pos = fourier_pos_enc(raw_xyz[fg_rows], B, mins, maxs) + tt[fg_times]
         bg_pos = sd["bg_query_pos.weight"]
         bg_q = sd["bg_query_feat.weight"]
@@ -144,19 +160,21 @@ def forward_mask(sd, pcd_features, raw_xyz, pos_enc, click_idx, click_time_idx,
         if len(bg_rows):
             bpos = fourier_pos_enc(raw_xyz[bg_rows], B, mins, maxs) + tt[list(click_time_idx["0"])]
             bg_pos = torch.cat([bg_pos, bpos], 0)
-            bg_q = torch.cat([bg_q, pcd_features[bg_rows]], 0)
-        fg_q = pcd_features[fg_rows]
+            bg_q = torch.cat([bg_q, qf[bg_rows]], 0)
+        fg_q = qf[fg_rows]
         n_fg, n_bg = fg_q.shape[0], bg_q.shape[0]
         qpos = torch.cat([fg_pos, bg_pos], 0)
         src = pcd_features
         attn_mask = None
         outs, masks = [], []
         for d in range(num_decoders):
+            drop = None if dropout is None else (lambda site, x, d=d: dropout(d, site, x))
             out = cross_attention_layer(sd, f"c2s_attention.{d}.0.", torch.cat([fg_q, bg_q], 0), src,
-                                        attn_mask, pos_enc, qpos)
-            out = self_attention_layer(sd, f"c2c_attention.{d}.0.", out, qpos)
-            queries = ffn_layer(sd, f"ffn_attention.{d}.0.", out)
-            src = cross_attention_layer(sd, f"s2c_attention.{d}.0.", src, queries, None, qpos, pos_enc)
+                                        attn_mask, pos_enc, qpos, drop, (SITE_C2S_ATTN, SITE_C2S_OUT))
+            out = self_attention_layer(sd, f"c2c_attention.{d}.0.", out, qpos, drop)
+            queries = ffn_layer(sd, f"ffn_attention.{d}.0.", out, drop)
+            src = cross_attention_layer(sd, f"s2c_attention.{d}.0.", src, queries, None, qpos, pos_enc, drop,
+                                        (SITE_S2C_ATTN, SITE_S2C_OUT))
             fg_q, bg_q = queries.split([n_fg, n_bg], 0)
             logits, attn_mask = mask_module(sd, fg_q, bg_q, src, fg_split)
             if force_masks is not None:

@@ -236,11 +236,10 @@ def _decoder_case(model):
 
 
 def test_decoder_tape_with_dropout_matches_autograd():
-    """The three decoder passes at p = 0.1 against float64 autograd through oracle/decoder.py whose layers are
-    restated here with attention_block.py's dropout sites, the masks taken from a3d_dropout_mask (and the ReLU and
-    attention masks from the tape, as in test_decoder_training_step_matches_autograd)."""
-    import math
-    import torch.nn.functional as F
+    """The three decoder passes at p = 0.1 against float64 autograd through oracle/decoder.py with its dropout hook at
+    attention_block.py's sites (pinned on the reference's own modules by tests/golden/make_decoder_train_goldens.py), the
+    masks taken from a3d_dropout_mask (and the ReLU and attention masks from the tape, as in
+    test_decoder_training_step_matches_autograd)."""
     from agile3d_amd import build_model, default_args
     from agile3d_amd.train_decoder import DecoderTape
     from oracle import decoder as od
@@ -249,41 +248,12 @@ def test_decoder_tape_with_dropout_matches_autograd():
     model = build_model(default_args(dropout=p)).cuda().train()
     pcd, xyz, sd, pos, ci, ct, R = _decoder_case(model)
     tape = DecoderTape(model, pcd.cuda(), pos.float().cuda(), ci, ct, dropout=p, seed=seed)
-    N, Q = pcd.shape[0], 16
-    state = {"d": -1, "s": 0}
-    site_of = {}
+    state = {"d": -1}
 
-    def Z(s, heads, rows, cols):
-        return zmat(seed, 0, 8 * state["d"] + s, p, heads, rows, cols)
-
-    def mha(sd_, prefix, query, key, value, attn_mask=None, nhead=8, s_attn=0):
-        E = query.shape[-1]
-        W, b = sd_[prefix + "in_proj_weight"], sd_[prefix + "in_proj_bias"]
-        q = (query @ W[:E].T + b[:E]).reshape(-1, 8, 16).transpose(0, 1) / 4.0
-        k = (key @ W[E:2 * E].T + b[E:2 * E]).reshape(-1, 8, 16).transpose(0, 1)
-        v = (value @ W[2 * E:].T + b[2 * E:]).reshape(-1, 8, 16).transpose(0, 1)
-        s = q @ k.transpose(1, 2)
-        if attn_mask is not None:
-            s = s.masked_fill(attn_mask.unsqueeze(0), float("-inf"))
-        pr = torch.softmax(s, -1) * Z(s_attn, 8, s.shape[1], s.shape[2])
-        o = (pr @ v).transpose(0, 1).reshape(-1, E)
-        return (o @ sd_[prefix + "out_proj.weight"].T + sd_[prefix + "out_proj.bias"]) * Z(s_attn + 1, 1, o.shape[0], 128)[0]
-
-    def cross(sd_, prefix, tgt, memory, memory_mask, pos_, query_pos):
-        if prefix.startswith("c2s"):
-            state["d"] += 1
-        s_attn = 0 if prefix.startswith("c2s") else 6
-        tgt2 = mha(sd_, prefix + "multihead_attn.", tgt + query_pos, memory + pos_, memory, memory_mask, s_attn=s_attn)
-        return od.layer_norm(tgt + tgt2, sd_, prefix + "norm.")
-
-    def selfl(sd_, prefix, tgt, query_pos):
-        qk = tgt + query_pos
-        return od.layer_norm(tgt + mha(sd_, prefix + "self_attn.", qk, qk, tgt, None, s_attn=2), sd_, prefix + "norm.")
-
-    def ffn(sd_, prefix, tgt):
-        h = od.RELU(tgt @ sd_[prefix + "linear1.weight"].T + sd_[prefix + "linear1.bias"]) * Z(4, 1, tgt.shape[0], 1024)[0]
-        tgt2 = (h @ sd_[prefix + "linear2.weight"].T + sd_[prefix + "linear2.bias"]) * Z(5, 1, tgt.shape[0], 128)[0]
-        return od.layer_norm(tgt + tgt2, sd_, prefix + "norm.")
+    def dropout(d, s, x):
+        state["d"] = max(state["d"], d)
+        heads, rows, cols = x.shape if x.dim() == 3 else (1,) + tuple(x.shape)
+        return x * zmat(seed, 0, 8 * d + s, p, heads, rows, cols).reshape(x.shape)
 
     n_fg = 6
     relu_seq = []
@@ -295,13 +265,12 @@ def test_decoder_tape_with_dropout_matches_autograd():
         if not k.startswith(("backbone.", "pos_enc.")):
             sd[k].requires_grad_()
     pcd_o = pcd.double().requires_grad_()
-    saved = (od.RELU, od.cross_attention_layer, od.self_attention_layer, od.ffn_layer)
-    od.RELU, od.cross_attention_layer, od.self_attention_layer, od.ffn_layer = lambda z: z * next(it), cross, selfl, ffn
+    od.RELU = lambda z: z * next(it)
     try:
         outs = od.forward_mask(sd, pcd_o, xyz.double(), pos, ci, ct, grad=True,
-                               force_masks=[m.cpu().bool() for m in tape.attn_masks])
+                               force_masks=[m.cpu().bool() for m in tape.attn_masks], dropout=dropout)
     finally:
-        od.RELU, od.cross_attention_layer, od.self_attention_layer, od.ffn_layer = saved
+        od.RELU = torch.relu
     assert state["d"] == 2
     for l in range(3):
         err = (tape.logits[l].cpu().double() - outs[l].detach()).abs().max().item()
