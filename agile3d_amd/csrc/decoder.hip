@@ -136,15 +136,19 @@ __global__ void k_minmax_final(const float* __restrict__ part, int nb, float* mi
   }
   if (lane == 0) minmax[a] = v;
 }
-// get_fourier_embeddings with normalize=True: u = (x-min)/(max-min); p = (2 pi u) @ B; [sin p, cos p]
+// get_fourier_embeddings: u = (x-min)/(max-min) with normalize=True (NORM), u = x without; p = (2 pi u) @ B; [sin p, cos p]
+template <bool NORM>
 __device__ __forceinline__ void fourier_row(const float* __restrict__ xyz, size_t i, int jj, const float* __restrict__ gaussB,
                                             const float* __restrict__ minmax, float* out) {
   const float two_pi = 6.283185307179586f;
   float p = 0.f;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const float mn = minmax[a], mx = minmax[3 + a];
-    float u = (xyz[3 * i + a] - mn) / (mx - mn);
+    float u = xyz[3 * i + a];
+    if (NORM) {
+      const float mn = minmax[a], mx = minmax[3 + a];
+      u = (u - mn) / (mx - mn);
+    }
     u *= two_pi;
     p += u * gaussB[a * 64 + jj];
   }
@@ -153,11 +157,12 @@ __device__ __forceinline__ void fourier_row(const float* __restrict__ xyz, size_
   out[i * D + jj] = sn;
   out[i * D + 64 + jj] = cs;
 }
+template <bool NORM>
 __global__ void k_fourier(const float* __restrict__ xyz, int n, const float* __restrict__ gaussB,
                           const float* __restrict__ minmax, float* out) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (size_t)n * 64) return;
-  fourier_row(xyz, e >> 6, (int)(e & 63), gaussB, minmax, out);
+  fourier_row<NORM>(xyz, e >> 6, (int)(e & 63), gaussB, minmax, out);
 }
 // ---- the same for every sample of a batch in three launches (rows of sample b = [start[b], start[b+1]) of one matrix)
 constexpr int kPosBlocks = 16;   // partial-reduction blocks per sample
@@ -195,6 +200,7 @@ __global__ void __launch_bounds__(256) k_minmax_partial_b(const float* __restric
   }
   if (threadIdx.x < 6) part[((size_t)b * kPosBlocks + blockIdx.x) * 6 + threadIdx.x] = s[threadIdx.x][0];
 }
+template <bool NORM>
 __global__ void k_fourier_b(const float* __restrict__ xyz, const PosBatch pb, const float* __restrict__ gaussB,
                             const float* __restrict__ minmax, float* out) {
   // blockIdx.y = sample (uniform: its row range comes from scalar loads), blockIdx.x = 4-row block inside it
@@ -202,7 +208,96 @@ __global__ void k_fourier_b(const float* __restrict__ xyz, const PosBatch pb, co
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = (size_t)r0 + (e >> 6);
   if (i >= (size_t)r1) return;
-  fourier_row(xyz, i, (int)(e & 63), gaussB, minmax + 6 * b, out);
+  fourier_row<NORM>(xyz, i, (int)(e & 63), gaussB, minmax + 6 * b, out);
+}
+
+// ---- positional_encoding_type "sine": get_sine_embeddings (position_embedding.py:75-121) for d_pos = 128, d_in = 3.
+// The 128 channels are 64 interleaved (sin, cos) pairs of ONE argument each: x owns pairs 0..21 (44 channels: ndim = 42 and
+// the remainder of 2 goes to the first axis), y pairs 22..42, z pairs 43..63; the argument of pair k of an axis with cdim
+// channels is 2 pi u / 10000^(2k / cdim), u the coordinate (NORM: shifted and scaled to [0, 1] by the sample's min / max).
+// The divisors have no parameter behind them: a table, the float32 values of 10000 ** (2 k / cdim) as the reference's
+// dim_t holds them (cdim = 44: 22 entries, then twice cdim = 42: 21 entries).
+__device__ const float kSineDimT[64] = {
+    1.0f, 1.519911f, 2.3101296f, 3.5111918f, 5.3366995f, 8.111309f, 12.328468f, 18.738173f,
+    28.480362f, 43.287613f, 65.79333f, 100.0f, 151.99113f, 231.01291f, 351.11914f, 533.6699f,
+    811.131f, 1232.8464f, 1873.8174f, 2848.0361f, 4328.762f, 6579.331f, 1.0f, 1.5505158f,
+    2.4040992f, 3.727594f, 5.779693f, 8.961505f, 13.894957f, 21.54435f, 33.404854f, 51.79475f,
+    80.30857f, 124.51974f, 193.06982f, 299.3578f, 464.15897f, 719.6858f, 1115.8842f, 1730.1959f,
+    2682.696f, 4159.5625f, 6449.467f, 1.0f, 1.5505158f, 2.4040992f, 3.727594f, 5.779693f,
+    8.961505f, 13.894957f, 21.54435f, 33.404854f, 51.79475f, 80.30857f, 124.51974f, 193.06982f,
+    299.3578f, 464.15897f, 719.6858f, 1115.8842f, 1730.1959f, 2682.696f, 4159.5625f, 6449.467f};
+// one lane = four adjacent channels = two pairs: one sincosf per pair (full precision: un-normalised arguments reach
+// hundreds of radians), one 16-byte store; 32 lanes write a 512-byte row
+template <bool NORM>
+__device__ __forceinline__ void sine_quad(const float* __restrict__ xyz, size_t i, int c4, const float* __restrict__ minmax,
+                                          float* out) {
+  const float two_pi = 6.283185307179586f;
+  float4 v;
+  float* vp = &v.x;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int p = 2 * c4 + h;
+    const int a = (p >= 22) + (p >= 43);
+    float u = xyz[3 * i + a];
+    if (NORM) {
+      const float mn = minmax[a], mx = minmax[3 + a];
+      u = (u - mn) / (mx - mn);
+    }
+    u *= two_pi;
+    sincosf(u / kSineDimT[p], &vp[2 * h], &vp[2 * h + 1]);
+  }
+  *reinterpret_cast<float4*>(out + i * D + 4 * c4) = v;
+}
+template <bool NORM>
+__global__ void k_sine(const float* __restrict__ xyz, int n, const float* __restrict__ minmax, float* out) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (size_t)n * 32) return;
+  sine_quad<NORM>(xyz, e >> 5, (int)(e & 31), minmax, out);
+}
+template <bool NORM>
+__global__ void k_sine_b(const float* __restrict__ xyz, const PosBatch pb, const float* __restrict__ minmax, float* out) {
+  const int b = blockIdx.y, r0 = pb.start[b], r1 = pb.start[b + 1];      // blockIdx.x = 8-row block inside sample b
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = (size_t)r0 + (e >> 5);
+  if (i >= (size_t)r1) return;
+  sine_quad<NORM>(xyz, i, (int)(e & 31), minmax + 6 * b, out);
+}
+
+// ---- positional_encoding_type "legacy": PositionalEncoding3D(128) (position_embedding.py:179-208) on the RAW coordinates
+// (neither the sample's range nor normalize_pos_enc enter).  Per axis 44 channels [sin(x f_j) (22), cos(x f_j) (22)],
+// f = the model's inv_freq buffer; the three axes side by side are 132 channels, of which the first 128 are kept (z loses
+// its last four cosines).  A block encodes kLegRows rows: one sincosf per (row, axis, frequency) goes into an LDS image
+// of the 132-channel rows, from which 32 lanes per row store the first 128 channels 16 bytes at a time.
+constexpr int kLegRows = 32, kLegF = 22, kLegLd = 6 * kLegF;
+__device__ __forceinline__ void legacy_rows(const float* __restrict__ xyz, size_t r0, int rows, const float* __restrict__ inv_freq,
+                                            float* out, float (*s)[kLegLd]) {
+  for (int t = threadIdx.x; t < rows * 3 * kLegF; t += blockDim.x) {
+    const int r = t / (3 * kLegF), q = t - 3 * kLegF * r, a = q / kLegF, j = q - kLegF * a;
+    float sn, cs;
+    sincosf(xyz[3 * (r0 + r) + a] * inv_freq[j], &sn, &cs);
+    s[r][2 * kLegF * a + j] = sn;
+    s[r][2 * kLegF * a + kLegF + j] = cs;
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < rows * 32; t += blockDim.x) {
+    const int r = t >> 5, c4 = t & 31;
+    *reinterpret_cast<float4*>(out + (r0 + r) * D + 4 * c4) = *reinterpret_cast<const float4*>(&s[r][4 * c4]);
+  }
+}
+__global__ void __launch_bounds__(256) k_legacy(const float* __restrict__ xyz, int n, const float* __restrict__ inv_freq,
+                                                float* out) {
+  __shared__ __align__(16) float s[kLegRows][kLegLd];
+  const size_t r0 = (size_t)blockIdx.x * kLegRows;
+  if (r0 >= (size_t)n) return;
+  legacy_rows(xyz, r0, (int)((size_t)n - r0 < (size_t)kLegRows ? (size_t)n - r0 : (size_t)kLegRows), inv_freq, out, s);
+}
+__global__ void __launch_bounds__(256) k_legacy_b(const float* __restrict__ xyz, const PosBatch pb,
+                                                  const float* __restrict__ inv_freq, float* out) {
+  __shared__ __align__(16) float s[kLegRows][kLegLd];
+  const int b = blockIdx.y, r1 = pb.start[b + 1];
+  const size_t r0 = (size_t)pb.start[b] + (size_t)blockIdx.x * kLegRows;
+  if (r0 >= (size_t)r1) return;
+  legacy_rows(xyz, r0, (int)((size_t)r1 - r0 < (size_t)kLegRows ? (size_t)r1 - r0 : (size_t)kLegRows), inv_freq, out, s);
 }
 
 struct QueryMeta {   // device-resident, uploaded once per forward_mask
@@ -2333,7 +2428,7 @@ extern "C" int a3d_posenc_fourier(const float* xyz_dev, int64_t n, const float* 
   k_minmax_partial<<<nb, 256, 0, st>>>(xyz_dev, (int)n, part);
   k_minmax_final<<<1, 384, 0, st>>>(part, nb, minmax_dev);
   const size_t total = (size_t)n * 64;
-  k_fourier<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(xyz_dev, (int)n, gauss_B_dev, minmax_dev, out_dev);
+  k_fourier<true><<<(unsigned)((total + 255) / 256), 256, 0, st>>>(xyz_dev, (int)n, gauss_B_dev, minmax_dev, out_dev);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -2369,8 +2464,106 @@ extern "C" int a3d_posenc_fourier_batch(const float* xyz_dev, const int64_t* sta
   k_minmax_final<<<n_samples, 384, 0, st>>>(part, kPosBlocks, minmax_dev);
   int n_max = 0;
   for (int b = 0; b < n_samples; ++b) n_max = std::max(n_max, pb.start[b + 1] - pb.start[b]);
-  k_fourier_b<<<dim3((unsigned)(((size_t)n_max * 64 + 255) / 256), n_samples), 256, 0, st>>>(xyz_dev, pb, gauss_B_dev, minmax_dev,
-                                                                                            out_dev);
+  k_fourier_b<true><<<dim3((unsigned)(((size_t)n_max * 64 + 255) / 256), n_samples), 256, 0, st>>>(xyz_dev, pb, gauss_B_dev,
+                                                                                                  minmax_dev, out_dev);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+// every encoding of the reference behind one pair of entry points (a3d_posenc_fourier[_batch] above = kind FOURIER, normalize 1)
+static int posenc_check(const char* who, int kind, int normalize, const float* table_dev, float* minmax_dev, float* out_dev,
+                        bool* use_minmax) {
+  if (kind != A3D_POSENC_FOURIER && kind != A3D_POSENC_SINE && kind != A3D_POSENC_LEGACY) {
+    set_error("%s: unknown encoding kind %d", who, kind);
+    return A3D_ERR_INVALID;
+  }
+  *use_minmax = normalize && kind != A3D_POSENC_LEGACY;
+  if ((kind != A3D_POSENC_SINE && !table_dev) || (*use_minmax && !minmax_dev) || !out_dev) {
+    set_error("%s: bad arguments (table_dev: gauss_B / inv_freq; minmax_dev where the encoding normalises)", who);
+    return A3D_ERR_INVALID;
+  }
+  if (((uintptr_t)out_dev & 15) != 0) {
+    set_error("%s: out_dev must be 16-byte aligned", who);
+    return A3D_ERR_INVALID;
+  }
+  return A3D_OK;
+}
+
+extern "C" int a3d_posenc(int kind, int normalize, const float* xyz_dev, int64_t n, const float* table_dev, float* minmax_dev,
+                          float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  bool mm;
+  if (int rc = posenc_check("a3d_posenc", kind, normalize, table_dev, minmax_dev, out_dev, &mm)) return rc;
+  if (!xyz_dev || n <= 0 || n > (int64_t)1 << 30) {
+    set_error("a3d_posenc: bad arguments");
+    return A3D_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(st, A3D_PROF_POSENC, 0, 0, 3, 128, (int)n);
+  if (mm) {
+    const int nb = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
+    if (!workspace_dev || workspace_bytes < (size_t)nb * 6 * 4) {
+      set_error("a3d_posenc: workspace needs >= %zu bytes", (size_t)256 * 6 * 4);
+      return A3D_ERR_WORKSPACE;
+    }
+    k_minmax_partial<<<nb, 256, 0, st>>>(xyz_dev, (int)n, (float*)workspace_dev);
+    k_minmax_final<<<1, 384, 0, st>>>((const float*)workspace_dev, nb, minmax_dev);
+  }
+  if (kind == A3D_POSENC_FOURIER) {
+    const unsigned g = (unsigned)(((size_t)n * 64 + 255) / 256);
+    if (mm) k_fourier<true><<<g, 256, 0, st>>>(xyz_dev, (int)n, table_dev, minmax_dev, out_dev);
+    else k_fourier<false><<<g, 256, 0, st>>>(xyz_dev, (int)n, table_dev, nullptr, out_dev);
+  } else if (kind == A3D_POSENC_SINE) {
+    const unsigned g = (unsigned)(((size_t)n * 32 + 255) / 256);
+    if (mm) k_sine<true><<<g, 256, 0, st>>>(xyz_dev, (int)n, minmax_dev, out_dev);
+    else k_sine<false><<<g, 256, 0, st>>>(xyz_dev, (int)n, nullptr, out_dev);
+  } else {
+    k_legacy<<<(unsigned)((n + kLegRows - 1) / kLegRows), 256, 0, st>>>(xyz_dev, (int)n, table_dev, out_dev);
+  }
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" int a3d_posenc_batch(int kind, int normalize, const float* xyz_dev, const int64_t* starts_host, int n_samples,
+                                const float* table_dev, float* minmax_dev, float* out_dev, void* workspace_dev,
+                                size_t workspace_bytes, void* stream) {
+  bool mm;
+  if (int rc = posenc_check("a3d_posenc_batch", kind, normalize, table_dev, minmax_dev, out_dev, &mm)) return rc;
+  if (!xyz_dev || !starts_host || n_samples < 1 || n_samples > 64) {
+    set_error("a3d_posenc_batch: bad arguments (1..64 samples)");
+    return A3D_ERR_INVALID;
+  }
+  PosBatch pb;
+  pb.ns = n_samples;
+  for (int b = 0; b <= n_samples; ++b) {
+    if (starts_host[b] < 0 || starts_host[b] > ((int64_t)1 << 30) || (b && starts_host[b] <= starts_host[b - 1])) {
+      set_error("a3d_posenc_batch: sample %d has no rows (starts must ascend)", b - 1);
+      return A3D_ERR_INVALID;
+    }
+    pb.start[b] = (int)starts_host[b];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(st, A3D_PROF_POSENC, 0, 0, 3, 128, pb.start[n_samples]);
+  if (mm) {
+    if (!workspace_dev || workspace_bytes < a3d_posenc_batch_workspace_bytes(n_samples)) {
+      set_error("a3d_posenc_batch: workspace needs >= %zu bytes", a3d_posenc_batch_workspace_bytes(n_samples));
+      return A3D_ERR_WORKSPACE;
+    }
+    k_minmax_partial_b<<<dim3(kPosBlocks, n_samples), 256, 0, st>>>(xyz_dev, pb, (float*)workspace_dev);
+    k_minmax_final<<<n_samples, 384, 0, st>>>((const float*)workspace_dev, kPosBlocks, minmax_dev);
+  }
+  int n_max = 0;
+  for (int b = 0; b < n_samples; ++b) n_max = std::max(n_max, pb.start[b + 1] - pb.start[b]);
+  if (kind == A3D_POSENC_FOURIER) {
+    const dim3 g((unsigned)(((size_t)n_max * 64 + 255) / 256), n_samples);
+    if (mm) k_fourier_b<true><<<g, 256, 0, st>>>(xyz_dev, pb, table_dev, minmax_dev, out_dev);
+    else k_fourier_b<false><<<g, 256, 0, st>>>(xyz_dev, pb, table_dev, nullptr, out_dev);
+  } else if (kind == A3D_POSENC_SINE) {
+    const dim3 g((unsigned)(((size_t)n_max * 32 + 255) / 256), n_samples);
+    if (mm) k_sine_b<true><<<g, 256, 0, st>>>(xyz_dev, pb, minmax_dev, out_dev);
+    else k_sine_b<false><<<g, 256, 0, st>>>(xyz_dev, pb, nullptr, out_dev);
+  } else {
+    k_legacy_b<<<dim3((unsigned)((n_max + kLegRows - 1) / kLegRows), n_samples), 256, 0, st>>>(xyz_dev, pb, table_dev, out_dev);
+  }
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

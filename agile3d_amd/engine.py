@@ -370,7 +370,11 @@ class DecoderPack:
         W.mask_w0, W.mask_b0 = tr(m0.weight), dv(m0.bias)
         W.mask_w2, W.mask_b2 = tr(m2.weight), dv(m2.bias)
         W.bg_query_feat, W.bg_query_pos = dv(model.bg_query_feat.weight), dv(model.bg_query_pos.weight)
-        W.gauss_B = dv(model.pos_enc.gauss_B)
+        # what the position-encoding kernels read: gauss_B (fourier), inv_freq (legacy), nothing (sine) -- the model's
+        # current buffer, so a loaded checkpoint's reaches the device with the next pack
+        kind = getattr(model, "pos_enc_type", "fourier")
+        W.gauss_B = dv(model.pos_enc.gauss_B) if kind == "fourier" else None
+        self.posenc_table_ptr = dv(model.pos_enc.inv_freq) if kind == "legacy" else W.gauss_B
         W.time_table = dv(time_table(d, 200))
         # the query side's matrices once more, in the order the single-block layer kernel's waves read them
         for l in range(n_layers):
@@ -506,7 +510,7 @@ class Engine:
         from .autograd import BackboneFn, _Holder
         from .train_backbone import BackboneTape
         lib = L.load()
-        self.refresh_decoder_if_stale(check_versions=True)      # gauss_B for the position encodings
+        self.refresh_decoder_if_stale(check_versions=True)      # gauss_B / inv_freq for the position encodings
         if not isinstance(x, SparseTensor) or x.device != self.device:
             x = SparseTensor(features=x.F, coordinates=x.C, device=self.device)
         if raw_coordinates is None:
@@ -583,11 +587,7 @@ class Engine:
         st.engine_id = id(self)
         st.ranges = [(0, n)]
         with torch.no_grad():
-            tmp = torch.empty(256 * 6 * 4, dtype=torch.uint8, device=self.device)
-            pe = torch.empty((n, 128), dtype=torch.float32, device=self.device)
-            mm = torch.empty(6, dtype=torch.float32, device=self.device)
-            L.check(lib.a3d_posenc_fourier(_ptr(raw), n, self.decoder.gauss_B_ptr, _ptr(mm), _ptr(pe), _ptr(tmp),
-                                           tmp.numel(), _stream()), "a3d_posenc_fourier")
+            pe, mm = self._posenc(raw)
         st.posenc, st.minmax = [pe], [mm]
         pcd = SparseTensor(features=feats, coordinates=C4)
         pcd._a3d = st
@@ -616,30 +616,48 @@ class Engine:
         coordinates = SparseTensor(features=raw, coordinates=C4)
         return pcd, None, coordinates, [[[None] * len(st.ranges)] for _ in range(4)] + [[list(st.posenc)]]
 
-    def _posenc_batch(self, raw, ranges):
-        """Fourier position encodings of every sample of a batch (agile3d.py:141-161 loops over the samples; each has its
-        own min / max) in three launches: (list of [n_b, 128] views of one matrix, list of [6] min/max views)."""
+    def _posenc(self, raw, starts=None):
+        """The position encoding this model was built with (args.positional_encoding_type, args.normalize_pos_enc;
+        DESIGN.md §4.8) of the rows ``raw`` [n, 3]: one sample (``starts`` None: ([n, 128], [6] min / max)) or the samples
+        ``[starts[b], starts[b + 1])`` (ctypes int64 array; ([n, 128], [ns, 6])).  The min / max is None where the
+        encoding does not normalise (no reduction runs).  The default model calls a3d_posenc_fourier[_batch], every other
+        configuration a3d_posenc[_batch]."""
         lib = L.load()
+        m = self.model
+        kind, norm = L.POSENC_KINDS[m.pos_enc_type], int(m.normalize_pos_enc and m.pos_enc_type != "legacy")
+        n = raw.shape[0]
+        ns = None if starts is None else len(starts) - 1
+        pe = torch.empty((n, 128), dtype=torch.float32, device=self.device)
+        mm = tmp = None
+        if norm:
+            mm = torch.empty(6 if ns is None else (ns, 6), dtype=torch.float32, device=self.device)
+            tmp = torch.empty(256 * 6 * 4 if ns is None else lib.a3d_posenc_batch_workspace_bytes(ns), dtype=torch.uint8,
+                              device=self.device)
+        tail = (_ptr(mm), _ptr(pe), _ptr(tmp), tmp.numel() if norm else 0, _stream())
+        table = self.decoder.posenc_table_ptr
+        if kind == 0 and norm:
+            if ns is None:
+                L.check(lib.a3d_posenc_fourier(_ptr(raw), n, table, *tail), "a3d_posenc_fourier")
+            else:
+                L.check(lib.a3d_posenc_fourier_batch(_ptr(raw), starts, ns, table, *tail), "a3d_posenc_fourier_batch")
+        elif ns is None:
+            L.check(lib.a3d_posenc(kind, norm, _ptr(raw), n, table, *tail), "a3d_posenc")
+        else:
+            L.check(lib.a3d_posenc_batch(kind, norm, _ptr(raw), starts, ns, table, *tail), "a3d_posenc_batch")
+        return pe, mm
+
+    def _posenc_batch(self, raw, ranges):
+        """Position encodings of every sample of a batch (agile3d.py:141-161 loops over the samples; each has its
+        own min / max) in three launches: (list of [n_b, 128] views of one matrix, list of [6] min/max views; None where
+        the model's encoding uses no min / max)."""
         ns = len(ranges)
         if ns > 64 or any(ranges[i][1] != ranges[i + 1][0] for i in range(ns - 1)) or any(e <= s for s, e in ranges):
-            pes, mms = [], []          # unusual layouts: sample by sample
-            tmp = torch.empty(256 * 6 * 4, dtype=torch.uint8, device=self.device)
-            for (s, e) in ranges:
-                pe = torch.empty((e - s, 128), dtype=torch.float32, device=self.device)
-                mm = torch.empty(6, dtype=torch.float32, device=self.device)
-                L.check(lib.a3d_posenc_fourier(_ptr(raw[s:e]), e - s, self.decoder.gauss_B_ptr, _ptr(mm), _ptr(pe), _ptr(tmp),
-                                               tmp.numel(), _stream()), "a3d_posenc_fourier")
-                pes.append(pe)
-                mms.append(mm)
-            return pes, mms
+            pairs = [self._posenc(raw[s:e]) for (s, e) in ranges]          # unusual layouts: sample by sample
+            return [p for p, _ in pairs], [m for _, m in pairs]
         s0, e1 = ranges[0][0], ranges[-1][1]
         starts = (C.c_int64 * (ns + 1))(*([r[0] - s0 for r in ranges] + [e1 - s0]))
-        pe_all = torch.empty((e1 - s0, 128), dtype=torch.float32, device=self.device)
-        mm_all = torch.empty((ns, 6), dtype=torch.float32, device=self.device)
-        tmp = torch.empty(lib.a3d_posenc_batch_workspace_bytes(ns), dtype=torch.uint8, device=self.device)
-        L.check(lib.a3d_posenc_fourier_batch(_ptr(raw[s0:e1]), starts, ns, self.decoder.gauss_B_ptr, _ptr(mm_all), _ptr(pe_all),
-                                             _ptr(tmp), tmp.numel(), _stream()), "a3d_posenc_fourier_batch")
-        return [pe_all[s - s0:e - s0] for (s, e) in ranges], [mm_all[b] for b in range(ns)]
+        pe_all, mm_all = self._posenc(raw[s0:e1], starts)
+        return [pe_all[s - s0:e - s0] for (s, e) in ranges], [None if mm_all is None else mm_all[b] for b in range(ns)]
 
     # ---------------------------------------------------------------- forward_mask
     def forward_mask(self, pcd_features, aux, coordinates, pos_encodings_pcd, click_idx=None, click_time_idx=None):

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("A3D_LIB_PATH") or os.path.join(HERE, "libagile3d_hip.
 A3D_NUM_LEVELS = 5
 A3D_MAX_QUERIES = 256
 A3D_MAX_DEC_LAYERS = 8
+POSENC_KINDS = {"fourier": 0, "sine": 1, "legacy": 2}   # A3D_POSENC_*: args.positional_encoding_type -> a3d_posenc kind
 OP_STEM, OP_CONV3, OP_DOWN, OP_UP, OP_LINEAR = 0, 1, 2, 3, 4
 BUF_NONE, BUF_EXT_OUT = -1, -2
 (TAB_XYZB, TAB_NBR27, TAB_GMASK27, TAB_CHILD8, TAB_GMASKDOWN, TAB_UP8, TAB_GMASKUP, TAB_UPROWS,
@@ -145,6 +146,10 @@ SYMBOLS = {
     "a3d_posenc_batch_workspace_bytes": (C.c_size_t, [C.c_int]),
     "a3d_posenc_fourier_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_posenc": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_size_t, C.c_void_p]),
+    "a3d_posenc_batch": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_decoder_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "a3d_decoder_query_pack_floats": (C.c_size_t, [C.c_int32]),
     "a3d_decoder_mask_pack_floats": (C.c_size_t, []),

@@ -9,8 +9,10 @@ Same argument meaning, same return structures, same ``state_dict`` keys.  All ar
 runs in ``libagile3d_hip.so`` (hand-written gfx950 kernels); there is NO CPU fallback --
 calling a forward without the HIP library or on a non-GPU tensor raises.  Both modes of the ``nn.Module`` are
 served: ``eval()`` by the fused inference kernels, ``train()`` by the training path tied into torch.autograd.
-``args.dropout`` (0 <= p < 1) is the decoder's dropout of the training-mode ``forward_mask``; refused:
-``pre_norm=True``, non-Fourier position encodings, ``hlevels != [4]``, ``hidden_dim`` / ``num_heads`` other than 128 / 8.
+``args.dropout`` (0 <= p < 1) is the decoder's dropout of the training-mode ``forward_mask`` (DESIGN.md §4.7);
+``args.positional_encoding_type`` ("fourier", "sine", "legacy") and ``args.normalize_pos_enc`` select the position
+encoding as in ``models/agile3d.py:57-69``; refused: ``pre_norm=True``, ``hlevels != [4]``,
+``hidden_dim`` / ``num_heads`` other than 128 / 8.
 """
 from __future__ import annotations
 
@@ -20,6 +22,9 @@ import torch
 import torch.nn as nn
 
 from . import modules as M
+
+
+POS_ENC_TYPES = ("fourier", "sine", "legacy")      # --positional_encoding_type of the reference's entry points
 
 
 def default_args(**overrides):
@@ -76,8 +81,9 @@ class Agile3d(nn.Module):
         super().__init__()
         if args.pre_norm:
             raise NotImplementedError("pre_norm=True is outside the hot path (reference default False)")
-        if args.positional_encoding_type != "fourier":
-            raise NotImplementedError("only the default 'fourier' position encoding is on the hot path")
+        if args.positional_encoding_type not in POS_ENC_TYPES:
+            raise ValueError(f"positional_encoding_type must be one of {', '.join(map(repr, POS_ENC_TYPES))}, "
+                             f"not {args.positional_encoding_type!r}")
         if list(args.hlevels) != [4]:
             raise NotImplementedError("only hlevels=[4] (reference default) is on the hot path")
         if not 0.0 <= float(args.dropout) < 1.0:
@@ -103,7 +109,17 @@ class Agile3d(nn.Module):
         self.bg_query_feat = nn.Embedding(args.num_bg_queries, d)
         self.bg_query_pos = nn.Embedding(args.num_bg_queries, d)
         self.mask_embed_head = nn.Sequential(nn.Linear(d, d), nn.ReLU(), nn.Linear(d, d))
-        self.pos_enc = M.FourierPosEncParams(d, 3, args.gauss_scale)
+        # the position encoding of the scene rows and (gathered from them) of the clicks: models/agile3d.py:57-69.  The
+        # holder owns what the reference's module owns (gauss_B / inv_freq / nothing); the engine encodes.
+        # 'legacy' takes the raw coordinates whatever normalize_pos_enc says (PositionalEncoding3D ignores input_range).
+        self.pos_enc_type = args.positional_encoding_type
+        self.normalize_pos_enc = bool(args.normalize_pos_enc)
+        if self.pos_enc_type == "fourier":
+            self.pos_enc = M.FourierPosEncParams(d, 3, args.gauss_scale)
+        elif self.pos_enc_type == "sine":
+            self.pos_enc = M.SinePosEncParams(d, 3)
+        else:
+            self.pos_enc = M.LegacyPosEncParams(d)
 
         n_shared = 1 if args.shared_decoder else args.num_decoders
         self.c2s_attention = nn.ModuleList()

@@ -152,6 +152,27 @@ class FourierPosEncParams(nn.Module):
         self.register_buffer("gauss_B", B)
 
 
+class SinePosEncParams(nn.Module):
+    """``PositionEmbeddingCoordsSine(pos_type='sine')``: no buffer and no parameter (its divisors ``dim_t`` are rebuilt
+    from the temperature at every call, ``position_embedding.py:105-107``), so no ``pos_enc.*`` key in the state dict."""
+
+    def __init__(self, d_pos=128, d_in=3):
+        super().__init__()
+        if (d_pos, d_in) != (128, 3):
+            raise NotImplementedError("the sine encoding kernel is specialised for d_pos=128, d_in=3")
+
+
+class LegacyPosEncParams(nn.Module):
+    """``PositionalEncoding3D(channels)``: owns the ``inv_freq`` buffer (``position_embedding.py:186-191``; 22 entries
+    for 128 channels) -- a state-dict key, so the kernel reads the loaded one."""
+
+    def __init__(self, channels=128):
+        super().__init__()
+        c = int(math.ceil(channels / 6) * 2)
+        c += c % 2
+        self.register_buffer("inv_freq", 1.0 / (10000 ** (torch.arange(0, c, 2).float() / c)))
+
+
 def cross_attention_params(d_model, nhead):
     return _AttnLayerParams(d_model, nhead, "multihead_attn")
 

@@ -530,6 +530,31 @@ int a3d_posenc_fourier_batch(const float* xyz_dev, const int64_t* starts_host, i
                              const float* gauss_B_dev /*[3][64]*/, float* minmax_dev /*[n_samples][6]*/,
                              float* out_dev /*[N][128]*/, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Every position encoding of the reference (--positional_encoding_type, --normalize_pos_enc; selected in
+ * models/agile3d.py:57-69) behind one pair of entry points shaped like the two above.  Channel layout of a row:
+ *   A3D_POSENC_FOURIER  get_fourier_embeddings (position_embedding.py:123-152): p = (2 pi u) @ gauss_B,
+ *                       [sin p (64), cos p (64)].  table_dev = gauss_B [3][64].
+ *   A3D_POSENC_SINE     get_sine_embeddings (:75-121): 64 interleaved (sin, cos) pairs of one argument each, x owns
+ *                       pairs 0..21 (44 channels), y 22..42, z 43..63 (42 each); argument of pair k of an axis with
+ *                       cdim channels = 2 pi u / 10000^(2k / cdim).  No parameter: table_dev is ignored (NULL).
+ *   A3D_POSENC_LEGACY   PositionalEncoding3D(128) (:179-208): per axis [sin(x f_j) (22), cos(x f_j) (22)], the three
+ *                       axes side by side cut to 128 channels.  table_dev = the model's inv_freq buffer [22] (the
+ *                       loaded one: a checkpoint's buffer is honoured).
+ * u is the coordinate shifted and scaled to [0, 1] by the sample's own min / max when `normalize` != 0 (FOURIER, SINE),
+ * the raw coordinate when it is 0; LEGACY always takes the raw coordinate and ignores `normalize`.  Where no min / max
+ * is needed the reduction is skipped: minmax_dev and the workspace are not touched and may be NULL / 0.  out_dev must
+ * be 16-byte aligned.  (FOURIER, normalize = 1) runs the kernels of a3d_posenc_fourier[_batch]: the same bits.
+ * a3d_posenc_batch: bit-identical to a3d_posenc per sample; workspace of a3d_posenc_batch_workspace_bytes. */
+#define A3D_POSENC_FOURIER 0
+#define A3D_POSENC_SINE 1
+#define A3D_POSENC_LEGACY 2
+int a3d_posenc(int kind, int normalize, const float* xyz_dev, int64_t n, const float* table_dev,
+               float* minmax_dev /*[6]*/, float* out_dev /*[n][128]*/, void* workspace_dev, size_t workspace_bytes,
+               void* stream);
+int a3d_posenc_batch(int kind, int normalize, const float* xyz_dev, const int64_t* starts_host, int n_samples,
+                     const float* table_dev, float* minmax_dev /*[n_samples][6]*/, float* out_dev /*[N][128]*/,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Click-query decoder.
  * Replaces: Agile3d.forward_mask + mask_module (models/agile3d.py:183-384) and the post-norm
