@@ -7,7 +7,8 @@ Public surface (mirrors the reference):
     Agile3d.forward_mask         models/agile3d.py:183-339
     SparseTensor, utils          the subset of MinkowskiEngine the callers touch
 Around the path (same names as the reference): ``datasets`` (scan datasets + collate), ``ply`` (binary PLY),
-``evaluate`` (Evaluate loops, NoC / IoU@k tables), ``clicks`` (click simulator, IoU), ``criterion`` (mask losses).
+``evaluate`` (Evaluate loops, NoC / IoU@k tables), ``clicks`` (click simulator, IoU), ``criterion`` (mask losses),
+``session`` (``InteractiveSession``: the interactive tool without a window -- pick, click, full-resolution labels).
 """
 from .hostcpu import cap_host_threads
 cap_host_threads()       # torch's CPU pool sized to the container's CPU quota (hostcpu.py: an oversized pool freezes the launch thread)

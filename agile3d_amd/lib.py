@@ -103,12 +103,33 @@ class IouSample(C.Structure):
                 ("n_full", C.c_int64)]
 
 
+class NearestSource(C.Structure):
+    """a3d_nearest_source: one row set of a3d_nearest_rows."""
+    _fields_ = [("xyz_dev", C.c_void_p), ("n", C.c_int64), ("rows_out_dev", C.c_void_p)]
+
+
+class PickResult(C.Structure):
+    """a3d_pick_result: what a3d_pick_ray writes (index -1 = the ray meets no point)."""
+    _fields_ = [("index", C.c_int32), ("x", C.c_float), ("y", C.c_float), ("z", C.c_float)]
+
+
+class SessionPaintArgs(C.Structure):
+    """a3d_session_paint_args."""
+    _fields_ = [("labels_qv_dev", C.c_void_p), ("n_qv", C.c_int64), ("inverse_map_dev", C.c_void_p), ("n_full", C.c_int64),
+                ("xyz_full_dev", C.c_void_p), ("colors_full_dev", C.c_void_p), ("palette_dev", C.c_void_p),
+                ("cubes_dev", C.c_void_p), ("n_palette", C.c_int32), ("n_cubes", C.c_int32), ("cube_size", C.c_float),
+                ("reserved_", C.c_int32), ("label_full_dev", C.c_void_p), ("colors_out_dev", C.c_void_p),
+                ("err_dev", C.c_void_p)]
+
+
 class ClickCluster(C.Structure):
     _fields_ = [("cluster_id", C.c_int32), ("row", C.c_int32), ("label", C.c_int32), ("pred", C.c_int32),
                 ("error_size", C.c_float)]
 
 
 A3D_MAX_CLICKS = 256
+A3D_NEAREST_MAX_QUERIES = 64
+A3D_NEAREST_MAX_SOURCES = 4
 PROF_DENSE = 11
 PROF_NAMES = ["spconv", "splitk_epilogue", "stem", "c2s_attn", "query_chain", "s2c_attn", "ln_mask", "posenc",
               "scene_sort_levels", "scene_tables", "click_simulator", "dense_gemm"]
@@ -282,6 +303,12 @@ SYMBOLS = {
                                       C.POINTER(C.c_int64), C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_click_loss_weights": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_float,
                                          C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "a3d_session_workspace_bytes": (C.c_size_t, []),
+    "a3d_nearest_rows": (C.c_int, [C.POINTER(NearestSource), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "a3d_pick_ray": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_void_p,
+                               C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_session_paint": (C.c_int, [C.POINTER(SessionPaintArgs), C.c_void_p]),
 }
 
 _lib = None

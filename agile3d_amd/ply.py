@@ -77,6 +77,13 @@ def _read_header(f) -> _Header:
     return _Header(order, elements)
 
 
+def is_triangular_mesh(filename) -> bool:
+    """True when the file's header declares a ``face`` element (read it with ``triangular_mesh=True``), False for a
+    point cloud -- what Open3D's ``read_file_geometry_type`` tells the reference's interactive data loader."""
+    with open(filename, "rb") as f:
+        return _read_header(f).element("face") is not None
+
+
 def read_ply(filename, triangular_mesh=False):
     """Read a binary ``.ply`` file (utils/ply.py:116-189).  Point clouds: one structured array of the vertex
     element.  ``triangular_mesh=True``: ``[vertex array, int32 faces [F, 3]]`` (faces must be ``uchar``-counted

@@ -1,0 +1,385 @@
+"""A headless interactive session: pick, click, paint full-resolution labels.
+
+The third caller of the model API in the reference is its interactive tool (``interactive_tool/
+interactive_segmentation_user.py`` + ``gui.py``).  ``InteractiveSession`` is that tool without a window: the same
+sequence of model calls (``forward_backbone`` once per scene, ``forward_mask`` per inference), the same click
+dictionaries, relabelled ground truth, record line and ``.npy`` files -- and no Open3D.  What surrounds the two model
+calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``):
+
+    pointer ray -> clicked point        a3d_pick_ray       (the GUI renders a depth image and unprojects, gui.py:247-271)
+    find_nearest, twice per click       a3d_nearest_rows   (utils.py:27-29: two full torch.cdist calls; here exact)
+    argmax + clicked rows               a3d_argmax_labels  (interactive_segmentation_user.py:78-81)
+    pred[inverse_map], colours, cubes   a3d_session_paint  (:83-84,125-140; gui.py:276-298,327)
+    IoU against the relabelled truth    a3d_iou_counts     (:86-88)
+
+There is no CPU path: the model and the scene live on the GPU.
+
+Departures from the reference, on purpose:
+  * nearest rows are EXACT (fp32 distances from the coordinate differences); ``torch.cdist`` for one query row uses
+    |a|^2 + |b|^2 - 2ab and misses the nearest row on scenes far from the origin;
+  * object ids beyond the palette wrap around it (the reference's colour table raises ``KeyError`` above 10 objects);
+  * ``infer()`` without a click raises (the reference returns early at ``num_clicks == 0``): a caller that asks for a
+    segmentation with nothing to segment has a bug worth hearing about;
+  * ``click`` refuses what the model would refuse later (an object id that leaves a gap, too many queries);
+  * a click is kept even when no vertex lies inside its cube (the GUI drops it, gui.py:281-282).
+"""
+from __future__ import annotations
+
+import colorsys
+import ctypes as C
+import os
+from datetime import datetime
+
+import numpy as np
+import torch
+
+from . import clicks as K
+from . import lib as L
+from . import ply
+from .sparse import SparseTensor, sparse_quantize
+
+RECORD_FILE, MASK_DIR, CLICK_DIR = "iou_record.csv", "masks", "clicks"
+BACKGROUND_CLICK_COLOR = (0.85, 0.15, 0.15)     # colour of a background click's cube (this project's choice)
+_N_IDS = 256                                    # object ids the IoU kernel counts (labels are 0..255)
+
+
+def default_palette(n_objects: int = 20) -> np.ndarray:
+    """[n_objects + 1, 3] fp32 colours in [0, 1], entry k = object k (entry 0, background, is never used: background
+    vertices keep their own colour).  Hues walk the circle by the golden angle, so neighbouring ids stay apart."""
+    pal = np.zeros((n_objects + 1, 3), np.float32)
+    for k in range(1, n_objects + 1):
+        pal[k] = colorsys.hsv_to_rgb((0.11 + 0.618033988749895 * (k - 1)) % 1.0, 0.85 if k % 2 else 0.6, 0.95)
+    return pal
+
+
+# ---- the strings the reference writes (interactive_segmentation_user.py:86-108), pure host code ------------------------
+def format_iou(miou) -> str:
+    """``'NA'`` without ground truth, else the mean IoU (a float32 value) in per cent, rounded to one decimal."""
+    if miou is None:
+        return "NA"
+    return str(round(float(miou) * 100, 1))
+
+
+def format_avg_clicks(num_clicks: int, num_obj: int) -> str:
+    return str(round(num_clicks / num_obj, 1))
+
+
+def record_line(now: datetime, scene_name: str, num_obj: int, num_clicks: int, iou: str) -> str:
+    return (now.strftime("%Y-%m-%d-%H-%M-%S") + "  " + scene_name + "  NumObjects:" + str(num_obj) + "  AvgNumClicks:"
+            + format_avg_clicks(num_clicks, num_obj) + "  mIoU:" + iou + "\n")
+
+
+def mask_file_name(num_clicks: int, num_obj: int, iou: str) -> str:
+    return "mask_" + format_avg_clicks(num_clicks, num_obj) + "_" + iou + ".npy"
+
+
+def click_file_name(num_clicks: int, num_obj: int, iou: str) -> str:
+    return "click_" + format_avg_clicks(num_clicks, num_obj) + "_" + iou + ".npy"
+
+
+class SessionResult:
+    """What one ``infer()`` returns.  ``labels_full`` int32 [n_full] and ``colors`` fp32 [n_full, 3] stay on the device;
+    ``miou`` is a Python float (the float32 mean IoU) or ``None`` without ground truth; ``record``, ``mask_path`` and
+    ``click_path`` are set when the scene has an ``out_dir``."""
+
+    __slots__ = ("labels_full", "colors", "miou", "iou_per_object", "num_obj", "avg_clicks", "record", "mask_path",
+                 "click_path")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _f3(values, what):
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.float32).reshape(-1))
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError(f"{what} must be three finite numbers")
+    return a
+
+
+class InteractiveSession:
+    """The headless counterpart of ``UserInteractiveSegmentationModel`` plus the GUI's click state.
+
+    ``model``: an ``eval()`` model on the GPU.  ``voxel_size``: the quantisation size (default ``model.voxel_size``).
+    ``cube_size``: half edge of the cube a click paints.  ``palette``: [K + 1, 3] colours in [0, 1] per object id (default
+    ``default_palette()``; ids above the table wrap over entries 1..K, which departs from the reference -- its table
+    raises ``KeyError`` above 10 objects).  ``clock``: a callable returning a ``datetime`` for the record line (default
+    ``datetime.now``)."""
+
+    def __init__(self, model, voxel_size=None, cube_size=0.1, palette=None, clock=None,
+                 background_click_color=BACKGROUND_CLICK_COLOR):
+        self.lib = L.load()
+        if model.training:
+            raise ValueError("InteractiveSession needs an eval() model")
+        self.model = model
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("InteractiveSession runs on the GPU only (model.to('cuda')); there is no CPU path")
+        self.voxel_size = float(model.voxel_size if voxel_size is None else voxel_size)
+        self.cube_size = float(cube_size)
+        pal = default_palette() if palette is None else np.asarray(palette, dtype=np.float32)
+        if pal.ndim != 2 or pal.shape[1] != 3 or not 2 <= pal.shape[0] <= 256:
+            raise ValueError("palette must be [K + 1, 3] with 1 <= K <= 255")
+        self.palette = np.ascontiguousarray(pal)
+        self._palette_dev = torch.from_numpy(self.palette).to(self.device)
+        self.background_click_color = tuple(float(c) for c in background_click_color)
+        self.clock = clock or datetime.now
+        self._ws = torch.empty(self.lib.a3d_session_workspace_bytes(), dtype=torch.uint8, device=self.device)
+        self._small = torch.empty(64, dtype=torch.int32, device=self.device)     # pick result / nearest rows
+        self._counts = torch.empty(3 * _N_IDS + 2, dtype=torch.int64, device=self.device)   # IoU counts + its flag + paint's flag
+        self._counts_host = torch.empty(3 * _N_IDS + 2, dtype=torch.int64).pin_memory()
+        # the click cubes (centre, colour): a pinned host table and its device copy; click() appends one row to both
+        self._cubes_host = torch.zeros((L.A3D_MAX_CLICKS, 6), dtype=torch.float32).pin_memory()
+        self._cubes = self._cubes_host.numpy()
+        self._cubes_dev = torch.zeros((L.A3D_MAX_CLICKS, 6), dtype=torch.float32, device=self.device)
+        self._mask_host = None                      # pinned staging of a scene's full-resolution labels (scenes with an out_dir)
+        self._drop_scene()
+
+    # ------------------------------------------------------------------ scene
+    def _drop_scene(self):
+        self.scene_name = None
+        self.out_dir = None
+        self.coords_full = self.colors_full = self.labels_full_ori = self.labels_qv_ori = None
+        self.inverse_map = self.raw_coords_qv = None
+        self._coords_host = None
+        self._backbone = None
+        self._mask_host = None
+        self._reset_clicks()
+
+    def _reset_clicks(self):
+        self.click_idx = {"0": []}
+        self.click_time_idx = {"0": []}
+        self.click_positions = {"0": []}
+        self.num_clicks = 0
+        self.new_labels = None if self.labels_full_ori is None else torch.zeros_like(self.labels_full_ori)
+        self._labels_qv = None if self.raw_coords_qv is None else torch.zeros(self.raw_coords_qv.shape[0], dtype=torch.int32,
+                                                                               device=self.device)
+
+    def load_scene(self, coords_full, colors_full, labels_full=None, name="scene", out_dir=None):
+        """Voxelise on the GPU, run the backbone once and keep what the clicks need
+        (interactive_segmentation_user.py:161-196).  ``coords_full`` [n, 3] float32 / float64 (quantised in its own
+        precision, like ``ME.utils.sparse_quantize``), ``colors_full`` [n, 3] in [0, 1], ``labels_full`` [n] instance ids
+        or ``None``.  With ``out_dir`` every ``infer()`` appends to ``out_dir/iou_record.csv`` and writes
+        ``out_dir/masks/mask_*.npy`` and ``out_dir/clicks/click_*.npy``.  Everything of a previous scene is dropped."""
+        self._drop_scene()
+        dev = self.device
+        xyz = torch.as_tensor(np.asarray(coords_full) if not torch.is_tensor(coords_full) else coords_full)
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] == 0:
+            raise ValueError("coords_full must be [n, 3] with n > 0")
+        if xyz.dtype not in (torch.float32, torch.float64):
+            xyz = xyz.to(torch.float64)
+        n = xyz.shape[0]
+        col = torch.as_tensor(np.asarray(colors_full) if not torch.is_tensor(colors_full) else colors_full)
+        if tuple(col.shape) != (n, 3):
+            raise ValueError("colors_full must be [n, 3]")
+        xyz = xyz.to(dev).contiguous()
+        col32 = col.to(dev).to(torch.float32).contiguous()
+        coords_qv, unique_map, inverse_map = sparse_quantize(xyz, quantization_size=self.voxel_size, return_index=True,
+                                                             return_inverse=True)
+        self.coords_full = xyz.to(torch.float32).contiguous()          # what find_nearest and the cubes see (gui.py:559)
+        self._coords_host = self.coords_full.cpu().numpy()
+        self.colors_full = col32
+        self.inverse_map = inverse_map.contiguous()
+        self.raw_coords_qv = xyz[unique_map].to(torch.float32).contiguous()
+        if labels_full is not None:
+            lab = torch.as_tensor(np.asarray(labels_full) if not torch.is_tensor(labels_full) else labels_full).reshape(-1)
+            if lab.shape[0] != n:
+                raise ValueError("labels_full must be [n]")
+            self.labels_full_ori = lab.to(dev).to(torch.int32).contiguous()
+            self.labels_qv_ori = self.labels_full_ori[unique_map]
+        bc = torch.cat([torch.zeros((coords_qv.shape[0], 1), dtype=torch.int32, device=dev), coords_qv.to(torch.int32)], 1)
+        data = SparseTensor(coordinates=bc, features=col32[unique_map], device=dev)
+        self._backbone = self.model.forward_backbone(data, raw_coordinates=self.raw_coords_qv)
+        self.scene_name = str(name)
+        self.out_dir = out_dir
+        if out_dir is not None:
+            self._mask_host = torch.empty(n, dtype=torch.int32).pin_memory()
+            os.makedirs(os.path.join(out_dir, MASK_DIR), exist_ok=True)
+            os.makedirs(os.path.join(out_dir, CLICK_DIR), exist_ok=True)
+        self._reset_clicks()
+        return self
+
+    def load_scene_dir(self, path, out_dir=None):
+        """A scene folder in the ``InteractiveDataLoader`` layout (interactive_tool/dataloader.py): ``scan.ply`` (binary;
+        a point cloud or a triangle mesh with x, y, z and red, green, blue), optionally ``label.ply`` with a ``label``
+        property.  The scene's name is the folder's without its ``scene_`` prefix."""
+        scan = os.path.join(path, "scan.ply")
+        v = ply.read_ply(scan, triangular_mesh=True)[0] if ply.is_triangular_mesh(scan) else ply.read_ply(scan)
+        names = v.dtype.names
+        if not all(k in names for k in ("x", "y", "z", "red", "green", "blue")):
+            raise ValueError(f"{scan}: vertex properties x, y, z, red, green, blue expected, found {names}")
+        xyz = np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float64)
+        rgb = np.stack([v["red"], v["green"], v["blue"]], 1)
+        rgb = rgb.astype(np.float64) / 255.0 if rgb.dtype.kind in "ui" else rgb.astype(np.float64)
+        labels = None
+        lab_file = os.path.join(path, "label.ply")
+        if os.path.exists(lab_file):
+            lv = ply.read_ply(lab_file, triangular_mesh=True)[0] if ply.is_triangular_mesh(lab_file) else ply.read_ply(lab_file)
+            labels = lv["label"].astype(np.int32)
+        base = os.path.basename(os.path.normpath(path))
+        name = base[len("scene_"):] if base.startswith("scene_") else base
+        return self.load_scene(xyz, rgb, labels, name=name, out_dir=out_dir)
+
+    def reset(self):
+        """A new annotation of the same scene: clicks, relabelled ground truth and labels start over; the backbone output
+        (and with it the scene's first-layer cache of ``forward_mask``) stays."""
+        self._need_scene()
+        self._reset_clicks()
+
+    def _need_scene(self):
+        if self._backbone is None:
+            raise RuntimeError("no scene loaded (load_scene / load_scene_dir)")
+
+    # ------------------------------------------------------------------ pick and click
+    def pick(self, origin, direction, radius=None):
+        """The vertex a pointer ray meets, ``[x, y, z]``, or ``None`` ("clicked on nothing").  The rule is this library's
+        (``a3d_pick_ray``): among the vertices in front of ``origin`` within ``radius`` (default ``voxel_size``) of the
+        ray, the first along it; ties go to the one closer to the ray, then to the lower index."""
+        self._need_scene()
+        o = _f3(origin, "origin")
+        d64 = np.asarray(direction, dtype=np.float64).reshape(-1)
+        if d64.shape != (3,) or not np.isfinite(d64).all() or not np.linalg.norm(d64) > 0:
+            raise ValueError("direction must be three finite numbers, not all zero")
+        d = np.ascontiguousarray((d64 / np.linalg.norm(d64)).astype(np.float32))
+        r = self.voxel_size if radius is None else float(radius)
+        fp = C.POINTER(C.c_float)
+        L.check(self.lib.a3d_pick_ray(self.coords_full.data_ptr(), self.coords_full.shape[0], o.ctypes.data_as(fp),
+                                      d.ctypes.data_as(fp), r, self._small.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                      _stream(self.device)), "a3d_pick_ray")
+        host = self._small[:4].cpu().numpy()
+        if int(host[0]) < 0:
+            return None
+        return [float(v) for v in host[1:4].view(np.float32)]
+
+    def nearest(self, point):
+        """(voxel row, full-resolution vertex) nearest to ``point``: both searches in one launch pair, exact."""
+        self._need_scene()
+        q = _f3(point, "point")
+        src = (L.NearestSource * 2)()
+        src[0].xyz_dev, src[0].n, src[0].rows_out_dev = self.raw_coords_qv.data_ptr(), self.raw_coords_qv.shape[0], self._small.data_ptr()
+        src[1].xyz_dev, src[1].n, src[1].rows_out_dev = self.coords_full.data_ptr(), self.coords_full.shape[0], self._small.data_ptr() + 4
+        L.check(self.lib.a3d_nearest_rows(src, 2, q.ctypes.data_as(C.POINTER(C.c_float)), 1, self._ws.data_ptr(),
+                                          self._ws.numel(), _stream(self.device)), "a3d_nearest_rows")
+        rows = self._small[:2].cpu().tolist()
+        return rows[0], rows[1]
+
+    def click(self, point, obj: int):
+        """One click at ``point`` for object ``obj`` (0 = background, k >= 1 = object k), booked as gui.py:290-331 does:
+        the voxel row nearest to the point joins ``click_idx``, the running click count ``click_time_idx``, the nearest
+        full-resolution vertex's coordinates ``click_positions``; the first click of a new object relabels the ground
+        truth (every vertex of the instance under the clicked voxel becomes ``obj``).  Returns (voxel row, vertex)."""
+        self._need_scene()
+        obj = int(obj)
+        key = str(obj)
+        n_obj = len(self.click_idx) - 1
+        if obj < 0 or obj > 255:
+            raise ValueError("object ids are 0 (background) .. 255")
+        if key not in self.click_idx and obj != n_obj + 1:
+            raise ValueError(f"object {obj} would leave a gap: the next new object is {n_obj + 1} (forward_mask needs ids 1..K)")
+        if self.num_clicks + 1 + self.model.num_bg_queries > L.A3D_MAX_QUERIES:
+            raise ValueError(f"too many queries: {self.num_clicks + 1} clicks + {self.model.num_bg_queries} background queries "
+                             f"> {L.A3D_MAX_QUERIES}")
+        q = _f3(point, "point")
+        row_qv, row_full = self.nearest(q)
+        position = self._coords_host[row_full].tolist()
+        if key not in self.click_idx:
+            self.click_idx[key], self.click_time_idx[key], self.click_positions[key] = [], [], []
+            if self.new_labels is not None:
+                self.new_labels[self.labels_full_ori == self.labels_qv_ori[row_qv]] = obj
+        self.click_idx[key].append(row_qv)
+        self.click_time_idx[key].append(self.num_clicks)
+        self.click_positions[key].append(position)
+        colour = self.background_click_color if obj == 0 else self._palette_entry(obj)
+        k = self.num_clicks
+        self._cubes[k] = (q[0], q[1], q[2], colour[0], colour[1], colour[2])
+        self._cubes_dev[k].copy_(self._cubes_host[k], non_blocking=True)      # (a row of its own in pinned memory: never rewritten while in flight)
+        self.num_clicks += 1
+        return row_qv, row_full
+
+    def _palette_entry(self, obj):
+        n = self.palette.shape[0]
+        return self.palette[obj if obj < n else 1 + (obj - 1) % (n - 1)]
+
+    # ------------------------------------------------------------------ paint and infer
+    def _launch_paint(self, labels_qv, paint_cubes):
+        n_full = self.coords_full.shape[0]
+        labels_full = torch.empty(n_full, dtype=torch.int32, device=self.device)
+        colors = torch.empty((n_full, 3), dtype=torch.float32, device=self.device)
+        n_cubes = self.num_clicks if paint_cubes else 0
+        cubes = self._cubes_dev if n_cubes else None
+        a = L.SessionPaintArgs()
+        a.labels_qv_dev, a.n_qv = labels_qv.data_ptr(), labels_qv.shape[0]
+        a.inverse_map_dev, a.n_full = self.inverse_map.data_ptr(), n_full
+        a.xyz_full_dev, a.colors_full_dev = self.coords_full.data_ptr(), self.colors_full.data_ptr()
+        a.palette_dev, a.n_palette = self._palette_dev.data_ptr(), self.palette.shape[0]
+        a.cubes_dev, a.n_cubes, a.cube_size = (cubes.data_ptr() if n_cubes else None), n_cubes, self.cube_size
+        a.label_full_dev, a.colors_out_dev = labels_full.data_ptr(), colors.data_ptr()
+        a.err_dev = self._counts.data_ptr() + 8 * (3 * _N_IDS + 1)
+        L.check(self.lib.a3d_session_paint(C.byref(a), _stream(self.device)), "a3d_session_paint")
+        return labels_full, colors, cubes
+
+    def preview(self, paint_cubes=True):
+        """Labels and colours of the current state WITHOUT running the model: the last inference's labels (background
+        before the first) with the clicks' cubes on top -- what the GUI shows between a click and the next inference."""
+        self._need_scene()
+        labels_full, colors, keep = self._launch_paint(self._labels_qv, paint_cubes)
+        if int(self._counts[3 * _N_IDS + 1:].cpu()[0]) & 0xffffffff:
+            raise RuntimeError("a3d_session_paint: inverse_map or labels out of range")
+        return labels_full, colors
+
+    def infer(self, paint_cubes=False, logits=None):
+        """The arithmetic of ``get_next_click(run_model=True)``: ``forward_mask`` on the session's clicks, arg-max with the
+        clicked rows keeping their object, the lift to full resolution with colours (and cubes when asked), the IoU
+        against the relabelled ground truth -- then ONE host round trip.  ``logits`` ([n_voxels, 1 + K], device):
+        use these instead of calling the model (replaying recorded logits)."""
+        self._need_scene()
+        num_obj = len(self.click_idx) - 1
+        if self.num_clicks == 0:
+            raise ValueError("infer() without a click (the reference returns early; here it is an error)")
+        if num_obj == 0:
+            raise ValueError("infer() needs a click on at least one object (the reference divides by the object count)")
+        dev = self.device
+        if logits is None:
+            out = self.model.forward_mask(*self._backbone, click_idx=[self.click_idx], click_time_idx=[self.click_time_idx])
+            logits = out["pred_masks"][0]
+        labels_qv = K.argmax_labels(logits, self.click_idx)
+        labels_full, colors, keep = self._launch_paint(labels_qv, paint_cubes)
+        have_gt = self.new_labels is not None
+        if have_gt:
+            L.check(self.lib.a3d_iou_counts(labels_qv.data_ptr(), labels_qv.shape[0], self.inverse_map.data_ptr(),
+                                            self.new_labels.data_ptr(), self.new_labels.shape[0], _N_IDS,
+                                            self._counts.data_ptr(), _stream(dev)), "a3d_iou_counts")
+        else:
+            self._counts[:3 * _N_IDS + 1].zero_()
+        mask_host = None
+        try:
+            self._counts_host.copy_(self._counts, non_blocking=True)
+            if self.out_dir is not None:
+                mask_host = self._mask_host
+                mask_host.copy_(labels_full, non_blocking=True)
+        finally:
+            torch.cuda.current_stream(dev).synchronize()      # the one host round trip
+        host = self._counts_host.numpy()
+        if host[3 * _N_IDS] or (int(host[3 * _N_IDS + 1]) & 0xffffffff):
+            raise RuntimeError("inverse_map or labels out of range")
+        self._labels_qv = labels_qv
+        miou, per_obj = None, None
+        if have_gt:
+            t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())
+            miou = t.tolist()
+        res = SessionResult(labels_full=labels_full, colors=colors, miou=miou, iou_per_object=per_obj, num_obj=num_obj,
+                            avg_clicks=round(self.num_clicks / num_obj, 1))
+        if self.out_dir is not None:
+            iou = format_iou(miou)
+            res.record = record_line(self.clock(), self.scene_name, num_obj, self.num_clicks, iou)
+            with open(os.path.join(self.out_dir, RECORD_FILE), "a") as f:
+                f.write(res.record)
+            res.mask_path = os.path.join(self.out_dir, MASK_DIR, mask_file_name(self.num_clicks, num_obj, iou))
+            res.click_path = os.path.join(self.out_dir, CLICK_DIR, click_file_name(self.num_clicks, num_obj, iou))
+            np.save(res.mask_path, mask_host.numpy().astype(np.int64))           # the reference saves an int64 arg-max
+            np.save(res.click_path, {"click_idx": self.click_idx, "click_time": self.click_time_idx})
+        return res

@@ -747,6 +747,72 @@ int    a3d_click_loss_weights(const float* xyz_dev, int64_t n, const int32_t* cl
                               float tita, float alpha, float beta, float* weights_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The headless interactive session (csrc/session.hip; agile3d_amd/session.py).
+ * Replaces what surrounds the two model calls of interactive_tool/: find_nearest (utils.py:27-29: one
+ * torch.cdist over all voxel rows and one over all vertices per click), the depth-image pick of gui.py:247-271,
+ * and pred[inverse_map] + get_colors + the click cubes (interactive_segmentation_user.py:83-84,125-140,
+ * gui.py:276-298,327).  a3d_nearest_rows and a3d_pick_ray take one scratch buffer of a fixed size (256-byte aligned).
+ * Both write their first-stage results into it: two calls that share a workspace must be ordered (the same stream, or
+ * an event between them); calls on different streams that may overlap each bring their own workspace.
+ * ------------------------------------------------------------------------------------------ */
+#define A3D_NEAREST_MAX_QUERIES 64
+#define A3D_NEAREST_MAX_SOURCES 4
+size_t a3d_session_workspace_bytes(void);
+
+/* For each of the m query points (HOST array [m][3]) and each source: rows_out_dev[q] = the FIRST arg-min over the
+ * source's rows of (x-qx)^2 + (y-qy)^2 + (z-qz)^2, evaluated in fp32 from the differences, squares added in x, y, z
+ * order, every operation rounded on its own (no fma contraction) -- exact, unlike the |a|^2+|b|^2-2ab form torch.cdist
+ * takes for one query row, which loses the nearest row on scenes far from the origin.  Ties -> the
+ * lowest row; -1 for an empty source.  Deterministic: a minimum over packed (distance bits, row) keys.  One launch pair
+ * serves all sources (a click searches the voxel rows and the full-resolution vertices).  n < 2^31 rows per source.
+ * Coordinates and queries are expected to be finite; the call does not check them.  A row whose distance is NaN orders
+ * behind every finite distance (its key holds the NaN's bits) and is returned only if the source has no other row. */
+typedef struct a3d_nearest_source {
+  const float* xyz_dev;        /* [n][3] */
+  int64_t      n;
+  int32_t*     rows_out_dev;   /* [m] */
+} a3d_nearest_source;
+int    a3d_nearest_rows(const a3d_nearest_source* sources, int n_sources, const float* queries, int m,
+                        void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The headless stand-in for "render a depth image and unproject".  The rule is this library's (the reference leaves
+ * picking to Open3D's renderer): origin o, UNIT direction d (HOST arrays of 3), radius r; among the points p with
+ * t = (p-o).d > 0 and perpendicular distance |(p-o) - t d| <= r the one with the smallest t, ties -> the smaller
+ * perpendicular distance, then the lower index.  result_dev: its index and coordinates; index -1 = the ray meets no
+ * point ("clicked on nothing", gui.py:265). */
+typedef struct a3d_pick_result {
+  int32_t index;
+  float   x, y, z;
+} a3d_pick_result;
+int    a3d_pick_ray(const float* xyz_dev, int64_t n, const float* origin, const float* direction, float radius,
+                    a3d_pick_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* One pass over the n_full full-resolution vertices: label_full[i] = labels_qv[inverse_map[i]] (labels_qv = what
+ * a3d_argmax_labels wrote, clicked rows already overwritten; inverse_map NULL = identity), colour = the palette entry of
+ * a label > 0 (labels >= n_palette wrap over entries 1..n_palette-1; entry 0 is unused) or the vertex's own colour for
+ * label 0, then the click cubes: a vertex whose three fp32 |coordinate differences| to cube c's centre are all < cube_size
+ * takes that cube's colour, the LAST such cube winning.  *err_dev (int32, cleared by the call): bit 0 = an inverse_map
+ * entry outside 0..n_qv-1 (that vertex is left unwritten), bit 1 = a negative label. */
+typedef struct a3d_session_paint_args {
+  const int32_t* labels_qv_dev;     /* [n_qv] */
+  int64_t        n_qv;
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL */
+  int64_t        n_full;
+  const float*   xyz_full_dev;      /* [n_full][3]; read only when n_cubes > 0 */
+  const float*   colors_full_dev;   /* [n_full][3] */
+  const float*   palette_dev;       /* [n_palette][3], 2 <= n_palette <= 256 */
+  const float*   cubes_dev;         /* [n_cubes][6]: centre x, y, z, colour r, g, b; n_cubes <= A3D_MAX_CLICKS */
+  int32_t        n_palette;
+  int32_t        n_cubes;
+  float          cube_size;
+  int32_t        reserved_;
+  int32_t*       label_full_dev;    /* out [n_full] int32 */
+  float*         colors_out_dev;    /* out [n_full][3] */
+  int32_t*       err_dev;
+} a3d_session_paint_args;
+int    a3d_session_paint(const a3d_session_paint_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mask losses (first piece of SURVEY.md section 8 row f-2).
  * Replaces: SetCriterion.loss_bce / loss_dice (models/criterion.py:14-110) for ONE sample and ONE
  * prediction level: losses_dev[0] = mean_i w_i * CE(logits_i, target_i), losses_dev[1] = mean_i w_i *

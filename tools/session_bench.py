@@ -1,0 +1,191 @@
+#!/usr/bin/env python3
+"""Stage times of one click of the headless interactive session, next to the torch / numpy recipe a user of the model API
+would write around the same ``forward_mask`` (the reference's: two ``torch.cdist(...).argmin()``, ``argmax`` + per-object
+overwrite, ``pred[inverse_map]``, ``.cpu().numpy()``, the per-object colour loop) -- both in ONE process and run,
+alternating, on one synthetic scene (~80 k voxels, ~250 k full-resolution vertices) at 1, 5, 10 and 20 clicks.
+
+    python tools/session_bench.py [--voxels 80000] [--reps 60] [--out profiles/session_bench.json]
+
+Every stage is timed twice: with device events around it (what the GPU spent) and with a host clock around a stage that
+ends in a synchronisation (what the caller waits).  Medians over ``--reps`` clicks after a warm-up of 10.  The baseline has
+no pick stage (the reference renders a depth image) and no IoU; the session's "paint + IoU" stage includes the IoU.  Needs
+the GPU; there is no CPU path to time."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from agile3d_amd import build_model, clicks as K, default_args, randomize_bn_stats  # noqa: E402
+from agile3d_amd.session import InteractiveSession  # noqa: E402
+from agile3d_amd.synthetic import make_scene  # noqa: E402
+
+STAGES = ("pick", "nearest", "forward_mask", "argmax", "paint_iou", "round_trip")
+BASE_STAGES = ("nearest", "forward_mask", "argmax", "lift", "round_trip", "colour_loop")
+
+
+class Timer:
+    """Device events + host clock per named stage; a stage's host time ends in a stream synchronisation."""
+
+    def __init__(self, names):
+        self.dev = {n: [] for n in names}
+        self.host = {n: [] for n in names}
+
+    def run(self, name, fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.current_stream().synchronize()
+        self.host[name].append(1e3 * (time.perf_counter() - t0))
+        self.dev[name].append(a.elapsed_time(b))
+        return out
+
+    def medians(self, skip):
+        return ({n: float(np.median(v[skip:])) for n, v in self.dev.items()},
+                {n: float(np.median(v[skip:])) for n, v in self.host.items()})
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--voxels", type=int, default=80_000)
+    ap.add_argument("--reps", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("session_bench needs the GPU")
+    torch.manual_seed(0)
+    model = randomize_bn_stats(build_model(default_args(voxel_size=0.02))).eval().cuda()
+    sc = make_scene(a.voxels, seed=0, voxel_size=0.02)
+    rng = np.random.default_rng(0)
+    raw = sc["raw_xyz"]
+    xyz = np.concatenate([raw] + [raw + rng.uniform(-0.004, 0.004, raw.shape).astype(np.float32) for _ in range(2)]).astype(np.float32)
+    col = np.concatenate([sc["feats"]] * 3).astype(np.float32)
+    lab = np.concatenate([sc["labels"]] * 3).astype(np.int32)
+    ses = InteractiveSession(model, voxel_size=0.02)
+    ses.load_scene(xyz, col, lab, name="bench")
+    n_full, n_qv = len(xyz), ses.raw_coords_qv.shape[0]
+    print(f"scene: {n_qv} voxels, {n_full} vertices")
+    inst = [i for i in np.unique(lab) if i > 0 and (lab == i).sum() > 200][:5]
+    palette_host = ses.palette
+    original = col.copy()
+    centre = xyz.mean(0)
+    result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
+    for n_clicks in (1, 5, 10, 20):
+        ses.reset()
+        objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
+        targets = [xyz[rng.choice(np.flatnonzero(lab == inst[o - 1]))] for o in objs]
+        for p, o in zip(targets[:-1], objs[:-1]):
+            ses.click(p, o)
+        base_state = ({k: list(v) for k, v in ses.click_idx.items()}, {k: list(v) for k, v in ses.click_time_idx.items()},
+                      {k: list(v) for k, v in ses.click_positions.items()}, ses.num_clicks,
+                      None if ses.new_labels is None else ses.new_labels.clone())
+        last_obj = objs[-1]
+        ts, tb = Timer(STAGES), Timer(BASE_STAGES)
+        whole_s, whole_b = [], []
+        for rep in range(a.warmup + a.reps):
+            tgt = xyz[rng.choice(np.flatnonzero(lab == inst[last_obj - 1]))]
+            direction = (tgt - (centre + np.array([0, 0, 3.0], np.float32))).astype(np.float64)
+            origin = tgt - 0.5 * direction / np.linalg.norm(direction)
+
+            def restore():
+                ses.click_idx, ses.click_time_idx, ses.click_positions = ({k: list(v) for k, v in base_state[0].items()},
+                                                                          {k: list(v) for k, v in base_state[1].items()},
+                                                                          {k: list(v) for k, v in base_state[2].items()})
+                ses.num_clicks = base_state[3]
+                if base_state[4] is not None:
+                    ses.new_labels = base_state[4].clone()
+
+            # ---- the session, stage by stage (the calls click() and infer() make)
+            restore()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            point = ts.run("pick", lambda: ses.pick(origin, direction))
+            point = tgt if point is None else point
+            q = np.asarray(point, np.float32)
+            rows = ts.run("nearest", lambda: ses.nearest(q))
+            key = str(last_obj)
+            if key not in ses.click_idx:
+                ses.click_idx[key], ses.click_time_idx[key], ses.click_positions[key] = [], [], []
+                ses.new_labels[ses.labels_full_ori == ses.labels_qv_ori[rows[0]]] = last_obj
+            ses.click_idx[key].append(rows[0])
+            ses.click_time_idx[key].append(ses.num_clicks)
+            ses.click_positions[key].append(ses._coords_host[rows[1]].tolist())
+            ses.num_clicks += 1
+            logits = ts.run("forward_mask", lambda: model.forward_mask(*ses._backbone, click_idx=[ses.click_idx],
+                                                                      click_time_idx=[ses.click_time_idx])["pred_masks"][0])
+            labels_qv = ts.run("argmax", lambda: K.argmax_labels(logits, ses.click_idx))
+
+            def paint_iou():
+                out = ses._launch_paint(labels_qv, False)
+                ses.lib.a3d_iou_counts(labels_qv.data_ptr(), labels_qv.shape[0], ses.inverse_map.data_ptr(), ses.new_labels.data_ptr(),
+                                       ses.new_labels.shape[0], 256, ses._counts.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                return out
+            ts.run("paint_iou", paint_iou)
+            ts.run("round_trip", lambda: ses._counts_host.copy_(ses._counts, non_blocking=True))
+            whole_s.append(1e3 * (time.perf_counter() - t0))
+
+            # ---- the torch / numpy recipe around the same forward_mask
+            restore()
+            ci = {k: list(v) for k, v in ses.click_idx.items()}
+            ct = {k: list(v) for k, v in ses.click_time_idx.items()}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+
+            def cdist2():
+                p = torch.tensor([[float(v) for v in q]]).to(ses.device)
+                r0 = torch.cdist(ses.raw_coords_qv, p, p=2).argmin().tolist()
+                r1 = torch.cdist(ses.coords_full, p, p=2).argmin().tolist()
+                return r0, ses.coords_full[r1].cpu().tolist()
+            r0, _pos = tb.run("nearest", cdist2)
+            ci.setdefault(key, []).append(r0)
+            ct.setdefault(key, []).append(ses.num_clicks)
+            blogits = tb.run("forward_mask", lambda: model.forward_mask(*ses._backbone, click_idx=[ci], click_time_idx=[ct])["pred_masks"][0])
+
+            def argmax_overwrite():
+                pred = blogits.argmax(1)
+                for obj_id, cids in ci.items():
+                    pred[cids] = int(obj_id)
+                return pred
+            pred = tb.run("argmax", argmax_overwrite)
+            pred_full = tb.run("lift", lambda: pred[ses.inverse_map])
+            host = tb.run("round_trip", lambda: pred_full.cpu().numpy())
+
+            def colour_loop():
+                colors = original.copy()
+                for obj_id in np.unique(host):
+                    if obj_id != 0:
+                        colors[host == obj_id] = palette_host[obj_id]
+                return colors
+            tb.run("colour_loop", colour_loop)
+            whole_b.append(1e3 * (time.perf_counter() - t0))
+        sd, sh = ts.medians(a.warmup)
+        bd, bh = tb.medians(a.warmup)
+        entry = {"session_device_ms": sd, "session_host_ms": sh, "baseline_device_ms": bd, "baseline_host_ms": bh,
+                 "session_click_ms": float(np.median(whole_s[a.warmup:])), "baseline_click_ms": float(np.median(whole_b[a.warmup:])),
+                 "queries": n_clicks + model.num_bg_queries}
+        entry["session_outside_forward_mask_host_ms"] = sum(v for k, v in sh.items() if k != "forward_mask")
+        entry["baseline_outside_forward_mask_host_ms"] = sum(v for k, v in bh.items() if k != "forward_mask")
+        result["clicks"][str(n_clicks)] = entry
+        print(f"\n== {n_clicks} click(s), {entry['queries']} queries: median of {a.reps} ==")
+        print("session   " + "  ".join(f"{k} {sd[k]:.3f}/{sh[k]:.3f}" for k in STAGES) + "   (device / host ms)")
+        print("baseline  " + "  ".join(f"{k} {bd[k]:.3f}/{bh[k]:.3f}" for k in BASE_STAGES))
+        print(f"outside forward_mask (host ms): session {entry['session_outside_forward_mask_host_ms']:.3f}  "
+              f"baseline {entry['baseline_outside_forward_mask_host_ms']:.3f}   forward_mask {sh['forward_mask']:.3f}")
+        print(f"whole click, staged (host ms): session {entry['session_click_ms']:.3f}  baseline {entry['baseline_click_ms']:.3f}")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+    print("RESULT " + json.dumps(result, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()
