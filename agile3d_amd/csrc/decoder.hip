@@ -92,6 +92,41 @@ constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kPointScoreScale = 0.25f * kLog2e;
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// ---- the leftover query tile of 17 .. 20 queries (k_kv_c2s<2, true>, k_s2c_out<2, .., LO = true>) ---------------------------
+// A 16-column MFMA on queries 16 .. 31 is 3/4 padding there.  v_mfma_f32_4x4x1_16B_f32 has the same FLOP rate at a row
+// granularity of 4: sixteen independent 4x4 blocks (block = lane / 4), one K-step per instruction, A row / B column =
+// lane % 4, D[row][col] = register row of lane 4 block + col; 2 passes against the 8 of a 16x16x4.  The operands the
+// 16-column products already hold are 4x4x1 operands as they stand: lane (g, j) of an A / B fragment register t is
+// channel (or point) 4 g + t of row j, so block (g, j / 4) multiplies rows 4 (j / 4) .. +3 over the K-steps 4 g .. 4 g + 3
+// -- a product is split over the four lane rows g and summed afterwards (scores, logits) or at the end of the kernel (P V
+// of click-to-scene), which changes the order of that sum: t inside a row, then the rows, instead of the rows inside an
+// instruction, then t.
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
+// reduce-scatter of four registers over the four lane rows: row g of the result holds the sum over the rows of register
+// kRowReg[g] = {0, 2, 1, 3}[g] -- each swap + add halves two registers at once (6 vector instructions, not 16)
+__device__ __forceinline__ float rows_sum_scatter(f32x4 s) {
+  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(s[0]), __float_as_uint(s[1]), false, false);
+  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(s[2]), __float_as_uint(s[3]), false, false);
+  const float r01 = __uint_as_float(a[0]) + __uint_as_float(a[1]);   // rows 0, 1: s[0] over (g, g ^ 2); rows 2, 3: s[1]
+  const float r23 = __uint_as_float(b[0]) + __uint_as_float(b[1]);
+  auto c = __builtin_amdgcn_permlane16_swap(__float_as_uint(r01), __float_as_uint(r23), false, false);
+  return __uint_as_float(c[0]) + __uint_as_float(c[1]);              // rows: s[0], s[2], s[1], s[3]
+}
+__device__ __forceinline__ int row_reg(int g) { return ((g & 1) << 1) | (g >> 1); }   // kRowReg, its own inverse
+// lane (row, j') of x for every lane: row is a compile-time constant at every use, so it lands in the instruction's offset field
+__device__ __forceinline__ float row_bcast(float x, int lane4, int row) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(lane4 + 64 * row, __float_as_int(x)));
+}
+// all-reduce over the four lanes l, l ^ 4, l ^ 8, l ^ 12 of a lane row (the four 4x4 blocks of a row)
+__device__ __forceinline__ float quads_max(float x) {
+  x = fmaxf(x, __shfl_xor(x, 4, 64));
+  return fmaxf(x, __shfl_xor(x, 8, 64));
+}
+__device__ __forceinline__ float quads_sum(float x) {
+  x += __shfl_xor(x, 4, 64);
+  return x + __shfl_xor(x, 8, 64);
+}
+
 // ------------------------------------------------------------------------------ posenc
 __global__ void __launch_bounds__(256) k_minmax_partial(const float* __restrict__ xyz, int n, float* part) {
   __shared__ float s[6][256];
@@ -490,7 +525,7 @@ __global__ void __launch_bounds__(512) k_c2s_attn_b(const DecSampleDev* __restri
 }
 
 
-// ---- K/V projections fused into the click-to-scene attention (<= 32 queries) ------------------------------
+// ---- K/V projections fused into the click-to-scene attention (<= 64 queries) ------------------------------
 // K = (src + pos) Wk^T + bk and V = src Wv^T + bv are produced per 16-point group straight into the MFMA
 // operand layouts the attention consumes and never reach HBM: the transposed product (weights as the A
 // operand) leaves K[point j][16h+4g..+3] in lane (g, j) = the A fragment of S = K_h q_h^T; the plain product
@@ -498,7 +533,13 @@ __global__ void __launch_bounds__(512) k_c2s_attn_b(const DecSampleDev* __restri
 // sit in LDS for the life of a persistent 8-wave workgroup; a wave walks its own sequence of 16-point groups,
 // head by head (one 16-column slice of each GEMM at a time), and keeps the flash state of all 8 heads in
 // registers.  Saves writing and re-reading K and V (4 x 41 MB per decoder iteration at 80 k points).
-template <int QT>
+// LO (QT = 2, every sample of the launch has 17 .. 20 queries): the second query tile is queries 16 .. 19 only and runs on
+// 4x4x1 MFMAs (see mfma4).  Scores: block (g, j / 4) = points 4 (j / 4) .. +3 x the four queries over channels 4 g .. +3,
+// reduce-scattered over g so that ONE register holds the 16 x 4 scores (point 4 (j / 4) + kRowReg[g], query j % 4) -- the
+// softmax upkeep of the tile is a quarter of a full tile's; the weights go to the P V operand layout (point 4 g + t of
+// query j % 4) through four ds_bpermute.  P V: block (g, j / 4) = channels 4 (j / 4) .. +3 x the queries over points
+// 4 g .. +3; the sum over g is taken once, when the workgroup writes its partial.
+template <int QT, bool LO = false>
 __global__ void __launch_bounds__(512) k_kv_c2s(const DecSampleDev* __restrict__ samples, int ns, int layer,
                                                 const float* __restrict__ Wk, const float* __restrict__ Wv,
                                                 const float* __restrict__ bk, const float* __restrict__ bv) {
@@ -508,6 +549,8 @@ __global__ void __launch_bounds__(512) k_kv_c2s(const DecSampleDev* __restrict__
   // register file).  48 / 64 queries double the state per head: four waves share a group, two heads each.  At 64 queries the
   // projected queries get [64][128] rows with the float4 column XOR-ed by the row (conflict-free b128 reads without the
   // 4-float pad) and the biases stay in registers: 128 KB of weights + 32 KB = exactly the 160 KB of LDS
+  static_assert(!LO || QT == 2, "the leftover-tile build is the two-tile kernel");
+  constexpr float kRefLazy = 8.f;   // log2 of how far a score may exceed the reference maximum before it moves
   constexpr int HW = QT <= 2 ? 4 : 2, WPG = H / HW, SPW = 8 / WPG;
   constexpr bool SWZ = QT == 4;
   constexpr int LDQ = SWZ ? 128 : 132;
@@ -566,9 +609,12 @@ __global__ void __launch_bounds__(512) k_kv_c2s(const DecSampleDev* __restrict__
   bool qmask[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    obj[qt] = gld(qobj + qt * 16 + j);
+    obj[qt] = gld(qobj + ((LO && qt == 1) ? 16 + (j & 3) : qt * 16 + j));
     qmask[qt] = labels != nullptr && obj[qt] >= 0 && gld(counts + obj[qt]) > 0;
   }
+  // LO: the point of a group whose score this lane holds after rows_sum_scatter, and the lane of row 0 that the P V operand
+  // is fetched relative to: point 4 g + t of query j % 4 sits in lane (row kRowReg[t], block g, j % 4)
+  const int lo_pt = (j & 12) + row_reg(g), lo_src = (4 * g + (j & 3)) * 4;
   __syncthreads();
   // WPG waves share a sequence of point groups, HW heads each
   const int h0 = (wave % WPG) * HW;
@@ -643,9 +689,10 @@ __global__ void __launch_bounds__(512) k_kv_c2s(const DecSampleDev* __restrict__
       }
     }
     // ---- attention of the 16 points against every query, flash-style running state per (head, query tile)
-    auto qfrag = [&](int qt, int h) {   // projected queries [16 qt + j][16 h + 4 g ..+3]
+    auto qfrag = [&](int qt, int h) {   // projected queries [16 qt + j][16 h + 4 g ..+3] (LO, second tile: [16 + j % 4])
       const int c = 4 * h + g;
-      return *(const f32x4*)(qp_l + (qt * 16 + j) * LDQ + (SWZ ? (c ^ j) : c) * 4);
+      const int r = (LO && qt == 1) ? 16 + (j & 3) : qt * 16 + j;
+      return *(const f32x4*)(qp_l + r * LDQ + (SWZ ? (c ^ j) : c) * 4);
     };
     f32x4 qf_n = qfrag(0, h0);   // the next tile's fragment, one tile ahead
     // which (point, query) pairs are blocked does not depend on the head: the mask is taken ONCE per group and query
@@ -661,6 +708,12 @@ __global__ void __launch_bounds__(512) k_kv_c2s(const DecSampleDev* __restrict__
         const bool blocked = pr >= n || (qmask[qt] && lab != obj[qt]);
         mb[qt][t] = blocked ? kNegBig : 0.f;
       }
+    float mb_lo = 0.f;   // LO: the same for the one score register of the second tile (its point's label byte from row lo_pt / 4)
+    if constexpr (LO) {
+      const unsigned labw = (unsigned)__shfl((int)lab4, 16 * (lo_pt >> 2), 64);
+      const int lab = (int)((labw >> (8 * (lo_pt & 3))) & 0xffu);
+      mb_lo = (p0 + lo_pt >= n || (qmask[1] && lab != obj[1])) ? kNegBig : 0.f;
+    }
 #pragma unroll
     for (int hl = 0; hl < HW; ++hl) {
       const int h = h0 + hl;
@@ -671,25 +724,48 @@ __global__ void __launch_bounds__(512) k_kv_c2s(const DecSampleDev* __restrict__
           const int i2 = hl * QT + qt + 1;
           if (i2 < HW * QT) qf_n = qfrag(i2 % QT, h0 + i2 / QT);
         }
+        if constexpr (LO) {
+          if (qt == 1) {
+            f32x4 s4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) s4 = mfma4(kf[hl][t], qf[t], s4);
+            const float sc1 = rows_sum_scatter(s4) + mb_lo;       // score of (point lo_pt, query 16 + j % 4)
+            if (__builtin_amdgcn_ballot_w64(sc1 - m[hl][1] > kRefLazy) != 0) {
+              const float mnew = fmaxf(m[hl][1], rows_max(quads_max(sc1)));
+              const float scl = exp2_fast(m[hl][1] - mnew);
+              m[hl][1] = mnew;
+              l[hl][1] *= scl;
+              acc[hl][1] *= scl;
+            }
+            const float pw1 = exp2_fast(sc1 - m[hl][1]);
+            l[hl][1] += pw1;                                      // this lane's share: summed over the 16 lanes of a query at the end
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              acc[hl][1] = mfma4(vv[hl][t], row_bcast(pw1, lo_src, row_reg(t)), acc[hl][1]);
+            }
+            continue;
+          }
+        }
         f32x4 sc4 = mb[qt];
 #pragma unroll
         for (int t = 0; t < 4; ++t) sc4 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[hl][t], qf[t], sc4, 0, 0, 0);
-        float mx = kNegBig;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) mx = fmaxf(mx, sc4[t]);
-        mx = rows_max(mx);
-        const float mnew = fmaxf(m[hl][qt], mx);
-        const float scl = exp2_fast(m[hl][qt] - mnew);
-        m[hl][qt] = mnew;
-        f32x4 pw;
-        float ps = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          pw[t] = exp2_fast(sc4[t] - mnew);
-          ps += pw[t];
+        // m is a REFERENCE maximum (the wide tier's scheme, decoder_wide.h): it moves, with the rescale of l and acc, only
+        // when some score of the wave exceeds it by more than 2^kRefLazy -- a wave-uniform, rarely taken branch instead of
+        // the max reduction, the correction's v_exp_f32 and five multiplies per (head, query tile, group).  The first
+        // group with an unblocked point takes the branch from m = kNegBig (scl = 0 wipes what blocked points left
+        // behind); a column that never sees one keeps m = kNegBig and weights of 1, as before.
+        const float mx4 = fmaxf(fmaxf(sc4[0], sc4[1]), fmaxf(sc4[2], sc4[3]));
+        if (__builtin_amdgcn_ballot_w64(mx4 - m[hl][qt] > kRefLazy) != 0) {
+          const float mnew = fmaxf(m[hl][qt], rows_max(mx4));
+          const float scl = exp2_fast(m[hl][qt] - mnew);
+          m[hl][qt] = mnew;
+          l[hl][qt] *= scl;
+          acc[hl][qt] *= scl;
         }
-        l[hl][qt] = l[hl][qt] * scl + ps;
-        acc[hl][qt] *= scl;
+        f32x4 pw;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) pw[t] = exp2_fast(sc4[t] - m[hl][qt]);
+        l[hl][qt] += (pw[0] + pw[1]) + (pw[2] + pw[3]);
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[hl][qt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[hl][t], pw[t], acc[hl][qt], 0, 0, 0);
       }
@@ -736,6 +812,23 @@ __global__ void __launch_bounds__(512) k_kv_c2s(const DecSampleDev* __restrict__
           for (int t = 0; t < 4; ++t) aa[t] = aa[t] * sa + r[128 + 64 * t] * sb;
         }
         const int h = h0 + hl;
+        if constexpr (LO) {
+          if (qt == 1) {   // lane (g, j): channels 4 (j / 4) .. +3 of query 16 + j % 4, a fourth of the points each
+            const float lt = rows_sum(quads_sum(ll));
+            float* pq = part + (((size_t)h * qp_total + 16 + (j & 3)) * nwg + lb) * kPartStride;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) aa[t] = rows_sum(aa[t]);
+            if (g == 0) {
+              if (j < 4) {
+                gst(pq, mm);
+                gst(pq + 1, lt);
+              }
+#pragma unroll
+              for (int t = 0; t < 4; ++t) gst(pq + 2 + (j & 12) + t, aa[t]);
+            }
+            continue;
+          }
+        }
         const float lt = rows_sum(ll);
         float* pq = part + (((size_t)h * qp_total + qt * 16 + j) * nwg + lb) * kPartStride;
         if (g == 0) {
@@ -1293,12 +1386,21 @@ __global__ void __launch_bounds__(512) k_out_ln_mask(const DecSampleDev* __restr
 // MFMAs) instead of LDS -- the build for 25..32 queries, where keys + transposed values + both weight matrices do not fit
 // QC: the queries of the layer from the scene's cache (as k_q_s2c<.., QC>): the Q projection -- 256 of a group's ~700 MFMAs -- and
 // the read of the position encodings are skipped
-template <int QT, int NW, bool KG = false, bool QC = false>
+// LO (QT = 2, keys in LDS, every sample of the launch has 17 .. 20 queries): queries 16 .. 19 run on 4x4x1 MFMAs (see mfma4).
+// Scores and logits: block (g, j / 4) = the four queries x points 4 (j / 4) .. +3 over channels 4 g .. +3 (of the head /
+// of every 16-channel step), reduce-scattered over g: lane (g, j) ends up with ONE score / logit of point j, that of
+// query 16 + kRowReg[g], where the full tile leaves it four of which twelve are padding.  P V: block (g, j / 4) = channels
+// 4 g .. +3 x points 4 (j / 4) .. +3, one query per instruction, straight onto the accumulator of the first tile.
+// last: the layer is the decoder's last -- nothing reads its output rows, label bytes or label histogram (they live in
+// the call's workspace; the caller sees the logits), so they are not stored.
+template <int QT, int NW, bool KG = false, bool QC = false, bool LO = false>
 __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restrict__ samples, int ns, int layer,
                                                  const float* __restrict__ Wq, const float* __restrict__ bq,
                                                  const float* __restrict__ Wo, const float* __restrict__ bo,
                                                  const float* __restrict__ gamma, const float* __restrict__ beta, int nqr_max,
-                                                 int Kmax) {
+                                                 int Kmax, int last) {
+  static_assert(!LO || (QT == 2 && !KG), "the leftover-tile build is the two-tile kernel with the keys in LDS");
+  constexpr int QF = LO ? 1 : QT;         // full 16-query tiles
   constexpr int LD = 136, NT = NW * 64;   // 136: the key fragments' ds_read_b128 (row 16 kt + j, floats 16 h + 4 g ..) are bank-
                                           // conflict-free ((8 j + 4 g) mod 64 distinct inside a 16-lane service group; 132 was 2-way)
   constexpr bool PF = NW == 8;   // register prefetch of the next group
@@ -1380,9 +1482,9 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
   //          score and head; read from LDS: eight more registers spill the twelve-wave build);
   //   oidp:  the object of each of this lane's QT x 4 query slots, one byte each (255 = padded): the per-object maximum
   //          of the logits is one SDWA byte compare + select + max per slot.
-  unsigned oidp[QT];
+  unsigned oidp[QF];
 #pragma unroll
-  for (int kt = 0; kt < QT; ++kt) {
+  for (int kt = 0; kt < QF; ++kt) {
     oidp[kt] = 0u;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -1395,6 +1497,21 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
       }
       oidp[kt] |= o << (8 * t);
     }
+  }
+  // LO: the query 16 + kRowReg[g] whose score / logit this lane holds after rows_sum_scatter, its score bias and object,
+  // and the LDS addresses of the tile's operands (the P V operand of query 16 + t is lane j of row kRowReg[t])
+  float sb_lo = 0.f;
+  unsigned oid_lo = 255u, ks_lo0 = 0u, vt_lo0 = 0u;
+  if constexpr (LO) {
+    const int q = 16 + row_reg(g);
+    sb_lo = q < nq ? 0.f : kNegBig;
+    if (q < nq) {
+      oid_lo = 0u;
+      for (int oo = 1; oo <= K; ++oo)
+        if (q >= qr_l[oo] && q < qr_l[oo + 1]) oid_lo = (unsigned)oo;
+    }
+    ks_lo0 = (unsigned)(size_t)ks_l + (unsigned)((16 + (j & 3)) * LD + 4 * g) * 4u;   // key row 16 + j % 4, floats 4 g ..
+    vt_lo0 = (unsigned)(size_t)vt_l + (unsigned)((4 * g + (j & 3)) * LT + 16) * 4u;   // value channel 4 g + j % 4, keys 16 .. 19
   }
   f32x4 nx[8], np[8];
   auto fetch = [&](int gq) {
@@ -1444,7 +1561,7 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
 #pragma unroll
       for (int u = 0; u < 2; ++u) qf[u] = *(const f32x4*)(bq_l + 16 * (h + u) + 4 * g);   // Q[point j][16h+4g..+3]
       }
-      f32x4 kfg[2][QT];
+      f32x4 kfg[2][QF];
       if constexpr (KG) {
 #pragma unroll
         for (int kt = 0; kt < QT; ++kt)
@@ -1473,12 +1590,21 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
           w1 = n1;
         }
       }
-      f32x4 sc[2][QT];
+      f32x4 sc[2][QF];
       float mx[2] = {kNegBig, kNegBig};
+      float s1[2] = {0.f, 0.f};           // LO: score, then weight, of (query 16 + ri, point j)
       {
-        f32x4 kf[2][QT];
+        f32x4 kf[2][QF];
+        f32x4 kl[2], s4[2];
+        if constexpr (LO) {
 #pragma unroll
-        for (int kt = 0; kt < QT; ++kt)
+          for (int u = 0; u < 2; ++u) {
+            kl[u] = lds4(ks_lo0 + (unsigned)((h + u) * DH) * 4u);
+            s4[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          }
+        }
+#pragma unroll
+        for (int kt = 0; kt < QF; ++kt)
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
             if constexpr (KG) kf[u][kt] = kfg[u][kt];
@@ -1486,16 +1612,28 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
             sc[u][kt] = *(const f32x4*)(sb_l + kt * 16 + 4 * g);
           }
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < 4; ++t) {
 #pragma unroll
-          for (int kt = 0; kt < QT; ++kt)
+          for (int kt = 0; kt < QF; ++kt)
 #pragma unroll
             for (int u = 0; u < 2; ++u) sc[u][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[u][kt][t], qf[u][t], sc[u][kt], 0, 0, 0);
+          if constexpr (LO) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) s4[u] = mfma4(kl[u][t], qf[u][t], s4[u]);
+          }
+        }
+        if constexpr (LO) {
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            s1[u] = rows_sum_scatter(s4[u]) + sb_lo;
+            mx[u] = s1[u];
+          }
+        }
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int kt = 0; kt < QT; ++kt)
+        for (int kt = 0; kt < QF; ++kt)
 #pragma unroll
           for (int t = 0; t < 4; ++t) mx[u] = fmaxf(mx[u], sc[u][kt][t]);   // padded queries sit at kNegBig (sb_l)
       float inv[2];
@@ -1504,12 +1642,16 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
         mx[u] = rows_max(mx[u]);
         float sum = 0.f;
 #pragma unroll
-        for (int kt = 0; kt < QT; ++kt)
+        for (int kt = 0; kt < QF; ++kt)
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             sc[u][kt][t] = exp2_fast(sc[u][kt][t] - mx[u]);
             sum += sc[u][kt][t];
           }
+        if constexpr (LO) {
+          s1[u] = exp2_fast(s1[u] - mx[u]);
+          sum += s1[u];
+        }
         sum = rows_sum(sum);
         inv[u] = __builtin_amdgcn_rcpf(sum);
       }
@@ -1517,17 +1659,33 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
       // the first output-projection fragments are requested before the P V products, every later pair one step ahead
       f32x4 wo0 = lds4(wo_a), wo1 = lds4(wo_a + 64 * 16);
       {
-        f32x4 vf[2][QT];
+        f32x4 vf[2][QF];
+        f32x4 vl[2];
+        float pl[2][4];
+        if constexpr (LO) {
 #pragma unroll
-        for (int kt = 0; kt < QT; ++kt)
+          for (int u = 0; u < 2; ++u) {
+            vl[u] = lds4(vt_lo0 + (unsigned)((h + u) * DH * LT) * 4u);   // V^T: keys 16 .. 19 of channel 16 (h + u) + 4 g + j % 4
+#pragma unroll
+            for (int t = 0; t < 4; ++t) pl[u][t] = row_bcast(s1[u], j * 4, row_reg(t));
+          }
+        }
+#pragma unroll
+        for (int kt = 0; kt < QF; ++kt)
 #pragma unroll
           for (int u = 0; u < 2; ++u) vf[u][kt] = lds4((u ? vt_a1 : vt_a) + kt * 64);   // V^T: keys 4g..4g+3 of channel 16h+j
 #pragma unroll
-        for (int kt = 0; kt < QT; ++kt)
+        for (int kt = 0; kt < QF; ++kt)
 #pragma unroll
           for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int u = 0; u < 2; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[u][kt][t], sc[u][kt][t], acc[u], 0, 0, 0);
+        if constexpr (LO) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) acc[u] = mfma4(vl[u][t], pl[u][t], acc[u]);
+        }
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u) acc[u] *= inv[u];   // the softmax normaliser once per output instead of once per weight
@@ -1576,34 +1734,57 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
       const f32x4 be = *(const f32x4*)(be_l + 16 * ct + 4 * g);
 #pragma unroll
       for (int t = 0; t < 4; ++t) y[ct][t] = (y[ct][t] - mean) * rstd * ga[t] + be[t];
-      if (p0 + j < n) gst4(yrow + 16 * ct + 4 * g, y[ct]);
+      if (!last && p0 + j < n) gst4(yrow + 16 * ct + 4 * g, y[ct]);
     }
     // mask embeddings of the queries as A fragments of the transposed logits product, E[query 16 qt + j][16 S + 4 g ..+3]:
     // re-read per group (16 KB, cache resident; requested behind the next group's rows, which went out three heads ago) --
     // held in registers for the whole group they cost 64 registers next to xp, y and the prefetch (spills)
-    f32x4 ef[QT][8];
+    f32x4 ef[QF][8];
 #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
+    for (int qt = 0; qt < QF; ++qt) {
       const float* er = sm.E + (size_t)min(qt * 16 + j, nq - 1) * D + 4 * g;
 #pragma unroll
       for (int S = 0; S < 8; ++S) ef[qt][S] = gld4(er + 16 * S);
     }
     // logits^T: lg[qt][t] = logit of query 16 qt + 4 g + t for point j (rows >= nq repeat the last query: never selected)
     // (even / odd K-steps on separate accumulators, query tiles interleaved: no back-to-back dependent MFMAs)
-    f32x4 lg[QT], lg2[QT];
+    f32x4 lg[QF], lg2[QF];
 #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) lg[qt] = lg2[qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int qt = 0; qt < QF; ++qt) lg[qt] = lg2[qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // LO: E[query 16 + j % 4][16 S + 4 g ..+3], requested a step pair ahead; l1 = logit of query 16 + ri for point j
+    f32x4 ll4 = (f32x4){0.f, 0.f, 0.f, 0.f}, ll4b = ll4, el[2] = {ll4, ll4};
+    const float* erl = nullptr;
+    if constexpr (LO) {
+      erl = sm.E + (size_t)min(16 + (j & 3), nq - 1) * D + 4 * g;
+      el[0] = gld4(erl);
+      el[1] = gld4(erl + 16);
+    }
 #pragma unroll
-    for (int S = 0; S < 8; S += 2)
+    for (int S = 0; S < 8; S += 2) {
+      f32x4 e0 = el[0], e1 = el[1];
+      if constexpr (LO) {
+        if (S + 2 < 8) {
+          el[0] = gld4(erl + 16 * (S + 2));
+          el[1] = gld4(erl + 16 * (S + 3));
+        }
+      }
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+      for (int t = 0; t < 4; ++t) {
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
+        for (int qt = 0; qt < QF; ++qt) {
           lg[qt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ef[qt][S][t], y[S][t], lg[qt], 0, 0, 0);
           lg2[qt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ef[qt][S + 1][t], y[S + 1][t], lg2[qt], 0, 0, 0);
         }
+        if constexpr (LO) {
+          ll4 = mfma4(e0[t], y[S][t], ll4);
+          ll4b = mfma4(e1[t], y[S + 1][t], ll4b);
+        }
+      }
+    }
 #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) lg[qt] += lg2[qt];
+    for (int qt = 0; qt < QF; ++qt) lg[qt] += lg2[qt];
+    float l1 = 0.f;
+    if constexpr (LO) l1 = rows_sum_scatter(ll4 + ll4b);
     // per-object max over the object's queries (k_out_ln_mask's order of comparisons: ascending query index; max is
     // order-independent), first-max argmax over the objects
     float best = 0.f;
@@ -1611,10 +1792,13 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
     for (int o = 0; o <= K; ++o) {
       float mxv = -3.4e38f;
 #pragma unroll
-      for (int qt = 0; qt < QT; ++qt)
+      for (int qt = 0; qt < QF; ++qt)
 #pragma unroll
         for (int t = 0; t < 4; ++t)
           if (((oidp[qt] >> (8 * t)) & 255u) == (unsigned)o) mxv = fmaxf(mxv, lg[qt][t]);
+      if constexpr (LO) {
+        if (oid_lo == (unsigned)o) mxv = fmaxf(mxv, l1);
+      }
       mxv = rows_max(mxv);
       if (g == (o & 3)) Ow[j * (K + 1) + o] = mxv;
       if (o == 0 || mxv > best) {
@@ -1622,7 +1806,7 @@ __global__ void __launch_bounds__(NW * 64) k_s2c_out(const DecSampleDev* __restr
         bi = o;
       }
     }
-    if (g == 0 && p0 + j < n) {
+    if (!last && g == 0 && p0 + j < n) {
       gst(labels + p0 + j, (unsigned char)bi);
       atomicAdd(&hist[bi], 1);
     }
@@ -2938,6 +3122,9 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
       A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, false, true>));
       A3D_ALLOW_LDS(big_lds, (k_s2c_out<1, 12, true, true>));
       A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, true, true>));
+      A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, false, false, true>));
+      A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, false, true, true>));
+      A3D_ALLOW_LDS(big_lds, (k_kv_c2s<2, true>));
       A3D_ALLOW_LDS(big_lds, k_kv_c2s<1>);
       A3D_ALLOW_LDS(big_lds, k_kv_c2s<2>);
       A3D_ALLOW_LDS(big_lds, k_kv_c2s<3>);
@@ -2947,13 +3134,17 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
   }
   const int n_counts = A3D_MAX_DEC_LAYERS * (A3D_MAX_QUERIES + 1);
   int64_t n_total = 0;
-  int Kmax = 0, nq_max = 0;
+  int Kmax = 0, nq_max = 0, nq_min = A3D_MAX_QUERIES;
   for (int si = 0; si < ns; ++si) {
     Prepared& p = P[si];
     n_total += p.n;
     Kmax = p.hm.K > Kmax ? p.hm.K : Kmax;
     nq_max = p.hm.nq > nq_max ? p.hm.nq : nq_max;
+    nq_min = p.hm.nq < nq_min ? p.hm.nq : nq_min;
   }
+  // every sample of the launch has 17 .. 20 queries: the second query tile is at most four queries wide and runs on the
+  // 4x4x1 builds of k_kv_c2s / k_s2c_out
+  const bool leftover = QT == 2 && nq_min >= 17 && nq_max <= 20;
   const size_t s2c_lds = (size_t)2 * QP * 132 * 4;             // keys + values of the queries (k_s2c_attn_wide)
   const size_t qs2c_lds = ((size_t)QP * 132 + (size_t)D * (QP + 4) + D) * 4;   // k_q_s2c: keys, transposed values, bias
   const size_t fused_lds = (size_t)64 * 1024 + ((size_t)3 * D + QP * 132 + 8 * 16 * (QP + 1) + 8 * 16 * (Kmax + 1)) * 4 +
@@ -3040,8 +3231,12 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
       // K / V projections fused in (K, V never reach HBM), all samples in one launch
       ProfScope ps(st, A3D_PROF_C2S, 0, 0, 0, 0, (int)n_total);
       const size_t c2s_lds = (size_t)128 * 1024 + (QT == 4 ? (size_t)QP * 128 * 4 : ((size_t)QP * 132 + 2 * D) * 4);
-      k_kv_c2s<QT><<<grid, 512, c2s_lds, st>>>(samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D,
-                                               LW.c2s_in_b + 2 * D);
+      if (QT == 2 && leftover)
+        k_kv_c2s<2, true><<<grid, 512, c2s_lds, st>>>(samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D,
+                                                      LW.c2s_in_b + 2 * D);
+      else
+        k_kv_c2s<QT><<<grid, 512, c2s_lds, st>>>(samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D,
+                                                 LW.c2s_in_b + 2 * D);
       A3D_LAUNCH_CHECK();
     } else {
       for (int si = 0; si < ns; ++si) {
@@ -3066,25 +3261,32 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
     if (fuse_all) {
       // the whole half in one pass: O never reaches HBM (k_s2c_out)
       ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, (int)n_total);
+      const int last = l + 1 == w->n_layers;   // nothing reads the last layer's rows, label bytes and histogram
       if constexpr (QT <= 2) {
-        if (qc0 && s2c_kg && s2c_out_lds12 <= 160 * 1024)
+        if (leftover && qc0 && !s2c_kg && s2c_out_lds12 <= 160 * 1024)
+          k_s2c_out<2, 12, false, true, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
+                                                                               LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
+        else if (leftover && !qc0 && !s2c_kg && s2c_out_lds12 <= 160 * 1024)
+          k_s2c_out<2, 12, false, false, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
+                                                                                LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
+        else if (qc0 && s2c_kg && s2c_out_lds12 <= 160 * 1024)
           k_s2c_out<QT, 12, true, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                         LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax);
+                                                                         LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
         else if (qc0 && !s2c_kg && s2c_out_lds12 <= 160 * 1024)
           k_s2c_out<QT, 12, false, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                          LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax);
+                                                                          LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
         else if (s2c_kg && s2c_out_lds12 <= 160 * 1024)
           k_s2c_out<QT, 12, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                   LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax);
+                                                                   LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
         else if (s2c_kg)
           k_s2c_out<QT, 8, true><<<grid, 512, s2c_out_lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax);
+                                                                LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
         else if (s2c_out_lds12 <= 160 * 1024)   // twelve waves (three per SIMD) when their logits staging fits, else eight
           k_s2c_out<QT, 12><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                             LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax);
+                                                             LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
         else
           k_s2c_out<QT, 8><<<grid, 512, s2c_out_lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                          LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax);
+                                                          LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
       }
       A3D_LAUNCH_CHECK();
       continue;
