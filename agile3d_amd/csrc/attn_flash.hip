@@ -626,6 +626,14 @@ static int fl_check(const char* what, const void* a, const void* b, const void* 
   return A3D_OK;
 }
 
+// One key: the softmax is the constant 1, so dq and dk vanish identically.  The kernels compute them as P (dP - D) with dP and
+// D = rowsum(dO o O) two differently rounded sums of the same 16 products: ~1e-6 of noise where the materialised path
+// (attn_train.hip) and autograd return exact zeros.  The backward entry points write the zeros; dv is the kernels'.
+static void fl_single_key_zeros(float* dq_dev, int64_t Lq, float* dk_dev, hipStream_t st) {
+  (void)hipMemsetAsync(dq_dev, 0, (size_t)Lq * FD * sizeof(float), st);
+  (void)hipMemsetAsync(dk_dev, 0, (size_t)FD * sizeof(float), st);
+}
+
 // the same kernels' launch with (drop) or without the dropout arguments: the DROP = false build keeps the kernel of the code
 // without dropout, argument block included
 template <int QT, bool DROP>
@@ -687,6 +695,7 @@ static int fl_c2s_backward(const char* what, const float* q_scaled_dev, const fl
     k_fl_c2s_bwd<false><<<G, 512, 0, st>>>(q_scaled_dev, k_dev, v_dev, mask_dev, (int)Lq, (int)Lk, stats_dev, Ds, d_o_dev, dqp, dk_dev,
                                     dv_dev);
   fl_reduce(dqp, G, (int)Lq, tmp, dq_scaled_dev, st);
+  if (Lk == 1) fl_single_key_zeros(dq_scaled_dev, Lq, dk_dev, st);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -786,6 +795,7 @@ static int fl_s2c_backward(const char* what, const float* q_scaled_dev, const fl
                                     dvp);
   fl_reduce(dkp, G, (int)Lk, tmp, dk_dev, st);
   fl_reduce(dvp, G, (int)Lk, tmp, dv_dev, st);
+  if (Lk == 1) fl_single_key_zeros(dq_scaled_dev, Lq, dk_dev, st);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

@@ -1,0 +1,341 @@
+"""-m gpu: the flash attention kernels of the training path (csrc/attn_flash.hip) on the branches the other flash tests never
+reach, each against float64 autograd of the plain formula on the CPU:
+
+  * the persistent walk: more than 256 chunks of 64 points, so that a workgroup takes chunks wg, wg + 256, ... -- the
+    c2s forward's prefetch across a chunk boundary and its online-softmax state carried from chunk to chunk, the
+    read-modify-write of the dQ slabs (c2s) and of the dK / dV slabs (s2c), the Philox counters of the dropout builds on a
+    second chunk, the slab reduction over 256 slabs;
+  * every build of the c2s forward (QT = 2, 4, 6, 8, 10, 14 query tiles) and its second launch for 225 .. 256 queries;
+  * short sides: fewer keys than one chunk / one group, a single key, a single query, 256 keys on the short side of s2c;
+  * the decoder tape on a scene long enough to walk, flash against materialised scores.
+
+Every input is seeded; nothing is read from disk.  The bar is the one of the other flash tests: max|diff| <= 2e-5 of the
+reference's largest magnitude, per output.  Workspaces and outputs start out as NaN: a slab element that is read before
+the walk's first chunk wrote it, or an output row nothing writes, fails the comparison instead of passing on zeros."""
+import ctypes as C
+import functools
+
+import pytest
+import torch
+
+from agile3d_amd import lib as L
+from dropout_ref import scale as drop_scale
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda")
+CHUNK = 64                 # points per chunk (kFlChunk)
+CAP = 256                  # workgroups of the persistent kernels; _assert_walks checks it against the library
+TOL = 2e-5
+P_DROP, SEED = 0.1, 0x0bad_cafe_4321
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _nan(*shape):
+    return torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
+
+
+def _workspace(nbytes):
+    return torch.full((nbytes,), 255, dtype=torch.uint8, device=DEV)        # 0xff bytes: NaN as floats
+
+
+def zmat(seed, sample, site, p, heads, rows, cols):
+    """Z = keep / (1 - p) in float64, from the library's mask (pinned on the numpy restatement in test_gpu_dropout.py)."""
+    out = torch.empty((heads, rows, cols), dtype=torch.uint8, device=DEV)
+    L.check(L.load().a3d_dropout_mask(seed, sample, site, p, heads, rows, cols, _ptr(out), _stream()), "a3d_dropout_mask")
+    return out.cpu().double() * drop_scale(p)
+
+
+# ---------------------------------------------------------------------------------------------------- reference
+def _mha_ref(q, k, v, w, mask, Z=None, per_head=False):
+    """softmax(q k^T / 4 + mask) (o Z) v per head (8 x 16) in float64 on the CPU, autograd for the loss sum(o * w):
+    (o, dq, dk, dv).  ``per_head``: one head at a time (16-channel slices, written back), for the cases whose [8, Lq, Lk]
+    float64 matrices would take gigabytes."""
+    Lq, Lk = q.shape[0], k.shape[0]
+    q64, k64, v64, w64 = (t.double() for t in (q, k, v, w))
+    blocked = mask.bool()[None] if mask is not None else None
+    o, dq = torch.empty(Lq, 128, dtype=torch.float64), torch.empty(Lq, 128, dtype=torch.float64)
+    dk, dv = torch.empty(Lk, 128, dtype=torch.float64), torch.empty(Lk, 128, dtype=torch.float64)
+    nh = 1 if per_head else 8
+    for h0 in range(0, 8, nh):
+        sl = slice(16 * h0, 16 * (h0 + nh))
+        qh, kh, vh = (t[:, sl].clone().requires_grad_(True) for t in (q64, k64, v64))
+        s = torch.einsum("ihd,jhd->hij", qh.view(Lq, nh, 16), kh.view(Lk, nh, 16)) / 4.0
+        if blocked is not None:
+            s = s.masked_fill(blocked, float("-inf"))
+        p = torch.softmax(s, -1)
+        if Z is not None:
+            p = p * Z[h0:h0 + nh]
+        oh = torch.einsum("hij,jhd->ihd", p, vh.view(Lk, nh, 16)).reshape(Lq, 16 * nh)
+        (oh * w64[:, sl]).sum().backward()
+        o[:, sl], dq[:, sl], dk[:, sl], dv[:, sl] = oh.detach(), qh.grad, kh.grad, vh.grad
+    return o, dq, dk, dv
+
+
+def _check(tag, got, want, tol=TOL):
+    errs = []
+    for name, g, r in zip(("o", "dq", "dk", "dv"), got, want):
+        err = (g.double().cpu() - r).abs().max().item()
+        sc = max(1e-6, r.abs().max().item())
+        print(f"{tag} {name}: max|diff| {err:.2e} (scale {sc:.2e}) -> {err / sc:.2e}")
+        errs.append((name, err, sc))
+    for name, err, sc in errs:
+        assert err <= tol * sc, (tag, name, err, sc)          # (a NaN fails: the comparison is False)
+
+
+# ---------------------------------------------------------------------------------------------------- inputs
+@functools.lru_cache(maxsize=None)
+def _qkvw(Lq, Lk, seed):
+    """randn q [Lq, 128], k, v [Lk, 128], w [Lq, 128]; shared between the tests of one shape, never modified."""
+    g = torch.Generator().manual_seed(seed)
+    q, k, v = (torch.randn(n, 128, generator=g) for n in (Lq, Lk, Lk))
+    return q, k, v, torch.randn(Lq, 128, generator=g)
+
+
+def _random_mask(Lq, Lk, seed):
+    """60 % blocked, one random key per row opened: no row fully blocked (the reference's mask_module guarantees that)."""
+    g = torch.Generator().manual_seed(seed + 1)
+    mask = torch.rand(Lq, Lk, generator=g) < 0.6
+    mask[torch.arange(Lq), torch.randint(0, Lk, (Lq,), generator=g)] = False
+    assert (~mask).any(1).all()
+    return mask.to(torch.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def _structured_mask(Lq, Lk, seed):
+    """The 60 % random mask of the long cases with four rows that pin the walk:
+    query 0: every key of the chunks 0, 256, 512, ... blocked -- workgroup 0's partial is the empty state (m = -1e30, l = 0);
+    query 1: every key of chunk 1 blocked, chunk 257 random -- workgroup 1 carries the empty state across its first chunk
+             and opens it on its second;
+    query 2: only the last key open;   query 3: only key 0 open."""
+    g = torch.Generator().manual_seed(seed + 1)
+    mask = torch.rand(Lq, Lk, generator=g) < 0.6
+    nchunk = (Lk + CHUNK - 1) // CHUNK
+    assert Lq >= 4 and nchunk > CAP + 1
+    for c in range(0, nchunk, CAP):
+        mask[0, c * CHUNK:(c + 1) * CHUNK] = True
+    mask[1, CHUNK:2 * CHUNK] = True
+    mask[2] = True
+    mask[2, Lk - 1] = False
+    mask[3] = True
+    mask[3, 0] = False
+    assert (~mask).any(1).all()                                       # every row keeps an open key
+    assert (~mask[1, (CAP + 1) * CHUNK:(CAP + 2) * CHUNK]).any()      # ... query 1 one in workgroup 1's second chunk
+    return mask.to(torch.uint8)
+
+
+def _assert_walks(workspace_bytes, long_side, *args):
+    """The case reaches the persistent walk: beyond the cap the workspace (one slab per workgroup) stops growing, below it
+    it is smaller.  A change of the cap fails here instead of quietly leaving the branch untested."""
+    def nbytes(n):
+        return workspace_bytes(*[n if a is None else a for a in args])
+    assert long_side > CAP * CHUNK
+    assert nbytes(CAP * CHUNK) == nbytes(long_side)
+    assert nbytes((CAP - 1) * CHUNK) < nbytes(CAP * CHUNK)
+
+
+# ---------------------------------------------------------------------------------------------------- the kernels
+def _flash_c2s(q, k, v, w, mask, drop=None, twice=False):
+    """a3d_flash_c2s_forward + _backward (their _dropout twins with ``drop``): o, dq, dk, dv of the unscaled operands."""
+    lib = L.load()
+    Lq, Lk = q.shape[0], k.shape[0]
+    qs, kd, vd, wd = (q * 0.25).to(DEV), k.to(DEV), v.to(DEV), w.to(DEV)
+    md = mask.to(DEV).contiguous() if mask is not None else None
+    nb = lib.a3d_flash_c2s_workspace_bytes(Lq, Lk)
+    ws = _workspace(nb)
+    o, stats = _nan(Lq, 128), _nan(2, 8, Lq)
+    if drop is None:
+        L.check(lib.a3d_flash_c2s_forward(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws), nb,
+                                          _stream()), "fwd")
+    else:
+        L.check(lib.a3d_flash_c2s_forward_dropout(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws),
+                                                  nb, drop, _stream()), "fwd")
+
+    def backward():
+        dq, dk, dv = _nan(Lq, 128), _nan(Lk, 128), _nan(Lk, 128)
+        if drop is None:
+            L.check(lib.a3d_flash_c2s_backward(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd),
+                                               _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nb, _stream()), "bwd")
+        else:
+            L.check(lib.a3d_flash_c2s_backward_dropout(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats),
+                                                       _ptr(wd), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nb, drop, _stream()), "bwd")
+        return dq, dk, dv
+    ws.fill_(255)                           # the backward's slabs share the forward's partials: nothing of them may be read
+    dq, dk, dv = backward()
+    if twice:                               # deterministic, and on a workspace that holds the first run's slabs
+        dq2, dk2, dv2 = backward()
+        assert torch.equal(dq, dq2) and torch.equal(dk, dk2) and torch.equal(dv, dv2)
+    return o, dq * 0.25, dk, dv
+
+
+def _flash_s2c(q, k, v, w, drop=None):
+    """a3d_flash_s2c_forward + _backward (their _dropout twins with ``drop``); the 1 / 4 goes on the few keys, as on the tape."""
+    lib = L.load()
+    Lq, Lk = q.shape[0], k.shape[0]
+    qd, ks, vd, wd = q.to(DEV), (k * 0.25).to(DEV), v.to(DEV), w.to(DEV)
+    o, stats = _nan(Lq, 128), _nan(Lq, 8, 2)
+    nb = lib.a3d_flash_s2c_workspace_bytes(Lq, Lk)
+    ws = _workspace(nb)
+    dq, dk, dv = _nan(Lq, 128), _nan(Lk, 128), _nan(Lk, 128)
+    if drop is None:
+        L.check(lib.a3d_flash_s2c_forward(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _stream()), "fwd")
+        L.check(lib.a3d_flash_s2c_backward(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd), _ptr(dq),
+                                           _ptr(dk), _ptr(dv), _ptr(ws), nb, _stream()), "bwd")
+    else:
+        L.check(lib.a3d_flash_s2c_forward_dropout(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), drop, _stream()),
+                "fwd")
+        L.check(lib.a3d_flash_s2c_backward_dropout(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd), _ptr(dq),
+                                                   _ptr(dk), _ptr(dv), _ptr(ws), nb, drop, _stream()), "bwd")
+    return o, dq, dk * 0.25, dv
+
+
+# ---------------------------------------------------------------------------------------------------- c2s
+@pytest.mark.parametrize("Lq,Lk,masked", [(20, 16485, True), (37, 32961, True), (5, 16400, False), (225, 16485, True)],
+                         ids=["A-20x16485", "B-37x32961", "C-5x16400-nomask", "D-225x16485"])
+def test_c2s_workgroups_walk_several_chunks(Lq, Lk, masked):
+    """Click-to-scene over more than 256 chunks of keys: forward and backward (the backward twice, bit-identical).
+    A: workgroups 0 and 1 take two chunks, the last chunk holds 37 keys (two full groups + 5) and the mask's rows are not a
+    multiple of four bytes; B: three chunks per workgroup, a last chunk of one key; C: no mask, fewer queries than a tile;
+    D: the 14-tile build and the second launch (q0 = 224, one query) both walking."""
+    _assert_walks(L.load().a3d_flash_c2s_workspace_bytes, Lk, Lq, None)
+    seed = Lq * 7 + Lk
+    q, k, v, w = _qkvw(Lq, Lk, seed)
+    mask = _structured_mask(Lq, Lk, seed) if masked else None
+    want = _mha_ref(q, k, v, w, mask, per_head=Lq > 100)
+    got = _flash_c2s(q, k, v, w, mask, twice=True)
+    _check(f"flash c2s walk {Lq}x{Lk}", got, want)
+
+
+@pytest.mark.parametrize("Lq", [1, 16, 17, 80, 96, 97, 128, 160, 161, 224, 225, 256])
+def test_c2s_every_forward_build(Lq):
+    """Every build of k_fl_c2s_fwd by tile count -- QT = 2 (1, 16, 17 queries), 6 (80, 96), 8 (97, 128), 10 (160), 14 (161,
+    224) -- and the second launch at q0 = 224 (225, 256 queries: one query, two full tiles), over 700 keys; masked for
+    odd Lq."""
+    Lk = 700
+    seed = Lq * 7 + Lk
+    q, k, v, w = _qkvw(Lq, Lk, seed)
+    mask = _random_mask(Lq, Lk, seed) if Lq % 2 else None
+    want = _mha_ref(q, k, v, w, mask)
+    got = _flash_c2s(q, k, v, w, mask)
+    _check(f"flash c2s builds {Lq}x{Lk}", got, want)
+
+
+@pytest.mark.parametrize("Lk", [1, 3, 15, 16, 17, 63, 64, 65])
+def test_c2s_short_key_side(Lk):
+    """Fewer keys than a chunk (one workgroup, fewer than four groups), than a group, a single key; 64 / 65: one chunk
+    exactly and one key into the second."""
+    Lq = 20
+    seed = Lq * 7 + Lk
+    q, k, v, w = _qkvw(Lq, Lk, seed)
+    mask = _random_mask(Lq, Lk, seed) if Lk >= 2 else None
+    want = _mha_ref(q, k, v, w, mask)
+    got = _flash_c2s(q, k, v, w, mask)
+    _check(f"flash c2s short {Lq}x{Lk}", got, want)
+
+
+# ---------------------------------------------------------------------------------------------------- s2c
+@pytest.mark.parametrize("Lq,Lk", [(16485, 20), (32961, 37)])
+def test_s2c_workgroups_walk_several_chunks(Lq, Lk):
+    """Scene-to-click over more than 256 chunks of points: the dK / dV slabs of a workgroup add up over its two / three
+    chunks (the last one of 37 points / one point), the key-side fragments are fetched again per chunk, 256 slabs reduce."""
+    _assert_walks(L.load().a3d_flash_s2c_workspace_bytes, Lq, None, Lk)
+    q, k, v, w = _qkvw(Lq, Lk, Lq * 3 + Lk)
+    want = _mha_ref(q, k, v, w, None)
+    got = _flash_s2c(q, k, v, w)
+    _check(f"flash s2c walk {Lq}x{Lk}", got, want)
+
+
+@pytest.mark.parametrize("Lq,Lk", [(700, 1), (700, 15), (700, 16), (700, 17), (700, 128), (700, 255), (700, 256),
+                                   (1, 20), (15, 20), (63, 20), (64, 20), (65, 20)])
+def test_s2c_short_sides(Lq, Lk):
+    """The key side from a single key to 256 (A3D_MAX_QUERIES) around the 16-key tile, and the point side below one group,
+    below one chunk, one chunk exactly and one point into the second."""
+    q, k, v, w = _qkvw(Lq, Lk, Lq * 3 + Lk)
+    want = _mha_ref(q, k, v, w, None)
+    got = _flash_s2c(q, k, v, w)
+    _check(f"flash s2c short {Lq}x{Lk}", got, want)
+
+
+# ---------------------------------------------------------------------------------------------------- dropout builds
+@pytest.mark.parametrize("Lq,Lk,walk", [(20, 16485, True), (225, 700, False)], ids=["A-20x16485", "225x700"])
+def test_c2s_dropout_walk_and_second_launch(Lq, Lk, walk):
+    """The DROP builds of click-to-scene at p = 0.1 with the keep matrix from a3d_dropout_mask: the Philox counters on a
+    workgroup's second chunk (A's shape and mask), and on the second launch's rows (225 queries)."""
+    sample, site = 1, 8
+    seed = Lq * 7 + Lk
+    q, k, v, w = _qkvw(Lq, Lk, seed)
+    if walk:
+        _assert_walks(L.load().a3d_flash_c2s_workspace_bytes, Lk, Lq, None)
+        mask = _structured_mask(Lq, Lk, seed)
+    else:
+        mask = _random_mask(Lq, Lk, seed)
+    Z = zmat(SEED, sample, site, P_DROP, 8, Lq, Lk)
+    want = _mha_ref(q, k, v, w, mask, Z, per_head=walk)
+    got = _flash_c2s(q, k, v, w, mask, drop=L.Dropout(SEED, P_DROP, sample, site, 0), twice=walk)
+    _check(f"flash c2s dropout {Lq}x{Lk}", got, want)
+
+
+@pytest.mark.parametrize("Lq,Lk", [(16485, 20), (700, 256)])
+def test_s2c_dropout_walk_and_widest_key_side(Lq, Lk):
+    """The DROP builds of scene-to-click at p = 0.1: a workgroup's second chunk of points, and 256 keys."""
+    sample, site = 2, 6
+    q, k, v, w = _qkvw(Lq, Lk, Lq * 3 + Lk)
+    if Lq > CAP * CHUNK:
+        _assert_walks(L.load().a3d_flash_s2c_workspace_bytes, Lq, None, Lk)
+    Z = zmat(SEED, sample, site, P_DROP, 8, Lq, Lk)
+    want = _mha_ref(q, k, v, w, None, Z)
+    got = _flash_s2c(q, k, v, w, drop=L.Dropout(SEED, P_DROP, sample, site, 0))
+    _check(f"flash s2c dropout {Lq}x{Lk}", got, want)
+
+
+# ---------------------------------------------------------------------------------------------------- the tape
+def test_tape_flash_matches_dense_on_a_walking_scene():
+    """DecoderTape on 17 000 decoder-input rows (266 chunks: the flash kernels of all three layers walk) with 12 clicks on
+    three objects and the background, flash against materialised scores (TD.FLASH = False): logits to 1e-4, every parameter
+    gradient and dL/d(pcd_features) to 1e-3 -- the bars of test_dense_path_with_dropout_matches_flash."""
+    import agile3d_amd.train_decoder as TD
+    from agile3d_amd import build_model, default_args
+    from oracle import decoder as od
+    N, Q = 17000, 12
+    lib = L.load()
+    _assert_walks(lib.a3d_flash_c2s_workspace_bytes, N, Q, None)
+    _assert_walks(lib.a3d_flash_s2c_workspace_bytes, N, None, Q)
+    torch.manual_seed(11)
+    model = build_model(default_args()).cuda().train()
+    g = torch.Generator().manual_seed(17)
+    pcd = torch.randn(N, 128, generator=g) * 0.7
+    xyz = (torch.rand(N, 3, generator=g) * 4.0).double()
+    B_ = model.state_dict()["pos_enc.gauss_B"].detach().cpu().double()
+    pos = od.fourier_pos_enc(xyz, B_, xyz.min(0)[0], xyz.max(0)[0]).float()
+    rows = torch.randperm(N, generator=g)[:Q].tolist()
+    ci = {"0": rows[0:3], "1": rows[3:6], "2": rows[6:9], "3": rows[9:12]}
+    ct = {"0": [3, 7, 11], "1": [0, 4, 8], "2": [1, 5, 9], "3": [2, 6, 10]}
+    R = [torch.randn(N, 4, generator=g) / 8 for _ in range(3)]
+    res = {}
+    for flash in (True, False):
+        TD.FLASH = flash
+        try:
+            t = TD.DecoderTape(model, pcd.cuda(), pos.cuda(), ci, ct)
+            masks = list(t.attn_masks)
+            res[flash] = (t.logits, t.backward([r.cuda() for r in R]), masks)
+        finally:
+            TD.FLASH = True
+    flips = sum(int((a != b).sum()) for a, b in zip(res[True][2], res[False][2]))
+    print(f"tape {N} rows: attention-mask entries that differ between the two runs: {flips}")
+    for l in range(3):
+        a, b = res[True][0][l], res[False][0][l]
+        err, sc = (a - b).abs().max().item(), max(1.0, b.abs().max().item())
+        print(f"tape {N} rows logits[{l}]: max|diff| {err:.2e} (scale {sc:.2e})")
+        assert err <= 1e-4 * sc, (l, err, sc)
+    (ga, da), (gb, db) = res[True][1], res[False][1]
+    assert set(ga) == set(gb)
+    worst = max(((ga[k] - gb[k]).abs().max().item() / max(1e-3, gb[k].abs().max().item()), k) for k in gb)
+    rel_p = (da - db).abs().max().item() / db.abs().max().item()
+    print(f"tape {N} rows: worst relative gradient difference {worst[0]:.2e} ({worst[1]}), d_pcd {rel_p:.2e}")
+    assert worst[0] <= 1e-3 and rel_p <= 1e-3, (worst, rel_p)
