@@ -1,12 +1,13 @@
-// session.hip -- the headless interactive session around forward_mask: exact nearest rows, ray picking and the
-// full-resolution paint pass (gfx950).
+// session.hip -- the headless interactive session around forward_mask: exact nearest rows, ray picking (vertices of a point
+// cloud, surfaces of a triangle mesh) and the full-resolution paint pass (gfx950).
 //
 // Replaces (reference file:line):
 //   find_nearest (torch.cdist over all voxel rows, again over all vertices)   interactive_tool/utils.py:27-29, gui.py:273-274
-//   "render a depth image and unproject" (Open3D's renderer)                  gui.py:247-271   -> k_pick_ray, a rule of OURS
+//   "render a depth image and unproject" (Open3D's renderer)                  gui.py:247-271   -> k_pick_ray (point clouds) and
+//                                                                             k_pick_mesh (triangle meshes), rules of OURS
 //   pred[inverse_map], get_colors, the click cubes                            interactive_segmentation_user.py:83-84,125-140, gui.py:276-298,327
 //
-// All three are streaming passes over 12-byte rows, memory bound, no MFMA.  Nothing here uses an atomic on a result: every
+// All four are streaming passes over 12-byte rows, memory bound, no MFMA.  Nothing here uses an atomic on a result: every
 // search is a minimum over a packed integer key whose order is total (distance bits, then row), reduced per wave with
 // shuffles, per workgroup through LDS, and over the workgroups by ONE second-stage block -- the result does not depend on
 // the order in which workgroups finish.  The tables of a call (sources, queries, ray) travel by value in the kernel
@@ -15,6 +16,17 @@
 // THE PICK RULE (ours: the reference delegates picking to Open3D's depth render).  Ray (o, d), |d| = 1, radius r: among the
 // points p with t = (p - o) . d > 0 and |(p - o) - t d| <= r the one with the smallest t; ties -> the smaller perpendicular
 // distance, then the lower index; none -> -1 ("clicked on nothing", gui.py:265).
+//
+// THE MESH PICK RULE (ours as well).  Ray (o, d), faces int32 [m][3] into the same vertex rows: the first SURFACE the ray
+// meets -- among the faces the ray crosses at a finite t > 0 the one with the smallest t, ties -> the lower face index; none
+// -> -1.  Faces are double-sided, edges inclusive.  The crossing test is the watertight one of Woop, Benthin and Wald
+// ("Watertight Ray/Triangle Intersection", JCGT 2013): vertices translated by the origin, axes permuted so that the ray's
+// dominant axis is z, sheared so that the ray becomes the z axis, then the three 2-D edge functions of the sheared x/y.  An
+// edge function is f(P, Q) = Qx Py - Qy Px of ITS two endpoints only; with every product and the difference rounded on its
+// own (no fma) f(P, Q) = -f(Q, P) exactly, so two faces that share an edge see the ray on opposite sides of it or both on
+// it, never both outside: no ray passes between them.  A function that comes out exactly 0 is recomputed in double (exact
+// products, one rounding), as in the paper.  Skipped, never an error: det == 0, a repeated index, a NaN, an index outside
+// [0, n) (which also sets bit 0 of the result's flags).
 #include "common.h"
 
 namespace a3d {
@@ -190,6 +202,117 @@ __global__ __launch_bounds__(64) void k_pick_finish(const PickTab t, const unsig
   }
 }
 
+// ---- mesh pick: the first face a ray crosses -------------------------------------------------------------------------------
+struct MeshTab {
+  const float* xyz;
+  long long n;
+  const int32_t* faces;
+  long long m;
+  float o[3];
+  float sx, sy, sz;                           // the shear: d[kx] / d[kz], d[ky] / d[kz], 1 / d[kz] (fp32, computed on the host)
+  int kx, ky, kz;                             // the permutation: kz = the ray's dominant axis, kx / ky swapped when d[kz] < 0
+  a3d_pick_mesh_result* out;
+};
+struct MeshFace {
+  float U, V, W, det, t;                      // edge functions opposite vertex 0, 1, 2; their sum; the ray parameter
+};
+// THE crossing test of both stages.  Returns 0 = no hit, 1 = hit (f filled), 2 = an index outside [0, n).  Every product,
+// sum and difference is rounded on its own (contraction off), in the order written: a numpy float32 restatement gives the
+// same bits.
+__device__ __forceinline__ int ses_face(const MeshTab& t, long long i, MeshFace& f, int32_t& i0, int32_t& i1, int32_t& i2) {
+#pragma clang fp contract(off)
+  i0 = t.faces[3 * i], i1 = t.faces[3 * i + 1], i2 = t.faces[3 * i + 2];
+  if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= t.n || i1 >= t.n || i2 >= t.n) return 2;
+  if (i0 == i1 || i1 == i2 || i0 == i2) return 0;
+  const float* __restrict__ pa = t.xyz + 3 * (size_t)i0;
+  const float* __restrict__ pb = t.xyz + 3 * (size_t)i1;
+  const float* __restrict__ pc = t.xyz + 3 * (size_t)i2;
+  const float a[3] = {pa[0] - t.o[0], pa[1] - t.o[1], pa[2] - t.o[2]};
+  const float b[3] = {pb[0] - t.o[0], pb[1] - t.o[1], pb[2] - t.o[2]};
+  const float c[3] = {pc[0] - t.o[0], pc[1] - t.o[1], pc[2] - t.o[2]};
+  const float akz = t.kz == 0 ? a[0] : t.kz == 1 ? a[1] : a[2], akx = t.kx == 0 ? a[0] : t.kx == 1 ? a[1] : a[2],
+              aky = t.ky == 0 ? a[0] : t.ky == 1 ? a[1] : a[2];
+  const float bkz = t.kz == 0 ? b[0] : t.kz == 1 ? b[1] : b[2], bkx = t.kx == 0 ? b[0] : t.kx == 1 ? b[1] : b[2],
+              bky = t.ky == 0 ? b[0] : t.ky == 1 ? b[1] : b[2];
+  const float ckz = t.kz == 0 ? c[0] : t.kz == 1 ? c[1] : c[2], ckx = t.kx == 0 ? c[0] : t.kx == 1 ? c[1] : c[2],
+              cky = t.ky == 0 ? c[0] : t.ky == 1 ? c[1] : c[2];
+  const float ax = akx - t.sx * akz, ay = aky - t.sy * akz;
+  const float bx = bkx - t.sx * bkz, by = bky - t.sy * bkz;
+  const float cx = ckx - t.sx * ckz, cy = cky - t.sy * ckz;
+  float U = cx * by - cy * bx;                // f(B, C)
+  float V = ax * cy - ay * cx;                // f(C, A)
+  float W = bx * ay - by * ax;                // f(A, B)
+  if (U == 0.f || V == 0.f || W == 0.f) {     // on an edge as far as fp32 can tell: products of floats are exact in double
+    U = (float)((double)cx * (double)by - (double)cy * (double)bx);
+    V = (float)((double)ax * (double)cy - (double)ay * (double)cx);
+    W = (float)((double)bx * (double)ay - (double)by * (double)ax);
+  }
+  if ((U < 0.f || V < 0.f || W < 0.f) && (U > 0.f || V > 0.f || W > 0.f)) return 0;   // (edges inclusive, both windings)
+  const float det = (U + V) + W;
+  if (det == 0.f) return 0;
+  const float az = t.sz * akz, bz = t.sz * bkz, cz = t.sz * ckz;
+  const float T = (U * az + V * bz) + W * cz;
+  const float tt = T / det;
+  if (!(tt > 0.f && tt < __builtin_inff())) return 0;   // (NaN fails the first test)
+  f.U = U, f.V = V, f.W = W, f.det = det, f.t = tt;
+  return 1;
+}
+__global__ __launch_bounds__(kSesBlock) void k_pick_mesh(const MeshTab t, unsigned long long* __restrict__ part_key,
+                                                         unsigned* __restrict__ part_flag) {
+  unsigned long long best = kNoKey;
+  int bad = 0;
+  const long long stride = (long long)gridDim.x * kSesBlock;
+  for (long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x; i < t.m; i += stride) {
+    MeshFace f;
+    int32_t i0, i1, i2;
+    const int r = ses_face(t, i, f, i0, i1, i2);
+    if (r == 1) {
+      const unsigned long long k = ses_key(f.t, (unsigned)i);   // t > 0: its bits order like t
+      best = k < best ? k : best;
+    }
+    bad |= r == 2;
+  }
+  best = ses_wave_min(best);
+  __shared__ unsigned long long sk[kSesBlock / 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) sk[wv] = best;
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kSesBlock / 64; ++w) best = sk[w] < best ? sk[w] : best;
+    part_key[blockIdx.x] = best;
+    part_flag[blockIdx.x] = bad ? 1u : 0u;
+  }
+}
+__global__ __launch_bounds__(64) void k_pick_mesh_finish(const MeshTab t, const unsigned long long* __restrict__ part_key,
+                                                         const unsigned* __restrict__ part_flag, int n_blocks) {
+  unsigned long long best = kNoKey;
+  int bad = 0;
+  for (int j = threadIdx.x; j < n_blocks; j += 64) {
+    best = part_key[j] < best ? part_key[j] : best;
+    bad |= part_flag[j] != 0;
+  }
+  best = ses_wave_min(best);
+  bad = __any(bad);
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    a3d_pick_mesh_result r;
+    r.face = -1, r.flags = bad ? 1 : 0, r.t = 0.f, r.x = r.y = r.z = 0.f, r.u = r.v = 0.f;
+    MeshFace f;
+    int32_t i0, i1, i2;
+    if (best != kNoKey && ses_face(t, (long long)(best & 0xffffffffu), f, i0, i1, i2) == 1) {   // (the first stage's bits again)
+      const float* pa = t.xyz + 3 * (size_t)i0;
+      const float* pb = t.xyz + 3 * (size_t)i1;
+      const float* pc = t.xyz + 3 * (size_t)i2;
+      const float u = f.V / f.det, v = f.W / f.det, w = (1.f - u) - v;
+      r.face = (int32_t)(best & 0xffffffffu), r.t = f.t, r.u = u, r.v = v;
+      r.x = (w * pa[0] + u * pb[0]) + v * pc[0];
+      r.y = (w * pa[1] + u * pb[1]) + v * pc[1];
+      r.z = (w * pa[2] + u * pb[2]) + v * pc[2];
+    }
+    *t.out = r;
+  }
+}
+
 // ---- paint: labels, colours and click cubes of every full-resolution vertex in one pass -----------------------------------
 __global__ __launch_bounds__(kSesBlock) void k_session_paint(const a3d_session_paint_args a) {
   __shared__ float pal[256 * 3];
@@ -230,6 +353,8 @@ struct SesWs {
   unsigned long long* near_part;
   unsigned long long* pick_a;
   unsigned* pick_row;
+  unsigned long long* mesh_key;
+  unsigned* mesh_flag;
   size_t bytes;
 };
 static SesWs carve_session(void* base) {
@@ -243,6 +368,8 @@ static SesWs carve_session(void* base) {
   w.near_part = (unsigned long long*)take((size_t)A3D_NEAREST_MAX_SOURCES * A3D_NEAREST_MAX_QUERIES * kSesMaxBlocks * 8);
   w.pick_a = (unsigned long long*)take((size_t)kSesMaxBlocks * 8);
   w.pick_row = (unsigned*)take((size_t)kSesMaxBlocks * 4);
+  w.mesh_key = (unsigned long long*)take((size_t)kSesMaxBlocks * 8);
+  w.mesh_flag = (unsigned*)take((size_t)kSesMaxBlocks * 4);
   w.bytes = off;
   return w;
 }
@@ -319,6 +446,44 @@ extern "C" int a3d_pick_ray(const float* xyz_dev, int64_t n, const float* origin
   k_pick_ray<<<nb, kSesBlock, 0, st>>>(t, w.pick_a, w.pick_row);
   A3D_LAUNCH_CHECK();
   k_pick_finish<<<1, 64, 0, st>>>(t, w.pick_a, w.pick_row, nb);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" int a3d_pick_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const float* origin,
+                             const float* direction, a3d_pick_mesh_result* result_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (n < 0 || n >= (1ll << 31) || m < 0 || m >= (1ll << 31) || (n && !xyz_dev) || (m && !faces_dev) || !origin || !direction ||
+      !result_dev) {
+    set_error("a3d_pick_mesh: bad arguments (n=%lld m=%lld)", (long long)n, (long long)m);
+    return A3D_ERR_INVALID;
+  }
+  const double len2 = (double)direction[0] * direction[0] + (double)direction[1] * direction[1] + (double)direction[2] * direction[2];
+  if (!(len2 > 0.999 && len2 < 1.001)) {
+    set_error("a3d_pick_mesh: the direction must be a unit vector (|d|^2 = %g)", len2);
+    return A3D_ERR_INVALID;
+  }
+  if (!ses_ws_ok(workspace_dev, workspace_bytes, "a3d_pick_mesh")) return A3D_ERR_WORKSPACE;
+  MeshTab t;
+  t.xyz = xyz_dev, t.n = n, t.faces = faces_dev, t.m = m;
+  for (int k = 0; k < 3; ++k) t.o[k] = origin[k];
+  int kz = 0;                                  // the dominant axis (the first of equals)
+  if (fabsf(direction[1]) > fabsf(direction[kz])) kz = 1;
+  if (fabsf(direction[2]) > fabsf(direction[kz])) kz = 2;
+  int kx = (kz + 1) % 3, ky = (kx + 1) % 3;
+  if (direction[kz] < 0.f) {                   // keep the winding
+    const int s = kx;
+    kx = ky, ky = s;
+  }
+  t.kx = kx, t.ky = ky, t.kz = kz;
+  t.sx = direction[kx] / direction[kz], t.sy = direction[ky] / direction[kz], t.sz = 1.f / direction[kz];
+  t.out = result_dev;
+  const SesWs w = carve_session(workspace_dev);
+  const int nb = ses_blocks(m);
+  k_pick_mesh<<<nb, kSesBlock, 0, st>>>(t, w.mesh_key, w.mesh_flag);
+  A3D_LAUNCH_CHECK();
+  k_pick_mesh_finish<<<1, 64, 0, st>>>(t, w.mesh_key, w.mesh_flag, nb);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

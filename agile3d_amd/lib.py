@@ -113,6 +113,13 @@ class PickResult(C.Structure):
     _fields_ = [("index", C.c_int32), ("x", C.c_float), ("y", C.c_float), ("z", C.c_float)]
 
 
+class PickMeshResult(C.Structure):
+    """a3d_pick_mesh_result: what a3d_pick_mesh writes (face -1 = the ray meets no surface; flags bit 0 = a face index
+    outside the vertex rows was skipped; u, v = the weights of the face's second and third vertex)."""
+    _fields_ = [("face", C.c_int32), ("flags", C.c_int32), ("t", C.c_float), ("x", C.c_float), ("y", C.c_float),
+                ("z", C.c_float), ("u", C.c_float), ("v", C.c_float)]
+
+
 class SessionPaintArgs(C.Structure):
     """a3d_session_paint_args."""
     _fields_ = [("labels_qv_dev", C.c_void_p), ("n_qv", C.c_int64), ("inverse_map_dev", C.c_void_p), ("n_full", C.c_int64),
@@ -308,6 +315,8 @@ SYMBOLS = {
                                    C.c_void_p]),
     "a3d_pick_ray": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_void_p,
                                C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_pick_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_session_paint": (C.c_int, [C.POINTER(SessionPaintArgs), C.c_void_p]),
 }
 

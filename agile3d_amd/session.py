@@ -7,6 +7,7 @@ dictionaries, relabelled ground truth, record line and ``.npy`` files -- and no 
 calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``):
 
     pointer ray -> clicked point        a3d_pick_ray       (the GUI renders a depth image and unprojects, gui.py:247-271)
+                                        a3d_pick_mesh      (the same for a triangle mesh: the first SURFACE under the pointer)
     find_nearest, twice per click       a3d_nearest_rows   (utils.py:27-29: two full torch.cdist calls; here exact)
     argmax + clicked rows               a3d_argmax_labels  (interactive_segmentation_user.py:78-81)
     pred[inverse_map], colours, cubes   a3d_session_paint  (:83-84,125-140; gui.py:276-298,327)
@@ -101,6 +102,21 @@ def _f3(values, what):
     return a
 
 
+def ray_from_pixel(u, v, intrinsic, extrinsic):
+    """The pointer ray of pixel ``(u, v)`` (column, row), sampled at its centre ``(u + 0.5, v + 0.5)``, for callers that
+    have a pixel and a camera rather than a ray -- the inverse of the GUI's unprojection (gui.py:268-270).  ``intrinsic``:
+    3 x 3 pinhole matrix (fx, fy, cx, cy); ``extrinsic``: 4 x 4 world-to-camera, the camera looking along +z.  Returns
+    ``(origin, direction)`` in world space, float64: the camera centre and a unit vector.  Pure numpy."""
+    k = np.asarray(intrinsic, dtype=np.float64)
+    e = np.asarray(extrinsic, dtype=np.float64)
+    if k.shape != (3, 3) or e.shape != (4, 4):
+        raise ValueError("intrinsic must be 3 x 3 and extrinsic 4 x 4 (world to camera)")
+    rot, trans = e[:3, :3], e[:3, 3]
+    d_cam = np.array([(float(u) + 0.5 - k[0, 2]) / k[0, 0], (float(v) + 0.5 - k[1, 2]) / k[1, 1], 1.0])
+    d = np.linalg.solve(rot, d_cam)                 # camera -> world (no assumption that the rotation is exactly orthogonal)
+    return -np.linalg.solve(rot, trans), d / np.linalg.norm(d)
+
+
 class InteractiveSession:
     """The headless counterpart of ``UserInteractiveSegmentationModel`` plus the GUI's click state.
 
@@ -145,6 +161,7 @@ class InteractiveSession:
         self.out_dir = None
         self.coords_full = self.colors_full = self.labels_full_ori = self.labels_qv_ori = None
         self.inverse_map = self.raw_coords_qv = None
+        self.faces = None                           # int32 [m, 3] on the device: a triangle-mesh scene (pick meets its surface)
         self._coords_host = None
         self._backbone = None
         self._mask_host = None
@@ -159,12 +176,14 @@ class InteractiveSession:
         self._labels_qv = None if self.raw_coords_qv is None else torch.zeros(self.raw_coords_qv.shape[0], dtype=torch.int32,
                                                                                device=self.device)
 
-    def load_scene(self, coords_full, colors_full, labels_full=None, name="scene", out_dir=None):
+    def load_scene(self, coords_full, colors_full, labels_full=None, name="scene", out_dir=None, faces=None):
         """Voxelise on the GPU, run the backbone once and keep what the clicks need
         (interactive_segmentation_user.py:161-196).  ``coords_full`` [n, 3] float32 / float64 (quantised in its own
         precision, like ``ME.utils.sparse_quantize``), ``colors_full`` [n, 3] in [0, 1], ``labels_full`` [n] instance ids
         or ``None``.  With ``out_dir`` every ``infer()`` appends to ``out_dir/iou_record.csv`` and writes
-        ``out_dir/masks/mask_*.npy`` and ``out_dir/clicks/click_*.npy``.  Everything of a previous scene is dropped."""
+        ``out_dir/masks/mask_*.npy`` and ``out_dir/clicks/click_*.npy``.  ``faces`` [m, 3] integer indices into
+        ``coords_full`` make the scene a triangle mesh: ``pick`` then meets its surface (``ses.faces``, int32 on the
+        device; indices outside ``[0, n)`` raise ``ValueError``).  Everything of a previous scene is dropped."""
         self._drop_scene()
         dev = self.device
         xyz = torch.as_tensor(np.asarray(coords_full) if not torch.is_tensor(coords_full) else coords_full)
@@ -176,6 +195,14 @@ class InteractiveSession:
         col = torch.as_tensor(np.asarray(colors_full) if not torch.is_tensor(colors_full) else colors_full)
         if tuple(col.shape) != (n, 3):
             raise ValueError("colors_full must be [n, 3]")
+        faces_dev = None
+        if faces is not None:
+            fa = np.asarray(faces.cpu() if torch.is_tensor(faces) else faces)
+            if fa.ndim != 2 or fa.shape[1] != 3 or fa.dtype.kind not in "iu":
+                raise ValueError("faces must be [m, 3] integer indices into coords_full")
+            if fa.size and (int(fa.min()) < 0 or int(fa.max()) >= n):     # checked once, here: the kernel only skips such faces
+                raise ValueError(f"faces: vertex indices outside [0, {n})")
+            faces_dev = torch.from_numpy(np.ascontiguousarray(fa, dtype=np.int32)).to(dev)
         xyz = xyz.to(dev).contiguous()
         col32 = col.to(dev).to(torch.float32).contiguous()
         coords_qv, unique_map, inverse_map = sparse_quantize(xyz, quantization_size=self.voxel_size, return_index=True,
@@ -194,6 +221,7 @@ class InteractiveSession:
         bc = torch.cat([torch.zeros((coords_qv.shape[0], 1), dtype=torch.int32, device=dev), coords_qv.to(torch.int32)], 1)
         data = SparseTensor(coordinates=bc, features=col32[unique_map], device=dev)
         self._backbone = self.model.forward_backbone(data, raw_coordinates=self.raw_coords_qv)
+        self.faces = faces_dev
         self.scene_name = str(name)
         self.out_dir = out_dir
         if out_dir is not None:
@@ -208,7 +236,11 @@ class InteractiveSession:
         a point cloud or a triangle mesh with x, y, z and red, green, blue), optionally ``label.ply`` with a ``label``
         property.  The scene's name is the folder's without its ``scene_`` prefix."""
         scan = os.path.join(path, "scan.ply")
-        v = ply.read_ply(scan, triangular_mesh=True)[0] if ply.is_triangular_mesh(scan) else ply.read_ply(scan)
+        faces = None
+        if ply.is_triangular_mesh(scan):
+            v, faces = ply.read_ply(scan, triangular_mesh=True)
+        else:
+            v = ply.read_ply(scan)
         names = v.dtype.names
         if not all(k in names for k in ("x", "y", "z", "red", "green", "blue")):
             raise ValueError(f"{scan}: vertex properties x, y, z, red, green, blue expected, found {names}")
@@ -222,7 +254,7 @@ class InteractiveSession:
             labels = lv["label"].astype(np.int32)
         base = os.path.basename(os.path.normpath(path))
         name = base[len("scene_"):] if base.startswith("scene_") else base
-        return self.load_scene(xyz, rgb, labels, name=name, out_dir=out_dir)
+        return self.load_scene(xyz, rgb, labels, name=name, out_dir=out_dir, faces=faces)
 
     def reset(self):
         """A new annotation of the same scene: clicks, relabelled ground truth and labels start over; the backbone output
@@ -235,18 +267,34 @@ class InteractiveSession:
             raise RuntimeError("no scene loaded (load_scene / load_scene_dir)")
 
     # ------------------------------------------------------------------ pick and click
-    def pick(self, origin, direction, radius=None):
-        """The vertex a pointer ray meets, ``[x, y, z]``, or ``None`` ("clicked on nothing").  The rule is this library's
-        (``a3d_pick_ray``): among the vertices in front of ``origin`` within ``radius`` (default ``voxel_size``) of the
-        ray, the first along it; ties go to the one closer to the ray, then to the lower index."""
+    def pick(self, origin, direction, radius=None, surface=None):
+        """The point a pointer ray meets, ``[x, y, z]``, or ``None`` ("clicked on nothing").  Both rules are this library's.
+        A point cloud (``a3d_pick_ray``): among the vertices in front of ``origin`` within ``radius`` (default
+        ``voxel_size``) of the ray, the first along it; ties go to the one closer to the ray, then to the lower index.  A
+        triangle mesh (``a3d_pick_mesh``): the point where the ray first crosses a face -- what the GUI's unprojection of
+        the rendered depth yields and what ``click`` takes.  ``surface=None`` uses the surface rule when the scene has
+        faces, ``False`` forces the vertex rule, ``True`` without faces raises ``ValueError``."""
         self._need_scene()
         o = _f3(origin, "origin")
         d64 = np.asarray(direction, dtype=np.float64).reshape(-1)
         if d64.shape != (3,) or not np.isfinite(d64).all() or not np.linalg.norm(d64) > 0:
             raise ValueError("direction must be three finite numbers, not all zero")
         d = np.ascontiguousarray((d64 / np.linalg.norm(d64)).astype(np.float32))
-        r = self.voxel_size if radius is None else float(radius)
+        if surface is None:
+            surface = self.faces is not None
         fp = C.POINTER(C.c_float)
+        if surface:
+            if self.faces is None:
+                raise ValueError("pick(surface=True): the scene has no faces (load_scene(..., faces=) or a mesh scan.ply)")
+            L.check(self.lib.a3d_pick_mesh(self.coords_full.data_ptr(), self.coords_full.shape[0], self.faces.data_ptr(),
+                                           self.faces.shape[0], o.ctypes.data_as(fp), d.ctypes.data_as(fp),
+                                           self._small.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                           _stream(self.device)), "a3d_pick_mesh")
+            host = self._small[:8].cpu().numpy()          # a3d_pick_mesh_result: face, flags, t, x, y, z, u, v
+            if int(host[0]) < 0:
+                return None
+            return [float(v) for v in host[3:6].view(np.float32)]
+        r = self.voxel_size if radius is None else float(radius)
         L.check(self.lib.a3d_pick_ray(self.coords_full.data_ptr(), self.coords_full.shape[0], o.ctypes.data_as(fp),
                                       d.ctypes.data_as(fp), r, self._small.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
                                       _stream(self.device)), "a3d_pick_ray")
@@ -299,6 +347,14 @@ class InteractiveSession:
         self._cubes_dev[k].copy_(self._cubes_host[k], non_blocking=True)      # (a row of its own in pinned memory: never rewritten while in flight)
         self.num_clicks += 1
         return row_qv, row_full
+
+    def click_ray(self, origin, direction, obj: int):
+        """``pick`` then ``click``: the click a pointer ray makes for object ``obj``.  Returns what ``click`` returns, or
+        ``None`` -- with nothing booked -- when the ray meets nothing."""
+        point = self.pick(origin, direction)
+        if point is None:
+            return None
+        return self.click(point, obj)
 
     def _palette_entry(self, obj):
         n = self.palette.shape[0]

@@ -751,8 +751,8 @@ int    a3d_click_loss_weights(const float* xyz_dev, int64_t n, const int32_t* cl
  * Replaces what surrounds the two model calls of interactive_tool/: find_nearest (utils.py:27-29: one
  * torch.cdist over all voxel rows and one over all vertices per click), the depth-image pick of gui.py:247-271,
  * and pred[inverse_map] + get_colors + the click cubes (interactive_segmentation_user.py:83-84,125-140,
- * gui.py:276-298,327).  a3d_nearest_rows and a3d_pick_ray take one scratch buffer of a fixed size (256-byte aligned).
- * Both write their first-stage results into it: two calls that share a workspace must be ordered (the same stream, or
+ * gui.py:276-298,327).  a3d_nearest_rows, a3d_pick_ray and a3d_pick_mesh take one scratch buffer of a fixed size (256-byte aligned).
+ * All write their first-stage results into it: two calls that share a workspace must be ordered (the same stream, or
  * an event between them); calls on different streams that may overlap each bring their own workspace.
  * ------------------------------------------------------------------------------------------ */
 #define A3D_NEAREST_MAX_QUERIES 64
@@ -786,6 +786,27 @@ typedef struct a3d_pick_result {
 } a3d_pick_result;
 int    a3d_pick_ray(const float* xyz_dev, int64_t n, const float* origin, const float* direction, float radius,
                     a3d_pick_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The same stand-in for a TRIANGLE MESH: the first surface the ray meets.  faces_dev: int32 [m][3] indices into the same
+ * xyz_dev rows [n][3] (no second copy of the vertices); origin o, UNIT direction d (HOST arrays of 3).  The rule is this
+ * library's: among the faces the ray crosses at a finite t > 0 the one with the smallest t, ties -> the lower face index.
+ * Faces are double-sided and their edges inclusive; the crossing test is the watertight one of Woop, Benthin and Wald
+ * (JCGT 2013) evaluated in fp32 without fma contraction, an edge function that is exactly 0 recomputed in double: two
+ * faces that share an edge classify every ray consistently, so no ray passes between them.  Skipped, never an error:
+ * faces with det == 0, a repeated index, a NaN coordinate, or an index outside 0..n-1 -- the last also sets bit 0 of
+ * flags.  m == 0 is valid.  result_dev: face -1 = the ray meets no surface; else t, the barycentric weights u (of the
+ * face's second vertex) and v (of its third; the first has 1 - u - v) and the hit point x, y, z = that combination of the
+ * face's three vertices in fp32 -- a point of the triangle, not o + t d.  Takes the session workspace like a3d_pick_ray. */
+typedef struct a3d_pick_mesh_result {
+  int32_t face;
+  int32_t flags;
+  float   t;
+  float   x, y, z;
+  float   u, v;
+} a3d_pick_mesh_result;
+int    a3d_pick_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const float* origin,
+                     const float* direction, a3d_pick_mesh_result* result_dev, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
 
 /* One pass over the n_full full-resolution vertices: label_full[i] = labels_qv[inverse_map[i]] (labels_qv = what
  * a3d_argmax_labels wrote, clicked rows already overwritten; inverse_map NULL = identity), colour = the palette entry of

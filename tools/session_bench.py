@@ -9,7 +9,13 @@ alternating, on one synthetic scene (~80 k voxels, ~250 k full-resolution vertic
 Every stage is timed twice: with device events around it (what the GPU spent) and with a host clock around a stage that
 ends in a synchronisation (what the caller waits).  Medians over ``--reps`` clicks after a warm-up of 10.  The baseline has
 no pick stage (the reference renders a depth image) and no IoU; the session's "paint + IoU" stage includes the IoU.  Needs
-the GPU; there is no CPU path to time."""
+the GPU; there is no CPU path to time.
+
+A last stage times the MESH pick (``a3d_pick_mesh``) next to the vertex pick (``a3d_pick_ray``) on the same vertices: a
+synthetic tessellated height field of about the scene's vertex count, vertices in scan order, two triangles per cell.
+Staged like ``pick`` above (the call and its small device-to-host copy, device events and host clock), and back to back
+(``--mesh-calls`` calls between two events, no copy: the two kernels of a call alone), with the bytes a call must move
+(12 B of indices per face + 12 B per vertex once) and the bytes it requests (12 + 36 B per face)."""
 import argparse
 import json
 import os
@@ -52,12 +58,85 @@ class Timer:
                 {n: float(np.median(v[skip:])) for n, v in self.host.items()})
 
 
+def mesh_pick_stage(ses, n_vertices, reps, warmup, calls):
+    """Mesh pick and vertex pick on one tessellated height field of ~n_vertices vertices (see the module docstring)."""
+    import ctypes as C
+    lib, dev = ses.lib, ses.device
+    side = int(round(np.sqrt(n_vertices)))
+    rng = np.random.default_rng(1)
+    g = np.arange(side, dtype=np.float64) * 0.02
+    x, y = np.meshgrid(g, g, indexing="ij")
+    z = 0.3 * np.sin(0.9 * x) * np.cos(0.7 * y) + rng.uniform(-0.004, 0.004, x.shape)
+    xyz = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
+    idx = np.arange(side * side, dtype=np.int32).reshape(side, side)
+    q00, q10, q01, q11 = idx[:-1, :-1], idx[1:, :-1], idx[:-1, 1:], idx[1:, 1:]
+    faces = np.stack([np.stack([q00, q10, q11], -1), np.stack([q00, q11, q01], -1)], 2).reshape(-1, 3)   # cell by cell
+    xyz_dev, faces_dev = torch.from_numpy(xyz).to(dev), torch.from_numpy(np.ascontiguousarray(faces)).to(dev)
+    n, m = len(xyz), len(faces)
+    fp = C.POINTER(C.c_float)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    out = ses._small
+
+    def ray():
+        tgt = np.array([rng.uniform(0.1, g[-1] - 0.1), rng.uniform(0.1, g[-1] - 0.1), 0.0])
+        o = np.array([0.5 * g[-1], 0.5 * g[-1], 3.0]) + rng.uniform(-0.5, 0.5, 3)
+        d = tgt - o
+        return np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d / np.linalg.norm(d), np.float32)
+
+    def call_mesh(o, d):
+        rc = lib.a3d_pick_mesh(xyz_dev.data_ptr(), n, faces_dev.data_ptr(), m, o.ctypes.data_as(fp), d.ctypes.data_as(fp),
+                               out.data_ptr(), ses._ws.data_ptr(), ses._ws.numel(), stream)
+        assert rc == 0, lib.a3d_last_error()
+
+    def call_ray(o, d):
+        rc = lib.a3d_pick_ray(xyz_dev.data_ptr(), n, o.ctypes.data_as(fp), d.ctypes.data_as(fp), 0.02, out.data_ptr(),
+                              ses._ws.data_ptr(), ses._ws.numel(), stream)
+        assert rc == 0, lib.a3d_last_error()
+
+    tm = Timer(("pick_mesh", "pick_ray"))
+    hits = 0
+    for _ in range(warmup + reps):
+        o, d = ray()
+        hits += int(tm.run("pick_mesh", lambda: (call_mesh(o, d), out[:8].cpu())[1])[0]) >= 0
+        tm.run("pick_ray", lambda: (call_ray(o, d), out[:4].cpu())[1])
+    dev_ms, host_ms = tm.medians(warmup)
+    back = {}
+    for name, fn in (("pick_mesh", call_mesh), ("pick_ray", call_ray)):
+        o, d = ray()
+        per_call = []
+        for _ in range(5):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(calls):
+                fn(o, d)
+            b.record()
+            torch.cuda.synchronize()
+            per_call.append(a.elapsed_time(b) / calls)
+        back[name] = float(np.median(per_call))
+    must = {"pick_mesh": 12 * m + 12 * n, "pick_ray": 12 * n}
+    asked = {"pick_mesh": 48 * m, "pick_ray": 12 * n}
+    res = {"vertices": n, "faces": m, "rays_hit": hits, "rays": warmup + reps, "staged_device_ms": dev_ms,
+           "staged_host_ms": host_ms, "back_to_back_device_ms": back, "calls_back_to_back": calls, "bytes_must_move": must,
+           "bytes_requested": asked,
+           "gbps_must_move": {k: must[k] / back[k] * 1e-6 for k in back},
+           "gbps_requested": {k: asked[k] / back[k] * 1e-6 for k in back}}
+    print(f"\n== mesh pick next to vertex pick: {n} vertices, {m} faces, {hits} of {warmup + reps} rays hit ==")
+    for k in ("pick_mesh", "pick_ray"):
+        print(f"{k}  staged {dev_ms[k]:.3f}/{host_ms[k]:.3f} (device / host ms)   back to back {1e3 * back[k]:.2f} us per call   "
+              f"must move {must[k] / 1e6:.2f} MB = {res['gbps_must_move'][k]:.0f} GB/s   requests {asked[k] / 1e6:.2f} MB = "
+              f"{res['gbps_requested'][k]:.0f} GB/s")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--voxels", type=int, default=80_000)
     ap.add_argument("--reps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mesh-calls", type=int, default=200, help="calls between two events in the mesh-pick stage")
+    ap.add_argument("--mesh-only", action="store_true", help="run the mesh-pick stage alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("session_bench needs the GPU")
@@ -78,7 +157,7 @@ def main():
     original = col.copy()
     centre = xyz.mean(0)
     result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
-    for n_clicks in (1, 5, 10, 20):
+    for n_clicks in (() if a.mesh_only else (1, 5, 10, 20)):
         ses.reset()
         objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
         targets = [xyz[rng.choice(np.flatnonzero(lab == inst[o - 1]))] for o in objs]
@@ -180,6 +259,7 @@ def main():
         print(f"outside forward_mask (host ms): session {entry['session_outside_forward_mask_host_ms']:.3f}  "
               f"baseline {entry['baseline_outside_forward_mask_host_ms']:.3f}   forward_mask {sh['forward_mask']:.3f}")
         print(f"whole click, staged (host ms): session {entry['session_click_ms']:.3f}  baseline {entry['baseline_click_ms']:.3f}")
+    result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
