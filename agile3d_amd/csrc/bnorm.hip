@@ -88,14 +88,20 @@ __global__ void __launch_bounds__(kBnThreads) k_col_partial(const ColArgs a) {
 // the first version took 7): every row block sums its rows, takes ITS mean, and sums the squared deviations from it in a
 // second loop over the same rows (L2-resident by then); k_bn_combine merges the blocks' (count, mean, M2) in block order
 // with Chan's update in fp64 -- the variance is still taken around a mean, never as E[x^2] - E[x]^2.
+// The merge is first-order sensitive to an error of a block's sum (2 (m_b - mean) err in the variance), and an fp32 sum of
+// 512 values near 100 is off by 1e-2: on x = 100 + 0.05 randn that cost save_rstd 4e-6 to 1.3e-5 relative, where torch's
+// fp32 two-pass variance loses 3e-7.  So every row is taken relative to ROW 0 of its column (an exact subtraction wherever
+// the mean is large against the spread, one more fp32 rounding elsewhere): the sums are sums of small numbers, and
+// k_bn_combine adds row 0 back to the merged mean.
 __global__ void __launch_bounds__(kBnThreads) k_bn_block_stats(const ColArgs a) {
   __shared__ f32x4 red[kBnThreads];
   __shared__ f32x4 bmean[kBnThreads];
   const int c4n = a.C >> 2;
   const int col = threadIdx.x % c4n, rsub = threadIdx.x / c4n, rstep = kBnThreads / c4n;
   const int r0 = blockIdx.x * a.rows_per_block, r1 = min(a.n, r0 + a.rows_per_block);
+  const f32x4 pv = *(const f32x4*)(a.x + 4 * col);
   f32x4 s0 = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int r = r0 + rsub; r < r1; r += rstep) s0 += *(const f32x4*)(a.x + (size_t)r * a.ldx + 4 * col);
+  for (int r = r0 + rsub; r < r1; r += rstep) s0 += *(const f32x4*)(a.x + (size_t)r * a.ldx + 4 * col) - pv;
   red[threadIdx.x] = s0;
   __syncthreads();
   if (rsub == 0) {
@@ -107,7 +113,7 @@ __global__ void __launch_bounds__(kBnThreads) k_bn_block_stats(const ColArgs a) 
   const f32x4 m = bmean[col];
   f32x4 s1 = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int r = r0 + rsub; r < r1; r += rstep) {
-    const f32x4 d = *(const f32x4*)(a.x + (size_t)r * a.ldx + 4 * col) - m;
+    const f32x4 d = (*(const f32x4*)(a.x + (size_t)r * a.ldx + 4 * col) - pv) - m;
     s1 += d * d;
   }
   red[threadIdx.x] = s1;
@@ -121,9 +127,10 @@ __global__ void __launch_bounds__(kBnThreads) k_bn_block_stats(const ColArgs a) 
 // thousand dependent L2 loads (38 us for a few KB of arithmetic; 130 of these launches per training iteration): a
 // 256-thread workgroup takes 16 consecutive columns, thread (bl, cc) folds the blocks bl, bl + 16, ... of column cc (64-byte
 // row segments per load), then one thread per column folds the 16 partial results in bl order -- fixed orders, fp64.
+// The partials are those of x - pivot (k_bn_block_stats: pivot = row 0 of x); the mean gets the pivot back.
 constexpr int kFinCols = 16, kFinLanes = 16;
-__global__ void __launch_bounds__(256) k_bn_combine(const float* __restrict__ partial, int nblocks, int rows_per_block, int n,
-                                                    int C, float eps, float* mean_out, float* rstd_out, float* running_mean,
+__global__ void __launch_bounds__(256) k_bn_combine(const float* __restrict__ partial, const float* __restrict__ pivot,
+                                                    int nblocks, int rows_per_block, int n, int C, float eps, float* mean_out, float* rstd_out, float* running_mean,
                                                     float* running_var, float momentum) {
   __shared__ double s_cnt[kFinLanes][kFinCols], s_mean[kFinLanes][kFinCols], s_m2[kFinLanes][kFinCols];
   const int cc = threadIdx.x % kFinCols, bl = threadIdx.x / kFinCols;
@@ -153,6 +160,7 @@ __global__ void __launch_bounds__(256) k_bn_combine(const float* __restrict__ pa
     m2 += s_m2[k][cc] + delta * delta * cnt * nb / tot;
     cnt = tot;
   }
+  mean += (double)pivot[c];
   const float var = (float)(m2 / cnt);
   mean_out[c] = (float)mean;
   rstd_out[c] = 1.0f / sqrtf(var + eps);
@@ -625,8 +633,8 @@ extern "C" int a3d_bn_train_forward(const float* x_dev, int ldx, int64_t n, int 
   (void)sums;
   (void)cb;
   k_bn_block_stats<<<blocks, kBnThreads, 0, st>>>(c);
-  k_bn_combine<<<(unsigned)((C + kFinCols - 1) / kFinCols), 256, 0, st>>>(partial, blocks, c.rows_per_block, (int)n, C, eps, save_mean_dev,
-                                                             save_rstd_dev, running_mean_dev, running_var_dev, momentum);
+  k_bn_combine<<<(unsigned)((C + kFinCols - 1) / kFinCols), 256, 0, st>>>(partial, x_dev, blocks, c.rows_per_block, (int)n, C, eps,
+                                                             save_mean_dev, save_rstd_dev, running_mean_dev, running_var_dev, momentum);
   ApplyArgs a;
   a.x = x_dev, a.mean = save_mean_dev, a.rstd = save_rstd_dev, a.gamma = gamma_dev, a.beta = beta_dev, a.res = res_dev;
   a.ldx = ldx, a.ldr = ldr, a.ldy = ldy, a.n = (int)n, a.C = C, a.relu = relu, a.y = y_dev, a.zero_row = y_zero_row;
