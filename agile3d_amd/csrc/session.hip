@@ -1,5 +1,6 @@
 // session.hip -- the headless interactive session around forward_mask: exact nearest rows, ray picking (vertices of a point
-// cloud, surfaces of a triangle mesh) and the full-resolution paint pass (gfx950).
+// cloud, surfaces of a triangle mesh), the rendered view (per pixel what the picks return) and the full-resolution paint
+// pass (gfx950).
 //
 // Replaces (reference file:line):
 //   find_nearest (torch.cdist over all voxel rows, again over all vertices)   interactive_tool/utils.py:27-29, gui.py:273-274
@@ -7,7 +8,8 @@
 //                                                                             k_pick_mesh (triangle meshes), rules of OURS
 //   pred[inverse_map], get_colors, the click cubes                            interactive_segmentation_user.py:83-84,125-140, gui.py:276-298,327
 //
-// All four are streaming passes over 12-byte rows, memory bound, no MFMA.  Nothing here uses an atomic on a result: every
+// The searches and the paint are streaming passes over 12-byte rows, memory bound, no MFMA; the rendered view bins primitives
+// to screen tiles and is bound by its exact tests (see "the rendered view" below).  Nothing here uses an atomic on a result: every
 // search is a minimum over a packed integer key whose order is total (distance bits, then row), reduced per wave with
 // shuffles, per workgroup through LDS, and over the workgroups by ONE second-stage block -- the result does not depend on
 // the order in which workgroups finish.  The tables of a call (sources, queries, ray) travel by value in the kernel
@@ -146,25 +148,30 @@ struct PickTab {
   float r2;
   a3d_pick_result* out;
 };
+// THE point test of the pick and of the rendered view: point (x, y, z), row i, against the ray (o, d), |d| = 1, and r^2.
+// Every operation rounded on its own, in the order written.  Folds a passing point's key into best.
+__device__ __forceinline__ void ses_point(const float* o, const float* d, float r2, float x, float y, float z, unsigned i,
+                                          PickKey& best) {
+#pragma clang fp contract(off)
+  const float vx = x - o[0], vy = y - o[1], vz = z - o[2];
+  const float tt = (vx * d[0] + vy * d[1]) + vz * d[2];
+  const float px = vx - tt * d[0], py = vy - tt * d[1], pz = vz - tt * d[2];
+  const float p2 = (px * px + py * py) + pz * pz;
+  if (tt > 0.f && p2 <= r2) {                  // (NaN fails both tests)
+    PickKey k;
+    k.a = ((unsigned long long)__float_as_uint(tt) << 32) | __float_as_uint(p2);
+    k.row = i;
+    best = pick_min(best, k);
+  }
+}
 __global__ __launch_bounds__(kSesBlock) void k_pick_ray(const PickTab t, unsigned long long* __restrict__ part_a,
                                                         unsigned* __restrict__ part_row) {
   const float* __restrict__ xyz = t.xyz;
   PickKey best;
   best.a = kNoKey, best.row = 0xffffffffu;
   const long long stride = (long long)gridDim.x * kSesBlock;
-  for (long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x; i < t.n; i += stride) {
-#pragma clang fp contract(off)
-    const float vx = xyz[3 * i] - t.o[0], vy = xyz[3 * i + 1] - t.o[1], vz = xyz[3 * i + 2] - t.o[2];
-    const float tt = (vx * t.d[0] + vy * t.d[1]) + vz * t.d[2];
-    const float px = vx - tt * t.d[0], py = vy - tt * t.d[1], pz = vz - tt * t.d[2];
-    const float p2 = (px * px + py * py) + pz * pz;
-    if (tt > 0.f && p2 <= t.r2) {              // (NaN fails both tests)
-      PickKey k;
-      k.a = ((unsigned long long)__float_as_uint(tt) << 32) | __float_as_uint(p2);
-      k.row = (unsigned)i;
-      best = pick_min(best, k);
-    }
-  }
+  for (long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x; i < t.n; i += stride)
+    ses_point(t.o, t.d, t.r2, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], (unsigned)i, best);
   best = pick_wave_min(best);
   __shared__ unsigned long long sa[kSesBlock / 64];
   __shared__ unsigned sr[kSesBlock / 64];
@@ -203,14 +210,31 @@ __global__ __launch_bounds__(64) void k_pick_finish(const PickTab t, const unsig
 }
 
 // ---- mesh pick: the first face a ray crosses -------------------------------------------------------------------------------
+struct RayShear {                             // a ray as the crossing test sees it
+  float o[3];
+  float sx, sy, sz;                           // the shear: d[kx] / d[kz], d[ky] / d[kz], 1 / d[kz] (fp32)
+  int kx, ky, kz;                             // the permutation: kz = the ray's dominant axis, kx / ky swapped when d[kz] < 0
+};
+// THE derivation of shear and permutation from a unit direction: on the host for a3d_pick_mesh's one ray, per pixel in the
+// rendered view (three correctly rounded fp32 divisions: the same bits on both sides).
+__host__ __device__ inline void ses_shear(const float* d, RayShear& r) {
+  int kz = 0;                                  // the dominant axis (the first of equals)
+  if (fabsf(d[1]) > fabsf(d[kz])) kz = 1;
+  if (fabsf(d[2]) > fabsf(d[kz])) kz = 2;
+  int kx = (kz + 1) % 3, ky = (kx + 1) % 3;
+  if (d[kz] < 0.f) {                           // keep the winding
+    const int s = kx;
+    kx = ky, ky = s;
+  }
+  r.kx = kx, r.ky = ky, r.kz = kz;
+  r.sx = d[kx] / d[kz], r.sy = d[ky] / d[kz], r.sz = 1.f / d[kz];
+}
 struct MeshTab {
   const float* xyz;
   long long n;
   const int32_t* faces;
   long long m;
-  float o[3];
-  float sx, sy, sz;                           // the shear: d[kx] / d[kz], d[ky] / d[kz], 1 / d[kz] (fp32, computed on the host)
-  int kx, ky, kz;                             // the permutation: kz = the ray's dominant axis, kx / ky swapped when d[kz] < 0
+  RayShear r;
   a3d_pick_mesh_result* out;
 };
 struct MeshFace {
@@ -219,14 +243,10 @@ struct MeshFace {
 // THE crossing test of both stages.  Returns 0 = no hit, 1 = hit (f filled), 2 = an index outside [0, n).  Every product,
 // sum and difference is rounded on its own (contraction off), in the order written: a numpy float32 restatement gives the
 // same bits.
-__device__ __forceinline__ int ses_face(const MeshTab& t, long long i, MeshFace& f, int32_t& i0, int32_t& i1, int32_t& i2) {
+// ses_face_test: the arithmetic, on three vertices wherever they lie (global memory, or LDS in the rendered view);
+// ses_face: the index checks in front of it.
+__device__ __forceinline__ int ses_face_test(const RayShear& t, const float* pa, const float* pb, const float* pc, MeshFace& f) {
 #pragma clang fp contract(off)
-  i0 = t.faces[3 * i], i1 = t.faces[3 * i + 1], i2 = t.faces[3 * i + 2];
-  if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= t.n || i1 >= t.n || i2 >= t.n) return 2;
-  if (i0 == i1 || i1 == i2 || i0 == i2) return 0;
-  const float* __restrict__ pa = t.xyz + 3 * (size_t)i0;
-  const float* __restrict__ pb = t.xyz + 3 * (size_t)i1;
-  const float* __restrict__ pc = t.xyz + 3 * (size_t)i2;
   const float a[3] = {pa[0] - t.o[0], pa[1] - t.o[1], pa[2] - t.o[2]};
   const float b[3] = {pb[0] - t.o[0], pb[1] - t.o[1], pb[2] - t.o[2]};
   const float c[3] = {pc[0] - t.o[0], pc[1] - t.o[1], pc[2] - t.o[2]};
@@ -256,6 +276,12 @@ __device__ __forceinline__ int ses_face(const MeshTab& t, long long i, MeshFace&
   if (!(tt > 0.f && tt < __builtin_inff())) return 0;   // (NaN fails the first test)
   f.U = U, f.V = V, f.W = W, f.det = det, f.t = tt;
   return 1;
+}
+__device__ __forceinline__ int ses_face(const MeshTab& t, long long i, MeshFace& f, int32_t& i0, int32_t& i1, int32_t& i2) {
+  i0 = t.faces[3 * i], i1 = t.faces[3 * i + 1], i2 = t.faces[3 * i + 2];
+  if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= t.n || i1 >= t.n || i2 >= t.n) return 2;
+  if (i0 == i1 || i1 == i2 || i0 == i2) return 0;
+  return ses_face_test(t.r, t.xyz + 3 * (size_t)i0, t.xyz + 3 * (size_t)i1, t.xyz + 3 * (size_t)i2, f);
 }
 __global__ __launch_bounds__(kSesBlock) void k_pick_mesh(const MeshTab t, unsigned long long* __restrict__ part_key,
                                                          unsigned* __restrict__ part_flag) {
@@ -385,6 +411,426 @@ static bool ses_ws_ok(const void* ws, size_t bytes, const char* what) {
   return true;
 }
 
+// ---- the rendered view: per pixel what the picks above return for the ray through the pixel's centre -----------------------
+// Three passes around one exclusive scan.  (1) k_render_bin: per primitive a conservative rectangle of tiles (render_rect_*),
+// kept in the workspace, its tiles counted; a primitive without a bound joins the everywhere-list.  (2) k_render_scan: one
+// block turns the counts into offsets and decides whether the pairs fit.  (3) k_render_fill: the rectangles again, ids into
+// the tiles' lists.  (4) k_render_tile_*: one workgroup per tile, one thread per pixel; the everywhere-list and the tile's
+// list pass through LDS in chunks of 256 primitives (vertices staged once per workgroup, then read by all 256 pixels at the
+// same address: a broadcast), every thread keeps its packed minimum in registers.  The minimum is order-free, so the order
+// in which the atomics of (3) fill a list does not reach the image.
+constexpr int kTile = A3D_RENDER_TILE;
+constexpr int kTilePixels = kTile * kTile;    // = the workgroup of the tile pass = the chunk staged in LDS
+constexpr int kMaxRectTiles = 256;            // a bound of more tiles: the primitive goes to the everywhere-list
+constexpr double kU = 5.9604644775390625e-8;  // 2^-24, unit roundoff of fp32
+
+struct RenderCam {
+  a3d_camera c;
+  double inv[9];                              // rows of [du dv d00]^-1: p -> (a, b, c), screen position (a / c, b / c)
+  double na, nb, nc;                          // the rows' norms
+  double dmax;                                // >= |d00 + u du + v dv| for every pixel
+  int tiles_x, tiles_y;
+};
+struct RenderWs {
+  unsigned* tile_count;                       // [tiles]       pairs of each tile; zeroed by the call
+  unsigned* tile_fill;                        // [tiles]       fill cursors; zeroed by the call
+  unsigned* every_count;                      // [1] (+ padding to 256 bytes); zeroed by the call
+  unsigned* tile_offset;                      // [tiles]
+  int4* rect;                                 // [n_primitives] tile rectangle tx0, ty0, tx1, ty1 (tx1 < tx0: none)
+  unsigned* every;                            // [n_primitives]
+  unsigned* pairs;                            // [pair_capacity]
+  size_t zero_bytes, bytes;
+};
+static RenderWs carve_render(void* base, long long n_prim, int width, int height, long long cap) {
+  RenderWs w;
+  size_t off = 0;
+  auto take = [&](size_t b) {
+    void* p = base ? (char*)base + off : nullptr;
+    off += align256(b);
+    return p;
+  };
+  const size_t tiles = (size_t)((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile);
+  w.tile_count = (unsigned*)take(tiles * 4);
+  w.tile_fill = (unsigned*)take(tiles * 4);
+  w.every_count = (unsigned*)take(4);
+  w.zero_bytes = off;
+  w.tile_offset = (unsigned*)take(tiles * 4);
+  w.rect = (int4*)take((size_t)(n_prim > 0 ? n_prim : 1) * 16);
+  w.every = (unsigned*)take((size_t)(n_prim > 0 ? n_prim : 1) * 4);
+  w.pairs = (unsigned*)take((size_t)(cap > 0 ? cap : 1) * 4);
+  w.bytes = off;
+  return w;
+}
+
+// The ray of pixel (u, v): the header's formula, one rounding per operation.
+__host__ __device__ inline void ses_pixel_ray(const a3d_camera& c, int u, int v, float* d) {
+#pragma clang fp contract(off)
+  const float fu = (float)u, fv = (float)v;
+  const float x = (c.d00[0] + fu * c.du[0]) + fv * c.dv[0];
+  const float y = (c.d00[1] + fu * c.du[1]) + fv * c.dv[1];
+  const float z = (c.d00[2] + fu * c.du[2]) + fv * c.dv[2];
+  const float len = sqrtf((x * x + y * y) + z * z);
+  d[0] = x / len, d[1] = y / len, d[2] = z / len;
+}
+
+// ---- the bound (tests/test_render_host.py restates it in numpy and holds it against the exact tests) ------
+// Screen positions are continuous pixel coordinates in which pixel (i, j)'s ray is the point (i, j).  A rectangle
+// [x0, x1] x [y0, y1] of them becomes the tiles of the pixels floor(x0) .. ceil(x1), clamped to the image.
+// Returns 0 = no pixel can pass, 1 = rect filled, 2 = no bound (everywhere).
+__device__ __forceinline__ int render_rect_tiles(const RenderCam& cam, double x0, double x1, double y0, double y1, int4& rect) {
+  if (!(x0 <= x1 && y0 <= y1)) return 2;      // (a NaN)
+  const double w1 = cam.c.width - 1, h1 = cam.c.height - 1;
+  if (x1 < 0. || y1 < 0. || x0 > w1 || y0 > h1) return 0;
+  const int px0 = (int)floor(fmax(x0, 0.)), px1 = (int)ceil(fmin(x1, w1));
+  const int py0 = (int)floor(fmax(y0, 0.)), py1 = (int)ceil(fmin(y1, h1));
+  rect.x = px0 / kTile, rect.y = py0 / kTile, rect.z = px1 / kTile, rect.w = py1 / kTile;
+  if ((rect.z - rect.x + 1) * (rect.w - rect.y + 1) > kMaxRectTiles) return 2;
+  return 1;
+}
+// A face with vertices A, B, C (fp32).  With p = vertex - o in double: R = the largest |coordinate| of the three p, g = the
+// distance from the origin to their bounding box.  A pixel's test passes only if its ray meets the triangle of the sheared
+// fp32 vertices, which lie within eta = 32 u R of the true ones (ray rounding included); the hit point q has |q| >= g - eta,
+// and q = c D(u, v) with |D| <= dmax, so c >= c_lo = 0.98 g / dmax.  g <= R / 1024: no bound.  The triangle is clipped to
+// c >= c_lo, its remaining corners projected, and the rectangle grown by what eta can move a corner at depth c_lo.
+__device__ __forceinline__ int render_rect_face(const RenderCam& cam, const float* A, const float* B, const float* C, int4& rect) {
+  double p[3][3];
+  double R = 0., g2 = 0.;
+  for (int k = 0; k < 3; ++k) {
+    p[0][k] = (double)A[k] - (double)cam.c.o[k], p[1][k] = (double)B[k] - (double)cam.c.o[k], p[2][k] = (double)C[k] - (double)cam.c.o[k];
+    if (p[0][k] != p[0][k] || p[1][k] != p[1][k] || p[2][k] != p[2][k]) return 0;   // a NaN vertex: the exact test never passes
+    const double lo = fmin(p[0][k], fmin(p[1][k], p[2][k])), hi = fmax(p[0][k], fmax(p[1][k], p[2][k]));
+    R = fmax(R, fmax(fabs(lo), fabs(hi)));
+    const double gap = fmax(0., fmax(lo, -hi));
+    g2 += gap * gap;
+  }
+  const double g = sqrt(g2);
+  if (!(R < 1e30) || !(g > R * (1. / 1024.))) return 2;
+  const double c_lo = 0.98 * g / cam.dmax, eta = 32. * kU * R;
+  double a[3], b[3], c[3];
+  for (int k = 0; k < 3; ++k) {
+    a[k] = cam.inv[0] * p[k][0] + cam.inv[1] * p[k][1] + cam.inv[2] * p[k][2];
+    b[k] = cam.inv[3] * p[k][0] + cam.inv[4] * p[k][1] + cam.inv[5] * p[k][2];
+    c[k] = cam.inv[6] * p[k][0] + cam.inv[7] * p[k][1] + cam.inv[8] * p[k][2];
+  }
+  double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
+  for (int k = 0; k < 3; ++k) {
+    const int j = k == 2 ? 0 : k + 1;
+    if (c[k] >= c_lo) {
+      const double x = a[k] / c[k], y = b[k] / c[k];
+      x0 = fmin(x0, x), x1 = fmax(x1, x), y0 = fmin(y0, y), y1 = fmax(y1, y);
+    }
+    if ((c[k] >= c_lo) != (c[j] >= c_lo)) {   // the edge k -> j crosses the plane c = c_lo
+      const double s = (c_lo - c[k]) / (c[j] - c[k]);
+      const double x = (a[k] + s * (a[j] - a[k])) / c_lo, y = (b[k] + s * (b[j] - b[k])) / c_lo;
+      x0 = fmin(x0, x), x1 = fmax(x1, x), y0 = fmin(y0, y), y1 = fmax(y1, y);
+    }
+  }
+  if (x0 > x1) return 0;                       // wholly behind c = c_lo
+  const double mx = 1. / 128. + (cam.na + 8192. * cam.nc) * eta / c_lo, my = 1. / 128. + (cam.nb + 8192. * cam.nc) * eta / c_lo;
+  return render_rect_tiles(cam, x0 - mx, x1 + mx, y0 - my, y1 + my, rect);
+}
+// A point P with radius r.  The fp32 test admits rays within r_eff = r (1 + 2^-10) + 128 u (|p| + r) of it.  |p| <= r_eff
+// (1 + 2^-10): no bound.  Else the ray's closest point q to P lies in the ball, at |q| >= t0 = sqrt(|p|^2 - r_eff^2), so its
+// c >= 0.98 t0 / dmax; the ball lies in the box (a +- r_eff na, b +- r_eff nb, c +- r_eff nc) of the camera's coordinates.
+__device__ __forceinline__ int render_rect_point(const RenderCam& cam, const float* P, double r, int4& rect) {
+  double p[3], n2 = 0.;
+  for (int k = 0; k < 3; ++k) {
+    p[k] = (double)P[k] - (double)cam.c.o[k];
+    n2 += p[k] * p[k];
+  }
+  if (!(n2 < 1e60)) return 0;                  // NaN or infinite: the exact test never passes
+  const double len = sqrt(n2);
+  const double reff = r * (1. + 1. / 1024.) + 128. * kU * (len + r);
+  if (!(len > reff * (1. + 1. / 1024.))) return 2;
+  const double t0 = sqrt(n2 - reff * reff);
+  const double a = cam.inv[0] * p[0] + cam.inv[1] * p[1] + cam.inv[2] * p[2];
+  const double b = cam.inv[3] * p[0] + cam.inv[4] * p[1] + cam.inv[5] * p[2];
+  const double c = cam.inv[6] * p[0] + cam.inv[7] * p[1] + cam.inv[8] * p[2];
+  const double ha = reff * cam.na, hb = reff * cam.nb, hc = reff * cam.nc;
+  const double c_lo = fmax(c - hc, 0.98 * t0 / cam.dmax), c_hi = c + hc;
+  if (!(c_hi >= c_lo)) return 0;               // behind the camera
+  const double x0 = fmin((a - ha) / c_lo, (a - ha) / c_hi), x1 = fmax((a + ha) / c_lo, (a + ha) / c_hi);
+  const double y0 = fmin((b - hb) / c_lo, (b - hb) / c_hi), y1 = fmax((b + hb) / c_lo, (b + hb) / c_hi);
+  return render_rect_tiles(cam, x0 - 1. / 128., x1 + 1. / 128., y0 - 1. / 128., y1 + 1. / 128., rect);
+}
+
+struct RenderTab {
+  RenderCam cam;
+  const float* xyz;
+  long long n;
+  const int32_t* faces;                       // a mesh's faces (may be NULL when m == 0)
+  int mesh;                                   // 1: faces of a mesh, 0: points of a cloud
+  long long m;                                // primitives: faces of a mesh, points of a cloud
+  float r2;
+  double radius;
+  a3d_render_out out;
+  long long cap;
+};
+__global__ __launch_bounds__(kSesBlock) void k_render_bin(const RenderTab t, const RenderWs w) {
+  const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (i >= t.m) return;
+  int4 rect = make_int4(1, 0, 0, 0);
+  int r = 0;
+  if (t.mesh) {
+    const int32_t i0 = t.faces[3 * i], i1 = t.faces[3 * i + 1], i2 = t.faces[3 * i + 2];
+    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= t.n || i1 >= t.n || i2 >= t.n)
+      atomicOr(&t.out.header_dev->flags, A3D_RENDER_BAD_INDEX);
+    else if (i0 != i1 && i1 != i2 && i0 != i2)
+      r = render_rect_face(t.cam, t.xyz + 3 * (size_t)i0, t.xyz + 3 * (size_t)i1, t.xyz + 3 * (size_t)i2, rect);
+  } else {
+    r = render_rect_point(t.cam, t.xyz + 3 * (size_t)i, t.radius, rect);
+  }
+  if (r == 2) w.every[atomicAdd(w.every_count, 1u)] = (unsigned)i;   // (at most one entry per primitive: < m)
+  if (r != 1) rect = make_int4(1, 0, 0, 0);
+  w.rect[i] = rect;
+  for (int ty = rect.y; ty <= rect.w; ++ty)
+    for (int tx = rect.x; tx <= rect.z; ++tx) atomicAdd(w.tile_count + ty * t.cam.tiles_x + tx, 1u);
+}
+// one block: exclusive scan of the tiles' counts (each thread a run of consecutive tiles), the verdict into the header
+__global__ __launch_bounds__(1024) void k_render_scan(const RenderTab t, const RenderWs w) {
+  const int tiles = t.cam.tiles_x * t.cam.tiles_y;
+  const int per = (tiles + 1023) / 1024;
+  const int lo = min((int)threadIdx.x * per, tiles), hi = min(lo + per, tiles);
+  unsigned long long sum = 0;
+  for (int k = lo; k < hi; ++k) sum += w.tile_count[k];
+  __shared__ unsigned long long part[1024];
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const unsigned long long add = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0ull;
+    __syncthreads();
+    part[threadIdx.x] += add;
+    __syncthreads();
+  }
+  const unsigned long long total = part[1023];
+  unsigned long long run = part[threadIdx.x] - sum;
+  if (total <= (unsigned long long)t.cap)     // (else the offsets are not used: no list is filled)
+    for (int k = lo; k < hi; ++k) {
+      w.tile_offset[k] = (unsigned)run;
+      run += w.tile_count[k];
+    }
+  if (threadIdx.x == 0) {
+    a3d_render_header* h = t.out.header_dev;
+    h->pairs_needed = (int64_t)total;
+    h->n_everywhere = (int32_t)*w.every_count;
+    if (total > (unsigned long long)t.cap) atomicOr(&h->flags, A3D_RENDER_OVERFLOW);
+  }
+}
+__global__ __launch_bounds__(kSesBlock) void k_render_fill(const RenderTab t, const RenderWs w) {
+  if (t.out.header_dev->flags & A3D_RENDER_OVERFLOW) return;
+  const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (i >= t.m) return;
+  const int4 rect = w.rect[i];
+  for (int ty = rect.y; ty <= rect.w; ++ty)
+    for (int tx = rect.x; tx <= rect.z; ++tx) {
+      const int tile = ty * t.cam.tiles_x + tx;
+      const unsigned long long pos = (unsigned long long)w.tile_offset[tile] + atomicAdd(w.tile_fill + tile, 1u);
+      if (pos < (unsigned long long)t.cap) w.pairs[pos] = (unsigned)i;   // (always: the counts are those of k_render_bin)
+    }
+}
+// The lists of a tile: the everywhere-list, then its own.  Entry e of the two, laid end to end.
+__device__ __forceinline__ unsigned render_list_entry(const RenderWs& w, unsigned n_every, unsigned offset, unsigned e) {
+  return e < n_every ? w.every[e] : w.pairs[offset + (e - n_every)];
+}
+__global__ __launch_bounds__(kTilePixels) void k_render_tile_mesh(const RenderTab t, const RenderWs w) {
+  if (t.out.header_dev->flags & A3D_RENDER_OVERFLOW) return;
+  __shared__ float vtx[kTilePixels][9];
+  __shared__ unsigned ids[kTilePixels];
+  const int tile = blockIdx.x;
+  const int px = (tile % t.cam.tiles_x) * kTile + (threadIdx.x & (kTile - 1));
+  const int py = (tile / t.cam.tiles_x) * kTile + (threadIdx.x >> 4);
+  const bool live = px < t.cam.c.width && py < t.cam.c.height;
+  RayShear ray;
+  float d[3];
+  ses_pixel_ray(t.cam.c, live ? px : 0, live ? py : 0, d);
+  ray.o[0] = t.cam.c.o[0], ray.o[1] = t.cam.c.o[1], ray.o[2] = t.cam.c.o[2];
+  ses_shear(d, ray);
+  const unsigned n_every = *w.every_count, total = n_every + w.tile_count[tile], offset = w.tile_offset[tile];
+  unsigned long long best = kNoKey;
+  for (unsigned base = 0; base < total; base += kTilePixels) {
+    const unsigned cnt = min((unsigned)kTilePixels, total - base);
+    __syncthreads();
+    if (threadIdx.x < cnt) {                   // (only faces whose indices k_render_bin found in range and distinct are listed)
+      const unsigned f = render_list_entry(w, n_every, offset, base + threadIdx.x);
+      ids[threadIdx.x] = f;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float* p = t.xyz + 3 * (size_t)t.faces[3 * (size_t)f + k];
+        vtx[threadIdx.x][3 * k] = p[0], vtx[threadIdx.x][3 * k + 1] = p[1], vtx[threadIdx.x][3 * k + 2] = p[2];
+      }
+    }
+    __syncthreads();
+    if (live)
+      for (unsigned k = 0; k < cnt; ++k) {
+        MeshFace f;
+        if (ses_face_test(ray, vtx[k], vtx[k] + 3, vtx[k] + 6, f) == 1) {
+          const unsigned long long key = ses_key(f.t, ids[k]);
+          best = key < best ? key : best;
+        }
+      }
+  }
+  if (!live) return;
+  const size_t at = (size_t)py * t.cam.c.width + px;
+  int32_t face = -1;
+  float tt = __builtin_inff(), u = 0.f, v = 0.f;
+  if (best != kNoKey) {
+    face = (int32_t)(unsigned)(best & 0xffffffffu);
+    tt = __uint_as_float((unsigned)(best >> 32));
+    if (t.out.u_dev || t.out.v_dev) {          // (the bits of the list pass again, as in k_pick_mesh_finish)
+      MeshTab mt;
+      mt.xyz = t.xyz, mt.n = t.n, mt.faces = t.faces, mt.m = t.m, mt.r = ray, mt.out = nullptr;
+      MeshFace f;
+      int32_t i0, i1, i2;
+      if (ses_face(mt, face, f, i0, i1, i2) == 1) u = f.V / f.det, v = f.W / f.det;
+    }
+  }
+  t.out.id_dev[at] = face;
+  t.out.t_dev[at] = tt;
+  if (t.out.u_dev) t.out.u_dev[at] = u;
+  if (t.out.v_dev) t.out.v_dev[at] = v;
+}
+__global__ __launch_bounds__(kTilePixels) void k_render_tile_points(const RenderTab t, const RenderWs w) {
+  if (t.out.header_dev->flags & A3D_RENDER_OVERFLOW) return;
+  __shared__ float pts[kTilePixels][3];
+  __shared__ unsigned ids[kTilePixels];
+  const int tile = blockIdx.x;
+  const int px = (tile % t.cam.tiles_x) * kTile + (threadIdx.x & (kTile - 1));
+  const int py = (tile / t.cam.tiles_x) * kTile + (threadIdx.x >> 4);
+  const bool live = px < t.cam.c.width && py < t.cam.c.height;
+  float d[3];
+  ses_pixel_ray(t.cam.c, live ? px : 0, live ? py : 0, d);
+  const float o[3] = {t.cam.c.o[0], t.cam.c.o[1], t.cam.c.o[2]};
+  const unsigned n_every = *w.every_count, total = n_every + w.tile_count[tile], offset = w.tile_offset[tile];
+  PickKey best;
+  best.a = kNoKey, best.row = 0xffffffffu;
+  for (unsigned base = 0; base < total; base += kTilePixels) {
+    const unsigned cnt = min((unsigned)kTilePixels, total - base);
+    __syncthreads();
+    if (threadIdx.x < cnt) {
+      const unsigned i = render_list_entry(w, n_every, offset, base + threadIdx.x);
+      ids[threadIdx.x] = i;
+      const float* p = t.xyz + 3 * (size_t)i;
+      pts[threadIdx.x][0] = p[0], pts[threadIdx.x][1] = p[1], pts[threadIdx.x][2] = p[2];
+    }
+    __syncthreads();
+    if (live)
+      for (unsigned k = 0; k < cnt; ++k) ses_point(o, d, t.r2, pts[k][0], pts[k][1], pts[k][2], ids[k], best);
+  }
+  if (!live) return;
+  const size_t at = (size_t)py * t.cam.c.width + px;
+  const bool hit = best.a != kNoKey;
+  t.out.id_dev[at] = hit ? (int32_t)best.row : -1;
+  t.out.t_dev[at] = hit ? __uint_as_float((unsigned)(best.a >> 32)) : __builtin_inff();
+}
+
+struct ShadeTab {
+  const int32_t* id;
+  const float *u, *v;
+  const int32_t* faces;
+  long long m, n;
+  const float* colors;
+  float bg[3];
+  uint8_t* rgb;
+  long long pixels;
+};
+__device__ __forceinline__ uint8_t shade_q(float c) { return (uint8_t)(fminf(fmaxf(c, 0.f), 1.f) * 255.f + 0.5f); }
+__global__ __launch_bounds__(kSesBlock) void k_render_shade(const ShadeTab t) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (i >= t.pixels) return;
+  const int32_t id = t.id[i];
+  float c[3] = {t.bg[0], t.bg[1], t.bg[2]};
+  if (!t.faces) {
+    if (id >= 0 && id < t.n)
+      for (int k = 0; k < 3; ++k) c[k] = t.colors[3 * (size_t)id + k];
+  } else if (id >= 0 && id < t.m) {
+    const int32_t i0 = t.faces[3 * (size_t)id], i1 = t.faces[3 * (size_t)id + 1], i2 = t.faces[3 * (size_t)id + 2];
+    if (i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < t.n && i1 < t.n && i2 < t.n) {
+      const float u = t.u[i], v = t.v[i], wgt = (1.f - u) - v;
+      for (int k = 0; k < 3; ++k)
+        c[k] = (wgt * t.colors[3 * (size_t)i0 + k] + u * t.colors[3 * (size_t)i1 + k]) + v * t.colors[3 * (size_t)i2 + k];
+    }
+  }
+  t.rgb[3 * i] = shade_q(c[0]), t.rgb[3 * i + 1] = shade_q(c[1]), t.rgb[3 * i + 2] = shade_q(c[2]);
+}
+
+// Host: what the bound needs from a camera, in double.  false: a camera the renders refuse.
+static bool render_camera(const a3d_camera* c, RenderCam& r) {
+  if (!c || c->width < 1 || c->height < 1 || c->width > A3D_RENDER_MAX_SIZE || c->height > A3D_RENDER_MAX_SIZE) return false;
+  double M[9];                                 // columns du, dv, d00
+  for (int k = 0; k < 3; ++k) {
+    if (!std::isfinite(c->o[k]) || !std::isfinite(c->d00[k]) || !std::isfinite(c->du[k]) || !std::isfinite(c->dv[k])) return false;
+    M[3 * k] = c->du[k], M[3 * k + 1] = c->dv[k], M[3 * k + 2] = c->d00[k];
+  }
+  const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
+  const double det = M[0] * c00 + M[1] * c01 + M[2] * c02;
+  double scale = 1.;
+  for (int col = 0; col < 3; ++col) scale *= std::sqrt(M[col] * M[col] + M[3 + col] * M[3 + col] + M[6 + col] * M[6 + col]);
+  if (!(std::fabs(det) > 1e-9 * scale)) return false;   // (du, dv, d00 close to one plane: no camera)
+  r.c = *c;
+  r.inv[0] = c00 / det, r.inv[1] = (M[2] * M[7] - M[1] * M[8]) / det, r.inv[2] = (M[1] * M[5] - M[2] * M[4]) / det;
+  r.inv[3] = c01 / det, r.inv[4] = (M[0] * M[8] - M[2] * M[6]) / det, r.inv[5] = (M[2] * M[3] - M[0] * M[5]) / det;
+  r.inv[6] = c02 / det, r.inv[7] = (M[1] * M[6] - M[0] * M[7]) / det, r.inv[8] = (M[0] * M[4] - M[1] * M[3]) / det;
+  r.na = std::sqrt(r.inv[0] * r.inv[0] + r.inv[1] * r.inv[1] + r.inv[2] * r.inv[2]);
+  r.nb = std::sqrt(r.inv[3] * r.inv[3] + r.inv[4] * r.inv[4] + r.inv[5] * r.inv[5]);
+  r.nc = std::sqrt(r.inv[6] * r.inv[6] + r.inv[7] * r.inv[7] + r.inv[8] * r.inv[8]);
+  double dmax = 0.;                            // |D| is convex in (u, v): its maximum over the image is at a corner
+  for (int corner = 0; corner < 4; ++corner) {
+    const double u = (corner & 1) ? c->width - 1 : 0, v = (corner & 2) ? c->height - 1 : 0;
+    double s = 0.;
+    for (int k = 0; k < 3; ++k) {
+      const double x = c->d00[k] + u * c->du[k] + v * c->dv[k];
+      s += x * x;
+    }
+    dmax = std::fmax(dmax, std::sqrt(s));
+  }
+  r.dmax = dmax * (1. + 1e-6);                 // (the fp32 direction's own rounding)
+  r.tiles_x = (c->width + kTile - 1) / kTile, r.tiles_y = (c->height + kTile - 1) / kTile;
+  return true;
+}
+static int render_run(const char* what, RenderTab& t, const a3d_camera* camera, const a3d_render_out* out, void* ws,
+                      size_t ws_bytes, hipStream_t st) {
+  if (!out || !out->id_dev || !out->t_dev || !out->header_dev) {
+    set_error("%s: id_dev, t_dev and header_dev are needed", what);
+    return A3D_ERR_INVALID;
+  }
+  if (!render_camera(camera, t.cam)) {
+    set_error("%s: bad camera (1..%d pixels each way; o, d00, du, dv finite, d00, du, dv linearly independent)", what,
+              A3D_RENDER_MAX_SIZE);
+    return A3D_ERR_INVALID;
+  }
+  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < carve_render(nullptr, t.m, camera->width, camera->height, 0).bytes) {
+    set_error("%s: workspace too small or misaligned (a3d_render_workspace_bytes, 256-byte aligned)", what);
+    return A3D_ERR_WORKSPACE;
+  }
+  // the pairs the workspace has room for: what is left behind the fixed tables
+  const size_t fixed = carve_render(nullptr, t.m, camera->width, camera->height, 0).bytes - 256;
+  t.cap = (long long)((ws_bytes - fixed) / 4);
+  if (t.cap > 0xffffffffll) t.cap = 0xffffffffll;
+  t.out = *out;
+  const RenderWs w = carve_render(ws, t.m, camera->width, camera->height, t.cap);
+  A3D_HIP_CHECK(hipMemsetAsync(ws, 0, w.zero_bytes, st));
+  A3D_HIP_CHECK(hipMemsetAsync(out->header_dev, 0, sizeof(a3d_render_header), st));
+  const unsigned blocks = (unsigned)((t.m + kSesBlock - 1) / kSesBlock);
+  if (blocks) {
+    k_render_bin<<<blocks, kSesBlock, 0, st>>>(t, w);
+    A3D_LAUNCH_CHECK();
+  }
+  k_render_scan<<<1, 1024, 0, st>>>(t, w);
+  A3D_LAUNCH_CHECK();
+  if (blocks) {
+    k_render_fill<<<blocks, kSesBlock, 0, st>>>(t, w);
+    A3D_LAUNCH_CHECK();
+  }
+  const unsigned tiles = (unsigned)(t.cam.tiles_x * t.cam.tiles_y);
+  if (t.mesh)
+    k_render_tile_mesh<<<tiles, kTilePixels, 0, st>>>(t, w);
+  else
+    k_render_tile_points<<<tiles, kTilePixels, 0, st>>>(t, w);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
 }  // namespace a3d
 
 using namespace a3d;
@@ -467,17 +913,8 @@ extern "C" int a3d_pick_mesh(const float* xyz_dev, int64_t n, const int32_t* fac
   if (!ses_ws_ok(workspace_dev, workspace_bytes, "a3d_pick_mesh")) return A3D_ERR_WORKSPACE;
   MeshTab t;
   t.xyz = xyz_dev, t.n = n, t.faces = faces_dev, t.m = m;
-  for (int k = 0; k < 3; ++k) t.o[k] = origin[k];
-  int kz = 0;                                  // the dominant axis (the first of equals)
-  if (fabsf(direction[1]) > fabsf(direction[kz])) kz = 1;
-  if (fabsf(direction[2]) > fabsf(direction[kz])) kz = 2;
-  int kx = (kz + 1) % 3, ky = (kx + 1) % 3;
-  if (direction[kz] < 0.f) {                   // keep the winding
-    const int s = kx;
-    kx = ky, ky = s;
-  }
-  t.kx = kx, t.ky = ky, t.kz = kz;
-  t.sx = direction[kx] / direction[kz], t.sy = direction[ky] / direction[kz], t.sz = 1.f / direction[kz];
+  for (int k = 0; k < 3; ++k) t.r.o[k] = origin[k];
+  ses_shear(direction, t.r);
   t.out = result_dev;
   const SesWs w = carve_session(workspace_dev);
   const int nb = ses_blocks(m);
@@ -505,6 +942,66 @@ extern "C" int a3d_session_paint(const a3d_session_paint_args* args, void* strea
   if (a.n_full == 0) return A3D_OK;
   const long long want = (a.n_full + kSesBlock - 1) / kSesBlock;
   k_session_paint<<<(unsigned)(want < 2048 ? want : 2048), kSesBlock, 0, st>>>(a);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" size_t a3d_render_workspace_bytes(int64_t n_primitives, int width, int height, int64_t pair_capacity) {
+  if (n_primitives < 0 || pair_capacity < 0 || width < 1 || height < 1 || width > A3D_RENDER_MAX_SIZE || height > A3D_RENDER_MAX_SIZE)
+    return 0;
+  return carve_render(nullptr, n_primitives, width, height, pair_capacity).bytes;
+}
+
+extern "C" int a3d_render_camera_bounds(const a3d_camera* camera, double* out13) {
+  RenderCam r;
+  if (!out13 || !render_camera(camera, r)) {
+    set_error("a3d_render_camera_bounds: bad camera");
+    return A3D_ERR_INVALID;
+  }
+  for (int k = 0; k < 9; ++k) out13[k] = r.inv[k];
+  out13[9] = r.na, out13[10] = r.nb, out13[11] = r.nc, out13[12] = r.dmax;
+  return A3D_OK;
+}
+
+extern "C" int a3d_render_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const a3d_camera* camera,
+                               const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (n < 0 || n >= (1ll << 31) || m < 0 || m >= (1ll << 31) || (n && !xyz_dev) || (m && !faces_dev)) {
+    set_error("a3d_render_mesh: bad arguments (n=%lld m=%lld)", (long long)n, (long long)m);
+    return A3D_ERR_INVALID;
+  }
+  RenderTab t;
+  memset(&t, 0, sizeof(t));
+  t.xyz = xyz_dev, t.n = n, t.faces = faces_dev, t.mesh = 1, t.m = m;
+  return render_run("a3d_render_mesh", t, camera, out, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int a3d_render_points(const float* xyz_dev, int64_t n, float radius, const a3d_camera* camera,
+                                 const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (n < 0 || n >= (1ll << 31) || (n && !xyz_dev) || !(radius >= 0.f) || !std::isfinite(radius)) {
+    set_error("a3d_render_points: bad arguments (n=%lld radius=%g)", (long long)n, (double)radius);
+    return A3D_ERR_INVALID;
+  }
+  RenderTab t;
+  memset(&t, 0, sizeof(t));
+  t.xyz = xyz_dev, t.n = n, t.faces = nullptr, t.mesh = 0, t.m = n;
+  t.r2 = radius * radius, t.radius = radius;
+  return render_run("a3d_render_points", t, camera, out, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int a3d_render_shade(const int32_t* id_dev, const float* u_dev, const float* v_dev, const int32_t* faces_dev, int64_t m,
+                                const float* colors_dev, int64_t n, const float* background, uint8_t* rgb_dev, int width,
+                                int height, void* stream) {
+  if (!id_dev || !rgb_dev || !background || width < 1 || height < 1 || width > A3D_RENDER_MAX_SIZE || height > A3D_RENDER_MAX_SIZE ||
+      n < 0 || m < 0 || (n && !colors_dev) || (faces_dev && (!u_dev || !v_dev))) {
+    set_error("a3d_render_shade: bad arguments (%d x %d, n=%lld m=%lld; a mesh needs u_dev and v_dev)", width, height,
+              (long long)n, (long long)m);
+    return A3D_ERR_INVALID;
+  }
+  ShadeTab t;
+  t.id = id_dev, t.u = u_dev, t.v = v_dev, t.faces = faces_dev, t.m = m, t.n = n, t.colors = colors_dev, t.rgb = rgb_dev;
+  for (int k = 0; k < 3; ++k) t.bg[k] = background[k];
+  t.pixels = (long long)width * height;
+  k_render_shade<<<(unsigned)((t.pixels + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

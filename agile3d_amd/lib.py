@@ -129,6 +129,24 @@ class SessionPaintArgs(C.Structure):
                 ("err_dev", C.c_void_p)]
 
 
+class Camera(C.Structure):
+    """a3d_camera: pixel (u, v)'s ray starts at o and runs along normalize(d00 + u du + v dv), evaluated in fp32."""
+    _fields_ = [("o", C.c_float * 3), ("d00", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
+                ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class RenderHeader(C.Structure):
+    """a3d_render_header: flags (bit 0 = a face index out of range, bit 1 = pair capacity too small, images untouched),
+    the primitives every pixel tested, the (tile, primitive) pairs the call needs."""
+    _fields_ = [("flags", C.c_int32), ("n_everywhere", C.c_int32), ("pairs_needed", C.c_int64)]
+
+
+class RenderOut(C.Structure):
+    """a3d_render_out: the images of a3d_render_mesh / a3d_render_points (u_dev, v_dev optional) and the header."""
+    _fields_ = [("id_dev", C.c_void_p), ("t_dev", C.c_void_p), ("u_dev", C.c_void_p), ("v_dev", C.c_void_p),
+                ("header_dev", C.c_void_p)]
+
+
 class ClickCluster(C.Structure):
     _fields_ = [("cluster_id", C.c_int32), ("row", C.c_int32), ("label", C.c_int32), ("pred", C.c_int32),
                 ("error_size", C.c_float)]
@@ -137,6 +155,9 @@ class ClickCluster(C.Structure):
 A3D_MAX_CLICKS = 256
 A3D_NEAREST_MAX_QUERIES = 64
 A3D_NEAREST_MAX_SOURCES = 4
+A3D_RENDER_MAX_SIZE = 4096
+A3D_RENDER_TILE = 16
+A3D_RENDER_BAD_INDEX, A3D_RENDER_OVERFLOW = 1, 2
 PROF_DENSE = 11
 PROF_NAMES = ["spconv", "splitk_epilogue", "stem", "c2s_attn", "query_chain", "s2c_attn", "ln_mask", "posenc",
               "scene_sort_levels", "scene_tables", "click_simulator", "dense_gemm"]
@@ -318,6 +339,14 @@ SYMBOLS = {
     "a3d_pick_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_session_paint": (C.c_int, [C.POINTER(SessionPaintArgs), C.c_void_p]),
+    "a3d_render_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int64]),
+    "a3d_render_camera_bounds": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_double)]),
+    "a3d_render_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(Camera), C.POINTER(RenderOut),
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_render_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.POINTER(Camera), C.POINTER(RenderOut), C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
+    "a3d_render_shade": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                   C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 
 _lib = None

@@ -8,6 +8,8 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``):
 
     pointer ray -> clicked point        a3d_pick_ray       (the GUI renders a depth image and unprojects, gui.py:247-271)
                                         a3d_pick_mesh      (the same for a triangle mesh: the first SURFACE under the pointer)
+    the view of the labelled scan       a3d_render_mesh / a3d_render_points / a3d_render_shade  (Open3D's renderer in the
+                                        GUI): id, depth and colour images, pixel by pixel what the two picks return
     find_nearest, twice per click       a3d_nearest_rows   (utils.py:27-29: two full torch.cdist calls; here exact)
     argmax + clicked rows               a3d_argmax_labels  (interactive_segmentation_user.py:78-81)
     pred[inverse_map], colours, cubes   a3d_session_paint  (:83-84,125-140; gui.py:276-298,327)
@@ -117,6 +119,47 @@ def ray_from_pixel(u, v, intrinsic, extrinsic):
     return -np.linalg.solve(rot, trans), d / np.linalg.norm(d)
 
 
+def camera_from_matrices(intrinsic, extrinsic, width, height):
+    """The ``lib.Camera`` (``a3d_camera``) of a pinhole camera in the conventions of ``ray_from_pixel``: ``intrinsic`` 3 x 3
+    (fx, fy, cx, cy), ``extrinsic`` 4 x 4 world-to-camera looking along +z, pixels sampled at their centres.  ``o`` = the
+    camera centre, ``d00`` = the unnormalised world direction of pixel (0, 0)'s centre (its camera-space z is 1), ``du`` /
+    ``dv`` = its change per column / row.  Computed in float64, rounded to the fp32 fields once.  Pure numpy."""
+    k = np.asarray(intrinsic, dtype=np.float64)
+    e = np.asarray(extrinsic, dtype=np.float64)
+    if k.shape != (3, 3) or e.shape != (4, 4):
+        raise ValueError("intrinsic must be 3 x 3 and extrinsic 4 x 4 (world to camera)")
+    if int(width) != width or int(height) != height or not (1 <= width <= L.A3D_RENDER_MAX_SIZE
+                                                             and 1 <= height <= L.A3D_RENDER_MAX_SIZE):
+        raise ValueError(f"width and height must be integers in 1 .. {L.A3D_RENDER_MAX_SIZE}")
+    if not (np.isfinite(k).all() and np.isfinite(e).all()) or k[0, 0] == 0 or k[1, 1] == 0:
+        raise ValueError("intrinsic and extrinsic must be finite, fx and fy not zero")
+    rot, trans = e[:3, :3], e[:3, 3]
+    cols = np.array([[1.0 / k[0, 0], 0.0, (0.5 - k[0, 2]) / k[0, 0]],
+                     [0.0, 1.0 / k[1, 1], (0.5 - k[1, 2]) / k[1, 1]],
+                     [0.0, 0.0, 1.0]])                 # camera-space du, dv, d00 as columns
+    world = np.linalg.solve(rot, cols)
+    cam = L.Camera()
+    cam.o[:] = [float(x) for x in (-np.linalg.solve(rot, trans)).astype(np.float32)]
+    cam.du[:] = [float(x) for x in world[:, 0].astype(np.float32)]
+    cam.dv[:] = [float(x) for x in world[:, 1].astype(np.float32)]
+    cam.d00[:] = [float(x) for x in world[:, 2].astype(np.float32)]
+    cam.width, cam.height = int(width), int(height)
+    return cam
+
+
+class RenderResult:
+    """What ``render()`` returns.  Device tensors: ``ids`` int32 [h, w] (face of a mesh, vertex of a cloud, -1 = nothing),
+    ``t`` fp32 [h, w] (+inf = nothing), ``rgb`` uint8 [h, w, 3], on a mesh ``u`` and ``v`` fp32 [h, w] (else ``None``).
+    ``camera``: the ``lib.Camera`` rendered.  ``mesh``: whether ids are faces.  ``pairs`` and ``n_everywhere``: the (tile,
+    primitive) pairs of the call and the primitives every pixel tested."""
+
+    __slots__ = ("ids", "t", "rgb", "u", "v", "camera", "mesh", "pairs", "n_everywhere")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
 class InteractiveSession:
     """The headless counterpart of ``UserInteractiveSegmentationModel`` plus the GUI's click state.
 
@@ -165,9 +208,11 @@ class InteractiveSession:
         self._coords_host = None
         self._backbone = None
         self._mask_host = None
+        self._render_ws = None                      # scratch of render(): kept per scene, grown when a view needs more pairs
         self._reset_clicks()
 
     def _reset_clicks(self):
+        self._colors_last = None                    # colours of the last infer / preview: what render() shows by default
         self.click_idx = {"0": []}
         self.click_time_idx = {"0": []}
         self.click_positions = {"0": []}
@@ -303,6 +348,87 @@ class InteractiveSession:
             return None
         return [float(v) for v in host[1:4].view(np.float32)]
 
+    # ------------------------------------------------------------------ the view
+    def render(self, intrinsic, extrinsic, width, height, colors=None, radius=None, background=(1.0, 1.0, 1.0)):
+        """Id, depth and colour images of the scene for a pinhole camera (``camera_from_matrices``): pixel by pixel what
+        ``pick`` returns for the ray through the pixel's centre -- faces when the scene has them (``a3d_render_mesh``),
+        else vertices within ``radius`` (default ``voxel_size``) of the ray (``a3d_render_points``).  ``colors`` [n, 3]
+        per-vertex colours on the device (default: those of the last ``infer`` / ``preview``, the scan's own before any);
+        ``background``: the colour of pixels that show nothing.  Returns a ``RenderResult``.  One small device-to-host
+        copy (the result header) per attempt; a view that needs more (tile, primitive) pairs than the scene's workspace
+        holds is rendered again with a larger one."""
+        self._need_scene()
+        cam = camera_from_matrices(intrinsic, extrinsic, width, height)
+        w, h = cam.width, cam.height
+        dev = self.device
+        bg = _f3(background, "background")
+        n = self.coords_full.shape[0]
+        col = self._colors_last if colors is None else colors
+        col = self.colors_full if col is None else col
+        if not torch.is_tensor(col) or col.device != dev or col.dtype != torch.float32 or tuple(col.shape) != (n, 3):
+            raise ValueError(f"colors must be a float32 tensor [{n}, 3] on the session's device")
+        col = col.contiguous()
+        mesh = self.faces is not None
+        n_prim = self.faces.shape[0] if mesh else n
+        r = self.voxel_size if radius is None else float(radius)
+        ids = torch.empty((h, w), dtype=torch.int32, device=dev)
+        t = torch.empty((h, w), dtype=torch.float32, device=dev)
+        u = torch.empty((h, w), dtype=torch.float32, device=dev) if mesh else None
+        v = torch.empty((h, w), dtype=torch.float32, device=dev) if mesh else None
+        rgb = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        header = self._small[16:20]
+        out = L.RenderOut(ids.data_ptr(), t.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
+                          header.data_ptr())
+        capacity = max(4 * n_prim, 1 << 16)
+        for attempt in range(3):
+            need = self.lib.a3d_render_workspace_bytes(n_prim, w, h, capacity)
+            if self._render_ws is None or self._render_ws.numel() < need:
+                self._render_ws = None              # (dropped first: the old and the new one need not live together)
+                self._render_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = self._render_ws
+            if mesh:
+                L.check(self.lib.a3d_render_mesh(self.coords_full.data_ptr(), n, self.faces.data_ptr(), n_prim, C.byref(cam),
+                                                 C.byref(out), ws.data_ptr(), ws.numel(), _stream(dev)), "a3d_render_mesh")
+            else:
+                L.check(self.lib.a3d_render_points(self.coords_full.data_ptr(), n, r, C.byref(cam), C.byref(out),
+                                                   ws.data_ptr(), ws.numel(), _stream(dev)), "a3d_render_points")
+            head = header.cpu().numpy()
+            flags, n_every, pairs = int(head[0]), int(head[1]), int(head[2:4].view(np.int64)[0])
+            if not flags & L.A3D_RENDER_OVERFLOW:
+                break
+            capacity = pairs + pairs // 8           # this view's pairs and room for the next one
+        else:
+            raise RuntimeError("a3d_render: the pair capacity it asked for did not suffice")
+        if flags & L.A3D_RENDER_BAD_INDEX:
+            raise RuntimeError("a3d_render_mesh: face indices out of range")
+        L.check(self.lib.a3d_render_shade(ids.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
+                                          self.faces.data_ptr() if mesh else None, n_prim if mesh else 0, col.data_ptr(), n,
+                                          bg.ctypes.data_as(C.POINTER(C.c_float)), rgb.data_ptr(), w, h, _stream(dev)),
+                "a3d_render_shade")
+        return RenderResult(ids=ids, t=t, rgb=rgb, u=u, v=v, camera=cam, mesh=mesh, pairs=pairs, n_everywhere=n_every)
+
+    def pick_from_render(self, result, u, v):
+        """The point a click through pixel ``(u, v)`` (column, row) of ``result`` takes -- what ``pick`` returns for that
+        pixel's ray: on a mesh the combination of the face's vertices with the rendered weights, (w a + u b) + v c in fp32
+        with w = (1 - u) - v; on a cloud the vertex; ``None`` where the pixel shows nothing."""
+        self._need_scene()
+        u, v = int(u), int(v)
+        h, w = result.ids.shape
+        if not (0 <= u < w and 0 <= v < h):
+            raise ValueError(f"pixel ({u}, {v}) outside the {w} x {h} image")
+        if result.mesh != (self.faces is not None):
+            raise ValueError("the render belongs to another scene")
+        idx = int(result.ids[v, u].cpu())
+        if idx < 0:
+            return None
+        if not result.mesh:
+            return [float(x) for x in self._coords_host[idx]]
+        f32 = np.float32
+        wu, wv = f32(result.u[v, u].cpu().numpy()), f32(result.v[v, u].cpu().numpy())
+        pa, pb, pc = self._coords_host[self.faces[idx].cpu().numpy()]
+        ww = f32(f32(1.0) - wu) - wv
+        return [float(x) for x in (ww * pa + wu * pb) + wv * pc]
+
     def nearest(self, point):
         """(voxel row, full-resolution vertex) nearest to ``point``: both searches in one launch pair, exact."""
         self._need_scene()
@@ -385,6 +511,7 @@ class InteractiveSession:
         labels_full, colors, keep = self._launch_paint(self._labels_qv, paint_cubes)
         if int(self._counts[3 * _N_IDS + 1:].cpu()[0]) & 0xffffffff:
             raise RuntimeError("a3d_session_paint: inverse_map or labels out of range")
+        self._colors_last = colors
         return labels_full, colors
 
     def infer(self, paint_cubes=False, logits=None):
@@ -423,6 +550,7 @@ class InteractiveSession:
         if host[3 * _N_IDS] or (int(host[3 * _N_IDS + 1]) & 0xffffffff):
             raise RuntimeError("inverse_map or labels out of range")
         self._labels_qv = labels_qv
+        self._colors_last = colors
         miou, per_obj = None, None
         if have_gt:
             t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())

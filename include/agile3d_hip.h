@@ -834,6 +834,78 @@ typedef struct a3d_session_paint_args {
 int    a3d_session_paint(const a3d_session_paint_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
+ * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a
+ * mesh the first face by a3d_pick_mesh's watertight test, on a point cloud the first vertex within the radius by
+ * a3d_pick_ray's key.  What the image shows as frontmost is what a click through that pixel hits, bit for bit.
+ *
+ * a3d_camera: the ray of pixel (u, v) = (column, row) starts at o; its direction is computed in fp32, every operation
+ * rounded on its own (no fma contraction), in exactly this order:
+ *     x = (d00[0] + (float)u * du[0]) + (float)v * dv[0]      (likewise y, z)
+ *     len = sqrtf((x*x + y*y) + z*z);   d = (x / len, y / len, z / len)
+ * with correctly rounded divide and sqrt.  d00 = the unnormalised direction of pixel (0, 0)'s centre, du / dv = its change
+ * per column / row.  1 <= width, height <= 4096; d00, du, dv finite and linearly independent.
+ *
+ * Primitives are binned to screen tiles of 16 x 16 pixels by a conservative bound, then every pixel runs
+ * the exact test on its tile's list; primitives whose bound cannot be established (the camera inside or within reach of
+ * their bounding box, a bound of more than 256 tiles) are tested by every pixel.  Pixel values do not depend on the order
+ * of the lists.  The library allocates nothing: workspace_dev holds a3d_render_workspace_bytes(n_primitives, width,
+ * height, pair_capacity) bytes (256-byte aligned), pair_capacity = the (tile, primitive) pairs it has room for.  A call
+ * that needs more writes NOTHING to the images, sets bit 1 of header flags and reports pairs_needed; call again with a
+ * workspace of that capacity.  Calls that share a workspace must be ordered.
+ * ------------------------------------------------------------------------------------------ */
+#define A3D_RENDER_MAX_SIZE 4096
+#define A3D_RENDER_TILE 16
+#define A3D_RENDER_BAD_INDEX 1       /* header flags bit 0: a face index outside 0..n-1 was skipped */
+#define A3D_RENDER_OVERFLOW  2       /* header flags bit 1: pair_capacity too small, images untouched */
+typedef struct a3d_camera {
+  float   o[3];
+  float   d00[3];
+  float   du[3];
+  float   dv[3];
+  int32_t width, height;
+} a3d_camera;
+typedef struct a3d_render_header {
+  int32_t flags;
+  int32_t n_everywhere;        /* primitives that every pixel tested (no bound) */
+  int64_t pairs_needed;        /* (tile, primitive) pairs of this call */
+} a3d_render_header;
+typedef struct a3d_render_out {
+  int32_t* id_dev;             /* [h][w] face (mesh) or vertex (points); -1 = nothing */
+  float*   t_dev;              /* [h][w] ray parameter of the hit; +inf = nothing */
+  float*   u_dev;              /* [h][w] or NULL (mesh only): weight of the face's second vertex, as a3d_pick_mesh computes it */
+  float*   v_dev;              /* [h][w] or NULL (mesh only): weight of its third vertex; both 0 where nothing was hit */
+  a3d_render_header* header_dev;
+} a3d_render_out;
+size_t a3d_render_workspace_bytes(int64_t n_primitives, int width, int height, int64_t pair_capacity);
+
+/* Host only, no GPU: what the bound derives from a camera, in double.  out[0..8] = the rows of the inverse of the matrix
+ * with columns du, dv, d00 (a world vector p relative to o has screen position (row0.p / row2.p, row1.p / row2.p)),
+ * out[9..11] = the rows' Euclidean norms, out[12] = an upper bound on the length of every pixel's unnormalised direction.
+ * Returns A3D_ERR_INVALID for a camera the renders refuse. */
+int    a3d_render_camera_bounds(const a3d_camera* camera, double* out13);
+
+/* Mesh: per pixel the face a3d_pick_mesh returns for that pixel's ray (smallest t, ties -> the lower face index,
+ * double-sided, edges inclusive; degenerate, NaN and out-of-range faces skipped, the last flagged), its t and -- when
+ * u_dev / v_dev are given -- the barycentric weights.  m == 0 is valid: an all-background image. */
+int    a3d_render_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const a3d_camera* camera,
+                       const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Point cloud: per pixel the vertex a3d_pick_ray returns for that pixel's ray and the radius (t > 0, perpendicular
+ * distance^2 <= r^2; smallest t, then smaller distance^2, then lower row) and its t.  n == 0 is valid.  u_dev / v_dev are
+ * ignored. */
+int    a3d_render_points(const float* xyz_dev, int64_t n, float radius, const a3d_camera* camera, const a3d_render_out* out,
+                         void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* rgb_dev uint8 [h][w][3] from an id image and per-vertex colours colors_dev fp32 [n][3].  faces_dev NULL: ids are
+ * vertices, the pixel takes the vertex's colour.  Else ids are faces and c = ((1 - u - v) c0 + u c1) + v c2 per channel in
+ * fp32 without contraction, 1 - u - v = (1 - u) - v.  id -1: background (HOST array of 3).  Quantisation:
+ * (uint8)(min(max(c, 0), 1) * 255 + 0.5f).  An id or a face's index outside its table gives the background. */
+int    a3d_render_shade(const int32_t* id_dev, const float* u_dev, const float* v_dev, const int32_t* faces_dev, int64_t m,
+                        const float* colors_dev, int64_t n, const float* background, uint8_t* rgb_dev, int width, int height,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mask losses (first piece of SURVEY.md section 8 row f-2).
  * Replaces: SetCriterion.loss_bce / loss_dice (models/criterion.py:14-110) for ONE sample and ONE
  * prediction level: losses_dev[0] = mean_i w_i * CE(logits_i, target_i), losses_dev[1] = mean_i w_i *

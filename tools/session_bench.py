@@ -15,7 +15,15 @@ A last stage times the MESH pick (``a3d_pick_mesh``) next to the vertex pick (``
 synthetic tessellated height field of about the scene's vertex count, vertices in scan order, two triangles per cell.
 Staged like ``pick`` above (the call and its small device-to-host copy, device events and host clock), and back to back
 (``--mesh-calls`` calls between two events, no copy: the two kernels of a call alone), with the bytes a call must move
-(12 B of indices per face + 12 B per vertex once) and the bytes it requests (12 + 36 B per face)."""
+(12 B of indices per face + 12 B per vertex once) and the bytes it requests (12 + 36 B per face).
+
+The RENDER stage (``a3d_render_mesh`` / ``a3d_render_points`` + ``a3d_render_shade``) draws the same height field, as a
+mesh and with its vertices as a cloud, at 640 x 480 and 1280 x 720 from two cameras: one above the field looking in, one
+40 cm over its middle looking along it (faces all around, across and behind the camera plane).  Per view: device events
+and host clock around the render and its header copy, the same around a call whose pair capacity is 1 (it bins, counts
+and stops: the cost of the binning passes before the fill), the (tile, primitive) pairs, pairs per tile, and the primitives
+that went to the everywhere-list.  What to check: the whole call should cost far more than the binning -- the tile pass,
+pixels x mean list length exact tests, is where the time belongs."""
 import argparse
 import json
 import os
@@ -58,12 +66,10 @@ class Timer:
                 {n: float(np.median(v[skip:])) for n, v in self.host.items()})
 
 
-def mesh_pick_stage(ses, n_vertices, reps, warmup, calls):
-    """Mesh pick and vertex pick on one tessellated height field of ~n_vertices vertices (see the module docstring)."""
-    import ctypes as C
-    lib, dev = ses.lib, ses.device
+def height_field(n_vertices, rng):
+    """(xyz fp32, faces int32, lattice coordinates g): a tessellated height field of ~n_vertices vertices 2 cm apart,
+    vertices in scan order, two triangles per cell."""
     side = int(round(np.sqrt(n_vertices)))
-    rng = np.random.default_rng(1)
     g = np.arange(side, dtype=np.float64) * 0.02
     x, y = np.meshgrid(g, g, indexing="ij")
     z = 0.3 * np.sin(0.9 * x) * np.cos(0.7 * y) + rng.uniform(-0.004, 0.004, x.shape)
@@ -71,6 +77,96 @@ def mesh_pick_stage(ses, n_vertices, reps, warmup, calls):
     idx = np.arange(side * side, dtype=np.int32).reshape(side, side)
     q00, q10, q01, q11 = idx[:-1, :-1], idx[1:, :-1], idx[:-1, 1:], idx[1:, 1:]
     faces = np.stack([np.stack([q00, q10, q11], -1), np.stack([q00, q11, q01], -1)], 2).reshape(-1, 3)   # cell by cell
+    return xyz, np.ascontiguousarray(faces), g
+
+
+def _look_at(eye, target):
+    z = (target - eye) / np.linalg.norm(target - eye)
+    x = np.cross(z, [0.0, 0.0, 1.0])
+    x /= np.linalg.norm(x)
+    ext = np.eye(4)
+    ext[:3, :3] = np.stack([x, np.cross(z, x), z])
+    ext[:3, 3] = -ext[:3, :3] @ eye
+    return ext
+
+
+def render_stage(ses, n_vertices, reps, warmup):
+    """The rendered view of the height field, mesh and cloud, two sizes, two cameras (see the module docstring)."""
+    import ctypes as C
+    from agile3d_amd import lib as L
+    from agile3d_amd.session import camera_from_matrices
+    lib, dev = ses.lib, ses.device
+    xyz, faces, g = height_field(n_vertices, np.random.default_rng(1))
+    xyz_dev, faces_dev = torch.from_numpy(xyz).to(dev), torch.from_numpy(faces).to(dev)
+    col_dev = torch.rand((len(xyz), 3), device=dev)
+    n, m = len(xyz), len(faces)
+    mid = 0.5 * g[-1]
+    cameras = {"outside": _look_at(np.array([mid, mid - 1.0, 4.0]), np.array([mid, mid, 0.0])),
+               "inside": _look_at(np.array([mid, mid, 0.4]), np.array([mid + 2.0, mid + 0.5, 0.2]))}
+    header = ses._small[16:20]
+    bg = np.ones(3, np.float32)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    out_rows = {}
+    print(f"\n== render: {n} vertices, {m} faces; median of {reps} ==")
+    for w, h in ((640, 480), (1280, 720)):
+        f = 0.5 * w / np.tan(np.radians(30.0))
+        intr = np.array([[f, 0, w / 2], [0, f, h / 2], [0, 0, 1.0]])
+        ids = torch.empty((h, w), dtype=torch.int32, device=dev)
+        t, u, v = (torch.empty((h, w), dtype=torch.float32, device=dev) for _ in range(3))
+        rgb = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        for cam_name, ext in cameras.items():
+            cam = camera_from_matrices(intr, ext, w, h)
+            for kind in ("mesh", "points"):
+                mesh = kind == "mesh"
+                n_prim = m if mesh else n
+                out = L.RenderOut(ids.data_ptr(), t.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
+                                  header.data_ptr())
+
+                def call(ws):
+                    if mesh:
+                        rc = lib.a3d_render_mesh(xyz_dev.data_ptr(), n, faces_dev.data_ptr(), m, C.byref(cam), C.byref(out),
+                                                 ws.data_ptr(), ws.numel(), stream)
+                    else:
+                        rc = lib.a3d_render_points(xyz_dev.data_ptr(), n, 0.02, C.byref(cam), C.byref(out), ws.data_ptr(),
+                                                   ws.numel(), stream)
+                    assert rc == 0, lib.a3d_last_error()
+                    return header.cpu().numpy()
+
+                def shade():
+                    rc = lib.a3d_render_shade(ids.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
+                                              faces_dev.data_ptr() if mesh else None, m if mesh else 0, col_dev.data_ptr(), n,
+                                              bg.ctypes.data_as(C.POINTER(C.c_float)), rgb.data_ptr(), w, h, stream)
+                    assert rc == 0, lib.a3d_last_error()
+
+                tiny = torch.empty(lib.a3d_render_workspace_bytes(n_prim, w, h, 1), dtype=torch.uint8, device=dev)
+                head = call(tiny)
+                pairs, n_every = int(head[2:4].view(np.int64)[0]), int(head[1])
+                ws = torch.empty(lib.a3d_render_workspace_bytes(n_prim, w, h, max(pairs, 1)), dtype=torch.uint8, device=dev)
+                tm = Timer(("render", "binning", "shade"))
+                for _ in range(warmup + reps):
+                    head = tm.run("render", lambda: call(ws))
+                    tm.run("binning", lambda: call(tiny))
+                    tm.run("shade", shade)
+                assert not int(head[0]) & L.A3D_RENDER_OVERFLOW
+                dev_ms, host_ms = tm.medians(warmup)
+                tiles = ((w + 15) // 16) * ((h + 15) // 16)
+                shown = int((ids >= 0).sum())
+                key = f"{w}x{h} {cam_name} {kind}"
+                out_rows[key] = {"device_ms": dev_ms, "host_ms": host_ms, "pairs": pairs, "tiles": tiles,
+                                 "pairs_per_tile": pairs / tiles, "everywhere": n_every, "pixels_shown": shown,
+                                 "exact_tests": (pairs / tiles + n_every) * w * h}
+                print(f"{key:28s} render {dev_ms['render']:.3f}/{host_ms['render']:.3f}  binning alone {dev_ms['binning']:.3f}/"
+                      f"{host_ms['binning']:.3f}  shade {dev_ms['shade']:.3f}/{host_ms['shade']:.3f} (device / host ms)   "
+                      f"pairs {pairs} = {pairs / tiles:.1f} per tile, everywhere {n_every}, {shown} of {w * h} pixels shown")
+    return {"vertices": n, "faces": m, "views": out_rows}
+
+
+def mesh_pick_stage(ses, n_vertices, reps, warmup, calls):
+    """Mesh pick and vertex pick on one tessellated height field of ~n_vertices vertices (see the module docstring)."""
+    import ctypes as C
+    lib, dev = ses.lib, ses.device
+    rng = np.random.default_rng(1)
+    xyz, faces, g = height_field(n_vertices, rng)
     xyz_dev, faces_dev = torch.from_numpy(xyz).to(dev), torch.from_numpy(np.ascontiguousarray(faces)).to(dev)
     n, m = len(xyz), len(faces)
     fp = C.POINTER(C.c_float)
@@ -137,6 +233,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--mesh-calls", type=int, default=200, help="calls between two events in the mesh-pick stage")
     ap.add_argument("--mesh-only", action="store_true", help="run the mesh-pick stage alone")
+    ap.add_argument("--render-only", action="store_true", help="run the render stage alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("session_bench needs the GPU")
@@ -157,7 +254,7 @@ def main():
     original = col.copy()
     centre = xyz.mean(0)
     result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
-    for n_clicks in (() if a.mesh_only else (1, 5, 10, 20)):
+    for n_clicks in (() if a.mesh_only or a.render_only else (1, 5, 10, 20)):
         ses.reset()
         objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
         targets = [xyz[rng.choice(np.flatnonzero(lab == inst[o - 1]))] for o in objs]
@@ -259,7 +356,10 @@ def main():
         print(f"outside forward_mask (host ms): session {entry['session_outside_forward_mask_host_ms']:.3f}  "
               f"baseline {entry['baseline_outside_forward_mask_host_ms']:.3f}   forward_mask {sh['forward_mask']:.3f}")
         print(f"whole click, staged (host ms): session {entry['session_click_ms']:.3f}  baseline {entry['baseline_click_ms']:.3f}")
-    result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
+    if not a.render_only:
+        result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
+    if not a.mesh_only:
+        result["render"] = render_stage(ses, n_full, a.reps, a.warmup)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
