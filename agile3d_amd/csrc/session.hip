@@ -734,24 +734,144 @@ struct ShadeTab {
   long long pixels;
 };
 __device__ __forceinline__ uint8_t shade_q(float c) { return (uint8_t)(fminf(fmaxf(c, 0.f), 1.f) * 255.f + 0.5f); }
-__global__ __launch_bounds__(kSesBlock) void k_render_shade(const ShadeTab t) {
+// THE base colour of pixel i, for the flat pass and the two shaded ones: the background, the vertex's colour (no faces) or
+// the face's interpolated one.  false: the pixel shows the background (id -1, or an id / a face's index outside its table).
+// On a mesh hit f holds the face's three vertices and u, v, wgt the pixel's weights.
+__device__ __forceinline__ bool shade_base(const ShadeTab& t, long long i, float* c, int32_t* f, float& u, float& v, float& wgt) {
 #pragma clang fp contract(off)
+  const int32_t id = t.id[i];
+  c[0] = t.bg[0], c[1] = t.bg[1], c[2] = t.bg[2];
+  if (!t.faces) {
+    if (!(id >= 0 && id < t.n)) return false;
+    for (int k = 0; k < 3; ++k) c[k] = t.colors[3 * (size_t)id + k];
+    return true;
+  }
+  if (!(id >= 0 && id < t.m)) return false;
+  f[0] = t.faces[3 * (size_t)id], f[1] = t.faces[3 * (size_t)id + 1], f[2] = t.faces[3 * (size_t)id + 2];
+  if (!(f[0] >= 0 && f[1] >= 0 && f[2] >= 0 && f[0] < t.n && f[1] < t.n && f[2] < t.n)) return false;
+  u = t.u[i], v = t.v[i], wgt = (1.f - u) - v;
+  for (int k = 0; k < 3; ++k)
+    c[k] = (wgt * t.colors[3 * (size_t)f[0] + k] + u * t.colors[3 * (size_t)f[1] + k]) + v * t.colors[3 * (size_t)f[2] + k];
+  return true;
+}
+__global__ __launch_bounds__(kSesBlock) void k_render_shade(const ShadeTab t) {
   const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
   if (i >= t.pixels) return;
-  const int32_t id = t.id[i];
-  float c[3] = {t.bg[0], t.bg[1], t.bg[2]};
-  if (!t.faces) {
-    if (id >= 0 && id < t.n)
-      for (int k = 0; k < 3; ++k) c[k] = t.colors[3 * (size_t)id + k];
-  } else if (id >= 0 && id < t.m) {
-    const int32_t i0 = t.faces[3 * (size_t)id], i1 = t.faces[3 * (size_t)id + 1], i2 = t.faces[3 * (size_t)id + 2];
-    if (i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < t.n && i1 < t.n && i2 < t.n) {
-      const float u = t.u[i], v = t.v[i], wgt = (1.f - u) - v;
-      for (int k = 0; k < 3; ++k)
-        c[k] = (wgt * t.colors[3 * (size_t)i0 + k] + u * t.colors[3 * (size_t)i1 + k]) + v * t.colors[3 * (size_t)i2 + k];
-    }
-  }
+  float c[3], u, v, wgt;
+  int32_t f[3];
+  shade_base(t, i, c, f, u, v, wgt);
   t.rgb[3 * i] = shade_q(c[0]), t.rgb[3 * i + 1] = shade_q(c[1]), t.rgb[3 * i + 2] = shade_q(c[2]);
+}
+
+// ---- lit shading (meshes): a double-sided light at the camera ---------------------------------------------------------------
+// THE RULE (ours; the header states it in full): base colour as above; the interpolated normal Nn = (w N0 + u N1) + v N2, the
+// pixel's unit ray d; k0 = min(|Nn . d| / |Nn|, 1), or 1 where |Nn|^2 is 0 or not finite; k = ambient + (1 - ambient) k0; each
+// channel c k.  Every operation rounded on its own, in the order written.
+struct LitTab {
+  ShadeTab s;                                 // (s.faces is never NULL here)
+  const float* normals;
+  a3d_camera cam;
+  float ambient;
+};
+__global__ __launch_bounds__(kSesBlock) void k_render_shade_lit(const LitTab t) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (i >= t.s.pixels) return;
+  float c[3], u, v, wgt;
+  int32_t f[3];
+  if (shade_base(t.s, i, c, f, u, v, wgt)) {
+    const float *n0 = t.normals + 3 * (size_t)f[0], *n1 = t.normals + 3 * (size_t)f[1], *n2 = t.normals + 3 * (size_t)f[2];
+    const float nx = (wgt * n0[0] + u * n1[0]) + v * n2[0];
+    const float ny = (wgt * n0[1] + u * n1[1]) + v * n2[1];
+    const float nz = (wgt * n0[2] + u * n1[2]) + v * n2[2];
+    const float l2 = (nx * nx + ny * ny) + nz * nz;
+    float k0 = 1.f;
+    if (l2 > 0.f && l2 < __builtin_inff()) {
+      float d[3];
+      ses_pixel_ray(t.cam, (int)(i % t.cam.width), (int)(i / t.cam.width), d);
+      const float dot = (nx * d[0] + ny * d[1]) + nz * d[2];
+      k0 = fminf(fabsf(dot) / sqrtf(l2), 1.f);
+    }
+    const float k = t.ambient + (1.f - t.ambient) * k0;
+    c[0] = c[0] * k, c[1] = c[1] * k, c[2] = c[2] * k;
+  }
+  t.s.rgb[3 * i] = shade_q(c[0]), t.s.rgb[3 * i + 1] = shade_q(c[1]), t.s.rgb[3 * i + 2] = shade_q(c[2]);
+}
+
+// ---- depth shading (point clouds have no normals): a pixel darkens by how far it lies behind its four neighbours -----------
+// THE RULE: s = (((0 + r(left)) + r(right)) + r(up)) + r(down), r(q) = max(t_p - t_q, 0) / t_p for a neighbour inside the
+// image that shows something (id >= 0), else 0; k = 1 / (1 + strength s); each channel c k.
+struct DepthTab {
+  ShadeTab s;
+  const float* t;
+  int width, height;
+  float strength;
+};
+__global__ __launch_bounds__(kSesBlock) void k_render_shade_depth(const DepthTab t) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (i >= t.s.pixels) return;
+  float c[3], u, v, wgt;
+  int32_t f[3];
+  if (shade_base(t.s, i, c, f, u, v, wgt)) {
+    const int px = (int)(i % t.width), py = (int)(i / t.width);
+    const float tp = t.t[i];
+    const long long q[4] = {i - 1, i + 1, i - t.width, i + t.width};
+    const bool in[4] = {px > 0, px + 1 < t.width, py > 0, py + 1 < t.height};
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float r = 0.f;
+      if (in[j] && t.s.id[q[j]] >= 0) r = fmaxf(tp - t.t[q[j]], 0.f) / tp;
+      s = s + r;
+    }
+    const float k = 1.f / (1.f + t.strength * s);
+    c[0] = c[0] * k, c[1] = c[1] * k, c[2] = c[2] * k;
+  }
+  t.s.rgb[3 * i] = shade_q(c[0]), t.s.rgb[3 * i + 1] = shade_q(c[1]), t.s.rgb[3 * i + 2] = shade_q(c[2]);
+}
+
+// ---- vertex normals: area-weighted sums of the incident faces' normals, in the order of the vertex's corner list -----------
+// One thread per vertex walks ITS list (offsets / corners, CSR, ascending by face then corner), so the sum is the sequential
+// one of the rule: no atomics, the same bits on every call.  A face's g = e1 x e2 is computed from the face alone, so the
+// three vertices of a face add the same three numbers.  A list entry outside [0, 3m) or a range outside the list is skipped,
+// never followed.
+struct NormalTab {
+  const float* xyz;
+  long long n;
+  const int32_t* faces;
+  long long m;
+  const int64_t* offsets;
+  const int32_t* corners;
+  float* out;
+};
+__global__ __launch_bounds__(kSesBlock) void k_vertex_normals(const NormalTab t) {
+#pragma clang fp contract(off)
+  const long long vtx = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (vtx >= t.n) return;
+  const long long lo = max((long long)t.offsets[vtx], 0ll), hi = min((long long)t.offsets[vtx + 1], 3 * t.m);
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+  for (long long e = lo; e < hi; ++e) {
+    const int32_t corner = t.corners[e];
+    if (corner < 0 || corner >= 3 * t.m) continue;
+    const long long face = corner / 3;
+    const int32_t a = t.faces[3 * face], b = t.faces[3 * face + 1], c = t.faces[3 * face + 2];
+    if (a < 0 || b < 0 || c < 0 || a >= t.n || b >= t.n || c >= t.n) continue;
+    const float *pa = t.xyz + 3 * (size_t)a, *pb = t.xyz + 3 * (size_t)b, *pc = t.xyz + 3 * (size_t)c;
+    const float e1x = pb[0] - pa[0], e1y = pb[1] - pa[1], e1z = pb[2] - pa[2];
+    const float e2x = pc[0] - pa[0], e2y = pc[1] - pa[1], e2z = pc[2] - pa[2];
+    const float gx = e1y * e2z - e1z * e2y, gy = e1z * e2x - e1x * e2z, gz = e1x * e2y - e1y * e2x;
+    const float inf = __builtin_inff();
+    if (!(fabsf(gx) < inf && fabsf(gy) < inf && fabsf(gz) < inf)) continue;   // (NaN fails the tests)
+    sx = sx + gx, sy = sy + gy, sz = sz + gz;
+  }
+  const float l2 = (sx * sx + sy * sy) + sz * sz;
+  float nx = 0.f, ny = 0.f, nz = 0.f;
+  if (l2 > 0.f && l2 < __builtin_inff()) {
+    const float len = sqrtf(l2);
+    nx = sx / len, ny = sy / len, nz = sz / len;
+  }
+  t.out[3 * vtx] = nx, t.out[3 * vtx + 1] = ny, t.out[3 * vtx + 2] = nz;
 }
 
 // Host: what the bound needs from a camera, in double.  false: a camera the renders refuse.
@@ -1002,6 +1122,70 @@ extern "C" int a3d_render_shade(const int32_t* id_dev, const float* u_dev, const
   for (int k = 0; k < 3; ++k) t.bg[k] = background[k];
   t.pixels = (long long)width * height;
   k_render_shade<<<(unsigned)((t.pixels + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" int a3d_render_shade_lit(const int32_t* id_dev, const float* u_dev, const float* v_dev, const int32_t* faces_dev,
+                                    int64_t m, const float* colors_dev, int64_t n, const float* normals_dev,
+                                    const a3d_camera* camera, float ambient, const float* background, uint8_t* rgb_dev,
+                                    void* stream) {
+  RenderCam rc;
+  if (!id_dev || !u_dev || !v_dev || !rgb_dev || !background || n < 0 || m < 0 || (m && !faces_dev) ||
+      (n && (!colors_dev || !normals_dev)) || !(ambient >= 0.f && ambient <= 1.f) || !render_camera(camera, rc)) {
+    set_error("a3d_render_shade_lit: bad arguments (n=%lld m=%lld ambient=%g; u_dev, v_dev, normals_dev and a camera the "
+              "renders accept are needed, ambient in [0, 1])", (long long)n, (long long)m, (double)ambient);
+    return A3D_ERR_INVALID;
+  }
+  LitTab t;
+  t.s.id = id_dev, t.s.u = u_dev, t.s.v = v_dev, t.s.faces = faces_dev, t.s.m = m, t.s.n = n, t.s.colors = colors_dev;
+  t.s.rgb = rgb_dev;
+  for (int k = 0; k < 3; ++k) t.s.bg[k] = background[k];
+  t.s.pixels = (long long)camera->width * camera->height;
+  t.normals = normals_dev, t.cam = *camera, t.ambient = ambient;
+  const unsigned blocks = (unsigned)((t.s.pixels + kSesBlock - 1) / kSesBlock);
+  if (m == 0) {                                // no face: no id is good.  The flat pass as a cloud without vertices: all background
+    t.s.faces = nullptr, t.s.n = 0;
+    k_render_shade<<<blocks, kSesBlock, 0, (hipStream_t)stream>>>(t.s);
+  } else {
+    k_render_shade_lit<<<blocks, kSesBlock, 0, (hipStream_t)stream>>>(t);
+  }
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" int a3d_render_shade_depth(const int32_t* id_dev, const float* t_dev, const float* u_dev, const float* v_dev,
+                                      const int32_t* faces_dev, int64_t m, const float* colors_dev, int64_t n, float strength,
+                                      const float* background, uint8_t* rgb_dev, int width, int height, void* stream) {
+  if (!id_dev || !t_dev || !rgb_dev || !background || width < 1 || height < 1 || width > A3D_RENDER_MAX_SIZE ||
+      height > A3D_RENDER_MAX_SIZE || n < 0 || m < 0 || (n && !colors_dev) || (faces_dev && (!u_dev || !v_dev)) ||
+      !(strength >= 0.f) || !std::isfinite(strength)) {
+    set_error("a3d_render_shade_depth: bad arguments (%d x %d, n=%lld m=%lld strength=%g; a mesh needs u_dev and v_dev)", width,
+              height, (long long)n, (long long)m, (double)strength);
+    return A3D_ERR_INVALID;
+  }
+  DepthTab t;
+  t.s.id = id_dev, t.s.u = u_dev, t.s.v = v_dev, t.s.faces = faces_dev, t.s.m = m, t.s.n = n, t.s.colors = colors_dev;
+  t.s.rgb = rgb_dev;
+  for (int k = 0; k < 3; ++k) t.s.bg[k] = background[k];
+  t.s.pixels = (long long)width * height;
+  t.t = t_dev, t.width = width, t.height = height, t.strength = strength;
+  k_render_shade_depth<<<(unsigned)((t.s.pixels + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" int a3d_vertex_normals(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const int64_t* offsets_dev,
+                                  const int32_t* corners_dev, float* normals_out_dev, void* stream) {
+  if (n < 0 || n >= (1ll << 31) || m < 0 || 3 * m >= (1ll << 31) || (n && (!xyz_dev || !offsets_dev || !normals_out_dev)) ||
+      (m && (!faces_dev || !corners_dev))) {
+    set_error("a3d_vertex_normals: bad arguments (n=%lld m=%lld; 3 m must fit int32)", (long long)n, (long long)m);
+    return A3D_ERR_INVALID;
+  }
+  if (n == 0) return A3D_OK;
+  NormalTab t;
+  t.xyz = xyz_dev, t.n = n, t.faces = faces_dev, t.m = m, t.offsets = offsets_dev, t.corners = corners_dev, t.out = normals_out_dev;
+  k_vertex_normals<<<(unsigned)((n + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

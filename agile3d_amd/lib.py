@@ -347,6 +347,14 @@ SYMBOLS = {
                                     C.c_size_t, C.c_void_p]),
     "a3d_render_shade": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                    C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "a3d_vertex_normals": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "a3d_render_shade_lit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.POINTER(Camera), C.c_float, C.POINTER(C.c_float), C.c_void_p,
+                                       C.c_void_p]),
+    "a3d_render_shade_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_int64, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p]),
 }
 
 _lib = None

@@ -10,6 +10,9 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``):
                                         a3d_pick_mesh      (the same for a triangle mesh: the first SURFACE under the pointer)
     the view of the labelled scan       a3d_render_mesh / a3d_render_points / a3d_render_shade  (Open3D's renderer in the
                                         GUI): id, depth and colour images, pixel by pixel what the two picks return
+    vertex normals, the lit material    a3d_vertex_normals / a3d_render_shade_lit / a3d_render_shade_depth  (gui.py:556-557,
+                                        135): render(lit=True); rules of ours, Open3D's lit material is not reproduced
+    the camera that frames the scene    default_view       (gui.py:561-565; host code)
     find_nearest, twice per click       a3d_nearest_rows   (utils.py:27-29: two full torch.cdist calls; here exact)
     argmax + clicked rows               a3d_argmax_labels  (interactive_segmentation_user.py:78-81)
     pred[inverse_map], colours, cubes   a3d_session_paint  (:83-84,125-140; gui.py:276-298,327)
@@ -147,13 +150,58 @@ def camera_from_matrices(intrinsic, extrinsic, width, height):
     return cam
 
 
+def vertex_corner_lists(faces, n):
+    """The incidence lists ``a3d_vertex_normals`` walks, in CSR form: ``(offsets int64 [n + 1], corners int32 [3 m])``.
+    Vertex ``v`` owns ``corners[offsets[v]:offsets[v + 1]]``, each entry ``3 * face + corner``, ascending -- that is, by
+    face and then by corner; a vertex listed twice in one face appears twice, an isolated vertex has an empty range.
+    Corners whose index lies outside ``[0, n)`` belong to no vertex: they sit behind ``offsets[n]``.  One stable sort of
+    the ``3 m`` vertex indices.  Pure numpy."""
+    f = np.asarray(faces).reshape(-1).astype(np.int64)
+    n = int(n)
+    if 3 * (f.size // 3) != f.size or f.size >= 1 << 31:
+        raise ValueError("faces must be [m, 3] with 3 m < 2^31")
+    key = np.where((f >= 0) & (f < n), f, n)
+    corners = np.argsort(key, kind="stable").astype(np.int32)
+    offsets = np.searchsorted(key[corners], np.arange(n + 1), side="left").astype(np.int64)
+    return offsets, corners
+
+
+def framing_view(coords, width, height, fov_deg=35.0):
+    """``(intrinsic 3 x 3, extrinsic 4 x 4)`` of a pinhole camera that frames the points ``coords`` [n, 3], in the
+    conventions of ``camera_from_matrices``; float64, pure numpy.  The camera looks at the centre of the bounding box from
+    ``centre + (0, -dist, 0)`` with +z up: rotation rows right (1, 0, 0), down (0, 0, -1), forward (0, 1, 0).
+    ``fov_deg`` is the vertical field of view: ``fx = fy = (height / 2) / tan(fov / 2)``, ``cx = width / 2``,
+    ``cy = height / 2``.  ``dist = R / sin(min(fov_v, fov_h) / 2)`` with ``R`` the largest distance of a point from the
+    centre: the bounding sphere fits the narrower of the two fields of view, so every point has camera-space z > 0 and
+    projects inside the image.  Rows with a non-finite coordinate are ignored; a single point is framed from 1 away."""
+    p = np.asarray(coords, dtype=np.float64).reshape(-1, 3)
+    p = p[np.isfinite(p).all(1)]
+    if int(width) != width or int(height) != height or width < 1 or height < 1:
+        raise ValueError("width and height must be positive integers")
+    if not (np.isfinite(fov_deg) and 0.0 < fov_deg < 180.0):
+        raise ValueError("fov_deg must lie in (0, 180)")
+    if len(p) == 0:
+        raise ValueError("no finite point to frame")
+    centre = 0.5 * (p.min(0) + p.max(0))
+    radius = float(np.sqrt(((p - centre) ** 2).sum(1).max()))
+    fov_v = np.radians(float(fov_deg))
+    f = 0.5 * height / np.tan(0.5 * fov_v)
+    fov_h = 2.0 * np.arctan(0.5 * width / f)
+    dist = radius / np.sin(0.5 * min(fov_v, fov_h)) if radius > 0 else 1.0
+    rot = np.array([[1.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]])
+    ext = np.eye(4)
+    ext[:3, :3] = rot
+    ext[:3, 3] = -rot @ (centre + np.array([0.0, -dist, 0.0]))
+    return np.array([[f, 0.0, 0.5 * width], [0.0, f, 0.5 * height], [0.0, 0.0, 1.0]]), ext
+
+
 class RenderResult:
     """What ``render()`` returns.  Device tensors: ``ids`` int32 [h, w] (face of a mesh, vertex of a cloud, -1 = nothing),
     ``t`` fp32 [h, w] (+inf = nothing), ``rgb`` uint8 [h, w, 3], on a mesh ``u`` and ``v`` fp32 [h, w] (else ``None``).
-    ``camera``: the ``lib.Camera`` rendered.  ``mesh``: whether ids are faces.  ``pairs`` and ``n_everywhere``: the (tile,
-    primitive) pairs of the call and the primitives every pixel tested."""
+    ``camera``: the ``lib.Camera`` rendered.  ``mesh``: whether ids are faces.  ``lit``: whether ``rgb`` is shaded.
+    ``pairs`` and ``n_everywhere``: the (tile, primitive) pairs of the call and the primitives every pixel tested."""
 
-    __slots__ = ("ids", "t", "rgb", "u", "v", "camera", "mesh", "pairs", "n_everywhere")
+    __slots__ = ("ids", "t", "rgb", "u", "v", "camera", "mesh", "lit", "pairs", "n_everywhere")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -205,6 +253,8 @@ class InteractiveSession:
         self.coords_full = self.colors_full = self.labels_full_ori = self.labels_qv_ori = None
         self.inverse_map = self.raw_coords_qv = None
         self.faces = None                           # int32 [m, 3] on the device: a triangle-mesh scene (pick meets its surface)
+        self._corner_lists = None                   # (offsets int64 [n + 1], corners int32 [3 m]) on the device: a mesh's incidence lists
+        self.normals = None                         # fp32 [n, 3] on the device: a mesh's vertex normals, computed by the first lit render
         self._coords_host = None
         self._backbone = None
         self._mask_host = None
@@ -228,7 +278,8 @@ class InteractiveSession:
         or ``None``.  With ``out_dir`` every ``infer()`` appends to ``out_dir/iou_record.csv`` and writes
         ``out_dir/masks/mask_*.npy`` and ``out_dir/clicks/click_*.npy``.  ``faces`` [m, 3] integer indices into
         ``coords_full`` make the scene a triangle mesh: ``pick`` then meets its surface (``ses.faces``, int32 on the
-        device; indices outside ``[0, n)`` raise ``ValueError``).  Everything of a previous scene is dropped."""
+        device; indices outside ``[0, n)`` raise ``ValueError``), and the vertices' incidence lists for the normals of a
+        lit ``render`` are built here, on the host (``vertex_corner_lists``).  Everything of a previous scene is dropped."""
         self._drop_scene()
         dev = self.device
         xyz = torch.as_tensor(np.asarray(coords_full) if not torch.is_tensor(coords_full) else coords_full)
@@ -240,7 +291,7 @@ class InteractiveSession:
         col = torch.as_tensor(np.asarray(colors_full) if not torch.is_tensor(colors_full) else colors_full)
         if tuple(col.shape) != (n, 3):
             raise ValueError("colors_full must be [n, 3]")
-        faces_dev = None
+        faces_dev = corner_lists = None
         if faces is not None:
             fa = np.asarray(faces.cpu() if torch.is_tensor(faces) else faces)
             if fa.ndim != 2 or fa.shape[1] != 3 or fa.dtype.kind not in "iu":
@@ -248,6 +299,7 @@ class InteractiveSession:
             if fa.size and (int(fa.min()) < 0 or int(fa.max()) >= n):     # checked once, here: the kernel only skips such faces
                 raise ValueError(f"faces: vertex indices outside [0, {n})")
             faces_dev = torch.from_numpy(np.ascontiguousarray(fa, dtype=np.int32)).to(dev)
+            corner_lists = tuple(torch.from_numpy(a).to(dev) for a in vertex_corner_lists(fa, n))   # once per scene, on the host
         xyz = xyz.to(dev).contiguous()
         col32 = col.to(dev).to(torch.float32).contiguous()
         coords_qv, unique_map, inverse_map = sparse_quantize(xyz, quantization_size=self.voxel_size, return_index=True,
@@ -267,6 +319,7 @@ class InteractiveSession:
         data = SparseTensor(coordinates=bc, features=col32[unique_map], device=dev)
         self._backbone = self.model.forward_backbone(data, raw_coordinates=self.raw_coords_qv)
         self.faces = faces_dev
+        self._corner_lists = corner_lists
         self.scene_name = str(name)
         self.out_dir = out_dir
         if out_dir is not None:
@@ -349,12 +402,40 @@ class InteractiveSession:
         return [float(v) for v in host[1:4].view(np.float32)]
 
     # ------------------------------------------------------------------ the view
-    def render(self, intrinsic, extrinsic, width, height, colors=None, radius=None, background=(1.0, 1.0, 1.0)):
+    def default_view(self, width, height, fov_deg=35.0):
+        """``(intrinsic, extrinsic)`` of a camera that frames the loaded scene -- ``render(*ses.default_view(w, h), w, h)``
+        shows all of it: ``framing_view`` on the host copy of the coordinates.  The counterpart of the GUI's camera setup
+        (gui.py:561-565), from which it departs: the GUI hard-codes the eye at (0, -15, 0) for data at the origin; here
+        the eye is ``centre + (0, -dist, 0)`` with ``dist`` from the scene's bounding sphere, wherever the scene lies."""
+        self._need_scene()
+        return framing_view(self._coords_host, width, height, fov_deg)
+
+    def _vertex_normals(self):
+        """``ses.normals`` of a mesh scene: ``a3d_vertex_normals`` once per scene, on first use."""
+        if self.normals is None:
+            n = self.coords_full.shape[0]
+            normals = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            offsets, corners = self._corner_lists
+            L.check(self.lib.a3d_vertex_normals(self.coords_full.data_ptr(), n, self.faces.data_ptr(), self.faces.shape[0],
+                                                offsets.data_ptr(), corners.data_ptr(), normals.data_ptr(),
+                                                _stream(self.device)), "a3d_vertex_normals")
+            self.normals = normals
+        return self.normals
+
+    def render(self, intrinsic, extrinsic, width, height, colors=None, radius=None, background=(1.0, 1.0, 1.0), lit=False,
+               ambient=0.35, depth_strength=8.0):
         """Id, depth and colour images of the scene for a pinhole camera (``camera_from_matrices``): pixel by pixel what
         ``pick`` returns for the ray through the pixel's centre -- faces when the scene has them (``a3d_render_mesh``),
         else vertices within ``radius`` (default ``voxel_size``) of the ray (``a3d_render_points``).  ``colors`` [n, 3]
         per-vertex colours on the device (default: those of the last ``infer`` / ``preview``, the scan's own before any);
-        ``background``: the colour of pixels that show nothing.  Returns a ``RenderResult``.  One small device-to-host
+        ``background``: the colour of pixels that show nothing.  ``lit=False``: flat colours (``a3d_render_shade``).
+        ``lit=True``: on a mesh the colours are lit from the camera, double-sided, by the vertex normals (``ses.normals``,
+        computed once per scene on first use; ``a3d_render_shade_lit``: colour x (``ambient`` + (1 - ``ambient``) |cos| of
+        the angle between the interpolated normal and the pixel's ray)); on a cloud, which has no normals, a pixel darkens
+        by how far it lies behind its four neighbours (``a3d_render_shade_depth``: colour / (1 + ``depth_strength`` x the
+        summed relative depth steps)).  ``ambient`` in [0, 1] and ``depth_strength`` >= 0 are used only when ``lit``; their
+        defaults, 0.35 and 8.0, are this project's settings, not the reference's (Open3D's lit material is not
+        reproduced).  Returns a ``RenderResult``.  One small device-to-host
         copy (the result header) per attempt; a view that needs more (tile, primitive) pairs than the scene's workspace
         holds is rendered again with a larger one."""
         self._need_scene()
@@ -362,6 +443,11 @@ class InteractiveSession:
         w, h = cam.width, cam.height
         dev = self.device
         bg = _f3(background, "background")
+        ambient, depth_strength = float(ambient), float(depth_strength)
+        if not 0.0 <= ambient <= 1.0:                   # (NaN fails both)
+            raise ValueError("ambient must lie in [0, 1]")
+        if not (np.isfinite(depth_strength) and depth_strength >= 0.0):
+            raise ValueError("depth_strength must be finite and >= 0")
         n = self.coords_full.shape[0]
         col = self._colors_last if colors is None else colors
         col = self.colors_full if col is None else col
@@ -401,11 +487,21 @@ class InteractiveSession:
             raise RuntimeError("a3d_render: the pair capacity it asked for did not suffice")
         if flags & L.A3D_RENDER_BAD_INDEX:
             raise RuntimeError("a3d_render_mesh: face indices out of range")
-        L.check(self.lib.a3d_render_shade(ids.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
-                                          self.faces.data_ptr() if mesh else None, n_prim if mesh else 0, col.data_ptr(), n,
-                                          bg.ctypes.data_as(C.POINTER(C.c_float)), rgb.data_ptr(), w, h, _stream(dev)),
-                "a3d_render_shade")
-        return RenderResult(ids=ids, t=t, rgb=rgb, u=u, v=v, camera=cam, mesh=mesh, pairs=pairs, n_everywhere=n_every)
+        bg_p = bg.ctypes.data_as(C.POINTER(C.c_float))
+        if lit and mesh:
+            L.check(self.lib.a3d_render_shade_lit(ids.data_ptr(), u.data_ptr(), v.data_ptr(), self.faces.data_ptr(), n_prim,
+                                                  col.data_ptr(), n, self._vertex_normals().data_ptr(), C.byref(cam), ambient,
+                                                  bg_p, rgb.data_ptr(), _stream(dev)), "a3d_render_shade_lit")
+        elif lit:
+            L.check(self.lib.a3d_render_shade_depth(ids.data_ptr(), t.data_ptr(), None, None, None, 0, col.data_ptr(), n,
+                                                    depth_strength, bg_p, rgb.data_ptr(), w, h, _stream(dev)),
+                    "a3d_render_shade_depth")
+        else:
+            L.check(self.lib.a3d_render_shade(ids.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
+                                              self.faces.data_ptr() if mesh else None, n_prim if mesh else 0, col.data_ptr(),
+                                              n, bg_p, rgb.data_ptr(), w, h, _stream(dev)), "a3d_render_shade")
+        return RenderResult(ids=ids, t=t, rgb=rgb, u=u, v=v, camera=cam, mesh=mesh, lit=bool(lit), pairs=pairs,
+                            n_everywhere=n_every)
 
     def pick_from_render(self, result, u, v):
         """The point a click through pixel ``(u, v)`` (column, row) of ``result`` takes -- what ``pick`` returns for that

@@ -906,6 +906,51 @@ int    a3d_render_shade(const int32_t* id_dev, const float* u_dev, const float* 
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Lighting the view (csrc/session.hip): per-vertex normals, a lit colour pass for meshes, a depth-based one for point
+ * clouds.  The counterpart of the GUI's compute_vertex_normals and its "defaultLit" material (gui.py:556-557, 135).
+ * Open3D's lit material (a sun plus image-based light) is not reproduced: THE RULES BELOW ARE THIS LIBRARY'S, as the pick
+ * rules are.  All arithmetic is fp32, every operation rounded on its own (no fma contraction), in exactly the order
+ * written, divide and sqrtf correctly rounded: a numpy float32 restatement gives the same bits.
+ *
+ * VERTEX NORMALS.  Every vertex has the list of its incident corners (face, corner), ascending by face, then by corner, in
+ * CSR form: offsets_dev int64 [n + 1], corners_dev int32 [3 m] holding 3 * face + corner (a vertex listed twice in a face
+ * appears twice).  For a face f = (a, b, c): e1 = P[b] - P[a], e2 = P[c] - P[a],
+ *     g = (e1y*e2z - e1z*e2y,  e1z*e2x - e1x*e2z,  e1x*e2y - e1y*e2x)          (area weighted, not normalised)
+ * A face contributes only if its three indices lie in 0..n-1 and all three components of g are finite.  Per component
+ *     s = (((0 + g_1) + g_2) + ...) in list order;    l2 = (sx*sx + sy*sy) + sz*sz
+ *     N = s / sqrtf(l2) per component if l2 > 0 and finite, else N = (0, 0, 0)
+ * (an isolated vertex, degenerate faces only, NaN).  One thread per vertex walks its own list: no atomics, two calls give
+ * the same bytes.  List entries outside 0..3m-1 and ranges outside the list are skipped.  normals_out_dev fp32 [n][3].
+ * No workspace.  3 m must fit int32.  The lists are the caller's to build (a stable sort of the 3 m vertex indices).
+ * ------------------------------------------------------------------------------------------ */
+int    a3d_vertex_normals(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const int64_t* offsets_dev,
+                          const int32_t* corners_dev, float* normals_out_dev, void* stream);
+
+/* Lit colour image of a MESH render: the inputs of a3d_render_shade (width and height are the camera's), the vertex
+ * normals normals_dev fp32 [n][3], the camera that rendered the ids and ambient in [0, 1].  Per pixel: the base colour c
+ * exactly as a3d_render_shade computes it; a pixel with id -1, or an id or a face's index outside its table, gets the
+ * background, unshaded.  Else, with the face's vertices 0, 1, 2 and w = (1 - u) - v,
+ *     Nn = (w*N0 + u*N1) + v*N2 per component;     l2 = (Nx*Nx + Ny*Ny) + Nz*Nz
+ *     d  = the pixel's unit ray direction by the a3d_camera rule above
+ *     k0 = fminf(fabsf((Nx*dx + Ny*dy) + Nz*dz) / sqrtf(l2), 1) if l2 > 0 and finite, else k0 = 1
+ *     k  = ambient + (1 - ambient) * k0;           each channel c * k, then a3d_render_shade's quantisation
+ * -- a double-sided light at the camera.  ambient == 1 gives k == 1 exactly: the image of a3d_render_shade, byte for byte.
+ * u_dev and v_dev are needed; faces_dev may be NULL only when m == 0 (every pixel the background). */
+int    a3d_render_shade_lit(const int32_t* id_dev, const float* u_dev, const float* v_dev, const int32_t* faces_dev, int64_t m,
+                            const float* colors_dev, int64_t n, const float* normals_dev, const a3d_camera* camera,
+                            float ambient, const float* background, uint8_t* rgb_dev, void* stream);
+
+/* Depth-shaded colour image, for POINT CLOUDS (which have no normals): the inputs of a3d_render_shade, the render's t image
+ * t_dev fp32 [h][w] and strength >= 0 (finite).  For a pixel p whose base colour c is not the background:
+ *     r(q) = fmaxf(t_p - t_q, 0) / t_p for a neighbour q inside the image whose id >= 0, else 0
+ *     s = (((0 + r(left)) + r(right)) + r(up)) + r(down);     k = 1 / (1 + strength * s);     each channel c * k
+ * -- a pixel darkens by how far it lies behind its neighbours.  strength == 0 gives a3d_render_shade's image byte for byte.
+ * faces_dev NULL: ids are vertices; else a mesh's images (u_dev, v_dev needed), shaded the same way. */
+int    a3d_render_shade_depth(const int32_t* id_dev, const float* t_dev, const float* u_dev, const float* v_dev,
+                              const int32_t* faces_dev, int64_t m, const float* colors_dev, int64_t n, float strength,
+                              const float* background, uint8_t* rgb_dev, int width, int height, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mask losses (first piece of SURVEY.md section 8 row f-2).
  * Replaces: SetCriterion.loss_bce / loss_dice (models/criterion.py:14-110) for ONE sample and ONE
  * prediction level: losses_dev[0] = mean_i w_i * CE(logits_i, target_i), losses_dev[1] = mean_i w_i *

@@ -23,7 +23,10 @@ mesh and with its vertices as a cloud, at 640 x 480 and 1280 x 720 from two came
 and host clock around the render and its header copy, the same around a call whose pair capacity is 1 (it bins, counts
 and stops: the cost of the binning passes before the fill), the (tile, primitive) pairs, pairs per tile, and the primitives
 that went to the everywhere-list.  What to check: the whole call should cost far more than the binning -- the tile pass,
-pixels x mean list length exact tests, is where the time belongs."""
+pixels x mean list length exact tests, is where the time belongs.  Every view is also shaded LIT, next to the flat shade
+and on the same images: the mesh with ``a3d_render_shade_lit``, the cloud with ``a3d_render_shade_depth``; the vertex
+normals (``a3d_vertex_normals``, once per scene in the session) and the host-side build of their incidence lists are timed
+once for the field.  The figure to read: lit shade time against flat shade time per view, with pixels and vertices."""
 import argparse
 import json
 import os
@@ -94,12 +97,30 @@ def render_stage(ses, n_vertices, reps, warmup):
     """The rendered view of the height field, mesh and cloud, two sizes, two cameras (see the module docstring)."""
     import ctypes as C
     from agile3d_amd import lib as L
-    from agile3d_amd.session import camera_from_matrices
+    from agile3d_amd.session import camera_from_matrices, vertex_corner_lists
     lib, dev = ses.lib, ses.device
     xyz, faces, g = height_field(n_vertices, np.random.default_rng(1))
     xyz_dev, faces_dev = torch.from_numpy(xyz).to(dev), torch.from_numpy(faces).to(dev)
     col_dev = torch.rand((len(xyz), 3), device=dev)
     n, m = len(xyz), len(faces)
+    # the normals of the field: the lists on the host (what load_scene pays once per scene), then the kernel
+    t0 = time.perf_counter()
+    offsets, corners = vertex_corner_lists(faces, n)
+    lists_host_ms = 1e3 * (time.perf_counter() - t0)
+    off_dev, cor_dev = torch.from_numpy(offsets).to(dev), torch.from_numpy(corners).to(dev)
+    normals_dev = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    stream0 = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def normals():
+        rc = lib.a3d_vertex_normals(xyz_dev.data_ptr(), n, faces_dev.data_ptr(), m, off_dev.data_ptr(), cor_dev.data_ptr(),
+                                    normals_dev.data_ptr(), stream0)
+        assert rc == 0, lib.a3d_last_error()
+
+    tn = Timer(("normals",))
+    for _ in range(warmup + reps):
+        tn.run("normals", normals)
+    normals_ms = {"device_ms": tn.medians(warmup)[0]["normals"], "host_ms": tn.medians(warmup)[1]["normals"],
+                  "lists_host_ms": lists_host_ms}
     mid = 0.5 * g[-1]
     cameras = {"outside": _look_at(np.array([mid, mid - 1.0, 4.0]), np.array([mid, mid, 0.0])),
                "inside": _look_at(np.array([mid, mid, 0.4]), np.array([mid + 2.0, mid + 0.5, 0.2]))}
@@ -108,6 +129,8 @@ def render_stage(ses, n_vertices, reps, warmup):
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     out_rows = {}
     print(f"\n== render: {n} vertices, {m} faces; median of {reps} ==")
+    print(f"vertex normals {normals_ms['device_ms']:.3f}/{normals_ms['host_ms']:.3f} (device / host ms), once per scene; their "
+          f"incidence lists on the host {lists_host_ms:.1f} ms")
     for w, h in ((640, 480), (1280, 720)):
         f = 0.5 * w / np.tan(np.radians(30.0))
         intr = np.array([[f, 0, w / 2], [0, f, h / 2], [0, 0, 1.0]])
@@ -138,15 +161,27 @@ def render_stage(ses, n_vertices, reps, warmup):
                                               bg.ctypes.data_as(C.POINTER(C.c_float)), rgb.data_ptr(), w, h, stream)
                     assert rc == 0, lib.a3d_last_error()
 
+                def shade_lit():
+                    if mesh:
+                        rc = lib.a3d_render_shade_lit(ids.data_ptr(), u.data_ptr(), v.data_ptr(), faces_dev.data_ptr(), m,
+                                                      col_dev.data_ptr(), n, normals_dev.data_ptr(), C.byref(cam), 0.35,
+                                                      bg.ctypes.data_as(C.POINTER(C.c_float)), rgb.data_ptr(), stream)
+                    else:
+                        rc = lib.a3d_render_shade_depth(ids.data_ptr(), t.data_ptr(), None, None, None, 0, col_dev.data_ptr(),
+                                                        n, 8.0, bg.ctypes.data_as(C.POINTER(C.c_float)), rgb.data_ptr(), w, h,
+                                                        stream)
+                    assert rc == 0, lib.a3d_last_error()
+
                 tiny = torch.empty(lib.a3d_render_workspace_bytes(n_prim, w, h, 1), dtype=torch.uint8, device=dev)
                 head = call(tiny)
                 pairs, n_every = int(head[2:4].view(np.int64)[0]), int(head[1])
                 ws = torch.empty(lib.a3d_render_workspace_bytes(n_prim, w, h, max(pairs, 1)), dtype=torch.uint8, device=dev)
-                tm = Timer(("render", "binning", "shade"))
+                tm = Timer(("render", "binning", "shade", "shade_lit"))
                 for _ in range(warmup + reps):
                     head = tm.run("render", lambda: call(ws))
                     tm.run("binning", lambda: call(tiny))
                     tm.run("shade", shade)
+                    tm.run("shade_lit", shade_lit)
                 assert not int(head[0]) & L.A3D_RENDER_OVERFLOW
                 dev_ms, host_ms = tm.medians(warmup)
                 tiles = ((w + 15) // 16) * ((h + 15) // 16)
@@ -154,11 +189,14 @@ def render_stage(ses, n_vertices, reps, warmup):
                 key = f"{w}x{h} {cam_name} {kind}"
                 out_rows[key] = {"device_ms": dev_ms, "host_ms": host_ms, "pairs": pairs, "tiles": tiles,
                                  "pairs_per_tile": pairs / tiles, "everywhere": n_every, "pixels_shown": shown,
-                                 "exact_tests": (pairs / tiles + n_every) * w * h}
+                                 "exact_tests": (pairs / tiles + n_every) * w * h, "pixels": w * h,
+                                 "lit_kernel": "a3d_render_shade_lit" if mesh else "a3d_render_shade_depth",
+                                 "lit_over_flat_device": dev_ms["shade_lit"] / dev_ms["shade"]}
                 print(f"{key:28s} render {dev_ms['render']:.3f}/{host_ms['render']:.3f}  binning alone {dev_ms['binning']:.3f}/"
-                      f"{host_ms['binning']:.3f}  shade {dev_ms['shade']:.3f}/{host_ms['shade']:.3f} (device / host ms)   "
+                      f"{host_ms['binning']:.3f}  shade {dev_ms['shade']:.3f}/{host_ms['shade']:.3f}  "
+                      f"{'lit' if mesh else 'depth'} shade {dev_ms['shade_lit']:.3f}/{host_ms['shade_lit']:.3f} (device / host ms)   "
                       f"pairs {pairs} = {pairs / tiles:.1f} per tile, everywhere {n_every}, {shown} of {w * h} pixels shown")
-    return {"vertices": n, "faces": m, "views": out_rows}
+    return {"vertices": n, "faces": m, "normals": normals_ms, "views": out_rows}
 
 
 def mesh_pick_stage(ses, n_vertices, reps, warmup, calls):
