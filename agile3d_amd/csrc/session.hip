@@ -375,6 +375,16 @@ __global__ __launch_bounds__(kSesBlock) void k_session_paint(const a3d_session_p
   }
 }
 
+// Hands out consecutive 256-byte aligned pieces of a workspace; with base == nullptr it only measures (off = the bytes).
+struct Carver {
+  void* base;
+  size_t off = 0;
+  void* take(size_t b) {
+    void* p = base ? (char*)base + off : nullptr;
+    off += align256(b);
+    return p;
+  }
+};
 struct SesWs {
   unsigned long long* near_part;
   unsigned long long* pick_a;
@@ -385,23 +395,28 @@ struct SesWs {
 };
 static SesWs carve_session(void* base) {
   SesWs w;
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    void* p = base ? (char*)base + off : nullptr;
-    off += align256(b);
-    return p;
-  };
-  w.near_part = (unsigned long long*)take((size_t)A3D_NEAREST_MAX_SOURCES * A3D_NEAREST_MAX_QUERIES * kSesMaxBlocks * 8);
-  w.pick_a = (unsigned long long*)take((size_t)kSesMaxBlocks * 8);
-  w.pick_row = (unsigned*)take((size_t)kSesMaxBlocks * 4);
-  w.mesh_key = (unsigned long long*)take((size_t)kSesMaxBlocks * 8);
-  w.mesh_flag = (unsigned*)take((size_t)kSesMaxBlocks * 4);
-  w.bytes = off;
+  Carver c{base};
+  w.near_part = (unsigned long long*)c.take((size_t)A3D_NEAREST_MAX_SOURCES * A3D_NEAREST_MAX_QUERIES * kSesMaxBlocks * 8);
+  w.pick_a = (unsigned long long*)c.take((size_t)kSesMaxBlocks * 8);
+  w.pick_row = (unsigned*)c.take((size_t)kSesMaxBlocks * 4);
+  w.mesh_key = (unsigned long long*)c.take((size_t)kSesMaxBlocks * 8);
+  w.mesh_flag = (unsigned*)c.take((size_t)kSesMaxBlocks * 4);
+  w.bytes = c.off;
   return w;
 }
 static int ses_blocks(long long n) {
   const long long want = (n + kSesBlock - 1) / kSesBlock;
   return (int)(want < 1 ? 1 : want > kSesMaxBlocks ? kSesMaxBlocks : want);
+}
+// n rows behind a pointer: a count that fits the kernels' 32-bit row ids, and rows to read unless there are none
+static bool ses_rows_ok(long long n, const void* rows) { return n >= 0 && n < (1ll << 31) && (!n || rows); }
+static bool ses_unit_direction(const char* what, const float* d) {
+  const double len2 = (double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2];
+  if (!(len2 > 0.999 && len2 < 1.001)) {
+    set_error("%s: the direction must be a unit vector (|d|^2 = %g)", what, len2);
+    return false;
+  }
+  return true;
 }
 static bool ses_ws_ok(const void* ws, size_t bytes, const char* what) {
   if (!ws || ((uintptr_t)ws & 255) || bytes < carve_session(nullptr).bytes) {
@@ -443,22 +458,17 @@ struct RenderWs {
 };
 static RenderWs carve_render(void* base, long long n_prim, int width, int height, long long cap) {
   RenderWs w;
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    void* p = base ? (char*)base + off : nullptr;
-    off += align256(b);
-    return p;
-  };
+  Carver c{base};
   const size_t tiles = (size_t)((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile);
-  w.tile_count = (unsigned*)take(tiles * 4);
-  w.tile_fill = (unsigned*)take(tiles * 4);
-  w.every_count = (unsigned*)take(4);
-  w.zero_bytes = off;
-  w.tile_offset = (unsigned*)take(tiles * 4);
-  w.rect = (int4*)take((size_t)(n_prim > 0 ? n_prim : 1) * 16);
-  w.every = (unsigned*)take((size_t)(n_prim > 0 ? n_prim : 1) * 4);
-  w.pairs = (unsigned*)take((size_t)(cap > 0 ? cap : 1) * 4);
-  w.bytes = off;
+  w.tile_count = (unsigned*)c.take(tiles * 4);
+  w.tile_fill = (unsigned*)c.take(tiles * 4);
+  w.every_count = (unsigned*)c.take(4);
+  w.zero_bytes = c.off;
+  w.tile_offset = (unsigned*)c.take(tiles * 4);
+  w.rect = (int4*)c.take((size_t)(n_prim > 0 ? n_prim : 1) * 16);
+  w.every = (unsigned*)c.take((size_t)(n_prim > 0 ? n_prim : 1) * 4);
+  w.pairs = (unsigned*)c.take((size_t)(cap > 0 ? cap : 1) * 4);
+  w.bytes = c.off;
   return w;
 }
 
@@ -632,20 +642,36 @@ __global__ __launch_bounds__(kSesBlock) void k_render_fill(const RenderTab t, co
 __device__ __forceinline__ unsigned render_list_entry(const RenderWs& w, unsigned n_every, unsigned offset, unsigned e) {
   return e < n_every ? w.every[e] : w.pairs[offset + (e - n_every)];
 }
+// What a thread of the tile pass (workgroup = tile blockIdx.x) starts from.  render_tile_pixel: its pixel and the pixel's
+// ray; returns whether the pixel lies inside the image (a thread outside still stages primitives).  render_tile_lists: the
+// length of the everywhere-list, of both lists, and the offset of the tile's own.
+__device__ __forceinline__ bool render_tile_pixel(const RenderTab& t, int& px, int& py, float* d) {
+  const int tile = blockIdx.x;
+  px = (tile % t.cam.tiles_x) * kTile + (threadIdx.x & (kTile - 1));
+  py = (tile / t.cam.tiles_x) * kTile + (threadIdx.x >> 4);
+  const bool live = px < t.cam.c.width && py < t.cam.c.height;
+  ses_pixel_ray(t.cam.c, live ? px : 0, live ? py : 0, d);
+  return live;
+}
+struct TileLists {
+  unsigned n_every, total, offset;
+};
+__device__ __forceinline__ TileLists render_tile_lists(const RenderWs& w) {
+  const int tile = blockIdx.x;
+  const unsigned n_every = *w.every_count;
+  return {n_every, n_every + w.tile_count[tile], w.tile_offset[tile]};
+}
 __global__ __launch_bounds__(kTilePixels) void k_render_tile_mesh(const RenderTab t, const RenderWs w) {
   if (t.out.header_dev->flags & A3D_RENDER_OVERFLOW) return;
   __shared__ float vtx[kTilePixels][9];
   __shared__ unsigned ids[kTilePixels];
-  const int tile = blockIdx.x;
-  const int px = (tile % t.cam.tiles_x) * kTile + (threadIdx.x & (kTile - 1));
-  const int py = (tile / t.cam.tiles_x) * kTile + (threadIdx.x >> 4);
-  const bool live = px < t.cam.c.width && py < t.cam.c.height;
-  RayShear ray;
+  int px, py;
   float d[3];
-  ses_pixel_ray(t.cam.c, live ? px : 0, live ? py : 0, d);
+  const bool live = render_tile_pixel(t, px, py, d);
+  RayShear ray;
   ray.o[0] = t.cam.c.o[0], ray.o[1] = t.cam.c.o[1], ray.o[2] = t.cam.c.o[2];
   ses_shear(d, ray);
-  const unsigned n_every = *w.every_count, total = n_every + w.tile_count[tile], offset = w.tile_offset[tile];
+  const auto [n_every, total, offset] = render_tile_lists(w);
   unsigned long long best = kNoKey;
   for (unsigned base = 0; base < total; base += kTilePixels) {
     const unsigned cnt = min((unsigned)kTilePixels, total - base);
@@ -693,14 +719,11 @@ __global__ __launch_bounds__(kTilePixels) void k_render_tile_points(const Render
   if (t.out.header_dev->flags & A3D_RENDER_OVERFLOW) return;
   __shared__ float pts[kTilePixels][3];
   __shared__ unsigned ids[kTilePixels];
-  const int tile = blockIdx.x;
-  const int px = (tile % t.cam.tiles_x) * kTile + (threadIdx.x & (kTile - 1));
-  const int py = (tile / t.cam.tiles_x) * kTile + (threadIdx.x >> 4);
-  const bool live = px < t.cam.c.width && py < t.cam.c.height;
+  int px, py;
   float d[3];
-  ses_pixel_ray(t.cam.c, live ? px : 0, live ? py : 0, d);
+  const bool live = render_tile_pixel(t, px, py, d);
   const float o[3] = {t.cam.c.o[0], t.cam.c.o[1], t.cam.c.o[2]};
-  const unsigned n_every = *w.every_count, total = n_every + w.tile_count[tile], offset = w.tile_offset[tile];
+  const auto [n_every, total, offset] = render_tile_lists(w);
   PickKey best;
   best.a = kNoKey, best.row = 0xffffffffu;
   for (unsigned base = 0; base < total; base += kTilePixels) {
@@ -733,6 +756,13 @@ struct ShadeTab {
   uint8_t* rgb;
   long long pixels;
 };
+static ShadeTab shade_tab(const int32_t* id, const float* u, const float* v, const int32_t* faces, long long m,
+                          const float* colors, long long n, const float* background, uint8_t* rgb, long long pixels) {
+  ShadeTab t;
+  t.id = id, t.u = u, t.v = v, t.faces = faces, t.m = m, t.n = n, t.colors = colors, t.rgb = rgb, t.pixels = pixels;
+  for (int k = 0; k < 3; ++k) t.bg[k] = background[k];
+  return t;
+}
 __device__ __forceinline__ uint8_t shade_q(float c) { return (uint8_t)(fminf(fmaxf(c, 0.f), 1.f) * 255.f + 0.5f); }
 // THE base colour of pixel i, for the flat pass and the two shaded ones: the background, the vertex's colour (no faces) or
 // the face's interpolated one.  false: the pixel shows the background (id -1, or an id / a face's index outside its table).
@@ -971,7 +1001,7 @@ extern "C" int a3d_nearest_rows(const a3d_nearest_source* sources, int n_sources
   long long n_max = 0;
   for (int s = 0; s < n_sources; ++s) {
     const a3d_nearest_source& sp = sources[s];
-    if (sp.n < 0 || sp.n >= (1ll << 31) || (sp.n && !sp.xyz_dev) || !sp.rows_out_dev) {
+    if (!ses_rows_ok(sp.n, sp.xyz_dev) || !sp.rows_out_dev) {
       set_error("a3d_nearest_rows: source %d: bad arguments (n=%lld)", s, (long long)sp.n);
       return A3D_ERR_INVALID;
     }
@@ -992,15 +1022,11 @@ extern "C" int a3d_nearest_rows(const a3d_nearest_source* sources, int n_sources
 extern "C" int a3d_pick_ray(const float* xyz_dev, int64_t n, const float* origin, const float* direction, float radius,
                             a3d_pick_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (n < 0 || n >= (1ll << 31) || (n && !xyz_dev) || !origin || !direction || !result_dev || !(radius >= 0.f)) {
+  if (!ses_rows_ok(n, xyz_dev) || !origin || !direction || !result_dev || !(radius >= 0.f)) {
     set_error("a3d_pick_ray: bad arguments (n=%lld radius=%g)", (long long)n, (double)radius);
     return A3D_ERR_INVALID;
   }
-  const double len2 = (double)direction[0] * direction[0] + (double)direction[1] * direction[1] + (double)direction[2] * direction[2];
-  if (!(len2 > 0.999 && len2 < 1.001)) {
-    set_error("a3d_pick_ray: the direction must be a unit vector (|d|^2 = %g)", len2);
-    return A3D_ERR_INVALID;
-  }
+  if (!ses_unit_direction("a3d_pick_ray", direction)) return A3D_ERR_INVALID;
   if (!ses_ws_ok(workspace_dev, workspace_bytes, "a3d_pick_ray")) return A3D_ERR_WORKSPACE;
   PickTab t;
   t.xyz = xyz_dev, t.n = n;
@@ -1020,16 +1046,11 @@ extern "C" int a3d_pick_mesh(const float* xyz_dev, int64_t n, const int32_t* fac
                              const float* direction, a3d_pick_mesh_result* result_dev, void* workspace_dev,
                              size_t workspace_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (n < 0 || n >= (1ll << 31) || m < 0 || m >= (1ll << 31) || (n && !xyz_dev) || (m && !faces_dev) || !origin || !direction ||
-      !result_dev) {
+  if (!ses_rows_ok(n, xyz_dev) || !ses_rows_ok(m, faces_dev) || !origin || !direction || !result_dev) {
     set_error("a3d_pick_mesh: bad arguments (n=%lld m=%lld)", (long long)n, (long long)m);
     return A3D_ERR_INVALID;
   }
-  const double len2 = (double)direction[0] * direction[0] + (double)direction[1] * direction[1] + (double)direction[2] * direction[2];
-  if (!(len2 > 0.999 && len2 < 1.001)) {
-    set_error("a3d_pick_mesh: the direction must be a unit vector (|d|^2 = %g)", len2);
-    return A3D_ERR_INVALID;
-  }
+  if (!ses_unit_direction("a3d_pick_mesh", direction)) return A3D_ERR_INVALID;
   if (!ses_ws_ok(workspace_dev, workspace_bytes, "a3d_pick_mesh")) return A3D_ERR_WORKSPACE;
   MeshTab t;
   t.xyz = xyz_dev, t.n = n, t.faces = faces_dev, t.m = m;
@@ -1085,7 +1106,7 @@ extern "C" int a3d_render_camera_bounds(const a3d_camera* camera, double* out13)
 
 extern "C" int a3d_render_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const a3d_camera* camera,
                                const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  if (n < 0 || n >= (1ll << 31) || m < 0 || m >= (1ll << 31) || (n && !xyz_dev) || (m && !faces_dev)) {
+  if (!ses_rows_ok(n, xyz_dev) || !ses_rows_ok(m, faces_dev)) {
     set_error("a3d_render_mesh: bad arguments (n=%lld m=%lld)", (long long)n, (long long)m);
     return A3D_ERR_INVALID;
   }
@@ -1097,7 +1118,7 @@ extern "C" int a3d_render_mesh(const float* xyz_dev, int64_t n, const int32_t* f
 
 extern "C" int a3d_render_points(const float* xyz_dev, int64_t n, float radius, const a3d_camera* camera,
                                  const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  if (n < 0 || n >= (1ll << 31) || (n && !xyz_dev) || !(radius >= 0.f) || !std::isfinite(radius)) {
+  if (!ses_rows_ok(n, xyz_dev) || !(radius >= 0.f) || !std::isfinite(radius)) {
     set_error("a3d_render_points: bad arguments (n=%lld radius=%g)", (long long)n, (double)radius);
     return A3D_ERR_INVALID;
   }
@@ -1117,10 +1138,7 @@ extern "C" int a3d_render_shade(const int32_t* id_dev, const float* u_dev, const
               (long long)n, (long long)m);
     return A3D_ERR_INVALID;
   }
-  ShadeTab t;
-  t.id = id_dev, t.u = u_dev, t.v = v_dev, t.faces = faces_dev, t.m = m, t.n = n, t.colors = colors_dev, t.rgb = rgb_dev;
-  for (int k = 0; k < 3; ++k) t.bg[k] = background[k];
-  t.pixels = (long long)width * height;
+  const ShadeTab t = shade_tab(id_dev, u_dev, v_dev, faces_dev, m, colors_dev, n, background, rgb_dev, (long long)width * height);
   k_render_shade<<<(unsigned)((t.pixels + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
@@ -1138,10 +1156,7 @@ extern "C" int a3d_render_shade_lit(const int32_t* id_dev, const float* u_dev, c
     return A3D_ERR_INVALID;
   }
   LitTab t;
-  t.s.id = id_dev, t.s.u = u_dev, t.s.v = v_dev, t.s.faces = faces_dev, t.s.m = m, t.s.n = n, t.s.colors = colors_dev;
-  t.s.rgb = rgb_dev;
-  for (int k = 0; k < 3; ++k) t.s.bg[k] = background[k];
-  t.s.pixels = (long long)camera->width * camera->height;
+  t.s = shade_tab(id_dev, u_dev, v_dev, faces_dev, m, colors_dev, n, background, rgb_dev, (long long)camera->width * camera->height);
   t.normals = normals_dev, t.cam = *camera, t.ambient = ambient;
   const unsigned blocks = (unsigned)((t.s.pixels + kSesBlock - 1) / kSesBlock);
   if (m == 0) {                                // no face: no id is good.  The flat pass as a cloud without vertices: all background
@@ -1165,10 +1180,7 @@ extern "C" int a3d_render_shade_depth(const int32_t* id_dev, const float* t_dev,
     return A3D_ERR_INVALID;
   }
   DepthTab t;
-  t.s.id = id_dev, t.s.u = u_dev, t.s.v = v_dev, t.s.faces = faces_dev, t.s.m = m, t.s.n = n, t.s.colors = colors_dev;
-  t.s.rgb = rgb_dev;
-  for (int k = 0; k < 3; ++k) t.s.bg[k] = background[k];
-  t.s.pixels = (long long)width * height;
+  t.s = shade_tab(id_dev, u_dev, v_dev, faces_dev, m, colors_dev, n, background, rgb_dev, (long long)width * height);
   t.t = t_dev, t.width = width, t.height = height, t.strength = strength;
   k_render_shade_depth<<<(unsigned)((t.s.pixels + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
   A3D_LAUNCH_CHECK();
@@ -1177,7 +1189,7 @@ extern "C" int a3d_render_shade_depth(const int32_t* id_dev, const float* t_dev,
 
 extern "C" int a3d_vertex_normals(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const int64_t* offsets_dev,
                                   const int32_t* corners_dev, float* normals_out_dev, void* stream) {
-  if (n < 0 || n >= (1ll << 31) || m < 0 || 3 * m >= (1ll << 31) || (n && (!xyz_dev || !offsets_dev || !normals_out_dev)) ||
+  if (!ses_rows_ok(n, xyz_dev) || m < 0 || 3 * m >= (1ll << 31) || (n && (!offsets_dev || !normals_out_dev)) ||
       (m && (!faces_dev || !corners_dev))) {
     set_error("a3d_vertex_normals: bad arguments (n=%lld m=%lld; 3 m must fit int32)", (long long)n, (long long)m);
     return A3D_ERR_INVALID;

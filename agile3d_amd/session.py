@@ -4,7 +4,7 @@ The third caller of the model API in the reference is its interactive tool (``in
 interactive_segmentation_user.py`` + ``gui.py``).  ``InteractiveSession`` is that tool without a window: the same
 sequence of model calls (``forward_backbone`` once per scene, ``forward_mask`` per inference), the same click
 dictionaries, relabelled ground truth, record line and ``.npy`` files -- and no Open3D.  What surrounds the two model
-calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``):
+calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``), reached through ``view.py`` and ``clicks.py``:
 
     pointer ray -> clicked point        a3d_pick_ray       (the GUI renders a depth image and unprojects, gui.py:247-271)
                                         a3d_pick_mesh      (the same for a triangle mesh: the first SURFACE under the pointer)
@@ -32,7 +32,6 @@ Departures from the reference, on purpose:
 from __future__ import annotations
 
 import colorsys
-import ctypes as C
 import os
 from datetime import datetime
 
@@ -42,6 +41,7 @@ import torch
 from . import clicks as K
 from . import lib as L
 from . import ply
+from . import view as V
 from .sparse import SparseTensor, sparse_quantize
 
 RECORD_FILE, MASK_DIR, CLICK_DIR = "iou_record.csv", "masks", "clicks"
@@ -94,10 +94,6 @@ class SessionResult:
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _f3(values, what):
@@ -235,7 +231,7 @@ class InteractiveSession:
         self._palette_dev = torch.from_numpy(self.palette).to(self.device)
         self.background_click_color = tuple(float(c) for c in background_click_color)
         self.clock = clock or datetime.now
-        self._ws = torch.empty(self.lib.a3d_session_workspace_bytes(), dtype=torch.uint8, device=self.device)
+        self._ws = V.session_workspace(self.device)
         self._small = torch.empty(64, dtype=torch.int32, device=self.device)     # pick result / nearest rows
         self._counts = torch.empty(3 * _N_IDS + 2, dtype=torch.int64, device=self.device)   # IoU counts + its flag + paint's flag
         self._counts_host = torch.empty(3 * _N_IDS + 2, dtype=torch.int64).pin_memory()
@@ -380,26 +376,16 @@ class InteractiveSession:
         d = np.ascontiguousarray((d64 / np.linalg.norm(d64)).astype(np.float32))
         if surface is None:
             surface = self.faces is not None
-        fp = C.POINTER(C.c_float)
         if surface:
             if self.faces is None:
                 raise ValueError("pick(surface=True): the scene has no faces (load_scene(..., faces=) or a mesh scan.ply)")
-            L.check(self.lib.a3d_pick_mesh(self.coords_full.data_ptr(), self.coords_full.shape[0], self.faces.data_ptr(),
-                                           self.faces.shape[0], o.ctypes.data_as(fp), d.ctypes.data_as(fp),
-                                           self._small.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                           _stream(self.device)), "a3d_pick_mesh")
-            host = self._small[:8].cpu().numpy()          # a3d_pick_mesh_result: face, flags, t, x, y, z, u, v
-            if int(host[0]) < 0:
-                return None
-            return [float(v) for v in host[3:6].view(np.float32)]
+            out = V.pick_mesh(self.coords_full, self.faces, o, d, out=self._small[:8], workspace=self._ws)
+            hit = V.read_pick_mesh(out.cpu().numpy())[0]
+            return None if hit["face"] < 0 else [float(hit[k]) for k in "xyz"]
         r = self.voxel_size if radius is None else float(radius)
-        L.check(self.lib.a3d_pick_ray(self.coords_full.data_ptr(), self.coords_full.shape[0], o.ctypes.data_as(fp),
-                                      d.ctypes.data_as(fp), r, self._small.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                      _stream(self.device)), "a3d_pick_ray")
-        host = self._small[:4].cpu().numpy()
-        if int(host[0]) < 0:
-            return None
-        return [float(v) for v in host[1:4].view(np.float32)]
+        out = V.pick_ray(self.coords_full, o, d, r, out=self._small[:4], workspace=self._ws)
+        index, xyz = V.read_pick(out.cpu().numpy())
+        return None if index < 0 else [float(v) for v in xyz]
 
     # ------------------------------------------------------------------ the view
     def default_view(self, width, height, fov_deg=35.0):
@@ -413,13 +399,7 @@ class InteractiveSession:
     def _vertex_normals(self):
         """``ses.normals`` of a mesh scene: ``a3d_vertex_normals`` once per scene, on first use."""
         if self.normals is None:
-            n = self.coords_full.shape[0]
-            normals = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-            offsets, corners = self._corner_lists
-            L.check(self.lib.a3d_vertex_normals(self.coords_full.data_ptr(), n, self.faces.data_ptr(), self.faces.shape[0],
-                                                offsets.data_ptr(), corners.data_ptr(), normals.data_ptr(),
-                                                _stream(self.device)), "a3d_vertex_normals")
-            self.normals = normals
+            self.normals = V.vertex_normals(self.coords_full, self.faces, *self._corner_lists)
         return self.normals
 
     def render(self, intrinsic, extrinsic, width, height, colors=None, radius=None, background=(1.0, 1.0, 1.0), lit=False,
@@ -457,29 +437,20 @@ class InteractiveSession:
         mesh = self.faces is not None
         n_prim = self.faces.shape[0] if mesh else n
         r = self.voxel_size if radius is None else float(radius)
-        ids = torch.empty((h, w), dtype=torch.int32, device=dev)
-        t = torch.empty((h, w), dtype=torch.float32, device=dev)
-        u = torch.empty((h, w), dtype=torch.float32, device=dev) if mesh else None
-        v = torch.empty((h, w), dtype=torch.float32, device=dev) if mesh else None
-        rgb = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        ids = t = u = v = None                      # (allocated by the first attempt, written again by a retry)
         header = self._small[16:20]
-        out = L.RenderOut(ids.data_ptr(), t.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
-                          header.data_ptr())
         capacity = max(4 * n_prim, 1 << 16)
         for attempt in range(3):
-            need = self.lib.a3d_render_workspace_bytes(n_prim, w, h, capacity)
+            need = V.render_workspace_bytes(n_prim, w, h, capacity)
             if self._render_ws is None or self._render_ws.numel() < need:
                 self._render_ws = None              # (dropped first: the old and the new one need not live together)
                 self._render_ws = torch.empty(need, dtype=torch.uint8, device=dev)
             ws = self._render_ws
             if mesh:
-                L.check(self.lib.a3d_render_mesh(self.coords_full.data_ptr(), n, self.faces.data_ptr(), n_prim, C.byref(cam),
-                                                 C.byref(out), ws.data_ptr(), ws.numel(), _stream(dev)), "a3d_render_mesh")
+                ids, t, u, v, _ = V.render_mesh(self.coords_full, self.faces, cam, ids, t, u, v, header=header, workspace=ws)
             else:
-                L.check(self.lib.a3d_render_points(self.coords_full.data_ptr(), n, r, C.byref(cam), C.byref(out),
-                                                   ws.data_ptr(), ws.numel(), _stream(dev)), "a3d_render_points")
-            head = header.cpu().numpy()
-            flags, n_every, pairs = int(head[0]), int(head[1]), int(head[2:4].view(np.int64)[0])
+                ids, t, _ = V.render_points(self.coords_full, r, cam, ids, t, header=header, workspace=ws)
+            flags, n_every, pairs = V.read_render_header(header.cpu().numpy())
             if not flags & L.A3D_RENDER_OVERFLOW:
                 break
             capacity = pairs + pairs // 8           # this view's pairs and room for the next one
@@ -487,19 +458,12 @@ class InteractiveSession:
             raise RuntimeError("a3d_render: the pair capacity it asked for did not suffice")
         if flags & L.A3D_RENDER_BAD_INDEX:
             raise RuntimeError("a3d_render_mesh: face indices out of range")
-        bg_p = bg.ctypes.data_as(C.POINTER(C.c_float))
         if lit and mesh:
-            L.check(self.lib.a3d_render_shade_lit(ids.data_ptr(), u.data_ptr(), v.data_ptr(), self.faces.data_ptr(), n_prim,
-                                                  col.data_ptr(), n, self._vertex_normals().data_ptr(), C.byref(cam), ambient,
-                                                  bg_p, rgb.data_ptr(), _stream(dev)), "a3d_render_shade_lit")
+            rgb = V.render_shade_lit(ids, u, v, self.faces, col, self._vertex_normals(), cam, ambient, bg)
         elif lit:
-            L.check(self.lib.a3d_render_shade_depth(ids.data_ptr(), t.data_ptr(), None, None, None, 0, col.data_ptr(), n,
-                                                    depth_strength, bg_p, rgb.data_ptr(), w, h, _stream(dev)),
-                    "a3d_render_shade_depth")
+            rgb = V.render_shade_depth(ids, t, None, None, None, col, depth_strength, bg)
         else:
-            L.check(self.lib.a3d_render_shade(ids.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
-                                              self.faces.data_ptr() if mesh else None, n_prim if mesh else 0, col.data_ptr(),
-                                              n, bg_p, rgb.data_ptr(), w, h, _stream(dev)), "a3d_render_shade")
+            rgb = V.render_shade(ids, u, v, self.faces, col, bg)
         return RenderResult(ids=ids, t=t, rgb=rgb, u=u, v=v, camera=cam, mesh=mesh, lit=bool(lit), pairs=pairs,
                             n_everywhere=n_every)
 
@@ -529,13 +493,9 @@ class InteractiveSession:
         """(voxel row, full-resolution vertex) nearest to ``point``: both searches in one launch pair, exact."""
         self._need_scene()
         q = _f3(point, "point")
-        src = (L.NearestSource * 2)()
-        src[0].xyz_dev, src[0].n, src[0].rows_out_dev = self.raw_coords_qv.data_ptr(), self.raw_coords_qv.shape[0], self._small.data_ptr()
-        src[1].xyz_dev, src[1].n, src[1].rows_out_dev = self.coords_full.data_ptr(), self.coords_full.shape[0], self._small.data_ptr() + 4
-        L.check(self.lib.a3d_nearest_rows(src, 2, q.ctypes.data_as(C.POINTER(C.c_float)), 1, self._ws.data_ptr(),
-                                          self._ws.numel(), _stream(self.device)), "a3d_nearest_rows")
-        rows = self._small[:2].cpu().tolist()
-        return rows[0], rows[1]
+        rows = V.nearest_rows([self.raw_coords_qv, self.coords_full], q[None], out=self._small[:2].view(2, 1),
+                              workspace=self._ws)
+        return tuple(rows.view(2).cpu().tolist())
 
     def click(self, point, obj: int):
         """One click at ``point`` for object ``obj`` (0 = background, k >= 1 = object k), booked as gui.py:290-331 does:
@@ -584,27 +544,16 @@ class InteractiveSession:
 
     # ------------------------------------------------------------------ paint and infer
     def _launch_paint(self, labels_qv, paint_cubes):
-        n_full = self.coords_full.shape[0]
-        labels_full = torch.empty(n_full, dtype=torch.int32, device=self.device)
-        colors = torch.empty((n_full, 3), dtype=torch.float32, device=self.device)
-        n_cubes = self.num_clicks if paint_cubes else 0
-        cubes = self._cubes_dev if n_cubes else None
-        a = L.SessionPaintArgs()
-        a.labels_qv_dev, a.n_qv = labels_qv.data_ptr(), labels_qv.shape[0]
-        a.inverse_map_dev, a.n_full = self.inverse_map.data_ptr(), n_full
-        a.xyz_full_dev, a.colors_full_dev = self.coords_full.data_ptr(), self.colors_full.data_ptr()
-        a.palette_dev, a.n_palette = self._palette_dev.data_ptr(), self.palette.shape[0]
-        a.cubes_dev, a.n_cubes, a.cube_size = (cubes.data_ptr() if n_cubes else None), n_cubes, self.cube_size
-        a.label_full_dev, a.colors_out_dev = labels_full.data_ptr(), colors.data_ptr()
-        a.err_dev = self._counts.data_ptr() + 8 * (3 * _N_IDS + 1)
-        L.check(self.lib.a3d_session_paint(C.byref(a), _stream(self.device)), "a3d_session_paint")
-        return labels_full, colors, cubes
+        cubes = self._cubes_dev[:self.num_clicks] if paint_cubes and self.num_clicks else None
+        err = self._counts[3 * _N_IDS + 1:].view(torch.int32)[:1]       # (the low word of the slot behind the IoU counts)
+        return V.session_paint(labels_qv, self.inverse_map, self.coords_full, self.colors_full, self._palette_dev, cubes,
+                               self.cube_size, err=err)[:2]
 
     def preview(self, paint_cubes=True):
         """Labels and colours of the current state WITHOUT running the model: the last inference's labels (background
         before the first) with the clicks' cubes on top -- what the GUI shows between a click and the next inference."""
         self._need_scene()
-        labels_full, colors, keep = self._launch_paint(self._labels_qv, paint_cubes)
+        labels_full, colors = self._launch_paint(self._labels_qv, paint_cubes)
         if int(self._counts[3 * _N_IDS + 1:].cpu()[0]) & 0xffffffff:
             raise RuntimeError("a3d_session_paint: inverse_map or labels out of range")
         self._colors_last = colors
@@ -626,12 +575,11 @@ class InteractiveSession:
             out = self.model.forward_mask(*self._backbone, click_idx=[self.click_idx], click_time_idx=[self.click_time_idx])
             logits = out["pred_masks"][0]
         labels_qv = K.argmax_labels(logits, self.click_idx)
-        labels_full, colors, keep = self._launch_paint(labels_qv, paint_cubes)
+        labels_full, colors = self._launch_paint(labels_qv, paint_cubes)
         have_gt = self.new_labels is not None
         if have_gt:
-            L.check(self.lib.a3d_iou_counts(labels_qv.data_ptr(), labels_qv.shape[0], self.inverse_map.data_ptr(),
-                                            self.new_labels.data_ptr(), self.new_labels.shape[0], _N_IDS,
-                                            self._counts.data_ptr(), _stream(dev)), "a3d_iou_counts")
+            K._launch_iou_counts([labels_qv], [self.new_labels], [self.inverse_map], _N_IDS,
+                                 self._counts[:3 * _N_IDS + 1].view(1, -1))
         else:
             self._counts[:3 * _N_IDS + 1].zero_()
         mask_host = None

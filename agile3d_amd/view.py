@@ -1,0 +1,255 @@
+"""The interactive session's library calls (``csrc/session.hip``) as functions of device tensors -- the one place where
+they are marshalled, as ``clicks.py`` is for ``csrc/clicks.hip``.  ``session.py`` and the tests call these.
+
+Every wrapper takes device tensors (or ``None`` where the C ABI takes a null pointer), checks dtype, device, shape and
+contiguity (``ValueError`` naming the argument, before the library is reached), hands a tensor without elements over as a
+null pointer, writes into the output tensors the caller passes (``out=``, ``rgb=``, ``header=`` ...; allocated otherwise),
+launches on the current stream of the tensors' device and returns device tensors: no synchronisation, no copy to the host.
+Three-vectors the C ABI reads on the host (origin, direction, background, queries) are anything ``numpy`` turns into fp32.
+The ``read_*`` functions decode a result record from its host copy.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import lib as L
+
+# the result records as numpy sees them (lib.PickResult, lib.PickMeshResult, lib.RenderHeader)
+PICK = np.dtype([("index", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
+PICK_MESH = np.dtype([("face", "<i4"), ("flags", "<i4"), ("t", "<f4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("u", "<f4"),
+                      ("v", "<f4")])
+RENDER_HEADER = np.dtype([("flags", "<i4"), ("n_everywhere", "<i4"), ("pairs_needed", "<i8")])
+assert C.sizeof(L.PickResult) == PICK.itemsize == 16
+assert C.sizeof(L.PickMeshResult) == PICK_MESH.itemsize == 32
+assert C.sizeof(L.RenderHeader) == RENDER_HEADER.itemsize == 16
+
+I32, I64, F32, U8 = torch.int32, torch.int64, torch.float32, torch.uint8
+
+
+# ---- decoding: pure functions of a host array ----------------------------------------------------------------------------
+def read_pick(host):
+    """``(index, xyz fp32 [3])`` of the int32 [4] host copy of an ``a3d_pick_result`` (index -1: the ray meets no point)."""
+    rec = np.ascontiguousarray(host).view(PICK)[0]
+    return int(rec["index"]), np.array([rec["x"], rec["y"], rec["z"]], np.float32)
+
+
+def read_pick_mesh(host):
+    """The ``PICK_MESH`` records of the int32 [8 k] host copy of k ``a3d_pick_mesh_result``s."""
+    return np.ascontiguousarray(host).view(PICK_MESH)
+
+
+def read_render_header(host):
+    """``(flags, n_everywhere, pairs)`` of the int32 [4] host copy of an ``a3d_render_header``."""
+    rec = np.ascontiguousarray(host).view(RENDER_HEADER)[0]
+    return int(rec["flags"]), int(rec["n_everywhere"]), int(rec["pairs_needed"])
+
+
+# ---- argument checks ---------------------------------------------------------------------------------------------------------
+def _device(name, t):
+    if not torch.is_tensor(t) or t.device.type != "cuda":
+        raise ValueError(f"{name} must be a tensor on the GPU (there is no CPU path)")
+    return t.device
+
+
+def _ptr(name, t, dtype, shape, dev, optional=False):
+    """The device pointer of tensor argument ``name`` (``shape``: ``None`` = any extent) -- ``None`` for a tensor without
+    elements and for an absent ``optional`` one."""
+    if t is None and optional:
+        return None
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise ValueError(f"{name} must be a {dtype} tensor")
+    if t.device != dev:
+        raise ValueError(f"{name} must live on {dev}")
+    if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
+        raise ValueError(f"{name} must have shape {list(shape)} (None: any), not {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return t.data_ptr() if t.numel() else None
+
+
+def _out(name, t, dtype, shape, dev):
+    """The output tensor ``name``: the caller's, checked, or a new one."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    _ptr(name, t, dtype, shape, dev)
+    return t
+
+
+def _f32p(name, values, shape):
+    """(array, pointer) of a small host argument; the array must outlive the call."""
+    a = np.ascontiguousarray(values, dtype=np.float32)
+    if a.shape != shape:
+        raise ValueError(f"{name} must have shape {list(shape)}")
+    return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def session_workspace(device):
+    """The scratch of ``nearest_rows``, ``pick_ray`` and ``pick_mesh`` (``a3d_session_workspace_bytes``)."""
+    return torch.empty(L.load().a3d_session_workspace_bytes(), dtype=U8, device=device)
+
+
+def _workspace(ws, dev):
+    if ws is None:
+        return session_workspace(dev)
+    _ptr("workspace", ws, U8, (None,), dev)
+    return ws
+
+
+def render_workspace_bytes(n_primitives, width, height, pair_capacity):
+    """``a3d_render_workspace_bytes``: 0 for sizes the renders refuse."""
+    return L.load().a3d_render_workspace_bytes(n_primitives, width, height, pair_capacity)
+
+
+# ---- nearest rows, picks -------------------------------------------------------------------------------------------------------
+def nearest_rows(sources, queries, out=None, workspace=None):
+    """``a3d_nearest_rows``: fp32 [n_s, 3] row sets x host queries [m, 3] -> int32 [len(sources), m] nearest rows."""
+    dev = _device("sources[0]", sources[0])
+    q, qp = _f32p("queries", queries, (np.shape(queries)[0], 3))
+    out = _out("out", out, I32, (len(sources), len(q)), dev)
+    ws = _workspace(workspace, dev)
+    src = (L.NearestSource * len(sources))()
+    for i, s in enumerate(sources):
+        src[i].xyz_dev, src[i].n, src[i].rows_out_dev = _ptr(f"sources[{i}]", s, F32, (None, 3), dev), s.shape[0], out[i].data_ptr()
+    L.check(L.load().a3d_nearest_rows(src, len(sources), qp, len(q), ws.data_ptr(), ws.numel(), _stream(dev)), "a3d_nearest_rows")
+    return out
+
+
+def pick_ray(xyz, origin, direction, radius, out=None, workspace=None):
+    """``a3d_pick_ray``: the first vertex of fp32 [n, 3] along a ray (unit ``direction``) -> int32 [4], see ``read_pick``."""
+    dev = _device("xyz", xyz)
+    xp = _ptr("xyz", xyz, F32, (None, 3), dev)
+    (o, op), (d, dp) = _f32p("origin", origin, (3,)), _f32p("direction", direction, (3,))
+    out = _out("out", out, I32, (4,), dev)
+    ws = _workspace(workspace, dev)
+    L.check(L.load().a3d_pick_ray(xp, xyz.shape[0], op, dp, float(radius), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _stream(dev)), "a3d_pick_ray")
+    return out
+
+
+def pick_mesh(xyz, faces, origin, direction, out=None, workspace=None):
+    """``a3d_pick_mesh``: the first face (int32 [m, 3] into ``xyz``) a ray crosses -> int32 [8], see ``read_pick_mesh``."""
+    dev = _device("xyz", xyz)
+    xp, fp = _ptr("xyz", xyz, F32, (None, 3), dev), _ptr("faces", faces, I32, (None, 3), dev)
+    (o, op), (d, dp) = _f32p("origin", origin, (3,)), _f32p("direction", direction, (3,))
+    out = _out("out", out, I32, (8,), dev)
+    ws = _workspace(workspace, dev)
+    L.check(L.load().a3d_pick_mesh(xp, xyz.shape[0], fp, faces.shape[0], op, dp, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _stream(dev)), "a3d_pick_mesh")
+    return out
+
+
+# ---- the rendered view -----------------------------------------------------------------------------------------------------------
+def _render(xyz, faces, radius, cam, ids, t, u, v, uv, header, workspace, capacity):
+    dev = _device("xyz", xyz)
+    xp = _ptr("xyz", xyz, F32, (None, 3), dev)
+    mesh = faces is not None
+    fp = _ptr("faces", faces, I32, (None, 3), dev) if mesh else None
+    h, w = cam.height, cam.width
+    ids, t = _out("ids", ids, I32, (h, w), dev), _out("t", t, F32, (h, w), dev)
+    u, v = (_out("u", u, F32, (h, w), dev), _out("v", v, F32, (h, w), dev)) if uv else (None, None)
+    header = _out("header", header, I32, (4,), dev)
+    out = L.RenderOut(ids.data_ptr(), t.data_ptr(), u.data_ptr() if uv else None, v.data_ptr() if uv else None, header.data_ptr())
+    n, m = xyz.shape[0], faces.shape[0] if mesh else xyz.shape[0]
+    if workspace is None:
+        workspace = torch.empty(render_workspace_bytes(m, w, h, capacity), dtype=U8, device=dev)
+    _ptr("workspace", workspace, U8, (None,), dev)
+    lib = L.load()
+    if mesh:
+        L.check(lib.a3d_render_mesh(xp, n, fp, m, C.byref(cam), C.byref(out), workspace.data_ptr(), workspace.numel(),
+                                    _stream(dev)), "a3d_render_mesh")
+    else:
+        L.check(lib.a3d_render_points(xp, n, float(radius), C.byref(cam), C.byref(out), workspace.data_ptr(), workspace.numel(),
+                                      _stream(dev)), "a3d_render_points")
+    return ids, t, u, v, header
+
+
+def render_mesh(xyz, faces, cam, ids=None, t=None, u=None, v=None, uv=True, header=None, workspace=None, capacity=1 << 16):
+    """``a3d_render_mesh``, ONE attempt: ``(ids int32 [h, w], t, u, v fp32 [h, w], header int32 [4])`` for the ``lib.Camera``
+    ``cam``; ``uv=False`` leaves the weights out (``u``, ``v`` come back ``None``).  ``workspace``: uint8 scratch whose size is
+    the pair capacity (``render_workspace_bytes``), else one for ``capacity`` pairs is allocated.  Whether the capacity
+    sufficed is in the header (``read_render_header``); the images are untouched when it did not."""
+    return _render(xyz, faces, None, cam, ids, t, u, v, uv, header, workspace, capacity)
+
+
+def render_points(xyz, radius, cam, ids=None, t=None, header=None, workspace=None, capacity=1 << 16):
+    """``a3d_render_points``, one attempt: ``(ids, t, header)`` as ``render_mesh``, ids = vertices within ``radius``."""
+    ids, t, _, _, header = _render(xyz, None, radius, cam, ids, t, None, None, False, header, workspace, capacity)
+    return ids, t, header
+
+
+def _shade_args(ids, u, v, faces, colors, background, rgb):
+    """What the three shading passes share: (device, (h, w), pointers of ids, u, v, faces, colors, m, n, background, rgb)."""
+    dev = _device("ids", ids)
+    ip = _ptr("ids", ids, I32, (None, None), dev)
+    h, w = ids.shape
+    mesh = faces is not None
+    ptrs = (ip, _ptr("u", u, F32, (h, w), dev, optional=not mesh),
+            _ptr("v", v, F32, (h, w), dev, optional=not mesh), _ptr("faces", faces, I32, (None, 3), dev, optional=True),
+            _ptr("colors", colors, F32, (None, 3), dev))
+    rgb = _out("rgb", rgb, U8, (h, w, 3), dev)
+    return dev, (h, w), ptrs, faces.shape[0] if mesh else 0, colors.shape[0], _f32p("background", background, (3,)), rgb
+
+
+def render_shade(ids, u, v, faces, colors, background, rgb=None):
+    """``a3d_render_shade``: uint8 [h, w, 3] flat colours of an id image; ``u``, ``v``, ``faces`` ``None`` on a cloud."""
+    dev, (h, w), (ip, up, vp, fp, cp), m, n, (bg, bgp), rgb = _shade_args(ids, u, v, faces, colors, background, rgb)
+    L.check(L.load().a3d_render_shade(ip, up, vp, fp, m, cp, n, bgp, rgb.data_ptr(), w, h, _stream(dev)), "a3d_render_shade")
+    return rgb
+
+
+def render_shade_lit(ids, u, v, faces, colors, normals, cam, ambient, background, rgb=None):
+    """``a3d_render_shade_lit``: a mesh's colours lit from the camera by the vertex normals (fp32 [n, 3])."""
+    dev, _, (ip, up, vp, fp, cp), m, n, (bg, bgp), rgb = _shade_args(ids, u, v, faces, colors, background, rgb)
+    np_ = _ptr("normals", normals, F32, (n, 3), dev)
+    L.check(L.load().a3d_render_shade_lit(ip, up, vp, fp, m, cp, n, np_, C.byref(cam), float(ambient), bgp, rgb.data_ptr(),
+                                          _stream(dev)), "a3d_render_shade_lit")
+    return rgb
+
+
+def render_shade_depth(ids, t, u, v, faces, colors, strength, background, rgb=None):
+    """``a3d_render_shade_depth``: colours darkened by the depth steps of the ``t`` image to a pixel's four neighbours."""
+    dev, (h, w), (ip, up, vp, fp, cp), m, n, (bg, bgp), rgb = _shade_args(ids, u, v, faces, colors, background, rgb)
+    tp = _ptr("t", t, F32, (h, w), dev)
+    L.check(L.load().a3d_render_shade_depth(ip, tp, up, vp, fp, m, cp, n, float(strength), bgp, rgb.data_ptr(), w, h,
+                                            _stream(dev)), "a3d_render_shade_depth")
+    return rgb
+
+
+def vertex_normals(xyz, faces, offsets, corners, out=None):
+    """``a3d_vertex_normals``: fp32 [n, 3] from the incidence lists (``session.vertex_corner_lists``: int64 [n + 1], int32 [3 m])."""
+    dev = _device("xyz", xyz)
+    xp, fp = _ptr("xyz", xyz, F32, (None, 3), dev), _ptr("faces", faces, I32, (None, 3), dev)
+    op, cp = _ptr("offsets", offsets, I64, (None,), dev), _ptr("corners", corners, I32, (None,), dev)
+    n, m = xyz.shape[0], faces.shape[0]
+    out = _out("out", out, F32, (n, 3), dev)
+    L.check(L.load().a3d_vertex_normals(xp, n, fp, m, op, cp, out.data_ptr() if n else None, _stream(dev)),
+            "a3d_vertex_normals")
+    return out
+
+
+# ---- paint -------------------------------------------------------------------------------------------------------------------------
+def session_paint(labels_qv, inverse_map, xyz, colors, palette, cubes, cube_size, labels_out=None, colors_out=None, err=None):
+    """``a3d_session_paint``: ``(labels int32 [n], colours fp32 [n, 3], err int32 [1])`` of the n full-resolution vertices
+    from the voxels' labels through ``inverse_map`` (int64 [n]), ``palette`` fp32 [K + 1, 3] and the click ``cubes`` fp32
+    [k, 6] (``None``: none).  ``err`` != 0 (on the device): inverse_map or labels out of range."""
+    dev = _device("labels_qv", labels_qv)
+    n = inverse_map.shape[0] if torch.is_tensor(inverse_map) else 0
+    a = L.SessionPaintArgs()
+    a.labels_qv_dev, a.n_qv = _ptr("labels_qv", labels_qv, I32, (None,), dev), labels_qv.shape[0]
+    a.inverse_map_dev, a.n_full = _ptr("inverse_map", inverse_map, I64, (None,), dev), n
+    a.xyz_full_dev, a.colors_full_dev = _ptr("xyz", xyz, F32, (n, 3), dev), _ptr("colors", colors, F32, (n, 3), dev)
+    a.palette_dev, a.n_palette = _ptr("palette", palette, F32, (None, 3), dev), palette.shape[0]
+    a.cubes_dev, a.n_cubes = _ptr("cubes", cubes, F32, (None, 6), dev, optional=True), 0 if cubes is None else cubes.shape[0]
+    a.cube_size = cube_size
+    labels_out, colors_out = _out("labels_out", labels_out, I32, (n,), dev), _out("colors_out", colors_out, F32, (n, 3), dev)
+    err = _out("err", err, I32, (1,), dev)
+    a.label_full_dev, a.colors_out_dev, a.err_dev = labels_out.data_ptr(), colors_out.data_ptr(), err.data_ptr()
+    L.check(L.load().a3d_session_paint(C.byref(a), _stream(dev)), "a3d_session_paint")
+    return labels_out, colors_out, err

@@ -3,7 +3,7 @@
 THE RULE (include/agile3d_hip.h): the image is, pixel by pixel, what the picks return for the ray through the pixel's
 centre.  ``pixel_rays`` restates the camera's fp32 ray formula one operation at a time; ``face_pass_f32`` and
 ``point_pass_f32`` restate the two exact tests for ONE ray against all primitives (the arithmetic of
-``test_session_mesh_host.mesh_rule_f32`` and of ``k_pick_ray``), ``render_mesh_rule`` / ``render_points_rule`` fold them into
+``pick_rule.mesh_rule_f32`` and of ``k_pick_ray``), ``render_mesh_rule`` / ``render_points_rule`` fold them into
 images by brute force, ``shade_rule`` restates the colour image.
 
 THE BOUND (csrc/session.hip: render_rect_face, render_rect_point, render_rect_tiles): ``camera_bounds``, ``rect_face``,
@@ -12,9 +12,8 @@ rectangle in whole pixels before it is widened to tiles of 16.
 """
 import numpy as np
 
-from test_session_mesh_host import F32, mesh_rule_f32, shear_of
+from pick_rule import F32, U, mesh_rule_f32, shear_of
 
-U = 2.0 ** -24
 TILE = 16
 MAX_RECT_TILES = 256
 
@@ -123,9 +122,15 @@ def render_points_rule(xyz32, r, cam):
     return index, t
 
 
-def shade_rule(ids, u, v, faces, colors32, background):
-    """uint8 [h, w, 3]: the vertex's colour (faces None) or ((1 - u - v) c0 + u c1) + v c2 in fp32, background where id < 0,
-    quantised as (uint8)(min(max(c, 0), 1) * 255 + 0.5)."""
+def quantise(c):
+    q = np.minimum(np.maximum(c, F32(0)), F32(1)) * F32(255) + F32(0.5)
+    assert q.dtype == F32
+    return q.astype(np.uint8)
+
+
+def base_colors(ids, u, v, faces, colors32, background):
+    """(fp32 [h, w, 3] unquantised colours, the mask of pixels that are not background) as a3d_render_shade computes them:
+    the vertex's colour (faces None) or ((1 - u - v) c0 + u c1) + v c2 in fp32, background where id < 0."""
     colors32 = np.asarray(colors32, F32)
     h, w = ids.shape
     c = np.empty((h, w, 3), F32)
@@ -139,9 +144,12 @@ def shade_rule(ids, u, v, faces, colors32, background):
         ww = (F32(1.0) - uu) - vv
         c[hit] = (ww * colors32[f[:, 0]] + uu * colors32[f[:, 1]]) + vv * colors32[f[:, 2]]
     assert c.dtype == F32
-    q = np.minimum(np.maximum(c, F32(0)), F32(1)) * F32(255) + F32(0.5)
-    assert q.dtype == F32
-    return q.astype(np.uint8)
+    return c, hit
+
+
+def shade_rule(ids, u, v, faces, colors32, background):
+    """uint8 [h, w, 3]: the base colours quantised as (uint8)(min(max(c, 0), 1) * 255 + 0.5)."""
+    return quantise(base_colors(ids, u, v, faces, colors32, background)[0])
 
 
 # ------------------------------------------------------------------------------------------- the bound

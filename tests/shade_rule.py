@@ -2,12 +2,12 @@
 ``test_gpu_shade.py``: vertex normals (``a3d_vertex_normals``), the lit colour image of a mesh (``a3d_render_shade_lit``)
 and the depth-shaded one of a cloud (``a3d_render_shade_depth``).  The rules are stated in include/agile3d_hip.h; every
 product, sum, difference, quotient and square root below is one fp32 operation, in the header's order, so the kernels
-must give these bits.  ``base_colors`` is the unquantised part of ``render_rule.shade_rule``.
+must give these bits.  The base colours and the quantisation are ``render_rule``'s.
 """
 import numpy as np
 
-from render_rule import pixel_rays
-from test_session_mesh_host import F32
+from pick_rule import F32
+from render_rule import base_colors, pixel_rays, quantise
 
 
 def vertex_normals_rule(xyz32, faces, offsets, corners):
@@ -35,30 +35,6 @@ def vertex_normals_rule(xyz32, faces, offsets, corners):
                 out[v] = s / np.sqrt(l2)
     assert out.dtype == F32
     return out
-
-
-def quantise(c):
-    q = np.minimum(np.maximum(c, F32(0)), F32(1)) * F32(255) + F32(0.5)
-    assert q.dtype == F32
-    return q.astype(np.uint8)
-
-
-def base_colors(ids, u, v, faces, colors32, background):
-    """(fp32 [h, w, 3] unquantised colours, the mask of pixels that are not background) as a3d_render_shade computes them."""
-    colors32 = np.asarray(colors32, F32)
-    h, w = ids.shape
-    c = np.empty((h, w, 3), F32)
-    c[:] = np.asarray(background, F32)
-    hit = ids >= 0
-    if faces is None:
-        c[hit] = colors32[ids[hit]]
-    else:
-        f = np.asarray(faces, np.int64).reshape(-1, 3)[ids[hit]]
-        uu, vv = u[hit][:, None], v[hit][:, None]
-        ww = (F32(1.0) - uu) - vv
-        c[hit] = (ww * colors32[f[:, 0]] + uu * colors32[f[:, 1]]) + vv * colors32[f[:, 2]]
-    assert c.dtype == F32
-    return c, hit
 
 
 def lit_factor(ids, u, v, faces, normals32, cam, ambient):

@@ -3,7 +3,8 @@ InteractiveSession.render / pick_from_render).
 
 The specification is in the tree: the image is, pixel by pixel, what the picks return for the ray through the pixel's
 centre.  The yardsticks are the numpy float32 restatements of ``render_rule.py`` (which ``test_render_host.py`` holds
-against each other and against the bound on the CPU) and the existing picks themselves.
+against each other and against the bound on the CPU) and the existing picks themselves.  Scenes, cameras and the adaptors
+that reach the library through ``agile3d_amd.view`` are in ``session_kit.py``.
 
 1  images equal the per-pixel pick rule bit for bit (ids, t, u, v), and a3d_pick_mesh / a3d_pick_ray on 64 sampled pixels
 2  no cracks: a jittered plane in front of a second one, near the origin and at 50 m
@@ -11,144 +12,24 @@ against each other and against the bound on the CPU) and the existing picks them
 4  shading
 5  the session: render, the hidden retry, pick_from_render
 """
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import session_kit
 from agile3d_amd import lib as L
+from agile3d_amd import view as V
 from agile3d_amd.session import camera_from_matrices
+from pick_rule import F32
 from render_rule import camera_fields, pixel_rays, render_mesh_rule, render_points_rule, shade_rule
-from test_gpu_session import _model, pick_ray
-from test_gpu_session_mesh import pick_mesh
-from test_render_host import intrinsic, look_at
-from test_session_fixtures import CASES, load_session_case
-from test_session_mesh_host import F32, PlanesScene, rotation
+from session_kit import (CASES, DEV, FAR, PlanesScene, bits, camera_of, cloud_scene, intrinsic, load_session_case, look_at,
+                         mesh_scene, pick_mesh, pick_ray, render, rotation, sampled_pixels, shade)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 SIZES = [(37, 29), (1, 1), (16, 16)]
-FAR = np.array([50.3, -48.7, 1.2])
-bits = lambda x: np.ascontiguousarray(x, F32).view(np.uint32)
-
-
-def render(xyz, faces, cam, radius=None, capacity=1 << 16, uv=True):
-    """a3d_render_mesh (``faces`` an array, possibly empty) or a3d_render_points (``faces`` None) through the raw library.
-    The images start as sentinels (-7 / -7.0) so that an untouched image shows."""
-    lib = L.load()
-    h, w = cam.height, cam.width
-    xyz_dev = torch.from_numpy(np.ascontiguousarray(xyz, F32).reshape(-1, 3)).to(DEV)
-    n = xyz_dev.shape[0]
-    mesh = faces is not None
-    m = len(faces) if mesh else n
-    faces_dev = torch.from_numpy(np.ascontiguousarray(faces, np.int32)).to(DEV) if mesh and m else None
-    ids = torch.full((h, w), -7, dtype=torch.int32, device=DEV)
-    t, u, v = (torch.full((h, w), -7.0, dtype=torch.float32, device=DEV) for _ in range(3))
-    header = torch.full((4,), -7, dtype=torch.int32, device=DEV)
-    out = L.RenderOut(ids.data_ptr(), t.data_ptr(), u.data_ptr() if uv else None, v.data_ptr() if uv else None,
-                      header.data_ptr())
-    ws = torch.empty(lib.a3d_render_workspace_bytes(m, w, h, capacity), dtype=torch.uint8, device=DEV)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if mesh:
-        L.check(lib.a3d_render_mesh(xyz_dev.data_ptr() if n else None, n, faces_dev.data_ptr() if m else None, m, C.byref(cam),
-                                    C.byref(out), ws.data_ptr(), ws.numel(), stream), "a3d_render_mesh")
-    else:
-        L.check(lib.a3d_render_points(xyz_dev.data_ptr() if n else None, n, float(radius), C.byref(cam), C.byref(out),
-                                      ws.data_ptr(), ws.numel(), stream), "a3d_render_points")
-    head = header.cpu().numpy()
-    return dict(ids=ids.cpu().numpy(), t=t.cpu().numpy(), u=u.cpu().numpy(), v=v.cpu().numpy(), flags=int(head[0]),
-                n_everywhere=int(head[1]), pairs=int(head[2:4].view(np.int64)[0]), dev=(ids, u, v, faces_dev))
-
-
-def shade(r, faces, colors, background, n_vertices):
-    lib = L.load()
-    ids, u, v, faces_dev = r["dev"]
-    h, w = ids.shape
-    col = torch.from_numpy(np.ascontiguousarray(colors, F32)).to(DEV)
-    rgb = torch.zeros((h, w, 3), dtype=torch.uint8, device=DEV)
-    bg = np.ascontiguousarray(background, F32)
-    mesh = faces is not None
-    L.check(lib.a3d_render_shade(ids.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
-                                 faces_dev.data_ptr() if mesh and len(faces) else None, len(faces) if mesh else 0,
-                                 col.data_ptr() if n_vertices else None, n_vertices, bg.ctypes.data_as(C.POINTER(C.c_float)),
-                                 rgb.data_ptr(), w, h, None), "a3d_render_shade")
-    return rgb.cpu().numpy()
-
-
-# ------------------------------------------------------------------------------------------- scenes
-def _grid_faces(idx):
-    q00, q10, q01, q11 = idx[:-1, :-1], idx[1:, :-1], idx[:-1, 1:], idx[1:, 1:]
-    return np.concatenate([np.stack([q00, q10, q11], -1).reshape(-1, 3), np.stack([q00, q11, q01], -1).reshape(-1, 3)])
-
-
-def _plane(grid, rng):
-    """A jittered lattice of grid x grid quads in the plane z = 0, x in [-1, 1], y in [0, 12]: seen from (0, -1, 0.6) it
-    recedes, its far faces smaller than a pixel of a 37-pixel image."""
-    gx, gy = np.linspace(-1, 1, grid + 1), np.linspace(0, 12, grid + 1)
-    x, y = np.meshgrid(gx, gy, indexing="ij")
-    p = np.stack([x, y, np.zeros_like(x)], -1)
-    p[1:-1, 1:-1, :2] += rng.uniform(-0.2, 0.2, (grid - 1, grid - 1, 2)) * [2 / grid, 12 / grid]
-    p[..., 2] += rng.uniform(-0.01, 0.01, p.shape[:2])
-    return p.reshape(-1, 3), _grid_faces(np.arange((grid + 1) ** 2).reshape(grid + 1, grid + 1))
-
-
-def _box(k=3):
-    """A closed box [-1, 1]^3, every side k x k quads: around a camera inside it faces lie ahead, cross the camera plane
-    and lie wholly behind."""
-    g = np.linspace(-1, 1, k + 1)
-    a, b = np.meshgrid(g, g, indexing="ij")
-    verts, faces = [], []
-    for axis in range(3):
-        for side in (-1.0, 1.0):
-            p = np.empty((k + 1, k + 1, 3))
-            p[..., axis], p[..., (axis + 1) % 3], p[..., (axis + 2) % 3] = side, a, b
-            faces.append(_grid_faces(len(verts) * (k + 1) ** 2 + np.arange((k + 1) ** 2).reshape(k + 1, k + 1)))
-            verts.append(p.reshape(-1, 3))
-    return np.concatenate(verts), np.concatenate(faces)
-
-
-@functools.lru_cache(maxsize=None)
-def mesh_scene(name):
-    """(xyz fp32, faces int32, eye, target, fov, expected flags)."""
-    rng = np.random.default_rng(5)
-    if name == "quad larger than the view":
-        xyz = np.array([[-50, 4, -50], [50, 4, -50], [50, 4, 50], [-50, 4, 50]], np.float64)
-        return xyz.astype(F32), np.array([[0, 1, 2], [0, 2, 3]], np.int32), [0.2, 0.0, 0.1], [0.0, 4.0, 0.0], 70.0, 0
-    if name in ("receding plane", "receding plane at 50 m"):
-        xyz, faces = _plane(14, rng)                                   # 392 faces
-        shift = FAR if name.endswith("50 m") else np.zeros(3)
-        return (xyz + shift).astype(F32), faces.astype(np.int32), shift + [0.0, -1.0, 0.6], shift + [0.0, 3.0, 0.0], 60.0, 0
-    if name == "inside a box":
-        xyz, faces = _box()
-        # and a slanted face across the box whose bounding box holds the camera: no bound, every pixel tests it
-        faces = np.concatenate([faces, [[len(xyz), len(xyz) + 1, len(xyz) + 2]]])
-        xyz = np.concatenate([xyz, [[0.0, -1.0, -1.0], [0.0, 1.0, -1.0], [1.6, 0.0, 1.0]]])
-        return xyz.astype(F32), faces.astype(np.int32), [0.3, -0.2, 0.1], [1.0, 0.4, 0.3], 100.0, 0
-    if name == "bad faces":
-        xyz, faces = _plane(6, rng)
-        nan_vertex = len(xyz)
-        xyz = np.concatenate([xyz, [[np.nan, 1.0, 0.5]]])
-        bad = [[0, 0, 5], [3, 9, nan_vertex], [1, 2, len(xyz)], [-1, 4, 7], [0, 7, 14]]   # repeated, NaN, out of range x 2, collinear
-        xyz[[0, 7, 14]] = [[-1, 0, 0.5], [-0.5, 1, 0.5], [0, 2, 0.5]]                      # (three lattice vertices moved onto a line)
-        return xyz.astype(F32), np.concatenate([bad, faces]).astype(np.int32), [0.0, -1.0, 0.6], [0.0, 3.0, 0.0], 60.0, 1
-    raise KeyError(name)
-
-
 MESH_SCENES = ["quad larger than the view", "receding plane", "receding plane at 50 m", "inside a box", "bad faces"]
-
-
-def camera_of(eye, target, fov, size):
-    w, h = size
-    return camera_from_matrices(intrinsic(w, h, fov), look_at(eye, target), w, h)
-
-
-def sampled_pixels(w, h, k=64):
-    rng = np.random.default_rng(w * h)
-    if w * h <= k:
-        return [(i, j) for j in range(h) for i in range(w)]
-    return [(int(rng.integers(w)), int(rng.integers(h))) for _ in range(k)]
 
 
 # ------------------------------------------------------------------------------------------- 1, 4: meshes
@@ -218,20 +99,6 @@ def test_no_faces_and_no_points(size):
 
 
 # ------------------------------------------------------------------------------------------- 1, 4: point clouds
-@functools.lru_cache(maxsize=None)
-def cloud_scene(name):
-    """(xyz fp32, radius, eye, target, fov).  ~2 000 points on a receding sheet whose discs (radius 6 cm: 2 to 40 pixels of
-    a 37-pixel image) straddle tile borders, exact duplicates of 20 of them at higher rows, and a point 3 cm from the eye,
-    to its right: it is the first vertex of the rays that look far enough to the right, and of no others."""
-    rng = np.random.default_rng(8)
-    shift = FAR if name.endswith("50 m") else np.zeros(3)
-    eye = shift + [0.0, -1.0, 0.6]
-    p = np.stack([rng.uniform(-1.5, 1.5, 2000), rng.uniform(-0.6, 6.0, 2000), rng.uniform(-0.05, 0.05, 2000)], 1) + shift
-    near = eye + [0.03, -0.012, 0.0]
-    xyz = np.concatenate([p, p[:20], [near]]).astype(F32)
-    return xyz, 0.06, eye, shift + [0.0, 3.0, 0.0], 60.0
-
-
 @functools.lru_cache(maxsize=None)
 def cloud_reference(name, size):
     xyz, r, eye, target, fov = cloud_scene(name)
@@ -318,15 +185,14 @@ def test_capacity_protocol_and_determinism():
     fit = render(cxyz, None, ccam, radius=r, capacity=tiny["pairs"])
     assert np.array_equal(fit["ids"], big["ids"]) and np.array_equal(bits(fit["t"]), bits(big["t"]))
     # argument checks
-    lib = L.load()
-    assert lib.a3d_render_workspace_bytes(10, 0, 5, 1) == 0 and lib.a3d_render_workspace_bytes(10, 4097, 5, 1) == 0
-    assert lib.a3d_render_workspace_bytes(10, 16, 16, 1 << 20) >= 4 << 20
+    assert V.render_workspace_bytes(10, 0, 5, 1) == 0 and V.render_workspace_bytes(10, 4097, 5, 1) == 0
+    assert V.render_workspace_bytes(10, 16, 16, 1 << 20) >= 4 << 20
 
 
 # ------------------------------------------------------------------------------------------- 5
 @pytest.fixture(scope="module")
 def model_005():
-    return _model(0.05)
+    return session_kit.model_005()
 
 
 def _ray_survives_pick(d32):

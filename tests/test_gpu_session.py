@@ -1,4 +1,5 @@
 """-m gpu: the headless interactive session (agile3d_amd/session.py on csrc/session.hip).  Reads tests/golden only.
+The library is reached through ``session_kit.py``'s adaptors over ``agile3d_amd.view``; the rules are in ``pick_rule.py``.
 
 1  a3d_nearest_rows against the float64 brute-force arg-min (fixture scenes, synthetic 80 k / 300 k rows x 64 queries)
 2  a3d_pick_ray against a float64 statement of the pick rule
@@ -10,7 +11,6 @@
 6  determinism, reset(), no state left from a previous scene; load_scene_dir == load_scene on the same arrays
 7  refusals
 """
-import ctypes as C
 import copy
 import os
 from datetime import datetime
@@ -19,46 +19,14 @@ import numpy as np
 import pytest
 import torch
 
-from agile3d_amd import build_model, default_args, randomize_bn_stats
+import session_kit
 from agile3d_amd import clicks as K
 from agile3d_amd import lib as L
 from agile3d_amd.synthetic import make_scene
-from test_session_fixtures import CASES, f64_argmin, load_session_case
+from pick_rule import U, fp32_rule_argmin, paint_numpy, pick_rule_f64
+from session_kit import CASES, DEV, _model, f64_argmin, load_session_case, nearest_rows, pick_ray, session_paint
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-U = 2.0 ** -24          # unit roundoff of fp32
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ws():
-    lib = L.load()
-    return torch.empty(lib.a3d_session_workspace_bytes(), dtype=torch.uint8, device=DEV)
-
-
-def nearest_rows(sources, queries):
-    """a3d_nearest_rows: list of fp32 [n, 3] arrays x fp32 [m, 3] queries -> int32 [n_sources, m]."""
-    lib = L.load()
-    q = np.ascontiguousarray(queries, np.float32)
-    dev = [torch.from_numpy(np.ascontiguousarray(s, np.float32)).to(DEV) for s in sources]
-    out = torch.full((len(dev), len(q)), -7, dtype=torch.int32, device=DEV)
-    src = (L.NearestSource * len(dev))()
-    for i, d in enumerate(dev):
-        src[i].xyz_dev, src[i].n, src[i].rows_out_dev = d.data_ptr(), d.shape[0], out[i].data_ptr()
-    ws = _ws()
-    L.check(lib.a3d_nearest_rows(src, len(dev), q.ctypes.data_as(C.POINTER(C.c_float)), len(q), ws.data_ptr(), ws.numel(),
-                                 _stream()), "a3d_nearest_rows")
-    return out.cpu().numpy()
-
-
-def fp32_rule_argmin(rows, q):
-    """The header's rule one fp32 operation at a time: (dx*dx + dy*dy) + dz*dz from the differences, first arg-min."""
-    d = rows.astype(np.float32) - q.astype(np.float32)
-    s = d * d
-    return int(((s[:, 0] + s[:, 1]) + s[:, 2]).argmin())
 
 
 def check_nearest(rows, queries, got, max_under=0.02):
@@ -138,36 +106,6 @@ def test_nearest_rows_synthetic(n, shift):
 
 
 # ---------------------------------------------------------------------------------------------------- 2
-def pick_ray(xyz_dev, o, d, r):
-    lib = L.load()
-    o = np.ascontiguousarray(o, np.float32)
-    d = np.ascontiguousarray(d, np.float32)
-    out = torch.zeros(4, dtype=torch.int32, device=DEV)
-    ws = _ws()
-    fp = C.POINTER(C.c_float)
-    L.check(lib.a3d_pick_ray(xyz_dev.data_ptr(), xyz_dev.shape[0], o.ctypes.data_as(fp), d.ctypes.data_as(fp), float(r),
-                             out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "a3d_pick_ray")
-    h = out.cpu().numpy()
-    return int(h[0]), h[1:].view(np.float32)
-
-
-def pick_rule_f64(xyz, o, d, r):
-    """The pick rule in float64: (index or -1, margin in t between the first two candidates, smallest distance of any
-    point in front of / near the origin plane to the cylinder surface, smallest |t| of a point inside the cylinder)."""
-    v = xyz.astype(np.float64) - o.astype(np.float64)
-    d = d.astype(np.float64)
-    t = v @ d
-    perp = np.linalg.norm(v - t[:, None] * d, axis=1)
-    cand = np.flatnonzero((t > 0) & (perp <= r))
-    surface = np.abs(perp[t > -1e-3] - r).min() if (t > -1e-3).any() else np.inf
-    plane = np.abs(t[perp <= r + 1e-3]).min() if (perp <= r + 1e-3).any() else np.inf
-    if len(cand) == 0:
-        return -1, np.inf, surface, plane
-    order = cand[np.lexsort((cand, perp[cand], t[cand]))]
-    gap = t[order[1]] - t[order[0]] if len(order) > 1 else np.inf
-    return int(order[0]), gap, surface, plane
-
-
 def _pick_scene():
     """A 20 k-point cloud plus, far above it (nothing else within metres), the points of the constructed cases."""
     xyz = make_scene(20_000, seed=4)["raw_xyz"].astype(np.float32)
@@ -260,35 +198,6 @@ def test_pick_ray_against_float64_rule():
 
 
 # ---------------------------------------------------------------------------------------------------- 3
-def session_paint(labels_qv, inverse_map, xyz32, colors32, palette, cubes, cube_size):
-    lib = L.load()
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(DEV)
-    lq, inv, xyz, col, pal = t(labels_qv, np.int32), t(inverse_map, np.int64), t(xyz32, np.float32), t(colors32, np.float32), t(palette, np.float32)
-    cb = t(cubes, np.float32) if len(cubes) else None
-    n = len(inverse_map)
-    lab = torch.full((n,), -9, dtype=torch.int32, device=DEV)
-    out = torch.full((n, 3), -9.0, dtype=torch.float32, device=DEV)
-    err = torch.ones(1, dtype=torch.int32, device=DEV)
-    a = L.SessionPaintArgs()
-    a.labels_qv_dev, a.n_qv, a.inverse_map_dev, a.n_full = lq.data_ptr(), len(labels_qv), inv.data_ptr(), n
-    a.xyz_full_dev, a.colors_full_dev, a.palette_dev, a.n_palette = xyz.data_ptr(), col.data_ptr(), pal.data_ptr(), len(palette)
-    a.cubes_dev, a.n_cubes, a.cube_size = (cb.data_ptr() if cb is not None else None), len(cubes), cube_size
-    a.label_full_dev, a.colors_out_dev, a.err_dev = lab.data_ptr(), out.data_ptr(), err.data_ptr()
-    L.check(lib.a3d_session_paint(C.byref(a), _stream()), "a3d_session_paint")
-    return lab.cpu().numpy(), out.cpu().numpy(), int(err.cpu()[0])
-
-
-def paint_numpy(labels_qv, inverse_map, xyz32, colors32, palette, cubes, cube_size):
-    lab = labels_qv[inverse_map]
-    n = len(palette)
-    entry = np.where(lab < n, lab, 1 + (lab - 1) % (n - 1))
-    col = np.where((lab > 0)[:, None], palette[entry], colors32).astype(np.float32)
-    for c in cubes:
-        inside = (np.abs(xyz32 - c[:3].astype(np.float32)) < np.float32(cube_size)).all(1)
-        col[inside] = c[3:]
-    return lab, col
-
-
 @pytest.mark.parametrize("name", CASES)
 def test_session_paint_fixture_scenes(name):
     c, meta = load_session_case(name)
@@ -325,11 +234,6 @@ def test_session_paint_fixture_scenes(name):
 
 
 # ---------------------------------------------------------------------------------------------------- 4..7
-def _model(voxel_size):
-    torch.manual_seed(0)
-    return randomize_bn_stats(build_model(default_args(voxel_size=voxel_size))).eval().to(DEV)
-
-
 @pytest.fixture(scope="module")
 def model_002():
     return _model(0.02)
@@ -337,7 +241,7 @@ def model_002():
 
 @pytest.fixture(scope="module")
 def model_005():
-    return _model(0.05)
+    return session_kit.model_005()
 
 
 def _synthetic_full(n_target, seed):

@@ -1,8 +1,9 @@
 """-m gpu: the mesh pick (a3d_pick_mesh in csrc/session.hip; InteractiveSession.pick / click_ray on a triangle mesh).
 
 No reference fixture exists for picking (the reference leaves it to Open3D's renderer): the yardsticks are the two
-statements of the rule in ``test_session_mesh_host.py`` -- float64 (Moeller-Trumbore form) and the kernel's arithmetic in
-numpy float32 -- which that file holds against each other on the CPU.
+statements of the rule in ``pick_rule.py`` -- float64 (Moeller-Trumbore form) and the kernel's arithmetic in numpy
+float32 -- which ``test_session_mesh_host.py`` holds against each other on the CPU.  The library is reached through
+``session_kit.py``'s adaptors over ``agile3d_amd.view``.
 
 1  bit identity with the fp32 restatement: face, t, u, v and hit point, at m = 0, 7, 256, 257 and 67 605 faces (the last
    is more than the first stage's 256 x 256 threads: the grid-stride loop takes a second trip), the aimed-at face at index
@@ -13,7 +14,6 @@ numpy float32 -- which that file holds against each other on the CPU.
 5  the rule's details on hand-built faces
 6  session plumbing
 """
-import ctypes as C
 import functools
 import os
 
@@ -21,35 +21,13 @@ import numpy as np
 import pytest
 import torch
 
-from agile3d_amd import build_model, default_args, randomize_bn_stats
-from agile3d_amd import lib as L
-from test_session_mesh_host import (F32, U, PlanesScene, first_of, mesh_rule_f32, mesh_rule_f64, rotation, shear_of,
-                                    subset_with_target)
+from agile3d_amd import view as V
+from pick_rule import F32, U, first_of, mesh_rule_f32, mesh_rule_f64, shear_of
+from session_kit import (DEV, PlanesScene, _model, f32_pointer, pick_mesh, pick_ray, rotation, status, subset_with_target)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-RESULT = np.dtype([("face", "i4"), ("flags", "i4"), ("t", "f4"), ("x", "f4"), ("y", "f4"), ("z", "f4"), ("u", "f4"), ("v", "f4")])
 PLACEMENTS = {"near": (0.0, 0.0, 0.0), "far": (50.3, -48.7, 1.2)}
 GRID = 130                                   # 2 x (2 x 130^2) + 5 = 67 605 faces > 65 536
-
-
-def pick_mesh(xyz, faces, rays):
-    """a3d_pick_mesh for every (origin, direction) of ``rays`` on one mesh: a RESULT record array, one copy at the end."""
-    lib = L.load()
-    assert C.sizeof(L.PickMeshResult) == RESULT.itemsize == 32
-    xyz_dev = torch.from_numpy(np.ascontiguousarray(xyz, F32)).to(DEV)
-    m = 0 if faces is None else len(faces)
-    faces_dev = torch.from_numpy(np.ascontiguousarray(faces, np.int32)).to(DEV) if m else None
-    out = torch.full((max(len(rays), 1) * 8,), -7, dtype=torch.int32, device=DEV)
-    ws = torch.empty(lib.a3d_session_workspace_bytes(), dtype=torch.uint8, device=DEV)
-    fp = C.POINTER(C.c_float)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    for i, (o, d) in enumerate(rays):
-        o, d = np.ascontiguousarray(o, F32), np.ascontiguousarray(d, F32)
-        L.check(lib.a3d_pick_mesh(xyz_dev.data_ptr(), xyz_dev.shape[0], faces_dev.data_ptr() if m else None, m,
-                                  o.ctypes.data_as(fp), d.ctypes.data_as(fp), out.data_ptr() + 32 * i, ws.data_ptr(),
-                                  ws.numel(), stream), "a3d_pick_mesh")
-    return out.cpu().numpy().view(RESULT)[:len(rays)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -260,8 +238,7 @@ def test_no_ray_leaks_through_shared_edges_and_vertices(placement):
 # ---------------------------------------------------------------------------------------------------- 4, 6
 @pytest.fixture(scope="module")
 def model_002():
-    torch.manual_seed(0)
-    return randomize_bn_stats(build_model(default_args(voxel_size=0.02))).eval().to(DEV)
+    return _model(0.02)
 
 
 def _wall_scene():
@@ -338,16 +315,8 @@ def test_session_plumbing(model_002, tmp_path):
     with pytest.raises(ValueError):
         ses.pick(origin, direction, surface=True)                   # no faces
     # and the vertex pick is a3d_pick_ray itself
-    lib = L.load()
-    out = torch.zeros(4, dtype=torch.int32, device=DEV)
-    o32 = np.ascontiguousarray(origin, F32)
-    d32 = np.ascontiguousarray((direction / np.linalg.norm(direction)).astype(F32))
-    fp = C.POINTER(C.c_float)
-    L.check(lib.a3d_pick_ray(ses.coords_full.data_ptr(), len(xyz), o32.ctypes.data_as(fp), d32.ctypes.data_as(fp), 0.02,
-                             out.data_ptr(), ses._ws.data_ptr(), ses._ws.numel(),
-                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "a3d_pick_ray")
-    h = out.cpu().numpy()
-    assert h[0] >= 0 and [float(x) for x in h[1:].view(F32)] == vertex_rule[0]
+    index, vertex = pick_ray(ses.coords_full, origin, (direction / np.linalg.norm(direction)).astype(F32), 0.02, workspace=ses._ws)
+    assert index >= 0 and [float(x) for x in vertex] == vertex_rule[0]
     # faces out of range raise at load, and leave no scene behind
     for bad in (len(xyz), -1):
         f = faces.copy()
@@ -419,16 +388,13 @@ def test_rule_details():
     # no faces at all
     g = pick_mesh(xyz, None, [(o, up)])[0]
     assert g["face"] == -1 and g["flags"] == 0
-    # the argument checks of a3d_pick_ray
-    lib = L.load()
-    ws = torch.empty(lib.a3d_session_workspace_bytes(), dtype=torch.uint8, device=DEV)
+    # the argument checks of a3d_pick_mesh: the entry point as it is (sizes no tensor of this test has)
+    ws = V.session_workspace(DEV)
     out = torch.zeros(8, dtype=torch.int32, device=DEV)
     dev = torch.from_numpy(xyz).to(DEV)
     fdev = torch.tensor([[0, 1, 2]], dtype=torch.int32, device=DEV)
-    fp = C.POINTER(C.c_float)
-    call = lambda n, m, d, ws_bytes: lib.a3d_pick_mesh(dev.data_ptr(), n, fdev.data_ptr(), m, o.ctypes.data_as(fp),
-                                                      np.ascontiguousarray(d, F32).ctypes.data_as(fp), out.data_ptr(),
-                                                      ws.data_ptr(), ws_bytes, None)
+    call = lambda n, m, d, ws_bytes: status("a3d_pick_mesh", dev.data_ptr(), n, fdev.data_ptr(), m, f32_pointer(o),
+                                            f32_pointer(d), out.data_ptr(), ws.data_ptr(), ws_bytes, None)
     assert call(12, 1, up, ws.numel()) == 0
     assert call(12, 1, 2 * up, ws.numel()) != 0                     # not a unit vector
     assert call(12, 2 ** 31, up, ws.numel()) != 0 and call(2 ** 31, 1, up, ws.numel()) != 0

@@ -2,14 +2,14 @@
 InteractiveSession.render(lit=True), default_view).
 
 The rules are this library's and stated in include/agile3d_hip.h; the yardstick is their numpy float32 restatement in
-``shade_rule.py`` (which ``test_shade_host.py`` holds to float64 on the CPU).  Every comparison is bit for bit.
+``shade_rule.py`` (which ``test_shade_host.py`` holds to float64 on the CPU).  Every comparison is bit for bit.  Scenes,
+cameras and the adaptors that reach the library through ``agile3d_amd.view`` are in ``session_kit.py``.
 
 1  vertex normals on five meshes, twice
 2  the lit colour image of three mesh views at three sizes; ambient = 1 is the flat image
 3  the depth-shaded image of a cloud (and of a mesh's t image); strength = 0 is the flat image
 4  the session: lit=False keeps today's bytes, lit=True on a mesh and on a cloud, default_view on the committed mesh
 """
-import ctypes as C
 import functools
 import os
 import shutil
@@ -18,74 +18,18 @@ import numpy as np
 import pytest
 import torch
 
-from agile3d_amd import lib as L
+import session_kit
 from agile3d_amd.session import vertex_corner_lists
 from conftest import ROOT
+from pick_rule import F32
 from render_rule import shade_rule
+from session_kit import (DEV, _dev, bits, byref, camera_of, cloud_scene, f32_pointer, intrinsic, jittered_grid, look_at,
+                         mesh_scene, normals_gpu, render, shade, shade_depth, shade_lit, status)
 from shade_rule import depth_factor, depth_rule, lit_factor, lit_rule, vertex_normals_rule
-from test_gpu_render import camera_of, cloud_scene, mesh_scene, render, shade
-from test_gpu_session import _model
-from test_render_host import intrinsic, look_at
-from test_session_mesh_host import F32
-from test_shade_host import jittered_grid
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 SIZES = [(37, 29), (16, 16), (1, 1)]
 BG = (0.25, 0.5, 1.0)
-bits = lambda x: np.ascontiguousarray(x, F32).view(np.uint32)
-fp = C.POINTER(C.c_float)
-
-
-def _dev(a, dtype):
-    a = np.ascontiguousarray(a, dtype)
-    return torch.from_numpy(a).to(DEV) if a.size else None
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def normals_gpu(xyz, faces, offsets, corners):
-    """a3d_vertex_normals through the raw library; the output starts as a sentinel."""
-    lib = L.load()
-    xyz_dev, faces_dev = _dev(np.asarray(xyz, F32).reshape(-1, 3), F32), _dev(np.asarray(faces).reshape(-1, 3), np.int32)
-    off_dev, cor_dev = _dev(offsets, np.int64), _dev(corners, np.int32)
-    n, m = len(xyz), len(faces)
-    out = torch.full((n, 3), -7.0, dtype=torch.float32, device=DEV)
-    L.check(lib.a3d_vertex_normals(_ptr(xyz_dev), n, _ptr(faces_dev), m, _ptr(off_dev), _ptr(cor_dev), out.data_ptr(), None),
-            "a3d_vertex_normals")
-    return out.cpu().numpy()
-
-
-def shade_lit(r, faces, colors, normals, cam, ambient, background, n_vertices):
-    """a3d_render_shade_lit on the device images of ``test_gpu_render.render``."""
-    lib = L.load()
-    ids, u, v, faces_dev = r["dev"]
-    h, w = ids.shape
-    col, nrm = _dev(colors, F32), _dev(normals, F32)
-    rgb = torch.full((h, w, 3), 7, dtype=torch.uint8, device=DEV)
-    bg = np.ascontiguousarray(background, F32)
-    L.check(lib.a3d_render_shade_lit(ids.data_ptr(), u.data_ptr(), v.data_ptr(), _ptr(faces_dev), len(faces), _ptr(col),
-                                     n_vertices, _ptr(nrm), C.byref(cam), float(ambient), bg.ctypes.data_as(fp), rgb.data_ptr(),
-                                     None), "a3d_render_shade_lit")
-    return rgb.cpu().numpy()
-
-
-def shade_depth(r, t, faces, colors, strength, background, n_vertices):
-    """a3d_render_shade_depth on the device images of ``test_gpu_render.render`` (``t``: the host copy of its t image)."""
-    lib = L.load()
-    ids, u, v, faces_dev = r["dev"]
-    h, w = ids.shape
-    mesh = faces is not None
-    col, t_dev = _dev(colors, F32), torch.from_numpy(np.ascontiguousarray(t, F32)).to(DEV)
-    rgb = torch.full((h, w, 3), 7, dtype=torch.uint8, device=DEV)
-    bg = np.ascontiguousarray(background, F32)
-    L.check(lib.a3d_render_shade_depth(ids.data_ptr(), t_dev.data_ptr(), u.data_ptr() if mesh else None,
-                                       v.data_ptr() if mesh else None, _ptr(faces_dev) if mesh else None,
-                                       len(faces) if mesh else 0, _ptr(col), n_vertices, float(strength), bg.ctypes.data_as(fp),
-                                       rgb.data_ptr(), w, h, None), "a3d_render_shade_depth")
-    return rgb.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------- 1: normals
@@ -136,7 +80,7 @@ def test_vertex_normals_equal_the_rule(name):
 
 
 def test_vertex_normals_arguments():
-    lib = L.load()
+    call = lambda *args: status("a3d_vertex_normals", *args)                                   # the entry point as it is
     xyz, faces = _normal_mesh("tetrahedron")
     offsets, corners = vertex_corner_lists(faces, 4)
     x, f, o, c = _dev(xyz, F32), _dev(faces, np.int32), _dev(offsets, np.int64), _dev(corners, np.int32)
@@ -145,17 +89,17 @@ def test_vertex_normals_arguments():
     for at, bad in ((0, None), (1, -1), (2, None), (3, -1), (4, None), (5, None), (6, None), (3, 1 << 30)):
         args = list(ok)
         args[at] = bad
-        assert lib.a3d_vertex_normals(*args) == -1, (at, bad)                                  # A3D_ERR_INVALID
-    assert lib.a3d_vertex_normals(None, 0, None, 0, None, None, None, None) == 0
+        assert call(*args) == -1, (at, bad)                                                    # A3D_ERR_INVALID
+    assert call(None, 0, None, 0, None, None, None, None) == 0
     # lists that point outside themselves are skipped, not followed: the isolated vertex's zeros
     wild = _dev(np.array([-5, 1 << 40, 0, 3, 3], np.int64), np.int64)
     junk = _dev(np.full(12, 1 << 20, np.int32), np.int32)
-    assert lib.a3d_vertex_normals(x.data_ptr(), 4, f.data_ptr(), 4, wild.data_ptr(), junk.data_ptr(), out.data_ptr(), None) == 0
+    assert call(x.data_ptr(), 4, f.data_ptr(), 4, wild.data_ptr(), junk.data_ptr(), out.data_ptr(), None) == 0
     assert not out.cpu().numpy().any()
     # a mesh without faces: zeros
     out.fill_(5.0)
     zero = _dev(np.zeros(5, np.int64), np.int64)
-    assert lib.a3d_vertex_normals(x.data_ptr(), 4, None, 0, zero.data_ptr(), None, out.data_ptr(), None) == 0
+    assert call(x.data_ptr(), 4, None, 0, zero.data_ptr(), None, out.data_ptr(), None) == 0
     assert not out.cpu().numpy().any()
 
 
@@ -211,37 +155,37 @@ def test_lit_image_equals_the_rule(name, size):
 
 
 def test_lit_arguments():
-    lib = L.load()
+    lit = lambda *args: status("a3d_render_shade_lit", *args)                                  # the entry points as they are
+    depth = lambda *args: status("a3d_render_shade_depth", *args)
     xyz, faces, eye, target, fov, normals = lit_scene("quad larger than the view")
     cam = camera_of(eye, target, fov, (16, 16))
     r = render(xyz, faces, cam)
     ids, u, v, faces_dev = r["dev"]
     col, nrm = _dev(np.ones((4, 3)), F32), _dev(normals, F32)
     rgb = torch.zeros((16, 16, 3), dtype=torch.uint8, device=DEV)
-    bg = np.ascontiguousarray(BG, F32)
-    ok = [ids.data_ptr(), u.data_ptr(), v.data_ptr(), faces_dev.data_ptr(), 2, col.data_ptr(), 4, nrm.data_ptr(), C.byref(cam),
-          0.35, bg.ctypes.data_as(fp), rgb.data_ptr(), None]
-    assert lib.a3d_render_shade_lit(*ok) == 0
+    ok = [ids.data_ptr(), u.data_ptr(), v.data_ptr(), faces_dev.data_ptr(), 2, col.data_ptr(), 4, nrm.data_ptr(), byref(cam),
+          0.35, f32_pointer(BG), rgb.data_ptr(), None]
+    assert lit(*ok) == 0
     for at, bad in ((0, None), (1, None), (2, None), (3, None), (4, -1), (5, None), (6, -1), (7, None), (8, None), (9, -0.01),
                     (9, 1.01), (9, float("nan")), (10, None), (11, None)):
         args = list(ok)
         args[at] = bad
-        assert lib.a3d_render_shade_lit(*args) == -1, (at, bad)
+        assert lit(*args) == -1, (at, bad)
     # no faces: every pixel the background, whatever the ids say
     args = list(ok)
     args[3], args[4] = None, 0
-    assert lib.a3d_render_shade_lit(*args) == 0
+    assert lit(*args) == 0
     assert (rgb.cpu().numpy() == np.array([64, 128, 255], np.uint8)).all()
     # the depth pass
     t = torch.from_numpy(r["t"]).to(DEV)
     okd = [ids.data_ptr(), t.data_ptr(), u.data_ptr(), v.data_ptr(), faces_dev.data_ptr(), 2, col.data_ptr(), 4, 8.0,
-           bg.ctypes.data_as(fp), rgb.data_ptr(), 16, 16, None]
-    assert lib.a3d_render_shade_depth(*okd) == 0
+           f32_pointer(BG), rgb.data_ptr(), 16, 16, None]
+    assert depth(*okd) == 0
     for at, bad in ((0, None), (1, None), (2, None), (5, -1), (6, None), (7, -1), (8, -1.0), (8, float("inf")), (8, float("nan")),
                     (9, None), (10, None), (11, 0), (12, 4097)):
         args = list(okd)
         args[at] = bad
-        assert lib.a3d_render_shade_depth(*args) == -1, (at, bad)
+        assert depth(*args) == -1, (at, bad)
 
 
 # ------------------------------------------------------------------------------------------- 3: the depth-shaded image
@@ -284,7 +228,7 @@ def test_depth_image_of_a_mesh(size):
 # ------------------------------------------------------------------------------------------- 4: the session
 @pytest.fixture(scope="module")
 def model_005():
-    return _model(0.05)
+    return session_kit.model_005()
 
 
 def test_session_lit_render(model_005):

@@ -1,32 +1,15 @@
 """Host side of the rendered view (no GPU): the camera, the fp32 pixel rays, and the conservative bound that bins
 primitives to screen tiles -- restated in ``render_rule.py`` and held here against the exact per-pixel tests, so that
-``test_gpu_render.py`` compares the kernels with yardsticks that agree."""
+``test_gpu_render.py`` compares the kernels with yardsticks that agree.  The cameras' builders are in ``session_kit.py``."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from render_rule import (U, camera_bounds, camera_fields, face_pass_f32, pixel_rays, point_pass_f32, rect_face, rect_point,
+from pick_rule import F32, U
+from render_rule import (camera_bounds, camera_fields, face_pass_f32, pixel_rays, point_pass_f32, rect_face, rect_point,
                          render_mesh_rule)
-from test_session_mesh_host import F32, mesh_rule_f32, rotation
-
-
-def look_at(eye, target, up=(0.0, 0.0, 1.0)):
-    """4 x 4 world-to-camera, +z towards ``target``, +y down the image."""
-    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
-    z = (target - eye) / np.linalg.norm(target - eye)
-    x = np.cross(z, np.asarray(up, np.float64))
-    x /= np.linalg.norm(x)
-    y = np.cross(z, x)
-    ext = np.eye(4)
-    ext[:3, :3] = np.stack([x, y, z])
-    ext[:3, 3] = -ext[:3, :3] @ eye
-    return ext
-
-
-def intrinsic(w, h, fov_deg=60.0):
-    f = 0.5 * w / np.tan(np.radians(fov_deg) / 2)
-    return np.array([[f, 0.0, w / 2.0], [0.0, f, h / 2.0], [0.0, 0.0, 1.0]])
+from session_kit import intrinsic, look_at
 
 
 CAMERAS = [  # (intrinsic, extrinsic, width, height)

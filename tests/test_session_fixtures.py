@@ -1,26 +1,12 @@
 """CPU checks of the interactive-session fixtures (tests/golden/session_case_*.npz / .json, written by
 make_session_goldens.py from the reference's own ``find_nearest`` / ``get_next_click``) and of the pure-Python
-formatting helpers of ``agile3d_amd.session`` against the strings the reference wrote."""
-import json
-import os
+formatting helpers of ``agile3d_amd.session`` against the strings the reference wrote.  The loader is in ``session_kit.py``."""
 from datetime import datetime
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
-
-CASES = ("near", "far")
-
-
-def load_session_case(name):
-    z = np.load(os.path.join(GOLDEN, f"session_case_{name}.npz"))
-    with open(os.path.join(GOLDEN, f"session_case_{name}.json")) as f:
-        return {k: z[k] for k in z.files}, json.load(f)
-
-
-def f64_argmin(rows, p):
-    return int(((rows.astype(np.float64) - p.astype(np.float64)) ** 2).sum(1).argmin())
+from session_kit import CASES, f64_argmin, load_session_case
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -1,24 +1,13 @@
 """Host side of the lit view (no GPU): the incidence lists ``load_scene`` builds for ``a3d_vertex_normals``, the camera
 ``default_view`` derives from a scene, and the numpy restatement of the normal rule (``shade_rule.py``) that
-``test_gpu_shade.py`` holds the kernel to."""
+``test_gpu_shade.py`` holds the kernel to.  ``jittered_grid`` is in ``session_kit.py``."""
 import numpy as np
 import pytest
 
 from agile3d_amd.session import camera_from_matrices, framing_view, vertex_corner_lists
+from pick_rule import F32
+from session_kit import jittered_grid
 from shade_rule import vertex_normals_rule
-from test_session_mesh_host import F32
-
-
-def jittered_grid(nx, ny, seed=0, shift=(0.0, 0.0, 0.0)):
-    """(xyz fp32 [nx * ny, 3], faces int32): a lattice 0.1 apart in the plane z = 0, jittered in all three directions, two
-    triangles per cell."""
-    rng = np.random.default_rng(seed)
-    x, y = np.meshgrid(np.arange(nx) * 0.1, np.arange(ny) * 0.1, indexing="ij")
-    p = np.stack([x, y, np.zeros_like(x)], -1) + rng.uniform(-0.03, 0.03, (nx, ny, 3))
-    idx = np.arange(nx * ny).reshape(nx, ny)
-    q00, q10, q01, q11 = idx[:-1, :-1], idx[1:, :-1], idx[:-1, 1:], idx[1:, 1:]
-    faces = np.concatenate([np.stack([q00, q10, q11], -1).reshape(-1, 3), np.stack([q00, q11, q01], -1).reshape(-1, 3)])
-    return (p.reshape(-1, 3) + np.asarray(shift)).astype(F32), faces.astype(np.int32)
 
 
 def test_corner_lists_on_a_hand_made_mesh():
