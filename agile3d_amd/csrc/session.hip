@@ -904,6 +904,112 @@ __global__ __launch_bounds__(kSesBlock) void k_vertex_normals(const NormalTab t)
   t.out[3 * vtx] = nx, t.out[3 * vtx + 1] = ny, t.out[3 * vtx + 2] = nz;
 }
 
+// ---- the annotation in the view: the label image, object outlines and click markers (rules of ours; the header states them) --
+// Both are per-pixel passes: no atomics, no workspace, two calls give the same bytes.
+//
+// THE LABEL RULE: a cloud's pixel shows its vertex's label; a mesh's pixel the label of its face's HEAVIEST corner, with
+// w = (1 - u) - v: corner 0 if w >= u && w >= v, else corner 1 if u >= v, else corner 2 (ties -> the lower corner; NaN weights
+// fail every test and end at corner 2).  -1 where shade_base shows the background.  Label values pass through unchecked.
+struct LabelTab {
+  const int32_t* id;
+  const float *u, *v;
+  const int32_t* faces;
+  long long m, n;
+  const int32_t* labels;
+  int32_t* out;
+  long long pixels;
+};
+__global__ __launch_bounds__(kSesBlock) void k_render_labels(const LabelTab t) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (i >= t.pixels) return;
+  const int32_t id = t.id[i];
+  int32_t lab = -1;
+  if (!t.faces) {
+    if (id >= 0 && id < t.n) lab = t.labels[id];
+  } else if (id >= 0 && id < t.m) {
+    const int32_t f0 = t.faces[3 * (size_t)id], f1 = t.faces[3 * (size_t)id + 1], f2 = t.faces[3 * (size_t)id + 2];
+    if (f0 >= 0 && f1 >= 0 && f2 >= 0 && f0 < t.n && f1 < t.n && f2 < t.n) {
+      const float u = t.u[i], v = t.v[i], w = (1.f - u) - v;
+      lab = t.labels[(w >= u && w >= v) ? f0 : (u >= v ? f1 : f2)];
+    }
+  }
+  t.out[i] = lab;
+}
+
+// THE ANNOTATION RULE, per pixel p = (px, py), in this order: (1) the bytes of rgb_in; (2) if outlines are on and L_p >= 1 and
+// a 4-neighbour INSIDE the image has a label != L_p: the outline colour; (3) for every marker k in table order with
+// d2 = dx*dx + dy*dy (dx = (float)px - x_k, dy = (float)py - y_k), d2 <= radius^2 and t_k - t_p <= depth_slack: the marker's
+// colour if d2 <= inner_radius^2, else the border colour -- the last covering marker wins.  A row with a NaN field covers
+// nothing: the staging below turns its x into NaN, so its first comparison fails.  Colours are quantised as shade_q does,
+// the product and the sum rounded on their own.
+// The table is staged into LDS once per workgroup, one field per array: in the loop every lane reads the same address
+// (a broadcast), and a pixel that no marker covers touches x, y and t only.  A pixel reads its own colour before it writes
+// it and reads its neighbours from the label image, so rgb_out may be rgb_in.
+static_assert(kSesBlock >= A3D_MAX_CLICKS, "k_render_annotate stages one marker per thread");
+struct AnnotTab {
+  const uint8_t* in;
+  const int32_t* label;
+  const float* t;
+  const float* markers;
+  int n_markers, outlines;
+  float r2, i2, slack;
+  float outline[3], border[3];
+  uint8_t* out;
+  int width, height;
+  long long pixels;
+};
+__device__ __forceinline__ uint8_t annot_q(float c) {
+#pragma clang fp contract(off)
+  const float s = fminf(fmaxf(c, 0.f), 1.f) * 255.f;
+  return (uint8_t)(s + 0.5f);
+}
+__global__ __launch_bounds__(kSesBlock) void k_render_annotate(const AnnotTab a) {
+#pragma clang fp contract(off)
+  __shared__ float mx[A3D_MAX_CLICKS], my[A3D_MAX_CLICKS], mt[A3D_MAX_CLICKS], mc[A3D_MAX_CLICKS][3];
+  if ((int)threadIdx.x < a.n_markers) {
+    const float* row = a.markers + 6 * (size_t)threadIdx.x;
+    float f[6];
+    bool nan = false;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) f[j] = row[j], nan |= f[j] != f[j];
+    mx[threadIdx.x] = nan ? __builtin_nanf("") : f[0], my[threadIdx.x] = f[1], mt[threadIdx.x] = f[2];
+    mc[threadIdx.x][0] = f[3], mc[threadIdx.x][1] = f[4], mc[threadIdx.x][2] = f[5];
+  }
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (i >= a.pixels) return;
+  const int px = (int)((unsigned)i % (unsigned)a.width), py = (int)((unsigned)i / (unsigned)a.width);   // (pixels <= 4096^2)
+  uint8_t c0 = a.in[3 * i], c1 = a.in[3 * i + 1], c2 = a.in[3 * i + 2];
+  if (a.outlines) {
+    const int32_t lab = a.label[i];
+    if (lab >= 1) {
+      const bool edge = (px > 0 && a.label[i - 1] != lab) || (px + 1 < a.width && a.label[i + 1] != lab) ||
+                        (py > 0 && a.label[i - a.width] != lab) || (py + 1 < a.height && a.label[i + a.width] != lab);
+      if (edge) c0 = annot_q(a.outline[0]), c1 = annot_q(a.outline[1]), c2 = annot_q(a.outline[2]);
+    }
+  }
+  if (a.n_markers) {
+    const float fx = (float)px, fy = (float)py, tp = a.t[i];
+    int hit = -1;
+    bool inner = false;
+    for (int k = 0; k < a.n_markers; ++k) {
+      const float dx = fx - mx[k], dy = fy - my[k];
+      const float xx = dx * dx, yy = dy * dy;
+      const float d2 = xx + yy;
+      const float behind = mt[k] - tp;
+      const bool cover = (d2 <= a.r2) & (behind <= a.slack);        // (no short circuit: the loop stays free of branches)
+      hit = cover ? k : hit, inner = cover ? d2 <= a.i2 : inner;
+    }
+    if (hit >= 0) {
+      c0 = annot_q(inner ? mc[hit][0] : a.border[0]);
+      c1 = annot_q(inner ? mc[hit][1] : a.border[1]);
+      c2 = annot_q(inner ? mc[hit][2] : a.border[2]);
+    }
+  }
+  a.out[3 * i] = c0, a.out[3 * i + 1] = c1, a.out[3 * i + 2] = c2;
+}
+
 // Host: what the bound needs from a camera, in double.  false: a camera the renders refuse.
 static bool render_camera(const a3d_camera* c, RenderCam& r) {
   if (!c || c->width < 1 || c->height < 1 || c->width > A3D_RENDER_MAX_SIZE || c->height > A3D_RENDER_MAX_SIZE) return false;
@@ -1198,6 +1304,50 @@ extern "C" int a3d_vertex_normals(const float* xyz_dev, int64_t n, const int32_t
   NormalTab t;
   t.xyz = xyz_dev, t.n = n, t.faces = faces_dev, t.m = m, t.offsets = offsets_dev, t.corners = corners_dev, t.out = normals_out_dev;
   k_vertex_normals<<<(unsigned)((n + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" int a3d_render_labels(const int32_t* id_dev, const float* u_dev, const float* v_dev, const int32_t* faces_dev, int64_t m,
+                                 const int32_t* labels_dev, int64_t n, int32_t* label_out_dev, int width, int height,
+                                 void* stream) {
+  if (!id_dev || !label_out_dev || width < 1 || height < 1 || width > A3D_RENDER_MAX_SIZE || height > A3D_RENDER_MAX_SIZE ||
+      n < 0 || m < 0 || (n && !labels_dev) || (faces_dev && (!u_dev || !v_dev))) {
+    set_error("a3d_render_labels: bad arguments (%d x %d, n=%lld m=%lld; a mesh needs u_dev and v_dev)", width, height,
+              (long long)n, (long long)m);
+    return A3D_ERR_INVALID;
+  }
+  LabelTab t;
+  t.id = id_dev, t.u = u_dev, t.v = v_dev, t.faces = faces_dev, t.m = m, t.n = n, t.labels = labels_dev, t.out = label_out_dev;
+  t.pixels = (long long)width * height;
+  k_render_labels<<<(unsigned)((t.pixels + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" int a3d_render_annotate(const uint8_t* rgb_in_dev, const int32_t* label_dev, const float* t_dev,
+                                   const float* markers_dev, int n_markers, float radius, float inner_radius, float depth_slack,
+                                   const float* outline, const float* border, uint8_t* rgb_out_dev, int width, int height,
+                                   void* stream) {
+  const bool sizes = width >= 1 && height >= 1 && width <= A3D_RENDER_MAX_SIZE && height <= A3D_RENDER_MAX_SIZE;
+  const size_t bytes = sizes ? (size_t)3 * width * height : 0;
+  const uintptr_t in = (uintptr_t)rgb_in_dev, out = (uintptr_t)rgb_out_dev;
+  if (!sizes || !rgb_in_dev || !rgb_out_dev || !t_dev || !border || (outline && !label_dev) || n_markers < 0 ||
+      n_markers > A3D_MAX_CLICKS || (n_markers && !markers_dev) || !std::isfinite(radius) || !std::isfinite(inner_radius) ||
+      !(inner_radius >= 0.f && radius >= inner_radius) || !std::isfinite(depth_slack) || !(depth_slack >= 0.f) ||
+      (in != out && in < out + bytes && out < in + bytes)) {
+    set_error("a3d_render_annotate: bad arguments (%d x %d, markers=%d radius=%g inner_radius=%g depth_slack=%g; at most %d "
+              "markers, radius >= inner_radius >= 0, depth_slack >= 0, outlines need label_dev, rgb_out_dev is rgb_in_dev or "
+              "apart from it)", width, height, n_markers, (double)radius, (double)inner_radius, (double)depth_slack,
+              A3D_MAX_CLICKS);
+    return A3D_ERR_INVALID;
+  }
+  AnnotTab a;
+  a.in = rgb_in_dev, a.label = label_dev, a.t = t_dev, a.markers = markers_dev, a.n_markers = n_markers, a.outlines = outline ? 1 : 0;
+  a.r2 = radius * radius, a.i2 = inner_radius * inner_radius, a.slack = depth_slack;
+  for (int k = 0; k < 3; ++k) a.outline[k] = outline ? outline[k] : 0.f, a.border[k] = border[k];
+  a.out = rgb_out_dev, a.width = width, a.height = height, a.pixels = (long long)width * height;
+  k_render_annotate<<<(unsigned)((a.pixels + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(a);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

@@ -355,6 +355,11 @@ SYMBOLS = {
     "a3d_render_shade_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.c_int64, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_int,
                                          C.c_void_p]),
+    "a3d_render_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "a3d_render_annotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                      C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_int,
+                                      C.c_void_p]),
 }
 
 _lib = None

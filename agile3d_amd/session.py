@@ -13,6 +13,8 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
     vertex normals, the lit material    a3d_vertex_normals / a3d_render_shade_lit / a3d_render_shade_depth  (gui.py:556-557,
                                         135): render(lit=True); rules of ours, Open3D's lit material is not reproduced
     the camera that frames the scene    default_view       (gui.py:561-565; host code)
+    the object under a pixel, object    a3d_render_labels / a3d_render_annotate  (label_image, object_at, annotate: the
+    borders, the clicks in the view     GUI's user reads them off the window; rules of ours)
     find_nearest, twice per click       a3d_nearest_rows   (utils.py:27-29: two full torch.cdist calls; here exact)
     argmax + clicked rows               a3d_argmax_labels  (interactive_segmentation_user.py:78-81)
     pred[inverse_map], colours, cubes   a3d_session_paint  (:83-84,125-140; gui.py:276-298,327)
@@ -259,6 +261,7 @@ class InteractiveSession:
 
     def _reset_clicks(self):
         self._colors_last = None                    # colours of the last infer / preview: what render() shows by default
+        self._labels_last = None                    # its full-resolution labels: what label_image() shows by default
         self.click_idx = {"0": []}
         self.click_time_idx = {"0": []}
         self.click_positions = {"0": []}
@@ -489,6 +492,71 @@ class InteractiveSession:
         ww = f32(f32(1.0) - wu) - wv
         return [float(x) for x in (ww * pa + wu * pb) + wv * pc]
 
+    # ------------------------------------------------------------------ the annotation in the view
+    def _view_labels(self, result, labels):
+        """(labels int32 [n] on the device, the images ``(ids, u, v, faces)`` as ``view.render_labels`` takes them)."""
+        self._need_scene()
+        if result.mesh != (self.faces is not None):
+            raise ValueError("the render belongs to another scene")
+        n = self.coords_full.shape[0]
+        lab = self._labels_last if labels is None else labels
+        if lab is None:                             # before any infer / preview: all background
+            lab = torch.zeros(n, dtype=torch.int32, device=self.device)
+        if not torch.is_tensor(lab) or lab.device != self.device or lab.dtype != torch.int32 or tuple(lab.shape) != (n,):
+            raise ValueError(f"labels must be an int32 tensor [{n}] on the session's device")
+        return lab.contiguous(), (result.ids, result.u, result.v, self.faces)
+
+    def label_image(self, result, labels=None):
+        """int32 [h, w] on the device: the object id each pixel of ``result`` shows (``a3d_render_labels``) -- 0 =
+        background, -1 = the pixel shows nothing.  ``labels`` int32 [n] per-vertex labels on the device (default: the
+        full-resolution labels of the last ``infer`` / ``preview``, all background before any).  On a cloud a pixel shows
+        its vertex's label; on a mesh that of the heaviest corner of its face, which cuts a face among its vertices by
+        crisp borders -- not the vertex ``click`` would snap to, which is the nearest by Euclidean distance."""
+        lab, (ids, u, v, faces) = self._view_labels(result, labels)
+        return V.render_labels(ids, u, v, faces, lab)
+
+    def object_at(self, result, u, v, labels=None):
+        """The object id under pixel ``(u, v)`` (column, row) of ``result`` -- ``label_image``'s value there, computed for
+        that pixel alone -- or ``None`` where the pixel shows nothing.  One small device-to-host copy."""
+        lab, (ids, wu, wv, faces) = self._view_labels(result, labels)
+        u, v = int(u), int(v)
+        h, w = result.ids.shape
+        if not (0 <= u < w and 0 <= v < h):
+            raise ValueError(f"pixel ({u}, {v}) outside the {w} x {h} image")
+        one = lambda image: None if image is None else image[v:v + 1, u:u + 1]
+        obj = int(V.render_labels(one(ids), one(wu), one(wv), faces, lab, out=self._small[20:21].view(1, 1)).cpu())
+        return None if obj < 0 else obj
+
+    def annotate(self, result, labels=None, outlines=True, markers=True, outline_color=(0.0, 0.0, 0.0), marker_px=6.0,
+                 marker_border_px=1.5, marker_border_color=(1.0, 1.0, 1.0), depth_slack=None):
+        """uint8 [h, w, 3], a new tensor: ``result.rgb`` (left untouched) with the state of the annotation drawn over it
+        (``a3d_render_annotate``).  ``outlines``: a pixel of an object (``label_image(result, labels)`` >= 1) with a
+        4-neighbour inside the image that shows something else takes ``outline_color`` -- a border one pixel wide on
+        either side between two objects, none along the image's edge, none around the background.  ``markers``: every
+        click of the session, in click order (later clicks on top), is a disc of radius ``marker_px`` pixels around the
+        projection of its picked point (``view.marker_table``), in its cube's colour with a rim ``marker_border_px`` wide in
+        ``marker_border_color`` -- also a click that has no vertex in its cube and so leaves ``preview``'s colours alone.
+        A click shows through pixels whose surface lies up to ``depth_slack`` world units (default ``cube_size``) in front of
+        it and is hidden behind nearer ones.  The defaults -- black outlines, 6-pixel discs with a white 1.5-pixel rim --
+        are this project's settings, not the reference's (the GUI shows clicks as recoloured vertices only)."""
+        marker_px, marker_border_px = float(marker_px), float(marker_border_px)
+        slack = self.cube_size if depth_slack is None else float(depth_slack)
+        if not (np.isfinite(marker_px) and 0.0 <= marker_border_px <= marker_px):      # (NaN fails)
+            raise ValueError("marker_px must be finite and marker_border_px lie in [0, marker_px]")
+        if not (np.isfinite(slack) and slack >= 0.0):
+            raise ValueError("depth_slack must be finite and >= 0")
+        outline = _f3(outline_color, "outline_color") if outlines else None
+        border = _f3(marker_border_color, "marker_border_color")
+        lab, images = self._view_labels(result, labels)
+        label_image = V.render_labels(*images, lab) if outlines else None
+        table = None
+        if markers and self.num_clicks:
+            cubes = self._cubes[:self.num_clicks]
+            rows = V.marker_table(result.camera, cubes[:, :3], cubes[:, 3:])
+            table = torch.from_numpy(rows).to(self.device) if len(rows) else None
+        return V.render_annotate(result.rgb, label_image, result.t, table, marker_px, marker_px - marker_border_px, slack,
+                                 outline, border)
+
     def nearest(self, point):
         """(voxel row, full-resolution vertex) nearest to ``point``: both searches in one launch pair, exact."""
         self._need_scene()
@@ -556,7 +624,7 @@ class InteractiveSession:
         labels_full, colors = self._launch_paint(self._labels_qv, paint_cubes)
         if int(self._counts[3 * _N_IDS + 1:].cpu()[0]) & 0xffffffff:
             raise RuntimeError("a3d_session_paint: inverse_map or labels out of range")
-        self._colors_last = colors
+        self._colors_last, self._labels_last = colors, labels_full
         return labels_full, colors
 
     def infer(self, paint_cubes=False, logits=None):
@@ -594,7 +662,7 @@ class InteractiveSession:
         if host[3 * _N_IDS] or (int(host[3 * _N_IDS + 1]) & 0xffffffff):
             raise RuntimeError("inverse_map or labels out of range")
         self._labels_qv = labels_qv
-        self._colors_last = colors
+        self._colors_last, self._labels_last = colors, labels_full
         miou, per_obj = None, None
         if have_gt:
             t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())

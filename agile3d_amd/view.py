@@ -6,7 +6,8 @@ contiguity (``ValueError`` naming the argument, before the library is reached), 
 null pointer, writes into the output tensors the caller passes (``out=``, ``rgb=``, ``header=`` ...; allocated otherwise),
 launches on the current stream of the tensors' device and returns device tensors: no synchronisation, no copy to the host.
 Three-vectors the C ABI reads on the host (origin, direction, background, queries) are anything ``numpy`` turns into fp32.
-The ``read_*`` functions decode a result record from its host copy.  There is no CPU path.
+The ``read_*`` functions decode a result record from its host copy; ``marker_table`` projects click points to the rows
+``render_annotate`` draws, on the host.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -232,6 +233,65 @@ def vertex_normals(xyz, faces, offsets, corners, out=None):
     L.check(L.load().a3d_vertex_normals(xp, n, fp, m, op, cp, out.data_ptr() if n else None, _stream(dev)),
             "a3d_vertex_normals")
     return out
+
+
+# ---- the annotation in the view ----------------------------------------------------------------------------------------------
+def render_labels(ids, u, v, faces, labels, out=None):
+    """``a3d_render_labels``: int32 [h, w] labels of an id image from per-vertex ``labels`` int32 [n] -- a cloud's vertex
+    (``u``, ``v``, ``faces`` ``None``) or the heaviest corner of a mesh's face; -1 where the pixel shows nothing."""
+    dev = _device("ids", ids)
+    ip = _ptr("ids", ids, I32, (None, None), dev)
+    h, w = ids.shape
+    mesh = faces is not None
+    up, vp = _ptr("u", u, F32, (h, w), dev, optional=not mesh), _ptr("v", v, F32, (h, w), dev, optional=not mesh)
+    fp, lp = _ptr("faces", faces, I32, (None, 3), dev, optional=True), _ptr("labels", labels, I32, (None,), dev)
+    m = faces.shape[0] if mesh else 0
+    n = 0 if mesh and m == 0 else labels.shape[0]       # a mesh without faces: a cloud without vertices, every pixel -1
+    out = _out("out", out, I32, (h, w), dev)
+    L.check(L.load().a3d_render_labels(ip, up, vp, fp, m, lp, n, out.data_ptr(), w, h, _stream(dev)), "a3d_render_labels")
+    return out
+
+
+def render_annotate(rgb, label_image, t, markers, radius, inner_radius, depth_slack, outline, border, out=None):
+    """``a3d_render_annotate``: uint8 [h, w, 3], ``rgb`` with the objects of ``label_image`` (int32 [h, w]) outlined in
+    ``outline`` (``None``: no outlines, ``label_image`` may then be ``None``) and the ``markers`` (fp32 [k, 6] on the device,
+    ``marker_table``'s rows; ``None``: none) drawn over the pixels whose ``t`` lies no more than ``depth_slack`` in front of
+    them.  ``out`` may be ``rgb`` itself."""
+    dev = _device("rgb", rgb)
+    rp = _ptr("rgb", rgb, U8, (None, None, 3), dev)
+    h, w = rgb.shape[:2]
+    lp = _ptr("label_image", label_image, I32, (h, w), dev, optional=outline is None)
+    tp = _ptr("t", t, F32, (h, w), dev)
+    mp = _ptr("markers", markers, F32, (None, 6), dev, optional=True)
+    k = 0 if markers is None else markers.shape[0]
+    (oa, op) = (None, None) if outline is None else _f32p("outline", outline, (3,))
+    ba, bp = _f32p("border", border, (3,))
+    out = _out("out", out, U8, (h, w, 3), dev)
+    L.check(L.load().a3d_render_annotate(rp, lp, tp, mp, k, float(radius), float(inner_radius), float(depth_slack), op, bp,
+                                         out.data_ptr(), w, h, _stream(dev)), "a3d_render_annotate")
+    return out
+
+
+def marker_table(camera, points, colors):
+    """The rows ``(x, y, t, r, g, b)`` of ``a3d_render_annotate``'s markers for world ``points`` [k, 3] seen by the
+    ``lib.Camera`` ``camera``, with ``colors`` [k, 3]: fp32 [k', 6], in the order given.  From the camera's fp32 fields,
+    widened to float64: ``(a, b, c) = solve([du dv d00], p - o)``, the position ``x = a / c``, ``y = b / c`` in pixels (the
+    centre of pixel (u, v) is the position (u, v)) and ``t = |p - o|``, the parameter of the pixel's unit ray at the point,
+    as the render's ``t`` image holds it.  Rows with ``c <= 0`` (behind the camera) or a value that is not finite are left
+    out; each value is rounded to fp32 once.  Pure numpy."""
+    o, d00, du, dv = (np.array(f[:], np.float64) for f in (camera.o, camera.d00, camera.du, camera.dv))
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    col = np.asarray(colors, dtype=np.float64).reshape(-1, 3)
+    if len(col) != len(p):
+        raise ValueError("points and colors must both be [k, 3]")
+    try:
+        abc = np.linalg.solve(np.stack([du, dv, d00], 1), (p - o).T).T
+    except np.linalg.LinAlgError:
+        raise ValueError("camera: du, dv and d00 must be linearly independent") from None
+    with np.errstate(all="ignore"):
+        rows = np.concatenate([abc[:, :2] / abc[:, 2:], np.linalg.norm(p - o, axis=1)[:, None], col], 1).astype(np.float32)
+    keep = (abc[:, 2] > 0) & np.isfinite(rows).all(1)
+    return np.ascontiguousarray(rows[keep])
 
 
 # ---- paint -------------------------------------------------------------------------------------------------------------------------

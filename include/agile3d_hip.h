@@ -951,6 +951,51 @@ int    a3d_render_shade_depth(const int32_t* id_dev, const float* t_dev, const f
                               const float* background, uint8_t* rgb_dev, int width, int height, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The annotation in the view (csrc/session.hip): which object a pixel belongs to, borders between objects, and the clicks
+ * themselves.  The reference's user reads all three off Open3D's window by eye; a headless session answers them in data.
+ * THE RULES ARE THIS LIBRARY'S.  Both calls are per-pixel passes without atomics or workspace: two calls give the same
+ * bytes.  All arithmetic is fp32, every operation rounded on its own (no fma contraction), in the order written.
+ *
+ * THE LABEL IMAGE: label_out_dev int32 [h][w] from a render's id / u / v images and per-vertex labels labels_dev int32 [n].
+ *   faces_dev NULL (a cloud): label = labels[id] if 0 <= id < n, else -1.
+ *   A mesh: -1 unless 0 <= id < m and the face's three indices lie in 0..n-1 (a3d_render_shade's tests for the background).
+ *   Else, with w = (1 - u) - v, the label of the face's HEAVIEST corner:
+ *       corner 0 if w >= u && w >= v;   else corner 1 if u >= v;   else corner 2
+ *   A tie goes to the lower corner (u == w: corner 0; u == v above w: corner 1).  A NaN in u or in v makes w NaN as well,
+ *   so both tests fail: NaN weights end at corner 2.
+ *   This partitions a face among its three vertices by straight borders that meet at the centroid.  It is NOT the vertex a
+ *   click on the pixel snaps to: that is the scene's nearest vertex by Euclidean distance (a3d_nearest_rows), which on a
+ *   sliver can be another corner or a vertex of another face.
+ *   -1 means "shows nothing"; label values are passed through unchecked (0 = background by the session's convention).
+ * ------------------------------------------------------------------------------------------ */
+int    a3d_render_labels(const int32_t* id_dev, const float* u_dev, const float* v_dev, const int32_t* faces_dev, int64_t m,
+                         const int32_t* labels_dev, int64_t n, int32_t* label_out_dev, int width, int height, void* stream);
+
+/* Outlines and click markers composed over a colour image: rgb_out_dev uint8 [h][w][3] from rgb_in_dev (the same layout),
+ * the label image label_dev, the render's t image t_dev (+inf = nothing) and the marker table markers_dev fp32
+ * [n_markers][6] = (x, y, t, r, g, b): a position in pixels (the centre of pixel (u, v) is the position (u, v)), the ray
+ * parameter of the marked point as the t image holds it, a colour.  0 <= n_markers <= A3D_MAX_CLICKS, radius >=
+ * inner_radius >= 0 in pixels and depth_slack >= 0 in world units, all finite; else A3D_ERR_INVALID.  outline: a HOST
+ * array of 3, or NULL for no outlines (label_dev may then be NULL); border: a HOST array of 3.
+ * Per pixel p = (px, py), in this order:
+ *   1. the bytes of rgb_in, unchanged;
+ *   2. if outline is given and L_p >= 1 and some 4-neighbour INSIDE the image has a label != L_p (one that shows -1 or the
+ *      background 0 counts as different): the outline colour.  So the background and "nothing" are never outlined, an
+ *      object that ends at the image's edge gets no outline there, and between two objects both sides are drawn.
+ *   3. for k = 0 .. n_markers-1 in table order:  dx = (float)px - x_k, dy = (float)py - y_k, d2 = dx*dx + dy*dy; the marker
+ *      covers the pixel if d2 <= radius*radius and t_k - t_p <= depth_slack (a pixel that shows nothing has t_p = +inf:
+ *      the test passes); the pixel then takes the marker's colour if d2 <= inner_radius*inner_radius, else border.  The
+ *      LAST covering marker wins, as the last cube wins in a3d_session_paint.  A marker with a NaN in any of its six
+ *      fields covers nothing.
+ * Colours are quantised by a3d_render_shade's rule.  Markers arrive already projected: the kernel holds comparisons and
+ * two products, no matrix inverse.  Every pixel walks the whole table (staged in LDS); there is no culling by tile.
+ * rgb_out_dev == rgb_in_dev is allowed -- a pixel reads only its own colour and writes only its own, its neighbours are read
+ * from the label image; buffers that overlap in part are refused. */
+int    a3d_render_annotate(const uint8_t* rgb_in_dev, const int32_t* label_dev, const float* t_dev, const float* markers_dev,
+                           int n_markers, float radius, float inner_radius, float depth_slack, const float* outline,
+                           const float* border, uint8_t* rgb_out_dev, int width, int height, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mask losses (first piece of SURVEY.md section 8 row f-2).
  * Replaces: SetCriterion.loss_bce / loss_dice (models/criterion.py:14-110) for ONE sample and ONE
  * prediction level: losses_dev[0] = mean_i w_i * CE(logits_i, target_i), losses_dev[1] = mean_i w_i *

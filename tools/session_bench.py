@@ -5,6 +5,7 @@ overwrite, ``pred[inverse_map]``, ``.cpu().numpy()``, the per-object colour loop
 alternating, on one synthetic scene (~80 k voxels, ~250 k full-resolution vertices) at 1, 5, 10 and 20 clicks.
 
     python tools/session_bench.py [--voxels 80000] [--reps 60] [--out profiles/session_bench.json]
+                                  [--mesh-only | --render-only | --annotate-only]
 
 Every stage is timed twice: with device events around it (what the GPU spent) and with a host clock around a stage that
 ends in a synchronisation (what the caller waits).  Medians over ``--reps`` clicks after a warm-up of 10.  The baseline has
@@ -26,7 +27,14 @@ that went to the everywhere-list.  What to check: the whole call should cost far
 pixels x mean list length exact tests, is where the time belongs.  Every view is also shaded LIT, next to the flat shade
 and on the same images: the mesh with ``a3d_render_shade_lit``, the cloud with ``a3d_render_shade_depth``; the vertex
 normals (``a3d_vertex_normals``, once per scene in the session) and the host-side build of their incidence lists are timed
-once for the field.  The figure to read: lit shade time against flat shade time per view, with pixels and vertices."""
+once for the field.  The figure to read: lit shade time against flat shade time per view, with pixels and vertices.
+
+The ANNOTATE stage times the passes that draw the state of the annotation over those views: ``a3d_render_labels`` and
+``a3d_render_annotate`` (outlines on) with 0, 20 and 256 markers, next to ``a3d_render_shade`` and the render itself on
+the same images.  One launch of these sits at the floor of what a staged call measures, so every figure here is
+``--mesh-calls`` calls back to back between two events, median of 5 such windows, after a warm-up window.  The vertices'
+labels are stripes of five objects with background between them; the markers are vertices of the field projected by
+``view.marker_table``.  The figure to read: annotate at 256 markers against the render of the same view."""
 import argparse
 import json
 import os
@@ -199,6 +207,111 @@ def render_stage(ses, n_vertices, reps, warmup):
     return {"vertices": n, "faces": m, "normals": normals_ms, "views": out_rows}
 
 
+def annotate_stage(ses, n_vertices, calls):
+    """Label image, outlines and markers over the render stage's views (see the module docstring)."""
+    import ctypes as C
+    from agile3d_amd import lib as L
+    from agile3d_amd import view as V
+    from agile3d_amd.session import camera_from_matrices
+    lib, dev = ses.lib, ses.device
+    rng = np.random.default_rng(2)
+    xyz, faces, g = height_field(n_vertices, np.random.default_rng(1))
+    xyz_dev, faces_dev = torch.from_numpy(xyz).to(dev), torch.from_numpy(faces).to(dev)
+    col_dev = torch.rand((len(xyz), 3), device=dev)
+    n, m = len(xyz), len(faces)
+    stripe = np.floor(xyz[:, 0] / 0.4).astype(np.int64)
+    labels = np.where(stripe % 2 == 0, 1 + (stripe // 2) % 5, 0).astype(np.int32)     # objects 40 cm wide, background between
+    labels_dev = torch.from_numpy(labels).to(dev)
+    mid = 0.5 * g[-1]
+    cameras = {"outside": _look_at(np.array([mid, mid - 1.0, 4.0]), np.array([mid, mid, 0.0])),
+               "inside": _look_at(np.array([mid, mid, 0.4]), np.array([mid + 2.0, mid + 0.5, 0.2]))}
+    header = ses._small[16:20]
+    fp = C.POINTER(C.c_float)
+    bg, black, white = (np.full(3, c, np.float32) for c in (1.0, 0.0, 1.0))
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def back_to_back(fn):
+        per_call = []
+        for window in range(6):                     # (the first window warms up)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            per_call.append(a.elapsed_time(b) / calls)
+        return float(np.median(per_call[1:]))
+
+    rows = {}
+    print(f"\n== annotate: {n} vertices, {m} faces; device ms per call, {calls} calls back to back, median of 5 windows ==")
+    for w, h in ((640, 480), (1280, 720)):
+        f = 0.5 * w / np.tan(np.radians(30.0))
+        intr = np.array([[f, 0, w / 2], [0, f, h / 2], [0, 0, 1.0]])
+        ids, label_img = (torch.empty((h, w), dtype=torch.int32, device=dev) for _ in range(2))
+        t, u, v = (torch.empty((h, w), dtype=torch.float32, device=dev) for _ in range(3))
+        rgb, rgb_out = (torch.empty((h, w, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+        for cam_name, ext in cameras.items():
+            cam = camera_from_matrices(intr, ext, w, h)
+            table = V.marker_table(cam, xyz[rng.permutation(n)[:16384]], rng.uniform(0, 1, (16384, 3)))
+            table = table[(table[:, 0] >= 0) & (table[:, 0] <= w - 1) & (table[:, 1] >= 0) & (table[:, 1] <= h - 1)][:L.A3D_MAX_CLICKS]
+            assert len(table) == L.A3D_MAX_CLICKS, len(table)
+            table_dev = torch.from_numpy(table).to(dev)
+            for kind in ("mesh", "points"):
+                mesh = kind == "mesh"
+                n_prim = m if mesh else n
+                out = L.RenderOut(ids.data_ptr(), t.data_ptr(), u.data_ptr() if mesh else None, v.data_ptr() if mesh else None,
+                                  header.data_ptr())
+                up, vp, fcp, mm = (u.data_ptr(), v.data_ptr(), faces_dev.data_ptr(), m) if mesh else (None, None, None, 0)
+
+                def render(ws):
+                    if mesh:
+                        rc = lib.a3d_render_mesh(xyz_dev.data_ptr(), n, faces_dev.data_ptr(), m, C.byref(cam), C.byref(out),
+                                                 ws.data_ptr(), ws.numel(), stream)
+                    else:
+                        rc = lib.a3d_render_points(xyz_dev.data_ptr(), n, 0.02, C.byref(cam), C.byref(out), ws.data_ptr(),
+                                                   ws.numel(), stream)
+                    assert rc == 0, lib.a3d_last_error()
+
+                def shade():
+                    rc = lib.a3d_render_shade(ids.data_ptr(), up, vp, fcp, mm, col_dev.data_ptr(), n, bg.ctypes.data_as(fp),
+                                              rgb.data_ptr(), w, h, stream)
+                    assert rc == 0, lib.a3d_last_error()
+
+                def label_image():
+                    rc = lib.a3d_render_labels(ids.data_ptr(), up, vp, fcp, mm, labels_dev.data_ptr(), n, label_img.data_ptr(),
+                                               w, h, stream)
+                    assert rc == 0, lib.a3d_last_error()
+
+                def annotate(k):
+                    rc = lib.a3d_render_annotate(rgb.data_ptr(), label_img.data_ptr(), t.data_ptr(), table_dev.data_ptr(), k, 6.0,
+                                                 4.5, 0.1, black.ctypes.data_as(fp), white.ctypes.data_as(fp), rgb_out.data_ptr(),
+                                                 w, h, stream)
+                    assert rc == 0, lib.a3d_last_error()
+
+                tiny = torch.empty(lib.a3d_render_workspace_bytes(n_prim, w, h, 1), dtype=torch.uint8, device=dev)
+                render(tiny)
+                pairs = int(header.cpu().numpy()[2:4].view(np.int64)[0])
+                ws = torch.empty(lib.a3d_render_workspace_bytes(n_prim, w, h, max(pairs, 1)), dtype=torch.uint8, device=dev)
+                render(ws)
+                assert not int(header.cpu()[0]) & L.A3D_RENDER_OVERFLOW
+                shade(), label_image(), annotate(L.A3D_MAX_CLICKS)
+                ms = {"render": back_to_back(lambda: render(ws)), "shade": back_to_back(shade), "labels": back_to_back(label_image)}
+                for k in (0, 20, L.A3D_MAX_CLICKS):
+                    ms[f"annotate_{k}"] = back_to_back(lambda: annotate(k))
+                lab = label_img.cpu().numpy()
+                drawn = int((rgb_out != rgb).any(-1).sum())
+                key = f"{w}x{h} {cam_name} {kind}"
+                rows[key] = {"device_ms_per_call": ms, "pixels": w * h, "pixels_labelled": int((lab >= 1).sum()),
+                             "pixels_changed_at_256_markers": drawn,
+                             "annotate_256_over_render": ms[f"annotate_{L.A3D_MAX_CLICKS}"] / ms["render"],
+                             "marker_tests_at_256": L.A3D_MAX_CLICKS * w * h}
+                print(f"{key:28s} render {ms['render']:.4f}  shade {ms['shade']:.4f}  labels {ms['labels']:.4f}  annotate with 0 / 20 / "
+                      f"256 markers {ms['annotate_0']:.4f} / {ms['annotate_20']:.4f} / {ms['annotate_256']:.4f}   256 markers = "
+                      f"{rows[key]['annotate_256_over_render']:.2f} x the render; {drawn} of {w * h} pixels drawn over")
+    return {"vertices": n, "faces": m, "calls_back_to_back": calls, "views": rows}
+
+
 def mesh_pick_stage(ses, n_vertices, reps, warmup, calls):
     """Mesh pick and vertex pick on one tessellated height field of ~n_vertices vertices (see the module docstring)."""
     import ctypes as C
@@ -272,6 +385,7 @@ def main():
     ap.add_argument("--mesh-calls", type=int, default=200, help="calls between two events in the mesh-pick stage")
     ap.add_argument("--mesh-only", action="store_true", help="run the mesh-pick stage alone")
     ap.add_argument("--render-only", action="store_true", help="run the render stage alone")
+    ap.add_argument("--annotate-only", action="store_true", help="run the annotate stage alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("session_bench needs the GPU")
@@ -292,7 +406,7 @@ def main():
     original = col.copy()
     centre = xyz.mean(0)
     result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
-    for n_clicks in (() if a.mesh_only or a.render_only else (1, 5, 10, 20)):
+    for n_clicks in (() if a.mesh_only or a.render_only or a.annotate_only else (1, 5, 10, 20)):
         ses.reset()
         objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
         targets = [xyz[rng.choice(np.flatnonzero(lab == inst[o - 1]))] for o in objs]
@@ -394,10 +508,12 @@ def main():
         print(f"outside forward_mask (host ms): session {entry['session_outside_forward_mask_host_ms']:.3f}  "
               f"baseline {entry['baseline_outside_forward_mask_host_ms']:.3f}   forward_mask {sh['forward_mask']:.3f}")
         print(f"whole click, staged (host ms): session {entry['session_click_ms']:.3f}  baseline {entry['baseline_click_ms']:.3f}")
-    if not a.render_only:
+    if not (a.render_only or a.annotate_only):
         result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
-    if not a.mesh_only:
+    if not (a.mesh_only or a.annotate_only):
         result["render"] = render_stage(ses, n_full, a.reps, a.warmup)
+    if not (a.mesh_only or a.render_only):
+        result["annotate"] = annotate_stage(ses, n_full, a.mesh_calls)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
