@@ -129,6 +129,13 @@ class SessionPaintArgs(C.Structure):
                 ("err_dev", C.c_void_p)]
 
 
+class SessionEditArgs(C.Structure):
+    """a3d_session_edit_args: the relabel half (labels_ori, instances, new_labels), the remap half (labels, lut, err)."""
+    _fields_ = [("labels_ori_dev", C.c_void_p), ("instances_dev", C.c_void_p), ("new_labels_dev", C.c_void_p),
+                ("n_full", C.c_int64), ("labels_dev", C.c_void_p), ("n_labels", C.c_int64), ("err_dev", C.c_void_p),
+                ("n_objects", C.c_int32), ("reserved_", C.c_int32), ("lut", C.c_uint8 * 256)]
+
+
 class Camera(C.Structure):
     """a3d_camera: pixel (u, v)'s ray starts at o and runs along normalize(d00 + u du + v dv), evaluated in fp32."""
     _fields_ = [("o", C.c_float * 3), ("d00", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
@@ -339,6 +346,7 @@ SYMBOLS = {
     "a3d_pick_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_session_paint": (C.c_int, [C.POINTER(SessionPaintArgs), C.c_void_p]),
+    "a3d_session_edit": (C.c_int, [C.POINTER(SessionEditArgs), C.c_void_p]),
     "a3d_render_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "a3d_render_camera_bounds": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_double)]),
     "a3d_render_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(Camera), C.POINTER(RenderOut),

@@ -19,6 +19,8 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
     argmax + clicked rows               a3d_argmax_labels  (interactive_segmentation_user.py:78-81)
     pred[inverse_map], colours, cubes   a3d_session_paint  (:83-84,125-140; gui.py:276-298,327)
     IoU against the relabelled truth    a3d_iou_counts     (:86-88)
+    taking a click back, resuming       a3d_session_edit   (undo, redo, remove_click, restore_clicks / restore_file: the
+                                        GUI's "unselect point" is a TODO, gui.py:283-287; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -29,7 +31,14 @@ Departures from the reference, on purpose:
   * ``infer()`` without a click raises (the reference returns early at ``num_clicks == 0``): a caller that asks for a
     segmentation with nothing to segment has a bug worth hearing about;
   * ``click`` refuses what the model would refuse later (an object id that leaves a gap, too many queries);
-  * a click is kept even when no vertex lies inside its cube (the GUI drops it, gui.py:281-282).
+  * a click is kept even when no vertex lies inside its cube (the GUI drops it, gui.py:281-282);
+  * clicks can be taken back and a saved click file resumed (the reference does neither).  The session's state is a function
+    of ONE ordered click list (``click_state``, ``remove_from_clicks``, ``instance_rows``): entry i is the click with time
+    index i; removing one lowers the time indices behind it, and removing an object's only click renumbers the objects above
+    it, so ids stay 1..K and times 0..m-1.  The relabelled ground truth of a list gives a vertex the HIGHEST object whose
+    instance (the original label under the object's EARLIEST click in the list) it carries -- in a session grown by clicks
+    alone that is the reference's "last created wins" (gui.py:318-319).  After an edit the labels shown are the last
+    inference's with the ids renumbered, not an earlier inference restored.
 """
 from __future__ import annotations
 
@@ -83,6 +92,131 @@ def mask_file_name(num_clicks: int, num_obj: int, iou: str) -> str:
 
 def click_file_name(num_clicks: int, num_obj: int, iou: str) -> str:
     return "click_" + format_avg_clicks(num_clicks, num_obj) + "_" + iou + ".npy"
+
+
+# ---- the click list and what derives from it: pure Python / numpy, no library ----------------------------------------------
+# A click is a mapping with ``obj`` (0 = background), ``point`` (the picked point, three fp32 values), ``row_qv`` (voxel row),
+# ``row_full`` (full-resolution vertex row) and ``position`` (that vertex's coordinates, a list).  A click LIST is a sequence
+# of clicks in time order: entry i is the click with time index i.  The functions below never modify their arguments.
+def click_state(clicks):
+    """``(click_idx, click_time_idx, click_positions)`` of a click list, the dictionaries ``forward_mask`` and the click
+    files take: under ``str(k)`` object k's voxel rows in time order, their indices in the list, their vertex positions.
+    ``"0"`` is always there and comes first; an object's key appears where its first click does.  The object ids present
+    must be exactly 1..K (``ValueError`` otherwise): ``forward_mask`` serves no gap."""
+    idx, time_idx, positions = {"0": []}, {"0": []}, {"0": []}
+    for i, c in enumerate(clicks):
+        obj = int(c["obj"])
+        if not 0 <= obj <= 255:
+            raise ValueError(f"click {i}: object ids are 0 (background) .. 255, not {obj}")
+        key = str(obj)
+        if key not in idx:
+            idx[key], time_idx[key], positions[key] = [], [], []
+        idx[key].append(int(c["row_qv"]))
+        time_idx[key].append(i)
+        positions[key].append(list(c["position"]))
+    n_obj = len(idx) - 1
+    missing = [k for k in range(1, n_obj + 1) if str(k) not in idx]
+    if missing:
+        raise ValueError(f"the objects of a click list must be 1..K without a gap: {n_obj} objects, but no click on {missing}")
+    return idx, time_idx, positions
+
+
+def remove_from_clicks(clicks, index):
+    """``(new_clicks, lut)``: the click list without entry ``index`` (``IndexError`` outside ``[0, len)``; no wrap-around).
+    The entries behind it move up, which lowers their time index by one.  If the click was its object's only one the
+    object ceases to exist and every id above it drops by one.  ``lut`` uint8 [256] maps old to new ids: the identity when
+    no object disappeared; else removed id k -> 0 and j -> j - 1 for j > k."""
+    clicks = list(clicks)
+    if int(index) != index or not 0 <= index < len(clicks):
+        raise IndexError(f"click {index} of {len(clicks)}")
+    gone = clicks.pop(int(index))
+    lut = np.arange(256, dtype=np.uint8)
+    k = int(gone["obj"])
+    if k > 0 and all(int(c["obj"]) != k for c in clicks):
+        lut[k] = 0
+        lut[k + 1:] = np.arange(k, 255, dtype=np.uint8)
+        clicks = [dict(c, obj=int(lut[int(c["obj"])])) if int(c["obj"]) > k else c for c in clicks]
+    return clicks, lut
+
+
+def restore_lut(lut):
+    """The table that takes ``remove_from_clicks``' renumbering back: ids at or above the removed one move up again.  The
+    removed object's own labels became background and stay so -- a renumbering keeps no memory of them."""
+    lut = np.asarray(lut, dtype=np.uint8)
+    back = np.arange(256, dtype=np.uint8)
+    gone = np.flatnonzero(lut[1:] == 0)
+    if len(gone):
+        k = int(gone[0]) + 1
+        back[k:255] = np.arange(k + 1, 256, dtype=np.uint8)
+        back[255] = 0                                  # (no label: 255 objects before the removal left at most 254)
+    return back
+
+
+def instance_rows(clicks):
+    """The voxel rows that name the objects' instances: entry k - 1 is ``row_qv`` of the EARLIEST click of object k in the
+    list, k = 1..K.  The relabelled ground truth of the list: a vertex gets the HIGHEST k with
+    ``labels_qv_ori[rows[k - 1]] == labels_full_ori[vertex]``, else 0 (``a3d_session_edit``)."""
+    first = {}
+    for c in clicks:
+        first.setdefault(int(c["obj"]), int(c["row_qv"]))
+    n_obj = max(first, default=0)
+    if any(k not in first for k in range(1, n_obj + 1)):
+        raise ValueError("the objects of a click list must be 1..K without a gap")
+    return [first[k] for k in range(1, n_obj + 1)]
+
+
+def clicks_from_dicts(click_idx, click_time_idx, n_rows, max_clicks):
+    """``[(obj, voxel row), ...]`` in time order from the two dictionaries of a click file (``click_idx``, ``click_time``)
+    -- what ``restore_clicks`` rebuilds its list from.  ``ValueError`` unless: both have the keys ``"0".."K"`` exactly, an
+    object k >= 1 has at least one click, rows and times pair up, the times are a permutation of 0..m-1, every row lies in
+    ``[0, n_rows)`` and m <= ``max_clicks``."""
+    if not isinstance(click_idx, dict) or not isinstance(click_time_idx, dict):
+        raise ValueError("click_idx and click_time_idx must be dictionaries")
+    keys = [str(k) for k in range(len(click_idx))]
+    if sorted(map(str, click_idx)) != sorted(keys) or sorted(map(str, click_time_idx)) != sorted(keys) or not keys:
+        raise ValueError(f'click_idx and click_time_idx must both have the keys "0" .. "K" exactly, not {list(click_idx)} '
+                         f"and {list(click_time_idx)}")
+    if any(not isinstance(k, str) for k in list(click_idx) + list(click_time_idx)):
+        raise ValueError("the keys of click_idx and click_time_idx are strings")
+    by_time = {}
+    for key in keys:
+        rows, times = list(click_idx[key]), list(click_time_idx[key])
+        if len(rows) != len(times):
+            raise ValueError(f"object {key}: {len(rows)} rows but {len(times)} time indices")
+        if key != "0" and not rows:
+            raise ValueError(f"object {key} has no click")
+        for r, t in zip(rows, times):
+            if int(r) != r or int(t) != t:
+                raise ValueError(f"object {key}: rows and time indices must be integers")
+            if not 0 <= r < n_rows:
+                raise ValueError(f"object {key}: row {r} outside the {n_rows} voxels")
+            if t in by_time:
+                raise ValueError(f"time index {t} appears twice")
+            by_time[int(t)] = (int(key), int(r))
+    m = len(by_time)
+    if sorted(by_time) != list(range(m)):
+        raise ValueError(f"the time indices must be a permutation of 0 .. {m - 1}")
+    if m > max_clicks:
+        raise ValueError(f"{m} clicks, but at most {max_clicks} fit beside the background queries")
+    return [by_time[t] for t in range(m)]
+
+
+def marker_hit(markers, u, v, t_pixel, marker_px, depth_slack):
+    """The row of ``markers`` (fp32 [k, 6], ``view.marker_table``) that ``a3d_render_annotate`` draws on top at pixel
+    ``(u, v)`` (column, row) whose ``t`` image holds ``t_pixel``, or ``None``: the LAST row with ``d2 <= marker_px^2`` and
+    ``t_k - t_pixel <= depth_slack``, ``d2 = dx dx + dy dy`` from ``dx = u - x_k``, ``dy = v - y_k`` -- each a single fp32
+    operation, as the kernel does them; a row with a NaN covers nothing."""
+    f32 = np.float32
+    m = np.asarray(markers, dtype=f32).reshape(-1, 6)
+    if not len(m):
+        return None
+    with np.errstate(all="ignore"):
+        dx, dy = f32(u) - m[:, 0], f32(v) - m[:, 1]
+        d2 = dx * dx + dy * dy
+        cover = (d2 <= f32(marker_px) * f32(marker_px)) & (m[:, 2] - f32(t_pixel) <= f32(depth_slack))
+    cover &= ~np.isnan(m).any(1)
+    hits = np.flatnonzero(cover)
+    return int(hits[-1]) if len(hits) else None
 
 
 class SessionResult:
@@ -242,6 +376,7 @@ class InteractiveSession:
         self._cubes = self._cubes_host.numpy()
         self._cubes_dev = torch.zeros((L.A3D_MAX_CLICKS, 6), dtype=torch.float32, device=self.device)
         self._mask_host = None                      # pinned staging of a scene's full-resolution labels (scenes with an out_dir)
+        self._edit_err = torch.zeros(1, dtype=torch.int32, device=self.device)   # a3d_session_edit's flag
         self._drop_scene()
 
     # ------------------------------------------------------------------ scene
@@ -262,6 +397,8 @@ class InteractiveSession:
     def _reset_clicks(self):
         self._colors_last = None                    # colours of the last infer / preview: what render() shows by default
         self._labels_last = None                    # its full-resolution labels: what label_image() shows by default
+        self._clicks = []                           # THE state: the ordered click list (entry i = time index i)
+        self._redo = []                             # (click list before an undo, the table that renumbers the labels back)
         self.click_idx = {"0": []}
         self.click_time_idx = {"0": []}
         self.click_positions = {"0": []}
@@ -569,7 +706,8 @@ class InteractiveSession:
         """One click at ``point`` for object ``obj`` (0 = background, k >= 1 = object k), booked as gui.py:290-331 does:
         the voxel row nearest to the point joins ``click_idx``, the running click count ``click_time_idx``, the nearest
         full-resolution vertex's coordinates ``click_positions``; the first click of a new object relabels the ground
-        truth (every vertex of the instance under the clicked voxel becomes ``obj``).  Returns (voxel row, vertex)."""
+        truth (every vertex of the instance under the clicked voxel becomes ``obj``).  The click joins the session's click
+        list, from which all of this derives (``click_state``), and empties the redo stack.  Returns (voxel row, vertex)."""
         self._need_scene()
         obj = int(obj)
         key = str(obj)
@@ -583,14 +721,13 @@ class InteractiveSession:
                              f"> {L.A3D_MAX_QUERIES}")
         q = _f3(point, "point")
         row_qv, row_full = self.nearest(q)
-        position = self._coords_host[row_full].tolist()
-        if key not in self.click_idx:
-            self.click_idx[key], self.click_time_idx[key], self.click_positions[key] = [], [], []
-            if self.new_labels is not None:
-                self.new_labels[self.labels_full_ori == self.labels_qv_ori[row_qv]] = obj
-        self.click_idx[key].append(row_qv)
-        self.click_time_idx[key].append(self.num_clicks)
-        self.click_positions[key].append(position)
+        new_object = key not in self.click_idx
+        self._clicks.append({"obj": obj, "point": tuple(float(x) for x in q), "row_qv": row_qv, "row_full": row_full,
+                             "position": self._coords_host[row_full].tolist()})
+        self._redo.clear()
+        self.click_idx, self.click_time_idx, self.click_positions = click_state(self._clicks)
+        if new_object and self.new_labels is not None:
+            self._launch_edit(None)
         colour = self.background_click_color if obj == 0 else self._palette_entry(obj)
         k = self.num_clicks
         self._cubes[k] = (q[0], q[1], q[2], colour[0], colour[1], colour[2])
@@ -605,6 +742,152 @@ class InteractiveSession:
         if point is None:
             return None
         return self.click(point, obj)
+
+    # ------------------------------------------------------------------ editing the click list
+    def clicks(self):
+        """The click list: one dict per click in time order -- ``index`` (its time index), ``obj``, ``point`` (the picked
+        point), ``row_qv``, ``row_full``, ``position`` (the vertex's coordinates).  Copies: changing them changes nothing."""
+        return [self._click_dict(i) for i in range(len(self._clicks))]
+
+    def _click_dict(self, i):
+        c = self._clicks[i]
+        return {"index": i, "obj": c["obj"], "point": list(c["point"]), "row_qv": c["row_qv"], "row_full": c["row_full"],
+                "position": list(c["position"])}
+
+    def _launch_edit(self, lut):
+        """ONE ``a3d_session_edit`` call: the relabelled ground truth of the click list (scenes that have one) and, with a
+        ``lut``, the renumbering of the last inference's voxel labels."""
+        relabel = self.new_labels is not None
+        if not relabel and lut is None:
+            return
+        instances = None
+        if relabel:
+            rows = instance_rows(self._clicks)
+            if rows:                                    # gathered on the device: the ids never visit the host
+                instances = self.labels_qv_ori[torch.tensor(rows, dtype=torch.int64, device=self.device)]
+        V.session_edit(labels_ori=self.labels_full_ori if relabel else None, instances=instances,
+                       new_labels=self.new_labels if relabel else None, labels=None if lut is None else self._labels_qv,
+                       lut=lut, err=None if lut is None else self._edit_err)
+
+    def _set_clicks(self, clicks, lut):
+        """Makes ``clicks`` the session's click list and rebuilds what derives from it: the dictionaries, the cube table
+        (pinned and on the device, colours from the new ids), the relabelled ground truth, the last inference's labels
+        through ``lut`` (``None``: left alone) and, by a ``preview()``, what the view shows."""
+        state = click_state(clicks)                     # (refuses a list with a gap before anything changes)
+        torch.cuda.current_stream(self.device).synchronize()   # no copy from a pinned cube row is in flight past this point
+        before, n = self.num_clicks, len(clicks)
+        self._clicks = list(clicks)
+        self.click_idx, self.click_time_idx, self.click_positions = state
+        self.num_clicks = n
+        for k, c in enumerate(self._clicks):
+            colour = self.background_click_color if c["obj"] == 0 else self._palette_entry(c["obj"])
+            self._cubes[k] = (*c["point"], colour[0], colour[1], colour[2])
+        self._cubes[n:max(n, before)] = 0.0
+        if max(n, before):
+            self._cubes_dev[:max(n, before)].copy_(self._cubes_host[:max(n, before)], non_blocking=True)
+        self._launch_edit(lut)
+        self.preview()
+        if lut is not None and int(self._edit_err.cpu()[0]):
+            raise RuntimeError("a3d_session_edit: a voxel label outside 0 .. 255")
+
+    def _remove(self, index):
+        before = self._clicks
+        n_obj = len(self.click_idx) - 1
+        clicks, lut = remove_from_clicks(before, index)
+        removed = self._click_dict(index)
+        self._set_clicks(clicks, lut)
+        removed["id_map"] = {k: int(lut[k]) for k in range(1, n_obj + 1)}
+        return removed, before, lut
+
+    def remove_click(self, index):
+        """Takes click ``index`` (its time index; ``IndexError`` outside ``[0, num_clicks)``) out of the annotation
+        (``remove_from_clicks``): later clicks move up by one time index, and if it was its object's only click the object
+        is gone and the ids above it drop by one.  The dictionaries, ``click_positions``, the cubes and the relabelled
+        ground truth follow the new list; the labels of the last inference are renumbered (a removed object's voxels show
+        as background until the next ``infer()``), and ``render`` / ``label_image`` / ``annotate`` show that at once.
+        Synchronises the stream once.  Empties the redo stack.  Returns the removed click's dict (``clicks()``) with
+        ``id_map``: {old object id: new id, 0 = gone}."""
+        self._need_scene()
+        removed = self._remove(index)[0]
+        self._redo.clear()
+        return removed
+
+    def undo(self):
+        """``remove_click`` of the last click, except that the list as it was goes onto the redo stack.  Returns the removed
+        click, or ``None`` -- with nothing changed -- when there is no click."""
+        self._need_scene()
+        if not self._clicks:
+            return None
+        removed, before, lut = self._remove(len(self._clicks) - 1)
+        self._redo.append((before, restore_lut(lut)))
+        return removed
+
+    def redo(self):
+        """Takes the last ``undo()`` back: the click list is again what it was before it; an object that had disappeared
+        comes back under its id and the ids at or above it move back up.  What does NOT come back is that object's labels:
+        the undo turned its voxels into background, and they stay background until the next ``infer()`` (labels after an
+        edit are the last inference renumbered, not an earlier one restored).  Returns the restored click, or ``None`` when
+        there is nothing to redo (``click``, ``remove_click``, ``restore_*``, ``reset`` and ``load_scene`` empty the stack)."""
+        self._need_scene()
+        if not self._redo:
+            return None
+        clicks, lut = self._redo.pop()
+        self._set_clicks(clicks, lut)
+        return self._click_dict(len(clicks) - 1)
+
+    def restore_clicks(self, click_idx, click_time_idx):
+        """Resumes an annotation from its click dictionaries (voxel rows and time indices per object, as ``infer()`` and the
+        reference tool save them): ``reset()``, then the click list rebuilt in time order.  A file keeps no picked points,
+        so a click's point is its voxel's coordinates ``raw_coords_qv[row]``, and its vertex (``a3d_nearest_rows``, 64
+        queries per launch) the one nearest to that -- ``click_idx``, ``click_time_idx`` and the relabelled ground truth are
+        the saving session's, cubes, markers and ``click_positions`` lie at most a voxel off.  ``ValueError``, with the
+        session untouched, for what ``clicks_from_dicts`` refuses: keys other than "0".."K", times that are no permutation
+        of 0..m-1, rows outside the voxels, more clicks than ``click()`` accepts."""
+        self._need_scene()
+        pairs = clicks_from_dicts(click_idx, click_time_idx, self.raw_coords_qv.shape[0],
+                                  L.A3D_MAX_QUERIES - self.model.num_bg_queries)
+        self.reset()
+        if not pairs:
+            return self
+        rows = torch.tensor([r for _, r in pairs], dtype=torch.int64, device=self.device)
+        points = self.raw_coords_qv[rows].cpu().numpy()
+        rows_full = []
+        for s in range(0, len(pairs), L.A3D_NEAREST_MAX_QUERIES):
+            chunk = points[s:s + L.A3D_NEAREST_MAX_QUERIES]
+            rows_full += V.nearest_rows([self.coords_full], chunk, workspace=self._ws)[0].cpu().tolist()
+        self._set_clicks([{"obj": o, "point": tuple(float(x) for x in p), "row_qv": r, "row_full": rf,
+                           "position": self._coords_host[rf].tolist()} for (o, r), p, rf in zip(pairs, points, rows_full)], None)
+        return self
+
+    def restore_file(self, path):
+        """``restore_clicks`` from a ``clicks/click_*.npy`` as ``infer()`` and the reference tool write it: a pickled dict
+        with ``click_idx`` and ``click_time`` (a pickle: load files you trust)."""
+        saved = np.load(path, allow_pickle=True)
+        saved = saved.item() if isinstance(saved, np.ndarray) and saved.shape == () else saved
+        if not isinstance(saved, dict) or "click_idx" not in saved or "click_time" not in saved:
+            raise ValueError(f"{path}: a dict with click_idx and click_time expected")
+        return self.restore_clicks(saved["click_idx"], saved["click_time"])
+
+    def click_at(self, result, u, v, marker_px=6.0, depth_slack=None):
+        """The time index of the click whose marker ``annotate(result, marker_px=, depth_slack=)`` draws on top at pixel
+        ``(u, v)`` (column, row), or ``None`` -- for a viewer that deletes the click under the pointer
+        (``remove_click(click_at(...))``).  ``annotate``'s cover test (``marker_hit``) on the host, from ``view.marker_table``
+        and one pixel of ``result.t``: one small device-to-host copy."""
+        self._need_scene()
+        u, v = int(u), int(v)
+        h, w = result.t.shape
+        if not (0 <= u < w and 0 <= v < h):
+            raise ValueError(f"pixel ({u}, {v}) outside the {w} x {h} image")
+        marker_px = float(marker_px)
+        slack = self.cube_size if depth_slack is None else float(depth_slack)
+        if not (np.isfinite(marker_px) and marker_px >= 0.0 and np.isfinite(slack) and slack >= 0.0):
+            raise ValueError("marker_px and depth_slack must be finite and >= 0")
+        if not self.num_clicks:
+            return None
+        cubes = self._cubes[:self.num_clicks]
+        rows, kept = V.marker_table(result.camera, cubes[:, :3], cubes[:, 3:], return_kept=True)
+        hit = marker_hit(rows, u, v, result.t[v, u].cpu().numpy(), marker_px, slack)
+        return None if hit is None else int(kept[hit])
 
     def _palette_entry(self, obj):
         n = self.palette.shape[0]

@@ -272,13 +272,14 @@ def render_annotate(rgb, label_image, t, markers, radius, inner_radius, depth_sl
     return out
 
 
-def marker_table(camera, points, colors):
+def marker_table(camera, points, colors, return_kept=False):
     """The rows ``(x, y, t, r, g, b)`` of ``a3d_render_annotate``'s markers for world ``points`` [k, 3] seen by the
     ``lib.Camera`` ``camera``, with ``colors`` [k, 3]: fp32 [k', 6], in the order given.  From the camera's fp32 fields,
     widened to float64: ``(a, b, c) = solve([du dv d00], p - o)``, the position ``x = a / c``, ``y = b / c`` in pixels (the
     centre of pixel (u, v) is the position (u, v)) and ``t = |p - o|``, the parameter of the pixel's unit ray at the point,
     as the render's ``t`` image holds it.  Rows with ``c <= 0`` (behind the camera) or a value that is not finite are left
-    out; each value is rounded to fp32 once.  Pure numpy."""
+    out; each value is rounded to fp32 once.  ``return_kept=True`` returns ``(rows, kept)`` with ``kept`` int64 [k'] the
+    indices into ``points`` of the rows that stayed (``session.marker_hit`` names a click by them).  Pure numpy."""
     o, d00, du, dv = (np.array(f[:], np.float64) for f in (camera.o, camera.d00, camera.du, camera.dv))
     p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     col = np.asarray(colors, dtype=np.float64).reshape(-1, 3)
@@ -291,7 +292,8 @@ def marker_table(camera, points, colors):
     with np.errstate(all="ignore"):
         rows = np.concatenate([abc[:, :2] / abc[:, 2:], np.linalg.norm(p - o, axis=1)[:, None], col], 1).astype(np.float32)
     keep = (abc[:, 2] > 0) & np.isfinite(rows).all(1)
-    return np.ascontiguousarray(rows[keep])
+    rows = np.ascontiguousarray(rows[keep])
+    return (rows, np.flatnonzero(keep)) if return_kept else rows
 
 
 # ---- paint -------------------------------------------------------------------------------------------------------------------------
@@ -313,3 +315,38 @@ def session_paint(labels_qv, inverse_map, xyz, colors, palette, cubes, cube_size
     a.label_full_dev, a.colors_out_dev, a.err_dev = labels_out.data_ptr(), colors_out.data_ptr(), err.data_ptr()
     L.check(L.load().a3d_session_paint(C.byref(a), _stream(dev)), "a3d_session_paint")
     return labels_out, colors_out, err
+
+
+# ---- edits of the click list -------------------------------------------------------------------------------------------------
+def session_edit(labels_ori=None, instances=None, new_labels=None, labels=None, lut=None, err=None):
+    """``a3d_session_edit``, either half or both.  Relabel (``labels_ori`` int32 [n] given): ``new_labels`` int32 [n] (``out``
+    style: the caller's or a new one) = the largest k with ``instances[k - 1] == labels_ori`` (``instances`` int32 [K] on the
+    device, K <= 255; ``None``: no object), else 0.  Remap (``labels`` int32 [m] given): ``labels = lut[labels]`` in place,
+    ``lut`` 256 host values in 0..255; ``err`` int32 [1] != 0 (on the device): a label outside 0..255, written as 0.
+    Returns ``(new_labels, labels, err)``, ``None`` for what an absent half would have given."""
+    if labels_ori is None and labels is None:
+        raise ValueError("session_edit: neither labels_ori (relabel) nor labels (remap) given")
+    dev = _device("labels_ori" if labels_ori is not None else "labels", labels_ori if labels_ori is not None else labels)
+    a = L.SessionEditArgs()
+    if labels_ori is not None:
+        a.labels_ori_dev, a.n_full = _ptr("labels_ori", labels_ori, I32, (None,), dev), labels_ori.shape[0]
+        a.instances_dev = _ptr("instances", instances, I32, (None,), dev, optional=True)
+        a.n_objects = 0 if instances is None else instances.shape[0]
+        if a.n_objects > 255:
+            raise ValueError("instances: at most 255 objects")
+        new_labels = _out("new_labels", new_labels, I32, (a.n_full,), dev)
+        a.new_labels_dev = new_labels.data_ptr() if a.n_full else None
+    elif instances is not None or new_labels is not None:
+        raise ValueError("instances and new_labels belong to the relabel half: labels_ori is missing")
+    if labels is not None:
+        a.labels_dev, a.n_labels = _ptr("labels", labels, I32, (None,), dev), labels.shape[0]
+        table = np.asarray(lut)
+        if table.shape != (256,) or table.dtype.kind not in "iu" or table.min() < 0 or table.max() > 255:
+            raise ValueError("lut must be 256 integers in 0 .. 255")
+        C.memmove(a.lut, np.ascontiguousarray(table, dtype=np.uint8).ctypes.data, 256)
+        err = _out("err", err, I32, (1,), dev)
+        a.err_dev = err.data_ptr()
+    elif lut is not None or err is not None:
+        raise ValueError("lut and err belong to the remap half: labels is missing")
+    L.check(L.load().a3d_session_edit(C.byref(a), _stream(dev)), "a3d_session_edit")
+    return new_labels, labels, err

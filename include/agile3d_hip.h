@@ -833,6 +833,34 @@ typedef struct a3d_session_paint_args {
 } a3d_session_paint_args;
 int    a3d_session_paint(const a3d_session_paint_args* args, void* stream);
 
+/* What an EDIT of the session's click list (undo, redo, remove, restore from a file) rebuilds on the device
+ * (csrc/session_edit.hip).  The rule is this library's: the reference cannot take a click back (gui.py:283-287 is a TODO).
+ * Two independent halves in one launch; a half whose count is 0 is absent and its pointers are not looked at.
+ *   RELABEL (n_full > 0): the relabelled ground truth of a click list.  instances_dev[k - 1] is the instance id object k
+ *     stands for (the session: the original label of the voxel under the EARLIEST click of k); 0 <= n_objects <= 255.
+ *         new_labels[i] = the largest k in 1..n_objects with instances[k - 1] == labels_ori[i], else 0
+ *     Ids compare as plain int32: 0, negative and large ids are values like any other.  Where two objects stand for the
+ *     same instance the HIGHER id wins -- in a list grown by clicks alone objects are created in id order, so this is the
+ *     reference's "the object created last wins" (gui.py:318-319).  new_labels_dev == labels_ori_dev is allowed.
+ *   REMAP (n_labels > 0): labels[i] = lut[labels[i]], in place, lut the old -> new object ids after a removal (identity, or
+ *     removed id -> 0 and every id above it one down) or their inverse.  A value outside 0..255 becomes 0 and sets bit 0 of
+ *     *err_dev (int32, cleared by the call whenever it is given).  labels_dev must not overlap the relabel's arrays.
+ * Streaming passes over 4-byte rows, no workspace, no atomic but the flag's: the result depends on the arguments alone.
+ * A count < 0, n_objects outside 0..255, or a count > 0 with one of its pointers NULL: A3D_ERR_INVALID, nothing launched. */
+typedef struct a3d_session_edit_args {
+  const int32_t* labels_ori_dev;    /* [n_full] the scene's instance ids */
+  const int32_t* instances_dev;     /* [n_objects] on the DEVICE (gathered there, no host round trip); NULL if n_objects == 0 */
+  int32_t*       new_labels_dev;    /* out [n_full] */
+  int64_t        n_full;
+  int32_t*       labels_dev;        /* in/out [n_labels] */
+  int64_t        n_labels;
+  int32_t*       err_dev;           /* needed when n_labels > 0 */
+  int32_t        n_objects;
+  int32_t        reserved_;
+  uint8_t        lut[256];
+} a3d_session_edit_args;
+int    a3d_session_edit(const a3d_session_edit_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
  * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a

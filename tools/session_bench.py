@@ -5,7 +5,7 @@ overwrite, ``pred[inverse_map]``, ``.cpu().numpy()``, the per-object colour loop
 alternating, on one synthetic scene (~80 k voxels, ~250 k full-resolution vertices) at 1, 5, 10 and 20 clicks.
 
     python tools/session_bench.py [--voxels 80000] [--reps 60] [--out profiles/session_bench.json]
-                                  [--mesh-only | --render-only | --annotate-only]
+                                  [--mesh-only | --render-only | --annotate-only | --edit-only]
 
 Every stage is timed twice: with device events around it (what the GPU spent) and with a host clock around a stage that
 ends in a synchronisation (what the caller waits).  Medians over ``--reps`` clicks after a warm-up of 10.  The baseline has
@@ -34,7 +34,12 @@ The ANNOTATE stage times the passes that draw the state of the annotation over t
 the same images.  One launch of these sits at the floor of what a staged call measures, so every figure here is
 ``--mesh-calls`` calls back to back between two events, median of 5 such windows, after a warm-up window.  The vertices'
 labels are stripes of five objects with background between them; the markers are vertices of the field projected by
-``view.marker_table``.  The figure to read: annotate at 256 markers against the render of the same view."""
+``view.marker_table``.  The figure to read: annotate at 256 markers against the render of the same view.
+
+The EDIT stage (``--edit-only``, a run of its own) times ``a3d_session_edit`` on the click scene, back to back like the
+annotate stage: the relabel with 5, 20 and 255 objects, over the scene's own labels and over labels no object claims (the
+whole table walked for every vertex), the remap of the voxel labels, and both in one call; then whole ``undo()`` /
+``redo()`` calls at 20 clicks on the host clock, synchronised.  The figure to read: the relabel against 8 bytes per vertex."""
 import argparse
 import json
 import os
@@ -46,6 +51,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from agile3d_amd import build_model, clicks as K, default_args, randomize_bn_stats  # noqa: E402
+from agile3d_amd import view as V  # noqa: E402
 from agile3d_amd.session import InteractiveSession  # noqa: E402
 from agile3d_amd.synthetic import make_scene  # noqa: E402
 
@@ -312,6 +318,82 @@ def annotate_stage(ses, n_vertices, calls):
     return {"vertices": n, "faces": m, "calls_back_to_back": calls, "views": rows}
 
 
+def edit_stage(ses, xyz, lab, inst, calls, reps):
+    """``a3d_session_edit`` on the bench scene -- the relabel with 5, 20 and 255 objects over the scene's own instance ids
+    (ids the scene does not have fill the table up) and over labels no object claims (every row walks the whole table), the
+    remap of the voxel labels, both in one call -- and a whole ``undo()`` / ``redo()`` at 20 clicks on the host clock."""
+    import ctypes as C
+    from agile3d_amd import lib as L
+    lib, dev = ses.lib, ses.device
+    rng = np.random.default_rng(3)
+    n_full, n_qv = ses.labels_full_ori.shape[0], ses.raw_coords_qv.shape[0]
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    new_labels = torch.empty(n_full, dtype=torch.int32, device=dev)
+    unclaimed = torch.full((n_full,), -5, dtype=torch.int32, device=dev)
+    labels_qv = torch.from_numpy(rng.integers(0, 256, n_qv).astype(np.int32)).to(dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ids = [int(i) for i in np.unique(lab) if i > 0]
+    ids += [10_000 + k for k in range(255 - len(ids))]
+
+    def back_to_back(fn):
+        per_call = []
+        for window in range(6):                     # (the first window warms up)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            per_call.append(a.elapsed_time(b) / calls)
+        return float(np.median(per_call[1:]))
+
+    def launcher(relabel, remap, instances, ori):
+        a = L.SessionEditArgs()
+        if relabel:
+            a.labels_ori_dev, a.instances_dev, a.new_labels_dev = ori.data_ptr(), instances.data_ptr(), new_labels.data_ptr()
+            a.n_full, a.n_objects = n_full, instances.shape[0]
+        if remap:
+            a.labels_dev, a.n_labels, a.err_dev = labels_qv.data_ptr(), n_qv, err.data_ptr()
+            C.memmove(a.lut, np.arange(256, dtype=np.uint8).ctypes.data, 256)       # the identity: the labels survive the repeats
+
+        def fn():
+            rc = lib.a3d_session_edit(C.byref(a), stream)
+            assert rc == 0, lib.a3d_last_error()
+        return fn
+
+    print(f"\n== edit: {n_full} vertices, {n_qv} voxels; device ms per call, {calls} calls back to back, median of 5 windows ==")
+    out = {"vertices": int(n_full), "voxels": int(n_qv), "calls_back_to_back": calls, "device_ms_per_call": {}}
+    never = torch.empty(0)
+    out["device_ms_per_call"]["remap"] = back_to_back(launcher(False, True, never, never))
+    for k in (5, 20, 255):
+        instances = torch.tensor(ids[:k], dtype=torch.int32, device=dev)
+        ms = {"relabel": back_to_back(launcher(True, False, instances, ses.labels_full_ori)),
+              "relabel_unclaimed": back_to_back(launcher(True, False, instances, unclaimed)),
+              "relabel_and_remap": back_to_back(launcher(True, True, instances, ses.labels_full_ori))}
+        out["device_ms_per_call"][f"objects_{k}"] = ms
+        print(f"{k:3d} objects   relabel {ms['relabel']:.4f}  relabel, no label claimed {ms['relabel_unclaimed']:.4f}  "
+              f"relabel + remap {ms['relabel_and_remap']:.4f}")
+    print(f"remap alone   {out['device_ms_per_call']['remap']:.4f}")
+    # a whole edit: 20 clicks on 5 objects, an inference, then undo() / redo() pairs on the host clock
+    ses.reset()
+    for k in range(20):
+        ses.click(xyz[rng.choice(np.flatnonzero(lab == inst[k % 5]))], 1 + k % 5)
+    ses.infer()
+    host = {"undo": [], "redo": []}
+    for _ in range(reps):
+        for name, call in (("undo", ses.undo), ("redo", ses.redo)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            assert call() is not None
+            torch.cuda.synchronize()
+            host[name].append(1e3 * (time.perf_counter() - t0))
+    out["host_ms_at_20_clicks"] = {k: float(np.median(v[reps // 4:])) for k, v in host.items()}
+    print("a whole edit at 20 clicks (host ms, synchronised): undo {undo:.3f}  redo {redo:.3f}".format(**out["host_ms_at_20_clicks"]))
+    ses.reset()
+    return out
+
+
 def mesh_pick_stage(ses, n_vertices, reps, warmup, calls):
     """Mesh pick and vertex pick on one tessellated height field of ~n_vertices vertices (see the module docstring)."""
     import ctypes as C
@@ -386,6 +468,7 @@ def main():
     ap.add_argument("--mesh-only", action="store_true", help="run the mesh-pick stage alone")
     ap.add_argument("--render-only", action="store_true", help="run the render stage alone")
     ap.add_argument("--annotate-only", action="store_true", help="run the annotate stage alone")
+    ap.add_argument("--edit-only", action="store_true", help="run the edit stage (a3d_session_edit, undo / redo) alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("session_bench needs the GPU")
@@ -406,7 +489,7 @@ def main():
     original = col.copy()
     centre = xyz.mean(0)
     result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
-    for n_clicks in (() if a.mesh_only or a.render_only or a.annotate_only else (1, 5, 10, 20)):
+    for n_clicks in (() if a.mesh_only or a.render_only or a.annotate_only or a.edit_only else (1, 5, 10, 20)):
         ses.reset()
         objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
         targets = [xyz[rng.choice(np.flatnonzero(lab == inst[o - 1]))] for o in objs]
@@ -442,7 +525,9 @@ def main():
             key = str(last_obj)
             if key not in ses.click_idx:
                 ses.click_idx[key], ses.click_time_idx[key], ses.click_positions[key] = [], [], []
-                ses.new_labels[ses.labels_full_ori == ses.labels_qv_ori[rows[0]]] = last_obj
+                first = [ses.click_idx[str(k)][0] for k in range(1, last_obj)] + [rows[0]]      # (click(): the list's relabel)
+                V.session_edit(labels_ori=ses.labels_full_ori, new_labels=ses.new_labels,
+                               instances=ses.labels_qv_ori[torch.tensor(first, dtype=torch.int64, device=ses.device)])
             ses.click_idx[key].append(rows[0])
             ses.click_time_idx[key].append(ses.num_clicks)
             ses.click_positions[key].append(ses._coords_host[rows[1]].tolist())
@@ -508,11 +593,13 @@ def main():
         print(f"outside forward_mask (host ms): session {entry['session_outside_forward_mask_host_ms']:.3f}  "
               f"baseline {entry['baseline_outside_forward_mask_host_ms']:.3f}   forward_mask {sh['forward_mask']:.3f}")
         print(f"whole click, staged (host ms): session {entry['session_click_ms']:.3f}  baseline {entry['baseline_click_ms']:.3f}")
-    if not (a.render_only or a.annotate_only):
+    if a.edit_only:
+        result["edit"] = edit_stage(ses, xyz, lab, inst, a.mesh_calls, a.reps)
+    if not (a.render_only or a.annotate_only or a.edit_only):
         result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
-    if not (a.mesh_only or a.annotate_only):
+    if not (a.mesh_only or a.annotate_only or a.edit_only):
         result["render"] = render_stage(ses, n_full, a.reps, a.warmup)
-    if not (a.mesh_only or a.render_only):
+    if not (a.mesh_only or a.render_only or a.edit_only):
         result["annotate"] = annotate_stage(ses, n_full, a.mesh_calls)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
