@@ -29,6 +29,13 @@
 // it, never both outside: no ray passes between them.  A function that comes out exactly 0 is recomputed in double (exact
 // products, one rounding), as in the paper.  Skipped, never an error: det == 0, a repeated index, a NaN, an index outside
 // [0, n) (which also sets bit 0 of the result's flags).
+//
+// THE SECTION RULE (ours; the header states it in full).  Planes (n, c) keep the side n . p >= c; a mesh may also drop the
+// faces that turn their back (or their front) to the ray.  On a mesh a section cuts the RAY, not the faces: the planes
+// become one interval [t_lo, t_hi] per ray (ses_section_ray) and a crossing counts iff its t lies in it, so faces that share
+// an edge still classify every ray consistently.  On a cloud a vertex shows iff it lies on the kept side of every plane.  The
+// section is a template parameter of the kernels that test primitives: NoSection is the code the entry points without a
+// section have always run, and the binning of the rendered view does not know about sections at all.
 #include "common.h"
 
 namespace a3d {
@@ -77,6 +84,62 @@ __device__ __forceinline__ PickKey pick_wave_min(PickKey k) {
     k = pick_min(k, other);
   }
   return k;
+}
+
+// ---- the section --------------------------------------------------------------------------------------------------------------
+struct NoSection {};                          // no section: every overload below folds to nothing
+struct RayCut {                               // a section as ONE ray of a mesh sees it
+  float t_lo, t_hi;                           // crossings count for t_lo <= t <= t_hi ...
+  int empty;                                  // ... unless the ray runs parallel to a plane on its cut side
+  int cull;
+};
+// THE interval of a ray (o, d) under the planes of s: on the host for a3d_pick_mesh_section's one ray and for
+// a3d_section_ray, per pixel in the rendered view.  Every operation rounded on its own, in the order written; the divisions
+// are correctly rounded on both sides: the same bits.  The maximum and the minimum are written as a comparison, not as fmaxf /
+// fminf: a NaN quotient leaves the bound as it is, as with those, and where both are zeros of either sign the bound stays
+// -- fmaxf(+0, -0) may return either zero, and host, device and numpy need not agree on which.
+__host__ __device__ inline void ses_section_ray(const a3d_section& s, const float* o, const float* d, RayCut& c) {
+#pragma clang fp contract(off)
+  c.t_lo = 0.f, c.t_hi = __builtin_inff(), c.empty = 0, c.cull = s.cull;
+  for (int k = 0; k < s.n_planes; ++k) {
+    const float nx = s.planes[k][0], ny = s.planes[k][1], nz = s.planes[k][2], cc = s.planes[k][3];
+    const float den = (nx * d[0] + ny * d[1]) + nz * d[2];
+    const float so = (nx * o[0] + ny * o[1]) + nz * o[2];
+    if (den > 0.f) {
+      const float q = (cc - so) / den;
+      c.t_lo = q > c.t_lo ? q : c.t_lo;
+    } else if (den < 0.f) {
+      const float q = (cc - so) / den;
+      c.t_hi = q < c.t_hi ? q : c.t_hi;
+    } else if (!(so >= cc)) {                 // (a NaN den lands here as well)
+      c.empty = 1;
+    }
+  }
+}
+__host__ __device__ inline NoSection ses_ray_cut(const NoSection&, const float*, const float*) { return NoSection{}; }
+__host__ __device__ inline RayCut ses_ray_cut(const a3d_section& s, const float* o, const float* d) {
+  RayCut c;
+  ses_section_ray(s, o, d, c);
+  return c;
+}
+// Whether a crossing the face test accepted counts: t inside the interval, both ends inclusive, and the facing.  The shear
+// keeps the winding, so det = (U + V) + W > 0 iff the vertices appear counter-clockwise from the origin: a FRONT face
+// (g . d < 0 for g = (b - a) x (c - a)); det < 0: a back face; det == 0 never gets here.
+__device__ __forceinline__ bool ses_counts(const NoSection&, float, float) { return true; }
+__device__ __forceinline__ bool ses_counts(const RayCut& c, float t, float det) {
+  if (c.empty || !(t >= c.t_lo && t <= c.t_hi)) return false;
+  return !((c.cull == A3D_CULL_BACK && det < 0.f) || (c.cull == A3D_CULL_FRONT && det > 0.f));
+}
+// Whether a cloud's vertex shows: on the kept side of every plane (a NaN fails).
+__device__ __forceinline__ bool ses_keeps(const NoSection&, float, float, float) { return true; }
+__device__ __forceinline__ bool ses_keeps(const a3d_section& s, float x, float y, float z) {
+#pragma clang fp contract(off)
+  bool keep = true;
+  for (int k = 0; k < s.n_planes; ++k) {
+    const float side = (s.planes[k][0] * x + s.planes[k][1] * y) + s.planes[k][2] * z;
+    keep = keep && side >= s.planes[k][3];
+  }
+  return keep;
 }
 
 // ---- nearest rows: m queries against up to A3D_NEAREST_MAX_SOURCES row sets in one launch pair -----------------------------
@@ -164,14 +227,17 @@ __device__ __forceinline__ void ses_point(const float* o, const float* d, float 
     best = pick_min(best, k);
   }
 }
+template <class S>                            // NoSection or a3d_section
 __global__ __launch_bounds__(kSesBlock) void k_pick_ray(const PickTab t, unsigned long long* __restrict__ part_a,
-                                                        unsigned* __restrict__ part_row) {
+                                                        unsigned* __restrict__ part_row, const S sec) {
   const float* __restrict__ xyz = t.xyz;
   PickKey best;
   best.a = kNoKey, best.row = 0xffffffffu;
   const long long stride = (long long)gridDim.x * kSesBlock;
-  for (long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x; i < t.n; i += stride)
-    ses_point(t.o, t.d, t.r2, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], (unsigned)i, best);
+  for (long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x; i < t.n; i += stride) {
+    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    if (ses_keeps(sec, x, y, z)) ses_point(t.o, t.d, t.r2, x, y, z, (unsigned)i, best);
+  }
   best = pick_wave_min(best);
   __shared__ unsigned long long sa[kSesBlock / 64];
   __shared__ unsigned sr[kSesBlock / 64];
@@ -283,8 +349,9 @@ __device__ __forceinline__ int ses_face(const MeshTab& t, long long i, MeshFace&
   if (i0 == i1 || i1 == i2 || i0 == i2) return 0;
   return ses_face_test(t.r, t.xyz + 3 * (size_t)i0, t.xyz + 3 * (size_t)i1, t.xyz + 3 * (size_t)i2, f);
 }
+template <class S>                            // NoSection or RayCut (the host derived it from the call's one ray)
 __global__ __launch_bounds__(kSesBlock) void k_pick_mesh(const MeshTab t, unsigned long long* __restrict__ part_key,
-                                                         unsigned* __restrict__ part_flag) {
+                                                         unsigned* __restrict__ part_flag, const S cut) {
   unsigned long long best = kNoKey;
   int bad = 0;
   const long long stride = (long long)gridDim.x * kSesBlock;
@@ -292,7 +359,7 @@ __global__ __launch_bounds__(kSesBlock) void k_pick_mesh(const MeshTab t, unsign
     MeshFace f;
     int32_t i0, i1, i2;
     const int r = ses_face(t, i, f, i0, i1, i2);
-    if (r == 1) {
+    if (r == 1 && ses_counts(cut, f.t, f.det)) {
       const unsigned long long k = ses_key(f.t, (unsigned)i);   // t > 0: its bits order like t
       best = k < best ? k : best;
     }
@@ -309,6 +376,7 @@ __global__ __launch_bounds__(kSesBlock) void k_pick_mesh(const MeshTab t, unsign
     part_flag[blockIdx.x] = bad ? 1u : 0u;
   }
 }
+// (The finish needs no section: the first stage chose the face, the finish only evaluates it again.)
 __global__ __launch_bounds__(64) void k_pick_mesh_finish(const MeshTab t, const unsigned long long* __restrict__ part_key,
                                                          const unsigned* __restrict__ part_flag, int n_blocks) {
   unsigned long long best = kNoKey;
@@ -661,7 +729,8 @@ __device__ __forceinline__ TileLists render_tile_lists(const RenderWs& w) {
   const unsigned n_every = *w.every_count;
   return {n_every, n_every + w.tile_count[tile], w.tile_offset[tile]};
 }
-__global__ __launch_bounds__(kTilePixels) void k_render_tile_mesh(const RenderTab t, const RenderWs w) {
+template <class S>                            // NoSection or a3d_section
+__global__ __launch_bounds__(kTilePixels) void k_render_tile_mesh(const RenderTab t, const RenderWs w, const S sec) {
   if (t.out.header_dev->flags & A3D_RENDER_OVERFLOW) return;
   __shared__ float vtx[kTilePixels][9];
   __shared__ unsigned ids[kTilePixels];
@@ -671,6 +740,7 @@ __global__ __launch_bounds__(kTilePixels) void k_render_tile_mesh(const RenderTa
   RayShear ray;
   ray.o[0] = t.cam.c.o[0], ray.o[1] = t.cam.c.o[1], ray.o[2] = t.cam.c.o[2];
   ses_shear(d, ray);
+  const auto cut = ses_ray_cut(sec, ray.o, d);  // the pixel's interval, as a3d_pick_mesh_section derives it for this ray
   const auto [n_every, total, offset] = render_tile_lists(w);
   unsigned long long best = kNoKey;
   for (unsigned base = 0; base < total; base += kTilePixels) {
@@ -689,7 +759,7 @@ __global__ __launch_bounds__(kTilePixels) void k_render_tile_mesh(const RenderTa
     if (live)
       for (unsigned k = 0; k < cnt; ++k) {
         MeshFace f;
-        if (ses_face_test(ray, vtx[k], vtx[k] + 3, vtx[k] + 6, f) == 1) {
+        if (ses_face_test(ray, vtx[k], vtx[k] + 3, vtx[k] + 6, f) == 1 && ses_counts(cut, f.t, f.det)) {
           const unsigned long long key = ses_key(f.t, ids[k]);
           best = key < best ? key : best;
         }
@@ -715,7 +785,8 @@ __global__ __launch_bounds__(kTilePixels) void k_render_tile_mesh(const RenderTa
   if (t.out.u_dev) t.out.u_dev[at] = u;
   if (t.out.v_dev) t.out.v_dev[at] = v;
 }
-__global__ __launch_bounds__(kTilePixels) void k_render_tile_points(const RenderTab t, const RenderWs w) {
+template <class S>                            // NoSection or a3d_section
+__global__ __launch_bounds__(kTilePixels) void k_render_tile_points(const RenderTab t, const RenderWs w, const S sec) {
   if (t.out.header_dev->flags & A3D_RENDER_OVERFLOW) return;
   __shared__ float pts[kTilePixels][3];
   __shared__ unsigned ids[kTilePixels];
@@ -733,7 +804,10 @@ __global__ __launch_bounds__(kTilePixels) void k_render_tile_points(const Render
       const unsigned i = render_list_entry(w, n_every, offset, base + threadIdx.x);
       ids[threadIdx.x] = i;
       const float* p = t.xyz + 3 * (size_t)i;
-      pts[threadIdx.x][0] = p[0], pts[threadIdx.x][1] = p[1], pts[threadIdx.x][2] = p[2];
+      // a vertex the section cuts away is staged as a NaN, which ses_point passes for no ray: the vertex rule does not depend
+      // on the view, so the thread that stages a vertex decides it once for the tile's 256 pixels
+      pts[threadIdx.x][0] = ses_keeps(sec, p[0], p[1], p[2]) ? p[0] : __builtin_nanf("");
+      pts[threadIdx.x][1] = p[1], pts[threadIdx.x][2] = p[2];
     }
     __syncthreads();
     if (live)
@@ -1044,8 +1118,32 @@ static bool render_camera(const a3d_camera* c, RenderCam& r) {
   r.tiles_x = (c->width + kTile - 1) / kTile, r.tiles_y = (c->height + kTile - 1) / kTile;
   return true;
 }
+// The section of a call as the kernels take it: NULL for none -- also for one without planes and culling, which then runs
+// the very code of the entry points that take no section.
+static const a3d_section* section_active(const a3d_section* s) { return s && (s->n_planes || s->cull) ? s : nullptr; }
+// false (error set): a section the header refuses.  Host arithmetic only; runs before anything else of a call.
+static bool section_ok(const char* what, const a3d_section* s, bool mesh) {
+  if (!s) return true;
+  if (s->n_planes < 0 || s->n_planes > A3D_SECTION_MAX_PLANES) {
+    set_error("%s: section: n_planes = %d, 0..%d planes", what, s->n_planes, A3D_SECTION_MAX_PLANES);
+    return false;
+  }
+  if (s->cull < A3D_CULL_NONE || s->cull > A3D_CULL_FRONT || (!mesh && s->cull != A3D_CULL_NONE)) {
+    set_error("%s: section: cull = %d (0 none, 1 back, 2 front; a point cloud has no faces to cull: 0)", what, s->cull);
+    return false;
+  }
+  for (int k = 0; k < s->n_planes; ++k) {
+    const float* p = s->planes[k];
+    const double n2 = (double)p[0] * p[0] + (double)p[1] * p[1] + (double)p[2] * p[2];
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]) || !std::isfinite(p[3]) || !(n2 >= 0.5 && n2 <= 2.)) {
+      set_error("%s: section: plane %d must be finite with 0.5 <= |n|^2 <= 2 (|n|^2 = %g)", what, k, n2);
+      return false;
+    }
+  }
+  return true;
+}
 static int render_run(const char* what, RenderTab& t, const a3d_camera* camera, const a3d_render_out* out, void* ws,
-                      size_t ws_bytes, hipStream_t st) {
+                      size_t ws_bytes, hipStream_t st, const a3d_section* sec) {
   if (!out || !out->id_dev || !out->t_dev || !out->header_dev) {
     set_error("%s: id_dev, t_dev and header_dev are needed", what);
     return A3D_ERR_INVALID;
@@ -1079,10 +1177,15 @@ static int render_run(const char* what, RenderTab& t, const a3d_camera* camera, 
     A3D_LAUNCH_CHECK();
   }
   const unsigned tiles = (unsigned)(t.cam.tiles_x * t.cam.tiles_y);
-  if (t.mesh)
-    k_render_tile_mesh<<<tiles, kTilePixels, 0, st>>>(t, w);
+  sec = section_active(sec);
+  if (t.mesh && sec)
+    k_render_tile_mesh<a3d_section><<<tiles, kTilePixels, 0, st>>>(t, w, *sec);
+  else if (t.mesh)
+    k_render_tile_mesh<NoSection><<<tiles, kTilePixels, 0, st>>>(t, w, NoSection{});
+  else if (sec)
+    k_render_tile_points<a3d_section><<<tiles, kTilePixels, 0, st>>>(t, w, *sec);
   else
-    k_render_tile_points<<<tiles, kTilePixels, 0, st>>>(t, w);
+    k_render_tile_points<NoSection><<<tiles, kTilePixels, 0, st>>>(t, w, NoSection{});
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -1125,15 +1228,18 @@ extern "C" int a3d_nearest_rows(const a3d_nearest_source* sources, int n_sources
   return A3D_OK;
 }
 
-extern "C" int a3d_pick_ray(const float* xyz_dev, int64_t n, const float* origin, const float* direction, float radius,
-                            a3d_pick_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+// Both a3d_pick_ray (sec NULL) and a3d_pick_ray_section.
+static int pick_ray_run(const char* what, const float* xyz_dev, int64_t n, const float* origin, const float* direction,
+                        float radius, const a3d_section* sec, a3d_pick_result* result_dev, void* workspace_dev,
+                        size_t workspace_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (!section_ok(what, sec, false)) return A3D_ERR_INVALID;
   if (!ses_rows_ok(n, xyz_dev) || !origin || !direction || !result_dev || !(radius >= 0.f)) {
-    set_error("a3d_pick_ray: bad arguments (n=%lld radius=%g)", (long long)n, (double)radius);
+    set_error("%s: bad arguments (n=%lld radius=%g)", what, (long long)n, (double)radius);
     return A3D_ERR_INVALID;
   }
-  if (!ses_unit_direction("a3d_pick_ray", direction)) return A3D_ERR_INVALID;
-  if (!ses_ws_ok(workspace_dev, workspace_bytes, "a3d_pick_ray")) return A3D_ERR_WORKSPACE;
+  if (!ses_unit_direction(what, direction)) return A3D_ERR_INVALID;
+  if (!ses_ws_ok(workspace_dev, workspace_bytes, what)) return A3D_ERR_WORKSPACE;
   PickTab t;
   t.xyz = xyz_dev, t.n = n;
   for (int k = 0; k < 3; ++k) t.o[k] = origin[k], t.d[k] = direction[k];
@@ -1141,23 +1247,40 @@ extern "C" int a3d_pick_ray(const float* xyz_dev, int64_t n, const float* origin
   t.out = result_dev;
   const SesWs w = carve_session(workspace_dev);
   const int nb = ses_blocks(n);
-  k_pick_ray<<<nb, kSesBlock, 0, st>>>(t, w.pick_a, w.pick_row);
+  sec = section_active(sec);
+  if (sec)
+    k_pick_ray<a3d_section><<<nb, kSesBlock, 0, st>>>(t, w.pick_a, w.pick_row, *sec);
+  else
+    k_pick_ray<NoSection><<<nb, kSesBlock, 0, st>>>(t, w.pick_a, w.pick_row, NoSection{});
   A3D_LAUNCH_CHECK();
   k_pick_finish<<<1, 64, 0, st>>>(t, w.pick_a, w.pick_row, nb);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
+extern "C" int a3d_pick_ray(const float* xyz_dev, int64_t n, const float* origin, const float* direction, float radius,
+                            a3d_pick_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return pick_ray_run("a3d_pick_ray", xyz_dev, n, origin, direction, radius, nullptr, result_dev, workspace_dev,
+                      workspace_bytes, stream);
+}
+extern "C" int a3d_pick_ray_section(const float* xyz_dev, int64_t n, const float* origin, const float* direction, float radius,
+                                    const a3d_section* section, a3d_pick_result* result_dev, void* workspace_dev,
+                                    size_t workspace_bytes, void* stream) {
+  return pick_ray_run("a3d_pick_ray_section", xyz_dev, n, origin, direction, radius, section, result_dev, workspace_dev,
+                      workspace_bytes, stream);
+}
 
-extern "C" int a3d_pick_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const float* origin,
-                             const float* direction, a3d_pick_mesh_result* result_dev, void* workspace_dev,
-                             size_t workspace_bytes, void* stream) {
+// Both a3d_pick_mesh (sec NULL) and a3d_pick_mesh_section.
+static int pick_mesh_run(const char* what, const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m,
+                         const float* origin, const float* direction, const a3d_section* sec, a3d_pick_mesh_result* result_dev,
+                         void* workspace_dev, size_t workspace_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (!section_ok(what, sec, true)) return A3D_ERR_INVALID;
   if (!ses_rows_ok(n, xyz_dev) || !ses_rows_ok(m, faces_dev) || !origin || !direction || !result_dev) {
-    set_error("a3d_pick_mesh: bad arguments (n=%lld m=%lld)", (long long)n, (long long)m);
+    set_error("%s: bad arguments (n=%lld m=%lld)", what, (long long)n, (long long)m);
     return A3D_ERR_INVALID;
   }
-  if (!ses_unit_direction("a3d_pick_mesh", direction)) return A3D_ERR_INVALID;
-  if (!ses_ws_ok(workspace_dev, workspace_bytes, "a3d_pick_mesh")) return A3D_ERR_WORKSPACE;
+  if (!ses_unit_direction(what, direction)) return A3D_ERR_INVALID;
+  if (!ses_ws_ok(workspace_dev, workspace_bytes, what)) return A3D_ERR_WORKSPACE;
   MeshTab t;
   t.xyz = xyz_dev, t.n = n, t.faces = faces_dev, t.m = m;
   for (int k = 0; k < 3; ++k) t.r.o[k] = origin[k];
@@ -1165,10 +1288,38 @@ extern "C" int a3d_pick_mesh(const float* xyz_dev, int64_t n, const int32_t* fac
   t.out = result_dev;
   const SesWs w = carve_session(workspace_dev);
   const int nb = ses_blocks(m);
-  k_pick_mesh<<<nb, kSesBlock, 0, st>>>(t, w.mesh_key, w.mesh_flag);
+  sec = section_active(sec);
+  if (sec)                                     // the ray's interval, here on the host: what a pixel of the view derives for the same ray
+    k_pick_mesh<RayCut><<<nb, kSesBlock, 0, st>>>(t, w.mesh_key, w.mesh_flag, ses_ray_cut(*sec, t.r.o, direction));
+  else
+    k_pick_mesh<NoSection><<<nb, kSesBlock, 0, st>>>(t, w.mesh_key, w.mesh_flag, NoSection{});
   A3D_LAUNCH_CHECK();
   k_pick_mesh_finish<<<1, 64, 0, st>>>(t, w.mesh_key, w.mesh_flag, nb);
   A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+extern "C" int a3d_pick_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const float* origin,
+                             const float* direction, a3d_pick_mesh_result* result_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream) {
+  return pick_mesh_run("a3d_pick_mesh", xyz_dev, n, faces_dev, m, origin, direction, nullptr, result_dev, workspace_dev,
+                       workspace_bytes, stream);
+}
+extern "C" int a3d_pick_mesh_section(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const float* origin,
+                                     const float* direction, const a3d_section* section, a3d_pick_mesh_result* result_dev,
+                                     void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return pick_mesh_run("a3d_pick_mesh_section", xyz_dev, n, faces_dev, m, origin, direction, section, result_dev, workspace_dev,
+                       workspace_bytes, stream);
+}
+extern "C" int a3d_section_ray(const a3d_section* section, const float* origin, const float* direction, float* out3) {
+  if (!section_ok("a3d_section_ray", section, true)) return A3D_ERR_INVALID;
+  if (!origin || !direction || !out3) {
+    set_error("a3d_section_ray: origin, direction and out3 are needed");
+    return A3D_ERR_INVALID;
+  }
+  a3d_section none;
+  none.n_planes = 0, none.cull = A3D_CULL_NONE;
+  const RayCut c = ses_ray_cut(section ? *section : none, origin, direction);
+  out3[0] = c.t_lo, out3[1] = c.t_hi, out3[2] = c.empty ? 1.f : 0.f;
   return A3D_OK;
 }
 
@@ -1210,29 +1361,55 @@ extern "C" int a3d_render_camera_bounds(const a3d_camera* camera, double* out13)
   return A3D_OK;
 }
 
-extern "C" int a3d_render_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const a3d_camera* camera,
-                               const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream) {
+// Both a3d_render_mesh (sec NULL) and a3d_render_mesh_section.
+static int render_mesh_run(const char* what, const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m,
+                           const a3d_camera* camera, const a3d_section* sec, const a3d_render_out* out, void* workspace_dev,
+                           size_t workspace_bytes, void* stream) {
+  if (!section_ok(what, sec, true)) return A3D_ERR_INVALID;
   if (!ses_rows_ok(n, xyz_dev) || !ses_rows_ok(m, faces_dev)) {
-    set_error("a3d_render_mesh: bad arguments (n=%lld m=%lld)", (long long)n, (long long)m);
+    set_error("%s: bad arguments (n=%lld m=%lld)", what, (long long)n, (long long)m);
     return A3D_ERR_INVALID;
   }
   RenderTab t;
   memset(&t, 0, sizeof(t));
   t.xyz = xyz_dev, t.n = n, t.faces = faces_dev, t.mesh = 1, t.m = m;
-  return render_run("a3d_render_mesh", t, camera, out, workspace_dev, workspace_bytes, (hipStream_t)stream);
+  return render_run(what, t, camera, out, workspace_dev, workspace_bytes, (hipStream_t)stream, sec);
+}
+extern "C" int a3d_render_mesh(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const a3d_camera* camera,
+                               const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return render_mesh_run("a3d_render_mesh", xyz_dev, n, faces_dev, m, camera, nullptr, out, workspace_dev, workspace_bytes, stream);
+}
+extern "C" int a3d_render_mesh_section(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m,
+                                       const a3d_camera* camera, const a3d_section* section, const a3d_render_out* out,
+                                       void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return render_mesh_run("a3d_render_mesh_section", xyz_dev, n, faces_dev, m, camera, section, out, workspace_dev,
+                         workspace_bytes, stream);
 }
 
-extern "C" int a3d_render_points(const float* xyz_dev, int64_t n, float radius, const a3d_camera* camera,
-                                 const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream) {
+// Both a3d_render_points (sec NULL) and a3d_render_points_section.
+static int render_points_run(const char* what, const float* xyz_dev, int64_t n, float radius, const a3d_camera* camera,
+                             const a3d_section* sec, const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes,
+                             void* stream) {
+  if (!section_ok(what, sec, false)) return A3D_ERR_INVALID;
   if (!ses_rows_ok(n, xyz_dev) || !(radius >= 0.f) || !std::isfinite(radius)) {
-    set_error("a3d_render_points: bad arguments (n=%lld radius=%g)", (long long)n, (double)radius);
+    set_error("%s: bad arguments (n=%lld radius=%g)", what, (long long)n, (double)radius);
     return A3D_ERR_INVALID;
   }
   RenderTab t;
   memset(&t, 0, sizeof(t));
   t.xyz = xyz_dev, t.n = n, t.faces = nullptr, t.mesh = 0, t.m = n;
   t.r2 = radius * radius, t.radius = radius;
-  return render_run("a3d_render_points", t, camera, out, workspace_dev, workspace_bytes, (hipStream_t)stream);
+  return render_run(what, t, camera, out, workspace_dev, workspace_bytes, (hipStream_t)stream, sec);
+}
+extern "C" int a3d_render_points(const float* xyz_dev, int64_t n, float radius, const a3d_camera* camera,
+                                 const a3d_render_out* out, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return render_points_run("a3d_render_points", xyz_dev, n, radius, camera, nullptr, out, workspace_dev, workspace_bytes, stream);
+}
+extern "C" int a3d_render_points_section(const float* xyz_dev, int64_t n, float radius, const a3d_camera* camera,
+                                         const a3d_section* section, const a3d_render_out* out, void* workspace_dev,
+                                         size_t workspace_bytes, void* stream) {
+  return render_points_run("a3d_render_points_section", xyz_dev, n, radius, camera, section, out, workspace_dev, workspace_bytes,
+                           stream);
 }
 
 extern "C" int a3d_render_shade(const int32_t* id_dev, const float* u_dev, const float* v_dev, const int32_t* faces_dev, int64_t m,

@@ -154,6 +154,11 @@ class RenderOut(C.Structure):
                 ("header_dev", C.c_void_p)]
 
 
+class Section(C.Structure):
+    """a3d_section: up to 8 planes (nx, ny, nz, c), each keeping the side n . p >= c, and a culling mode (meshes only)."""
+    _fields_ = [("n_planes", C.c_int32), ("cull", C.c_int32), ("planes", (C.c_float * 4) * 8)]
+
+
 class ClickCluster(C.Structure):
     _fields_ = [("cluster_id", C.c_int32), ("row", C.c_int32), ("label", C.c_int32), ("pred", C.c_int32),
                 ("error_size", C.c_float)]
@@ -165,6 +170,9 @@ A3D_NEAREST_MAX_SOURCES = 4
 A3D_RENDER_MAX_SIZE = 4096
 A3D_RENDER_TILE = 16
 A3D_RENDER_BAD_INDEX, A3D_RENDER_OVERFLOW = 1, 2
+A3D_SECTION_MAX_PLANES = 8
+A3D_CULL_NONE, A3D_CULL_BACK, A3D_CULL_FRONT = 0, 1, 2
+A3D_ERR_INVALID = -1
 PROF_DENSE = 11
 PROF_NAMES = ["spconv", "splitk_epilogue", "stem", "c2s_attn", "query_chain", "s2c_attn", "ln_mask", "posenc",
               "scene_sort_levels", "scene_tables", "click_simulator", "dense_gemm"]
@@ -345,6 +353,11 @@ SYMBOLS = {
                                C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_pick_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_pick_ray_section": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,
+                                       C.POINTER(Section), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_pick_mesh_section": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        C.POINTER(Section), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_section_ray": (C.c_int, [C.POINTER(Section), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "a3d_session_paint": (C.c_int, [C.POINTER(SessionPaintArgs), C.c_void_p]),
     "a3d_session_edit": (C.c_int, [C.POINTER(SessionEditArgs), C.c_void_p]),
     "a3d_render_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int64]),
@@ -353,6 +366,10 @@ SYMBOLS = {
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_render_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.POINTER(Camera), C.POINTER(RenderOut), C.c_void_p,
                                     C.c_size_t, C.c_void_p]),
+    "a3d_render_mesh_section": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(Camera), C.POINTER(Section),
+                                          C.POINTER(RenderOut), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "a3d_render_points_section": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.POINTER(Camera), C.POINTER(Section),
+                                            C.POINTER(RenderOut), C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_render_shade": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                    C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "a3d_vertex_normals": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

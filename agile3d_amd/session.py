@@ -19,6 +19,9 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
     argmax + clicked rows               a3d_argmax_labels  (interactive_segmentation_user.py:78-81)
     pred[inverse_map], colours, cubes   a3d_session_paint  (:83-84,125-140; gui.py:276-298,327)
     IoU against the relabelled truth    a3d_iou_counts     (:86-88)
+    looking into the scan               a3d_pick_ray_section / a3d_pick_mesh_section / a3d_render_mesh_section /
+                                        a3d_render_points_section  (Section, set_section: section planes and back-face
+                                        culling; in the GUI the camera's near plane cuts a wall away; a rule of ours)
     taking a click back, resuming       a3d_session_edit   (undo, redo, remove_click, restore_clicks / restore_file: the
                                         GUI's "unselect point" is a TODO, gui.py:283-287; a rule of ours)
 
@@ -327,13 +330,126 @@ def framing_view(coords, width, height, fov_deg=35.0):
     return np.array([[f, 0.0, 0.5 * width], [0.0, f, 0.5 * height], [0.0, 0.0, 1.0]]), ext
 
 
+_CULL = {"none": L.A3D_CULL_NONE, "back": L.A3D_CULL_BACK, "front": L.A3D_CULL_FRONT}
+
+
+class Section:
+    """What of a scene the picks and the view leave out (include/agile3d_hip.h, ``a3d_section``): up to 8 section planes and,
+    on a mesh, the culling of faces by the side they turn to the ray.  Host data, immutable, pure numpy.
+
+    ``planes``: a sequence of ``(normal, offset)`` -- the kept side is ``normal . p >= offset`` -- or ``(normal,
+    point_on_plane)``, the kept side the one the normal points to.  A normal is normalised in float64 (an offset divided by
+    its length, a point projected on the unit normal) and each value rounded to fp32 once; a value that is not finite or a
+    zero normal raises ``ValueError``.  ``cull``: ``"none"``, ``"back"`` (drop the faces seen from behind: the near walls
+    of a room seen from outside, the "dollhouse" view) or ``"front"``.
+
+    ``normals`` fp32 [k, 3], ``offsets`` fp32 [k], ``cull``.  On a mesh the planes cut the RAY: a crossing counts when its
+    ``t`` lies in the ray's interval.  On a cloud they select vertices: ``keeps``."""
+
+    __slots__ = ("normals", "offsets", "cull")
+
+    def __init__(self, planes=(), cull="none"):
+        if cull not in _CULL:
+            raise ValueError(f"cull must be one of {sorted(_CULL)}, not {cull!r}")
+        planes = list(planes)
+        if len(planes) > L.A3D_SECTION_MAX_PLANES:
+            raise ValueError(f"at most {L.A3D_SECTION_MAX_PLANES} planes, not {len(planes)}")
+        normals, offsets = np.zeros((len(planes), 3), np.float32), np.zeros(len(planes), np.float32)
+        for k, plane in enumerate(planes):
+            try:
+                normal, where = plane
+                n = np.asarray(normal, dtype=np.float64).reshape(-1)
+                w = np.asarray(where, dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError(f"plane {k} must be (normal, offset) or (normal, point_on_plane)") from None
+            if n.shape != (3,) or w.shape not in ((1,), (3,)) or not (np.isfinite(n).all() and np.isfinite(w).all()):
+                raise ValueError(f"plane {k}: a normal of three and an offset or a point of three, all finite")
+            length = float(np.linalg.norm(n))
+            if not length > 0.0:
+                raise ValueError(f"plane {k}: the normal is zero")
+            unit = n / length
+            c = float(w[0]) / length if w.shape == (1,) else float(unit @ w)
+            with np.errstate(over="ignore"):
+                normals[k], offsets[k] = unit.astype(np.float32), np.float32(c)
+            if not (np.isfinite(normals[k]).all() and np.isfinite(offsets[k])):
+                raise ValueError(f"plane {k}: not finite in fp32")
+        normals.setflags(write=False)
+        offsets.setflags(write=False)
+        object.__setattr__(self, "normals", normals)
+        object.__setattr__(self, "offsets", offsets)
+        object.__setattr__(self, "cull", cull)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Section is immutable (with_cull, or a new one)")
+
+    def __repr__(self):
+        planes = ", ".join(f"({n.tolist()}, {float(c)})" for n, c in zip(self.normals, self.offsets))
+        return f"Section(planes=[{planes}], cull={self.cull!r})"
+
+    @property
+    def n_planes(self):
+        return len(self.offsets)
+
+    @classmethod
+    def box(cls, lo, hi, cull="none"):
+        """Six planes that keep the axis-aligned box ``lo <= p <= hi``."""
+        lo, hi = np.asarray(lo, np.float64).reshape(-1), np.asarray(hi, np.float64).reshape(-1)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("lo and hi must be three numbers each")
+        eye = np.eye(3)
+        return cls([(eye[k], float(lo[k])) for k in range(3)] + [(-eye[k], -float(hi[k])) for k in range(3)], cull)
+
+    @classmethod
+    def below(cls, z, cull="none"):
+        """One plane that keeps ``z' <= z``: it cuts a ceiling off."""
+        return cls([((0.0, 0.0, -1.0), -float(z))], cull)
+
+    def with_cull(self, cull):
+        """The same planes, bit for bit, with another culling mode (the stored fp32 values are shared, not normalised again:
+        a view under one and a pick under the other cut at the same planes)."""
+        if cull not in _CULL:
+            raise ValueError(f"cull must be one of {sorted(_CULL)}, not {cull!r}")
+        other = object.__new__(Section)
+        object.__setattr__(other, "normals", self.normals)
+        object.__setattr__(other, "offsets", self.offsets)
+        object.__setattr__(other, "cull", cull)
+        return other
+
+    def keeps(self, points):
+        """bool [k]: which of ``points`` [k, 3] lie on the kept side of every plane -- the vertex rule of the header in
+        fp32, one operation at a time: ``(nx*x + ny*y) + nz*z >= c``; a NaN fails.  Culling plays no part."""
+        p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+        keep = np.ones(len(p), bool)
+        with np.errstate(all="ignore"):
+            for n, c in zip(self.normals, self.offsets):
+                keep &= (n[0] * p[:, 0] + n[1] * p[:, 1]) + n[2] * p[:, 2] >= c
+        return keep
+
+    def struct(self):
+        """The ``lib.Section`` (``a3d_section``) the library takes."""
+        s = L.Section()
+        s.n_planes, s.cull = self.n_planes, _CULL[self.cull]
+        for k in range(self.n_planes):
+            s.planes[k][:] = [float(x) for x in self.normals[k]] + [float(self.offsets[k])]
+        return s
+
+
+def visible_clicks(section, points):
+    """int64 [k']: the indices of the click ``points`` [k, 3] whose marker a view under ``section`` shows -- all of them
+    without a section (``None``), else those that ``section.keeps``.  A marker of a click inside the cut-away part would
+    float over whatever lies behind it.  Pure numpy."""
+    p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    return np.arange(len(p)) if section is None else np.flatnonzero(section.keeps(p))
+
+
 class RenderResult:
     """What ``render()`` returns.  Device tensors: ``ids`` int32 [h, w] (face of a mesh, vertex of a cloud, -1 = nothing),
     ``t`` fp32 [h, w] (+inf = nothing), ``rgb`` uint8 [h, w, 3], on a mesh ``u`` and ``v`` fp32 [h, w] (else ``None``).
     ``camera``: the ``lib.Camera`` rendered.  ``mesh``: whether ids are faces.  ``lit``: whether ``rgb`` is shaded.
-    ``pairs`` and ``n_everywhere``: the (tile, primitive) pairs of the call and the primitives every pixel tested."""
+    ``pairs`` and ``n_everywhere``: the (tile, primitive) pairs of the call and the primitives every pixel tested.
+    ``section``: the ``Section`` the view was rendered under, or ``None``."""
 
-    __slots__ = ("ids", "t", "rgb", "u", "v", "camera", "mesh", "lit", "pairs", "n_everywhere")
+    __slots__ = ("ids", "t", "rgb", "u", "v", "camera", "mesh", "lit", "pairs", "n_everywhere", "section")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -392,6 +508,7 @@ class InteractiveSession:
         self._backbone = None
         self._mask_host = None
         self._render_ws = None                      # scratch of render(): kept per scene, grown when a view needs more pairs
+        self.section = None                         # the Section pick, click_ray and render apply by default (set_section)
         self._reset_clicks()
 
     def _reset_clicks(self):
@@ -415,7 +532,8 @@ class InteractiveSession:
         ``out_dir/masks/mask_*.npy`` and ``out_dir/clicks/click_*.npy``.  ``faces`` [m, 3] integer indices into
         ``coords_full`` make the scene a triangle mesh: ``pick`` then meets its surface (``ses.faces``, int32 on the
         device; indices outside ``[0, n)`` raise ``ValueError``), and the vertices' incidence lists for the normals of a
-        lit ``render`` are built here, on the host (``vertex_corner_lists``).  Everything of a previous scene is dropped."""
+        lit ``render`` are built here, on the host (``vertex_corner_lists``).  Everything of a previous scene is dropped,
+        its section (``set_section``) included."""
         self._drop_scene()
         dev = self.device
         xyz = torch.as_tensor(np.asarray(coords_full) if not torch.is_tensor(coords_full) else coords_full)
@@ -492,7 +610,8 @@ class InteractiveSession:
 
     def reset(self):
         """A new annotation of the same scene: clicks, relabelled ground truth and labels start over; the backbone output
-        (and with it the scene's first-layer cache of ``forward_mask``) stays."""
+        (and with it the scene's first-layer cache of ``forward_mask``) stays, and so does the section (``set_section``): it
+        belongs to the view, not to the annotation."""
         self._need_scene()
         self._reset_clicks()
 
@@ -500,14 +619,39 @@ class InteractiveSession:
         if self._backbone is None:
             raise RuntimeError("no scene loaded (load_scene / load_scene_dir)")
 
+    # ------------------------------------------------------------------ the section
+    def set_section(self, section):
+        """Makes ``section`` (a ``Section``, or ``None`` for none) what ``pick``, ``click_ray`` and ``render`` apply when
+        they are given no other: section planes to look into the scan, back-face culling to look through the walls that
+        face away.  A property of the view: ``reset`` and edits of the click list keep it, ``load_scene`` drops it."""
+        self._need_scene()
+        if section is not None and not isinstance(section, Section):
+            raise TypeError("set_section takes a Section or None")
+        self.section = section
+        return self
+
+    def _section_of(self, section, mesh):
+        """(the ``Section`` a call applies -- its own, else the session's -- or ``None`` when that leaves everything in; the
+        ``lib.Section`` of it)."""
+        sec = self.section if section is None else section
+        if sec is not None and not isinstance(sec, Section):
+            raise TypeError("section must be a Section or None")
+        if sec is None or (sec.n_planes == 0 and sec.cull == "none"):
+            return None, None
+        if not mesh and sec.cull != "none":
+            raise ValueError(f"a section with cull={sec.cull!r} on a point cloud: only a mesh has faces to cull")
+        return sec, sec.struct()
+
     # ------------------------------------------------------------------ pick and click
-    def pick(self, origin, direction, radius=None, surface=None):
+    def pick(self, origin, direction, radius=None, surface=None, section=None):
         """The point a pointer ray meets, ``[x, y, z]``, or ``None`` ("clicked on nothing").  Both rules are this library's.
         A point cloud (``a3d_pick_ray``): among the vertices in front of ``origin`` within ``radius`` (default
         ``voxel_size``) of the ray, the first along it; ties go to the one closer to the ray, then to the lower index.  A
         triangle mesh (``a3d_pick_mesh``): the point where the ray first crosses a face -- what the GUI's unprojection of
         the rendered depth yields and what ``click`` takes.  ``surface=None`` uses the surface rule when the scene has
-        faces, ``False`` forces the vertex rule, ``True`` without faces raises ``ValueError``."""
+        faces, ``False`` forces the vertex rule, ``True`` without faces raises ``ValueError``.  ``section``: a ``Section``
+        to pick under (``a3d_pick_mesh_section`` / ``a3d_pick_ray_section``; default: the session's, ``set_section``; an empty
+        ``Section()`` picks without one); culling under the vertex rule raises ``ValueError``."""
         self._need_scene()
         o = _f3(origin, "origin")
         d64 = np.asarray(direction, dtype=np.float64).reshape(-1)
@@ -519,11 +663,19 @@ class InteractiveSession:
         if surface:
             if self.faces is None:
                 raise ValueError("pick(surface=True): the scene has no faces (load_scene(..., faces=) or a mesh scan.ply)")
-            out = V.pick_mesh(self.coords_full, self.faces, o, d, out=self._small[:8], workspace=self._ws)
+            sec, cut = self._section_of(section, True)
+            if sec is None:
+                out = V.pick_mesh(self.coords_full, self.faces, o, d, out=self._small[:8], workspace=self._ws)
+            else:
+                out = V.pick_mesh_section(self.coords_full, self.faces, o, d, cut, out=self._small[:8], workspace=self._ws)
             hit = V.read_pick_mesh(out.cpu().numpy())[0]
             return None if hit["face"] < 0 else [float(hit[k]) for k in "xyz"]
         r = self.voxel_size if radius is None else float(radius)
-        out = V.pick_ray(self.coords_full, o, d, r, out=self._small[:4], workspace=self._ws)
+        sec, cut = self._section_of(section, False)
+        if sec is None:
+            out = V.pick_ray(self.coords_full, o, d, r, out=self._small[:4], workspace=self._ws)
+        else:
+            out = V.pick_ray_section(self.coords_full, o, d, r, cut, out=self._small[:4], workspace=self._ws)
         index, xyz = V.read_pick(out.cpu().numpy())
         return None if index < 0 else [float(v) for v in xyz]
 
@@ -543,7 +695,7 @@ class InteractiveSession:
         return self.normals
 
     def render(self, intrinsic, extrinsic, width, height, colors=None, radius=None, background=(1.0, 1.0, 1.0), lit=False,
-               ambient=0.35, depth_strength=8.0):
+               ambient=0.35, depth_strength=8.0, section=None):
         """Id, depth and colour images of the scene for a pinhole camera (``camera_from_matrices``): pixel by pixel what
         ``pick`` returns for the ray through the pixel's centre -- faces when the scene has them (``a3d_render_mesh``),
         else vertices within ``radius`` (default ``voxel_size``) of the ray (``a3d_render_points``).  ``colors`` [n, 3]
@@ -555,7 +707,10 @@ class InteractiveSession:
         by how far it lies behind its four neighbours (``a3d_render_shade_depth``: colour / (1 + ``depth_strength`` x the
         summed relative depth steps)).  ``ambient`` in [0, 1] and ``depth_strength`` >= 0 are used only when ``lit``; their
         defaults, 0.35 and 8.0, are this project's settings, not the reference's (Open3D's lit material is not
-        reproduced).  Returns a ``RenderResult``.  One small device-to-host
+        reproduced).  ``section``: the ``Section`` to render under (``a3d_render_mesh_section`` /
+        ``a3d_render_points_section``; default: the session's; an empty ``Section()`` renders without one; culling on a cloud
+        raises ``ValueError``) -- the image stays what ``pick`` under the same section returns, and ``result.section`` keeps
+        it for ``annotate`` and ``click_at``.  Returns a ``RenderResult``.  One small device-to-host
         copy (the result header) per attempt; a view that needs more (tile, primitive) pairs than the scene's workspace
         holds is rendered again with a larger one."""
         self._need_scene()
@@ -575,6 +730,7 @@ class InteractiveSession:
             raise ValueError(f"colors must be a float32 tensor [{n}, 3] on the session's device")
         col = col.contiguous()
         mesh = self.faces is not None
+        sec, cut = self._section_of(section, mesh)
         n_prim = self.faces.shape[0] if mesh else n
         r = self.voxel_size if radius is None else float(radius)
         ids = t = u = v = None                      # (allocated by the first attempt, written again by a retry)
@@ -586,10 +742,15 @@ class InteractiveSession:
                 self._render_ws = None              # (dropped first: the old and the new one need not live together)
                 self._render_ws = torch.empty(need, dtype=torch.uint8, device=dev)
             ws = self._render_ws
-            if mesh:
+            if mesh and sec is None:
                 ids, t, u, v, _ = V.render_mesh(self.coords_full, self.faces, cam, ids, t, u, v, header=header, workspace=ws)
-            else:
+            elif mesh:
+                ids, t, u, v, _ = V.render_mesh_section(self.coords_full, self.faces, cam, cut, ids, t, u, v, header=header,
+                                                        workspace=ws)
+            elif sec is None:
                 ids, t, _ = V.render_points(self.coords_full, r, cam, ids, t, header=header, workspace=ws)
+            else:
+                ids, t, _ = V.render_points_section(self.coords_full, r, cam, cut, ids, t, header=header, workspace=ws)
             flags, n_every, pairs = V.read_render_header(header.cpu().numpy())
             if not flags & L.A3D_RENDER_OVERFLOW:
                 break
@@ -605,7 +766,7 @@ class InteractiveSession:
         else:
             rgb = V.render_shade(ids, u, v, self.faces, col, bg)
         return RenderResult(ids=ids, t=t, rgb=rgb, u=u, v=v, camera=cam, mesh=mesh, lit=bool(lit), pairs=pairs,
-                            n_everywhere=n_every)
+                            n_everywhere=n_every, section=sec)
 
     def pick_from_render(self, result, u, v):
         """The point a click through pixel ``(u, v)`` (column, row) of ``result`` takes -- what ``pick`` returns for that
@@ -674,7 +835,9 @@ class InteractiveSession:
         projection of its picked point (``view.marker_table``), in its cube's colour with a rim ``marker_border_px`` wide in
         ``marker_border_color`` -- also a click that has no vertex in its cube and so leaves ``preview``'s colours alone.
         A click shows through pixels whose surface lies up to ``depth_slack`` world units (default ``cube_size``) in front of
-        it and is hidden behind nearer ones.  The defaults -- black outlines, 6-pixel discs with a white 1.5-pixel rim --
+        it and is hidden behind nearer ones.  A click whose picked point the planes of ``result.section`` cut away has no
+        marker (``visible_clicks``: the vertex rule on the point, so a click made exactly on a plane may lose its marker to
+        the rounding of the point).  The defaults -- black outlines, 6-pixel discs with a white 1.5-pixel rim --
         are this project's settings, not the reference's (the GUI shows clicks as recoloured vertices only)."""
         marker_px, marker_border_px = float(marker_px), float(marker_border_px)
         slack = self.cube_size if depth_slack is None else float(depth_slack)
@@ -689,6 +852,7 @@ class InteractiveSession:
         table = None
         if markers and self.num_clicks:
             cubes = self._cubes[:self.num_clicks]
+            cubes = cubes[visible_clicks(result.section, cubes[:, :3])]
             rows = V.marker_table(result.camera, cubes[:, :3], cubes[:, 3:])
             table = torch.from_numpy(rows).to(self.device) if len(rows) else None
         return V.render_annotate(result.rgb, label_image, result.t, table, marker_px, marker_px - marker_border_px, slack,
@@ -735,10 +899,10 @@ class InteractiveSession:
         self.num_clicks += 1
         return row_qv, row_full
 
-    def click_ray(self, origin, direction, obj: int):
+    def click_ray(self, origin, direction, obj: int, section=None):
         """``pick`` then ``click``: the click a pointer ray makes for object ``obj``.  Returns what ``click`` returns, or
-        ``None`` -- with nothing booked -- when the ray meets nothing."""
-        point = self.pick(origin, direction)
+        ``None`` -- with nothing booked -- when the ray meets nothing.  ``section``: as ``pick``'s."""
+        point = self.pick(origin, direction, section=section)
         if point is None:
             return None
         return self.click(point, obj)
@@ -885,9 +1049,11 @@ class InteractiveSession:
         if not self.num_clicks:
             return None
         cubes = self._cubes[:self.num_clicks]
+        visible = visible_clicks(result.section, cubes[:, :3])      # (as annotate: no marker in the cut-away part)
+        cubes = cubes[visible]
         rows, kept = V.marker_table(result.camera, cubes[:, :3], cubes[:, 3:], return_kept=True)
         hit = marker_hit(rows, u, v, result.t[v, u].cpu().numpy(), marker_px, slack)
-        return None if hit is None else int(kept[hit])
+        return None if hit is None else int(visible[kept[hit]])
 
     def _palette_entry(self, obj):
         n = self.palette.shape[0]

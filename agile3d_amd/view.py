@@ -122,32 +122,78 @@ def nearest_rows(sources, queries, out=None, workspace=None):
     return out
 
 
-def pick_ray(xyz, origin, direction, radius, out=None, workspace=None):
-    """``a3d_pick_ray``: the first vertex of fp32 [n, 3] along a ray (unit ``direction``) -> int32 [4], see ``read_pick``."""
+# The ``*_section`` calls take a ``lib.Section`` or ``None`` (the C ABI's NULL: no section).  ``_PLAIN`` stands for "the entry
+# point without a section": the wrappers that have always been here keep calling exactly that.
+_PLAIN = object()
+
+
+def _section_ptr(section):
+    if section is not None and not isinstance(section, L.Section):
+        raise ValueError("section must be a lib.Section or None")
+    return None if section is None else C.byref(section)
+
+
+def _pick_ray(xyz, origin, direction, radius, section, out, workspace):
     dev = _device("xyz", xyz)
     xp = _ptr("xyz", xyz, F32, (None, 3), dev)
     (o, op), (d, dp) = _f32p("origin", origin, (3,)), _f32p("direction", direction, (3,))
     out = _out("out", out, I32, (4,), dev)
     ws = _workspace(workspace, dev)
-    L.check(L.load().a3d_pick_ray(xp, xyz.shape[0], op, dp, float(radius), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                  _stream(dev)), "a3d_pick_ray")
+    tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+    if section is _PLAIN:
+        L.check(L.load().a3d_pick_ray(xp, xyz.shape[0], op, dp, float(radius), *tail), "a3d_pick_ray")
+    else:
+        L.check(L.load().a3d_pick_ray_section(xp, xyz.shape[0], op, dp, float(radius), _section_ptr(section), *tail),
+                "a3d_pick_ray_section")
     return out
 
 
-def pick_mesh(xyz, faces, origin, direction, out=None, workspace=None):
-    """``a3d_pick_mesh``: the first face (int32 [m, 3] into ``xyz``) a ray crosses -> int32 [8], see ``read_pick_mesh``."""
+def _pick_mesh(xyz, faces, origin, direction, section, out, workspace):
     dev = _device("xyz", xyz)
     xp, fp = _ptr("xyz", xyz, F32, (None, 3), dev), _ptr("faces", faces, I32, (None, 3), dev)
     (o, op), (d, dp) = _f32p("origin", origin, (3,)), _f32p("direction", direction, (3,))
     out = _out("out", out, I32, (8,), dev)
     ws = _workspace(workspace, dev)
-    L.check(L.load().a3d_pick_mesh(xp, xyz.shape[0], fp, faces.shape[0], op, dp, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   _stream(dev)), "a3d_pick_mesh")
+    tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+    if section is _PLAIN:
+        L.check(L.load().a3d_pick_mesh(xp, xyz.shape[0], fp, faces.shape[0], op, dp, *tail), "a3d_pick_mesh")
+    else:
+        L.check(L.load().a3d_pick_mesh_section(xp, xyz.shape[0], fp, faces.shape[0], op, dp, _section_ptr(section), *tail),
+                "a3d_pick_mesh_section")
     return out
 
 
+def pick_ray(xyz, origin, direction, radius, out=None, workspace=None):
+    """``a3d_pick_ray``: the first vertex of fp32 [n, 3] along a ray (unit ``direction``) -> int32 [4], see ``read_pick``."""
+    return _pick_ray(xyz, origin, direction, radius, _PLAIN, out, workspace)
+
+
+def pick_mesh(xyz, faces, origin, direction, out=None, workspace=None):
+    """``a3d_pick_mesh``: the first face (int32 [m, 3] into ``xyz``) a ray crosses -> int32 [8], see ``read_pick_mesh``."""
+    return _pick_mesh(xyz, faces, origin, direction, _PLAIN, out, workspace)
+
+
+def pick_ray_section(xyz, origin, direction, radius, section, out=None, workspace=None):
+    """``a3d_pick_ray_section``: ``pick_ray`` among the vertices on the kept side of every plane of the ``lib.Section``."""
+    return _pick_ray(xyz, origin, direction, radius, section, out, workspace)
+
+
+def pick_mesh_section(xyz, faces, origin, direction, section, out=None, workspace=None):
+    """``a3d_pick_mesh_section``: ``pick_mesh`` with the ray cut to the section's interval and its faces culled."""
+    return _pick_mesh(xyz, faces, origin, direction, section, out, workspace)
+
+
+def section_ray(section, origin, direction):
+    """``a3d_section_ray`` (host only, no GPU): ``(t_lo, t_hi, empty)`` -- two ``numpy.float32`` and a bool -- of a ray under
+    the planes of a ``lib.Section``, by the function the kernels call."""
+    (o, op), (d, dp) = _f32p("origin", origin, (3,)), _f32p("direction", direction, (3,))
+    out = np.zeros(3, np.float32)
+    L.check(L.load().a3d_section_ray(_section_ptr(section), op, dp, out.ctypes.data_as(C.POINTER(C.c_float))), "a3d_section_ray")
+    return out[0], out[1], bool(out[2])
+
+
 # ---- the rendered view -----------------------------------------------------------------------------------------------------------
-def _render(xyz, faces, radius, cam, ids, t, u, v, uv, header, workspace, capacity):
+def _render(xyz, faces, radius, cam, ids, t, u, v, uv, header, workspace, capacity, section=_PLAIN):
     dev = _device("xyz", xyz)
     xp = _ptr("xyz", xyz, F32, (None, 3), dev)
     mesh = faces is not None
@@ -162,12 +208,16 @@ def _render(xyz, faces, radius, cam, ids, t, u, v, uv, header, workspace, capaci
         workspace = torch.empty(render_workspace_bytes(m, w, h, capacity), dtype=U8, device=dev)
     _ptr("workspace", workspace, U8, (None,), dev)
     lib = L.load()
-    if mesh:
-        L.check(lib.a3d_render_mesh(xp, n, fp, m, C.byref(cam), C.byref(out), workspace.data_ptr(), workspace.numel(),
-                                    _stream(dev)), "a3d_render_mesh")
+    tail = (C.byref(out), workspace.data_ptr(), workspace.numel(), _stream(dev))
+    if mesh and section is _PLAIN:
+        L.check(lib.a3d_render_mesh(xp, n, fp, m, C.byref(cam), *tail), "a3d_render_mesh")
+    elif mesh:
+        L.check(lib.a3d_render_mesh_section(xp, n, fp, m, C.byref(cam), _section_ptr(section), *tail), "a3d_render_mesh_section")
+    elif section is _PLAIN:
+        L.check(lib.a3d_render_points(xp, n, float(radius), C.byref(cam), *tail), "a3d_render_points")
     else:
-        L.check(lib.a3d_render_points(xp, n, float(radius), C.byref(cam), C.byref(out), workspace.data_ptr(), workspace.numel(),
-                                      _stream(dev)), "a3d_render_points")
+        L.check(lib.a3d_render_points_section(xp, n, float(radius), C.byref(cam), _section_ptr(section), *tail),
+                "a3d_render_points_section")
     return ids, t, u, v, header
 
 
@@ -182,6 +232,19 @@ def render_mesh(xyz, faces, cam, ids=None, t=None, u=None, v=None, uv=True, head
 def render_points(xyz, radius, cam, ids=None, t=None, header=None, workspace=None, capacity=1 << 16):
     """``a3d_render_points``, one attempt: ``(ids, t, header)`` as ``render_mesh``, ids = vertices within ``radius``."""
     ids, t, _, _, header = _render(xyz, None, radius, cam, ids, t, None, None, False, header, workspace, capacity)
+    return ids, t, header
+
+
+def render_mesh_section(xyz, faces, cam, section, ids=None, t=None, u=None, v=None, uv=True, header=None, workspace=None,
+                        capacity=1 << 16):
+    """``a3d_render_mesh_section``: ``render_mesh`` under a ``lib.Section`` (``None``: the C ABI's NULL) -- per pixel what
+    ``pick_mesh_section`` returns for the pixel's ray."""
+    return _render(xyz, faces, None, cam, ids, t, u, v, uv, header, workspace, capacity, section)
+
+
+def render_points_section(xyz, radius, cam, section, ids=None, t=None, header=None, workspace=None, capacity=1 << 16):
+    """``a3d_render_points_section``: ``render_points`` under a ``lib.Section`` -- per pixel ``pick_ray_section``'s vertex."""
+    ids, t, _, _, header = _render(xyz, None, radius, cam, ids, t, None, None, False, header, workspace, capacity, section)
     return ids, t, header
 
 

@@ -934,6 +934,73 @@ int    a3d_render_shade(const int32_t* id_dev, const float* u_dev, const float* 
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Looking INTO a scan: section planes and back-face culling, for the picks and the view together (csrc/session.hip).
+ * The counterpart of what the GUI's user gets from the near plane of Open3D's camera when zooming through a wall; THE RULE
+ * IS THIS LIBRARY'S, and the rule of the view stays true under it: the image is, pixel by pixel, what a click through that
+ * pixel picks under the same section, bit for bit.  All arithmetic below is fp32, every operation rounded on its own (no
+ * fma contraction), in the order written, divisions correctly rounded: a numpy float32 restatement gives the same bits.
+ *
+ * a3d_section: n_planes planes (nx, ny, nz, c), each keeping the side n . p >= c, and a culling mode.  Refused with
+ * A3D_ERR_INVALID before anything else of a call is looked at (no GPU is needed to be refused): n_planes outside 0..8; cull
+ * outside 0..2, or not 0 in a point-cloud call; a used plane with a value that is not finite or with nx*nx + ny*ny + nz*nz
+ * outside [0.5, 2] (normals are meant to be unit vectors; the bound keeps den and the quotients below finite).
+ *
+ * MESH: a section cuts the RAY, not the faces.  Once per ray (o, d):
+ *     t_lo = 0, t_hi = +inf, empty = false
+ *     for k = 0 .. n_planes - 1:
+ *         den = (nx*dx + ny*dy) + nz*dz;   so = (nx*ox + ny*oy) + nz*oz
+ *         den > 0:  t_lo = fmaxf(t_lo, (c - so) / den)
+ *         den < 0:  t_hi = fminf(t_hi, (c - so) / den)
+ *         else   :  if !(so >= c) empty = true           (the ray runs inside a plane's direction: all of it or nothing)
+ * where fmaxf(a, q) stands for q > a ? q : a and fminf(a, q) for q < a ? q : a: a NaN q leaves the bound alone, and of two
+ * zeros the bound's own stays, so that the bits of t_lo and t_hi are defined down to the sign of a zero.
+ * A crossing that a3d_pick_mesh's test accepts counts iff !empty && t >= t_lo && t <= t_hi, both ends inclusive; all else
+ * is a3d_pick_mesh's: the smallest t, then the lower face index; u, v and the hit point of the face found.  The interval is
+ * ONE pair per ray, so two faces that share an edge still classify every ray consistently: a section opens no crack.
+ *
+ * CULLING (meshes).  A face (a, b, c) is FRONT for a ray when its vertices appear counter-clockwise seen from the ray's
+ * origin: g . d < 0 for g = (b - a) x (c - a), the vector a3d_vertex_normals sums.  The crossing test's shear keeps the
+ * winding, so the facing is read off its det = (U + V) + W alone: det > 0 is FRONT, det < 0 is BACK (det == 0 is no hit
+ * anyway).  A3D_CULL_BACK drops the back faces, A3D_CULL_FRONT the front faces.  Scanned surfaces face the scanner: seen
+ * from outside a room, its near walls are back faces.
+ *
+ * POINT CLOUD: a vertex (x, y, z) shows iff (nx*x + ny*y) + nz*z >= c for every plane (a NaN fails); a3d_pick_ray's test
+ * runs on the vertices that show.  This does not depend on the ray.
+ *
+ * The view's binning is not touched: the rule lives in the exact per-pixel test, and a list that was conservative stays so
+ * when fewer primitives pass.  Workspaces are those of the calls without a section.
+ * ------------------------------------------------------------------------------------------ */
+#define A3D_SECTION_MAX_PLANES 8
+#define A3D_CULL_NONE 0
+#define A3D_CULL_BACK 1
+#define A3D_CULL_FRONT 2
+typedef struct a3d_section {
+  int32_t n_planes;            /* 0 .. A3D_SECTION_MAX_PLANES */
+  int32_t cull;                /* A3D_CULL_*; meshes only */
+  float   planes[A3D_SECTION_MAX_PLANES][4];   /* (nx, ny, nz, c): the KEPT side is n . p >= c */
+} a3d_section;                 /* 136 bytes */
+
+/* The four calls above under a section; everything else is theirs.  section NULL = none.  With NULL, or with no plane and
+ * A3D_CULL_NONE, a call runs the code of its counterpart without a section and writes the same bytes. */
+int    a3d_pick_ray_section(const float* xyz_dev, int64_t n, const float* origin, const float* direction, float radius,
+                            const a3d_section* section, a3d_pick_result* result_dev, void* workspace_dev,
+                            size_t workspace_bytes, void* stream);
+int    a3d_pick_mesh_section(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const float* origin,
+                             const float* direction, const a3d_section* section, a3d_pick_mesh_result* result_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+int    a3d_render_mesh_section(const float* xyz_dev, int64_t n, const int32_t* faces_dev, int64_t m, const a3d_camera* camera,
+                               const a3d_section* section, const a3d_render_out* out, void* workspace_dev,
+                               size_t workspace_bytes, void* stream);
+int    a3d_render_points_section(const float* xyz_dev, int64_t n, float radius, const a3d_camera* camera,
+                                 const a3d_section* section, const a3d_render_out* out, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream);
+
+/* Host only, no GPU: the interval of the ray (origin, direction; HOST arrays of 3) under the section's planes, by the
+ * function the kernels call: out3 = t_lo, t_hi, empty as 0 or 1.  The direction is taken as it is.  section NULL: 0, +inf, 0.
+ * A3D_ERR_INVALID for a section the calls refuse or a NULL array. */
+int    a3d_section_ray(const a3d_section* section, const float* origin, const float* direction, float* out3);
+
+/* ------------------------------------------------------------------------------------------
  * Lighting the view (csrc/session.hip): per-vertex normals, a lit colour pass for meshes, a depth-based one for point
  * clouds.  The counterpart of the GUI's compute_vertex_normals and its "defaultLit" material (gui.py:556-557, 135).
  * Open3D's lit material (a sun plus image-based light) is not reproduced: THE RULES BELOW ARE THIS LIBRARY'S, as the pick

@@ -6,6 +6,7 @@ alternating, on one synthetic scene (~80 k voxels, ~250 k full-resolution vertic
 
     python tools/session_bench.py [--voxels 80000] [--reps 60] [--out profiles/session_bench.json]
                                   [--mesh-only | --render-only | --annotate-only | --edit-only]
+                                  [--section-only [--other-lib PATH]]
 
 Every stage is timed twice: with device events around it (what the GPU spent) and with a host clock around a stage that
 ends in a synchronisation (what the caller waits).  Medians over ``--reps`` clicks after a warm-up of 10.  The baseline has
@@ -39,7 +40,14 @@ labels are stripes of five objects with background between them; the markers are
 The EDIT stage (``--edit-only``, a run of its own) times ``a3d_session_edit`` on the click scene, back to back like the
 annotate stage: the relabel with 5, 20 and 255 objects, over the scene's own labels and over labels no object claims (the
 whole table walked for every vertex), the remap of the voxel labels, and both in one call; then whole ``undo()`` /
-``redo()`` calls at 20 clicks on the host clock, synchronised.  The figure to read: the relabel against 8 bytes per vertex."""
+``redo()`` calls at 20 clicks on the host clock, synchronised.  The figure to read: the relabel against 8 bytes per vertex.
+
+The SECTION stage (``--section-only``, a run of its own) times ONE view, the render stage's height field as a mesh at 640 x
+480 from the outside camera, three ways that alternate call by call in one process: ``a3d_render_mesh``;
+``a3d_render_mesh_section`` under ``Section.below(0)`` with back-face culling; and, with ``--other-lib``, ``a3d_render_mesh``
+of another build of the library (the commit before the section: an A/B of two shared objects).  ``--reps`` calls per window,
+5 windows after a warm-up window; per case the median of the window medians and their spread (largest minus smallest).
+The figure to read: the difference between this build and the other one without a section, against the other one's spread."""
 import argparse
 import json
 import os
@@ -394,6 +402,79 @@ def edit_stage(ses, xyz, lab, inst, calls, reps):
     return out
 
 
+def section_stage(ses, n_vertices, reps, other_lib):
+    """One view, with and without a section, next to another build of the library (see the module docstring)."""
+    import ctypes as C
+    from agile3d_amd import lib as L
+    from agile3d_amd.session import Section, camera_from_matrices
+    lib, dev = ses.lib, ses.device
+    xyz, faces, g = height_field(n_vertices, np.random.default_rng(1))
+    xyz_dev, faces_dev = torch.from_numpy(xyz).to(dev), torch.from_numpy(faces).to(dev)
+    n, m, (w, h) = len(xyz), len(faces), (640, 480)
+    mid = 0.5 * g[-1]
+    f = 0.5 * w / np.tan(np.radians(30.0))
+    cam = camera_from_matrices(np.array([[f, 0, w / 2], [0, f, h / 2], [0, 0, 1.0]]),
+                               _look_at(np.array([mid, mid - 1.0, 4.0]), np.array([mid, mid, 0.0])), w, h)
+    libs = {"this build": lib}
+    if other_lib:
+        other = C.CDLL(other_lib)
+        for name in ("a3d_render_mesh", "a3d_render_workspace_bytes", "a3d_last_error"):
+            getattr(other, name).restype, getattr(other, name).argtypes = L.SYMBOLS[name]
+        libs["other build"] = other
+    section = Section.below(0.0, cull="back").struct()
+    header = ses._small[16:20]
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    images = {}
+
+    def images_of(case):
+        if case not in images:
+            images[case] = (torch.empty((h, w), dtype=torch.int32, device=dev),
+                            *(torch.empty((h, w), dtype=torch.float32, device=dev) for _ in range(3)))
+        return images[case]
+
+    def call(case, ws):
+        ids, t, u, v = images_of(case)
+        out = L.RenderOut(ids.data_ptr(), t.data_ptr(), u.data_ptr(), v.data_ptr(), header.data_ptr())
+        args = (xyz_dev.data_ptr(), n, faces_dev.data_ptr(), m, C.byref(cam))
+        tail = (C.byref(out), ws.data_ptr(), ws.numel(), stream)
+        if case == "section":
+            rc = lib.a3d_render_mesh_section(*args, C.byref(section), *tail)
+        else:
+            rc = libs[case].a3d_render_mesh(*args, *tail)
+        assert rc == 0, (case, lib.a3d_last_error())
+        return header.cpu().numpy()
+
+    tiny = torch.empty(lib.a3d_render_workspace_bytes(m, w, h, 1), dtype=torch.uint8, device=dev)
+    pairs = int(call("this build", tiny)[2:4].view(np.int64)[0])
+    ws = torch.empty(lib.a3d_render_workspace_bytes(m, w, h, max(pairs, 1)), dtype=torch.uint8, device=dev)
+    cases = ["this build", "section"] + (["other build"] if other_lib else [])
+    windows = {c: {"device_ms": [], "host_ms": []} for c in cases}
+    for window in range(6):                         # (the first one warms up)
+        tm = Timer(cases)
+        for _ in range(reps):
+            for c in cases:
+                tm.run(c, lambda: call(c, ws))
+        dev_ms, host_ms = tm.medians(0)
+        if window:
+            for c in cases:
+                windows[c]["device_ms"].append(dev_ms[c]), windows[c]["host_ms"].append(host_ms[c])
+    res = {"vertices": n, "faces": m, "view": f"{w}x{h} outside mesh", "pairs": pairs, "reps": reps, "cases": {}}
+    for c in cases:
+        shown = int((images_of(c)[0] >= 0).sum())
+        res["cases"][c] = {k: {"median": float(np.median(v)), "spread": float(max(v) - min(v)), "windows": v}
+                           for k, v in windows[c].items()}
+        res["cases"][c]["pixels_shown"] = shown
+    if other_lib:                                   # without a section the two builds must draw the same image
+        res["same_bytes_as_other_build"] = all(torch.equal(a, b) for a, b in zip(images_of("this build"), images_of("other build")))
+        assert res["same_bytes_as_other_build"]
+    print(f"\n== section: {n} vertices, {m} faces, {w} x {h}, {pairs} pairs; 5 windows of {reps} calls, cases alternating ==")
+    for c in cases:
+        d, hh = res["cases"][c]["device_ms"], res["cases"][c]["host_ms"]
+        print(f"{c:12s} device {d['median']:.4f} ms (spread {d['spread']:.4f})   host {hh['median']:.4f} ms (spread "
+              f"{hh['spread']:.4f})   {res['cases'][c]['pixels_shown']} pixels shown")
+    return res
+
+
 def mesh_pick_stage(ses, n_vertices, reps, warmup, calls):
     """Mesh pick and vertex pick on one tessellated height field of ~n_vertices vertices (see the module docstring)."""
     import ctypes as C
@@ -469,6 +550,8 @@ def main():
     ap.add_argument("--render-only", action="store_true", help="run the render stage alone")
     ap.add_argument("--annotate-only", action="store_true", help="run the annotate stage alone")
     ap.add_argument("--edit-only", action="store_true", help="run the edit stage (a3d_session_edit, undo / redo) alone")
+    ap.add_argument("--section-only", action="store_true", help="run the section stage (one view with and without a section) alone")
+    ap.add_argument("--other-lib", default=None, help="section stage: another build of libagile3d_hip.so to time beside this one")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("session_bench needs the GPU")
@@ -489,7 +572,8 @@ def main():
     original = col.copy()
     centre = xyz.mean(0)
     result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
-    for n_clicks in (() if a.mesh_only or a.render_only or a.annotate_only or a.edit_only else (1, 5, 10, 20)):
+    alone = a.mesh_only or a.render_only or a.annotate_only or a.edit_only or a.section_only
+    for n_clicks in (() if alone else (1, 5, 10, 20)):
         ses.reset()
         objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
         targets = [xyz[rng.choice(np.flatnonzero(lab == inst[o - 1]))] for o in objs]
@@ -595,11 +679,13 @@ def main():
         print(f"whole click, staged (host ms): session {entry['session_click_ms']:.3f}  baseline {entry['baseline_click_ms']:.3f}")
     if a.edit_only:
         result["edit"] = edit_stage(ses, xyz, lab, inst, a.mesh_calls, a.reps)
-    if not (a.render_only or a.annotate_only or a.edit_only):
+    if a.section_only:
+        result["section"] = section_stage(ses, n_full, a.reps, a.other_lib)
+    if not (a.render_only or a.annotate_only or a.edit_only or a.section_only):
         result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
-    if not (a.mesh_only or a.annotate_only or a.edit_only):
+    if not (a.mesh_only or a.annotate_only or a.edit_only or a.section_only):
         result["render"] = render_stage(ses, n_full, a.reps, a.warmup)
-    if not (a.mesh_only or a.render_only or a.edit_only):
+    if not (a.mesh_only or a.render_only or a.edit_only or a.section_only):
         result["annotate"] = annotate_stage(ses, n_full, a.mesh_calls)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
