@@ -128,10 +128,20 @@ __device__ __forceinline__ float quads_sum(float x) {
 }
 
 // ------------------------------------------------------------------------------ posenc
-__global__ void __launch_bounds__(256) k_minmax_partial(const float* __restrict__ xyz, int n, float* part) {
+// Every encoding takes a batch: the rows of sample b = blockIdx.y are [start[b], start[b + 1]) of one matrix, each sample is
+// normalised by ITS OWN min / max, and the whole batch is three launches (two where nothing normalises).  One sample is a
+// batch of one.
+constexpr int kPosBlocks = 16;   // partial-reduction blocks per sample of a batched call; a one-sample call takes up to 256
+struct PosBatch {
+  int ns;
+  int start[64 + 1];
+};
+// min / max of a sample's rows over gridDim.x blocks: part[sample][block][6]
+__global__ void __launch_bounds__(256) k_minmax_partial_b(const float* __restrict__ xyz, const PosBatch pb, float* part) {
   __shared__ float s[6][256];
+  const int b = blockIdx.y, r0 = pb.start[b], r1 = pb.start[b + 1];
   float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+  for (int i = r0 + blockIdx.x * 256 + threadIdx.x; i < r1; i += gridDim.x * 256) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const float v = xyz[3 * (size_t)i + a];
@@ -155,7 +165,7 @@ __global__ void __launch_bounds__(256) k_minmax_partial(const float* __restrict_
     }
     __syncthreads();
   }
-  if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
+  if (threadIdx.x < 6) part[((size_t)b * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = s[threadIdx.x][0];
 }
 __global__ void k_minmax_final(const float* __restrict__ part, int nb, float* minmax) {
   // 6 waves, one per statistic (min x,y,z, max x,y,z) over the nb block partials; blockIdx.x = sample of a batch
@@ -191,49 +201,6 @@ __device__ __forceinline__ void fourier_row(const float* __restrict__ xyz, size_
   sincosf(p, &sn, &cs);   // one argument reduction for both (full precision: the encoding's bar is 1e-4)
   out[i * D + jj] = sn;
   out[i * D + 64 + jj] = cs;
-}
-template <bool NORM>
-__global__ void k_fourier(const float* __restrict__ xyz, int n, const float* __restrict__ gaussB,
-                          const float* __restrict__ minmax, float* out) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= (size_t)n * 64) return;
-  fourier_row<NORM>(xyz, e >> 6, (int)(e & 63), gaussB, minmax, out);
-}
-// ---- the same for every sample of a batch in three launches (rows of sample b = [start[b], start[b+1]) of one matrix)
-constexpr int kPosBlocks = 16;   // partial-reduction blocks per sample
-struct PosBatch {
-  int ns;
-  int start[64 + 1];
-};
-__global__ void __launch_bounds__(256) k_minmax_partial_b(const float* __restrict__ xyz, const PosBatch pb, float* part) {
-  __shared__ float s[6][256];
-  const int b = blockIdx.y, r0 = pb.start[b], r1 = pb.start[b + 1];
-  float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-  for (int i = r0 + blockIdx.x * 256 + threadIdx.x; i < r1; i += kPosBlocks * 256) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float v = xyz[3 * (size_t)i + a];
-      mn[a] = fminf(mn[a], v);
-      mx[a] = fmaxf(mx[a], v);
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    s[a][threadIdx.x] = mn[a];
-    s[3 + a][threadIdx.x] = mx[a];
-  }
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        s[a][threadIdx.x] = fminf(s[a][threadIdx.x], s[a][threadIdx.x + o]);
-        s[3 + a][threadIdx.x] = fmaxf(s[3 + a][threadIdx.x], s[3 + a][threadIdx.x + o]);
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 6) part[((size_t)b * kPosBlocks + blockIdx.x) * 6 + threadIdx.x] = s[threadIdx.x][0];
 }
 template <bool NORM>
 __global__ void k_fourier_b(const float* __restrict__ xyz, const PosBatch pb, const float* __restrict__ gaussB,
@@ -284,12 +251,6 @@ __device__ __forceinline__ void sine_quad(const float* __restrict__ xyz, size_t 
   *reinterpret_cast<float4*>(out + i * D + 4 * c4) = v;
 }
 template <bool NORM>
-__global__ void k_sine(const float* __restrict__ xyz, int n, const float* __restrict__ minmax, float* out) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= (size_t)n * 32) return;
-  sine_quad<NORM>(xyz, e >> 5, (int)(e & 31), minmax, out);
-}
-template <bool NORM>
 __global__ void k_sine_b(const float* __restrict__ xyz, const PosBatch pb, const float* __restrict__ minmax, float* out) {
   const int b = blockIdx.y, r0 = pb.start[b], r1 = pb.start[b + 1];      // blockIdx.x = 8-row block inside sample b
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -318,13 +279,6 @@ __device__ __forceinline__ void legacy_rows(const float* __restrict__ xyz, size_
     const int r = t >> 5, c4 = t & 31;
     *reinterpret_cast<float4*>(out + (r0 + r) * D + 4 * c4) = *reinterpret_cast<const float4*>(&s[r][4 * c4]);
   }
-}
-__global__ void __launch_bounds__(256) k_legacy(const float* __restrict__ xyz, int n, const float* __restrict__ inv_freq,
-                                                float* out) {
-  __shared__ __align__(16) float s[kLegRows][kLegLd];
-  const size_t r0 = (size_t)blockIdx.x * kLegRows;
-  if (r0 >= (size_t)n) return;
-  legacy_rows(xyz, r0, (int)((size_t)n - r0 < (size_t)kLegRows ? (size_t)n - r0 : (size_t)kLegRows), inv_freq, out, s);
 }
 __global__ void __launch_bounds__(256) k_legacy_b(const float* __restrict__ xyz, const PosBatch pb,
                                                   const float* __restrict__ inv_freq, float* out) {
@@ -2595,148 +2549,47 @@ __global__ void __launch_bounds__(512) k_query_block(const QuerySample* __restri
 using namespace a3d;
 
 // ------------------------------------------------------------------------------ C ABI
-extern "C" int a3d_posenc_fourier(const float* xyz_dev, int64_t n, const float* gauss_B_dev, float* minmax_dev,
-                                  float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  if (!xyz_dev || !gauss_B_dev || !minmax_dev || !out_dev || n <= 0 || n > (int64_t)1 << 30) {
-    set_error("a3d_posenc_fourier: bad arguments");
-    return A3D_ERR_INVALID;
-  }
-  const int nb = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
-  if (!workspace_dev || workspace_bytes < (size_t)nb * 6 * 4) {
-    set_error("a3d_posenc_fourier: workspace needs >= %zu bytes", (size_t)256 * 6 * 4);
-    return A3D_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)workspace_dev;
-  ProfScope ps(st, A3D_PROF_POSENC, 0, 0, 3, 128, (int)n);
-  k_minmax_partial<<<nb, 256, 0, st>>>(xyz_dev, (int)n, part);
-  k_minmax_final<<<1, 384, 0, st>>>(part, nb, minmax_dev);
-  const size_t total = (size_t)n * 64;
-  k_fourier<true><<<(unsigned)((total + 255) / 256), 256, 0, st>>>(xyz_dev, (int)n, gauss_B_dev, minmax_dev, out_dev);
-  A3D_LAUNCH_CHECK();
-  return A3D_OK;
-}
-
-extern "C" size_t a3d_posenc_batch_workspace_bytes(int n_samples) {
-  return n_samples >= 1 && n_samples <= 64 ? (size_t)n_samples * kPosBlocks * 6 * 4 : 0;
-}
-extern "C" int a3d_posenc_fourier_batch(const float* xyz_dev, const int64_t* starts_host, int n_samples,
-                                        const float* gauss_B_dev, float* minmax_dev, float* out_dev, void* workspace_dev,
-                                        size_t workspace_bytes, void* stream) {
-  if (!xyz_dev || !starts_host || !gauss_B_dev || !minmax_dev || !out_dev || n_samples < 1 || n_samples > 64) {
-    set_error("a3d_posenc_fourier_batch: bad arguments (1..64 samples)");
-    return A3D_ERR_INVALID;
-  }
-  PosBatch pb;
-  pb.ns = n_samples;
-  for (int b = 0; b <= n_samples; ++b) {
-    if (starts_host[b] < 0 || starts_host[b] > ((int64_t)1 << 30) || (b && starts_host[b] <= starts_host[b - 1])) {
-      set_error("a3d_posenc_fourier_batch: sample %d has no rows (starts must ascend)", b - 1);
-      return A3D_ERR_INVALID;
-    }
-    pb.start[b] = (int)starts_host[b];
-  }
-  if (!workspace_dev || workspace_bytes < a3d_posenc_batch_workspace_bytes(n_samples)) {
-    set_error("a3d_posenc_fourier_batch: workspace needs >= %zu bytes", a3d_posenc_batch_workspace_bytes(n_samples));
-    return A3D_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)workspace_dev;
-  const int n_total = pb.start[n_samples];
-  ProfScope ps(st, A3D_PROF_POSENC, 0, 0, 3, 128, n_total);
-  k_minmax_partial_b<<<dim3(kPosBlocks, n_samples), 256, 0, st>>>(xyz_dev, pb, part);
-  k_minmax_final<<<n_samples, 384, 0, st>>>(part, kPosBlocks, minmax_dev);
-  int n_max = 0;
-  for (int b = 0; b < n_samples; ++b) n_max = std::max(n_max, pb.start[b + 1] - pb.start[b]);
-  k_fourier_b<true><<<dim3((unsigned)(((size_t)n_max * 64 + 255) / 256), n_samples), 256, 0, st>>>(xyz_dev, pb, gauss_B_dev,
-                                                                                                  minmax_dev, out_dev);
-  A3D_LAUNCH_CHECK();
-  return A3D_OK;
-}
-
-// every encoding of the reference behind one pair of entry points (a3d_posenc_fourier[_batch] above = kind FOURIER, normalize 1)
-static int posenc_check(const char* who, int kind, int normalize, const float* table_dev, float* minmax_dev, float* out_dev,
-                        bool* use_minmax) {
+// Every encoding of the reference, one sample or a batch, behind one host path: validation, the per-sample min / max where
+// the encoding normalises (part_blocks partial blocks per sample, then k_minmax_final) and ONE launch of the row kernel of
+// (kind, normalize).  who: the entry point the caller called.
+static int posenc_run(const char* who, int kind, int normalize, const float* xyz_dev, const int64_t* starts, int n_samples,
+                      int part_blocks, const float* table_dev, float* minmax_dev, float* out_dev, void* workspace_dev,
+                      size_t workspace_bytes, void* stream) {
   if (kind != A3D_POSENC_FOURIER && kind != A3D_POSENC_SINE && kind != A3D_POSENC_LEGACY) {
     set_error("%s: unknown encoding kind %d", who, kind);
     return A3D_ERR_INVALID;
   }
-  *use_minmax = normalize && kind != A3D_POSENC_LEGACY;
-  if ((kind != A3D_POSENC_SINE && !table_dev) || (*use_minmax && !minmax_dev) || !out_dev) {
+  const bool mm = normalize && kind != A3D_POSENC_LEGACY;
+  if ((kind != A3D_POSENC_SINE && !table_dev) || (mm && !minmax_dev) || !out_dev) {
     set_error("%s: bad arguments (table_dev: gauss_B / inv_freq; minmax_dev where the encoding normalises)", who);
     return A3D_ERR_INVALID;
   }
-  if (((uintptr_t)out_dev & 15) != 0) {
-    set_error("%s: out_dev must be 16-byte aligned", who);
-    return A3D_ERR_INVALID;
-  }
-  return A3D_OK;
-}
-
-extern "C" int a3d_posenc(int kind, int normalize, const float* xyz_dev, int64_t n, const float* table_dev, float* minmax_dev,
-                          float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  bool mm;
-  if (int rc = posenc_check("a3d_posenc", kind, normalize, table_dev, minmax_dev, out_dev, &mm)) return rc;
-  if (!xyz_dev || n <= 0 || n > (int64_t)1 << 30) {
-    set_error("a3d_posenc: bad arguments");
-    return A3D_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(st, A3D_PROF_POSENC, 0, 0, 3, 128, (int)n);
-  if (mm) {
-    const int nb = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
-    if (!workspace_dev || workspace_bytes < (size_t)nb * 6 * 4) {
-      set_error("a3d_posenc: workspace needs >= %zu bytes", (size_t)256 * 6 * 4);
-      return A3D_ERR_WORKSPACE;
-    }
-    k_minmax_partial<<<nb, 256, 0, st>>>(xyz_dev, (int)n, (float*)workspace_dev);
-    k_minmax_final<<<1, 384, 0, st>>>((const float*)workspace_dev, nb, minmax_dev);
-  }
-  if (kind == A3D_POSENC_FOURIER) {
-    const unsigned g = (unsigned)(((size_t)n * 64 + 255) / 256);
-    if (mm) k_fourier<true><<<g, 256, 0, st>>>(xyz_dev, (int)n, table_dev, minmax_dev, out_dev);
-    else k_fourier<false><<<g, 256, 0, st>>>(xyz_dev, (int)n, table_dev, nullptr, out_dev);
-  } else if (kind == A3D_POSENC_SINE) {
-    const unsigned g = (unsigned)(((size_t)n * 32 + 255) / 256);
-    if (mm) k_sine<true><<<g, 256, 0, st>>>(xyz_dev, (int)n, minmax_dev, out_dev);
-    else k_sine<false><<<g, 256, 0, st>>>(xyz_dev, (int)n, nullptr, out_dev);
-  } else {
-    k_legacy<<<(unsigned)((n + kLegRows - 1) / kLegRows), 256, 0, st>>>(xyz_dev, (int)n, table_dev, out_dev);
-  }
-  A3D_LAUNCH_CHECK();
-  return A3D_OK;
-}
-
-extern "C" int a3d_posenc_batch(int kind, int normalize, const float* xyz_dev, const int64_t* starts_host, int n_samples,
-                                const float* table_dev, float* minmax_dev, float* out_dev, void* workspace_dev,
-                                size_t workspace_bytes, void* stream) {
-  bool mm;
-  if (int rc = posenc_check("a3d_posenc_batch", kind, normalize, table_dev, minmax_dev, out_dev, &mm)) return rc;
-  if (!xyz_dev || !starts_host || n_samples < 1 || n_samples > 64) {
-    set_error("a3d_posenc_batch: bad arguments (1..64 samples)");
+  if (!xyz_dev || !starts || n_samples < 1 || n_samples > 64) {
+    set_error("%s: bad arguments (1..64 samples)", who);
     return A3D_ERR_INVALID;
   }
   PosBatch pb;
   pb.ns = n_samples;
+  int n_max = 0;
   for (int b = 0; b <= n_samples; ++b) {
-    if (starts_host[b] < 0 || starts_host[b] > ((int64_t)1 << 30) || (b && starts_host[b] <= starts_host[b - 1])) {
-      set_error("a3d_posenc_batch: sample %d has no rows (starts must ascend)", b - 1);
+    if (starts[b] < 0 || starts[b] > ((int64_t)1 << 30) || (b && starts[b] <= starts[b - 1])) {
+      set_error("%s: sample %d has no rows (1..2^30 rows in all, starts must ascend)", who, b - 1);
       return A3D_ERR_INVALID;
     }
-    pb.start[b] = (int)starts_host[b];
+    pb.start[b] = (int)starts[b];
+    if (b) n_max = std::max(n_max, pb.start[b] - pb.start[b - 1]);
+  }
+  const size_t part_bytes = (size_t)n_samples * part_blocks * 6 * 4;
+  if (mm && (!workspace_dev || workspace_bytes < part_bytes)) {
+    set_error("%s: workspace needs >= %zu bytes", who, part_bytes);
+    return A3D_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, A3D_PROF_POSENC, 0, 0, 3, 128, pb.start[n_samples]);
   if (mm) {
-    if (!workspace_dev || workspace_bytes < a3d_posenc_batch_workspace_bytes(n_samples)) {
-      set_error("a3d_posenc_batch: workspace needs >= %zu bytes", a3d_posenc_batch_workspace_bytes(n_samples));
-      return A3D_ERR_WORKSPACE;
-    }
-    k_minmax_partial_b<<<dim3(kPosBlocks, n_samples), 256, 0, st>>>(xyz_dev, pb, (float*)workspace_dev);
-    k_minmax_final<<<n_samples, 384, 0, st>>>((const float*)workspace_dev, kPosBlocks, minmax_dev);
+    k_minmax_partial_b<<<dim3(part_blocks, n_samples), 256, 0, st>>>(xyz_dev, pb, (float*)workspace_dev);
+    k_minmax_final<<<n_samples, 384, 0, st>>>((const float*)workspace_dev, part_blocks, minmax_dev);
   }
-  int n_max = 0;
-  for (int b = 0; b < n_samples; ++b) n_max = std::max(n_max, pb.start[b + 1] - pb.start[b]);
   if (kind == A3D_POSENC_FOURIER) {
     const dim3 g((unsigned)(((size_t)n_max * 64 + 255) / 256), n_samples);
     if (mm) k_fourier_b<true><<<g, 256, 0, st>>>(xyz_dev, pb, table_dev, minmax_dev, out_dev);
@@ -2750,6 +2603,55 @@ extern "C" int a3d_posenc_batch(int kind, int normalize, const float* xyz_dev, c
   }
   A3D_LAUNCH_CHECK();
   return A3D_OK;
+}
+// one sample = a batch of one, reduced over a grid of its own: a block per 256 rows, 256 at the most (an 80 k-point scene
+// keeps the wide reduction it always had; the batched calls spend kPosBlocks per sample)
+static int posenc_one(const char* who, int kind, int normalize, const float* xyz_dev, int64_t n, const float* table_dev,
+                      float* minmax_dev, float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (n <= 0 || n > (int64_t)1 << 30) {
+    set_error("%s: bad arguments", who);
+    return A3D_ERR_INVALID;
+  }
+  const int64_t starts[2] = {0, n};
+  const int nb = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
+  return posenc_run(who, kind, normalize, xyz_dev, starts, 1, nb, table_dev, minmax_dev, out_dev, workspace_dev,
+                    workspace_bytes, stream);
+}
+
+extern "C" size_t a3d_posenc_batch_workspace_bytes(int n_samples) {
+  return n_samples >= 1 && n_samples <= 64 ? (size_t)n_samples * kPosBlocks * 6 * 4 : 0;
+}
+// a3d_posenc[_batch] ask for 16-byte aligned rows (the sine and legacy kernels store 16 bytes at a time), whatever the kind;
+// a3d_posenc_fourier[_batch] never did
+static int posenc_aligned(const char* who, const float* out_dev) {
+  if (((uintptr_t)out_dev & 15) == 0) return A3D_OK;
+  set_error("%s: out_dev must be 16-byte aligned", who);
+  return A3D_ERR_INVALID;
+}
+extern "C" int a3d_posenc(int kind, int normalize, const float* xyz_dev, int64_t n, const float* table_dev, float* minmax_dev,
+                          float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (int rc = posenc_aligned("a3d_posenc", out_dev)) return rc;
+  return posenc_one("a3d_posenc", kind, normalize, xyz_dev, n, table_dev, minmax_dev, out_dev, workspace_dev,
+                    workspace_bytes, stream);
+}
+extern "C" int a3d_posenc_batch(int kind, int normalize, const float* xyz_dev, const int64_t* starts_host, int n_samples,
+                                const float* table_dev, float* minmax_dev, float* out_dev, void* workspace_dev,
+                                size_t workspace_bytes, void* stream) {
+  if (int rc = posenc_aligned("a3d_posenc_batch", out_dev)) return rc;
+  return posenc_run("a3d_posenc_batch", kind, normalize, xyz_dev, starts_host, n_samples, kPosBlocks, table_dev,
+                    minmax_dev, out_dev, workspace_dev, workspace_bytes, stream);
+}
+// the default model's encoding under its first names: (FOURIER, normalize = 1)
+extern "C" int a3d_posenc_fourier(const float* xyz_dev, int64_t n, const float* gauss_B_dev, float* minmax_dev,
+                                  float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return posenc_one("a3d_posenc_fourier", A3D_POSENC_FOURIER, 1, xyz_dev, n, gauss_B_dev, minmax_dev, out_dev,
+                    workspace_dev, workspace_bytes, stream);
+}
+extern "C" int a3d_posenc_fourier_batch(const float* xyz_dev, const int64_t* starts_host, int n_samples,
+                                        const float* gauss_B_dev, float* minmax_dev, float* out_dev, void* workspace_dev,
+                                        size_t workspace_bytes, void* stream) {
+  return posenc_run("a3d_posenc_fourier_batch", A3D_POSENC_FOURIER, 1, xyz_dev, starts_host, n_samples, kPosBlocks,
+                    gauss_B_dev, minmax_dev, out_dev, workspace_dev, workspace_bytes, stream);
 }
 
 static int check_weights(const a3d_decoder_weights* w) {
@@ -2858,22 +2760,18 @@ extern "C" int a3d_decoder_pack_query_weights(const a3d_decoder_weights* w, int3
   return A3D_OK;
 }
 
-static bool fused_c2s() {   // A3D_FUSED_C2S=0 keeps the separate K / V GEMMs + k_c2s_attn (A/B switch)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("A3D_FUSED_C2S");
-    v = e ? atoi(e) : 1;
-  }
-  return v != 0;
+// the A/B switches of the environment: each is read once per process, into the function-local static of its reader
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
-
+static bool fused_c2s() {   // A3D_FUSED_C2S=0 keeps the separate K / V GEMMs + k_c2s_attn (A/B switch)
+  static const bool v = env_int("A3D_FUSED_C2S", 1) != 0;
+  return v;
+}
 static bool fused_wide() {   // A3D_FUSED_WIDE=0 (or A3D_FUSED_C2S=0) keeps the unfused kernels above 64 queries (A/B switch, tests)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("A3D_FUSED_WIDE");
-    v = e ? atoi(e) : 1;
-  }
-  return v != 0 && fused_c2s();
+  static const bool v = env_int("A3D_FUSED_WIDE", 1) != 0;
+  return v && fused_c2s();
 }
 
 // The wide tier's kernels take a sample's tile count from the table, so they serve fewer than 65 queries too (under the
@@ -2882,21 +2780,29 @@ static bool fused_wide() {   // A3D_FUSED_WIDE=0 (or A3D_FUSED_C2S=0) keeps the 
 // then share the launch group of a call's larger ones.  Up to 32 queries k_s2c_out (one kernel for the whole scene-to-click
 // half) stays ahead.  A3D_WIDE_FROM=<queries> moves the edge (65: the round's first protocol; A/B, tests).
 static bool fused_s2o() {   // A3D_FUSED_S2O=0: k_s2c_w + k_out_w for up to five query tiles too (A/B, tests)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("A3D_FUSED_S2O");
-    v = e ? atoi(e) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("A3D_FUSED_S2O", 1) != 0;
+  return v;
 }
 static int wide_from() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("A3D_WIDE_FROM");
-    v = e ? atoi(e) : 33;
-    v = v < 17 ? 17 : v;
-  }
+  static const int v = std::max(17, env_int("A3D_WIDE_FROM", 33));
   return v;
+}
+// The dynamic-LDS limit of a kernel is raised where the kernel is NAMED for launch -- big_lds<k_x<..>>()<<<..>>>(..) --
+// once per instantiation and process: an instantiation cannot be launched without it.  (A3D_ALLOW_LDS of common.h, which
+// would report every failure under the name "K"; here the function's own name carries the instantiation.)  The raise is
+// lazy: the first pass of a process that reaches a new instantiation -- a new query-count tier, a first cached layer --
+// issues one hipFuncSetAttribute there, later passes none.  Run every tier once before capturing these launches in a graph.
+template <auto K>
+static auto big_lds() {
+  static const bool raised = [] {
+    if (hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+      (void)hipGetLastError();   // not the next launch check's to report
+      fprintf(stderr, "agile3d_hip: cannot raise the dynamic LDS limit to 160 KB: %s\n", __PRETTY_FUNCTION__);
+    }
+    return true;
+  }();
+  (void)raised;
+  return K;
 }
 
 // one batch sample on the host: validated query list, workspace layout and the views into its workspace
@@ -3027,6 +2933,44 @@ static int upload_tables(Prepared* P, int ns, bool wg_per_group, bool part_per_w
   return A3D_OK;
 }
 
+// ---- what run_decoder and run_decoder_wide share
+// the point rows layer l reads and writes: layer 0 reads the backbone's features, the layers alternate between bufC and bufD
+static const float* layer_src(const Prepared& p, int l) { return l == 0 ? p.feats : ((l - 1) & 1) ? p.bufD : p.bufC; }
+static float* layer_dst(const Prepared& p, int l) { return (l & 1) ? p.bufD : p.bufC; }
+// totals of a launch group
+struct GroupTotals {
+  int64_t n_total = 0;
+  int Kmax = 0, nq_max = 0, nq_min = A3D_MAX_QUERIES;
+};
+static GroupTotals group_totals(const Prepared* P, int ns) {
+  GroupTotals t;
+  for (int si = 0; si < ns; ++si) {
+    t.n_total += P[si].n;
+    t.Kmax = std::max(t.Kmax, P[si].hm.K);
+    t.nq_max = std::max(t.nq_max, P[si].hm.nq);
+    t.nq_min = std::min(t.nq_min, P[si].hm.nq);
+  }
+  return t;
+}
+// The first layer runs on the scene's cached keys / values / scene-to-click queries (a3d_decoder_sample::kv0_dev) when EVERY
+// sample of the group has a usable cache: K = (feats + pos) Wk^T + bk, V = feats Wv^T + bv and Q = (feats + pos) Wq^T + bq
+// (agile3d.py:305-312) depend on the scene only, the interactive loop runs ~100 passes on it
+static bool all_cached(const Prepared* P, int ns) {
+  for (int si = 0; si < ns; ++si)
+    if (!P[si].kv0 || P[si].kv0_state == 0) return false;
+  return true;
+}
+// kv0_state 1: this pass fills the sample's cache [3][n][128] from the first layer's weights
+static int fill_kv0(const a3d_decoder_layer& LW, const Prepared& p, hipStream_t st) {
+  if (p.kv0_state != 1) return A3D_OK;
+  const size_t blk = (size_t)p.n * D;
+  int rc = a3d_linear(p.feats, D, p.posenc, D, p.n, D, D, LW.c2s_wk_packed, nullptr, LW.c2s_in_b + D, nullptr, 0, 0, p.kv0, D, nullptr, 0, st);
+  if (rc) return rc;
+  rc = a3d_linear(p.feats, D, nullptr, 0, p.n, D, D, LW.c2s_wv_packed, nullptr, LW.c2s_in_b + 2 * D, nullptr, 0, 0, p.kv0 + blk, D, nullptr, 0, st);
+  if (rc) return rc;
+  return a3d_linear(p.feats, D, p.posenc, D, p.n, D, D, LW.s2c_wq_packed, nullptr, LW.s2c_in_b, nullptr, 0, 0, p.kv0 + 2 * blk, D, nullptr, 0, st);
+}
+
 // the query side of decoder layer l for every sample of a call: merge of the click-to-scene partials, then one workgroup
 // (or chain of 64-query blocks, QT = 4) per sample
 template <int QT>
@@ -3057,12 +3001,7 @@ static int launch_query_side(const a3d_decoder_weights* w, int l, QuerySample* q
     const size_t ql_lds = (size_t)4 * QP * kQLD * 4 + 16;   // four [QP][132] tiles + the word of block_any
     // FFN helper workgroups next to a block's workgroup (A3D_QL_HELPERS = total workgroups per block, 1 = none: the
     // switch the tests use to compare the hand-off with the single-workgroup chain)
-    static int nh_env = -1;
-    if (nh_env < 0) {
-      const char* e = getenv("A3D_QL_HELPERS");
-      nh_env = e ? atoi(e) : kQlMaxHelpers;
-      nh_env = nh_env < 1 ? 1 : nh_env > kQlMaxHelpers ? kQlMaxHelpers : nh_env;
-    }
+    static const int nh_env = std::min(std::max(env_int("A3D_QL_HELPERS", kQlMaxHelpers), 1), kQlMaxHelpers);
     if (!(QW.qpack && QW.mpack && (QW.next_qpack || !QW.next_c2s_in_wt))) {
       set_error("a3d_decoder_forward: the decoder weights carry no query-side packs (a3d_decoder_pack_query_weights "
                 "fills a3d_decoder_layer::query_pack and a3d_decoder_weights::mask_pack)");
@@ -3070,10 +3009,10 @@ static int launch_query_side(const a3d_decoder_weights* w, int l, QuerySample* q
     }
     const size_t qb_lds = ql_lds + (size_t)kQVec * 4;
     if (nblk == 1) {
-      k_query_block<QT, 0><<<dim3(nh_env, 1, ns), 512, qb_lds, st>>>(qs_dev, QW);
+      big_lds<k_query_block<QT, 0>>()<<<dim3(nh_env, 1, ns), 512, qb_lds, st>>>(qs_dev, QW);
     } else if constexpr (QT == 4 || QT == 2) {   // blocks of 64 rows (unfused path) or of 32 (wide tier: more, shorter chains)
-      k_query_block<QT, 1><<<dim3(1, nblk, ns), 512, qb_lds, st>>>(qs_dev, QW);
-      k_query_block<QT, 2><<<dim3(nh_env, nblk, ns), 512, qb_lds, st>>>(qs_dev, QW);
+      big_lds<k_query_block<QT, 1>>()<<<dim3(1, nblk, ns), 512, qb_lds, st>>>(qs_dev, QW);
+      big_lds<k_query_block<QT, 2>>()<<<dim3(nh_env, nblk, ns), 512, qb_lds, st>>>(qs_dev, QW);
     }
   }
   A3D_LAUNCH_CHECK();
@@ -3086,62 +3025,10 @@ template <int QT>
 static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStream_t st) {
   constexpr int QP = QT * 16;
   const int nblk = P[0].L.qp / QP;          // query blocks (1 unless nq > 64)
-  {
-    static bool big = false;
-    if (!big) {
-      big = true;
-      const int big_lds = 160 * 1024;
-      A3D_ALLOW_LDS(big_lds, k_query_block<1, 0>);
-      A3D_ALLOW_LDS(big_lds, k_query_block<2, 0>);
-      A3D_ALLOW_LDS(big_lds, k_query_block<3, 0>);
-      A3D_ALLOW_LDS(big_lds, k_query_block<4, 0>);
-      A3D_ALLOW_LDS(big_lds, k_query_block<4, 1>);
-      A3D_ALLOW_LDS(big_lds, k_query_block<4, 2>);
-      A3D_ALLOW_LDS(big_lds, k_s2c_attn_wide<4>);
-      A3D_ALLOW_LDS(big_lds, k_q_s2c<1>);
-      A3D_ALLOW_LDS(big_lds, k_q_s2c<2>);
-      A3D_ALLOW_LDS(big_lds, k_q_s2c<3>);
-      A3D_ALLOW_LDS(big_lds, k_q_s2c<4>);
-      A3D_ALLOW_LDS(big_lds, k_out_ln_mask<1>);
-      A3D_ALLOW_LDS(big_lds, k_out_ln_mask<2>);
-      A3D_ALLOW_LDS(big_lds, k_out_ln_mask<3>);
-      A3D_ALLOW_LDS(big_lds, k_out_ln_mask<4>);
-      A3D_ALLOW_LDS(big_lds, k_s2c_out<1, 8>);
-      A3D_ALLOW_LDS(big_lds, k_s2c_out<2, 8>);
-      A3D_ALLOW_LDS(big_lds, k_s2c_out<1, 12>);
-      A3D_ALLOW_LDS(big_lds, k_s2c_out<2, 12>);
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 8, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<1, 12, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<1, 8, true>));
-      A3D_ALLOW_LDS(big_lds, (k_q_s2c<1, true>));
-      A3D_ALLOW_LDS(big_lds, (k_q_s2c<2, true>));
-      A3D_ALLOW_LDS(big_lds, (k_q_s2c<3, true>));
-      A3D_ALLOW_LDS(big_lds, (k_q_s2c<4, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<1, 12, false, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, false, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<1, 12, true, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, true, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, false, false, true>));
-      A3D_ALLOW_LDS(big_lds, (k_s2c_out<2, 12, false, true, true>));
-      A3D_ALLOW_LDS(big_lds, (k_kv_c2s<2, true>));
-      A3D_ALLOW_LDS(big_lds, k_kv_c2s<1>);
-      A3D_ALLOW_LDS(big_lds, k_kv_c2s<2>);
-      A3D_ALLOW_LDS(big_lds, k_kv_c2s<3>);
-      A3D_ALLOW_LDS(big_lds, k_kv_c2s<4>);
-      A3D_ALLOW_LDS(big_lds, k_ln_mask<4>);
-    }
-  }
   const int n_counts = A3D_MAX_DEC_LAYERS * (A3D_MAX_QUERIES + 1);
-  int64_t n_total = 0;
-  int Kmax = 0, nq_max = 0, nq_min = A3D_MAX_QUERIES;
-  for (int si = 0; si < ns; ++si) {
-    Prepared& p = P[si];
-    n_total += p.n;
-    Kmax = p.hm.K > Kmax ? p.hm.K : Kmax;
-    nq_max = p.hm.nq > nq_max ? p.hm.nq : nq_max;
-    nq_min = p.hm.nq < nq_min ? p.hm.nq : nq_min;
-  }
+  const GroupTotals tot = group_totals(P, ns);
+  const int64_t n_total = tot.n_total;
+  const int Kmax = tot.Kmax, nq_max = tot.nq_max, nq_min = tot.nq_min;
   // every sample of the launch has 17 .. 20 queries: the second query tile is at most four queries wide and runs on the
   // 4x4x1 builds of k_kv_c2s / k_s2c_out
   const bool leftover = QT == 2 && nq_min >= 17 && nq_max <= 20;
@@ -3171,11 +3058,7 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
   const bool s2c_kg = (size_t)128 * 1024 + s2c_keys + s2c_rest + staging12 > 160 * 1024;
   const size_t s2c_out_lds = (size_t)128 * 1024 + (s2c_kg ? 0 : s2c_keys) + s2c_rest;
   const size_t s2c_out_lds12 = s2c_out_lds + staging12;
-  static int fused_s2c_env = -1;
-  if (fused_s2c_env < 0) {
-    const char* e = getenv("A3D_FUSED_S2C");
-    fused_s2c_env = e ? atoi(e) : 1;
-  }
+  static const bool fused_s2c_env = env_int("A3D_FUSED_S2C", 1) != 0;
   const bool fuse_all = fuse_out && fused_s2c_env && QT <= 2 && s2c_out_lds <= 160 * 1024;
   DecTables T;
   {
@@ -3194,30 +3077,18 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
   for (int l = 0; l < w->n_layers; ++l) {
     const a3d_decoder_layer& LW = w->layers[l];
     int rc;
-    // ---- click-to-scene
-    // first layer on the scene's cached keys / values (a3d_decoder_sample::kv0_dev): K = (feats + pos) Wk^T + bk and
-    // V = feats Wv^T + bv depend on the scene only, the interactive loop runs ~100 passes on it
-    bool cached0 = l == 0;
-    for (int si = 0; si < ns && cached0; ++si) cached0 = P[si].kv0 != nullptr && P[si].kv0_state != 0;
+    // ---- click-to-scene; the first layer on the scene's cached keys / values when every sample has them
+    const bool cached0 = l == 0 && all_cached(P, ns);
     const bool qc0 = cached0;   // the scene-to-click half of this layer reads its queries from the cache too
     if (cached0) {
       for (int si = 0; si < ns; ++si) {
         Prepared& p = P[si];
-        float* K0 = p.kv0;
-        float* V0 = p.kv0 + (size_t)p.n * D;
-        if (p.kv0_state == 1) {
-          rc = a3d_linear(p.feats, D, p.posenc, D, p.n, D, D, LW.c2s_wk_packed, nullptr, LW.c2s_in_b + D, nullptr, 0, 0, K0, D, nullptr, 0, st);
-          if (rc) return rc;
-          rc = a3d_linear(p.feats, D, nullptr, 0, p.n, D, D, LW.c2s_wv_packed, nullptr, LW.c2s_in_b + 2 * D, nullptr, 0, 0, V0, D, nullptr, 0, st);
-          if (rc) return rc;
-          // ... and the scene-to-click QUERIES of the first layer, (feats + pos) Wq^T + bq: click-independent too (agile3d.py:305-312)
-          rc = a3d_linear(p.feats, D, p.posenc, D, p.n, D, D, LW.s2c_wq_packed, nullptr, LW.s2c_in_b, nullptr, 0, 0,
-                          p.kv0 + (size_t)2 * p.n * D, D, nullptr, 0, st);
-          if (rc) return rc;
-        }
+        rc = fill_kv0(LW, p, st);
+        if (rc) return rc;
         if (nblk == 1) continue;              // one query block: all samples in ONE launch below
         ProfScope ps(st, A3D_PROF_C2S, 0, 0, 0, 0, p.n);
-        k_c2s_attn<QT><<<dim3(p.L.nchunk, nblk), 512, 0, st>>>(K0, V0, p.n, p.B.qproj, p.meta->obj, nullptr, nullptr, p.part, p.L.qp);
+        k_c2s_attn<QT><<<dim3(p.L.nchunk, nblk), 512, 0, st>>>(p.kv0, p.kv0 + (size_t)p.n * D, p.n, p.B.qproj, p.meta->obj, nullptr, nullptr,
+                                                              p.part, p.L.qp);
         A3D_LAUNCH_CHECK();
       }
       if (nblk == 1) {
@@ -3231,17 +3102,13 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
       // K / V projections fused in (K, V never reach HBM), all samples in one launch
       ProfScope ps(st, A3D_PROF_C2S, 0, 0, 0, 0, (int)n_total);
       const size_t c2s_lds = (size_t)128 * 1024 + (QT == 4 ? (size_t)QP * 128 * 4 : ((size_t)QP * 132 + 2 * D) * 4);
-      if (QT == 2 && leftover)
-        k_kv_c2s<2, true><<<grid, 512, c2s_lds, st>>>(samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D,
-                                                      LW.c2s_in_b + 2 * D);
-      else
-        k_kv_c2s<QT><<<grid, 512, c2s_lds, st>>>(samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D,
-                                                 LW.c2s_in_b + 2 * D);
+      (leftover ? big_lds<k_kv_c2s<2, true>>() : big_lds<k_kv_c2s<QT>>())<<<grid, 512, c2s_lds, st>>>(
+          samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D, LW.c2s_in_b + 2 * D);
       A3D_LAUNCH_CHECK();
     } else {
       for (int si = 0; si < ns; ++si) {
         Prepared& p = P[si];
-        const float* src = l == 0 ? p.feats : (((l - 1) & 1) ? p.bufD : p.bufC);
+        const float* src = layer_src(p, l);
         const int* prev_counts = l > 0 ? p.counts + (size_t)(l - 1) * (A3D_MAX_QUERIES + 1) : nullptr;
         // K = (src + pos) Wk^T + bk, V = src Wv^T + bv   (attention_block.py:88-94)
         rc = a3d_linear(src, D, p.posenc, D, p.n, D, D, LW.c2s_wk_packed, nullptr, LW.c2s_in_b + D, nullptr, 0, 0, p.bufA, D, nullptr, 0, st);
@@ -3263,43 +3130,34 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
       ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, (int)n_total);
       const int last = l + 1 == w->n_layers;   // nothing reads the last layer's rows, label bytes and histogram
       if constexpr (QT <= 2) {
-        if (leftover && qc0 && !s2c_kg && s2c_out_lds12 <= 160 * 1024)
-          k_s2c_out<2, 12, false, true, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                               LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
-        else if (leftover && !qc0 && !s2c_kg && s2c_out_lds12 <= 160 * 1024)
-          k_s2c_out<2, 12, false, false, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                                LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
-        else if (qc0 && s2c_kg && s2c_out_lds12 <= 160 * 1024)
-          k_s2c_out<QT, 12, true, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                         LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
-        else if (qc0 && !s2c_kg && s2c_out_lds12 <= 160 * 1024)
-          k_s2c_out<QT, 12, false, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                          LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
-        else if (s2c_kg && s2c_out_lds12 <= 160 * 1024)
-          k_s2c_out<QT, 12, true><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                   LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
-        else if (s2c_kg)
-          k_s2c_out<QT, 8, true><<<grid, 512, s2c_out_lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                                LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
-        else if (s2c_out_lds12 <= 160 * 1024)   // twelve waves (three per SIMD) when their logits staging fits, else eight
-          k_s2c_out<QT, 12><<<grid, 768, s2c_out_lds12, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                             LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
-        else
-          k_s2c_out<QT, 8><<<grid, 512, s2c_out_lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                          LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, nqr_max, Kmax, last);
+        // twelve waves (three per SIMD) when their logits staging fits, else eight
+        const bool fits12 = s2c_out_lds12 <= 160 * 1024;
+        int waves = 12;
+        decltype(&k_s2c_out<QT, 12>) kern;
+        if (leftover && qc0 && !s2c_kg && fits12) kern = big_lds<k_s2c_out<2, 12, false, true, true>>();
+        else if (leftover && !qc0 && !s2c_kg && fits12) kern = big_lds<k_s2c_out<2, 12, false, false, true>>();
+        else if (qc0 && s2c_kg && fits12) kern = big_lds<k_s2c_out<QT, 12, true, true>>();
+        else if (qc0 && !s2c_kg && fits12) kern = big_lds<k_s2c_out<QT, 12, false, true>>();
+        else if (s2c_kg && fits12) kern = big_lds<k_s2c_out<QT, 12, true>>();
+        else if (s2c_kg) kern = big_lds<k_s2c_out<QT, 8, true>>(), waves = 8;
+        else if (fits12) kern = big_lds<k_s2c_out<QT, 12>>();
+        else kern = big_lds<k_s2c_out<QT, 8>>(), waves = 8;
+        kern<<<grid, 64 * waves, waves == 12 ? s2c_out_lds12 : s2c_out_lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b,
+                                                                                 LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w,
+                                                                                 LW.s2c_norm_b, nqr_max, Kmax, last);
       }
       A3D_LAUNCH_CHECK();
       continue;
     }
     if (fuse_s2c) {
       ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, (int)n_total);
-      if (qc0) k_q_s2c<QT, true><<<grid, 512, (size_t)64 * 1024 + qs2c_lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b);
-      else k_q_s2c<QT><<<grid, 512, (size_t)64 * 1024 + qs2c_lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b);
+      (qc0 ? big_lds<k_q_s2c<QT, true>>() : big_lds<k_q_s2c<QT>>())<<<grid, 512, (size_t)64 * 1024 + qs2c_lds, st>>>(
+          samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b);
       A3D_LAUNCH_CHECK();
     } else {
       for (int si = 0; si < ns; ++si) {
         Prepared& p = P[si];
-        const float* src = l == 0 ? p.feats : (((l - 1) & 1) ? p.bufD : p.bufC);
+        const float* src = layer_src(p, l);
         const float* Qs = p.bufA;
         if (qc0) {
           Qs = p.kv0 + (size_t)2 * p.n * D;     // the cached queries of the first layer
@@ -3308,29 +3166,29 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
           if (rc) return rc;
         }
         ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, p.n);
-        k_s2c_attn_wide<QT><<<(p.n + 127) / 128, 512, s2c_lds, st>>>(Qs, p.n, p.B.ks, p.B.vs, p.hm.nq, nblk, p.bufB);
+        big_lds<k_s2c_attn_wide<QT>>()<<<(p.n + 127) / 128, 512, s2c_lds, st>>>(Qs, p.n, p.B.ks, p.B.vs, p.hm.nq, nblk, p.bufB);
         A3D_LAUNCH_CHECK();
       }
     }
     if (fuse_out) {
       // ---- output projection + residual + LayerNorm + mask head in one pass (the pre-norm activation stays on chip)
       ProfScope ps(st, A3D_PROF_LNMASK, 0, 0, 0, 0, (int)n_total);
-      k_out_ln_mask<QT><<<grid, 512, fused_lds, st>>>(samples_dev, ns, l, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w,
-                                                      LW.s2c_norm_b);
+      big_lds<k_out_ln_mask<QT>>()<<<grid, 512, fused_lds, st>>>(samples_dev, ns, l, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w,
+                                                                 LW.s2c_norm_b);
       A3D_LAUNCH_CHECK();
     } else {
       for (int si = 0; si < ns; ++si) {
         Prepared& p = P[si];
-        const float* src = l == 0 ? p.feats : (((l - 1) & 1) ? p.bufD : p.bufC);
-        float* Y = (l & 1) ? p.bufD : p.bufC;
+        const float* src = layer_src(p, l);
+        float* Y = layer_dst(p, l);
         const int K = p.hm.K;
         const size_t lnm_lds = ((size_t)QP * 132 + 4 * 16 * (p.L.qp + 1) + 4 * 16 * (K + 1)) * 4 + (size_t)(K + 1) * 4;
         rc = a3d_linear(p.bufB, D, nullptr, 0, p.n, D, D, LW.s2c_wo_packed, nullptr, LW.s2c_out_b, src, D, 0, Y, D, nullptr, 0, st);
         if (rc) return rc;
         ProfScope ps(st, A3D_PROF_LNMASK, 0, 0, 0, 0, p.n);
-        k_ln_mask<QT><<<(p.n + 63) / 64, 256, lnm_lds, st>>>(Y, p.n, LW.s2c_norm_w, LW.s2c_norm_b, p.B.E, p.hm.nq, p.meta->qrange,
-                                                          p.hm.n_fg, K, p.logits + (size_t)l * p.n * (K + 1), p.labels,
-                                                          p.counts + (size_t)l * (A3D_MAX_QUERIES + 1), nblk);
+        big_lds<k_ln_mask<QT>>()<<<(p.n + 63) / 64, 256, lnm_lds, st>>>(Y, p.n, LW.s2c_norm_w, LW.s2c_norm_b, p.B.E, p.hm.nq,
+                                                                     p.meta->qrange, p.hm.n_fg, K, p.logits + (size_t)l * p.n * (K + 1),
+                                                                     p.labels, p.counts + (size_t)l * (A3D_MAX_QUERIES + 1), nblk);
         A3D_LAUNCH_CHECK();
       }
     }
@@ -3344,28 +3202,10 @@ template <int QT>
 static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, hipStream_t st) {
   int qp = 0;   // rows of the longest query-side buffers of the group
   for (int si = 0; si < ns; ++si) qp = std::max(qp, P[si].L.qp);
-  {
-    static bool big = false;
-    if (!big) {
-      big = true;
-      const int big_lds = 160 * 1024;
-      A3D_ALLOW_LDS(big_lds, k_query_block<2, 1>);
-      A3D_ALLOW_LDS(big_lds, k_query_block<2, 2>);
-      A3D_ALLOW_LDS(big_lds, k_out_w<QT>);      // its per-object maxima grow with the objects: past 64 KB from ~43 objects on
-      if constexpr (QT == 5) {
-        A3D_ALLOW_LDS(big_lds, (k_s2o_w<5, false>));
-        A3D_ALLOW_LDS(big_lds, (k_s2o_w<5, true>));
-      }
-    }
-  }
   const int n_counts = A3D_MAX_DEC_LAYERS * (A3D_MAX_QUERIES + 1);
-  int64_t n_total = 0;
-  int Kmax = 0, nq_max = 0;
-  for (int si = 0; si < ns; ++si) {
-    n_total += P[si].n;
-    Kmax = P[si].hm.K > Kmax ? P[si].hm.K : Kmax;
-    nq_max = P[si].hm.nq > nq_max ? P[si].hm.nq : nq_max;
-  }
+  const GroupTotals tot = group_totals(P, ns);
+  const int64_t n_total = tot.n_total;
+  const int Kmax = tot.Kmax, nq_max = tot.nq_max;
   const size_t stage_lds = (size_t)2 * 2 * kWTile * 4;                       // two slots of (rows, position encodings)
   const size_t out_lds = ((size_t)6 * kWTile + 2 * 256 + 2 * 32 * (Kmax + 1)) * 4 + (size_t)(Kmax + 1) * 4;   // k_out_w: O slots, rows, statistics, maxima, histogram
   if (out_lds > 160 * 1024) {
@@ -3387,24 +3227,14 @@ static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, h
   for (int l = 0; l < w->n_layers; ++l) {
     const a3d_decoder_layer& LW = w->layers[l];
     // ---- click-to-scene; the first layer on the scene's cached keys / values when every sample has them
-    bool cached0 = l == 0;
-    for (int si = 0; si < ns && cached0; ++si) cached0 = P[si].kv0 != nullptr && P[si].kv0_state != 0;
+    const bool cached0 = l == 0 && all_cached(P, ns);
     const bool qc0 = cached0;
     if (cached0) {
       int nchunk_max = 0, nqt_max = 0;
       for (int si = 0; si < ns; ++si) {
         Prepared& p = P[si];
-        float* K0 = p.kv0;
-        float* V0 = p.kv0 + (size_t)p.n * D;
-        if (p.kv0_state == 1) {
-          rc = a3d_linear(p.feats, D, p.posenc, D, p.n, D, D, LW.c2s_wk_packed, nullptr, LW.c2s_in_b + D, nullptr, 0, 0, K0, D, nullptr, 0, st);
-          if (rc) return rc;
-          rc = a3d_linear(p.feats, D, nullptr, 0, p.n, D, D, LW.c2s_wv_packed, nullptr, LW.c2s_in_b + 2 * D, nullptr, 0, 0, V0, D, nullptr, 0, st);
-          if (rc) return rc;
-          rc = a3d_linear(p.feats, D, p.posenc, D, p.n, D, D, LW.s2c_wq_packed, nullptr, LW.s2c_in_b, nullptr, 0, 0,
-                          p.kv0 + (size_t)2 * p.n * D, D, nullptr, 0, st);
-          if (rc) return rc;
-        }
+        rc = fill_kv0(LW, p, st);
+        if (rc) return rc;
         nchunk_max = p.L.nchunk > nchunk_max ? p.L.nchunk : nchunk_max;
         const int t = (p.hm.nq + 15) / 16;
         nqt_max = t > nqt_max ? t : nqt_max;
@@ -3443,11 +3273,8 @@ static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, h
       if (fused_s2o()) {
         ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, (int)n_total);
         const size_t s2o_lds = ((size_t)(4 + 5) * kWTile + 2 * 256 + 2 * 32 * (Kmax + 1) + ((Kmax + 1 + 3) & ~3)) * 4;
-        if (qc0) k_s2o_w<5, true><<<T.grid, 512, s2o_lds, st>>>(T.samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed,
-                                                              LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, Kmax);
-        else k_s2o_w<5, false><<<T.grid, 512, s2o_lds + (size_t)4 * kWTile * 4, st>>>(T.samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b,
-                                                                                     LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w,
-                                                                                     LW.s2c_norm_b, Kmax);
+        (qc0 ? big_lds<k_s2o_w<5, true>>() : big_lds<k_s2o_w<5, false>>())<<<T.grid, 512, s2o_lds + (qc0 ? 0 : (size_t)4 * kWTile * 4), st>>>(
+            T.samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, Kmax);
         A3D_LAUNCH_CHECK();
         continue;
       }
@@ -3460,7 +3287,9 @@ static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, h
     }
     {
       ProfScope ps(st, A3D_PROF_LNMASK, 0, 0, 0, 0, (int)n_total);
-      k_out_w<QT><<<T.grid, 512, out_lds, st>>>(T.samples_dev, ns, l, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, Kmax);
+      // (its per-object maxima grow with the objects: past 64 KB from ~43 objects on)
+      big_lds<k_out_w<QT>>()<<<T.grid, 512, out_lds, st>>>(
+          T.samples_dev, ns, l, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, Kmax);
       A3D_LAUNCH_CHECK();
     }
   }
@@ -3604,32 +3433,17 @@ extern "C" int a3d_decoder_forward_batch(const a3d_decoder_weights* w, const a3d
   // training click round pay the persistent kernels' start-up and tail once.  The others: consecutive samples with the same
   // padded query count share the <= 64-query kernels.  Several groups are independent chains of launches on their own
   // workspaces: group g goes on side stream g mod 4 (forked from / joined to the caller's stream with events), group 0 stays.
-  // A3D_WIDE_MERGE=0: one group per padded query count as before; 2: when the samples of a call do not share ONE padded
-  // query count, all of them go through the wide kernels.
-  static int merge_mode = -1;
-  if (merge_mode < 0) {
-    const char* e = getenv("A3D_WIDE_MERGE");
-    merge_mode = e ? atoi(e) : 1;
-  }
-  {
-    bool mixed = false;
-    for (int i = 1; i < n_samples; ++i) mixed = mixed || P[(size_t)i].L.qp != P[0].L.qp || P[(size_t)i].qtw != P[0].qtw;
-    if (fused_wide() && merge_mode == 2 && mixed)
-      for (int i = 0; i < n_samples; ++i)
-        if (P[(size_t)i].qtw == 0 && P[(size_t)i].hm.nq <= 224) P[(size_t)i].qtw = 5;
-    if (merge_mode != 0) {   // wide samples first (stable): they form the leading group(s)
-      std::vector<Prepared> Q;
-      Q.reserve((size_t)n_samples);
-      for (int pass = 0; pass < 2; ++pass)
-        for (int i = 0; i < n_samples; ++i)
-          if ((P[(size_t)i].qtw > 0) == (pass == 0)) Q.push_back(P[(size_t)i]);
-      P.swap(Q);
-    }
-  }
-  auto same_group = [&](const Prepared& a, const Prepared& b) {
-    if (merge_mode != 0 && a.qtw > 0 && b.qtw > 0) return true;
-    return a.L.qp == b.L.qp && a.qtw == b.qtw;
+  std::stable_partition(P.begin(), P.end(), [](const Prepared& p) { return p.qtw > 0; });   // wide samples first: the leading group(s)
+  auto same_group = [](const Prepared& a, const Prepared& b) {
+    return (a.qtw > 0 && b.qtw > 0) || (a.L.qp == b.L.qp && a.qtw == b.qtw);
   };
+  std::vector<int> group_end;   // one past the last sample of every group
+  for (int i = 0; i < n_samples;) {
+    int e = i + 1;
+    while (e < n_samples && e - i < kMaxBatchSamples && same_group(P[(size_t)i], P[(size_t)e])) ++e;
+    group_end.push_back(e);
+    i = e;
+  }
   struct Side {
     hipStream_t s[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fork = nullptr, done[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -3639,14 +3453,7 @@ extern "C" int a3d_decoder_forward_batch(const a3d_decoder_weights* w, const a3d
   int dev_id = 0;
   (void)hipGetDevice(&dev_id);
   Side& side = sides[dev_id & 15];
-  int n_groups = 0;
-  for (int i = 0; i < n_samples;) {
-    int e = i + 1;
-    while (e < n_samples && e - i < kMaxBatchSamples && same_group(P[(size_t)i], P[(size_t)e])) ++e;
-    ++n_groups;
-    i = e;
-  }
-  bool use_side = n_groups > 1;
+  bool use_side = group_end.size() > 1;
   if (use_side && !side.tried) {
     side.tried = true;
     bool ok = hipEventCreateWithFlags(&side.fork, hipEventDisableTiming) == hipSuccess;
@@ -3659,10 +3466,9 @@ extern "C" int a3d_decoder_forward_batch(const a3d_decoder_weights* w, const a3d
   use_side = use_side && side.ok;
   bool used[4] = {false, false, false, false};
   if (use_side) A3D_HIP_CHECK(hipEventRecord(side.fork, st));
-  int g = 0, rc_all = A3D_OK;
-  for (int i = 0; i < n_samples && rc_all == A3D_OK;) {
-    int e = i + 1;
-    while (e < n_samples && e - i < kMaxBatchSamples && same_group(P[(size_t)i], P[(size_t)e])) ++e;
+  int rc_all = A3D_OK;
+  for (int g = 0; g < (int)group_end.size() && rc_all == A3D_OK; ++g) {
+    const int i = g ? group_end[(size_t)g - 1] : 0;
     hipStream_t gs = st;
     if (use_side && g > 0) {
       const int k = (g - 1) & 3;
@@ -3672,9 +3478,7 @@ extern "C" int a3d_decoder_forward_batch(const a3d_decoder_weights* w, const a3d
         if (hipStreamWaitEvent(gs, side.fork, 0) != hipSuccess) rc_all = A3D_ERR_HIP;
       }
     }
-    if (rc_all == A3D_OK) rc_all = dispatch_decoder(w, &P[(size_t)i], e - i, gs);
-    ++g;
-    i = e;
+    if (rc_all == A3D_OK) rc_all = dispatch_decoder(w, &P[(size_t)i], group_end[(size_t)g] - i, gs);
   }
   // join: the caller's stream continues after every side stream's work (also when a later group failed)
   for (int k = 0; k < 4; ++k)

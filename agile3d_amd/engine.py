@@ -620,8 +620,7 @@ class Engine:
         """The position encoding this model was built with (args.positional_encoding_type, args.normalize_pos_enc;
         DESIGN.md §4.8) of the rows ``raw`` [n, 3]: one sample (``starts`` None: ([n, 128], [6] min / max)) or the samples
         ``[starts[b], starts[b + 1])`` (ctypes int64 array; ([n, 128], [ns, 6])).  The min / max is None where the
-        encoding does not normalise (no reduction runs).  The default model calls a3d_posenc_fourier[_batch], every other
-        configuration a3d_posenc[_batch]."""
+        encoding does not normalise (no reduction runs)."""
         lib = L.load()
         m = self.model
         kind, norm = L.POSENC_KINDS[m.pos_enc_type], int(m.normalize_pos_enc and m.pos_enc_type != "legacy")
@@ -635,12 +634,7 @@ class Engine:
                               device=self.device)
         tail = (_ptr(mm), _ptr(pe), _ptr(tmp), tmp.numel() if norm else 0, _stream())
         table = self.decoder.posenc_table_ptr
-        if kind == 0 and norm:
-            if ns is None:
-                L.check(lib.a3d_posenc_fourier(_ptr(raw), n, table, *tail), "a3d_posenc_fourier")
-            else:
-                L.check(lib.a3d_posenc_fourier_batch(_ptr(raw), starts, ns, table, *tail), "a3d_posenc_fourier_batch")
-        elif ns is None:
+        if ns is None:
             L.check(lib.a3d_posenc(kind, norm, _ptr(raw), n, table, *tail), "a3d_posenc")
         else:
             L.check(lib.a3d_posenc_batch(kind, norm, _ptr(raw), starts, ns, table, *tail), "a3d_posenc_batch")

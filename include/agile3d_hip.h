@@ -543,7 +543,7 @@ int a3d_posenc_fourier_batch(const float* xyz_dev, const int64_t* starts_host, i
  * u is the coordinate shifted and scaled to [0, 1] by the sample's own min / max when `normalize` != 0 (FOURIER, SINE),
  * the raw coordinate when it is 0; LEGACY always takes the raw coordinate and ignores `normalize`.  Where no min / max
  * is needed the reduction is skipped: minmax_dev and the workspace are not touched and may be NULL / 0.  out_dev must
- * be 16-byte aligned.  (FOURIER, normalize = 1) runs the kernels of a3d_posenc_fourier[_batch]: the same bits.
+ * be 16-byte aligned.  a3d_posenc_fourier[_batch] above are these two at (FOURIER, normalize = 1), without that alignment.
  * a3d_posenc_batch: bit-identical to a3d_posenc per sample; workspace of a3d_posenc_batch_workspace_bytes. */
 #define A3D_POSENC_FOURIER 0
 #define A3D_POSENC_SINE 1

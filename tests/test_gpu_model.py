@@ -196,8 +196,9 @@ def test_forward_mask_many_clicks(model_and_sd, decoder_weights, n_obj, per_obj,
 
 
 def test_batched_position_encoding_equals_per_sample_calls(model_and_sd):
-    """a3d_posenc_fourier_batch (three launches for the whole batch, what forward_backbone calls) against one
-    a3d_posenc_fourier per sample: every sample is normalised by ITS OWN min / max (agile3d.py:141-161) -- same bits."""
+    """The batched encoding (three launches for the whole batch, what forward_backbone calls) against one
+    a3d_posenc_fourier per sample: every sample is normalised by ITS OWN min / max (agile3d.py:141-161) -- same bits;
+    the old entry point forwards to the one host path at (FOURIER, 1)."""
     import ctypes as C
     from agile3d_amd import lib as L
     model, _ = model_and_sd

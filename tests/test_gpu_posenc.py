@@ -198,6 +198,43 @@ def test_default_fourier_path_is_unchanged(decoder_weights):
     assert not torch.equal(b_old, o_old)                                       # per-sample ranges really differ
 
 
+@pytest.mark.parametrize("config", ["fourier_norm", "sine_norm"])
+def test_one_sample_reduction_past_its_block_cap(config, decoder_weights):
+    """A one-sample call reduces over min(ceil(n / 256), 256) blocks: at n = 65 836 the 256 x 256 threads cover 65 536
+    rows and some take a second sweep.  Every extreme of the sample lies in a row only that sweep reads (the first row
+    past the cap, the last row and two in between), so a reduction that stopped at the cap would miss all six.  Its
+    min / max is exact, and its rows carry the same bits as the same points as sample 0 of a batched call (16 blocks per
+    sample) and as a3d_posenc_batch called with that one sample."""
+    eng = _model(config, decoder_weights)._get_engine()
+    eng.refresh_decoder_if_stale(check_versions=True)
+    n, n1, cap = 65836, 300, 256 * 256
+    g = torch.Generator().manual_seed(65836)
+    xyz = torch.rand(n + n1, 3, generator=g) * torch.tensor((9.0, 7.0, 3.0)) - 2.0          # x in [-2, 7), y [-2, 5), z [-2, 1)
+    xyz[cap] = torch.tensor((-2.5, 0.0, 1.25))         # min x, max z
+    xyz[cap + 131] = torch.tensor((7.5, -2.75, 0.0))   # max x, min y
+    xyz[n - 2] = torch.tensor((0.0, 5.5, 0.0))         # max y
+    xyz[n - 1] = torch.tensor((0.0, 0.0, -3.0))        # min z
+    xyz = xyz.cuda()
+    one = xyz[:n]
+    below = torch.cat([one[:cap].min(0)[0], one[:cap].max(0)[0]])
+    assert (below != torch.cat([one.min(0)[0], one.max(0)[0]])).all()       # all six extremes lie past the block cap
+    pe, mm = eng._posenc(one)
+    assert torch.equal(mm, torch.cat([one.min(0)[0], one.max(0)[0]]))
+    pes, mms = eng._posenc_batch(xyz, [(0, n), (n, n + n1)])
+    assert pes[0].data_ptr() + 4 * 128 * n == pes[1].data_ptr()                 # one matrix: the batched launch ran
+    assert torch.equal(pes[0], pe) and torch.equal(mms[0], mm)
+    lib = L.load()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    kind, table = L.POSENC_KINDS[ALL_CONFIGS[config]["positional_encoding_type"]], eng.decoder.posenc_table_ptr
+    out = torch.empty((n, 128), dtype=torch.float32, device="cuda")
+    bmm = torch.empty((1, 6), dtype=torch.float32, device="cuda")
+    tmp = torch.empty(lib.a3d_posenc_batch_workspace_bytes(1), dtype=torch.uint8, device="cuda")
+    _call(lib, "a3d_posenc_batch", kind, 1, p(one), (C.c_int64 * 2)(0, n), 1, table, p(bmm), p(out), p(tmp), tmp.numel(),
+          C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert torch.equal(out, pe) and torch.equal(bmm[0], mm)
+    assert torch.isfinite(pe).all() and pe.abs().max().item() <= 1.0
+
+
 def test_entry_points_refuse_bad_arguments():
     lib = L.load()
     xyz = torch.rand(64, 3, device="cuda")
