@@ -136,6 +136,25 @@ class SessionEditArgs(C.Structure):
                 ("n_objects", C.c_int32), ("reserved_", C.c_int32), ("lut", C.c_uint8 * 256)]
 
 
+class SessionGuideSummary(C.Structure):
+    """a3d_session_guide_summary: rows and contested rows per label, the complemented packed key of the least confident row (0 =
+    none), the error word (bit 0 = a NaN margin, bit 1 = an inverse_map entry out of range)."""
+    _fields_ = [("voxels", C.c_int32 * 256), ("contested", C.c_int32 * 256), ("least_key", C.c_uint64), ("err", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+class SessionGuideArgs(C.Structure):
+    """a3d_session_guide_args: the voxel half (logits -> labels, runner, margin, want), the vertex half (inverse_map, colours,
+    palette -> margin_full, colors_out), the summary, the settings and the clicks by value."""
+    _fields_ = [("logits_dev", C.c_void_p), ("n_qv", C.c_int64), ("inverse_map_dev", C.c_void_p), ("n_full", C.c_int64),
+                ("colors_full_dev", C.c_void_p), ("palette_dev", C.c_void_p), ("labels_qv_dev", C.c_void_p),
+                ("runner_qv_dev", C.c_void_p), ("margin_qv_dev", C.c_void_p), ("want_qv_dev", C.c_void_p),
+                ("margin_full_dev", C.c_void_p), ("colors_out_dev", C.c_void_p), ("summary_dev", C.c_void_p),
+                ("n_classes", C.c_int32), ("n_palette", C.c_int32), ("n_clicks", C.c_int32), ("threshold", C.c_float),
+                ("full_margin", C.c_float), ("doubt", C.c_float * 3), ("click_row", C.c_int32 * 256),
+                ("click_obj", C.c_uint8 * 256)]
+
+
 class Camera(C.Structure):
     """a3d_camera: pixel (u, v)'s ray starts at o and runs along normalize(d00 + u du + v dv), evaluated in fp32."""
     _fields_ = [("o", C.c_float * 3), ("d00", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
@@ -360,6 +379,7 @@ SYMBOLS = {
     "a3d_section_ray": (C.c_int, [C.POINTER(Section), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "a3d_session_paint": (C.c_int, [C.POINTER(SessionPaintArgs), C.c_void_p]),
     "a3d_session_edit": (C.c_int, [C.POINTER(SessionEditArgs), C.c_void_p]),
+    "a3d_session_guide": (C.c_int, [C.POINTER(SessionGuideArgs), C.c_void_p]),
     "a3d_render_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "a3d_render_camera_bounds": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_double)]),
     "a3d_render_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(Camera), C.POINTER(RenderOut),

@@ -24,6 +24,8 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
                                         culling; in the GUI the camera's near plane cuts a wall away; a rule of ours)
     taking a click back, resuming       a3d_session_edit   (undo, redo, remove_click, restore_clicks / restore_file: the
                                         GUI's "unselect point" is a TODO, gui.py:283-287; a rule of ours)
+    where the labels are unsure, the    a3d_session_guide + a3d_click_clusters  (guide, confidence_at: the tool drops the
+    next click                          logits after the arg-max, :78-81; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -46,6 +48,7 @@ Departures from the reference, on purpose:
 from __future__ import annotations
 
 import colorsys
+import ctypes
 import os
 from datetime import datetime
 
@@ -220,6 +223,51 @@ def marker_hit(markers, u, v, t_pixel, marker_px, depth_slack):
     cover &= ~np.isnan(m).any(1)
     hits = np.flatnonzero(cover)
     return int(hits[-1]) if len(hits) else None
+
+
+def rank_suggestions(clusters, coords_row_lookup, max_suggestions):
+    """The suggested clicks of ``guide()``, best first, from the records of the cluster search (dicts with ``cluster_id``,
+    ``row``, ``label``, ``pred``, ``error_size``; any order): ranked by ``error_size``, largest first; equal sizes keep
+    ascending cluster id -- the stable order ``clicks._pick_clicks`` ranks by, without its shuffle.  At most
+    ``max_suggestions`` entries ``{row, point, object, current, size}``: the voxel row, its coordinates (``coords_row_lookup``:
+    a callable ``row -> xyz`` or anything indexed by the row), the object the click would go to (the record's ``label``: the
+    region's runner-up), the object the row has now (its ``pred``), the distance from the row to the region's border in
+    metres.  Pure Python."""
+    if int(max_suggestions) != max_suggestions or max_suggestions < 0:
+        raise ValueError("max_suggestions must be an integer >= 0")
+    lookup = coords_row_lookup if callable(coords_row_lookup) else coords_row_lookup.__getitem__
+    ranked = sorted(sorted(clusters, key=lambda c: c["cluster_id"]), key=lambda c: c["error_size"], reverse=True)
+    return [{"row": int(c["row"]), "point": [float(x) for x in lookup(int(c["row"]))], "object": int(c["label"]),
+             "current": int(c["pred"]), "size": float(c["error_size"])} for c in ranked[:int(max_suggestions)]]
+
+
+def suggest_clicks(clusters, least_confident, coords_row_lookup, max_suggestions):
+    """``rank_suggestions`` -- unless a record's ``error_size`` is not finite: the search found a region that has nothing
+    outside it, so it covers every voxel (and is the only record) and no voxel is deeper in it than another.  The
+    suggestion is then the least confident voxel alone (``least_confident`` = ``(row, margin)``), for the region's runner-up,
+    with ``size = inf``; none when there is no such voxel.  Pure Python."""
+    if all(np.isfinite(c["error_size"]) for c in clusters):
+        return rank_suggestions(clusters, coords_row_lookup, max_suggestions)
+    if least_confident is None:
+        return []
+    whole = next(c for c in clusters if not np.isfinite(c["error_size"]))
+    return rank_suggestions([dict(whole, row=int(least_confident[0]), error_size=float("inf"))], coords_row_lookup,
+                            min(1, max_suggestions))
+
+
+class GuideResult:
+    """What ``guide()`` returns.  Device tensors: ``labels_qv`` int32 [n_voxels] (what ``infer()`` computed), ``runner_qv``
+    int32 (the second choice), ``margin_qv`` fp32 (winner's logit minus runner-up's; +inf on a clicked voxel), ``margin_full``
+    fp32 [n_full], ``colors`` fp32 [n_full, 3] (the confidence view, for ``render(colors=)``).  Host: ``object_voxels`` and
+    ``object_contested`` int64 [1 + K] (voxels and contested voxels per object id), ``least_confident`` = ``(row, margin)``
+    or ``None``, ``n_contested``, ``suggestions`` (``rank_suggestions``), ``threshold`` and ``full_margin`` as used."""
+
+    __slots__ = ("labels_qv", "runner_qv", "margin_qv", "margin_full", "colors", "object_voxels", "object_contested",
+                 "least_confident", "n_contested", "suggestions", "threshold", "full_margin")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
 
 
 class SessionResult:
@@ -493,6 +541,8 @@ class InteractiveSession:
         self._cubes_dev = torch.zeros((L.A3D_MAX_CLICKS, 6), dtype=torch.float32, device=self.device)
         self._mask_host = None                      # pinned staging of a scene's full-resolution labels (scenes with an out_dir)
         self._edit_err = torch.zeros(1, dtype=torch.int32, device=self.device)   # a3d_session_edit's flag
+        self._guide_sum = torch.empty(V.GUIDE_SUMMARY.itemsize, dtype=torch.uint8, device=self.device)   # a3d_session_guide's summary
+        self._guide_sum_host = torch.empty(V.GUIDE_SUMMARY.itemsize, dtype=torch.uint8).pin_memory()
         self._drop_scene()
 
     # ------------------------------------------------------------------ scene
@@ -505,6 +555,8 @@ class InteractiveSession:
         self._corner_lists = None                   # (offsets int64 [n + 1], corners int32 [3 m]) on the device: a mesh's incidence lists
         self.normals = None                         # fp32 [n, 3] on the device: a mesh's vertex normals, computed by the first lit render
         self._coords_host = None
+        self._coords_qv_host = None                 # host copy of raw_coords_qv: the points of guide()'s suggestions
+        self._vertex_ids = None                     # int32 [n] 0..n-1 on the device, built by the first confidence_at()
         self._backbone = None
         self._mask_host = None
         self._render_ws = None                      # scratch of render(): kept per scene, grown when a view needs more pairs
@@ -514,6 +566,8 @@ class InteractiveSession:
     def _reset_clicks(self):
         self._colors_last = None                    # colours of the last infer / preview: what render() shows by default
         self._labels_last = None                    # its full-resolution labels: what label_image() shows by default
+        self._guide_logits = None                   # (logits, click_idx) of the last infer(): what guide() describes; dropped by
+        self._guide_last = None                     # whatever changes the clicks or the scene.  The last guide()'s result.
         self._clicks = []                           # THE state: the ordered click list (entry i = time index i)
         self._redo = []                             # (click list before an undo, the table that renumbers the labels back)
         self.click_idx = {"0": []}
@@ -563,6 +617,7 @@ class InteractiveSession:
         self.colors_full = col32
         self.inverse_map = inverse_map.contiguous()
         self.raw_coords_qv = xyz[unique_map].to(torch.float32).contiguous()
+        self._coords_qv_host = self.raw_coords_qv.cpu().numpy()
         if labels_full is not None:
             lab = torch.as_tensor(np.asarray(labels_full) if not torch.is_tensor(labels_full) else labels_full).reshape(-1)
             if lab.shape[0] != n:
@@ -889,6 +944,7 @@ class InteractiveSession:
         self._clicks.append({"obj": obj, "point": tuple(float(x) for x in q), "row_qv": row_qv, "row_full": row_full,
                              "position": self._coords_host[row_full].tolist()})
         self._redo.clear()
+        self._guide_logits = self._guide_last = None    # the kept logits belong to the list before this click
         self.click_idx, self.click_time_idx, self.click_positions = click_state(self._clicks)
         if new_object and self.new_labels is not None:
             self._launch_edit(None)
@@ -941,6 +997,7 @@ class InteractiveSession:
         torch.cuda.current_stream(self.device).synchronize()   # no copy from a pinned cube row is in flight past this point
         before, n = self.num_clicks, len(clicks)
         self._clicks = list(clicks)
+        self._guide_logits = self._guide_last = None    # the kept logits belong to the list before the edit
         self.click_idx, self.click_time_idx, self.click_positions = state
         self.num_clicks = n
         for k, c in enumerate(self._clicks):
@@ -1091,6 +1148,7 @@ class InteractiveSession:
         if logits is None:
             out = self.model.forward_mask(*self._backbone, click_idx=[self.click_idx], click_time_idx=[self.click_time_idx])
             logits = out["pred_masks"][0]
+        logits = logits.contiguous()
         labels_qv = K.argmax_labels(logits, self.click_idx)
         labels_full, colors = self._launch_paint(labels_qv, paint_cubes)
         have_gt = self.new_labels is not None
@@ -1112,6 +1170,7 @@ class InteractiveSession:
             raise RuntimeError("inverse_map or labels out of range")
         self._labels_qv = labels_qv
         self._colors_last, self._labels_last = colors, labels_full
+        self._guide_logits, self._guide_last = (logits, self.click_idx), None
         miou, per_obj = None, None
         if have_gt:
             t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())
@@ -1128,3 +1187,96 @@ class InteractiveSession:
             np.save(res.mask_path, mask_host.numpy().astype(np.int64))           # the reference saves an int64 arg-max
             np.save(res.click_path, {"click_idx": self.click_idx, "click_time": self.click_time_idx})
         return res
+
+    # ------------------------------------------------------------------ where the labels are unsure
+    def guide(self, threshold=1.0, full_margin=4.0, doubt_color=(1.0, 1.0, 1.0), max_suggestions=5):
+        """Where the LAST ``infer()`` is unsure, and where a next click would help most.  From the logits that inference
+        used (``ValueError`` when there are none: before the first ``infer()``, and after anything that changed the click
+        list or the scene since -- ``click``, ``undo``, ``redo``, ``remove_click``, ``restore_*``, ``reset``, ``load_scene``):
+
+        * per voxel the winning object, the runner-up and the MARGIN between their logits (``a3d_session_guide``; a clicked
+          voxel has margin +inf), lifted to the vertices through the inverse map;
+        * the confidence view ``colors``: a vertex's object colour (its own for the background) faded towards ``doubt_color``
+          as the margin falls from ``full_margin`` to 0 -- ``render(colors=g.colors)`` shows it as it is;
+        * voxels and contested voxels per object; a voxel is CONTESTED when its margin lies below ``threshold``;
+        * ``suggestions``: the contested voxels form regions, one per (runner-up, winner) pair; each region's deepest voxel
+          -- the one farthest from everything outside the region, found by the click simulator's search
+          (``a3d_click_clusters`` with the runner-up as the wanted label) -- is a suggested click for the RUNNER-UP, ranked by
+          that depth (``rank_suggestions``), at most ``max_suggestions``.  ``ses.click(s["point"], s["object"])`` takes one.
+          A region that covers every voxel has no border and no depth: the suggestion is then the least confident voxel
+          alone, with ``size = inf`` (``suggest_clicks``) -- a case for logits without a clicked voxel, which is never
+          contested and so lies outside every region.
+
+        ``threshold`` and ``full_margin`` are in logit units.  The defaults, 1.0 and 4.0, are this project's choice and are
+        NOT tuned on real scans.  A region is told from another by the simulator's cluster id, 96 x runner-up + 11 x winner,
+        which is unique while object ids stay below 96; above that two regions can share an id and count as one.
+        One ``a3d_session_guide`` call, the cluster search, then ONE host round trip.  Returns a ``GuideResult``."""
+        self._need_scene()
+        if self._guide_logits is None:
+            raise ValueError("guide() describes the last infer(): there is none, or the clicks or the scene changed since "
+                             "(call infer() first)")
+        logits, click_idx = self._guide_logits
+        n_ids = max(len(click_idx), logits.shape[1])
+        rows, objs = [], []
+        for key, cids in click_idx.items():          # dict order, as a3d_argmax_labels applied them in infer()
+            rows += [int(c) for c in cids]
+            objs += [int(key)] * len(cids)
+        dev = self.device
+        labels, runner, margin, want, margin_full, colors, _ = V.session_guide(
+            logits, rows, objs, threshold, inverse_map=self.inverse_map, colors=self.colors_full, palette=self._palette_dev,
+            doubt_color=doubt_color, full_margin=full_margin, summary=self._guide_sum)
+        work, out, out_host = K._cluster_buffers(dev, labels.numel())
+        try:
+            K._launch_clusters(labels, want, self.raw_coords_qv, work, out)
+            self._guide_sum_host.copy_(self._guide_sum, non_blocking=True)
+            out_host.copy_(out, non_blocking=True)
+        finally:
+            torch.cuda.current_stream(dev).synchronize()      # the one host round trip
+        summary = V.read_guide_summary(self._guide_sum_host.numpy())
+        if summary["err"] & V.GUIDE_BAD_INDEX:
+            raise RuntimeError("a3d_session_guide: inverse_map out of range")
+        if summary["err"] & V.GUIDE_NAN_MARGIN:
+            raise RuntimeError("a3d_session_guide: the logits hold a NaN (or two infinities of one sign in a row)")
+        host = out_host.numpy()
+        rec_bytes = K.MAX_CLUSTERS * ctypes.sizeof(L.ClickCluster)
+        count = int(host[rec_bytes:rec_bytes + 4].view(np.int32)[0])
+        if count < 0:
+            raise RuntimeError("a3d_click_clusters: labels outside 0 .. 255")
+        if count > K.MAX_CLUSTERS:
+            raise RuntimeError(f"a3d_click_clusters: {count} contested regions > {K.MAX_CLUSTERS}")
+        recs = np.frombuffer(host[:count * ctypes.sizeof(L.ClickCluster)].tobytes(), dtype=K._REC)
+        clusters = [dict(zip(recs.dtype.names, t)) for t in recs.tolist()]
+        suggestions = suggest_clicks(clusters, summary["least"], self._coords_qv_host, max_suggestions)
+        res = GuideResult(labels_qv=labels, runner_qv=runner, margin_qv=margin, margin_full=margin_full, colors=colors,
+                          object_voxels=summary["voxels"][:n_ids].copy(),
+                          object_contested=summary["contested"][:n_ids].copy(), least_confident=summary["least"],
+                          n_contested=int(summary["contested"].sum()), suggestions=suggestions,
+                          threshold=float(threshold), full_margin=float(full_margin))
+        self._guide_last = res
+        return res
+
+    def confidence_at(self, result, u, v, guide=None):
+        """The margin (a float; ``inf`` on a clicked voxel's vertices) of the vertex that pixel ``(u, v)`` (column, row) of
+        ``result`` shows, or ``None`` where the pixel shows nothing: on a cloud the pixel's vertex, on a mesh the heaviest
+        corner of its face -- the vertex whose object ``object_at`` reports (``a3d_render_labels`` over the vertices' own
+        indices).  ``guide``: a ``GuideResult`` of this scene (default: the last ``guide()``'s; ``ValueError`` when the clicks
+        or the scene changed since).  Two small device-to-host copies."""
+        self._need_scene()
+        guide = self._guide_last if guide is None else guide
+        if guide is None:
+            raise ValueError("confidence_at() reads the last guide(): there is none, or the clicks or the scene changed since")
+        if result.mesh != (self.faces is not None):
+            raise ValueError("the render belongs to another scene")
+        n = self.coords_full.shape[0]
+        if tuple(guide.margin_full.shape) != (n,):
+            raise ValueError("the guide belongs to another scene")
+        u, v = int(u), int(v)
+        h, w = result.ids.shape
+        if not (0 <= u < w and 0 <= v < h):
+            raise ValueError(f"pixel ({u}, {v}) outside the {w} x {h} image")
+        if self._vertex_ids is None:
+            self._vertex_ids = torch.arange(n, dtype=torch.int32, device=self.device)
+        one = lambda image: None if image is None else image[v:v + 1, u:u + 1]
+        vertex = int(V.render_labels(one(result.ids), one(result.u), one(result.v), self.faces, self._vertex_ids,
+                                     out=self._small[20:21].view(1, 1)).cpu())
+        return None if vertex < 0 else float(guide.margin_full[vertex].cpu())

@@ -1,4 +1,4 @@
-"""The interactive session's library calls (``csrc/session.hip``) as functions of device tensors -- the one place where
+"""The interactive session's library calls (``csrc/session*.hip``) as functions of device tensors -- the one place where
 they are marshalled, as ``clicks.py`` is for ``csrc/clicks.hip``.  ``session.py`` and the tests call these.
 
 Every wrapper takes device tensors (or ``None`` where the C ABI takes a null pointer), checks dtype, device, shape and
@@ -413,3 +413,81 @@ def session_edit(labels_ori=None, instances=None, new_labels=None, labels=None, 
         raise ValueError("lut and err belong to the remap half: labels is missing")
     L.check(L.load().a3d_session_edit(C.byref(a), _stream(dev)), "a3d_session_edit")
     return new_labels, labels, err
+
+
+# ---- the guide: margins, the confidence view, what the cluster search takes ---------------------------------------------------
+GUIDE_SUMMARY = np.dtype([("voxels", "<i4", (256,)), ("contested", "<i4", (256,)), ("least_key", "<u8"), ("err", "<i4"),
+                          ("reserved_", "<i4")])
+assert C.sizeof(L.SessionGuideSummary) == GUIDE_SUMMARY.itemsize == 2064
+GUIDE_NAN_MARGIN, GUIDE_BAD_INDEX = 1, 2        # the bits of the summary's error word
+
+
+def read_guide_summary(host):
+    """The host copy of an ``a3d_session_guide_summary`` (uint8 [2064], or anything of those bytes) as a dict: ``voxels``
+    and ``contested`` int64 [256] (rows and contested rows per label), ``least`` = ``(row, margin)`` of the least confident
+    row -- the smallest finite margin, ties to the lowest row -- or ``None`` when no row has a finite margin, ``err`` (bit
+    ``GUIDE_NAN_MARGIN``, bit ``GUIDE_BAD_INDEX``)."""
+    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:GUIDE_SUMMARY.itemsize].view(GUIDE_SUMMARY)[0]
+    key = ~int(rec["least_key"]) & ((1 << 64) - 1)       # (stored complemented: the cleared record means "no row")
+    least = None
+    if key != (1 << 64) - 1:
+        least = (key & 0xffffffff, float(np.array([key >> 32], np.uint32).view(np.float32)[0]))
+    return {"voxels": rec["voxels"].astype(np.int64), "contested": rec["contested"].astype(np.int64), "least": least,
+            "err": int(rec["err"])}
+
+
+def session_guide(logits, click_rows, click_objs, threshold, inverse_map=None, colors=None, palette=None,
+                  doubt_color=(1.0, 1.0, 1.0), full_margin=4.0, labels=None, runner=None, margin=None, want=None,
+                  margin_full=None, colors_out=None, summary=None):
+    """``a3d_session_guide``: how sure ``logits`` fp32 [n, C] (2 <= C <= 256) are, row by row.  ``click_rows`` /
+    ``click_objs``: host sequences of equal length (at most ``A3D_MAX_CLICKS``; objects in 0..255), applied in order.
+    ``threshold`` > 0: a row whose margin lies below it is contested.  The vertex half runs when ``colors`` fp32 [m, 3] is
+    given: ``inverse_map`` int64 [m] (``None``: the identity), ``palette`` fp32 [K + 1, 3], ``doubt_color`` three numbers,
+    ``full_margin`` > 0 (the margin from which a vertex shows its plain colour).  Outputs are the caller's or allocated.
+    Returns ``(labels int32 [n], runner int32 [n], margin fp32 [n], want int32 [n], margin_full fp32 [m] or None, colours
+    fp32 [m, 3] or None, summary uint8 [2064])`` on the device; ``read_guide_summary`` decodes the summary's host copy."""
+    dev = _device("logits", logits)
+    a = L.SessionGuideArgs()
+    a.logits_dev = _ptr("logits", logits, F32, (None, None), dev)
+    n, a.n_classes = logits.shape
+    if not 2 <= a.n_classes <= 256:
+        raise ValueError(f"logits must have 2 .. 256 columns, not {a.n_classes}")
+    a.n_qv = n
+    rows, objs = np.asarray(click_rows, dtype=np.int64).reshape(-1), np.asarray(click_objs, dtype=np.int64).reshape(-1)
+    if len(rows) != len(objs) or len(rows) > L.A3D_MAX_CLICKS:
+        raise ValueError(f"click_rows and click_objs must have one length, at most {L.A3D_MAX_CLICKS}")
+    if len(objs) and (objs.min() < 0 or objs.max() > 255):
+        raise ValueError("click_objs are object ids in 0 .. 255")
+    a.n_clicks = len(rows)
+    for k, (r, o) in enumerate(zip(rows.tolist(), objs.tolist())):
+        a.click_row[k], a.click_obj[k] = (r if -1 <= r < 1 << 31 else -1), o     # (a row no int32 holds is a row outside)
+    threshold, full_margin = float(threshold), float(full_margin)
+    f32 = np.float32
+    with np.errstate(over="ignore"):
+        if not (np.isfinite(f32(threshold)) and f32(threshold) > 0 and np.isfinite(f32(full_margin)) and f32(full_margin) > 0):
+            raise ValueError("threshold and full_margin must be finite and > 0 (in fp32)")
+    a.threshold, a.full_margin = threshold, full_margin
+    labels, runner = _out("labels", labels, I32, (n,), dev), _out("runner", runner, I32, (n,), dev)
+    margin, want = _out("margin", margin, F32, (n,), dev), _out("want", want, I32, (n,), dev)
+    a.labels_qv_dev, a.runner_qv_dev = labels.data_ptr() if n else None, runner.data_ptr() if n else None
+    a.margin_qv_dev, a.want_qv_dev = margin.data_ptr() if n else None, want.data_ptr() if n else None
+    if colors is not None:
+        m = colors.shape[0] if torch.is_tensor(colors) and colors.dim() == 2 else 0
+        a.n_full = m
+        a.colors_full_dev = _ptr("colors", colors, F32, (None, 3), dev)
+        a.inverse_map_dev = _ptr("inverse_map", inverse_map, I64, (m,), dev, optional=True)
+        a.palette_dev = _ptr("palette", palette, F32, (None, 3), dev)
+        a.n_palette = palette.shape[0]
+        if not 2 <= a.n_palette <= 256:
+            raise ValueError("palette must be [K + 1, 3] with 1 <= K <= 255")
+        a.doubt[:] = [float(x) for x in _f32p("doubt_color", doubt_color, (3,))[0]]
+        margin_full, colors_out = _out("margin_full", margin_full, F32, (m,), dev), _out("colors_out", colors_out, F32, (m, 3), dev)
+        a.margin_full_dev, a.colors_out_dev = (margin_full.data_ptr(), colors_out.data_ptr()) if m else (None, None)
+    elif inverse_map is not None or margin_full is not None or colors_out is not None:
+        raise ValueError("inverse_map, margin_full and colors_out belong to the vertex half: colors is missing")
+    summary = _out("summary", summary, U8, (GUIDE_SUMMARY.itemsize,), dev)
+    if summary.data_ptr() % 8:
+        raise ValueError("summary must be 8-byte aligned")
+    a.summary_dev = summary.data_ptr()
+    L.check(L.load().a3d_session_guide(C.byref(a), _stream(dev)), "a3d_session_guide")
+    return labels, runner, margin, want, margin_full, colors_out, summary

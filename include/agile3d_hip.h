@@ -861,6 +861,67 @@ typedef struct a3d_session_edit_args {
 } a3d_session_edit_args;
 int    a3d_session_edit(const a3d_session_edit_args* args, void* stream);
 
+/* How SURE the last inference is, and where a next click should look (csrc/session_guide.hip).  The rule is this library's:
+ * the reference keeps the arg-max of forward_mask's logits and drops the logits (interactive_segmentation_user.py:78-81).
+ * Two independent halves, one launch each; a half whose count is 0 is absent.
+ *   VOXELS (n_qv > 0), over logits [n_qv][n_classes] fp32 row-major, 2 <= n_classes <= 256, n_qv < 2^31; every row is written:
+ *     label  = the FIRST maximum of the row: scan from column 0, replace on `>` (what a3d_argmax_labels writes)
+ *     runner = the first maximum among the OTHER columns, by the same scan
+ *     margin = logits[label] - logits[runner], one fp32 subtraction; >= 0 unless it is NaN
+ *     then the clicks click_row[k] / click_obj[k], k = 0..n_clicks-1 in order (the last entry of a row wins; a row outside
+ *     0..n_qv-1 is ignored, as a3d_argmax_labels ignores it): label = runner = click_obj[k], margin = +inf
+ *     want   = runner where margin < threshold (strictly: the row is CONTESTED), else label
+ *     A row whose margin is NaN (a NaN logit, or two infinities of one sign) sets bit 0 of the summary's err; its label and
+ *     runner are what the two scans leave (columns in 0..n_classes-1) and it is not contested.
+ *     Fed to a3d_click_clusters as pred = label, labels = want, the contested rows become its "error" clusters: one per
+ *     (runner, label) pair, each with the row farthest from everything outside it -- the deepest point of the region.
+ *   SUMMARY (always written; cleared by the call): voxels[l] = rows whose label is l, contested[l] = contested rows among
+ *     them; least_key = the COMPLEMENT of the minimum over the rows with a FINITE margin of (margin bits << 32 | row) --
+ *     the smallest margin, ties to the lowest row -- and 0, the cleared record, when no row has one (~0 holds row -1);
+ *     err as above.  Integer sums and a maximum: identical from run to run.
+ *   VERTICES (n_full > 0): src = inverse_map[i] (NULL = identity).  src outside 0..n_qv-1 sets bit 1 of err and leaves
+ *     vertex i unwritten.  Else margin_full[i] = margin[src] and, per channel,
+ *         colour = base * s + doubt * (1 - s),   s = (x < 1 ? x : 1),   x = margin[src] * (1 / full_margin)
+ *     in fp32, every operation (the reciprocal, x, both products, the difference, the sum) rounded on its own, no fma
+ *     contraction.  base = the palette entry of label[src] > 0 with a3d_session_paint's wrap, the vertex's own colour
+ *     otherwise.  A margin >= full_margin gives exactly base, a margin of 0 exactly doubt; a NaN margin counts as sure.
+ *     No click cubes: a3d_render_annotate draws the clicks.
+ * A3D_ERR_INVALID with nothing launched: n_classes outside 2..256, a negative count, n_qv >= 2^31, n_clicks >
+ * A3D_MAX_CLICKS, threshold or full_margin not finite or <= 0, no summary_dev, a half with a count > 0 and one of its
+ * pointers NULL (the vertices need labels_qv_dev and margin_qv_dev too, and 2 <= n_palette <= 256).  click_obj is not
+ * checked against n_classes: the session's clicks are its objects. */
+typedef struct a3d_session_guide_summary {
+  int32_t  voxels[256];
+  int32_t  contested[256];
+  uint64_t least_key;               /* ~((margin bits << 32) | row); 0 = no row with a finite margin */
+  int32_t  err;                     /* bit 0 = a NaN margin, bit 1 = an inverse_map entry out of range */
+  int32_t  reserved_;
+} a3d_session_guide_summary;
+typedef struct a3d_session_guide_args {
+  const float*   logits_dev;        /* [n_qv][n_classes] */
+  int64_t        n_qv;
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL */
+  int64_t        n_full;
+  const float*   colors_full_dev;   /* [n_full][3] */
+  const float*   palette_dev;       /* [n_palette][3] */
+  int32_t*       labels_qv_dev;     /* out [n_qv] */
+  int32_t*       runner_qv_dev;     /* out [n_qv] */
+  float*         margin_qv_dev;     /* out [n_qv] */
+  int32_t*       want_qv_dev;       /* out [n_qv] */
+  float*         margin_full_dev;   /* out [n_full] */
+  float*         colors_out_dev;    /* out [n_full][3] */
+  a3d_session_guide_summary* summary_dev;
+  int32_t        n_classes;
+  int32_t        n_palette;
+  int32_t        n_clicks;
+  float          threshold;
+  float          full_margin;
+  float          doubt[3];
+  int32_t        click_row[A3D_MAX_CLICKS];
+  uint8_t        click_obj[A3D_MAX_CLICKS];
+} a3d_session_guide_args;
+int    a3d_session_guide(const a3d_session_guide_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
  * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a

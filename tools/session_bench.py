@@ -5,7 +5,7 @@ overwrite, ``pred[inverse_map]``, ``.cpu().numpy()``, the per-object colour loop
 alternating, on one synthetic scene (~80 k voxels, ~250 k full-resolution vertices) at 1, 5, 10 and 20 clicks.
 
     python tools/session_bench.py [--voxels 80000] [--reps 60] [--out profiles/session_bench.json]
-                                  [--mesh-only | --render-only | --annotate-only | --edit-only]
+                                  [--mesh-only | --render-only | --annotate-only | --edit-only | --guide-only]
                                   [--section-only [--other-lib PATH]]
 
 Every stage is timed twice: with device events around it (what the GPU spent) and with a host clock around a stage that
@@ -41,6 +41,14 @@ The EDIT stage (``--edit-only``, a run of its own) times ``a3d_session_edit`` on
 annotate stage: the relabel with 5, 20 and 255 objects, over the scene's own labels and over labels no object claims (the
 whole table walked for every vertex), the remap of the voxel labels, and both in one call; then whole ``undo()`` /
 ``redo()`` calls at 20 clicks on the host clock, synchronised.  The figure to read: the relabel against 8 bytes per vertex.
+
+The GUIDE stage (``--guide-only``, a run of its own) times ``a3d_session_guide`` on the click scene with random logits of 3, 11
+and 21 columns and ten clicks, back to back like the annotate stage: its voxel pass alone (``n_full = 0``; the clear of the
+summary record is part of the call) next to ``a3d_argmax_labels`` on the same logits and clicks; both passes in one call,
+and the difference of the two as the full-resolution pass, next to ``a3d_session_paint`` without cubes on the same arrays.
+Then, with one click on each of C - 1 objects and the model's own logits, whole ``infer()`` and ``guide()`` calls on the host
+clock, synchronised.  The figures to read: the voxel pass against the arg-max (it reads the same logits and writes 16
+bytes per voxel where the arg-max writes 4), the full-resolution pass against the paint (16 bytes per vertex against 16).
 
 The SECTION stage (``--section-only``, a run of its own) times ONE view, the render stage's height field as a mesh at 640 x
 480 from the outside camera, three ways that alternate call by call in one process: ``a3d_render_mesh``;
@@ -402,6 +410,97 @@ def edit_stage(ses, xyz, lab, inst, calls, reps):
     return out
 
 
+def guide_stage(ses, xyz, calls, reps):
+    """``a3d_session_guide`` beside ``a3d_argmax_labels`` and ``a3d_session_paint``; ``guide()`` beside ``infer()`` (see the
+    module docstring)."""
+    import ctypes as C
+    from agile3d_amd import lib as L
+    lib, dev = ses.lib, ses.device
+    rng = np.random.default_rng(4)
+    n_full, n_qv = ses.coords_full.shape[0], ses.raw_coords_qv.shape[0]
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    lab, run, want, pred = (torch.empty(n_qv, dtype=torch.int32, device=dev) for _ in range(4))
+    margin = torch.empty(n_qv, dtype=torch.float32, device=dev)
+    margin_full, label_full = torch.empty(n_full, dtype=torch.float32, device=dev), torch.empty(n_full, dtype=torch.int32, device=dev)
+    colors_out = torch.empty((n_full, 3), dtype=torch.float32, device=dev)
+    summary = torch.empty(V.GUIDE_SUMMARY.itemsize, dtype=torch.uint8, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    click_rows = np.ascontiguousarray(rng.choice(n_qv, 10, replace=False), dtype=np.int32)
+
+    def back_to_back(fn):
+        per_call = []
+        for window in range(6):                     # (the first window warms up)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            per_call.append(a.elapsed_time(b) / calls)
+        return float(np.median(per_call[1:]))
+
+    print(f"\n== guide: {n_qv} voxels, {n_full} vertices; device ms per call, {calls} calls back to back, median of 5 windows ==")
+    out = {"voxels": int(n_qv), "vertices": int(n_full), "calls_back_to_back": calls, "columns": {}}
+    for c in (3, 11, 21):
+        logits = torch.from_numpy(rng.normal(0, 2, (n_qv, c)).astype(np.float32)).to(dev)
+        click_objs = np.ascontiguousarray(rng.integers(0, c, 10), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+
+        def argmax():
+            rc = lib.a3d_argmax_labels(logits.data_ptr(), n_qv, c, click_rows.ctypes.data_as(ip), click_objs.ctypes.data_as(ip), 10,
+                                       pred.data_ptr(), stream)
+            assert rc == 0, lib.a3d_last_error()
+
+        def guide_args(full):
+            a = L.SessionGuideArgs()
+            a.logits_dev, a.n_qv, a.n_classes = logits.data_ptr(), n_qv, c
+            a.labels_qv_dev, a.runner_qv_dev, a.margin_qv_dev, a.want_qv_dev = (t.data_ptr() for t in (lab, run, margin, want))
+            a.summary_dev, a.threshold, a.full_margin, a.n_clicks = summary.data_ptr(), 1.0, 4.0, 10
+            a.doubt[:] = [1.0, 1.0, 1.0]
+            for k in range(10):
+                a.click_row[k], a.click_obj[k] = int(click_rows[k]), int(click_objs[k])
+            if full:
+                a.inverse_map_dev, a.n_full, a.colors_full_dev = ses.inverse_map.data_ptr(), n_full, ses.colors_full.data_ptr()
+                a.palette_dev, a.n_palette = ses._palette_dev.data_ptr(), ses._palette_dev.shape[0]
+                a.margin_full_dev, a.colors_out_dev = margin_full.data_ptr(), colors_out.data_ptr()
+
+            def fn():
+                rc = lib.a3d_session_guide(C.byref(a), stream)
+                assert rc == 0, lib.a3d_last_error()
+            return fn
+
+        def paint():
+            V.session_paint(lab, ses.inverse_map, ses.coords_full, ses.colors_full, ses._palette_dev, None, ses.cube_size,
+                            labels_out=label_full, colors_out=colors_out, err=err)
+
+        ms = {"argmax_labels": back_to_back(argmax), "guide_voxels": back_to_back(guide_args(False)),
+              "guide_both": back_to_back(guide_args(True)), "session_paint": back_to_back(paint)}
+        assert torch.equal(pred, lab)                   # the same labels, row for row
+        ms["guide_full"] = ms["guide_both"] - ms["guide_voxels"]
+        ms["voxels_over_argmax"] = ms["guide_voxels"] / ms["argmax_labels"]
+        ms["full_over_paint"] = ms["guide_full"] / ms["session_paint"]
+        # whole calls with the model's own logits: one click on each of c - 1 objects
+        ses.reset()
+        for k, row in enumerate(rng.choice(n_full, c - 1, replace=False)):
+            ses.click(xyz[row], k + 1)
+        host = {"infer": [], "guide": []}
+        for _ in range(reps):
+            for name, call in (("infer", ses.infer), ("guide", ses.guide)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call()
+                torch.cuda.synchronize()
+                host[name].append(1e3 * (time.perf_counter() - t0))
+        ms["host_ms"] = {k: float(np.median(v[reps // 4:])) for k, v in host.items()}
+        out["columns"][str(c)] = ms
+        print(f"C = {c:2d}   argmax {ms['argmax_labels']:.4f}  guide voxels {ms['guide_voxels']:.4f} (x{ms['voxels_over_argmax']:.2f})  "
+              f"guide both {ms['guide_both']:.4f}  full pass {ms['guide_full']:.4f}  paint {ms['session_paint']:.4f} "
+              f"(x{ms['full_over_paint']:.2f})   host ms: infer() {ms['host_ms']['infer']:.3f}  guide() {ms['host_ms']['guide']:.3f}")
+    ses.reset()
+    return out
+
+
 def section_stage(ses, n_vertices, reps, other_lib):
     """One view, with and without a section, next to another build of the library (see the module docstring)."""
     import ctypes as C
@@ -550,6 +649,7 @@ def main():
     ap.add_argument("--render-only", action="store_true", help="run the render stage alone")
     ap.add_argument("--annotate-only", action="store_true", help="run the annotate stage alone")
     ap.add_argument("--edit-only", action="store_true", help="run the edit stage (a3d_session_edit, undo / redo) alone")
+    ap.add_argument("--guide-only", action="store_true", help="run the guide stage (a3d_session_guide, guide()) alone")
     ap.add_argument("--section-only", action="store_true", help="run the section stage (one view with and without a section) alone")
     ap.add_argument("--other-lib", default=None, help="section stage: another build of libagile3d_hip.so to time beside this one")
     a = ap.parse_args()
@@ -572,7 +672,7 @@ def main():
     original = col.copy()
     centre = xyz.mean(0)
     result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
-    alone = a.mesh_only or a.render_only or a.annotate_only or a.edit_only or a.section_only
+    alone = a.mesh_only or a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only
     for n_clicks in (() if alone else (1, 5, 10, 20)):
         ses.reset()
         objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
@@ -679,13 +779,15 @@ def main():
         print(f"whole click, staged (host ms): session {entry['session_click_ms']:.3f}  baseline {entry['baseline_click_ms']:.3f}")
     if a.edit_only:
         result["edit"] = edit_stage(ses, xyz, lab, inst, a.mesh_calls, a.reps)
+    if a.guide_only:
+        result["guide"] = guide_stage(ses, xyz, a.mesh_calls, a.reps)
     if a.section_only:
         result["section"] = section_stage(ses, n_full, a.reps, a.other_lib)
-    if not (a.render_only or a.annotate_only or a.edit_only or a.section_only):
+    if not (a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only):
         result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
-    if not (a.mesh_only or a.annotate_only or a.edit_only or a.section_only):
+    if not (a.mesh_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only):
         result["render"] = render_stage(ses, n_full, a.reps, a.warmup)
-    if not (a.mesh_only or a.render_only or a.edit_only or a.section_only):
+    if not (a.mesh_only or a.render_only or a.edit_only or a.section_only or a.guide_only):
         result["annotate"] = annotate_stage(ses, n_full, a.mesh_calls)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
