@@ -25,14 +25,6 @@ from . import lib as L
 _KVOL = {L.OP_CONV3: 27, L.OP_DOWN: 8, L.OP_UP: 8, L.OP_LINEAR: 1}
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 _arena: dict = {}
 _POISON = __import__("os").environ.get("A3D_POISON", "0") == "1"   # debugging aid, see tests/conftest.py
 
@@ -82,9 +74,14 @@ def pack_weight(w: torch.Tensor) -> torch.Tensor:
     lib = L.load()
     w = w.contiguous()
     out = torch.empty(lib.a3d_conv_weight_packed_floats(w.shape[0], w.shape[1], w.shape[2]), dtype=torch.float32, device=w.device)
-    L.check(lib.a3d_pack_conv_weight(_ptr(w), w.shape[0], w.shape[1], w.shape[2], _ptr(out), _stream()),
+    L.check(lib.a3d_pack_conv_weight(L.ptr(w), w.shape[0], w.shape[1], w.shape[2], L.ptr(out), L.stream()),
             "a3d_pack_conv_weight")
     return out
+
+
+def pack_weights_multi(table, n_jobs, n_chunks):
+    """a3d_pack_conv_weights_multi: every job of ``table`` (lib.pack_job_table) repacked by one launch."""
+    L.check(L.load().a3d_pack_conv_weights_multi(table.data_ptr(), n_jobs, n_chunks, L.stream()), "a3d_pack_conv_weights_multi")
 
 
 def run_conv(scene, kind, level_in, w_packed, x, cin, cout):
@@ -112,7 +109,7 @@ def run_conv(scene, kind, level_in, w_packed, x, cin, cout):
         off = lib.a3d_program_buffer_offset(scene.handle, bufs, 2, i)
         return ws[off:off + (rows + 1) * ch * 4].view(torch.float32).view(rows + 1, ch)
     view(0, n_in, cin)[:n_in].copy_(x)
-    L.check(lib.a3d_program_run(scene.handle, bufs, 2, ops, 1, None, None, 0, _ptr(ws), nbytes, _stream()),
+    L.check(lib.a3d_program_run(scene.handle, bufs, 2, ops, 1, None, None, 0, L.ptr(ws), nbytes, L.stream()),
             "a3d_program_run")
     return view(1, n_out, cout)[:n_out].clone()
 
@@ -135,8 +132,8 @@ def conv_apply(scene, kind, level_in, w_packed, x, cin, cout, out=None, out_cols
     if nbytes == 0:
         raise L.A3DError(lib.a3d_last_error().decode())
     ws = _workspace(nbytes, x.device, "conv")
-    L.check(lib.a3d_conv_apply(scene.handle, kind, level_in, _ptr(x), x.shape[1], cin, _ptr(w_packed), cout,
-                               C.c_void_p(y.data_ptr()), ldy, int(zero_row), _ptr(ws), ws.numel(), _stream()),
+    L.check(lib.a3d_conv_apply(scene.handle, kind, level_in, L.ptr(x), x.shape[1], cin, L.ptr(w_packed), cout,
+                               C.c_void_p(y.data_ptr()), ldy, int(zero_row), L.ptr(ws), ws.numel(), L.stream()),
             "a3d_conv_apply")
     return out
 
@@ -152,9 +149,9 @@ def conv_apply_acc(scene, kind, level_in, w_packed, x, cin, cout, y, acc=False, 
     if nbytes == 0:
         raise L.A3DError(lib.a3d_last_error().decode())
     ws = _workspace(nbytes, x.device, "conv")
-    L.check(lib.a3d_conv_apply_acc(scene.handle, kind, level_in, _ptr(x), x.stride(0), cin, _ptr(w_packed), cout,
-                                   _ptr(y), y.stride(0), int(zero_row), _ptr(y) if acc else None, y.stride(0) if acc else 0,
-                                   state.take() if state is not None else None, _ptr(ws), ws.numel(), _stream()),
+    L.check(lib.a3d_conv_apply_acc(scene.handle, kind, level_in, L.ptr(x), x.stride(0), cin, L.ptr(w_packed), cout,
+                                   L.ptr(y), y.stride(0), int(zero_row), L.ptr(y) if acc else None, y.stride(0) if acc else 0,
+                                   state.take() if state is not None else None, L.ptr(ws), ws.numel(), L.stream()),
             "a3d_conv_apply_acc")
     return y
 
@@ -186,11 +183,11 @@ def conv_bn_train_forward(scene, kind, level_in, w_packed, x, cin, cout, gamma, 
         raise L.A3DError(lib.a3d_last_error().decode())
     ws = _workspace(nbytes, x.device, "convbn")
     res = _rows(res) if res is not None else None
-    L.check(lib.a3d_conv_bn_train_forward(scene.handle, kind, level_in, _ptr(x), x.stride(0), cin, _ptr(w_packed), cout,
-                                          _ptr(raw), cout, _ptr(gamma), _ptr(beta), eps, _ptr(res),
-                                          res.stride(0) if res is not None else 0, int(relu), _ptr(y), y.stride(0), 1,
-                                          _ptr(mean), _ptr(rstd), _ptr(running_mean), _ptr(running_var), momentum,
-                                          state.take() if state is not None else None, _ptr(ws), ws.numel(), _stream()),
+    L.check(lib.a3d_conv_bn_train_forward(scene.handle, kind, level_in, L.ptr(x), x.stride(0), cin, L.ptr(w_packed), cout,
+                                          L.ptr(raw), cout, L.ptr(gamma), L.ptr(beta), eps, L.ptr(res),
+                                          res.stride(0) if res is not None else 0, int(relu), L.ptr(y), y.stride(0), 1,
+                                          L.ptr(mean), L.ptr(rstd), L.ptr(running_mean), L.ptr(running_var), momentum,
+                                          state.take() if state is not None else None, L.ptr(ws), ws.numel(), L.stream()),
             "a3d_conv_bn_train_forward")
     return raw, mean, rstd
 
@@ -211,10 +208,10 @@ def conv_dgrad_bn(scene, kind, level_in, part, dy, cout_fwd, out, acc, y, raw, m
     ws = _workspace(nbytes, dy.device, "convbn")
     sums = torch.empty((2, width), dtype=torch.float64, device=dy.device)
     yy = _rows(y) if relu else None
-    L.check(lib.a3d_conv_dgrad_bn(scene.handle, back_kind, lo, _ptr(dy), dy.stride(0), cout_fwd, _ptr(wp), width, _ptr(out),
-                                  out.stride(0), int(acc), _ptr(yy), yy.stride(0) if yy is not None else 0, _ptr(raw),
-                                  raw.stride(0), _ptr(mean), _ptr(rstd), int(relu), _ptr(sums),
-                                  state.take() if state is not None else None, _ptr(ws), ws.numel(), _stream()),
+    L.check(lib.a3d_conv_dgrad_bn(scene.handle, back_kind, lo, L.ptr(dy), dy.stride(0), cout_fwd, L.ptr(wp), width, L.ptr(out),
+                                  out.stride(0), int(acc), L.ptr(yy), yy.stride(0) if yy is not None else 0, L.ptr(raw),
+                                  raw.stride(0), L.ptr(mean), L.ptr(rstd), int(relu), L.ptr(sums),
+                                  state.take() if state is not None else None, L.ptr(ws), ws.numel(), L.stream()),
             "a3d_conv_dgrad_bn")
     return sums
 
@@ -227,9 +224,9 @@ def bn_backward_from_sums(x, g, gamma, mean, rstd, sums, dx):
     x, g = _rows(x), _rows(g)
     dgamma = torch.empty(C_, dtype=torch.float32, device=x.device)
     dbeta = torch.empty_like(dgamma)
-    L.check(lib.a3d_bn_backward_apply(_ptr(x), x.stride(0), None, 0, _ptr(g), g.stride(0), n, C_, _ptr(gamma), _ptr(mean),
-                                      _ptr(rstd), 0, _ptr(sums), n, _ptr(sums), _ptr(dx), dx.stride(0), None, 0, _ptr(dgamma),
-                                      _ptr(dbeta), 1, _stream()), "a3d_bn_backward_apply")
+    L.check(lib.a3d_bn_backward_apply(L.ptr(x), x.stride(0), None, 0, L.ptr(g), g.stride(0), n, C_, L.ptr(gamma), L.ptr(mean),
+                                      L.ptr(rstd), 0, L.ptr(sums), n, L.ptr(sums), L.ptr(dx), dx.stride(0), None, 0, L.ptr(dgamma),
+                                      L.ptr(dbeta), 1, L.stream()), "a3d_bn_backward_apply")
     return dgamma, dbeta
 
 
@@ -243,10 +240,10 @@ def bn_train_backward_into(x, y, dy, gamma, mean, rstd, relu, dx, dres=None):
     dgamma = torch.empty(C_, dtype=torch.float32, device=x.device)
     dbeta = torch.empty_like(dgamma)
     ws = _ws(n, C_, x.device)
-    L.check(lib.a3d_bn_train_backward(_ptr(x), x.stride(0), _ptr(yy), yy.stride(0) if yy is not None else 0, _ptr(dy),
-                                      dy.stride(0), n, C_, _ptr(gamma), _ptr(mean), _ptr(rstd), int(relu), _ptr(dx),
-                                      dx.stride(0), _ptr(dres), dres.stride(0) if dres is not None else 0, _ptr(dgamma),
-                                      _ptr(dbeta), 1, _ptr(ws), ws.numel(), _stream()), "a3d_bn_train_backward")
+    L.check(lib.a3d_bn_train_backward(L.ptr(x), x.stride(0), L.ptr(yy), yy.stride(0) if yy is not None else 0, L.ptr(dy),
+                                      dy.stride(0), n, C_, L.ptr(gamma), L.ptr(mean), L.ptr(rstd), int(relu), L.ptr(dx),
+                                      dx.stride(0), L.ptr(dres), dres.stride(0) if dres is not None else 0, L.ptr(dgamma),
+                                      L.ptr(dbeta), 1, L.ptr(ws), ws.numel(), L.stream()), "a3d_bn_train_backward")
     return dgamma, dbeta
 
 
@@ -315,8 +312,8 @@ def conv_weight_grad(scene, kind, level_in, x: torch.Tensor, dy: torch.Tensor) -
     if nbytes == 0:
         raise L.A3DError(lib.a3d_last_error().decode())
     ws = _workspace(nbytes, x.device, "wgrad")
-    L.check(lib.a3d_conv_wgrad(scene.handle, kind, level_in, _ptr(x), x.stride(0), _ptr(dy), dy.stride(0), cin, cout,
-                               _ptr(dw), _ptr(ws), ws.numel(), _stream()), "a3d_conv_wgrad")
+    L.check(lib.a3d_conv_wgrad(scene.handle, kind, level_in, L.ptr(x), x.stride(0), L.ptr(dy), dy.stride(0), cin, cout,
+                               L.ptr(dw), L.ptr(ws), ws.numel(), L.stream()), "a3d_conv_wgrad")
     return dw
 
 
@@ -340,9 +337,9 @@ def bn_train_forward(x, gamma, beta, eps=1e-5, res=None, relu=False, running_mea
     rstd = torch.empty_like(mean)
     res = res.contiguous() if res is not None else None
     ws = _ws(n, C_, x.device)
-    L.check(lib.a3d_bn_train_forward(_ptr(x), C_, n, C_, _ptr(gamma), _ptr(beta), eps, _ptr(res), C_, int(relu), _ptr(y),
-                                     C_, _ptr(mean), _ptr(rstd), _ptr(running_mean), _ptr(running_var), momentum,
-                                     int(zero_row), _ptr(ws), ws.numel(), _stream()), "a3d_bn_train_forward")
+    L.check(lib.a3d_bn_train_forward(L.ptr(x), C_, n, C_, L.ptr(gamma), L.ptr(beta), eps, L.ptr(res), C_, int(relu), L.ptr(y),
+                                     C_, L.ptr(mean), L.ptr(rstd), L.ptr(running_mean), L.ptr(running_var), momentum,
+                                     int(zero_row), L.ptr(ws), ws.numel(), L.stream()), "a3d_bn_train_forward")
     return y, mean, rstd
 
 
@@ -358,9 +355,9 @@ def bn_train_backward(x, y, dy, gamma, mean, rstd, relu=False, want_dres=False, 
     dgamma = torch.empty(C_, dtype=torch.float32, device=x.device)
     dbeta = torch.empty_like(dgamma)
     ws = _ws(n, C_, x.device)
-    L.check(lib.a3d_bn_train_backward(_ptr(x), C_, _ptr(y.contiguous()) if relu else None, C_, _ptr(dy), C_, n, C_,
-                                      _ptr(gamma), _ptr(mean), _ptr(rstd), int(relu), _ptr(dx), C_, _ptr(dres), C_,
-                                      _ptr(dgamma), _ptr(dbeta), int(zero_row), _ptr(ws), ws.numel(), _stream()),
+    L.check(lib.a3d_bn_train_backward(L.ptr(x), C_, L.ptr(y.contiguous()) if relu else None, C_, L.ptr(dy), C_, n, C_,
+                                      L.ptr(gamma), L.ptr(mean), L.ptr(rstd), int(relu), L.ptr(dx), C_, L.ptr(dres), C_,
+                                      L.ptr(dgamma), L.ptr(dbeta), int(zero_row), L.ptr(ws), ws.numel(), L.stream()),
             "a3d_bn_train_backward")
     return dx, dgamma, dbeta, dres
 
@@ -378,7 +375,7 @@ def bn_sync_forward(x, gamma, beta, eps=1e-5, res=None, relu=False, running_mean
     n, C_ = x.shape
     ws = _ws(n, C_, x.device)
     st = torch.empty(2 * C_ + 1, dtype=torch.float64, device=x.device)
-    L.check(lib.a3d_bn_local_stats(_ptr(x), C_, n, C_, _ptr(st), _ptr(ws), ws.numel(), _stream()), "a3d_bn_local_stats")
+    L.check(lib.a3d_bn_local_stats(L.ptr(x), C_, n, C_, L.ptr(st), L.ptr(ws), ws.numel(), L.stream()), "a3d_bn_local_stats")
     st[2 * C_] = float(n)
     from .optim import dist_all_gather
     allst = dist_all_gather(st, group)                           # [world, 2C+1]
@@ -395,8 +392,8 @@ def bn_sync_forward(x, gamma, beta, eps=1e-5, res=None, relu=False, running_mean
         running_var.mul_(1.0 - momentum).add_(unbiased, alpha=momentum)
     y = torch.empty((n + 1 if zero_row else n, C_), dtype=torch.float32, device=x.device)
     res = res.contiguous() if res is not None else None
-    L.check(lib.a3d_bn_apply(_ptr(x), C_, n, C_, _ptr(gamma), _ptr(beta), _ptr(mean_f), _ptr(rstd), _ptr(res), C_,
-                             int(relu), _ptr(y), C_, int(zero_row), _stream()), "a3d_bn_apply")
+    L.check(lib.a3d_bn_apply(L.ptr(x), C_, n, C_, L.ptr(gamma), L.ptr(beta), L.ptr(mean_f), L.ptr(rstd), L.ptr(res), C_,
+                             int(relu), L.ptr(y), C_, int(zero_row), L.stream()), "a3d_bn_apply")
     return y, mean_f, rstd, int(n_glob.item())
 
 
@@ -410,8 +407,8 @@ def bn_sync_backward(x, y, dy, gamma, mean, rstd, n_global, relu=False, want_dre
     ws = _ws(n, C_, x.device)
     local = torch.empty(2 * C_, dtype=torch.float64, device=x.device)
     yy = y.contiguous() if relu else None
-    L.check(lib.a3d_bn_backward_sums(_ptr(x), C_, _ptr(yy), C_, _ptr(dy), C_, n, C_, _ptr(mean), _ptr(rstd), int(relu),
-                                     _ptr(local), _ptr(ws), ws.numel(), _stream()), "a3d_bn_backward_sums")
+    L.check(lib.a3d_bn_backward_sums(L.ptr(x), C_, L.ptr(yy), C_, L.ptr(dy), C_, n, C_, L.ptr(mean), L.ptr(rstd), int(relu),
+                                     L.ptr(local), L.ptr(ws), ws.numel(), L.stream()), "a3d_bn_backward_sums")
     from .optim import dist_all_reduce
     glob = dist_all_reduce(local.clone(), group)
     rows = n + 1 if zero_row else n
@@ -419,9 +416,9 @@ def bn_sync_backward(x, y, dy, gamma, mean, rstd, n_global, relu=False, want_dre
     dres = torch.empty((rows, C_), dtype=torch.float32, device=x.device) if want_dres else None
     dgamma = torch.empty(C_, dtype=torch.float32, device=x.device)
     dbeta = torch.empty_like(dgamma)
-    L.check(lib.a3d_bn_backward_apply(_ptr(x), C_, _ptr(yy), C_, _ptr(dy), C_, n, C_, _ptr(gamma), _ptr(mean), _ptr(rstd),
-                                      int(relu), _ptr(glob), int(n_global), _ptr(local), _ptr(dx), C_, _ptr(dres), C_,
-                                      _ptr(dgamma), _ptr(dbeta), int(zero_row), _stream()), "a3d_bn_backward_apply")
+    L.check(lib.a3d_bn_backward_apply(L.ptr(x), C_, L.ptr(yy), C_, L.ptr(dy), C_, n, C_, L.ptr(gamma), L.ptr(mean), L.ptr(rstd),
+                                      int(relu), L.ptr(glob), int(n_global), L.ptr(local), L.ptr(dx), C_, L.ptr(dres), C_,
+                                      L.ptr(dgamma), L.ptr(dbeta), int(zero_row), L.stream()), "a3d_bn_backward_apply")
     return dx, dgamma, dbeta, dres
 
 
@@ -431,7 +428,7 @@ def column_sums(x):
     n, C_ = x.shape
     out = torch.empty(C_, dtype=torch.float32, device=x.device)
     ws = _ws(n, C_, x.device)
-    L.check(lib.a3d_column_sums(_ptr(x), C_, n, C_, _ptr(out), _ptr(ws), ws.numel(), _stream()), "a3d_column_sums")
+    L.check(lib.a3d_column_sums(L.ptr(x), C_, n, C_, L.ptr(out), L.ptr(ws), ws.numel(), L.stream()), "a3d_column_sums")
     return out
 
 
@@ -446,8 +443,8 @@ def stem_weight_grad(scene, feats3, dy, kernel_volume=125):
     if nbytes == 0:
         raise L.A3DError("stem_weight_grad: kernel volume must be 125 or 27")
     ws = _workspace(nbytes, dy.device, "stem_wgrad")
-    L.check(lib.a3d_stem_wgrad(scene.handle, _ptr(feats3), _ptr(dy), dy.stride(0), kernel_volume, _ptr(dw), _ptr(ws),
-                               ws.numel(), _stream()), "a3d_stem_wgrad")
+    L.check(lib.a3d_stem_wgrad(scene.handle, L.ptr(feats3), L.ptr(dy), dy.stride(0), kernel_volume, L.ptr(dw), L.ptr(ws),
+                               ws.numel(), L.stream()), "a3d_stem_wgrad")
     return dw
 
 
@@ -456,7 +453,7 @@ def layernorm_forward(x, gamma, beta, eps=1e-5):
     x = x.contiguous()
     n, C_ = x.shape
     y = torch.empty_like(x)
-    L.check(lib.a3d_layernorm_forward(_ptr(x), C_, n, C_, _ptr(gamma), _ptr(beta), eps, _ptr(y), C_, _stream()),
+    L.check(lib.a3d_layernorm_forward(L.ptr(x), C_, n, C_, L.ptr(gamma), L.ptr(beta), eps, L.ptr(y), C_, L.stream()),
             "a3d_layernorm_forward")
     return y
 
@@ -470,8 +467,8 @@ def layernorm_backward(x, dy, gamma, eps=1e-5):
     dgamma = torch.empty(C_, dtype=torch.float32, device=x.device)
     dbeta = torch.empty_like(dgamma)
     ws = _ws(n, C_, x.device)
-    L.check(lib.a3d_layernorm_backward(_ptr(x), C_, _ptr(dy), C_, n, C_, _ptr(gamma), eps, _ptr(dx), _ptr(dgamma),
-                                       _ptr(dbeta), _ptr(ws), ws.numel(), _stream()), "a3d_layernorm_backward")
+    L.check(lib.a3d_layernorm_backward(L.ptr(x), C_, L.ptr(dy), C_, n, C_, L.ptr(gamma), eps, L.ptr(dx), L.ptr(dgamma),
+                                       L.ptr(dbeta), L.ptr(ws), ws.numel(), L.stream()), "a3d_layernorm_backward")
     return dx, dgamma, dbeta
 
 
@@ -486,7 +483,7 @@ def linear_weight_grad(x, dy):
         raise L.A3DError(lib.a3d_last_error().decode())
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     dw = torch.empty((cin, cout), dtype=torch.float32, device=x.device)
-    L.check(lib.a3d_linear_wgrad(_ptr(x), cin, _ptr(dy), cout, n, cin, cout, _ptr(dw), _ptr(ws), nbytes, _stream()),
+    L.check(lib.a3d_linear_wgrad(L.ptr(x), cin, L.ptr(dy), cout, n, cin, cout, L.ptr(dw), L.ptr(ws), nbytes, L.stream()),
             "a3d_linear_wgrad")
     return dw
 
@@ -508,6 +505,6 @@ def linear_weight_grad_into(x, dy, dw, transposed=True, accumulate=False, db=Non
     if nbytes == 0:
         raise L.A3DError(lib.a3d_last_error().decode())
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    L.check(lib.a3d_linear_wgrad_into(_ptr(x), cin, _ptr(dy), cout, n, cin, cout, _ptr(dw), want[1], 1 if transposed else 0,
-                                      1 if accumulate else 0, _ptr(db) if db is not None else None, 1 if db_accumulate else 0,
-                                      _ptr(ws), nbytes, _stream()), "a3d_linear_wgrad_into")
+    L.check(lib.a3d_linear_wgrad_into(L.ptr(x), cin, L.ptr(dy), cout, n, cin, cout, L.ptr(dw), want[1], 1 if transposed else 0,
+                                      1 if accumulate else 0, L.ptr(db) if db is not None else None, 1 if db_accumulate else 0,
+                                      L.ptr(ws), nbytes, L.stream()), "a3d_linear_wgrad_into")

@@ -25,10 +25,6 @@ def _i32(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.int32).contiguous()
 
 
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _host_i32(values):
     a = np.ascontiguousarray(values, dtype=np.int32)
     return a, a.ctypes.data_as(C.POINTER(C.c_int32))
@@ -49,7 +45,7 @@ def argmax_labels(logits: torch.Tensor, click_idx: dict | None = None) -> torch.
     o, op = _host_i32(objs)
     pred = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
     L.check(lib.a3d_argmax_labels(logits.data_ptr(), logits.shape[0], logits.shape[1], rp, op, len(rows),
-                                  pred.data_ptr(), _stream(logits)), "a3d_argmax_labels")
+                                  pred.data_ptr(), L.stream(logits.device)), "a3d_argmax_labels")
     return pred
 
 
@@ -88,7 +84,7 @@ def argmax_labels_batch(logits_list, click_idx_list=None):
     ws = _ws_cache.get(key)
     if ws is None:
         ws = _ws_cache[key] = torch.empty(lib.a3d_argmax_labels_batch_workspace_bytes(ns), dtype=torch.uint8, device=dev)
-    L.check(lib.a3d_argmax_labels_batch(C.cast(arr, C.c_void_p), ns, ws.data_ptr(), ws.numel(), _stream(logits_list[0])),
+    L.check(lib.a3d_argmax_labels_batch(C.cast(arr, C.c_void_p), ns, ws.data_ptr(), ws.numel(), L.stream(logits_list[0].device)),
             "a3d_argmax_labels_batch")
     return preds
 
@@ -108,7 +104,7 @@ def iou_counts(pred, labels, inverse_map=None, n_ids: int | None = None) -> np.n
     n_ids = 256 if n_ids is None else n_ids
     counts = torch.empty(3 * n_ids + 1, dtype=torch.int64, device=p.device)
     L.check(lib.a3d_iou_counts(p.data_ptr(), p.numel(), inv.data_ptr() if inv is not None else None, l.data_ptr(),
-                               l.numel(), n_ids, counts.data_ptr(), _stream(p)), "a3d_iou_counts")
+                               l.numel(), n_ids, counts.data_ptr(), L.stream(p.device)), "a3d_iou_counts")
     host = counts.cpu().numpy()
     if host[-1]:
         raise RuntimeError("iou_counts: inverse_map holds rows outside the prediction")
@@ -138,7 +134,7 @@ def _launch_iou_counts(preds, labels, inverse_maps, n_ids, counts):
             sp = arr[k]
             sp.pred_dev, sp.n_pred, sp.inverse_map_dev = p.data_ptr(), p.numel(), inv.data_ptr() if inv is not None else None
             sp.labels_dev, sp.n_full = l.data_ptr(), l.numel()
-        L.check(lib.a3d_iou_counts_batch(C.cast(arr, C.c_void_p), len(part), n_ids, counts[c0].data_ptr(), _stream(counts)),
+        L.check(lib.a3d_iou_counts_batch(C.cast(arr, C.c_void_p), len(part), n_ids, counts[c0].data_ptr(), L.stream(counts.device)),
                 "a3d_iou_counts_batch")
     return keep
 
@@ -203,7 +199,7 @@ def _launch_clusters(p, l, xyz, work, out):
         raise RuntimeError("error_clusters: pred [N], labels [N], coords [N,3] expected")
     L.check(L.load().a3d_click_clusters(xyz.data_ptr(), p.data_ptr(), l.data_ptr(), n, out.data_ptr(), MAX_CLUSTERS,
                                         out.data_ptr() + MAX_CLUSTERS * C.sizeof(L.ClickCluster), work.data_ptr(),
-                                        work.numel(), _stream(p)), "a3d_click_clusters")
+                                        work.numel(), L.stream(p.device)), "a3d_click_clusters")
 
 
 def _parse_clusters(host: np.ndarray):
@@ -255,7 +251,7 @@ def _spatial_order(xyz):
         inv = torch.empty(n, dtype=torch.int32, device=xyz.device)
         ws = torch.empty(lib.a3d_click_spatial_order_workspace_bytes(n), dtype=torch.uint8, device=xyz.device)
         L.check(lib.a3d_click_spatial_order(xyz.data_ptr(), n, order.data_ptr(), inv.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            _stream(xyz)), "a3d_click_spatial_order")
+                                            L.stream(xyz.device)), "a3d_click_spatial_order")
         hit = (order, inv)
         while len(_order_cache) >= 256:
             _order_cache.pop(next(iter(_order_cache)))
@@ -300,7 +296,7 @@ def _launch_clusters_batch(preds, labels, coords):
         sp.workspace_dev, sp.workspace_bytes = work.data_ptr(), work.numel()
         so = _spatial_order(x)
         sp.order_dev, sp.inv_dev = (so[0].data_ptr(), so[1].data_ptr()) if so is not None else (None, None)
-    L.check(lib.a3d_click_clusters_batch(C.cast(arr, C.c_void_p), len(live), _stream(live[0][0])), "a3d_click_clusters_batch")
+    L.check(lib.a3d_click_clusters_batch(C.cast(arr, C.c_void_p), len(live), L.stream(live[0][0].device)), "a3d_click_clusters_batch")
     host.copy_(out, non_blocking=True)
     keep.append(live)
     return host, slots, keep
@@ -439,6 +435,6 @@ def cal_click_loss_weights(batch_idx, raw_coords, labels, click_idx, alpha=0.8, 
         r, rp = _host_i32(rows)
         w = torch.empty(xyz.shape[0], dtype=torch.float32, device=xyz.device)
         L.check(lib.a3d_click_loss_weights(xyz.data_ptr(), xyz.shape[0], rp, len(rows), tita, alpha, beta,
-                                           w.data_ptr(), _stream(xyz)), "a3d_click_loss_weights")
+                                           w.data_ptr(), L.stream(xyz.device)), "a3d_click_loss_weights")
         weights.append(w)
     return weights

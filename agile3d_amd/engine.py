@@ -22,14 +22,7 @@ from . import lib as L
 from .sparse import SparseTensor
 
 BN_EPS = 1e-5
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+_ptr, _stream = L.ptr, L.stream      # DEPRECATED, no caller in this repository: tests written before lib.ptr / lib.stream import them
 
 
 class Scene:
@@ -45,7 +38,7 @@ class Scene:
             raise L.A3DError(f"cannot build a scene of {n} voxels")
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=coords.device)
         h = C.c_void_p()
-        L.check(lib.a3d_scene_create(_ptr(self.coords), n, _ptr(self.workspace), nbytes, _stream(), C.byref(h)),
+        L.check(lib.a3d_scene_create(L.ptr(self.coords), n, L.ptr(self.workspace), nbytes, L.stream(), C.byref(h)),
                 "a3d_scene_create")
         self.handle = h
         self.n = [int(lib.a3d_scene_level_size(h, i)) for i in range(L.A3D_NUM_LEVELS)]
@@ -65,7 +58,7 @@ class Scene:
             lib = L.load()
             nbytes = lib.a3d_scene_wgrad_lists_bytes(self.handle)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.workspace.device)
-            L.check(lib.a3d_scene_build_wgrad_lists(self.handle, _ptr(ws), nbytes, _stream()), "a3d_scene_build_wgrad_lists")
+            L.check(lib.a3d_scene_build_wgrad_lists(self.handle, L.ptr(ws), nbytes, L.stream()), "a3d_scene_build_wgrad_lists")
             self._wgrad_lists = ws
 
     def table(self, level: int, which: int) -> np.ndarray:
@@ -75,7 +68,7 @@ class Scene:
         L.check(lib.a3d_scene_table(self.handle, level, which, C.byref(p), C.byref(cnt)), "a3d_scene_table")
         dt = np.uint32 if which in (L.TAB_GMASK27, L.TAB_GMASKDOWN, L.TAB_GMASKUP) else np.int32
         out = np.empty(cnt.value, dtype=dt)
-        L.check(lib.a3d_memcpy_d2h(out.ctypes.data_as(C.c_void_p), p, out.nbytes, _stream()), "a3d_memcpy_d2h")
+        L.check(lib.a3d_memcpy_d2h(out.ctypes.data_as(C.c_void_p), p, out.nbytes, L.stream()), "a3d_memcpy_d2h")
         return out
 
     def table_dev(self, level: int, which: int) -> torch.Tensor:
@@ -136,7 +129,7 @@ class BackboneProgram:
             w = (conv.kernel3().detach() if w is None else w).to(dev, torch.float32).contiguous()
             K, cin, cout = w.shape
             out = torch.empty(lib.a3d_conv_weight_packed_floats(K, cin, cout), dtype=torch.float32, device=dev)
-            L.check(lib.a3d_pack_conv_weight(_ptr(w), K, cin, cout, _ptr(out), _stream()), "a3d_pack_conv_weight")
+            L.check(lib.a3d_pack_conv_weight(L.ptr(w), K, cin, cout, L.ptr(out), L.stream()), "a3d_pack_conv_weight")
             self.keep.append(out)
             return out
 
@@ -284,7 +277,7 @@ class BackboneProgram:
             raise L.A3DError("a3d_program_workspace_bytes: " + lib.a3d_last_error().decode())
         ws = torch.empty(nbytes, dtype=torch.uint8, device=feats.device)
         L.check(lib.a3d_program_run(scene.handle, self.bufs_arr, self.n_bufs, self.ops_arr, self.n_ops,
-                                    _ptr(feats), _ptr(out), out.shape[1], _ptr(ws), nbytes, _stream()),
+                                    L.ptr(feats), L.ptr(out), out.shape[1], L.ptr(ws), nbytes, L.stream()),
                 "a3d_program_run")
         return ws
 
@@ -333,7 +326,7 @@ class DecoderPack:
         def packed(wt_in_out):  # [in][out] -> MFMA fragment order
             w = wt_in_out.detach().to(dev, torch.float32).contiguous().unsqueeze(0)
             out = torch.empty_like(w)
-            L.check(lib.a3d_pack_conv_weight(_ptr(w), 1, w.shape[1], w.shape[2], _ptr(out), _stream()),
+            L.check(lib.a3d_pack_conv_weight(L.ptr(w), 1, w.shape[1], w.shape[2], L.ptr(out), L.stream()),
                     "a3d_pack_conv_weight")
             self.keep.append(out)
             return out.data_ptr()
@@ -379,11 +372,11 @@ class DecoderPack:
         # the query side's matrices once more, in the order the single-block layer kernel's waves read them
         for l in range(n_layers):
             qp = torch.empty(lib.a3d_decoder_query_pack_floats(W.dim_ff), dtype=torch.float32, device=dev)
-            L.check(lib.a3d_decoder_pack_query_weights(C.byref(W), l, _ptr(qp), _stream()), "a3d_decoder_pack_query_weights")
+            L.check(lib.a3d_decoder_pack_query_weights(C.byref(W), l, L.ptr(qp), L.stream()), "a3d_decoder_pack_query_weights")
             self.keep.append(qp)
             W.layers[l].query_pack = qp.data_ptr()
         mp = torch.empty(lib.a3d_decoder_mask_pack_floats(), dtype=torch.float32, device=dev)
-        L.check(lib.a3d_decoder_pack_query_weights(C.byref(W), -1, _ptr(mp), _stream()), "a3d_decoder_pack_query_weights")
+        L.check(lib.a3d_decoder_pack_query_weights(C.byref(W), -1, L.ptr(mp), L.stream()), "a3d_decoder_pack_query_weights")
         self.keep.append(mp)
         W.mask_pack = mp.data_ptr()
         self.W = W
@@ -632,12 +625,12 @@ class Engine:
             mm = torch.empty(6 if ns is None else (ns, 6), dtype=torch.float32, device=self.device)
             tmp = torch.empty(256 * 6 * 4 if ns is None else lib.a3d_posenc_batch_workspace_bytes(ns), dtype=torch.uint8,
                               device=self.device)
-        tail = (_ptr(mm), _ptr(pe), _ptr(tmp), tmp.numel() if norm else 0, _stream())
+        tail = (L.ptr(mm), L.ptr(pe), L.ptr(tmp), tmp.numel() if norm else 0, L.stream())
         table = self.decoder.posenc_table_ptr
         if ns is None:
-            L.check(lib.a3d_posenc(kind, norm, _ptr(raw), n, table, *tail), "a3d_posenc")
+            L.check(lib.a3d_posenc(kind, norm, L.ptr(raw), n, table, *tail), "a3d_posenc")
         else:
-            L.check(lib.a3d_posenc_batch(kind, norm, _ptr(raw), starts, ns, table, *tail), "a3d_posenc_batch")
+            L.check(lib.a3d_posenc_batch(kind, norm, L.ptr(raw), starts, ns, table, *tail), "a3d_posenc_batch")
         return pe, mm
 
     def _posenc_batch(self, raw, ranges):
@@ -717,18 +710,18 @@ class Engine:
                 a_rows, a_objs, a_times = arr(rows), arr(objs), arr(times)
                 keep += [ws, feats, a_rows, a_objs, a_times]
                 sp = samples[b]
-                sp.feats128_dev, sp.posenc_dev, sp.n = _ptr(feats), _ptr(st.posenc[b]), nb
+                sp.feats128_dev, sp.posenc_dev, sp.n = L.ptr(feats), L.ptr(st.posenc[b]), nb
                 sp.click_row = C.cast(a_rows, C.POINTER(C.c_int32))
                 sp.click_obj = C.cast(a_objs, C.POINTER(C.c_int32))
                 sp.click_time = C.cast(a_times, C.POINTER(C.c_int32))
                 sp.n_clicks, sp.n_objects = nc, K
-                sp.logits_dev, sp.workspace_dev, sp.workspace_bytes = _ptr(logits), _ptr(ws), wsb
-                sp.kv0_dev, sp.kv0_state = (_ptr(kv_bufs[b]), kv_state) if kv_state else (None, 0)
+                sp.logits_dev, sp.workspace_dev, sp.workspace_bytes = L.ptr(logits), L.ptr(ws), wsb
+                sp.kv0_dev, sp.kv0_state = (L.ptr(kv_bufs[b]), kv_state) if kv_state else (None, 0)
                 sp.kv0_blocks = int(kv_bufs[b].shape[0]) if kv_state else 0
                 for l in range(n_layers):
                     preds[l].append(logits[l])
             try:
-                L.check(lib.a3d_decoder_forward_batch(C.byref(W), samples, len(st.ranges), _stream()),
+                L.check(lib.a3d_decoder_forward_batch(C.byref(W), samples, len(st.ranges), L.stream()),
                         "a3d_decoder_forward_batch")
             except Exception:
                 st.kv0, st.kv0_version = None, None     # a failed call leaves no cache behind (filled or being read)

@@ -8,6 +8,9 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+import torch
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("A3D_LIB_PATH") or os.path.join(HERE, "libagile3d_hip.so")   # override: A/B of two builds
 
@@ -62,6 +65,17 @@ class PackJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("K", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
                 ("src_cin", C.c_int32), ("src_cout", C.c_int32), ("transposed", C.c_int32), ("flip", C.c_int32),
                 ("c0", C.c_int32), ("chunk0", C.c_int32), ("pad_", C.c_int32)]
+
+
+# the same record as numpy sees it: the rows of the table a3d_pack_conv_weights_multi reads
+PACK_JOB = np.dtype([("src", "<u8"), ("dst", "<u8"), ("K", "<i4"), ("cin", "<i4"), ("cout", "<i4"), ("src_cin", "<i4"),
+                     ("src_cout", "<i4"), ("transposed", "<i4"), ("flip", "<i4"), ("c0", "<i4"), ("chunk0", "<i4"), ("pad", "<i4")])
+assert C.sizeof(PackJob) == PACK_JOB.itemsize == 56
+
+
+def pack_job_table(rows, device):
+    """The device table (uint8) of a3d_pack_conv_weights_multi from job rows, one tuple in ``PACK_JOB``'s field order each."""
+    return torch.from_numpy(np.array(rows, dtype=PACK_JOB).view(np.uint8)).to(device)
 
 
 class ProfEntry(C.Structure):
@@ -439,6 +453,23 @@ def load():
                        "(include/agile3d_hip.h: A3D_ABI_VERSION); rebuild the library")
     _lib = lib
     return lib
+
+
+def ptr(t):
+    """The device pointer of ``t`` as the C ABI takes it (``None``: a null pointer); nothing is checked."""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # torch's own shortcut past the Stream object
+
+
+def stream(device=None):
+    """The current stream of ``device`` (a CUDA ``torch.device``; ``None``: the current device), what every library call launches
+    on: ``torch.cuda.current_stream(device).cuda_stream``, read without building the ``Stream`` object where torch allows."""
+    if _raw_stream is None or (device is not None and device.type != "cuda"):      # (torch refuses a device that is not CUDA)
+        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    index = torch.cuda.current_device() if device is None or device.index is None else device.index
+    return C.c_void_p(_raw_stream(index))
 
 
 def check(rc: int, what: str = ""):

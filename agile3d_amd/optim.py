@@ -9,20 +9,11 @@ Gradients are a dict {parameter name: tensor} as ``train_backbone.BackboneTape.b
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 
 from . import lib as L
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 MT_CHUNK = 4096   # A3D_MT_CHUNK
@@ -91,7 +82,7 @@ def total_grad_norm(grads: dict) -> float:
     tabd = _to_device(tab, dev)
     ws = torch.empty(lib.a3d_mt_workspace_bytes(nchunks), dtype=torch.uint8, device=dev)
     out = torch.empty(1, dtype=torch.float64, device=dev)
-    L.check(lib.a3d_sum_squares_multi(_ptr(tabd), len(gs), nchunks, _ptr(out), _ptr(ws), ws.numel(), _stream(gs[0])),
+    L.check(lib.a3d_sum_squares_multi(L.ptr(tabd), len(gs), nchunks, L.ptr(out), L.ptr(ws), ws.numel(), L.stream(gs[0].device)),
             "a3d_sum_squares_multi")
     return math.sqrt(float(out.item()))      # the one host synchronisation of the clip
 
@@ -163,8 +154,8 @@ class AdamW:
         tab["bias2_sqrt"] = np.sqrt(1.0 - self.betas[1] ** t)
         dev = self.params[names[0]].device
         tabd = _to_device(tab, dev)
-        L.check(lib.a3d_adamw_step_multi(_ptr(tabd), len(names), nchunks, self.lr, self.betas[0], self.betas[1], self.eps,
-                                         self.weight_decay, grad_scale, _stream(self.params[names[0]])), "a3d_adamw_step_multi")
+        L.check(lib.a3d_adamw_step_multi(L.ptr(tabd), len(names), nchunks, self.lr, self.betas[0], self.betas[1], self.eps,
+                                         self.weight_decay, grad_scale, L.stream(self.params[names[0]].device)), "a3d_adamw_step_multi")
 
 
 def dist_all_reduce(t, group=None):

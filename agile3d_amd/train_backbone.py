@@ -80,11 +80,6 @@ class PackedWeights:
         return hit[1], hit[2]
 
     def _build_table(self):
-        import numpy as np
-        dt = np.dtype([("src", "<u8"), ("dst", "<u8"), ("K", "<i4"), ("cin", "<i4"), ("cout", "<i4"), ("src_cin", "<i4"),
-                       ("src_cout", "<i4"), ("transposed", "<i4"), ("flip", "<i4"), ("c0", "<i4"), ("chunk0", "<i4"),
-                       ("pad", "<i4")])
-        assert dt.itemsize == 56
         rows, chunk, sig, dev = [], 0, [], None
         for key, (ver, wf, parts, conv, kind) in self._c.items():
             w = conv.kernel3().detach()
@@ -101,8 +96,7 @@ class PackedWeights:
             sig.append((key, w.data_ptr()))
         if not rows:
             return None
-        tab = np.array(rows, dtype=dt)
-        return (torch.from_numpy(tab.view(np.uint8)).to(dev), len(rows), chunk, tuple(sig))
+        return (L.pack_job_table(rows, dev), len(rows), chunk, tuple(sig))
 
     def refresh_all(self):
         stale = [h for h in self._c.values() if h[0] != self._version(h[3])]
@@ -114,8 +108,7 @@ class PackedWeights:
         if self._table is None:
             return                   # get() repacks entry by entry
         tab, n_jobs, n_chunks, _ = self._table
-        L.check(L.load().a3d_pack_conv_weights_multi(tab.data_ptr(), n_jobs, n_chunks, B._stream()),
-                "a3d_pack_conv_weights_multi")
+        B.pack_weights_multi(tab, n_jobs, n_chunks)
         for h in self._c.values():
             h[0] = self._version(h[3])
 
@@ -141,7 +134,7 @@ def _run_stem(scene, w, feats3, kvol):
     ops = (L.Op * 1)(o)
     nbytes = lib.a3d_program_workspace_bytes(scene.handle, bufs, 1, ops, 1)
     ws = B._workspace(nbytes, feats3.device, "stem")
-    L.check(lib.a3d_program_run(scene.handle, bufs, 1, ops, 1, B._ptr(feats3), None, 0, B._ptr(ws), nbytes, B._stream()),
+    L.check(lib.a3d_program_run(scene.handle, bufs, 1, ops, 1, L.ptr(feats3), None, 0, L.ptr(ws), nbytes, L.stream()),
             "a3d_program_run")
     off = lib.a3d_program_buffer_offset(scene.handle, bufs, 1, 0)
     return ws[off:off + (n0 + 1) * 32 * 4].view(torch.float32).view(n0 + 1, 32).clone()

@@ -9,22 +9,22 @@ The inference path runs the decoder in a handful of fused kernels that keep noth
 activations, so this path is the plain composition of attention_block.py -- nn.Linear = ``a3d_linear`` (the MFMA GEMM
 kernels), their gradients = ``a3d_linear`` with the transposed weight + ``a3d_linear_wgrad``, LayerNorm, and the
 attention / mask-head primitives of csrc/attn_train.hip with the score matrices materialised.  This module is the
-reverse-mode bookkeeping (which tensor feeds which op; fan-outs are tensor adds, ReLU a mask multiply).  A parity
+reverse-mode bookkeeping (which tensor feeds which op; fan-outs are tensor adds, ReLU a mask multiply); the library calls
+themselves are marshalled in decoder_ops.py (and backward.py), none here.  A parity
 executor: every FLOP of consequence is in libagile3d_hip, nothing is tuned yet.  Dropout (``dropout=p > 0``, main.py
 --dropout) is applied at the eight sites of every decoder pass with masks regenerated in the kernels from a
 counter-based RNG: one 64-bit seed per tape, the sample index and the site decide every mask, nothing mask-shaped is kept.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import backward as B
+from . import decoder_ops as ops
 from . import lib as L
+from .decoder_ops import DH, H
 from .engine import time_table
 
-H, DH = 8, 16
 # FLASH = False (tests set it): the attentions over the N points keep their [8, Lq, Lk] score matrices (attn_train.hip), the
 # path the flash kernels (attn_flash.hip) are checked against
 FLASH = True
@@ -98,30 +98,6 @@ class _Alias:
         self.t.add_grad_rows(rows, vals)
 
 
-def _next_layer_mask(logits, grp_of_query, n_groups):
-    """uint8 [Q, N] attention mask of the next layer's click-to-scene attention from this layer's [N, 1 + K] mask logits
-    (agile3d.py:362-383): a3d_next_layer_mask -- label arg-max + histogram, then the mask, instead of eight torch launches."""
-    lib = L.load()
-    N, G = logits.shape
-    Q = grp_of_query.numel()
-    if G != n_groups or G > 256:
-        raise RuntimeError("next-layer mask: the logits have one column per group (at most 256)")
-    lg = logits.contiguous()
-    mask = torch.empty((Q, N), dtype=torch.uint8, device=logits.device)
-    wsb = lib.a3d_next_layer_mask_workspace_bytes(N, G)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=logits.device)
-    L.check(lib.a3d_next_layer_mask(_ptr(lg), N, G, _ptr(grp_of_query), Q, _ptr(mask), _ptr(ws), wsb, _stream()), "a3d_next_layer_mask")
-    return mask
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 # dropout sites of one decoder pass (DESIGN.md §4.7): site code = 8 * pass + site
 SITE_C2S_ATTN, SITE_C2S_OUT, SITE_C2C_ATTN, SITE_C2C_OUT, SITE_FFN_HIDDEN, SITE_FFN_OUT, SITE_S2C_ATTN, SITE_S2C_OUT = range(8)
 
@@ -129,40 +105,6 @@ SITE_C2S_ATTN, SITE_C2S_OUT, SITE_C2C_ATTN, SITE_C2C_OUT, SITE_FFN_HIDDEN, SITE_
 def draw_seed():
     """One 64-bit dropout seed from torch's default CPU generator (``torch.manual_seed`` makes a run repeatable)."""
     return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) * 2 + int(torch.randint(0, 2, (1,)).item())
-
-
-def _pack(w_in_out):
-    cin, cout = w_in_out.shape
-    return B.pack_weight(w_in_out.reshape(1, cin, cout)), cin, cout
-
-
-def _linear(x, packed, bias=None, acc=None, out=None, res=None):
-    """x [n, cin] @ w [cin, cout] (+ bias) through a3d_linear; ``packed`` = _pack(w).  ``acc`` [n, cout]: the product is ADDED
-    to it in place (the kernel's residual input and its output are the same rows: one rounding, like ``acc + product``).
-    ``out`` [n, cout] contiguous rows (e.g. a sample's row range of a batched tensor): the product is written there."""
-    lib = L.load()
-    wp, cin, cout = packed
-    x = x.contiguous()
-    n = x.shape[0]
-    if out is not None and (acc is not None or out.shape != (n, cout) or not out.is_contiguous() or out.dtype != torch.float32):
-        raise RuntimeError("_linear: out must be a contiguous fp32 [n, cout] block (and excludes acc)")
-    y = acc if acc is not None else out if out is not None else torch.empty((n, cout), dtype=torch.float32, device=x.device)
-    r = acc
-    if res is not None:                 # ``res`` [n, cout]: a residual read in the GEMM's epilogue, y = res + x w (+ bias) in fresh rows
-        if acc is not None or res.shape != (n, cout) or not res.is_contiguous():
-            raise RuntimeError("_linear: res must be a contiguous [n, cout] block (and excludes acc)")
-        r = res
-    L.check(lib.a3d_linear(_ptr(x), cin, None, 0, n, cin, cout, _ptr(wp), None, _ptr(bias), _ptr(r), cout if r is not None else 0,
-                           0, _ptr(y), cout, None, 0, _stream()), "a3d_linear")
-    return y
-
-
-def _apply(P, V, Lq, Lk, Hh, dh, transposed, scale, out):
-    lib = L.load()
-    nbytes = lib.a3d_attn_apply_workspace_bytes(Lq, Lk, Hh, dh, transposed)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
-    L.check(lib.a3d_attn_apply(_ptr(P), _ptr(V), Lq, Lk, Hh, dh, transposed, scale, _ptr(out), _ptr(ws), nbytes, _stream()),
-            "a3d_attn_apply")
 
 
 class DecoderPacks:
@@ -197,13 +139,8 @@ class DecoderPacks:
         return hit[1], hit[2]
 
     def _refresh(self):
-        import numpy as np
-        lib = L.load()
         sig = tuple((k, h[4].data_ptr()) for k, h in self.e.items())
         if self._table is None or self._table[3] != sig:
-            dt = np.dtype([("src", "<u8"), ("dst", "<u8"), ("K", "<i4"), ("cin", "<i4"), ("cout", "<i4"), ("src_cin", "<i4"),
-                           ("src_cout", "<i4"), ("transposed", "<i4"), ("flip", "<i4"), ("c0", "<i4"), ("chunk0", "<i4"),
-                           ("pad", "<i4")])
             rows_, chunk = [], 0
             for (name, _), h in self.e.items():
                 p, (r0, r1) = h[4], h[5]
@@ -217,11 +154,10 @@ class DecoderPacks:
                 # backward: packed(W): element (ci = out, co = in) = W[r0 + ci][co]  -> a plain job on the slice's rows
                 rows_.append((p.data_ptr() + 4 * r0 * in_f, h[2][0].data_ptr(), 1, w, in_f, w, in_f, 0, 0, 0, chunk, 0))
                 chunk += (in_f * w + 4095) // 4096
-            tab = np.array(rows_, dtype=dt)
             dev = next(iter(self.e.values()))[4].device
-            self._table = (torch.from_numpy(tab.view(np.uint8)).to(dev), len(rows_), chunk, sig)
+            self._table = (L.pack_job_table(rows_, dev), len(rows_), chunk, sig)
         tab, n_jobs, n_chunks, _ = self._table
-        L.check(lib.a3d_pack_conv_weights_multi(tab.data_ptr(), n_jobs, n_chunks, _stream()), "a3d_pack_conv_weights_multi")
+        B.pack_weights_multi(tab, n_jobs, n_chunks)
         for h in self.e.values():
             h[0] = self._version(h[4])
 
@@ -281,24 +217,18 @@ class DecoderTape:
 
     def _rows_drop(self, x, res, ranges, site, relu=False):
         """y = res + Z o f(x) per sample on its row range (f = relu or the identity; res may be None)."""
-        lib = L.load()
         y = torch.empty_like(x)
-        cols = x.shape[1]
         for b, (r0, r1) in enumerate(ranges):
             if r1 > r0:
-                L.check(lib.a3d_dropout_rows_forward(_ptr(x[r0:r1]), _ptr(res[r0:r1] if res is not None else None), _ptr(y[r0:r1]),
-                                                     r1 - r0, cols, int(relu), self._drop(b, site), _stream()), "dropout_rows_forward")
+                ops.dropout_rows_forward(x[r0:r1], res[r0:r1] if res is not None else None, relu, self._drop(b, site), out=y[r0:r1])
         return y
 
     def _rows_drop_bwd(self, dy, x_pre, ranges, drops):
         """dx = Z o dy (o [x_pre > 0]) per sample, with the forward's a3d_dropout structs ``drops``."""
-        lib = L.load()
         dx = torch.empty_like(dy)
-        cols = dy.shape[1]
         for (r0, r1), d in zip(ranges, drops):
             if r1 > r0:
-                L.check(lib.a3d_dropout_rows_backward(_ptr(dy[r0:r1]), _ptr(x_pre[r0:r1] if x_pre is not None else None),
-                                                      _ptr(dx[r0:r1]), r1 - r0, cols, d, _stream()), "dropout_rows_backward")
+                ops.dropout_rows_backward(dy[r0:r1], x_pre[r0:r1] if x_pre is not None else None, d, out=dx[r0:r1])
         return dx
 
     def add(self, a: _T, b: _T) -> _T:
@@ -338,9 +268,9 @@ class DecoderTape:
         if drop is not None and self.p > 0:
             site, ranges = drop
             drops = [self._drop(b_, site) for b_ in range(len(ranges))]
-            y = _T(self._rows_drop(_linear(x.v, fwd_w, bc), res.v.contiguous() if res is not None else None, ranges, site))
+            y = _T(self._rows_drop(ops.linear(x.v, fwd_w, bc), res.v.contiguous() if res is not None else None, ranges, site))
         else:
-            y = _T(_linear(x.v, fwd_w, bc, res=res.v.contiguous() if res is not None else None))
+            y = _T(ops.linear(x.v, fwd_w, bc, res=res.v.contiguous() if res is not None else None))
 
         def back():
             if y.g is None:
@@ -349,9 +279,9 @@ class DecoderTape:
             if drops is not None:
                 dy = self._rows_drop_bwd(dy, None, drop[1], drops)            # Z o dy: what reaches the product
             if x.needs_grad and x.g is not None and x.own and x.g.is_contiguous():
-                _linear(dy, bwd_w, acc=x.g)                              # x.g += dy @ W in the GEMM's epilogue (no [N, 128] add)
+                ops.linear(dy, bwd_w, acc=x.g)                              # x.g += dy @ W in the GEMM's epilogue (no [N, 128] add)
             elif x.needs_grad:
-                x.add_grad(_linear(dy, bwd_w), fresh=True)               # dy @ W
+                x.add_grad(ops.linear(dy, bwd_w), fresh=True)               # dy @ W
             # dW [out, in] and the bias gradient from ONE pass over dy, written (a parameter's / slice's first contribution) or
             # added where the tape keeps the parameter's gradient: no transposing copy, no zero-filled full-size matrix + slice
             # copy + add per in_proj slice, no column-sum launches
@@ -400,127 +330,9 @@ class DecoderTape:
         self.steps.append(back)
         return y
 
-    # ---- attention, per batch sample on row ranges of the batched tensors.  Three implementations of
-    # softmax(q k^T / sqrt(dh) + mask) v per head, each a (forward, backward) pair on plain tensors:
-    #   "flash_c2s"  few queries over the N points, masked   (csrc/attn_flash.hip: no [8, Lq, Lk] matrix)
-    #   "flash_s2c"  the N points as queries over few keys   (csrc/attn_flash.hip)
-    #   "dense"      scores materialised (csrc/attn_train.hip): the click-to-click self attention, and everything when
-    #                FLASH is False (the path the flash kernels are checked against)
-    @staticmethod
-    def _dense_fwd(qv, kv, vv, mask, o, drop=None):
-        lib = L.load()
-        Lq, Lk = qv.shape[0], kv.shape[0]
-        dev = qv.device
-        scale = 1.0 / (DH ** 0.5)
-        transposed = mask is None and Lq >= 1024 and Lq > 8 * Lk      # the long index fastest in every kernel
-        if transposed:
-            Pm = torch.empty((H, Lk, Lq), dtype=torch.float32, device=dev)                      # P^T[h][key][query]
-            L.check(lib.a3d_attn_scores(_ptr(kv), _ptr(qv), Lk, Lq, H, DH, scale, None, _ptr(Pm), _stream()), "scores")
-            L.check(lib.a3d_softmax_cols(_ptr(Pm), H, Lk, Lq, _stream()), "softmax_cols")         # over the keys
-        else:
-            Pm = torch.empty((H, Lq, Lk), dtype=torch.float32, device=dev)
-            L.check(lib.a3d_attn_scores(_ptr(qv), _ptr(kv), Lq, Lk, H, DH, scale, _ptr(mask), _ptr(Pm), _stream()), "scores")
-            L.check(lib.a3d_softmax_rows(_ptr(Pm), H * Lq, Lk, _stream()), "softmax")
-        Pd = Pm
-        if drop is not None:            # the dropped probabilities multiply V; the softmax backward needs the undropped ones
-            Pd = torch.empty_like(Pm)
-            L.check(lib.a3d_attn_dropout(_ptr(Pm), H, Lq, Lk, int(transposed), _ptr(Pd), drop, _stream()), "attn_dropout")
-        if transposed:
-            _apply(Pd, vv, Lk, Lq, H, DH, 1, 1.0, o)
-        else:
-            _apply(Pd, vv, Lq, Lk, H, DH, 0, 1.0, o)
-        return (Pm, transposed) if drop is None else (Pm, transposed, Pd)
-
-    @staticmethod
-    def _dense_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv, drop=None):
-        lib = L.load()
-        Pm, transposed = saved[:2]
-        Pd = saved[2] if drop is not None else Pm
-        Lq, Lk = qv.shape[0], kv.shape[0]
-        scale = 1.0 / (DH ** 0.5)
-        dP = torch.empty_like(Pm)
-        if transposed:
-            L.check(lib.a3d_attn_scores(_ptr(vv), _ptr(do), Lk, Lq, H, DH, 1.0, None, _ptr(dP), _stream()), "scores")
-            _apply(Pd, do, Lk, Lq, H, DH, 0, 1.0, dv)                                        # dv[key] = sum_query P^T dO
-            if drop is not None:
-                L.check(lib.a3d_attn_dropout(_ptr(dP), H, Lq, Lk, 1, _ptr(dP), drop, _stream()), "attn_dropout")   # Z o dP
-            L.check(lib.a3d_softmax_cols_backward(_ptr(Pm), _ptr(dP), H, Lk, Lq, _stream()), "softmax_cols_bwd")
-            _apply(dP, kv, Lk, Lq, H, DH, 1, scale, dq)                                      # dq[query] = sum_key dS^T k
-            _apply(dP, qv, Lk, Lq, H, DH, 0, scale, dk)                                      # dk[key] = sum_query dS^T q
-        else:
-            L.check(lib.a3d_attn_scores(_ptr(do), _ptr(vv), Lq, Lk, H, DH, 1.0, None, _ptr(dP), _stream()), "scores")
-            _apply(Pd, do, Lq, Lk, H, DH, 1, 1.0, dv)
-            if drop is not None:
-                L.check(lib.a3d_attn_dropout(_ptr(dP), H, Lq, Lk, 0, _ptr(dP), drop, _stream()), "attn_dropout")   # Z o dP
-            L.check(lib.a3d_softmax_rows_backward(_ptr(Pm), _ptr(dP), H * Lq, Lk, _stream()), "softmax_bwd")   # dP <- dS
-            _apply(dP, kv, Lq, Lk, H, DH, 0, scale, dq)
-            _apply(dP, qv, Lq, Lk, H, DH, 1, scale, dk)
-
-    @staticmethod
-    def _c2s_fwd(qv, kv, vv, mask, o, drop=None):
-        lib = L.load()
-        Lq, Lk = qv.shape[0], kv.shape[0]
-        dev = qv.device
-        qs = qv * 0.25                                                     # 1 / sqrt(16): exact
-        nbytes = lib.a3d_flash_c2s_workspace_bytes(Lq, Lk)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        stats = torch.empty((2, H, Lq), dtype=torch.float32, device=dev)
-        if drop is None:
-            L.check(lib.a3d_flash_c2s_forward(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws),
-                                              nbytes, _stream()), "flash_c2s_forward")
-        else:
-            L.check(lib.a3d_flash_c2s_forward_dropout(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats),
-                                                      _ptr(ws), nbytes, drop, _stream()), "flash_c2s_forward_dropout")
-        return qs, stats
-
-    @staticmethod
-    def _c2s_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv, drop=None):
-        lib = L.load()
-        qs, stats = saved
-        Lq, Lk = qv.shape[0], kv.shape[0]
-        nbytes = lib.a3d_flash_c2s_workspace_bytes(Lq, Lk)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=qv.device)
-        if drop is None:
-            L.check(lib.a3d_flash_c2s_backward(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats), _ptr(do),
-                                               _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _stream()), "flash_c2s_backward")
-        else:
-            L.check(lib.a3d_flash_c2s_backward_dropout(_ptr(qs), _ptr(kv), _ptr(vv), _ptr(mask), Lq, Lk, _ptr(o), _ptr(stats),
-                                                       _ptr(do), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, drop, _stream()),
-                    "flash_c2s_backward_dropout")
-        dq *= 0.25
-
-    @staticmethod
-    def _s2c_fwd(qv, kv, vv, mask, o, drop=None):
-        # the 1 / sqrt(16) goes on the FEW keys, not on the N queries: q . (k / 4) has the bits of (q / 4) . k (a power of two),
-        # and the kernel's dq = dS (k / 4) is then already the gradient of the unscaled queries
-        lib = L.load()
-        Lq, Lk = qv.shape[0], kv.shape[0]
-        ks = kv * 0.25
-        stats = torch.empty((Lq, H, 2), dtype=torch.float32, device=qv.device)
-        if drop is None:
-            L.check(lib.a3d_flash_s2c_forward(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), _stream()),
-                    "flash_s2c_forward")
-        else:
-            L.check(lib.a3d_flash_s2c_forward_dropout(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), drop, _stream()),
-                    "flash_s2c_forward_dropout")
-        return ks, stats
-
-    @staticmethod
-    def _s2c_bwd(qv, kv, vv, mask, o, saved, do, dq, dk, dv, drop=None):
-        lib = L.load()
-        ks, stats = saved
-        Lq, Lk = qv.shape[0], kv.shape[0]
-        nbytes = lib.a3d_flash_s2c_workspace_bytes(Lq, Lk)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=qv.device)
-        if drop is None:
-            L.check(lib.a3d_flash_s2c_backward(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), _ptr(do), _ptr(dq),
-                                               _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _stream()), "flash_s2c_backward")
-        else:
-            L.check(lib.a3d_flash_s2c_backward_dropout(_ptr(qv), _ptr(ks), _ptr(vv), Lq, Lk, _ptr(o), _ptr(stats), _ptr(do),
-                                                       _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, drop, _stream()),
-                    "flash_s2c_backward_dropout")
-        dk *= 0.25
-
+    # ---- attention, per batch sample on row ranges of the batched tensors: one of decoder_ops' three implementations
+    # ("s2c" and "c2s": the flash kernels with the N points on one side; "dense": scores materialised -- the click-to-click
+    # self attention, and everything when FLASH is False)
     def attention_seg(self, q: _T, k: _T, v: _T, q_ranges, k_ranges, masks=None, site=None) -> _T:
         """Attention of every batch sample on ITS rows: sample b's queries are rows q_ranges[b] of ``q``, its keys / values
         rows k_ranges[b] of ``k`` / ``v`` (contiguous row ranges of the batched tensors: views, no copies); masks[b] uint8
@@ -538,10 +350,10 @@ class DecoderTape:
                 kind = "c2s"
             else:
                 kind = "dense"
-            fwd = {"s2c": self._s2c_fwd, "c2s": self._c2s_fwd, "dense": self._dense_fwd}[kind]
+            fwd = {"s2c": ops.s2c_forward, "c2s": ops.c2s_forward, "dense": ops.dense_forward}[kind]
             o = out[q0:q1]                                  # the sample's rows of the batched result: written in place
             drop = self._drop(b, site) if site is not None and self.p > 0 else None
-            sv = fwd(qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o) if drop is None else fwd(qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o, drop)
+            _, sv = fwd(qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o, drop)
             saved.append((kind, o, sv, mask, drop))
         y = _T(out)
 
@@ -551,9 +363,8 @@ class DecoderTape:
             do = y.g.contiguous()
             dq, dk, dv = torch.empty_like(qv), torch.empty_like(kv), torch.empty_like(vv)
             for ((q0, q1), (k0, k1)), (kind, o, sv, mask, drop) in zip(zip(q_ranges, k_ranges), saved):
-                bwd = {"s2c": self._s2c_bwd, "c2s": self._c2s_bwd, "dense": self._dense_bwd}[kind]
-                args = (qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o, sv, do[q0:q1], dq[q0:q1], dk[k0:k1], dv[k0:k1])
-                bwd(*args) if drop is None else bwd(*args, drop)
+                bwd = {"s2c": ops.s2c_backward, "c2s": ops.c2s_backward, "dense": ops.dense_backward}[kind]
+                bwd(qv[q0:q1], kv[k0:k1], vv[k0:k1], mask, o, sv, do[q0:q1], dq[q0:q1], dk[k0:k1], dv[k0:k1], drop)
             q.add_grad(dq, fresh=True)
             k.add_grad(dk, fresh=True)
             v.add_grad(dv, fresh=True)
@@ -576,7 +387,6 @@ class DecoderTape:
     def mask_head(self, queries: _T, src: _T, n_ranges, q_ranges, groups):
         """Agile3d.mask_module (agile3d.py:342-384): per-object max over its queries of src . MLP(LN(q)); the MLP runs over
         the queries of the whole batch, the products per sample.  Returns one [N_b, 1 + K_b] node per sample."""
-        lib = L.load()
         e = self.ln(queries, "decoder_norm.")
         e = self.relu(self.lin(e, "mask_embed_head.0.weight", "mask_embed_head.0.bias"))
         E = self.lin(e, "mask_embed_head.2.weight", "mask_embed_head.2.bias")
@@ -586,7 +396,7 @@ class DecoderTape:
         def padded(Q):      # the GEMM kernels write 32 / 64 / 96 or multiples of 128 output columns
             return 32 if Q <= 32 else 64 if Q <= 64 else 96 if Q <= 96 else (Q + 127) // 128 * 128
         for (n0, n1), (q0, q1), grp in zip(n_ranges, q_ranges, groups):
-            N, Q, G = n1 - n0, q1 - q0, len(grp)
+            Q = q1 - q0
             Qp = padded(Q)
             sv = src.v[n0:n1]
             # logits of every query on the matrix cores: [N, 128] x [128, Qp] with the embeddings zero-padded to Qp
@@ -594,15 +404,13 @@ class DecoderTape:
             # padded columns stay in the row layout, no group covers them
             Ep = torch.zeros((Qp, 128), dtype=torch.float32, device=dev)
             Ep[:Q] = E.v[q0:q1]
-            lq = _linear(sv, _pack(Ep.t().contiguous()))
+            lq = ops.linear(sv, ops.pack_linear(Ep.t().contiguous()))
             tabs = self._group_tabs.get(id(grp))       # the groups' query ranges: the same in every layer of the pass
             if tabs is None:
                 tabs = self._group_tabs[id(grp)] = (torch.tensor([g[0] for g in grp], dtype=torch.int32, device=dev),
                                                     torch.tensor([g[1] for g in grp], dtype=torch.int32, device=dev), grp)
             qb, qe = tabs[0], tabs[1]
-            out = torch.empty((N, G), dtype=torch.float32, device=dev)
-            arg = torch.empty((N, G), dtype=torch.int32, device=dev)
-            L.check(lib.a3d_group_max(_ptr(lq), N, Qp, _ptr(qb), _ptr(qe), G, _ptr(out), _ptr(arg), _stream()), "group_max")
+            out, arg = ops.group_max(lq, qb, qe)
             outs.append(_T(out))
             saved.append((arg, Ep, Qp))
             self.args.append(arg)
@@ -614,12 +422,11 @@ class DecoderTape:
                 if y.g is None:
                     dsrc[n0:n1].zero_()
                     continue
-                N, Q, G = n1 - n0, q1 - q0, len(grp)
-                dlq = torch.empty((N, Qp), dtype=torch.float32, device=dev)
-                L.check(lib.a3d_group_max_backward(_ptr(y.g.contiguous()), _ptr(arg), N, Qp, G, _ptr(dlq), _stream()), "gm_bwd")
+                Q = q1 - q0
+                dlq = ops.group_max_backward(y.g.contiguous(), arg, Qp)
                 # d(src) = dlq Ep and dE = dlq^T src: both on the matrix cores (a GEMM and a weight-gradient reduction over
                 # the N rows, wgrad.hip), the padded query columns carry zeros
-                _linear(dlq, _pack(Ep), out=dsrc[n0:n1])      # straight into the sample's rows (no [N, 128] copy)
+                ops.linear(dlq, ops.pack_linear(Ep), out=dsrc[n0:n1])      # straight into the sample's rows (no [N, 128] copy)
                 dE[q0:q1] = B.linear_weight_grad(dlq, src.v[n0:n1])[:Q]
             src.add_grad(dsrc, fresh=True)
             E.add_grad(dE, fresh=True)
@@ -718,7 +525,7 @@ class DecoderTape:
             # times per layer and sample
             masks = []
             for out, sm, grp in zip(outs, samples, groups):
-                masks.append(_next_layer_mask(out.v, sm["grp_of_query"], len(grp)))
+                masks.append(ops.next_layer_mask(out.v, sm["grp_of_query"]))
             self.attn_masks.append(masks[0] if self._single else masks)
         if self._single:
             self.logits = [layer[0].v for layer in self.logits_nodes]
@@ -746,3 +553,22 @@ class DecoderTape:
         for back in reversed(self.steps):
             back()
         return self.grads, self.pcd.g
+
+
+
+# DEPRECATED, no caller in this repository: the names through which tests written before decoder_ops.py reached the primitives,
+# kept only so that such a test still runs against this package.  New code calls decoder_ops; delete these with the next change
+# that may break those callers.
+def _apply(P, V, Lq, Lk, Hh, dh, transposed, scale, out):
+    ops.attn_apply(P, V, transposed, scale, out)
+
+
+def _next_layer_mask(logits, grp_of_query, n_groups):
+    return ops.next_layer_mask(logits.contiguous(), grp_of_query)
+
+
+def _dense_fwd(q, k, v, mask, o, drop=None):
+    return ops.dense_forward(q, k, v, mask, o, drop)[1]
+
+
+DecoderTape._dense_fwd, DecoderTape._dense_bwd = staticmethod(_dense_fwd), staticmethod(ops.dense_backward)

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from ._args import F32, I32, I64, U8, _device, _out, _ptr
 
 # the result records as numpy sees them (lib.PickResult, lib.PickMeshResult, lib.RenderHeader)
 PICK = np.dtype([("index", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
@@ -26,8 +27,6 @@ RENDER_HEADER = np.dtype([("flags", "<i4"), ("n_everywhere", "<i4"), ("pairs_nee
 assert C.sizeof(L.PickResult) == PICK.itemsize == 16
 assert C.sizeof(L.PickMeshResult) == PICK_MESH.itemsize == 32
 assert C.sizeof(L.RenderHeader) == RENDER_HEADER.itemsize == 16
-
-I32, I64, F32, U8 = torch.int32, torch.int64, torch.float32, torch.uint8
 
 
 # ---- decoding: pure functions of a host array ----------------------------------------------------------------------------
@@ -48,47 +47,13 @@ def read_render_header(host):
     return int(rec["flags"]), int(rec["n_everywhere"]), int(rec["pairs_needed"])
 
 
-# ---- argument checks ---------------------------------------------------------------------------------------------------------
-def _device(name, t):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise ValueError(f"{name} must be a tensor on the GPU (there is no CPU path)")
-    return t.device
-
-
-def _ptr(name, t, dtype, shape, dev, optional=False):
-    """The device pointer of tensor argument ``name`` (``shape``: ``None`` = any extent) -- ``None`` for a tensor without
-    elements and for an absent ``optional`` one."""
-    if t is None and optional:
-        return None
-    if not torch.is_tensor(t) or t.dtype != dtype:
-        raise ValueError(f"{name} must be a {dtype} tensor")
-    if t.device != dev:
-        raise ValueError(f"{name} must live on {dev}")
-    if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-        raise ValueError(f"{name} must have shape {list(shape)} (None: any), not {list(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return t.data_ptr() if t.numel() else None
-
-
-def _out(name, t, dtype, shape, dev):
-    """The output tensor ``name``: the caller's, checked, or a new one."""
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    _ptr(name, t, dtype, shape, dev)
-    return t
-
-
+# ---- argument checks (the tensor checkers are _args.py's, shared with decoder_ops.py) --------------------------------------
 def _f32p(name, values, shape):
     """(array, pointer) of a small host argument; the array must outlive the call."""
     a = np.ascontiguousarray(values, dtype=np.float32)
     if a.shape != shape:
         raise ValueError(f"{name} must have shape {list(shape)}")
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def session_workspace(device):
@@ -118,7 +83,7 @@ def nearest_rows(sources, queries, out=None, workspace=None):
     src = (L.NearestSource * len(sources))()
     for i, s in enumerate(sources):
         src[i].xyz_dev, src[i].n, src[i].rows_out_dev = _ptr(f"sources[{i}]", s, F32, (None, 3), dev), s.shape[0], out[i].data_ptr()
-    L.check(L.load().a3d_nearest_rows(src, len(sources), qp, len(q), ws.data_ptr(), ws.numel(), _stream(dev)), "a3d_nearest_rows")
+    L.check(L.load().a3d_nearest_rows(src, len(sources), qp, len(q), ws.data_ptr(), ws.numel(), L.stream(dev)), "a3d_nearest_rows")
     return out
 
 
@@ -139,7 +104,7 @@ def _pick_ray(xyz, origin, direction, radius, section, out, workspace):
     (o, op), (d, dp) = _f32p("origin", origin, (3,)), _f32p("direction", direction, (3,))
     out = _out("out", out, I32, (4,), dev)
     ws = _workspace(workspace, dev)
-    tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+    tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream(dev))
     if section is _PLAIN:
         L.check(L.load().a3d_pick_ray(xp, xyz.shape[0], op, dp, float(radius), *tail), "a3d_pick_ray")
     else:
@@ -154,7 +119,7 @@ def _pick_mesh(xyz, faces, origin, direction, section, out, workspace):
     (o, op), (d, dp) = _f32p("origin", origin, (3,)), _f32p("direction", direction, (3,))
     out = _out("out", out, I32, (8,), dev)
     ws = _workspace(workspace, dev)
-    tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+    tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream(dev))
     if section is _PLAIN:
         L.check(L.load().a3d_pick_mesh(xp, xyz.shape[0], fp, faces.shape[0], op, dp, *tail), "a3d_pick_mesh")
     else:
@@ -208,7 +173,7 @@ def _render(xyz, faces, radius, cam, ids, t, u, v, uv, header, workspace, capaci
         workspace = torch.empty(render_workspace_bytes(m, w, h, capacity), dtype=U8, device=dev)
     _ptr("workspace", workspace, U8, (None,), dev)
     lib = L.load()
-    tail = (C.byref(out), workspace.data_ptr(), workspace.numel(), _stream(dev))
+    tail = (C.byref(out), workspace.data_ptr(), workspace.numel(), L.stream(dev))
     if mesh and section is _PLAIN:
         L.check(lib.a3d_render_mesh(xp, n, fp, m, C.byref(cam), *tail), "a3d_render_mesh")
     elif mesh:
@@ -264,7 +229,7 @@ def _shade_args(ids, u, v, faces, colors, background, rgb):
 def render_shade(ids, u, v, faces, colors, background, rgb=None):
     """``a3d_render_shade``: uint8 [h, w, 3] flat colours of an id image; ``u``, ``v``, ``faces`` ``None`` on a cloud."""
     dev, (h, w), (ip, up, vp, fp, cp), m, n, (bg, bgp), rgb = _shade_args(ids, u, v, faces, colors, background, rgb)
-    L.check(L.load().a3d_render_shade(ip, up, vp, fp, m, cp, n, bgp, rgb.data_ptr(), w, h, _stream(dev)), "a3d_render_shade")
+    L.check(L.load().a3d_render_shade(ip, up, vp, fp, m, cp, n, bgp, rgb.data_ptr(), w, h, L.stream(dev)), "a3d_render_shade")
     return rgb
 
 
@@ -273,7 +238,7 @@ def render_shade_lit(ids, u, v, faces, colors, normals, cam, ambient, background
     dev, _, (ip, up, vp, fp, cp), m, n, (bg, bgp), rgb = _shade_args(ids, u, v, faces, colors, background, rgb)
     np_ = _ptr("normals", normals, F32, (n, 3), dev)
     L.check(L.load().a3d_render_shade_lit(ip, up, vp, fp, m, cp, n, np_, C.byref(cam), float(ambient), bgp, rgb.data_ptr(),
-                                          _stream(dev)), "a3d_render_shade_lit")
+                                          L.stream(dev)), "a3d_render_shade_lit")
     return rgb
 
 
@@ -282,7 +247,7 @@ def render_shade_depth(ids, t, u, v, faces, colors, strength, background, rgb=No
     dev, (h, w), (ip, up, vp, fp, cp), m, n, (bg, bgp), rgb = _shade_args(ids, u, v, faces, colors, background, rgb)
     tp = _ptr("t", t, F32, (h, w), dev)
     L.check(L.load().a3d_render_shade_depth(ip, tp, up, vp, fp, m, cp, n, float(strength), bgp, rgb.data_ptr(), w, h,
-                                            _stream(dev)), "a3d_render_shade_depth")
+                                            L.stream(dev)), "a3d_render_shade_depth")
     return rgb
 
 
@@ -293,7 +258,7 @@ def vertex_normals(xyz, faces, offsets, corners, out=None):
     op, cp = _ptr("offsets", offsets, I64, (None,), dev), _ptr("corners", corners, I32, (None,), dev)
     n, m = xyz.shape[0], faces.shape[0]
     out = _out("out", out, F32, (n, 3), dev)
-    L.check(L.load().a3d_vertex_normals(xp, n, fp, m, op, cp, out.data_ptr() if n else None, _stream(dev)),
+    L.check(L.load().a3d_vertex_normals(xp, n, fp, m, op, cp, out.data_ptr() if n else None, L.stream(dev)),
             "a3d_vertex_normals")
     return out
 
@@ -311,7 +276,7 @@ def render_labels(ids, u, v, faces, labels, out=None):
     m = faces.shape[0] if mesh else 0
     n = 0 if mesh and m == 0 else labels.shape[0]       # a mesh without faces: a cloud without vertices, every pixel -1
     out = _out("out", out, I32, (h, w), dev)
-    L.check(L.load().a3d_render_labels(ip, up, vp, fp, m, lp, n, out.data_ptr(), w, h, _stream(dev)), "a3d_render_labels")
+    L.check(L.load().a3d_render_labels(ip, up, vp, fp, m, lp, n, out.data_ptr(), w, h, L.stream(dev)), "a3d_render_labels")
     return out
 
 
@@ -331,7 +296,7 @@ def render_annotate(rgb, label_image, t, markers, radius, inner_radius, depth_sl
     ba, bp = _f32p("border", border, (3,))
     out = _out("out", out, U8, (h, w, 3), dev)
     L.check(L.load().a3d_render_annotate(rp, lp, tp, mp, k, float(radius), float(inner_radius), float(depth_slack), op, bp,
-                                         out.data_ptr(), w, h, _stream(dev)), "a3d_render_annotate")
+                                         out.data_ptr(), w, h, L.stream(dev)), "a3d_render_annotate")
     return out
 
 
@@ -376,7 +341,7 @@ def session_paint(labels_qv, inverse_map, xyz, colors, palette, cubes, cube_size
     labels_out, colors_out = _out("labels_out", labels_out, I32, (n,), dev), _out("colors_out", colors_out, F32, (n, 3), dev)
     err = _out("err", err, I32, (1,), dev)
     a.label_full_dev, a.colors_out_dev, a.err_dev = labels_out.data_ptr(), colors_out.data_ptr(), err.data_ptr()
-    L.check(L.load().a3d_session_paint(C.byref(a), _stream(dev)), "a3d_session_paint")
+    L.check(L.load().a3d_session_paint(C.byref(a), L.stream(dev)), "a3d_session_paint")
     return labels_out, colors_out, err
 
 
@@ -411,7 +376,7 @@ def session_edit(labels_ori=None, instances=None, new_labels=None, labels=None, 
         a.err_dev = err.data_ptr()
     elif lut is not None or err is not None:
         raise ValueError("lut and err belong to the remap half: labels is missing")
-    L.check(L.load().a3d_session_edit(C.byref(a), _stream(dev)), "a3d_session_edit")
+    L.check(L.load().a3d_session_edit(C.byref(a), L.stream(dev)), "a3d_session_edit")
     return new_labels, labels, err
 
 
@@ -489,5 +454,5 @@ def session_guide(logits, click_rows, click_objs, threshold, inverse_map=None, c
     if summary.data_ptr() % 8:
         raise ValueError("summary must be 8-byte aligned")
     a.summary_dev = summary.data_ptr()
-    L.check(L.load().a3d_session_guide(C.byref(a), _stream(dev)), "a3d_session_guide")
+    L.check(L.load().a3d_session_guide(C.byref(a), L.stream(dev)), "a3d_session_guide")
     return labels, runner, margin, want, margin_full, colors_out, summary

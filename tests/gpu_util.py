@@ -6,7 +6,8 @@ import numpy as np
 import torch
 
 from agile3d_amd import lib as L
-from agile3d_amd.engine import Scene, _ptr, _stream
+from agile3d_amd.engine import Scene
+from agile3d_amd.lib import ptr as _ptr, stream as _stream
 
 
 def key4(c):

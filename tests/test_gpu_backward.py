@@ -722,24 +722,22 @@ def test_checkpoint_resume_continues_bit_identically(tmp_path):
 def test_attention_primitives_long_dimensions(Lq, Lk, Hh, dh, tr):
     """a3d_attn_scores / a3d_attn_apply at the sizes of the training path (tens of thousands of points on one side): the
     split / per-head / matrix-core variants against float64 einsum."""
-    from agile3d_amd.train_decoder import _apply
-    lib = L.load()
+    from agile3d_amd import decoder_ops as ops
     g = torch.Generator().manual_seed(Lq + Lk + dh)
     C_ = Hh * dh
     q = torch.randn(Lq, C_, generator=g).cuda()
     k = torch.randn(Lk, C_, generator=g).cuda()
-    S = torch.empty((Hh, Lq, Lk), dtype=torch.float32, device="cuda")
-    L.check(lib.a3d_attn_scores(q.data_ptr(), k.data_ptr(), Lq, Lk, Hh, dh, 0.25, None, S.data_ptr(), None), "scores")
+    S = ops.attn_scores(q, k, 0.25, heads=Hh)
     ref_S = 0.25 * torch.einsum("ihd,jhd->hij", q.cpu().double().view(Lq, Hh, dh), k.cpu().double().view(Lk, Hh, dh))
     assert (S.cpu().double() - ref_S).abs().max().item() <= 1e-4
     P = torch.softmax(S, -1).contiguous()
     if tr:      # O[j, h, :] = sum_i P[h, i, j] X[i, h, :]
         out = torch.empty((Lk, C_), dtype=torch.float32, device="cuda")
-        _apply(P, q, Lq, Lk, Hh, dh, 1, 0.5, out)
+        ops.attn_apply(P, q, True, 0.5, out)
         ref = 0.5 * torch.einsum("hij,ihd->jhd", P.cpu().double(), q.cpu().double().view(Lq, Hh, dh)).reshape(Lk, C_)
     else:       # O[i, h, :] = sum_j P[h, i, j] V[j, h, :]
         out = torch.empty((Lq, C_), dtype=torch.float32, device="cuda")
-        _apply(P, k, Lq, Lk, Hh, dh, 0, 0.5, out)
+        ops.attn_apply(P, k, False, 0.5, out)
         ref = 0.5 * torch.einsum("hij,jhd->ihd", P.cpu().double(), k.cpu().double().view(Lk, Hh, dh)).reshape(Lq, C_)
     err = (out.cpu().double() - ref).abs().max().item()
     assert err <= 2e-5 * max(1.0, ref.abs().max().item()), err
@@ -825,33 +823,13 @@ def test_reference_training_sequence_through_the_model_api():
     assert torch.isfinite(r[0].F).all()
 
 
-def _ptr(t):
-    import ctypes as C
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    import ctypes as C
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _mha_ref(q, k, v, mask):
-    """softmax(q k^T / 4 + mask) v per head (8 x 16) in float64 with autograd: (o, dq, dk, dv) for the loss sum(o * w)."""
-    q, k, v = (t.double().clone().requires_grad_(True) for t in (q, k, v))
-    Lq, Lk = q.shape[0], k.shape[0]
-    s = torch.einsum("ihd,jhd->hij", q.view(Lq, 8, 16), k.view(Lk, 8, 16)) / 4.0
-    if mask is not None:
-        s = s.masked_fill(mask.bool()[None], float("-inf"))
-    o = torch.einsum("hij,jhd->ihd", torch.softmax(s, -1), v.view(Lk, 8, 16)).reshape(Lq, 128)
-    return o, q, k, v
-
-
 @pytest.mark.parametrize("Lq,Lk,masked", [(37, 5003, True), (20, 3000, False), (130, 1700, True)])
 def test_flash_click_to_scene_attention_vs_float64_autograd(Lq, Lk, masked):
     """a3d_flash_c2s_forward / _backward (no [8, Lq, Lk] matrix; softmax statistics kept, probabilities recomputed in the
     backward pass) against float64 autograd of the plain formula: output, dq, dk, dv; ragged sizes (Lq, Lk not multiples
     of 16 / 64), a mask that blocks 60 % of the entries and whole 64-key chunks of some queries."""
-    lib = L.load()
+    from agile3d_amd import decoder_ops as ops
+    from attn_kit import check, mha_ref
     g = torch.Generator().manual_seed(Lq * 7 + Lk)
     q, k, v = (torch.randn(n, 128, generator=g) for n in (Lq, Lk, Lk))
     w = torch.randn(Lq, 128, generator=g)
@@ -861,54 +839,30 @@ def test_flash_click_to_scene_attention_vs_float64_autograd(Lq, Lk, masked):
         mask[:, 5] = False                                  # no row fully blocked (the reference's mask_module guarantees it)
         mask[3, 64:640] = True                              # whole chunks blocked for one query
         mask = mask.to(torch.uint8)
-    o_ref, qr, kr, vr = _mha_ref(q, k, v, mask)
-    (o_ref * w.double()).sum().backward()
+    want = mha_ref(q, k, v, w, mask)
     dev = torch.device("cuda")
     qs, kd, vd, md, wd = (q * 0.25).to(dev), k.to(dev), v.to(dev), (mask.to(dev).contiguous() if masked else None), w.to(dev)
-    nb = lib.a3d_flash_c2s_workspace_bytes(Lq, Lk)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    o = torch.empty(Lq, 128, device=dev)
-    stats = torch.empty(2, 8, Lq, device=dev)
-    L.check(lib.a3d_flash_c2s_forward(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws), nb,
-                                      _stream()), "fwd")
-    dq, dk, dv = torch.empty_like(qs), torch.empty_like(kd), torch.empty_like(vd)
-    L.check(lib.a3d_flash_c2s_backward(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd), _ptr(dq),
-                                       _ptr(dk), _ptr(dv), _ptr(ws), nb, _stream()), "bwd")
-    dq2, dk2, dv2 = torch.empty_like(qs), torch.empty_like(kd), torch.empty_like(vd)
-    L.check(lib.a3d_flash_c2s_backward(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd), _ptr(dq2),
-                                       _ptr(dk2), _ptr(dv2), _ptr(ws), nb, _stream()), "bwd")
+    o, stats = ops.flash_c2s_forward(qs, kd, vd, md)
+    dq, dk, dv = ops.flash_c2s_backward(qs, kd, vd, md, o, stats, wd)
+    dq2, dk2, dv2 = ops.flash_c2s_backward(qs, kd, vd, md, o, stats, wd)
     assert torch.equal(dq, dq2) and torch.equal(dk, dk2) and torch.equal(dv, dv2)      # deterministic
-    for name, got, want in (("o", o, o_ref), ("dq", dq * 0.25, qr.grad), ("dk", dk, kr.grad), ("dv", dv, vr.grad)):
-        err = (got.double().cpu() - want.detach()).abs().max().item()
-        scale = max(1e-6, want.detach().abs().max().item())
-        print(f"flash c2s {Lq}x{Lk} {name}: max|diff| {err:.2e} (scale {scale:.2e})")
-        assert err <= 2e-5 * scale, (name, err, scale)
+    check(f"flash c2s {Lq}x{Lk}", (o, dq * 0.25, dk, dv), want)
 
 
 @pytest.mark.parametrize("Lq,Lk", [(5003, 37), (3000, 20), (1700, 130)])
 def test_flash_scene_to_click_attention_vs_float64_autograd(Lq, Lk):
     """a3d_flash_s2c_forward / _backward (the N points as queries over few keys) against float64 autograd."""
-    lib = L.load()
+    from agile3d_amd import decoder_ops as ops
+    from attn_kit import check, mha_ref
     g = torch.Generator().manual_seed(Lq * 3 + Lk)
     q, k, v = (torch.randn(n, 128, generator=g) for n in (Lq, Lk, Lk))
     w = torch.randn(Lq, 128, generator=g)
-    o_ref, qr, kr, vr = _mha_ref(q, k, v, None)
-    (o_ref * w.double()).sum().backward()
+    want = mha_ref(q, k, v, w, None)
     dev = torch.device("cuda")
     qs, kd, vd, wd = (q * 0.25).to(dev), k.to(dev), v.to(dev), w.to(dev)
-    o = torch.empty(Lq, 128, device=dev)
-    stats = torch.empty(Lq, 8, 2, device=dev)
-    L.check(lib.a3d_flash_s2c_forward(_ptr(qs), _ptr(kd), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _stream()), "fwd")
-    nb = lib.a3d_flash_s2c_workspace_bytes(Lq, Lk)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    dq, dk, dv = torch.empty_like(qs), torch.empty_like(kd), torch.empty_like(vd)
-    L.check(lib.a3d_flash_s2c_backward(_ptr(qs), _ptr(kd), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd), _ptr(dq), _ptr(dk),
-                                       _ptr(dv), _ptr(ws), nb, _stream()), "bwd")
-    for name, got, want in (("o", o, o_ref), ("dq", dq * 0.25, qr.grad), ("dk", dk, kr.grad), ("dv", dv, vr.grad)):
-        err = (got.double().cpu() - want.detach()).abs().max().item()
-        scale = max(1e-6, want.detach().abs().max().item())
-        print(f"flash s2c {Lq}x{Lk} {name}: max|diff| {err:.2e} (scale {scale:.2e})")
-        assert err <= 2e-5 * scale, (name, err, scale)
+    o, stats = ops.flash_s2c_forward(qs, kd, vd)
+    dq, dk, dv = ops.flash_s2c_backward(qs, kd, vd, o, stats, wd)
+    check(f"flash s2c {Lq}x{Lk}", (o, dq * 0.25, dk, dv), want)
 
 
 def test_batched_decoder_tape_equals_one_tape_per_sample():
@@ -967,7 +921,7 @@ def test_next_layer_mask_matches_the_torch_expression(N, G, Q):
     """a3d_next_layer_mask (the training tape's attention mask of the next decoder layer, agile3d.py:362-383) against the torch
     expression it replaces: label = first arg-max over the 1 + K logits, mask[q][n] = label[n] != group(q) and some point
     carries group(q).  Ties (equal logits), groups that own no point and groups no query belongs to are in the data."""
-    from agile3d_amd.train_decoder import _next_layer_mask
+    from agile3d_amd.decoder_ops import next_layer_mask
     g = torch.Generator().manual_seed(N + 7 * G + Q)
     logits = torch.randn(N, G, generator=g)
     logits[:, G - 1] = -50.0                                   # a group that never wins: "nothing blocked" for its queries
@@ -977,7 +931,7 @@ def test_next_layer_mask_matches_the_torch_expression(N, G, Q):
     gq = torch.randint(0, G, (Q,), generator=g, dtype=torch.int32)
     gq[0] = G - 1
     lg, gqd = logits.cuda(), gq.cuda()
-    got = _next_layer_mask(lg, gqd, G)
+    got = next_layer_mask(lg, gqd)
     labels = lg.argmax(1)
     counts = torch.bincount(labels, minlength=G)
     want = ((labels[None, :] != gqd.long()[:, None]) & (counts[gqd.long()] > 0)[:, None]).to(torch.uint8)

@@ -154,7 +154,7 @@ def test_stem_hash_path(ks):
 
 
 def test_standalone_linear_matches_matmul():
-    from agile3d_amd.engine import _ptr, _stream
+    from agile3d_amd.lib import ptr as _ptr, stream as _stream
     lib = L.load()
     g = torch.Generator().manual_seed(3)
     for n in (1, 100, 128, 5000):
@@ -175,7 +175,7 @@ def test_standalone_linear_matches_matmul():
 def test_dense_linear_all_options(cin, cout):
     """k_dense: second input added on the fly, BN-style scale/shift, residual, relu, strided operands,
     ragged row counts (tile = 128 rows, wave = 32 rows, group = 16 rows)."""
-    from agile3d_amd.engine import _ptr, _stream
+    from agile3d_amd.lib import ptr as _ptr, stream as _stream
     lib = L.load()
     g = torch.Generator().manual_seed(cin + cout)
     W = torch.randn(cin, cout, generator=g).cuda() / 9.0
@@ -198,7 +198,7 @@ def test_dense_linear_all_options(cin, cout):
 
 
 def test_linear_other_shapes_use_the_conv_kernel_and_reject_in_add():
-    from agile3d_amd.engine import _ptr, _stream
+    from agile3d_amd.lib import ptr as _ptr, stream as _stream
     lib = L.load()
     g = torch.Generator().manual_seed(5)
     n = 3000
@@ -271,7 +271,7 @@ def test_fused_projection_op_and_its_fallback(world, conv_kernel_family, level, 
     96 -> 64 and 32 -> 32 have no fused instantiation (stage width 96 / the LDS-resident 32-channel kernel) -- the program
     falls back to the conv + a 1x1 launch added in place instead of failing mid-forward."""
     import ctypes as C
-    from agile3d_amd.engine import _ptr, _stream
+    from agile3d_amd.lib import ptr as _ptr, stream as _stream
     coords, sc, lv, maps = world
     lib = L.load()
     g = torch.Generator().manual_seed(level * 7919 + cin * 31 + cout + cin2)
@@ -318,7 +318,7 @@ def test_fused_head_op_and_its_fallback(world, level, cin, cout, head):
     input -- the workgroup holds complete 96-column rows in exactly the operand layout of the next MFMA -- against float64,
     rows of the external output in the CALLER's order; the op's own output must be unchanged.  Level 1 and the 64- / 32-column
     shapes have no fused build: the library runs the head as its own launch (level 1: not a level-0 op -> refused)."""
-    from agile3d_amd.engine import _ptr, _stream
+    from agile3d_amd.lib import ptr as _ptr, stream as _stream
     coords, sc, lv, maps = world
     lib = L.load()
     g = torch.Generator().manual_seed(level * 977 + cin * 13 + cout + head)

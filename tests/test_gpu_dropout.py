@@ -1,39 +1,23 @@
 """Decoder dropout on the GPU: the in-kernel masks against the numpy restatement of their RNG, every
 dropout primitive against float64 autograd with those masks, the whole decoder tape at p = 0.1 against the reference
 layers with the same masks, the p = 0 / eval invariance, and repeatable training runs."""
-import copy
-import ctypes as C
 import random
 
 import numpy as np
 import pytest
 import torch
 
+from agile3d_amd import decoder_ops as ops
 from agile3d_amd import lib as L
 from agile3d_amd.synthetic import make_scene
-from dropout_ref import keep_mask, scale
+from attn_kit import DEV, check as _check, mha_ref as _mha_ref, zmat
+from dropout_ref import keep_mask
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda")
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def gpu_mask(seed, sample, site, p, heads, rows, cols):
-    out = torch.empty((heads, rows, cols), dtype=torch.uint8, device=DEV)
-    L.check(L.load().a3d_dropout_mask(seed, sample, site, p, heads, rows, cols, _ptr(out), _stream()), "a3d_dropout_mask")
-    return out
-
-
-def zmat(seed, sample, site, p, heads, rows, cols):
-    """Z = keep / (1 - p) in float64, from the library's mask."""
-    return gpu_mask(seed, sample, site, p, heads, rows, cols).cpu().double() * scale(p)
+    return ops.dropout_mask(seed, sample, site, p, heads, rows, cols)
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the masks
@@ -60,24 +44,6 @@ def test_mask_statistics(p):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. primitives
-def _mha_ref(q, k, v, mask, Z):
-    q, k, v = (t.double().clone().requires_grad_(True) for t in (q, k, v))
-    Lq, Lk = q.shape[0], k.shape[0]
-    s = torch.einsum("ihd,jhd->hij", q.view(Lq, 8, 16), k.view(Lk, 8, 16)) / 4.0
-    if mask is not None:
-        s = s.masked_fill(mask.bool()[None], float("-inf"))
-    o = torch.einsum("hij,jhd->ihd", torch.softmax(s, -1) * Z, v.view(Lk, 8, 16)).reshape(Lq, 128)
-    return o, q, k, v
-
-
-def _check(tag, pairs, tol=2e-5):
-    for name, got, want in pairs:
-        err = (got.double().cpu() - want.detach()).abs().max().item()
-        sc = max(1e-6, want.detach().abs().max().item())
-        print(f"{tag} {name}: max|diff| {err:.2e} (scale {sc:.2e})")
-        assert err <= tol * sc, (tag, name, err, sc)
-
-
 def _inputs(Lq, Lk, masked, seed):
     g = torch.Generator().manual_seed(seed)
     q, k, v = (torch.randn(n, 128, generator=g) for n in (Lq, Lk, Lk))
@@ -91,18 +57,10 @@ def _inputs(Lq, Lk, masked, seed):
 
 
 def _flash_c2s(q, k, v, w, mask, drop):
-    lib = L.load()
-    Lq, Lk = q.shape[0], k.shape[0]
     qs, kd, vd, wd = (q * 0.25).to(DEV), k.to(DEV), v.to(DEV), w.to(DEV)
     md = mask.to(DEV).contiguous() if mask is not None else None
-    nb = lib.a3d_flash_c2s_workspace_bytes(Lq, Lk)
-    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
-    o, stats = torch.empty(Lq, 128, device=DEV), torch.empty(2, 8, Lq, device=DEV)
-    L.check(lib.a3d_flash_c2s_forward_dropout(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws), nb,
-                                              drop, _stream()), "fwd")
-    dq, dk, dv = torch.empty_like(qs), torch.empty_like(kd), torch.empty_like(vd)
-    L.check(lib.a3d_flash_c2s_backward_dropout(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd),
-                                               _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nb, drop, _stream()), "bwd")
+    o, stats = ops.flash_c2s_forward(qs, kd, vd, md, drop=drop)
+    dq, dk, dv = ops.flash_c2s_backward(qs, kd, vd, md, o, stats, wd, drop=drop)
     return o, dq * 0.25, dk, dv
 
 
@@ -111,41 +69,29 @@ def test_flash_c2s_dropout_vs_float64_autograd(Lq, Lk, masked):
     p, seed, sample, site = 0.1, 0xdead_beef_0123, 1, 8
     q, k, v, w, mask = _inputs(Lq, Lk, masked, Lq * 7 + Lk)
     Z = zmat(seed, sample, site, p, 8, Lq, Lk)
-    o_ref, qr, kr, vr = _mha_ref(q, k, v, mask, Z)
-    (o_ref * w.double()).sum().backward()
+    want = _mha_ref(q, k, v, w, mask, Z)
     got = _flash_c2s(q, k, v, w, mask, L.Dropout(seed, p, sample, site, 0))
-    _check(f"flash c2s dropout {Lq}x{Lk}", zip(("o", "dq", "dk", "dv"), got, (o_ref, qr.grad, kr.grad, vr.grad)))
+    _check(f"flash c2s dropout {Lq}x{Lk}", got, want)
 
 
 @pytest.mark.parametrize("Lq,Lk", [(5003, 37), (1700, 130)])
 def test_flash_s2c_dropout_vs_float64_autograd(Lq, Lk):
-    lib = L.load()
     p, seed, sample, site = 0.1, 77, 2, 6
     q, k, v, w, _ = _inputs(Lq, Lk, False, Lq * 3 + Lk)
     Z = zmat(seed, sample, site, p, 8, Lq, Lk)
-    o_ref, qr, kr, vr = _mha_ref(q, k, v, None, Z)
-    (o_ref * w.double()).sum().backward()
+    want = _mha_ref(q, k, v, w, None, Z)
     drop = L.Dropout(seed, p, sample, site, 0)
     qd, ks, vd, wd = q.to(DEV), (k * 0.25).to(DEV), v.to(DEV), w.to(DEV)
-    o, stats = torch.empty(Lq, 128, device=DEV), torch.empty(Lq, 8, 2, device=DEV)
-    L.check(lib.a3d_flash_s2c_forward_dropout(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), drop, _stream()), "fwd")
-    nb = lib.a3d_flash_s2c_workspace_bytes(Lq, Lk)
-    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
-    dq, dk, dv = torch.empty_like(qd), torch.empty_like(ks), torch.empty_like(vd)
-    L.check(lib.a3d_flash_s2c_backward_dropout(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd), _ptr(dq),
-                                               _ptr(dk), _ptr(dv), _ptr(ws), nb, drop, _stream()), "bwd")
-    _check(f"flash s2c dropout {Lq}x{Lk}", zip(("o", "dq", "dk", "dv"), (o, dq, dk * 0.25, dv),
-                                                (o_ref, qr.grad, kr.grad, vr.grad)))
+    o, stats = ops.flash_s2c_forward(qd, ks, vd, drop=drop)
+    dq, dk, dv = ops.flash_s2c_backward(qd, ks, vd, o, stats, wd, drop=drop)
+    _check(f"flash s2c dropout {Lq}x{Lk}", (o, dq, dk * 0.25, dv), want)
 
 
 def _dense(q, k, v, w, mask, drop):
-    from agile3d_amd.train_decoder import DecoderTape
     qd, kd, vd, wd = q.to(DEV), k.to(DEV), v.to(DEV), w.to(DEV)
     md = mask.to(DEV).contiguous() if mask is not None else None
-    o = torch.empty(q.shape[0], 128, device=DEV)
-    saved = DecoderTape._dense_fwd(qd, kd, vd, md, o, drop)
-    dq, dk, dv = torch.empty_like(qd), torch.empty_like(kd), torch.empty_like(vd)
-    DecoderTape._dense_bwd(qd, kd, vd, md, o, saved, wd, dq, dk, dv, drop)
+    o, saved = ops.dense_forward(qd, kd, vd, md, drop=drop)
+    dq, dk, dv = ops.dense_backward(qd, kd, vd, md, o, saved, wd, drop=drop)
     return o, dq, dk, dv, saved[1]
 
 
@@ -154,11 +100,10 @@ def test_dense_dropout_vs_float64_autograd(Lq, Lk, masked):
     p, seed, sample, site = 0.1, 5, 0, 2
     q, k, v, w, mask = _inputs(Lq, Lk, masked, Lq + Lk)
     Z = zmat(seed, sample, site, p, 8, Lq, Lk)
-    o_ref, qr, kr, vr = _mha_ref(q, k, v, mask, Z)
-    (o_ref * w.double()).sum().backward()
+    want = _mha_ref(q, k, v, w, mask, Z)
     *got, transposed = _dense(q, k, v, w, mask, L.Dropout(seed, p, sample, site, 0))
     assert transposed == (Lq == 1500)                        # both layouts of the materialised path are covered
-    _check(f"dense dropout {Lq}x{Lk}", zip(("o", "dq", "dk", "dv"), got, (o_ref, qr.grad, kr.grad, vr.grad)))
+    _check(f"dense dropout {Lq}x{Lk}", got, want)
 
 
 def test_flash_and_dense_dropout_agree():
@@ -199,25 +144,23 @@ def test_linear_residual_dropout_vs_float64():
     xr, Wr, br, rr = (t.clone().requires_grad_(True) for t in (x.double(), W, b, r.double()))
     yr = rr + (xr @ Wr.T + br) * Z
     (yr * dyv.double()).sum().backward()
-    _check("linear + residual dropout", [("y", y.v, yr), ("dx", xt.g, xr.grad), ("dres", rt.g, rr.grad),
-                                          ("dW", tape.grads[wname], Wr.grad), ("db", tape.grads[bname], br.grad)])
+    _check("linear + residual dropout", (y.v, xt.g, rt.g, tape.grads[wname], tape.grads[bname]),
+           (yr, xr.grad, rr.grad, Wr.grad, br.grad), names=("y", "dx", "dres", "dW", "db"))
 
 
 def test_relu_dropout_vs_float64():
-    lib = L.load()
     g = torch.Generator().manual_seed(9)
     n = 77
     x, dy = torch.randn(n, 1024, generator=g), torch.randn(n, 1024, generator=g)
     drop = L.Dropout(555, 0.1, 3, 12, 0)
     xd, dyd = x.to(DEV), dy.to(DEV)
-    y, dx = torch.empty_like(xd), torch.empty_like(xd)
-    L.check(lib.a3d_dropout_rows_forward(_ptr(xd), None, _ptr(y), n, 1024, 1, drop, _stream()), "fwd")
-    L.check(lib.a3d_dropout_rows_backward(_ptr(dyd), _ptr(xd), _ptr(dx), n, 1024, drop, _stream()), "bwd")
+    y = ops.dropout_rows_forward(xd, None, True, drop)
+    dx = ops.dropout_rows_backward(dyd, xd, drop)
     Z = zmat(555, 3, 12, 0.1, 1, n, 1024)[0]
     xr = x.double().requires_grad_(True)
     yr = torch.relu(xr) * Z
     (yr * dy.double()).sum().backward()
-    _check("relu + dropout", [("y", y, yr), ("dx", dx, xr.grad)], tol=1e-6)
+    _check("relu + dropout", (y, dx), (yr, xr.grad), tol=1e-6, names=("y", "dx"))
 
 
 # ---------------------------------------------------------------------------------------------------- 3. whole tape

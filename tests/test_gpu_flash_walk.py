@@ -12,81 +12,19 @@ reach, each against float64 autograd of the plain formula on the CPU:
 Every input is seeded; nothing is read from disk.  The bar is the one of the other flash tests: max|diff| <= 2e-5 of the
 reference's largest magnitude, per output.  Workspaces and outputs start out as NaN: a slab element that is read before
 the walk's first chunk wrote it, or an output row nothing writes, fails the comparison instead of passing on zeros."""
-import ctypes as C
 import functools
 
 import pytest
 import torch
 
+from agile3d_amd import decoder_ops as ops
 from agile3d_amd import lib as L
-from dropout_ref import scale as drop_scale
+from attn_kit import DEV, check as _check, mha_ref as _mha_ref, nan as _nan, poisoned as _workspace, zmat
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda")
 CHUNK = 64                 # points per chunk (kFlChunk)
 CAP = 256                  # workgroups of the persistent kernels; _assert_walks checks it against the library
-TOL = 2e-5
 P_DROP, SEED = 0.1, 0x0bad_cafe_4321
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _nan(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
-
-
-def _workspace(nbytes):
-    return torch.full((nbytes,), 255, dtype=torch.uint8, device=DEV)        # 0xff bytes: NaN as floats
-
-
-def zmat(seed, sample, site, p, heads, rows, cols):
-    """Z = keep / (1 - p) in float64, from the library's mask (pinned on the numpy restatement in test_gpu_dropout.py)."""
-    out = torch.empty((heads, rows, cols), dtype=torch.uint8, device=DEV)
-    L.check(L.load().a3d_dropout_mask(seed, sample, site, p, heads, rows, cols, _ptr(out), _stream()), "a3d_dropout_mask")
-    return out.cpu().double() * drop_scale(p)
-
-
-# ---------------------------------------------------------------------------------------------------- reference
-def _mha_ref(q, k, v, w, mask, Z=None, per_head=False):
-    """softmax(q k^T / 4 + mask) (o Z) v per head (8 x 16) in float64 on the CPU, autograd for the loss sum(o * w):
-    (o, dq, dk, dv).  ``per_head``: one head at a time (16-channel slices, written back), for the cases whose [8, Lq, Lk]
-    float64 matrices would take gigabytes."""
-    Lq, Lk = q.shape[0], k.shape[0]
-    q64, k64, v64, w64 = (t.double() for t in (q, k, v, w))
-    blocked = mask.bool()[None] if mask is not None else None
-    o, dq = torch.empty(Lq, 128, dtype=torch.float64), torch.empty(Lq, 128, dtype=torch.float64)
-    dk, dv = torch.empty(Lk, 128, dtype=torch.float64), torch.empty(Lk, 128, dtype=torch.float64)
-    nh = 1 if per_head else 8
-    for h0 in range(0, 8, nh):
-        sl = slice(16 * h0, 16 * (h0 + nh))
-        qh, kh, vh = (t[:, sl].clone().requires_grad_(True) for t in (q64, k64, v64))
-        s = torch.einsum("ihd,jhd->hij", qh.view(Lq, nh, 16), kh.view(Lk, nh, 16)) / 4.0
-        if blocked is not None:
-            s = s.masked_fill(blocked, float("-inf"))
-        p = torch.softmax(s, -1)
-        if Z is not None:
-            p = p * Z[h0:h0 + nh]
-        oh = torch.einsum("hij,jhd->ihd", p, vh.view(Lk, nh, 16)).reshape(Lq, 16 * nh)
-        (oh * w64[:, sl]).sum().backward()
-        o[:, sl], dq[:, sl], dk[:, sl], dv[:, sl] = oh.detach(), qh.grad, kh.grad, vh.grad
-    return o, dq, dk, dv
-
-
-def _check(tag, got, want, tol=TOL):
-    errs = []
-    for name, g, r in zip(("o", "dq", "dk", "dv"), got, want):
-        err = (g.double().cpu() - r).abs().max().item()
-        sc = max(1e-6, r.abs().max().item())
-        print(f"{tag} {name}: max|diff| {err:.2e} (scale {sc:.2e}) -> {err / sc:.2e}")
-        errs.append((name, err, sc))
-    for name, err, sc in errs:
-        assert err <= tol * sc, (tag, name, err, sc)          # (a NaN fails: the comparison is False)
 
 
 # ---------------------------------------------------------------------------------------------------- inputs
@@ -142,30 +80,16 @@ def _assert_walks(workspace_bytes, long_side, *args):
 
 # ---------------------------------------------------------------------------------------------------- the kernels
 def _flash_c2s(q, k, v, w, mask, drop=None, twice=False):
-    """a3d_flash_c2s_forward + _backward (their _dropout twins with ``drop``): o, dq, dk, dv of the unscaled operands."""
-    lib = L.load()
+    """flash_c2s_forward + _backward (their _dropout twins with ``drop``): o, dq, dk, dv of the unscaled operands."""
     Lq, Lk = q.shape[0], k.shape[0]
     qs, kd, vd, wd = (q * 0.25).to(DEV), k.to(DEV), v.to(DEV), w.to(DEV)
     md = mask.to(DEV).contiguous() if mask is not None else None
-    nb = lib.a3d_flash_c2s_workspace_bytes(Lq, Lk)
-    ws = _workspace(nb)
-    o, stats = _nan(Lq, 128), _nan(2, 8, Lq)
-    if drop is None:
-        L.check(lib.a3d_flash_c2s_forward(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws), nb,
-                                          _stream()), "fwd")
-    else:
-        L.check(lib.a3d_flash_c2s_forward_dropout(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(ws),
-                                                  nb, drop, _stream()), "fwd")
+    ws = _workspace(ops.flash_c2s_workspace_bytes(Lq, Lk))
+    o, stats = ops.flash_c2s_forward(qs, kd, vd, md, o=_nan(Lq, 128), stats=_nan(2, 8, Lq), workspace=ws, drop=drop)
 
     def backward():
-        dq, dk, dv = _nan(Lq, 128), _nan(Lk, 128), _nan(Lk, 128)
-        if drop is None:
-            L.check(lib.a3d_flash_c2s_backward(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd),
-                                               _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nb, _stream()), "bwd")
-        else:
-            L.check(lib.a3d_flash_c2s_backward_dropout(_ptr(qs), _ptr(kd), _ptr(vd), _ptr(md), Lq, Lk, _ptr(o), _ptr(stats),
-                                                       _ptr(wd), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nb, drop, _stream()), "bwd")
-        return dq, dk, dv
+        return ops.flash_c2s_backward(qs, kd, vd, md, o, stats, wd, dq=_nan(Lq, 128), dk=_nan(Lk, 128), dv=_nan(Lk, 128),
+                                      workspace=ws, drop=drop)
     ws.fill_(255)                           # the backward's slabs share the forward's partials: nothing of them may be read
     dq, dk, dv = backward()
     if twice:                               # deterministic, and on a workspace that holds the first run's slabs
@@ -175,23 +99,12 @@ def _flash_c2s(q, k, v, w, mask, drop=None, twice=False):
 
 
 def _flash_s2c(q, k, v, w, drop=None):
-    """a3d_flash_s2c_forward + _backward (their _dropout twins with ``drop``); the 1 / 4 goes on the few keys, as on the tape."""
-    lib = L.load()
+    """flash_s2c_forward + _backward (their _dropout twins with ``drop``); the 1 / 4 goes on the few keys, as on the tape."""
     Lq, Lk = q.shape[0], k.shape[0]
     qd, ks, vd, wd = q.to(DEV), (k * 0.25).to(DEV), v.to(DEV), w.to(DEV)
-    o, stats = _nan(Lq, 128), _nan(Lq, 8, 2)
-    nb = lib.a3d_flash_s2c_workspace_bytes(Lq, Lk)
-    ws = _workspace(nb)
-    dq, dk, dv = _nan(Lq, 128), _nan(Lk, 128), _nan(Lk, 128)
-    if drop is None:
-        L.check(lib.a3d_flash_s2c_forward(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _stream()), "fwd")
-        L.check(lib.a3d_flash_s2c_backward(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd), _ptr(dq),
-                                           _ptr(dk), _ptr(dv), _ptr(ws), nb, _stream()), "bwd")
-    else:
-        L.check(lib.a3d_flash_s2c_forward_dropout(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), drop, _stream()),
-                "fwd")
-        L.check(lib.a3d_flash_s2c_backward_dropout(_ptr(qd), _ptr(ks), _ptr(vd), Lq, Lk, _ptr(o), _ptr(stats), _ptr(wd), _ptr(dq),
-                                                   _ptr(dk), _ptr(dv), _ptr(ws), nb, drop, _stream()), "bwd")
+    o, stats = ops.flash_s2c_forward(qd, ks, vd, o=_nan(Lq, 128), stats=_nan(Lq, 8, 2), drop=drop)
+    dq, dk, dv = ops.flash_s2c_backward(qd, ks, vd, o, stats, wd, dq=_nan(Lq, 128), dk=_nan(Lk, 128), dv=_nan(Lk, 128),
+                                        workspace=_workspace(ops.flash_s2c_workspace_bytes(Lq, Lk)), drop=drop)
     return o, dq, dk * 0.25, dv
 
 
@@ -203,7 +116,7 @@ def test_c2s_workgroups_walk_several_chunks(Lq, Lk, masked):
     A: workgroups 0 and 1 take two chunks, the last chunk holds 37 keys (two full groups + 5) and the mask's rows are not a
     multiple of four bytes; B: three chunks per workgroup, a last chunk of one key; C: no mask, fewer queries than a tile;
     D: the 14-tile build and the second launch (q0 = 224, one query) both walking."""
-    _assert_walks(L.load().a3d_flash_c2s_workspace_bytes, Lk, Lq, None)
+    _assert_walks(ops.flash_c2s_workspace_bytes, Lk, Lq, None)
     seed = Lq * 7 + Lk
     q, k, v, w = _qkvw(Lq, Lk, seed)
     mask = _structured_mask(Lq, Lk, seed) if masked else None
@@ -244,7 +157,7 @@ def test_c2s_short_key_side(Lk):
 def test_s2c_workgroups_walk_several_chunks(Lq, Lk):
     """Scene-to-click over more than 256 chunks of points: the dK / dV slabs of a workgroup add up over its two / three
     chunks (the last one of 37 points / one point), the key-side fragments are fetched again per chunk, 256 slabs reduce."""
-    _assert_walks(L.load().a3d_flash_s2c_workspace_bytes, Lq, None, Lk)
+    _assert_walks(ops.flash_s2c_workspace_bytes, Lq, None, Lk)
     q, k, v, w = _qkvw(Lq, Lk, Lq * 3 + Lk)
     want = _mha_ref(q, k, v, w, None)
     got = _flash_s2c(q, k, v, w)
@@ -271,7 +184,7 @@ def test_c2s_dropout_walk_and_second_launch(Lq, Lk, walk):
     seed = Lq * 7 + Lk
     q, k, v, w = _qkvw(Lq, Lk, seed)
     if walk:
-        _assert_walks(L.load().a3d_flash_c2s_workspace_bytes, Lk, Lq, None)
+        _assert_walks(ops.flash_c2s_workspace_bytes, Lk, Lq, None)
         mask = _structured_mask(Lq, Lk, seed)
     else:
         mask = _random_mask(Lq, Lk, seed)
@@ -287,7 +200,7 @@ def test_s2c_dropout_walk_and_widest_key_side(Lq, Lk):
     sample, site = 2, 6
     q, k, v, w = _qkvw(Lq, Lk, Lq * 3 + Lk)
     if Lq > CAP * CHUNK:
-        _assert_walks(L.load().a3d_flash_s2c_workspace_bytes, Lq, None, Lk)
+        _assert_walks(ops.flash_s2c_workspace_bytes, Lq, None, Lk)
     Z = zmat(SEED, sample, site, P_DROP, 8, Lq, Lk)
     want = _mha_ref(q, k, v, w, None, Z)
     got = _flash_s2c(q, k, v, w, drop=L.Dropout(SEED, P_DROP, sample, site, 0))
@@ -303,9 +216,8 @@ def test_tape_flash_matches_dense_on_a_walking_scene():
     from agile3d_amd import build_model, default_args
     from oracle import decoder as od
     N, Q = 17000, 12
-    lib = L.load()
-    _assert_walks(lib.a3d_flash_c2s_workspace_bytes, N, Q, None)
-    _assert_walks(lib.a3d_flash_s2c_workspace_bytes, N, None, Q)
+    _assert_walks(ops.flash_c2s_workspace_bytes, N, Q, None)
+    _assert_walks(ops.flash_s2c_workspace_bytes, N, None, Q)
     torch.manual_seed(11)
     model = build_model(default_args()).cuda().train()
     g = torch.Generator().manual_seed(17)

@@ -10,22 +10,18 @@ the kernel is allowed FOUR times the error torch's own float32 CPU implementatio
 the float64 reference on the same inputs, plus 1e-7 (an exact float32 result must not make the bound zero; the factor of
 four covers a different but valid summation order) -- ``_derived_bound``.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from agile3d_amd import backward as B
+from agile3d_amd import decoder_ops as ops
 from agile3d_amd import lib as L
+from agile3d_amd.lib import ptr as _ptr
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _err(got, ref):
@@ -227,19 +223,8 @@ def test_softmax_rows_and_backward_around_the_lane_strides_and_the_512_switch(Lk
     Measured on an MI355X, largest over the 24 cases (float32-CPU error / kernel error; largest ratio of a single case):
       softmax            2.96e-07 / 2.13e-07   ratio <= 2.31 (L = 63: 7.2e-08 / 1.67e-07)
       softmax backward   1.90e-07 / 2.73e-07   ratio <= 2.04 (L = 128 masked: 6.9e-08 / 1.40e-07)"""
-    lib = L.load()
-    rows = 24
-    S, dP, blocked = _softmax_inputs((rows, Lk), 1, masked, 31 * Lk + masked)
-
-    def forward(s):
-        L.check(lib.a3d_softmax_rows(_ptr(s), rows, Lk, None), "a3d_softmax_rows")
-        return s
-
-    def backward(p, d):
-        L.check(lib.a3d_softmax_rows_backward(_ptr(p), _ptr(d), rows, Lk, None), "a3d_softmax_rows_backward")
-        return d
-
-    _softmax_check(f"rows L={Lk} masked={masked}", S, dP, blocked, 1, forward, backward)
+    S, dP, blocked = _softmax_inputs((24, Lk), 1, masked, 31 * Lk + masked)
+    _softmax_check(f"rows L={Lk} masked={masked}", S, dP, blocked, 1, ops.softmax_rows, ops.softmax_rows_backward)
 
 
 @pytest.mark.parametrize("Lq", [1, 3, 20])
@@ -252,19 +237,8 @@ def test_softmax_cols_and_backward(Lq, Lk):
     Measured on an MI355X, largest over the 12 cases (float32-CPU error / kernel error; largest ratio of a single case):
       softmax            4.91e-07 / 4.91e-07   ratio <= 1.00
       softmax backward   7.64e-07 / 9.73e-07   ratio <= 1.36 (Lq = 20, Lk = 255)"""
-    lib = L.load()
-    H = 8
-    S, dP, _ = _softmax_inputs((H, Lq, Lk), 1, False, 97 * Lq + Lk)
-
-    def forward(s):
-        L.check(lib.a3d_softmax_cols(_ptr(s), H, Lq, Lk, None), "a3d_softmax_cols")
-        return s
-
-    def backward(p, d):
-        L.check(lib.a3d_softmax_cols_backward(_ptr(p), _ptr(d), H, Lq, Lk, None), "a3d_softmax_cols_backward")
-        return d
-
-    _softmax_check(f"cols Lq={Lq} Lk={Lk}", S, dP, None, 1, forward, backward)
+    S, dP, _ = _softmax_inputs((8, Lq, Lk), 1, False, 97 * Lq + Lk)
+    _softmax_check(f"cols Lq={Lq} Lk={Lk}", S, dP, None, 1, ops.softmax_cols, ops.softmax_cols_backward)
 
 
 @pytest.mark.parametrize("Lq,Lk,H,dh", [(20, 20, 8, 16), (5, 300, 8, 16), (20, 1500, 8, 16), (1500, 7, 8, 16),
@@ -272,14 +246,13 @@ def test_softmax_cols_and_backward(Lq, Lk):
 def test_attn_scores_with_a_mask(Lq, Lk, H, dh):
     """a3d_attn_scores with its uint8 mask (~30 % blocked): the thread-per-element kernel, k_tr_scores_long by key and by
     query, and its dh = 128 build.  Unblocked entries against float64 einsum to the project's 1e-4, blocked ones are -inf."""
-    lib = L.load()
     g = torch.Generator().manual_seed(Lq * 7 + Lk)
     q, k = torch.randn(Lq, H * dh, generator=g), torch.randn(Lk, H * dh, generator=g)
     mask = (torch.rand(Lq, Lk, generator=g) < 0.3)
     scale = dh ** -0.5
     S = torch.full((H, Lq, Lk), NAN, device="cuda")
     q_d, k_d, mask_d = q.cuda(), k.cuda(), mask.to(torch.uint8).cuda()
-    L.check(lib.a3d_attn_scores(_ptr(q_d), _ptr(k_d), Lq, Lk, H, dh, scale, _ptr(mask_d), _ptr(S), None), "a3d_attn_scores")
+    ops.attn_scores(q_d, k_d, scale, mask_d, out=S, heads=H)
     ref = scale * torch.einsum("ihd,jhd->hij", q.double().view(Lq, H, dh), k.double().view(Lk, H, dh))
     S = S.cpu()
     blocked = mask.expand(H, Lq, Lk)
@@ -292,13 +265,13 @@ def test_attn_scores_with_a_mask(Lq, Lk, H, dh):
 def test_attn_apply_at_the_self_attention_sizes(Lq, Lk, H, dh, transposed):
     """a3d_attn_apply where nothing is split: k_tr_apply / k_tr_apply_t at the click-to-click sizes and
     k_tr_apply_t_head<128>, against float64 einsum to the project's 2e-5 max(1, |ref|max)."""
-    from agile3d_amd.train_decoder import _apply
     g = torch.Generator().manual_seed(Lq + 3 * Lk + transposed)
     P = torch.softmax(torch.randn(H, Lq, Lk, generator=g) * 2, -1)
     rows_in, rows_out = (Lq, Lk) if transposed else (Lk, Lq)
     V = torch.randn(rows_in, H * dh, generator=g)
     out = torch.full((rows_out, H * dh), NAN, device="cuda")
-    _apply(P.cuda(), V.cuda(), Lq, Lk, H, dh, transposed, 0.5, out)
+    ops.attn_apply(P.cuda(), V.cuda(), transposed, 0.5, out,
+                   workspace=_scratch(ops.attn_apply_workspace_bytes(Lq, Lk, H, dh, transposed)))
     eq = "hij,ihd->jhd" if transposed else "hij,jhd->ihd"
     ref = 0.5 * torch.einsum(eq, P.double(), V.double().view(rows_in, H, dh)).reshape(rows_out, H * dh)
     assert _err(out, ref) <= 2e-5 * max(1.0, ref.abs().max().item())
@@ -334,7 +307,6 @@ def test_group_max_and_its_backward_pick_the_first_maximum(N):
     of the points (point 0 always) the group's largest value is copied to another query of the group, so the maximum is
     tied; values and indices must equal numpy's max / argmax (first occurrence) exactly, and the backward must put every
     dout on that index and exact zeros elsewhere."""
-    lib = L.load()
     lq, qbeg, qend, ref_out, ref_arg = _group_max_inputs(N)
     Q, G = lq.shape[1], len(qbeg)
     rng = np.random.default_rng(N + 1)
@@ -342,14 +314,14 @@ def test_group_max_and_its_backward_pick_the_first_maximum(N):
     out = torch.full((N, G), NAN, device="cuda")
     arg = torch.full((N, G), -1, dtype=torch.int32, device="cuda")
     qbeg_d, qend_d = torch.from_numpy(qbeg).cuda(), torch.from_numpy(qend).cuda()
-    L.check(lib.a3d_group_max(_ptr(lq_d), N, Q, _ptr(qbeg_d), _ptr(qend_d), G, _ptr(out), _ptr(arg), None), "a3d_group_max")
+    ops.group_max(lq_d, qbeg_d, qend_d, out=out, arg=arg)
     assert np.array_equal(out.cpu().numpy(), ref_out) and np.array_equal(arg.cpu().numpy(), ref_arg)
     dout = rng.standard_normal((N, G)).astype(np.float32)
     ref_dlq = np.zeros((N, Q), np.float32)
     np.put_along_axis(ref_dlq, ref_arg.astype(np.int64), dout, 1)
     dlq = torch.full((N, Q), NAN, device="cuda")
     dout_d = torch.from_numpy(dout).cuda()
-    L.check(lib.a3d_group_max_backward(_ptr(dout_d), _ptr(arg), N, Q, G, _ptr(dlq), None), "a3d_group_max_backward")
+    ops.group_max_backward(dout_d, arg, Q, out=dlq)
     assert np.array_equal(dlq.cpu().numpy(), ref_dlq)
 
 

@@ -6,7 +6,8 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from agile3d_amd import lib as L
-from agile3d_amd.train_decoder import _pack, _ptr, _stream
+from agile3d_amd.decoder_ops import pack_linear
+from agile3d_amd.lib import ptr as _ptr, stream as _stream
 
 nbuf = int(sys.argv[1]) if len(sys.argv) > 1 else 24
 fragment = len(sys.argv) > 2 and sys.argv[2] == "1"
@@ -20,7 +21,7 @@ if fragment:                                  # odd-sized blocks allocated and f
     junk = junk[::2]
 bufs = [torch.randn(n, 128, device="cuda") for _ in range(nbuf)]
 W = torch.randn(128, 128, device="cuda") / 11
-wp = _pack(W)[0]
+wp = pack_linear(W)[0]
 bias = torch.zeros(128, device="cuda")
 def run(x, y):
     L.check(lib.a3d_linear(_ptr(x), 128, None, 0, n, 128, 128, _ptr(wp), None, _ptr(bias), None, 0, 0, _ptr(y), 128,
