@@ -6,6 +6,8 @@
 //   a3d_adamw_step  : torch's single-tensor AdamW update with the clip coefficient folded into the gradient read:
 //                     p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
 //                     p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+//                     (hyper-parameters are doubles; 1 - lr*wd, 1 - b1, 1 - b2 and the bias terms are formed in double on
+//                     the host and rounded to fp32 once, as torch forms its scalars)
 #include "common.h"
 
 namespace a3d {
@@ -35,20 +37,36 @@ __global__ void k_sumsq_final(const double* partial, int nb, double* out, int ac
   }
 }
 
-__global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                        size_t n, float grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
-                        float bias1, float bias2_sqrt) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float gi = g[i] * grad_scale;
-  float pi = p[i] * (1.f - lr * weight_decay);
-  const float mi = beta1 * m[i] + (1.f - beta1) * gi;          // exp_avg.lerp_(grad, 1 - beta1)
-  const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
-  const float denom = sqrtf(vi) / bias2_sqrt + eps;
-  pi -= (lr / bias1) * (mi / denom);
+// The scalars of one update, formed in DOUBLE on the host from the double hyper-parameters and rounded once -- torch's
+// scalar semantics: (float)(1 - beta2) is 0.001f, while 1.f - 0.999f is 0.00099998713 (1.3e-5 off in every exp_avg_sq).
+struct adamw_scalars {
+  float grad_scale, decay, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, lr;
+};
+static adamw_scalars make_adamw_scalars(double lr, double beta1, double beta2, double eps, double weight_decay,
+                                        double grad_scale) {
+  return {(float)grad_scale, (float)(1.0 - lr * weight_decay), (float)beta1, (float)(1.0 - beta1), (float)beta2,
+          (float)(1.0 - beta2), (float)eps, (float)lr};
+}
+// the one statement of the update: k_adamw and k_mt_adamw both call it, so their results are the same bits
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, int64_t i, const adamw_scalars& c, float bias1,
+                                             float bias2_sqrt) {
+  const float gi = g[i] * c.grad_scale;
+  float pi = p[i] * c.decay;
+  const float mi = c.beta1 * m[i] + c.one_minus_beta1 * gi;          // exp_avg.lerp_(grad, 1 - beta1)
+  const float vi = c.beta2 * v[i] + c.one_minus_beta2 * gi * gi;
+  const float denom = sqrtf(vi) / bias2_sqrt + c.eps;
+  pi -= (c.lr / bias1) * (mi / denom);
   p[i] = pi;
   m[i] = mi;
   v[i] = vi;
+}
+
+__global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                        size_t n, adamw_scalars c, float bias1, float bias2_sqrt) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  adamw_update(p, g, m, v, (int64_t)i, c, bias1, bias2_sqrt);
 }
 
 // ---- all parameter tensors in one launch: a workgroup handles one 4096-element chunk, its tensor found by a binary
@@ -94,23 +112,14 @@ __global__ void __launch_bounds__(1024) k_mt_sumsq_final(const double* __restric
   }
   if (threadIdx.x == 0) *out = red[0];
 }
-__global__ void __launch_bounds__(256) k_mt_adamw(const a3d_mt_tensor* __restrict__ tab, int nt, float grad_scale, float lr,
-                                                  float beta1, float beta2, float eps, float weight_decay) {
+__global__ void __launch_bounds__(256) k_mt_adamw(const a3d_mt_tensor* __restrict__ tab, int nt, adamw_scalars c) {
   const int ti = mt_find(tab, nt, blockIdx.x);
   const a3d_mt_tensor t = tab[ti];
   const int64_t base = (int64_t)(blockIdx.x - t.chunk0) * A3D_MT_CHUNK;
   for (int e = threadIdx.x; e < A3D_MT_CHUNK; e += 256) {
     const int64_t i = base + e;
     if (i >= t.n) break;
-    const float gi = t.g[i] * grad_scale;   // the same arithmetic, in the same order, as k_adamw
-    float pi = t.p[i] * (1.f - lr * weight_decay);
-    const float mi = beta1 * t.m[i] + (1.f - beta1) * gi;
-    const float vi = beta2 * t.v[i] + (1.f - beta2) * gi * gi;
-    const float denom = sqrtf(vi) / t.bias2_sqrt + eps;
-    pi -= (lr / t.bias1) * (mi / denom);
-    t.p[i] = pi;
-    t.m[i] = mi;
-    t.v[i] = vi;
+    adamw_update(t.p, t.g, t.m, t.v, i, c, t.bias1, t.bias2_sqrt);
   }
 }
 
@@ -159,17 +168,17 @@ extern "C" int a3d_sum_squares_accumulate(const float* g_dev, int64_t n, double*
 }
 
 extern "C" int a3d_adamw_step(float* param_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev,
-                              int64_t n, int step, float lr, float beta1, float beta2, float eps, float weight_decay,
-                              float grad_scale, void* stream) {
+                              int64_t n, int step, double lr, double beta1, double beta2, double eps,
+                              double weight_decay, double grad_scale, void* stream) {
   if (!param_dev || !grad_dev || !exp_avg_dev || !exp_avg_sq_dev || n <= 0 || step < 1) {
     set_error("a3d_adamw_step: bad arguments (step counts from 1)");
     return A3D_ERR_INVALID;
   }
   // bias corrections in double on the host, like torch's scalar path
-  const double b1 = 1.0 - pow((double)beta1, (double)step), b2 = 1.0 - pow((double)beta2, (double)step);
-  k_adamw<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(param_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev,
-                                                                       (size_t)n, grad_scale, lr, beta1, beta2, eps,
-                                                                       weight_decay, (float)b1, (float)sqrt(b2));
+  const double b1 = 1.0 - pow(beta1, (double)step), b2 = 1.0 - pow(beta2, (double)step);
+  k_adamw<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      param_dev, grad_dev, exp_avg_dev, exp_avg_sq_dev, (size_t)n,
+      make_adamw_scalars(lr, beta1, beta2, eps, weight_decay, grad_scale), (float)b1, (float)sqrt(b2));
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -194,14 +203,15 @@ extern "C" int a3d_sum_squares_multi(const a3d_mt_tensor* table_dev, int n_tenso
   return A3D_OK;
 }
 
-extern "C" int a3d_adamw_step_multi(const a3d_mt_tensor* table_dev, int n_tensors, int64_t n_chunks, float lr, float beta1,
-                                    float beta2, float eps, float weight_decay, float grad_scale, void* stream) {
+extern "C" int a3d_adamw_step_multi(const a3d_mt_tensor* table_dev, int n_tensors, int64_t n_chunks, double lr,
+                                    double beta1, double beta2, double eps, double weight_decay, double grad_scale,
+                                    void* stream) {
   if (!table_dev || n_tensors < 1 || n_chunks < 1 || n_chunks > 0x7fffffff) {
     set_error("a3d_adamw_step_multi: bad arguments");
     return A3D_ERR_INVALID;
   }
-  k_mt_adamw<<<(unsigned)n_chunks, 256, 0, (hipStream_t)stream>>>(table_dev, n_tensors, grad_scale, lr, beta1, beta2, eps,
-                                                                  weight_decay);
+  k_mt_adamw<<<(unsigned)n_chunks, 256, 0, (hipStream_t)stream>>>(
+      table_dev, n_tensors, make_adamw_scalars(lr, beta1, beta2, eps, weight_decay, grad_scale));
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

@@ -338,12 +338,12 @@ SYMBOLS = {
     "a3d_sum_squares_workspace_bytes": (C.c_size_t, []),
     "a3d_sum_squares": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_void_p]),
     "a3d_sum_squares_accumulate": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "a3d_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float,
-                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "a3d_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double,
+                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "a3d_mt_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "a3d_sum_squares_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "a3d_adamw_step_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.c_float, C.c_void_p]),
+    "a3d_adamw_step_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_void_p]),
     "a3d_bn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "a3d_bn_train_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                        C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -428,7 +428,7 @@ class A3DError(RuntimeError):
     pass
 
 
-ABI_VERSION = 3   # include/agile3d_hip.h: A3D_ABI_VERSION
+ABI_VERSION = 4   # include/agile3d_hip.h: A3D_ABI_VERSION
 
 
 def load():

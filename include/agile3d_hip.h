@@ -36,9 +36,9 @@ extern "C" {
 #define A3D_NUM_LEVELS 5           /* tensor strides 1,2,4,8,16 (res16unet.py:222-295) */
 
 /* Version of this interface: bumped whenever a struct grows or a buffer contract changes (2: a3d_op's fused-head fields, the
- * third block of a3d_decoder_sample::kv0_dev + kv0_blocks; 3: a3d_conv_wgrad needs a3d_scene_build_wgrad_lists).  A host binding compares it with the header it was written
+ * third block of a3d_decoder_sample::kv0_dev + kv0_blocks; 3: a3d_conv_wgrad needs a3d_scene_build_wgrad_lists; 4: the hyper-parameters of a3d_adamw_step and a3d_adamw_step_multi are doubles).  A host binding compares it with the header it was written
  * against before the first call (agile3d_amd/lib.py does). */
-#define A3D_ABI_VERSION 3
+#define A3D_ABI_VERSION 4
 int         a3d_version(void);
 const char* a3d_last_error(void);
 /* plain hipMemcpy device->host (+ stream sync); lets non-torch hosts and tests read tables */
@@ -450,7 +450,9 @@ int a3d_dropout_rows_backward(const float* dy_dev, const float* x_pre_dev, float
  * clip_grad_norm_(parameters, max_norm) (engine.py:145-150).  a3d_sum_squares returns sum g^2 of one tensor to the
  * host (the caller adds the tensors, clip coefficient = min(1, max_norm / (sqrt(total) + 1e-6))); a3d_adamw_step is
  * torch's single-tensor AdamW update with the gradient read multiplied by grad_scale (the clip coefficient);
- * step counts from 1. */
+ * step counts from 1.  The hyper-parameters are doubles, as torch holds them: 1 - lr * weight_decay, 1 - beta1,
+ * 1 - beta2 and the bias corrections are formed in double on the host and rounded to fp32 once ((float)(1 - 0.999)
+ * is 0.001f; 1.f - 0.999f is 1.3e-5 away from it, which every element of exp_avg_sq would carry). */
 size_t a3d_sum_squares_workspace_bytes(void);
 int    a3d_sum_squares(const float* g_dev, int64_t n, double* out_host, void* workspace_dev, size_t workspace_bytes,
                        void* stream);
@@ -458,15 +460,16 @@ int    a3d_sum_squares(const float* g_dev, int64_t n, double* out_host, void* wo
 int    a3d_sum_squares_accumulate(const float* g_dev, int64_t n, double* acc_dev, void* workspace_dev,
                                   size_t workspace_bytes, void* stream);
 int    a3d_adamw_step(float* param_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n,
-                      int step, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                      void* stream);
+                      int step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                      double grad_scale, void* stream);
 
 /* The same two operations over ALL parameter tensors in one launch each (a training step updates 268 tensors).  The
  * caller uploads a table of a3d_mt_tensor entries, one per tensor in any fixed order: chunk0 = number of
  * A3D_MT_CHUNK-element chunks of the tensors before it, bias1 = 1 - beta1^step, bias2_sqrt = sqrt(1 - beta2^step) of
  * THAT tensor's step count (torch.optim.AdamW's per-parameter state['step']).  a3d_sum_squares_multi writes
  * sum over all tensors of sum g^2 to *out_dev (fp64, deterministic); a3d_adamw_step_multi = a3d_adamw_step on every
- * entry (bit-identical results). */
+ * entry (bit-identical results when bias1 and bias2_sqrt are (float) of the doubles above: one device function does
+ * the update for both). */
 #define A3D_MT_CHUNK 4096
 typedef struct a3d_mt_tensor {
   float* p; const float* g; float* m; float* v;
@@ -478,8 +481,8 @@ typedef struct a3d_mt_tensor {
 size_t a3d_mt_workspace_bytes(int64_t n_chunks);
 int    a3d_sum_squares_multi(const a3d_mt_tensor* table_dev, int n_tensors, int64_t n_chunks, double* out_dev,
                              void* workspace_dev, size_t workspace_bytes, void* stream);
-int    a3d_adamw_step_multi(const a3d_mt_tensor* table_dev, int n_tensors, int64_t n_chunks, float lr, float beta1,
-                            float beta2, float eps, float weight_decay, float grad_scale, void* stream);
+int    a3d_adamw_step_multi(const a3d_mt_tensor* table_dev, int n_tensors, int64_t n_chunks, double lr, double beta1,
+                            double beta2, double eps, double weight_decay, double grad_scale, void* stream);
 
 /* Many conv weights packed by ONE launch (a training iteration repacks both orientations of every sparse-conv kernel
  * after the optimiser step: ~230 a3d_pack_conv_weight calls plus the transposes / flips / slices feeding them).  Job i
