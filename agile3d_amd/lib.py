@@ -169,6 +169,40 @@ class SessionGuideArgs(C.Structure):
                 ("click_obj", C.c_uint8 * 256)]
 
 
+class Piece(C.Structure):
+    """a3d_piece: one connected piece -- its root (the smallest caller row), key, voxels, 1 if it holds a clicked row, and the
+    inclusive bounding box in voxel coordinates."""
+    _fields_ = [("root", C.c_int32), ("key", C.c_int32), ("voxels", C.c_int32), ("clicked", C.c_int32),
+                ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+
+class LabelPiecesArgs(C.Structure):
+    """a3d_label_pieces_args: the scene and the keys, the optional lift to full resolution, the outputs (piece_qv, piece_full,
+    the records, int32 [2] count and error word), the workspace, the settings and the clicked rows by value."""
+    _fields_ = [("scene", C.c_void_p), ("n", C.c_int64), ("keys_dev", C.c_void_p), ("inverse_map_dev", C.c_void_p),
+                ("n_full", C.c_int64), ("piece_qv_dev", C.c_void_p), ("piece_full_dev", C.c_void_p), ("out_dev", C.c_void_p),
+                ("n_out_dev", C.c_void_p), ("workspace_dev", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("connectivity", C.c_int32), ("max_out", C.c_int32), ("n_clicks", C.c_int32), ("reserved_", C.c_int32),
+                ("click_row", C.c_int32 * 256)]
+
+
+class AbsorbSummary(C.Structure):
+    """a3d_absorb_summary: small pieces (the capacity needed on overflow), relabelled pieces and voxels, kept-isolated pieces,
+    the error word (A3D_ABSORB_OVERFLOW, A3D_ABSORB_BAD_LABEL)."""
+    _fields_ = [("small_pieces", C.c_int32), ("relabelled_pieces", C.c_int32), ("relabelled_voxels", C.c_int32),
+                ("kept_isolated", C.c_int32), ("err", C.c_int32), ("reserved_", C.c_int32 * 3)]
+
+
+class AbsorbPiecesArgs(C.Structure):
+    """a3d_absorb_pieces_args: the scene, the labels and their pieces, the output labels and summary, the workspace
+    a3d_label_pieces used, the settings and the clicked rows by value."""
+    _fields_ = [("scene", C.c_void_p), ("n", C.c_int64), ("labels_dev", C.c_void_p), ("piece_qv_dev", C.c_void_p),
+                ("labels_out_dev", C.c_void_p), ("summary_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("min_voxels", C.c_int32), ("connectivity", C.c_int32),
+                ("n_classes", C.c_int32), ("capacity", C.c_int32), ("n_clicks", C.c_int32), ("reserved_", C.c_int32),
+                ("click_row", C.c_int32 * 256)]
+
+
 class Camera(C.Structure):
     """a3d_camera: pixel (u, v)'s ray starts at o and runs along normalize(d00 + u du + v dv), evaluated in fp32."""
     _fields_ = [("o", C.c_float * 3), ("d00", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
@@ -394,6 +428,10 @@ SYMBOLS = {
     "a3d_session_paint": (C.c_int, [C.POINTER(SessionPaintArgs), C.c_void_p]),
     "a3d_session_edit": (C.c_int, [C.POINTER(SessionEditArgs), C.c_void_p]),
     "a3d_session_guide": (C.c_int, [C.POINTER(SessionGuideArgs), C.c_void_p]),
+    "a3d_pieces_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "a3d_label_pieces": (C.c_int, [C.POINTER(LabelPiecesArgs), C.c_void_p]),
+    "a3d_absorb_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "a3d_absorb_pieces": (C.c_int, [C.POINTER(AbsorbPiecesArgs), C.c_void_p]),
     "a3d_render_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "a3d_render_camera_bounds": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_double)]),
     "a3d_render_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(Camera), C.POINTER(RenderOut),

@@ -26,6 +26,8 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
                                         GUI's "unselect point" is a TODO, gui.py:283-287; a rule of ours)
     where the labels are unsure, the    a3d_session_guide + a3d_click_clusters  (guide, confidence_at: the tool drops the
     next click                          logits after the arg-max, :78-81; a rule of ours)
+    where in space a label lies         a3d_label_pieces / a3d_absorb_pieces  (pieces, piece_at, despeckle, guide(regions=
+                                        "connected"): connected pieces of a labelling on the voxel lattice; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -255,15 +257,56 @@ def suggest_clicks(clusters, least_confident, coords_row_lookup, max_suggestions
                             min(1, max_suggestions))
 
 
+MAX_SPOTS = 255                                 # the pseudo ids 1..255 the cluster search tells apart
+
+
+def rank_spots(records, max_spots=MAX_SPOTS):
+    """The spots ``guide(regions="connected")`` searches, from the records of ``a3d_label_pieces`` (anything with ``root`` and
+    ``voxels`` per entry; any order): ranked by size, largest first, ties to the lower root; at most ``max_spots``.  Returns
+    the indices into ``records``; the spot at position k gets pseudo id k + 1.  Pure Python."""
+    if int(max_spots) != max_spots or max_spots < 0:
+        raise ValueError("max_spots must be an integer >= 0")
+    order = sorted(range(len(records)), key=lambda k: (-int(records[k]["voxels"]), int(records[k]["root"])))
+    return order[:int(max_spots)]
+
+
+class PiecesResult:
+    """What ``pieces()`` returns.  Device tensors: ``piece_qv`` int32 [n_voxels] (the smallest voxel row of the voxel's piece)
+    and ``piece_full`` int32 [n_full] (the same lifted to the vertices).  Host: ``records``, a numpy structured array
+    (``view.PIECE``: root, key = the object id, voxels, clicked, lo, hi) in ascending root; ``object_pieces`` int64 (pieces per
+    object id); ``n_pieces``; ``connectivity`` as used."""
+
+    __slots__ = ("piece_qv", "piece_full", "records", "object_pieces", "n_pieces", "connectivity")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+class DespeckleResult:
+    """What ``despeckle()`` returns: ``labels_full``, ``colors``, ``miou`` and ``iou_per_object`` as a ``SessionResult`` holds
+    them, ``labels_qv`` int32 [n_voxels] on the device, and the counts of ``a3d_absorb_pieces``' summary: ``small_pieces``,
+    ``relabelled_pieces``, ``relabelled_voxels``, ``kept_isolated``; ``min_voxels`` and ``connectivity`` as used."""
+
+    __slots__ = ("labels_full", "colors", "miou", "iou_per_object", "labels_qv", "small_pieces", "relabelled_pieces",
+                 "relabelled_voxels", "kept_isolated", "min_voxels", "connectivity")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
 class GuideResult:
     """What ``guide()`` returns.  Device tensors: ``labels_qv`` int32 [n_voxels] (what ``infer()`` computed), ``runner_qv``
     int32 (the second choice), ``margin_qv`` fp32 (winner's logit minus runner-up's; +inf on a clicked voxel), ``margin_full``
     fp32 [n_full], ``colors`` fp32 [n_full, 3] (the confidence view, for ``render(colors=)``).  Host: ``object_voxels`` and
     ``object_contested`` int64 [1 + K] (voxels and contested voxels per object id), ``least_confident`` = ``(row, margin)``
-    or ``None``, ``n_contested``, ``suggestions`` (``rank_suggestions``), ``threshold`` and ``full_margin`` as used."""
+    or ``None``, ``n_contested``, ``suggestions`` (``rank_suggestions``), ``threshold`` and ``full_margin`` as used.  With
+    ``regions="connected"``: ``n_spots`` (connected contested spots) and ``n_spots_searched`` (those among them, at most
+    ``MAX_SPOTS``, whose deepest voxel was searched); ``None`` otherwise."""
 
     __slots__ = ("labels_qv", "runner_qv", "margin_qv", "margin_full", "colors", "object_voxels", "object_contested",
-                 "least_confident", "n_contested", "suggestions", "threshold", "full_margin")
+                 "least_confident", "n_contested", "suggestions", "threshold", "full_margin", "n_spots", "n_spots_searched")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -1189,7 +1232,7 @@ class InteractiveSession:
         return res
 
     # ------------------------------------------------------------------ where the labels are unsure
-    def guide(self, threshold=1.0, full_margin=4.0, doubt_color=(1.0, 1.0, 1.0), max_suggestions=5):
+    def guide(self, threshold=1.0, full_margin=4.0, doubt_color=(1.0, 1.0, 1.0), max_suggestions=5, regions="pairs"):
         """Where the LAST ``infer()`` is unsure, and where a next click would help most.  From the logits that inference
         used (``ValueError`` when there are none: before the first ``infer()``, and after anything that changed the click
         list or the scene since -- ``click``, ``undo``, ``redo``, ``remove_click``, ``restore_*``, ``reset``, ``load_scene``):
@@ -1210,8 +1253,22 @@ class InteractiveSession:
         ``threshold`` and ``full_margin`` are in logit units.  The defaults, 1.0 and 4.0, are this project's choice and are
         NOT tuned on real scans.  A region is told from another by the simulator's cluster id, 96 x runner-up + 11 x winner,
         which is unique while object ids stay below 96; above that two regions can share an id and count as one.
-        One ``a3d_session_guide`` call, the cluster search, then ONE host round trip.  Returns a ``GuideResult``."""
+        One ``a3d_session_guide`` call, the cluster search, then ONE host round trip.  Returns a ``GuideResult``.
+
+        ``regions="connected"`` tells regions apart by WHERE they lie: a SPOT is a connected piece (26-connectivity,
+        ``a3d_label_pieces``) of the contested voxels with one (runner-up, winner) pair -- key ``256 x runner-up + winner``,
+        -1 on the other voxels -- so two doubtful places between the same two objects are two spots and get a suggestion
+        each.  The spots are ranked by size, ties to the lower root (``rank_spots``); the first ``MAX_SPOTS`` = 255 get the
+        pseudo ids 1..255 in a per-voxel array built on the device, and the same exact search runs with these as the wanted
+        labels over a prediction of 0 everywhere: each spot's deepest voxel is the one farthest from every voxel outside THAT
+        spot.  Suggestions are ranked by depth as before, the object is the spot's runner-up, and each carries ``voxels`` (the
+        spot's size) and ``root`` (its smallest voxel row); ``n_spots`` and ``n_spots_searched`` say how many spots there are
+        and how many were searched.  A spot that covers every voxel falls back to the least confident voxel as above.  This
+        mode costs a SECOND small host round trip: the choice of spots needs the record list on the host.  ``"pairs"``, the
+        default, is the behaviour described first and keeps its one round trip."""
         self._need_scene()
+        if regions not in ("pairs", "connected"):
+            raise ValueError('regions must be "pairs" or "connected"')
         if self._guide_logits is None:
             raise ValueError("guide() describes the last infer(): there is none, or the clicks or the scene changed since "
                              "(call infer() first)")
@@ -1226,8 +1283,11 @@ class InteractiveSession:
             logits, rows, objs, threshold, inverse_map=self.inverse_map, colors=self.colors_full, palette=self._palette_dev,
             doubt_color=doubt_color, full_margin=full_margin, summary=self._guide_sum)
         work, out, out_host = K._cluster_buffers(dev, labels.numel())
+        search_pred, search_want, spots = labels, want, None
+        if regions == "connected":
+            search_pred, search_want, spots, n_spots = self._contested_spots(labels, want)
         try:
-            K._launch_clusters(labels, want, self.raw_coords_qv, work, out)
+            K._launch_clusters(search_pred, search_want, self.raw_coords_qv, work, out)
             self._guide_sum_host.copy_(self._guide_sum, non_blocking=True)
             out_host.copy_(out, non_blocking=True)
         finally:
@@ -1246,14 +1306,156 @@ class InteractiveSession:
             raise RuntimeError(f"a3d_click_clusters: {count} contested regions > {K.MAX_CLUSTERS}")
         recs = np.frombuffer(host[:count * ctypes.sizeof(L.ClickCluster)].tobytes(), dtype=K._REC)
         clusters = [dict(zip(recs.dtype.names, t)) for t in recs.tolist()]
+        if spots is not None:                        # a cluster's `label` is its spot's pseudo id: back to the spot's two objects
+            by_row = {}
+            for c in clusters:
+                spot = spots[c["label"] - 1]
+                c["label"], c["pred"] = int(spot["key"]) >> 8, int(spot["key"]) & 255
+                by_row[c["row"]] = spot
         suggestions = suggest_clicks(clusters, summary["least"], self._coords_qv_host, max_suggestions)
+        if spots is not None:
+            for s in suggestions:                    # (the fallback's row is the least confident voxel of the one spot there is)
+                spot = by_row.get(s["row"], spots[0])
+                s["voxels"], s["root"] = int(spot["voxels"]), int(spot["root"])
         res = GuideResult(labels_qv=labels, runner_qv=runner, margin_qv=margin, margin_full=margin_full, colors=colors,
                           object_voxels=summary["voxels"][:n_ids].copy(),
                           object_contested=summary["contested"][:n_ids].copy(), least_confident=summary["least"],
                           n_contested=int(summary["contested"].sum()), suggestions=suggestions,
                           threshold=float(threshold), full_margin=float(full_margin))
+        if spots is not None:
+            res.n_spots, res.n_spots_searched = n_spots, len(spots)
         self._guide_last = res
         return res
+
+    # ------------------------------------------------------------------ where in space a label lies
+    def _scene_handle(self):
+        return self._backbone[0]._a3d.scene
+
+    def _click_rows(self):
+        return [int(r) for rows in self.click_idx.values() for r in rows]
+
+    def _label_pieces(self, keys, connectivity, click_rows=(), lift=False, max_out=1024, workspace=None):
+        """``a3d_label_pieces`` on the session's voxels and the copy of its record list: ``(piece_qv, piece_full, records,
+        n_pieces)``.  One library call and ONE host round trip; when there are more pieces than ``max_out`` records, once
+        more with the reported count (as ``render`` grows its pair buffer)."""
+        dev, scene = self.device, self._scene_handle()
+        for _ in range(2):
+            buf = torch.empty(max_out * V.PIECE.itemsize + 8, dtype=torch.uint8, device=dev)
+            records, count = buf[:max_out * V.PIECE.itemsize], buf[max_out * V.PIECE.itemsize:].view(torch.int32)
+            piece_qv, piece_full, _, _, workspace = V.label_pieces(
+                scene, keys, connectivity, click_rows, inverse_map=self.inverse_map if lift else None, records=records,
+                count=count, workspace=workspace)
+            host = buf.cpu().numpy()                                  # the one host round trip
+            recs, n_pieces, err = V.read_pieces(host[:-8], host[-8:])
+            if err & V.PIECES_BAD_INDEX:
+                raise RuntimeError("a3d_label_pieces: inverse_map out of range")
+            if n_pieces <= max_out:
+                return piece_qv, piece_full, recs, n_pieces
+            max_out = n_pieces
+        raise RuntimeError("a3d_label_pieces: the record list did not fit twice")
+
+    def _contested_spots(self, labels, want):
+        """What ``guide(regions="connected")`` hands to the cluster search: ``(pred = 0 everywhere, the pseudo id of every
+        voxel's spot (0: none), the records of the searched spots in pseudo-id order, the number of spots)``."""
+        key = torch.where(want != labels, want * 256 + labels, torch.full_like(labels, -1))
+        piece_qv, _, recs, n_spots = self._label_pieces(key, 26)
+        spots = [recs[k] for k in rank_spots(recs)]
+        table = torch.zeros(labels.numel() + 1, dtype=torch.int32, device=self.device)      # root row -> pseudo id; slot n: no piece
+        if spots:
+            roots = torch.tensor([int(r["root"]) for r in spots], dtype=torch.int64).to(self.device)
+            table[roots] = torch.arange(1, len(spots) + 1, dtype=torch.int32, device=self.device)
+        pseudo = table[torch.where(piece_qv >= 0, piece_qv, torch.full_like(piece_qv, labels.numel())).long()].contiguous()
+        return torch.zeros_like(labels), pseudo, spots, n_spots
+
+    def pieces(self, connectivity=26, labels=None):
+        """The connected PIECES of the session's current voxel labelling -- what ``preview()`` paints, so valid from
+        ``load_scene`` on -- or of ``labels`` (int32 [n_voxels] on the device, object ids 0..255): voxels that are neighbours
+        under ``connectivity`` (6: faces, 18: faces and edges, 26: faces, edges and corners) and carry the same object id
+        belong to one piece, named by its smallest voxel row (``a3d_label_pieces``; the adjacency is the scene's own
+        neighbour table).  Returns a ``PiecesResult``: which piece every voxel and vertex lies in, one record per piece
+        (object id, voxels, whether it holds a clicked voxel, bounding box in voxel coordinates) and the pieces per object.
+        One library call and ONE host round trip (a second of each when there are more than 1024 pieces)."""
+        self._need_scene()
+        keys = self._labels_qv if labels is None else labels
+        piece_qv, piece_full, recs, n_pieces = self._label_pieces(keys, connectivity, self._click_rows(), lift=True)
+        n_ids = max(len(self.click_idx), int(recs["key"].max()) + 1 if len(recs) else 1)
+        return PiecesResult(piece_qv=piece_qv, piece_full=piece_full, records=recs, n_pieces=n_pieces,
+                            object_pieces=np.bincount(recs["key"], minlength=n_ids).astype(np.int64), connectivity=connectivity)
+
+    def piece_at(self, result, u, v, pieces=None):
+        """The record (a ``view.PIECE`` row: root, key, voxels, clicked, lo, hi) of the piece that pixel ``(u, v)`` (column,
+        row) of ``result`` shows, or ``None`` where the pixel shows nothing -- resolved as ``confidence_at`` resolves a vertex:
+        the pixel's vertex on a cloud, the heaviest corner of its face on a mesh.  ``pieces``: a ``PiecesResult`` of this scene
+        (default: ``pieces()`` of the current labelling, computed here)."""
+        self._need_scene()
+        pieces = self.pieces() if pieces is None else pieces
+        if tuple(pieces.piece_full.shape) != (self.coords_full.shape[0],):
+            raise ValueError("the pieces belong to another scene")
+        vertex = self._vertex_at(result, u, v)
+        if vertex < 0:
+            return None
+        root = int(pieces.piece_full[vertex].cpu())
+        k = int(np.searchsorted(pieces.records["root"], root))
+        return pieces.records[k] if root >= 0 and k < len(pieces.records) and pieces.records["root"][k] == root else None
+
+    def despeckle(self, min_voxels=8, connectivity=26, paint_cubes=False):
+        """The current voxel labelling with its SPECKS removed, without touching the session: every piece (``pieces``) of
+        fewer than ``min_voxels`` voxels that holds no clicked voxel takes the object most of its differently labelled
+        neighbour pairs vote for (ties: the lowest id; a piece with no neighbour of another label keeps its own) -- ONE
+        simultaneous step on the labels as they are (``a3d_absorb_pieces``).  Returns a ``DespeckleResult``: ``labels_qv``,
+        ``labels_full`` and ``colors`` (through ``a3d_session_paint``), ``miou`` / ``iou_per_object`` against the relabelled
+        ground truth when the scene has one, and the counts of small, relabelled and kept-isolated pieces.  It changes NO
+        session state -- not the clicks, not the labels ``preview()`` paints, not the logits ``guide()`` reads:
+        ``annotate(result, labels=r.labels_full)`` and ``render(colors=r.colors)`` show it.  The default ``min_voxels`` = 8 is
+        this project's choice and is NOT tuned on real scans.  One host round trip (a second when there are more than 4096
+        small pieces)."""
+        self._need_scene()
+        dev, scene, n = self.device, self._scene_handle(), self._labels_qv.numel()
+        labels, rows = self._labels_qv, self._click_rows()
+        have_gt = self.new_labels is not None
+        capacity = 4096
+        for _ in range(2):
+            ws = V.pieces_workspace(n, dev, capacity, _N_IDS)
+            piece_qv = V.label_pieces(scene, labels, connectivity, rows, records=torch.empty(0, dtype=torch.uint8, device=dev),
+                                      workspace=ws)[0]
+            labels_qv, summary = V.absorb_pieces(scene, labels, piece_qv, ws, min_voxels, connectivity, rows, _N_IDS, capacity)
+            labels_full, colors = self._launch_paint(labels_qv, paint_cubes)
+            if have_gt:
+                K._launch_iou_counts([labels_qv], [self.new_labels], [self.inverse_map], _N_IDS,
+                                     self._counts[:3 * _N_IDS + 1].view(1, -1))
+            else:
+                self._counts[:3 * _N_IDS + 1].zero_()
+            packed = torch.cat([self._counts.view(torch.uint8), summary]).cpu().numpy()      # the one host round trip
+            host, s = packed[:-V.ABSORB_SUMMARY.itemsize].view(np.int64), V.read_absorb_summary(packed[-V.ABSORB_SUMMARY.itemsize:])
+            if not s["err"] & V.ABSORB_OVERFLOW:
+                break
+            capacity = s["small_pieces"]
+        if s["err"] & V.ABSORB_BAD_LABEL or host[3 * _N_IDS] or (int(host[3 * _N_IDS + 1]) & 0xffffffff):
+            raise RuntimeError("despeckle: inverse_map or labels out of range")
+        miou, per_obj = None, None
+        if have_gt:
+            t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())
+            miou = t.tolist()
+        return DespeckleResult(labels_full=labels_full, colors=colors, miou=miou, iou_per_object=per_obj, labels_qv=labels_qv,
+                               small_pieces=s["small_pieces"], relabelled_pieces=s["relabelled_pieces"],
+                               relabelled_voxels=s["relabelled_voxels"], kept_isolated=s["kept_isolated"],
+                               min_voxels=int(min_voxels), connectivity=connectivity)
+
+    def _vertex_at(self, result, u, v):
+        """The vertex that pixel ``(u, v)`` of ``result`` shows (-1: none): on a cloud the pixel's vertex, on a mesh the
+        heaviest corner of its face (``a3d_render_labels`` over the vertices' own indices).  One small device-to-host copy."""
+        if result.mesh != (self.faces is not None):
+            raise ValueError("the render belongs to another scene")
+        n = self.coords_full.shape[0]
+        u, v = int(u), int(v)
+        h, w = result.ids.shape
+        if not (0 <= u < w and 0 <= v < h):
+            raise ValueError(f"pixel ({u}, {v}) outside the {w} x {h} image")
+        if self._vertex_ids is None:
+            self._vertex_ids = torch.arange(n, dtype=torch.int32, device=self.device)
+        one = lambda image: None if image is None else image[v:v + 1, u:u + 1]
+        return int(V.render_labels(one(result.ids), one(result.u), one(result.v), self.faces, self._vertex_ids,
+                                   out=self._small[20:21].view(1, 1)).cpu())
 
     def confidence_at(self, result, u, v, guide=None):
         """The margin (a float; ``inf`` on a clicked voxel's vertices) of the vertex that pixel ``(u, v)`` (column, row) of
@@ -1267,16 +1469,7 @@ class InteractiveSession:
             raise ValueError("confidence_at() reads the last guide(): there is none, or the clicks or the scene changed since")
         if result.mesh != (self.faces is not None):
             raise ValueError("the render belongs to another scene")
-        n = self.coords_full.shape[0]
-        if tuple(guide.margin_full.shape) != (n,):
+        if tuple(guide.margin_full.shape) != (self.coords_full.shape[0],):
             raise ValueError("the guide belongs to another scene")
-        u, v = int(u), int(v)
-        h, w = result.ids.shape
-        if not (0 <= u < w and 0 <= v < h):
-            raise ValueError(f"pixel ({u}, {v}) outside the {w} x {h} image")
-        if self._vertex_ids is None:
-            self._vertex_ids = torch.arange(n, dtype=torch.int32, device=self.device)
-        one = lambda image: None if image is None else image[v:v + 1, u:u + 1]
-        vertex = int(V.render_labels(one(result.ids), one(result.u), one(result.v), self.faces, self._vertex_ids,
-                                     out=self._small[20:21].view(1, 1)).cpu())
+        vertex = self._vertex_at(result, u, v)
         return None if vertex < 0 else float(guide.margin_full[vertex].cpu())

@@ -456,3 +456,140 @@ def session_guide(logits, click_rows, click_objs, threshold, inverse_map=None, c
     a.summary_dev = summary.data_ptr()
     L.check(L.load().a3d_session_guide(C.byref(a), L.stream(dev)), "a3d_session_guide")
     return labels, runner, margin, want, margin_full, colors_out, summary
+
+
+# ---- the pieces of a labelling, despeckle --------------------------------------------------------------------------------------
+PIECE = np.dtype([("root", "<i4"), ("key", "<i4"), ("voxels", "<i4"), ("clicked", "<i4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,))])
+ABSORB_SUMMARY = np.dtype([("small_pieces", "<i4"), ("relabelled_pieces", "<i4"), ("relabelled_voxels", "<i4"),
+                           ("kept_isolated", "<i4"), ("err", "<i4"), ("reserved_", "<i4", (3,))])
+assert C.sizeof(L.Piece) == PIECE.itemsize == 40
+assert C.sizeof(L.AbsorbSummary) == ABSORB_SUMMARY.itemsize == 32
+PIECES_BAD_INDEX = 1                            # the bit of a3d_label_pieces' error word
+ABSORB_OVERFLOW, ABSORB_BAD_LABEL = 1, 2        # the bits of the absorb summary's error word
+CONNECTIVITIES = (6, 18, 26)
+
+
+def read_pieces(records_host, count_host):
+    """``(records, n_pieces, err)`` of the host copies of ``label_pieces``' record buffer (uint8, 40 bytes a record) and its
+    int32 [2] count: the ``PIECE`` records that were written (at most the buffer's, in ascending root), the TRUE number of
+    pieces, the error word (bit ``PIECES_BAD_INDEX``)."""
+    count = np.ascontiguousarray(count_host).view(np.int32).reshape(-1)
+    raw = np.ascontiguousarray(records_host).view(np.uint8).reshape(-1)
+    n = int(count[0])
+    kept = min(n, len(raw) // PIECE.itemsize)
+    return raw[:kept * PIECE.itemsize].view(PIECE).copy(), n, int(count[1])
+
+
+def read_absorb_summary(host):
+    """The host copy of an ``a3d_absorb_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints:
+    ``small_pieces`` (on ``ABSORB_OVERFLOW`` the capacity needed), ``relabelled_pieces``, ``relabelled_voxels``,
+    ``kept_isolated``, ``err`` (bits ``ABSORB_OVERFLOW``, ``ABSORB_BAD_LABEL``)."""
+    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:ABSORB_SUMMARY.itemsize].view(ABSORB_SUMMARY)[0]
+    return {k: int(rec[k]) for k in ("small_pieces", "relabelled_pieces", "relabelled_voxels", "kept_isolated", "err")}
+
+
+def pieces_workspace(n, device, capacity=None, n_classes=256):
+    """The scratch of ``label_pieces`` for n voxels (``a3d_pieces_workspace_bytes``); with ``capacity`` also room for
+    ``absorb_pieces`` with that many small pieces and ``n_classes`` labels (``a3d_absorb_workspace_bytes``)."""
+    lib = L.load()
+    nbytes = lib.a3d_pieces_workspace_bytes(n) if capacity is None else lib.a3d_absorb_workspace_bytes(n, capacity, n_classes)
+    if nbytes == 0:
+        raise ValueError(f"no pieces workspace for n={n} capacity={capacity} n_classes={n_classes}")
+    return torch.empty(nbytes, dtype=U8, device=device)
+
+
+def _scene_rows(scene):
+    if getattr(scene, "handle", None) is None or not getattr(scene, "n", None):
+        raise ValueError("scene must be an engine.Scene")
+    return getattr(scene.handle, "value", scene.handle), scene.n[0]
+
+
+def _connectivity(connectivity):
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"connectivity must be one of {CONNECTIVITIES}, not {connectivity!r}")
+    return int(connectivity)
+
+
+def _click_rows(dst, click_rows):
+    rows = np.asarray(click_rows, dtype=np.int64).reshape(-1)
+    if len(rows) > L.A3D_MAX_CLICKS:
+        raise ValueError(f"click_rows: at most {L.A3D_MAX_CLICKS}")
+    for k, r in enumerate(rows.tolist()):
+        dst[k] = r if -1 <= r < 1 << 31 else -1               # (a row no int32 holds is a row outside)
+    return len(rows)
+
+
+def label_pieces(scene, keys, connectivity=26, click_rows=(), inverse_map=None, piece_qv=None, piece_full=None, records=None,
+                 count=None, workspace=None):
+    """``a3d_label_pieces``: the connected pieces of ``keys`` int32 [n] (the rows of ``scene``, an ``engine.Scene``, in the
+    caller's order; a negative key belongs to no piece) under ``connectivity`` 6, 18 or 26.  ``click_rows``: a host sequence
+    of at most ``A3D_MAX_CLICKS`` rows.  ``inverse_map`` int64 [m]: also lift the pieces to m vertices.  ``records``: a uint8
+    buffer of 40 bytes per record the call may write (default: room for 1024); ``count`` int32 [2]; ``workspace``:
+    ``pieces_workspace``.  Returns ``(piece_qv int32 [n], piece_full int32 [m] or None, records, count, workspace)`` on the
+    device; ``read_pieces`` decodes the host copies of the last two."""
+    dev = _device("keys", keys)
+    handle, n = _scene_rows(scene)
+    a = L.LabelPiecesArgs()
+    a.scene, a.n = handle, n
+    a.keys_dev = _ptr("keys", keys, I32, (n,), dev)
+    a.connectivity = _connectivity(connectivity)
+    a.n_clicks = _click_rows(a.click_row, click_rows)
+    piece_qv = _out("piece_qv", piece_qv, I32, (n,), dev)
+    a.piece_qv_dev = piece_qv.data_ptr()
+    if inverse_map is not None:
+        a.inverse_map_dev = _ptr("inverse_map", inverse_map, I64, (None,), dev)
+        a.n_full = inverse_map.shape[0]
+        piece_full = _out("piece_full", piece_full, I32, (a.n_full,), dev)
+        a.piece_full_dev = piece_full.data_ptr() if a.n_full else None
+    elif piece_full is not None:
+        raise ValueError("piece_full belongs to the lift: inverse_map is missing")
+    if records is None:
+        records = torch.empty(1024 * PIECE.itemsize, dtype=U8, device=dev)
+    _ptr("records", records, U8, (None,), dev)
+    if records.data_ptr() % 4:
+        raise ValueError("records must be 4-byte aligned")
+    a.max_out = min(records.shape[0] // PIECE.itemsize, (1 << 31) - 1)
+    a.out_dev = records.data_ptr() if a.max_out else None
+    count = _out("count", count, I32, (2,), dev)
+    a.n_out_dev = count.data_ptr()
+    if workspace is None:
+        workspace = pieces_workspace(n, dev)
+    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
+    L.check(L.load().a3d_label_pieces(C.byref(a), L.stream(dev)), "a3d_label_pieces")
+    return piece_qv, piece_full, records, count, workspace
+
+
+def absorb_pieces(scene, labels, piece_qv, workspace, min_voxels, connectivity=26, click_rows=(), n_classes=256, capacity=1024,
+                  labels_out=None, summary=None):
+    """``a3d_absorb_pieces``: one despeckle step on ``labels`` int32 [n] in 0..n_classes-1.  ``piece_qv`` and ``workspace``:
+    what ``label_pieces`` returned for ``keys = labels`` under the same ``connectivity`` (the workspace holds the pieces'
+    sizes; it must be a ``pieces_workspace(n, device, capacity, n_classes)``).  A piece of fewer than ``min_voxels`` voxels
+    without a clicked row takes the label most of its differently labelled neighbour pairs vote for.  Returns ``(labels_out
+    int32 [n], summary uint8 [32])`` on the device; ``read_absorb_summary`` decodes the summary's host copy -- on
+    ``ABSORB_OVERFLOW`` nothing was written to ``labels_out`` and ``small_pieces`` is the capacity to call again with."""
+    dev = _device("labels", labels)
+    handle, n = _scene_rows(scene)
+    a = L.AbsorbPiecesArgs()
+    a.scene, a.n = handle, n
+    a.labels_dev = _ptr("labels", labels, I32, (n,), dev)
+    a.piece_qv_dev = _ptr("piece_qv", piece_qv, I32, (n,), dev)
+    a.connectivity = _connectivity(connectivity)
+    a.n_clicks = _click_rows(a.click_row, click_rows)
+    for name, value, lo, hi in (("min_voxels", min_voxels, 0, (1 << 31) - 1), ("n_classes", n_classes, 1, 256),
+                                ("capacity", capacity, 0, (1 << 31) - 1)):
+        if int(value) != value or not lo <= value <= hi:
+            raise ValueError(f"{name} must be an integer in {lo} .. {hi}")
+    a.min_voxels, a.n_classes, a.capacity = int(min_voxels), int(n_classes), int(capacity)
+    labels_out = _out("labels_out", labels_out, I32, (n,), dev)
+    if n and labels_out.data_ptr() == labels.data_ptr():
+        raise ValueError("labels_out may not alias labels")
+    a.labels_out_dev = labels_out.data_ptr()
+    summary = _out("summary", summary, U8, (ABSORB_SUMMARY.itemsize,), dev)
+    if summary.data_ptr() % 4:
+        raise ValueError("summary must be 4-byte aligned")
+    a.summary_dev = summary.data_ptr()
+    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
+    if a.workspace_bytes < L.load().a3d_absorb_workspace_bytes(n, a.capacity, a.n_classes):
+        raise ValueError("workspace too small for this capacity and n_classes (pieces_workspace(n, device, capacity, n_classes))")
+    L.check(L.load().a3d_absorb_pieces(C.byref(a), L.stream(dev)), "a3d_absorb_pieces")
+    return labels_out, summary

@@ -925,6 +925,108 @@ typedef struct a3d_session_guide_args {
 } a3d_session_guide_args;
 int    a3d_session_guide(const a3d_session_guide_args* args, void* stream);
 
+/* WHERE IN SPACE a label lies: the connected pieces of a keyed voxel set, and the despeckle step (csrc/session_pieces.hip).
+ * The rules are this library's: the reference keeps an arg-max per voxel and has no notion of a piece.  The adjacency is the
+ * scene's own level-0 table A3D_TAB_NBR27, both ends translated through A3D_TAB_ORIGROW: nothing is hashed or built again.
+ *
+ * a3d_label_pieces.  scene: level 0 = the voxels, n = its size (a3d_scene_level_size(scene, 0)); keys_dev int32 [n] in the
+ * CALLER's row order; connectivity 6, 18 or 26; up to A3D_MAX_CLICKS clicked rows by value (a row outside 0..n-1 is
+ * ignored); optionally inverse_map_dev int64 [n_full] (NULL = identity) with n_full > 0.
+ *   A row with key < 0 belongs to no piece.
+ *   Two rows are JOINED when both hold:
+ *     - they are neighbours under the connectivity, where 6 means |d|1 = 1, 18 means |d|1 <= 2, and 26 means all of the 3^3
+ *       table (d = the difference of their voxel coordinates; the scene's table already keeps batch samples apart);
+ *     - they have the same key.
+ *   A PIECE is a class of the transitive closure.
+ *   piece_qv[i] is the SMALLEST CALLER ROW of i's piece, or -1 for a row that belongs to none.
+ *   piece_full[v] = piece_qv[inverse_map[v]].  An index outside 0..n-1 sets bit 0 of the error word n_out_dev[1] and leaves
+ *   the vertex unwritten, as a3d_session_guide does.
+ *   RECORDS: one a3d_piece per piece, in ASCENDING root row: the root row, the key, the number of voxels, clicked = 1 when
+ *   the piece holds a clicked row (else 0), and the inclusive bounding box lo[3], hi[3] in voxel coordinates (A3D_TAB_XYZB).
+ *   n_out_dev is int32 [2], cleared by the call: n_out_dev[0] = the TRUE number of pieces (it may exceed max_out: only the
+ *   first max_out records, in root order, are written -- as a3d_click_clusters reports), n_out_dev[1] = the error word.
+ *   Everything is integer; the result does not depend on the order in which workgroups run: two calls give the same bytes.
+ *   How: union-find over parent[] indexed by caller row -- init, hook (one thread per voxel, the 13 offsets of one
+ *   half-space, the larger root linked under the smaller with atomicCAS), flatten.  Parents only decrease and no thread waits
+ *   for another: every loop ends on its own (no spin-wait, no grid barrier), at any graph diameter.
+ *   The workspace (a3d_pieces_workspace_bytes(n), 256-byte aligned) holds, behind the call, the sizes of the pieces at their
+ *   roots' slots: a3d_absorb_pieces reads them there.  The library allocates nothing and does not synchronise.
+ *   A3D_ERR_INVALID with nothing launched: no scene, n != the scene's level-0 size, a connectivity other than 6 / 18 / 26,
+ *   n_clicks outside 0..A3D_MAX_CLICKS, max_out < 0, n_full < 0, no n_out_dev, a needed pointer NULL (out_dev when max_out >
+ *   0, piece_full_dev when n_full > 0), a workspace that is too small or misaligned.
+ *
+ * a3d_absorb_pieces -- despeckle.  labels_dev int32 [n] in 0..n_classes-1 (n_classes <= 256); piece_qv_dev = what
+ * a3d_label_pieces wrote for keys = these labels under the SAME connectivity, and workspace_dev = the workspace of that call
+ * (it holds the sizes), now of at least a3d_absorb_workspace_bytes(n, capacity, n_classes) bytes; min_voxels; the clicked
+ * rows; capacity = the number of small pieces the call has room for (the caller's choice).
+ * The rule is ONE simultaneous step on the INPUT labels:
+ *   A piece is SMALL when it has fewer than min_voxels voxels and holds no clicked row.
+ *   Consider every voxel i of a small piece and every present neighbour j under the connectivity with label[j] != label[i].
+ *   Each such pair gives one vote to label[j].
+ *   The piece takes the label with the most votes.  Ties go to the lowest label.
+ *   A piece with no vote keeps its label.  Such a piece is isolated in space.
+ *   Nothing else changes.
+ * labels_out_dev int32 [n] may not alias labels_dev.  The summary (cleared by the call): small pieces, relabelled pieces,
+ * relabelled voxels, kept-isolated pieces, and the error word: A3D_ABSORB_OVERFLOW = there are more small pieces than
+ * `capacity`: NOTHING is written to labels_out and small_pieces is the capacity needed (call again with that much, as with
+ * a3d_render_header::pairs_needed); A3D_ABSORB_BAD_LABEL = a neighbour's label outside 0..n_classes-1 (its vote is dropped).
+ * Votes are integer atomics: the result is order-free.  A3D_ERR_INVALID as above, and for n_classes outside 1..256,
+ * capacity < 0, min_voxels < 0, no summary_dev, labels_out_dev == labels_dev. */
+typedef struct a3d_piece {
+  int32_t root, key, voxels, clicked;
+  int32_t lo[3], hi[3];
+} a3d_piece;                       /* 40 bytes */
+typedef struct a3d_label_pieces_args {
+  const a3d_scene* scene;
+  int64_t        n;
+  const int32_t* keys_dev;          /* [n] caller's row order */
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL */
+  int64_t        n_full;
+  int32_t*       piece_qv_dev;      /* out [n] */
+  int32_t*       piece_full_dev;    /* out [n_full] */
+  a3d_piece*     out_dev;           /* out: max_out records */
+  int32_t*       n_out_dev;         /* out int32 [2]: the true count, the error word */
+  void*          workspace_dev;
+  size_t         workspace_bytes;
+  int32_t        connectivity;
+  int32_t        max_out;
+  int32_t        n_clicks;
+  int32_t        reserved_;
+  int32_t        click_row[A3D_MAX_CLICKS];
+} a3d_label_pieces_args;
+size_t a3d_pieces_workspace_bytes(int64_t n);
+int    a3d_label_pieces(const a3d_label_pieces_args* args, void* stream);
+
+#define A3D_ABSORB_OVERFLOW  1
+#define A3D_ABSORB_BAD_LABEL 2
+typedef struct a3d_absorb_summary {
+  int32_t small_pieces;             /* also the capacity needed when A3D_ABSORB_OVERFLOW is set */
+  int32_t relabelled_pieces;
+  int32_t relabelled_voxels;
+  int32_t kept_isolated;
+  int32_t err;
+  int32_t reserved_[3];
+} a3d_absorb_summary;              /* 32 bytes */
+typedef struct a3d_absorb_pieces_args {
+  const a3d_scene* scene;
+  int64_t        n;
+  const int32_t* labels_dev;        /* [n] */
+  const int32_t* piece_qv_dev;      /* [n] a3d_label_pieces' of these labels */
+  int32_t*       labels_out_dev;    /* out [n] */
+  a3d_absorb_summary* summary_dev;
+  void*          workspace_dev;     /* the workspace a3d_label_pieces used */
+  size_t         workspace_bytes;
+  int32_t        min_voxels;
+  int32_t        connectivity;
+  int32_t        n_classes;
+  int32_t        capacity;
+  int32_t        n_clicks;
+  int32_t        reserved_;
+  int32_t        click_row[A3D_MAX_CLICKS];
+} a3d_absorb_pieces_args;
+size_t a3d_absorb_workspace_bytes(int64_t n, int capacity, int n_classes);
+int    a3d_absorb_pieces(const a3d_absorb_pieces_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
  * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a

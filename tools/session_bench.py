@@ -50,6 +50,13 @@ Then, with one click on each of C - 1 objects and the model's own logits, whole 
 clock, synchronised.  The figures to read: the voxel pass against the arg-max (it reads the same logits and writes 16
 bytes per voxel where the arg-max writes 4), the full-resolution pass against the paint (16 bytes per vertex against 16).
 
+The PIECES stage (``--pieces-only``, a run of its own) times ``a3d_label_pieces`` and ``a3d_absorb_pieces`` on the click scene,
+back to back like the annotate stage.  The model is FITTED first (``agile3d_amd.fit``: ``--fit-iters`` iterations on four
+5 000-voxel synthetic scenes), three objects and the background are clicked, and the labellings are the arg-max ``infer()``
+keeps and that labelling with 5 % of the rows relabelled at random (specks).  The expectation is a memory-bound pass, about
+27 x 4 B of table plus the gathered keys per voxel, twice: the figure ``table_gb_s`` is 2 x 27 x 4 B x voxels over the time of
+both calls.  Beside it the host time of ``pieces()``, ``despeckle()`` and the two modes of ``guide()``.
+
 The SECTION stage (``--section-only``, a run of its own) times ONE view, the render stage's height field as a mesh at 640 x
 480 from the outside camera, three ways that alternate call by call in one process: ``a3d_render_mesh``;
 ``a3d_render_mesh_section`` under ``Section.below(0)`` with back-face culling; and, with ``--other-lib``, ``a3d_render_mesh``
@@ -501,6 +508,102 @@ def guide_stage(ses, xyz, calls, reps):
     return out
 
 
+def pieces_stage(ses, xyz, lab, inst, calls, reps):
+    """``a3d_label_pieces`` and ``a3d_absorb_pieces`` on the fitted model's arg-max and on that with 5 % specks (see the module
+    docstring)."""
+    import ctypes as C
+    from agile3d_amd import lib as L
+    lib, dev = ses.lib, ses.device
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    rng = np.random.default_rng(11)
+    n_qv = ses.raw_coords_qv.shape[0]
+
+    def back_to_back(fn):
+        per_call = []
+        for window in range(6):                     # (the first window warms up)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            per_call.append(a.elapsed_time(b) / calls)
+        return float(np.median(per_call[1:]))
+
+    ses.reset()
+    for k, i in enumerate(inst[:3]):
+        ses.click(xyz[np.flatnonzero(lab == i)[0]], k + 1)
+    ses.click(xyz[np.flatnonzero(lab == 0)[0]], 0)
+    res = ses.infer()
+    argmax = ses._labels_qv.cpu().numpy()
+    specks = argmax.copy()
+    rows = rng.choice(n_qv, n_qv // 20, replace=False)
+    specks[rows] = rng.choice(np.unique(argmax), len(rows))
+    scene, clicks = ses._scene_handle(), ses._click_rows()
+    capacity = 4096                                 # (what despeckle() starts with)
+    ws = V.pieces_workspace(n_qv, dev, capacity, 256)
+    records = torch.empty(4096 * V.PIECE.itemsize, dtype=torch.uint8, device=dev)
+    count = torch.empty(2, dtype=torch.int32, device=dev)
+    piece, out = torch.empty(n_qv, dtype=torch.int32, device=dev), torch.empty(n_qv, dtype=torch.int32, device=dev)
+    summary = torch.empty(V.ABSORB_SUMMARY.itemsize, dtype=torch.uint8, device=dev)
+    print(f"\n== pieces: {n_qv} voxels, mIoU of the fitted model's inference {res.miou:.3f}; device ms per call, {calls} calls "
+          f"back to back, median of 5 windows ==")
+    result = {"voxels": int(n_qv), "calls_back_to_back": calls, "miou": res.miou, "labellings": {}}
+    for name, host_labels in (("argmax", argmax), ("argmax_5pct_specks", specks)):
+        labels = torch.from_numpy(host_labels.astype(np.int32)).to(dev)
+        entry = {}
+        for c in (6, 26):
+            la, ab = L.LabelPiecesArgs(), L.AbsorbPiecesArgs()          # (the arguments built once: the calls are the library's alone)
+            la.scene = ab.scene = scene.handle.value
+            la.n = ab.n = n_qv
+            la.keys_dev = ab.labels_dev = labels.data_ptr()
+            la.piece_qv_dev = ab.piece_qv_dev = piece.data_ptr()
+            la.out_dev, la.max_out, la.n_out_dev = records.data_ptr(), 4096, count.data_ptr()
+            la.workspace_dev = ab.workspace_dev = ws.data_ptr()
+            la.workspace_bytes = ab.workspace_bytes = ws.numel()
+            la.connectivity = ab.connectivity = c
+            la.n_clicks = ab.n_clicks = len(clicks)
+            for k, r in enumerate(clicks):
+                la.click_row[k] = ab.click_row[k] = r
+            ab.labels_out_dev, ab.summary_dev = out.data_ptr(), summary.data_ptr()
+            ab.min_voxels, ab.n_classes, ab.capacity = 8, 256, capacity
+
+            def label():
+                rc = lib.a3d_label_pieces(C.byref(la), stream)
+                assert rc == 0, lib.a3d_last_error()
+
+            def absorb():
+                rc = lib.a3d_absorb_pieces(C.byref(ab), stream)
+                assert rc == 0, lib.a3d_last_error()
+            ms = {"label_pieces": back_to_back(label), "absorb_pieces": back_to_back(absorb)}
+            label(), absorb()
+            s = V.read_absorb_summary(summary.cpu().numpy())
+            assert s["err"] == 0, s
+            ms.update(pieces=int(count.cpu()[0]), **{k: s[k] for k in ("small_pieces", "relabelled_pieces", "relabelled_voxels", "kept_isolated")})
+            ms["table_gb_s"] = 2 * 27 * 4 * n_qv / (1e6 * (ms["label_pieces"] + ms["absorb_pieces"]))
+            entry[str(c)] = ms
+            print(f"{name:20s} connectivity {c:2d}   label {ms['label_pieces']:.4f}  absorb {ms['absorb_pieces']:.4f}   {ms['pieces']} pieces, "
+                  f"{ms['small_pieces']} small, {ms['relabelled_voxels']} voxels relabelled   2 x 27 x 4 B x voxels = {ms['table_gb_s']:.0f} GB/s")
+        result["labellings"][name] = entry
+    # whole calls on the inference's own labelling (host ms, synchronised)
+    host = {"pieces": [], "despeckle": [], "guide": [], "guide_connected": []}
+    for _ in range(reps):
+        for key, call in (("pieces", ses.pieces), ("despeckle", ses.despeckle), ("guide", ses.guide),
+                          ("guide_connected", lambda: ses.guide(regions="connected"))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = call()
+            torch.cuda.synchronize()
+            host[key].append(1e3 * (time.perf_counter() - t0))
+    result["host_ms"] = {k: float(np.median(v[reps // 4:])) for k, v in host.items()}
+    result["spots"] = {"n_spots": got.n_spots, "searched": got.n_spots_searched, "contested": got.n_contested}
+    print("whole calls (host ms, synchronised): " + "  ".join(f"{k}() {v:.3f}" for k, v in result["host_ms"].items()) +
+          f"   guide(regions='connected'): {got.n_spots} spots over {got.n_contested} contested voxels")
+    ses.reset()
+    return result
+
+
 def section_stage(ses, n_vertices, reps, other_lib):
     """One view, with and without a section, next to another build of the library (see the module docstring)."""
     import ctypes as C
@@ -650,6 +753,8 @@ def main():
     ap.add_argument("--annotate-only", action="store_true", help="run the annotate stage alone")
     ap.add_argument("--edit-only", action="store_true", help="run the edit stage (a3d_session_edit, undo / redo) alone")
     ap.add_argument("--guide-only", action="store_true", help="run the guide stage (a3d_session_guide, guide()) alone")
+    ap.add_argument("--pieces-only", action="store_true", help="run the pieces stage (a3d_label_pieces, a3d_absorb_pieces) alone")
+    ap.add_argument("--fit-iters", type=int, default=120, help="pieces stage: iterations the model is fitted for first")
     ap.add_argument("--section-only", action="store_true", help="run the section stage (one view with and without a section) alone")
     ap.add_argument("--other-lib", default=None, help="section stage: another build of libagile3d_hip.so to time beside this one")
     a = ap.parse_args()
@@ -657,6 +762,10 @@ def main():
         raise SystemExit("session_bench needs the GPU")
     torch.manual_seed(0)
     model = randomize_bn_stats(build_model(default_args(voxel_size=0.02))).eval().cuda()
+    if a.pieces_only:
+        from agile3d_amd.fit import fit, labelled_scenes
+        fit(model, labelled_scenes(4, voxels=5000, objects=3), torch.device("cuda"), iters=a.fit_iters, lr=1e-3, batch=2, seed=7)
+        model.eval()
     sc = make_scene(a.voxels, seed=0, voxel_size=0.02)
     rng = np.random.default_rng(0)
     raw = sc["raw_xyz"]
@@ -672,7 +781,7 @@ def main():
     original = col.copy()
     centre = xyz.mean(0)
     result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
-    alone = a.mesh_only or a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only
+    alone = a.mesh_only or a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only
     for n_clicks in (() if alone else (1, 5, 10, 20)):
         ses.reset()
         objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
@@ -781,13 +890,15 @@ def main():
         result["edit"] = edit_stage(ses, xyz, lab, inst, a.mesh_calls, a.reps)
     if a.guide_only:
         result["guide"] = guide_stage(ses, xyz, a.mesh_calls, a.reps)
+    if a.pieces_only:
+        result["pieces"] = pieces_stage(ses, xyz, lab, inst, a.mesh_calls, a.reps)
     if a.section_only:
         result["section"] = section_stage(ses, n_full, a.reps, a.other_lib)
-    if not (a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only):
+    if not (a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only):
         result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
-    if not (a.mesh_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only):
+    if not (a.mesh_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only):
         result["render"] = render_stage(ses, n_full, a.reps, a.warmup)
-    if not (a.mesh_only or a.render_only or a.edit_only or a.section_only or a.guide_only):
+    if not (a.mesh_only or a.render_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only):
         result["annotate"] = annotate_stage(ses, n_full, a.mesh_calls)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
