@@ -203,6 +203,29 @@ class AbsorbPiecesArgs(C.Structure):
                 ("click_row", C.c_int32 * 256)]
 
 
+class ObjectMoments(C.Structure):
+    """a3d_object_moments: one object of a labelling -- vertices and voxels, the sums of the fixed-point coordinates (X, Y, Z)
+    and of their products (XX, XY, XZ, YY, YZ, ZZ), the covered surface in thirds of area quanta, the exact fp32 box."""
+    _fields_ = [("vertices", C.c_int64), ("voxels", C.c_int64), ("sum", C.c_int64 * 3), ("mom", C.c_int64 * 6),
+                ("area_thirds", C.c_int64), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("reserved_", C.c_int32 * 2)]
+
+
+class MeasureArgs(C.Structure):
+    """a3d_measure_args: the vertices and their labels, optionally the voxels' labels and the faces, the records and the
+    error word, and by value the fixed-point frame (origin, quantum, bits), the area quantum and the number of object ids."""
+    _fields_ = [("xyz_dev", C.c_void_p), ("labels_dev", C.c_void_p), ("n", C.c_int64), ("labels_qv_dev", C.c_void_p),
+                ("n_qv", C.c_int64), ("faces_dev", C.c_void_p), ("m", C.c_int64), ("out_dev", C.c_void_p),
+                ("err_dev", C.c_void_p), ("origin", C.c_double * 3), ("quantum", C.c_double), ("area_quantum", C.c_double),
+                ("n_classes", C.c_int32), ("bits", C.c_int32)]
+
+
+class ExtentsArgs(C.Structure):
+    """a3d_extents_args: the vertices and their labels, three axes per object, the (min, max) per (object, axis) and the
+    error word."""
+    _fields_ = [("xyz_dev", C.c_void_p), ("labels_dev", C.c_void_p), ("n", C.c_int64), ("axes_dev", C.c_void_p),
+                ("out_dev", C.c_void_p), ("err_dev", C.c_void_p), ("n_classes", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class Camera(C.Structure):
     """a3d_camera: pixel (u, v)'s ray starts at o and runs along normalize(d00 + u du + v dv), evaluated in fp32."""
     _fields_ = [("o", C.c_float * 3), ("d00", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
@@ -239,6 +262,9 @@ A3D_RENDER_TILE = 16
 A3D_RENDER_BAD_INDEX, A3D_RENDER_OVERFLOW = 1, 2
 A3D_SECTION_MAX_PLANES = 8
 A3D_CULL_NONE, A3D_CULL_BACK, A3D_CULL_FRONT = 0, 1, 2
+A3D_MEASURE_RANGE, A3D_MEASURE_BAD_LABEL = 1, 2
+A3D_MEASURE_MAX_BITS, A3D_MEASURE_MAX_Q, A3D_MEASURE_MAX_FACES = 20, 1 << 38, 1 << 23
+A3D_MEASURE_BLOCK, A3D_MEASURE_CHUNK = 256, 1024
 A3D_ERR_INVALID = -1
 PROF_DENSE = 11
 PROF_NAMES = ["spconv", "splitk_epilogue", "stem", "c2s_attn", "query_chain", "s2c_attn", "ln_mask", "posenc",
@@ -432,6 +458,8 @@ SYMBOLS = {
     "a3d_label_pieces": (C.c_int, [C.POINTER(LabelPiecesArgs), C.c_void_p]),
     "a3d_absorb_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "a3d_absorb_pieces": (C.c_int, [C.POINTER(AbsorbPiecesArgs), C.c_void_p]),
+    "a3d_measure_objects": (C.c_int, [C.POINTER(MeasureArgs), C.c_void_p]),
+    "a3d_object_extents": (C.c_int, [C.POINTER(ExtentsArgs), C.c_void_p]),
     "a3d_render_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "a3d_render_camera_bounds": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_double)]),
     "a3d_render_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(Camera), C.POINTER(RenderOut),

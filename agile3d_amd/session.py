@@ -28,6 +28,8 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
     next click                          logits after the arg-max, :78-81; a rule of ours)
     where in space a label lies         a3d_label_pieces / a3d_absorb_pieces  (pieces, piece_at, despeckle, guide(regions=
                                         "connected"): connected pieces of a labelling on the voxel lattice; a rule of ours)
+    how big an object is, its boxes     a3d_measure_objects / a3d_object_extents  (measure, MeasureResult.section, frame: size,
+                                        centroid, axis-aligned and oriented box, covered surface per object; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -294,6 +296,93 @@ class DespeckleResult:
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
+
+
+def object_table(moments, origin, quantum, area_quantum=None, voxel_size=None):
+    """What the records of ``a3d_measure_objects`` (``view.OBJECT_MOMENTS``, one per object id) say in world units -- float64
+    from the exact integers, pure numpy.  ``origin``, ``quantum``: the fixed-point frame the call was given; ``area_quantum``
+    (``None``: a cloud, no area) and ``voxel_size`` (``None``: no volume).  Returns a dict of arrays over the object ids:
+
+    * ``vertices``, ``voxels`` int64;
+    * ``centroid`` [K, 3] = origin + quantum * sum / vertices (NaN for an object without a vertex);
+    * ``cov`` [K, 3, 3] = quantum^2 * (mom / vertices - mean mean^T), the population covariance of the quantised
+      coordinates; the difference is taken in exact integers (vertices * mom - sum sum^T) and divided once, so nothing
+      cancels in floating point (NaN without a vertex);
+    * ``area`` [K] = area_thirds * area_quantum / 6: a face's area goes in thirds to the objects of its corners;
+    * ``volume`` [K] = voxels * voxel_size^3 -- the volume of the OCCUPIED VOXELS (a scan's surface, one voxel thick), not of
+      the solid the surface encloses."""
+    m = np.asarray(moments)
+    o, q = np.asarray(origin, dtype=np.float64).reshape(3), float(quantum)
+    k = len(m)
+    vertices, voxels = m["vertices"].astype(np.int64), m["voxels"].astype(np.int64)
+    centroid, cov = np.full((k, 3), np.nan), np.full((k, 3, 3), np.nan)
+    pairs = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+    for i in np.flatnonzero(vertices > 0):
+        n, s = int(vertices[i]), [int(v) for v in m["sum"][i]]
+        centroid[i] = o + q * (np.array(s, dtype=np.float64) / n)
+        for (a, b), mom in zip(pairs, m["mom"][i]):
+            cov[i, a, b] = cov[i, b, a] = q * q * ((n * int(mom) - s[a] * s[b]) / (n * n))      # Python integers: exact
+    table = {"vertices": vertices, "voxels": voxels, "centroid": centroid, "cov": cov, "area": None, "volume": None}
+    if area_quantum is not None:
+        table["area"] = m["area_thirds"].astype(np.float64) * (float(area_quantum) / 6.0)
+    if voxel_size is not None:
+        table["volume"] = voxels.astype(np.float64) * float(voxel_size) ** 3
+    return table
+
+
+def principal_axes(cov, vertices=None):
+    """The axes of an oriented box from a covariance ``cov`` [3, 3] (or [K, 3, 3], with ``vertices`` [K]): ``(axes, variances)``
+    with ``axes`` [.., 3, 3], row j = axis j, and ``variances`` [.., 3] descending.  THE CONVENTION: ``numpy.linalg.eigh``,
+    eigenvalues in descending order; axes 0 and 1 are each signed so that their component of largest magnitude is positive (a
+    tie goes to the lowest index); axis 2 = axis 0 x axis 1, so the frame is right-handed.  An object with fewer than 3
+    vertices, or a covariance that is zero or not finite, gets the identity axes (variances: the diagonal, 0 where not
+    finite).  float64, pure numpy."""
+    c = np.asarray(cov, dtype=np.float64)
+    single = c.ndim == 2
+    c = c.reshape(-1, 3, 3)
+    count = np.full(len(c), 3) if vertices is None else np.asarray(vertices).reshape(-1)
+    axes, variances = np.tile(np.eye(3), (len(c), 1, 1)), np.zeros((len(c), 3))
+    for i in range(len(c)):
+        if not np.isfinite(c[i]).all():
+            continue
+        variances[i] = np.diag(c[i])
+        if count[i] < 3 or not c[i].any():
+            continue
+        w, v = np.linalg.eigh(c[i])
+        a = v[:, ::-1].T.copy()                      # rows, largest eigenvalue first
+        for j in (0, 1):
+            if a[j, np.argmax(np.abs(a[j]))] < 0:
+                a[j] = -a[j]
+        a[2] = np.cross(a[0], a[1])
+        axes[i], variances[i] = a, w[::-1]
+    return (axes[0], variances[0]) if single else (axes, variances)
+
+
+class MeasureResult:
+    """What ``measure()`` returns: arrays over the object ids 0..K (host, float64 unless noted).  ``vertices``, ``voxels``
+    int64; ``centroid`` [K + 1, 3]; ``lo``, ``hi`` fp32 [K + 1, 3], the exact axis-aligned box (+inf / -inf for an object without
+    a vertex); ``cov`` [K + 1, 3, 3]; ``area`` (``None`` on a cloud) and ``volume`` (of the occupied voxels) [K + 1].  With
+    ``oriented=True`` the oriented box: ``axes`` [K + 1, 3, 3] (``principal_axes``, rounded to fp32: what the second pass
+    projected on), ``centre`` [K + 1, 3] and ``extents`` [K + 1, 3] (its full size along each axis); ``None`` otherwise.
+    ``origin``, ``quantum``, ``bits``, ``area_quantum``: the fixed-point frame used; ``moments``: the records as they came."""
+
+    __slots__ = ("vertices", "voxels", "centroid", "lo", "hi", "cov", "area", "volume", "axes", "centre", "extents", "origin",
+                 "quantum", "bits", "area_quantum", "moments")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def section(self, obj, margin=0.0, cull="none"):
+        """The ``Section`` that isolates object ``obj`` in ``render`` / ``pick``: ``Section.box(lo - margin, hi + margin)``
+        of its axis-aligned box.  With ``margin = 0`` the planes are the box's own fp32 values: every vertex of the object is
+        kept.  ``ValueError`` for an object without a vertex."""
+        obj = int(obj)
+        if not 0 <= obj < len(self.vertices) or self.vertices[obj] == 0:
+            raise ValueError(f"object {obj} has no vertex")
+        if not (np.isfinite(margin) and margin >= 0):
+            raise ValueError("margin must be finite and >= 0")
+        return Section.box(self.lo[obj].astype(np.float64) - float(margin), self.hi[obj].astype(np.float64) + float(margin), cull)
 
 
 class GuideResult:
@@ -603,6 +692,8 @@ class InteractiveSession:
         self._backbone = None
         self._mask_host = None
         self._render_ws = None                      # scratch of render(): kept per scene, grown when a view needs more pairs
+        self._unique_map = None                     # int64 [n_voxels]: the vertex each voxel was made from (measure(labels=))
+        self._measure_frame = None                  # (origin, quantum, bits) of measure(): once per scene, on first use
         self.section = None                         # the Section pick, click_ray and render apply by default (set_section)
         self._reset_clicks()
 
@@ -659,6 +750,7 @@ class InteractiveSession:
         self._coords_host = self.coords_full.cpu().numpy()
         self.colors_full = col32
         self.inverse_map = inverse_map.contiguous()
+        self._unique_map = unique_map
         self.raw_coords_qv = xyz[unique_map].to(torch.float32).contiguous()
         self._coords_qv_host = self.raw_coords_qv.cpu().numpy()
         if labels_full is not None:
@@ -1440,6 +1532,99 @@ class InteractiveSession:
                                small_pieces=s["small_pieces"], relabelled_pieces=s["relabelled_pieces"],
                                relabelled_voxels=s["relabelled_voxels"], kept_isolated=s["kept_isolated"],
                                min_voxels=int(min_voxels), connectivity=connectivity)
+
+    # ------------------------------------------------------------------ how big an object is
+    def _fixed_point_frame(self):
+        """``(origin float64 [3], quantum, bits)`` of the scene, once per scene: the origin is the centre of the box of the finite
+        vertices, ``quantum = 2^(e - bits)`` with ``2^e`` >= the largest half extent -- so every vertex lies within ``2^bits``
+        quanta of the origin -- and ``bits`` the largest value up to 20 with ``n * 2^(2 bits) <= 2^62``."""
+        if self._measure_frame is None:
+            p = self._coords_host[np.isfinite(self._coords_host).all(1)].astype(np.float64)
+            lo, hi = (p.min(0), p.max(0)) if len(p) else (np.zeros(3), np.zeros(3))
+            origin = 0.5 * (lo + hi)
+            half = float(np.maximum(hi - origin, origin - lo).max())
+            e = int(np.ceil(np.log2(half))) if half > 0 else 0
+            while 2.0 ** e < half:                    # (log2 rounds: make sure of the property itself)
+                e += 1
+            n = max(int(self._coords_host.shape[0]), 1)
+            bits = min(L.A3D_MEASURE_MAX_BITS, (62 - (n - 1).bit_length()) // 2)
+            self._measure_frame = (origin, 2.0 ** (e - bits), bits)
+        return self._measure_frame
+
+    def measure(self, labels=None, oriented=True):
+        """The OBJECTS of a labelling, measured: per object id its vertices and voxels, centroid, exact axis-aligned box,
+        covariance, the surface it covers (a mesh scene; ``None`` on a cloud), the volume of its occupied voxels and, with
+        ``oriented=True``, the box along its principal axes.  Valid from ``load_scene`` on; it changes NO session state.  By
+        default the current full-resolution labelling is measured -- the voxel labels ``preview()`` paints, lifted through the
+        inverse map -- else ``labels``: int32 [n_full] on the device with object ids 0..255 (the ground truth, or
+        ``despeckle().labels_full``); a voxel then carries the label of the vertex it was made from.
+
+        One ``a3d_measure_objects`` call accumulates exact integers on the device (counts, fixed-point first and second
+        moments about the centre of the scene's box, minima and maxima, face areas in quanta); ``object_table`` turns them into
+        world units on the host and ``principal_axes`` into axes (PCA of the vertices: the stated definition, not a
+        minimum-volume box); a second call, ``a3d_object_extents``, projects every vertex on its object's axes.  ONE host round
+        trip, TWO with ``oriented=True``.  An error bit (a label outside 0..255, a coordinate that is not finite) raises
+        ``RuntimeError``.  Returns a ``MeasureResult``."""
+        self._need_scene()
+        dev, n_full = self.device, self.coords_full.shape[0]
+        if labels is None:
+            labels_qv = self._labels_qv
+            labels = labels_qv[self.inverse_map]
+        else:
+            if not torch.is_tensor(labels) or labels.dtype is not torch.int32 or tuple(labels.shape) != (n_full,) or labels.device != dev:
+                raise ValueError(f"labels must be an int32 tensor [{n_full}] on {dev}")
+            labels = labels.contiguous()
+            labels_qv = labels[self._unique_map]
+        origin, quantum, bits = self._fixed_point_frame()
+        area_quantum = quantum * quantum * 256.0 if self.faces is not None else None
+        rec_bytes = _N_IDS * V.OBJECT_MOMENTS.itemsize
+        buf = torch.empty(rec_bytes + 8, dtype=torch.uint8, device=dev)
+        V.measure_objects(self.coords_full, labels, origin, quantum, bits, _N_IDS, labels_qv=labels_qv, faces=self.faces,
+                          area_quantum=area_quantum, records=buf[:rec_bytes], err=buf[rec_bytes:rec_bytes + 4].view(torch.int32))
+        host = buf.cpu().numpy()                                          # the one host round trip
+        err = int(host[rec_bytes:rec_bytes + 4].view(np.int32)[0])
+        if err:
+            raise RuntimeError(f"a3d_measure_objects: labels outside 0 .. {_N_IDS - 1} or coordinates out of range (error word {err})")
+        moments = V.read_object_moments(host[:rec_bytes])
+        used = np.flatnonzero((moments["vertices"] > 0) | (moments["voxels"] > 0))
+        k = max(len(self.click_idx), int(used.max()) + 1 if len(used) else 1)
+        moments = moments[:k]
+        t = object_table(moments, origin, quantum, area_quantum, self.voxel_size)
+        res = MeasureResult(vertices=t["vertices"], voxels=t["voxels"], centroid=t["centroid"], lo=moments["lo"].copy(),
+                            hi=moments["hi"].copy(), cov=t["cov"], area=t["area"], volume=t["volume"], origin=origin,
+                            quantum=quantum, bits=bits, area_quantum=area_quantum, moments=moments)
+        if oriented:
+            axes32 = np.tile(np.eye(3, dtype=np.float32), (_N_IDS, 1, 1))
+            axes32[:k] = principal_axes(t["cov"], t["vertices"])[0].astype(np.float32)
+            out = torch.empty(_N_IDS * 6 + 1, dtype=torch.float32, device=dev)
+            V.object_extents(self.coords_full, labels, torch.from_numpy(axes32).to(dev), extents=out[:_N_IDS * 6].view(_N_IDS, 3, 2),
+                             err=out[_N_IDS * 6:].view(torch.int32))
+            host = out.cpu().numpy()                                      # the second host round trip
+            if int(host[_N_IDS * 6:].view(np.int32)[0]):
+                raise RuntimeError("a3d_object_extents: labels or coordinates out of range")
+            span = host[:_N_IDS * 6].reshape(_N_IDS, 3, 2)[:k].astype(np.float64)
+            axes = axes32[:k].astype(np.float64)
+            empty = t["vertices"] == 0
+            with np.errstate(invalid="ignore"):
+                mid, size = 0.5 * (span[..., 0] + span[..., 1]), span[..., 1] - span[..., 0]
+            mid[empty], size[empty] = np.nan, 0.0
+            res.axes, res.extents = axes, size
+            res.centre = np.einsum("kj,kjc->kc", mid, axes)
+        return res
+
+    def frame(self, obj, width, height, fov_deg=35.0, measure=None):
+        """``(intrinsic, extrinsic)`` of a camera that frames object ``obj``: ``framing_view`` on the 8 corners of its
+        axis-aligned box, so every vertex of the object has camera-space z > 0 and projects inside the image.  ``measure``: a
+        ``MeasureResult`` of this scene (default: ``measure(oriented=False)`` of the current labelling, computed here).
+        ``ValueError`` for an object without a vertex."""
+        self._need_scene()
+        m = self.measure(oriented=False) if measure is None else measure
+        obj = int(obj)
+        if not 0 <= obj < len(m.vertices) or m.vertices[obj] == 0:
+            raise ValueError(f"object {obj} has no vertex")
+        lo, hi = m.lo[obj].astype(np.float64), m.hi[obj].astype(np.float64)
+        corners = np.array([[(lo, hi)[(c >> a) & 1][a] for a in range(3)] for c in range(8)])
+        return framing_view(corners, width, height, fov_deg)
 
     def _vertex_at(self, result, u, v):
         """The vertex that pixel ``(u, v)`` of ``result`` shows (-1: none): on a cloud the pixel's vertex, on a mesh the

@@ -593,3 +593,99 @@ def absorb_pieces(scene, labels, piece_qv, workspace, min_voxels, connectivity=2
         raise ValueError("workspace too small for this capacity and n_classes (pieces_workspace(n, device, capacity, n_classes))")
     L.check(L.load().a3d_absorb_pieces(C.byref(a), L.stream(dev)), "a3d_absorb_pieces")
     return labels_out, summary
+
+
+# ---- measuring the objects of a labelling ---------------------------------------------------------------------------------------
+OBJECT_MOMENTS = np.dtype([("vertices", "<i8"), ("voxels", "<i8"), ("sum", "<i8", (3,)), ("mom", "<i8", (6,)),
+                           ("area_thirds", "<i8"), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("reserved_", "<i4", (2,))])
+assert C.sizeof(L.ObjectMoments) == OBJECT_MOMENTS.itemsize == 128
+MEASURE_RANGE, MEASURE_BAD_LABEL = L.A3D_MEASURE_RANGE, L.A3D_MEASURE_BAD_LABEL      # the bits of the two calls' error word
+
+
+def read_object_moments(host):
+    """The ``OBJECT_MOMENTS`` records (one per object id) of the host copy of ``measure_objects``' record buffer (uint8, 128
+    bytes a record, or anything of those bytes): ``vertices``, ``voxels``, ``sum`` [3] and ``mom`` [6] (fixed-point, int64),
+    ``area_thirds``, ``lo`` / ``hi`` fp32 [3].  A copy."""
+    raw = np.ascontiguousarray(host).view(np.uint8).reshape(-1)
+    return raw[:len(raw) // OBJECT_MOMENTS.itemsize * OBJECT_MOMENTS.itemsize].view(OBJECT_MOMENTS).copy()
+
+
+def _power_of_two(name, value):
+    value = float(value)
+    if not (np.isfinite(value) and value > 0.0 and np.frexp(value)[0] == 0.5):
+        raise ValueError(f"{name} must be a positive power of two, not {value!r}")
+    return value
+
+
+def _n_classes(n_classes):
+    if int(n_classes) != n_classes or not 1 <= n_classes <= 256:
+        raise ValueError("n_classes must be an integer in 1 .. 256")
+    return int(n_classes)
+
+
+def measure_objects(xyz, labels, origin, quantum, bits=L.A3D_MEASURE_MAX_BITS, n_classes=256, labels_qv=None, faces=None,
+                    area_quantum=None, records=None, err=None):
+    """``a3d_measure_objects``: one record per object id 0..n_classes-1 of ``labels`` int32 [n] over the vertices ``xyz`` fp32
+    [n, 3] -- vertices, the exact fp32 box, and the sums of the fixed-point coordinates ``X = rint((x - origin) / quantum)`` and
+    of their products; a vertex with ``|X| > 2^bits`` or a label outside counts nowhere and sets a bit of the error word.
+    ``origin``: three finite numbers; ``quantum``: a positive power of two; ``bits`` in 0..20 with ``n * 2^(2 bits) <= 2^62``.
+    ``labels_qv`` int32 [n_qv]: also count the voxels per object.  ``faces`` int32 [m, 3] (m <= 2^23): also the surface each
+    object covers, in thirds of ``area_quantum`` (a positive power of two; default ``quantum^2 * 2^8``).  Returns ``(records
+    uint8 [128 n_classes], err int32 [1])`` on the device, the caller's or allocated; ``read_object_moments`` decodes the host
+    copy of the first, the second holds ``MEASURE_RANGE`` / ``MEASURE_BAD_LABEL``."""
+    dev = _device("xyz", xyz)
+    a = L.MeasureArgs()
+    a.xyz_dev = _ptr("xyz", xyz, F32, (None, 3), dev)
+    a.n = n = xyz.shape[0]
+    a.labels_dev = _ptr("labels", labels, I32, (n,), dev)
+    a.n_classes = _n_classes(n_classes)
+    if int(bits) != bits or not 0 <= bits <= L.A3D_MEASURE_MAX_BITS:
+        raise ValueError(f"bits must be an integer in 0 .. {L.A3D_MEASURE_MAX_BITS}")
+    a.bits = int(bits)
+    if n >= 1 << 31 or n << (2 * a.bits) > 1 << 62:
+        raise ValueError(f"{n} vertices at bits={a.bits}: the sums could overflow (n * 2^(2 bits) <= 2^62)")
+    o = np.asarray(origin, dtype=np.float64).reshape(-1)
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError("origin must be three finite numbers")
+    a.origin[:] = o.tolist()
+    a.quantum = _power_of_two("quantum", quantum)
+    if labels_qv is not None:
+        a.labels_qv_dev = _ptr("labels_qv", labels_qv, I32, (None,), dev)
+        a.n_qv = labels_qv.shape[0]
+    if faces is not None:
+        a.faces_dev = _ptr("faces", faces, I32, (None, 3), dev)
+        a.m = faces.shape[0]
+        if a.m > L.A3D_MEASURE_MAX_FACES:
+            raise ValueError(f"at most {L.A3D_MEASURE_MAX_FACES} faces")
+        a.area_quantum = _power_of_two("area_quantum", a.quantum * a.quantum * 256.0 if area_quantum is None else area_quantum)
+    elif area_quantum is not None:
+        raise ValueError("area_quantum belongs to the faces: faces is missing")
+    records = _out("records", records, U8, (a.n_classes * OBJECT_MOMENTS.itemsize,), dev)
+    if records.data_ptr() % 8:
+        raise ValueError("records must be 8-byte aligned")
+    err = _out("err", err, I32, (1,), dev)
+    a.out_dev, a.err_dev = records.data_ptr(), err.data_ptr()
+    L.check(L.load().a3d_measure_objects(C.byref(a), L.stream(dev)), "a3d_measure_objects")
+    return records, err
+
+
+def object_extents(xyz, labels, axes, extents=None, err=None):
+    """``a3d_object_extents``: for every object id k of ``labels`` int32 [n] (0..n_classes-1, ``n_classes`` = ``axes.shape[0]``)
+    and each of its three axes ``axes`` fp32 [n_classes, 3, 3] (row j of object k = axis j) the smallest and the largest
+    projection ``(a_x x + a_y y) + a_z z`` (fp32, one operation at a time) of the object's vertices ``xyz`` fp32 [n, 3].
+    Returns ``(extents fp32 [n_classes, 3, 2] = (min, max), err int32 [1])`` on the device, the caller's or allocated; an object
+    without a vertex has ``(+inf, -inf)``."""
+    dev = _device("xyz", xyz)
+    a = L.ExtentsArgs()
+    a.xyz_dev = _ptr("xyz", xyz, F32, (None, 3), dev)
+    a.n = n = xyz.shape[0]
+    a.labels_dev = _ptr("labels", labels, I32, (n,), dev)
+    a.axes_dev = _ptr("axes", axes, F32, (None, 3, 3), dev)
+    a.n_classes = _n_classes(axes.shape[0])
+    if n >= 1 << 31:
+        raise ValueError("at most 2^31 - 1 vertices")
+    extents = _out("extents", extents, F32, (a.n_classes, 3, 2), dev)
+    err = _out("err", err, I32, (1,), dev)
+    a.out_dev, a.err_dev = extents.data_ptr(), err.data_ptr()
+    L.check(L.load().a3d_object_extents(C.byref(a), L.stream(dev)), "a3d_object_extents")
+    return extents, err

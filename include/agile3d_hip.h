@@ -1027,6 +1027,106 @@ typedef struct a3d_absorb_pieces_args {
 size_t a3d_absorb_workspace_bytes(int64_t n, int capacity, int n_classes);
 int    a3d_absorb_pieces(const a3d_absorb_pieces_args* args, void* stream);
 
+/* HOW BIG an object is and where it lies: one record per object id of a labelling (csrc/session_measure.hip).  The rules are
+ * this library's: the reference exports a mask and measures nothing.  Everything accumulated is an INTEGER (counts, sums of
+ * fixed-point coordinates, minima and maxima of order-preserving keys), so a result does not depend on the order in which
+ * workgroups run: two calls give the same bytes, and so does any permutation of the vertices (with their labels).
+ *
+ * a3d_measure_objects.  xyz_dev fp32 [n][3], labels_dev int32 [n], object ids 0..n_classes-1, 1 <= n_classes <= 256;
+ * optionally labels_qv_dev int32 [n_qv] (NULL with n_qv = 0: none) and faces_dev int32 [m][3] (NULL with m = 0: a cloud).
+ * out_dev: n_classes records a3d_object_moments, 8-byte aligned; err_dev: int32 [1].  Both are cleared by the call.
+ * Record k:
+ *   vertices, voxels   how many entries of labels / labels_qv equal k -- for `vertices`, among the vertices that COUNT (below).
+ *   lo[3], hi[3]       the exact axis-aligned box of the vertices that count, fp32.  Coordinates are compared by the total
+ *                      order of their IEEE bit patterns: -0 lies below +0.  An object without a vertex has lo = +inf, hi = -inf.
+ *                      (How: key = bits ^ (bits >> 31 ? 0xffffffff : 0x80000000) orders like the value; integer min / max.)
+ *   sum[3], mom[6]     first and second moments in FIXED POINT: X_a = llrint(((double)x_a - origin[a]) / quantum), round half
+ *                      to even; sum[a] = the sum of X_a; mom = the sums of (XX, XY, XZ, YY, YZ, ZZ).  origin (doubles, finite)
+ *                      and quantum (a double, a positive power of two) are passed by value.
+ *   A vertex COUNTS when its label lies in 0..n_classes-1 and |X_a| <= 2^bits on every axis (0 <= bits <= 20, by value).
+ *   Else it contributes to nothing: a label outside sets A3D_MEASURE_BAD_LABEL, a coordinate outside -- or one that is not
+ *   finite -- sets A3D_MEASURE_RANGE (a vertex can set both).
+ *   OVERFLOW BOUND: |X_a X_b| <= 2^(2 bits), so no sum can leave int64 while n * 2^(2 bits) <= 2^62; the call refuses any
+ *   other n (bits = 20: n <= 2^22 vertices; bits = 16: n <= 2^30), and n, n_qv >= 2^31.
+ *   area_thirds        the surface the object covers on the mesh.  For every face (a, b, c), in double, every operation rounded
+ *                      on its own (no fma contraction) and in this order:
+ *                          e1 = b - a;  e2 = c - a
+ *                          nx = e1y*e2z - e1z*e2y;  ny = e1z*e2x - e1x*e2z;  nz = e1x*e2y - e1y*e2x
+ *                          len = sqrt((nx*nx + ny*ny) + nz*nz);  Q = llrint(len / area_quantum)
+ *                      (len = twice the face's area; divide and sqrt correctly rounded).  Q is added to the object of EACH of
+ *                      the three corners: the object's area is area_thirds * area_quantum / 6, and the areas of all objects sum
+ *                      EXACTLY to the sum of Q over the counted faces, times area_quantum / 2.  area_quantum: a positive power
+ *                      of two, by value (suggested: quantum^2 * 2^8; needed only when m > 0).
+ *   A face with a corner index outside 0..n-1 is skipped silently (as the renders skip it); one with a corner whose label
+ *   lies outside is skipped and sets A3D_MEASURE_BAD_LABEL; one with len / area_quantum above A3D_MEASURE_MAX_Q = 2^38, or
+ *   not a number, is skipped and sets A3D_MEASURE_RANGE.  Coordinates play no other part: a corner outside the fixed-point
+ *   range still carries its face.
+ *   OVERFLOW BOUND: an object receives at most 3 Q per face, so area_thirds <= 3 m 2^38 < 2^63 while m <= A3D_MEASURE_MAX_FACES
+ *   = 2^23; the call refuses a larger m.  (With the suggested area_quantum and bits = 20 a face as large as the scene's box has
+ *   Q < 2^36.)
+ *   A voxel label outside 0..n_classes-1 sets A3D_MEASURE_BAD_LABEL and is not counted.
+ *   How: a workgroup of A3D_MEASURE_BLOCK threads owns A3D_MEASURE_CHUNK consecutive vertices and keeps the 256 records in LDS;
+ *   a wave whose lanes carry one label -- labels are coherent in space, so most do -- folds its lanes with shuffles and
+ *   updates LDS once, a mixed wave falls back to per-lane LDS atomics; the non-empty records then go to out_dev with integer
+ *   atomics (add, unsigned min / max: no compare-and-swap loop).  Voxels and faces are launches of their own, shaped alike.
+ *   The library allocates nothing and does not synchronise.
+ *   A3D_ERR_INVALID with nothing launched and nothing written: no arguments, n_classes outside 1..256, bits outside 0..20, n, n_qv
+ *   or m negative or beyond the bounds above, out_dev or err_dev NULL, out_dev not 8-byte aligned, a needed input NULL (xyz_dev,
+ *   labels_dev when n > 0; labels_qv_dev when n_qv > 0; faces_dev when m > 0), an origin that is not finite, a quantum (or, with
+ *   m > 0, an area_quantum) that is not a positive power of two.
+ *
+ * a3d_object_extents -- the second pass, for oriented boxes.  axes_dev fp32 [n_classes][3][3]: three axes per object (row j of
+ * object k = axis j).  For every vertex whose label k lies in range and whose coordinates are finite, and every axis j, in fp32,
+ * every operation rounded on its own:  p = (a_x*x + a_y*y) + a_z*z.  out_dev fp32 [n_classes][3][2] = (min, max) of p per
+ * (object, axis), by the same total order of bit patterns; an object without a vertex has (+inf, -inf).  err_dev int32 [1]: a
+ * label outside sets A3D_MEASURE_BAD_LABEL; a coordinate that is not finite sets A3D_MEASURE_RANGE and the vertex is skipped;
+ * a projection that is NaN (axes that are not finite) sets A3D_MEASURE_RANGE and is skipped.  Both outputs are cleared by the
+ * call; the same kernel shape; A3D_ERR_INVALID as above (n_classes, n, NULL pointers; out_dev 4-byte aligned). */
+#define A3D_MEASURE_RANGE     1
+#define A3D_MEASURE_BAD_LABEL 2
+#define A3D_MEASURE_MAX_BITS  20
+#define A3D_MEASURE_MAX_Q     (1ll << 38)
+#define A3D_MEASURE_MAX_FACES (1ll << 23)
+#define A3D_MEASURE_BLOCK     256
+#define A3D_MEASURE_CHUNK     1024
+typedef struct a3d_object_moments {
+  int64_t vertices, voxels;
+  int64_t sum[3];                   /* X, Y, Z */
+  int64_t mom[6];                   /* XX, XY, XZ, YY, YZ, ZZ */
+  int64_t area_thirds;
+  float   lo[3], hi[3];
+  int32_t reserved_[2];
+} a3d_object_moments;              /* 128 bytes */
+typedef struct a3d_measure_args {
+  const float*   xyz_dev;           /* [n][3] */
+  const int32_t* labels_dev;        /* [n] */
+  int64_t        n;
+  const int32_t* labels_qv_dev;     /* [n_qv] or NULL */
+  int64_t        n_qv;
+  const int32_t* faces_dev;         /* [m][3] or NULL */
+  int64_t        m;
+  a3d_object_moments* out_dev;      /* out [n_classes] */
+  int32_t*       err_dev;           /* out int32 [1] */
+  double         origin[3];
+  double         quantum;
+  double         area_quantum;
+  int32_t        n_classes;
+  int32_t        bits;
+} a3d_measure_args;
+int    a3d_measure_objects(const a3d_measure_args* args, void* stream);
+
+typedef struct a3d_extents_args {
+  const float*   xyz_dev;           /* [n][3] */
+  const int32_t* labels_dev;        /* [n] */
+  int64_t        n;
+  const float*   axes_dev;          /* [n_classes][3][3] */
+  float*         out_dev;           /* out [n_classes][3][2] */
+  int32_t*       err_dev;           /* out int32 [1] */
+  int32_t        n_classes;
+  int32_t        reserved_;
+} a3d_extents_args;
+int    a3d_object_extents(const a3d_extents_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
  * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a

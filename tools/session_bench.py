@@ -6,7 +6,7 @@ alternating, on one synthetic scene (~80 k voxels, ~250 k full-resolution vertic
 
     python tools/session_bench.py [--voxels 80000] [--reps 60] [--out profiles/session_bench.json]
                                   [--mesh-only | --render-only | --annotate-only | --edit-only | --guide-only]
-                                  [--section-only [--other-lib PATH]]
+                                  [--section-only [--other-lib PATH]] [--pieces-only] [--measure-only]
 
 Every stage is timed twice: with device events around it (what the GPU spent) and with a host clock around a stage that
 ends in a synchronisation (what the caller waits).  Medians over ``--reps`` clicks after a warm-up of 10.  The baseline has
@@ -56,6 +56,15 @@ back to back like the annotate stage.  The model is FITTED first (``agile3d_amd.
 keeps and that labelling with 5 % of the rows relabelled at random (specks).  The expectation is a memory-bound pass, about
 27 x 4 B of table plus the gathered keys per voxel, twice: the figure ``table_gb_s`` is 2 x 27 x 4 B x voxels over the time of
 both calls.  Beside it the host time of ``pieces()``, ``despeckle()`` and the two modes of ``guide()``.
+
+The MEASURE stage (``--measure-only``, a run of its own) times ``a3d_measure_objects`` and ``a3d_object_extents`` back to back
+like the annotate stage: on the click scene's vertices and voxels with the scene's instance labels (the bench scene's rows are
+shuffled, so every wave is mixed: the per-lane LDS atomics), with the same rows sorted by object (every wave carries one label:
+the folded path), and with labels drawn at random over 256 ids, and on the render
+stage's height field with and without its faces (objects: stripes 40 cm wide).  A vertex is 16 bytes (12 of coordinates, 4 of
+label) and a face requests 48 (12 of indices, 36 of corners): the figures to read are the GB/s these give.  Beside them whole
+``measure()`` calls on the host clock and what the same table costs when the labels are copied to the host and reduced there
+(``measure_numpy_table``).
 
 The SECTION stage (``--section-only``, a run of its own) times ONE view, the render stage's height field as a mesh at 640 x
 480 from the outside camera, three ways that alternate call by call in one process: ``a3d_render_mesh``;
@@ -604,6 +613,103 @@ def pieces_stage(ses, xyz, lab, inst, calls, reps):
     return result
 
 
+def measure_numpy_table(xyz, labels, n_ids):
+    """What a user writes in numpy for the same table once the labels are on the host: counts, centroid, box and covariance
+    per object (float64 sums through ``np.bincount`` weights, the box through ``np.minimum.at``)."""
+    p = xyz.astype(np.float64)
+    count = np.bincount(labels, minlength=n_ids).astype(np.float64)
+    mean = np.stack([np.bincount(labels, p[:, a], n_ids) for a in range(3)], 1) / np.maximum(count, 1)[:, None]
+    c = p - mean[labels]
+    cov = np.stack([np.bincount(labels, c[:, a] * c[:, b], n_ids) for a in range(3) for b in range(3)], 1) / np.maximum(count, 1)[:, None]
+    lo, hi = np.full((n_ids, 3), np.inf, np.float32), np.full((n_ids, 3), -np.inf, np.float32)
+    np.minimum.at(lo, labels, xyz)
+    np.maximum.at(hi, labels, xyz)
+    return count, mean, cov.reshape(n_ids, 3, 3), lo, hi
+
+
+def measure_stage(ses, n_vertices, calls, reps):
+    """``a3d_measure_objects`` and ``a3d_object_extents`` back to back on the click scene (a cloud) and on the render stage's
+    height field (a mesh); whole ``measure()`` calls next to the numpy recipe (see the module docstring)."""
+    lib, dev = ses.lib, ses.device
+    rng = np.random.default_rng(12)
+
+    def back_to_back(fn):
+        per_call = []
+        for window in range(6):                     # (the first window warms up)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            per_call.append(a.elapsed_time(b) / calls)
+        return float(np.median(per_call[1:]))
+
+    origin, quantum, bits = ses._fixed_point_frame()
+    n_full, n_qv = ses.coords_full.shape[0], ses.raw_coords_qv.shape[0]
+    records = torch.empty(256 * V.OBJECT_MOMENTS.itemsize, dtype=torch.uint8, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    extents = torch.empty((256, 3, 2), dtype=torch.float32, device=dev)
+    axes = torch.from_numpy(np.stack([np.linalg.qr(rng.normal(size=(3, 3)))[0] for _ in range(256)]).astype(np.float32)).to(dev)
+    truth = ses.labels_full_ori % 256
+    by_object = torch.argsort(truth, stable=True)      # the bench scene's rows are shuffled; a scan's are coherent: sorted by object
+    labellings = {"instances": (ses.coords_full, truth, truth[ses._unique_map]),
+                  "instances_rows_by_object": (ses.coords_full[by_object].contiguous(), truth[by_object].contiguous(), truth[ses._unique_map]),
+                  "random_over_256": (ses.coords_full, torch.from_numpy(rng.integers(0, 256, n_full).astype(np.int32)).to(dev),
+                                      torch.from_numpy(rng.integers(0, 256, n_qv).astype(np.int32)).to(dev))}
+    print(f"\n== measure: {n_full} vertices, {n_qv} voxels, bits = {bits}; device ms per call, {calls} calls back to back, median of 5 "
+          f"windows ==")
+    out = {"vertices": int(n_full), "voxels": int(n_qv), "bits": bits, "calls_back_to_back": calls, "cloud": {}}
+    for name, (coords, labels, labels_qv) in labellings.items():
+        ms = {"measure_objects": back_to_back(lambda: V.measure_objects(coords, labels, origin, quantum, bits, 256,
+                                                                        labels_qv=labels_qv, records=records, err=err)),
+              "object_extents": back_to_back(lambda: V.object_extents(coords, labels, axes, extents=extents, err=err))}
+        assert int(err.cpu()[0]) == 0
+        host_labels = labels.cpu().numpy()[:n_full // 64 * 64].reshape(-1, 64)
+        uniform = float((host_labels == host_labels[:, :1]).all(1).mean())
+        ms["gb_s_at_16_bytes_per_vertex"] = 16 * n_full / (1e6 * ms["measure_objects"])
+        ms["waves_with_one_label"] = uniform
+        out["cloud"][name] = ms
+        print(f"{name:24s} measure_objects {ms['measure_objects']:.4f} = {ms['gb_s_at_16_bytes_per_vertex']:.0f} GB/s at 16 B per vertex   "
+              f"object_extents {ms['object_extents']:.4f}   waves with one label: {uniform:.2f}")
+    # the height field: a mesh of about as many vertices, two faces per cell; objects = stripes 40 cm wide
+    xyz, faces, g = height_field(n_vertices, np.random.default_rng(1))
+    stripe = (np.floor(xyz[:, 0] / 0.4).astype(np.int64) % 256).astype(np.int32)
+    xyz_dev, faces_dev, lab_dev = torch.from_numpy(xyz).to(dev), torch.from_numpy(faces).to(dev), torch.from_numpy(stripe).to(dev)
+    centre = 0.5 * (xyz.min(0) + xyz.max(0)).astype(np.float64)
+    q = 2.0 ** (int(np.ceil(np.log2(np.abs(xyz - centre).max()))) - bits)
+    mesh_ms = {"without_faces": back_to_back(lambda: V.measure_objects(xyz_dev, lab_dev, centre, q, bits, 256, records=records, err=err)),
+               "with_faces": back_to_back(lambda: V.measure_objects(xyz_dev, lab_dev, centre, q, bits, 256, faces=faces_dev,
+                                                                    records=records, err=err))}
+    assert int(err.cpu()[0]) == 0
+    mesh_ms["faces_pass"] = mesh_ms["with_faces"] - mesh_ms["without_faces"]
+    mesh_ms["faces_gb_s_at_48_bytes_per_face"] = 48 * len(faces) / (1e6 * mesh_ms["faces_pass"])
+    waves = stripe[:len(stripe) // 64 * 64].reshape(-1, 64)
+    out["mesh"] = dict(mesh_ms, vertices=len(xyz), faces=len(faces), waves_with_one_label=float((waves == waves[:, :1]).all(1).mean()))
+    print(f"height field, {len(xyz)} vertices, {len(faces)} faces, waves with one label: {out['mesh']['waves_with_one_label']:.2f}   without faces {mesh_ms['without_faces']:.4f}  with faces "
+          f"{mesh_ms['with_faces']:.4f}  the faces' pass {mesh_ms['faces_pass']:.4f} = {mesh_ms['faces_gb_s_at_48_bytes_per_face']:.0f} "
+          f"GB/s at 48 B requested per face")
+    # whole calls on the host clock, synchronised, next to: copy the labels to the host, reduce in numpy
+    host = {"measure": [], "measure_oriented_false": [], "numpy_copy_and_reduce": []}
+    coords_host = ses._coords_host
+    for _ in range(reps):
+        for key, call in (("measure", lambda: ses.measure(labels=truth)), ("measure_oriented_false", lambda: ses.measure(labels=truth, oriented=False)),
+                          ("numpy_copy_and_reduce", lambda: measure_numpy_table(coords_host, truth.cpu().numpy().astype(np.int64), 256))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = call()
+            torch.cuda.synchronize()
+            host[key].append(1e3 * (time.perf_counter() - t0))
+    out["host_ms"] = {k: float(np.median(v[reps // 4:])) for k, v in host.items()}
+    m = ses.measure(labels=truth, oriented=False)
+    live = m.vertices > 0
+    assert np.allclose(m.centroid[live], got[1][:len(live)][live], atol=quantum) and np.array_equal(m.lo[live], got[3][:len(live)][live])
+    print("whole calls (host ms, synchronised): " + "  ".join(f"{k} {v:.3f}" for k, v in out["host_ms"].items()) +
+          f"   {int(live.sum())} objects")
+    return out
+
+
 def section_stage(ses, n_vertices, reps, other_lib):
     """One view, with and without a section, next to another build of the library (see the module docstring)."""
     import ctypes as C
@@ -754,6 +860,7 @@ def main():
     ap.add_argument("--edit-only", action="store_true", help="run the edit stage (a3d_session_edit, undo / redo) alone")
     ap.add_argument("--guide-only", action="store_true", help="run the guide stage (a3d_session_guide, guide()) alone")
     ap.add_argument("--pieces-only", action="store_true", help="run the pieces stage (a3d_label_pieces, a3d_absorb_pieces) alone")
+    ap.add_argument("--measure-only", action="store_true", help="run the measure stage (a3d_measure_objects, a3d_object_extents) alone")
     ap.add_argument("--fit-iters", type=int, default=120, help="pieces stage: iterations the model is fitted for first")
     ap.add_argument("--section-only", action="store_true", help="run the section stage (one view with and without a section) alone")
     ap.add_argument("--other-lib", default=None, help="section stage: another build of libagile3d_hip.so to time beside this one")
@@ -781,7 +888,7 @@ def main():
     original = col.copy()
     centre = xyz.mean(0)
     result = {"voxels": int(n_qv), "vertices": int(n_full), "reps": a.reps, "warmup": a.warmup, "clicks": {}}
-    alone = a.mesh_only or a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only
+    alone = a.mesh_only or a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only or a.measure_only
     for n_clicks in (() if alone else (1, 5, 10, 20)):
         ses.reset()
         objs = [1 + (k % min(5, n_clicks)) for k in range(n_clicks)]
@@ -892,13 +999,15 @@ def main():
         result["guide"] = guide_stage(ses, xyz, a.mesh_calls, a.reps)
     if a.pieces_only:
         result["pieces"] = pieces_stage(ses, xyz, lab, inst, a.mesh_calls, a.reps)
+    if a.measure_only:
+        result["measure"] = measure_stage(ses, n_full, a.mesh_calls, a.reps)
     if a.section_only:
         result["section"] = section_stage(ses, n_full, a.reps, a.other_lib)
-    if not (a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only):
+    if not (a.render_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only or a.measure_only):
         result["mesh_pick"] = mesh_pick_stage(ses, n_full, a.reps, a.warmup, a.mesh_calls)
-    if not (a.mesh_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only):
+    if not (a.mesh_only or a.annotate_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only or a.measure_only):
         result["render"] = render_stage(ses, n_full, a.reps, a.warmup)
-    if not (a.mesh_only or a.render_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only):
+    if not (a.mesh_only or a.render_only or a.edit_only or a.section_only or a.guide_only or a.pieces_only or a.measure_only):
         result["annotate"] = annotate_stage(ses, n_full, a.mesh_calls)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
