@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include "../../include/agile3d_hip.h"
 
@@ -140,6 +141,31 @@ static inline int radix_passes(int bit_begin, int bit_end, RadixPass* out, int n
       fprintf(stderr, "agile3d_hip: cannot raise the dynamic LDS limit of %s to %d bytes\n", #__VA_ARGS__, (int)(BYTES)); \
     }                                                                                                                    \
   } while (0)
+
+// The dynamic-LDS limit of a kernel is raised where the kernel is NAMED for launch -- big_lds<k_x<..>>()<<<..>>>(..) --
+// once per instantiation and process: an instantiation cannot be launched without it.  (A3D_ALLOW_LDS above would report
+// every failure under the name "K"; here the function's own name carries the instantiation.)  The raise is lazy: the
+// first call of a process that reaches a new instantiation -- a new query-count tier, a first cached layer, a new conv
+// shape class -- issues one hipFuncSetAttribute there, later calls none.  Run every tier / shape class once before
+// capturing these launches in a graph.
+template <auto K>
+static auto big_lds() {
+  static const bool raised = [] {
+    if (hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+      (void)hipGetLastError();   // not the next launch check's to report
+      fprintf(stderr, "agile3d_hip: cannot raise the dynamic LDS limit to 160 KB: %s\n", __PRETTY_FUNCTION__);
+    }
+    return true;
+  }();
+  (void)raised;
+  return K;
+}
+
+// the A/B switches of the environment: each is read once per process, into a static of its reader
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 size_t radix_sort_temp_bytes(int n_max);
 // stable, ascending in the listed digits; digits that are constant over the input are skipped on the device;

@@ -2760,11 +2760,7 @@ extern "C" int a3d_decoder_pack_query_weights(const a3d_decoder_weights* w, int3
   return A3D_OK;
 }
 
-// the A/B switches of the environment: each is read once per process, into the function-local static of its reader
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+// the A/B switches of the environment (env_int, common.h)
 static bool fused_c2s() {   // A3D_FUSED_C2S=0 keeps the separate K / V GEMMs + k_c2s_attn (A/B switch)
   static const bool v = env_int("A3D_FUSED_C2S", 1) != 0;
   return v;
@@ -2787,23 +2783,7 @@ static int wide_from() {
   static const int v = std::max(17, env_int("A3D_WIDE_FROM", 33));
   return v;
 }
-// The dynamic-LDS limit of a kernel is raised where the kernel is NAMED for launch -- big_lds<k_x<..>>()<<<..>>>(..) --
-// once per instantiation and process: an instantiation cannot be launched without it.  (A3D_ALLOW_LDS of common.h, which
-// would report every failure under the name "K"; here the function's own name carries the instantiation.)  The raise is
-// lazy: the first pass of a process that reaches a new instantiation -- a new query-count tier, a first cached layer --
-// issues one hipFuncSetAttribute there, later passes none.  Run every tier once before capturing these launches in a graph.
-template <auto K>
-static auto big_lds() {
-  static const bool raised = [] {
-    if (hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      (void)hipGetLastError();   // not the next launch check's to report
-      fprintf(stderr, "agile3d_hip: cannot raise the dynamic LDS limit to 160 KB: %s\n", __PRETTY_FUNCTION__);
-    }
-    return true;
-  }();
-  (void)raised;
-  return K;
-}
+// (every kernel here that needs more than 64 KB of LDS is named for launch through big_lds<..>(), common.h)
 
 // one batch sample on the host: validated query list, workspace layout and the views into its workspace
 struct Prepared {

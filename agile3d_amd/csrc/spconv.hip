@@ -27,7 +27,7 @@
 //   * weights are the MFMA A operand: a lane ends up with 4 consecutive output channels of one row, so
 //     BatchNorm(eval) scale/shift, residual, ReLU and the channel-slice concat are 16-byte epilogue accesses.
 #include "common.h"
-#include <stdlib.h>
+#include <algorithm>
 
 namespace a3d {
 
@@ -1242,12 +1242,7 @@ __global__ void __launch_bounds__(1024) k_conv_wl(const ConvArgs c, int ngroups,
   }
 }
 
-static bool conv_wl_supported(const ConvArgs& c) {
-  if (c.K <= 1 || !c.nbr || !c.gmask) return false;
-  if (!(c.cin == 32 && c.cout == 32)) return false;   // 64 -> 64 stride-2 (128 KB) measured slower than k_conv_sk (21 vs 18 us)
-  return (size_t)c.K * c.cin * c.cout * 4 <= 144 * 1024;
-}
-
+// the 32 -> 32 layers with a kernel map (plan_conv's family kConvWl)
 static int launch_conv_wl(const ConvArgs& c, hipStream_t st, float* stats = nullptr, int stats_ld = 0, const BwArgs* bw = nullptr) {
   const int ngroups = (c.n_out + 15) / 16;
   const size_t lds = (size_t)c.K * c.cin * c.cout * 4;
@@ -1257,15 +1252,8 @@ static int launch_conv_wl(const ConvArgs& c, hipStream_t st, float* stats = null
   if ((long long)grid * nw > ngroups) grid = (ngroups + nw - 1) / nw;
   if (grid < 1) grid = 1;
   ProfScope ps(st, A3D_PROF_SPCONV, c.cout, c.K, c.cin, c.cout, c.n_out, c.tag_table, c.tag_level, 0);   // stage width 0: k_conv_wl
-  if (stats) {
-    if (c.cin != 32) {
-      set_error("spconv: no statistics build of the 64-channel LDS-resident kernel");
-      return A3D_ERR_UNSUPPORTED;
-    }
-    if (bw) k_conv_wl<2, 2, 2><<<grid, 64 * nw, lds, st>>>(c, ngroups, stats, stats_ld, *bw);
-    else k_conv_wl<2, 2, 1><<<grid, 64 * nw, lds, st>>>(c, ngroups, stats, stats_ld);
-  } else if (c.cin == 32) k_conv_wl<2, 2><<<grid, 64 * nw, lds, st>>>(c, ngroups);
-  else k_conv_wl<4, 4><<<grid, 64 * nw, lds, st>>>(c, ngroups);
+  const auto kern = bw ? big_lds<k_conv_wl<2, 2, 2>>() : stats ? big_lds<k_conv_wl<2, 2, 1>>() : big_lds<k_conv_wl<2, 2>>();
+  kern<<<grid, 64 * nw, lds, st>>>(c, ngroups, stats, stats_ld, bw ? *bw : BwArgs());
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -1382,7 +1370,6 @@ __global__ void __launch_bounds__(768) k_dense(const float* __restrict__ X, int 
   }
 }
 
-static void allow_big_lds();
 static bool dense_supported(int cin, int cout) {
   return (cin == 96 || cin == 128) && (cout == 96 || cout == 128);
 }
@@ -1393,7 +1380,6 @@ static int launch_dense(const float* X, int ldx, const float* X2, int ldx2, int 
     set_error("a3d_linear: leading dimensions must be multiples of 4");
     return A3D_ERR_INVALID;
   }
-  allow_big_lds();
   const int ngroups = (n + 15) / 16;
   // workgroup shape by row count.  80 k rows, 128 -> 128: 4x2 41 us, 8x2 48, 8x1 47, 12x1 46, 6x2 60; 1.28 M rows (16-scene
   // batch), 128 -> 96 / 96 -> 128: 4x2 387 / 366 us, 6x2 461 / 441, 8x2 379 / 364, 12x1 350 / 335 -- the kernel is latency-bound
@@ -1404,18 +1390,10 @@ static int launch_dense(const float* X, int ldx, const float* X2, int ldx2, int 
   ProfScope ps(st, A3D_PROF_DENSE, 0, 1, cin, cout, n, A3D_OP_LINEAR, tag_level, 1);
   const int max_grid = 256 * wg_per_cu;
   const int grid = (ngroups + nw - 1) / nw < max_grid ? (ngroups + nw - 1) / nw : max_grid;
-#define A3D_DENSE(NS_, NCT_) \
-  do { \
-    if (X2) k_dense<NS_, NCT_, true><<<grid, 64 * nw, lds, st>>>(X, ldx, X2, ldx2, n, Wp, scale, shift, res, ldr, relu, Y, ldy, ngroups, \
-                                                                 zero_row, out_map); \
-    else k_dense<NS_, NCT_, false><<<grid, 64 * nw, lds, st>>>(X, ldx, X2, ldx2, n, Wp, scale, shift, res, ldr, relu, Y, ldy, ngroups, \
-                                                               zero_row, out_map); \
-  } while (0)
-  if (cin == 128 && cout == 128) A3D_DENSE(8, 8);
-  else if (cin == 128 && cout == 96) A3D_DENSE(8, 6);
-  else if (cin == 96 && cout == 128) A3D_DENSE(6, 8);
-  else A3D_DENSE(6, 6);
+#define A3D_DENSE(NS_, NCT_) (X2 ? big_lds<k_dense<NS_, NCT_, true>>() : big_lds<k_dense<NS_, NCT_, false>>())
+  const auto kern = cin == 128 ? (cout == 128 ? A3D_DENSE(8, 8) : A3D_DENSE(8, 6)) : (cout == 128 ? A3D_DENSE(6, 8) : A3D_DENSE(6, 6));
 #undef A3D_DENSE
+  kern<<<grid, 64 * nw, lds, st>>>(X, ldx, X2, ldx2, n, Wp, scale, shift, res, ldr, relu, Y, ldy, ngroups, zero_row, out_map);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -1638,22 +1616,34 @@ __global__ void k_pack_weight(const float* __restrict__ w, int K, int cin, int c
 }
 
 // ------------------------------------------------------------------------------ host: launch
+// ---- planning: which kernel family and geometry an op gets.  Plain C++ from here to the end-of-planning mark (no HIP
+// types; env_int is common.h's), so that the block compiles into a stand-alone host program that sweeps it.
 constexpr int kMaxQueuesPerOp = 1024;  // ints of zeroed per-op state: k_conv_sk ticket [0], failure word [1], hand-off flags [2..2+G)
 constexpr int kSkMaxG = 1020;
 
-// ---- k_conv_sk: launch geometry
-struct SkPlan {
-  int bn, ch, pair, nchunk, ov, n_cblk, G, ntile;
+// what an op runs on: the answer of plan_conv below, and of the two planners it chooses between
+enum ConvFamily { kConvWl, kConvDeep, kConvSk };
+struct ConvPlan {
+  ConvFamily family;
+  int bn, ch, pair;    // the build (pair: k_conv_sk only)
+  int D, P;            // k_conv_deep: ring slots, parts per unit
+  int G, n_cblk, ntile, nchunk, nchunk2, ov;   // G = 0: plan_deep leaves the layer to the stream-K kernel
+  bool handoff, prio;  // k_conv_sk: shares cut inside tiles; static wave priorities
+  // would the stream-K kernel take the projection / the head into this op?  (Asked of its geometry whatever the family: a
+  // projection that only the deep kernel could fuse still runs as two launches, as it always has.)
+  bool fused_ok, head_ok;
   size_t lds, slab_floats;
 };
-static int sk_ch(int cin, int bn) {   // input channels per stage
+
+// ---- k_conv_sk: launch geometry
+static int sk_ch(int cin, int bn) {   // input channels per stage (0: none -- such a cin is refused before any launch)
+  if (cin % 32) return 0;
   // 128-column workgroups: 32-channel stages as well.  Measured on the 16-scene batch against 64-channel stages
   // (profiles/r03_experiments.txt): every <128,*> layer 1-3 % faster, L4 128 -> 256 63 -> 53 us
-  if (bn == 128 && cin % 32 == 0) return 32;
   // 96-column workgroups: 32-channel stages -- 157 registers, a 25 KB weight ring: THREE workgroups per CU, the third
   // covers the per-tile prologues / epilogues and the stage barriers of the other two (measured on the 4-scene batch:
   // L0 96 -> 96 700 -> 620 us = 108 TF/s, 128 -> 96 850 -> 790 us = 113 TF/s against 96- / 64-channel stages with two)
-  if (bn == 96 && cin % 32 == 0) return 32;
+  if (bn == 128 || bn == 96) return 32;
   const int cand[3] = {96, 64, 32};
   for (int i = 0; i < 3; ++i)
     if (cin % cand[i] == 0 && 2 * cand[i] * bn * 4 + 64 <= 80 * 1024) return cand[i];
@@ -1677,7 +1667,6 @@ static int sk_wgs_per_cu(int bn, int ch, int pair, size_t lds) {
   } else {
     if (bn == 32) by_regs = ch <= 32 ? 5 : 4;
     else if (bn == 64) by_regs = ch <= 32 ? 4 : 3;
-    else if (bn == 96) by_regs = ch <= 48 ? 3 : 2;
   }
   const int by_lds = (int)(160 * 1024 / lds);
   const int w = by_regs < by_lds ? by_regs : by_lds;
@@ -1685,8 +1674,11 @@ static int sk_wgs_per_cu(int bn, int ch, int pair, size_t lds) {
 }
 // force_ch > 0: that stage width instead of sk_ch's choice (a fused projection whose input channels the preferred width does
 // not divide: the 32 -> 64 block of level 2 runs its 64 -> 64 conv with 32-channel stages)
-static SkPlan plan_sk(int n_rows, int K, int cin, int cout, bool handoff, int force_ch = 0) {
-  SkPlan p;
+static ConvPlan plan_sk(int n_rows, int K, int cin, int cout, bool handoff, int force_ch = 0) {
+  ConvPlan p;
+  memset(&p, 0, sizeof(p));
+  p.family = kConvSk;
+  p.handoff = handoff;
   p.ntile = (n_rows + 63) / 64;
   if (p.ntile < 1) p.ntile = 1;
   const int k_eff = K == 27 ? 13 : K;   // a 3^3 map has 11-17 of its 27 offsets per tile (the kernel uses the exact counts)
@@ -1726,6 +1718,7 @@ static SkPlan plan_sk(int n_rows, int K, int cin, int cout, bool handoff, int fo
       break;
     }
   }
+  p.prio = handoff && p.G > 256;   // static wave priorities: measured +1 % on the 96-column layers (L0 593 -> 588 us)
   return p;
 }
 
@@ -1739,24 +1732,16 @@ static SkPlan plan_sk(int n_rows, int K, int cin, int cout, bool handoff, int fo
 // The kernel is preferred while the layer's matrix work per CU stays below A3D_DEEP_MAX_US (18): beyond that the stream-K
 // kernel's two workgroups per CU win (measured: level 3 384 -> 256 a tie at 23 us of work per CU, level 2 192 -> 128 lost).
 // A3D_CONV_DEEP=0 switches the kernel off (A/B).
-struct DeepPlan {
-  bool use;
-  int bn, ch, P, G, n_cblk, ntile, nchunk, D;
-  size_t lds, slab_floats;
-  float est_us;
-};
 static int g_deep_mode = -1;
 static int deep_mode() {
-  if (g_deep_mode < 0) {
-    const char* e = getenv("A3D_CONV_DEEP");
-    g_deep_mode = e ? atoi(e) : 1;
-  }
+  if (g_deep_mode < 0) g_deep_mode = env_int("A3D_CONV_DEEP", 1);
   return g_deep_mode;
 }
 // `up`: a transposed 2^3 layer -- its fine rows are sorted by child slot, a tile has one or two of the eight offsets
-static DeepPlan plan_deep(int n_rows, int K, int cin, int cout, int cin2, bool up = false) {
-  DeepPlan best;
+static ConvPlan plan_deep(int n_rows, int K, int cin, int cout, int cin2, bool up = false) {
+  ConvPlan best;
   memset(&best, 0, sizeof(best));
+  best.family = kConvDeep;
   if (!deep_mode() || K < 2 || K > 27 || cin % 32 || cout % 32) return best;
   static float max_us = -1.f;
   if (max_us < 0.f) {
@@ -1818,89 +1803,191 @@ static DeepPlan plan_deep(int n_rows, int K, int cin, int cout, int cin2, bool u
     }
   }
   if (best_t > 1e29f) return best;
-  best.use = true;
-  best.est_us = best_t;
+  best.nchunk2 = cin2 > 0 ? cin2 / best.ch : 0;
   best.lds = lds_of(best.bn, best.ch, best.D);
   best.slab_floats = best.P > 1 ? (size_t)best.G * 64 * best.bn : 0;
   return best;
 }
 
-static void allow_big_lds() {
-  static bool done = false;
-  if (done) return;
-  done = true;
-#define A3D_BIG3(BN_, CH_) \
-  A3D_ALLOW_LDS(160 * 1024, k_conv_sk<BN_, CH_, 0>); \
-  A3D_ALLOW_LDS(160 * 1024, k_conv_sk<BN_, CH_, 1>); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_sk<BN_, CH_, 0, false, 1>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_sk<BN_, CH_, 1, false, 1>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_sk<BN_, CH_, 0, false, 2>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_sk<BN_, CH_, 1, false, 2>));
-  A3D_BIG3(32, 32) A3D_BIG3(32, 64) A3D_BIG3(32, 96) A3D_BIG3(64, 32) A3D_BIG3(64, 64) A3D_BIG3(64, 96)
-  A3D_BIG3(96, 32) A3D_BIG3(96, 48) A3D_BIG3(96, 64) A3D_BIG3(96, 96) A3D_BIG3(128, 32) A3D_BIG3(128, 64)
-#undef A3D_BIG3
-#define A3D_BIGF(BN_, CH_) \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_sk<BN_, CH_, 0, true>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_sk<BN_, CH_, 1, true>));
-  A3D_BIGF(64, 32) A3D_BIGF(64, 64) A3D_BIGF(96, 32) A3D_BIGF(128, 32)
-#undef A3D_BIGF
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_sk<96, 32, 1, false, 0, true>));
-#define A3D_BIGD(BN_, CH_) \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, false, 3>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, true, 3>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, false, 2>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, true, 2>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, false, 3, 1>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, false, 2, 1>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, false, 3, 2>)); \
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_deep<BN_, CH_, false, 2, 2>));
-  A3D_BIGD(128, 32) A3D_BIGD(64, 64) A3D_BIGD(64, 32) A3D_BIGD(32, 64) A3D_BIGD(32, 32)
-#undef A3D_BIGD
-  A3D_ALLOW_LDS(160 * 1024, k_conv_wl<2, 2>);
-  A3D_ALLOW_LDS(160 * 1024, k_conv_wl<4, 4>);
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_wl<2, 2, 1>));
-  A3D_ALLOW_LDS(160 * 1024, (k_conv_wl<2, 2, 2>));
-  A3D_ALLOW_LDS(160 * 1024, (k_dense<8, 8, false>));
-  A3D_ALLOW_LDS(160 * 1024, (k_dense<8, 6, false>));
-  A3D_ALLOW_LDS(160 * 1024, (k_dense<6, 8, false>));
-  A3D_ALLOW_LDS(160 * 1024, (k_dense<6, 6, false>));
-  A3D_ALLOW_LDS(160 * 1024, (k_dense<8, 8, true>));
-  A3D_ALLOW_LDS(160 * 1024, (k_dense<8, 6, true>));
-  A3D_ALLOW_LDS(160 * 1024, (k_dense<6, 8, true>));
-  A3D_ALLOW_LDS(160 * 1024, (k_dense<6, 6, true>));
+// ---- the builds that exist, each list written once: V(BN, CH, PAIR) of k_conv_sk (what plan_sk can return for the channel
+// counts launch_conv_sk admits), the subset that has a fused-projection build, and V(BN, CH) of k_conv_deep (plan_deep's
+// candidates).  sk_kernel / deep_kernel below instantiate from them; plan_conv answers "is there a fused build" from them.
+#define A3D_SK_BUILDS(V) \
+  V(32, 32, 0) V(32, 64, 0) V(32, 96, 0) V(64, 32, 0) V(64, 64, 0) V(64, 96, 0) V(96, 32, 1) V(128, 32, 0) V(128, 32, 1)
+#define A3D_SK_FUSED_BUILDS(V) V(64, 32, 0) V(64, 64, 0) V(96, 32, 1) V(128, 32, 0) V(128, 32, 1)
+#define A3D_DEEP_BUILDS(V) V(128, 32) V(64, 64) V(64, 32) V(32, 64) V(32, 32)
+
+// ---- one plan per op: what launch_conv_sk launches, and what a3d_program_run asks before it fuses anything into an op
+struct ConvShape {
+  int n_out, K, cin, cout;
+  int cin2;            // input channels of a fused residual projection (0: none)
+  int head_cout;       // output columns of a fused head (0: none)
+  int stats;           // 0: none, 1: BatchNorm partials from the epilogue, 2: the BatchNorm-backward sums
+  bool up;             // a transposed 2^3 layer
+  bool tables;         // the op has a kernel map (neighbour table and group masks)
+  bool proj_in_ok;     // cin2 > 0: its operand can be gathered (3^3 op, 16-byte rows inside the gather window)
+  bool has_state;      // zeroed hand-off state is at hand ...
+  size_t slab_floats;  // ... and this much hand-off slab
+};
+static bool conv_channels_ok(int cin, int cout) {
+  return cin % 32 == 0 && cout % 16 == 0 && (cout % 128 == 0 || cout == 32 || cout == 64 || cout == 96);
+}
+static ConvPlan plan_conv(const ConvShape& s) {
+  // the LDS-resident kernel: 32 -> 32 with a kernel map (64 -> 64 stride-2, 128 KB, measured slower than k_conv_sk: 21 vs 18 us)
+  if (s.cin2 == 0 && s.K > 1 && s.tables && s.cin == 32 && s.cout == 32 && (size_t)s.K * s.cin * s.cout * 4 <= 144 * 1024) {
+    ConvPlan wl;
+    memset(&wl, 0, sizeof(wl));
+    wl.family = kConvWl;
+    return wl;
+  }
+  // hand-offs (shares cut inside tiles) pay where a tile is long and tiles are few: the 3^3 maps, and the 2^3 maps of
+  // the small levels.  1x1 layers and 2^3 maps with a tile per workgroup slot or more run whole tiles: no ticket, no
+  // search, no flags -- their fixed latency is what matters
+  bool handoff = s.has_state && s.K > 1;
+  if (handoff && s.K <= 8) {
+    const ConvPlan q = plan_sk(s.n_out, s.K, s.cin, s.cout, false);
+    if ((long long)q.ntile * q.n_cblk >= 192) handoff = false;
+  }
+  ConvPlan p = plan_sk(s.n_out, s.K, s.cin, s.cout, handoff);
+  if (s.cin2 > 0 && p.ch && s.cin2 % p.ch != 0 && s.cin2 % 32 == 0) p = plan_sk(s.n_out, s.K, s.cin, s.cout, handoff, 32);
+  p.nchunk2 = s.cin2 > 0 && p.ch ? s.cin2 / p.ch : 0;
+#define A3D_V(BN_, CH_, PAIR_) || (p.bn == BN_ && p.ch == CH_ && p.pair == PAIR_)
+  const bool fused_ok = s.cin2 > 0 && conv_channels_ok(s.cin, s.cout) && p.ch && s.cin2 % p.ch == 0 && (false A3D_SK_FUSED_BUILDS(A3D_V));
+#undef A3D_V
+  const bool head_ok = s.head_cout > 0 && s.head_cout % 16 == 0 && s.head_cout <= 256 && s.cout == 96 && s.cin % 32 == 0 &&
+                       s.cin2 == 0 && !s.stats && p.bn == 96 && p.ch == 32 && p.pair == 1;   // the one HEAD build
+  if (s.has_state && s.head_cout == 0 && s.K > 1) {
+    const ConvPlan d = plan_deep(s.n_out, s.K, s.cin, s.cout, s.cin2, s.up);
+    if (d.G > 0 && d.slab_floats <= s.slab_floats && (s.cin2 == 0 || s.proj_in_ok)) p = d;
+  }
+  p.fused_ok = fused_ok, p.head_ok = head_ok;
+  // training: the (last arriver's / owner's) epilogue writes the tile's BatchNorm partials, the four waves meet in LDS
+  if (s.stats) p.lds += (size_t)8 * p.bn * 4;
+  return p;
 }
 
-// does a fused-projection build of k_conv_sk exist for what plan_sk picks at this row count?  (the stage width and the
-// column block depend on the rows; a3d_program_run falls back to conv + separate 1x1 launch when not)
-static bool sk_fused_ok(int n_rows, int cin, int cout, int cin2) {
-  if (cin % 32 != 0 || cout % 16 != 0 || !(cout % 128 == 0 || cout == 32 || cout == 64 || cout == 96)) return false;
-  if (cin2 <= 0) return false;
-  SkPlan p = plan_sk(n_rows, 27, cin, cout, true);
-  if (p.ch && cin2 % p.ch != 0 && cin2 % 32 == 0) p = plan_sk(n_rows, 27, cin, cout, true, 32);
-  if (!p.ch || cin2 % p.ch != 0) return false;
-  return (p.bn == 64 && (p.ch == 32 || p.ch == 64)) || (p.bn == 96 && p.ch == 32) || (p.bn == 128 && p.ch == 32);
+// The largest hand-off slab a launch at this shape can ask for.  The stream-K candidates count whatever a3d_conv_deep_mode
+// says (the tests size a workspace under one mode and use it under the other: with the deep kernel switched off its layers
+// fall to these plans), the deep plan counts while it is selectable; one sized without it is still served, since plan_conv
+// takes the deep kernel only where its slab fits.  cin2 > 0: the fused projection may run with 32-channel stages -- another
+// share count.
+static size_t max_slab_floats(int n_rows, int K, int cin, int cout, int cin2, bool up) {
+  size_t m = plan_sk(n_rows, K, cin, cout, true).slab_floats;
+  if (cin2 > 0) m = std::max(m, plan_sk(n_rows, K, cin, cout, true, 32).slab_floats);
+  return std::max(m, plan_deep(n_rows, K, cin, cout, cin2, up).slab_floats);
+}
+// ---- end of planning
+
+// ---- launches: the kernel of a plan, named through big_lds (common.h) -- its LDS limit is raised where it is first needed
+using SkKernel = void (*)(SkArgs);
+using DeepKernel = void (*)(DeepArgs);
+template <bool FUSE, int STATS>
+static SkKernel sk_kernel(const ConvPlan& p) {
+#define A3D_V(BN_, CH_, PAIR_) \
+  if (p.bn == BN_ && p.ch == CH_ && p.pair == PAIR_) return big_lds<k_conv_sk<BN_, CH_, PAIR_, FUSE, STATS>>();
+  if constexpr (FUSE) { A3D_SK_FUSED_BUILDS(A3D_V) } else { A3D_SK_BUILDS(A3D_V) }
+#undef A3D_V
+  return nullptr;
+}
+template <bool FUSE, int STATS>
+static DeepKernel deep_kernel(const ConvPlan& p) {
+#define A3D_V(BN_, CH_) \
+  if (p.bn == BN_ && p.ch == CH_) \
+    return p.D == 2 ? big_lds<k_conv_deep<BN_, CH_, FUSE, 2, STATS>>() : big_lds<k_conv_deep<BN_, CH_, FUSE, 3, STATS>>();
+  A3D_DEEP_BUILDS(A3D_V)
+#undef A3D_V
+  return nullptr;
+}
+
+// A3D_DEEP_DBG=1 (tuning): per-workgroup phase timestamps of every k_conv_deep launch, summarised on stderr (synchronises
+// the stream).  deep_dbg_buffer: the device buffer of the timestamps, nullptr while the switch is off
+static unsigned long long* deep_dbg_buffer() {
+  static unsigned long long* buf = nullptr;
+  static const bool on = env_int("A3D_DEEP_DBG", 0) && hipMalloc(&buf, (size_t)(kSkMaxG * 6 + 2) * 8) == hipSuccess;
+  return on ? buf : nullptr;
+}
+static void deep_dbg_report(const unsigned long long* dbg_buf, const ConvArgs& c, const ConvPlan& d, hipStream_t st) {
+  static unsigned long long host[kSkMaxG * 6 + 2];
+  (void)hipStreamSynchronize(st);
+  (void)hipMemcpy(host, dbg_buf, (size_t)(d.G * 6 + 2) * 8, hipMemcpyDeviceToHost);
+  unsigned long long t0min = ~0ull, tend = 0;
+  for (int w = 0; w < d.G; ++w) {
+    if (host[w * 6] < t0min) t0min = host[w * 6];
+    for (int q = 0; q < 6; ++q) if (host[w * 6 + q] > tend) tend = host[w * 6 + q];
+  }
+  double sum[6] = {0, 0, 0, 0, 0, 0}, mx[6] = {0, 0, 0, 0, 0, 0};
+  int cntq[6] = {0, 0, 0, 0, 0, 0};
+  for (int w = 0; w < d.G; ++w)
+    for (int q = 0; q < 6; ++q)
+      if (host[w * 6 + q]) {
+        const double v = (double)(host[w * 6 + q] - t0min) * 0.01;
+        sum[q] += v, ++cntq[q];
+        if (v > mx[q]) mx[q] = v;
+      }
+  fprintf(stderr, "deep<%d,%d,D%d>%s K=%d %d->%d rows=%d units=%d P=%d G=%d span %.2f us | avg/max since first start:", d.bn, d.ch, d.D,
+          c.cin2 > 0 ? "+p" : "", c.K, c.cin, c.cout, c.n_out, d.G / d.P, d.P, d.G, (double)(tend - t0min) * 0.01);
+  const char* nm[6] = {"start", "table", "stage0", "loop", "publish", "end"};
+  for (int q = 0; q < 6; ++q)
+    fprintf(stderr, " %s %.2f/%.2f", nm[q], cntq[q] ? sum[q] / cntq[q] : 0.0, mx[q]);
+  if (host[3] > host[0])   // workgroup 0: shader-clock ticks per 10 ns tick between its start and the end of its loop
+    fprintf(stderr, " | clock %.0f MHz", (double)(host[d.G * 6 + 1] - host[d.G * 6]) / (double)(host[3] - host[0]) * 100.0);
+  fprintf(stderr, "\n");
+}
+
+static int launch_conv_deep(const ConvArgs& c, const ConvPlan& d, float* slab_ws, int* state, hipStream_t st, float* stats,
+                            int stats_ld, const BwArgs* bw) {
+  DeepArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = c;
+  a.P = d.P, a.n_cblk = d.n_cblk, a.nchunk = d.nchunk, a.nchunk2 = d.nchunk2;
+  a.cnt = state + 2, a.slab = slab_ws;
+  a.in_row_bytes = (unsigned)c.ldi * 4u, a.in2_row_bytes = (unsigned)c.ldi2 * 4u;
+  a.stats = stats, a.stats_ld = stats_ld;
+  if (bw) a.bw = *bw;
+  // the kernel-volume field as k_conv_sk's (K | cin2 << 8); the column field carries 1000 + BN: "deep" in the layer tables
+  ProfScope ps(st, A3D_PROF_SPCONV, 1000 + d.bn, c.K | (c.cin2 << 8), c.cin, c.cout, c.n_out, c.tag_table, c.tag_level, d.ch);
+  a.dbg = deep_dbg_buffer();
+  if (a.dbg) (void)hipMemsetAsync(a.dbg, 0, (size_t)kSkMaxG * 6 * 8, st);
+  const DeepKernel kern = bw ? deep_kernel<false, 2>(d) : stats ? deep_kernel<false, 1>(d)
+                          : c.cin2 > 0 ? deep_kernel<true, 0>(d) : deep_kernel<false, 0>(d);
+  if (!kern) {
+    set_error("spconv: no deep kernel for BN %d CH %d", d.bn, d.ch);
+    return A3D_ERR_UNSUPPORTED;
+  }
+  kern<<<d.G, 256, d.lds, st>>>(a);
+  A3D_LAUNCH_CHECK();
+  if (a.dbg) deep_dbg_report(a.dbg, c, d, st);
+  return A3D_OK;
+}
+
+// rows x ld floats (+ the zero row) inside the 4 GB window a gather's 32-bit byte offsets reach
+static bool in_gather_window(int rows, int ld) { return (uint64_t)(rows + 1) * (uint64_t)ld * 4ull < (1ull << 32); }
+// what plan_conv needs to know of a launch
+static ConvShape conv_shape(const ConvArgs& c, int stats, bool has_state, size_t slab_floats) {
+  ConvShape s;
+  s.n_out = c.n_out, s.K = c.K, s.cin = c.cin, s.cout = c.cout, s.cin2 = c.cin2, s.head_cout = c.head_cout;
+  s.stats = stats;
+  s.up = c.tag_table == A3D_OP_UP;
+  s.tables = c.nbr && c.gmask;
+  s.proj_in_ok = c.K == 27 && c.in2 && !(c.ldi2 & 3) && in_gather_window(c.n_out, c.ldi2);
+  s.has_state = has_state;
+  s.slab_floats = slab_floats;
+  return s;
 }
 
 // stats != nullptr (training): the kernel's epilogue also writes BatchNorm partials, [blocks][2][stats_ld] with
-// *stats_rows rows per block (64: k_conv_sk tiles, 16: the groups of k_conv_wl); the op must carry no scale / shift / residual
-// is there a fused-head build for what plan_sk picks here?  (a3d_program_run runs the 1x1 layer on its own otherwise)
-static bool sk_head_ok(int n_rows, int K, int cin, int cout, int head_cout, bool handoff) {
-  if (cout != 96 || head_cout <= 0 || head_cout % 16 || head_cout > 256 || cin % 32) return false;
-  const SkPlan p = plan_sk(n_rows, K, cin, cout, handoff);
-  return p.bn == 96 && p.ch == 32 && p.pair == 1;
-}
-
+// *stats_rows rows per block (64: k_conv_sk / k_conv_deep tiles, 16: the groups of k_conv_wl); the op must carry no scale /
+// shift / residual
 // bw != nullptr (with stats): the BatchNorm-BACKWARD sums instead (STATS == 2: the op is an input-gradient conv, a residual =
 // the gradient already accumulated in the buffer is allowed)
 static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t slab_ws_floats, int* state,
                           hipStream_t st, float* stats = nullptr, int stats_ld = 0, int* stats_rows = nullptr,
                           const BwArgs* bw = nullptr) {
-  allow_big_lds();
   if (stats && (c.scale || c.shift || c.relu || c.cin2 > 0 || !stats_rows || (c.res && !bw))) {
     set_error("spconv: BatchNorm statistics are taken of a raw convolution (no epilogue, no fused projection)");
     return A3D_ERR_UNSUPPORTED;
   }
-  if (c.cin % 32 != 0 || c.cout % 16 != 0 || !(c.cout % 128 == 0 || c.cout == 32 || c.cout == 64 || c.cout == 96)) {
+  if (!conv_channels_ok(c.cin, c.cout)) {
     set_error("spconv: unsupported channels cin=%d cout=%d", c.cin, c.cout);
     return A3D_ERR_UNSUPPORTED;
   }
@@ -1908,209 +1995,104 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
     set_error("spconv: kernel volume %d > 27", c.K);
     return A3D_ERR_UNSUPPORTED;
   }
-  if ((uint64_t)(c.n_in + 1) * (uint64_t)c.ldi * 4ull >= (1ull << 32)) {
+  if (!in_gather_window(c.n_in, c.ldi)) {
     set_error("spconv: input of %d rows x %d floats exceeds the 4 GB gather window", c.n_in, c.ldi);
     return A3D_ERR_UNSUPPORTED;
   }
-  if (c.cin2 == 0 && conv_wl_supported(c)) {
-    if (stats) *stats_rows = 16;
-    return launch_conv_wl(c, st, stats, stats_ld, bw);
-  }
-  if (state && c.head_cout == 0 && c.K > 1) {
-    const DeepPlan d = plan_deep(c.n_out, c.K, c.cin, c.cout, c.cin2, c.tag_table == A3D_OP_UP);
-    if (d.use && d.slab_floats <= slab_ws_floats && (c.cin2 == 0 || (c.K == 27 && c.in2 && !(c.ldi2 & 3) &&
-        (uint64_t)(c.n_out + 1) * (uint64_t)c.ldi2 * 4ull < (1ull << 32)))) {
-      DeepArgs a;
-      memset(&a, 0, sizeof(a));
-      c.n_tiles = d.ntile;
-      a.c = c;
-      a.P = d.P;
-      a.n_cblk = d.n_cblk;
-      a.nchunk = d.nchunk;
-      a.nchunk2 = c.cin2 > 0 ? c.cin2 / d.ch : 0;
-      a.cnt = state + 2;
-      a.slab = slab_ws;
-      a.in_row_bytes = (unsigned)c.ldi * 4u;
-      a.in2_row_bytes = (unsigned)c.ldi2 * 4u;
-      size_t lds = d.lds;
-      if (stats) {   // training: the last arriver's epilogue writes the tile's BatchNorm partials (k_conv_sk's layout and orders)
-        a.stats = stats;
-        a.stats_ld = stats_ld;
-        *stats_rows = 64;
-        if (bw) a.bw = *bw;
-        lds += (size_t)8 * d.bn * 4;
-      }
-      // the kernel-volume field as k_conv_sk's (K | cin2 << 8); the column field carries 1000 + BN: "deep" in the layer tables
-      ProfScope ps(st, A3D_PROF_SPCONV, 1000 + d.bn, c.K | (c.cin2 << 8), c.cin, c.cout, c.n_out, c.tag_table, c.tag_level, d.ch);
-      // A3D_DEEP_DBG=1 (tuning): per-workgroup phase timestamps of every launch, summarised on stderr (synchronises the stream)
-      static int dbg_on = -1;
-      static unsigned long long* dbg_buf = nullptr;
-      if (dbg_on < 0) {
-        const char* e = getenv("A3D_DEEP_DBG");
-        dbg_on = e ? atoi(e) : 0;
-        if (dbg_on && hipMalloc(&dbg_buf, (size_t)(kSkMaxG * 6 + 2) * 8) != hipSuccess) dbg_on = 0;
-      }
-      if (dbg_on) {
-        a.dbg = dbg_buf;
-        (void)hipMemsetAsync(dbg_buf, 0, (size_t)kSkMaxG * 6 * 8, st);
-      }
-      if (stats) {
-        const bool two = d.D == 2;
-#define A3D_LT(BN_, CH_) \
-  if (d.bn == BN_ && d.ch == CH_) { \
-    if (bw) { if (two) k_conv_deep<BN_, CH_, false, 2, 2><<<d.G, 256, lds, st>>>(a); else k_conv_deep<BN_, CH_, false, 3, 2><<<d.G, 256, lds, st>>>(a); } \
-    else { if (two) k_conv_deep<BN_, CH_, false, 2, 1><<<d.G, 256, lds, st>>>(a); else k_conv_deep<BN_, CH_, false, 3, 1><<<d.G, 256, lds, st>>>(a); } \
-  } else
-        A3D_LT(128, 32) A3D_LT(64, 64) A3D_LT(64, 32) A3D_LT(32, 64) A3D_LT(32, 32)
-        { set_error("spconv: no deep kernel for BN %d CH %d", d.bn, d.ch); return A3D_ERR_UNSUPPORTED; }
-#undef A3D_LT
-      } else {
-        const bool two = d.D == 2;
-#define A3D_LD(BN_, CH_) \
-  if (d.bn == BN_ && d.ch == CH_) { \
-    if (c.cin2 > 0) { if (two) k_conv_deep<BN_, CH_, true, 2><<<d.G, 256, d.lds, st>>>(a); else k_conv_deep<BN_, CH_, true, 3><<<d.G, 256, d.lds, st>>>(a); } \
-    else { if (two) k_conv_deep<BN_, CH_, false, 2><<<d.G, 256, d.lds, st>>>(a); else k_conv_deep<BN_, CH_, false, 3><<<d.G, 256, d.lds, st>>>(a); } \
-  } else
-        A3D_LD(128, 32) A3D_LD(64, 64) A3D_LD(64, 32) A3D_LD(32, 64) A3D_LD(32, 32)
-        { set_error("spconv: no deep kernel for BN %d CH %d", d.bn, d.ch); return A3D_ERR_UNSUPPORTED; }
-#undef A3D_LD
-      }
-      A3D_LAUNCH_CHECK();
-      if (dbg_on) {
-        static unsigned long long host[kSkMaxG * 6 + 2];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(host, dbg_buf, (size_t)(d.G * 6 + 2) * 8, hipMemcpyDeviceToHost);
-        unsigned long long t0min = ~0ull, tend = 0;
-        for (int w = 0; w < d.G; ++w) {
-          if (host[w * 6] < t0min) t0min = host[w * 6];
-          for (int q = 0; q < 6; ++q) if (host[w * 6 + q] > tend) tend = host[w * 6 + q];
-        }
-        double sum[6] = {0, 0, 0, 0, 0, 0}, mx[6] = {0, 0, 0, 0, 0, 0};
-        int cntq[6] = {0, 0, 0, 0, 0, 0};
-        for (int w = 0; w < d.G; ++w)
-          for (int q = 0; q < 6; ++q)
-            if (host[w * 6 + q]) {
-              const double v = (double)(host[w * 6 + q] - t0min) * 0.01;
-              sum[q] += v, ++cntq[q];
-              if (v > mx[q]) mx[q] = v;
-            }
-        fprintf(stderr, "deep<%d,%d,D%d>%s K=%d %d->%d rows=%d units=%d P=%d G=%d span %.2f us | avg/max since first start:", d.bn, d.ch, d.D,
-                c.cin2 > 0 ? "+p" : "", c.K, c.cin, c.cout, c.n_out, d.G / d.P, d.P, d.G, (double)(tend - t0min) * 0.01);
-        const char* nm[6] = {"start", "table", "stage0", "loop", "publish", "end"};
-        for (int q = 0; q < 6; ++q)
-          fprintf(stderr, " %s %.2f/%.2f", nm[q], cntq[q] ? sum[q] / cntq[q] : 0.0, mx[q]);
-        if (host[3] > host[0])   // workgroup 0: shader-clock ticks per 10 ns tick between its start and the end of its loop
-          fprintf(stderr, " | clock %.0f MHz", (double)(host[d.G * 6 + 1] - host[d.G * 6]) / (double)(host[3] - host[0]) * 100.0);
-        fprintf(stderr, "\n");
-      }
-      return A3D_OK;
-    }
-  }
-  // hand-offs (shares cut inside tiles) pay where a tile is long and tiles are few: the 3^3 maps, and the 2^3 maps of
-  // the small levels.  1x1 layers and 2^3 maps with a tile per workgroup slot or more run whole tiles: no ticket, no
-  // search, no flags -- their fixed latency is what matters
-  bool handoff = state != nullptr && c.K > 1;
-  if (handoff && c.K <= 8) {
-    const SkPlan q = plan_sk(c.n_out, c.K, c.cin, c.cout, false);
-    if ((long long)q.ntile * q.n_cblk >= 192) handoff = false;
-  }
-  SkPlan p = plan_sk(c.n_out, c.K, c.cin, c.cout, handoff);
-  if (c.cin2 > 0 && p.ch && c.cin2 % p.ch != 0 && c.cin2 % 32 == 0) p = plan_sk(c.n_out, c.K, c.cin, c.cout, handoff, 32);
-  if (!p.ch) {
-    set_error("spconv: no stage size for cin=%d with %d-column workgroups", c.cin, p.bn);
-    return A3D_ERR_UNSUPPORTED;
-  }
-  if (handoff && p.slab_floats > slab_ws_floats) {
+  const ConvShape s = conv_shape(c, bw ? 2 : stats ? 1 : 0, state != nullptr, slab_ws_floats);
+  const ConvPlan p = plan_conv(s);
+  if (stats) *stats_rows = p.family == kConvWl ? 16 : 64;
+  if (p.family == kConvWl) return launch_conv_wl(c, st, stats, stats_ld, bw);
+  c.n_tiles = p.ntile;
+  if (p.family == kConvDeep) return launch_conv_deep(c, p, slab_ws, state, st, stats, stats_ld, bw);
+  if (p.handoff && p.slab_floats > slab_ws_floats) {
     set_error("spconv: hand-off workspace too small");
     return A3D_ERR_WORKSPACE;
   }
-  SkArgs a;
-  memset(&a, 0, sizeof(a));
-  c.n_tiles = p.ntile;
-  a.c = c;
-  const int* pre = pre64;
-  a.pre = c.K > 1 ? pre : nullptr;
-  a.nchunk = p.nchunk;
-  a.ov = p.ov;
-  a.n_cblk = p.n_cblk;
-  a.G = p.G;
-  a.ticket = handoff ? state : nullptr;
-  a.fail = handoff ? state + 1 : nullptr;
-  a.flags = handoff ? (unsigned*)(state + 2) : nullptr;
-  a.slab = slab_ws;
-  a.in_row_bytes = (unsigned)c.ldi * 4u;
-  a.prio = handoff && p.G > 256;   // static wave priorities: measured +1 % on the 96-column layers (L0 593 -> 588 us)
-  if (c.K > 1 && !pre) {
+  if (c.K > 1 && !pre64) {
     set_error("spconv: a gathered convolution needs the scene's tile prefix table");
     return A3D_ERR_INVALID;
+  }
+  SkArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = c;
+  a.pre = c.K > 1 ? pre64 : nullptr;
+  a.nchunk = p.nchunk, a.nchunk2 = p.nchunk2, a.ov = p.ov, a.n_cblk = p.n_cblk, a.G = p.G, a.prio = p.prio;
+  if (p.handoff) a.ticket = state, a.fail = state + 1, a.flags = (unsigned*)(state + 2);
+  a.slab = slab_ws;
+  a.in_row_bytes = (unsigned)c.ldi * 4u, a.in2_row_bytes = (unsigned)c.ldi2 * 4u;
+  a.stats = stats, a.stats_ld = stats_ld;
+  if (bw) {
+    a.bw_y = bw->y, a.bw_raw = bw->raw, a.bw_mean = bw->mean, a.bw_rstd = bw->rstd;
+    a.bw_ldy = bw->ldy, a.bw_ldraw = bw->ldraw, a.bw_relu = bw->relu;
   }
   // kernel-volume field: K, plus the fused projection's input channels in the bits above (cin2 << 8); last field: stage width
   // ... and a fused head's output columns above those (head_cout << 20)
   ProfScope ps(st, A3D_PROF_SPCONV, p.bn, c.K | (c.cin2 << 8) | (c.head_cout << 20), c.cin, c.cout, c.n_out, c.tag_table, c.tag_level,
                p.ch);
+  SkKernel kern;
   if (c.cin2 > 0) {
     // fused residual projection: the shapes the U-Net's second block convs run on
-    if (c.K != 27 || !c.in2 || c.cin2 % p.ch != 0 || (c.ldi2 & 3) ||
-        (uint64_t)(c.n_out + 1) * (uint64_t)c.ldi2 * 4ull >= (1ull << 32)) {
+    if (!s.proj_in_ok || c.cin2 % p.ch != 0) {
       set_error("spconv: fused projection unsupported here (K=%d cin2=%d stage %d)", c.K, c.cin2, p.ch);
       return A3D_ERR_UNSUPPORTED;
     }
-    a.nchunk2 = c.cin2 / p.ch;
-    a.in2_row_bytes = (unsigned)c.ldi2 * 4u;
-#define A3D_LF(BN_, CH_) \
-  if (p.bn == BN_ && p.ch == CH_) { if (p.pair) k_conv_sk<BN_, CH_, 1, true><<<p.G, 256, p.lds, st>>>(a); else k_conv_sk<BN_, CH_, 0, true><<<p.G, 256, p.lds, st>>>(a); } else
-    A3D_LF(64, 32) A3D_LF(64, 64) A3D_LF(96, 32) A3D_LF(128, 32)
-    { set_error("spconv: no fused kernel for BN %d CH %d", p.bn, p.ch); return A3D_ERR_UNSUPPORTED; }
-#undef A3D_LF
-    A3D_LAUNCH_CHECK();
-    return A3D_OK;
-  }
-  if (c.head_cout > 0) {
-    if (!(p.bn == 96 && p.ch == 32 && p.pair == 1) || c.cin2 > 0 || stats || !c.head_w || !c.head_out) {
+    kern = sk_kernel<true, 0>(p);
+    if (!kern) {
+      set_error("spconv: no fused kernel for BN %d CH %d", p.bn, p.ch);
+      return A3D_ERR_UNSUPPORTED;
+    }
+  } else if (c.head_cout > 0) {
+    if (!p.head_ok || !c.head_w || !c.head_out) {
       set_error("spconv: no fused-head build for BN %d CH %d pair %d", p.bn, p.ch, p.pair);
       return A3D_ERR_UNSUPPORTED;
     }
-    k_conv_sk<96, 32, 1, false, 0, true><<<p.G, 256, p.lds, st>>>(a);
-    A3D_LAUNCH_CHECK();
-    return A3D_OK;
-  }
-  if (stats) {
-    a.stats = stats;
-    a.stats_ld = stats_ld;
-    *stats_rows = 64;
-    const size_t lds_s = p.lds + (size_t)2 * 4 * p.bn * 4;
-    if (bw) {
-      a.bw_y = bw->y, a.bw_raw = bw->raw, a.bw_mean = bw->mean, a.bw_rstd = bw->rstd;
-      a.bw_ldy = bw->ldy, a.bw_ldraw = bw->ldraw, a.bw_relu = bw->relu;
-#define A3D_LB(BN_, CH_) \
-  if (p.bn == BN_ && p.ch == CH_) { if (p.pair) k_conv_sk<BN_, CH_, 1, false, 2><<<p.G, 256, lds_s, st>>>(a); else k_conv_sk<BN_, CH_, 0, false, 2><<<p.G, 256, lds_s, st>>>(a); } else
-      A3D_LB(32, 32) A3D_LB(32, 64) A3D_LB(32, 96) A3D_LB(64, 32) A3D_LB(64, 64) A3D_LB(64, 96)
-      A3D_LB(96, 32) A3D_LB(96, 48) A3D_LB(96, 64) A3D_LB(96, 96) A3D_LB(128, 32) A3D_LB(128, 64)
-      { set_error("spconv: no kernel for BN %d CH %d", p.bn, p.ch); return A3D_ERR_UNSUPPORTED; }
-#undef A3D_LB
-      A3D_LAUNCH_CHECK();
-      return A3D_OK;
+    kern = big_lds<k_conv_sk<96, 32, 1, false, 0, true>>();
+  } else {
+    kern = bw ? sk_kernel<false, 2>(p) : stats ? sk_kernel<false, 1>(p) : sk_kernel<false, 0>(p);
+    if (!kern) {
+      set_error("spconv: no kernel for BN %d CH %d", p.bn, p.ch);
+      return A3D_ERR_UNSUPPORTED;
     }
-#define A3D_LS(BN_, CH_) \
-  if (p.bn == BN_ && p.ch == CH_) { if (p.pair) k_conv_sk<BN_, CH_, 1, false, 1><<<p.G, 256, lds_s, st>>>(a); else k_conv_sk<BN_, CH_, 0, false, 1><<<p.G, 256, lds_s, st>>>(a); } else
-    A3D_LS(32, 32) A3D_LS(32, 64) A3D_LS(32, 96) A3D_LS(64, 32) A3D_LS(64, 64) A3D_LS(64, 96)
-    A3D_LS(96, 32) A3D_LS(96, 48) A3D_LS(96, 64) A3D_LS(96, 96) A3D_LS(128, 32) A3D_LS(128, 64)
-    { set_error("spconv: no kernel for BN %d CH %d", p.bn, p.ch); return A3D_ERR_UNSUPPORTED; }
-#undef A3D_LS
-    A3D_LAUNCH_CHECK();
-    return A3D_OK;
   }
-#define A3D_L3(BN_, CH_) \
-  if (p.bn == BN_ && p.ch == CH_) { if (p.pair) k_conv_sk<BN_, CH_, 1><<<p.G, 256, p.lds, st>>>(a); else k_conv_sk<BN_, CH_, 0><<<p.G, 256, p.lds, st>>>(a); } else
-  A3D_L3(32, 32) A3D_L3(32, 64) A3D_L3(32, 96) A3D_L3(64, 32) A3D_L3(64, 64) A3D_L3(64, 96)
-  A3D_L3(96, 32) A3D_L3(96, 48) A3D_L3(96, 64) A3D_L3(96, 96) A3D_L3(128, 32) A3D_L3(128, 64)
-  { set_error("spconv: no kernel for BN %d CH %d", p.bn, p.ch); return A3D_ERR_UNSUPPORTED; }
-#undef A3D_L3
+  kern<<<p.G, 256, p.lds, st>>>(a);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
 
 // ------------------------------------------------------------------------------ program
+// an op kind's output level, kernel volume and tables
+static int level_out(int kind, int level_in) { return level_in + (kind == A3D_OP_DOWN ? 1 : kind == A3D_OP_UP ? -1 : 0); }
+static int kind_volume(int kind) { return kind == A3D_OP_CONV3 ? 27 : kind == A3D_OP_LINEAR ? 1 : 8; }
+// binds the kind's neighbour table, group masks and (transposed) row map at input level Lin into `a`, its tile prefix table
+// into *pre; false: no such kind.  The op's output level is inside the level range.
+static bool bind_tables(const a3d_scene* s, int kind, int Lin, ConvArgs& a, const int** pre) {
+  const Level& lv = s->lv[kind == A3D_OP_UP ? Lin - 1 : Lin];   // the level that owns the map
+  *pre = nullptr;
+  switch (kind) {
+    case A3D_OP_CONV3:
+      a.nbr = lv.nbr27, a.nbr_stride = lv.npad, a.gmask = lv.gmask27, *pre = lv.pre27;
+      return true;
+    case A3D_OP_DOWN:
+      a.nbr = lv.child8, a.nbr_stride = s->lv[Lin + 1].npad, a.gmask = lv.gmask_down, *pre = lv.pre_down;
+      return true;
+    case A3D_OP_UP:
+      a.nbr = lv.up8, a.nbr_stride = lv.npad, a.gmask = lv.gmask_up, a.out_map = lv.up_rows, *pre = lv.pre_up;
+      return true;
+    case A3D_OP_LINEAR:
+      return true;
+  }
+  return false;
+}
+// a 1x1 layer over n rows of the caller's arrays: no map, no zero row; epilogue fields are the caller's to add
+static ConvArgs linear_args(const float* in, int ldi, int n, int cin, int cout, const float* w, float* out, int ldo, int tag_level) {
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = in, a.ldi = ldi, a.n_in = n, a.w = w, a.K = 1, a.cin = cin, a.cout = cout;
+  a.out = out, a.ldo = ldo, a.n_out = n, a.zero_row = -1, a.tag_table = A3D_OP_LINEAR, a.tag_level = tag_level;
+  return a;
+}
+
 struct ProgLayout {
   size_t buf_off[64];
   size_t feats4_off, partial_off, partial_floats, queue_off, total;
@@ -2137,21 +2119,13 @@ static int layout_program(const a3d_scene* s, const a3d_buf_desc* bufs, int n_bu
   for (int i = 0; i < n_ops; ++i) {
     const a3d_op& o = ops[i];
     if (o.kind == A3D_OP_STEM) continue;
-    int lvl_out = o.level_in;
-    if (o.kind == A3D_OP_DOWN) lvl_out = o.level_in + 1;
-    if (o.kind == A3D_OP_UP) lvl_out = o.level_in - 1;
+    const int lvl_out = level_out(o.kind, o.level_in);
     if (lvl_out < 0 || lvl_out >= A3D_NUM_LEVELS) {
       set_error("program: op %d leaves the level range", i);
       return A3D_ERR_INVALID;
     }
-    SkPlan q = plan_sk(s->lv[lvl_out].n, o.kernel_volume, o.cin, o.cout, true);
-    if (q.slab_floats > pf) pf = q.slab_floats;
-    if (o.proj_cin > 0) {   // the fused projection may run with 32-channel stages (launch_conv_sk): another share count
-      q = plan_sk(s->lv[lvl_out].n, o.kernel_volume, o.cin, o.cout, true, 32);
-      if (q.slab_floats > pf) pf = q.slab_floats;
-    }
-    const DeepPlan dp = plan_deep(s->lv[lvl_out].n, o.kernel_volume, o.cin, o.cout, o.proj_cin, o.kind == A3D_OP_UP);
-    if (dp.use && dp.slab_floats > pf) pf = dp.slab_floats;
+    const size_t f = max_slab_floats(s->lv[lvl_out].n, o.kernel_volume, o.cin, o.cout, o.proj_cin, o.kind == A3D_OP_UP);
+    if (f > pf) pf = f;
   }
   L.partial_off = off;
   L.partial_floats = pf;
@@ -2250,7 +2224,12 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
   int* queues = (int*)(ws + L.queue_off);
   A3D_HIP_CHECK(hipMemsetAsync(queues, 0, (size_t)n_ops * kMaxQueuesPerOp * 4, st));
   bool feats_ready = false;
-  auto buf_ptr = [&](int id) -> float* { return (float*)(ws + L.buf_off[id]); };
+  // channels [coff, coff + ch) of buffer `id`, which must live on `level`: the slice and its leading dimension (nullptr: no such slice)
+  auto slice = [&](int id, int coff, int ch, int level, int* ld) -> float* {
+    if (id < 0 || id >= n_bufs || bufs[id].level != level || coff + ch > bufs[id].channels) return nullptr;
+    *ld = bufs[id].channels;
+    return (float*)(ws + L.buf_off[id]) + coff;
+  };
 
   for (int i = 0; i < n_ops; ++i) {
     const a3d_op& o = ops[i];
@@ -2264,9 +2243,7 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
     int ldo = 0;
     const int* out_map = nullptr;
     int zero_row = -1;
-    int lvl_out = Lin;
-    if (o.kind == A3D_OP_DOWN) lvl_out = Lin + 1;
-    if (o.kind == A3D_OP_UP) lvl_out = Lin - 1;
+    const int lvl_out = level_out(o.kind, Lin);
     if (o.out_buf == A3D_BUF_EXT_OUT) {
       if (!ext_out_dev || lvl_out != 0 || o.kind == A3D_OP_UP) {
         set_error("op %d: external output needs a level-0, non-transposed op", i);
@@ -2276,25 +2253,21 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
       ldo = ext_out_ld;
       out_map = s->orig_row;
     } else {
-      if (o.out_buf < 0 || o.out_buf >= n_bufs || bufs[o.out_buf].level != lvl_out ||
-          o.out_coff + o.cout > bufs[o.out_buf].channels) {
+      out = slice(o.out_buf, o.out_coff, o.cout, lvl_out, &ldo);
+      if (!out) {
         set_error("op %d: bad output buffer", i);
         return A3D_ERR_INVALID;
       }
-      out = buf_ptr(o.out_buf) + o.out_coff;
-      ldo = bufs[o.out_buf].channels;
       zero_row = s->lv[lvl_out].n;
     }
     const float* res = nullptr;
     int ldr = 0;
     if (o.res_buf != A3D_BUF_NONE) {
-      if (o.res_buf < 0 || o.res_buf >= n_bufs || bufs[o.res_buf].level != lvl_out ||
-          o.res_coff + o.cout > bufs[o.res_buf].channels || o.out_buf == A3D_BUF_EXT_OUT) {
+      res = slice(o.res_buf, o.res_coff, o.cout, lvl_out, &ldr);
+      if (!res || o.out_buf == A3D_BUF_EXT_OUT) {
         set_error("op %d: bad residual buffer", i);
         return A3D_ERR_INVALID;
       }
-      res = buf_ptr(o.res_buf) + o.res_coff;
-      ldr = bufs[o.res_buf].channels;
     }
 
     if (o.kind == A3D_OP_STEM) {
@@ -2315,83 +2288,48 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
       // 8 waves per 64-voxel workgroup (measured: 4 waves 229 us, 8 waves 164 us, 16 waves 159 us)
       Level glv = lv;
       if (ks / 2 > kGridPad) glv.grid = nullptr;   // the grid's empty border covers 5^3 neighbourhoods
-      if (ks == 5)
-        k_stem<512, 5><<<(lv.n + 63) / 64, 512, lds, st>>>(lv.xyzb, lv.n, lv.hkeys, lv.hvals, lv.hmask, feats4, o.w_dev, ks,
-                                                           o.scale_dev, o.shift_dev, o.relu, out, ldo, zero_row, glv);
-      else
-        k_stem<512, 3><<<(lv.n + 63) / 64, 512, lds, st>>>(lv.xyzb, lv.n, lv.hkeys, lv.hvals, lv.hmask, feats4, o.w_dev, ks,
-                                                           o.scale_dev, o.shift_dev, o.relu, out, ldo, zero_row, glv);
+      (ks == 5 ? k_stem<512, 5> : k_stem<512, 3>)<<<(lv.n + 63) / 64, 512, lds, st>>>(
+          lv.xyzb, lv.n, lv.hkeys, lv.hvals, lv.hmask, feats4, o.w_dev, ks, o.scale_dev, o.shift_dev, o.relu, out, ldo, zero_row, glv);
       A3D_LAUNCH_CHECK();
       continue;
     }
 
     // ---- input placement
-    if (o.in_buf < 0 || o.in_buf >= n_bufs || bufs[o.in_buf].level != Lin ||
-        o.in_coff + o.cin > bufs[o.in_buf].channels) {
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = slice(o.in_buf, o.in_coff, o.cin, Lin, &a.ldi);
+    if (!a.in) {
       set_error("op %d: bad input buffer", i);
       return A3D_ERR_INVALID;
     }
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = buf_ptr(o.in_buf) + o.in_coff;
-    a.ldi = bufs[o.in_buf].channels;
-    a.n_in = s->lv[Lin].n;
-    a.w = o.w_dev;
-    a.K = o.kernel_volume;
-    a.cin = o.cin;
-    a.cout = o.cout;
-    a.out = out;
-    a.ldo = ldo;
-    a.out_map = out_map;
-    a.scale = o.scale_dev;
-    a.shift = o.shift_dev;
-    a.res = res;
-    a.ldr = ldr;
-    a.relu = o.relu;
-    a.zero_row = zero_row;
-    a.n_out = s->lv[lvl_out].n;
-    a.tag_table = o.kind;
-    a.tag_level = Lin;
+    a.n_in = s->lv[Lin].n, a.w = o.w_dev, a.K = o.kernel_volume, a.cin = o.cin, a.cout = o.cout;
+    a.out = out, a.ldo = ldo, a.out_map = out_map, a.n_out = s->lv[lvl_out].n, a.zero_row = zero_row;
+    a.scale = o.scale_dev, a.shift = o.shift_dev, a.res = res, a.ldr = ldr, a.relu = o.relu;
+    a.tag_table = o.kind, a.tag_level = Lin;
     if (o.proj_cin > 0) {   // fused residual projection (see a3d_op)
-      if (o.kind != A3D_OP_CONV3 || o.proj_buf < 0 || o.proj_buf >= n_bufs || bufs[o.proj_buf].level != Lin ||
-          o.proj_coff + o.proj_cin > bufs[o.proj_buf].channels || o.scale_dev) {
+      a.in2 = slice(o.proj_buf, o.proj_coff, o.proj_cin, Lin, &a.ldi2);
+      if (o.kind != A3D_OP_CONV3 || !a.in2 || o.scale_dev) {
         set_error("op %d: bad fused projection", i);
         return A3D_ERR_INVALID;
       }
-      a.in2 = buf_ptr(o.proj_buf) + o.proj_coff;
-      a.ldi2 = bufs[o.proj_buf].channels;
       a.cin2 = o.proj_cin;
     }
     const int* pre = nullptr;
-    switch (o.kind) {
-      case A3D_OP_CONV3:
-        if (o.kernel_volume != 27) { set_error("op %d: CONV3 needs kernel volume 27", i); return A3D_ERR_INVALID; }
-        a.nbr = s->lv[Lin].nbr27;
-        a.nbr_stride = s->lv[Lin].npad;
-        a.gmask = s->lv[Lin].gmask27;
-        pre = s->lv[Lin].pre27;
-        break;
-      case A3D_OP_DOWN:
-        if (o.kernel_volume != 8 || Lin >= A3D_NUM_LEVELS - 1) { set_error("op %d: bad DOWN", i); return A3D_ERR_INVALID; }
-        a.nbr = s->lv[Lin].child8;
-        a.nbr_stride = s->lv[Lin + 1].npad;
-        a.gmask = s->lv[Lin].gmask_down;
-        pre = s->lv[Lin].pre_down;
-        break;
-      case A3D_OP_UP:
-        if (o.kernel_volume != 8 || Lin < 1) { set_error("op %d: bad UP", i); return A3D_ERR_INVALID; }
-        a.nbr = s->lv[Lin - 1].up8;
-        a.nbr_stride = s->lv[Lin - 1].npad;
-        a.gmask = s->lv[Lin - 1].gmask_up;
-        a.out_map = s->lv[Lin - 1].up_rows;
-        pre = s->lv[Lin - 1].pre_up;
-        break;
-      case A3D_OP_LINEAR:
-        if (o.kernel_volume != 1) { set_error("op %d: LINEAR needs kernel volume 1", i); return A3D_ERR_INVALID; }
-        break;
-      default:
-        set_error("op %d: unknown kind %d", i, o.kind);
-        return A3D_ERR_INVALID;
+    if (!bind_tables(s, o.kind, Lin, a, &pre)) {   // (the level range of DOWN and UP: layout_program)
+      set_error("op %d: unknown kind %d", i, o.kind);
+      return A3D_ERR_INVALID;
+    }
+    if (o.kernel_volume != kind_volume(o.kind)) {
+      static const char* const what[] = {"CONV3 needs kernel volume 27", "bad DOWN", "bad UP", "LINEAR needs kernel volume 1"};
+      set_error("op %d: %s", i, what[o.kind - A3D_OP_CONV3]);
+      return A3D_ERR_INVALID;
+    }
+    // a head or a projection rides along where launch_conv_sk's plan for the op has a build for it
+    ConvPlan plan = {};
+    if (o.head_cout > 0 || a.cin2 > 0) {
+      ConvShape shape = conv_shape(a, 0, true, L.partial_floats);
+      shape.head_cout = o.head_cout;
+      plan = plan_conv(shape);
     }
     bool head_after = false;
     if (o.head_cout > 0) {
@@ -2400,12 +2338,7 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
         set_error("op %d: a fused head needs a level-0 op into a buffer, packed head weights and the external output", i);
         return A3D_ERR_INVALID;
       }
-      bool handoff_h = o.kernel_volume > 1;
-      if (handoff_h && o.kernel_volume <= 8) {
-        const SkPlan q = plan_sk(a.n_out, a.K, a.cin, a.cout, false);
-        if ((long long)q.ntile * q.n_cblk >= 192) handoff_h = false;
-      }
-      if (o.kind != A3D_OP_LINEAR && a.cin2 == 0 && !(conv_wl_supported(a)) && sk_head_ok(a.n_out, a.K, a.cin, a.cout, o.head_cout, handoff_h)) {
+      if (o.kind != A3D_OP_LINEAR && plan.head_ok) {
         a.head_w = o.head_w_dev;
         a.head_bias = o.head_bias_dev;
         a.head_out = ext_out_dev;
@@ -2416,7 +2349,7 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
         head_after = true;   // same arithmetic as its own launch below
       }
     }
-    if (a.cin2 > 0 && !sk_fused_ok(a.n_out, a.cin, a.cout, a.cin2)) {
+    if (a.cin2 > 0 && !plan.fused_ok) {
       // no fused build for this (row count, shape): the same arithmetic as two launches on the same packed weights --
       // the 27 offsets into `out` without the ReLU, then the 1x1 slice (packed right behind them) added in place
       ConvArgs c1 = a;
@@ -2427,12 +2360,8 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
         set_error("op %d: fused projection has no fallback for a row-mapped output", i);
         return A3D_ERR_UNSUPPORTED;
       }
-      ConvArgs c2;
-      memset(&c2, 0, sizeof(c2));
-      c2.in = a.in2, c2.ldi = a.ldi2, c2.n_in = a.n_out, c2.K = 1, c2.cin = a.cin2, c2.cout = a.cout;
-      c2.w = a.w + (size_t)27 * a.cin * a.cout;
-      c2.out = a.out, c2.ldo = a.ldo, c2.n_out = a.n_out, c2.res = a.out, c2.ldr = a.ldo, c2.relu = a.relu;
-      c2.zero_row = a.zero_row, c2.tag_table = A3D_OP_LINEAR, c2.tag_level = Lin;
+      ConvArgs c2 = linear_args(a.in2, a.ldi2, a.n_out, a.cin2, a.cout, a.w + (size_t)27 * a.cin * a.cout, a.out, a.ldo, Lin);
+      c2.res = a.out, c2.ldr = a.ldo, c2.relu = a.relu, c2.zero_row = a.zero_row;
       rc = launch_conv_sk(c2, nullptr, nullptr, 0, nullptr, st);
       if (rc != A3D_OK) return rc;
     } else
@@ -2447,11 +2376,8 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
         rc = launch_dense(out, ldo, nullptr, 0, a.n_out, o.cout, o.head_cout, o.head_w_dev, nullptr, o.head_bias_dev, nullptr, 0, 0,
                           ext_out_dev, ext_out_ld, -1, Lin, s->orig_row, st);
       else {
-        ConvArgs h;
-        memset(&h, 0, sizeof(h));
-        h.in = out, h.ldi = ldo, h.n_in = a.n_out, h.w = o.head_w_dev, h.K = 1, h.cin = o.cout, h.cout = o.head_cout;
-        h.out = ext_out_dev, h.ldo = ext_out_ld, h.n_out = a.n_out, h.out_map = s->orig_row, h.shift = o.head_bias_dev;
-        h.zero_row = -1, h.tag_table = A3D_OP_LINEAR, h.tag_level = Lin;
+        ConvArgs h = linear_args(out, ldo, a.n_out, o.cout, o.head_cout, o.head_w_dev, ext_out_dev, ext_out_ld, Lin);
+        h.out_map = s->orig_row, h.shift = o.head_bias_dev;
         rc = launch_conv_sk(h, nullptr, nullptr, 0, nullptr, st);
       }
       if (rc != A3D_OK) return rc;
@@ -2467,13 +2393,9 @@ extern "C" int a3d_program_run(const a3d_scene* s, const a3d_buf_desc* bufs, int
 // the program.  Workspace: a3d_conv_apply_workspace_bytes (hand-off state, zeroed here, + partial-accumulator slab).
 extern "C" size_t a3d_conv_apply_workspace_bytes(const a3d_scene* s, int kind, int level_in, int cin, int cout) {
   if (!s || level_in < 0 || level_in >= A3D_NUM_LEVELS) return 0;
-  int lvl_out = level_in + (kind == A3D_OP_DOWN ? 1 : kind == A3D_OP_UP ? -1 : 0);
+  const int lvl_out = level_out(kind, level_in);
   if (lvl_out < 0 || lvl_out >= A3D_NUM_LEVELS) return 0;
-  const int K = kind == A3D_OP_CONV3 ? 27 : kind == A3D_OP_LINEAR ? 1 : 8;
-  SkPlan q = plan_sk(s->lv[lvl_out].n, K, cin, cout, true);
-  size_t slab = q.slab_floats;
-  const DeepPlan dp = plan_deep(s->lv[lvl_out].n, K, cin, cout, 0, kind == A3D_OP_UP);
-  if (dp.use && dp.slab_floats > slab) slab = dp.slab_floats;
+  const size_t slab = max_slab_floats(s->lv[lvl_out].n, kind_volume(kind), cin, cout, 0, kind == A3D_OP_UP);
   return align256((size_t)kMaxQueuesPerOp * 4) + align256(slab * 4) + 256;
 }
 
@@ -2488,7 +2410,7 @@ static int conv_apply_impl(const a3d_scene* s, int kind, int level_in, const flo
     return A3D_ERR_INVALID;
   }
   const int Lin = level_in;
-  int lvl_out = Lin + (kind == A3D_OP_DOWN ? 1 : kind == A3D_OP_UP ? -1 : 0);
+  const int lvl_out = level_out(kind, Lin);
   if (lvl_out < 0 || lvl_out >= A3D_NUM_LEVELS) {
     set_error("%s: the op leaves the level range", who);
     return A3D_ERR_INVALID;
@@ -2500,50 +2422,14 @@ static int conv_apply_impl(const a3d_scene* s, int kind, int level_in, const flo
   }
   ConvArgs a;
   memset(&a, 0, sizeof(a));
-  a.in = x_dev;
-  a.ldi = ldx;
-  a.n_in = s->lv[Lin].n;
-  a.w = w_packed_dev;
-  a.cin = cin;
-  a.cout = cout;
-  a.out = y_dev;
-  a.ldo = ldy;
-  a.res = res_dev;
-  a.ldr = ldr;
-  a.n_out = s->lv[lvl_out].n;
-  a.zero_row = y_zero_row ? s->lv[lvl_out].n : -1;
-  a.tag_table = kind;
-  a.tag_level = Lin;
+  a.in = x_dev, a.ldi = ldx, a.n_in = s->lv[Lin].n, a.w = w_packed_dev, a.K = kind_volume(kind), a.cin = cin, a.cout = cout;
+  a.out = y_dev, a.ldo = ldy, a.n_out = s->lv[lvl_out].n, a.zero_row = y_zero_row ? s->lv[lvl_out].n : -1;
+  a.res = res_dev, a.ldr = ldr;
+  a.tag_table = kind, a.tag_level = Lin;
   const int* pre = nullptr;
-  switch (kind) {
-    case A3D_OP_CONV3:
-      a.K = 27;
-      a.nbr = s->lv[Lin].nbr27;
-      a.nbr_stride = s->lv[Lin].npad;
-      a.gmask = s->lv[Lin].gmask27;
-      pre = s->lv[Lin].pre27;
-      break;
-    case A3D_OP_DOWN:
-      a.K = 8;
-      a.nbr = s->lv[Lin].child8;
-      a.nbr_stride = s->lv[Lin + 1].npad;
-      a.gmask = s->lv[Lin].gmask_down;
-      pre = s->lv[Lin].pre_down;
-      break;
-    case A3D_OP_UP:
-      a.K = 8;
-      a.nbr = s->lv[Lin - 1].up8;
-      a.nbr_stride = s->lv[Lin - 1].npad;
-      a.gmask = s->lv[Lin - 1].gmask_up;
-      a.out_map = s->lv[Lin - 1].up_rows;
-      pre = s->lv[Lin - 1].pre_up;
-      break;
-    case A3D_OP_LINEAR:
-      a.K = 1;
-      break;
-    default:
-      set_error("%s: unknown kind %d", who, kind);
-      return A3D_ERR_INVALID;
+  if (!bind_tables(s, kind, Lin, a, &pre)) {
+    set_error("%s: unknown kind %d", who, kind);
+    return A3D_ERR_INVALID;
   }
   // the hand-off state (ticket, failure word, flags): the caller's zeroed block, or the head of the workspace zeroed here
   int* state = state_dev ? state_dev : (int*)workspace_dev;
@@ -2600,7 +2486,7 @@ extern "C" int a3d_conv_dgrad_bn(const a3d_scene* s, int kind, int level_in, con
                            (int*)state_dev, partial, cout, &rows_per_block, workspace_dev, conv_bytes, st, "a3d_conv_dgrad_bn",
                            &bw);
   if (rc != A3D_OK) return rc;
-  const int lvl_out = level_in + (kind == A3D_OP_DOWN ? 1 : kind == A3D_OP_UP ? -1 : 0);
+  const int lvl_out = level_out(kind, level_in);
   const int n = s->lv[lvl_out].n;
   return bn_sums_from_partials(partial, (n + rows_per_block - 1) / rows_per_block, cout, sums_dev, st);
 }
@@ -2608,7 +2494,7 @@ extern "C" int a3d_conv_dgrad_bn(const a3d_scene* s, int kind, int level_in, con
 extern "C" size_t a3d_conv_bn_train_workspace_bytes(const a3d_scene* s, int kind, int level_in, int cin, int cout) {
   const size_t conv = a3d_conv_apply_workspace_bytes(s, kind, level_in, cin, cout);
   if (!conv) return 0;
-  const int lvl_out = level_in + (kind == A3D_OP_DOWN ? 1 : kind == A3D_OP_UP ? -1 : 0);
+  const int lvl_out = level_out(kind, level_in);
   const size_t groups = ((size_t)s->lv[lvl_out].n + 15) / 16;                  // the finest partial granularity (k_conv_wl)
   return align256(conv) + align256(groups * 2 * (size_t)cout * 4) + 256;
 }
@@ -2633,7 +2519,7 @@ extern "C" int a3d_conv_bn_train_forward(const a3d_scene* s, int kind, int level
                            (int*)state_dev, partial, cout, &rows_per_block, workspace_dev, conv_bytes, st,
                            "a3d_conv_bn_train_forward");
   if (rc != A3D_OK) return rc;
-  const int lvl_out = level_in + (kind == A3D_OP_DOWN ? 1 : kind == A3D_OP_UP ? -1 : 0);
+  const int lvl_out = level_out(kind, level_in);
   const int n = s->lv[lvl_out].n;
   const int nblocks = (n + rows_per_block - 1) / rows_per_block;
   return bn_finish_from_partials(partial, nblocks, rows_per_block, raw_dev, ld_raw, n, cout, gamma_dev, beta_dev, eps, res_dev,
@@ -2656,26 +2542,8 @@ extern "C" int a3d_linear(const float* in_dev, int ldi, const float* in_add_dev,
     set_error("a3d_linear: a second input is only supported for 96/128 -> 96/128 channels (got %d -> %d)", cin, cout);
     return A3D_ERR_UNSUPPORTED;
   }
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = in_dev;
-  a.ldi = ldi;
-  a.n_in = (int)n;
-  a.w = w_packed_dev;
-  a.K = 1;
-  a.cin = cin;
-  a.cout = cout;
-  a.out = out_dev;
-  a.ldo = ldo;
-  a.n_out = (int)n;
-  a.scale = scale_dev;
-  a.shift = shift_dev;
-  a.res = res_dev;
-  a.ldr = ldr;
-  a.relu = relu;
-  a.zero_row = -1;
-  a.tag_table = A3D_OP_LINEAR;
-  a.tag_level = -1;
+  ConvArgs a = linear_args(in_dev, ldi, (int)n, cin, cout, w_packed_dev, out_dev, ldo, -1);
+  a.scale = scale_dev, a.shift = shift_dev, a.res = res_dev, a.ldr = ldr, a.relu = relu;
   (void)workspace_dev;
   (void)workspace_bytes;   // a 1x1 layer runs whole tiles (no hand-off state)
   return launch_conv_sk(a, nullptr, nullptr, 0, nullptr, (hipStream_t)stream);

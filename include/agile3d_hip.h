@@ -49,7 +49,7 @@ int         a3d_memcpy_d2h(void* dst_host, const void* src_dev, size_t bytes, vo
  * kernels listed below is bracketed by a hipEvent pair on the launch stream.
  * ------------------------------------------------------------------------------------------ */
 enum {
-  A3D_PROF_SPCONV = 0,      /* k_spconv2<bn,ch> (3^3 / 2^3 s2 / transposed / small 1x1)      */
+  A3D_PROF_SPCONV = 0,      /* k_conv_sk / k_conv_deep / k_conv_wl (3^3 / 2^3 s2 / transposed / small 1x1) */
   A3D_PROF_SPLITK = 1,      /* retired (the split-K reduction launches of round 1)          */
   A3D_PROF_STEM = 2,        /* 5^3 stem                                                  */
   A3D_PROF_C2S = 3,         /* click-to-scene attention                                  */

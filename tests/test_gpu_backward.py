@@ -202,6 +202,39 @@ def test_conv_bn_unit_with_statistics_from_the_conv_epilogue(world, kind, level_
     per tile in the conv kernel's epilogue) against float64: raw output, mean / rstd, running statistics, y written into a
     column slice of a wider buffer, for every kernel family the training convs run on (k_conv_sk with and without
     hand-offs, the LDS-resident 32-channel kernel, 1x1)."""
+    _check_conv_bn_unit(world, kind, level_in, cin, cout)
+
+
+@pytest.fixture(scope="module")
+def world_9000():
+    """One scene whose level 0 has at least 8192 rows: from there on a 128-column layer with 32-channel stages runs the
+    low-register build of the stream-K kernel, which the 7500 voxels of `world` do not reach."""
+    coords = make_scene(9000, seed=8)["coords"]
+    sc = Scene(torch.from_numpy(coords).cuda())
+    assert sc.n[0] >= 8192
+    lv = ob.SparseLevels(coords)
+    return sc, lv, [torch.from_numpy(internal_to_oracle_rows(sc, lv, 0))]
+
+
+@pytest.fixture
+def streamk_only():
+    lib = L.load()
+    before = lib.a3d_conv_deep_mode(0)
+    yield
+    lib.a3d_conv_deep_mode(before)
+
+
+def test_conv_bn_unit_low_register_128_column_build_from_8192_rows(world_9000, streamk_only):
+    """The same check where the conv is 3^3, 32 -> 128 on 9000 rows (its statistics build)."""
+    _check_conv_bn_unit(world_9000, L.OP_CONV3, 0, 32, 128)
+
+
+def test_input_gradient_conv_low_register_128_column_build_from_8192_rows(world_9000, streamk_only):
+    """The same check where the input-gradient conv is 3^3, 32 -> 128 on 9000 rows (its backward-sums build)."""
+    _check_input_gradient_conv_bn(world_9000, L.OP_CONV3, 0, 128, 32, True, True)
+
+
+def _check_conv_bn_unit(world, kind, level_in, cin, cout):
     sc, lv, maps = world
     lo = B.level_out(kind, level_in)
     n_in, n_out = sc.n[level_in], sc.n[lo]
@@ -256,6 +289,10 @@ def test_input_gradient_conv_with_batchnorm_backward_sums(world, kind, level_in,
     masks it and sums g, g xhat in its epilogue.  Against the plain input-gradient conv (checked against autograd above)
     followed by the mask and float64 sums; then a3d_bn_backward_apply on those sums against the layer-at-a-time
     a3d_bn_train_backward."""
+    _check_input_gradient_conv_bn(world, kind, level_in, cin, cout, acc, relu)
+
+
+def _check_input_gradient_conv_bn(world, kind, level_in, cin, cout, acc, relu):
     sc, lv, maps = world
     lo = B.level_out(kind, level_in)
     n_in, n_out = sc.n[level_in], sc.n[lo]

@@ -264,6 +264,37 @@ def test_conv_apply_every_shape_class_small_scene(small_world, conv_kernel_famil
     print(f"conv_apply {kind} L{level}: worst relative error {worst:.2e} over {len(_WIDTHS_IN) * len(_WIDTHS_OUT)} shapes")
 
 
+def test_conv_apply_low_register_128_column_build_from_8192_rows():
+    """The same check at the one shape class the scenes above are too small for: from 8192 output rows on, a 128-column layer
+    with 32-channel stages runs the low-register build of the stream-K kernel (3^3, 32 -> 128 on a level 0 of 9000 voxels,
+    the small-level kernel switched off)."""
+    from agile3d_amd import backward as B
+    coords = make_scene(9000, seed=21)["coords"]
+    sc = Scene(torch.from_numpy(coords).cuda())
+    lv = ob.SparseLevels(coords)
+    m = torch.from_numpy(internal_to_oracle_rows(sc, lv, 0))
+    n = sc.n[0]
+    assert n >= 8192
+    cin, cout = 32, 128
+    g = torch.Generator().manual_seed(9000 + cin * 100 + cout)
+    X = torch.randn(n, cin, generator=g, dtype=torch.float64)
+    W = torch.randn(27, cin, cout, generator=g, dtype=torch.float64) / (cin * 27 / 2) ** 0.5
+    x = torch.zeros(n + 1, cin, device="cuda")
+    x[:n] = X[m].float().cuda()
+    lib = L.load()
+    before = lib.a3d_conv_deep_mode(0)
+    try:
+        y = B.conv_apply(sc, L.OP_CONV3, 0, pack_weight(W.float().cuda()), x, cin, cout)
+        torch.cuda.synchronize()
+    finally:
+        lib.a3d_conv_deep_mode(before)
+    ref = ob.sparse_conv(X.float().double(), W.float().double(), lv.kernel_map(0, 3), n)[m]
+    err = (y[:n].double().cpu() - ref).abs().max().item() / max(1.0, ref.abs().max().item())
+    print(f"conv_apply conv3 L0 {cin}->{cout} on {n} rows: relative error {err:.2e}")
+    assert err <= 2e-5, err
+    assert (y[n] == 0).all()
+
+
 @pytest.mark.parametrize("level,cin,cout,cin2", [(1, 96, 96, 128), (2, 128, 128, 192), (1, 96, 64, 64), (0, 32, 32, 64)])
 def test_fused_projection_op_and_its_fallback(world, conv_kernel_family, level, cin, cout, cin2):
     """a3d_op with a fused residual projection (proj_buf / proj_cin: BasicBlock.downsample as a 28th offset of the block's
