@@ -36,7 +36,7 @@
 // an edge still classify every ray consistently.  On a cloud a vertex shows iff it lies on the kept side of every plane.  The
 // section is a template parameter of the kernels that test primitives: NoSection is the code the entry points without a
 // section have always run, and the binning of the rendered view does not know about sections at all.
-#include "common.h"
+#include "session_rules.h"                    // ses_pixel_ray, ses_keeps(a3d_section): shared with session_region.hip
 
 namespace a3d {
 
@@ -130,17 +130,8 @@ __device__ __forceinline__ bool ses_counts(const RayCut& c, float t, float det) 
   if (c.empty || !(t >= c.t_lo && t <= c.t_hi)) return false;
   return !((c.cull == A3D_CULL_BACK && det < 0.f) || (c.cull == A3D_CULL_FRONT && det > 0.f));
 }
-// Whether a cloud's vertex shows: on the kept side of every plane (a NaN fails).
+// Whether a cloud's vertex shows: ses_keeps(a3d_section) of session_rules.h; without a section every vertex does.
 __device__ __forceinline__ bool ses_keeps(const NoSection&, float, float, float) { return true; }
-__device__ __forceinline__ bool ses_keeps(const a3d_section& s, float x, float y, float z) {
-#pragma clang fp contract(off)
-  bool keep = true;
-  for (int k = 0; k < s.n_planes; ++k) {
-    const float side = (s.planes[k][0] * x + s.planes[k][1] * y) + s.planes[k][2] * z;
-    keep = keep && side >= s.planes[k][3];
-  }
-  return keep;
-}
 
 // ---- nearest rows: m queries against up to A3D_NEAREST_MAX_SOURCES row sets in one launch pair -----------------------------
 struct NearestTab {
@@ -538,17 +529,6 @@ static RenderWs carve_render(void* base, long long n_prim, int width, int height
   w.pairs = (unsigned*)c.take((size_t)(cap > 0 ? cap : 1) * 4);
   w.bytes = c.off;
   return w;
-}
-
-// The ray of pixel (u, v): the header's formula, one rounding per operation.
-__host__ __device__ inline void ses_pixel_ray(const a3d_camera& c, int u, int v, float* d) {
-#pragma clang fp contract(off)
-  const float fu = (float)u, fv = (float)v;
-  const float x = (c.d00[0] + fu * c.du[0]) + fv * c.dv[0];
-  const float y = (c.d00[1] + fu * c.du[1]) + fv * c.dv[1];
-  const float z = (c.d00[2] + fu * c.du[2]) + fv * c.dv[2];
-  const float len = sqrtf((x * x + y * y) + z * z);
-  d[0] = x / len, d[1] = y / len, d[2] = z / len;
 }
 
 // ---- the bound (tests/test_render_host.py restates it in numpy and holds it against the exact tests) ------

@@ -249,6 +249,35 @@ class Section(C.Structure):
     _fields_ = [("n_planes", C.c_int32), ("cull", C.c_int32), ("planes", (C.c_float * 4) * 8)]
 
 
+class SelectSummary(C.Structure):
+    """a3d_select_summary: selected vertices, vertices in view, flags (bit 0 = a coordinate that is not finite)."""
+    _fields_ = [("selected", C.c_int64), ("in_view", C.c_int64), ("flags", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class SelectArgs(C.Structure):
+    """a3d_select_args: the vertices, the camera and the fp32 rows of [du dv d00]^-1, the depth slack, the mask and (or NULL)
+    the t image, the section (a HOST pointer or NULL), the selection and the summary."""
+    _fields_ = [("xyz_dev", C.c_void_p), ("n", C.c_int64), ("camera", Camera), ("rows", C.c_float * 9), ("slack", C.c_float),
+                ("mask_dev", C.c_void_p), ("t_dev", C.c_void_p), ("section", C.POINTER(Section)), ("selected_dev", C.c_void_p),
+                ("summary_dev", C.c_void_p)]
+
+
+class OverlaySummary(C.Structure):
+    """a3d_overlay_summary: layer entries the call altered, vertices overridden after it, those whose manual label differs
+    from the model's, the error word (bit 0 = a label outside 0..255 where it was used)."""
+    _fields_ = [("changed", C.c_int64), ("overridden", C.c_int64), ("differing", C.c_int64), ("err", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+class SessionOverlayArgs(C.Structure):
+    """a3d_session_overlay_args: the model's labels, the manual layer (on, obj; in/out), the selection (or NULL), the colours and
+    the palette, the outputs (NULL together: a pure layer update), the summary, the operation and its object."""
+    _fields_ = [("labels_in_dev", C.c_void_p), ("n", C.c_int64), ("manual_on_dev", C.c_void_p), ("manual_obj_dev", C.c_void_p),
+                ("selected_dev", C.c_void_p), ("colors_full_dev", C.c_void_p), ("palette_dev", C.c_void_p),
+                ("labels_out_dev", C.c_void_p), ("colors_out_dev", C.c_void_p), ("summary_dev", C.c_void_p), ("op", C.c_int32),
+                ("obj", C.c_int32), ("n_palette", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class ClickCluster(C.Structure):
     _fields_ = [("cluster_id", C.c_int32), ("row", C.c_int32), ("label", C.c_int32), ("pred", C.c_int32),
                 ("error_size", C.c_float)]
@@ -262,6 +291,11 @@ A3D_RENDER_TILE = 16
 A3D_RENDER_BAD_INDEX, A3D_RENDER_OVERFLOW = 1, 2
 A3D_SECTION_MAX_PLANES = 8
 A3D_CULL_NONE, A3D_CULL_BACK, A3D_CULL_FRONT = 0, 1, 2
+A3D_REGION_MAX_POINTS = 256
+A3D_REGION_POLYGON, A3D_REGION_STROKE = 0, 1
+A3D_REGION_REPLACE, A3D_REGION_ADD, A3D_REGION_SUBTRACT = 0, 1, 2
+A3D_SELECT_NOT_FINITE = 1
+A3D_OVERLAY_NONE, A3D_OVERLAY_PAINT, A3D_OVERLAY_ERASE = 0, 1, 2
 A3D_MEASURE_RANGE, A3D_MEASURE_BAD_LABEL = 1, 2
 A3D_MEASURE_MAX_BITS, A3D_MEASURE_MAX_Q, A3D_MEASURE_MAX_FACES = 20, 1 << 38, 1 << 23
 A3D_MEASURE_BLOCK, A3D_MEASURE_CHUNK = 256, 1024
@@ -458,6 +492,10 @@ SYMBOLS = {
     "a3d_label_pieces": (C.c_int, [C.POINTER(LabelPiecesArgs), C.c_void_p]),
     "a3d_absorb_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "a3d_absorb_pieces": (C.c_int, [C.POINTER(AbsorbPiecesArgs), C.c_void_p]),
+    "a3d_region_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                  C.c_void_p]),
+    "a3d_select_vertices": (C.c_int, [C.POINTER(SelectArgs), C.c_void_p]),
+    "a3d_session_overlay": (C.c_int, [C.POINTER(SessionOverlayArgs), C.c_void_p]),
     "a3d_measure_objects": (C.c_int, [C.POINTER(MeasureArgs), C.c_void_p]),
     "a3d_object_extents": (C.c_int, [C.POINTER(ExtentsArgs), C.c_void_p]),
     "a3d_render_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int64]),

@@ -30,6 +30,9 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
                                         "connected"): connected pieces of a labelling on the voxel lattice; a rule of ours)
     how big an object is, its boxes     a3d_measure_objects / a3d_object_extents  (measure, MeasureResult.section, frame: size,
                                         centroid, axis-aligned and oriented box, covered surface per object; a rule of ours)
+    circling what is still wrong and    a3d_region_mask / a3d_select_vertices / a3d_session_overlay  (region_mask, select, paint,
+    saying what it is                   erase, corrected: a manual label layer over the model's labels; Open3D gives the
+                                        GUI no lasso; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -296,6 +299,34 @@ class DespeckleResult:
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
+
+
+class SelectResult:
+    """What ``select()`` returns: ``selected`` uint8 [n_full] on the device (1 = the vertex is selected), and on the host
+    ``count`` (how many are), ``in_view`` (the vertices the camera sees at all: in front of it, inside the image, on the
+    kept side of the section), ``through`` and ``slack`` as used."""
+
+    __slots__ = ("selected", "count", "in_view", "through", "slack")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+class CorrectedResult:
+    """What ``corrected()`` returns: ``labels_full`` int32 [n_full] and ``colors`` fp32 [n_full, 3] on the device -- the model's
+    labels with the manual layer laid over them -- ``miou`` and ``iou_per_object`` as a ``SessionResult`` holds them (``None``
+    without ground truth), ``overridden`` (vertices the layer holds) and ``differing`` (those of them whose manual label is
+    not the model's)."""
+
+    __slots__ = ("labels_full", "colors", "miou", "iou_per_object", "overridden", "differing")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+_RENDERED = object()                            # select(section=): "the section the view was rendered under"
 
 
 def object_table(moments, origin, quantum, area_quantum=None, voxel_size=None):
@@ -675,6 +706,8 @@ class InteractiveSession:
         self._edit_err = torch.zeros(1, dtype=torch.int32, device=self.device)   # a3d_session_edit's flag
         self._guide_sum = torch.empty(V.GUIDE_SUMMARY.itemsize, dtype=torch.uint8, device=self.device)   # a3d_session_guide's summary
         self._guide_sum_host = torch.empty(V.GUIDE_SUMMARY.itemsize, dtype=torch.uint8).pin_memory()
+        self._manual_err = torch.zeros(1, dtype=torch.int32, device=self.device)   # the flag of the manual layer's own a3d_session_edit
+        self._region_sum = torch.empty(V.OVERLAY_SUMMARY.itemsize, dtype=torch.uint8, device=self.device)   # select's / overlay's summary
         self._drop_scene()
 
     # ------------------------------------------------------------------ scene
@@ -704,6 +737,7 @@ class InteractiveSession:
         self._guide_last = None                     # whatever changes the clicks or the scene.  The last guide()'s result.
         self._clicks = []                           # THE state: the ordered click list (entry i = time index i)
         self._redo = []                             # (click list before an undo, the table that renumbers the labels back)
+        self._manual = None                         # the manual layer (on uint8 [n], obj int32 [n]) on the device; None = empty
         self.click_idx = {"0": []}
         self.click_time_idx = {"0": []}
         self.click_positions = {"0": []}
@@ -1142,9 +1176,14 @@ class InteractiveSession:
         if max(n, before):
             self._cubes_dev[:max(n, before)].copy_(self._cubes_host[:max(n, before)], non_blocking=True)
         self._launch_edit(lut)
+        layer = lut is not None and self._manual is not None
+        if layer:                                       # the manual layer's ids go through the same table as the voxels' labels
+            V.session_edit(labels=self._manual[1], lut=lut, err=self._manual_err)
         self.preview()
         if lut is not None and int(self._edit_err.cpu()[0]):
             raise RuntimeError("a3d_session_edit: a voxel label outside 0 .. 255")
+        if layer and int(self._manual_err.cpu()[0]):
+            raise RuntimeError("a3d_session_edit: a manual label outside 0 .. 255")
 
     def _remove(self, index):
         before = self._clicks
@@ -1532,6 +1571,147 @@ class InteractiveSession:
                                small_pieces=s["small_pieces"], relabelled_pieces=s["relabelled_pieces"],
                                relabelled_voxels=s["relabelled_voxels"], kept_isolated=s["kept_isolated"],
                                min_voxels=int(min_voxels), connectivity=connectivity)
+
+    # ------------------------------------------------------------------ correcting by hand
+    def region_mask(self, result, polygon=None, stroke=None, radius=None, mask=None, mode="replace"):
+        """A region of the screen of ``result`` (a ``RenderResult``) as a mask: uint8 [h, w] on the device, 1 inside
+        (``a3d_region_mask``).  ``polygon``: [k, 2] points ``(x, y)`` in pixels, 3 <= k <= 256, filled even-odd -- a lasso; it
+        may cross itself and leave the image.  ``stroke``: [k, 2] points, 1 <= k <= 256, joined by segments and widened to
+        ``radius`` > 0 pixels -- a brush; one point is a disc.  Exactly one of the two.  The centre of pixel (u, v) is the
+        position (u, v).  ``mode``: ``"replace"`` (a new mask, or ``mask`` overwritten), ``"add"`` / ``"subtract"``: the
+        region joined to / taken out of ``mask``, in place.  Any uint8 or bool tensor of that shape is as good a mask for
+        ``select``: ``ses.label_image(result) == 3`` is "everything that shows as object 3"."""
+        self._need_scene()
+        if (polygon is None) == (stroke is None):
+            raise ValueError("region_mask takes a polygon or a stroke, one of them")
+        cam = result.camera
+        shape, points = ("polygon", polygon) if stroke is None else ("stroke", stroke)
+        return V.region_mask(shape, points, cam.width, cam.height, radius, mode, mask, self.device)
+
+    def select(self, result, mask, through=False, slack=None, section=_RENDERED):
+        """The vertices the camera of ``result`` sees inside ``mask`` (uint8 or bool [h, w] on the device: ``region_mask``, or
+        any image of the caller's): a ``SelectResult`` (``a3d_select_vertices``).  A vertex is IN VIEW when it lies in front of
+        the camera, projects to a pixel of the image and lies on the kept side of every plane of ``section`` (default: the
+        section ``result`` was rendered under; ``None``: none; on a mesh too it is the vertex that is tested, and culling plays
+        no part).  It is selected when its pixel is set in the mask and -- unless ``through`` -- it lies no more than ``slack``
+        world units behind what the pixel shows (``result.t``): the visible side of the scan.  ``through=True`` selects
+        everything under the mask, whatever lies in front of it.  The default ``slack`` is the session's voxel size: a vertex
+        shares its pixel with its neighbours a voxel away, of which only the nearest is shown.  This is this project's choice
+        and is NOT tuned on real scans.  One host round trip; it changes no session state."""
+        self._need_scene()
+        if result.mesh != (self.faces is not None):
+            raise ValueError("the render belongs to another scene")
+        sec = result.section if section is _RENDERED else section
+        if sec is not None and not isinstance(sec, Section):
+            raise TypeError("section must be a Section or None")
+        slack = self.voxel_size if slack is None else float(slack)
+        if not (np.isfinite(slack) and slack >= 0.0):
+            raise ValueError("slack must be finite and >= 0")
+        if torch.is_tensor(mask) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)               # (the same bytes: 0 or 1)
+        selected, summary = V.select_vertices(self.coords_full, result.camera, mask, None if through else result.t, slack,
+                                              None if sec is None or sec.n_planes == 0 else sec.struct(),
+                                              summary=self._region_sum[:V.SELECT_SUMMARY.itemsize])
+        s = V.read_select_summary(summary.cpu().numpy())                # the one host round trip
+        return SelectResult(selected=selected, count=s["selected"], in_view=s["in_view"], through=bool(through), slack=slack)
+
+    def _selection(self, selection):
+        sel = selection.selected if isinstance(selection, SelectResult) else selection
+        n = self.coords_full.shape[0]
+        if not torch.is_tensor(sel) or sel.device != self.device or sel.dtype not in (torch.uint8, torch.bool) or tuple(sel.shape) != (n,):
+            raise ValueError(f"the selection must be a SelectResult of this scene, or a uint8 / bool tensor [{n}] on the session's device")
+        return (sel.view(torch.uint8) if sel.dtype == torch.bool else sel).contiguous()
+
+    def _edit_layer(self, selection, op, obj):
+        self._need_scene()
+        sel = self._selection(selection)
+        n = self.coords_full.shape[0]
+        if self._manual is None:
+            self._manual = (torch.zeros(n, dtype=torch.uint8, device=self.device), torch.zeros(n, dtype=torch.int32, device=self.device))
+        # The model's labels at the vertices: those of the last infer / preview, which every change of the voxels' labels
+        # refreshes (_set_clicks); there are none only while every voxel is still background.
+        model = self._labels_last if self._labels_last is not None else torch.zeros(n, dtype=torch.int32, device=self.device)
+        summary = V.session_overlay(model, *self._manual, sel, op, obj, summary=self._region_sum)[2]
+        s = V.read_overlay_summary(summary.cpu().numpy())
+        if s["err"]:
+            raise RuntimeError("a3d_session_overlay: a label outside 0 .. 255")
+        return s["changed"]
+
+    def paint(self, selection, obj):
+        """Says "these vertices belong to object ``obj``": the manual layer takes ``obj`` -- 0 (background) or the id of an object
+        that has a click; ``ValueError`` otherwise -- on every vertex of ``selection`` (a ``SelectResult``, or a uint8 / bool
+        tensor [n_full] on the device; one of another scene's length raises ``ValueError``).  The model is not run and its
+        labels are not touched: ``corrected()`` lays the layer over them.  The layer follows the click list: ``load_scene``
+        and ``reset`` clear it, and whatever renumbers the objects (``remove_click``, ``undo``, ``redo``) renumbers the paint
+        by the same table -- a removed object's paint becomes background.  Returns how many vertices' layer entry changed.
+        One host round trip."""
+        obj = int(obj)
+        if not 0 <= obj <= len(self.click_idx) - 1:
+            raise ValueError(f"object {obj}: paint takes 0 (background) or an existing object id 1 .. {len(self.click_idx) - 1}")
+        return self._edit_layer(selection, "paint", obj)
+
+    def erase(self, selection):
+        """Takes the manual layer off the vertices of ``selection``: they show the model's labels again.  Returns how many
+        vertices' layer entry changed.  One host round trip."""
+        return self._edit_layer(selection, "erase", 0)
+
+    def manual_labels(self):
+        """``(on uint8 [n_full], obj int32 [n_full])``: copies of the manual layer on the device -- ``on`` 1 where a vertex is
+        overridden, ``obj`` the object it is given (0 elsewhere).  For a caller's own history, or a file."""
+        self._need_scene()
+        n = self.coords_full.shape[0]
+        if self._manual is None:
+            return torch.zeros(n, dtype=torch.uint8, device=self.device), torch.zeros(n, dtype=torch.int32, device=self.device)
+        on, obj = self._manual                          # (an erased vertex keeps its last object in the layer: not shown here)
+        return on.clone(), torch.where(on != 0, obj, torch.zeros_like(obj))
+
+    def set_manual(self, on, obj):
+        """Makes ``(on, obj)`` -- as ``manual_labels()`` returns them; ``on`` uint8 or bool -- the manual layer.  ``obj`` is
+        looked at only where ``on`` is set and must lie in 0..255 there (``ValueError``, the layer as it was); ids are not
+        checked against the click list, as a file may be restored before its clicks.  One host round trip."""
+        self._need_scene()
+        n = self.coords_full.shape[0]
+        for name, t, kinds in (("on", on, (torch.uint8, torch.bool)), ("obj", obj, (torch.int32,))):
+            if not torch.is_tensor(t) or t.device != self.device or t.dtype not in kinds or tuple(t.shape) != (n,):
+                raise ValueError(f"{name} must be a tensor [{n}] on the session's device (on: uint8 or bool, obj: int32)")
+        new_on = (on != 0).to(torch.uint8)
+        new_obj = torch.where(on != 0, obj, torch.zeros_like(obj))      # (what is off holds 0: a later renumbering reads every entry)
+        summary = V.session_overlay(new_obj, new_on, new_obj, summary=self._region_sum)[2]     # its range check, nothing written
+        if V.read_overlay_summary(summary.cpu().numpy())["err"]:
+            raise ValueError("obj must lie in 0 .. 255 where on is set")
+        self._manual = (new_on, new_obj)
+        return self
+
+    def corrected(self):
+        """The labelling as corrected by hand: the current voxel labels -- those ``preview()`` paints -- lifted to the vertices
+        with the manual layer laid over them (``a3d_session_overlay``): a ``CorrectedResult`` with ``labels_full``, ``colors``
+        (the palette's, no click cubes), ``miou`` / ``iou_per_object`` against the relabelled ground truth when the scene has
+        one, and how many vertices the layer holds and changes.  With an empty layer ``labels_full`` is ``preview()``'s.
+        ``annotate(result, labels=r.labels_full)``, ``render(colors=r.colors)`` and ``measure(labels=r.labels_full)`` take it.
+        It changes no session state.  One host round trip."""
+        self._need_scene()
+        n = self.coords_full.shape[0]
+        model = self._launch_paint(self._labels_qv, False)[0]
+        layer = self._manual
+        if layer is None:
+            layer = (torch.zeros(n, dtype=torch.uint8, device=self.device), torch.zeros(n, dtype=torch.int32, device=self.device))
+        labels_full, colors, summary = V.session_overlay(model, *layer, colors=self.colors_full, palette=self._palette_dev,
+                                                         summary=self._region_sum)
+        have_gt = self.new_labels is not None
+        if have_gt:
+            K._launch_iou_counts([labels_full], [self.new_labels], [None], _N_IDS, self._counts[:3 * _N_IDS + 1].view(1, -1))
+        else:
+            self._counts[:3 * _N_IDS + 1].zero_()
+        packed = torch.cat([self._counts.view(torch.uint8), summary]).cpu().numpy()      # the one host round trip
+        host, s = packed[:-V.OVERLAY_SUMMARY.itemsize].view(np.int64), V.read_overlay_summary(packed[-V.OVERLAY_SUMMARY.itemsize:])
+        if s["err"] or host[3 * _N_IDS] or (int(host[3 * _N_IDS + 1]) & 0xffffffff):
+            raise RuntimeError("corrected: inverse_map or labels out of range")
+        miou, per_obj = None, None
+        if have_gt:
+            t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())
+            miou = t.tolist()
+        return CorrectedResult(labels_full=labels_full, colors=colors, miou=miou, iou_per_object=per_obj,
+                               overridden=s["overridden"], differing=s["differing"])
 
     # ------------------------------------------------------------------ how big an object is
     def _fixed_point_frame(self):

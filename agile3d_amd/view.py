@@ -689,3 +689,155 @@ def object_extents(xyz, labels, axes, extents=None, err=None):
     a.out_dev, a.err_dev = extents.data_ptr(), err.data_ptr()
     L.check(L.load().a3d_object_extents(C.byref(a), L.stream(dev)), "a3d_object_extents")
     return extents, err
+
+
+# ---- correcting by hand: a screen region, the vertices seen inside it, the manual layer ----------------------------------------
+SELECT_SUMMARY = np.dtype([("selected", "<i8"), ("in_view", "<i8"), ("flags", "<i4"), ("reserved_", "<i4")])
+OVERLAY_SUMMARY = np.dtype([("changed", "<i8"), ("overridden", "<i8"), ("differing", "<i8"), ("err", "<i4"), ("reserved_", "<i4")])
+assert C.sizeof(L.SelectSummary) == SELECT_SUMMARY.itemsize == 24
+assert C.sizeof(L.OverlaySummary) == OVERLAY_SUMMARY.itemsize == 32
+REGION_SHAPES = {"polygon": L.A3D_REGION_POLYGON, "stroke": L.A3D_REGION_STROKE}
+REGION_MODES = {"replace": L.A3D_REGION_REPLACE, "add": L.A3D_REGION_ADD, "subtract": L.A3D_REGION_SUBTRACT}
+OVERLAY_OPS = {"none": L.A3D_OVERLAY_NONE, "paint": L.A3D_OVERLAY_PAINT, "erase": L.A3D_OVERLAY_ERASE}
+SELECT_NOT_FINITE = L.A3D_SELECT_NOT_FINITE     # the bit of the select summary's flags
+OVERLAY_BAD_LABEL = 1                           # the bit of the overlay summary's error word
+
+
+def read_select_summary(host):
+    """The host copy of an ``a3d_select_summary`` (uint8 [24], or anything of those bytes) as a dict of Python ints:
+    ``selected``, ``in_view``, ``flags`` (bit ``SELECT_NOT_FINITE``)."""
+    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:SELECT_SUMMARY.itemsize].view(SELECT_SUMMARY)[0]
+    return {k: int(rec[k]) for k in ("selected", "in_view", "flags")}
+
+
+def read_overlay_summary(host):
+    """The host copy of an ``a3d_overlay_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints:
+    ``changed``, ``overridden``, ``differing``, ``err`` (bit ``OVERLAY_BAD_LABEL``)."""
+    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:OVERLAY_SUMMARY.itemsize].view(OVERLAY_SUMMARY)[0]
+    return {k: int(rec[k]) for k in ("changed", "overridden", "differing", "err")}
+
+
+def _summary(summary, nbytes, dev):
+    summary = _out("summary", summary, U8, (nbytes,), dev)
+    if summary.data_ptr() % 8:
+        raise ValueError("summary must be 8-byte aligned")
+    return summary
+
+
+def camera_rows(camera):
+    """fp32 [9] (numpy): the rows of the inverse of the matrix with columns ``du``, ``dv``, ``d00`` of the ``lib.Camera`` as
+    ``a3d_render_camera_bounds`` computes them in double (host only, no GPU), each value rounded to fp32 once -- what
+    ``select_vertices`` projects with.  ``ValueError`` for a camera the renders refuse."""
+    out = (C.c_double * 13)()
+    if L.load().a3d_render_camera_bounds(C.byref(camera), out) != 0:
+        raise ValueError("camera: a size outside 1 .. 4096, a value that is not finite, or du, dv and d00 close to one plane")
+    with np.errstate(over="ignore"):
+        return np.array(out[:9], np.float64).astype(np.float32)
+
+
+def region_mask(shape, points, width, height, radius=None, mode="replace", mask=None, device=None):
+    """``a3d_region_mask``: a screen region as uint8 [height, width] on the device, 1 inside.  ``shape``: ``"polygon"``
+    (``points`` [k, 2] with 3 <= k <= 256, even-odd; ``radius`` must be ``None``) or ``"stroke"`` (1 <= k <= 256 points joined
+    by segments, every pixel within ``radius`` > 0 of one of them).  ``points`` are host numbers ``(x, y)`` in pixels: the
+    centre of pixel (u, v) is the position (u, v).  ``mode``: ``"replace"`` writes the region into ``mask`` (allocated on
+    ``device`` when ``None``), ``"add"`` / ``"subtract"`` join it to / take it out of the caller's ``mask``, in place."""
+    if shape not in REGION_SHAPES or mode not in REGION_MODES:
+        raise ValueError(f"shape must be one of {sorted(REGION_SHAPES)} and mode one of {sorted(REGION_MODES)}")
+    pts = np.ascontiguousarray(points, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 2 or not (3 if shape == "polygon" else 1) <= len(pts) <= L.A3D_REGION_MAX_POINTS:
+        raise ValueError(f"points must be [k, 2] with k in 3 .. {L.A3D_REGION_MAX_POINTS} (a polygon) or 1 .. "
+                         f"{L.A3D_REGION_MAX_POINTS} (a stroke)")
+    if not np.isfinite(pts).all():
+        raise ValueError("points must be finite (in fp32)")
+    if shape == "polygon":
+        if radius is not None:
+            raise ValueError("radius belongs to a stroke")
+        radius = 0.0
+    else:
+        with np.errstate(over="ignore"):
+            r32 = np.float32(np.nan if radius is None else radius)
+        if not (np.isfinite(r32) and r32 > 0):
+            raise ValueError("a stroke needs a finite radius > 0 (in fp32)")
+    width, height = int(width), int(height)
+    if not (1 <= width <= L.A3D_RENDER_MAX_SIZE and 1 <= height <= L.A3D_RENDER_MAX_SIZE):
+        raise ValueError(f"width and height must lie in 1 .. {L.A3D_RENDER_MAX_SIZE}")
+    if mask is None:
+        if mode != "replace":
+            raise ValueError(f"mode {mode!r} changes a mask: mask is missing")
+        if device is None:
+            raise ValueError("device is needed to allocate the mask")
+        mask = torch.empty((height, width), dtype=U8, device=device)
+    dev = _device("mask", mask)
+    mp = _ptr("mask", mask, U8, (height, width), dev)
+    L.check(L.load().a3d_region_mask(width, height, REGION_SHAPES[shape], pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts),
+                                     float(radius), REGION_MODES[mode], mp, L.stream(dev)), "a3d_region_mask")
+    return mask
+
+
+def select_vertices(xyz, cam, mask, t=None, slack=0.0, section=None, rows=None, selected=None, summary=None):
+    """``a3d_select_vertices``: which of the vertices ``xyz`` fp32 [n, 3] the ``lib.Camera`` ``cam`` sees inside ``mask`` uint8
+    [h, w] -- ``(selected uint8 [n], summary uint8 [24])`` on the device; ``read_select_summary`` decodes the summary's host
+    copy.  ``t`` fp32 [h, w]: a render's t image; a vertex then also has to lie no more than ``slack`` >= 0 behind what its
+    pixel shows (``None``: select through everything).  ``section``: a ``lib.Section`` or ``None``; a vertex on the cut side
+    of a plane is not in view.  ``rows``: fp32 [9] as ``camera_rows(cam)`` gives them (computed when ``None``)."""
+    dev = _device("xyz", xyz)
+    h, w = cam.height, cam.width
+    a = L.SelectArgs()
+    a.xyz_dev, a.n = _ptr("xyz", xyz, F32, (None, 3), dev), xyz.shape[0]
+    a.camera = cam
+    r = camera_rows(cam) if rows is None else np.ascontiguousarray(rows, dtype=np.float32)
+    if r.shape != (9,) or not np.isfinite(r).all():
+        raise ValueError("rows must be nine finite numbers (in fp32)")
+    a.rows[:] = r.tolist()
+    with np.errstate(over="ignore"):
+        s32 = np.float32(slack)
+    if not (np.isfinite(s32) and s32 >= 0):
+        raise ValueError("slack must be finite and >= 0 (in fp32)")
+    a.slack = float(s32)
+    a.mask_dev = _ptr("mask", mask, U8, (h, w), dev)
+    a.t_dev = _ptr("t", t, F32, (h, w), dev, optional=True)
+    _section_ptr(section)                       # (a lib.Section or None)
+    if section is not None:
+        a.section = C.pointer(section)
+    selected = _out("selected", selected, U8, (a.n,), dev)
+    a.selected_dev = selected.data_ptr() if a.n else None
+    summary = _summary(summary, SELECT_SUMMARY.itemsize, dev)
+    a.summary_dev = summary.data_ptr()
+    L.check(L.load().a3d_select_vertices(C.byref(a), L.stream(dev)), "a3d_select_vertices")
+    return selected, summary
+
+
+def session_overlay(labels_in, manual_on, manual_obj, selected=None, op="none", obj=0, colors=None, palette=None,
+                    labels_out=None, colors_out=None, summary=None):
+    """``a3d_session_overlay``: the manual layer ``(manual_on uint8 [n], manual_obj int32 [n])`` -- updated IN PLACE where
+    ``selected`` uint8 [n] is not 0: ``op`` ``"paint"`` sets them to ``obj`` (0..255), ``"erase"`` clears them, ``"none"``
+    leaves the layer alone -- laid over the model's labels ``labels_in`` int32 [n].  With ``colors`` fp32 [n, 3] and ``palette``
+    fp32 [K + 1, 3] the labels and colours of the result are written (``labels_out``, ``colors_out``: the caller's or
+    allocated); without ``colors`` the call is a pure layer update and both come back ``None``.  Returns ``(labels_out,
+    colors_out, summary uint8 [32])`` on the device; ``read_overlay_summary`` decodes the summary's host copy."""
+    dev = _device("labels_in", labels_in)
+    if op not in OVERLAY_OPS:
+        raise ValueError(f"op must be one of {sorted(OVERLAY_OPS)}")
+    if int(obj) != obj or not 0 <= obj <= 255:
+        raise ValueError("obj must be an integer in 0 .. 255")
+    a = L.SessionOverlayArgs()
+    a.labels_in_dev, a.n = _ptr("labels_in", labels_in, I32, (None,), dev), labels_in.shape[0]
+    n = a.n
+    a.manual_on_dev, a.manual_obj_dev = _ptr("manual_on", manual_on, U8, (n,), dev), _ptr("manual_obj", manual_obj, I32, (n,), dev)
+    a.selected_dev = _ptr("selected", selected, U8, (n,), dev, optional=True)
+    a.op, a.obj = OVERLAY_OPS[op], int(obj)
+    if colors is not None:
+        a.colors_full_dev = _ptr("colors", colors, F32, (n, 3), dev)
+        a.palette_dev = _ptr("palette", palette, F32, (None, 3), dev)
+        a.n_palette = palette.shape[0]
+        if not 2 <= a.n_palette <= 256:
+            raise ValueError("palette must be [K + 1, 3] with 1 <= K <= 255")
+        labels_out, colors_out = _out("labels_out", labels_out, I32, (n,), dev), _out("colors_out", colors_out, F32, (n, 3), dev)
+        # (without vertices there is nothing to write: the pointers of empty tensors travel as NULL, a pure layer update)
+        a.labels_out_dev, a.colors_out_dev = (labels_out.data_ptr(), colors_out.data_ptr()) if n else (None, None)
+    elif palette is not None or labels_out is not None or colors_out is not None:
+        raise ValueError("palette, labels_out and colors_out belong to the outputs: colors is missing")
+    summary = _summary(summary, OVERLAY_SUMMARY.itemsize, dev)
+    a.summary_dev = summary.data_ptr()
+    L.check(L.load().a3d_session_overlay(C.byref(a), L.stream(dev)), "a3d_session_overlay")
+    return labels_out, colors_out, summary

@@ -1357,6 +1357,136 @@ int    a3d_render_annotate(const uint8_t* rgb_in_dev, const int32_t* label_dev, 
                            const float* border, uint8_t* rgb_out_dev, int width, int height, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Correcting a labelling by hand (csrc/session_region.hip): a region of the screen as a mask image, the vertices a camera
+ * sees inside it, and a manual label layer laid over the model's labels.  The reference's tool has no counterpart (Open3D
+ * gives it no lasso): THE RULES ARE THIS LIBRARY'S.  All arithmetic is fp32, every operation rounded on its own (no fma
+ * contraction), in the order written, divide and sqrtf correctly rounded: a numpy float32 restatement gives the same bits.
+ * Positions are in pixels as everywhere above: the centre of pixel (u, v) is the position (u, v).
+ *
+ * THE REGION MASK: mask_dev uint8 [h][w], in/out, from a shape given by k points (x, y) -- points: a HOST array fp32 [k][2],
+ * they travel by value in the kernel arguments -- and a mode.  1 <= width, height <= 4096.  Per pixel p = ((float)u, (float)v):
+ *   A3D_REGION_POLYGON, 3 <= k <= A3D_REGION_MAX_POINTS, even-odd: covered = the parity of the edges a = P[j],
+ *     b = P[(j + 1) % k] with
+ *         (a.y > p.y) != (b.y > p.y)   and   p.x < ((b.x - a.x) * (p.y - a.y)) / (b.y - a.y) + a.x
+ *     (the quotient is looked at only where the first test holds: there b.y != a.y).  Vertices may lie outside the image;
+ *     a polygon that crosses itself is valid, the parity is what it is.  An edge through a pixel's centre: the pixel is
+ *     inside when the polygon lies to its right, outside when it lies to its left (`<`); a pixel's centre on a horizontal
+ *     edge is inside when the polygon lies at larger y, outside when it lies at smaller y (`>`).  radius is not looked at.
+ *   A3D_REGION_STROKE, 1 <= k <= A3D_REGION_MAX_POINTS, radius r > 0 finite: covered iff for some segment j = 0 .. k-2
+ *     (k == 1: the one segment a = b = P[0], a disc), a = P[j], b = P[j + 1]:
+ *         e = b - a;  w = p - a;  L = e.x*e.x + e.y*e.y
+ *         h = 0 if !(L > 0), else q = (w.x*e.x + w.y*e.y) / L,  h = q < 0 ? 0 : (q > 1 ? 1 : q)
+ *         dx = w.x - h*e.x;  dy = w.y - h*e.y;  dx*dx + dy*dy <= r*r
+ *     (a repeated point is a disc as well; a NaN q, possible only from overflow, passes both comparisons and stays).
+ *   mode: A3D_REGION_REPLACE mask = covered; A3D_REGION_ADD mask |= covered; A3D_REGION_SUBTRACT mask &= !covered.  A byte
+ *   that is read counts as 1 when it is not 0; the bytes written are 0 or 1; every byte is written.
+ * A3D_ERR_INVALID with nothing launched (no GPU is needed to be refused): a point that is not finite, k outside its
+ * range, a shape or mode that is none of the above, a size outside 1..4096, a stroke's radius not finite or <= 0, points
+ * or mask_dev NULL.  No workspace, no atomic: two calls give the same bytes.
+ * ------------------------------------------------------------------------------------------ */
+#define A3D_REGION_MAX_POINTS 256
+#define A3D_REGION_POLYGON  0
+#define A3D_REGION_STROKE   1
+#define A3D_REGION_REPLACE  0
+#define A3D_REGION_ADD      1
+#define A3D_REGION_SUBTRACT 2
+int    a3d_region_mask(int width, int height, int shape, const float* points, int n_points, float radius, int mode,
+                       uint8_t* mask_dev, void* stream);
+
+/* WHICH VERTICES THE CAMERA SEES INSIDE THE MASK: one streaming pass over the n rows of xyz_dev, selected_dev uint8 [n] = 0
+ * or 1, every byte written.  rows = the inverse of the matrix with columns du, dv, d00 as a3d_render_camera_bounds computes
+ * it in double (its out[0..8]), each value rounded to fp32 ONCE by the caller: the kernel holds no matrix inverse.  Per
+ * vertex p = (px, py, pz), in this order (R0, R1, R2 = rows[0..2], rows[3..5], rows[6..8]; o = the camera's):
+ *   1. w = p - o per component;  a = (R0x*wx + R0y*wy) + R0z*wz, likewise b (R1) and c (R2).  In front iff c > 0.
+ *      x = a / c, y = b / c.
+ *   2. xr = floorf(x + 0.5f), yr = floorf(y + 0.5f).  In the image iff xr >= 0 && xr < (float)width && yr >= 0 &&
+ *      yr < (float)height (a NaN fails); only then u = (int)xr, v = (int)yr -- no float outside the image is converted.
+ *      A position exactly on x = -0.5 rounds to pixel 0, one exactly on x = width - 0.5 to pixel width: outside.
+ *   3. The vertex shows iff (nx*px + ny*py) + nz*pz >= c_k for every plane of the section: the point-cloud rule of
+ *      a3d_section, applied to the vertices of clouds and meshes alike; cull is not looked at (it is checked for its range).
+ *   4. in_view = 1, 2 and 3 all pass.
+ *   5. mask[v][u] != 0.
+ *   6. Only when t_dev is given (the VISIBLE mode): d = the unit ray of pixel (u, v) by the a3d_camera rule,
+ *      tt = (wx*dx + wy*dy) + wz*dz -- the t of a3d_pick_ray, the same formula in the same order -- and the vertex passes
+ *      iff tt - t[v][u] <= slack.  t = +inf (the pixel shows nothing) passes; a NaN fails.  With t_dev NULL (the THROUGH
+ *      mode) everything under the mask is selected, whatever lies in front of it.
+ *   7. selected[i] = 4, 5 and 6 all pass.
+ * On the image of a3d_render_points of the same rows under the same camera and section, with slack 0 and a mask of ones, every
+ * vertex the id image shows at the pixel it projects to is selected: its tt is bit for bit the t the image holds there.
+ * summary_dev (cleared by the call): the number of selected vertices, of vertices in view, and flags: bit 0
+ * (A3D_SELECT_NOT_FINITE) = some vertex has a coordinate that is not finite (it is in view nowhere).  Integer sums, reduced
+ * per workgroup, one atomic per workgroup and counter: identical from run to run.
+ * A3D_ERR_INVALID with nothing launched: a camera the renders refuse; a section the section calls refuse; slack negative
+ * or not finite; a rows value that is not finite; n < 0 or n >= 2^31; mask_dev or summary_dev NULL; n > 0 with xyz_dev or
+ * selected_dev NULL.  n == 0 is valid.  No workspace. */
+#define A3D_SELECT_NOT_FINITE 1
+typedef struct a3d_select_summary {
+  int64_t selected;
+  int64_t in_view;
+  int32_t flags;
+  int32_t reserved_;
+} a3d_select_summary;              /* 24 bytes */
+typedef struct a3d_select_args {
+  const float*   xyz_dev;           /* [n][3] */
+  int64_t        n;
+  a3d_camera     camera;
+  float          rows[9];           /* rows of [du dv d00]^-1, fp32 */
+  float          slack;             /* >= 0, world units; used only with t_dev */
+  const uint8_t* mask_dev;          /* [h][w] */
+  const float*   t_dev;             /* [h][w] a render's t image, or NULL: select through everything */
+  const a3d_section* section;       /* HOST, or NULL: none */
+  uint8_t*       selected_dev;      /* out [n] */
+  a3d_select_summary* summary_dev;
+} a3d_select_args;
+int    a3d_select_vertices(const a3d_select_args* args, void* stream);
+
+/* THE MANUAL LAYER over the model's labels: two full-resolution arrays, manual_on_dev uint8 [n] (not 0 = this vertex is
+ * overridden) and manual_obj_dev int32 [n] (the object it is given, 0..255) -- two arrays and no -1 sentinel, so that the
+ * REMAP half of a3d_session_edit renumbers manual_obj_dev as it renumbers any labels.  Per vertex i, in this order:
+ *   1. if op != A3D_OVERLAY_NONE and selected_dev is given and selected[i] != 0:
+ *        A3D_OVERLAY_PAINT: on = 1, manual_obj[i] = obj;      A3D_OVERLAY_ERASE: on = 0 (manual_obj[i] stays)
+ *      The two arrays are written only where this alters them.
+ *   2. L = on ? manual_obj[i] : labels_in[i]
+ *   3. labels_out[i] = L
+ *   4. colors_out[i] = the palette entry of L > 0 with the wrap of a3d_session_paint (L >= n_palette: entry
+ *      1 + (L - 1) % (n_palette - 1)), the vertex's own colour colors_full[i] for L == 0.  No click cubes.
+ * An L outside 0..255 sets bit 0 of the summary's err and leaves labels_out[i] and colors_out[i] unwritten.
+ * summary_dev (cleared by the call), int64 sums: changed = vertices whose layer entry step 1 altered (on flipped, or
+ * manual_obj replaced by another value while on); overridden = on after the call; differing = on && manual_obj[i] !=
+ * labels_in[i] after the call, compared as plain int32.  Integer sums, one atomic per workgroup and counter.
+ * labels_out_dev and colors_out_dev may be NULL TOGETHER: a pure layer update, steps 3 and 4 skipped (colors_full_dev and
+ * palette_dev are then not looked at).  A3D_ERR_INVALID with nothing launched: n < 0 or n >= 2^31; an op that is none of
+ * the three; obj outside 0..255; summary_dev NULL; n > 0 with labels_in_dev, manual_on_dev or manual_obj_dev NULL; one
+ * output without the other; with outputs: colors_full_dev or palette_dev NULL, n_palette outside 2..256. */
+#define A3D_OVERLAY_NONE  0
+#define A3D_OVERLAY_PAINT 1
+#define A3D_OVERLAY_ERASE 2
+typedef struct a3d_overlay_summary {
+  int64_t changed;
+  int64_t overridden;
+  int64_t differing;
+  int32_t err;                      /* bit 0 = a label outside 0..255 where it was used */
+  int32_t reserved_;
+} a3d_overlay_summary;             /* 32 bytes */
+typedef struct a3d_session_overlay_args {
+  const int32_t* labels_in_dev;     /* [n] the model's labels, lifted to the vertices */
+  int64_t        n;
+  uint8_t*       manual_on_dev;     /* in/out [n] */
+  int32_t*       manual_obj_dev;    /* in/out [n] */
+  const uint8_t* selected_dev;      /* [n] or NULL */
+  const float*   colors_full_dev;   /* [n][3] */
+  const float*   palette_dev;       /* [n_palette][3] */
+  int32_t*       labels_out_dev;    /* out [n], or NULL together with colors_out_dev */
+  float*         colors_out_dev;    /* out [n][3] */
+  a3d_overlay_summary* summary_dev;
+  int32_t        op;                /* A3D_OVERLAY_* */
+  int32_t        obj;               /* 0..255; used by A3D_OVERLAY_PAINT */
+  int32_t        n_palette;
+  int32_t        reserved_;
+} a3d_session_overlay_args;
+int    a3d_session_overlay(const a3d_session_overlay_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mask losses (first piece of SURVEY.md section 8 row f-2).
  * Replaces: SetCriterion.loss_bce / loss_dice (models/criterion.py:14-110) for ONE sample and ONE
  * prediction level: losses_dev[0] = mean_i w_i * CE(logits_i, target_i), losses_dev[1] = mean_i w_i *
