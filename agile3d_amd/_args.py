@@ -1,5 +1,5 @@
-"""The checks every marshalling module (``view.py``, ``decoder_ops.py``) makes on a tensor argument before the library is
-reached: ``ValueError`` naming the argument."""
+"""The checks every marshalling module (``view.py``, ``decoder_ops.py``, ``backward.py``) makes on a tensor argument before the
+library is reached: ``ValueError`` naming the argument."""
 from __future__ import annotations
 
 import torch
@@ -36,3 +36,32 @@ def _out(name, t, dtype, shape, dev):
         return torch.empty(shape, dtype=dtype, device=dev)
     _ptr(name, t, dtype, shape, dev)
     return t
+
+
+def _contig(name, t, shape, dev):
+    """Input ``name`` (float32 of ``shape`` on ``dev``; None: any extent) as a contiguous tensor, copied if it is not one."""
+    t = t.contiguous() if isinstance(t, torch.Tensor) else t
+    _ptr(name, t, F32, shape, dev)
+    return t
+
+
+def _vectors(dev, C_, optional=False, **named):
+    """Every named per-channel operand is a contiguous float32 [C_] on ``dev`` (``optional``: or None)."""
+    for name, t in named.items():
+        _ptr(name, t, F32, (C_,), dev, optional)
+
+
+def _row_view(name, t, rows, C_, dev, out=False, more_rows=False):
+    """Operand ``name`` as a row view the conv and BatchNorm kernels take in place (pointer + row stride): float32
+    [rows, >= C_] (``more_rows``: rows or more) on ``dev``, unit channel stride, row stride a multiple of 4 floats.  An input
+    in another layout is copied, an output (``out``) refused."""
+    sh = t.shape if isinstance(t, torch.Tensor) else ()
+    if len(sh) != 2 or t.dtype is not F32 or t.device != dev or sh[1] < C_ or (sh[0] < rows if more_rows else sh[0] != rows):
+        raise ValueError(f"{name} must be a float32 [{rows}{' or more' if more_rows else ''}, >= {C_}] tensor on {dev}, not "
+                         f"{getattr(t, 'dtype', type(t))} {list(sh)} on {getattr(t, 'device', None)}")
+    if t.stride(1) == 1 and t.stride(0) % 4 == 0:
+        return t
+    if out:
+        raise ValueError(f"{name} must have unit channel stride and a row stride of a multiple of 4 floats (it is written in "
+                         f"place), not strides {t.stride()}")
+    return t.contiguous()

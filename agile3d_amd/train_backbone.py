@@ -15,6 +15,10 @@ half is ``train_decoder.DecoderTape``, the whole iteration ``train_step.train_on
 """
 from __future__ import annotations
 
+import os
+from dataclasses import make_dataclass
+from types import SimpleNamespace
+
 import torch
 
 from . import backward as B
@@ -39,12 +43,9 @@ class _T:
         return self.g
 
 
-class _View:
-    """What the tests read off ``relu_levels``: the [n, C] rows of an activation."""
-    __slots__ = ("v",)
-
-    def __init__(self, v):
-        self.v = v
+# one conv's entry of PackedWeights: _version(conv) when the packed forward weight and the input-gradient parts
+# (backward.packed_input_grad_weights) were last written, the conv and its kind
+_Packed = make_dataclass("_Packed", ["version", "forward", "parts", "conv", "kind"])
 
 
 class PackedWeights:
@@ -58,7 +59,7 @@ class PackedWeights:
     -- one launch instead of ~230 packs plus the transposes / flips / slice copies that fed them."""
 
     def __init__(self):
-        self._c = {}             # id(param) -> [version, packed forward, input-grad parts, conv, kind]
+        self._c = {}             # id(param) -> _Packed
         self.epoch = 0
         self._table = None       # (device job table, n_jobs, n_chunks, signature)
 
@@ -73,23 +74,23 @@ class PackedWeights:
         key = id(conv.kernel)
         ver = self._version(conv)
         hit = self._c.get(key)
-        if hit is None or hit[0] != ver:
+        if hit is None or hit.version != ver:
             w = conv.kernel3().detach().contiguous()
-            hit = self._c[key] = [ver, B.pack_weight(w), B.packed_input_grad_weights(kind, w), conv, kind]
+            hit = self._c[key] = _Packed(ver, B.pack_weight(w), B.packed_input_grad_weights(kind, w), conv, kind)
             self._table = None
-        return hit[1], hit[2]
+        return hit.forward, hit.parts
 
     def _build_table(self):
         rows, chunk, sig, dev = [], 0, [], None
-        for key, (ver, wf, parts, conv, kind) in self._c.items():
-            w = conv.kernel3().detach()
+        for key, e in self._c.items():
+            w = e.conv.kernel3().detach()
             K, cin, cout = w.shape
             if not w.is_contiguous():
                 return None          # a weight the one-launch pack does not cover (strided view)
             dev = w.device
-            jobs = [(w.data_ptr(), wf.data_ptr(), K, cin, cout, cin, cout, 0, 0, 0)]
-            for c0, width, pk in parts:
-                jobs.append((w.data_ptr(), pk.data_ptr(), K, cout, width, cin, cout, 1, 1 if kind == L.OP_CONV3 else 0, c0))
+            jobs = [(w.data_ptr(), e.forward.data_ptr(), K, cin, cout, cin, cout, 0, 0, 0)]
+            for c0, width, pk in e.parts:
+                jobs.append((w.data_ptr(), pk.data_ptr(), K, cout, width, cin, cout, 1, 1 if e.kind == L.OP_CONV3 else 0, c0))
             for j in jobs:
                 rows.append(j + (chunk, 0))
                 chunk += (j[2] * j[3] * j[4] + 4095) // 4096
@@ -99,52 +100,28 @@ class PackedWeights:
         return (L.pack_job_table(rows, dev), len(rows), chunk, tuple(sig))
 
     def refresh_all(self):
-        stale = [h for h in self._c.values() if h[0] != self._version(h[3])]
-        if not stale:
+        if all(e.version == self._version(e.conv) for e in self._c.values()):
             return
-        sig = tuple((k, h[3].kernel3().data_ptr()) for k, h in self._c.items())
+        sig = tuple((k, e.conv.kernel3().data_ptr()) for k, e in self._c.items())
         if self._table is None or self._table[3] != sig:
             self._table = self._build_table()
         if self._table is None:
             return                   # get() repacks entry by entry
         tab, n_jobs, n_chunks, _ = self._table
         B.pack_weights_multi(tab, n_jobs, n_chunks)
-        for h in self._c.values():
-            h[0] = self._version(h[3])
+        for e in self._c.values():
+            e.version = self._version(e.conv)
 
 
 def packed_weights_of(model) -> PackedWeights:
-    pw = getattr(model, "_a3d_packed_train", None)
-    if pw is None:
-        pw = PackedWeights()
-        object.__setattr__(model, "_a3d_packed_train", pw)
-    return pw
-
-
-def _run_stem(scene, w, feats3, kvol):
-    """conv0p1s1 on its own (OP_STEM reads the caller-ordered features) -> [n0 + 1, 32] internal order, zero row last."""
-    lib = L.load()
-    n0 = scene.n[0]
-    bufs = (L.BufDesc * 1)(L.BufDesc(0, 32))
-    o = L.Op()
-    o.kind, o.level_in, o.cin, o.cout = L.OP_STEM, 0, 3, 32
-    o.in_buf, o.in_coff, o.out_buf, o.out_coff = L.BUF_NONE, 0, 0, 0
-    o.res_buf, o.res_coff, o.relu, o.kernel_volume = L.BUF_NONE, 0, 0, kvol
-    o.w_dev, o.scale_dev, o.shift_dev = w.data_ptr(), None, None
-    ops = (L.Op * 1)(o)
-    nbytes = lib.a3d_program_workspace_bytes(scene.handle, bufs, 1, ops, 1)
-    ws = B._workspace(nbytes, feats3.device, "stem")
-    L.check(lib.a3d_program_run(scene.handle, bufs, 1, ops, 1, L.ptr(feats3), None, 0, L.ptr(ws), nbytes, L.stream()),
-            "a3d_program_run")
-    off = lib.a3d_program_buffer_offset(scene.handle, bufs, 1, 0)
-    return ws[off:off + (n0 + 1) * 32 * 4].view(torch.float32).view(n0 + 1, 32).clone()
+    if getattr(model, "_a3d_packed_train", None) is None:
+        object.__setattr__(model, "_a3d_packed_train", PackedWeights())
+    return model._a3d_packed_train
 
 
 def _sync_bn_default():
     """SyncBN is opt-in: ``A3D_SYNC_BN=1`` (or ``BackboneTape(..., sync_bn=True)``) and an initialised process group of
     more than one rank.  Off, every rank normalises over its own scenes (what plain DDP does)."""
-    import os
-
     import torch.distributed as dist
     return os.environ.get("A3D_SYNC_BN", "0") == "1" and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
 
@@ -156,7 +133,6 @@ def _wgrad_stream(device):
     """The stream the weight-gradient kernels of the backward pass run on (one per device): a unit's weight gradient and its
     input gradient both depend only on d(raw), so they run side by side -- k_wgrad's waves wait for gathered rows half of
     the time (0.42-0.5 of the matrix peak), the input-gradient conv's workgroups fill in.  A3D_WGRAD_STREAM=0: one stream."""
-    import os
     if os.environ.get("A3D_WGRAD_STREAM", "1") == "0":
         return None
     key = str(device)
@@ -173,7 +149,6 @@ class BackboneTape:
     cat / copy on the tape.  ``sync_bn`` keeps the layer-at-a-time BatchNorm."""
 
     def __init__(self, model, scene, feats3: torch.Tensor, sync_bn=None):
-        import os
         if not feats3.is_cuda:
             raise RuntimeError("BackboneTape runs on the GPU only")
         self.model, self.scene = model, scene
@@ -211,6 +186,53 @@ class BackboneTape:
     def _new(self, level, C_):
         return torch.empty((self.scene.n[level] + 1, C_), dtype=torch.float32, device=self.feats3.device)
 
+    def _bn_forward(self, b, x, res, relu, out):
+        """BatchNorm on batch statistics of x [n, C] (+ res)(ReLU) as a layer of its own, over the rows of all ranks with
+        ``sync_bn``, into the view ``out`` [n + 1, C] (its zero row included) -> (mean, rstd, global row count or None)."""
+        fn = B.bn_sync_forward if self.sync_bn else B.bn_train_forward
+        y, *stats = fn(x, b.weight.detach(), b.bias.detach(), b.eps, res, relu, b.running_mean, b.running_var, b.momentum,
+                       zero_row=True)
+        out.copy_(y)
+        return tuple(stats) if self.sync_bn else (*stats, None)
+
+    def _bn_backward(self, gamma, x, y, g, stats, relu, dx, dres):
+        """Backward of ``_bn_forward`` (``stats`` from it) into dx [n + 1, C] and, unless None, dres -> (dgamma, dbeta)."""
+        mean, rstd, n_glob = stats
+        if not self.sync_bn:
+            return B.bn_train_backward_into(x, y, g, gamma, mean, rstd, relu, dx, dres)
+        n = x.shape[0]
+        d, dg, db, dr = B.bn_sync_backward(x, y[:n], g[:n], gamma, mean, rstd, n_glob, relu, dres is not None, zero_row=True)
+        dx.copy_(d)
+        if dres is not None:
+            dres.copy_(dr)
+        return dg, db
+
+    def _conv_backward(self, kind, x: _T, conv, wb, dy, side):
+        """The conv half of a backward step for y = conv(x) with dL/dy = ``dy`` [n_out + 1, cout]: the weight gradient (on the
+        stream ``side``, None: this one), then the input gradient written / accumulated into the input node's buffer."""
+        sc = self.scene
+        K, cin, cout = conv.kernel3().shape
+        n_in, n_out = sc.n[x.level], sc.n[B.level_out(kind, x.level)]
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream())           # dy is complete
+            with torch.cuda.stream(side):
+                dw = B.conv_weight_grad(sc, kind, x.level, x.v[:n_in], dy[:n_out])
+            dy.record_stream(side)                                  # its memory is not handed out again before the kernel is done
+            self._side_used = True
+        else:
+            dw = B.conv_weight_grad(sc, kind, x.level, x.v[:n_in], dy[:n_out])
+        self._pgrad(conv.kernel, dw)
+        x.pending -= 1
+        if x.pending == 0 and x.bn is not None and len(wb) == 1:
+            # this conv completes dL/dx and x is the output of a conv + BatchNorm unit: mask + BatchNorm-backward sums in
+            # this launch's epilogue (a3d_conv_dgrad_bn)
+            xr, xm, xs, xrelu = x.bn
+            x.sums = B.conv_dgrad_bn(sc, kind, x.level, wb[0], dy, cout, x.grad_buffer(), x.ginit, x.v, xr, xm, xs, xrelu,
+                                     state=self.state)
+        else:
+            B.conv_input_grad_into(sc, kind, x.level, wb, dy, cin, cout, x.grad_buffer(), acc=x.ginit, state=self.state)
+        x.ginit = True
+
     def _conv_bn(self, kind, x: _T, conv, norm, res: _T | None = None, relu=True, out=None) -> _T:
         """conv -> BatchNorm on batch statistics (+ res)(ReLU): one unit of res16unet.py:222-295 / resnet_block.py:48-64.
         ``out``: the [n_out + 1, cout] view the result is written to (a slice of a concatenation's buffer)."""
@@ -219,34 +241,27 @@ class BackboneTape:
         sc, b = self.scene, norm.bn
         self._bns.append(b)
         lo = B.level_out(kind, x.level)
-        n_in, n_out = sc.n[x.level], sc.n[lo]
+        n_out = sc.n[lo]
         yv = out if out is not None else self._new(lo, cout)
-        gamma, beta = b.weight.detach(), b.bias.detach()
-        n_glob = None
+        gamma = b.weight.detach()
         if self.fused_bn:
-            raw, mean, rstd = B.conv_bn_train_forward(sc, kind, x.level, wf, x.v, cin, cout, gamma, beta, b.eps,
-                                                      res.v if res is not None else None, relu, yv, b.running_mean,
-                                                      b.running_var, b.momentum, state=self.state)
+            raw, *stats = B.conv_bn_train_forward(sc, kind, x.level, wf, x.v, cin, cout, gamma, b.bias.detach(), b.eps,
+                                                  res.v if res is not None else None, relu, yv, b.running_mean,
+                                                  b.running_var, b.momentum, state=self.state)
+            stats.append(None)
         else:
             rawz = self._new(lo, cout)
             B.conv_apply_acc(sc, kind, x.level, wf, x.v, cin, cout, rawz, zero_row=False, state=self.state)
             raw = rawz[:n_out]
-            rv = res.v[:n_out] if res is not None else None
-            if self.sync_bn:
-                v, mean, rstd, n_glob = B.bn_sync_forward(raw, gamma, beta, b.eps, rv, relu, b.running_mean, b.running_var,
-                                                          b.momentum, zero_row=True)
-            else:
-                v, mean, rstd = B.bn_train_forward(raw, gamma, beta, b.eps, rv, relu, b.running_mean, b.running_var,
-                                                   b.momentum, zero_row=True)
-            yv.copy_(v)
+            stats = self._bn_forward(b, raw, res.v[:n_out] if res is not None else None, relu, yv)
         y = _T(yv, lo)
         if self.fused_bn and self.fuse_bwd:
-            y.bn = (raw, mean, rstd, relu)
+            y.bn = (raw, stats[0], stats[1], relu)
         x.pending += 1
         if res is not None:
             res.pending += 1
         if relu:
-            self.relu_levels.append((lo, _View(yv[:n_out])))   # forward order of the ReLUs (tests read the 0/1 masks)
+            self.relu_levels.append((lo, SimpleNamespace(v=yv[:n_out])))   # forward order of the ReLUs (tests read the 0/1 masks)
 
         def back():
             # BatchNorm: g = dy (y > 0) -> d(raw) (with its zero row: the input-gradient conv gathers it), d(res) = g
@@ -264,41 +279,15 @@ class BackboneTape:
             if y.sums is not None:
                 # the last contribution to dL/dy was an input-gradient conv that masked it (g) and summed g, g xhat in its
                 # epilogue: no pass over dy / y / raw for the sums, and d(res) = g IS the buffer (no copy)
-                dg, db = B.bn_backward_from_sums(raw, y.g, gamma, mean, rstd, y.sums, draw)
+                dg, db = B.bn_backward_from_sums(raw, y.g, gamma, stats[0], stats[1], y.sums, draw)
                 if res is not None:
                     res.g = y.g
-            elif self.sync_bn:
-                dx, dg, db, dr = B.bn_sync_backward(raw, yv[:n_out], y.g[:n_out], gamma, mean, rstd, n_glob, relu,
-                                                    res is not None, zero_row=True)
-                draw.copy_(dx)
-                if dres is not None:
-                    dres.copy_(dr)
             else:
-                dg, db = B.bn_train_backward_into(raw, yv, y.g, gamma, mean, rstd, relu, draw, dres)
+                dg, db = self._bn_backward(gamma, raw, yv, y.g, stats, relu, draw, dres)
             self._pgrad(b.weight, dg)
             self._pgrad(b.bias, db)
             y.g = None
-            # conv: weight gradient, then the input gradient written / accumulated into the input node's buffer
-            side = self.wgrad_stream
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream())           # d(raw) is complete
-                with torch.cuda.stream(side):
-                    dw = B.conv_weight_grad(sc, kind, x.level, x.v[:n_in], draw[:n_out])
-                draw.record_stream(side)                                # its memory is not handed out again before the kernel is done
-                self._side_used = True
-            else:
-                dw = B.conv_weight_grad(sc, kind, x.level, x.v[:n_in], draw[:n_out])
-            self._pgrad(conv.kernel, dw)
-            x.pending -= 1
-            if x.pending == 0 and x.bn is not None and len(wb) == 1:
-                # this conv completes dL/dx and x is the output of a conv + BatchNorm unit: mask + BatchNorm-backward sums in
-                # this launch's epilogue (a3d_conv_dgrad_bn)
-                xr, xm, xs, xrelu = x.bn
-                x.sums = B.conv_dgrad_bn(sc, kind, x.level, wb[0], draw, cout, x.grad_buffer(), x.ginit, x.v, xr, xm, xs, xrelu,
-                                         state=self.state)
-            else:
-                B.conv_input_grad_into(sc, kind, x.level, wb, draw, cin, cout, x.grad_buffer(), acc=x.ginit, state=self.state)
-            x.ginit = True
+            self._conv_backward(kind, x, conv, wb, draw, self.wgrad_stream)
         self.steps.append(back)
         return y
 
@@ -345,11 +334,9 @@ class BackboneTape:
         cat7 = self._new(1, P[6] + P[0])
         cat6 = self._new(2, P[5] + P[1])
         cat5 = self._new(3, P[4] + P[2])
-        stem = _T(_run_stem(sc, w0, self.feats3, w0.shape[0]), 0)
-
-        def stem_back():
-            self._pgrad(bb.conv0p1s1.kernel, B.stem_weight_grad(sc, self.feats3, stem.g[:sc.n[0]], w0.shape[0]))
-        self.steps.append(stem_back)
+        stem = _T(B.stem_forward(sc, w0, self.feats3, w0.shape[0]), 0)
+        self.steps.append(lambda: self._pgrad(bb.conv0p1s1.kernel,
+                                              B.stem_weight_grad(sc, self.feats3, stem.g[:sc.n[0]], w0.shape[0])))
         out_p1 = self._bn_only(stem, bb.bn0, cat8[:, P[7]:])
         out = self._conv_bn(L.OP_DOWN, out_p1, bb.conv1p1s2, bb.bn1)
         out_b1p2 = self._layer(bb.block1, out, cat7[:, P[6]:])
@@ -375,22 +362,9 @@ class BackboneTape:
         yh = self._new(0, cout)
         B.conv_apply_acc(sc, L.OP_LINEAR, 0, wf, out.v, cin, cout, yh, state=self.state)
         self.head_out = _T(yh, 0)
-        x_head = out
-        x_head.pending += 1
-
-        def head_back():
-            g = self.head_out.g
-            self._pgrad(head.kernel, B.conv_weight_grad(sc, L.OP_LINEAR, 0, x_head.v[:n0], g[:n0]))
-            x_head.pending -= 1
-            if x_head.pending == 0 and x_head.bn is not None and len(wb) == 1:
-                xr, xm, xs, xrelu = x_head.bn
-                x_head.sums = B.conv_dgrad_bn(sc, L.OP_LINEAR, 0, wb[0], g, cout, x_head.grad_buffer(), x_head.ginit, x_head.v,
-                                              xr, xm, xs, xrelu, state=self.state)
-            else:
-                B.conv_input_grad_into(sc, L.OP_LINEAR, 0, wb, g, cin, cout, x_head.grad_buffer(), acc=x_head.ginit,
-                                       state=self.state)
-            x_head.ginit = True
-        self.steps.append(head_back)
+        out.pending += 1
+        # (the head's weight gradient has always run on this stream, the units' run on the side stream)
+        self.steps.append(lambda: self._conv_backward(L.OP_LINEAR, out, head, wb, self.head_out.g, None))
         self.orig_row = sc.table_dev(0, L.TAB_ORIGROW)[:n0].long()
         bias = head.bias.detach().reshape(1, -1)
         pcd = torch.empty((n0, cout), dtype=torch.float32, device=yh.device)
@@ -403,25 +377,12 @@ class BackboneTape:
         self._bns.append(b)
         n = self.scene.n[x.level]
         xv = x.v[:n]
-        gamma, beta = b.weight.detach(), b.bias.detach()
-        n_glob = None
-        if self.sync_bn:
-            v, mean, rstd, n_glob = B.bn_sync_forward(xv, gamma, beta, b.eps, None, True, b.running_mean, b.running_var,
-                                                      b.momentum, zero_row=True)
-        else:
-            v, mean, rstd = B.bn_train_forward(xv, gamma, beta, b.eps, None, True, b.running_mean, b.running_var, b.momentum,
-                                               zero_row=True)
-        out.copy_(v)
+        stats = self._bn_forward(b, xv, None, True, out)
         y = _T(out, x.level)
-        self.relu_levels.append((x.level, _View(out[:n])))
+        self.relu_levels.append((x.level, SimpleNamespace(v=out[:n])))
 
         def back():
-            dx = x.grad_buffer()
-            if self.sync_bn:
-                d, dg, db, _ = B.bn_sync_backward(xv, out[:n], y.g[:n], gamma, mean, rstd, n_glob, True, False, zero_row=True)
-                dx.copy_(d)
-            else:
-                dg, db = B.bn_train_backward_into(xv, out, y.g, gamma, mean, rstd, True, dx, None)
+            dg, db = self._bn_backward(b.weight.detach(), xv, out, y.g, stats, True, x.grad_buffer(), None)
             x.ginit = True
             self._pgrad(b.weight, dg)
             self._pgrad(b.bias, db)

@@ -506,12 +506,13 @@ def test_backbone_trains_with_clip_and_adamw():
             from agile3d_amd import backward as B
             from agile3d_amd.train_backbone import packed_weights_of
             pw = packed_weights_of(model)
-            ptrs = {k: h[1].data_ptr() for k, h in pw._c.items()}
+            ptrs = {k: e.forward.data_ptr() for k, e in pw._c.items()}
             pw.refresh_all()
             assert pw._table is not None and pw._table[1] > len(pw._c) and len(pw._c) >= 40
-            for k, (ver, wf, parts, conv, kind) in pw._c.items():
+            for k, e in pw._c.items():
+                wf, parts, conv, kind = e.forward, e.parts, e.conv, e.kind
                 w = conv.kernel3().detach().contiguous()
-                assert wf.data_ptr() == ptrs[k] and ver == pw._version(conv)
+                assert wf.data_ptr() == ptrs[k] and e.version == pw._version(conv)
                 assert torch.equal(wf, B.pack_weight(w)), k
                 fresh = B.packed_input_grad_weights(kind, w)
                 assert [(a, b) for a, b, _ in fresh] == [(a, b) for a, b, _ in parts]

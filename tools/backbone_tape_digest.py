@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Digests of the training backbone tape on seeded inputs, to compare two commits: per case the sha256 of the call trace --
+the ordered list of (symbol, every argument that is not a pointer) of all library calls made by BackboneTape's forward +
+backward -- the number of calls, and the sha256 of ``tape.output``, of every gradient in name order and of the activations
+in ``relu_levels``.  Cases, all on one seeded 3000-voxel scene with seeded weights and d_output: the defaults,
+A3D_FUSE_BN_BWD=0, A3D_WGRAD_STREAM=0, a second tape on the same model after ``optim.WEIGHT_EPOCH`` moved (PackedWeights'
+one-launch ``refresh_all``), and ``sync_bn=True`` in a one-rank gloo group on a file store.  Last, the input convolution on
+its own (``backward.stem_forward``, ``train_backbone._run_stem`` before that existed) for kernel volumes 125 and 27.  Only
+BackboneTape's constructor, ``output``, ``relu_levels``, ``backward()`` and ``release()`` and setattr on the loaded library's
+symbols are used, so the same file runs on either commit:
+  python tools/backbone_tape_digest.py [--json digests.json]"""
+import argparse, ctypes, hashlib, json, os, sys, tempfile
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from agile3d_amd import backward as B
+from agile3d_amd import build_model, default_args, optim
+from agile3d_amd import lib as L
+from agile3d_amd import train_backbone as TB
+from agile3d_amd.engine import Scene
+from agile3d_amd.synthetic import make_scene
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--json", default="", help="write {case: {name: sha256}} here")
+args = ap.parse_args()
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def plain(a):
+    """A by-value argument as something with a stable repr: numbers as they are, a struct as the tuple of its fields."""
+    if isinstance(a, ctypes.Structure):
+        return tuple(plain(getattr(a, f[0])) for f in a._fields_)
+    return getattr(a, "value", a)
+
+
+lib, trace = L.load(), []
+for name, (_, argtypes) in L.SYMBOLS.items():
+    by_value = [i for i, t in enumerate(argtypes) if t is not ctypes.c_void_p and not hasattr(t, "contents")]
+    fn = getattr(lib, name)
+    setattr(lib, name, lambda *a, _fn=fn, _n=name, _v=by_value: (trace.append((_n,) + tuple(plain(a[i]) for i in _v)), _fn(*a))[1])
+
+torch.manual_seed(0)
+model = build_model(default_args()).cuda().train()
+with torch.no_grad():                                       # non-trivial BatchNorm parameters
+    for n_, p in model.named_parameters():
+        if n_.endswith("bn.weight"):
+            p.uniform_(0.5, 1.5)
+        elif n_.endswith("bn.bias"):
+            p.normal_(0, 0.2)
+state0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
+scn = make_scene(3000, seed=1)
+scene = Scene(torch.from_numpy(scn["coords"]).cuda())
+g = torch.Generator().manual_seed(2)
+rows = len(scn["coords"])
+feats3 = torch.rand(rows, 3, generator=g).cuda()
+d_output = (torch.randn(rows, 128, generator=g) / 16).cuda()
+
+digests = {}
+
+
+def run(case, env=(), sync_bn=None, restore=True):
+    """One tape (forward + backward) from the seeded state; ``restore=False`` keeps the model as the last case left it."""
+    if restore:
+        model.load_state_dict(state0)
+    old = {k: os.environ.get(k) for k, _ in env}
+    os.environ.update(dict(env))
+    del trace[:]
+    try:
+        tape = TB.BackboneTape(model, scene, feats3, sync_bn=sync_bn)
+        grads = tape.backward(d_output)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    torch.cuda.synchronize()
+    vals = {"output": tape.output, **{f"grad {k}": grads[k] for k in sorted(grads)},
+            **{f"relu[{i}] level {lvl}": node.v for i, (lvl, node) in enumerate(tape.relu_levels)}}
+    d = digests[case] = {k: sha(v) for k, v in vals.items()}
+    for part in ("output", "grad", "relu"):
+        d[f"{part}s"] = hashlib.sha256("".join(d[k] for k in vals if k.startswith(part)).encode()).hexdigest()
+    d["trace"] = hashlib.sha256(repr(trace).encode()).hexdigest()
+    d["calls"] = len(trace)
+    tape.release()
+    print(f"{case} | calls {d['calls']} | trace {d['trace'][:16]} | output {d['outputs'][:16]} | grads {d['grads'][:16]} | "
+          f"relu_levels {d['relus'][:16]}", flush=True)
+
+
+run("default")
+run("A3D_FUSE_BN_BWD=0", env=(("A3D_FUSE_BN_BWD", "0"),))
+run("A3D_WGRAD_STREAM=0", env=(("A3D_WGRAD_STREAM", "0"),))
+# the weights as an optimiser step of the library's own AdamW leaves them: written through raw pointers, WEIGHT_EPOCH bumped
+with torch.no_grad():
+    gw = torch.Generator().manual_seed(3)
+    for n_, p in model.named_parameters():
+        if n_.endswith("kernel"):
+            p.data.add_((torch.randn(p.shape, generator=gw) * 1e-3).cuda())     # (.data: torch's version counter stays put)
+optim.WEIGHT_EPOCH[0] += 1
+run("second tape after WEIGHT_EPOCH moved (refresh_all)", restore=False)
+try:
+    import torch.distributed as dist
+    store = dist.FileStore(os.path.join(tempfile.mkdtemp(), "store"), 1)
+    dist.init_process_group("gloo", store=store, rank=0, world_size=1)
+    try:
+        run("sync_bn=True, one-rank gloo group", sync_bn=True)
+    finally:
+        dist.destroy_process_group()
+except Exception as e:      # the case is then tests/test_gpu_distributed.py's alone
+    print(f"sync_bn=True, one-rank gloo group | not run: {type(e).__name__}: {e}", flush=True)
+
+stem = getattr(B, "stem_forward", None) or TB._run_stem
+for kvol in (125, 27):
+    w = (torch.randn(kvol, 3, 32, generator=torch.Generator().manual_seed(kvol)) / 6.0).cuda()
+    y = stem(scene, w, feats3, kvol)
+    torch.cuda.synchronize()
+    digests[f"stem {kvol}"] = {"values": sha(y)}
+    print(f"stem kernel volume {kvol} | shape {list(y.shape)} | sha256 {digests[f'stem {kvol}']['values']}", flush=True)
+if args.json:
+    with open(args.json, "w") as f:
+        json.dump(digests, f, indent=1)
