@@ -52,20 +52,6 @@ constexpr long long kSmallPairs = 1ll << 26;  // (wrong points) x (points) below
 constexpr int kMaxChamp = 1024;              // clusters that get a lower bound (phase B); further ones are not pruned
 constexpr int kChampSplit = 8;
 
-// ---- argmax over the 1+K mask logits of every point (first maximum wins, like torch.argmax) ------
-__global__ void k_argmax_labels(const float* __restrict__ logits, int64_t n, int C, int32_t* __restrict__ pred) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* r = logits + i * C;
-  float best = r[0];
-  int arg = 0;
-  for (int c = 1; c < C; ++c) {
-    const float v = r[c];
-    if (v > best) { best = v; arg = c; }
-  }
-  pred[i] = arg;
-}
-
 struct ClickList {
   int n;
   int row[A3D_MAX_CLICKS];
@@ -77,7 +63,8 @@ __global__ void k_click_overwrite(ClickList cl, int64_t n, int32_t* __restrict__
     if (cl.row[i] >= 0 && cl.row[i] < n) pred[cl.row[i]] = cl.obj[i];
 }
 
-// ---- the same two kernels for all samples of a round (blockIdx.y = sample; the per-sample pointers travel by value) ----
+// ---- argmax over the 1+K mask logits of every point (first maximum wins, like torch.argmax), for all samples of a round:
+// blockIdx.y = sample, the per-sample pointers travel by value (a3d_argmax_labels is a table of one) ----
 struct ArgmaxBatch {
   const float* logits[A3D_MAX_ROUND_SAMPLES];
   int32_t* pred[A3D_MAX_ROUND_SAMPLES];
@@ -110,15 +97,28 @@ __global__ void k_click_overwrite_b(const ArgmaxBatch b, const int32_t* __restri
 }
 
 // ---- IoU counts: counts[0][id] = |pred==id & label==id|, [1][id] = |pred==id|, [2][id] = |label==id| ----
-__global__ void k_iou_counts(const int32_t* __restrict__ pred, const int64_t* __restrict__ inverse_map,
-                             const int32_t* __restrict__ labels, int64_t n_full, int64_t n_pred, int n_ids,
-                             unsigned long long* __restrict__ counts, int* __restrict__ err) {
+struct IouBatch {
+  const int32_t* pred[A3D_MAX_ROUND_SAMPLES];
+  const int64_t* inv[A3D_MAX_ROUND_SAMPLES];
+  const int32_t* lab[A3D_MAX_ROUND_SAMPLES];
+  long long n_full[A3D_MAX_ROUND_SAMPLES];
+  long long n_pred[A3D_MAX_ROUND_SAMPLES];
+};
+// one per-workgroup histogram per sample (blockIdx.y), merged into the sample's counts [3][n_ids] + error slot
+__global__ void k_iou_counts_b(const IouBatch b, int n_ids, unsigned long long* __restrict__ counts_all) {
   __shared__ unsigned h[3 * 256];
+  const int s = blockIdx.y;
+  const int32_t* __restrict__ pred = b.pred[s];
+  const int64_t* __restrict__ inverse_map = b.inv[s];
+  const int32_t* __restrict__ labels = b.lab[s];
+  const long long n_full = b.n_full[s], n_pred = b.n_pred[s];
+  unsigned long long* counts = counts_all + (size_t)s * (3 * n_ids + 1);
+  int* err = (int*)(counts + (size_t)3 * n_ids);
   for (int i = threadIdx.x; i < 3 * 256; i += blockDim.x) h[i] = 0;
   __syncthreads();
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_full; i += stride) {
-    const int64_t src = inverse_map ? inverse_map[i] : i;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_full; i += stride) {
+    const long long src = inverse_map ? inverse_map[i] : i;
     if (src < 0 || src >= n_pred) { atomicOr(err, 1); continue; }
     const int p = pred[src], l = labels[i];
     if (p >= 0 && p < n_ids) atomicAdd(&h[256 + p], 1u);
@@ -643,15 +643,26 @@ static ClickWs carve_click(void* base, int64_t n) {
 
 using namespace a3d;
 
+// sample i of an argmax table; false: bad arguments (the entry point says so under its own name)
+static bool argmax_put(ArgmaxBatch& b, int i, const float* logits, long long n, int n_classes, int n_clicks, int32_t* pred) {
+  if (n < 0 || n_classes < 1 || n_clicks < 0 || n_clicks > A3D_MAX_CLICKS || (n && (!logits || !pred))) return false;
+  b.logits[i] = logits, b.pred[i] = pred, b.n[i] = n, b.C[i] = n_classes;
+  return true;
+}
+
+// a table of one through the batch's arg-max kernel; the clicks travel by value (no workspace, no staging copy: this is the
+// session's infer() and the single-scene latency path)
 extern "C" int a3d_argmax_labels(const float* logits_dev, int64_t n, int n_classes, const int32_t* click_row,
                                  const int32_t* click_obj, int n_clicks, int32_t* pred_dev, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (n < 0 || n_classes < 1 || n_clicks < 0 || n_clicks > A3D_MAX_CLICKS || !pred_dev || (n && !logits_dev)) {
+  ArgmaxBatch b;
+  memset(&b, 0, sizeof(b));
+  if (!pred_dev || !argmax_put(b, 0, logits_dev, n, n_classes, n_clicks, pred_dev)) {
     set_error("a3d_argmax_labels: bad arguments (n=%lld classes=%d clicks=%d)", (long long)n, n_classes, n_clicks);
     return A3D_ERR_INVALID;
   }
   if (n == 0) return A3D_OK;
-  k_argmax_labels<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(logits_dev, n, n_classes, pred_dev);
+  k_argmax_labels_b<<<dim3((unsigned)((n + 255) / 256), 1), 256, 0, st>>>(b);
   A3D_LAUNCH_CHECK();
   if (n_clicks) {
     ClickList cl;
@@ -670,66 +681,11 @@ extern "C" int a3d_argmax_labels(const float* logits_dev, int64_t n, int n_class
   return A3D_OK;
 }
 
-extern "C" int a3d_iou_counts(const int32_t* pred_dev, int64_t n_pred, const int64_t* inverse_map_dev,
-                              const int32_t* labels_dev, int64_t n_full, int n_ids, int64_t* counts_dev,
-                              void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (n_full < 0 || n_pred < 0 || n_ids < 1 || n_ids > 256 || !counts_dev) {
-    set_error("a3d_iou_counts: bad arguments (n_full=%lld n_ids=%d)", (long long)n_full, n_ids);
-    return A3D_ERR_INVALID;
-  }
-  // counts_dev: [3][n_ids] int64 followed by one int32 error flag slot (caller passes 3*n_ids+1 int64)
-  A3D_HIP_CHECK(hipMemsetAsync(counts_dev, 0, ((size_t)3 * n_ids + 1) * 8, st));
-  if (n_full == 0) return A3D_OK;
-  const int64_t want = (n_full + 1023) / 1024;
-  const unsigned grid = (unsigned)(want < 2048 ? want : 2048);
-  k_iou_counts<<<grid, 256, 0, st>>>(pred_dev, inverse_map_dev, labels_dev, n_full, n_pred, n_ids,
-                                     (unsigned long long*)counts_dev, (int*)(counts_dev + (size_t)3 * n_ids));
-  A3D_LAUNCH_CHECK();
-  return A3D_OK;
-}
-
-struct IouBatch {
-  const int32_t* pred[A3D_MAX_ROUND_SAMPLES];
-  const int64_t* inv[A3D_MAX_ROUND_SAMPLES];
-  const int32_t* lab[A3D_MAX_ROUND_SAMPLES];
-  long long n_full[A3D_MAX_ROUND_SAMPLES];
-  long long n_pred[A3D_MAX_ROUND_SAMPLES];
-};
-// k_iou_counts for sample blockIdx.y (the same per-workgroup histogram, the same atomics)
-__global__ void k_iou_counts_b(const IouBatch b, int n_ids, unsigned long long* __restrict__ counts_all) {
-  __shared__ unsigned h[3 * 256];
-  const int s = blockIdx.y;
-  const int32_t* __restrict__ pred = b.pred[s];
-  const int64_t* __restrict__ inverse_map = b.inv[s];
-  const int32_t* __restrict__ labels = b.lab[s];
-  const long long n_full = b.n_full[s], n_pred = b.n_pred[s];
-  unsigned long long* counts = counts_all + (size_t)s * (3 * n_ids + 1);
-  int* err = (int*)(counts + (size_t)3 * n_ids);
-  for (int i = threadIdx.x; i < 3 * 256; i += blockDim.x) h[i] = 0;
-  __syncthreads();
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_full; i += stride) {
-    const long long src = inverse_map ? inverse_map[i] : i;
-    if (src < 0 || src >= n_pred) { atomicOr(err, 1); continue; }
-    const int p = pred[src], l = labels[i];
-    if (p >= 0 && p < n_ids) atomicAdd(&h[256 + p], 1u);
-    if (l >= 0 && l < n_ids) {
-      atomicAdd(&h[512 + l], 1u);
-      if (p == l) atomicAdd(&h[l], 1u);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * 256; i += blockDim.x) {
-    const int id = i & 255;
-    if (id < n_ids && h[i]) atomicAdd(&counts[(size_t)(i >> 8) * n_ids + id], (unsigned long long)h[i]);
-  }
-}
-
-extern "C" int a3d_iou_counts_batch(const a3d_iou_sample* samples, int n_samples, int n_ids, int64_t* counts_all_dev, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// counts_all_dev: per sample [3][n_ids] int64 followed by one error flag slot (3 n_ids + 1 int64 a sample)
+static int iou_counts_table(const char* who, const a3d_iou_sample* samples, int n_samples, int n_ids, int64_t* counts_all_dev,
+                            hipStream_t st) {
   if (!samples || n_samples < 1 || n_samples > A3D_MAX_ROUND_SAMPLES || n_ids < 1 || n_ids > 256 || !counts_all_dev) {
-    set_error("a3d_iou_counts_batch: bad arguments (1..%d samples, 1..256 ids)", A3D_MAX_ROUND_SAMPLES);
+    set_error("%s: bad arguments (1..%d samples, 1..256 ids; n_ids=%d)", who, A3D_MAX_ROUND_SAMPLES, n_ids);
     return A3D_ERR_INVALID;
   }
   IouBatch b;
@@ -738,7 +694,7 @@ extern "C" int a3d_iou_counts_batch(const a3d_iou_sample* samples, int n_samples
   for (int i = 0; i < n_samples; ++i) {
     const a3d_iou_sample& sp = samples[i];
     if (sp.n_full < 0 || sp.n_pred < 0 || (sp.n_full > 0 && (!sp.pred_dev || !sp.labels_dev))) {
-      set_error("a3d_iou_counts_batch: sample %d: bad arguments (n_full=%lld)", i, (long long)sp.n_full);
+      set_error("%s: sample %d: bad arguments (n_full=%lld)", who, i, (long long)sp.n_full);
       return A3D_ERR_INVALID;
     }
     b.pred[i] = sp.pred_dev, b.inv[i] = sp.inverse_map_dev, b.lab[i] = sp.labels_dev;
@@ -752,6 +708,18 @@ extern "C" int a3d_iou_counts_batch(const a3d_iou_sample* samples, int n_samples
   k_iou_counts_b<<<dim3(grid, n_samples), 256, 0, st>>>(b, n_ids, (unsigned long long*)counts_all_dev);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
+}
+
+extern "C" int a3d_iou_counts(const int32_t* pred_dev, int64_t n_pred, const int64_t* inverse_map_dev,
+                              const int32_t* labels_dev, int64_t n_full, int n_ids, int64_t* counts_dev,
+                              void* stream) {
+  a3d_iou_sample one;
+  one.pred_dev = pred_dev, one.n_pred = n_pred, one.inverse_map_dev = inverse_map_dev, one.labels_dev = labels_dev, one.n_full = n_full;
+  return iou_counts_table("a3d_iou_counts", &one, 1, n_ids, counts_dev, (hipStream_t)stream);
+}
+
+extern "C" int a3d_iou_counts_batch(const a3d_iou_sample* samples, int n_samples, int n_ids, int64_t* counts_all_dev, void* stream) {
+  return iou_counts_table("a3d_iou_counts_batch", samples, n_samples, n_ids, counts_all_dev, (hipStream_t)stream);
 }
 
 extern "C" size_t a3d_argmax_labels_batch_workspace_bytes(int n_samples) {
@@ -771,13 +739,12 @@ extern "C" int a3d_argmax_labels_batch(const a3d_argmax_sample* samples, int n_s
   int total = 0;
   for (int i = 0; i < n_samples; ++i) {
     const a3d_argmax_sample& sp = samples[i];
-    if (sp.n < 0 || sp.n_classes < 1 || sp.n_clicks < 0 || sp.n_clicks > A3D_MAX_CLICKS || (sp.n && (!sp.logits_dev || !sp.pred_dev)) ||
+    if (!argmax_put(b, i, sp.logits_dev, sp.n, sp.n_classes, sp.n_clicks, sp.pred_dev) ||
         (sp.n_clicks && (!sp.click_row || !sp.click_obj))) {
       set_error("a3d_argmax_labels_batch: sample %d: bad arguments (n=%lld classes=%d clicks=%d)", i, (long long)sp.n, sp.n_classes,
                 sp.n_clicks);
       return A3D_ERR_INVALID;
     }
-    b.logits[i] = sp.logits_dev, b.pred[i] = sp.pred_dev, b.n[i] = sp.n, b.C[i] = sp.n_classes;
     b.click_off[i] = total;
     total += sp.n ? sp.n_clicks : 0;
     n_max = sp.n > n_max ? sp.n : n_max;
@@ -832,24 +799,13 @@ extern "C" int a3d_click_clusters_batch(const a3d_click_sample* samples, int n_s
     set_error("a3d_click_clusters_batch: 1..%d samples per call", kMaxClickBatch);
     return A3D_ERR_INVALID;
   }
-  static int prune = -1;   // A3D_CLICK_PRUNE=0: the plain pass over all points (A/B)
-  if (prune < 0) {
-    const char* e = getenv("A3D_CLICK_PRUNE");
-    prune = e ? atoi(e) : 1;
-  }
-  static int coarse_from = -1;   // the coarse bounding stage in front of the fine one from this many points on
-  if (coarse_from < 0) {
-    const char* e = getenv("A3D_CLICK_COARSE_FROM");
-    coarse_from = e ? atoi(e) : kCoarseFrom;
-  }
+  static const int prune = env_int("A3D_CLICK_PRUNE", 1);                        // 0: the plain pass over all points (A/B)
+  static const int coarse_from = env_int("A3D_CLICK_COARSE_FROM", kCoarseFrom);   // the coarse bounding stage in front of the fine one from this many points on
+  static const int use_order = env_int("A3D_CLICK_ORDER", 1);                    // 0: ignore the samples' spatial orders (A/B, tests)
+  static const int dbg = env_int("A3D_CLICK_DBG", 0);   // 1: the stages' row counts of every sample on stderr (synchronises: tuning only)
   ClickDev host[kMaxClickBatch];
   int64_t n_max = 0;
   bool any_plain = false, any_bounded = false, any_two = false, any_order = false, any_sampled = false;
-  static int use_order = -1;   // A3D_CLICK_ORDER=0: ignore the samples' spatial orders (A/B, tests)
-  if (use_order < 0) {
-    const char* e = getenv("A3D_CLICK_ORDER");
-    use_order = e ? atoi(e) : 1;
-  }
   for (int i = 0; i < n_samples; ++i) {
     const a3d_click_sample& sp = samples[i];
     if (sp.n <= 0 || !sp.xyz_dev || !sp.pred_dev || !sp.labels_dev || !sp.out_dev || !sp.n_out_dev || sp.max_out < 1) {
@@ -946,11 +902,6 @@ extern "C" int a3d_click_clusters_batch(const a3d_click_sample* samples, int n_s
   }
   k_cluster_list<<<dim3(1, ns), 1024, 0, st>>>(tab);
   A3D_LAUNCH_CHECK();
-  static int dbg = -1;   // A3D_CLICK_DBG=1: the stages' row counts of every sample on stderr (synchronises: tuning only)
-  if (dbg < 0) {
-    const char* e = getenv("A3D_CLICK_DBG");
-    dbg = e ? atoi(e) : 0;
-  }
   if (dbg) {
     (void)hipStreamSynchronize(st);
     for (int i = 0; i < n_samples; ++i) {

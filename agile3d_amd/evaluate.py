@@ -59,8 +59,8 @@ def Evaluate(model, data_loader, args, device, on_round=None):
                 if current:
                     logits = model.forward_mask(*backbone_out, click_idx=click_idx,
                                                 click_time_idx=click_time_idx)["pred_masks"]
-                # the samples of a batch side by side, IoU counts and error clusters behind ONE host round trip (the clusters
-                # do not depend on the IoU; their kernels overlap on side streams); clicks are picked in sample order
+                # the samples of a batch side by side, IoU counts and error clusters behind ONE host round trip; clicks are
+                # picked in sample order
                 preds = ([torch.zeros(labels[idx].shape[0], dtype=torch.int32, device=device) for idx in range(n_samples)]
                          if current == 0 else argmax_labels_batch(logits, click_idx))       # + sparse-gt update, all samples in two launches
                 ious, clusters = mean_iou_and_clusters_batch(preds, labels_full, inverse_map, labels, raw_s)

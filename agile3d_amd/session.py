@@ -55,7 +55,6 @@ Departures from the reference, on purpose:
 from __future__ import annotations
 
 import colorsys
-import ctypes
 import os
 from datetime import datetime
 
@@ -1307,6 +1306,22 @@ class InteractiveSession:
         self._colors_last, self._labels_last = colors, labels_full
         return labels_full, colors
 
+    def _launch_iou(self, labels, inverse_map):
+        """IoU counts of ``labels`` (read through ``inverse_map`` when given) against the relabelled ground truth into the head
+        of ``self._counts`` on the current stream; zeros when the scene has none."""
+        head = self._counts[:3 * _N_IDS + 1]
+        if self.new_labels is not None:
+            K.launch_iou_counts([labels], [self.new_labels], [inverse_map], _N_IDS, head.view(1, -1))
+        else:
+            head.zero_()
+
+    def _read_iou(self, host):
+        """``(miou, iou_per_object)`` from the host copy of ``self._counts``; two Nones without a ground truth."""
+        if self.new_labels is None:
+            return None, None
+        t, per_obj = K.mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())
+        return t.tolist(), per_obj
+
     def infer(self, paint_cubes=False, logits=None):
         """The arithmetic of ``get_next_click(run_model=True)``: ``forward_mask`` on the session's clicks, arg-max with the
         clicked rows keeping their object, the lift to full resolution with colours (and cubes when asked), the IoU
@@ -1325,12 +1340,7 @@ class InteractiveSession:
         logits = logits.contiguous()
         labels_qv = K.argmax_labels(logits, self.click_idx)
         labels_full, colors = self._launch_paint(labels_qv, paint_cubes)
-        have_gt = self.new_labels is not None
-        if have_gt:
-            K._launch_iou_counts([labels_qv], [self.new_labels], [self.inverse_map], _N_IDS,
-                                 self._counts[:3 * _N_IDS + 1].view(1, -1))
-        else:
-            self._counts[:3 * _N_IDS + 1].zero_()
+        self._launch_iou(labels_qv, self.inverse_map)
         mask_host = None
         try:
             self._counts_host.copy_(self._counts, non_blocking=True)
@@ -1345,10 +1355,7 @@ class InteractiveSession:
         self._labels_qv = labels_qv
         self._colors_last, self._labels_last = colors, labels_full
         self._guide_logits, self._guide_last = (logits, self.click_idx), None
-        miou, per_obj = None, None
-        if have_gt:
-            t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())
-            miou = t.tolist()
+        miou, per_obj = self._read_iou(host)
         res = SessionResult(labels_full=labels_full, colors=colors, miou=miou, iou_per_object=per_obj, num_obj=num_obj,
                             avg_clicks=round(self.num_clicks / num_obj, 1))
         if self.out_dir is not None:
@@ -1405,20 +1412,16 @@ class InteractiveSession:
                              "(call infer() first)")
         logits, click_idx = self._guide_logits
         n_ids = max(len(click_idx), logits.shape[1])
-        rows, objs = [], []
-        for key, cids in click_idx.items():          # dict order, as a3d_argmax_labels applied them in infer()
-            rows += [int(c) for c in cids]
-            objs += [int(key)] * len(cids)
+        rows, objs = K.click_lists(click_idx)        # dict order, as a3d_argmax_labels applied them in infer()
         dev = self.device
         labels, runner, margin, want, margin_full, colors, _ = V.session_guide(
             logits, rows, objs, threshold, inverse_map=self.inverse_map, colors=self.colors_full, palette=self._palette_dev,
             doubt_color=doubt_color, full_margin=full_margin, summary=self._guide_sum)
-        work, out, out_host = K._cluster_buffers(dev, labels.numel())
         search_pred, search_want, spots = labels, want, None
         if regions == "connected":
             search_pred, search_want, spots, n_spots = self._contested_spots(labels, want)
         try:
-            K._launch_clusters(search_pred, search_want, self.raw_coords_qv, work, out)
+            out, out_host = K.launch_clusters(search_pred, search_want, self.raw_coords_qv)
             self._guide_sum_host.copy_(self._guide_sum, non_blocking=True)
             out_host.copy_(out, non_blocking=True)
         finally:
@@ -1428,15 +1431,8 @@ class InteractiveSession:
             raise RuntimeError("a3d_session_guide: inverse_map out of range")
         if summary["err"] & V.GUIDE_NAN_MARGIN:
             raise RuntimeError("a3d_session_guide: the logits hold a NaN (or two infinities of one sign in a row)")
-        host = out_host.numpy()
-        rec_bytes = K.MAX_CLUSTERS * ctypes.sizeof(L.ClickCluster)
-        count = int(host[rec_bytes:rec_bytes + 4].view(np.int32)[0])
-        if count < 0:
-            raise RuntimeError("a3d_click_clusters: labels outside 0 .. 255")
-        if count > K.MAX_CLUSTERS:
-            raise RuntimeError(f"a3d_click_clusters: {count} contested regions > {K.MAX_CLUSTERS}")
-        recs = np.frombuffer(host[:count * ctypes.sizeof(L.ClickCluster)].tobytes(), dtype=K._REC)
-        clusters = [dict(zip(recs.dtype.names, t)) for t in recs.tolist()]
+        clusters = K.read_clusters(out_host.numpy(), bad_ids="a3d_click_clusters: labels outside 0 .. 255",
+                                   too_many="a3d_click_clusters: {} contested regions", whole_sample_ok=True)
         if spots is not None:                        # a cluster's `label` is its spot's pseudo id: back to the spot's two objects
             by_row = {}
             for c in clusters:
@@ -1543,7 +1539,6 @@ class InteractiveSession:
         self._need_scene()
         dev, scene, n = self.device, self._scene_handle(), self._labels_qv.numel()
         labels, rows = self._labels_qv, self._click_rows()
-        have_gt = self.new_labels is not None
         capacity = 4096
         for _ in range(2):
             ws = V.pieces_workspace(n, dev, capacity, _N_IDS)
@@ -1551,11 +1546,7 @@ class InteractiveSession:
                                       workspace=ws)[0]
             labels_qv, summary = V.absorb_pieces(scene, labels, piece_qv, ws, min_voxels, connectivity, rows, _N_IDS, capacity)
             labels_full, colors = self._launch_paint(labels_qv, paint_cubes)
-            if have_gt:
-                K._launch_iou_counts([labels_qv], [self.new_labels], [self.inverse_map], _N_IDS,
-                                     self._counts[:3 * _N_IDS + 1].view(1, -1))
-            else:
-                self._counts[:3 * _N_IDS + 1].zero_()
+            self._launch_iou(labels_qv, self.inverse_map)
             packed = torch.cat([self._counts.view(torch.uint8), summary]).cpu().numpy()      # the one host round trip
             host, s = packed[:-V.ABSORB_SUMMARY.itemsize].view(np.int64), V.read_absorb_summary(packed[-V.ABSORB_SUMMARY.itemsize:])
             if not s["err"] & V.ABSORB_OVERFLOW:
@@ -1563,10 +1554,7 @@ class InteractiveSession:
             capacity = s["small_pieces"]
         if s["err"] & V.ABSORB_BAD_LABEL or host[3 * _N_IDS] or (int(host[3 * _N_IDS + 1]) & 0xffffffff):
             raise RuntimeError("despeckle: inverse_map or labels out of range")
-        miou, per_obj = None, None
-        if have_gt:
-            t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())
-            miou = t.tolist()
+        miou, per_obj = self._read_iou(host)
         return DespeckleResult(labels_full=labels_full, colors=colors, miou=miou, iou_per_object=per_obj, labels_qv=labels_qv,
                                small_pieces=s["small_pieces"], relabelled_pieces=s["relabelled_pieces"],
                                relabelled_voxels=s["relabelled_voxels"], kept_isolated=s["kept_isolated"],
@@ -1697,19 +1685,12 @@ class InteractiveSession:
             layer = (torch.zeros(n, dtype=torch.uint8, device=self.device), torch.zeros(n, dtype=torch.int32, device=self.device))
         labels_full, colors, summary = V.session_overlay(model, *layer, colors=self.colors_full, palette=self._palette_dev,
                                                          summary=self._region_sum)
-        have_gt = self.new_labels is not None
-        if have_gt:
-            K._launch_iou_counts([labels_full], [self.new_labels], [None], _N_IDS, self._counts[:3 * _N_IDS + 1].view(1, -1))
-        else:
-            self._counts[:3 * _N_IDS + 1].zero_()
+        self._launch_iou(labels_full, None)
         packed = torch.cat([self._counts.view(torch.uint8), summary]).cpu().numpy()      # the one host round trip
         host, s = packed[:-V.OVERLAY_SUMMARY.itemsize].view(np.int64), V.read_overlay_summary(packed[-V.OVERLAY_SUMMARY.itemsize:])
         if s["err"] or host[3 * _N_IDS] or (int(host[3 * _N_IDS + 1]) & 0xffffffff):
             raise RuntimeError("corrected: inverse_map or labels out of range")
-        miou, per_obj = None, None
-        if have_gt:
-            t, per_obj = K._mean_iou_from_counts(host[:3 * _N_IDS].reshape(3, _N_IDS).copy())
-            miou = t.tolist()
+        miou, per_obj = self._read_iou(host)
         return CorrectedResult(labels_full=labels_full, colors=colors, miou=miou, iou_per_object=per_obj,
                                overridden=s["overridden"], differing=s["differing"])
 

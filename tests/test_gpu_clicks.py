@@ -92,8 +92,8 @@ def test_simulated_clicks_vs_reference(name, mode):
 
 @pytest.mark.parametrize("mode", ["eval0", "evalk", "train"])
 def test_batched_round_equals_the_per_sample_loop(mode):
-    """get_simulated_clicks_batch / mean_iou_scene_batch over all golden cases as ONE batch (error clusters on side
-    streams, one host round trip) against the per-sample calls in the same order with the same ``random`` seed:
+    """get_simulated_clicks_batch / mean_iou_scene_batch over all golden cases as ONE batch (one set of launches on the
+    caller's stream, one host round trip) against the per-sample calls in the same order with the same ``random`` seed:
     identical clicks, order, positions and IoU bits -- and therefore identical to the reference's goldens."""
     xs = [torch.from_numpy(G[f"{n}/xyz"]).cuda() for n in NAMES]
     labs = [torch.from_numpy(G[f"{n}/labels"]).cuda().long() for n in NAMES]
@@ -296,8 +296,8 @@ def test_batched_clusters_and_spatial_order(monkeypatch):
 
 
 def test_one_sync_round_equals_the_two_calls():
-    """mean_iou_and_clusters_batch (IoU counts on the caller's stream, error clusters on side streams, one host
-    synchronisation) returns what mean_iou_scene_batch and error_clusters_batch return, inverse maps included."""
+    """mean_iou_and_clusters_batch (IoU counts and error clusters on the caller's stream, one host synchronisation)
+    returns what mean_iou_scene_batch and error_clusters_batch return, inverse maps included."""
     rng = np.random.default_rng(3)
     preds, labs, labs_full, invs, xyzs = [], [], [], [], []
     for n in (1500, 4097, 2600):
@@ -471,3 +471,141 @@ def test_batched_argmax_and_iou_counts_equal_the_per_sample_calls():
     for i in range(4):
         want = pc.iou_counts(batch[i], labels[i], inv[i], n_ids=256)
         assert np.array_equal(got[i], want), i
+
+
+def test_more_than_one_chunk_equals_the_per_sample_calls():
+    """65 samples cross the 64 samples a library call takes once: argmax_labels_batch, iou_counts_batch, error_clusters_batch
+    and mean_iou_and_clusters_batch chunk and equal the per-sample calls in sample order (argmax and counts also a numpy
+    statement).  1 .. 400 points, ragged class counts, a sample without clicks, a row clicked for two objects, an inverse
+    map on one sample, a sample of 0 points in the cluster search.  Row 0 of every sample is labelled right, so no error
+    cluster covers a whole sample (that case raises by design)."""
+    rng = np.random.default_rng(5)
+    ns, with_inv, empty = 65, 7, 11
+    sizes = [1 + (37 * i) % 400 for i in range(ns)]
+    sizes[0], sizes[64] = 400, 1                                   # the largest first, the second chunk is one point
+    classes = [2 + i % 7 for i in range(ns)]
+    logits = [rng.standard_normal((n, c)).astype(np.float32) for n, c in zip(sizes, classes)]
+    clicks = [{"0": [int(rng.integers(n))], str(c - 1): [int(rng.integers(n)), n - 1]} for n, c in zip(sizes, classes)]
+    clicks[3] = {}
+    clicks[5] = {"0": [2, 9], "1": [9], "2": []}                    # row 9 twice: the last one wins
+    refs = []
+    for lg, ck in zip(logits, clicks):
+        ref = lg.argmax(-1).astype(np.int32)
+        for o, rows in ck.items():
+            ref[rows] = int(o)
+        refs.append(ref)
+    t = lambda a: torch.from_numpy(a).cuda()
+    lg_dev = [t(lg) for lg in logits]
+    preds = pc.argmax_labels_batch(lg_dev, clicks)
+    assert len(preds) == ns
+    for i in range(ns):
+        assert preds[i].dtype == torch.int32 and torch.equal(preds[i], pc.argmax_labels(lg_dev[i], clicks[i])), i
+        assert np.array_equal(preds[i].cpu().numpy(), refs[i]), i
+    assert refs[5][9] == 1
+    # IoU counts: labels at full resolution through an inverse map on one sample
+    invs = [None] * ns
+    invs[with_inv] = t(rng.integers(0, sizes[with_inv], 2 * sizes[with_inv]))
+    labels_iou = [rng.integers(0, c + 1, len(invs[i]) if invs[i] is not None else n).astype(np.int32)
+                  for i, (n, c) in enumerate(zip(sizes, classes))]
+    lab_dev = [t(l) for l in labels_iou]
+    counts = pc.iou_counts_batch(preds, lab_dev, invs)
+    assert len(counts) == ns
+    for i in range(ns):
+        assert np.array_equal(counts[i], pc.iou_counts(preds[i], lab_dev[i], invs[i])), i
+        pf = refs[i] if invs[i] is None else refs[i][invs[i].cpu().numpy()]
+        for k in range(classes[i] + 1):
+            assert (counts[i][:, k] == [((pf == k) & (labels_iou[i] == k)).sum(), (pf == k).sum(), (labels_iou[i] == k).sum()]).all()
+    # the cluster search: a third of the rows wrong, never row 0; one sample has no points
+    labels_qv, xyzs = [], []
+    for ref, c in zip(refs, classes):
+        lab = ref.copy()
+        m = rng.random(len(ref)) < 0.35
+        m[0] = False
+        lab[m] = (ref[m] + 1 + rng.integers(0, 2, m.sum())) % (c + 1)
+        labels_qv.append(t(lab))
+        xyzs.append(t(rng.uniform(0, 2, (len(ref), 3)).astype(np.float32)))
+    preds_c = list(preds)
+    preds_c[empty], labels_qv[empty], xyzs[empty] = preds[empty][:0], labels_qv[empty][:0], xyzs[empty][:0]
+    single = [pc.error_clusters(p, l, x) for p, l, x in zip(preds_c, labels_qv, xyzs)]
+    assert single[empty] == [] and single[64] == [] and sum(len(c) for c in single) > 100
+    assert pc.error_clusters_batch(preds_c, labels_qv, xyzs) == single
+    lab_c, invs_c = list(lab_dev), list(invs)
+    lab_c[empty] = lab_dev[empty][:0]
+    ious, clusters = pc.mean_iou_and_clusters_batch(preds_c, lab_c, invs_c, labels_qv, xyzs)
+    assert clusters == single and len(ious) == ns
+    for i in range(ns):
+        want, wper = pc.mean_iou_scene(preds_c[i], lab_c[i], invs_c[i])
+        assert ious[i][0].numpy().tobytes() == want.numpy().tobytes() and ious[i][1] == wper, i
+
+
+def test_per_sample_iou_entry_point_directly():
+    """a3d_iou_counts, which clicks.py no longer calls (iou_counts is a batch of one), through the bound library: 5000
+    predictions read by 23 000 full-resolution rows through an inverse map (test_iou_counts_through_inverse_map's data)
+    against numpy and bit-equal to iou_counts; an inverse map outside the prediction sets the error slot."""
+    from agile3d_amd import lib as L
+    lib = L.load()
+    rng = np.random.default_rng(3)
+    n, nf, n_ids = 5000, 23000, 16
+    pred = rng.integers(0, 7, n).astype(np.int32)
+    inv = rng.integers(0, n, nf)
+    lab_full = rng.integers(0, 9, nf).astype(np.int32)
+    p, l, m = torch.from_numpy(pred).cuda(), torch.from_numpy(lab_full).cuda(), torch.from_numpy(inv).cuda()
+
+    def run(inverse_map):
+        counts = torch.full((3 * n_ids + 1,), -1, dtype=torch.int64, device="cuda")
+        L.check(lib.a3d_iou_counts(p.data_ptr(), n, inverse_map.data_ptr(), l.data_ptr(), nf, n_ids, counts.data_ptr(),
+                                   L.stream(p.device)), "a3d_iou_counts")
+        return counts.cpu().numpy()
+
+    host = run(m)
+    assert host[-1] == 0
+    c = host[:-1].reshape(3, n_ids)
+    pf = pred[inv]
+    for i in range(n_ids):
+        assert c[0, i] == ((pf == i) & (lab_full == i)).sum() and c[1, i] == (pf == i).sum() and c[2, i] == (lab_full == i).sum()
+    assert np.array_equal(c, pc.iou_counts(p, l, m, n_ids))
+    assert run(m + n)[-1] != 0
+
+
+def test_spatial_order_cache_follows_the_tensor(monkeypatch):
+    """The spatial order is cached on the coordinate tensor the caller passed (20 000 points = _ORDER_FROM: below it there is
+    no order): the same tensor gives the same order and inverse objects; written in place, a new pair that is a
+    permutation and its inverse; a float64 and a non-contiguous tensor hit on their second call; the entry dies with its
+    tensor; and the clusters with the cache warm equal those without any order."""
+    import gc
+    n = pc._ORDER_FROM
+    rng = np.random.default_rng(9)
+    xyz_np = rng.uniform(0, 4, (n, 3)).astype(np.float32)
+    xyz = torch.from_numpy(xyz_np).cuda()
+    labels = (xyz_np[:, 0] // 1).astype(np.int32)
+    pred = labels.copy()
+    for _ in range(6):
+        c = xyz_np[rng.integers(n)]
+        pred[np.linalg.norm(xyz_np - c, axis=1) < rng.uniform(0.3, 1.2)] = rng.integers(0, 7)
+    p, l = torch.from_numpy(pred).cuda(), torch.from_numpy(labels).cuda()
+    assert pc._spatial_order(xyz[:n - 1]) is None
+    order, inv = pc._spatial_order(xyz)
+    again = pc._spatial_order(xyz)
+    assert again[0] is order and again[1] is inv
+    warm = pc.error_clusters_batch([p], [l], [xyz])
+    assert pc._spatial_order(xyz)[0] is order and len(warm) == 1 and len(warm[0]) >= 3
+    saved = xyz.clone()
+    xyz[:, 0] = 4.0 - xyz[:, 0]                                     # in place: the version moves, the order is stale
+    order2, inv2 = pc._spatial_order(xyz)
+    assert order2 is not order and inv2 is not inv and not torch.equal(order2, order)
+    ar = torch.arange(n, dtype=torch.int32)
+    assert torch.equal(order2.cpu().sort().values, ar) and torch.equal(inv2[order2.long()].cpu(), ar)
+    xyz.copy_(saved)
+    for make in (lambda: xyz.double(), lambda: xyz.t().contiguous().t()):
+        other = make()
+        assert other.dtype != torch.float32 or not other.is_contiguous()
+        first = pc._spatial_order(other)
+        second = pc._spatial_order(other)
+        assert second[0] is first[0] and second[1] is first[1]
+        assert pc.error_clusters_batch([p], [l], [other]) == warm
+        entries = len(pc._orders)
+        del other
+        gc.collect()
+        assert len(pc._orders) == entries - 1
+    monkeypatch.setattr(pc, "_spatial_order", lambda xyz: None)
+    assert pc.error_clusters_batch([p], [l], [xyz]) == warm
