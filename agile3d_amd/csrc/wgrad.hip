@@ -488,7 +488,7 @@ static bool wgrad_plan(int ngroups, int K, const int* counts, int cin, int cout,
   // The segment length is chosen by a model of the launch: items go to the XCD's workgroup slots in rounds (equal items
   // finish together), a slot's waves share their SIMD's matrix pipe with the other resident workgroups, every item pays a
   // fixed prologue / fold / partial write and a pass of the reduce kernel.
-  static const int tgt_env = getenv("A3D_WGRAD_SEG") ? atoi(getenv("A3D_WGRAD_SEG")) : 0;     // experiments: a fixed segment length
+  static const int tgt_env = getenv("A3D_WGRAD_SEG") ? atoi(getenv("A3D_WGRAD_SEG")) : 0;     // a fixed segment length: the edge tests rely on it (tests/test_gpu_wgrad_edges.py)
   long long total = 0;
   int cmax = 0;
   for (int k = 0; k < 27; ++k) {

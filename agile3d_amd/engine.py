@@ -61,6 +61,29 @@ class Scene:
             L.check(lib.a3d_scene_build_wgrad_lists(self.handle, L.ptr(ws), nbytes, L.stream()), "a3d_scene_build_wgrad_lists")
             self._wgrad_lists = ws
 
+    def wgrad_lists(self):
+        """The weight-gradient work lists on the host (tests / debugging; synchronises):
+        ``{(kind, level): (lists [K, stride] int32, counts [K] int32)}`` for kind in (OP_CONV3, OP_DOWN, OP_UP), level = the
+        level that owns the list (OP_UP: the FINE level, level_in - 1 of the op) -- ``lists[k, :counts[k]]`` are the ascending
+        16-position groups that have offset k.  The layout is the one wgrad_list_set (csrc/wgrad.hip) writes: the maps
+        behind one another in (kind, level) order -- 3^3 maps of the five levels, stride-2 and transposed maps of four --,
+        each [K][stride] ints with stride = ceil(ngroups / 64) * 64 and ngroups = ceil(positions / 16) (OP_DOWN: positions of
+        level + 1); the counts, one int per (map, offset) in the same order, start at byte align256(4 * ints)."""
+        self.prepare_wgrad()
+        torch.cuda.current_stream(self.workspace.device).synchronize()
+        raw = self._wgrad_lists.cpu().numpy()
+        maps, off, jobs = [], 0, 0
+        for kind in (L.OP_CONV3, L.OP_DOWN, L.OP_UP):
+            for level in range(L.A3D_NUM_LEVELS - (0 if kind == L.OP_CONV3 else 1)):
+                K = 27 if kind == L.OP_CONV3 else 8
+                npos = self.n[level + 1] if kind == L.OP_DOWN else self.n[level]
+                stride = ((npos + 15) // 16 + 63) // 64 * 64
+                maps.append((kind, level, K, stride, off, jobs))
+                off, jobs = off + K * stride, jobs + K
+        counts = raw[(4 * off + 255) // 256 * 256:][:4 * jobs].view(np.int32)
+        return {(kind, level): (raw[4 * o:4 * (o + K * stride)].view(np.int32).reshape(K, stride).copy(), counts[j:j + K].copy())
+                for kind, level, K, stride, o, j in maps}
+
     def table(self, level: int, which: int) -> np.ndarray:
         """Copy one scene table to the host (tests / debugging)."""
         lib = L.load()

@@ -81,3 +81,53 @@ class OneOp:
                                     _ptr(feats3) if feats3 is not None else None, None, 0,
                                     _ptr(self.ws), self.nbytes, _stream()), "a3d_program_run")
         torch.cuda.synchronize()
+
+
+def scratch(nbytes):
+    """Workspace that starts out as NaN patterns (0xFF bytes): a partial slot no workgroup wrote shows up in the result."""
+    return torch.full((int(nbytes),), 255, dtype=torch.uint8, device="cuda")
+
+
+def _random_coords(n, extent, seed, batches=1, negative=False):
+    rng = np.random.default_rng(seed)
+    parts = []
+    for b in range(batches):
+        pts = rng.integers(0, extent, (4 * n, 3))
+        pts = np.unique(pts, axis=0)
+        pts = pts[rng.permutation(len(pts))[:n]]
+        if negative:
+            pts = pts - extent // 2
+        parts.append(np.concatenate([np.full((len(pts), 1), b), pts], 1))
+    return np.concatenate(parts, 0).astype(np.int32)
+
+
+# adversarial input families (x = features, w = weights; both fp32):
+#   wide       every element scaled by its own power of two in 2^-24 .. 2^24: products span 2^-48 .. 2^48 inside one sum
+#   cancel     channels in pairs (x, -x) against weights (w, w (1 + u 2^-12)): the big products cancel, 2^-12 of them is left
+#   same_sign  |x|, |w|: nothing cancels, every rounding error adds up over the whole sum
+#   tiny       x ~ 2^-60, w ~ 2^40
+#   subnormal  x ~ 2^-118, w ~ 2^100: features at the bottom of the fp32 normal range, the smallest of them below it
+ERR_FAMILIES = ["wide", "cancel", "same_sign", "tiny", "subnormal"]
+
+
+def _adversarial_inputs(family, n, cin, cout, K, seed):
+    """(X [n, cin], W [K, cin, cout]) float32, deterministic."""
+    g = torch.Generator().manual_seed(seed)
+    X = torch.randn(n, cin, generator=g)
+    W = torch.randn(K, cin, cout, generator=g) / (cin * K / 2) ** 0.5
+    if family == "wide":
+        X = X * torch.exp2(torch.randint(-24, 25, X.shape, generator=g).float())
+        W = W * torch.exp2(torch.randint(-24, 25, W.shape, generator=g).float())
+    elif family == "cancel":
+        X[:, 1::2] = -X[:, 0::2]
+        u = torch.rand(K, cin // 2, cout, generator=g) * 2 - 1
+        W[:, 1::2] = W[:, 0::2] * (1 + u * 2.0 ** -12)
+    elif family == "same_sign":
+        X, W = X.abs(), W.abs()
+    elif family == "tiny":
+        X, W = X * 2.0 ** -60, W * 2.0 ** 40
+    elif family == "subnormal":
+        X, W = X * 2.0 ** -118, W * 2.0 ** 100
+    else:
+        raise ValueError(family)
+    return X.contiguous(), W.contiguous()

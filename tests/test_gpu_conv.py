@@ -7,7 +7,7 @@ import torch
 from agile3d_amd import lib as L
 from agile3d_amd.engine import Scene
 from agile3d_amd.synthetic import make_scene
-from gpu_util import OneOp, internal_to_oracle_rows, pack_weight
+from gpu_util import ERR_FAMILIES, OneOp, _adversarial_inputs, internal_to_oracle_rows, pack_weight
 from oracle import backbone as ob
 
 pytestmark = pytest.mark.gpu
@@ -404,38 +404,6 @@ ERR_SHAPES = [("conv3", 0, 32, 32), ("conv3", 1, 32, 64), ("conv3", 2, 64, 64), 
               ("conv3", 3, 64, 128), ("conv3", 2, 128, 128), ("conv3", 2, 192, 128), ("conv3", 4, 128, 256),
               ("conv3", 4, 256, 256), ("conv3", 3, 384, 256), ("down", 0, 32, 32), ("down", 2, 64, 64), ("down", 3, 128, 128),
               ("up", 4, 256, 256), ("up", 3, 256, 128), ("up", 2, 128, 96), ("up", 1, 96, 96)]
-# adversarial input families (x = features, w = weights; both fp32):
-#   wide       every element scaled by its own power of two in 2^-24 .. 2^24: products span 2^-48 .. 2^48 inside one sum
-#   cancel     channels in pairs (x, -x) against weights (w, w (1 + u 2^-12)): the big products cancel, 2^-12 of them is left
-#   same_sign  |x|, |w|: nothing cancels, every rounding error adds up over the whole sum
-#   tiny       x ~ 2^-60, w ~ 2^40
-#   subnormal  x ~ 2^-118, w ~ 2^100: features at the bottom of the fp32 normal range, the smallest of them below it
-ERR_FAMILIES = ["wide", "cancel", "same_sign", "tiny", "subnormal"]
-
-
-def _adversarial_inputs(family, n, cin, cout, K, seed):
-    """(X [n, cin], W [K, cin, cout]) float32, deterministic."""
-    g = torch.Generator().manual_seed(seed)
-    X = torch.randn(n, cin, generator=g)
-    W = torch.randn(K, cin, cout, generator=g) / (cin * K / 2) ** 0.5
-    if family == "wide":
-        X = X * torch.exp2(torch.randint(-24, 25, X.shape, generator=g).float())
-        W = W * torch.exp2(torch.randint(-24, 25, W.shape, generator=g).float())
-    elif family == "cancel":
-        X[:, 1::2] = -X[:, 0::2]
-        u = torch.rand(K, cin // 2, cout, generator=g) * 2 - 1
-        W[:, 1::2] = W[:, 0::2] * (1 + u * 2.0 ** -12)
-    elif family == "same_sign":
-        X, W = X.abs(), W.abs()
-    elif family == "tiny":
-        X, W = X * 2.0 ** -60, W * 2.0 ** 40
-    elif family == "subnormal":
-        X, W = X * 2.0 ** -118, W * 2.0 ** 100
-    else:
-        raise ValueError(family)
-    return X.contiguous(), W.contiguous()
-
-
 def _geometry(shape, sc, lv):
     """(rows in, rows out, level out, kernel volume, oracle kernel map)"""
     kind, level, cin, cout = shape

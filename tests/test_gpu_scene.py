@@ -6,23 +6,10 @@ import torch
 from agile3d_amd import lib as L
 from agile3d_amd.engine import Scene
 from agile3d_amd.synthetic import make_scene
-from gpu_util import internal_to_oracle_rows, key4
+from gpu_util import _random_coords, internal_to_oracle_rows, key4
 from oracle import backbone as ob
 
 pytestmark = pytest.mark.gpu
-
-
-def _random_coords(n, extent, seed, batches=1, negative=False):
-    rng = np.random.default_rng(seed)
-    parts = []
-    for b in range(batches):
-        pts = rng.integers(0, extent, (4 * n, 3))
-        pts = np.unique(pts, axis=0)
-        pts = pts[rng.permutation(len(pts))[:n]]
-        if negative:
-            pts = pts - extent // 2
-        parts.append(np.concatenate([np.full((len(pts), 1), b), pts], 1))
-    return np.concatenate(parts, 0).astype(np.int32)
 
 
 CASES = {
