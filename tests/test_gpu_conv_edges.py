@@ -1,0 +1,433 @@
+"""-m gpu: the forward kernels of the sparse convolutions (csrc/spconv.hip: k_conv_wl, k_conv_deep, k_conv_sk, k_stem) at their
+plan and scene edges, bit for bit.
+
+plan_conv picks, from the output row count, K, cin and cout alone, one of three kernel families and a dozen geometries; of
+the 64 + 53 plan classes reachable on the scenes below (small-level kernel on + off) the tolerance tests of test_gpu_conv.py
+and the conv-apply tests of the training path leave 30 + 20 without any comparison (profiles/conv_forward_edge_classes.txt).  The cases here are
+chosen by plan class (conv_edge_cases.py; test_conv_plan_classes.py holds the table against the planner on the CPU): scenes of
+1, 37, 63 / 64 / 65 and 128 voxels, two touching batch samples, a level 0 on the hash table, the 8191 / 8192-row switch of
+the 128-column build, 1024 / 1025 / 2047 / 2048 level-0 groups, and 20 k voxels for the clamped share counts, the 2^3 layers
+without hand-offs and k_conv_deep with two workgroups per CU.
+
+Reference: the pairs of offset k come from the CPU oracle's kernel maps (oracle.backbone.SparseLevels), remapped to the
+library's internal rows by coordinates; ref = sum_k index_add(out rows_k, x[in rows_k] @ W[k]) in float64 (gathers and matmuls
+on the device), then the epilogue in float64.
+
+EXACT arithmetic: x, W, residual, shift, the projection's input and weight, the head's weight and bias are integers in
+[-3, 3], stem colours in {0..3}, BatchNorm scales in {-2, -1, 1, 2}.  Every product and every partial sum, in any order, is an
+integer of magnitude <= 27 * 384 * 9 + 384 * 9 = 96768, doubled by the scale, plus 6: far below 2^24.  The fused-head cases
+use scale 1 and cin <= 128, so the head's sums stay <= 96 * 3 * (27 * 128 * 9 + 6) + 3 < 2^24.  fp32 is therefore exact
+whatever the partition, the hand-off order or the MFMA association, and every assertion is BIT EQUALITY with the float64
+reference cast to fp32: one dropped, doubled or misplaced (row, offset, channel-chunk) stage, one partial slab added twice or
+not at all, one tile a clamped share skips changes an integer.  No tolerance appears in this module.
+
+Poison: outputs start as NaN, every workspace as 0xFF bytes (only the hand-off state is zeroed: by the library, or by the
+test where it owns the block -- then its failure word must still be 0 afterwards); the zero row must come out 0 and the
+columns beside an op's slice must still be NaN.
+"""
+import pytest
+import torch
+
+import conv_edge_cases as E
+from agile3d_amd import lib as L
+from agile3d_amd.lib import ptr as _ptr, stream as _stream
+from conv_kit import _ints, scratch, world
+from gpu_util import pack_weight
+
+pytestmark = pytest.mark.gpu
+
+NAN = float("nan")
+KINDS = {"conv3": L.OP_CONV3, "down": L.OP_DOWN, "up": L.OP_UP}
+
+
+@pytest.fixture(params=[1, 0], ids=["deep", "streamk"])
+def mode(request):
+    """a3d_conv_deep_mode: with the small-level kernel (k_conv_deep takes what its cost model allows) and without."""
+    lib = L.load()
+    before = lib.a3d_conv_deep_mode(request.param)
+    yield request.param
+    lib.a3d_conv_deep_mode(before)
+
+
+def _set_mode(m):
+    return L.load().a3d_conv_deep_mode(m)
+
+
+def _world(name):
+    w = world(name)
+    want = E.SCENE_LEVELS[name]
+    assert w.sc.n[:len(want)] == want and [w.lv.n(i) for i in range(len(want))] == want, (name, w.sc.n)
+    if name == "outlier":
+        assert w.sc.grid_dims is None                                 # level 0 on the hash table
+    return w
+
+
+def _rows(w, kind, level_in):
+    return w.sc.n[level_in], w.sc.n[E.level_out(kind, level_in)]
+
+
+def _conv_ref(pairs, x64, w64, n_out):
+    """sum_k index_add(out rows_k, x[in rows_k] @ W[k]) in float64 on the device"""
+    ref = torch.zeros(n_out, w64.shape[2], dtype=torch.float64, device="cuda")
+    for k, (ri, ro) in enumerate(pairs):
+        if len(ri):
+            ref.index_add_(0, ro, x64[ri] @ w64[k])
+    return ref
+
+
+def _assert_bits(got, ref64, where):
+    """got (fp32) == the float64 reference cast to fp32, element for element"""
+    ref = ref64.float()
+    assert (ref.double() == ref64).all(), (where, "the reference left the exact range")
+    if torch.equal(got, ref):
+        return
+    bad = got != ref                                # NaN differs from everything
+    r, c = (int(v) for v in bad.nonzero()[0])
+    rows = bad.any(1).nonzero().flatten()
+    pytest.fail(f"{where}: out[{r}, {c}] = {got[r, c].item()!r}, expected {ref[r, c].item()!r}; {int(bad.sum())} elements differ "
+                f"in {len(rows)} rows ({rows[:8].tolist()} ...), columns {bad.any(0).nonzero().flatten()[:8].tolist()} ...")
+
+
+def _with_zero_row(t):
+    return torch.cat([t, torch.zeros(1, t.shape[1], device="cuda")])
+
+
+def _conv_apply(sc, kind, level_in, x, cin, cout, wp, n_out):
+    """a3d_conv_apply on a NaN-filled y and a 0xFF-filled workspace (the library zeroes the hand-off state)"""
+    lib = L.load()
+    nbytes = lib.a3d_conv_apply_workspace_bytes(sc.handle, KINDS[kind], level_in, cin, cout)
+    assert nbytes, lib.a3d_last_error().decode()
+    ws = scratch(nbytes)
+    y = torch.full((n_out + 1, cout), NAN, device="cuda")
+    L.check(lib.a3d_conv_apply(sc.handle, KINDS[kind], level_in, _ptr(x), x.stride(0), cin, _ptr(wp), cout, _ptr(y), cout, 1, _ptr(ws),
+                               nbytes, _stream()), "a3d_conv_apply")
+    return y
+
+
+def _profiled(run):
+    """the spconv profile entries of the launches inside run()"""
+    lib = L.load()
+    lib.a3d_profile_read(None, 0)
+    lib.a3d_profile_enable(1)
+    try:
+        out = run()
+        torch.cuda.synchronize()
+    finally:
+        lib.a3d_profile_enable(0)
+    buf = (L.ProfEntry * 64)()
+    n = lib.a3d_profile_read(buf, 64)
+    assert n >= 0, lib.a3d_last_error().decode()
+    return out, [(buf[i].bn, buf[i].ksplit, buf[i].kernel_volume & 255, buf[i].cin, buf[i].cout, buf[i].n_out) for i in range(n)
+                 if buf[i].id == 0]
+
+
+def _assert_ran_its_class(entries, cls, K, cin, cout, n_out, where):
+    """the profile entry carries the small-level kernel (column field >= 1000) or not, the column width, the stage width"""
+    assert len(entries) == 1, (where, entries)
+    if cls[0] == "wl":
+        want = (cout, 0)                                             # stage width 0: k_conv_wl
+    elif cls[0] == "deep":
+        want = (1000 + cls[2], cls[3])
+    else:
+        want = (cls[2], cls[3])
+    assert entries[0] == want + (K, cin, cout, n_out), (where, cls, entries[0])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 1. small scenes: every kind, level and width pair
+# ----------------------------------------------------------------------------------------------------------------------
+_SMALL = [(s, k, l) for s in E.SMALL_SCENES for k, l in E.KIND_LEVELS]
+
+
+@pytest.mark.parametrize("name,kind,level_in", _SMALL, ids=[f"{s}-{k}-L{l}" for s, k, l in _SMALL])
+def test_small_scenes_every_width_pair(mode, name, kind, level_in):
+    """a3d_conv_apply over the 7 x 5 width pairs of test_gpu_conv.py.  Levels of 1 .. 1800 rows: fewer cost units than the
+    plan has workgroups (one voxel, 384 -> 32 with the small-level kernel off: 13 workgroups for 7 units), fewer rows than a
+    64-row tile, exactly one and two tiles (no tail), a line whose maps lack 24 of 27 offsets, two touching samples, the hash
+    path.  One x / W at the widest pair; the references of the seven input widths are running sums over channel ranges."""
+    w = _world(name)
+    n_in, n_out = _rows(w, kind, level_in)
+    pairs = w.pairs(kind, level_in)
+    K = E.KVOL[kind]
+    assert len(pairs) == K
+    X = _with_zero_row(_ints((n_in, E.WIDTHS_IN[-1]), -3, 3, name, kind, level_in, "x"))
+    W = _ints((K, E.WIDTHS_IN[-1], E.WIDTHS_OUT[-1]), -3, 3, name, kind, level_in, "w")
+    X64, W64 = X.double(), W.double()
+    refs, acc = {}, 0
+    for a, b in zip([0] + E.WIDTHS_IN, E.WIDTHS_IN):
+        acc = acc + _conv_ref(pairs, X64[:, a:b], W64[:, a:b], n_out)
+        refs[b] = acc
+    for cin in E.WIDTHS_IN:
+        x = X[:, :cin].contiguous()
+        for cout in E.WIDTHS_OUT:
+            y = _conv_apply(w.sc, kind, level_in, x, cin, cout, pack_weight(W[:, :cin, :cout]), n_out)
+            where = f"scene {name} {kind} level {level_in} {cin}->{cout} mode {mode}"
+            _assert_bits(y[:n_out], refs[cin][:, :cout], where)
+            assert (y[n_out] == 0).all(), (where, "zero row")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 2. large scenes: one row per plan class
+# ----------------------------------------------------------------------------------------------------------------------
+def _row_id(row):
+    name, kind, level_in, cin, cout, cin2, m = row
+    return f"{name}-{kind}-L{level_in}-{cin}-{cout}" + (f"+{cin2}" if cin2 else "") + ("-deep" if m else "-streamk")
+
+
+def _operands(w, kind, level_in, cin, cout, tag):
+    n_in, n_out = _rows(w, kind, level_in)
+    x = _with_zero_row(_ints((n_in, cin), -3, 3, w.name, kind, level_in, cin, tag, "x"))
+    W = _ints((E.KVOL[kind], cin, cout), -3, 3, w.name, kind, level_in, cin, cout, tag, "w")
+    ref = _conv_ref(w.pairs(kind, level_in), x.double(), W.double(), n_out)
+    return x, W, ref
+
+
+@pytest.mark.parametrize("row,cls", E.LARGE_CASES, ids=[_row_id(r) for r, _ in E.LARGE_CASES])
+def test_large_scene_plan_classes(row, cls):
+    """One a3d_conv_apply per row of the case table; the class next to the row is what the planner gives it
+    (test_conv_plan_classes.py), the profile entry shows the family, column width and stage width that ran."""
+    name, kind, level_in, cin, cout, cin2, m = row
+    assert cin2 == 0
+    w = _world(name)
+    n_in, n_out = _rows(w, kind, level_in)
+    x, W, ref = _operands(w, kind, level_in, cin, cout, "large")
+    wp = pack_weight(W)
+    where = f"scene {name} {kind} level {level_in} {cin}->{cout} mode {m} {cls}"
+    before = _set_mode(m)
+    try:
+        y, entries = _profiled(lambda: _conv_apply(w.sc, kind, level_in, x, cin, cout, wp, n_out))
+    finally:
+        _set_mode(before)
+    _assert_ran_its_class(entries, cls, E.KVOL[kind], cin, cout, n_out, where)
+    _assert_bits(y[:n_out], ref, where)
+    assert (y[n_out] == 0).all(), (where, "zero row")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 3. k_conv_wl at its wave / grid switches
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["conv3", "down"])
+@pytest.mark.parametrize("name", E.WL_SCENES)
+def test_conv_wl_wave_and_grid_choice(mode, name, kind):
+    """32 -> 32 at level 0.  launch_conv_wl halves its 16 waves while 256 workgroups x waves exceed twice the 16-row groups:
+    1024 and 1025 groups run 8 waves (grid 128 / 129), 2047 8 waves (grid 256), 2048 16 waves (grid 128); 1, 3 and 4 groups
+    run one workgroup of 4 waves.  (`down` counts the groups of level 1.)"""
+    w = _world(name)
+    if name.startswith("g"):
+        assert (w.sc.n[0] + 15) // 16 == int(name[1:])
+    n_in, n_out = _rows(w, kind, 0)
+    x, W, ref = _operands(w, kind, 0, 32, 32, "wl")
+    wp = pack_weight(W)
+    where = f"scene {name} {kind} level 0 32->32 mode {mode}"
+    y, entries = _profiled(lambda: _conv_apply(w.sc, kind, 0, x, 32, 32, wp, n_out))
+    _assert_ran_its_class(entries, ("wl", E.KVOL[kind]), E.KVOL[kind], 32, 32, n_out, where)
+    _assert_bits(y[:n_out], ref, where)
+    assert (y[n_out] == 0).all(), (where, "zero row")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 4. one-op programs: epilogues, fused projection, fused head, stem
+# ----------------------------------------------------------------------------------------------------------------------
+class Program:
+    """A one-op a3d_program_run whose workspace starts as 0xFF bytes: buffers [0] input, [1] output, then residual and
+    projection input where asked for; every buffer NaN until the test fills its slice."""
+
+    def __init__(self, sc, kind, level_in, cin, cout, kvol, w_dev, scale=None, shift=None, relu=False, use_res=False, in_pad=0,
+                 out_pad=0, proj_cin=0, proj_pad=0, head=None):
+        self.sc = sc
+        lo = level_in + (1 if kind == L.OP_DOWN else -1 if kind == L.OP_UP else 0)
+        self.descs = [(level_in, 4 if kind == L.OP_STEM else cin + in_pad), (lo, cout + out_pad)]
+        o = L.Op()
+        o.kind, o.level_in, o.cin, o.cout = kind, level_in, cin, cout
+        o.in_buf, o.in_coff = (L.BUF_NONE, 0) if kind == L.OP_STEM else (0, in_pad)
+        o.out_buf, o.out_coff = 1, out_pad
+        o.res_buf, o.res_coff = L.BUF_NONE, 0
+        if use_res:
+            o.res_buf = len(self.descs)
+            self.res_buf = len(self.descs)
+            self.descs.append((lo, cout))
+        o.relu, o.kernel_volume = int(relu), kvol
+        o.w_dev = w_dev.data_ptr()
+        o.scale_dev = scale.data_ptr() if scale is not None else None
+        o.shift_dev = shift.data_ptr() if shift is not None else None
+        if proj_cin:
+            o.proj_buf, o.proj_coff, o.proj_cin = len(self.descs), proj_pad, proj_cin
+            self.proj_buf = len(self.descs)
+            self.descs.append((level_in, proj_cin + proj_pad))
+        if head is not None:
+            head_w, head_bias, head_cout = head
+            o.head_w_dev, o.head_bias_dev, o.head_cout = head_w.data_ptr(), head_bias.data_ptr(), head_cout
+        self.keep = [w_dev, scale, shift, head]
+        self.bufs = (L.BufDesc * len(self.descs))(*[L.BufDesc(a, b) for a, b in self.descs])
+        self.ops = (L.Op * 1)(o)
+        lib = L.load()
+        self.nbytes = lib.a3d_program_workspace_bytes(sc.handle, self.bufs, len(self.descs), self.ops, 1)
+        assert self.nbytes > 0, lib.a3d_last_error()
+        self.ws = scratch(self.nbytes)
+
+    def buffer(self, i):
+        off = L.load().a3d_program_buffer_offset(self.sc.handle, self.bufs, len(self.descs), i)
+        level, ch = self.descs[i]
+        rows = self.sc.n[level] + 1
+        return self.ws[off:off + rows * ch * 4].view(torch.float32).view(rows, ch)
+
+    def fill(self, i, t, c0=0):
+        """buffer i: columns [c0, c0 + width) = t over the level's rows, its zero row 0 there; NaN (0xFF) elsewhere"""
+        b = self.buffer(i)
+        b[:t.shape[0], c0:c0 + t.shape[1]] = t
+        b[t.shape[0]:, c0:c0 + t.shape[1]] = 0
+
+    def run(self, feats3=None, ext=None):
+        L.check(L.load().a3d_program_run(self.sc.handle, self.bufs, len(self.descs), self.ops, 1,
+                                         _ptr(feats3) if feats3 is not None else None, _ptr(ext) if ext is not None else None,
+                                         ext.stride(0) if ext is not None else 0, _ptr(self.ws), self.nbytes, _stream()),
+                "a3d_program_run")
+        torch.cuda.synchronize()
+
+
+def _scales(cout, *seed):
+    """BatchNorm scales from {-2, -1, 1, 2}"""
+    return torch.tensor([-2.0, -1.0, 1.0, 2.0], device="cuda")[_ints((cout,), 0, 3, *seed, "scale").long()].contiguous()
+
+
+@pytest.mark.parametrize("row,cls", E.EPI_CASES, ids=[_row_id(r) for r, _ in E.EPI_CASES])
+def test_epilogue_in_a_program(row, cls):
+    """relu(conv * scale + shift + residual) through a3d_program_run, input and output as column slices at 32 of buffers 32
+    wider: every build of k_conv_sk and k_conv_deep a gathered op can get, and k_conv_wl, on a small and a large scene."""
+    name, kind, level_in, cin, cout, _, m = row
+    w = _world(name)
+    n_in, n_out = _rows(w, kind, level_in)
+    x, W, ref = _operands(w, kind, level_in, cin, cout, "epi")
+    scale, shift = _scales(cout, name, kind, cin, cout), _ints((cout,), -3, 3, name, kind, cin, cout, "shift")
+    R = _ints((n_out, cout), -3, 3, name, kind, cin, cout, "res")
+    ref = torch.relu(ref * scale.double() + shift.double() + R.double())
+    where = f"scene {name} {kind} level {level_in} {cin}->{cout} mode {m} {cls} (program, epilogue)"
+    before = _set_mode(m)
+    try:
+        op = Program(w.sc, KINDS[kind], level_in, cin, cout, E.KVOL[kind], pack_weight(W), scale, shift, relu=True, use_res=True,
+                     in_pad=32, out_pad=32)
+        op.fill(0, x[:n_in], 32)
+        op.fill(op.res_buf, R)
+        _, entries = _profiled(op.run)
+    finally:
+        _set_mode(before)
+    _assert_ran_its_class(entries, cls, E.KVOL[kind], cin, cout, n_out, where)
+    out = op.buffer(1)
+    _assert_bits(out[:n_out, 32:], ref, where)
+    assert (out[n_out, 32:] == 0).all(), (where, "zero row")
+    assert torch.isnan(out[:, :32]).all(), (where, "wrote outside its column slice")
+
+
+@pytest.mark.parametrize("row,cls", E.EPI_CASES, ids=[_row_id(r) for r, _ in E.EPI_CASES])
+def test_accumulate_in_place(row, cls):
+    """a3d_conv_apply_acc with the output as its own residual: y += conv(x) in the kernel's epilogue, y a column slice at 32
+    of a buffer 64 wider, x one at 32 of a buffer 32 wider, the hand-off state the test's own zeroed block."""
+    name, kind, level_in, cin, cout, _, m = row
+    w = _world(name)
+    lib = L.load()
+    n_in, n_out = _rows(w, kind, level_in)
+    x, W, ref = _operands(w, kind, level_in, cin, cout, "acc")
+    Y0 = _ints((n_out, cout), -3, 3, name, kind, cin, cout, "y0")
+    xw = torch.full((n_in + 1, cin + 32), NAN, device="cuda")
+    xw[:, 32:] = x
+    yw = torch.full((n_out + 1, cout + 64), NAN, device="cuda")
+    yw[:n_out, 32:32 + cout] = Y0
+    xs, ys = xw[:, 32:], yw[:, 32:32 + cout]
+    state = torch.zeros(lib.a3d_conv_state_bytes() // 4, dtype=torch.int32, device="cuda")
+    wp = pack_weight(W)
+    where = f"scene {name} {kind} level {level_in} {cin}->{cout} mode {m} {cls} (accumulate in place)"
+    before = _set_mode(m)
+    try:
+        nbytes = lib.a3d_conv_apply_workspace_bytes(w.sc.handle, KINDS[kind], level_in, cin, cout)
+        ws = scratch(nbytes)
+        L.check(lib.a3d_conv_apply_acc(w.sc.handle, KINDS[kind], level_in, _ptr(xs), xw.stride(0), cin, _ptr(wp), cout, _ptr(ys),
+                                       yw.stride(0), 1, _ptr(ys), yw.stride(0), _ptr(state), _ptr(ws), nbytes, _stream()),
+                "a3d_conv_apply_acc")
+        torch.cuda.synchronize()
+    finally:
+        _set_mode(before)
+    _assert_bits(ys[:n_out].contiguous(), ref + Y0.double(), where)
+    assert (ys[n_out] == 0).all(), (where, "zero row")
+    assert torch.isnan(yw[:, :32]).all() and torch.isnan(yw[:, 32 + cout:]).all(), (where, "wrote outside its column slice")
+    assert int(state[1]) == 0, (where, "failure word", int(state[1]))
+
+
+_PROJ = [(s, l) for s in E.PROJ_SMALL_SCENES for l in range(5)] + [(s, 0) for s in E.PROJ_LARGE_SCENES]
+
+
+@pytest.mark.parametrize("name,level", _PROJ, ids=[f"{s}-L{l}" for s, l in _PROJ])
+def test_fused_projection(mode, name, level):
+    """a3d_op.proj_*: relu(conv3(x) + x2 @ Wp + shift), the projection's input a column slice at 32.  The network's six
+    shapes; 96 -> 64 (+64), which the planner moves to 32-channel stages to fuse; 96 -> 64 (+96), which has no fused build and
+    runs as two launches.  box8192 reaches <128, 32, 1, FUSE>, box8191 <128, 32, 0, FUSE>, s20000 the clamped share counts."""
+    w = _world(name)
+    n = w.sc.n[level]
+    pairs = w.pairs("conv3", level)
+    for cin, cout, cin2 in E.PROJ_SHAPES:
+        x = _with_zero_row(_ints((n, cin), -3, 3, name, level, cin, "proj x"))
+        x2 = _ints((n, cin2), -3, 3, name, level, cin2, "proj x2")
+        W = _ints((27, cin, cout), -3, 3, name, level, cin, cout, "proj w")
+        Wp = _ints((1, cin2, cout), -3, 3, name, level, cin2, cout, "proj wp")
+        shift = _ints((cout,), -3, 3, name, level, cout, "proj shift")
+        ref = torch.relu(_conv_ref(pairs, x.double(), W.double(), n) + x2.double() @ Wp[0].double() + shift.double())
+        both = torch.cat([pack_weight(W), pack_weight(Wp)]).contiguous()
+        op = Program(w.sc, L.OP_CONV3, level, cin, cout, 27, both, None, shift, relu=True, proj_cin=cin2, proj_pad=32)
+        op.fill(0, x[:n])
+        op.fill(op.proj_buf, x2, 32)
+        op.run()
+        where = f"scene {name} conv3 level {level} {cin}->{cout} (+{cin2}) mode {mode}"
+        out = op.buffer(1)
+        _assert_bits(out[:n], ref, where)
+        assert (out[n] == 0).all(), (where, "zero row")
+
+
+@pytest.mark.parametrize("name", E.HEAD_SCENES)
+def test_fused_head(mode, name):
+    """a3d_op.head_*: relu(conv3 + shift + residual) into the op's buffer AND that @ Wh + bias into the external output, rows
+    in the CALLER's order (two_batch: across two samples), 32 columns beyond the head's left NaN.  s20000 runs the clamped
+    <96, 32, 1, HEAD>."""
+    w = _world(name)
+    n = w.sc.n[0]
+    pairs = w.pairs("conv3", 0)
+    to_caller = torch.from_numpy(w.to_oracle[0]).cuda()         # the scene was built from the oracle's (= caller's) row order
+    for cin, cout, head in E.HEAD_SHAPES:
+        x = _with_zero_row(_ints((n, cin), -3, 3, name, cin, "head x"))
+        W = _ints((27, cin, cout), -3, 3, name, cin, cout, "head w")
+        Wh = _ints((1, cout, head), -3, 3, name, cout, head, "head wh")
+        bias, shift = _ints((head,), -3, 3, name, head, "head bias"), _ints((cout,), -3, 3, name, cout, "head shift")
+        R = _ints((n, cout), -3, 3, name, cout, "head res")
+        y_ref = torch.relu(_conv_ref(pairs, x.double(), W.double(), n) + shift.double() + R.double())
+        h_ref = torch.empty(n, head, dtype=torch.float64, device="cuda")
+        h_ref[to_caller] = y_ref @ Wh[0].double() + bias.double()
+        op = Program(w.sc, L.OP_CONV3, 0, cin, cout, 27, pack_weight(W), None, shift, relu=True, use_res=True,
+                     head=(pack_weight(Wh), bias, head))
+        op.fill(0, x[:n])
+        op.fill(op.res_buf, R)
+        ext = torch.full((n, head + 32), NAN, device="cuda")
+        op.run(ext=ext)
+        where = f"scene {name} conv3 level 0 {cin}->{cout} head {head} mode {mode}"
+        out = op.buffer(1)
+        _assert_bits(out[:n], y_ref, where + ": own output")
+        assert (out[n] == 0).all(), (where, "zero row")
+        _assert_bits(ext[:, :head].contiguous(), h_ref, where + ": external output")
+        assert torch.isnan(ext[:, head:]).all(), (where, "wrote beyond the head's columns")
+
+
+@pytest.mark.parametrize("ks", [5, 3])
+@pytest.mark.parametrize("name", ["one", "line37", "box63", "box64", "box65", "two_batch", "outlier"])
+def test_stem(name, ks):
+    """The input convolution through a one-op program: colours in {0..3} in the CALLER's row order, relu(conv * scale + shift)
+    into columns 96.. of a 128-column buffer.  one / two_batch / outlier look their neighbours up in the hash table."""
+    w = _world(name)
+    n = w.sc.n[0]
+    feats3 = _ints((n, 3), 0, 3, name, "colours")
+    W = _ints((ks ** 3, 3, 32), -3, 3, name, ks, "stem w")
+    scale, shift = _scales(32, name, ks), _ints((32,), -3, 3, name, ks, "stem shift")
+    ref = torch.relu(_conv_ref(w.stem_pairs(ks), feats3.double(), W.double(), n) * scale.double() + shift.double())
+    op = Program(w.sc, L.OP_STEM, 0, 3, 32, ks ** 3, W.contiguous(), scale, shift, relu=True, out_pad=96)
+    op.run(feats3)
+    where = f"scene {name} stem {ks}^3"
+    out = op.buffer(1)
+    _assert_bits(out[:n, 96:], ref, where)
+    assert (out[n, 96:] == 0).all(), (where, "zero row")
+    assert torch.isnan(out[:, :96]).all(), (where, "wrote outside its column slice")
