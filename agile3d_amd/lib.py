@@ -203,6 +203,25 @@ class AbsorbPiecesArgs(C.Structure):
                 ("click_row", C.c_int32 * 256)]
 
 
+class GrowSummary(C.Structure):
+    """a3d_grow_summary: seeds, reached voxels, selected vertices, the largest dist reached, the error word
+    (A3D_GROW_BAD_INDEX)."""
+    _fields_ = [("seeds", C.c_int64), ("reached", C.c_int64), ("selected", C.c_int64), ("max_dist", C.c_int32),
+                ("err", C.c_int32)]
+
+
+class GrowVoxelsArgs(C.Structure):
+    """a3d_grow_voxels_args: the scene, the keys (or NULL), the seeds per voxel and per vertex (one of them at least), the
+    lift (inverse_map, n_full), the optional outputs, the summary, the workspace, and by value the connectivity, the limit and
+    the face / edge / corner step costs."""
+    _fields_ = [("scene", C.c_void_p), ("n", C.c_int64), ("keys_dev", C.c_void_p), ("seed_qv_dev", C.c_void_p),
+                ("seed_full_dev", C.c_void_p), ("inverse_map_dev", C.c_void_p), ("n_full", C.c_int64),
+                ("dist_qv_dev", C.c_void_p), ("owner_qv_dev", C.c_void_p), ("selected_full_dev", C.c_void_p),
+                ("dist_full_dev", C.c_void_p), ("summary_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("connectivity", C.c_int32), ("limit", C.c_int32), ("cost", C.c_int32 * 3),
+                ("reserved_", C.c_int32)]
+
+
 class ObjectMoments(C.Structure):
     """a3d_object_moments: one object of a labelling -- vertices and voxels, the sums of the fixed-point coordinates (X, Y, Z)
     and of their products (XX, XY, XZ, YY, YZ, ZZ), the covered surface in thirds of area quanta, the exact fp32 box."""
@@ -299,6 +318,7 @@ A3D_OVERLAY_NONE, A3D_OVERLAY_PAINT, A3D_OVERLAY_ERASE = 0, 1, 2
 A3D_MEASURE_RANGE, A3D_MEASURE_BAD_LABEL = 1, 2
 A3D_MEASURE_MAX_BITS, A3D_MEASURE_MAX_Q, A3D_MEASURE_MAX_FACES = 20, 1 << 38, 1 << 23
 A3D_MEASURE_BLOCK, A3D_MEASURE_CHUNK = 256, 1024
+A3D_GROW_MAX_STEPS, A3D_GROW_BAD_INDEX = 1024, 1
 A3D_ERR_INVALID = -1
 PROF_DENSE = 11
 PROF_NAMES = ["spconv", "splitk_epilogue", "stem", "c2s_attn", "query_chain", "s2c_attn", "ln_mask", "posenc",
@@ -492,6 +512,8 @@ SYMBOLS = {
     "a3d_label_pieces": (C.c_int, [C.POINTER(LabelPiecesArgs), C.c_void_p]),
     "a3d_absorb_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "a3d_absorb_pieces": (C.c_int, [C.POINTER(AbsorbPiecesArgs), C.c_void_p]),
+    "a3d_grow_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "a3d_grow_voxels": (C.c_int, [C.POINTER(GrowVoxelsArgs), C.c_void_p]),
     "a3d_region_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, C.c_void_p,
                                   C.c_void_p]),
     "a3d_select_vertices": (C.c_int, [C.POINTER(SelectArgs), C.c_void_p]),

@@ -312,6 +312,46 @@ class SelectResult:
             setattr(self, k, kw.get(k))
 
 
+class GrowResult:
+    """What ``grow()``, ``grow_at()`` and ``shrink()`` return.  Device tensors: ``selected`` uint8 [n_full] (1 = the vertex is
+    selected; ``paint`` / ``erase`` take it as it is), ``dist_full`` int32 [n_full] and ``dist_qv`` int32 [n_voxels] (the path
+    cost from the nearest seed in the units of ``cost``, -1: not reached), ``owner_qv`` int32 [n_voxels] (the voxel row of that
+    seed; of seeds equally near the smallest row; -1: not reached).  Host: ``count`` (selected vertices), ``reached_voxels``,
+    ``seeds`` (seed voxels), ``max_distance`` (the largest distance reached, in world units: cost units / 1024 voxels with
+    ``radius``, hops x the voxel size with ``steps``), and ``limit``, ``cost``, ``connectivity``, ``within`` as used.  After
+    ``shrink()`` the distances and owners are those FROM THE OUTSIDE of the selection and ``selected`` is the eroded set."""
+
+    __slots__ = ("selected", "dist_full", "dist_qv", "owner_qv", "count", "reached_voxels", "seeds", "max_distance", "limit",
+                 "cost", "connectivity", "within")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def grow_limit(radius, steps, voxel_size):
+    """``(cost, limit)`` of ``grow(radius=, steps=)``, pure Python.  Exactly one of the two: ``radius`` >= 0 in world units
+    walks with the metric costs ``view.GROW_METRIC_COST`` = round(1024 (1, sqrt 2, sqrt 3)) up to ``limit = floor(radius /
+    voxel_size * 1024)``, computed in float64; ``steps``, an int >= 0, counts hops (costs 1, 1, 1, ``limit = steps``).
+    ``ValueError`` for anything else, and for a limit of more than ``view.GROW_MAX_STEPS`` steps: ``pieces()`` answers what
+    is connected at all."""
+    if (radius is None) == (steps is None):
+        raise ValueError("give a radius (world units) or steps (hops), one of them")
+    if steps is not None:
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 0:
+            raise ValueError("steps must be an int >= 0")
+        cost, limit = (1, 1, 1), int(steps)
+    else:
+        r = np.float64(radius)
+        if not (np.isfinite(r) and r >= 0.0):
+            raise ValueError("radius must be finite and >= 0")
+        cost, q = V.GROW_METRIC_COST, np.floor(r / np.float64(voxel_size) * np.float64(1024.0))
+        limit = int(min(q, np.float64(2.0 ** 40)))
+    if limit // min(cost) > V.GROW_MAX_STEPS:
+        raise ValueError(f"that is more than {V.GROW_MAX_STEPS} voxel steps: pieces() answers what is connected at all")
+    return cost, limit
+
+
 class CorrectedResult:
     """What ``corrected()`` returns: ``labels_full`` int32 [n_full] and ``colors`` fp32 [n_full, 3] on the device -- the model's
     labels with the manual layer laid over them -- ``miou`` and ``iou_per_object`` as a ``SessionResult`` holds them (``None``
@@ -726,6 +766,7 @@ class InteractiveSession:
         self._render_ws = None                      # scratch of render(): kept per scene, grown when a view needs more pairs
         self._unique_map = None                     # int64 [n_voxels]: the vertex each voxel was made from (measure(labels=))
         self._measure_frame = None                  # (origin, quantum, bits) of measure(): once per scene, on first use
+        self._grow_ws = None                        # scratch of grow(): once per scene, on first use
         self.section = None                         # the Section pick, click_ray and render apply by default (set_section)
         self._reset_clicks()
 
@@ -1604,10 +1645,11 @@ class InteractiveSession:
         return SelectResult(selected=selected, count=s["selected"], in_view=s["in_view"], through=bool(through), slack=slack)
 
     def _selection(self, selection):
-        sel = selection.selected if isinstance(selection, SelectResult) else selection
+        sel = selection.selected if isinstance(selection, (SelectResult, GrowResult)) else selection
         n = self.coords_full.shape[0]
         if not torch.is_tensor(sel) or sel.device != self.device or sel.dtype not in (torch.uint8, torch.bool) or tuple(sel.shape) != (n,):
-            raise ValueError(f"the selection must be a SelectResult of this scene, or a uint8 / bool tensor [{n}] on the session's device")
+            raise ValueError(f"the selection must be a SelectResult or GrowResult of this scene, or a uint8 / bool tensor [{n}] on the "
+                             "session's device")
         return (sel.view(torch.uint8) if sel.dtype == torch.bool else sel).contiguous()
 
     def _edit_layer(self, selection, op, obj):
@@ -1642,6 +1684,121 @@ class InteractiveSession:
         """Takes the manual layer off the vertices of ``selection``: they show the model's labels again.  Returns how many
         vertices' layer entry changed.  One host round trip."""
         return self._edit_layer(selection, "erase", 0)
+
+    # ------------------------------------------------------------------ along the surface
+    def _grow_keys(self, within):
+        """The keys ``a3d_grow_voxels`` walks by (``None``: walk anywhere) of ``grow(within=)``."""
+        n = self._labels_qv.numel()
+        if isinstance(within, str):
+            if within == "all":
+                return None
+            if within == "label":
+                return self._labels_qv
+        elif torch.is_tensor(within) and within.device == self.device and tuple(within.shape) == (n,):
+            if within.dtype == torch.int32:
+                return within.contiguous()
+            if within.dtype in (torch.uint8, torch.bool):
+                return (within != 0).to(torch.int32) - 1            # a mask: key 0 inside, -1 outside
+        raise ValueError(f'within must be "all", "label", an int32 tensor [{n}] of keys or a uint8 / bool tensor [{n}] (a mask) on '
+                         "the session's device")
+
+    def _grow_seeds(self, seeds):
+        """``(seed_qv, seed_full)`` of ``grow(seeds)``: one of the two is ``None``."""
+        if isinstance(seeds, (SelectResult, GrowResult)) or torch.is_tensor(seeds):
+            return None, self._selection(seeds)
+        n = self._labels_qv.numel()
+        if isinstance(seeds, str):
+            if seeds != "clicks":
+                raise ValueError('seeds: the only name is "clicks"')
+            rows = self._click_rows()
+        else:
+            try:
+                rows = [int(r) for r in seeds]
+            except (TypeError, ValueError):
+                raise ValueError('seeds must be a SelectResult / GrowResult, a uint8 / bool tensor over the vertices, "clicks" or a '
+                                 "list of voxel rows") from None
+            if any(not 0 <= r < n for r in rows):
+                raise ValueError(f"seeds: a voxel row outside 0 .. {n - 1}")
+        seed_qv = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        if rows:
+            seed_qv[torch.tensor(rows, dtype=torch.int64).to(self.device)] = 1
+        return seed_qv, None
+
+    def _grow(self, seed_qv, seed_full, cost, limit, keys, connectivity, within):
+        """``a3d_grow_voxels`` on the session's voxels, lifted to its vertices: ONE library call, ONE host round trip."""
+        n_full = self.coords_full.shape[0]
+        if self._grow_ws is None:
+            self._grow_ws = V.grow_workspace(self._labels_qv.numel(), self.device)
+        dist_qv, owner_qv, selected, dist_full, summary, _ = V.grow_voxels(
+            self._scene_handle(), n_full, keys, seed_qv, seed_full, self.inverse_map, cost, limit, connectivity,
+            summary=self._region_sum[:V.GROW_SUMMARY.itemsize], workspace=self._grow_ws)
+        s = V.read_grow_summary(summary.cpu().numpy())                  # the one host round trip
+        if s["err"] & V.GROW_BAD_INDEX:
+            raise RuntimeError("a3d_grow_voxels: inverse_map out of range")
+        unit = self.voxel_size / 1024.0 if cost == V.GROW_METRIC_COST else self.voxel_size
+        return GrowResult(selected=selected, dist_full=dist_full, dist_qv=dist_qv, owner_qv=owner_qv, count=s["selected"],
+                          reached_voxels=s["reached"], seeds=s["seeds"], max_distance=s["max_dist"] * unit, limit=limit,
+                          cost=cost, connectivity=connectivity, within=within if isinstance(within, str) else "keys")
+
+    def grow(self, seeds, radius=None, steps=None, within="all", connectivity=26):
+        """Grows a selection ALONG THE SURFACE: everything within a distance of ``seeds``, the distance measured as the
+        cheapest walk over neighbouring voxels, not across the screen or through the air (``a3d_grow_voxels``; the adjacency is
+        the scene's own neighbour table, as in ``pieces()``).  ``seeds``: a ``SelectResult`` / ``GrowResult``, a uint8 / bool
+        tensor [n_full] on the device (the voxels that hold a selected vertex are the seeds), ``"clicks"`` (the clicked voxels)
+        or a list of voxel rows.  Exactly one of ``radius`` (world units >= 0: face, edge and corner steps cost 1024, 1448 and
+        1774 = round(1024 (1, sqrt 2, sqrt 3)), and the walk may cost ``floor(radius / voxel_size * 1024)``, computed in
+        float64) and ``steps`` (an int >= 0: every step costs 1).  More than ``view.GROW_MAX_STEPS`` voxel steps raise
+        ``ValueError``: ``pieces()`` answers what is connected at all.  ``within``: ``"all"`` walks anywhere; ``"label"``
+        stays inside the object of each seed -- the labels ``preview()`` paints; an int32 tensor [n_voxels] of keys walks
+        between equal keys >= 0; a uint8 / bool tensor [n_voxels] is a mask to stay inside.  ``connectivity``: 6, 18 or 26.
+        Returns a ``GrowResult``: the selected vertices (``paint`` / ``erase`` take it), the distance of every vertex and
+        voxel, and for every voxel the seed voxel nearest to it -- ``grow("clicks", ..., within="label")`` splits each object
+        between its clicks.  A selection is ROUNDED UP TO WHOLE VOXELS: every vertex of a reached voxel is selected.  The
+        voxel lattice is the resolution at which labels live; a mesh's own edges are not walked.  The costs and the default
+        ``within`` are this project's choice and are NOT tuned on real scans.  One library call, one host round trip; it
+        changes no session state."""
+        self._need_scene()
+        cost, limit = grow_limit(radius, steps, self.voxel_size)
+        connectivity = V._connectivity(connectivity)
+        keys = self._grow_keys(within)
+        seed_qv, seed_full = self._grow_seeds(seeds)
+        return self._grow(seed_qv, seed_full, cost, limit, keys, connectivity, within)
+
+    def grow_at(self, result, u, v, radius=None, steps=None, within="label", connectivity=26):
+        """The SURFACE BRUSH: ``grow`` from the vertex that pixel ``(u, v)`` (column, row) of ``result`` shows -- resolved as
+        ``piece_at`` / ``confidence_at`` resolve it: the pixel's vertex on a cloud, the heaviest corner of its face on a mesh
+        -- or ``None`` where the pixel shows nothing.  With the default ``within="label"`` the brush stays on the object under
+        the pointer: over the edge of a chair's seat it does not take the floor that shows beside it.  That default is this
+        project's choice and is NOT tuned on real scans.  One small device-to-host copy, then as ``grow``."""
+        self._need_scene()
+        cost, limit = grow_limit(radius, steps, self.voxel_size)
+        connectivity = V._connectivity(connectivity)
+        keys = self._grow_keys(within)
+        vertex = self._vertex_at(result, u, v)
+        if vertex < 0:
+            return None
+        seed_full = torch.zeros(self.coords_full.shape[0], dtype=torch.uint8, device=self.device)
+        seed_full[vertex] = 1
+        return self._grow(None, seed_full, cost, limit, keys, connectivity, within)
+
+    def shrink(self, selection, radius=None, steps=None, connectivity=26):
+        """Pulls a selection IN by a margin (``radius`` or ``steps`` as in ``grow``).  The voxels that hold no selected vertex
+        are the OUTSIDE (found by one ``grow`` at limit 0); a selected vertex stays when its voxel is NOT reached from the
+        outside within the limit (a second ``grow``, seeded with the outside, walking anywhere).  Returns a ``GrowResult``
+        whose ``selected`` is the eroded set and ``count`` its size; its distances and owners are the second call's, measured
+        from the outside.  Like ``grow`` it ROUNDS A SELECTION UP TO WHOLE VOXELS: a voxel with one selected vertex is inside
+        as a whole, so ``shrink(grow(s, steps=k), steps=k)`` keeps every vertex of ``s`` whose voxel is not near the border of
+        the scene's own surface, and may keep more.  Two library calls, three host round trips; no session state changes."""
+        self._need_scene()
+        cost, limit = grow_limit(radius, steps, self.voxel_size)
+        connectivity = V._connectivity(connectivity)
+        sel = self._selection(selection)
+        held = self._grow(None, sel, cost, 0, None, connectivity, "all")
+        outside = (held.dist_qv < 0).to(torch.uint8)
+        res = self._grow(outside, None, cost, limit, None, connectivity, "all")
+        res.selected = ((sel != 0) & (res.selected == 0)).to(torch.uint8)
+        res.count = int(res.selected.sum().cpu())
+        return res
 
     def manual_labels(self):
         """``(on uint8 [n_full], obj int32 [n_full])``: copies of the manual layer on the device -- ``on`` 1 where a vertex is

@@ -595,6 +595,96 @@ def absorb_pieces(scene, labels, piece_qv, workspace, min_voxels, connectivity=2
     return labels_out, summary
 
 
+# ---- growing a selection along the surface ------------------------------------------------------------------------------------
+GROW_SUMMARY = np.dtype([("seeds", "<i8"), ("reached", "<i8"), ("selected", "<i8"), ("max_dist", "<i4"), ("err", "<i4")])
+assert C.sizeof(L.GrowSummary) == GROW_SUMMARY.itemsize == 32
+assert C.sizeof(L.GrowVoxelsArgs) == 136
+GROW_BAD_INDEX = L.A3D_GROW_BAD_INDEX           # the bit of the grow summary's error word
+GROW_MAX_STEPS = L.A3D_GROW_MAX_STEPS
+GROW_METRIC_COST = (1024, 1448, 1774)           # round(1024 * (1, sqrt 2, sqrt 3)): face, edge, corner steps in 1/1024 voxel
+GROW_MAX_COST, GROW_MAX_LIMIT = 1 << 16, 1 << 30
+
+
+def read_grow_summary(host):
+    """The host copy of an ``a3d_grow_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints: ``seeds``,
+    ``reached`` (voxels), ``selected`` (vertices), ``max_dist``, ``err`` (bit ``GROW_BAD_INDEX``)."""
+    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:GROW_SUMMARY.itemsize].view(GROW_SUMMARY)[0]
+    return {k: int(rec[k]) for k in ("seeds", "reached", "selected", "max_dist", "err")}
+
+
+def grow_workspace(n, device):
+    """The scratch of ``grow_voxels`` for n voxels (``a3d_grow_workspace_bytes``)."""
+    nbytes = L.load().a3d_grow_workspace_bytes(n)
+    if nbytes == 0:
+        raise ValueError(f"no grow workspace for n={n}")
+    return torch.empty(nbytes, dtype=U8, device=device)
+
+
+def grow_settings(cost, limit, connectivity):
+    """``(cost, limit, connectivity)`` as ``a3d_grow_voxels`` takes them, checked on the host: three integer step costs in
+    1 .. 65536 (face, edge, corner), an integer limit in 0 .. 2^30 that is at most ``GROW_MAX_STEPS`` steps of the cheapest,
+    a connectivity of 6, 18 or 26.  ``ValueError`` naming the argument."""
+    connectivity = _connectivity(connectivity)
+    try:
+        cost = tuple(cost)
+    except TypeError:
+        cost = ()
+    if len(cost) != 3 or any(isinstance(c, bool) or int(c) != c or not 1 <= c <= GROW_MAX_COST for c in cost):
+        raise ValueError(f"cost must be three integers in 1 .. {GROW_MAX_COST} (face, edge, corner)")
+    cost = tuple(int(c) for c in cost)
+    if isinstance(limit, bool) or int(limit) != limit or not 0 <= limit <= GROW_MAX_LIMIT:
+        raise ValueError(f"limit must be an integer in 0 .. {GROW_MAX_LIMIT}")
+    if int(limit) // min(cost) > GROW_MAX_STEPS:
+        raise ValueError(f"limit = {limit} is more than {GROW_MAX_STEPS} steps of cost {min(cost)}: everything connected is "
+                         "what label_pieces answers")
+    return cost, int(limit), connectivity
+
+
+def grow_voxels(scene, n_full, keys=None, seed_qv=None, seed_full=None, inverse_map=None, cost=GROW_METRIC_COST, limit=0,
+                connectivity=26, dist_qv=None, owner_qv=None, selected_full=None, dist_full=None, summary=None, workspace=None):
+    """``a3d_grow_voxels``: the bounded shortest-path distance from a set of seed voxels over the voxels of ``scene`` (an
+    ``engine.Scene``; n rows in the caller's order), and the seed that is nearest.  ``n_full``: the number of vertices the
+    result is lifted to (0: none).  ``keys`` int32 [n] or ``None`` (all 0): a key < 0 cannot be walked on, an edge is walkable
+    between equal keys.  Seeds: ``seed_qv`` uint8 [n] and / or ``seed_full`` uint8 [n_full] through ``inverse_map`` int64
+    [n_full] (``None``: the identity); one of the two at least.  ``cost``: the face, edge and corner step; ``limit``: the
+    largest path cost (``grow_settings``).  Outputs: a tensor of the caller's, ``None`` = allocated, ``False`` = not wanted.
+    Returns ``(dist_qv int32 [n], owner_qv int32 [n], selected_full uint8 [n_full], dist_full int32 [n_full], summary uint8
+    [32], workspace)`` on the device, ``None`` for what was not wanted; ``read_grow_summary`` decodes the summary's host copy."""
+    cost, limit, connectivity = grow_settings(cost, limit, connectivity)
+    if isinstance(n_full, bool) or int(n_full) != n_full or not 0 <= n_full < 1 << 31:
+        raise ValueError("n_full must be an integer in 0 .. 2^31 - 1")
+    n_full = int(n_full)
+    if seed_qv is None and seed_full is None:
+        raise ValueError("seed_qv or seed_full: one of the two seed arrays must be given")
+    if n_full == 0 and (seed_full is not None or inverse_map is not None):
+        raise ValueError("seed_full and inverse_map belong to the vertices: n_full is 0")
+    handle, n = _scene_rows(scene)
+    dev = _device("seed_qv" if seed_qv is not None else "seed_full", seed_qv if seed_qv is not None else seed_full)
+    a = L.GrowVoxelsArgs()
+    a.scene, a.n, a.n_full = handle, n, n_full
+    a.keys_dev = _ptr("keys", keys, I32, (n,), dev, optional=True)
+    a.seed_qv_dev = _ptr("seed_qv", seed_qv, U8, (n,), dev, optional=True)
+    a.seed_full_dev = _ptr("seed_full", seed_full, U8, (n_full,), dev, optional=True)
+    a.inverse_map_dev = _ptr("inverse_map", inverse_map, I64, (n_full,), dev, optional=True)
+    a.connectivity, a.limit = connectivity, limit
+    a.cost[:] = cost
+    outs = []
+    for name, t, dtype, rows in (("dist_qv", dist_qv, I32, n), ("owner_qv", owner_qv, I32, n),
+                                 ("selected_full", selected_full, U8, n_full), ("dist_full", dist_full, I32, n_full)):
+        t = None if t is False else _out(name, t, dtype, (rows,), dev)
+        setattr(a, name + "_dev", t.data_ptr() if t is not None and rows else None)
+        outs.append(t)
+    summary = _summary(summary, GROW_SUMMARY.itemsize, dev)
+    a.summary_dev = summary.data_ptr()
+    if workspace is None:
+        workspace = grow_workspace(n, dev)
+    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
+    if a.workspace_bytes < L.load().a3d_grow_workspace_bytes(n) or workspace.data_ptr() % 256:
+        raise ValueError("workspace too small or not 256-byte aligned (grow_workspace(n, device))")
+    L.check(L.load().a3d_grow_voxels(C.byref(a), L.stream(dev)), "a3d_grow_voxels")
+    return (*outs, summary, workspace)
+
+
 # ---- measuring the objects of a labelling ---------------------------------------------------------------------------------------
 OBJECT_MOMENTS = np.dtype([("vertices", "<i8"), ("voxels", "<i8"), ("sum", "<i8", (3,)), ("mom", "<i8", (6,)),
                            ("area_thirds", "<i8"), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("reserved_", "<i4", (2,))])

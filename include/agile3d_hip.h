@@ -1027,6 +1027,76 @@ typedef struct a3d_absorb_pieces_args {
 size_t a3d_absorb_workspace_bytes(int64_t n, int capacity, int n_classes);
 int    a3d_absorb_pieces(const a3d_absorb_pieces_args* args, void* stream);
 
+/* HOW FAR ALONG THE SURFACE: a bounded shortest-path distance from a set of seed voxels over the same adjacency, and which
+ * seed is nearest (csrc/session_grow.hip).  The rule is this library's: the reference's tool selects nothing by distance.
+ * a3d_label_pieces answers "what is connected at all"; this answers "what is connected within a distance, and how far".
+ *
+ * a3d_grow_voxels.  The graph's NODES are the level-0 voxels of `scene`, n = its size, in the CALLER's row order.
+ *   CONNECTIVITY 6, 18 or 26 with exactly the offsets a3d_label_pieces admits; the neighbours are the scene's (A3D_TAB_NBR27,
+ *   both ends through A3D_TAB_ORIGROW), so never across batch samples.
+ *   KEYS: keys_dev int32 [n], or NULL = every voxel has key 0.  A voxel with key < 0 cannot be walked on.  An edge is
+ *   WALKABLE only when both ends hold the SAME key (a3d_label_pieces' convention: all zeros = walk anywhere, a 0 / -1 mask =
+ *   walk inside a region, the labels = stay inside one object).
+ *   STEP COST: cost[0], cost[1], cost[2] for the face, edge and corner offsets (|d|1 = 1, 2, 3), each in 1 .. 65536.
+ *   LIMIT: 0 .. 2^30, with limit / min(cost) <= A3D_GROW_MAX_STEPS: a path within the limit has at most that many edges.
+ *   A larger limit is refused: "everything connected" is what a3d_label_pieces is for.
+ *   SEEDS: a voxel is a seed when its key is >= 0 and either seed_qv_dev[row] != 0 (uint8 [n], optional), or some vertex i
+ *   has seed_full_dev[i] != 0 and inverse_map_dev[i] == row (uint8 [n_full] and int64 [n_full], optional; a NULL map is the
+ *   identity).  At least one of the two seed arrays must be given.
+ *   THE VALUE of a voxel v is the LEXICOGRAPHIC MINIMUM, over the seeds s with a walkable path to v of total cost
+ *   d <= limit, of the pair (d, s), s being the seed's caller row: dist[v] = d, owner[v] = s; both are -1 when there is no
+ *   such seed.  A seed has dist 0 and owns itself.  Everything is an integer: there is no tolerance anywhere.
+ *   LIFTING (n_full > 0): for vertex i, row = inverse_map[i]; selected_full[i] = dist[row] >= 0 (uint8 0 / 1) and
+ *   dist_full[i] = dist[row].  For an index outside 0..n-1: 0 / -1, and A3D_GROW_BAD_INDEX is set in the summary's err; a
+ *   seed vertex with such an index is ignored (and sets the same bit).
+ *   OUTPUTS, all optional but the summary: dist_qv_dev int32 [n], owner_qv_dev int32 [n], selected_full_dev uint8 [n_full],
+ *   dist_full_dev int32 [n_full].  The summary (cleared by the call): seeds, reached voxels (dist >= 0, the seeds
+ *   included), selected vertices, the largest dist reached (0 when nothing is), the error word.  Integer sums and maxima
+ *   only, one atomic per workgroup and counter.
+ *   How: (dist, owner) is ONE 64-bit word dist << 32 | owner, relaxed with a 64-bit atomicMin until nothing changes: the
+ *   fixed point of value[v] = min over walkable neighbours u of (dist[u] + cost, owner[u]) is the value above, in whatever
+ *   order the relaxations land, so two calls give the same bytes in every output.  In a sweep the voxels lowered in the
+ *   sweep before offer their word to their neighbours; at most limit / min(cost) sweeps are launched; each raises a device
+ *   flag when it lowered anything, and a sweep whose predecessor's flag is clear returns at once.  The host reads nothing
+ *   in mid-call; no thread waits for another (no grid barrier, no spin-wait).
+ *   The workspace: a3d_grow_workspace_bytes(n) bytes, 256-byte aligned.  The library allocates nothing and does not
+ *   synchronise.
+ *   A3D_ERR_INVALID with nothing launched and nothing written: no arguments, no scene, n != the scene's level-0 size, a
+ *   connectivity other than 6 / 18 / 26, a cost outside 1 .. 65536, a limit outside 0 .. 2^30 or beyond
+ *   A3D_GROW_MAX_STEPS steps, neither seed array, no summary_dev, n_full < 0, n > 0 without a workspace, a workspace that is
+ *   too small or misaligned. */
+#define A3D_GROW_MAX_STEPS 1024
+#define A3D_GROW_BAD_INDEX 1
+typedef struct a3d_grow_summary {
+  int64_t seeds;
+  int64_t reached;                  /* voxels with dist >= 0 */
+  int64_t selected;                 /* vertices with selected_full = 1 */
+  int32_t max_dist;
+  int32_t err;                      /* A3D_GROW_BAD_INDEX */
+} a3d_grow_summary;                /* 32 bytes */
+typedef struct a3d_grow_voxels_args {
+  const a3d_scene* scene;
+  int64_t        n;
+  const int32_t* keys_dev;          /* [n] caller's row order, or NULL: all 0 */
+  const uint8_t* seed_qv_dev;       /* [n] or NULL */
+  const uint8_t* seed_full_dev;     /* [n_full] or NULL */
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL: identity */
+  int64_t        n_full;
+  int32_t*       dist_qv_dev;       /* out [n] or NULL */
+  int32_t*       owner_qv_dev;      /* out [n] or NULL */
+  uint8_t*       selected_full_dev; /* out [n_full] or NULL */
+  int32_t*       dist_full_dev;     /* out [n_full] or NULL */
+  a3d_grow_summary* summary_dev;
+  void*          workspace_dev;
+  size_t         workspace_bytes;
+  int32_t        connectivity;
+  int32_t        limit;
+  int32_t        cost[3];           /* face, edge, corner */
+  int32_t        reserved_;
+} a3d_grow_voxels_args;
+size_t a3d_grow_workspace_bytes(int64_t n);
+int    a3d_grow_voxels(const a3d_grow_voxels_args* args, void* stream);
+
 /* HOW BIG an object is and where it lies: one record per object id of a labelling (csrc/session_measure.hip).  The rules are
  * this library's: the reference exports a mask and measures nothing.  Everything accumulated is an INTEGER (counts, sums of
  * fixed-point coordinates, minima and maxima of order-preserving keys), so a result does not depend on the order in which
