@@ -852,7 +852,7 @@ __global__ __launch_bounds__(kSesBlock) void k_render_shade(const ShadeTab t) {
 // pixel's unit ray d; k0 = min(|Nn . d| / |Nn|, 1), or 1 where |Nn|^2 is 0 or not finite; k = ambient + (1 - ambient) k0; each
 // channel c k.  Every operation rounded on its own, in the order written.
 struct LitTab {
-  ShadeTab s;                                 // (s.faces is never NULL here)
+  ShadeTab s;                                 // (s.faces is NULL only in k_render_shade_lit_points)
   const float* normals;
   a3d_camera cam;
   float ambient;
@@ -868,6 +868,32 @@ __global__ __launch_bounds__(kSesBlock) void k_render_shade_lit(const LitTab t) 
     const float nx = (wgt * n0[0] + u * n1[0]) + v * n2[0];
     const float ny = (wgt * n0[1] + u * n1[1]) + v * n2[1];
     const float nz = (wgt * n0[2] + u * n1[2]) + v * n2[2];
+    const float l2 = (nx * nx + ny * ny) + nz * nz;
+    float k0 = 1.f;
+    if (l2 > 0.f && l2 < __builtin_inff()) {
+      float d[3];
+      ses_pixel_ray(t.cam, (int)(i % t.cam.width), (int)(i / t.cam.width), d);
+      const float dot = (nx * d[0] + ny * d[1]) + nz * d[2];
+      k0 = fminf(fabsf(dot) / sqrtf(l2), 1.f);
+    }
+    const float k = t.ambient + (1.f - t.ambient) * k0;
+    c[0] = c[0] * k, c[1] = c[1] * k, c[2] = c[2] * k;
+  }
+  t.s.rgb[3 * i] = shade_q(c[0]), t.s.rgb[3 * i + 1] = shade_q(c[1]), t.s.rgb[3 * i + 2] = shade_q(c[2]);
+}
+
+// ---- lit shading (point clouds with estimated normals): the same light, the pixel's vertex in place of the corners -----------
+// THE RULE: base colour as above (s.faces is NULL: ids are vertices); N = the vertex's normal as it is stored; the rest is
+// k_render_shade_lit's, operation for operation.  A zero normal (a voxel without a valid one) leaves the colour unshaded.
+__global__ __launch_bounds__(kSesBlock) void k_render_shade_lit_points(const LitTab t) {
+#pragma clang fp contract(off)
+  const long long i = (long long)blockIdx.x * kSesBlock + threadIdx.x;
+  if (i >= t.s.pixels) return;
+  float c[3], u, v, wgt;
+  int32_t f[3];
+  if (shade_base(t.s, i, c, f, u, v, wgt)) {
+    const float* nn = t.normals + 3 * (size_t)t.s.id[i];
+    const float nx = nn[0], ny = nn[1], nz = nn[2];
     const float l2 = (nx * nx + ny * ny) + nz * nz;
     float k0 = 1.f;
     if (l2 > 0.f && l2 < __builtin_inff()) {
@@ -1428,6 +1454,24 @@ extern "C" int a3d_render_shade_lit(const int32_t* id_dev, const float* u_dev, c
   } else {
     k_render_shade_lit<<<blocks, kSesBlock, 0, (hipStream_t)stream>>>(t);
   }
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+extern "C" int a3d_render_shade_lit_points(const int32_t* id_dev, const float* colors_dev, int64_t n, const float* normals_dev,
+                                           const a3d_camera* camera, float ambient, const float* background, uint8_t* rgb_dev,
+                                           void* stream) {
+  RenderCam rc;
+  if (!id_dev || !rgb_dev || !background || n < 0 || (n && (!colors_dev || !normals_dev)) || !(ambient >= 0.f && ambient <= 1.f) ||
+      !render_camera(camera, rc)) {
+    set_error("a3d_render_shade_lit_points: bad arguments (n=%lld ambient=%g; colors_dev, normals_dev and a camera the renders "
+              "accept are needed, ambient in [0, 1])", (long long)n, (double)ambient);
+    return A3D_ERR_INVALID;
+  }
+  LitTab t;
+  t.s = shade_tab(id_dev, nullptr, nullptr, nullptr, 0, colors_dev, n, background, rgb_dev, (long long)camera->width * camera->height);
+  t.normals = normals_dev, t.cam = *camera, t.ambient = ambient;
+  k_render_shade_lit_points<<<(unsigned)((t.s.pixels + kSesBlock - 1) / kSesBlock), kSesBlock, 0, (hipStream_t)stream>>>(t);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

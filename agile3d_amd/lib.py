@@ -222,6 +222,25 @@ class GrowVoxelsArgs(C.Structure):
                 ("reserved_", C.c_int32)]
 
 
+class NormalsSummary(C.Structure):
+    """a3d_normals_summary: counted vertices, voxels with and without a valid normal, the error word (A3D_NORMALS_RANGE,
+    A3D_NORMALS_BAD_INDEX)."""
+    _fields_ = [("counted", C.c_int64), ("valid", C.c_int64), ("invalid", C.c_int64), ("err", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+class EstimateNormalsArgs(C.Structure):
+    """a3d_estimate_normals_args: the scene, the vertices and their inverse map (or NULL), the optional outputs per voxel and
+    per vertex, the summary, the workspace, and by value the fixed-point frame (origin, quantum, bits) and the viewpoint with
+    its flag."""
+    _fields_ = [("scene", C.c_void_p), ("n", C.c_int64), ("xyz_dev", C.c_void_p), ("inverse_map_dev", C.c_void_p),
+                ("n_full", C.c_int64), ("normal_qv_dev", C.c_void_p), ("variation_qv_dev", C.c_void_p),
+                ("count_qv_dev", C.c_void_p), ("moments_qv_dev", C.c_void_p), ("normal_full_dev", C.c_void_p),
+                ("summary_dev", C.c_void_p), ("workspace_dev", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("origin", C.c_double * 3), ("quantum", C.c_double), ("viewpoint", C.c_double * 3), ("bits", C.c_int32),
+                ("has_viewpoint", C.c_int32)]
+
+
 class ObjectMoments(C.Structure):
     """a3d_object_moments: one object of a labelling -- vertices and voxels, the sums of the fixed-point coordinates (X, Y, Z)
     and of their products (XX, XY, XZ, YY, YZ, ZZ), the covered surface in thirds of area quanta, the exact fp32 box."""
@@ -319,6 +338,7 @@ A3D_MEASURE_RANGE, A3D_MEASURE_BAD_LABEL = 1, 2
 A3D_MEASURE_MAX_BITS, A3D_MEASURE_MAX_Q, A3D_MEASURE_MAX_FACES = 20, 1 << 38, 1 << 23
 A3D_MEASURE_BLOCK, A3D_MEASURE_CHUNK = 256, 1024
 A3D_GROW_MAX_STEPS, A3D_GROW_BAD_INDEX = 1024, 1
+A3D_NORMALS_RANGE, A3D_NORMALS_BAD_INDEX = 1, 2
 A3D_ERR_INVALID = -1
 PROF_DENSE = 11
 PROF_NAMES = ["spconv", "splitk_epilogue", "stem", "c2s_attn", "query_chain", "s2c_attn", "ln_mask", "posenc",
@@ -514,6 +534,14 @@ SYMBOLS = {
     "a3d_absorb_pieces": (C.c_int, [C.POINTER(AbsorbPiecesArgs), C.c_void_p]),
     "a3d_grow_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "a3d_grow_voxels": (C.c_int, [C.POINTER(GrowVoxelsArgs), C.c_void_p]),
+    "a3d_normals_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "a3d_estimate_normals": (C.c_int, [C.POINTER(EstimateNormalsArgs), C.c_void_p]),
+    "a3d_normals_solve": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_double,
+                                    C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "a3d_cull_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "a3d_render_shade_lit_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Camera), C.c_float,
+                                              C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "a3d_region_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, C.c_void_p,
                                   C.c_void_p]),
     "a3d_select_vertices": (C.c_int, [C.POINTER(SelectArgs), C.c_void_p]),

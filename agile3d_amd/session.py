@@ -33,6 +33,9 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
     circling what is still wrong and    a3d_region_mask / a3d_select_vertices / a3d_session_overlay  (region_mask, select, paint,
     saying what it is                   erase, corrected: a manual label layer over the model's labels; Open3D gives the
                                         GUI no lasso; a rule of ours)
+    which way a cloud's surface faces   a3d_estimate_normals / a3d_render_shade_lit_points / a3d_cull_points  (estimate_normals,
+                                        normal_at: one normal per voxel from its 27-voxel neighbourhood; after it a cloud is
+                                        lit and culled as a mesh is; the GUI shows clouds unlit; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -350,6 +353,24 @@ def grow_limit(radius, steps, voxel_size):
     if limit // min(cost) > V.GROW_MAX_STEPS:
         raise ValueError(f"that is more than {V.GROW_MAX_STEPS} voxel steps: pieces() answers what is connected at all")
     return cost, limit
+
+
+class NormalsResult:
+    """What ``estimate_normals()`` returns.  Device tensors: ``normals_full`` fp32 [n_full, 3] (unit vectors; zero where the
+    vertex's voxel has no valid normal), ``normals_qv`` fp32 [n_voxels, 3], ``variation_qv`` fp32 [n_voxels] (the surface
+    variation, smallest eigenvalue over the sum: 0 on a plane, 1/3 for a blob), ``count_qv`` int32 [n_voxels] (the vertices of
+    the voxel's 27-voxel neighbourhood).  Host: ``counted`` (vertices that took part), ``valid`` / ``invalid`` (voxels with /
+    without a normal), ``err`` (``view.NORMALS_RANGE``: some coordinate is not finite) and ``viewpoint`` (float64 [3] the
+    normals are turned towards, or ``None``: the canonical sign)."""
+
+    __slots__ = ("normals_full", "normals_qv", "variation_qv", "count_qv", "counted", "valid", "invalid", "err", "viewpoint")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+_MAX_CULLED = 4                                 # culled copies of a cloud kept at a time (one per eye and mode)
 
 
 class CorrectedResult:
@@ -757,7 +778,10 @@ class InteractiveSession:
         self.inverse_map = self.raw_coords_qv = None
         self.faces = None                           # int32 [m, 3] on the device: a triangle-mesh scene (pick meets its surface)
         self._corner_lists = None                   # (offsets int64 [n + 1], corners int32 [3 m]) on the device: a mesh's incidence lists
-        self.normals = None                         # fp32 [n, 3] on the device: a mesh's vertex normals, computed by the first lit render
+        self.normals = None                         # fp32 [n, 3] on the device: a mesh's vertex normals, computed by the first lit
+        #                                             render; a cloud's estimated ones, there after estimate_normals() only
+        self._normals_last = None                   # a cloud's NormalsResult (normal_at's default)
+        self._culled = {}                           # (eye bytes, mode) -> a cloud's culled coordinates; dropped with the normals
         self._coords_host = None
         self._coords_qv_host = None                 # host copy of raw_coords_qv: the points of guide()'s suggestions
         self._vertex_ids = None                     # int32 [n] 0..n-1 on the device, built by the first confidence_at()
@@ -902,9 +926,29 @@ class InteractiveSession:
             raise TypeError("section must be a Section or None")
         if sec is None or (sec.n_planes == 0 and sec.cull == "none"):
             return None, None
-        if not mesh and sec.cull != "none":
+        if not mesh and sec.cull != "none" and not self._cloud_culls():
             raise ValueError(f"a section with cull={sec.cull!r} on a point cloud: only a mesh has faces to cull")
         return sec, sec.struct()
+
+    def _cloud_culls(self):
+        """Whether the scene is a cloud whose normals have been estimated: only then a cloud has sides to cull."""
+        return self.faces is None and self.normals is not None
+
+    def _cloud_under(self, sec, cut, eye):
+        """``(coordinates, lib.Section or None)`` a point-cloud call runs on under ``sec`` (with its ``lib.Section`` ``cut``) for
+        an ``eye`` (fp32 [3]).  Without culling: the scene's own coordinates and ``cut``, today's call.  With it: the culled copy
+        for that eye and mode (``a3d_cull_points``; the culled vertices have NaN coordinates, which no pick, render or
+        selection sees) and the section's planes alone -- ``None`` when it has none: the call without a section."""
+        if sec is None or sec.cull == "none":
+            return self.coords_full, cut
+        key = (np.ascontiguousarray(eye, np.float32).tobytes(), sec.cull)
+        xyz = self._culled.pop(key, None)
+        if xyz is None:
+            while len(self._culled) >= _MAX_CULLED:
+                self._culled.pop(next(iter(self._culled)))              # (the one used longest ago)
+            xyz = V.cull_points(self.coords_full, self.normals, eye, sec.cull, hidden=False, count=False)[0]
+        self._culled[key] = xyz                                         # (most recently used: last)
+        return xyz, sec.with_cull("none").struct() if sec.n_planes else None
 
     # ------------------------------------------------------------------ pick and click
     def pick(self, origin, direction, radius=None, surface=None, section=None):
@@ -915,7 +959,8 @@ class InteractiveSession:
         the rendered depth yields and what ``click`` takes.  ``surface=None`` uses the surface rule when the scene has
         faces, ``False`` forces the vertex rule, ``True`` without faces raises ``ValueError``.  ``section``: a ``Section``
         to pick under (``a3d_pick_mesh_section`` / ``a3d_pick_ray_section``; default: the session's, ``set_section``; an empty
-        ``Section()`` picks without one); culling under the vertex rule raises ``ValueError``."""
+        ``Section()`` picks without one); culling under the vertex rule raises ``ValueError`` -- except on a cloud after
+        ``estimate_normals()``: the pick then runs on the copy of the cloud culled for ``origin`` (``a3d_cull_points``)."""
         self._need_scene()
         o = _f3(origin, "origin")
         d64 = np.asarray(direction, dtype=np.float64).reshape(-1)
@@ -936,10 +981,11 @@ class InteractiveSession:
             return None if hit["face"] < 0 else [float(hit[k]) for k in "xyz"]
         r = self.voxel_size if radius is None else float(radius)
         sec, cut = self._section_of(section, False)
-        if sec is None:
-            out = V.pick_ray(self.coords_full, o, d, r, out=self._small[:4], workspace=self._ws)
+        xyz, cut = self._cloud_under(sec, cut, o)       # (the scene's own coordinates unless a cloud is culled: the eye is the ray's origin)
+        if cut is None:
+            out = V.pick_ray(xyz, o, d, r, out=self._small[:4], workspace=self._ws)
         else:
-            out = V.pick_ray_section(self.coords_full, o, d, r, cut, out=self._small[:4], workspace=self._ws)
+            out = V.pick_ray_section(xyz, o, d, r, cut, out=self._small[:4], workspace=self._ws)
         index, xyz = V.read_pick(out.cpu().numpy())
         return None if index < 0 else [float(v) for v in xyz]
 
@@ -959,7 +1005,7 @@ class InteractiveSession:
         return self.normals
 
     def render(self, intrinsic, extrinsic, width, height, colors=None, radius=None, background=(1.0, 1.0, 1.0), lit=False,
-               ambient=0.35, depth_strength=8.0, section=None):
+               ambient=0.35, depth_strength=8.0, section=None, cloud_shade="auto"):
         """Id, depth and colour images of the scene for a pinhole camera (``camera_from_matrices``): pixel by pixel what
         ``pick`` returns for the ray through the pixel's centre -- faces when the scene has them (``a3d_render_mesh``),
         else vertices within ``radius`` (default ``voxel_size``) of the ray (``a3d_render_points``).  ``colors`` [n, 3]
@@ -969,7 +1015,11 @@ class InteractiveSession:
         computed once per scene on first use; ``a3d_render_shade_lit``: colour x (``ambient`` + (1 - ``ambient``) |cos| of
         the angle between the interpolated normal and the pixel's ray)); on a cloud, which has no normals, a pixel darkens
         by how far it lies behind its four neighbours (``a3d_render_shade_depth``: colour / (1 + ``depth_strength`` x the
-        summed relative depth steps)).  ``ambient`` in [0, 1] and ``depth_strength`` >= 0 are used only when ``lit``; their
+        summed relative depth steps)).  A cloud whose normals have been estimated (``estimate_normals()``) is lit as a mesh
+        is, by its vertices' normals (``a3d_render_shade_lit_points``; a vertex without a valid normal keeps its colour),
+        and may be rendered under a culling section (on the copy culled for the camera's centre, ``a3d_cull_points``);
+        ``cloud_shade="depth"`` still asks for the depth shade (``"auto"``: the normals when there are some).
+        ``ambient`` in [0, 1] and ``depth_strength`` >= 0 are used only when ``lit``; their
         defaults, 0.35 and 8.0, are this project's settings, not the reference's (Open3D's lit material is not
         reproduced).  ``section``: the ``Section`` to render under (``a3d_render_mesh_section`` /
         ``a3d_render_points_section``; default: the session's; an empty ``Section()`` renders without one; culling on a cloud
@@ -995,6 +1045,11 @@ class InteractiveSession:
         col = col.contiguous()
         mesh = self.faces is not None
         sec, cut = self._section_of(section, mesh)
+        if cloud_shade not in ("auto", "depth"):
+            raise ValueError("cloud_shade must be 'auto' or 'depth'")
+        xyz = self.coords_full
+        if not mesh:                                    # (a culled cloud: the copy for the camera's centre, and the planes alone)
+            xyz, cut = self._cloud_under(sec, cut, np.array(cam.o[:], np.float32))
         n_prim = self.faces.shape[0] if mesh else n
         r = self.voxel_size if radius is None else float(radius)
         ids = t = u = v = None                      # (allocated by the first attempt, written again by a retry)
@@ -1011,10 +1066,10 @@ class InteractiveSession:
             elif mesh:
                 ids, t, u, v, _ = V.render_mesh_section(self.coords_full, self.faces, cam, cut, ids, t, u, v, header=header,
                                                         workspace=ws)
-            elif sec is None:
-                ids, t, _ = V.render_points(self.coords_full, r, cam, ids, t, header=header, workspace=ws)
+            elif cut is None:
+                ids, t, _ = V.render_points(xyz, r, cam, ids, t, header=header, workspace=ws)
             else:
-                ids, t, _ = V.render_points_section(self.coords_full, r, cam, cut, ids, t, header=header, workspace=ws)
+                ids, t, _ = V.render_points_section(xyz, r, cam, cut, ids, t, header=header, workspace=ws)
             flags, n_every, pairs = V.read_render_header(header.cpu().numpy())
             if not flags & L.A3D_RENDER_OVERFLOW:
                 break
@@ -1025,6 +1080,8 @@ class InteractiveSession:
             raise RuntimeError("a3d_render_mesh: face indices out of range")
         if lit and mesh:
             rgb = V.render_shade_lit(ids, u, v, self.faces, col, self._vertex_normals(), cam, ambient, bg)
+        elif lit and self.normals is not None and cloud_shade == "auto":
+            rgb = V.render_shade_lit_points(ids, col, self.normals, cam, ambient, bg)
         elif lit:
             rgb = V.render_shade_depth(ids, t, None, None, None, col, depth_strength, bg)
         else:
@@ -1622,7 +1679,8 @@ class InteractiveSession:
         any image of the caller's): a ``SelectResult`` (``a3d_select_vertices``).  A vertex is IN VIEW when it lies in front of
         the camera, projects to a pixel of the image and lies on the kept side of every plane of ``section`` (default: the
         section ``result`` was rendered under; ``None``: none; on a mesh too it is the vertex that is tested, and culling plays
-        no part).  It is selected when its pixel is set in the mask and -- unless ``through`` -- it lies no more than ``slack``
+        no part -- except on a cloud after ``estimate_normals()``, where a culling section leaves only the vertices it shows
+        from the camera's centre).  It is selected when its pixel is set in the mask and -- unless ``through`` -- it lies no more than ``slack``
         world units behind what the pixel shows (``result.t``): the visible side of the scan.  ``through=True`` selects
         everything under the mask, whatever lies in front of it.  The default ``slack`` is the session's voxel size: a vertex
         shares its pixel with its neighbours a voxel away, of which only the nearest is shown.  This is this project's choice
@@ -1638,7 +1696,10 @@ class InteractiveSession:
             raise ValueError("slack must be finite and >= 0")
         if torch.is_tensor(mask) and mask.dtype == torch.bool:
             mask = mask.view(torch.uint8)               # (the same bytes: 0 or 1)
-        selected, summary = V.select_vertices(self.coords_full, result.camera, mask, None if through else result.t, slack,
+        xyz = self.coords_full
+        if sec is not None and sec.cull != "none" and self._cloud_culls():      # only the vertices the culled view shows
+            xyz = self._cloud_under(sec, None, np.array(result.camera.o[:], np.float32))[0]
+        selected, summary = V.select_vertices(xyz, result.camera, mask, None if through else result.t, slack,
                                               None if sec is None or sec.n_planes == 0 else sec.struct(),
                                               summary=self._region_sum[:V.SELECT_SUMMARY.itemsize])
         s = V.read_select_summary(summary.cpu().numpy())                # the one host round trip
@@ -1976,3 +2037,63 @@ class InteractiveSession:
             raise ValueError("the guide belongs to another scene")
         vertex = self._vertex_at(result, u, v)
         return None if vertex < 0 else float(guide.margin_full[vertex].cpu())
+
+    # ------------------------------------------------------------------ which way the surface faces
+    def estimate_normals(self, viewpoint="centre"):
+        """One normal per voxel from the vertices of its 3 x 3 x 3 neighbourhood, lifted to the vertices
+        (``a3d_estimate_normals``: exact integer moments in the fixed-point frame of ``measure()``, then one fixed sequence of
+        double operations per voxel -- two calls give the same bytes).  ``viewpoint``: a point [x, y, z] the normals are
+        turned towards; ``"centre"``, the centre of the scene's bounding box -- right for the walls, floor and ceiling of a
+        room scanned from inside, and this project's choice, not tuned on real scans; or ``None``: the canonical sign (the
+        component of largest magnitude positive).  A voxel whose neighbourhood holds fewer than 3 vertices, or only a line
+        of them, gets no normal (zeros).  All vertices of a voxel share its normal: shading is faceted at the voxel size.
+
+        On a CLOUD the normals are kept with the scene (``ses.normals``; ``load_scene`` drops them, ``reset`` keeps them, a
+        second call replaces them): from then on ``render(lit=True)`` lights the cloud by them and a ``Section`` with
+        ``cull="back"`` / ``"front"`` is accepted by ``pick``, ``click_ray``, ``render`` and ``select``, which run on the copy
+        of the cloud culled for the call's eye -- the ray's origin, the camera's centre (``a3d_cull_points``; a few copies are
+        kept, one per eye and mode).  On a MESH the result is returned and no session state changes: a mesh is lit and
+        culled by its faces.  One host round trip (the summary).  Returns a ``NormalsResult``."""
+        self._need_scene()
+        origin, quantum, bits = self._fixed_point_frame()
+        if viewpoint is None:
+            vp = None
+        elif isinstance(viewpoint, str):
+            if viewpoint != "centre":
+                raise ValueError("viewpoint must be a point, 'centre' or None")
+            vp = np.array(origin, np.float64)
+        else:
+            vp = np.asarray(viewpoint, dtype=np.float64).reshape(-1)
+            if vp.shape != (3,) or not np.isfinite(vp).all():
+                raise ValueError("viewpoint must be three finite numbers, 'centre' or None")
+        normal_qv, variation_qv, count_qv, _, normal_full, summary, _ = V.estimate_normals(
+            self._scene_handle(), self.coords_full, origin, quantum, bits, inverse_map=self.inverse_map, viewpoint=vp,
+            moments_qv=False, summary=self._region_sum[:V.NORMALS_SUMMARY.itemsize])
+        s = V.read_normals_summary(summary.cpu().numpy())               # the one host round trip
+        if s["err"] & V.NORMALS_BAD_INDEX:
+            raise RuntimeError("a3d_estimate_normals: inverse_map out of range")
+        res = NormalsResult(normals_full=normal_full, normals_qv=normal_qv, variation_qv=variation_qv, count_qv=count_qv,
+                            counted=s["counted"], valid=s["valid"], invalid=s["invalid"], err=s["err"], viewpoint=vp)
+        if self.faces is None:
+            self.normals, self._normals_last, self._culled = normal_full, res, {}
+        return res
+
+    def normal_at(self, result, u, v, normals=None):
+        """``(normal fp32 [3], variation)`` of the vertex that pixel ``(u, v)`` (column, row) of ``result`` shows, or ``None``
+        where the pixel shows nothing: on a cloud the pixel's vertex, on a mesh the heaviest corner of its face, as
+        ``confidence_at`` resolves it.  ``normals``: a ``NormalsResult`` of this scene (default: the one ``estimate_normals()``
+        left with a cloud; ``ValueError`` when there is none).  A vertex whose voxel has no valid normal gives zeros and 0.
+        Two small device-to-host copies."""
+        self._need_scene()
+        normals = self._normals_last if normals is None else normals
+        if not isinstance(normals, NormalsResult):
+            raise ValueError("normal_at() reads a NormalsResult: estimate_normals() first (on a mesh, pass its result)")
+        if tuple(normals.normals_full.shape) != (self.coords_full.shape[0], 3) or \
+                tuple(normals.variation_qv.shape) != (self.raw_coords_qv.shape[0],):
+            raise ValueError("the normals belong to another scene")
+        vertex = self._vertex_at(result, u, v)
+        if vertex < 0:
+            return None
+        row = self.inverse_map[vertex]
+        both = torch.cat([normals.normals_full[vertex], normals.variation_qv[row].reshape(1)]).cpu().numpy()
+        return both[:3].copy(), float(both[3])

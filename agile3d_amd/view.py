@@ -781,6 +781,136 @@ def object_extents(xyz, labels, axes, extents=None, err=None):
     return extents, err
 
 
+# ---- normals for point clouds: the estimate, the lit pass, the culled copy -------------------------------------------------------
+NORMALS_SUMMARY = np.dtype([("counted", "<i8"), ("valid", "<i8"), ("invalid", "<i8"), ("err", "<i4"), ("reserved_", "<i4")])
+assert C.sizeof(L.NormalsSummary) == NORMALS_SUMMARY.itemsize == 32
+assert C.sizeof(L.EstimateNormalsArgs) == 168
+NORMALS_RANGE, NORMALS_BAD_INDEX = L.A3D_NORMALS_RANGE, L.A3D_NORMALS_BAD_INDEX      # the bits of the summary's error word
+CULL_MODES = {"back": L.A3D_CULL_BACK, "front": L.A3D_CULL_FRONT}
+
+
+def read_normals_summary(host):
+    """The host copy of an ``a3d_normals_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints:
+    ``counted`` (vertices), ``valid`` / ``invalid`` (voxels with / without a normal), ``err`` (``NORMALS_RANGE``,
+    ``NORMALS_BAD_INDEX``)."""
+    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:NORMALS_SUMMARY.itemsize].view(NORMALS_SUMMARY)[0]
+    return {k: int(rec[k]) for k in ("counted", "valid", "invalid", "err")}
+
+
+def normals_workspace(n, device):
+    """The scratch of ``estimate_normals`` for n voxels (``a3d_normals_workspace_bytes``)."""
+    nbytes = L.load().a3d_normals_workspace_bytes(n)
+    if nbytes == 0:
+        raise ValueError(f"no normals workspace for n={n}")
+    return torch.empty(nbytes, dtype=U8, device=device)
+
+
+def _three_finite(name, values):
+    a = np.asarray(values, dtype=np.float64).reshape(-1)
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be three finite numbers")
+    return a.tolist()
+
+
+def estimate_normals(scene, xyz, origin, quantum, bits=L.A3D_MEASURE_MAX_BITS, inverse_map=None, viewpoint=None, normal_qv=None,
+                     variation_qv=None, count_qv=None, moments_qv=None, normal_full=None, summary=None, workspace=None):
+    """``a3d_estimate_normals``: one unoriented normal per voxel of ``scene`` (an ``engine.Scene``; n rows in the caller's
+    order) from the vertices ``xyz`` fp32 [n_full, 3] of its 3 x 3 x 3 neighbourhood -- ``inverse_map`` int64 [n_full] names
+    each vertex's voxel (``None``: the identity) -- lifted to the vertices.  ``origin``, ``quantum``, ``bits``: the fixed-point
+    frame of ``measure_objects`` (three finite numbers, a positive power of two, 0..20 with ``n_full * 2^(2 bits) <= 2^62``).
+    ``viewpoint``: three finite numbers the normals are turned towards, or ``None``: the component of largest magnitude is
+    made positive.  Outputs: a tensor of the caller's, ``None`` = allocated, ``False`` = not wanted.  Returns ``(normal_qv fp32
+    [n, 3], variation_qv fp32 [n], count_qv int32 [n], moments_qv int64 [n, 10], normal_full fp32 [n_full, 3], summary uint8
+    [32], workspace)`` on the device, ``None`` for what was not wanted; ``read_normals_summary`` decodes the summary's host
+    copy."""
+    handle, n = _scene_rows(scene)
+    dev = _device("xyz", xyz)
+    a = L.EstimateNormalsArgs()
+    a.scene, a.n = handle, n
+    a.xyz_dev = _ptr("xyz", xyz, F32, (None, 3), dev)
+    a.n_full = n_full = xyz.shape[0]
+    a.inverse_map_dev = _ptr("inverse_map", inverse_map, I64, (n_full,), dev, optional=True)
+    if isinstance(bits, bool) or int(bits) != bits or not 0 <= bits <= L.A3D_MEASURE_MAX_BITS:
+        raise ValueError(f"bits must be an integer in 0 .. {L.A3D_MEASURE_MAX_BITS}")
+    a.bits = int(bits)
+    if n_full >= 1 << 31 or n_full << (2 * a.bits) > 1 << 62:
+        raise ValueError(f"{n_full} vertices at bits={a.bits}: the sums could overflow (n_full * 2^(2 bits) <= 2^62)")
+    a.origin[:] = _three_finite("origin", origin)
+    a.quantum = _power_of_two("quantum", quantum)
+    a.has_viewpoint = int(viewpoint is not None)
+    if viewpoint is not None:
+        a.viewpoint[:] = _three_finite("viewpoint", viewpoint)
+    outs = []
+    for name, t, dtype, shape in (("normal_qv", normal_qv, F32, (n, 3)), ("variation_qv", variation_qv, F32, (n,)),
+                                  ("count_qv", count_qv, I32, (n,)), ("moments_qv", moments_qv, I64, (n, 10)),
+                                  ("normal_full", normal_full, F32, (n_full, 3))):
+        t = None if t is False else _out(name, t, dtype, shape, dev)
+        setattr(a, name + "_dev", t.data_ptr() if t is not None and shape[0] else None)
+        outs.append(t)
+    summary = _summary(summary, NORMALS_SUMMARY.itemsize, dev)
+    a.summary_dev = summary.data_ptr()
+    if workspace is None:
+        workspace = normals_workspace(n, dev)
+    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
+    if a.workspace_bytes < L.load().a3d_normals_workspace_bytes(n) or workspace.data_ptr() % 256:
+        raise ValueError("workspace too small or not 256-byte aligned (normals_workspace(n, device))")
+    L.check(L.load().a3d_estimate_normals(C.byref(a), L.stream(dev)), "a3d_estimate_normals")
+    return (*outs, summary, workspace)
+
+
+def normals_solve(count, sums, moments, origin, quantum, viewpoint=None):
+    """``a3d_normals_solve`` (host only, no GPU): stage B of ``a3d_estimate_normals`` for ONE neighbourhood from its integer
+    sums -- ``count``, ``sums`` [3] (X, Y, Z), ``moments`` [6] (XX, XY, XZ, YY, YZ, ZZ), each an integer an int64 holds -- by the
+    function the kernel calls: ``(normal fp32 [3], variation numpy.float32, valid bool)``."""
+    s = (C.c_int64 * 3)(*[int(v) for v in sums])
+    m = (C.c_int64 * 6)(*[int(v) for v in moments])
+    o = (C.c_double * 3)(*_three_finite("origin", origin))
+    vp = None if viewpoint is None else (C.c_double * 3)(*_three_finite("viewpoint", viewpoint))
+    out = np.zeros(5, np.float32)
+    L.check(L.load().a3d_normals_solve(int(count), s, m, o, _power_of_two("quantum", quantum), vp,
+                                       out.ctypes.data_as(C.POINTER(C.c_float))), "a3d_normals_solve")
+    return out[:3].copy(), out[3], bool(out[4])
+
+
+def render_shade_lit_points(ids, colors, normals, cam, ambient, background, rgb=None):
+    """``a3d_render_shade_lit_points``: a cloud's colours lit from the camera by per-vertex normals fp32 [n, 3] (the
+    ``normal_full`` of ``estimate_normals``); a vertex with a zero normal keeps its colour."""
+    dev, (h, w), (ip, _, _, _, cp), _, n, (bg, bgp), rgb = _shade_args(ids, None, None, None, colors, background, rgb)
+    if (h, w) != (cam.height, cam.width):
+        raise ValueError(f"ids must have the camera's shape [{cam.height}, {cam.width}]")
+    ambient = float(ambient)
+    if not 0.0 <= ambient <= 1.0:                       # (NaN fails both)
+        raise ValueError("ambient must lie in [0, 1]")
+    np_ = _ptr("normals", normals, F32, (n, 3), dev)
+    L.check(L.load().a3d_render_shade_lit_points(ip, cp, n, np_, C.byref(cam), ambient, bgp, rgb.data_ptr(), L.stream(dev)),
+            "a3d_render_shade_lit_points")
+    return rgb
+
+
+def cull_points(xyz, normals, eye, mode, out=None, hidden=None, count=None):
+    """``a3d_cull_points``: the copy of ``xyz`` fp32 [n, 3] in which the vertices whose normal (``normals`` fp32 [n, 3]) points
+    away from ``eye`` (``mode="back"``) or towards it (``"front"``) have NaN coordinates -- what the picks, the renders and
+    ``select_vertices`` then do not see.  ``eye``: three finite numbers (rounded to fp32).  ``hidden`` uint8 [n] and ``count``
+    int64 [1]: a tensor of the caller's, ``None`` = allocated, ``False`` = not wanted.  Returns ``(out, hidden, count)`` on the
+    device."""
+    if mode not in CULL_MODES:
+        raise ValueError(f"mode must be one of {sorted(CULL_MODES)}, not {mode!r}")
+    dev = _device("xyz", xyz)
+    xp = _ptr("xyz", xyz, F32, (None, 3), dev)
+    n = xyz.shape[0]
+    np_ = _ptr("normals", normals, F32, (n, 3), dev)
+    if max(abs(c) for c in _three_finite("eye", eye)) > float(np.finfo(np.float32).max):
+        raise ValueError("eye must be three finite numbers in fp32")
+    e, ep = _f32p("eye", eye, (3,))
+    out = _out("out", out, F32, (n, 3), dev)
+    hidden = None if hidden is False else _out("hidden", hidden, U8, (n,), dev)
+    count = None if count is False else _out("count", count, I64, (1,), dev)
+    L.check(L.load().a3d_cull_points(xp, np_, n, ep, CULL_MODES[mode], out.data_ptr() if n else None,
+                                     hidden.data_ptr() if hidden is not None and n else None,
+                                     count.data_ptr() if count is not None else None, L.stream(dev)), "a3d_cull_points")
+    return out, hidden, count
+
+
 # ---- correcting by hand: a screen region, the vertices seen inside it, the manual layer ----------------------------------------
 SELECT_SUMMARY = np.dtype([("selected", "<i8"), ("in_view", "<i8"), ("flags", "<i4"), ("reserved_", "<i4")])
 OVERLAY_SUMMARY = np.dtype([("changed", "<i8"), ("overridden", "<i8"), ("differing", "<i8"), ("err", "<i4"), ("reserved_", "<i4")])

@@ -1197,6 +1197,102 @@ typedef struct a3d_extents_args {
 } a3d_extents_args;
 int    a3d_object_extents(const a3d_extents_args* args, void* stream);
 
+/* WHICH WAY THE SURFACE FACES: one unoriented normal per level-0 voxel, from the points of its 3 x 3 x 3 neighbourhood, lifted
+ * to the vertices (csrc/session_normals.hip).  With it a point cloud is lit (a3d_render_shade_lit_points) and culled
+ * (a3d_cull_points) as a mesh is.  The rule is this library's: the reference shows clouds unlit.  Two stages: the first is
+ * INTEGER, so that the order in which workgroups run cannot matter; the second is ONE SEQUENTIAL double-precision
+ * computation per voxel, every operation rounded on its own (no fma contraction), using only + - x / sqrt (all correctly
+ * rounded) in the order written: a restatement in float64 scalars gives the same bits (tests/normals_rule.py).
+ *
+ * a3d_estimate_normals.  scene, n = its level-0 size (rows in the CALLER's order); xyz_dev fp32 [n_full][3];
+ * inverse_map_dev int64 [n_full], NULL = the identity; origin (doubles, finite), quantum (a positive power of two) and bits
+ * (0..20) by value, a3d_measure_objects' fixed-point frame; optionally viewpoint (doubles, finite) with has_viewpoint != 0.
+ *   STAGE A, per vertex i: row = inverse_map[i];  X_a = llrint(((double)x_a - origin[a]) / quantum), round half to even.
+ *   The vertex COUNTS when 0 <= row < n and |X_a| <= 2^bits on every axis.  Else it contributes nothing: a row outside sets
+ *   A3D_NORMALS_BAD_INDEX, a coordinate outside -- or one that is not finite -- sets A3D_NORMALS_RANGE (a vertex can set
+ *   both).  Per voxel (caller row), over the vertices that count: cnt (int32), sum[3] = the sums of X_a, mom[6] = the sums of
+ *   (XX, XY, XZ, YY, YZ, ZZ), int64, by integer atomics.
+ *   OVERFLOW BOUND, a3d_measure_objects': no sum can leave int64 while n_full * 2^(2 bits) <= 2^62; the call refuses any
+ *   other n_full, and n_full >= 2^31.
+ *   STAGE B, per voxel: the NEIGHBOURHOOD is the voxel and its present neighbours in A3D_TAB_NBR27, all 27 offsets, both ends
+ *   through A3D_TAB_ORIGROW: never across batch samples.  N, S_a, M_ab = the integer sums of cnt, sum, mom over it.
+ *   N < 3: no normal.  Else recentre EXACTLY, in integers, about R_a = floor(S_a / N):
+ *       s_a = S_a - N R_a;       m_ab = M_ab - R_a S_b - R_b S_a + N R_a R_b
+ *   (= the sums of (X_a - R_a) and (X_a - R_a)(X_b - R_b): 0 <= s_a < N, and m_aa <= M_aa + N since the sum of squares about
+ *   the mean is the least, so both fit int64 and wrapping 64-bit arithmetic yields them exactly whatever the intermediates do).
+ *   Convert s_a, m_ab and N to double (round to nearest even).  From here on doubles:
+ *       C_ab = m_ab - (s_a * s_b) / N                              (a, b = 0..2; C is symmetric, V starts as the identity)
+ *   6 SWEEPS of cyclic Jacobi, each over the pairs (p, q) = (0, 1), (0, 2), (1, 2) in this order, r the third index.  A pair
+ *   whose C_pq == 0 is skipped.  Else, with app = C_pp, aqq = C_qq, apq = C_pq:
+ *       theta = (aqq - app) / (2 * apq)
+ *       t = 1 / (|theta| + sqrt(theta * theta + 1));   if theta < 0: t = -t      (an infinite theta * theta gives t = 0)
+ *       c = 1 / sqrt(t * t + 1);   s = t * c;   h = t * apq
+ *       C_pp = app - h;   C_qq = aqq + h;   C_pq = C_qp = 0
+ *       arp = C_rp, arq = C_rq:   C_rp = C_pr = c * arp - s * arq;   C_rq = C_qr = s * arp + c * arq
+ *       for k = 0..2, vkp = V_kp, vkq = V_kq:   V_kp = c * vkp - s * vkq;   V_kq = s * vkp + c * vkq
+ *   d = (C_00, C_11, C_22).  imin = 0; if d_1 < d_imin: imin = 1; if d_2 < d_imin: imin = 2 (ties: the lowest index); imax
+ *   likewise with >; d_mid = d of the remaining index, or d_imin when imin == imax.  The normal is VALID iff
+ *   d_mid * 2^20 > d_imax and d_imax < +inf (the product is exact): a neighbourhood narrower than 1/1024 of its length, in
+ *   standard deviation, is a line and has no normal.  v = column imin of V.
+ *   THE SIGN.  With a viewpoint:  mean_a = origin[a] + quantum * ((double)R_a + s_a / N);
+ *       g = (v_0 * (vp_0 - mean_0) + v_1 * (vp_1 - mean_1)) + v_2 * (vp_2 - mean_2);   g < 0: v = -v (towards the viewpoint)
+ *   Without: the component of largest |v_a| (the first of equals) is made positive: if it is < 0, v = -v.
+ *   normal = (float)v per component;  variation = (float)(max(d_imin, 0) / ((d_0 + d_1) + d_2)), 0 when that sum is not > 0
+ *   (the surface variation: 0 on a plane, 1/3 for an isotropic blob).  A voxel without a valid normal has normal (0, 0, 0)
+ *   and variation 0.
+ *   THE LIFT: normal_full[i] = normal_qv[inverse_map[i]], (0, 0, 0) for a row outside 0..n-1.
+ *   OUTPUTS, all optional but the summary: normal_qv_dev fp32 [n][3], variation_qv_dev fp32 [n], count_qv_dev int32 [n] (the
+ *   neighbourhood's N), moments_qv_dev int64 [n][10] (stage A's own words of the voxel: cnt, sum[3], mom[6]), normal_full_dev
+ *   fp32 [n_full][3].  The summary (cleared by the call): counted vertices, voxels with and without a valid normal, the error
+ *   word.  Integer sums, one atomic per workgroup and counter.
+ *   The workspace: a3d_normals_workspace_bytes(n) bytes, 256-byte aligned, cleared by the call.  The library allocates
+ *   nothing and does not synchronise; the stages are launches -- no grid barrier, no spin-wait.  Two calls give the same
+ *   bytes in every output, and so does any permutation of the vertices (with their map entries).
+ *   A3D_ERR_INVALID with nothing launched and nothing written: no arguments, no scene, n != the scene's level-0 size, n_full
+ *   > 0 without xyz_dev, n_full < 0 or beyond the bound above, bits outside 0..20, a quantum that is not a positive power of
+ *   two, an origin or (with has_viewpoint) a viewpoint that is not finite, no summary_dev, a workspace that is missing, too
+ *   small or misaligned.
+ *   LIMITS: all vertices of a voxel share one normal (shading is faceted at the voxel size); the sign is only as good as the
+ *   viewpoint (no propagation between voxels). */
+#define A3D_NORMALS_RANGE     1
+#define A3D_NORMALS_BAD_INDEX 2
+typedef struct a3d_normals_summary {
+  int64_t counted;                  /* vertices that counted */
+  int64_t valid;                    /* voxels with a valid normal */
+  int64_t invalid;                  /* voxels without one */
+  int32_t err;                      /* A3D_NORMALS_RANGE | A3D_NORMALS_BAD_INDEX */
+  int32_t reserved_;
+} a3d_normals_summary;             /* 32 bytes */
+typedef struct a3d_estimate_normals_args {
+  const a3d_scene* scene;
+  int64_t        n;
+  const float*   xyz_dev;           /* [n_full][3] */
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL: identity */
+  int64_t        n_full;
+  float*         normal_qv_dev;     /* out [n][3] or NULL */
+  float*         variation_qv_dev;  /* out [n] or NULL */
+  int32_t*       count_qv_dev;      /* out [n] or NULL */
+  int64_t*       moments_qv_dev;    /* out [n][10] or NULL */
+  float*         normal_full_dev;   /* out [n_full][3] or NULL */
+  a3d_normals_summary* summary_dev;
+  void*          workspace_dev;
+  size_t         workspace_bytes;
+  double         origin[3];
+  double         quantum;
+  double         viewpoint[3];      /* looked at only with has_viewpoint */
+  int32_t        bits;
+  int32_t        has_viewpoint;
+} a3d_estimate_normals_args;       /* 168 bytes */
+size_t a3d_normals_workspace_bytes(int64_t n);
+int    a3d_estimate_normals(const a3d_estimate_normals_args* args, void* stream);
+
+/* Host only, no GPU: STAGE B of one neighbourhood from its integer sums (count = N, sum3 = S, mom6 = M; HOST arrays), by the
+ * function the kernel calls: out5 = normal[3], variation, valid as 0 or 1.  origin: a HOST array of 3; viewpoint: a HOST
+ * array of 3, or NULL for the sign without one.  A3D_ERR_INVALID for a NULL array, count < 0 or a quantum that is not a
+ * positive power of two. */
+int    a3d_normals_solve(int64_t count, const int64_t* sum3, const int64_t* mom6, const double* origin, double quantum,
+                         const double* viewpoint, float* out5);
+
 /* ------------------------------------------------------------------------------------------
  * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
  * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a
@@ -1370,6 +1466,36 @@ int    a3d_vertex_normals(const float* xyz_dev, int64_t n, const int32_t* faces_
 int    a3d_render_shade_lit(const int32_t* id_dev, const float* u_dev, const float* v_dev, const int32_t* faces_dev, int64_t m,
                             const float* colors_dev, int64_t n, const float* normals_dev, const a3d_camera* camera,
                             float ambient, const float* background, uint8_t* rgb_dev, void* stream);
+
+/* Lit colour image of a POINT CLOUD render whose vertices have been given normals (a3d_estimate_normals' normal_full): the
+ * inputs of a3d_render_shade for a cloud (ids are vertices; width and height are the camera's), normals_dev fp32 [n][3], the
+ * camera that rendered the ids and ambient in [0, 1].  Per pixel with 0 <= id < n (else the background, unshaded): the base
+ * colour c = the vertex's; N = normals[id] as stored;
+ *     l2 = (Nx*Nx + Ny*Ny) + Nz*Nz;     d = the pixel's unit ray direction by the a3d_camera rule
+ *     k0 = fminf(fabsf((Nx*dx + Ny*dy) + Nz*dz) / sqrtf(l2), 1) if l2 > 0 and finite, else k0 = 1
+ *     k  = ambient + (1 - ambient) * k0;           each channel c * k, then a3d_render_shade's quantisation
+ * -- a3d_render_shade_lit's rule with the pixel's vertex in place of the interpolated corner normals.  A vertex without a
+ * valid normal (zero, NaN) keeps its colour.  ambient == 1 gives a3d_render_shade's image byte for byte. */
+int    a3d_render_shade_lit_points(const int32_t* id_dev, const float* colors_dev, int64_t n, const float* normals_dev,
+                                   const a3d_camera* camera, float ambient, const float* background, uint8_t* rgb_dev,
+                                   void* stream);
+
+/* CULLING A CLOUD without touching a render or pick kernel (csrc/session_normals.hip): xyz_out_dev fp32 [n][3] = a copy of
+ * xyz_dev in which every culled vertex has all three coordinates NaN (bits 0x7fc00000).  eye: a HOST array of 3, finite;
+ * mode A3D_CULL_BACK or A3D_CULL_FRONT.  Per vertex, in fp32, every operation rounded on its own:
+ *     g = (Nx*(x - ex) + Ny*(y - ey)) + Nz*(z - ez)
+ * The vertex is BACK when g > 0 (its normal points away from the eye) and FRONT when g < 0; A3D_CULL_BACK hides the BACK
+ * vertices, A3D_CULL_FRONT the FRONT ones.  A zero or NaN normal, a NaN coordinate, or g == 0 is neither: the vertex is
+ * copied as it is.  Optionally hidden_dev uint8 [n] (1 = hidden, every byte written) and count_dev int64 [1] (8-byte
+ * aligned, cleared by the call: the hidden vertices, one atomic per workgroup).  xyz_out_dev may be xyz_dev itself.
+ * WHY THIS IS ENOUGH: a vertex with NaN coordinates fails a3d_pick_ray's test, is binned nowhere by the view (its exact
+ * test never passes) and is in view nowhere for a3d_select_vertices, so picks, renders and selections of the copy see
+ * exactly the vertices that show, the ids stay vertex ids, and "the image is what a click through that pixel picks" keeps
+ * holding as long as pick and view use the copy of the same eye.  (A selection of the copy reports A3D_SELECT_NOT_FINITE.)
+ * A3D_ERR_INVALID with nothing launched: n < 0 or n >= 2^31, a mode that is neither, eye NULL or not finite, n > 0 with
+ * xyz_dev, normals_dev or xyz_out_dev NULL, a misaligned count_dev.  No workspace. */
+int    a3d_cull_points(const float* xyz_dev, const float* normals_dev, int64_t n, const float* eye, int mode,
+                       float* xyz_out_dev, uint8_t* hidden_dev, int64_t* count_dev, void* stream);
 
 /* Depth-shaded colour image, for POINT CLOUDS (which have no normals): the inputs of a3d_render_shade, the render's t image
  * t_dev fp32 [h][w] and strength >= 0 (finite).  For a pixel p whose base colour c is not the background:
