@@ -1,5 +1,8 @@
-// session_pieces.hip -- the connected pieces of a labelling on the voxel lattice, and the despeckle step that gives a
-// small piece to its surroundings (gfx950).  Two entry points: a3d_label_pieces and a3d_absorb_pieces.
+// session_pieces.hip -- the connected pieces of a labelling on the voxel lattice, the despeckle step that gives a small
+// piece to its surroundings, the pieces under a SIMILARITY of normals and colours (smooth patches, the magic wand) and the
+// vote that snaps a labelling to such a partition (gfx950).  Entry points: a3d_label_pieces, a3d_absorb_pieces,
+// a3d_similar_pieces, a3d_vote_pieces -- and a3d_similar_pair, the pair predicate on the host by the function the kernel
+// calls, for the tests without a GPU.
 //
 // The reference has no counterpart: its tool keeps an arg-max per voxel and never asks where in space a label lies.
 // THE RULES (ours, stated in include/agile3d_hip.h at the two entry points):
@@ -36,8 +39,21 @@
 // turns counts into offsets), so the list comes out in root order without an atomic append.
 // ABSORB: small pieces are numbered by the same one-block scan; votes are integer atomicAdds into votes[small][label].
 // Sums of integers, minima and maxima do not depend on the order of arrival: two calls give the same bytes.
+//
+// SIMILAR PIECES: the same three launches with another edge test.  k_similar_init writes parent[i] = -1 for a row that is
+// not ADMISSIBLE (key < 0, or it fails the test against the reference normal / colour); k_similar_hook unites two admissible
+// neighbours of one key when sim_normals and sim_feats pass (fp32, one rounding per operation, stated in the header).  Both
+// are symmetric bit for bit, so it does not matter that only the end that looks into the half-space evaluates them, and the
+// order-free argument above holds unchanged: the classes are a function of the arguments, the root is the minimum.
+// The hook issues a stage's loads TOGETHER: 13 table entries, then 13 caller rows, then 13 keys / normals / colours, each
+// into registers with constant indices (a missing neighbour reads the thread's own row, so no load hangs on a branch); the
+// 13 bits that survive are then united one by one -- that part is a dependent chain by nature.
+// VOTE: the eligible pieces (>= min_voxels) are numbered by the one-block scan; votes[slot][label] are integer atomicAdds;
+// one thread per eligible root picks the winner, tests the share in int64 and looks through the clicks for one that
+// contradicts it.
 #include "common.h"
 
+#include <cmath>
 #include <cstdlib>
 
 namespace a3d {
@@ -237,7 +253,7 @@ __global__ __launch_bounds__(kPiecesScan) void k_pieces_records(const a3d_label_
   for (int i = lo; i < hi && run < a.max_out; ++i)
     if (piece[i] == i) {
       a3d_piece rec;
-      rec.root = i, rec.key = keys[i], rec.voxels = w.size[i], rec.clicked = w.clicked[i];
+      rec.root = i, rec.key = keys ? keys[i] : 0, rec.voxels = w.size[i], rec.clicked = w.clicked[i];
 #pragma unroll
       for (int c = 0; c < 3; ++c) rec.lo[c] = w.lo[(size_t)c * n + i], rec.hi[c] = w.hi[(size_t)c * n + i];
       a.out_dev[run++] = rec;
@@ -346,6 +362,226 @@ __global__ __launch_bounds__(kPiecesBlock) void k_absorb_write(const a3d_absorb_
   }
 }
 
+// ---- similar pieces -------------------------------------------------------------------------------------------------------
+// NSIM and FSIM of the header: every operation rounded on its own, in the order written; a NaN fails the comparison.
+__host__ __device__ inline bool sim_normals(const float a0, const float a1, const float a2, const float b0, const float b1,
+                                            const float b2, const float c, const int oriented) {
+#pragma clang fp contract(off)
+  const float dot = (a0 * b0 + a1 * b1) + a2 * b2;
+  return (oriented ? dot : fabsf(dot)) >= c;
+}
+__host__ __device__ inline bool sim_feats(const float a0, const float a1, const float a2, const float b0, const float b1,
+                                          const float b2, const float t) {
+#pragma clang fp contract(off)
+  const float d0 = a0 - b0, d1 = a1 - b1, d2 = a2 - b2;
+  const float q = (d0 * d0 + d1 * d1) + d2 * d2;
+  return q <= t;
+}
+
+struct SimilarTab {
+  const int32_t* keys;       // [n] or NULL: all 0
+  const float* normal;       // [n][3] or NULL
+  const float* feat;         // [n][3] or NULL
+  float cos_min, tol2, ref_cos_min, ref_tol2;
+  float ref_normal[3], ref_feat[3];
+  int oriented, ref_flags;
+};
+
+__global__ __launch_bounds__(kPiecesBlock) void k_similar_init(const SimilarTab s, const PiecesWs w, const int n) {
+  const int stride = gridDim.x * kPiecesBlock;
+  for (int i = blockIdx.x * kPiecesBlock + threadIdx.x; i < n; i += stride) {
+    bool ok = !s.keys || s.keys[i] >= 0;
+    if (s.ref_flags & A3D_SIMILAR_REF_NORMAL) {
+      const float* a = s.normal + 3 * (size_t)i;
+      ok = ok && sim_normals(a[0], a[1], a[2], s.ref_normal[0], s.ref_normal[1], s.ref_normal[2], s.ref_cos_min, s.oriented);
+    }
+    if (s.ref_flags & A3D_SIMILAR_REF_FEAT) {
+      const float* a = s.feat + 3 * (size_t)i;
+      ok = ok && sim_feats(a[0], a[1], a[2], s.ref_feat[0], s.ref_feat[1], s.ref_feat[2], s.ref_tol2);
+    }
+    w.parent[i] = ok ? i : -1;
+    w.size[i] = 0, w.clicked[i] = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w.lo[(size_t)c * n + i] = 0x7fffffff, w.hi[(size_t)c * n + i] = (int32_t)0x80000000;
+  }
+}
+
+template <bool HAS_N, bool HAS_F>
+__global__ __launch_bounds__(kPiecesBlock) void k_similar_hook(const SimilarTab s, const PiecesTab t, int32_t* parent) {
+  const int stride = gridDim.x * kPiecesBlock;
+  for (int r = blockIdx.x * kPiecesBlock + threadIdx.x; r < t.n; r += stride) {
+    const int i = t.orig[r];
+    if (parent_now(parent, i) < 0) continue;             // not admissible: -1 since k_similar_init, never written again
+    int j[13];
+#pragma unroll
+    for (int k = 0; k < 13; ++k) j[k] = ((t.mask >> k) & 1u) ? t.nbr[(size_t)k * t.npad + r] : t.n;
+    unsigned join = 0;
+#pragma unroll
+    for (int k = 0; k < 13; ++k) {
+      const bool there = (unsigned)j[k] < (unsigned)t.n;
+      join |= (there ? 1u : 0u) << k;
+      j[k] = t.orig[there ? j[k] : r];                   // a missing neighbour reads this thread's own row: no load waits on a branch
+    }
+    if (s.keys) {
+      const int key = s.keys[i];
+      int kj[13];
+#pragma unroll
+      for (int k = 0; k < 13; ++k) kj[k] = s.keys[j[k]];
+#pragma unroll
+      for (int k = 0; k < 13; ++k) join &= ~((kj[k] != key ? 1u : 0u) << k);
+    }
+    if (s.ref_flags) {                                   // (without a reference, admissible = key >= 0, and the keys are equal)
+      int pj[13];
+#pragma unroll
+      for (int k = 0; k < 13; ++k) pj[k] = parent_now(parent, j[k]);
+#pragma unroll
+      for (int k = 0; k < 13; ++k) join &= ~((pj[k] < 0 ? 1u : 0u) << k);
+    }
+    if (HAS_N) {
+      const float a0 = s.normal[3 * (size_t)i], a1 = s.normal[3 * (size_t)i + 1], a2 = s.normal[3 * (size_t)i + 2];
+      float b[13][3];
+#pragma unroll
+      for (int k = 0; k < 13; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b[k][c] = s.normal[3 * (size_t)j[k] + c];
+#pragma unroll
+      for (int k = 0; k < 13; ++k)
+        join &= ~((sim_normals(a0, a1, a2, b[k][0], b[k][1], b[k][2], s.cos_min, s.oriented) ? 0u : 1u) << k);
+    }
+    if (HAS_F) {
+      const float a0 = s.feat[3 * (size_t)i], a1 = s.feat[3 * (size_t)i + 1], a2 = s.feat[3 * (size_t)i + 2];
+      float b[13][3];
+#pragma unroll
+      for (int k = 0; k < 13; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b[k][c] = s.feat[3 * (size_t)j[k] + c];
+#pragma unroll
+      for (int k = 0; k < 13; ++k) join &= ~((sim_feats(a0, a1, a2, b[k][0], b[k][1], b[k][2], s.tol2) ? 0u : 1u) << k);
+    }
+#pragma unroll
+    for (int k = 0; k < 13; ++k)
+      if ((join >> k) & 1u) unite(parent, i, j[k]);
+  }
+}
+
+// ---- vote -----------------------------------------------------------------------------------------------------------------
+struct VoteWs {
+  int32_t* size;       // [n] what the labelling call left at the roots
+  int32_t* slot;       // [n] number of the eligible piece rooted here, -1 elsewhere
+  int32_t* decision;   // [capacity] the label the piece's voxels take, -1: the piece is left alone
+  int32_t* votes;      // [capacity][n_classes]; the slots in use are zeroed by the call
+  size_t bytes;
+};
+static VoteWs carve_vote(void* base, long long n, long long capacity, int n_classes) {
+  const PiecesWs p = carve_pieces(base, n, 0, 1);
+  VoteWs w;
+  size_t off = p.label_bytes;
+  auto take = [&](size_t ints) {
+    char* q = (char*)base + off;
+    off += align256((ints > 0 ? ints : 1) * 4);
+    return (int32_t*)q;
+  };
+  w.size = p.size;
+  w.slot = take((size_t)(n > 0 ? n : 1)), w.decision = take((size_t)capacity);
+  w.votes = take((size_t)capacity * (size_t)n_classes);
+  w.bytes = off;
+  return w;
+}
+
+// ONE block: numbers the eligible pieces in root order; says whether they fit
+__global__ __launch_bounds__(kPiecesScan) void k_vote_scan(const a3d_vote_pieces_args a, const VoteWs w, const int n) {
+  __shared__ int part[kPiecesScan];
+  const int32_t* __restrict__ piece = a.piece_qv_dev;
+  const int per = (n + kPiecesScan - 1) / kPiecesScan;
+  const long long lo64 = (long long)threadIdx.x * per;
+  const int lo = (int)(lo64 < n ? lo64 : n), hi = (int)(lo64 + per < n ? lo64 + per : n);
+  int mine = 0;
+  for (int i = lo; i < hi; ++i) mine += piece[i] == i && w.size[i] >= a.min_voxels;
+  int total;
+  int run = block_scan_exclusive(mine, part, &total);
+  for (int i = lo; i < hi; ++i) w.slot[i] = (piece[i] == i && w.size[i] >= a.min_voxels) ? run++ : -1;
+  if (threadIdx.x == 0) {
+    a.summary_dev->eligible_pieces = total;
+    if (total > a.capacity) atomicOr(&a.summary_dev->err, A3D_VOTE_OVERFLOW);
+  }
+}
+
+// zeroes the votes of the slots in use: the cost follows the eligible pieces, not the capacity
+__global__ __launch_bounds__(kPiecesBlock) void k_vote_clear(const a3d_vote_pieces_args a, const VoteWs w) {
+  const int used = a.summary_dev->eligible_pieces;
+  if (used > a.capacity) return;
+  const long long words = (long long)used * a.n_classes, stride = (long long)gridDim.x * kPiecesBlock;
+  for (long long k = (long long)blockIdx.x * kPiecesBlock + threadIdx.x; k < words; k += stride) w.votes[k] = 0;
+}
+
+__global__ __launch_bounds__(kPiecesBlock) void k_vote_count(const a3d_vote_pieces_args a, const VoteWs w, const int n) {
+  if (a.summary_dev->eligible_pieces > a.capacity) return;
+  const int stride = gridDim.x * kPiecesBlock;
+  for (int i = blockIdx.x * kPiecesBlock + threadIdx.x; i < n; i += stride) {
+    const int label = a.labels_dev[i];
+    if ((unsigned)label >= (unsigned)a.n_classes) {
+      atomicOr(&a.summary_dev->err, A3D_VOTE_BAD_LABEL);
+      continue;
+    }
+    const int root = a.piece_qv_dev[i];
+    if ((unsigned)root >= (unsigned)n) continue;
+    const int s = w.slot[root];
+    if (s >= 0) atomicAdd(w.votes + (size_t)s * a.n_classes + label, 1);
+  }
+}
+
+__global__ __launch_bounds__(kPiecesBlock) void k_vote_decide(const a3d_vote_pieces_args a, const VoteWs w, const int n) {
+  if (a.summary_dev->eligible_pieces > a.capacity) return;
+  const int stride = gridDim.x * kPiecesBlock;
+  for (int i = blockIdx.x * kPiecesBlock + threadIdx.x; i < n; i += stride) {
+    const int s = w.slot[i];
+    if (s < 0) continue;
+    const int32_t* v = w.votes + (size_t)s * a.n_classes;
+    int winner = 0, most = v[0], cast = v[0];
+    for (int c = 1; c < a.n_classes; ++c) {
+      cast += v[c];
+      if (v[c] > most) most = v[c], winner = c;          // ties: the lowest label
+    }
+    const int voxels = w.size[i];
+    int decision = -1;
+    if (most == voxels) {
+      atomicAdd(&a.summary_dev->uniform_pieces, 1);
+    } else if ((long long)most * a.share_den < (long long)voxels * a.share_num) {
+      atomicAdd(&a.summary_dev->below_share_pieces, 1);
+    } else {
+      bool blocked = false;
+      for (int c = 0; c < a.n_clicks; ++c) {
+        const int row = a.click_row[c];
+        if ((unsigned)row < (unsigned)n && a.piece_qv_dev[row] == i && a.labels_dev[row] != winner) blocked = true;
+      }
+      if (blocked) {
+        atomicAdd(&a.summary_dev->blocked_pieces, 1);
+      } else {
+        decision = winner;
+        if (cast > most) {
+          atomicAdd(&a.summary_dev->relabelled_pieces, 1);
+          atomicAdd(&a.summary_dev->relabelled_voxels, cast - most);
+        }
+      }
+    }
+    w.decision[s] = decision;
+  }
+}
+
+__global__ __launch_bounds__(kPiecesBlock) void k_vote_write(const a3d_vote_pieces_args a, const VoteWs w, const int n) {
+  if (a.summary_dev->eligible_pieces > a.capacity) return;
+  const int stride = gridDim.x * kPiecesBlock;
+  for (int i = blockIdx.x * kPiecesBlock + threadIdx.x; i < n; i += stride) {
+    int out = a.labels_dev[i];
+    const int root = a.piece_qv_dev[i];
+    if ((unsigned)root < (unsigned)n && (unsigned)out < (unsigned)a.n_classes) {
+      const int s = w.slot[root];
+      if (s >= 0 && w.decision[s] >= 0) out = w.decision[s];
+    }
+    a.labels_out_dev[i] = out;
+  }
+}
+
 static bool pieces_tab(const a3d_scene* s, int connectivity, PiecesTab* t) {
   if (!s || !s->lv[0].nbr27 || !s->orig_row || !s->lv[0].xyzb || s->n0 != s->lv[0].n) return false;
   t->nbr = s->lv[0].nbr27, t->orig = s->orig_row, t->xyzb = s->lv[0].xyzb;
@@ -447,6 +683,130 @@ extern "C" int a3d_absorb_pieces(const a3d_absorb_pieces_args* args, void* strea
     k_absorb_decide<<<grid, kPiecesBlock, 0, st>>>(a, w, n);
     A3D_LAUNCH_CHECK();
     k_absorb_write<<<grid, kPiecesBlock, 0, st>>>(a, w, n);
+    A3D_LAUNCH_CHECK();
+  }
+  return A3D_OK;
+}
+
+static bool sim_unit(float c) { return std::isfinite(c) && c >= -1.f && c <= 1.f; }
+static bool sim_tol(float t) { return std::isfinite(t) && t >= 0.f; }
+
+extern "C" int a3d_similar_pair(const float* normal_a, const float* normal_b, const float* feat_a, const float* feat_b,
+                                float cos_min, float tol2, int oriented) {
+  if (!normal_a != !normal_b || !feat_a != !feat_b || (oriented != 0 && oriented != 1)) {
+    set_error("a3d_similar_pair: a pointer without its partner, or oriented=%d", oriented);
+    return -1;
+  }
+  bool ok = true;
+  if (normal_a) ok = ok && sim_normals(normal_a[0], normal_a[1], normal_a[2], normal_b[0], normal_b[1], normal_b[2], cos_min, oriented);
+  if (feat_a) ok = ok && sim_feats(feat_a[0], feat_a[1], feat_a[2], feat_b[0], feat_b[1], feat_b[2], tol2);
+  return ok ? 1 : 0;
+}
+
+extern "C" int a3d_similar_pieces(const a3d_similar_pieces_args* args, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!args) {
+    set_error("a3d_similar_pieces: no arguments");
+    return A3D_ERR_INVALID;
+  }
+  const a3d_similar_pieces_args& a = *args;
+  PiecesTab t;
+  const bool bad_conn = a.connectivity != 6 && a.connectivity != 18 && a.connectivity != 26;
+  if (bad_conn || !pieces_tab(a.scene, a.connectivity, &t) || a.n != t.n || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS ||
+      a.max_out < 0 || a.n_full < 0 || !a.n_out_dev || (a.max_out > 0 && !a.out_dev) ||
+      (a.n > 0 && (!a.piece_qv_dev || !a.workspace_dev)) || (a.n_full > 0 && (!a.piece_full_dev || !a.piece_qv_dev)) ||
+      ((uintptr_t)a.workspace_dev & 255) || a.workspace_bytes < a3d_pieces_workspace_bytes(a.n)) {
+    set_error("a3d_similar_pieces: bad arguments (n=%lld connectivity=%d clicks=%d max_out=%d n_full=%lld workspace=%zu)",
+              (long long)a.n, a.connectivity, a.n_clicks, a.max_out, (long long)a.n_full, a.workspace_bytes);
+    return A3D_ERR_INVALID;
+  }
+  bool ref_ok = !(a.ref_flags & ~(A3D_SIMILAR_REF_NORMAL | A3D_SIMILAR_REF_FEAT)) &&
+                !((a.ref_flags & A3D_SIMILAR_REF_NORMAL) && !a.normal_qv_dev) && !((a.ref_flags & A3D_SIMILAR_REF_FEAT) && !a.feat_qv_dev);
+  for (int c = 0; c < 3; ++c) ref_ok = ref_ok && std::isfinite(a.ref_normal[c]) && std::isfinite(a.ref_feat[c]);
+  if (!ref_ok || !sim_unit(a.cos_min) || !sim_unit(a.ref_cos_min) || !sim_tol(a.tol2) || !sim_tol(a.ref_tol2) ||
+      (a.oriented != 0 && a.oriented != 1)) {
+    set_error("a3d_similar_pieces: bad thresholds or reference (cos_min=%g tol2=%g ref_cos_min=%g ref_tol2=%g oriented=%d "
+              "ref_flags=%d)", a.cos_min, a.tol2, a.ref_cos_min, a.ref_tol2, a.oriented, a.ref_flags);
+    return A3D_ERR_INVALID;
+  }
+  A3D_HIP_CHECK(hipMemsetAsync(a.n_out_dev, 0, 2 * sizeof(int32_t), st));
+  // the kernels behind the hook are a3d_label_pieces' own: they take its argument block
+  a3d_label_pieces_args la = {};
+  la.scene = a.scene, la.n = a.n, la.keys_dev = a.keys_dev, la.inverse_map_dev = a.inverse_map_dev, la.n_full = a.n_full;
+  la.piece_qv_dev = a.piece_qv_dev, la.piece_full_dev = a.piece_full_dev, la.out_dev = a.out_dev, la.n_out_dev = a.n_out_dev;
+  la.workspace_dev = a.workspace_dev, la.workspace_bytes = a.workspace_bytes;
+  la.connectivity = a.connectivity, la.max_out = a.max_out, la.n_clicks = a.n_clicks;
+  for (int c = 0; c < a.n_clicks; ++c) la.click_row[c] = a.click_row[c];
+  const int n = t.n;
+  if (n > 0) {
+    SimilarTab s;
+    s.keys = a.keys_dev, s.normal = a.normal_qv_dev, s.feat = a.feat_qv_dev;
+    s.cos_min = a.cos_min, s.tol2 = a.tol2, s.ref_cos_min = a.ref_cos_min, s.ref_tol2 = a.ref_tol2;
+    for (int c = 0; c < 3; ++c) s.ref_normal[c] = a.ref_normal[c], s.ref_feat[c] = a.ref_feat[c];
+    s.oriented = a.oriented, s.ref_flags = a.ref_flags;
+    const PiecesWs w = carve_pieces(a.workspace_dev, n, 0, 1);
+    const unsigned grid = pieces_grid(n);
+    k_similar_init<<<grid, kPiecesBlock, 0, st>>>(s, w, n);
+    A3D_LAUNCH_CHECK();
+    if (s.normal && s.feat)
+      k_similar_hook<true, true><<<grid, kPiecesBlock, 0, st>>>(s, t, w.parent);
+    else if (s.normal)
+      k_similar_hook<true, false><<<grid, kPiecesBlock, 0, st>>>(s, t, w.parent);
+    else if (s.feat)
+      k_similar_hook<false, true><<<grid, kPiecesBlock, 0, st>>>(s, t, w.parent);
+    else
+      k_similar_hook<false, false><<<grid, kPiecesBlock, 0, st>>>(s, t, w.parent);
+    A3D_LAUNCH_CHECK();
+    k_pieces_flatten<<<grid, kPiecesBlock, 0, st>>>(w.parent, a.piece_qv_dev, n);
+    A3D_LAUNCH_CHECK();
+    k_pieces_stats<<<grid, kPiecesBlock, 0, st>>>(la, t, w);
+    A3D_LAUNCH_CHECK();
+    k_pieces_records<<<1, kPiecesScan, 0, st>>>(la, a.keys_dev, w, n);
+    A3D_LAUNCH_CHECK();
+  }
+  if (a.n_full > 0) {
+    k_pieces_full<<<pieces_grid(a.n_full), kPiecesBlock, 0, st>>>(la, n);
+    A3D_LAUNCH_CHECK();
+  }
+  return A3D_OK;
+}
+
+extern "C" size_t a3d_vote_workspace_bytes(int64_t n, int capacity, int n_classes) {
+  if (n < 0 || n > 0x7fffffffll || capacity < 0 || n_classes < 1 || n_classes > 256) return 0;
+  return carve_vote(nullptr, n, capacity, n_classes).bytes;
+}
+
+extern "C" int a3d_vote_pieces(const a3d_vote_pieces_args* args, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!args) {
+    set_error("a3d_vote_pieces: no arguments");
+    return A3D_ERR_INVALID;
+  }
+  const a3d_vote_pieces_args& a = *args;
+  PiecesTab t;
+  if (!pieces_tab(a.scene, 26, &t) || a.n != t.n || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS || a.n_classes < 1 ||
+      a.n_classes > 256 || a.capacity < 0 || a.min_voxels < 1 || a.share_num < 1 || a.share_num > a.share_den ||
+      a.share_den > 65536 || !a.summary_dev ||
+      (a.n > 0 && (!a.labels_dev || !a.piece_qv_dev || !a.labels_out_dev || !a.workspace_dev || a.labels_out_dev == a.labels_dev)) ||
+      ((uintptr_t)a.workspace_dev & 255) || a.workspace_bytes < a3d_vote_workspace_bytes(a.n, a.capacity, a.n_classes)) {
+    set_error("a3d_vote_pieces: bad arguments (n=%lld clicks=%d classes=%d capacity=%d min_voxels=%d share=%d/%d workspace=%zu)",
+              (long long)a.n, a.n_clicks, a.n_classes, a.capacity, a.min_voxels, a.share_num, a.share_den, a.workspace_bytes);
+    return A3D_ERR_INVALID;
+  }
+  A3D_HIP_CHECK(hipMemsetAsync(a.summary_dev, 0, sizeof(a3d_vote_summary), st));
+  const int n = t.n;
+  if (n > 0) {
+    const VoteWs w = carve_vote(a.workspace_dev, n, a.capacity, a.n_classes);
+    const unsigned grid = pieces_grid(n);
+    k_vote_scan<<<1, kPiecesScan, 0, st>>>(a, w, n);
+    A3D_LAUNCH_CHECK();
+    k_vote_clear<<<grid, kPiecesBlock, 0, st>>>(a, w);
+    A3D_LAUNCH_CHECK();
+    k_vote_count<<<grid, kPiecesBlock, 0, st>>>(a, w, n);
+    A3D_LAUNCH_CHECK();
+    k_vote_decide<<<grid, kPiecesBlock, 0, st>>>(a, w, n);
+    A3D_LAUNCH_CHECK();
+    k_vote_write<<<grid, kPiecesBlock, 0, st>>>(a, w, n);
     A3D_LAUNCH_CHECK();
   }
   return A3D_OK;

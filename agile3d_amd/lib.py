@@ -203,6 +203,40 @@ class AbsorbPiecesArgs(C.Structure):
                 ("click_row", C.c_int32 * 256)]
 
 
+A3D_SIMILAR_REF_NORMAL, A3D_SIMILAR_REF_FEAT = 1, 2
+A3D_VOTE_OVERFLOW, A3D_VOTE_BAD_LABEL = 1, 2
+
+
+class SimilarPiecesArgs(C.Structure):
+    """a3d_similar_pieces_args: a3d_label_pieces' (keys_dev may be NULL), the normals and colours per voxel (either may be
+    NULL), and by value the pairwise thresholds, ``oriented``, the reference test's flags, values and thresholds."""
+    _fields_ = [("scene", C.c_void_p), ("n", C.c_int64), ("keys_dev", C.c_void_p), ("inverse_map_dev", C.c_void_p),
+                ("n_full", C.c_int64), ("piece_qv_dev", C.c_void_p), ("piece_full_dev", C.c_void_p), ("out_dev", C.c_void_p),
+                ("n_out_dev", C.c_void_p), ("workspace_dev", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("normal_qv_dev", C.c_void_p), ("feat_qv_dev", C.c_void_p), ("cos_min", C.c_float), ("tol2", C.c_float),
+                ("oriented", C.c_int32), ("ref_flags", C.c_int32), ("ref_normal", C.c_float * 3), ("ref_cos_min", C.c_float),
+                ("ref_feat", C.c_float * 3), ("ref_tol2", C.c_float),
+                ("connectivity", C.c_int32), ("max_out", C.c_int32), ("n_clicks", C.c_int32), ("reserved_", C.c_int32),
+                ("click_row", C.c_int32 * 256)]
+
+
+class VoteSummary(C.Structure):
+    """a3d_vote_summary: eligible pieces (the capacity needed on overflow), uniform, relabelled pieces and voxels, blocked and
+    below-share pieces, the error word (A3D_VOTE_OVERFLOW, A3D_VOTE_BAD_LABEL)."""
+    _fields_ = [("eligible_pieces", C.c_int32), ("uniform_pieces", C.c_int32), ("relabelled_pieces", C.c_int32),
+                ("relabelled_voxels", C.c_int32), ("blocked_pieces", C.c_int32), ("below_share_pieces", C.c_int32),
+                ("err", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class VotePiecesArgs(C.Structure):
+    """a3d_vote_pieces_args: the scene, the labels and a partition, the output labels and summary, the workspace of the call
+    that wrote the partition, the settings (min_voxels, n_classes, capacity, the share as a fraction) and the clicked rows."""
+    _fields_ = [("scene", C.c_void_p), ("n", C.c_int64), ("labels_dev", C.c_void_p), ("piece_qv_dev", C.c_void_p),
+                ("labels_out_dev", C.c_void_p), ("summary_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("min_voxels", C.c_int32), ("n_classes", C.c_int32), ("capacity", C.c_int32),
+                ("share_num", C.c_int32), ("share_den", C.c_int32), ("n_clicks", C.c_int32), ("click_row", C.c_int32 * 256)]
+
+
 class GrowSummary(C.Structure):
     """a3d_grow_summary: seeds, reached voxels, selected vertices, the largest dist reached, the error word
     (A3D_GROW_BAD_INDEX)."""
@@ -532,6 +566,11 @@ SYMBOLS = {
     "a3d_label_pieces": (C.c_int, [C.POINTER(LabelPiecesArgs), C.c_void_p]),
     "a3d_absorb_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "a3d_absorb_pieces": (C.c_int, [C.POINTER(AbsorbPiecesArgs), C.c_void_p]),
+    "a3d_similar_pieces": (C.c_int, [C.POINTER(SimilarPiecesArgs), C.c_void_p]),
+    "a3d_similar_pair": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.c_float, C.c_float, C.c_int]),
+    "a3d_vote_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "a3d_vote_pieces": (C.c_int, [C.POINTER(VotePiecesArgs), C.c_void_p]),
     "a3d_grow_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "a3d_grow_voxels": (C.c_int, [C.POINTER(GrowVoxelsArgs), C.c_void_p]),
     "a3d_normals_workspace_bytes": (C.c_size_t, [C.c_int64]),

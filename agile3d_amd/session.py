@@ -36,6 +36,9 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
     which way a cloud's surface faces   a3d_estimate_normals / a3d_render_shade_lit_points / a3d_cull_points  (estimate_normals,
                                         normal_at: one normal per voxel from its 27-voxel neighbourhood; after it a cloud is
                                         lit and culled as a mesh is; the GUI shows clouds unlit; a rule of ours)
+    which voxels belong to one surface  a3d_similar_pieces / a3d_vote_pieces  (patches, wand_at, snap: connected components
+                                        under a similarity of normals and colours, the patch under a pixel as a selection,
+                                        labels snapped to patches by a vote that never contradicts a click; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -301,6 +304,70 @@ class DespeckleResult:
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
+
+
+class PatchesResult:
+    """What ``patches()`` returns: the fields of a ``PiecesResult`` -- ``piece_qv`` int32 [n_voxels] (the smallest voxel row of
+    the voxel's patch, -1: none; ``grow(within=r.piece_qv)`` walks inside one patch), ``piece_full`` int32 [n_full], ``records``
+    (``view.PIECE``; key = the key of ``within``, 0 with ``"all"``) in ascending root, ``n_pieces``, ``connectivity``,
+    ``object_pieces`` (patches per object id with ``within="label"``, else ``None``) -- and the thresholds as used:
+    ``normal_deg`` and ``cos_min`` (fp32; ``None``: no normal test), ``color_tol`` and ``tol2`` (fp32; ``None``: no colour
+    test), ``oriented``, ``within``; and ``workspace``, the call's scratch on the device, which holds the patches' sizes for ``snap``."""
+
+    __slots__ = PiecesResult.__slots__ + ("normal_deg", "cos_min", "color_tol", "tol2", "oriented", "within", "workspace")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+class WandResult:
+    """What ``wand_at()`` returns: ``selected`` uint8 [n_full] on the device (1 = the vertex lies in the patch under the pixel;
+    ``paint``, ``erase``, ``grow`` and ``shrink`` take the result as it is), ``piece_qv`` int32 [n_voxels] (the partition the
+    call computed), and on the host ``count`` (selected vertices), ``record`` (the patch's ``view.PIECE`` row, ``None`` when
+    the voxel under the pixel belongs to no patch), ``mode``, ``normal_deg``, ``color_tol``, ``connectivity``, ``within``."""
+
+    __slots__ = ("selected", "count", "record", "piece_qv", "mode", "normal_deg", "color_tol", "connectivity", "within")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+class SnapResult:
+    """What ``snap()`` returns: ``labels_full``, ``colors``, ``miou`` and ``iou_per_object`` as a ``SessionResult`` holds them,
+    ``labels_qv`` int32 [n_voxels] on the device, and the counts of ``a3d_vote_pieces``' summary: ``eligible_pieces``,
+    ``uniform_pieces``, ``relabelled_pieces``, ``relabelled_voxels``, ``blocked_pieces``, ``below_share_pieces``;
+    ``min_voxels`` and ``min_share`` as used."""
+
+    __slots__ = ("labels_full", "colors", "miou", "iou_per_object", "labels_qv", "eligible_pieces", "uniform_pieces",
+                 "relabelled_pieces", "relabelled_voxels", "blocked_pieces", "below_share_pieces", "min_voxels", "min_share")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def patch_thresholds(normal_deg, color_tol):
+    """``(cos_min, tol2)`` of ``patches(normal_deg=, color_tol=)``, pure numpy: ``cos_min = float32(cos(radians(normal_deg)))``
+    for an angle in 0 .. 180 degrees, ``tol2 = float32(color_tol) ** 2`` (an fp32 product) for a tolerance >= 0 whose square
+    is finite; ``None`` for a test that is switched off (``None``).  ``ValueError`` for anything else."""
+    cos_min = tol2 = None
+    if normal_deg is not None:
+        deg = np.float64(normal_deg)
+        if not (np.isfinite(deg) and 0.0 <= deg <= 180.0):
+            raise ValueError("normal_deg must be an angle in 0 .. 180 degrees, or None (no normal test)")
+        cos_min = np.float32(np.cos(np.radians(deg)))
+    if color_tol is not None:
+        tol = np.float32(color_tol)
+        with np.errstate(over="ignore"):
+            tol2 = tol * tol
+        if not (np.isfinite(tol2) and tol >= 0.0):
+            raise ValueError("color_tol must be finite and >= 0, or None (no colour test)")
+    return cos_min, tol2
+
+
+WAND_MODES = ("chain", "seed", "both")
 
 
 class SelectResult:
@@ -791,6 +858,7 @@ class InteractiveSession:
         self._unique_map = None                     # int64 [n_voxels]: the vertex each voxel was made from (measure(labels=))
         self._measure_frame = None                  # (origin, quantum, bits) of measure(): once per scene, on first use
         self._grow_ws = None                        # scratch of grow(): once per scene, on first use
+        self._colors_qv = None                      # fp32 [n_voxels, 3]: the colours the backbone was fed (patches(color_tol=))
         self.section = None                         # the Section pick, click_ray and render apply by default (set_section)
         self._reset_clicks()
 
@@ -1559,25 +1627,32 @@ class InteractiveSession:
     def _click_rows(self):
         return [int(r) for rows in self.click_idx.values() for r in rows]
 
-    def _label_pieces(self, keys, connectivity, click_rows=(), lift=False, max_out=1024, workspace=None):
-        """``a3d_label_pieces`` on the session's voxels and the copy of its record list: ``(piece_qv, piece_full, records,
+    def _label_pieces(self, keys, connectivity, click_rows=(), lift=False, max_out=1024, workspace=None, similar=None, also=None):
+        """``a3d_label_pieces`` -- with ``similar``, a dict of ``view.similar_pieces``' normals, colours and thresholds,
+        ``a3d_similar_pieces`` -- on the session's voxels and the copy of its record list: ``(piece_qv, piece_full, records,
         n_pieces)``.  One library call and ONE host round trip; when there are more pieces than ``max_out`` records, once
-        more with the reported count (as ``render`` grows its pair buffer)."""
+        more with the reported count (as ``render`` grows its pair buffer).  ``also``: a function of ``(piece_qv,
+        piece_full)`` that returns a tensor to bring along in that round trip; its host copy is then a fifth value."""
         dev, scene = self.device, self._scene_handle()
+        name = "a3d_label_pieces" if similar is None else "a3d_similar_pieces"
         for _ in range(2):
             buf = torch.empty(max_out * V.PIECE.itemsize + 8, dtype=torch.uint8, device=dev)
             records, count = buf[:max_out * V.PIECE.itemsize], buf[max_out * V.PIECE.itemsize:].view(torch.int32)
-            piece_qv, piece_full, _, _, workspace = V.label_pieces(
-                scene, keys, connectivity, click_rows, inverse_map=self.inverse_map if lift else None, records=records,
-                count=count, workspace=workspace)
-            host = buf.cpu().numpy()                                  # the one host round trip
-            recs, n_pieces, err = V.read_pieces(host[:-8], host[-8:])
+            shared = dict(connectivity=connectivity, click_rows=click_rows, inverse_map=self.inverse_map if lift else None,
+                          records=records, count=count, workspace=workspace)
+            if similar is None:
+                piece_qv, piece_full, _, _, workspace = V.label_pieces(scene, keys, **shared)
+            else:
+                piece_qv, piece_full, _, _, workspace = V.similar_pieces(scene, keys, **similar, **shared)
+            extra = None if also is None else also(piece_qv, piece_full).contiguous().view(-1).view(torch.uint8)
+            host = (buf if extra is None else torch.cat([buf, extra])).cpu().numpy()       # the one host round trip
+            recs, n_pieces, err = V.read_pieces(host[:buf.numel() - 8], host[buf.numel() - 8:buf.numel()])
             if err & V.PIECES_BAD_INDEX:
-                raise RuntimeError("a3d_label_pieces: inverse_map out of range")
+                raise RuntimeError(f"{name}: inverse_map out of range")
             if n_pieces <= max_out:
-                return piece_qv, piece_full, recs, n_pieces
+                return (piece_qv, piece_full, recs, n_pieces) + (() if also is None else (host[buf.numel():].copy(),))
             max_out = n_pieces
-        raise RuntimeError("a3d_label_pieces: the record list did not fit twice")
+        raise RuntimeError(f"{name}: the record list did not fit twice")
 
     def _contested_spots(self, labels, want):
         """What ``guide(regions="connected")`` hands to the cluster search: ``(pred = 0 everywhere, the pseudo id of every
@@ -1658,6 +1733,155 @@ class InteractiveSession:
                                relabelled_voxels=s["relabelled_voxels"], kept_isolated=s["kept_isolated"],
                                min_voxels=int(min_voxels), connectivity=connectivity)
 
+    # ------------------------------------------------------------------ which voxels belong to one surface
+    def _patch_inputs(self, normal_deg, color_tol, normals):
+        """``(normals_qv or None, colors_qv or None, cos_min or None, tol2 or None)`` of ``patches`` / ``wand_at``."""
+        cos_min, tol2 = patch_thresholds(normal_deg, color_tol)
+        n = self._labels_qv.numel()
+        normal_qv = feat_qv = None
+        if cos_min is not None:
+            res = self._normals_last if normals is None and self.faces is None else normals
+            if res is None:
+                raise ValueError("no normals: call estimate_normals() first (on a mesh it keeps none with the scene: pass its "
+                                 "result as normals=), or switch the normal test off with normal_deg=None")
+            if not isinstance(res, NormalsResult) or not torch.is_tensor(res.normals_qv) or res.normals_qv.device != self.device \
+                    or tuple(res.normals_qv.shape) != (n, 3):
+                raise ValueError("normals must be a NormalsResult of this scene (estimate_normals())")
+            normal_qv = res.normals_qv.contiguous()
+        if tol2 is not None:
+            if self._colors_qv is None:
+                self._colors_qv = self.colors_full[self._unique_map].contiguous()       # what load_scene fed the backbone
+            feat_qv = self._colors_qv
+        return normal_qv, feat_qv, cos_min, tol2
+
+    def patches(self, normal_deg=15.0, color_tol=None, connectivity=26, within="all", oriented=False, normals=None):
+        """The SMOOTH PATCHES of the scan: voxels that are neighbours under ``connectivity`` belong to one patch when their
+        normals differ by at most ``normal_deg`` degrees (``|dot| >= cos_min = float32(cos(radians(normal_deg)))``; with
+        ``oriented=True`` the sign counts: ``dot >= cos_min``) and, with ``color_tol``, their colours -- ``colors_full`` of the
+        vertex each voxel was made from, what ``load_scene`` fed the backbone -- lie within ``color_tol`` of each other
+        (squared distance ``<= float32(color_tol) ** 2``); ``None`` switches a test off, and the colour test is off by
+        default (``a3d_similar_pieces``; the rule, fp32 with one rounding per operation, is stated in
+        include/agile3d_hip.h).  A patch is a class of the transitive closure -- a CHAIN: a wall is one patch, and so is a
+        smoothly curved surface however far it turns; a crease of more than ``normal_deg`` separates.  ``normals``: a
+        ``NormalsResult``; ``None`` takes the one ``estimate_normals()`` left with a cloud -- a mesh keeps none, so there it
+        must be passed; with neither, ``ValueError``.  ``within`` as in ``grow``: ``"all"``, ``"label"`` (a patch stays inside
+        one object of the current labelling), an int32 tensor of keys or a uint8 / bool mask over the voxels.  Returns a
+        ``PatchesResult``; ``grow(..., within=r.piece_qv)`` then stays on the patch it starts on, and ``snap(r)`` votes.
+        LIMITS: a voxel's normal is blended over its 27-voxel neighbourhood, so the voxels along a crease hold intermediate
+        normals and fall out as tiny patches of their own; a voxel without a valid normal (zeros) joins nobody.  The defaults
+        (15 degrees, no colour test, 26) are this project's choice and are NOT tuned on real scans.  One library call and ONE
+        host round trip (a second of each when there are more than 16384 patches); no session state changes."""
+        self._need_scene()
+        connectivity = V._connectivity(connectivity)
+        keys = self._grow_keys(within)
+        normal_qv, feat_qv, cos_min, tol2 = self._patch_inputs(normal_deg, color_tol, normals)
+        similar = dict(normals=normal_qv, feats=feat_qv, cos_min=1.0 if cos_min is None else cos_min,
+                       tol2=0.0 if tol2 is None else tol2, oriented=oriented)
+        ws = V.pieces_workspace(self._labels_qv.numel(), self.device)
+        piece_qv, piece_full, recs, n_pieces = self._label_pieces(keys, connectivity, self._click_rows(), lift=True, max_out=16384,
+                                                                  workspace=ws, similar=similar)
+        per_object = None
+        if isinstance(within, str) and within == "label":
+            n_ids = max(len(self.click_idx), int(recs["key"].max()) + 1 if len(recs) else 1)
+            per_object = np.bincount(recs["key"], minlength=n_ids).astype(np.int64)
+        res = PatchesResult(piece_qv=piece_qv, piece_full=piece_full, records=recs, n_pieces=n_pieces, object_pieces=per_object,
+                            connectivity=connectivity, normal_deg=normal_deg, cos_min=cos_min, color_tol=color_tol, tol2=tol2,
+                            oriented=bool(oriented), within=within if isinstance(within, str) else "keys", workspace=ws)
+        return res
+
+    def wand_at(self, result, u, v, normal_deg=15.0, color_tol=None, mode="chain", within="all", connectivity=26, normals=None):
+        """The MAGIC WAND: the patch under pixel ``(u, v)`` (column, row) of ``result`` as a selection, or ``None`` where the
+        pixel shows nothing -- the vertex resolved as ``grow_at`` resolves it.  ``mode="chain"``: the patch of ``patches()``
+        with these thresholds that holds the pixel's voxel (neighbour to neighbour; a curved surface is followed all the way
+        round).  ``"seed"``: the connected voxels whose normal and colour lie within the thresholds of THE PIXEL'S VOXEL's own
+        -- a paint program's tolerance from the clicked sample; neighbours are then joined whatever they hold (the pairwise
+        thresholds are the loosest the library takes: ``cos_min = -1``, ``tol2`` = the largest fp32).  ``"both"``: both
+        tests.  Normals are compared unoriented.  ``normal_deg``, ``color_tol``, ``within``, ``connectivity``, ``normals`` as
+        in ``patches``.  Returns a ``WandResult``: ``selected`` uint8 [n_full] (``paint``, ``erase``, ``grow``, ``shrink``
+        take the result), ``count``, the patch's ``record`` and the partition ``piece_qv``; a voxel that belongs to no patch
+        (outside ``within``; under ``"seed"`` / ``"both"`` a voxel without a valid normal) selects nothing.  Like ``grow`` it
+        ROUNDS UP TO WHOLE VOXELS.  The defaults are this project's choice and are NOT tuned on real scans.  ONE library
+        call; beyond the pixel's small read (and, for ``"seed"`` / ``"both"``, one of the voxel's normal and colour) the
+        host round trips of ``patches()``; no session state changes."""
+        self._need_scene()
+        if mode not in WAND_MODES:
+            raise ValueError(f"mode must be one of {WAND_MODES}, not {mode!r}")
+        connectivity = V._connectivity(connectivity)
+        keys = self._grow_keys(within)
+        normal_qv, feat_qv, cos_min, tol2 = self._patch_inputs(normal_deg, color_tol, normals)
+        vertex = self._vertex_at(result, u, v)
+        if vertex < 0:
+            return None
+        dev, n_full = self.device, self.coords_full.shape[0]
+        row = self.inverse_map[vertex]                                  # stays on the device
+        made = dict(mode=mode, normal_deg=normal_deg, color_tol=color_tol, connectivity=connectivity,
+                    within=within if isinstance(within, str) else "keys")
+        similar = dict(normals=normal_qv, feats=feat_qv, cos_min=-1.0, tol2=float(np.finfo(np.float32).max), oriented=False)
+        if mode != "seed":
+            similar.update(cos_min=1.0 if cos_min is None else cos_min, tol2=0.0 if tol2 is None else tol2)
+        if mode != "chain" and (normal_qv is not None or feat_qv is not None):
+            seed = torch.cat([t[row] for t in (normal_qv, feat_qv) if t is not None]).cpu().numpy()     # the voxel's own sample
+            if not np.isfinite(seed).all():
+                return WandResult(selected=torch.zeros(n_full, dtype=torch.uint8, device=dev), count=0, record=None,
+                                  piece_qv=torch.full_like(self._labels_qv, -1), **made)
+            if normal_qv is not None:
+                similar.update(ref_normal=seed[:3], ref_cos_min=cos_min)
+            if feat_qv is not None:
+                similar.update(ref_feat=seed[-3:], ref_tol2=tol2)
+        kept = {}
+
+        def also(piece_qv, piece_full):
+            root = piece_qv[row]
+            kept["selected"] = ((piece_full == root) & (root >= 0)).to(torch.uint8)
+            return torch.stack([root.to(torch.int64), kept["selected"].sum()])
+
+        piece_qv, _, recs, _, tail = self._label_pieces(keys, connectivity, self._click_rows(), lift=True, max_out=16384,
+                                                        similar=similar, also=also)
+        root, count = (int(x) for x in tail.view(np.int64))
+        k = int(np.searchsorted(recs["root"], root))
+        record = recs[k] if root >= 0 and k < len(recs) and recs["root"][k] == root else None
+        return WandResult(selected=kept["selected"], count=count, record=record, piece_qv=piece_qv, **made)
+
+    def snap(self, patches=None, min_voxels=8, min_share=(2, 3), paint_cubes=False):
+        """The current voxel labelling SNAPPED to smooth patches, without touching the session: every patch of ``patches`` (a
+        ``PatchesResult`` of this scene; ``None``: ``patches()`` with its defaults, computed here) with at least
+        ``min_voxels`` voxels whose most frequent object (ties: the lowest id) holds at least ``min_share = (num, den)`` of
+        its voxels gives ALL its voxels that object -- unless the patch holds a clicked voxel of another object: the snap
+        never contradicts a click.  ONE simultaneous step on the labels as they are (``a3d_vote_pieces``); a boundary that
+        cuts across a flat table top moves to the table's edge, which ``despeckle`` never does.  Returns a ``SnapResult``:
+        ``labels_qv``, ``labels_full`` and ``colors`` (through ``a3d_session_paint``), ``miou`` / ``iou_per_object`` against
+        the relabelled ground truth when the scene has one, and the counts of eligible, already uniform, relabelled, blocked
+        and below-share patches.  It changes NO session state: ``annotate(result, labels=r.labels_full)`` and
+        ``render(colors=r.colors)`` show it.  The defaults (8 voxels, 2/3) are this project's choice and are NOT tuned on real
+        scans.  One host round trip (a second when there are more than 4096 eligible patches), after those of ``patches()``
+        when it is computed here."""
+        self._need_scene()
+        dev, scene, n = self.device, self._scene_handle(), self._labels_qv.numel()
+        min_voxels, num, den = V.vote_settings(min_voxels, min_share, _N_IDS, 0)[:3]
+        patches = self.patches() if patches is None else patches
+        held = getattr(patches, "workspace", None)
+        if not isinstance(patches, PatchesResult) or held is None or tuple(patches.piece_qv.shape) != (n,) or \
+                patches.piece_qv.device != dev:
+            raise ValueError("patches must be a PatchesResult of this scene (patches())")
+        labels, rows = self._labels_qv, self._click_rows()
+        capacity = 4096
+        for _ in range(2):
+            ws = V.vote_workspace(n, dev, capacity, _N_IDS)
+            ws[:held.numel()] = held                                  # the sizes at the roots, as patches() left them
+            labels_qv, summary = V.vote_pieces(scene, labels, patches.piece_qv, ws, min_voxels, (num, den), rows, _N_IDS, capacity)
+            labels_full, colors = self._launch_paint(labels_qv, paint_cubes)
+            self._launch_iou(labels_qv, self.inverse_map)
+            packed = torch.cat([self._counts.view(torch.uint8), summary]).cpu().numpy()      # the one host round trip
+            host, s = packed[:-V.VOTE_SUMMARY.itemsize].view(np.int64), V.read_vote_summary(packed[-V.VOTE_SUMMARY.itemsize:])
+            if not s["err"] & V.VOTE_OVERFLOW:
+                break
+            capacity = s["eligible_pieces"]
+        if s["err"] & V.VOTE_BAD_LABEL or host[3 * _N_IDS] or (int(host[3 * _N_IDS + 1]) & 0xffffffff):
+            raise RuntimeError("snap: inverse_map or labels out of range")
+        miou, per_obj = self._read_iou(host)
+        return SnapResult(labels_full=labels_full, colors=colors, miou=miou, iou_per_object=per_obj, labels_qv=labels_qv,
+                          min_voxels=min_voxels, min_share=(num, den), **{k: s[k] for k in s if k != "err"})
+
     # ------------------------------------------------------------------ correcting by hand
     def region_mask(self, result, polygon=None, stroke=None, radius=None, mask=None, mode="replace"):
         """A region of the screen of ``result`` (a ``RenderResult``) as a mask: uint8 [h, w] on the device, 1 inside
@@ -1706,10 +1930,10 @@ class InteractiveSession:
         return SelectResult(selected=selected, count=s["selected"], in_view=s["in_view"], through=bool(through), slack=slack)
 
     def _selection(self, selection):
-        sel = selection.selected if isinstance(selection, (SelectResult, GrowResult)) else selection
+        sel = selection.selected if isinstance(selection, (SelectResult, GrowResult, WandResult)) else selection
         n = self.coords_full.shape[0]
         if not torch.is_tensor(sel) or sel.device != self.device or sel.dtype not in (torch.uint8, torch.bool) or tuple(sel.shape) != (n,):
-            raise ValueError(f"the selection must be a SelectResult or GrowResult of this scene, or a uint8 / bool tensor [{n}] on the "
+            raise ValueError(f"the selection must be a SelectResult, GrowResult or WandResult of this scene, or a uint8 / bool tensor [{n}] on the "
                              "session's device")
         return (sel.view(torch.uint8) if sel.dtype == torch.bool else sel).contiguous()
 
@@ -1765,7 +1989,7 @@ class InteractiveSession:
 
     def _grow_seeds(self, seeds):
         """``(seed_qv, seed_full)`` of ``grow(seeds)``: one of the two is ``None``."""
-        if isinstance(seeds, (SelectResult, GrowResult)) or torch.is_tensor(seeds):
+        if isinstance(seeds, (SelectResult, GrowResult, WandResult)) or torch.is_tensor(seeds):
             return None, self._selection(seeds)
         n = self._labels_qv.numel()
         if isinstance(seeds, str):
@@ -1811,7 +2035,8 @@ class InteractiveSession:
         float64) and ``steps`` (an int >= 0: every step costs 1).  More than ``view.GROW_MAX_STEPS`` voxel steps raise
         ``ValueError``: ``pieces()`` answers what is connected at all.  ``within``: ``"all"`` walks anywhere; ``"label"``
         stays inside the object of each seed -- the labels ``preview()`` paints; an int32 tensor [n_voxels] of keys walks
-        between equal keys >= 0; a uint8 / bool tensor [n_voxels] is a mask to stay inside.  ``connectivity``: 6, 18 or 26.
+        between equal keys >= 0 -- ``patches().piece_qv`` keeps the walk on the smooth patch it starts on --; a uint8 / bool
+        tensor [n_voxels] is a mask to stay inside.  ``connectivity``: 6, 18 or 26.
         Returns a ``GrowResult``: the selected vertices (``paint`` / ``erase`` take it), the distance of every vertex and
         voxel, and for every voxel the seed voxel nearest to it -- ``grow("clicks", ..., within="label")`` splits each object
         between its clicks.  A selection is ROUNDED UP TO WHOLE VOXELS: every vertex of a reached voxel is selected.  The

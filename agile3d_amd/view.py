@@ -519,19 +519,10 @@ def _click_rows(dst, click_rows):
     return len(rows)
 
 
-def label_pieces(scene, keys, connectivity=26, click_rows=(), inverse_map=None, piece_qv=None, piece_full=None, records=None,
-                 count=None, workspace=None):
-    """``a3d_label_pieces``: the connected pieces of ``keys`` int32 [n] (the rows of ``scene``, an ``engine.Scene``, in the
-    caller's order; a negative key belongs to no piece) under ``connectivity`` 6, 18 or 26.  ``click_rows``: a host sequence
-    of at most ``A3D_MAX_CLICKS`` rows.  ``inverse_map`` int64 [m]: also lift the pieces to m vertices.  ``records``: a uint8
-    buffer of 40 bytes per record the call may write (default: room for 1024); ``count`` int32 [2]; ``workspace``:
-    ``pieces_workspace``.  Returns ``(piece_qv int32 [n], piece_full int32 [m] or None, records, count, workspace)`` on the
-    device; ``read_pieces`` decodes the host copies of the last two."""
-    dev = _device("keys", keys)
-    handle, n = _scene_rows(scene)
-    a = L.LabelPiecesArgs()
-    a.scene, a.n = handle, n
-    a.keys_dev = _ptr("keys", keys, I32, (n,), dev)
+def _pieces_outputs(a, n, dev, connectivity, click_rows, inverse_map, piece_qv, piece_full, records, count, workspace):
+    """What ``label_pieces`` and ``similar_pieces`` share, written into either argument block: the connectivity, the clicked
+    rows, the lift, the outputs (the caller's, checked, or new ones) and the workspace.  Returns ``(piece_qv, piece_full,
+    records, count, workspace)``."""
     a.connectivity = _connectivity(connectivity)
     a.n_clicks = _click_rows(a.click_row, click_rows)
     piece_qv = _out("piece_qv", piece_qv, I32, (n,), dev)
@@ -555,8 +546,25 @@ def label_pieces(scene, keys, connectivity=26, click_rows=(), inverse_map=None, 
     if workspace is None:
         workspace = pieces_workspace(n, dev)
     a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
-    L.check(L.load().a3d_label_pieces(C.byref(a), L.stream(dev)), "a3d_label_pieces")
     return piece_qv, piece_full, records, count, workspace
+
+
+def label_pieces(scene, keys, connectivity=26, click_rows=(), inverse_map=None, piece_qv=None, piece_full=None, records=None,
+                 count=None, workspace=None):
+    """``a3d_label_pieces``: the connected pieces of ``keys`` int32 [n] (the rows of ``scene``, an ``engine.Scene``, in the
+    caller's order; a negative key belongs to no piece) under ``connectivity`` 6, 18 or 26.  ``click_rows``: a host sequence
+    of at most ``A3D_MAX_CLICKS`` rows.  ``inverse_map`` int64 [m]: also lift the pieces to m vertices.  ``records``: a uint8
+    buffer of 40 bytes per record the call may write (default: room for 1024); ``count`` int32 [2]; ``workspace``:
+    ``pieces_workspace``.  Returns ``(piece_qv int32 [n], piece_full int32 [m] or None, records, count, workspace)`` on the
+    device; ``read_pieces`` decodes the host copies of the last two."""
+    dev = _device("keys", keys)
+    handle, n = _scene_rows(scene)
+    a = L.LabelPiecesArgs()
+    a.scene, a.n = handle, n
+    a.keys_dev = _ptr("keys", keys, I32, (n,), dev)
+    outs = _pieces_outputs(a, n, dev, connectivity, click_rows, inverse_map, piece_qv, piece_full, records, count, workspace)
+    L.check(L.load().a3d_label_pieces(C.byref(a), L.stream(dev)), "a3d_label_pieces")
+    return outs
 
 
 def absorb_pieces(scene, labels, piece_qv, workspace, min_voxels, connectivity=26, click_rows=(), n_classes=256, capacity=1024,
@@ -592,6 +600,169 @@ def absorb_pieces(scene, labels, piece_qv, workspace, min_voxels, connectivity=2
     if a.workspace_bytes < L.load().a3d_absorb_workspace_bytes(n, a.capacity, a.n_classes):
         raise ValueError("workspace too small for this capacity and n_classes (pieces_workspace(n, device, capacity, n_classes))")
     L.check(L.load().a3d_absorb_pieces(C.byref(a), L.stream(dev)), "a3d_absorb_pieces")
+    return labels_out, summary
+
+
+# ---- smooth patches, the magic wand, the snap --------------------------------------------------------------------------------
+VOTE_SUMMARY = np.dtype([("eligible_pieces", "<i4"), ("uniform_pieces", "<i4"), ("relabelled_pieces", "<i4"),
+                         ("relabelled_voxels", "<i4"), ("blocked_pieces", "<i4"), ("below_share_pieces", "<i4"), ("err", "<i4"),
+                         ("reserved_", "<i4")])
+assert C.sizeof(L.VoteSummary) == VOTE_SUMMARY.itemsize == 32
+assert C.sizeof(L.SimilarPiecesArgs) == 1192 and C.sizeof(L.VotePiecesArgs) == 1112
+SIMILAR_REF_NORMAL, SIMILAR_REF_FEAT = L.A3D_SIMILAR_REF_NORMAL, L.A3D_SIMILAR_REF_FEAT
+VOTE_OVERFLOW, VOTE_BAD_LABEL = L.A3D_VOTE_OVERFLOW, L.A3D_VOTE_BAD_LABEL      # the bits of the vote summary's error word
+VOTE_MAX_DEN = 1 << 16
+
+
+def read_vote_summary(host):
+    """The host copy of an ``a3d_vote_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints:
+    ``eligible_pieces`` (on ``VOTE_OVERFLOW`` the capacity needed), ``uniform_pieces``, ``relabelled_pieces``,
+    ``relabelled_voxels``, ``blocked_pieces``, ``below_share_pieces``, ``err`` (bits ``VOTE_OVERFLOW``, ``VOTE_BAD_LABEL``)."""
+    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:VOTE_SUMMARY.itemsize].view(VOTE_SUMMARY)[0]
+    return {k: int(rec[k]) for k in VOTE_SUMMARY.names[:-1]}
+
+
+def vote_workspace(n, device, capacity, n_classes=256):
+    """The scratch of ``label_pieces`` / ``similar_pieces`` for n voxels with room behind it for ``vote_pieces`` with
+    ``capacity`` eligible pieces and ``n_classes`` labels (``a3d_vote_workspace_bytes``)."""
+    nbytes = L.load().a3d_vote_workspace_bytes(n, capacity, n_classes)
+    if nbytes == 0:
+        raise ValueError(f"no vote workspace for n={n} capacity={capacity} n_classes={n_classes}")
+    return torch.empty(nbytes, dtype=U8, device=device)
+
+
+def _cosine(name, value):
+    with np.errstate(over="ignore"):
+        value = float(np.float32(value))
+    if not (np.isfinite(value) and -1.0 <= value <= 1.0):
+        raise ValueError(f"{name} must be a finite cosine in [-1, 1], not {value!r}")
+    return value
+
+
+def _tolerance2(name, value):
+    with np.errstate(over="ignore"):
+        value = float(np.float32(value))
+    if not (np.isfinite(value) and value >= 0.0):
+        raise ValueError(f"{name} must be finite and >= 0, not {value!r}")
+    return value
+
+
+def _reference(name, value):
+    a = np.asarray(value, dtype=np.float32).reshape(-1)
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be three finite values")
+    return [float(x) for x in a]
+
+
+def similar_settings(cos_min=1.0, tol2=0.0, oriented=False, ref_normal=None, ref_cos_min=1.0, ref_feat=None, ref_tol2=0.0):
+    """The by-value settings of ``a3d_similar_pieces`` checked on the host as the library checks them: ``(cos_min, tol2,
+    oriented, ref_flags, ref_normal, ref_cos_min, ref_feat, ref_tol2)``.  Cosines finite in [-1, 1], squared tolerances
+    finite and >= 0 (as fp32), ``oriented`` a bool or 0 / 1, a reference three finite values or ``None`` (its bit of
+    ``ref_flags`` then stays clear).  ``ValueError`` naming the argument.  Pure Python."""
+    if oriented not in (False, True, 0, 1):
+        raise ValueError("oriented must be a bool")
+    flags = (SIMILAR_REF_NORMAL if ref_normal is not None else 0) | (SIMILAR_REF_FEAT if ref_feat is not None else 0)
+    return (_cosine("cos_min", cos_min), _tolerance2("tol2", tol2), int(bool(oriented)), flags,
+            _reference("ref_normal", ref_normal) if ref_normal is not None else [0.0] * 3, _cosine("ref_cos_min", ref_cos_min),
+            _reference("ref_feat", ref_feat) if ref_feat is not None else [0.0] * 3, _tolerance2("ref_tol2", ref_tol2))
+
+
+def similar_pair(normal_a=None, normal_b=None, feat_a=None, feat_b=None, cos_min=1.0, tol2=0.0, oriented=False):
+    """``a3d_similar_pair`` (host only, no GPU): whether the pair predicate of ``a3d_similar_pieces`` joins two voxels with
+    these normals (fp32 [3] each, or both ``None``: no normal test) and colours (the same) -- evaluated by the function the
+    kernel calls.  The admissibility test is the same call with the reference as ``b``.  NaNs and zeros are passed on as
+    they are; the thresholds are checked as ``similar_settings`` checks them."""
+    cos_min, tol2, oriented = similar_settings(cos_min, tol2, oriented)[:3]
+    if (normal_a is None) != (normal_b is None) or (feat_a is None) != (feat_b is None):
+        raise ValueError("normal_a / normal_b and feat_a / feat_b are given or left out in pairs")
+    keep, ptrs = [], []
+    for name, v in (("normal_a", normal_a), ("normal_b", normal_b), ("feat_a", feat_a), ("feat_b", feat_b)):
+        a, p = _f32p(name, v, (3,)) if v is not None else (None, None)
+        keep.append(a), ptrs.append(p)
+    got = L.load().a3d_similar_pair(*ptrs, cos_min, tol2, oriented)
+    if got not in (0, 1):
+        raise L.A3DError("a3d_similar_pair refused its arguments")
+    return bool(got)
+
+
+def similar_pieces(scene, keys=None, normals=None, feats=None, cos_min=1.0, tol2=0.0, oriented=False, ref_normal=None,
+                   ref_cos_min=1.0, ref_feat=None, ref_tol2=0.0, connectivity=26, click_rows=(), inverse_map=None, piece_qv=None,
+                   piece_full=None, records=None, count=None, workspace=None):
+    """``a3d_similar_pieces``: the connected pieces of the voxels of ``scene`` (an ``engine.Scene``; n rows in the caller's
+    order) under a SIMILARITY: two neighbours under ``connectivity`` are joined when they hold the same key (``keys`` int32
+    [n], ``None``: all 0; a negative key belongs to no piece), their ``normals`` fp32 [n, 3] have ``|dot| >= cos_min`` (``dot``
+    with ``oriented``) and their ``feats`` fp32 [n, 3] a squared distance ``<= tol2`` -- each test only when its array is given.
+    ``ref_normal`` / ``ref_feat`` (three values, with ``ref_cos_min`` / ``ref_tol2``): only the rows that pass the same test
+    against this reference take part at all; a reference needs its array.  Everything else -- ``click_rows``,
+    ``inverse_map``, ``records``, ``count``, ``workspace`` and the return value ``(piece_qv, piece_full, records, count,
+    workspace)`` -- is ``label_pieces``'; ``read_pieces`` decodes the host copies of the last two."""
+    handle, n = _scene_rows(scene)
+    settings = similar_settings(cos_min, tol2, oriented, ref_normal, ref_cos_min, ref_feat, ref_tol2)
+    if (ref_normal is not None and normals is None) or (ref_feat is not None and feats is None):
+        raise ValueError("a reference needs its array: ref_normal goes with normals, ref_feat with feats")
+    connectivity = _connectivity(connectivity)
+    first = next((t for t in (keys, normals, feats, piece_qv, workspace) if t is not None), None)
+    dev = _device("keys", first) if first is not None else _device("scene", getattr(scene, "workspace", None))
+    a = L.SimilarPiecesArgs()
+    a.scene, a.n = handle, n
+    a.keys_dev = _ptr("keys", keys, I32, (n,), dev, optional=True)
+    a.normal_qv_dev = _ptr("normals", normals, F32, (n, 3), dev, optional=True)
+    a.feat_qv_dev = _ptr("feats", feats, F32, (n, 3), dev, optional=True)
+    a.cos_min, a.tol2, a.oriented, a.ref_flags = settings[:4]
+    a.ref_normal[:], a.ref_cos_min, a.ref_feat[:], a.ref_tol2 = settings[4:]
+    outs = _pieces_outputs(a, n, dev, connectivity, click_rows, inverse_map, piece_qv, piece_full, records, count, workspace)
+    L.check(L.load().a3d_similar_pieces(C.byref(a), L.stream(dev)), "a3d_similar_pieces")
+    return outs
+
+
+def vote_settings(min_voxels, share, n_classes=256, capacity=1024):
+    """``(min_voxels, share_num, share_den, n_classes, capacity)`` as ``a3d_vote_pieces`` takes them, checked on the host:
+    ``min_voxels`` an integer >= 1, ``share`` a pair of integers with ``1 <= num <= den <= 65536``, ``n_classes`` in 1 .. 256,
+    ``capacity`` an integer >= 0.  ``ValueError`` naming the argument.  Pure Python."""
+    try:
+        num, den = share
+    except (TypeError, ValueError):
+        raise ValueError("share must be a pair of integers (num, den)") from None
+    for name, value, lo, hi in (("min_voxels", min_voxels, 1, (1 << 31) - 1), ("share numerator", num, 1, VOTE_MAX_DEN),
+                                ("share denominator", den, 1, VOTE_MAX_DEN), ("n_classes", n_classes, 1, 256),
+                                ("capacity", capacity, 0, (1 << 31) - 1)):
+        if isinstance(value, (bool, float)) or int(value) != value or not lo <= value <= hi:
+            raise ValueError(f"{name} must be an integer in {lo} .. {hi}")
+    if num > den:
+        raise ValueError("share must be at most 1: num <= den")
+    return int(min_voxels), int(num), int(den), int(n_classes), int(capacity)
+
+
+def vote_pieces(scene, labels, piece_qv, workspace, min_voxels=8, share=(2, 3), click_rows=(), n_classes=256, capacity=1024,
+                labels_out=None, summary=None):
+    """``a3d_vote_pieces``: snaps ``labels`` int32 [n] in 0..n_classes-1 to a partition.  ``piece_qv`` and ``workspace``: what
+    ``label_pieces`` or ``similar_pieces`` returned for this scene (the workspace holds the pieces' sizes; it must be a
+    ``vote_workspace(n, device, capacity, n_classes)``).  Every piece of at least ``min_voxels`` voxels whose most frequent
+    label (ties: the lowest) holds at least ``share = (num, den)`` of its voxels, and which holds no clicked row of another
+    label, gives all its voxels that label; everything else is copied.  Returns ``(labels_out int32 [n], summary uint8
+    [32])`` on the device; ``read_vote_summary`` decodes the summary's host copy -- on ``VOTE_OVERFLOW`` nothing was written
+    to ``labels_out`` and ``eligible_pieces`` is the capacity to call again with."""
+    settings = vote_settings(min_voxels, share, n_classes, capacity)
+    handle, n = _scene_rows(scene)
+    dev = _device("labels", labels)
+    a = L.VotePiecesArgs()
+    a.scene, a.n = handle, n
+    a.labels_dev = _ptr("labels", labels, I32, (n,), dev)
+    a.piece_qv_dev = _ptr("piece_qv", piece_qv, I32, (n,), dev)
+    a.n_clicks = _click_rows(a.click_row, click_rows)
+    a.min_voxels, a.share_num, a.share_den, a.n_classes, a.capacity = settings
+    labels_out = _out("labels_out", labels_out, I32, (n,), dev)
+    if n and labels_out.data_ptr() == labels.data_ptr():
+        raise ValueError("labels_out may not alias labels")
+    a.labels_out_dev = labels_out.data_ptr()
+    summary = _out("summary", summary, U8, (VOTE_SUMMARY.itemsize,), dev)
+    if summary.data_ptr() % 4:
+        raise ValueError("summary must be 4-byte aligned")
+    a.summary_dev = summary.data_ptr()
+    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
+    if a.workspace_bytes < L.load().a3d_vote_workspace_bytes(n, a.capacity, a.n_classes) or workspace.data_ptr() % 256:
+        raise ValueError("workspace too small or not 256-byte aligned (vote_workspace(n, device, capacity, n_classes))")
+    L.check(L.load().a3d_vote_pieces(C.byref(a), L.stream(dev)), "a3d_vote_pieces")
     return labels_out, summary
 
 

@@ -1027,6 +1027,133 @@ typedef struct a3d_absorb_pieces_args {
 size_t a3d_absorb_workspace_bytes(int64_t n, int capacity, int n_classes);
 int    a3d_absorb_pieces(const a3d_absorb_pieces_args* args, void* stream);
 
+/* WHICH VOXELS BELONG TO ONE SURFACE: connected components under a pairwise SIMILARITY of normals and colours, and the vote
+ * that snaps a labelling to such a partition (csrc/session_pieces.hip).  The rules are this library's: the reference's tool
+ * has neither a magic wand nor a snap.  Adjacency, record list, capacity protocol and workspace are a3d_label_pieces' and
+ * a3d_absorb_pieces'.
+ *
+ * a3d_similar_pieces.  Everything a3d_label_pieces takes -- keys_dev may be NULL here: every key is 0 -- and
+ * normal_qv_dev fp32 [n][3] or NULL, feat_qv_dev fp32 [n][3] or NULL (the colours the backbone was fed), both in the CALLER's
+ * row order; by value cos_min, tol2, oriented, ref_flags, ref_normal[3], ref_cos_min, ref_feat[3], ref_tol2.
+ *   THE PREDICATES are fp32, every operation rounded on its own (fp contract off), in the order written:
+ *     NSIM(a, b, c):  dot = (a0*b0 + a1*b1) + a2*b2;  passes iff (oriented ? dot : fabsf(dot)) >= c.
+ *     FSIM(a, b, t):  d_k = a_k - b_k;  q = (d0*d0 + d1*d1) + d2*d2;  passes iff q <= t.
+ *   A comparison with a NaN fails.  There is NO special case for a zero normal: its dot is 0, so with cos_min > 0 such a
+ *   voxel joins nobody.
+ *   A row is ADMISSIBLE iff its key is >= 0, and with A3D_SIMILAR_REF_NORMAL set NSIM(normal[i], ref_normal, ref_cos_min),
+ *   and with A3D_SIMILAR_REF_FEAT set FSIM(feat[i], ref_feat, ref_tol2).  A row that is not admissible belongs to no piece
+ *   (piece_qv = -1).
+ *   Two admissible rows are JOINED iff they are neighbours under the connectivity (a3d_label_pieces' offsets, never across
+ *   batch samples), hold the same key, NSIM(normal[i], normal[j], cos_min) when normal_qv_dev is given, and
+ *   FSIM(feat[i], feat[j], tol2) when feat_qv_dev is given.
+ *   Both predicates are SYMMETRIC BIT FOR BIT: products commute, and a - b and b - a have equal squares.  It therefore does
+ *   not matter which end of an edge evaluates them: the components are a function of the arguments, and by a3d_label_pieces'
+ *   argument (the root of a class is its smallest row) so is every output.  Two calls give the same bytes.
+ *   A PIECE is a class of the transitive closure of "joined" -- a CHAIN: along a smoothly turning surface the two ends of a
+ *   piece may differ by far more than the threshold; the reference test bounds every member against one value instead.
+ *   piece_qv, piece_full, the records in ascending root order, n_out_dev and the workspace contents (of
+ *   a3d_pieces_workspace_bytes(n) bytes; a3d_vote_pieces and a3d_absorb_pieces read the sizes there) are exactly as
+ *   a3d_label_pieces defines them.  With neither array and ref_flags == 0 the call writes the bytes a3d_label_pieces writes.
+ *   A3D_ERR_INVALID with nothing launched: everything a3d_label_pieces refuses (but keys_dev may be NULL); cos_min or
+ *   ref_cos_min not finite or outside [-1, 1]; tol2 or ref_tol2 not finite or < 0; a ref_flags bit without its array; bits
+ *   other than 0 and 1; a reference value that is not finite; oriented other than 0 or 1.
+ *
+ * a3d_similar_pair -- the pair predicate on the host, by the function the kernel calls (no GPU): 1 when
+ * (normal_a == NULL || NSIM(normal_a, normal_b, cos_min)) && (feat_a == NULL || FSIM(feat_a, feat_b, tol2)), else 0.  A pair
+ * of pointers is given or left out together.  The admissibility test is the same function with the reference as `b`.
+ * -1 for a pointer without its partner or oriented other than 0 or 1.  The thresholds are NOT range-checked here.
+ *
+ * a3d_vote_pieces -- snap a labelling to a partition.  labels_dev int32 [n] in 0..n_classes-1 (n_classes <= 256);
+ * piece_qv_dev = ANY partition a3d_label_pieces or a3d_similar_pieces wrote for this scene, and workspace_dev = the workspace
+ * of that call (it holds the sizes at the roots), now of at least a3d_vote_workspace_bytes(n, capacity, n_classes) bytes -- or
+ * a buffer of that size whose first a3d_pieces_workspace_bytes(n) bytes are a copy of that workspace, taken after the call;
+ * min_voxels >= 1; share_num, share_den with 1 <= num <= den <= 65536; the clicked rows; capacity = the number of eligible
+ * pieces the call has room for.
+ * The rule is ONE simultaneous step on the INPUT labels, all integers:
+ *   A piece is ELIGIBLE when it has >= min_voxels voxels.
+ *   votes[l] = the number of its voxels with label l.  A label outside 0..n_classes-1 sets A3D_VOTE_BAD_LABEL; such a voxel
+ *   casts no vote and keeps its label.
+ *   The WINNER is the label with the most votes.  Ties go to the lowest label.
+ *   The piece PASSES iff votes[winner] * share_den >= voxels * share_num (int64).
+ *   It is BLOCKED when it holds a clicked row whose label differs from the winner: the snap never contradicts a click.  A
+ *   clicked row outside 0..n-1 is ignored.
+ *   A piece that is eligible, passes and is not blocked gives every one of its voxels (with a label in range) the winner.
+ *   Everything else is copied unchanged, rows with no piece included.
+ * labels_out_dev int32 [n] may not alias labels_dev.  The summary (cleared by the call) sorts every eligible piece into at
+ * most one class, tested in this order: UNIFORM (every voxel already holds the winner), BELOW SHARE (does not pass), BLOCKED,
+ * RELABELLED (at least one voxel changed); relabelled_voxels counts the voxels that changed.  (An eligible piece whose only
+ * other voxels hold labels out of range falls in none of the four.)  A3D_VOTE_OVERFLOW = there are more eligible pieces than
+ * `capacity`: NOTHING is written to labels_out and eligible_pieces is the capacity needed.  The eligible pieces are numbered
+ * by a3d_absorb_pieces' one-block scan, votes are integer atomics: two calls give the same bytes.
+ * A3D_ERR_INVALID with nothing launched: no scene, n != the scene's level-0 size, n_clicks outside 0..A3D_MAX_CLICKS,
+ * n_classes outside 1..256, capacity < 0, min_voxels < 1, share_num / share_den outside 1 <= num <= den <= 65536, no
+ * summary_dev, a needed pointer NULL, labels_out_dev == labels_dev, a workspace that is too small or misaligned. */
+#define A3D_SIMILAR_REF_NORMAL 1
+#define A3D_SIMILAR_REF_FEAT   2
+typedef struct a3d_similar_pieces_args {
+  const a3d_scene* scene;
+  int64_t        n;
+  const int32_t* keys_dev;          /* [n] caller's row order, or NULL: all 0 */
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL */
+  int64_t        n_full;
+  int32_t*       piece_qv_dev;      /* out [n] */
+  int32_t*       piece_full_dev;    /* out [n_full] */
+  a3d_piece*     out_dev;           /* out: max_out records */
+  int32_t*       n_out_dev;         /* out int32 [2]: the true count, the error word */
+  void*          workspace_dev;
+  size_t         workspace_bytes;
+  const float*   normal_qv_dev;     /* [n][3] or NULL */
+  const float*   feat_qv_dev;       /* [n][3] or NULL */
+  float          cos_min;
+  float          tol2;
+  int32_t        oriented;
+  int32_t        ref_flags;
+  float          ref_normal[3];
+  float          ref_cos_min;
+  float          ref_feat[3];
+  float          ref_tol2;
+  int32_t        connectivity;
+  int32_t        max_out;
+  int32_t        n_clicks;
+  int32_t        reserved_;
+  int32_t        click_row[A3D_MAX_CLICKS];
+} a3d_similar_pieces_args;
+int    a3d_similar_pieces(const a3d_similar_pieces_args* args, void* stream);
+int    a3d_similar_pair(const float* normal_a, const float* normal_b, const float* feat_a, const float* feat_b, float cos_min,
+                        float tol2, int oriented);
+
+#define A3D_VOTE_OVERFLOW  1
+#define A3D_VOTE_BAD_LABEL 2
+typedef struct a3d_vote_summary {
+  int32_t eligible_pieces;          /* also the capacity needed when A3D_VOTE_OVERFLOW is set */
+  int32_t uniform_pieces;
+  int32_t relabelled_pieces;
+  int32_t relabelled_voxels;
+  int32_t blocked_pieces;
+  int32_t below_share_pieces;
+  int32_t err;
+  int32_t reserved_;
+} a3d_vote_summary;                /* 32 bytes */
+typedef struct a3d_vote_pieces_args {
+  const a3d_scene* scene;
+  int64_t        n;
+  const int32_t* labels_dev;        /* [n] */
+  const int32_t* piece_qv_dev;      /* [n] a partition a3d_label_pieces / a3d_similar_pieces wrote */
+  int32_t*       labels_out_dev;    /* out [n] */
+  a3d_vote_summary* summary_dev;
+  void*          workspace_dev;     /* the workspace of the call that wrote piece_qv */
+  size_t         workspace_bytes;
+  int32_t        min_voxels;
+  int32_t        n_classes;
+  int32_t        capacity;
+  int32_t        share_num;
+  int32_t        share_den;
+  int32_t        n_clicks;
+  int32_t        click_row[A3D_MAX_CLICKS];
+} a3d_vote_pieces_args;
+size_t a3d_vote_workspace_bytes(int64_t n, int capacity, int n_classes);
+int    a3d_vote_pieces(const a3d_vote_pieces_args* args, void* stream);
+
 /* HOW FAR ALONG THE SURFACE: a bounded shortest-path distance from a set of seed voxels over the same adjacency, and which
  * seed is nearest (csrc/session_grow.hip).  The rule is this library's: the reference's tool selects nothing by distance.
  * a3d_label_pieces answers "what is connected at all"; this answers "what is connected within a distance, and how far".
