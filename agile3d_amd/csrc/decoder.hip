@@ -2680,12 +2680,265 @@ static int check_packs(const a3d_decoder_weights* w) {
   return A3D_OK;
 }
 
+// ---- planning: which kernel builds a launch group of the decoder runs, and with how much LDS.  Plain C++ from here to the
+// end-of-planning mark (no HIP types; env_int is common.h's; D, H, kWTile, A3D_MAX_QUERIES and the A3D_* codes are the ones
+// above), so that the block compiles into a stand-alone host program that sweeps it (tests/decoder_plan_main.cpp).
+static_assert(D == 128 && H == 8 && kWTile == 16 * 136 && A3D_MAX_QUERIES == 256, "tests/decoder_plan_main.cpp states these too");
+constexpr size_t kDecLdsMax = (size_t)160 * 1024;
+
+// the A/B switches of the environment, read once per process
+struct DecSwitches {
+  bool fused_c2s;    // A3D_FUSED_C2S=0 keeps the separate K / V GEMMs + k_c2s_attn
+  bool fused_wide;   // A3D_FUSED_WIDE=0 (or A3D_FUSED_C2S=0) keeps the unfused kernels above 64 queries
+  bool fused_s2o;    // A3D_FUSED_S2O=0: k_s2c_w + k_out_w for up to five query tiles too
+  bool fused_s2c;    // A3D_FUSED_S2C=0: k_q_s2c + k_out_ln_mask instead of k_s2c_out
+  // The wide tier's kernels take a sample's tile count from the table, so they serve fewer than 65 queries too (under the
+  // 5-tile build).  From 33 queries on they are the default: a pass at 80 k points 0.83 -> 0.80 ms at 35 queries, 0.97 -> 0.83
+  // at 60 (k_q_s2c + k_out_ln_mask and a 64-row query block against k_s2c_w + k_out_w and two 32-row blocks), and those samples
+  // then share the launch group of a call's larger ones.  Up to 32 queries k_s2c_out (one kernel for the whole scene-to-click
+  // half) stays ahead.  A3D_WIDE_FROM=<queries> moves the edge (65: the round's first protocol; A/B, tests).
+  int wide_from;
+};
+inline DecSwitches make_dec_switches(int fused_c2s, int fused_wide, int fused_s2o, int fused_s2c, int wide_from) {
+  DecSwitches s;
+  s.fused_c2s = fused_c2s != 0;
+  s.fused_wide = fused_wide != 0 && s.fused_c2s;
+  s.fused_s2o = fused_s2o != 0;
+  s.fused_s2c = fused_s2c != 0;
+  s.wide_from = wide_from < 17 ? 17 : wide_from;
+  return s;
+}
+inline const DecSwitches& dec_switches() {
+  static const DecSwitches v = make_dec_switches(env_int("A3D_FUSED_C2S", 1), env_int("A3D_FUSED_WIDE", 1), env_int("A3D_FUSED_S2O", 1),
+                                                 env_int("A3D_FUSED_S2C", 1), env_int("A3D_WIDE_FROM", 33));
+  return v;
+}
+
+// rows of a sample's query-side buffers
+constexpr int round_qp(int nq) { return nq <= 16 ? 16 : nq <= 32 ? 32 : nq <= 48 ? 48 : (nq + 63) / 64 * 64; }
+// smallest wide-tier tile count that holds nq queries (0: not served -- more than 224 queries run the unfused kernels)
+constexpr int wide_qt(int nq) {
+  return nq <= 64 ? 0 : nq <= 80 ? 5 : nq <= 96 ? 6 : nq <= 112 ? 7 : nq <= 128 ? 8 : nq <= 160 ? 10 : nq <= 192 ? 12 : nq <= 224 ? 14 : 0;
+}
+// tile count of the k_c2s_attn_b build that holds `tiles` 16-query tiles of a sample whose buffers have round_qp(nq) rows
+constexpr int wide_qt_of_tiles(int tiles) { return tiles <= 8 ? tiles : tiles <= 10 ? 10 : tiles <= 12 ? 12 : 14; }
+// a query list the kernels are not built for
+inline bool dec_sample_unsupported(int nq, int n_objects, int n_clicks) {
+  return nq > A3D_MAX_QUERIES || n_objects > 254 || n_clicks > 200;
+}
+// tile count of the fused wide tier (decoder_wide.h) that serves a sample, 0 = none
+inline int dec_sample_qtw(int nq, const DecSwitches& sw) {
+  int qtw = sw.fused_wide ? wide_qt(nq) : 0;
+  if (sw.fused_wide && nq >= sw.wide_from && nq <= 64) qtw = 5;   // (the smallest build; the kernels take the sample's own tile count)
+  return qtw;
+}
+// consecutive samples of a call share a launch group: the wide tier's whatever their query counts, the others by padded count
+inline bool dec_same_group(int qtw_a, int qp_a, int qtw_b, int qp_b) {
+  return (qtw_a > 0 && qtw_b > 0) || (qp_a == qp_b && qtw_a == qtw_b);
+}
+// k_ln_mask's LDS for a sample of K objects whose buffers have qp rows, in blocks of QP rows
+inline size_t dec_ln_mask_lds(int QP, int qp, int K) {
+  return ((size_t)QP * 132 + 4 * 16 * (qp + 1) + 4 * 16 * (K + 1)) * 4 + (size_t)(K + 1) * 4;
+}
+
+// Workgroups of the persistent point-side kernels, dealt to the samples of a launch group in proportion to their 16-point
+// groups and held to [1, useful]: eight waves take a group each (useful = ceil(groups / 8)), or the workgroup takes one
+// (wg_per_group: decoder_wide.h).  Sample i gets the workgroups [wg_begin[i], wg_end[i]); returns the grid.
+inline int dec_wg_shares(const int* n, int ns, bool wg_per_group, int* wg_begin, int* wg_end) {
+  int64_t tot_groups = 0;
+  for (int si = 0; si < ns; ++si) tot_groups += (n[si] + 15) / 16;
+  const int max_grid = 256;
+  int grid = 0;
+  for (int si = 0; si < ns; ++si) {
+    const int ngroups = (n[si] + 15) / 16;
+    int share = (int)((int64_t)max_grid * ngroups / tot_groups);
+    const int useful = wg_per_group ? ngroups : (ngroups + 7) / 8;
+    share = share < 1 ? 1 : share;
+    share = share > useful ? useful : share;
+    wg_begin[si] = grid;
+    wg_end[si] = grid += share;
+  }
+  return grid;
+}
+
+struct DecSampleShape {
+  int nq, K;        // queries (clicks + learned background queries), objects
+  int qtw;          // dec_sample_qtw
+  int kv0_state;    // 0: no first-layer cache, 1: this pass fills it, 2: this pass reads it
+};
+enum DecKernel {
+  kDkNone,
+  kDkC2sAttn,       // k_c2s_attn<QT>, a launch per sample (after two a3d_linear calls unless the cache serves K / V)
+  kDkC2sAttnB,      // k_c2s_attn_b<QT>: the cached first layer, all samples in one launch
+  kDkKvC2s,         // k_kv_c2s<QT, LO>
+  kDkC2sW,          // k_c2s_w<QT>
+  kDkS2cOut,        // k_s2c_out<QT, NW, KG, QC, LO>
+  kDkQS2c,          // k_q_s2c<QT, QC>
+  kDkS2cAttnWide,   // k_s2c_attn_wide<QT>, a launch per sample (after a3d_linear unless the cache serves Q)
+  kDkS2oW,          // k_s2o_w<5, QC>
+  kDkS2cW,          // k_s2c_w<QT, QC>
+  kDkOutLnMask,     // k_out_ln_mask<QT>
+  kDkLnMask,        // k_ln_mask<QT>, a launch per sample after a3d_linear (lds: dec_ln_mask_lds of the sample)
+  kDkOutW           // k_out_w<QT>
+};
+struct DecPhase {
+  DecKernel kernel;
+  int qt, waves;      // the build's tile count; waves per workgroup
+  bool kg, qc, lo;    // k_s2c_out: keys in global memory; queries from the cache (also k_q_s2c, k_s2o_w, k_s2c_w); leftover tile (also k_kv_c2s)
+  size_t lds;         // dynamic LDS bytes of the launch
+};
+struct DecPlan {
+  int rc;                   // A3D_OK, or A3D_ERR_UNSUPPORTED: err_nq queries (0: the group) x err_K objects need err_lds bytes
+  int err_nq, err_K;
+  size_t err_lds;
+  bool wide;                // run_decoder_wide<qt>, else run_decoder<qt>
+  int qt, qp, nblk;         // qp: rows of the (longest) query-side buffers, nblk: query blocks of the query side
+  int Kmax, nq_max, nq_min, nqr_max;
+  bool cached0, fill0;      // the first layer runs on the cached keys / values / queries; some sample's cache is filled first
+  bool leftover, fuse_c2s, fuse_s2c, fuse_out, fuse_all, s2c_kg, fits12;
+  bool wg_per_group, part_per_wg;   // upload_tables: a workgroup (not a wave) takes a 16-point group; one flash partial per workgroup
+  DecPhase c2s[2], s2c[2], out[2];  // per phase: [0] the first layer, [1] the others
+};
+
+inline DecPhase dec_phase(DecKernel k, int qt, size_t lds, int waves = 8, bool kg = false, bool qc = false, bool lo = false) {
+  DecPhase ph;
+  ph.kernel = k, ph.qt = qt, ph.waves = waves, ph.kg = kg, ph.qc = qc, ph.lo = lo, ph.lds = lds;
+  return ph;
+}
+
+// The plan of one launch group (consecutive samples for which dec_same_group holds).
+inline DecPlan plan_decoder(const DecSampleShape* s, int ns, const DecSwitches& sw) {
+  DecPlan p = {};
+  p.rc = A3D_OK;
+  p.nq_min = A3D_MAX_QUERIES;
+  // The first layer runs on the scene's cached keys / values / scene-to-click queries when EVERY sample of the group has a
+  // usable cache: K = (feats + pos) Wk^T + bk, V = feats Wv^T + bv and Q = (feats + pos) Wq^T + bq (agile3d.py:305-312)
+  // depend on the scene only, the interactive loop runs ~100 passes on it
+  p.cached0 = true;
+  int qp_max = 0, nqt_max = 0, qtw = 0;
+  for (int i = 0; i < ns; ++i) {
+    p.Kmax = s[i].K > p.Kmax ? s[i].K : p.Kmax;
+    p.nq_max = s[i].nq > p.nq_max ? s[i].nq : p.nq_max;
+    p.nq_min = s[i].nq < p.nq_min ? s[i].nq : p.nq_min;
+    p.cached0 = p.cached0 && s[i].kv0_state != 0;
+    qp_max = round_qp(s[i].nq) > qp_max ? round_qp(s[i].nq) : qp_max;
+    nqt_max = (s[i].nq + 15) / 16 > nqt_max ? (s[i].nq + 15) / 16 : nqt_max;
+    // the wide build that holds the longest query list of the group (0: the group runs the <= 64 / unfused kernels)
+    if (s[0].qtw > 0) {
+      qtw = s[i].qtw > qtw ? s[i].qtw : qtw;
+      qtw = wide_qt(s[i].nq) > qtw ? wide_qt(s[i].nq) : qtw;
+    }
+  }
+  for (int i = 0; i < ns; ++i) p.fill0 = p.fill0 || (p.cached0 && s[i].kv0_state == 1);
+  const int Kmax = p.Kmax, nq_max = p.nq_max;
+  p.nqr_max = (nq_max + 3) & ~3;
+  const DecPhase none = dec_phase(kDkNone, 0, 0, 0);
+
+  if (qtw > 0) {
+    // ---- the fused wide tier (decoder_wide.h): QT = padded queries / 16 of the three point-side kernels; the query side
+    // runs in blocks of 32 rows, as many as the longest query list of the group needs
+    const int QT = qtw;
+    p.wide = true, p.qt = QT, p.qp = qp_max, p.nblk = (nq_max + 31) / 32;
+    p.wg_per_group = true, p.part_per_wg = true;
+    const size_t stage_lds = (size_t)2 * 2 * kWTile * 4;                       // two slots of (rows, position encodings)
+    const size_t out_lds = ((size_t)6 * kWTile + 2 * 256 + 2 * 32 * (Kmax + 1)) * 4 + (size_t)(Kmax + 1) * 4;   // k_out_w: O slots, rows, statistics, maxima, histogram
+    if (out_lds > kDecLdsMax) {
+      p.rc = A3D_ERR_UNSUPPORTED, p.err_nq = 0, p.err_K = Kmax, p.err_lds = out_lds;
+      return p;
+    }
+    for (int first = 0; first < 2; ++first) {
+      const bool cached = first && p.cached0, qc = cached;
+      DecPhase &c2s = p.c2s[first ? 0 : 1], &s2c = p.s2c[first ? 0 : 1], &out = p.out[first ? 0 : 1];
+      // the unfused flash kernel over the cached keys / values, ALL samples in one launch: the widest sample's kernel, every
+      // sample by its OWN tile count (c2s_attn_body skips the tiles past it)
+      c2s = cached ? dec_phase(kDkC2sAttnB, wide_qt_of_tiles(nqt_max), 0) : dec_phase(kDkC2sW, QT, stage_lds);
+      // scene-to-click: up to five query tiles as ONE kernel (k_s2o_w), else attention, then output projection + residual +
+      // LayerNorm + mask head
+      if (QT == 5 && sw.fused_s2o) {
+        const size_t s2o_lds = ((size_t)(4 + 5) * kWTile + 2 * 256 + 2 * 32 * (Kmax + 1) + ((Kmax + 1 + 3) & ~3)) * 4;
+        s2c = dec_phase(kDkS2oW, 5, s2o_lds + (qc ? 0 : (size_t)4 * kWTile * 4), 8, false, qc);
+        out = none;
+      } else {
+        s2c = dec_phase(kDkS2cW, QT, qc ? 0 : stage_lds, 8, false, qc);
+        out = dec_phase(kDkOutW, QT, out_lds);   // (its per-object maxima grow with the objects: past 64 KB from ~43 objects on)
+      }
+    }
+    return p;
+  }
+
+  // ---- up to 64 queries (and the unfused kernels): all samples of the group share QT (= padded query count / 16, 4 from 64 on)
+  p.qp = round_qp(s[0].nq);
+  const int QT = p.qp == 16 ? 1 : p.qp == 32 ? 2 : p.qp == 48 ? 3 : 4, QP = QT * 16;
+  p.qt = QT, p.nblk = p.qp / QP;             // query blocks (1 unless nq > 64)
+  const int nblk = p.nblk;
+  // every sample of the launch has 17 .. 20 queries: the second query tile is at most four queries wide and runs on the
+  // 4x4x1 builds of k_kv_c2s / k_s2c_out
+  p.leftover = QT == 2 && p.nq_min >= 17 && nq_max <= 20;
+  const size_t s2c_lds = (size_t)2 * QP * 132 * 4;             // keys + values of the queries (k_s2c_attn_wide)
+  const size_t qs2c_lds = ((size_t)QP * 132 + (size_t)D * (QP + 4) + D) * 4;   // k_q_s2c: keys, transposed values, bias
+  const size_t fused_lds = (size_t)64 * 1024 + ((size_t)3 * D + QP * 132 + 8 * 16 * (QP + 1) + 8 * 16 * (Kmax + 1)) * 4 +
+                           (size_t)(2 * Kmax + 3) * 4;
+  for (int i = 0; i < ns; ++i) {
+    const size_t lnm_lds = dec_ln_mask_lds(QP, round_qp(s[i].nq), s[i].K);
+    if (lnm_lds > kDecLdsMax) {
+      p.rc = A3D_ERR_UNSUPPORTED, p.err_nq = s[i].nq, p.err_K = s[i].K, p.err_lds = lnm_lds;
+      return p;
+    }
+  }
+  // which of the wide phases run as one fused launch for the batch
+  p.fuse_c2s = sw.fused_c2s && nblk == 1;   // up to 64 queries (k_kv_c2s<1..4>)
+  p.fuse_s2c = sw.fused_c2s && nblk == 1;
+  p.fuse_out = p.fuse_s2c && fused_lds <= kDecLdsMax;
+  p.part_per_wg = p.fuse_c2s;
+  // scene-to-click + output projection + LayerNorm + mask head as ONE kernel when both packed weight matrices and the
+  // queries' compact keys / values fit the LDS (about 24 queries at 5 objects); A3D_FUSED_S2C=0 keeps the two kernels
+  const int nqr_max = p.nqr_max;
+  const size_t s2c_rest = ((size_t)D * (nqr_max + 4) + 4 * D + (size_t)8 * 16 * (Kmax + 1) + 2 * Kmax + 3 + QT * 16 + 1) * 4;
+  const size_t s2c_keys = (size_t)nqr_max * 136 * 4;
+  const size_t staging12 = (size_t)4 * 16 * (Kmax + 1) * 4;   // twelve waves' logits staging
+  // the keys move out of LDS (k_s2c_out<.., KG>) when everything else still fits: 25..32 queries at 5 objects
+  p.s2c_kg = (size_t)128 * 1024 + s2c_keys + s2c_rest + staging12 > kDecLdsMax;
+  const size_t s2c_out_lds = (size_t)128 * 1024 + (p.s2c_kg ? 0 : s2c_keys) + s2c_rest;
+  const size_t s2c_out_lds12 = s2c_out_lds + staging12;
+  p.fuse_all = p.fuse_out && sw.fused_s2c && QT <= 2 && s2c_out_lds <= kDecLdsMax;
+  // twelve waves (three per SIMD) when their logits staging fits, else eight; keys that stay in LDS imply that it fits
+  p.fits12 = s2c_out_lds12 <= kDecLdsMax;
+  for (int first = 0; first < 2; ++first) {
+    const bool cached = first && p.cached0, qc = cached;   // the scene-to-click half of the first layer reads its queries from the cache too
+    DecPhase &c2s = p.c2s[first ? 0 : 1], &s2c = p.s2c[first ? 0 : 1], &out = p.out[first ? 0 : 1];
+    // ---- click-to-scene
+    if (cached) {
+      c2s = nblk == 1 ? dec_phase(kDkC2sAttnB, QT, 0) : dec_phase(kDkC2sAttn, QT, 0);   // one query block: all samples in ONE launch
+    } else if (p.fuse_c2s) {
+      // K / V projections fused in (K, V never reach HBM), all samples in one launch
+      const size_t c2s_lds = (size_t)128 * 1024 + (QT == 4 ? (size_t)QP * 128 * 4 : ((size_t)QP * 132 + 2 * D) * 4);
+      c2s = dec_phase(kDkKvC2s, QT, c2s_lds, 8, false, false, p.leftover);
+    } else {
+      c2s = dec_phase(kDkC2sAttn, QT, 0);
+    }
+    // ---- scene-to-click
+    if (p.fuse_all) {
+      // the whole half in one pass: O never reaches HBM (k_s2c_out).  A cached group that needs the 8-wave build runs the one
+      // without the cached queries (it recomputes them); the leftover builds keep their keys in LDS
+      const int waves = p.fits12 ? 12 : 8;
+      const bool lo = p.leftover && !p.s2c_kg && p.fits12;
+      s2c = dec_phase(kDkS2cOut, QT, p.fits12 ? s2c_out_lds12 : s2c_out_lds, waves, p.s2c_kg, qc && p.fits12, lo);
+      out = none;
+      continue;
+    }
+    s2c = p.fuse_s2c ? dec_phase(kDkQS2c, QT, (size_t)64 * 1024 + qs2c_lds, 8, false, qc) : dec_phase(kDkS2cAttnWide, QT, s2c_lds, 8, false, qc);
+    // ---- output projection + residual + LayerNorm + mask head in one pass (the pre-norm activation stays on chip), or apart
+    out = p.fuse_out ? dec_phase(kDkOutLnMask, QT, fused_lds) : dec_phase(kDkLnMask, QT, dec_ln_mask_lds(QP, p.qp, Kmax), 4);
+  }
+  return p;
+}
+// ---- end of planning
+
 namespace {
 struct DecLayout {
   size_t buf[4], labels, counts, part, meta, desc, q[12], sync, total;
   int qp, nchunk;
 };
-int round_qp(int nq) { return nq <= 16 ? 16 : nq <= 32 ? 32 : nq <= 48 ? 48 : (nq + 63) / 64 * 64; }
 void dec_layout(int64_t n, int nq, DecLayout& L) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -2760,29 +3013,6 @@ extern "C" int a3d_decoder_pack_query_weights(const a3d_decoder_weights* w, int3
   return A3D_OK;
 }
 
-// the A/B switches of the environment (env_int, common.h)
-static bool fused_c2s() {   // A3D_FUSED_C2S=0 keeps the separate K / V GEMMs + k_c2s_attn (A/B switch)
-  static const bool v = env_int("A3D_FUSED_C2S", 1) != 0;
-  return v;
-}
-static bool fused_wide() {   // A3D_FUSED_WIDE=0 (or A3D_FUSED_C2S=0) keeps the unfused kernels above 64 queries (A/B switch, tests)
-  static const bool v = env_int("A3D_FUSED_WIDE", 1) != 0;
-  return v && fused_c2s();
-}
-
-// The wide tier's kernels take a sample's tile count from the table, so they serve fewer than 65 queries too (under the
-// 5-tile build).  From 33 queries on they are the default: a pass at 80 k points 0.83 -> 0.80 ms at 35 queries, 0.97 -> 0.83
-// at 60 (k_q_s2c + k_out_ln_mask and a 64-row query block against k_s2c_w + k_out_w and two 32-row blocks), and those samples
-// then share the launch group of a call's larger ones.  Up to 32 queries k_s2c_out (one kernel for the whole scene-to-click
-// half) stays ahead.  A3D_WIDE_FROM=<queries> moves the edge (65: the round's first protocol; A/B, tests).
-static bool fused_s2o() {   // A3D_FUSED_S2O=0: k_s2c_w + k_out_w for up to five query tiles too (A/B, tests)
-  static const bool v = env_int("A3D_FUSED_S2O", 1) != 0;
-  return v;
-}
-static int wide_from() {
-  static const int v = std::max(17, env_int("A3D_WIDE_FROM", 33));
-  return v;
-}
 // (every kernel here that needs more than 64 KB of LDS is named for launch through big_lds<..>(), common.h)
 
 // one batch sample on the host: validated query list, workspace layout and the views into its workspace
@@ -2827,8 +3057,8 @@ struct Prepared {
   }
 };
 
-// The device tables of one call -- the samples' QueryMeta records, the wide kernels' sample table (workgroups in proportion to
-// the samples' point groups) and the query-side table -- built on the host and uploaded in ONE copy into the first sample's
+// The device tables of one call -- the samples' QueryMeta records, the wide kernels' sample table (workgroups by
+// dec_wg_shares) and the query-side table -- built on the host and uploaded in ONE copy into the first sample's
 // workspace.  wg_per_group: a workgroup (not a wave) takes a 16-point group (decoder_wide.h); part_per_wg: the click-to-scene
 // kernel writes one flash partial per workgroup.
 struct DecTables {
@@ -2851,18 +3081,13 @@ static int upload_tables(Prepared* P, int ns, bool wg_per_group, bool part_per_w
     std::vector<char> up_host(up_bytes);
     for (int si = 0; si < ns; ++si) memcpy(up_host.data() + up_meta + sizeof(QueryMeta) * si, &P[si].hm, sizeof(QueryMeta));
     DecSampleDev* hd = (DecSampleDev*)(up_host.data() + up_samples);
-    int64_t tot_groups = 0;
-    for (int si = 0; si < ns; ++si) tot_groups += (P[si].n + 15) / 16;
-    const int max_grid = 256;
+    int n_pts[kMaxBatchSamples], wg_begin[kMaxBatchSamples], wg_end[kMaxBatchSamples];   // (dispatch_decoder holds ns to that)
+    for (int si = 0; si < ns; ++si) n_pts[si] = P[si].n;
+    grid = dec_wg_shares(n_pts, ns, wg_per_group, wg_begin, wg_end);
     for (int si = 0; si < ns; ++si) {
       Prepared& p = P[si];
-      const int ngroups = (p.n + 15) / 16;
-      int share = (int)((int64_t)max_grid * ngroups / tot_groups);
-      const int useful = wg_per_group ? ngroups : (ngroups + 7) / 8;   // eight waves take a group each, or the workgroup takes one
-      share = share < 1 ? 1 : share;
-      share = share > useful ? useful : share;
-      p.wg_begin = grid;
-      p.wg_end = grid += share;
+      p.wg_begin = wg_begin[si];
+      p.wg_end = wg_end[si];
       DecSampleDev& d = hd[si];
       d.wg_begin = p.wg_begin;
       d.wg_end = p.wg_end;
@@ -2917,28 +3142,11 @@ static int upload_tables(Prepared* P, int ns, bool wg_per_group, bool part_per_w
 // the point rows layer l reads and writes: layer 0 reads the backbone's features, the layers alternate between bufC and bufD
 static const float* layer_src(const Prepared& p, int l) { return l == 0 ? p.feats : ((l - 1) & 1) ? p.bufD : p.bufC; }
 static float* layer_dst(const Prepared& p, int l) { return (l & 1) ? p.bufD : p.bufC; }
-// totals of a launch group
-struct GroupTotals {
+// points of a launch group (the profiler's scopes)
+static int64_t group_points(const Prepared* P, int ns) {
   int64_t n_total = 0;
-  int Kmax = 0, nq_max = 0, nq_min = A3D_MAX_QUERIES;
-};
-static GroupTotals group_totals(const Prepared* P, int ns) {
-  GroupTotals t;
-  for (int si = 0; si < ns; ++si) {
-    t.n_total += P[si].n;
-    t.Kmax = std::max(t.Kmax, P[si].hm.K);
-    t.nq_max = std::max(t.nq_max, P[si].hm.nq);
-    t.nq_min = std::min(t.nq_min, P[si].hm.nq);
-  }
-  return t;
-}
-// The first layer runs on the scene's cached keys / values / scene-to-click queries (a3d_decoder_sample::kv0_dev) when EVERY
-// sample of the group has a usable cache: K = (feats + pos) Wk^T + bk, V = feats Wv^T + bv and Q = (feats + pos) Wq^T + bq
-// (agile3d.py:305-312) depend on the scene only, the interactive loop runs ~100 passes on it
-static bool all_cached(const Prepared* P, int ns) {
-  for (int si = 0; si < ns; ++si)
-    if (!P[si].kv0 || P[si].kv0_state == 0) return false;
-  return true;
+  for (int si = 0; si < ns; ++si) n_total += P[si].n;
+  return n_total;
 }
 // kv0_state 1: this pass fills the sample's cache [3][n][128] from the first layer's weights
 static int fill_kv0(const a3d_decoder_layer& LW, const Prepared& p, hipStream_t st) {
@@ -2999,50 +3207,36 @@ static int launch_query_side(const a3d_decoder_weights* w, int l, QuerySample* q
   return A3D_OK;
 }
 
-// All samples of one call share QT (= padded query count / 16).  Per decoder layer: ONE launch of each fused wide
-// kernel for the whole batch (DecSampleDev table), the small query-side kernels once per sample in between.
+// the build of k_s2c_out a plan names.  Builds no plan names, whatever the switches and the number of learned background
+// queries, are not instantiated (the sweeps of tests/test_decoder_plan_classes.py): keys that stay in LDS imply that twelve
+// waves fit, so there is no <QT, 8> without KG; with the keys out of LDS twelve waves fit up to 25 objects, and one tile has at
+// most 16, so there is no <1, 8, KG>.  (One tile does move its keys out: 16 queries from 15 objects on, which takes a model
+// with fewer than two learned background queries.)
 template <int QT>
-static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStream_t st) {
-  constexpr int QP = QT * 16;
-  const int nblk = P[0].L.qp / QP;          // query blocks (1 unless nq > 64)
-  const int n_counts = A3D_MAX_DEC_LAYERS * (A3D_MAX_QUERIES + 1);
-  const GroupTotals tot = group_totals(P, ns);
-  const int64_t n_total = tot.n_total;
-  const int Kmax = tot.Kmax, nq_max = tot.nq_max, nq_min = tot.nq_min;
-  // every sample of the launch has 17 .. 20 queries: the second query tile is at most four queries wide and runs on the
-  // 4x4x1 builds of k_kv_c2s / k_s2c_out
-  const bool leftover = QT == 2 && nq_min >= 17 && nq_max <= 20;
-  const size_t s2c_lds = (size_t)2 * QP * 132 * 4;             // keys + values of the queries (k_s2c_attn_wide)
-  const size_t qs2c_lds = ((size_t)QP * 132 + (size_t)D * (QP + 4) + D) * 4;   // k_q_s2c: keys, transposed values, bias
-  const size_t fused_lds = (size_t)64 * 1024 + ((size_t)3 * D + QP * 132 + 8 * 16 * (QP + 1) + 8 * 16 * (Kmax + 1)) * 4 +
-                           (size_t)(2 * Kmax + 3) * 4;
-  for (int si = 0; si < ns; ++si) {
-    const size_t lnm_lds = ((size_t)QP * 132 + 4 * 16 * (P[si].L.qp + 1) + 4 * 16 * (P[si].hm.K + 1)) * 4 + (size_t)(P[si].hm.K + 1) * 4;
-    if (lnm_lds > 160 * 1024) {
-      set_error("a3d_decoder_forward: %d queries x %d objects need %zu bytes of LDS in the mask head", P[si].hm.nq,
-                P[si].hm.K, lnm_lds);
-      return A3D_ERR_UNSUPPORTED;
-    }
+static auto s2c_out_kernel(const DecPhase& ph) -> decltype(&k_s2c_out<QT, 12>) {
+  if constexpr (QT <= 2) {
+    if (ph.waves == 12 && !ph.lo && !ph.kg) return ph.qc ? big_lds<k_s2c_out<QT, 12, false, true>>() : big_lds<k_s2c_out<QT, 12>>();
+    if (ph.waves == 12 && !ph.lo && ph.kg) return ph.qc ? big_lds<k_s2c_out<QT, 12, true, true>>() : big_lds<k_s2c_out<QT, 12, true>>();
   }
-  // which of the wide phases run as one fused launch for the batch
-  const bool fuse_c2s = fused_c2s() && nblk == 1;   // up to 64 queries (k_kv_c2s<1..4>)
-  const bool fuse_s2c = fused_c2s() && nblk == 1;
-  const bool fuse_out = fuse_s2c && fused_lds <= 160 * 1024;
-  // scene-to-click + output projection + LayerNorm + mask head as ONE kernel when both packed weight matrices and the
-  // queries' compact keys / values fit the LDS (about 24 queries at 5 objects); A3D_FUSED_S2C=0 keeps the two kernels
-  const int nqr_max = (nq_max + 3) & ~3;
-  const size_t s2c_rest = ((size_t)D * (nqr_max + 4) + 4 * D + (size_t)8 * 16 * (Kmax + 1) + 2 * Kmax + 3 + QT * 16 + 1) * 4;
-  const size_t s2c_keys = (size_t)nqr_max * 136 * 4;
-  const size_t staging12 = (size_t)4 * 16 * (Kmax + 1) * 4;   // twelve waves' logits staging
-  // the keys move out of LDS (k_s2c_out<.., KG>) when everything else still fits: 25..32 queries at 5 objects
-  const bool s2c_kg = (size_t)128 * 1024 + s2c_keys + s2c_rest + staging12 > 160 * 1024;
-  const size_t s2c_out_lds = (size_t)128 * 1024 + (s2c_kg ? 0 : s2c_keys) + s2c_rest;
-  const size_t s2c_out_lds12 = s2c_out_lds + staging12;
-  static const bool fused_s2c_env = env_int("A3D_FUSED_S2C", 1) != 0;
-  const bool fuse_all = fuse_out && fused_s2c_env && QT <= 2 && s2c_out_lds <= 160 * 1024;
+  if constexpr (QT == 2) {
+    if (ph.waves == 12 && ph.lo && !ph.kg) return ph.qc ? big_lds<k_s2c_out<2, 12, false, true, true>>() : big_lds<k_s2c_out<2, 12, false, false, true>>();
+    if (ph.waves == 8 && !ph.lo && ph.kg && !ph.qc) return big_lds<k_s2c_out<2, 8, true>>();
+  }
+  return nullptr;
+}
+
+// All samples of one call share QT (= padded query count / 16).  Per decoder layer: ONE launch of each fused wide
+// kernel for the whole batch (DecSampleDev table), the small query-side kernels once per sample in between.  Which kernels,
+// and their LDS: plan_decoder's answer.
+template <int QT>
+static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStream_t st, const DecPlan& plan) {
+  const int nblk = plan.nblk;
+  const int n_counts = A3D_MAX_DEC_LAYERS * (A3D_MAX_QUERIES + 1);
+  const int64_t n_total = group_points(P, ns);
+  const int Kmax = plan.Kmax, nq_max = plan.nq_max;
   DecTables T;
   {
-    const int rc_t = upload_tables(P, ns, false, fuse_c2s, st, T);
+    const int rc_t = upload_tables(P, ns, plan.wg_per_group, plan.part_per_wg, st, T);
     if (rc_t) return rc_t;
   }
   const int grid = T.grid;
@@ -3056,33 +3250,32 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
   }
   for (int l = 0; l < w->n_layers; ++l) {
     const a3d_decoder_layer& LW = w->layers[l];
+    const DecPhase &c2s = plan.c2s[l ? 1 : 0], &s2c = plan.s2c[l ? 1 : 0], &out = plan.out[l ? 1 : 0];
     int rc;
     // ---- click-to-scene; the first layer on the scene's cached keys / values when every sample has them
-    const bool cached0 = l == 0 && all_cached(P, ns);
-    const bool qc0 = cached0;   // the scene-to-click half of this layer reads its queries from the cache too
+    const bool cached0 = l == 0 && plan.cached0;
     if (cached0) {
       for (int si = 0; si < ns; ++si) {
         Prepared& p = P[si];
         rc = fill_kv0(LW, p, st);
         if (rc) return rc;
-        if (nblk == 1) continue;              // one query block: all samples in ONE launch below
+        if (c2s.kernel != kDkC2sAttn) continue;              // one query block: all samples in ONE launch below
         ProfScope ps(st, A3D_PROF_C2S, 0, 0, 0, 0, p.n);
         k_c2s_attn<QT><<<dim3(p.L.nchunk, nblk), 512, 0, st>>>(p.kv0, p.kv0 + (size_t)p.n * D, p.n, p.B.qproj, p.meta->obj, nullptr, nullptr,
                                                               p.part, p.L.qp);
         A3D_LAUNCH_CHECK();
       }
-      if (nblk == 1) {
+      if (c2s.kernel == kDkC2sAttnB) {
         int nchunk_max = 0;
         for (int si = 0; si < ns; ++si) nchunk_max = P[si].L.nchunk > nchunk_max ? P[si].L.nchunk : nchunk_max;
         ProfScope ps(st, A3D_PROF_C2S, 0, 0, 0, 0, (int)n_total);
         k_c2s_attn_b<QT><<<dim3(nchunk_max, ns), 512, 0, st>>>(samples_dev);
         A3D_LAUNCH_CHECK();
       }
-    } else if (fuse_c2s) {
+    } else if (c2s.kernel == kDkKvC2s) {
       // K / V projections fused in (K, V never reach HBM), all samples in one launch
       ProfScope ps(st, A3D_PROF_C2S, 0, 0, 0, 0, (int)n_total);
-      const size_t c2s_lds = (size_t)128 * 1024 + (QT == 4 ? (size_t)QP * 128 * 4 : ((size_t)QP * 132 + 2 * D) * 4);
-      (leftover ? big_lds<k_kv_c2s<2, true>>() : big_lds<k_kv_c2s<QT>>())<<<grid, 512, c2s_lds, st>>>(
+      (c2s.lo ? big_lds<k_kv_c2s<2, true>>() : big_lds<k_kv_c2s<QT>>())<<<grid, 512, c2s.lds, st>>>(
           samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D, LW.c2s_in_b + 2 * D);
       A3D_LAUNCH_CHECK();
     } else {
@@ -3102,36 +3295,26 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
       }
     }
     // ---- query side, per sample
-    rc = launch_query_side<QT>(w, l, qs_dev, P[0].L.qp, nblk, ns, nq_max, cached0, st);
+    rc = launch_query_side<QT>(w, l, qs_dev, plan.qp, nblk, ns, nq_max, cached0, st);
     if (rc) return rc;
     // ---- scene-to-click: Q = (src + pos) Wq^T + bq; attention; Y = O Wo^T + bo + src; LN
-    if (fuse_all) {
+    if (s2c.kernel == kDkS2cOut) {
       // the whole half in one pass: O never reaches HBM (k_s2c_out)
       ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, (int)n_total);
       const int last = l + 1 == w->n_layers;   // nothing reads the last layer's rows, label bytes and histogram
-      if constexpr (QT <= 2) {
-        // twelve waves (three per SIMD) when their logits staging fits, else eight
-        const bool fits12 = s2c_out_lds12 <= 160 * 1024;
-        int waves = 12;
-        decltype(&k_s2c_out<QT, 12>) kern;
-        if (leftover && qc0 && !s2c_kg && fits12) kern = big_lds<k_s2c_out<2, 12, false, true, true>>();
-        else if (leftover && !qc0 && !s2c_kg && fits12) kern = big_lds<k_s2c_out<2, 12, false, false, true>>();
-        else if (qc0 && s2c_kg && fits12) kern = big_lds<k_s2c_out<QT, 12, true, true>>();
-        else if (qc0 && !s2c_kg && fits12) kern = big_lds<k_s2c_out<QT, 12, false, true>>();
-        else if (s2c_kg && fits12) kern = big_lds<k_s2c_out<QT, 12, true>>();
-        else if (s2c_kg) kern = big_lds<k_s2c_out<QT, 8, true>>(), waves = 8;
-        else if (fits12) kern = big_lds<k_s2c_out<QT, 12>>();
-        else kern = big_lds<k_s2c_out<QT, 8>>(), waves = 8;
-        kern<<<grid, 64 * waves, waves == 12 ? s2c_out_lds12 : s2c_out_lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b,
-                                                                                 LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w,
-                                                                                 LW.s2c_norm_b, nqr_max, Kmax, last);
+      const auto kern = s2c_out_kernel<QT>(s2c);
+      if (!kern) {
+        set_error("a3d_decoder_forward: no k_s2c_out build for %d queries x %d objects", nq_max, Kmax);
+        return A3D_ERR_UNSUPPORTED;
       }
+      kern<<<grid, 64 * s2c.waves, s2c.lds, st>>>(samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed, LW.s2c_out_b,
+                                                  LW.s2c_norm_w, LW.s2c_norm_b, plan.nqr_max, Kmax, last);
       A3D_LAUNCH_CHECK();
       continue;
     }
-    if (fuse_s2c) {
+    if (s2c.kernel == kDkQS2c) {
       ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, (int)n_total);
-      (qc0 ? big_lds<k_q_s2c<QT, true>>() : big_lds<k_q_s2c<QT>>())<<<grid, 512, (size_t)64 * 1024 + qs2c_lds, st>>>(
+      (s2c.qc ? big_lds<k_q_s2c<QT, true>>() : big_lds<k_q_s2c<QT>>())<<<grid, 512, s2c.lds, st>>>(
           samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b);
       A3D_LAUNCH_CHECK();
     } else {
@@ -3139,22 +3322,22 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
         Prepared& p = P[si];
         const float* src = layer_src(p, l);
         const float* Qs = p.bufA;
-        if (qc0) {
+        if (s2c.qc) {
           Qs = p.kv0 + (size_t)2 * p.n * D;     // the cached queries of the first layer
         } else {
           rc = a3d_linear(src, D, p.posenc, D, p.n, D, D, LW.s2c_wq_packed, nullptr, LW.s2c_in_b, nullptr, 0, 0, p.bufA, D, nullptr, 0, st);
           if (rc) return rc;
         }
         ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, p.n);
-        big_lds<k_s2c_attn_wide<QT>>()<<<(p.n + 127) / 128, 512, s2c_lds, st>>>(Qs, p.n, p.B.ks, p.B.vs, p.hm.nq, nblk, p.bufB);
+        big_lds<k_s2c_attn_wide<QT>>()<<<(p.n + 127) / 128, 512, s2c.lds, st>>>(Qs, p.n, p.B.ks, p.B.vs, p.hm.nq, nblk, p.bufB);
         A3D_LAUNCH_CHECK();
       }
     }
-    if (fuse_out) {
+    if (out.kernel == kDkOutLnMask) {
       // ---- output projection + residual + LayerNorm + mask head in one pass (the pre-norm activation stays on chip)
       ProfScope ps(st, A3D_PROF_LNMASK, 0, 0, 0, 0, (int)n_total);
-      big_lds<k_out_ln_mask<QT>>()<<<grid, 512, fused_lds, st>>>(samples_dev, ns, l, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w,
-                                                                 LW.s2c_norm_b);
+      big_lds<k_out_ln_mask<QT>>()<<<grid, 512, out.lds, st>>>(samples_dev, ns, l, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w,
+                                                               LW.s2c_norm_b);
       A3D_LAUNCH_CHECK();
     } else {
       for (int si = 0; si < ns; ++si) {
@@ -3162,13 +3345,12 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
         const float* src = layer_src(p, l);
         float* Y = layer_dst(p, l);
         const int K = p.hm.K;
-        const size_t lnm_lds = ((size_t)QP * 132 + 4 * 16 * (p.L.qp + 1) + 4 * 16 * (K + 1)) * 4 + (size_t)(K + 1) * 4;
         rc = a3d_linear(p.bufB, D, nullptr, 0, p.n, D, D, LW.s2c_wo_packed, nullptr, LW.s2c_out_b, src, D, 0, Y, D, nullptr, 0, st);
         if (rc) return rc;
         ProfScope ps(st, A3D_PROF_LNMASK, 0, 0, 0, 0, p.n);
-        big_lds<k_ln_mask<QT>>()<<<(p.n + 63) / 64, 256, lnm_lds, st>>>(Y, p.n, LW.s2c_norm_w, LW.s2c_norm_b, p.B.E, p.hm.nq,
-                                                                     p.meta->qrange, p.hm.n_fg, K, p.logits + (size_t)l * p.n * (K + 1),
-                                                                     p.labels, p.counts + (size_t)l * (A3D_MAX_QUERIES + 1), nblk);
+        big_lds<k_ln_mask<QT>>()<<<(p.n + 63) / 64, 256, dec_ln_mask_lds(QT * 16, p.L.qp, K), st>>>(
+            Y, p.n, LW.s2c_norm_w, LW.s2c_norm_b, p.B.E, p.hm.nq, p.meta->qrange, p.hm.n_fg, K, p.logits + (size_t)l * p.n * (K + 1),
+            p.labels, p.counts + (size_t)l * (A3D_MAX_QUERIES + 1), nblk);
         A3D_LAUNCH_CHECK();
       }
     }
@@ -3179,21 +3361,13 @@ static int run_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStr
 // ---- the fused wide tier (decoder_wide.h): 65 .. 224 queries, QT = padded queries / 16 of the three point-side kernels; the
 // query side runs its 64-query blocks on buffers of L.qp rows as before
 template <int QT>
-static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, hipStream_t st) {
-  int qp = 0;   // rows of the longest query-side buffers of the group
-  for (int si = 0; si < ns; ++si) qp = std::max(qp, P[si].L.qp);
+static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, hipStream_t st, const DecPlan& plan) {
+  const int qp = plan.qp;   // rows of the longest query-side buffers of the group
   const int n_counts = A3D_MAX_DEC_LAYERS * (A3D_MAX_QUERIES + 1);
-  const GroupTotals tot = group_totals(P, ns);
-  const int64_t n_total = tot.n_total;
-  const int Kmax = tot.Kmax, nq_max = tot.nq_max;
-  const size_t stage_lds = (size_t)2 * 2 * kWTile * 4;                       // two slots of (rows, position encodings)
-  const size_t out_lds = ((size_t)6 * kWTile + 2 * 256 + 2 * 32 * (Kmax + 1)) * 4 + (size_t)(Kmax + 1) * 4;   // k_out_w: O slots, rows, statistics, maxima, histogram
-  if (out_lds > 160 * 1024) {
-    set_error("a3d_decoder_forward: %d objects need %zu bytes of LDS in the output half", Kmax, out_lds);
-    return A3D_ERR_UNSUPPORTED;
-  }
+  const int64_t n_total = group_points(P, ns);
+  const int Kmax = plan.Kmax, nq_max = plan.nq_max;
   DecTables T;
-  int rc = upload_tables(P, ns, true, true, st, T);
+  int rc = upload_tables(P, ns, plan.wg_per_group, plan.part_per_wg, st, T);
   if (rc) return rc;
   {
     ProfScope ps(st, A3D_PROF_QUERY, 0, 0, 0, 0, nq_max);
@@ -3202,29 +3376,25 @@ static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, h
                                                       w->layers[0].c2s_in_w, w->layers[0].c2s_in_b, n_counts);
     A3D_LAUNCH_CHECK();
   }
-  // the query side in blocks of 32 rows: as many as the longest query list of the call needs
-  const int nblk = (nq_max + 31) / 32;
+  const int nblk = plan.nblk;   // the query side in blocks of 32 rows
   for (int l = 0; l < w->n_layers; ++l) {
     const a3d_decoder_layer& LW = w->layers[l];
+    const DecPhase &c2s = plan.c2s[l ? 1 : 0], &s2c = plan.s2c[l ? 1 : 0], &out = plan.out[l ? 1 : 0];
     // ---- click-to-scene; the first layer on the scene's cached keys / values when every sample has them
-    const bool cached0 = l == 0 && all_cached(P, ns);
-    const bool qc0 = cached0;
+    const bool cached0 = l == 0 && plan.cached0;
     if (cached0) {
-      int nchunk_max = 0, nqt_max = 0;
+      int nchunk_max = 0;
       for (int si = 0; si < ns; ++si) {
         Prepared& p = P[si];
         rc = fill_kv0(LW, p, st);
         if (rc) return rc;
         nchunk_max = p.L.nchunk > nchunk_max ? p.L.nchunk : nchunk_max;
-        const int t = (p.hm.nq + 15) / 16;
-        nqt_max = t > nqt_max ? t : nqt_max;
       }
       {
         ProfScope ps(st, A3D_PROF_C2S, 0, 0, 0, 0, (int)n_total);
-        // the unfused flash kernel over the cached keys / values, ALL samples in one launch: the widest sample's kernel, every
-        // sample by its OWN tile count (c2s_attn_body skips the tiles past it)
+        // the unfused flash kernel over the cached keys / values, ALL samples in one launch
         const dim3 cg(nchunk_max, ns);
-        switch (wide_qt_of_tiles(nqt_max)) {
+        switch (c2s.qt) {
           case 1: k_c2s_attn_b<1><<<cg, 512, 0, st>>>(T.samples_dev); break;
           case 2: k_c2s_attn_b<2><<<cg, 512, 0, st>>>(T.samples_dev); break;
           case 3: k_c2s_attn_b<3><<<cg, 512, 0, st>>>(T.samples_dev); break;
@@ -3241,8 +3411,8 @@ static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, h
       }
     } else {
       ProfScope ps(st, A3D_PROF_C2S, 0, 0, 0, 0, (int)n_total);
-      k_c2s_w<QT><<<T.grid, 512, stage_lds, st>>>(T.samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D,
-                                                  LW.c2s_in_b + 2 * D);
+      k_c2s_w<QT><<<T.grid, 512, c2s.lds, st>>>(T.samples_dev, ns, l, LW.c2s_wk_packed, LW.c2s_wv_packed, LW.c2s_in_b + D,
+                                                LW.c2s_in_b + 2 * D);
       A3D_LAUNCH_CHECK();
     }
     rc = launch_query_side<2>(w, l, T.qs_dev, qp, nblk, ns, nq_max, cached0, st);
@@ -3250,10 +3420,9 @@ static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, h
     // ---- scene-to-click: up to five query tiles as ONE kernel (k_s2o_w), else attention, then output projection +
     // residual + LayerNorm + mask head
     if constexpr (QT == 5) {
-      if (fused_s2o()) {
+      if (s2c.kernel == kDkS2oW) {
         ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, (int)n_total);
-        const size_t s2o_lds = ((size_t)(4 + 5) * kWTile + 2 * 256 + 2 * 32 * (Kmax + 1) + ((Kmax + 1 + 3) & ~3)) * 4;
-        (qc0 ? big_lds<k_s2o_w<5, true>>() : big_lds<k_s2o_w<5, false>>())<<<T.grid, 512, s2o_lds + (qc0 ? 0 : (size_t)4 * kWTile * 4), st>>>(
+        (s2c.qc ? big_lds<k_s2o_w<5, true>>() : big_lds<k_s2o_w<5, false>>())<<<T.grid, 512, s2c.lds, st>>>(
             T.samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, Kmax);
         A3D_LAUNCH_CHECK();
         continue;
@@ -3261,14 +3430,13 @@ static int run_decoder_wide(const a3d_decoder_weights* w, Prepared* P, int ns, h
     }
     {
       ProfScope ps(st, A3D_PROF_S2C, 0, 0, 0, 0, (int)n_total);
-      if (qc0) k_s2c_w<QT, true><<<T.grid, 512, 0, st>>>(T.samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b);
-      else k_s2c_w<QT, false><<<T.grid, 512, stage_lds, st>>>(T.samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b);
+      if (s2c.qc) k_s2c_w<QT, true><<<T.grid, 512, s2c.lds, st>>>(T.samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b);
+      else k_s2c_w<QT, false><<<T.grid, 512, s2c.lds, st>>>(T.samples_dev, ns, l, LW.s2c_wq_packed, LW.s2c_in_b);
       A3D_LAUNCH_CHECK();
     }
     {
       ProfScope ps(st, A3D_PROF_LNMASK, 0, 0, 0, 0, (int)n_total);
-      // (its per-object maxima grow with the objects: past 64 KB from ~43 objects on)
-      big_lds<k_out_w<QT>>()<<<T.grid, 512, out_lds, st>>>(
+      big_lds<k_out_w<QT>>()<<<T.grid, 512, out.lds, st>>>(
           T.samples_dev, ns, l, LW.s2c_wo_packed, LW.s2c_out_b, LW.s2c_norm_w, LW.s2c_norm_b, Kmax);
       A3D_LAUNCH_CHECK();
     }
@@ -3289,7 +3457,7 @@ static int prepare_sample(const a3d_decoder_weights* w, const a3d_decoder_sample
     return A3D_ERR_INVALID;
   }
   const int nq = n_clicks + w->n_bg_queries;
-  if (nq > A3D_MAX_QUERIES || n_objects > 254 || n_clicks > 200) {
+  if (dec_sample_unsupported(nq, n_objects, n_clicks)) {
     set_error("a3d_decoder_forward: %d queries > %d", nq, A3D_MAX_QUERIES);
     return A3D_ERR_UNSUPPORTED;
   }
@@ -3343,8 +3511,7 @@ static int prepare_sample(const a3d_decoder_weights* w, const a3d_decoder_sample
     hm.row[i] = -1;
   }
   dec_layout(n, nq, P.L);
-  P.qtw = fused_wide() ? wide_qt(nq) : 0;
-  if (fused_wide() && nq >= wide_from() && nq <= 64) P.qtw = 5;   // (the smallest build; the kernels take the sample's own tile count)
+  P.qtw = dec_sample_qtw(nq, dec_switches());
   if (!sp.workspace_dev || sp.workspace_bytes < P.L.total || ((uintptr_t)sp.workspace_dev & 255)) {
     set_error("a3d_decoder_forward: workspace too small or misaligned (%zu < %zu)", sp.workspace_bytes, P.L.total);
     return A3D_ERR_WORKSPACE;
@@ -3366,24 +3533,34 @@ static int prepare_sample(const a3d_decoder_weights* w, const a3d_decoder_sample
 }
 
 static int dispatch_decoder(const a3d_decoder_weights* w, Prepared* P, int ns, hipStream_t st) {
-  int qtw = 0;   // the wide build that holds the longest query list of the group (0: the group runs the <= 64 / unfused kernels)
-  if (P[0].qtw > 0)
-    for (int i = 0; i < ns; ++i) qtw = std::max(qtw, std::max(P[i].qtw, wide_qt(P[i].hm.nq)));
-  switch (qtw) {
-    case 5: return run_decoder_wide<5>(w, P, ns, st);
-    case 6: return run_decoder_wide<6>(w, P, ns, st);
-    case 7: return run_decoder_wide<7>(w, P, ns, st);
-    case 8: return run_decoder_wide<8>(w, P, ns, st);
-    case 10: return run_decoder_wide<10>(w, P, ns, st);
-    case 12: return run_decoder_wide<12>(w, P, ns, st);
-    case 14: return run_decoder_wide<14>(w, P, ns, st);
-    default: break;
+  DecSampleShape shapes[kMaxBatchSamples];   // (a launch group has at most kMaxBatchSamples samples)
+  if (ns > kMaxBatchSamples) {
+    set_error("a3d_decoder_forward_batch: a launch group of %d samples", ns);
+    return A3D_ERR_INVALID;
   }
-  switch (P[0].L.qp) {
-    case 16: return run_decoder<1>(w, P, ns, st);
-    case 32: return run_decoder<2>(w, P, ns, st);
-    case 48: return run_decoder<3>(w, P, ns, st);
-    default: return run_decoder<4>(w, P, ns, st);
+  for (int i = 0; i < ns; ++i) shapes[i] = {P[i].hm.nq, P[i].hm.K, P[i].qtw, P[i].kv0 ? P[i].kv0_state : 0};
+  const DecPlan plan = plan_decoder(shapes, ns, dec_switches());
+  if (plan.rc) {
+    if (plan.wide) set_error("a3d_decoder_forward: %d objects need %zu bytes of LDS in the output half", plan.err_K, plan.err_lds);
+    else set_error("a3d_decoder_forward: %d queries x %d objects need %zu bytes of LDS in the mask head", plan.err_nq, plan.err_K, plan.err_lds);
+    return plan.rc;
+  }
+  if (plan.wide) {
+    switch (plan.qt) {
+      case 5: return run_decoder_wide<5>(w, P, ns, st, plan);
+      case 6: return run_decoder_wide<6>(w, P, ns, st, plan);
+      case 7: return run_decoder_wide<7>(w, P, ns, st, plan);
+      case 8: return run_decoder_wide<8>(w, P, ns, st, plan);
+      case 10: return run_decoder_wide<10>(w, P, ns, st, plan);
+      case 12: return run_decoder_wide<12>(w, P, ns, st, plan);
+      default: return run_decoder_wide<14>(w, P, ns, st, plan);
+    }
+  }
+  switch (plan.qt) {
+    case 1: return run_decoder<1>(w, P, ns, st, plan);
+    case 2: return run_decoder<2>(w, P, ns, st, plan);
+    case 3: return run_decoder<3>(w, P, ns, st, plan);
+    default: return run_decoder<4>(w, P, ns, st, plan);
   }
 }
 
@@ -3414,9 +3591,7 @@ extern "C" int a3d_decoder_forward_batch(const a3d_decoder_weights* w, const a3d
   // padded query count share the <= 64-query kernels.  Several groups are independent chains of launches on their own
   // workspaces: group g goes on side stream g mod 4 (forked from / joined to the caller's stream with events), group 0 stays.
   std::stable_partition(P.begin(), P.end(), [](const Prepared& p) { return p.qtw > 0; });   // wide samples first: the leading group(s)
-  auto same_group = [](const Prepared& a, const Prepared& b) {
-    return (a.qtw > 0 && b.qtw > 0) || (a.L.qp == b.L.qp && a.qtw == b.qtw);
-  };
+  auto same_group = [](const Prepared& a, const Prepared& b) { return dec_same_group(a.qtw, a.L.qp, b.qtw, b.L.qp); };
   std::vector<int> group_end;   // one past the last sample of every group
   for (int i = 0; i < n_samples;) {
     int e = i + 1;

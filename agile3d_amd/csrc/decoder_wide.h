@@ -23,15 +23,7 @@ constexpr int kWLD = 136;                       // row stride (floats) of the st
 constexpr int kWTile = 16 * kWLD;               // floats per staged tile
 constexpr int kWideGridMax = 256;               // persistent workgroups (one per CU: 8 waves x up to 256 VGPRs)
 
-// smallest wide-tier tile count that holds nq queries (0: not served -- more than 224 queries run the unfused kernels)
-__host__ __device__ constexpr int wide_qt(int nq) {
-  return nq <= 64 ? 0 : nq <= 80 ? 5 : nq <= 96 ? 6 : nq <= 112 ? 7 : nq <= 128 ? 8 : nq <= 160 ? 10 : nq <= 192 ? 12 : nq <= 224 ? 14 : 0;
-}
-
-// tile count of the k_c2s_attn build that holds `tiles` 16-query tiles of a sample whose buffers have round_qp(nq) rows
-__host__ __device__ constexpr int wide_qt_of_tiles(int tiles) {
-  return tiles <= 8 ? tiles : tiles <= 10 ? 10 : tiles <= 12 ? 12 : 14;
-}
+// (which tile count serves a query count: wide_qt, in the planning block of decoder.hip)
 
 // the 512 threads of a workgroup move one group's rows of X and of the position encodings (16 x 128 floats each):
 // thread -> (row lr, float4 column lc)

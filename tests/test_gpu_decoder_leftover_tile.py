@@ -1,5 +1,8 @@
 """The decoder at 17 .. 32 queries: a scene with 17 .. 20 queries runs its second query tile (queries 16 .. 19) on the
-4x4x1 builds of k_kv_c2s / k_s2c_out, and the last layer stores only its logits.  forward_mask's pred_masks and every
+4x4x1 build of k_kv_c2s and, while the queries' keys stay in LDS (up to 8 objects at 19 and 20 queries), of k_s2c_out; the
+last layer stores only its logits.  By the planner (test_decoder_plan_classes.py) the 17- and 18-query cases and the batch
+below run both leftover builds; the 20-query case with its ten objects runs k_kv_c2s<2, LO> next to k_s2c_out<2, 12, KG>,
+the two-tile build with the keys in global memory.  forward_mask's pred_masks and every
 aux output against (a) the unfused live path (A3D_FUSED_C2S=0 A3D_FUSED_S2C=0, read once per process -> a second
 interpreter) at the tolerance of test_one_pass_scene_to_click_half_matches_the_two_kernel_path, and (b) the CPU oracle at
 the 1e-3 bar of test_gpu_model.py.  16 and 33 queries are the neighbours on either side (one tile; the wide tier)."""
