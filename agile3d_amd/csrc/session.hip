@@ -36,6 +36,7 @@
 // an edge still classify every ray consistently.  On a cloud a vertex shows iff it lies on the kept side of every plane.  The
 // section is a template parameter of the kernels that test primitives: NoSection is the code the entry points without a
 // section have always run, and the binning of the rendered view does not know about sections at all.
+#include "session_device.h"                   // Carver, capped_grid
 #include "session_rules.h"                    // ses_pixel_ray, ses_keeps(a3d_section): shared with session_region.hip
 
 namespace a3d {
@@ -434,16 +435,6 @@ __global__ __launch_bounds__(kSesBlock) void k_session_paint(const a3d_session_p
   }
 }
 
-// Hands out consecutive 256-byte aligned pieces of a workspace; with base == nullptr it only measures (off = the bytes).
-struct Carver {
-  void* base;
-  size_t off = 0;
-  void* take(size_t b) {
-    void* p = base ? (char*)base + off : nullptr;
-    off += align256(b);
-    return p;
-  }
-};
 struct SesWs {
   unsigned long long* near_part;
   unsigned long long* pick_a;
@@ -462,10 +453,6 @@ static SesWs carve_session(void* base) {
   w.mesh_flag = (unsigned*)c.take((size_t)kSesMaxBlocks * 4);
   w.bytes = c.off;
   return w;
-}
-static int ses_blocks(long long n) {
-  const long long want = (n + kSesBlock - 1) / kSesBlock;
-  return (int)(want < 1 ? 1 : want > kSesMaxBlocks ? kSesMaxBlocks : want);
 }
 // n rows behind a pointer: a count that fits the kernels' 32-bit row ids, and rows to read unless there are none
 static bool ses_rows_ok(long long n, const void* rows) { return n >= 0 && n < (1ll << 31) && (!n || rows); }
@@ -1221,12 +1208,12 @@ extern "C" int a3d_nearest_rows(const a3d_nearest_source* sources, int n_sources
       return A3D_ERR_INVALID;
     }
     t.xyz[s] = sp.xyz_dev, t.n[s] = sp.n, t.out[s] = sp.rows_out_dev;
-    t.n_blocks[s] = ses_blocks(sp.n);
+    t.n_blocks[s] = (int)capped_grid(sp.n, kSesBlock, kSesMaxBlocks);
     n_max = sp.n > n_max ? sp.n : n_max;
   }
   memcpy(t.q, queries, (size_t)m * 3 * sizeof(float));
   const SesWs w = carve_session(workspace_dev);
-  const int nb = ses_blocks(n_max);
+  const int nb = (int)capped_grid(n_max, kSesBlock, kSesMaxBlocks);
   k_nearest_rows<<<dim3(nb, n_sources, (m + kSesQT - 1) / kSesQT), kSesBlock, 0, st>>>(t, w.near_part);
   A3D_LAUNCH_CHECK();
   k_nearest_finish<<<1, kSesBlock, 0, st>>>(t, w.near_part);
@@ -1252,7 +1239,7 @@ static int pick_ray_run(const char* what, const float* xyz_dev, int64_t n, const
   t.r2 = radius * radius;
   t.out = result_dev;
   const SesWs w = carve_session(workspace_dev);
-  const int nb = ses_blocks(n);
+  const int nb = (int)capped_grid(n, kSesBlock, kSesMaxBlocks);
   sec = section_active(sec);
   if (sec)
     k_pick_ray<a3d_section><<<nb, kSesBlock, 0, st>>>(t, w.pick_a, w.pick_row, *sec);
@@ -1293,7 +1280,7 @@ static int pick_mesh_run(const char* what, const float* xyz_dev, int64_t n, cons
   ses_shear(direction, t.r);
   t.out = result_dev;
   const SesWs w = carve_session(workspace_dev);
-  const int nb = ses_blocks(m);
+  const int nb = (int)capped_grid(m, kSesBlock, kSesMaxBlocks);
   sec = section_active(sec);
   if (sec)                                     // the ray's interval, here on the host: what a pixel of the view derives for the same ray
     k_pick_mesh<RayCut><<<nb, kSesBlock, 0, st>>>(t, w.mesh_key, w.mesh_flag, ses_ray_cut(*sec, t.r.o, direction));
@@ -1344,8 +1331,7 @@ extern "C" int a3d_session_paint(const a3d_session_paint_args* args, void* strea
   }
   A3D_HIP_CHECK(hipMemsetAsync(a.err_dev, 0, sizeof(int32_t), st));
   if (a.n_full == 0) return A3D_OK;
-  const long long want = (a.n_full + kSesBlock - 1) / kSesBlock;
-  k_session_paint<<<(unsigned)(want < 2048 ? want : 2048), kSesBlock, 0, st>>>(a);
+  k_session_paint<<<capped_grid(a.n_full, kSesBlock, 2048), kSesBlock, 0, st>>>(a);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

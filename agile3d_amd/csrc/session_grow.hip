@@ -60,7 +60,7 @@
 // LDS, ONE 64-bit atomic per workgroup and counter (none for a zero).  Few, fat workgroups (1024 threads, at most one per
 // CU) for the reason recorded at a3d_select_vertices: the atomics of a call land on the same few addresses and are served one
 // after the other.  Sums of integers and maxima do not depend on the order of arrival.
-#include "common.h"
+#include "session_device.h"
 
 namespace a3d {
 
@@ -80,16 +80,15 @@ struct GrowWs {
 };
 static GrowWs carve_grow(void* base, long long n) {
   GrowWs w;
-  char* p = (char*)base;
+  Carver c{base};
   const size_t m = (size_t)(n > 0 ? n : 1);
-  size_t off = 0;
-  w.value = (unsigned long long*)(p + off), off += align256(m * 8);
-  const size_t zero_from = off;
-  w.seed = (uint8_t*)(p + off), off += align256(m);
-  w.flag = (int32_t*)(p + off), off += align256((A3D_GROW_MAX_STEPS + 1) * sizeof(int32_t));
-  w.zero_bytes = off - zero_from;
-  w.stamp = (int32_t*)(p + off), off += align256(m * 4);
-  w.bytes = off;
+  w.value = (unsigned long long*)c.take(m * 8);
+  const size_t zero_from = c.off;
+  w.seed = (uint8_t*)c.take(m);
+  w.flag = (int32_t*)c.take((A3D_GROW_MAX_STEPS + 1) * sizeof(int32_t));
+  w.zero_bytes = c.off - zero_from;
+  w.stamp = (int32_t*)c.take(m * 4);
+  w.bytes = c.off;
   return w;
 }
 
@@ -192,33 +191,6 @@ __global__ __launch_bounds__(kGrowBlock) void k_grow_sweep(const int32_t* __rest
   if (__any(lowered) && (threadIdx.x & 63) == 0) *mine = 1;            // (every writer stores 1)
 }
 
-// The sum of v over the workgroup, in thread 0 (the other threads' return value is not meant to be used).
-__device__ __forceinline__ long long grow_block_sum(int v, int* wave_part) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();                             // (wave_part may still be read from the reduction before)
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long s = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kGrowFat / 64; ++w) s += wave_part[w];
-  return s;
-}
-__device__ __forceinline__ int grow_block_max(int v, int* wave_part) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int m = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kGrowFat / 64; ++w) m = max(m, wave_part[w]);
-  return m;
-}
-__device__ __forceinline__ void grow_add(int64_t* dst, long long s) {
-  if (s) atomicAdd((unsigned long long*)dst, (unsigned long long)s);
-}
-
 // The words decoded, the lift, the summary: one streaming pass, behind a launch boundary (plain loads).
 __global__ __launch_bounds__(kGrowFat) void k_grow_lift(const a3d_grow_voxels_args a, const unsigned long long* __restrict__ value) {
   __shared__ int wave_part[kGrowFat / 64];
@@ -244,25 +216,16 @@ __global__ __launch_bounds__(kGrowFat) void k_grow_lift(const a3d_grow_voxels_ar
     if (a.dist_full_dev) a.dist_full_dev[v] = d;
     n_selected += d >= 0;
   }
-  const long long s_seeds = grow_block_sum(n_seeds, wave_part), s_reached = grow_block_sum(n_reached, wave_part);
-  const long long s_selected = grow_block_sum(n_selected, wave_part), s_bad = grow_block_sum(bad, wave_part);
-  const int m_far = grow_block_max(far, wave_part);
+  const long long s_seeds = block_sum<kGrowFat>(n_seeds, wave_part), s_reached = block_sum<kGrowFat>(n_reached, wave_part);
+  const long long s_selected = block_sum<kGrowFat>(n_selected, wave_part), s_bad = block_sum<kGrowFat>(bad, wave_part);
+  const int m_far = block_max<kGrowFat>(far, wave_part);
   if (threadIdx.x == 0) {
-    grow_add(&a.summary_dev->seeds, s_seeds);
-    grow_add(&a.summary_dev->reached, s_reached);
-    grow_add(&a.summary_dev->selected, s_selected);
+    add_i64(&a.summary_dev->seeds, s_seeds);
+    add_i64(&a.summary_dev->reached, s_reached);
+    add_i64(&a.summary_dev->selected, s_selected);
     if (m_far > 0) atomicMax(&a.summary_dev->max_dist, m_far);
     if (s_bad) atomicOr(&a.summary_dev->err, A3D_GROW_BAD_INDEX);
   }
-}
-
-static unsigned grow_grid(long long n) {
-  const long long want = (n + kGrowBlock - 1) / kGrowBlock;
-  return (unsigned)(want < 1 ? 1 : want < kGrowMaxBlocks ? want : kGrowMaxBlocks);
-}
-static unsigned grow_fat_grid(long long n) {
-  const long long want = (n + kGrowFat - 1) / kGrowFat;
-  return (unsigned)(want < 1 ? 1 : want < kGrowFatBlocks ? want : kGrowFatBlocks);
 }
 
 }  // namespace a3d
@@ -282,7 +245,7 @@ extern "C" int a3d_grow_voxels(const a3d_grow_voxels_args* args, void* stream) {
   }
   const a3d_grow_voxels_args& a = *args;
   const a3d_scene* s = a.scene;
-  const bool bad_scene = !s || !s->lv[0].nbr27 || !s->orig_row || s->n0 != s->lv[0].n || a.n != s->lv[0].n;
+  const bool bad_scene = !scene_walkable(s, a.n);
   const bool bad_conn = a.connectivity != 6 && a.connectivity != 18 && a.connectivity != 26;
   int cheapest = 65536;
   bool bad_cost = false;
@@ -306,10 +269,10 @@ extern "C" int a3d_grow_voxels(const a3d_grow_voxels_args* args, void* stream) {
   if (n > 0) {
     A3D_HIP_CHECK(hipMemsetAsync(w.seed, 0, w.zero_bytes, st));        // the seed bytes and the flags
     if (a.seed_full_dev && a.n_full > 0) {
-      k_grow_scatter<<<grow_fat_grid(a.n_full), kGrowFat, 0, st>>>(a, w.seed);
+      k_grow_scatter<<<capped_grid(a.n_full, kGrowFat, kGrowFatBlocks), kGrowFat, 0, st>>>(a, w.seed);
       A3D_LAUNCH_CHECK();
     }
-    const unsigned grid = grow_grid(n);
+    const unsigned grid = capped_grid(n, kGrowBlock, kGrowMaxBlocks);
     k_grow_init<<<grid, kGrowBlock, 0, st>>>(a.keys_dev, a.seed_qv_dev, s->orig_row, w, n);
     A3D_LAUNCH_CHECK();
     GrowTab t;
@@ -338,7 +301,7 @@ extern "C" int a3d_grow_voxels(const a3d_grow_voxels_args* args, void* stream) {
   }
   if (n > 0 || a.n_full > 0) {
     const long long longest = a.n_full > n ? a.n_full : n;
-    k_grow_lift<<<grow_fat_grid(longest), kGrowFat, 0, st>>>(a, w.value);
+    k_grow_lift<<<capped_grid(longest, kGrowFat, kGrowFatBlocks), kGrowFat, 0, st>>>(a, w.value);
     A3D_LAUNCH_CHECK();
   }
   return A3D_OK;

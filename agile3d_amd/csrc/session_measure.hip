@@ -25,9 +25,7 @@
 // uniform-wave fold.  The records are prepared by k_measure_init (zeros; lo = key(+inf), hi = key(-inf)) and the keys turned
 // back into floats IN PLACE by k_measure_finish: five small launches at most, ordered by the stream.
 // The error word collects in a register per thread, is folded per wave and sent with one atomicOr.
-#include "common.h"
-
-#include <cmath>
+#include "session_device.h"
 
 namespace a3d {
 
@@ -41,8 +39,6 @@ static_assert(kMeasBlock == kMeasIds, "thread k of a workgroup owns record k");
 static_assert(kMeasChunk % kMeasBlock == 0, "a chunk is whole rounds of the workgroup");
 static_assert(sizeof(a3d_object_moments) == 128, "the record of the header");
 
-typedef unsigned long long u64;
-
 // the total order of fp32 bit patterns as an unsigned order: negative values are complemented, the others get the top bit
 __device__ __forceinline__ unsigned key_of(float v) {
   const unsigned b = __float_as_uint(v);
@@ -50,23 +46,6 @@ __device__ __forceinline__ unsigned key_of(float v) {
 }
 __device__ __forceinline__ float value_of(unsigned k) {
   return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
-}
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(y) & 0x7f800000u) != 0x7f800000u &&
-         (__float_as_uint(z) & 0x7f800000u) != 0x7f800000u;
-}
-// X = llrint((x - origin) / quantum) when |X| <= lim (= 2^bits); a NaN or an infinity fails the comparison
-__device__ __forceinline__ bool fixed_point(float x, double origin, double quantum, double lim, long long& X) {
-  const double r = rint(((double)x - origin) / quantum);
-  if (!(fabs(r) <= lim)) return false;
-  X = (long long)r;
-  return true;
-}
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 __device__ __forceinline__ unsigned wave_min(unsigned v) {
 #pragma unroll
@@ -77,11 +56,6 @@ __device__ __forceinline__ unsigned wave_max(unsigned v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
   return v;
-}
-__device__ __forceinline__ void send_error(int32_t* err_dev, int err) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) err |= __shfl_xor(err, o);
-  if ((threadIdx.x & 63) == 0 && err) atomicOr(err_dev, err);
 }
 // the label every counting lane of the wave carries, or -1 when they carry more than one (`live` is not empty)
 __device__ __forceinline__ int wave_label(bool counts, int label, u64 live) {
@@ -365,15 +339,6 @@ __global__ __launch_bounds__(kMeasBlock) void k_extents_vertices(const a3d_exten
   send_error(a.err_dev, err);
 }
 
-static bool power_of_two(double q) {
-  int e;
-  return std::isfinite(q) && q > 0.0 && std::frexp(q, &e) == 0.5;
-}
-static unsigned stride_grid(long long n) {
-  const long long want = (n + kMeasBlock - 1) / kMeasBlock;
-  return (unsigned)(want < 1 ? 1 : want < kMeasMaxBlocks ? want : kMeasMaxBlocks);
-}
-
 }  // namespace a3d
 
 using namespace a3d;
@@ -406,11 +371,11 @@ extern "C" int a3d_measure_objects(const a3d_measure_args* args, void* stream) {
     A3D_LAUNCH_CHECK();
   }
   if (a.n_qv > 0) {
-    k_measure_voxels<<<stride_grid(a.n_qv), kMeasBlock, 0, st>>>(a);
+    k_measure_voxels<<<capped_grid(a.n_qv, kMeasBlock, kMeasMaxBlocks), kMeasBlock, 0, st>>>(a);
     A3D_LAUNCH_CHECK();
   }
   if (a.m > 0) {
-    k_measure_faces<<<stride_grid(a.m), kMeasBlock, 0, st>>>(a);
+    k_measure_faces<<<capped_grid(a.m, kMeasBlock, kMeasMaxBlocks), kMeasBlock, 0, st>>>(a);
     A3D_LAUNCH_CHECK();
   }
   k_measure_finish<<<1, kMeasIds, 0, st>>>(a.out_dev, a.n_classes);

@@ -37,9 +37,7 @@
 // (it holds 169 registers: three waves a SIMD) and up to 1024 workgroups, which a CU takes three at a time.
 // No grid barrier, no spin-wait: the stages are launches, ordered by the stream.  The library allocates nothing and does
 // not synchronise.
-#include "common.h"
-
-#include <cmath>
+#include "session_device.h"
 
 namespace a3d {
 
@@ -50,8 +48,6 @@ constexpr int kNrmBBlocks = 1024;
 constexpr int kNrmSweeps = 6;
 static_assert(sizeof(a3d_estimate_normals_args) == 168 && sizeof(a3d_normals_summary) == 32, "lib.py: EstimateNormalsArgs, NormalsSummary");
 
-typedef unsigned long long u64;
-
 struct NormalsWs {
   int32_t* cnt;                // [n] vertices counted in the voxel (caller row)
   u64* word;                   // [9][n] X, Y, Z, XX, XY, XZ, YY, YZ, ZZ (two's complement)
@@ -61,42 +57,15 @@ struct NormalsWs {
 };
 static NormalsWs carve_normals(void* base, long long n) {
   NormalsWs w;
-  char* p = (char*)base;
+  Carver c{base};
   const size_t m = (size_t)(n > 0 ? n : 1);
-  size_t off = 0;
-  w.cnt = (int32_t*)(p + off), off += align256(m * 4);
+  w.cnt = (int32_t*)c.take(m * 4);
   w.plane = align256(m * 8) / 8;
-  w.word = (u64*)(p + off), off += 9 * w.plane * 8;
-  w.zero_bytes = off;
-  w.normal = (float*)(p + off), off += align256(m * 12);
-  w.bytes = off;
+  w.word = (u64*)c.take(9 * w.plane * 8);
+  w.zero_bytes = c.off;
+  w.normal = (float*)c.take(m * 12);
+  w.bytes = c.off;
   return w;
-}
-
-// the sum of v over the workgroup (BLOCK threads), in thread 0
-template <int BLOCK>
-__device__ __forceinline__ long long nrm_block_sum(int v, int* wave_part) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();                             // (wave_part may still be read from the reduction before)
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long s = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < BLOCK / 64; ++w) s += wave_part[w];
-  return s;
-}
-__device__ __forceinline__ void nrm_add(int64_t* dst, long long s) {
-  if (s) atomicAdd((u64*)dst, (u64)s);
-}
-
-// X = llrint((x - origin) / quantum) when |X| <= lim (= 2^bits); a NaN or an infinity fails the comparison
-__device__ __forceinline__ bool nrm_fixed_point(float x, double origin, double quantum, double lim, long long& X) {
-#pragma clang fp contract(off)
-  const double r = rint(((double)x - origin) / quantum);
-  if (!(fabs(r) <= lim)) return false;
-  X = (long long)r;
-  return true;
 }
 
 // ---- stage A: the ten words of every voxel ------------------------------------------------------------------------------------
@@ -108,8 +77,8 @@ __global__ __launch_bounds__(kNrmFat) void k_normals_moments(const a3d_estimate_
     const long long row = a.inverse_map_dev ? a.inverse_map_dev[i] : i;
     const float x = a.xyz_dev[3 * i], y = a.xyz_dev[3 * i + 1], z = a.xyz_dev[3 * i + 2];
     long long X = 0, Y = 0, Z = 0;
-    const bool fx = nrm_fixed_point(x, a.origin[0], a.quantum, lim, X), fy = nrm_fixed_point(y, a.origin[1], a.quantum, lim, Y),
-               fz = nrm_fixed_point(z, a.origin[2], a.quantum, lim, Z);
+    const bool fx = fixed_point(x, a.origin[0], a.quantum, lim, X), fy = fixed_point(y, a.origin[1], a.quantum, lim, Y),
+               fz = fixed_point(z, a.origin[2], a.quantum, lim, Z);
     const bool in_range = fx && fy && fz, inside = row >= 0 && row < a.n;
     if (!inside) err |= A3D_NORMALS_BAD_INDEX;
     if (!in_range) err |= A3D_NORMALS_RANGE;
@@ -121,10 +90,10 @@ __global__ __launch_bounds__(kNrmFat) void k_normals_moments(const a3d_estimate_
     atomicAdd(p + 3 * w.plane, (u64)(X * X)), atomicAdd(p + 4 * w.plane, (u64)(X * Y)), atomicAdd(p + 5 * w.plane, (u64)(X * Z));
     atomicAdd(p + 6 * w.plane, (u64)(Y * Y)), atomicAdd(p + 7 * w.plane, (u64)(Y * Z)), atomicAdd(p + 8 * w.plane, (u64)(Z * Z));
   }
-  const long long s_counted = nrm_block_sum<kNrmFat>(counted, wave_part), s_err_range = nrm_block_sum<kNrmFat>(err & A3D_NORMALS_RANGE, wave_part),
-                  s_err_index = nrm_block_sum<kNrmFat>(err & A3D_NORMALS_BAD_INDEX, wave_part);
+  const long long s_counted = block_sum<kNrmFat>(counted, wave_part), s_err_range = block_sum<kNrmFat>(err & A3D_NORMALS_RANGE, wave_part),
+                  s_err_index = block_sum<kNrmFat>(err & A3D_NORMALS_BAD_INDEX, wave_part);
   if (threadIdx.x == 0) {
-    nrm_add(&a.summary_dev->counted, s_counted);
+    add_i64(&a.summary_dev->counted, s_counted);
     const int e = (s_err_range ? A3D_NORMALS_RANGE : 0) | (s_err_index ? A3D_NORMALS_BAD_INDEX : 0);
     if (e) atomicOr(&a.summary_dev->err, e);
   }
@@ -284,8 +253,8 @@ __global__ __launch_bounds__(kNrmB) void k_normals_solve(const a3d_estimate_norm
       for (int p = 0; p < 9; ++p) out[1 + p] = (int64_t)w.word[(size_t)p * w.plane + i];
     }
   }
-  const long long s_valid = nrm_block_sum<kNrmB>(n_valid, wave_part), s_invalid = nrm_block_sum<kNrmB>(n_invalid, wave_part);
-  if (threadIdx.x == 0) nrm_add(&a.summary_dev->valid, s_valid), nrm_add(&a.summary_dev->invalid, s_invalid);
+  const long long s_valid = block_sum<kNrmB>(n_valid, wave_part), s_invalid = block_sum<kNrmB>(n_invalid, wave_part);
+  if (threadIdx.x == 0) add_i64(&a.summary_dev->valid, s_valid), add_i64(&a.summary_dev->invalid, s_invalid);
 }
 
 // ---- the lift: behind a launch boundary (plain loads) --------------------------------------------------------------------------
@@ -326,18 +295,9 @@ __global__ __launch_bounds__(kNrmFat) void k_cull_points(const CullTab t) {
     n_hidden += hide;
   }
   if (t.count) {                               // (uniform over the launch)
-    const long long s = nrm_block_sum<kNrmFat>(n_hidden, wave_part);
-    if (threadIdx.x == 0) nrm_add(t.count, s);
+    const long long s = block_sum<kNrmFat>(n_hidden, wave_part);
+    if (threadIdx.x == 0) add_i64(t.count, s);
   }
-}
-
-static bool nrm_power_of_two(double q) {
-  int e;
-  return std::isfinite(q) && q > 0.0 && std::frexp(q, &e) == 0.5;
-}
-static unsigned nrm_fat_grid(long long n) {
-  const long long want = (n + kNrmFat - 1) / kNrmFat;
-  return (unsigned)(want < 1 ? 1 : want < kNrmFatBlocks ? want : kNrmFatBlocks);
 }
 
 }  // namespace a3d
@@ -357,11 +317,11 @@ extern "C" int a3d_estimate_normals(const a3d_estimate_normals_args* args, void*
   }
   const a3d_estimate_normals_args& a = *args;
   const a3d_scene* s = a.scene;
-  const bool bad_scene = !s || !s->lv[0].nbr27 || !s->orig_row || s->n0 != s->lv[0].n || a.n != s->lv[0].n;
+  const bool bad_scene = !scene_walkable(s, a.n);
   const bool bits_ok = a.bits >= 0 && a.bits <= A3D_MEASURE_MAX_BITS;
   // n_full 2^(2 bits) <= 2^62, in integers (a3d_measure_objects' bound)
   const bool sums_ok = bits_ok && a.n_full >= 0 && a.n_full < (1ll << 31) && a.n_full <= ((1ll << 62) >> (2 * a.bits));
-  bool frame_ok = nrm_power_of_two(a.quantum);
+  bool frame_ok = power_of_two(a.quantum);
   for (int k = 0; k < 3; ++k) frame_ok = frame_ok && std::isfinite(a.origin[k]) && (!a.has_viewpoint || std::isfinite(a.viewpoint[k]));
   if (bad_scene || !sums_ok || !frame_ok || (a.n_full > 0 && !a.xyz_dev) || !a.summary_dev || !a.workspace_dev ||
       ((uintptr_t)a.workspace_dev & 255) || a.workspace_bytes < a3d_normals_workspace_bytes(a.n)) {
@@ -375,17 +335,15 @@ extern "C" int a3d_estimate_normals(const a3d_estimate_normals_args* args, void*
   const NormalsWs w = carve_normals(a.workspace_dev, n);
   A3D_HIP_CHECK(hipMemsetAsync(w.cnt, 0, w.zero_bytes, st));
   if (a.n_full > 0) {
-    k_normals_moments<<<nrm_fat_grid(a.n_full), kNrmFat, 0, st>>>(a, w, std::ldexp(1.0, a.bits));
+    k_normals_moments<<<capped_grid(a.n_full, kNrmFat, kNrmFatBlocks), kNrmFat, 0, st>>>(a, w, std::ldexp(1.0, a.bits));
     A3D_LAUNCH_CHECK();
   }
   if (n > 0) {
-    const long long want = ((long long)n + kNrmB - 1) / kNrmB;
-    k_normals_solve<<<(unsigned)(want < kNrmBBlocks ? want : kNrmBBlocks), kNrmB, 0, st>>>(a, w, s->lv[0].nbr27, s->orig_row, n,
-                                                                                          s->lv[0].npad);
+    k_normals_solve<<<capped_grid(n, kNrmB, kNrmBBlocks), kNrmB, 0, st>>>(a, w, s->lv[0].nbr27, s->orig_row, n, s->lv[0].npad);
     A3D_LAUNCH_CHECK();
   }
   if (a.n_full > 0 && a.normal_full_dev) {
-    k_normals_lift<<<nrm_fat_grid(a.n_full), kNrmFat, 0, st>>>(a, w.normal);
+    k_normals_lift<<<capped_grid(a.n_full, kNrmFat, kNrmFatBlocks), kNrmFat, 0, st>>>(a, w.normal);
     A3D_LAUNCH_CHECK();
   }
   return A3D_OK;
@@ -393,7 +351,7 @@ extern "C" int a3d_estimate_normals(const a3d_estimate_normals_args* args, void*
 
 extern "C" int a3d_normals_solve(int64_t count, const int64_t* sum3, const int64_t* mom6, const double* origin, double quantum,
                                  const double* viewpoint, float* out5) {
-  if (count < 0 || !sum3 || !mom6 || !origin || !out5 || !nrm_power_of_two(quantum)) {
+  if (count < 0 || !sum3 || !mom6 || !origin || !out5 || !power_of_two(quantum)) {
     set_error("a3d_normals_solve: bad arguments (count=%lld quantum=%g)", (long long)count, quantum);
     return A3D_ERR_INVALID;
   }
@@ -421,7 +379,7 @@ extern "C" int a3d_cull_points(const float* xyz_dev, const float* normals_dev, i
     CullTab t;
     t.xyz = xyz_dev, t.normals = normals_dev, t.out = xyz_out_dev, t.hidden = hidden_dev, t.count = count_dev, t.n = n, t.mode = mode;
     for (int k = 0; k < 3; ++k) t.eye[k] = eye[k];
-    k_cull_points<<<nrm_fat_grid(n), kNrmFat, 0, st>>>(t);
+    k_cull_points<<<capped_grid(n, kNrmFat, kNrmFatBlocks), kNrmFat, 0, st>>>(t);
     A3D_LAUNCH_CHECK();
   }
   return A3D_OK;

@@ -51,9 +51,8 @@
 // VOTE: the eligible pieces (>= min_voxels) are numbered by the one-block scan; votes[slot][label] are integer atomicAdds;
 // one thread per eligible root picks the winner, tests the share in int64 and looks through the clicks for one that
 // contradicts it.
-#include "common.h"
+#include "session_device.h"
 
-#include <cmath>
 #include <cstdlib>
 
 namespace a3d {
@@ -76,23 +75,20 @@ struct PiecesWs {
   int32_t* votes;      // [capacity][n_classes]
   size_t label_bytes, zero_bytes, bytes;
 };
+// k int32 of a workspace (at least one)
+static int32_t* take_ints(Carver& c, size_t k) { return (int32_t*)c.take((k > 0 ? k : 1) * 4); }
 static PiecesWs carve_pieces(void* base, long long n, long long capacity, int n_classes) {
   PiecesWs w;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t ints) {
-    char* q = p + off;
-    off += align256((ints > 0 ? ints : 1) * 4);
-    return (int32_t*)q;
-  };
+  Carver c{base};
   const size_t m = (size_t)(n > 0 ? n : 1);
-  w.size = take(m), w.clicked = take(m), w.lo = take(3 * m), w.hi = take(3 * m), w.parent = take(m);
-  w.label_bytes = off;
-  w.slot = take(m), w.newlabel = take((size_t)capacity);
-  const size_t zero_from = off;
-  w.cflag = take(m), w.votes = take((size_t)capacity * (size_t)n_classes);
-  w.zero_bytes = off - zero_from;
-  w.bytes = off;
+  w.size = take_ints(c, m), w.clicked = take_ints(c, m), w.lo = take_ints(c, 3 * m), w.hi = take_ints(c, 3 * m);
+  w.parent = take_ints(c, m);
+  w.label_bytes = c.off;
+  w.slot = take_ints(c, m), w.newlabel = take_ints(c, (size_t)capacity);
+  const size_t zero_from = c.off;
+  w.cflag = take_ints(c, m), w.votes = take_ints(c, (size_t)capacity * (size_t)n_classes);
+  w.zero_bytes = c.off - zero_from;
+  w.bytes = c.off;
   return w;
 }
 
@@ -475,16 +471,11 @@ struct VoteWs {
 static VoteWs carve_vote(void* base, long long n, long long capacity, int n_classes) {
   const PiecesWs p = carve_pieces(base, n, 0, 1);
   VoteWs w;
-  size_t off = p.label_bytes;
-  auto take = [&](size_t ints) {
-    char* q = (char*)base + off;
-    off += align256((ints > 0 ? ints : 1) * 4);
-    return (int32_t*)q;
-  };
+  Carver c{base, p.label_bytes};                // behind what the labelling call left
   w.size = p.size;
-  w.slot = take((size_t)(n > 0 ? n : 1)), w.decision = take((size_t)capacity);
-  w.votes = take((size_t)capacity * (size_t)n_classes);
-  w.bytes = off;
+  w.slot = take_ints(c, (size_t)(n > 0 ? n : 1)), w.decision = take_ints(c, (size_t)capacity);
+  w.votes = take_ints(c, (size_t)capacity * (size_t)n_classes);
+  w.bytes = c.off;
   return w;
 }
 
@@ -582,16 +573,12 @@ __global__ __launch_bounds__(kPiecesBlock) void k_vote_write(const a3d_vote_piec
   }
 }
 
-static bool pieces_tab(const a3d_scene* s, int connectivity, PiecesTab* t) {
-  if (!s || !s->lv[0].nbr27 || !s->orig_row || !s->lv[0].xyzb || s->n0 != s->lv[0].n) return false;
+static bool pieces_tab(const a3d_scene* s, long long n, int connectivity, PiecesTab* t) {
+  if (!scene_walkable(s, n) || !s->lv[0].xyzb) return false;
   t->nbr = s->lv[0].nbr27, t->orig = s->orig_row, t->xyzb = s->lv[0].xyzb;
   t->n = s->lv[0].n, t->npad = s->lv[0].npad;
   t->mask = offset_mask(connectivity);
   return true;
-}
-static unsigned pieces_grid(long long n) {
-  const long long want = (n + kPiecesBlock - 1) / kPiecesBlock;
-  return (unsigned)(want < 1 ? 1 : want < kPiecesMaxBlocks ? want : kPiecesMaxBlocks);
 }
 
 }  // namespace a3d
@@ -617,7 +604,7 @@ extern "C" int a3d_label_pieces(const a3d_label_pieces_args* args, void* stream)
   const a3d_label_pieces_args& a = *args;
   PiecesTab t;
   const bool bad_conn = a.connectivity != 6 && a.connectivity != 18 && a.connectivity != 26;
-  if (bad_conn || !pieces_tab(a.scene, a.connectivity, &t) || a.n != t.n || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS ||
+  if (bad_conn || !pieces_tab(a.scene, a.n, a.connectivity, &t) || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS ||
       a.max_out < 0 || a.n_full < 0 || !a.n_out_dev || (a.max_out > 0 && !a.out_dev) ||
       (a.n > 0 && (!a.keys_dev || !a.piece_qv_dev || !a.workspace_dev)) || (a.n_full > 0 && (!a.piece_full_dev || !a.piece_qv_dev)) ||
       ((uintptr_t)a.workspace_dev & 255) || a.workspace_bytes < a3d_pieces_workspace_bytes(a.n)) {
@@ -629,7 +616,7 @@ extern "C" int a3d_label_pieces(const a3d_label_pieces_args* args, void* stream)
   const int n = t.n;
   if (n > 0) {
     const PiecesWs w = carve_pieces(a.workspace_dev, n, 0, 1);
-    const unsigned grid = pieces_grid(n);
+    const unsigned grid = capped_grid(n, kPiecesBlock, kPiecesMaxBlocks);
     k_pieces_init<<<grid, kPiecesBlock, 0, st>>>(a.keys_dev, w, n);
     A3D_LAUNCH_CHECK();
     k_pieces_hook<<<grid, kPiecesBlock, 0, st>>>(a.keys_dev, t, w.parent);
@@ -642,7 +629,7 @@ extern "C" int a3d_label_pieces(const a3d_label_pieces_args* args, void* stream)
     A3D_LAUNCH_CHECK();
   }
   if (a.n_full > 0) {
-    k_pieces_full<<<pieces_grid(a.n_full), kPiecesBlock, 0, st>>>(a, n);
+    k_pieces_full<<<capped_grid(a.n_full, kPiecesBlock, kPiecesMaxBlocks), kPiecesBlock, 0, st>>>(a, n);
     A3D_LAUNCH_CHECK();
   }
   return A3D_OK;
@@ -657,7 +644,7 @@ extern "C" int a3d_absorb_pieces(const a3d_absorb_pieces_args* args, void* strea
   const a3d_absorb_pieces_args& a = *args;
   PiecesTab t;
   const bool bad_conn = a.connectivity != 6 && a.connectivity != 18 && a.connectivity != 26;
-  if (bad_conn || !pieces_tab(a.scene, a.connectivity, &t) || a.n != t.n || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS ||
+  if (bad_conn || !pieces_tab(a.scene, a.n, a.connectivity, &t) || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS ||
       a.n_classes < 1 || a.n_classes > 256 || a.capacity < 0 || a.min_voxels < 0 || !a.summary_dev ||
       (a.n > 0 && (!a.labels_dev || !a.piece_qv_dev || !a.labels_out_dev || !a.workspace_dev || a.labels_out_dev == a.labels_dev)) ||
       ((uintptr_t)a.workspace_dev & 255) || a.workspace_bytes < a3d_absorb_workspace_bytes(a.n, a.capacity, a.n_classes)) {
@@ -671,7 +658,7 @@ extern "C" int a3d_absorb_pieces(const a3d_absorb_pieces_args* args, void* strea
   if (n > 0) {
     const PiecesWs w = carve_pieces(a.workspace_dev, n, a.capacity, a.n_classes);
     A3D_HIP_CHECK(hipMemsetAsync(w.cflag, 0, w.zero_bytes, st));       // the click flags and the votes
-    const unsigned grid = pieces_grid(n);
+    const unsigned grid = capped_grid(n, kPiecesBlock, kPiecesMaxBlocks);
     if (a.n_clicks > 0) {
       k_absorb_clicks<<<1, kPiecesBlock, 0, st>>>(a, w, n);
       A3D_LAUNCH_CHECK();
@@ -712,7 +699,7 @@ extern "C" int a3d_similar_pieces(const a3d_similar_pieces_args* args, void* str
   const a3d_similar_pieces_args& a = *args;
   PiecesTab t;
   const bool bad_conn = a.connectivity != 6 && a.connectivity != 18 && a.connectivity != 26;
-  if (bad_conn || !pieces_tab(a.scene, a.connectivity, &t) || a.n != t.n || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS ||
+  if (bad_conn || !pieces_tab(a.scene, a.n, a.connectivity, &t) || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS ||
       a.max_out < 0 || a.n_full < 0 || !a.n_out_dev || (a.max_out > 0 && !a.out_dev) ||
       (a.n > 0 && (!a.piece_qv_dev || !a.workspace_dev)) || (a.n_full > 0 && (!a.piece_full_dev || !a.piece_qv_dev)) ||
       ((uintptr_t)a.workspace_dev & 255) || a.workspace_bytes < a3d_pieces_workspace_bytes(a.n)) {
@@ -745,7 +732,7 @@ extern "C" int a3d_similar_pieces(const a3d_similar_pieces_args* args, void* str
     for (int c = 0; c < 3; ++c) s.ref_normal[c] = a.ref_normal[c], s.ref_feat[c] = a.ref_feat[c];
     s.oriented = a.oriented, s.ref_flags = a.ref_flags;
     const PiecesWs w = carve_pieces(a.workspace_dev, n, 0, 1);
-    const unsigned grid = pieces_grid(n);
+    const unsigned grid = capped_grid(n, kPiecesBlock, kPiecesMaxBlocks);
     k_similar_init<<<grid, kPiecesBlock, 0, st>>>(s, w, n);
     A3D_LAUNCH_CHECK();
     if (s.normal && s.feat)
@@ -765,7 +752,7 @@ extern "C" int a3d_similar_pieces(const a3d_similar_pieces_args* args, void* str
     A3D_LAUNCH_CHECK();
   }
   if (a.n_full > 0) {
-    k_pieces_full<<<pieces_grid(a.n_full), kPiecesBlock, 0, st>>>(la, n);
+    k_pieces_full<<<capped_grid(a.n_full, kPiecesBlock, kPiecesMaxBlocks), kPiecesBlock, 0, st>>>(la, n);
     A3D_LAUNCH_CHECK();
   }
   return A3D_OK;
@@ -784,7 +771,7 @@ extern "C" int a3d_vote_pieces(const a3d_vote_pieces_args* args, void* stream) {
   }
   const a3d_vote_pieces_args& a = *args;
   PiecesTab t;
-  if (!pieces_tab(a.scene, 26, &t) || a.n != t.n || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS || a.n_classes < 1 ||
+  if (!pieces_tab(a.scene, a.n, 26, &t) || a.n_clicks < 0 || a.n_clicks > A3D_MAX_CLICKS || a.n_classes < 1 ||
       a.n_classes > 256 || a.capacity < 0 || a.min_voxels < 1 || a.share_num < 1 || a.share_num > a.share_den ||
       a.share_den > 65536 || !a.summary_dev ||
       (a.n > 0 && (!a.labels_dev || !a.piece_qv_dev || !a.labels_out_dev || !a.workspace_dev || a.labels_out_dev == a.labels_dev)) ||
@@ -797,7 +784,7 @@ extern "C" int a3d_vote_pieces(const a3d_vote_pieces_args* args, void* stream) {
   const int n = t.n;
   if (n > 0) {
     const VoteWs w = carve_vote(a.workspace_dev, n, a.capacity, a.n_classes);
-    const unsigned grid = pieces_grid(n);
+    const unsigned grid = capped_grid(n, kPiecesBlock, kPiecesMaxBlocks);
     k_vote_scan<<<1, kPiecesScan, 0, st>>>(a, w, n);
     A3D_LAUNCH_CHECK();
     k_vote_clear<<<grid, kPiecesBlock, 0, st>>>(a, w);

@@ -26,6 +26,7 @@
 // addresses and are served one after the other, about 15 ns each: at 1 M vertices a grid of 2048 workgroups of 256 spent
 // 70 us in select, 45 of them in that queue.  Hence workgroups of 1024 threads and at most one per CU (256): 256 - 768
 // atomics a call, 27 us (profiles/region_timing.txt); 16 waves per CU still hide the latency of the loads.
+#include "session_device.h"
 #include "session_rules.h"
 
 namespace a3d {
@@ -92,23 +93,6 @@ __global__ __launch_bounds__(kMaskBlock) void k_region_mask(const MaskTab t) {
   *m = out ? 1 : 0;
 }
 
-// The sum of v over the workgroup, in thread 0 (the other threads' return value is not meant to be used).
-__device__ __forceinline__ long long reg_block_sum(int v, int* wave_sum) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();                             // (wave_sum may still be read from the sum before)
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long s = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kRegBlock / 64; ++w) s += wave_sum[w];
-  return s;
-}
-__device__ __forceinline__ void reg_add(int64_t* dst, long long s) {
-  if (s) atomicAdd((unsigned long long*)dst, (unsigned long long)s);
-}
-__device__ __forceinline__ bool reg_not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
 struct SelectTab {
   const float* xyz;
   long long n;
@@ -130,7 +114,7 @@ __global__ __launch_bounds__(kRegBlock) void k_select_vertices(const SelectTab t
   const long long stride = (long long)gridDim.x * kRegBlock;
   for (long long i = (long long)blockIdx.x * kRegBlock + threadIdx.x; i < t.n; i += stride) {
     const float px = xyz[3 * i], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
-    if (reg_not_finite(px) || reg_not_finite(py) || reg_not_finite(pz)) odd = 1;
+    if (not_finite(px) || not_finite(py) || not_finite(pz)) odd = 1;
     const float wx = px - t.cam.o[0], wy = py - t.cam.o[1], wz = pz - t.cam.o[2];
     const float a = (t.R[0] * wx + t.R[1] * wy) + t.R[2] * wz;
     const float b = (t.R[3] * wx + t.R[4] * wy) + t.R[5] * wz;
@@ -154,11 +138,11 @@ __global__ __launch_bounds__(kRegBlock) void k_select_vertices(const SelectTab t
     t.selected[i] = sel ? 1 : 0;
     n_view += in_view, n_selected += sel;
   }
-  const long long s_sel = reg_block_sum(n_selected, wave_sum), s_view = reg_block_sum(n_view, wave_sum);
-  const long long s_odd = reg_block_sum(odd, wave_sum);
+  const long long s_sel = block_sum<kRegBlock>(n_selected, wave_sum), s_view = block_sum<kRegBlock>(n_view, wave_sum);
+  const long long s_odd = block_sum<kRegBlock>(odd, wave_sum);
   if (threadIdx.x == 0) {
-    reg_add(&t.summary->selected, s_sel);
-    reg_add(&t.summary->in_view, s_view);
+    add_i64(&t.summary->selected, s_sel);
+    add_i64(&t.summary->in_view, s_view);
     if (s_odd) atomicOr(&t.summary->flags, A3D_SELECT_NOT_FINITE);
   }
 }
@@ -207,19 +191,14 @@ __global__ __launch_bounds__(kRegBlock) void k_session_overlay(const a3d_session
     }
     a.colors_out_dev[3 * i] = r, a.colors_out_dev[3 * i + 1] = g, a.colors_out_dev[3 * i + 2] = b;
   }
-  const long long s_changed = reg_block_sum(n_changed, wave_sum), s_on = reg_block_sum(n_on, wave_sum);
-  const long long s_differ = reg_block_sum(n_differ, wave_sum), s_bad = reg_block_sum(bad, wave_sum);
+  const long long s_changed = block_sum<kRegBlock>(n_changed, wave_sum), s_on = block_sum<kRegBlock>(n_on, wave_sum);
+  const long long s_differ = block_sum<kRegBlock>(n_differ, wave_sum), s_bad = block_sum<kRegBlock>(bad, wave_sum);
   if (threadIdx.x == 0) {
-    reg_add(&a.summary_dev->changed, s_changed);
-    reg_add(&a.summary_dev->overridden, s_on);
-    reg_add(&a.summary_dev->differing, s_differ);
+    add_i64(&a.summary_dev->changed, s_changed);
+    add_i64(&a.summary_dev->overridden, s_on);
+    add_i64(&a.summary_dev->differing, s_differ);
     if (s_bad) atomicOr(&a.summary_dev->err, 1);
   }
-}
-
-static unsigned reg_blocks(long long n) {
-  const long long want = (n + kRegBlock - 1) / kRegBlock;
-  return (unsigned)(want < kRegMaxBlocks ? want : kRegMaxBlocks);
 }
 
 }  // namespace a3d
@@ -293,7 +272,7 @@ extern "C" int a3d_select_vertices(const a3d_select_args* args, void* stream) {
   a3d_section sec;
   memset(&sec, 0, sizeof sec);                 // no section: no plane
   if (a.section) sec = *a.section;
-  k_select_vertices<<<reg_blocks(a.n), kRegBlock, 0, st>>>(t, sec);
+  k_select_vertices<<<capped_grid(a.n, kRegBlock, kRegMaxBlocks), kRegBlock, 0, st>>>(t, sec);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -317,7 +296,7 @@ extern "C" int a3d_session_overlay(const a3d_session_overlay_args* args, void* s
   }
   A3D_HIP_CHECK(hipMemsetAsync(a.summary_dev, 0, sizeof(a3d_overlay_summary), st));
   if (a.n == 0) return A3D_OK;
-  k_session_overlay<<<reg_blocks(a.n), kRegBlock, 0, st>>>(a);
+  k_session_overlay<<<capped_grid(a.n, kRegBlock, kRegMaxBlocks), kRegBlock, 0, st>>>(a);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

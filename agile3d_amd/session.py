@@ -280,7 +280,18 @@ def rank_spots(records, max_spots=MAX_SPOTS):
     return order[:int(max_spots)]
 
 
-class PiecesResult:
+class _Result:
+    """What the ``*Result`` classes share: keyword arguments become the fields their ``__slots__`` name, ``None`` for what
+    was not given."""
+
+    __slots__ = ()
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+class PiecesResult(_Result):
     """What ``pieces()`` returns.  Device tensors: ``piece_qv`` int32 [n_voxels] (the smallest voxel row of the voxel's piece)
     and ``piece_full`` int32 [n_full] (the same lifted to the vertices).  Host: ``records``, a numpy structured array
     (``view.PIECE``: root, key = the object id, voxels, clicked, lo, hi) in ascending root; ``object_pieces`` int64 (pieces per
@@ -288,12 +299,8 @@ class PiecesResult:
 
     __slots__ = ("piece_qv", "piece_full", "records", "object_pieces", "n_pieces", "connectivity")
 
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
-
-class DespeckleResult:
+class DespeckleResult(_Result):
     """What ``despeckle()`` returns: ``labels_full``, ``colors``, ``miou`` and ``iou_per_object`` as a ``SessionResult`` holds
     them, ``labels_qv`` int32 [n_voxels] on the device, and the counts of ``a3d_absorb_pieces``' summary: ``small_pieces``,
     ``relabelled_pieces``, ``relabelled_voxels``, ``kept_isolated``; ``min_voxels`` and ``connectivity`` as used."""
@@ -301,12 +308,8 @@ class DespeckleResult:
     __slots__ = ("labels_full", "colors", "miou", "iou_per_object", "labels_qv", "small_pieces", "relabelled_pieces",
                  "relabelled_voxels", "kept_isolated", "min_voxels", "connectivity")
 
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
-
-class PatchesResult:
+class PatchesResult(_Result):
     """What ``patches()`` returns: the fields of a ``PiecesResult`` -- ``piece_qv`` int32 [n_voxels] (the smallest voxel row of
     the voxel's patch, -1: none; ``grow(within=r.piece_qv)`` walks inside one patch), ``piece_full`` int32 [n_full], ``records``
     (``view.PIECE``; key = the key of ``within``, 0 with ``"all"``) in ascending root, ``n_pieces``, ``connectivity``,
@@ -316,12 +319,8 @@ class PatchesResult:
 
     __slots__ = PiecesResult.__slots__ + ("normal_deg", "cos_min", "color_tol", "tol2", "oriented", "within", "workspace")
 
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
-
-class WandResult:
+class WandResult(_Result):
     """What ``wand_at()`` returns: ``selected`` uint8 [n_full] on the device (1 = the vertex lies in the patch under the pixel;
     ``paint``, ``erase``, ``grow`` and ``shrink`` take the result as it is), ``piece_qv`` int32 [n_voxels] (the partition the
     call computed), and on the host ``count`` (selected vertices), ``record`` (the patch's ``view.PIECE`` row, ``None`` when
@@ -329,12 +328,8 @@ class WandResult:
 
     __slots__ = ("selected", "count", "record", "piece_qv", "mode", "normal_deg", "color_tol", "connectivity", "within")
 
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
-
-class SnapResult:
+class SnapResult(_Result):
     """What ``snap()`` returns: ``labels_full``, ``colors``, ``miou`` and ``iou_per_object`` as a ``SessionResult`` holds them,
     ``labels_qv`` int32 [n_voxels] on the device, and the counts of ``a3d_vote_pieces``' summary: ``eligible_pieces``,
     ``uniform_pieces``, ``relabelled_pieces``, ``relabelled_voxels``, ``blocked_pieces``, ``below_share_pieces``;
@@ -342,10 +337,6 @@ class SnapResult:
 
     __slots__ = ("labels_full", "colors", "miou", "iou_per_object", "labels_qv", "eligible_pieces", "uniform_pieces",
                  "relabelled_pieces", "relabelled_voxels", "blocked_pieces", "below_share_pieces", "min_voxels", "min_share")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def patch_thresholds(normal_deg, color_tol):
@@ -370,19 +361,15 @@ def patch_thresholds(normal_deg, color_tol):
 WAND_MODES = ("chain", "seed", "both")
 
 
-class SelectResult:
+class SelectResult(_Result):
     """What ``select()`` returns: ``selected`` uint8 [n_full] on the device (1 = the vertex is selected), and on the host
     ``count`` (how many are), ``in_view`` (the vertices the camera sees at all: in front of it, inside the image, on the
     kept side of the section), ``through`` and ``slack`` as used."""
 
     __slots__ = ("selected", "count", "in_view", "through", "slack")
 
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
-
-class GrowResult:
+class GrowResult(_Result):
     """What ``grow()``, ``grow_at()`` and ``shrink()`` return.  Device tensors: ``selected`` uint8 [n_full] (1 = the vertex is
     selected; ``paint`` / ``erase`` take it as it is), ``dist_full`` int32 [n_full] and ``dist_qv`` int32 [n_voxels] (the path
     cost from the nearest seed in the units of ``cost``, -1: not reached), ``owner_qv`` int32 [n_voxels] (the voxel row of that
@@ -393,10 +380,6 @@ class GrowResult:
 
     __slots__ = ("selected", "dist_full", "dist_qv", "owner_qv", "count", "reached_voxels", "seeds", "max_distance", "limit",
                  "cost", "connectivity", "within")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def grow_limit(radius, steps, voxel_size):
@@ -422,7 +405,7 @@ def grow_limit(radius, steps, voxel_size):
     return cost, limit
 
 
-class NormalsResult:
+class NormalsResult(_Result):
     """What ``estimate_normals()`` returns.  Device tensors: ``normals_full`` fp32 [n_full, 3] (unit vectors; zero where the
     vertex's voxel has no valid normal), ``normals_qv`` fp32 [n_voxels, 3], ``variation_qv`` fp32 [n_voxels] (the surface
     variation, smallest eigenvalue over the sum: 0 on a plane, 1/3 for a blob), ``count_qv`` int32 [n_voxels] (the vertices of
@@ -432,25 +415,17 @@ class NormalsResult:
 
     __slots__ = ("normals_full", "normals_qv", "variation_qv", "count_qv", "counted", "valid", "invalid", "err", "viewpoint")
 
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
-
 
 _MAX_CULLED = 4                                 # culled copies of a cloud kept at a time (one per eye and mode)
 
 
-class CorrectedResult:
+class CorrectedResult(_Result):
     """What ``corrected()`` returns: ``labels_full`` int32 [n_full] and ``colors`` fp32 [n_full, 3] on the device -- the model's
     labels with the manual layer laid over them -- ``miou`` and ``iou_per_object`` as a ``SessionResult`` holds them (``None``
     without ground truth), ``overridden`` (vertices the layer holds) and ``differing`` (those of them whose manual label is
     not the model's)."""
 
     __slots__ = ("labels_full", "colors", "miou", "iou_per_object", "overridden", "differing")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 _RENDERED = object()                            # select(section=): "the section the view was rendered under"
@@ -516,7 +491,7 @@ def principal_axes(cov, vertices=None):
     return (axes[0], variances[0]) if single else (axes, variances)
 
 
-class MeasureResult:
+class MeasureResult(_Result):
     """What ``measure()`` returns: arrays over the object ids 0..K (host, float64 unless noted).  ``vertices``, ``voxels``
     int64; ``centroid`` [K + 1, 3]; ``lo``, ``hi`` fp32 [K + 1, 3], the exact axis-aligned box (+inf / -inf for an object without
     a vertex); ``cov`` [K + 1, 3, 3]; ``area`` (``None`` on a cloud) and ``volume`` (of the occupied voxels) [K + 1].  With
@@ -526,10 +501,6 @@ class MeasureResult:
 
     __slots__ = ("vertices", "voxels", "centroid", "lo", "hi", "cov", "area", "volume", "axes", "centre", "extents", "origin",
                  "quantum", "bits", "area_quantum", "moments")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
     def section(self, obj, margin=0.0, cull="none"):
         """The ``Section`` that isolates object ``obj`` in ``render`` / ``pick``: ``Section.box(lo - margin, hi + margin)``
@@ -543,7 +514,7 @@ class MeasureResult:
         return Section.box(self.lo[obj].astype(np.float64) - float(margin), self.hi[obj].astype(np.float64) + float(margin), cull)
 
 
-class GuideResult:
+class GuideResult(_Result):
     """What ``guide()`` returns.  Device tensors: ``labels_qv`` int32 [n_voxels] (what ``infer()`` computed), ``runner_qv``
     int32 (the second choice), ``margin_qv`` fp32 (winner's logit minus runner-up's; +inf on a clicked voxel), ``margin_full``
     fp32 [n_full], ``colors`` fp32 [n_full, 3] (the confidence view, for ``render(colors=)``).  Host: ``object_voxels`` and
@@ -555,22 +526,14 @@ class GuideResult:
     __slots__ = ("labels_qv", "runner_qv", "margin_qv", "margin_full", "colors", "object_voxels", "object_contested",
                  "least_confident", "n_contested", "suggestions", "threshold", "full_margin", "n_spots", "n_spots_searched")
 
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
-
-class SessionResult:
+class SessionResult(_Result):
     """What one ``infer()`` returns.  ``labels_full`` int32 [n_full] and ``colors`` fp32 [n_full, 3] stay on the device;
     ``miou`` is a Python float (the float32 mean IoU) or ``None`` without ground truth; ``record``, ``mask_path`` and
     ``click_path`` are set when the scene has an ``out_dir``."""
 
     __slots__ = ("labels_full", "colors", "miou", "iou_per_object", "num_obj", "avg_clicks", "record", "mask_path",
                  "click_path")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def _f3(values, what):
@@ -780,7 +743,7 @@ def visible_clicks(section, points):
     return np.arange(len(p)) if section is None else np.flatnonzero(section.keeps(p))
 
 
-class RenderResult:
+class RenderResult(_Result):
     """What ``render()`` returns.  Device tensors: ``ids`` int32 [h, w] (face of a mesh, vertex of a cloud, -1 = nothing),
     ``t`` fp32 [h, w] (+inf = nothing), ``rgb`` uint8 [h, w, 3], on a mesh ``u`` and ``v`` fp32 [h, w] (else ``None``).
     ``camera``: the ``lib.Camera`` rendered.  ``mesh``: whether ids are faces.  ``lit``: whether ``rgb`` is shaded.
@@ -788,10 +751,6 @@ class RenderResult:
     ``section``: the ``Section`` the view was rendered under, or ``None``."""
 
     __slots__ = ("ids", "t", "rgb", "u", "v", "camera", "mesh", "lit", "pairs", "n_everywhere", "section")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 class InteractiveSession:

@@ -30,9 +30,20 @@ assert C.sizeof(L.RenderHeader) == RENDER_HEADER.itemsize == 16
 
 
 # ---- decoding: pure functions of a host array ----------------------------------------------------------------------------
+def _record(host, dtype):
+    """The ``dtype`` record at the front of a host buffer (of those bytes, whatever its own dtype and shape)."""
+    return np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:dtype.itemsize].view(dtype)[0]
+
+
+def _summary_ints(host, dtype):
+    """The fields of a summary record as a dict of Python ints (the padding left out)."""
+    rec = _record(host, dtype)
+    return {k: int(rec[k]) for k in dtype.names if k != "reserved_"}
+
+
 def read_pick(host):
     """``(index, xyz fp32 [3])`` of the int32 [4] host copy of an ``a3d_pick_result`` (index -1: the ray meets no point)."""
-    rec = np.ascontiguousarray(host).view(PICK)[0]
+    rec = _record(host, PICK)
     return int(rec["index"]), np.array([rec["x"], rec["y"], rec["z"]], np.float32)
 
 
@@ -43,7 +54,7 @@ def read_pick_mesh(host):
 
 def read_render_header(host):
     """``(flags, n_everywhere, pairs)`` of the int32 [4] host copy of an ``a3d_render_header``."""
-    rec = np.ascontiguousarray(host).view(RENDER_HEADER)[0]
+    rec = _record(host, RENDER_HEADER)
     return int(rec["flags"]), int(rec["n_everywhere"]), int(rec["pairs_needed"])
 
 
@@ -54,6 +65,45 @@ def _f32p(name, values, shape):
     if a.shape != shape:
         raise ValueError(f"{name} must have shape {list(shape)}")
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _int_in(name, value, lo, hi, message=None):
+    """``int(value)`` of an integer (no bool; a float only when it is whole) in lo .. hi, else ``ValueError(message)``."""
+    if isinstance(value, bool) or int(value) != value or not lo <= value <= hi:
+        raise ValueError(message or f"{name} must be an integer in {lo} .. {hi}")
+    return int(value)
+
+
+def _summary(summary, nbytes, dev, align=8):
+    summary = _out("summary", summary, U8, (nbytes,), dev)
+    if summary.data_ptr() % align:
+        raise ValueError(f"summary must be {align}-byte aligned")
+    return summary
+
+
+def _scratch(nbytes, device, refusal):
+    """uint8 [nbytes] of scratch on the device; 0 is the library's "no such workspace": ``ValueError(refusal)``."""
+    if nbytes == 0:
+        raise ValueError(refusal)
+    return torch.empty(nbytes, dtype=U8, device=device)
+
+
+def _attach(a, workspace, dev, need=None, message=None):
+    """The workspace into the argument block ``a``; with ``need`` (bytes) the size and the 256-byte alignment are checked."""
+    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
+    if need is not None and (a.workspace_bytes < need or workspace.data_ptr() % 256):
+        raise ValueError(message)
+
+
+def _wanted(a, dev, outputs):
+    """The optional outputs ``(name, tensor, dtype, shape)`` of a call: ``None`` = allocated, ``False`` = not wanted (a null
+    pointer, as for one without rows).  Sets ``a.<name>_dev``; returns the tensors, ``None`` for what was not wanted."""
+    outs = []
+    for name, t, dtype, shape in outputs:
+        t = None if t is False else _out(name, t, dtype, shape, dev)
+        setattr(a, name + "_dev", t.data_ptr() if t is not None and shape[0] else None)
+        outs.append(t)
+    return outs
 
 
 def session_workspace(device):
@@ -392,7 +442,7 @@ def read_guide_summary(host):
     and ``contested`` int64 [256] (rows and contested rows per label), ``least`` = ``(row, margin)`` of the least confident
     row -- the smallest finite margin, ties to the lowest row -- or ``None`` when no row has a finite margin, ``err`` (bit
     ``GUIDE_NAN_MARGIN``, bit ``GUIDE_BAD_INDEX``)."""
-    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:GUIDE_SUMMARY.itemsize].view(GUIDE_SUMMARY)[0]
+    rec = _record(host, GUIDE_SUMMARY)
     key = ~int(rec["least_key"]) & ((1 << 64) - 1)       # (stored complemented: the cleared record means "no row")
     least = None
     if key != (1 << 64) - 1:
@@ -450,9 +500,7 @@ def session_guide(logits, click_rows, click_objs, threshold, inverse_map=None, c
         a.margin_full_dev, a.colors_out_dev = (margin_full.data_ptr(), colors_out.data_ptr()) if m else (None, None)
     elif inverse_map is not None or margin_full is not None or colors_out is not None:
         raise ValueError("inverse_map, margin_full and colors_out belong to the vertex half: colors is missing")
-    summary = _out("summary", summary, U8, (GUIDE_SUMMARY.itemsize,), dev)
-    if summary.data_ptr() % 8:
-        raise ValueError("summary must be 8-byte aligned")
+    summary = _summary(summary, GUIDE_SUMMARY.itemsize, dev)
     a.summary_dev = summary.data_ptr()
     L.check(L.load().a3d_session_guide(C.byref(a), L.stream(dev)), "a3d_session_guide")
     return labels, runner, margin, want, margin_full, colors_out, summary
@@ -484,8 +532,7 @@ def read_absorb_summary(host):
     """The host copy of an ``a3d_absorb_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints:
     ``small_pieces`` (on ``ABSORB_OVERFLOW`` the capacity needed), ``relabelled_pieces``, ``relabelled_voxels``,
     ``kept_isolated``, ``err`` (bits ``ABSORB_OVERFLOW``, ``ABSORB_BAD_LABEL``)."""
-    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:ABSORB_SUMMARY.itemsize].view(ABSORB_SUMMARY)[0]
-    return {k: int(rec[k]) for k in ("small_pieces", "relabelled_pieces", "relabelled_voxels", "kept_isolated", "err")}
+    return _summary_ints(host, ABSORB_SUMMARY)
 
 
 def pieces_workspace(n, device, capacity=None, n_classes=256):
@@ -493,9 +540,7 @@ def pieces_workspace(n, device, capacity=None, n_classes=256):
     ``absorb_pieces`` with that many small pieces and ``n_classes`` labels (``a3d_absorb_workspace_bytes``)."""
     lib = L.load()
     nbytes = lib.a3d_pieces_workspace_bytes(n) if capacity is None else lib.a3d_absorb_workspace_bytes(n, capacity, n_classes)
-    if nbytes == 0:
-        raise ValueError(f"no pieces workspace for n={n} capacity={capacity} n_classes={n_classes}")
-    return torch.empty(nbytes, dtype=U8, device=device)
+    return _scratch(nbytes, device, f"no pieces workspace for n={n} capacity={capacity} n_classes={n_classes}")
 
 
 def _scene_rows(scene):
@@ -545,7 +590,7 @@ def _pieces_outputs(a, n, dev, connectivity, click_rows, inverse_map, piece_qv, 
     a.n_out_dev = count.data_ptr()
     if workspace is None:
         workspace = pieces_workspace(n, dev)
-    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
+    _attach(a, workspace, dev)                  # (the library checks the size: a vote's workspace is one as well)
     return piece_qv, piece_full, records, count, workspace
 
 
@@ -583,22 +628,16 @@ def absorb_pieces(scene, labels, piece_qv, workspace, min_voxels, connectivity=2
     a.piece_qv_dev = _ptr("piece_qv", piece_qv, I32, (n,), dev)
     a.connectivity = _connectivity(connectivity)
     a.n_clicks = _click_rows(a.click_row, click_rows)
-    for name, value, lo, hi in (("min_voxels", min_voxels, 0, (1 << 31) - 1), ("n_classes", n_classes, 1, 256),
-                                ("capacity", capacity, 0, (1 << 31) - 1)):
-        if int(value) != value or not lo <= value <= hi:
-            raise ValueError(f"{name} must be an integer in {lo} .. {hi}")
-    a.min_voxels, a.n_classes, a.capacity = int(min_voxels), int(n_classes), int(capacity)
+    a.min_voxels = _int_in("min_voxels", min_voxels, 0, (1 << 31) - 1)
+    a.n_classes, a.capacity = _int_in("n_classes", n_classes, 1, 256), _int_in("capacity", capacity, 0, (1 << 31) - 1)
     labels_out = _out("labels_out", labels_out, I32, (n,), dev)
     if n and labels_out.data_ptr() == labels.data_ptr():
         raise ValueError("labels_out may not alias labels")
     a.labels_out_dev = labels_out.data_ptr()
-    summary = _out("summary", summary, U8, (ABSORB_SUMMARY.itemsize,), dev)
-    if summary.data_ptr() % 4:
-        raise ValueError("summary must be 4-byte aligned")
+    summary = _summary(summary, ABSORB_SUMMARY.itemsize, dev, 4)
     a.summary_dev = summary.data_ptr()
-    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
-    if a.workspace_bytes < L.load().a3d_absorb_workspace_bytes(n, a.capacity, a.n_classes):
-        raise ValueError("workspace too small for this capacity and n_classes (pieces_workspace(n, device, capacity, n_classes))")
+    _attach(a, workspace, dev, L.load().a3d_absorb_workspace_bytes(n, a.capacity, a.n_classes),
+            "workspace too small for this capacity and n_classes (pieces_workspace(n, device, capacity, n_classes))")
     L.check(L.load().a3d_absorb_pieces(C.byref(a), L.stream(dev)), "a3d_absorb_pieces")
     return labels_out, summary
 
@@ -618,17 +657,14 @@ def read_vote_summary(host):
     """The host copy of an ``a3d_vote_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints:
     ``eligible_pieces`` (on ``VOTE_OVERFLOW`` the capacity needed), ``uniform_pieces``, ``relabelled_pieces``,
     ``relabelled_voxels``, ``blocked_pieces``, ``below_share_pieces``, ``err`` (bits ``VOTE_OVERFLOW``, ``VOTE_BAD_LABEL``)."""
-    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:VOTE_SUMMARY.itemsize].view(VOTE_SUMMARY)[0]
-    return {k: int(rec[k]) for k in VOTE_SUMMARY.names[:-1]}
+    return _summary_ints(host, VOTE_SUMMARY)
 
 
 def vote_workspace(n, device, capacity, n_classes=256):
     """The scratch of ``label_pieces`` / ``similar_pieces`` for n voxels with room behind it for ``vote_pieces`` with
     ``capacity`` eligible pieces and ``n_classes`` labels (``a3d_vote_workspace_bytes``)."""
-    nbytes = L.load().a3d_vote_workspace_bytes(n, capacity, n_classes)
-    if nbytes == 0:
-        raise ValueError(f"no vote workspace for n={n} capacity={capacity} n_classes={n_classes}")
-    return torch.empty(nbytes, dtype=U8, device=device)
+    return _scratch(L.load().a3d_vote_workspace_bytes(n, capacity, n_classes), device,
+                    f"no vote workspace for n={n} capacity={capacity} n_classes={n_classes}")
 
 
 def _cosine(name, value):
@@ -723,14 +759,12 @@ def vote_settings(min_voxels, share, n_classes=256, capacity=1024):
         num, den = share
     except (TypeError, ValueError):
         raise ValueError("share must be a pair of integers (num, den)") from None
-    for name, value, lo, hi in (("min_voxels", min_voxels, 1, (1 << 31) - 1), ("share numerator", num, 1, VOTE_MAX_DEN),
-                                ("share denominator", den, 1, VOTE_MAX_DEN), ("n_classes", n_classes, 1, 256),
-                                ("capacity", capacity, 0, (1 << 31) - 1)):
-        if isinstance(value, (bool, float)) or int(value) != value or not lo <= value <= hi:
-            raise ValueError(f"{name} must be an integer in {lo} .. {hi}")
+    settings = tuple(_int_in(name, value, lo, hi) for name, value, lo, hi in (
+        ("min_voxels", min_voxels, 1, (1 << 31) - 1), ("share numerator", num, 1, VOTE_MAX_DEN),
+        ("share denominator", den, 1, VOTE_MAX_DEN), ("n_classes", n_classes, 1, 256), ("capacity", capacity, 0, (1 << 31) - 1)))
     if num > den:
         raise ValueError("share must be at most 1: num <= den")
-    return int(min_voxels), int(num), int(den), int(n_classes), int(capacity)
+    return settings
 
 
 def vote_pieces(scene, labels, piece_qv, workspace, min_voxels=8, share=(2, 3), click_rows=(), n_classes=256, capacity=1024,
@@ -755,13 +789,10 @@ def vote_pieces(scene, labels, piece_qv, workspace, min_voxels=8, share=(2, 3), 
     if n and labels_out.data_ptr() == labels.data_ptr():
         raise ValueError("labels_out may not alias labels")
     a.labels_out_dev = labels_out.data_ptr()
-    summary = _out("summary", summary, U8, (VOTE_SUMMARY.itemsize,), dev)
-    if summary.data_ptr() % 4:
-        raise ValueError("summary must be 4-byte aligned")
+    summary = _summary(summary, VOTE_SUMMARY.itemsize, dev, 4)
     a.summary_dev = summary.data_ptr()
-    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
-    if a.workspace_bytes < L.load().a3d_vote_workspace_bytes(n, a.capacity, a.n_classes) or workspace.data_ptr() % 256:
-        raise ValueError("workspace too small or not 256-byte aligned (vote_workspace(n, device, capacity, n_classes))")
+    _attach(a, workspace, dev, L.load().a3d_vote_workspace_bytes(n, a.capacity, a.n_classes),
+            "workspace too small or not 256-byte aligned (vote_workspace(n, device, capacity, n_classes))")
     L.check(L.load().a3d_vote_pieces(C.byref(a), L.stream(dev)), "a3d_vote_pieces")
     return labels_out, summary
 
@@ -779,16 +810,12 @@ GROW_MAX_COST, GROW_MAX_LIMIT = 1 << 16, 1 << 30
 def read_grow_summary(host):
     """The host copy of an ``a3d_grow_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints: ``seeds``,
     ``reached`` (voxels), ``selected`` (vertices), ``max_dist``, ``err`` (bit ``GROW_BAD_INDEX``)."""
-    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:GROW_SUMMARY.itemsize].view(GROW_SUMMARY)[0]
-    return {k: int(rec[k]) for k in ("seeds", "reached", "selected", "max_dist", "err")}
+    return _summary_ints(host, GROW_SUMMARY)
 
 
 def grow_workspace(n, device):
     """The scratch of ``grow_voxels`` for n voxels (``a3d_grow_workspace_bytes``)."""
-    nbytes = L.load().a3d_grow_workspace_bytes(n)
-    if nbytes == 0:
-        raise ValueError(f"no grow workspace for n={n}")
-    return torch.empty(nbytes, dtype=U8, device=device)
+    return _scratch(L.load().a3d_grow_workspace_bytes(n), device, f"no grow workspace for n={n}")
 
 
 def grow_settings(cost, limit, connectivity):
@@ -800,12 +827,11 @@ def grow_settings(cost, limit, connectivity):
         cost = tuple(cost)
     except TypeError:
         cost = ()
-    if len(cost) != 3 or any(isinstance(c, bool) or int(c) != c or not 1 <= c <= GROW_MAX_COST for c in cost):
-        raise ValueError(f"cost must be three integers in 1 .. {GROW_MAX_COST} (face, edge, corner)")
-    cost = tuple(int(c) for c in cost)
-    if isinstance(limit, bool) or int(limit) != limit or not 0 <= limit <= GROW_MAX_LIMIT:
-        raise ValueError(f"limit must be an integer in 0 .. {GROW_MAX_LIMIT}")
-    if int(limit) // min(cost) > GROW_MAX_STEPS:
+    three = f"cost must be three integers in 1 .. {GROW_MAX_COST} (face, edge, corner)"
+    if len(cost) != 3:
+        raise ValueError(three)
+    cost = tuple(_int_in("cost", c, 1, GROW_MAX_COST, three) for c in cost)
+    if _int_in("limit", limit, 0, GROW_MAX_LIMIT) // min(cost) > GROW_MAX_STEPS:
         raise ValueError(f"limit = {limit} is more than {GROW_MAX_STEPS} steps of cost {min(cost)}: everything connected is "
                          "what label_pieces answers")
     return cost, int(limit), connectivity
@@ -822,9 +848,7 @@ def grow_voxels(scene, n_full, keys=None, seed_qv=None, seed_full=None, inverse_
     Returns ``(dist_qv int32 [n], owner_qv int32 [n], selected_full uint8 [n_full], dist_full int32 [n_full], summary uint8
     [32], workspace)`` on the device, ``None`` for what was not wanted; ``read_grow_summary`` decodes the summary's host copy."""
     cost, limit, connectivity = grow_settings(cost, limit, connectivity)
-    if isinstance(n_full, bool) or int(n_full) != n_full or not 0 <= n_full < 1 << 31:
-        raise ValueError("n_full must be an integer in 0 .. 2^31 - 1")
-    n_full = int(n_full)
+    n_full = _int_in("n_full", n_full, 0, (1 << 31) - 1, "n_full must be an integer in 0 .. 2^31 - 1")
     if seed_qv is None and seed_full is None:
         raise ValueError("seed_qv or seed_full: one of the two seed arrays must be given")
     if n_full == 0 and (seed_full is not None or inverse_map is not None):
@@ -839,19 +863,14 @@ def grow_voxels(scene, n_full, keys=None, seed_qv=None, seed_full=None, inverse_
     a.inverse_map_dev = _ptr("inverse_map", inverse_map, I64, (n_full,), dev, optional=True)
     a.connectivity, a.limit = connectivity, limit
     a.cost[:] = cost
-    outs = []
-    for name, t, dtype, rows in (("dist_qv", dist_qv, I32, n), ("owner_qv", owner_qv, I32, n),
-                                 ("selected_full", selected_full, U8, n_full), ("dist_full", dist_full, I32, n_full)):
-        t = None if t is False else _out(name, t, dtype, (rows,), dev)
-        setattr(a, name + "_dev", t.data_ptr() if t is not None and rows else None)
-        outs.append(t)
+    outs = _wanted(a, dev, (("dist_qv", dist_qv, I32, (n,)), ("owner_qv", owner_qv, I32, (n,)),
+                            ("selected_full", selected_full, U8, (n_full,)), ("dist_full", dist_full, I32, (n_full,))))
     summary = _summary(summary, GROW_SUMMARY.itemsize, dev)
     a.summary_dev = summary.data_ptr()
     if workspace is None:
         workspace = grow_workspace(n, dev)
-    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
-    if a.workspace_bytes < L.load().a3d_grow_workspace_bytes(n) or workspace.data_ptr() % 256:
-        raise ValueError("workspace too small or not 256-byte aligned (grow_workspace(n, device))")
+    _attach(a, workspace, dev, L.load().a3d_grow_workspace_bytes(n),
+            "workspace too small or not 256-byte aligned (grow_workspace(n, device))")
     L.check(L.load().a3d_grow_voxels(C.byref(a), L.stream(dev)), "a3d_grow_voxels")
     return (*outs, summary, workspace)
 
@@ -878,12 +897,6 @@ def _power_of_two(name, value):
     return value
 
 
-def _n_classes(n_classes):
-    if int(n_classes) != n_classes or not 1 <= n_classes <= 256:
-        raise ValueError("n_classes must be an integer in 1 .. 256")
-    return int(n_classes)
-
-
 def measure_objects(xyz, labels, origin, quantum, bits=L.A3D_MEASURE_MAX_BITS, n_classes=256, labels_qv=None, faces=None,
                     area_quantum=None, records=None, err=None):
     """``a3d_measure_objects``: one record per object id 0..n_classes-1 of ``labels`` int32 [n] over the vertices ``xyz`` fp32
@@ -899,10 +912,8 @@ def measure_objects(xyz, labels, origin, quantum, bits=L.A3D_MEASURE_MAX_BITS, n
     a.xyz_dev = _ptr("xyz", xyz, F32, (None, 3), dev)
     a.n = n = xyz.shape[0]
     a.labels_dev = _ptr("labels", labels, I32, (n,), dev)
-    a.n_classes = _n_classes(n_classes)
-    if int(bits) != bits or not 0 <= bits <= L.A3D_MEASURE_MAX_BITS:
-        raise ValueError(f"bits must be an integer in 0 .. {L.A3D_MEASURE_MAX_BITS}")
-    a.bits = int(bits)
+    a.n_classes = _int_in("n_classes", n_classes, 1, 256)
+    a.bits = _int_in("bits", bits, 0, L.A3D_MEASURE_MAX_BITS)
     if n >= 1 << 31 or n << (2 * a.bits) > 1 << 62:
         raise ValueError(f"{n} vertices at bits={a.bits}: the sums could overflow (n * 2^(2 bits) <= 2^62)")
     o = np.asarray(origin, dtype=np.float64).reshape(-1)
@@ -942,7 +953,7 @@ def object_extents(xyz, labels, axes, extents=None, err=None):
     a.n = n = xyz.shape[0]
     a.labels_dev = _ptr("labels", labels, I32, (n,), dev)
     a.axes_dev = _ptr("axes", axes, F32, (None, 3, 3), dev)
-    a.n_classes = _n_classes(axes.shape[0])
+    a.n_classes = _int_in("n_classes", axes.shape[0], 1, 256)
     if n >= 1 << 31:
         raise ValueError("at most 2^31 - 1 vertices")
     extents = _out("extents", extents, F32, (a.n_classes, 3, 2), dev)
@@ -964,16 +975,12 @@ def read_normals_summary(host):
     """The host copy of an ``a3d_normals_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints:
     ``counted`` (vertices), ``valid`` / ``invalid`` (voxels with / without a normal), ``err`` (``NORMALS_RANGE``,
     ``NORMALS_BAD_INDEX``)."""
-    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:NORMALS_SUMMARY.itemsize].view(NORMALS_SUMMARY)[0]
-    return {k: int(rec[k]) for k in ("counted", "valid", "invalid", "err")}
+    return _summary_ints(host, NORMALS_SUMMARY)
 
 
 def normals_workspace(n, device):
     """The scratch of ``estimate_normals`` for n voxels (``a3d_normals_workspace_bytes``)."""
-    nbytes = L.load().a3d_normals_workspace_bytes(n)
-    if nbytes == 0:
-        raise ValueError(f"no normals workspace for n={n}")
-    return torch.empty(nbytes, dtype=U8, device=device)
+    return _scratch(L.load().a3d_normals_workspace_bytes(n), device, f"no normals workspace for n={n}")
 
 
 def _three_finite(name, values):
@@ -1001,9 +1008,7 @@ def estimate_normals(scene, xyz, origin, quantum, bits=L.A3D_MEASURE_MAX_BITS, i
     a.xyz_dev = _ptr("xyz", xyz, F32, (None, 3), dev)
     a.n_full = n_full = xyz.shape[0]
     a.inverse_map_dev = _ptr("inverse_map", inverse_map, I64, (n_full,), dev, optional=True)
-    if isinstance(bits, bool) or int(bits) != bits or not 0 <= bits <= L.A3D_MEASURE_MAX_BITS:
-        raise ValueError(f"bits must be an integer in 0 .. {L.A3D_MEASURE_MAX_BITS}")
-    a.bits = int(bits)
+    a.bits = _int_in("bits", bits, 0, L.A3D_MEASURE_MAX_BITS)
     if n_full >= 1 << 31 or n_full << (2 * a.bits) > 1 << 62:
         raise ValueError(f"{n_full} vertices at bits={a.bits}: the sums could overflow (n_full * 2^(2 bits) <= 2^62)")
     a.origin[:] = _three_finite("origin", origin)
@@ -1011,20 +1016,15 @@ def estimate_normals(scene, xyz, origin, quantum, bits=L.A3D_MEASURE_MAX_BITS, i
     a.has_viewpoint = int(viewpoint is not None)
     if viewpoint is not None:
         a.viewpoint[:] = _three_finite("viewpoint", viewpoint)
-    outs = []
-    for name, t, dtype, shape in (("normal_qv", normal_qv, F32, (n, 3)), ("variation_qv", variation_qv, F32, (n,)),
-                                  ("count_qv", count_qv, I32, (n,)), ("moments_qv", moments_qv, I64, (n, 10)),
-                                  ("normal_full", normal_full, F32, (n_full, 3))):
-        t = None if t is False else _out(name, t, dtype, shape, dev)
-        setattr(a, name + "_dev", t.data_ptr() if t is not None and shape[0] else None)
-        outs.append(t)
+    outs = _wanted(a, dev, (("normal_qv", normal_qv, F32, (n, 3)), ("variation_qv", variation_qv, F32, (n,)),
+                            ("count_qv", count_qv, I32, (n,)), ("moments_qv", moments_qv, I64, (n, 10)),
+                            ("normal_full", normal_full, F32, (n_full, 3))))
     summary = _summary(summary, NORMALS_SUMMARY.itemsize, dev)
     a.summary_dev = summary.data_ptr()
     if workspace is None:
         workspace = normals_workspace(n, dev)
-    a.workspace_dev, a.workspace_bytes = _ptr("workspace", workspace, U8, (None,), dev), workspace.shape[0]
-    if a.workspace_bytes < L.load().a3d_normals_workspace_bytes(n) or workspace.data_ptr() % 256:
-        raise ValueError("workspace too small or not 256-byte aligned (normals_workspace(n, device))")
+    _attach(a, workspace, dev, L.load().a3d_normals_workspace_bytes(n),
+            "workspace too small or not 256-byte aligned (normals_workspace(n, device))")
     L.check(L.load().a3d_estimate_normals(C.byref(a), L.stream(dev)), "a3d_estimate_normals")
     return (*outs, summary, workspace)
 
@@ -1097,22 +1097,13 @@ OVERLAY_BAD_LABEL = 1                           # the bit of the overlay summary
 def read_select_summary(host):
     """The host copy of an ``a3d_select_summary`` (uint8 [24], or anything of those bytes) as a dict of Python ints:
     ``selected``, ``in_view``, ``flags`` (bit ``SELECT_NOT_FINITE``)."""
-    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:SELECT_SUMMARY.itemsize].view(SELECT_SUMMARY)[0]
-    return {k: int(rec[k]) for k in ("selected", "in_view", "flags")}
+    return _summary_ints(host, SELECT_SUMMARY)
 
 
 def read_overlay_summary(host):
     """The host copy of an ``a3d_overlay_summary`` (uint8 [32], or anything of those bytes) as a dict of Python ints:
     ``changed``, ``overridden``, ``differing``, ``err`` (bit ``OVERLAY_BAD_LABEL``)."""
-    rec = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:OVERLAY_SUMMARY.itemsize].view(OVERLAY_SUMMARY)[0]
-    return {k: int(rec[k]) for k in ("changed", "overridden", "differing", "err")}
-
-
-def _summary(summary, nbytes, dev):
-    summary = _out("summary", summary, U8, (nbytes,), dev)
-    if summary.data_ptr() % 8:
-        raise ValueError("summary must be 8-byte aligned")
-    return summary
+    return _summary_ints(host, OVERLAY_SUMMARY)
 
 
 def camera_rows(camera):
@@ -1209,14 +1200,13 @@ def session_overlay(labels_in, manual_on, manual_obj, selected=None, op="none", 
     dev = _device("labels_in", labels_in)
     if op not in OVERLAY_OPS:
         raise ValueError(f"op must be one of {sorted(OVERLAY_OPS)}")
-    if int(obj) != obj or not 0 <= obj <= 255:
-        raise ValueError("obj must be an integer in 0 .. 255")
+    obj = _int_in("obj", obj, 0, 255)
     a = L.SessionOverlayArgs()
     a.labels_in_dev, a.n = _ptr("labels_in", labels_in, I32, (None,), dev), labels_in.shape[0]
     n = a.n
     a.manual_on_dev, a.manual_obj_dev = _ptr("manual_on", manual_on, U8, (n,), dev), _ptr("manual_obj", manual_obj, I32, (n,), dev)
     a.selected_dev = _ptr("selected", selected, U8, (n,), dev, optional=True)
-    a.op, a.obj = OVERLAY_OPS[op], int(obj)
+    a.op, a.obj = OVERLAY_OPS[op], obj
     if colors is not None:
         a.colors_full_dev = _ptr("colors", colors, F32, (n, 3), dev)
         a.palette_dev = _ptr("palette", palette, F32, (None, 3), dev)
