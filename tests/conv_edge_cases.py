@@ -12,7 +12,7 @@ import os
 import shutil
 import subprocess
 
-from conv_kit import SCENES
+from conv_kit import KVOL, SCENE_LEVELS, SCENES, level_out  # noqa: F401  (the tables' users read them from here too)
 from oracle import backbone as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,30 +22,9 @@ BLOCK_BEGIN, BLOCK_END = "// ---- planning:", "// ---- end of planning"
 
 WIDTHS_IN = [32, 64, 96, 128, 192, 256, 384]      # test_gpu_conv.py's _WIDTHS_IN x _WIDTHS_OUT
 WIDTHS_OUT = [32, 64, 96, 128, 256]
-KVOL = {"conv3": 27, "down": 8, "up": 8}
-KIND_LEVELS = [(kind, lvl) for kind in KVOL for lvl in range(5)
+KIND_LEVELS = [(kind, lvl) for kind in ("conv3", "down", "up") for lvl in range(5)
                if not (kind == "down" and lvl == 4) and not (kind == "up" and lvl == 0)]
 
-# level sizes by the CPU oracle; both test modules assert them, so that a change of make_scene or of the oracle cannot
-# silently move a case off its edge
-SCENE_LEVELS = {
-    "one": [1, 1, 1, 1, 1],
-    "line37": [37, 19, 10, 5, 3],
-    "box63": [63, 63, 62, 54, 26],
-    "box64": [64, 64, 63, 56, 25],
-    "box65": [65, 65, 65, 61, 25],
-    "box128": [128, 127, 123, 101, 27],
-    "outlier": [701, 582, 208, 28, 9],
-    "two_batch": [1800, 1721, 1198, 404, 118],
-    "s1500": [1493, 302, 40, 6, 2],
-    "box8191": [8191, 6362, 1718, 216, 27],
-    "box8192": [8192, 6328, 1714, 216, 27],
-    "g1024": [16384, 10009, 1728, 216, 27],
-    "g1025": [16385, 10054, 1728, 216, 27],
-    "s20000": [20136, 4349, 942, 184, 40],
-    "g2047": [32752],                              # level 0 only (32 -> 32 layers)
-    "g2048": [32768],
-}
 SMALL_SCENES = ["one", "line37", "box63", "box64", "box65", "box128", "outlier", "two_batch", "s1500"]
 LARGE_SCENES = ["box8191", "box8192", "g1024", "g1025", "s20000"]
 
@@ -61,10 +40,6 @@ HEAD_SCENES = ["one", "line37", "box65", "two_batch", "box8192", "s20000"]
 WL_SCENES = ["one", "line37", "box64", "g1024", "g1025", "g2047", "g2048"]      # 32 -> 32 conv3 and down at level 0
 
 
-def level_out(kind, level_in):
-    return level_in + (1 if kind == "down" else -1 if kind == "up" else 0)
-
-
 _LEVELS = {}
 
 
@@ -76,9 +51,10 @@ def oracle_levels(name):
     return _LEVELS[name]
 
 
-def op_query(levels, kind, level_in, cin, cout, mode, cin2=0, head=0):
-    """the planner's view of an op: (n_out, K, cin, cout, cin2, head_cout, up, mode)"""
-    return (levels[level_out(kind, level_in)], KVOL[kind], cin, cout, cin2, head, int(kind == "up"), mode)
+def op_query(levels, kind, level_in, cin, cout, mode, cin2=0, head=0, stats=0):
+    """the planner's view of an op: (n_out, K, cin, cout, cin2, head_cout, up, mode, stats); stats as ConvShape.stats: 0 the
+    inference build, 1 a3d_conv_bn_train_forward's, 2 a3d_conv_dgrad_bn's"""
+    return (levels[level_out(kind, level_in)], KVOL[kind], cin, cout, cin2, head, int(kind == "up"), mode, stats)
 
 
 # ---- the planner as a host program ---------------------------------------------------------------------------------
@@ -252,6 +228,42 @@ EPI_CASES = [
 ]
 
 
+# ---- rows of the training builds alone (test_gpu_conv_train_edges.py; plan_conv reads ConvShape.stats only to add LDS and to
+# forbid the fused head -- test_conv_plan_classes.py holds that -- so the tables above serve STATS = 1 and 2 as they stand)
+# 1x1 layers (A3D_OP_LINEAR, K = 1; the training path runs them with statistics): whole tiles, no hand-off, no kernel map
+LINEAR_CASES = [
+    (("box65", "linear", 0, 128, 96, 0, 1), ("sk", 1, 96, 32, 1, 0, 0, 0)),   # G 2 P 0 tiles 2
+    (("box65", "linear", 0, 128, 96, 0, 0), ("sk", 1, 96, 32, 1, 0, 0, 0)),
+    (("two_batch", "linear", 3, 384, 256, 0, 1), ("sk", 1, 128, 32, 0, 0, 0, 0)),   # G 14 P 0 tiles 7
+    (("two_batch", "linear", 3, 384, 256, 0, 0), ("sk", 1, 128, 32, 0, 0, 0, 0)),
+    (("s20000", "linear", 2, 32, 64, 0, 1), ("sk", 1, 64, 32, 0, 0, 0, 0)),   # G 15 P 0 tiles 15
+    (("s20000", "linear", 2, 32, 64, 0, 0), ("sk", 1, 64, 32, 0, 0, 0, 0)),
+    # k_conv_sk<32, 32, 0>: with a kernel map 32 -> 32 is k_conv_wl's, so only a 1x1 layer runs this build
+    (("box65", "linear", 0, 32, 32, 0, 1), ("sk", 1, 32, 32, 0, 0, 0, 0)),   # G 2 P 0 tiles 2
+    (("box65", "linear", 0, 32, 32, 0, 0), ("sk", 1, 32, 32, 0, 0, 0, 0)),
+    (("s20000", "linear", 0, 32, 32, 0, 1), ("sk", 1, 32, 32, 0, 0, 0, 0)),   # G 315 P 0 tiles 315
+    (("s20000", "linear", 0, 32, 32, 0, 0), ("sk", 1, 32, 32, 0, 0, 0, 0)),
+]
+# 63 / 64 per-block partials: below 64 blocks bn_sums_from_partials folds them with k_col_final, from 64 on with
+# k_col_final_tiles (bnorm.hip).  64-row tiles of k_conv_sk / k_conv_deep on box4032 / box4096, 16-row groups of k_conv_wl
+# on box1008 / box1024; level 0 only, not part of SMALL_SCENES / LARGE_SCENES (the reachability sweep keeps its meaning)
+TRAIN_BOX_CASES = [
+    (("box1008", "conv3", 0, 32, 32, 0, 1), ("wl", 27)),
+    (("box1008", "conv3", 0, 32, 32, 0, 0), ("wl", 27)),
+    (("box1024", "conv3", 0, 32, 32, 0, 1), ("wl", 27)),
+    (("box1024", "conv3", 0, 32, 32, 0, 0), ("wl", 27)),
+    (("box4032", "conv3", 0, 32, 64, 0, 1), ("deep", 27, 32, 32, 3, 1, 1)),   # G 504 P 4 tiles 63
+    (("box4032", "conv3", 0, 32, 64, 0, 0), ("sk", 27, 64, 32, 0, 1, 0, 0)),   # G 252 P 0 tiles 63
+    (("box4032", "conv3", 0, 96, 96, 0, 1), ("deep", 27, 32, 32, 3, 1, 1)),   # G 378 P 2 tiles 63
+    (("box4032", "conv3", 0, 96, 96, 0, 0), ("sk", 27, 96, 32, 1, 1, 0, 0)),   # G 330 P 0 tiles 63
+    (("box4096", "conv3", 0, 32, 64, 0, 1), ("deep", 27, 32, 32, 3, 1, 1)),   # G 512 P 4 tiles 64
+    (("box4096", "conv3", 0, 32, 64, 0, 0), ("sk", 27, 64, 32, 0, 1, 0, 0)),   # G 256 P 0 tiles 64
+    (("box4096", "conv3", 0, 96, 96, 0, 1), ("deep", 27, 32, 32, 3, 1, 1)),   # G 384 P 2 tiles 64
+    (("box4096", "conv3", 0, 96, 96, 0, 0), ("sk", 27, 96, 32, 1, 1, 0, 0)),   # G 336 P 0 tiles 64
+]
+TRAIN_CASES = LINEAR_CASES + TRAIN_BOX_CASES
+
+
 def small_sweep_rows():
     """(scene, kind, level_in, cin, cout, 0, mode): the full width sets on every small scene"""
     return [(name, kind, lvl, ci, co, 0, mode) for name in SMALL_SCENES for mode in (1, 0) for kind, lvl in KIND_LEVELS
@@ -273,9 +285,9 @@ def head_rows():
     return [((name, "conv3", 0, ci, co, 0, mode), h) for name in HEAD_SCENES for mode in (1, 0) for ci, co, h in HEAD_SHAPES]
 
 
-def row_query(row, head=0):
+def row_query(row, head=0, stats=0):
     name, kind, level_in, cin, cout, cin2, mode = row
-    return op_query(oracle_levels(name), kind, level_in, cin, cout, mode, cin2, head)
+    return op_query(oracle_levels(name), kind, level_in, cin, cout, mode, cin2, head, stats)
 
 
 def all_case_queries():

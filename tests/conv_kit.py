@@ -1,11 +1,14 @@
-"""Scenes and references shared by the exact sparse-convolution tests (test_gpu_wgrad_edges.py, test_gpu_conv_edges.py) and the
-CPU-side plan-class test: named scenes, the World of a scene (oracle levels, row maps both ways, internal-row pair lists
-from the CPU oracle's kernel maps) and seeded integer operands.  The coordinate builders need no GPU; a World does."""
+"""Scenes and references shared by the exact sparse-convolution tests (test_gpu_wgrad_edges.py, test_gpu_conv_edges.py,
+test_gpu_conv_train_edges.py) and the CPU-side plan-class test: named scenes, the World of a scene (oracle levels, row maps
+both ways, internal-row pair lists from the CPU oracle's kernel maps), seeded integer operands, and what the two forward
+modules share (reference, bit equality, profile entries).  The coordinate builders need no GPU; a World does."""
 import zlib
 
 import numpy as np
+import pytest
 import torch
 
+from agile3d_amd import lib as L
 from agile3d_amd.engine import Scene
 from agile3d_amd.synthetic import make_scene
 from gpu_util import _random_coords, internal_to_oracle_rows, scratch  # noqa: F401  (scratch: the NaN-poisoned workspace)
@@ -43,7 +46,45 @@ SCENES = {
     "box8192": lambda: _box(8192, 8192),
     "g2047": lambda: _box(32752, 2047),
     "g2048": lambda: _box(32768, 2048),
+    # the training builds' edges (test_gpu_conv_train_edges.py): 63 / 64 per-tile partials (64-row tiles) and 63 / 64
+    # per-group partials (16-row groups of k_conv_wl) -- where bn_sums_from_partials changes its kernel
+    "box4032": lambda: _box(4032, 4032),
+    "box4096": lambda: _box(4096, 4096),
+    "box1008": lambda: _box(1008, 1008),
+    "box1024": lambda: _box(1024, 1024),
 }
+
+
+# level sizes by the CPU oracle; both test modules assert them, so that a change of make_scene or of the oracle cannot
+# silently move a case off its edge
+SCENE_LEVELS = {
+    "one": [1, 1, 1, 1, 1],
+    "line37": [37, 19, 10, 5, 3],
+    "box63": [63, 63, 62, 54, 26],
+    "box64": [64, 64, 63, 56, 25],
+    "box65": [65, 65, 65, 61, 25],
+    "box128": [128, 127, 123, 101, 27],
+    "outlier": [701, 582, 208, 28, 9],
+    "two_batch": [1800, 1721, 1198, 404, 118],
+    "s1500": [1493, 302, 40, 6, 2],
+    "box8191": [8191, 6362, 1718, 216, 27],
+    "box8192": [8192, 6328, 1714, 216, 27],
+    "g1024": [16384, 10009, 1728, 216, 27],
+    "g1025": [16385, 10054, 1728, 216, 27],
+    "s20000": [20136, 4349, 942, 184, 40],
+    "g2047": [32752],                              # level 0 only (32 -> 32 layers)
+    "g2048": [32768],
+    "box4032": [4032],                             # level 0 only: 63 / 64 tiles of 64 rows, 63 / 64 groups of 16 rows
+    "box4096": [4096],                             # (the training builds' per-block partials, TRAIN_BOX_CASES)
+    "box1008": [1008],
+    "box1024": [1024],
+}
+
+KVOL = {"conv3": 27, "down": 8, "up": 8, "linear": 1}      # linear: A3D_OP_LINEAR, the rows of LINEAR_CASES only
+
+
+def level_out(kind, level_in):
+    return level_in + (1 if kind == "down" else -1 if kind == "up" else 0)
 
 
 class World:
@@ -107,3 +148,103 @@ def _ints(shape, lo, hi, *seed):
     """integers in [lo, hi] as float32 on the device, from a generator seeded by the case"""
     g = torch.Generator().manual_seed(zlib.crc32(repr(seed).encode()))
     return torch.randint(lo, hi + 1, shape, generator=g).float().cuda()
+
+
+# ---- shared by the exact forward modules (test_gpu_conv_edges.py: the inference builds, test_gpu_conv_train_edges.py: the
+# training builds): the a3d_conv_deep_mode fixture, case-table worlds and operands, the float64 reference, bit equality, the
+# profile entry of a launch against its declared plan class.
+KINDS = {"conv3": L.OP_CONV3, "down": L.OP_DOWN, "up": L.OP_UP, "linear": L.OP_LINEAR}
+
+
+@pytest.fixture(params=[1, 0], ids=["deep", "streamk"])
+def mode(request):
+    """a3d_conv_deep_mode: with the small-level kernel (k_conv_deep takes what its cost model allows) and without."""
+    lib = L.load()
+    before = lib.a3d_conv_deep_mode(request.param)
+    yield request.param
+    lib.a3d_conv_deep_mode(before)
+
+
+def _set_mode(m):
+    return L.load().a3d_conv_deep_mode(m)
+
+
+def _world(name):
+    w = world(name)
+    want = SCENE_LEVELS[name]
+    assert w.sc.n[:len(want)] == want and [w.lv.n(i) for i in range(len(want))] == want, (name, w.sc.n)
+    if name == "outlier":
+        assert w.sc.grid_dims is None                                 # level 0 on the hash table
+    return w
+
+
+def _rows(w, kind, level_in):
+    return w.sc.n[level_in], w.sc.n[level_out(kind, level_in)]
+
+
+def _conv_ref(pairs, x64, w64, n_out):
+    """sum_k index_add(out rows_k, x[in rows_k] @ W[k]) in float64 on the device"""
+    ref = torch.zeros(n_out, w64.shape[2], dtype=torch.float64, device="cuda")
+    for k, (ri, ro) in enumerate(pairs):
+        if len(ri):
+            ref.index_add_(0, ro, x64[ri] @ w64[k])
+    return ref
+
+
+def _assert_bits(got, ref64, where):
+    """got (fp32) == the float64 reference cast to fp32, element for element"""
+    ref = ref64.float()
+    assert (ref.double() == ref64).all(), (where, "the reference left the exact range")
+    if torch.equal(got, ref):
+        return
+    bad = got != ref                                # NaN differs from everything
+    r, c = (int(v) for v in bad.nonzero()[0])
+    rows = bad.any(1).nonzero().flatten()
+    pytest.fail(f"{where}: out[{r}, {c}] = {got[r, c].item()!r}, expected {ref[r, c].item()!r}; {int(bad.sum())} elements differ "
+                f"in {len(rows)} rows ({rows[:8].tolist()} ...), columns {bad.any(0).nonzero().flatten()[:8].tolist()} ...")
+
+
+def _with_zero_row(t):
+    return torch.cat([t, torch.zeros(1, t.shape[1], device="cuda")])
+
+
+def _row_id(row):
+    name, kind, level_in, cin, cout, cin2, m = row
+    return f"{name}-{kind}-L{level_in}-{cin}-{cout}" + (f"+{cin2}" if cin2 else "") + ("-deep" if m else "-streamk")
+
+
+def _operands(w, kind, level_in, cin, cout, tag, lo=-3, hi=3):
+    n_in, n_out = _rows(w, kind, level_in)
+    x = _with_zero_row(_ints((n_in, cin), lo, hi, w.name, kind, level_in, cin, tag, "x"))
+    W = _ints((KVOL[kind], cin, cout), lo, hi, w.name, kind, level_in, cin, cout, tag, "w")
+    ref = _conv_ref(w.pairs(kind, level_in), x.double(), W.double(), n_out)
+    return x, W, ref
+
+
+def _profiled(run):
+    """the spconv profile entries of the launches inside run()"""
+    lib = L.load()
+    lib.a3d_profile_read(None, 0)
+    lib.a3d_profile_enable(1)
+    try:
+        out = run()
+        torch.cuda.synchronize()
+    finally:
+        lib.a3d_profile_enable(0)
+    buf = (L.ProfEntry * 64)()
+    n = lib.a3d_profile_read(buf, 64)
+    assert n >= 0, lib.a3d_last_error().decode()
+    return out, [(buf[i].bn, buf[i].ksplit, buf[i].kernel_volume & 255, buf[i].cin, buf[i].cout, buf[i].n_out) for i in range(n)
+                 if buf[i].id == 0]
+
+
+def _assert_ran_its_class(entries, cls, K, cin, cout, n_out, where):
+    """the profile entry carries the small-level kernel (column field >= 1000) or not, the column width, the stage width"""
+    assert len(entries) == 1, (where, entries)
+    if cls[0] == "wl":
+        want = (cout, 0)                                             # stage width 0: k_conv_wl
+    elif cls[0] == "deep":
+        want = (1000 + cls[2], cls[3])
+    else:
+        want = (cls[2], cls[3])
+    assert entries[0] == want + (K, cin, cout, n_out), (where, cls, entries[0])

@@ -31,65 +31,13 @@ import torch
 import conv_edge_cases as E
 from agile3d_amd import lib as L
 from agile3d_amd.lib import ptr as _ptr, stream as _stream
-from conv_kit import _ints, scratch, world
+from conv_kit import (KINDS, _assert_bits, _assert_ran_its_class, _conv_ref, _ints, _operands, _profiled, _row_id, _rows, _set_mode,
+                      _with_zero_row, _world, mode, scratch)  # noqa: F401  (mode: the a3d_conv_deep_mode fixture)
 from gpu_util import pack_weight
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
-KINDS = {"conv3": L.OP_CONV3, "down": L.OP_DOWN, "up": L.OP_UP}
-
-
-@pytest.fixture(params=[1, 0], ids=["deep", "streamk"])
-def mode(request):
-    """a3d_conv_deep_mode: with the small-level kernel (k_conv_deep takes what its cost model allows) and without."""
-    lib = L.load()
-    before = lib.a3d_conv_deep_mode(request.param)
-    yield request.param
-    lib.a3d_conv_deep_mode(before)
-
-
-def _set_mode(m):
-    return L.load().a3d_conv_deep_mode(m)
-
-
-def _world(name):
-    w = world(name)
-    want = E.SCENE_LEVELS[name]
-    assert w.sc.n[:len(want)] == want and [w.lv.n(i) for i in range(len(want))] == want, (name, w.sc.n)
-    if name == "outlier":
-        assert w.sc.grid_dims is None                                 # level 0 on the hash table
-    return w
-
-
-def _rows(w, kind, level_in):
-    return w.sc.n[level_in], w.sc.n[E.level_out(kind, level_in)]
-
-
-def _conv_ref(pairs, x64, w64, n_out):
-    """sum_k index_add(out rows_k, x[in rows_k] @ W[k]) in float64 on the device"""
-    ref = torch.zeros(n_out, w64.shape[2], dtype=torch.float64, device="cuda")
-    for k, (ri, ro) in enumerate(pairs):
-        if len(ri):
-            ref.index_add_(0, ro, x64[ri] @ w64[k])
-    return ref
-
-
-def _assert_bits(got, ref64, where):
-    """got (fp32) == the float64 reference cast to fp32, element for element"""
-    ref = ref64.float()
-    assert (ref.double() == ref64).all(), (where, "the reference left the exact range")
-    if torch.equal(got, ref):
-        return
-    bad = got != ref                                # NaN differs from everything
-    r, c = (int(v) for v in bad.nonzero()[0])
-    rows = bad.any(1).nonzero().flatten()
-    pytest.fail(f"{where}: out[{r}, {c}] = {got[r, c].item()!r}, expected {ref[r, c].item()!r}; {int(bad.sum())} elements differ "
-                f"in {len(rows)} rows ({rows[:8].tolist()} ...), columns {bad.any(0).nonzero().flatten()[:8].tolist()} ...")
-
-
-def _with_zero_row(t):
-    return torch.cat([t, torch.zeros(1, t.shape[1], device="cuda")])
 
 
 def _conv_apply(sc, kind, level_in, x, cin, cout, wp, n_out):
@@ -169,19 +117,6 @@ def test_small_scenes_every_width_pair(mode, name, kind, level_in):
 # ----------------------------------------------------------------------------------------------------------------------
 # 2. large scenes: one row per plan class
 # ----------------------------------------------------------------------------------------------------------------------
-def _row_id(row):
-    name, kind, level_in, cin, cout, cin2, m = row
-    return f"{name}-{kind}-L{level_in}-{cin}-{cout}" + (f"+{cin2}" if cin2 else "") + ("-deep" if m else "-streamk")
-
-
-def _operands(w, kind, level_in, cin, cout, tag):
-    n_in, n_out = _rows(w, kind, level_in)
-    x = _with_zero_row(_ints((n_in, cin), -3, 3, w.name, kind, level_in, cin, tag, "x"))
-    W = _ints((E.KVOL[kind], cin, cout), -3, 3, w.name, kind, level_in, cin, cout, tag, "w")
-    ref = _conv_ref(w.pairs(kind, level_in), x.double(), W.double(), n_out)
-    return x, W, ref
-
-
 @pytest.mark.parametrize("row,cls", E.LARGE_CASES, ids=[_row_id(r) for r, _ in E.LARGE_CASES])
 def test_large_scene_plan_classes(row, cls):
     """One a3d_conv_apply per row of the case table; the class next to the row is what the planner gives it
