@@ -51,6 +51,30 @@ def click_lists(click_idx):
     return np.array(rows, dtype=np.int32), np.array(objs, dtype=np.int32)
 
 
+def query_list(click_idx, click_time_idx):
+    """One sample's click dictionaries (keys ``"0".."K"``: voxel rows / click times per object, 0 = background) as the
+    decoder's query list (agile3d.py:201-240): ``(fg_rows, fg_times, counts, bg_rows, bg_times)`` -- the clicks of objects
+    1..K in object order as Python ints, how many each object has, and the background's.  The inference decoder
+    (``Engine.forward_mask``) and the training tape (``DecoderTape``) both order their queries this way; one pass over the
+    clicks.  ``ValueError``: a key is missing, rows and times do not pair up, or an object >= 1 has no click."""
+    K = len(click_idx) - 1
+    fg_rows, fg_times, counts = [], [], []
+    for o in list(range(1, K + 1)) + [0]:
+        try:
+            r, t = click_idx[str(o)], click_time_idx[str(o)]
+        except KeyError:
+            raise ValueError(f'click_idx and click_time_idx need the keys "0" .. "{K}" (no "{o}")') from None
+        if len(r) != len(t):
+            raise ValueError("click_idx / click_time_idx length mismatch")
+        if o == 0:
+            return fg_rows, fg_times, counts, [int(v) for v in r], [int(v) for v in t]
+        if len(r) == 0:    # an empty group has no maximum
+            raise ValueError(f"object {o} has no click (the reference fails on an empty max, agile3d.py:353)")
+        fg_rows.extend(map(int, r))
+        fg_times.extend(map(int, t))
+        counts.append(len(r))
+
+
 def _logits(logits):
     logits = logits.contiguous()
     if logits.dtype != torch.float32 or not logits.is_cuda or logits.dim() != 2:

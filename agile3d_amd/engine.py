@@ -14,15 +14,16 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import lib as L
+from .clicks import query_list
+from .modules import walk_res16unet34c
 from .sparse import SparseTensor
-
-BN_EPS = 1e-5
-_ptr, _stream = L.ptr, L.stream      # DEPRECATED, no caller in this repository: tests written before lib.ptr / lib.stream import them
+from .train_backbone import BackboneTape, packed_weights_of
 
 
 class Scene:
@@ -131,150 +132,137 @@ class _Pool:
         self.free.setdefault(self.descs[i], []).append(i)
 
 
+# what the walk of the topology passes around: ``ch`` columns from ``coff`` of pool buffer ``buf`` (``temp``: back to the pool
+# once the layer that reads it ran).  A concatenation's buffer goes around as its skip half: the columns from c_up = ``coff``
+_Act = namedtuple("_Act", "buf coff ch level temp")
+
+
 class BackboneProgram:
-    """Res16UNet34C + lin_squeeze_head as a list of ``a3d_op`` (built once per weight version)."""
+    """Res16UNet34C + lin_squeeze_head as a list of ``a3d_op`` (built once per weight version): a builder of
+    ``modules.walk_res16unet34c``, which states the topology."""
 
     def __init__(self, model, device, fuse_proj=None):
-        lib = L.load()
         self.keep = []          # tensors referenced by raw pointers
         self.ops = []
         self.pool = _Pool()
-        self.fm_bufs = []       # buffer ids of the 5 feature maps (res16unet.py:250-290)
-        bb = model.backbone
-        dev = device
-
+        self.dev = device
         # the residual projections (BasicBlock.downsample) run inside the block's second conv (a3d_op.proj_*);
         # A3D_FUSE_PROJ=0 keeps the separate 1x1 launches (tests compare the two)
-        fuse_proj = os.environ.get("A3D_FUSE_PROJ", "1") != "0" if fuse_proj is None else fuse_proj
+        self.fuse_proj = os.environ.get("A3D_FUSE_PROJ", "1") != "0" if fuse_proj is None else fuse_proj
         self.fused_projections = 0
+        self.fm_bufs = [x.buf for x in walk_res16unet34c(model.backbone, model.lin_squeeze_head, self)]    # buffers of the 5 feature maps
+        self.n_ops = len(self.ops)
+        self.ops_arr = (L.Op * self.n_ops)(*self.ops)
+        self.n_bufs = len(self.pool.descs)
+        self.bufs_arr = (L.BufDesc * self.n_bufs)(*[L.BufDesc(lv, ch) for lv, ch in self.pool.descs])
 
-        def pack(conv, w=None):
-            w = (conv.kernel3().detach() if w is None else w).to(dev, torch.float32).contiguous()
-            K, cin, cout = w.shape
-            out = torch.empty(lib.a3d_conv_weight_packed_floats(K, cin, cout), dtype=torch.float32, device=dev)
-            L.check(lib.a3d_pack_conv_weight(L.ptr(w), K, cin, cout, L.ptr(out), L.stream()), "a3d_pack_conv_weight")
-            self.keep.append(out)
-            return out
+    def _pack(self, conv, w=None):
+        lib = L.load()
+        w = (conv.kernel3().detach() if w is None else w).to(self.dev, torch.float32).contiguous()
+        K, cin, cout = w.shape
+        out = torch.empty(lib.a3d_conv_weight_packed_floats(K, cin, cout), dtype=torch.float32, device=self.dev)
+        L.check(lib.a3d_pack_conv_weight(L.ptr(w), K, cin, cout, L.ptr(out), L.stream()), "a3d_pack_conv_weight")
+        self.keep.append(out)
+        return out
 
-        def fold(bn):
-            b = bn.bn
-            scale = (b.weight.detach() / torch.sqrt(b.running_var.detach() + b.eps)).to(dev, torch.float32)
-            shift = (b.bias.detach() - b.running_mean.detach() * scale.to(b.bias.device)).to(dev, torch.float32)
-            scale, shift = scale.contiguous(), shift.contiguous()
-            self.keep += [scale, shift]
-            return scale, shift
+    def _fold(self, bn):
+        b = bn.bn
+        scale = (b.weight.detach() / torch.sqrt(b.running_var.detach() + b.eps)).to(self.dev, torch.float32)
+        shift = (b.bias.detach() - b.running_mean.detach() * scale.to(b.bias.device)).to(self.dev, torch.float32)
+        scale, shift = scale.contiguous(), shift.contiguous()
+        self.keep += [scale, shift]
+        return scale, shift
 
-        def op(kind, level_in, cin, cout, src, dst, res, relu, kvol, w, scale, shift, proj=None):
-            o = L.Op()
-            o.kind, o.level_in, o.cin, o.cout = kind, level_in, cin, cout
-            o.in_buf, o.in_coff = src
-            o.out_buf, o.out_coff = dst
-            o.res_buf, o.res_coff = res if res is not None else (L.BUF_NONE, 0)
-            o.relu, o.kernel_volume = int(relu), kvol
-            o.w_dev = w.data_ptr()
-            o.scale_dev = scale.data_ptr() if scale is not None else None
-            o.shift_dev = shift.data_ptr() if shift is not None else None
-            if proj is not None:
-                (o.proj_buf, o.proj_coff), o.proj_cin = proj[0], proj[1]
-            self.ops.append(o)
+    def _op(self, kind, level_in, cin, cout, src, dst, res, relu, kvol, w, scale, shift, proj=None):
+        o = L.Op()
+        o.kind, o.level_in, o.cin, o.cout = kind, level_in, cin, cout
+        o.in_buf, o.in_coff = src
+        o.out_buf, o.out_coff = dst
+        o.res_buf, o.res_coff = res if res is not None else (L.BUF_NONE, 0)
+        o.relu, o.kernel_volume = int(relu), kvol
+        o.w_dev = w.data_ptr()
+        o.scale_dev = scale.data_ptr() if scale is not None else None
+        o.shift_dev = shift.data_ptr() if shift is not None else None
+        if proj is not None:
+            (o.proj_buf, o.proj_coff), o.proj_cin = proj[0], proj[1]
+        self.ops.append(o)
 
-        def basic_block(blk, level, src, cin, cout, dst):
-            """BasicBlock.forward (resnet_block.py:48-64); src/dst = (buffer, column offset)."""
-            tmp = self.pool.get(level, cout)
-            s1, h1 = fold(blk.norm1)
-            op(L.OP_CONV3, level, cin, cout, src, (tmp, 0), None, True, 27, pack(blk.conv1), s1, h1)
-            res, proj = src, None
-            if blk.downsample is not None and fuse_proj and cin % 32 == 0:
-                # out = relu(s2 conv2(h) + h2 + sp (x Wp) + hp): both scales into the weights, one accumulator, one launch.
-                # (the kernel's stage width at these shapes is 32 or 64 channels; the 32 -> 64 block of level 2 runs its
-                # 64 -> 64 conv with 32-channel stages so that its 32-channel projection is a whole stage: all seven fused)
-                s2, h2 = fold(blk.norm2)
-                sp, hp = fold(blk.downsample[1])
-                w2 = blk.conv2.kernel3().detach().to(dev, torch.float32) * s2[None, None, :]
-                wp = blk.downsample[0].kernel3().detach().to(dev, torch.float32) * sp[None, None, :]
-                both = torch.cat([pack(None, w2), pack(None, wp)]).contiguous()
-                shift = (h2 + hp).contiguous()
-                self.keep += [both, shift]
-                op(L.OP_CONV3, level, cout, cout, (tmp, 0), dst, None, True, 27, both, None, shift, proj=(src, cin))
-                self.fused_projections += 1
-                self.pool.put(tmp)
-                return
-            if blk.downsample is not None:
-                proj = self.pool.get(level, cout)
-                sp, hp = fold(blk.downsample[1])
-                op(L.OP_LINEAR, level, cin, cout, src, (proj, 0), None, False, 1, pack(blk.downsample[0]), sp, hp)
-                res = (proj, 0)
-            s2, h2 = fold(blk.norm2)
-            op(L.OP_CONV3, level, cout, cout, (tmp, 0), dst, res, True, 27, pack(blk.conv2), s2, h2)
+    def _basic_block(self, blk, level, src, cin, cout, dst):
+        """BasicBlock.forward (resnet_block.py:48-64); src/dst = (buffer, column offset)."""
+        tmp = self.pool.get(level, cout)
+        s1, h1 = self._fold(blk.norm1)
+        self._op(L.OP_CONV3, level, cin, cout, src, (tmp, 0), None, True, 27, self._pack(blk.conv1), s1, h1)
+        res, proj = src, None
+        if blk.downsample is not None and self.fuse_proj and cin % 32 == 0:
+            # out = relu(s2 conv2(h) + h2 + sp (x Wp) + hp): both scales into the weights, one accumulator, one launch.
+            # (the kernel's stage width at these shapes is 32 or 64 channels; the 32 -> 64 block of level 2 runs its
+            # 64 -> 64 conv with 32-channel stages so that its 32-channel projection is a whole stage: all seven fused)
+            s2, h2 = self._fold(blk.norm2)
+            sp, hp = self._fold(blk.downsample[1])
+            w2 = blk.conv2.kernel3().detach().to(self.dev, torch.float32) * s2[None, None, :]
+            wp = blk.downsample[0].kernel3().detach().to(self.dev, torch.float32) * sp[None, None, :]
+            both = torch.cat([self._pack(None, w2), self._pack(None, wp)]).contiguous()
+            shift = (h2 + hp).contiguous()
+            self.keep += [both, shift]
+            self._op(L.OP_CONV3, level, cout, cout, (tmp, 0), dst, None, True, 27, both, None, shift, proj=(src, cin))
+            self.fused_projections += 1
             self.pool.put(tmp)
-            if proj is not None:
-                self.pool.put(proj)
+            return
+        if blk.downsample is not None:
+            proj = self.pool.get(level, cout)
+            sp, hp = self._fold(blk.downsample[1])
+            self._op(L.OP_LINEAR, level, cin, cout, src, (proj, 0), None, False, 1, self._pack(blk.downsample[0]), sp, hp)
+            res = (proj, 0)
+        s2, h2 = self._fold(blk.norm2)
+        self._op(L.OP_CONV3, level, cout, cout, (tmp, 0), dst, res, True, 27, self._pack(blk.conv2), s2, h2)
+        self.pool.put(tmp)
+        if proj is not None:
+            self.pool.put(proj)
 
-        def layer(blocks, level, src, cin, cout, dst, free_src):
-            """_make_layer's Sequential of BasicBlocks; the last block writes to dst."""
-            cur, cur_c, owned = src, cin, free_src
-            n = len(blocks)
-            for i, blk in enumerate(blocks):
-                if i == n - 1:
-                    out = dst
-                else:
-                    out = (self.pool.get(level, cout), 0)
-                basic_block(blk, level, cur, cur_c, cout, out)
-                if owned:
-                    self.pool.put(cur[0])
-                cur, cur_c, owned = out, cout, (i != n - 1)
+    def _unit(self, kind, conv, bn, x, y):
+        """Strided / transposed conv + BatchNorm + ReLU from the activation ``x`` into ``y``."""
+        s, h = self._fold(bn)
+        self._op(kind, x.level, conv.cin, conv.cout, x[:2], y[:2], None, True, 8, self._pack(conv), s, h)
+        return y
 
-        P = bb.PLANES
-        # concat buffers: [upsampled | skip] -- me.cat(out, skip) puts the skip LAST (res16unet.py:257)
-        cat8 = self.pool.get(0, P[7] + 32)
-        cat7 = self.pool.get(1, P[6] + P[0])
-        cat6 = self.pool.get(2, P[5] + P[1])
-        cat5 = self.pool.get(3, P[4] + P[2])
-        s, h = fold(bb.bn0)
-        w0 = bb.conv0p1s1.kernel3().detach().to(dev, torch.float32).contiguous()
+    # ---------------------------------------------------------------- the builder's verbs (modules.walk_res16unet34c)
+    def concat_buffer(self, level, c_up, c_skip):
+        return _Act(self.pool.get(level, c_up + c_skip), c_up, c_skip, level, False)
+
+    def stem(self, conv, bn, cat):
+        s, h = self._fold(bn)
+        w0 = conv.kernel3().detach().to(self.dev, torch.float32).contiguous()
         self.keep.append(w0)
-        op(L.OP_STEM, 0, 3, 32, (L.BUF_NONE, 0), (cat8, P[7]), None, True, w0.shape[0], w0, s, h)
+        self._op(L.OP_STEM, 0, conv.cin, conv.cout, (L.BUF_NONE, 0), cat[:2], None, True, w0.shape[0], w0, s, h)
+        return cat
 
-        def down(conv, bn, level, src, c):
-            dst = self.pool.get(level + 1, c)
-            sc, sh = fold(bn)
-            op(L.OP_DOWN, level, c, c, src, (dst, 0), None, True, 8, pack(conv), sc, sh)
-            return dst
+    def down(self, conv, bn, x):
+        return self._unit(L.OP_DOWN, conv, bn, x, _Act(self.pool.get(x.level + 1, conv.cout), 0, conv.cout, x.level + 1, True))
 
-        x = down(bb.conv1p1s2, bb.bn1, 0, (cat8, P[7]), 32)
-        layer(bb.block1, 1, (x, 0), 32, P[0], (cat7, P[6]), True)
-        x = down(bb.conv2p2s2, bb.bn2, 1, (cat7, P[6]), P[0])
-        layer(bb.block2, 2, (x, 0), P[0], P[1], (cat6, P[5]), True)
-        x = down(bb.conv3p4s2, bb.bn3, 2, (cat6, P[5]), P[1])
-        layer(bb.block3, 3, (x, 0), P[1], P[2], (cat5, P[4]), True)
-        x = down(bb.conv4p8s2, bb.bn4, 3, (cat5, P[4]), P[2])
-        f0 = self.pool.get(4, P[3])
-        layer(bb.block4, 4, (x, 0), P[2], P[3], (f0, 0), True)
+    def layer(self, blocks, x, skip_of=None):
+        cout = blocks[-1].conv2.cout
+        out = skip_of if skip_of is not None else _Act(self.pool.get(x.level, cout), 0, cout, x.level, False)
+        for i, blk in enumerate(blocks):
+            y = out if i == len(blocks) - 1 else _Act(self.pool.get(x.level, cout), 0, cout, x.level, True)
+            self._basic_block(blk, x.level, x[:2], x.ch, cout, y[:2])
+            if x.temp:
+                self.pool.put(x.buf)
+            x = y
+        return out
 
-        def up(conv, bn, level_in, src, cin, dst, cout):
-            sc, sh = fold(bn)
-            op(L.OP_UP, level_in, cin, cout, src, dst, None, True, 8, pack(conv), sc, sh)
+    def up(self, conv, bn, x, cat):
+        self._unit(L.OP_UP, conv, bn, x, cat._replace(coff=0))
 
-        up(bb.convtr4p16s2, bb.bntr4, 4, (f0, 0), P[3], (cat5, 0), P[4])
-        f1 = self.pool.get(3, P[4])
-        layer(bb.block5, 3, (cat5, 0), P[4] + P[2], P[4], (f1, 0), False)
-        up(bb.convtr5p8s2, bb.bntr5, 3, (f1, 0), P[4], (cat6, 0), P[5])
-        f2 = self.pool.get(2, P[5])
-        layer(bb.block6, 2, (cat6, 0), P[5] + P[1], P[5], (f2, 0), False)
-        up(bb.convtr6p4s2, bb.bntr6, 2, (f2, 0), P[5], (cat7, 0), P[6])
-        f3 = self.pool.get(1, P[6])
-        layer(bb.block7, 1, (cat7, 0), P[6] + P[0], P[6], (f3, 0), False)
-        up(bb.convtr7p2s2, bb.bntr7, 1, (f3, 0), P[6], (cat8, 0), P[7])
-        f4 = self.pool.get(0, P[7])
-        layer(bb.block8, 0, (cat8, 0), P[7] + 32, P[7], (f4, 0), False)
-        self.fm_bufs = [f0, f1, f2, f3, f4]
-        # lin_squeeze_head: 1x1 conv + bias into the caller-ordered output (agile3d.py:179)
-        head = model.lin_squeeze_head
-        hb = head.bias.detach().reshape(-1).to(dev, torch.float32).contiguous()
+    def concat(self, cat):
+        return _Act(cat.buf, 0, cat.coff + cat.ch, cat.level, False)
+
+    def head(self, head, x):
+        """lin_squeeze_head: 1x1 conv + bias into the caller-ordered output (agile3d.py:179)."""
+        hb = head.bias.detach().reshape(-1).to(self.dev, torch.float32).contiguous()
         self.keep.append(hb)
-        hw = pack(head)
+        hw = self._pack(head)
         last = self.ops[-1]                   # block8's last conv: its workgroups hold complete 96-column output rows
-        if (os.environ.get("A3D_FUSE_HEAD", "0") == "1" and last.kind == L.OP_CONV3 and last.out_buf == f4
+        if (os.environ.get("A3D_FUSE_HEAD", "0") == "1" and last.kind == L.OP_CONV3 and last.out_buf == x.buf
                 and last.proj_cin == 0):
             # lin_squeeze_head as a second GEMM in that conv's epilogue (SURVEY 2.1's second fusion): the [N, 96] rows are
             # not read back, one launch less.  The library runs the head as its own 1x1 launch where no fused build exists.
@@ -282,16 +270,11 @@ class BackboneProgram:
             # batch against 2 190 + 336 for conv + k_dense (four workgroups per CU each stream the 48 KB head weights through
             # the CU's L1 for every 64-row tile), 640-643 vs 643-646 scenes/s; one scene: 208 vs 172 + 33 us
             # (profiles/r05_experiments.txt).  The separate launch stays the default.
-            last.head_w_dev, last.head_bias_dev, last.head_cout = hw.data_ptr(), hb.data_ptr(), model.mask_dim
+            last.head_w_dev, last.head_bias_dev, last.head_cout = hw.data_ptr(), hb.data_ptr(), head.cout
             self.fused_head = True
         else:
-            op(L.OP_LINEAR, 0, P[7], model.mask_dim, (f4, 0), (L.BUF_EXT_OUT, 0), None, False, 1, hw, None, hb)
+            self._op(L.OP_LINEAR, 0, x.ch, head.cout, x[:2], (L.BUF_EXT_OUT, 0), None, False, 1, hw, None, hb)
             self.fused_head = False
-
-        self.n_ops = len(self.ops)
-        self.ops_arr = (L.Op * self.n_ops)(*self.ops)
-        self.n_bufs = len(self.pool.descs)
-        self.bufs_arr = (L.BufDesc * self.n_bufs)(*[L.BufDesc(lv, ch) for lv, ch in self.pool.descs])
 
     def run(self, scene: Scene, feats: torch.Tensor, out: torch.Tensor):
         lib = L.load()
@@ -414,7 +397,6 @@ def _kv_cache_mb():
     """Cap of the per-scene key / value cache of forward_mask in MB (A3D_KV_CACHE_MB, default 4096; 0 = off)."""
     global _KV_MB
     if _KV_MB is None:
-        import os
         _KV_MB = int(os.environ.get("A3D_KV_CACHE_MB", "4096"))
     return _KV_MB
 
@@ -422,19 +404,23 @@ def _kv_cache_mb():
 class _SceneState:
     """Everything forward_mask needs from forward_backbone; rides on the returned pcd_features."""
 
-    def __init__(self):
-        self.scene = None
-        self.ws = None
-        self.ranges = None
-        self.posenc = None      # list[Tensor [n_b,128]]
-        self.minmax = None      # list[Tensor [6]]
-        self.engine_id = None
-        self.train = False      # produced by the training-mode forward (no inference workspace, aux placeholders)
+    def __init__(self, engine_id, ranges, posenc, minmax, scene=None, ws=None, train=False):
+        self.engine_id = engine_id
+        self.ranges = ranges
+        self.posenc = posenc    # list[Tensor [n_b,128]]
+        self.minmax = minmax    # list[Tensor [6]]
+        self.scene, self.ws = scene, ws
+        self.train = train      # produced by the training-mode forward (no inference workspace, aux placeholders)
         # per-scene cache of the first decoder layer's click-to-scene keys / values (click-independent): allocated and
         # filled by the SECOND forward_mask on this backbone output, read by every later one
         self.mask_calls = 0
         self.kv0 = None         # list[Tensor [3, n_b, 128]]: keys, values, scene-to-click queries of the first layer
         self.kv0_version = None
+
+
+def _is_backbone(name):
+    """Whether a state-dict key belongs to forward_backbone's half of the model (the rest is forward_mask's)."""
+    return name.startswith(("backbone.", "lin_squeeze_head."))
 
 
 class Engine:
@@ -446,23 +432,29 @@ class Engine:
         self._stale_dec = True
         self._version = None
         self._version_dec = None
+        self._dec_epoch = 0          # counts the decoder packs: what a scene's cached keys / values were made with
         self._dec_tensors = None
         self._all_tensors = None
         self.program = None
         self.decoder = None
 
+    def backbone_statistics_moved(self):
+        """The BatchNorm running statistics were written through raw pointers (a training-mode forward, BackboneTape): the
+        folded backbone program is out of date."""
+        self._stale = True
+
     def mark_stale(self):
+        """The weights were written behind torch's back (the library's AdamW, load_state_dict): every pack is out of date,
+        the training tapes' packed conv weights included."""
         self._stale = True
         self._stale_dec = True
-        pw = getattr(self.model, "_a3d_packed_train", None)      # the training tapes' packed conv weights
-        if pw is not None:
-            pw.invalidate()
+        packed_weights_of(self.model).invalidate()
 
     def _weights_version(self, decoder_only=False):
         if self._dec_tensors is None:
             sd = self.model.state_dict(keep_vars=True)
             self._all_tensors = list(sd.values())
-            self._dec_tensors = [v for k, v in sd.items() if not k.startswith("backbone.") and not k.startswith("lin_squeeze_head.")]
+            self._dec_tensors = [v for k, v in sd.items() if not _is_backbone(k)]
         return sum(int(t._version) for t in (self._dec_tensors if decoder_only else self._all_tensors))
 
     def refresh_weights_if_stale(self, check_versions=False):
@@ -488,149 +480,90 @@ class Engine:
                 self.decoder = DecoderPack(self.model, self.device)
             self._version_dec = self._weights_version(True)
             self._stale_dec = False
-            self._dec_epoch = getattr(self, "_dec_epoch", 0) + 1     # what a scene's cached keys / values were made with
+            self._dec_epoch += 1
 
     # ---------------------------------------------------------------- forward_backbone
-    def forward_backbone(self, x, raw_coordinates=None):
-        lib = L.load()
-        self.refresh_weights_if_stale(check_versions=True)
-        if not isinstance(x, SparseTensor):
-            x = SparseTensor(features=x.F, coordinates=x.C, device=self.device)
-        if x.device != self.device:
-            x = SparseTensor(features=x.F, coordinates=x.C, device=self.device)
+    def _raw_rows(self, raw_coordinates, n):
+        """``raw_coordinates`` as the fp32 [n, 3] tensor on this device that the position encodings are made from."""
         if raw_coordinates is None:
             raise ValueError("forward_backbone needs raw_coordinates (agile3d.py:163)")
         raw = raw_coordinates.to(self.device, torch.float32).contiguous()
-        n = len(x)
         if raw.shape != (n, 3):
             raise ValueError("raw_coordinates must be [N,3]")
-        with torch.no_grad():
-            st = _SceneState()
-            st.engine_id = id(self)
-            st.scene = Scene(x.C)
-            out = torch.empty((n, self.model.mask_dim), dtype=torch.float32, device=self.device)
-            st.ws = self.program.run(st.scene, x.F, out)
-            st.ranges = st.scene.batch_ranges      # from the scene build's single read-back, no torch kernels
-            st.posenc, st.minmax = self._posenc_batch(raw, st.ranges)
-        pcd_features = SparseTensor(features=out, coordinates=x.C)
+        return raw
+
+    def _sparse_input(self, x, raw_coordinates):
+        """``x`` as a SparseTensor on this device and its raw coordinates (``_raw_rows``)."""
+        if not isinstance(x, SparseTensor) or x.device != self.device:
+            x = SparseTensor(features=x.F, coordinates=x.C, device=self.device)
+        return x, self._raw_rows(raw_coordinates, len(x))
+
+    def _backbone_result(self, feats, coords, raw, st):
+        """What forward_backbone returns (agile3d.py:181), with ``st`` riding on pcd_features: (pcd_features, aux,
+        coordinates, pos_encodings_pcd) -- only the finest level's position encodings exist (hlevels = [4])."""
+        pcd_features = SparseTensor(features=feats, coordinates=coords)
         pcd_features._a3d = st
-        coordinates = SparseTensor(features=raw, coordinates=x.C)
-        aux = _AuxList(self.program, st)
+        aux = [None] * 5 if st.train else _AuxList(self.program, st) if st.ws is not None else None
         pos_encodings_pcd = [[[None] * len(st.ranges)] for _ in range(4)] + [[list(st.posenc)]]
-        return pcd_features, aux, coordinates, pos_encodings_pcd
+        return pcd_features, aux, SparseTensor(features=raw, coordinates=coords), pos_encodings_pcd
+
+    def forward_backbone(self, x, raw_coordinates=None):
+        self.refresh_weights_if_stale(check_versions=True)
+        x, raw = self._sparse_input(x, raw_coordinates)
+        with torch.no_grad():
+            scene = Scene(x.C)
+            out = torch.empty((len(x), self.model.mask_dim), dtype=torch.float32, device=self.device)
+            ws = self.program.run(scene, x.F, out)
+            ranges = scene.batch_ranges      # from the scene build's single read-back, no torch kernels
+            st = _SceneState(id(self), ranges, *self._posenc_batch(raw, ranges), scene=scene, ws=ws)
+        return self._backbone_result(out, x.C, raw, st)
 
     def forward_backbone_train(self, x, raw_coordinates=None):
         """``forward_backbone`` of a model in training mode (engine.py:53 of the reference): BatchNorm on the statistics
         of this batch (running statistics updated), every activation kept for the backward pass (BackboneTape), the
         result tied into torch.autograd -- ``pcd_features.F`` depends on every backbone parameter."""
         from .autograd import BackboneFn, _Holder
-        from .train_backbone import BackboneTape
-        lib = L.load()
         self.refresh_decoder_if_stale(check_versions=True)      # gauss_B / inv_freq for the position encodings
-        if not isinstance(x, SparseTensor) or x.device != self.device:
-            x = SparseTensor(features=x.F, coordinates=x.C, device=self.device)
-        if raw_coordinates is None:
-            raise ValueError("forward_backbone needs raw_coordinates (agile3d.py:163)")
-        raw = raw_coordinates.to(self.device, torch.float32).contiguous()
-        n = len(x)
-        if raw.shape != (n, 3):
-            raise ValueError("raw_coordinates must be [N,3]")
-        st = _SceneState()
-        st.engine_id = id(self)
-        st.train = True
+        x, raw = self._sparse_input(x, raw_coordinates)
         with torch.no_grad():
-            from .train_backbone import packed_weights_of
             packed_weights_of(self.model).refresh_all()      # scene-independent: queued before the scene build's host round trip
-            st.scene = Scene(x.C)
-            tape = BackboneTape(self.model, st.scene, x.F.detach())
-            st.ranges = st.scene.batch_ranges
-            st.posenc, st.minmax = self._posenc_batch(raw, st.ranges)
-        named = [(k, p) for k, p in self.model.named_parameters()
-                 if k.startswith("backbone.") or k.startswith("lin_squeeze_head.")]
+            scene = Scene(x.C)
+            tape = BackboneTape(self.model, scene, x.F.detach())
+            ranges = scene.batch_ranges
+            st = _SceneState(id(self), ranges, *self._posenc_batch(raw, ranges), scene=scene, train=True)
+        named = [(k, p) for k, p in self.model.named_parameters() if _is_backbone(k)]
         holder = _Holder(tape=tape, names=[k for k, _ in named])
         out = BackboneFn.apply(holder, *[p for _, p in named]) if torch.is_grad_enabled() else tape.output
-        pcd_features = SparseTensor(features=out, coordinates=x.C)
-        pcd_features._a3d = st
-        coordinates = SparseTensor(features=raw, coordinates=x.C)
-        pos_encodings_pcd = [[[None] * len(st.ranges)] for _ in range(4)] + [[list(st.posenc)]]
-        return pcd_features, [None] * 5, coordinates, pos_encodings_pcd
-
-    def forward_mask_train(self, pcd_features, aux, coordinates, pos_encodings_pcd, click_idx=None, click_time_idx=None):
-        """``forward_mask`` of a model in training mode (engine.py:120-122): one DecoderTape per batch sample
-        (agile3d.py:192 loops over the samples), logits tied into torch.autograd."""
-        from .autograd import DecoderFn, _Holder
-        from .train_decoder import DecoderTape, draw_seed
-        st = getattr(pcd_features, "_a3d", None)
-        if st is None or st.engine_id != id(self):
-            raise RuntimeError("forward_mask needs the objects returned by this model's forward_backbone")
-        if click_idx is None or click_time_idx is None:
-            raise ValueError("click_idx and click_time_idx are required")
-        named = [(k, p) for k, p in self.model.named_parameters()
-                 if not (k.startswith("backbone.") or k.startswith("lin_squeeze_head."))]
-        names, params = [k for k, _ in named], [p for _, p in named]
-        n_layers = self.model.num_decoders
-        preds = [[] for _ in range(n_layers)]
-        # dropout: one seed per call, sample b's masks keyed by b -- the masks a batched tape of the same seed draws
-        p = getattr(self.model, "dropout", 0.0)
-        seed = draw_seed() if p > 0 else None
-        for b, (s, e) in enumerate(st.ranges):
-            rows = pcd_features.F[s:e]
-            with torch.no_grad():
-                tape = DecoderTape(self.model, rows.detach(), st.posenc[b], click_idx[b], click_time_idx[b], dropout=p, seed=seed,
-                                   sample_base=b)
-            if torch.is_grad_enabled():
-                logits = DecoderFn.apply(_Holder(tape=tape, names=names), rows, *params)
-            else:
-                logits = tape.logits
-            for l in range(n_layers):
-                preds[l].append(logits[l])
-        out = {"pred_masks": preds[-1], "backbone_features": pcd_features}
-        if self.model.aux:
-            out["aux_outputs"] = [{"pred_masks": p} for p in preds[:-1]]
-        return out
+        return self._backbone_result(out, x.C, raw, st)
 
     def decoder_inputs(self, feats128: torch.Tensor, raw_xyz: torch.Tensor):
         """Single-sample decoder inputs from an explicit [N,128] feature matrix (what
         forward_backbone would have produced) -- used by the golden-vector parity tests, which
         hold the reference's decoder inputs directly."""
-        lib = L.load()
         self.refresh_decoder_if_stale(check_versions=True)
         feats = feats128.to(self.device, torch.float32).contiguous()
-        raw = raw_xyz.to(self.device, torch.float32).contiguous()
         n = feats.shape[0]
-        C4 = torch.zeros((n, 4), dtype=torch.int32, device=self.device)
-        st = _SceneState()
-        st.engine_id = id(self)
-        st.ranges = [(0, n)]
+        raw = self._raw_rows(raw_xyz, n)
         with torch.no_grad():
             pe, mm = self._posenc(raw)
-        st.posenc, st.minmax = [pe], [mm]
-        pcd = SparseTensor(features=feats, coordinates=C4)
-        pcd._a3d = st
-        coordinates = SparseTensor(features=raw, coordinates=C4)
-        return pcd, None, coordinates, [[[None]] for _ in range(4)] + [[[pe]]]
+        coords = torch.zeros((n, 4), dtype=torch.int32, device=self.device)
+        return self._backbone_result(feats, coords, raw, _SceneState(id(self), [(0, n)], [pe], [mm]))
 
     def decoder_inputs_batch(self, feats128: torch.Tensor, raw_xyz: torch.Tensor, ranges):
         """Decoder inputs of a whole batch from an explicit feature matrix (rows of sample i = ``ranges[i]``): what
         forward_backbone returns for it -- the training iteration runs its no-grad click rounds on the training-mode
         backbone's features this way (engine.py:82-116 of the reference)."""
-        lib = L.load()
         self.refresh_decoder_if_stale(check_versions=True)
         feats = feats128.to(self.device, torch.float32).contiguous()
-        raw = raw_xyz.to(self.device, torch.float32).contiguous()
         n = feats.shape[0]
-        C4 = torch.zeros((n, 4), dtype=torch.int32, device=self.device)
-        st = _SceneState()
-        st.engine_id = id(self)
-        st.ranges = [(int(s), int(e)) for s, e in ranges]
+        raw = self._raw_rows(raw_xyz, n)
+        coords = torch.zeros((n, 4), dtype=torch.int32, device=self.device)
+        ranges = [(int(s), int(e)) for s, e in ranges]
         with torch.no_grad():
-            for b, (s, e) in enumerate(st.ranges):
-                C4[s:e, 0] = b
-            st.posenc, st.minmax = self._posenc_batch(raw, st.ranges)
-        pcd = SparseTensor(features=feats, coordinates=C4)
-        pcd._a3d = st
-        coordinates = SparseTensor(features=raw, coordinates=C4)
-        return pcd, None, coordinates, [[[None] * len(st.ranges)] for _ in range(4)] + [[list(st.posenc)]]
+            for b, (s, e) in enumerate(ranges):
+                coords[s:e, 0] = b
+            st = _SceneState(id(self), ranges, *self._posenc_batch(raw, ranges))
+        return self._backbone_result(feats, coords, raw, st)
 
     def _posenc(self, raw, starts=None):
         """The position encoding this model was built with (args.positional_encoding_type, args.normalize_pos_enc;
@@ -670,13 +603,51 @@ class Engine:
         return [pe_all[s - s0:e - s0] for (s, e) in ranges], [None if mm_all is None else mm_all[b] for b in range(ns)]
 
     # ---------------------------------------------------------------- forward_mask
-    def forward_mask(self, pcd_features, aux, coordinates, pos_encodings_pcd, click_idx=None, click_time_idx=None):
-        lib = L.load()
+    def _mask_state(self, pcd_features, click_idx, click_time_idx):
+        """The state forward_backbone left on ``pcd_features``, after the argument checks of both forward_masks."""
         st = getattr(pcd_features, "_a3d", None)
         if st is None or st.engine_id != id(self):
             raise RuntimeError("forward_mask needs the objects returned by this model's forward_backbone")
         if click_idx is None or click_time_idx is None:
             raise ValueError("click_idx and click_time_idx are required")
+        return st
+
+    def _mask_result(self, preds, pcd_features):
+        """forward_mask's dictionary (agile3d.py:325-339) from ``preds[layer][sample]``."""
+        out = {"pred_masks": preds[-1], "backbone_features": pcd_features}
+        if self.model.aux:
+            out["aux_outputs"] = [{"pred_masks": p} for p in preds[:-1]]
+        return out
+
+    def forward_mask_train(self, pcd_features, aux, coordinates, pos_encodings_pcd, click_idx=None, click_time_idx=None):
+        """``forward_mask`` of a model in training mode (engine.py:120-122): one DecoderTape per batch sample
+        (agile3d.py:192 loops over the samples), logits tied into torch.autograd."""
+        from .autograd import DecoderFn, _Holder
+        from .train_decoder import DecoderTape, draw_seed
+        st = self._mask_state(pcd_features, click_idx, click_time_idx)
+        named = [(k, p) for k, p in self.model.named_parameters() if not _is_backbone(k)]
+        names, params = [k for k, _ in named], [p for _, p in named]
+        n_layers = self.model.num_decoders
+        preds = [[] for _ in range(n_layers)]
+        # dropout: one seed per call, sample b's masks keyed by b -- the masks a batched tape of the same seed draws
+        p = getattr(self.model, "dropout", 0.0)
+        seed = draw_seed() if p > 0 else None
+        for b, (s, e) in enumerate(st.ranges):
+            rows = pcd_features.F[s:e]
+            with torch.no_grad():
+                tape = DecoderTape(self.model, rows.detach(), st.posenc[b], click_idx[b], click_time_idx[b], dropout=p, seed=seed,
+                                   sample_base=b)
+            if torch.is_grad_enabled():
+                logits = DecoderFn.apply(_Holder(tape=tape, names=names), rows, *params)
+            else:
+                logits = tape.logits
+            for l in range(n_layers):
+                preds[l].append(logits[l])
+        return self._mask_result(preds, pcd_features)
+
+    def forward_mask(self, pcd_features, aux, coordinates, pos_encodings_pcd, click_idx=None, click_time_idx=None):
+        lib = L.load()
+        st = self._mask_state(pcd_features, click_idx, click_time_idx)
         self.refresh_decoder_if_stale(check_versions=True)
         W = self.decoder.W
         n_layers = self.decoder.n_layers
@@ -708,19 +679,15 @@ class Engine:
             keep = []                                   # host arrays / tensors the library reads during the call
             for b, (s, e) in enumerate(st.ranges):
                 nb = e - s
-                ci, ct = click_idx[b], click_time_idx[b]
-                K = len(ci) - 1
-                rows, objs, times = [], [], []
-                for o in list(range(1, K + 1)) + [0]:
-                    r, t = ci[str(o)], ct[str(o)]
-                    if len(r) != len(t):
-                        raise ValueError("click_idx / click_time_idx length mismatch")
-                    if o > 0 and len(r) == 0:
-                        raise ValueError(f"object {o} has no click (the reference fails on an empty max, "
-                                         "agile3d.py:353)")
-                    rows.extend(map(int, r))
-                    times.extend(map(int, t))
-                    objs.extend([o] * len(r))
+                # the queries: the clicks of objects 1..K in object order, then the background's (clicks.query_list)
+                rows, times, counts, bg_rows, bg_times = query_list(click_idx[b], click_time_idx[b])
+                K = len(counts)
+                objs = []
+                for o, c in enumerate(counts, start=1):
+                    objs += [o] * c
+                objs += [0] * len(bg_rows)
+                rows += bg_rows
+                times += bg_times
                 nc = len(rows)
                 nq = nc + W.n_bg_queries
                 wsb = lib.a3d_decoder_workspace_bytes(nb, nq)
@@ -751,10 +718,7 @@ class Engine:
                 raise
             if kv_state == 1:                           # stamped valid only once the fill has been issued without an error
                 st.kv0, st.kv0_version = kv_fill, kv_key
-        out = {"pred_masks": preds[-1], "backbone_features": pcd_features}
-        if self.model.aux:
-            out["aux_outputs"] = [{"pred_masks": p} for p in preds[:-1]]
-        return out
+        return self._mask_result(preds, pcd_features)
 
 
 class _AuxFeature:

@@ -133,7 +133,6 @@ class Agile3d(nn.Module):
             self.ffn_attention.append(nn.ModuleList([M.FFNLayerParams(d, ff)]))
         self.decoder_norm = nn.LayerNorm(d)
         self._engine = None          # lazily created agile3d_amd.engine.Engine
-        self._packed_version = None
 
     def train(self, mode: bool = True):
         """``nn.Module.train`` walks the module tree recursively (~900 Python calls, 0.4 ms for this model); the training step

@@ -117,6 +117,37 @@ class Res16UNet34CParams(nn.Module):
         self.block8 = _make_layer(P[7] + 32, P[7], L[7], m)
 
 
+def walk_res16unet34c(bb, head, b):
+    """``Res16UNet34C.forward`` (res16unet.py:222-295) + ``lin_squeeze_head`` (agile3d.py:179), stated ONCE for its two builders:
+    ``engine.BackboneProgram`` (an op program over pooled buffers) and ``train_backbone.BackboneTape`` (a tape of activations);
+    oracle/backbone.py stays an independent statement that both are checked against.  Activations ``x`` and concatenation
+    buffers ``cat`` are the builder's own objects.  Its verbs (every conv + BatchNorm unit ends in a ReLU):
+        concat_buffer(level, c_up, c_skip) -> cat   the buffer of me.cat(up-sampled, skip) at ``level``: the skip half LAST
+        stem(conv, bn, cat) -> x                    the input conv + bn0 into the skip half of ``cat``
+        down(conv, bn, x) -> x                      stride-2 conv + BatchNorm, one level coarser
+        layer(blocks, x, skip_of=None) -> x         _make_layer's BasicBlocks, the last one into the skip half of ``skip_of``
+        up(conv, bn, x, cat)                        transposed conv + BatchNorm into the up-sampled half of ``cat``
+        concat(cat) -> x                            the concatenation, both halves written
+        head(conv, x)                               1x1 conv + bias into the caller's row order
+    Returns the five feature maps (res16unet.py:250-290: out_b4p16, then every decoder layer's output)."""
+    encoder = [(bb.conv1p1s2, bb.bn1, bb.block1), (bb.conv2p2s2, bb.bn2, bb.block2),
+               (bb.conv3p4s2, bb.bn3, bb.block3), (bb.conv4p8s2, bb.bn4, bb.block4)]      # from level 0, 1, 2, 3
+    decoder = [(bb.convtr7p2s2, bb.bntr7, bb.block8), (bb.convtr6p4s2, bb.bntr6, bb.block7),
+               (bb.convtr5p8s2, bb.bntr5, bb.block6), (bb.convtr4p16s2, bb.bntr4, bb.block5)]    # into level 0, 1, 2, 3
+    skips = [bb.conv0p1s1] + [blocks[-1].conv2 for _, _, blocks in encoder[:3]]      # what writes the skip of level 0 .. 3
+    cats = [b.concat_buffer(level, decoder[level][0].cout, skips[level].cout) for level in range(4)]
+    x = b.stem(bb.conv0p1s1, bb.bn0, cats[0])
+    for level, (conv, bn, blocks) in enumerate(encoder):
+        x = b.layer(blocks, b.down(conv, bn, x), skip_of=cats[level + 1] if level < 3 else None)
+    feature_maps = [x]
+    for (conv, bn, blocks), cat in zip(reversed(decoder), reversed(cats)):
+        b.up(conv, bn, x, cat)
+        x = b.layer(blocks, b.concat(cat))
+        feature_maps.append(x)
+    b.head(head, x)
+    return feature_maps
+
+
 class _AttnLayerParams(nn.Module):
     """CrossAttentionLayer / SelfAttentionLayer parameters (``attention_block.py:5-24,63-82``)."""
 

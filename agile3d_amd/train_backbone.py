@@ -23,6 +23,7 @@ import torch
 
 from . import backward as B
 from . import lib as L
+from .modules import walk_res16unet34c
 
 
 class _T:
@@ -166,7 +167,7 @@ class BackboneTape:
         self.packed.refresh_all()
         self.state = B.StateArena(self.feats3.device, 320)    # 63 forward convs + <= 4 launches per conv in the backward
         self._bns = []           # the BatchNorms this forward pass ran through (running statistics updated in place)
-        self._forward()
+        walk_res16unet34c(model.backbone, model.lin_squeeze_head, self)      # the forward pass (res16unet.py:222-295)
         # the kernels wrote running_mean / running_var through raw device pointers: torch's version counters did not
         # move, so (1) count the batch like nn.BatchNorm1d does (state-dict parity with torch, one multi-tensor launch;
         # the buffers' version bump is what refresh_weights_if_stale(check_versions=True) sees) and (2) tell the
@@ -175,7 +176,7 @@ class BackboneTape:
             torch._foreach_add_([b.num_batches_tracked for b in self._bns], 1)
         eng = getattr(model, "_engine", None)
         if eng is not None:
-            eng._stale = True
+            eng.backbone_statistics_moved()
 
     # ------------------------------------------------------------------ layers
     def _pgrad(self, param, g):
@@ -318,44 +319,38 @@ class BackboneTape:
         # first write into the residual node), then the projection, then conv1 -- both accumulate into x
         return self._conv_bn(L.OP_CONV3, h, blk.conv2, blk.norm2, res=res, relu=True, out=out)
 
-    def _layer(self, blocks, x: _T, out=None) -> _T:
+    # ------------------------------------------------------------------ the builder's verbs (modules.walk_res16unet34c)
+    def concat_buffer(self, level, c_up, c_skip):      # both halves are written straight into their column slices
+        return SimpleNamespace(buf=self._new(level, c_up + c_skip), c_up=c_up, up=None, skip=None)      # up, skip: the nodes
+
+    def stem(self, conv, bn, cat) -> _T:
+        sc = self.scene
+        w0 = conv.kernel3().detach().contiguous()
+        stem = _T(B.stem_forward(sc, w0, self.feats3, w0.shape[0]), 0)
+        self.steps.append(lambda: self._pgrad(conv.kernel, B.stem_weight_grad(sc, self.feats3, stem.g[:sc.n[0]], w0.shape[0])))
+        cat.skip = self._bn_only(stem, bn, cat.buf[:, cat.c_up:])
+        return cat.skip
+
+    def down(self, conv, bn, x: _T) -> _T:
+        return self._conv_bn(L.OP_DOWN, x, conv, bn)
+
+    def layer(self, blocks, x: _T, skip_of=None) -> _T:
+        into = skip_of.buf[:, skip_of.c_up:] if skip_of is not None else None
         for i, blk in enumerate(blocks):
-            x = self._block(blk, x, out if i == len(blocks) - 1 else None)
+            x = self._block(blk, x, into if i == len(blocks) - 1 else None)
+        if skip_of is not None:
+            skip_of.skip = x
         return x
 
-    # ------------------------------------------------------------------ forward (res16unet.py:222-295)
-    def _forward(self):
-        bb, sc = self.model.backbone, self.scene
-        P = bb.PLANES
-        w0 = bb.conv0p1s1.kernel3().detach().contiguous()
-        # the concatenation buffers [up-sampled | skip] (me.cat puts the skip LAST): the encoder's skip tensors and the
-        # transposed convs' outputs are written straight into their column slices
-        cat8 = self._new(0, P[7] + 32)
-        cat7 = self._new(1, P[6] + P[0])
-        cat6 = self._new(2, P[5] + P[1])
-        cat5 = self._new(3, P[4] + P[2])
-        stem = _T(B.stem_forward(sc, w0, self.feats3, w0.shape[0]), 0)
-        self.steps.append(lambda: self._pgrad(bb.conv0p1s1.kernel,
-                                              B.stem_weight_grad(sc, self.feats3, stem.g[:sc.n[0]], w0.shape[0])))
-        out_p1 = self._bn_only(stem, bb.bn0, cat8[:, P[7]:])
-        out = self._conv_bn(L.OP_DOWN, out_p1, bb.conv1p1s2, bb.bn1)
-        out_b1p2 = self._layer(bb.block1, out, cat7[:, P[6]:])
-        out = self._conv_bn(L.OP_DOWN, out_b1p2, bb.conv2p2s2, bb.bn2)
-        out_b2p4 = self._layer(bb.block2, out, cat6[:, P[5]:])
-        out = self._conv_bn(L.OP_DOWN, out_b2p4, bb.conv3p4s2, bb.bn3)
-        out_b3p8 = self._layer(bb.block3, out, cat5[:, P[4]:])
-        out = self._conv_bn(L.OP_DOWN, out_b3p8, bb.conv4p8s2, bb.bn4)
-        out = self._layer(bb.block4, out)
-        up = self._conv_bn(L.OP_UP, out, bb.convtr4p16s2, bb.bntr4, out=cat5[:, :P[4]])
-        out = self._layer(bb.block5, self._cat(cat5, up, out_b3p8))
-        up = self._conv_bn(L.OP_UP, out, bb.convtr5p8s2, bb.bntr5, out=cat6[:, :P[5]])
-        out = self._layer(bb.block6, self._cat(cat6, up, out_b2p4))
-        up = self._conv_bn(L.OP_UP, out, bb.convtr6p4s2, bb.bntr6, out=cat7[:, :P[6]])
-        out = self._layer(bb.block7, self._cat(cat7, up, out_b1p2))
-        up = self._conv_bn(L.OP_UP, out, bb.convtr7p2s2, bb.bntr7, out=cat8[:, :P[7]])
-        out = self._layer(bb.block8, self._cat(cat8, up, out_p1))
-        # lin_squeeze_head: 1x1 conv + bias (agile3d.py:43-45,179), back to the caller's row order
-        head = self.model.lin_squeeze_head
+    def up(self, conv, bn, x: _T, cat):
+        cat.up = self._conv_bn(L.OP_UP, x, conv, bn, out=cat.buf[:, :cat.c_up])
+
+    def concat(self, cat) -> _T:
+        return self._cat(cat.buf, cat.up, cat.skip)
+
+    def head(self, head, out: _T):
+        """lin_squeeze_head: 1x1 conv + bias (agile3d.py:43-45,179), back to the caller's row order."""
+        sc = self.scene
         K, cin, cout = head.kernel3().shape
         wf, wb = self.packed.get(head, L.OP_LINEAR)
         n0 = sc.n[0]

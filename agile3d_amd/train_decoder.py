@@ -22,6 +22,7 @@ import torch
 from . import backward as B
 from . import decoder_ops as ops
 from . import lib as L
+from .clicks import query_list
 from .decoder_ops import DH, H
 from .engine import time_table
 
@@ -443,14 +444,7 @@ class DecoderTape:
         n_at = q_at = 0
         q_parts, qpos_parts = [], []
         for pcd, pos_enc, click_idx, click_time_idx in zip(pcds, pos_encs, click_idxs, click_time_idxs):
-            K = len(click_idx) - 1
-            fg_split = [len(click_idx[str(i)]) for i in range(1, K + 1)]
-            for i, c in enumerate(fg_split):
-                if c == 0:   # an empty group has no maximum: the reference fails on it too (agile3d.py:353)
-                    raise ValueError(f"object {i + 1} has no click (the reference fails on an empty max, agile3d.py:353)")
-            fg_rows = [r for i in range(1, K + 1) for r in click_idx[str(i)]]
-            fg_times = [t for i in range(1, K + 1) for t in click_time_idx[str(i)]]
-            bg_rows, bg_times = list(click_idx["0"]), list(click_time_idx["0"])
+            fg_rows, fg_times, fg_split, bg_rows, bg_times = query_list(click_idx, click_time_idx)
             n_fg = len(fg_rows)
             rows = torch.tensor(fg_rows + bg_rows, dtype=torch.long, device=dev)
             fixed_pos = pos_enc[rows] + tt[torch.tensor(fg_times + bg_times, dtype=torch.long, device=dev)]
@@ -553,22 +547,3 @@ class DecoderTape:
         for back in reversed(self.steps):
             back()
         return self.grads, self.pcd.g
-
-
-
-# DEPRECATED, no caller in this repository: the names through which tests written before decoder_ops.py reached the primitives,
-# kept only so that such a test still runs against this package.  New code calls decoder_ops; delete these with the next change
-# that may break those callers.
-def _apply(P, V, Lq, Lk, Hh, dh, transposed, scale, out):
-    ops.attn_apply(P, V, transposed, scale, out)
-
-
-def _next_layer_mask(logits, grp_of_query, n_groups):
-    return ops.next_layer_mask(logits.contiguous(), grp_of_query)
-
-
-def _dense_fwd(q, k, v, mask, o, drop=None):
-    return ops.dense_forward(q, k, v, mask, o, drop)[1]
-
-
-DecoderTape._dense_fwd, DecoderTape._dense_bwd = staticmethod(_dense_fwd), staticmethod(ops.dense_backward)

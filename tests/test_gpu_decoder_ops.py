@@ -259,20 +259,3 @@ def test_dense_pair_into_the_callers_tensors(drop):
         _same([ops.attn_apply(saved[0], V, transposed, 0.5, nan(rows, 128), workspace=ws)],
               [ops.attn_apply(saved[0], V, transposed, 0.5)])
 
-
-def test_deprecated_names_forward_to_decoder_ops():
-    """engine._ptr / _stream and train_decoder._apply, _next_layer_mask, DecoderTape._dense_fwd / _dense_bwd, which tests
-    written before decoder_ops.py import: the same results as the wrappers they forward to."""
-    from agile3d_amd import engine, train_decoder as TD
-    assert engine._ptr is L.ptr and engine._stream is L.stream
-    q, k, v, w, mask = _qkvw(LQ, LK)
-    o0, saved0 = ops.dense_forward(q, k, v, mask)
-    o, g = nan(LQ, 128), (nan(LQ, 128), nan(LK, 128), nan(LK, 128))
-    saved = TD.DecoderTape._dense_fwd(q, k, v, mask, o)
-    TD.DecoderTape._dense_bwd(q, k, v, mask, o, saved, w, *g)
-    _same((o, saved[0]) + g, (o0, saved0[0]) + ops.dense_backward(q, k, v, mask, o0, saved0, w))
-    out = nan(LQ, 128)
-    TD._apply(saved[0], v, LQ, LK, 8, 16, 0, 0.5, out)
-    _same([out], [ops.attn_apply(saved[0], v, False, 0.5)])
-    logits, grp = torch.randn(7, 3, device=DEV), torch.tensor([0, 2, 1, 1], dtype=torch.int32, device=DEV)
-    assert torch.equal(TD._next_layer_mask(logits, grp, 3), ops.next_layer_mask(logits, grp))

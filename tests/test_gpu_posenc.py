@@ -18,6 +18,7 @@ import torch
 
 from agile3d_amd import SparseTensor, build_model, default_args
 from agile3d_amd import lib as L
+from agile3d_amd.clicks import query_list
 from agile3d_amd.synthetic import make_clicks, make_scene
 from conftest import GOLDEN, arrays_to_clicks, load_case
 
@@ -60,20 +61,20 @@ def _run(model, c):
     pcd, aux, coords, pos = eng.decoder_inputs(torch.from_numpy(c["feats128"]), torch.from_numpy(c["xyz"]))
     out = model.forward_mask(pcd, aux, coords, pos, click_idx=[ci], click_time_idx=[ct])
     got = [a["pred_masks"][0].cpu().numpy() for a in out["aux_outputs"]] + [out["pred_masks"][0].cpu().numpy()]
-    return pos[4][0][0].cpu().numpy(), got, ci
+    return pos[4][0][0].cpu().numpy(), got, (ci, ct)
 
 
-def _attn_mask(logits, ci, n_bg_learned=10):
+def _attn_mask(logits, clicks, n_bg_learned=10):
     """The attention mask the next decoder layer gets from a level's logits (mask_module, agile3d.py:362-384): the rows
     of an object's queries block every point not labelled with it; a row that would block everything blocks nothing."""
     lab = logits.argmax(1)
-    K = len(ci) - 1
+    _, _, counts, bg_rows, _ = query_list(*clicks)    # the decoder's query order: objects 1..K, then the background
     rows = []
-    for o in list(range(1, K + 1)) + [0]:
+    for o, c in list(enumerate(counts, start=1)) + [(0, len(bg_rows) + n_bg_learned)]:
         m = lab != o
         if m.all():
             m = np.zeros_like(m)
-        rows += [m] * (len(ci[str(o)]) + (n_bg_learned if o == 0 else 0))
+        rows += [m] * c
     return np.stack(rows)
 
 
@@ -85,7 +86,7 @@ def test_encoding_and_logits_match_the_reference_fixtures(config, scene, decoder
     nq = len(c["click_rows"]) + 10
     assert (nq <= 32) if scene == "q27" else (nq > 64)
     model = _model(config, decoder_weights, inv_freq=c.get("inv_freq"))
-    enc, got, ci = _run(model, c)
+    enc, got, clicks = _run(model, c)
     raw = config in ("sine_raw", "fourier_raw")
     bar = max(1e-4, 4.0 * float(c["pos_enc_fp64_gap"])) if raw else 1e-4
     perr = np.abs(enc - c["pos_enc"]).max()
@@ -95,7 +96,7 @@ def test_encoding_and_logits_match_the_reference_fixtures(config, scene, decoder
     assert perr <= bar
     assert max(errs) <= TOL, errs
     for i in range(2):
-        assert np.array_equal(_attn_mask(got[i], ci), c[f"attn_mask{i}"]), i
+        assert np.array_equal(_attn_mask(got[i], clicks), c[f"attn_mask{i}"]), i
 
 
 def test_legacy_uses_the_loaded_inv_freq_buffer(decoder_weights):

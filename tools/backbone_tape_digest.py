@@ -9,12 +9,12 @@ its own (``backward.stem_forward``, ``train_backbone._run_stem`` before that exi
 BackboneTape's constructor, ``output``, ``relu_levels``, ``backward()`` and ``release()`` and setattr on the loaded library's
 symbols are used, so the same file runs on either commit:
   python tools/backbone_tape_digest.py [--json digests.json]"""
-import argparse, ctypes, hashlib, json, os, sys, tempfile
+import argparse, hashlib, json, os, sys, tempfile
 import torch
+import lib_trace
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from agile3d_amd import backward as B
 from agile3d_amd import build_model, default_args, optim
-from agile3d_amd import lib as L
 from agile3d_amd import train_backbone as TB
 from agile3d_amd.engine import Scene
 from agile3d_amd.synthetic import make_scene
@@ -28,18 +28,7 @@ def sha(t):
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
 
 
-def plain(a):
-    """A by-value argument as something with a stable repr: numbers as they are, a struct as the tuple of its fields."""
-    if isinstance(a, ctypes.Structure):
-        return tuple(plain(getattr(a, f[0])) for f in a._fields_)
-    return getattr(a, "value", a)
-
-
-lib, trace = L.load(), []
-for name, (_, argtypes) in L.SYMBOLS.items():
-    by_value = [i for i, t in enumerate(argtypes) if t is not ctypes.c_void_p and not hasattr(t, "contents")]
-    fn = getattr(lib, name)
-    setattr(lib, name, lambda *a, _fn=fn, _n=name, _v=by_value: (trace.append((_n,) + tuple(plain(a[i]) for i in _v)), _fn(*a))[1])
+trace = lib_trace.install()
 
 torch.manual_seed(0)
 model = build_model(default_args()).cuda().train()
@@ -79,7 +68,7 @@ def run(case, env=(), sync_bn=None, restore=True):
     d = digests[case] = {k: sha(v) for k, v in vals.items()}
     for part in ("output", "grad", "relu"):
         d[f"{part}s"] = hashlib.sha256("".join(d[k] for k in vals if k.startswith(part)).encode()).hexdigest()
-    d["trace"] = hashlib.sha256(repr(trace).encode()).hexdigest()
+    d["trace"] = lib_trace.digest(trace)
     d["calls"] = len(trace)
     tape.release()
     print(f"{case} | calls {d['calls']} | trace {d['trace'][:16]} | output {d['outputs'][:16]} | grads {d['grads'][:16]} | "

@@ -12,10 +12,11 @@ file runs on either commit:
 import argparse, ctypes, hashlib, json, os, random, sys, tempfile, types
 import numpy as np
 import torch
+import lib_trace
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from agile3d_amd import build_model, clicks as pc, default_args, lib as L, randomize_bn_stats
+from agile3d_amd import build_model, clicks as pc, default_args, randomize_bn_stats
 from agile3d_amd.evaluate import Evaluate
 from agile3d_amd.session import InteractiveSession
 from agile3d_amd.synthetic import make_scene
@@ -42,11 +43,7 @@ def plain(v):
     return getattr(v, "value", v)
 
 
-lib, trace = L.load(), []
-for name, (_, argtypes) in L.SYMBOLS.items():
-    by_value = [i for i, t in enumerate(argtypes) if t is not ctypes.c_void_p and not hasattr(t, "contents")]
-    fn = getattr(lib, name)
-    setattr(lib, name, lambda *a, _fn=fn, _n=name, _v=by_value: (trace.append((_n,) + tuple(plain(a[i]) for i in _v)), _fn(*a))[1])
+trace = lib_trace.install(plain)
 
 digests = {}
 
@@ -55,7 +52,7 @@ def record(section, value, with_trace=False):
     digests[section] = hashlib.sha256(repr(plain(value)).encode()).hexdigest()
     line = f"{section} | values {digests[section][:16]}"
     if with_trace:
-        digests[section + " trace"] = hashlib.sha256(repr(trace).encode()).hexdigest()
+        digests[section + " trace"] = lib_trace.digest(trace)
         digests[section + " calls"] = len(trace)
         line += f" | trace {digests[section + ' trace'][:16]} [{len(trace)} calls]"
         for t in trace:

@@ -6,11 +6,11 @@ dropout 0 / 0.1 (fixed seed) x a one-sample tape of 3000 voxels / a batched tape
 the materialised path even with FLASH on), 12 clicks on 3 objects per sample.  Only DecoderTape's constructor, backward()
 and release() and setattr on the loaded library's symbols are used, so the same file runs on either commit:
   python tools/tape_digest.py [--json digests.json] [--tensors values.pt]"""
-import argparse, ctypes, hashlib, json, os, sys
+import argparse, hashlib, json, os, sys
 import torch
+import lib_trace
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from agile3d_amd import build_model, default_args
-from agile3d_amd import lib as L
 from agile3d_amd import train_decoder as TD
 from agile3d_amd.synthetic import make_clicks, make_scene
 
@@ -24,18 +24,7 @@ def sha(t):
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
 
 
-def plain(a):
-    """A by-value argument as something with a stable repr: numbers as they are, a struct as the tuple of its fields."""
-    if isinstance(a, ctypes.Structure):
-        return tuple(plain(getattr(a, f[0])) for f in a._fields_)
-    return getattr(a, "value", a)
-
-
-lib, trace = L.load(), []
-for name, (_, argtypes) in L.SYMBOLS.items():
-    by_value = [i for i, t in enumerate(argtypes) if t is not ctypes.c_void_p and not hasattr(t, "contents")]
-    fn = getattr(lib, name)
-    setattr(lib, name, lambda *a, _fn=fn, _n=name, _v=by_value: (trace.append((_n,) + tuple(plain(a[i]) for i in _v)), _fn(*a))[1])
+trace = lib_trace.install()
 
 torch.manual_seed(0)
 model = build_model(default_args(dropout=0.1)).cuda().train()
@@ -72,7 +61,7 @@ for flash in (True, False):
             vals = dict(logits, d_pcd=d_pcd, **{f"grad {k}": grads[k] for k in sorted(grads)})
             digests[case] = {k: sha(v) for k, v in vals.items()}
             digests[case]["values"] = hashlib.sha256("".join(digests[case][k] for k in vals).encode()).hexdigest()
-            digests[case]["trace"] = hashlib.sha256(repr(trace).encode()).hexdigest()
+            digests[case]["trace"] = lib_trace.digest(trace)
             digests[case]["calls"] = len(trace)
             if args.tensors:
                 tensors[case] = {k: v.detach().cpu().clone() for k, v in vals.items()}
