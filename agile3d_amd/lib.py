@@ -275,6 +275,13 @@ class EstimateNormalsArgs(C.Structure):
                 ("has_viewpoint", C.c_int32)]
 
 
+class TransferSummary(C.Structure):
+    """a3d_transfer_summary: matched, unmatched and non-finite queries, source rows left out as not finite, the error word
+    (A3D_TRANSFER_UNKEYABLE, A3D_TRANSFER_SORT_FAILED)."""
+    _fields_ = [("matched", C.c_int64), ("unmatched", C.c_int64), ("nonfinite", C.c_int64), ("source_left_out", C.c_int64),
+                ("err", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class ObjectMoments(C.Structure):
     """a3d_object_moments: one object of a labelling -- vertices and voxels, the sums of the fixed-point coordinates (X, Y, Z)
     and of their products (XX, XY, XZ, YY, YZ, ZZ), the covered surface in thirds of area quanta, the exact fp32 box."""
@@ -373,7 +380,9 @@ A3D_MEASURE_MAX_BITS, A3D_MEASURE_MAX_Q, A3D_MEASURE_MAX_FACES = 20, 1 << 38, 1 
 A3D_MEASURE_BLOCK, A3D_MEASURE_CHUNK = 256, 1024
 A3D_GROW_MAX_STEPS, A3D_GROW_BAD_INDEX = 1024, 1
 A3D_NORMALS_RANGE, A3D_NORMALS_BAD_INDEX = 1, 2
+A3D_TRANSFER_UNKEYABLE, A3D_TRANSFER_SORT_FAILED = 1, 2
 A3D_ERR_INVALID = -1
+A3D_ERR_WORKSPACE = -5
 PROF_DENSE = 11
 PROF_NAMES = ["spconv", "splitk_epilogue", "stem", "c2s_attn", "query_chain", "s2c_attn", "ln_mask", "posenc",
               "scene_sort_levels", "scene_tables", "click_simulator", "dense_gemm"]
@@ -577,6 +586,12 @@ SYMBOLS = {
     "a3d_estimate_normals": (C.c_int, [C.POINTER(EstimateNormalsArgs), C.c_void_p]),
     "a3d_normals_solve": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_double,
                                     C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "a3d_point_index_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "a3d_point_index_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.POINTER(C.c_void_p)]),
+    "a3d_point_index_destroy": (None, [C.c_void_p]),
+    "a3d_point_index_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "a3d_cull_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "a3d_render_shade_lit_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Camera), C.c_float,

@@ -39,6 +39,9 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
     which voxels belong to one surface  a3d_similar_pieces / a3d_vote_pieces  (patches, wand_at, snap: connected components
                                         under a similarity of normals and colours, the patch under a pixel as a selection,
                                         labels snapped to patches by a vote that never contradicts a click; a rule of ours)
+    labels on another point set         a3d_point_index_create / a3d_point_index_nearest  (nearest_vertices, transfer,
+                                        import_labels: an index over any point set and the bulk exact nearest row within a
+                                        reach -- labels to a high-resolution mesh, ground truth from one; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -419,6 +422,21 @@ class NormalsResult(_Result):
 _MAX_CULLED = 4                                 # culled copies of a cloud kept at a time (one per eye and mode)
 
 
+class TransferResult(_Result):
+    """What ``nearest_vertices()``, ``transfer()`` and ``import_labels()`` return, one entry per QUERY point (for
+    ``import_labels`` the queries are the scene's vertices).  Device tensors: ``nearest`` int32 [m] (the row of the nearest
+    source point within ``max_distance``, -1 without one), ``distance2`` fp32 [m] (its squared fp32 distance, +inf without
+    one), and where labels were carried ``labels`` int32 [m] (``fill`` without a match) and ``colors`` fp32 [m, 3] (the
+    palette's); ``None`` otherwise.  Host: ``matched``, ``unmatched`` (finite points with nothing in reach), ``nonfinite``
+    (points with a NaN or an infinity: also -1), ``source_left_out`` (source points that are not finite) and the
+    ``max_distance`` of the call."""
+
+    __slots__ = ("nearest", "distance2", "labels", "colors", "matched", "unmatched", "nonfinite", "source_left_out", "max_distance")
+
+
+_MAX_POINT_INDICES = 4                          # indices over a scene's vertices kept at a time (one per cell size)
+
+
 class CorrectedResult(_Result):
     """What ``corrected()`` returns: ``labels_full`` int32 [n_full] and ``colors`` fp32 [n_full, 3] on the device -- the model's
     labels with the manual layer laid over them -- ``miou`` and ``iou_per_object`` as a ``SessionResult`` holds them (``None``
@@ -794,6 +812,8 @@ class InteractiveSession:
         self._guide_sum_host = torch.empty(V.GUIDE_SUMMARY.itemsize, dtype=torch.uint8).pin_memory()
         self._manual_err = torch.zeros(1, dtype=torch.int32, device=self.device)   # the flag of the manual layer's own a3d_session_edit
         self._region_sum = torch.empty(V.OVERLAY_SUMMARY.itemsize, dtype=torch.uint8, device=self.device)   # select's / overlay's summary
+        self._transfer_sum = torch.empty(V.TRANSFER_SUMMARY.itemsize, dtype=torch.uint8, device=self.device)   # a3d_point_index_nearest's
+        self._point_indices = {}
         self._drop_scene()
 
     # ------------------------------------------------------------------ scene
@@ -818,6 +838,9 @@ class InteractiveSession:
         self._measure_frame = None                  # (origin, quantum, bits) of measure(): once per scene, on first use
         self._grow_ws = None                        # scratch of grow(): once per scene, on first use
         self._colors_qv = None                      # fp32 [n_voxels, 3]: the colours the backbone was fed (patches(color_tol=))
+        for index in self._point_indices.values():  # cell size (fp32) -> view.PointIndex over coords_full (nearest_vertices, transfer)
+            index.close()
+        self._point_indices = {}
         self.section = None                         # the Section pick, click_ray and render apply by default (set_section)
         self._reset_clicks()
 
@@ -2281,3 +2304,106 @@ class InteractiveSession:
         row = self.inverse_map[vertex]
         both = torch.cat([normals.normals_full[vertex], normals.variation_qv[row].reshape(1)]).cpu().numpy()
         return both[:3].copy(), float(both[3])
+
+    # ------------------------------------------------------------------ labels to and from another point set
+    def _points(self, name, points):
+        """``points`` (numpy, or a tensor on any device) as fp32 [m, 3] on the session's device."""
+        p = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
+        if p.dim() != 2 or p.shape[1] != 3 or not (p.dtype.is_floating_point or p.numel() == 0):
+            raise ValueError(f"{name} must be [m, 3] floating-point coordinates")
+        return p.to(self.device).to(torch.float32).contiguous()
+
+    def _reach(self, max_distance):
+        """``(max_distance, cell_size)`` as fp32 values: the cells are twice the reach, which is then exactly half a cell."""
+        with np.errstate(over="ignore"):
+            r = np.float32(self.voxel_size if max_distance is None else max_distance)
+            cell = np.float32(2.0) * r
+        if not (np.isfinite(cell) and r > 0):
+            raise ValueError("max_distance must be finite and > 0 in fp32")
+        return float(r), float(cell)
+
+    def _vertex_index(self, cell):
+        """The index over ``coords_full`` with cells of ``cell``: built on first use, kept with the scene."""
+        index = self._point_indices.get(cell)
+        if index is None:
+            while len(self._point_indices) >= _MAX_POINT_INDICES:
+                self._point_indices.pop(next(iter(self._point_indices))).close()
+            index = self._point_indices[cell] = V.point_index_create(self.coords_full, cell)
+        return index
+
+    def _palette_colors(self, labels):
+        """fp32 [m, 3]: the palette's colour of every label, ids beyond the table wrapped as ``_palette_entry`` wraps them."""
+        n = self._palette_dev.shape[0]
+        lab = labels.to(torch.int64).clamp_(min=0)
+        return self._palette_dev[torch.where(lab < n, lab, 1 + (lab - 1) % (n - 1))]
+
+    def _nearest(self, index, queries, r, labels_src, fill):
+        nearest, d2, labels, summary = V.point_index_nearest(index, queries, r, labels_src=labels_src, fill=fill,
+                                                             summary=self._transfer_sum)
+        s = V.read_transfer_summary(summary.cpu().numpy())              # the one host round trip
+        return TransferResult(nearest=nearest, distance2=d2, labels=labels, colors=None if labels is None else self._palette_colors(labels),
+                              matched=s["matched"], unmatched=s["unmatched"], nonfinite=s["nonfinite"],
+                              source_left_out=s["source_left_out"], max_distance=r)
+
+    def nearest_vertices(self, points, max_distance=None):
+        """For every row of ``points`` [m, 3] (numpy, or a tensor on any device) the scene's nearest vertex within
+        ``max_distance`` (default ``voxel_size``), exactly: the first arg-min of the fp32 distance ``click`` searches by, over
+        the finite vertices in reach (``a3d_point_index_nearest``); -1 where there is none.  The index over ``coords_full``
+        has cells of twice ``max_distance``; it is built on first use and kept with the scene, one per cell size.  Returns a
+        ``TransferResult`` (``labels`` and ``colors`` are ``None``).  One host round trip (the counts)."""
+        self._need_scene()
+        q = self._points("points", points)
+        r, cell = self._reach(max_distance)
+        return self._nearest(self._vertex_index(cell), q, r, None, 0)
+
+    def transfer(self, points, labels=None, max_distance=None, fill=0):
+        """The scene's labels carried to another point set: every row of ``points`` takes the label of its nearest vertex
+        within ``max_distance`` (``nearest_vertices``' search; the labels are gathered in the same kernel), ``fill`` where
+        no vertex is in reach.  ``labels`` int32 [n_full] on the session's device (default: the full-resolution labels of
+        the last ``infer`` / ``preview``; ``ValueError`` before any).  Returns a ``TransferResult`` with ``labels`` and
+        ``colors``.  One host round trip."""
+        self._need_scene()
+        n = self.coords_full.shape[0]
+        lab = self._labels_last if labels is None else labels
+        if lab is None:
+            raise ValueError("transfer() carries the labels of the last infer() / preview(): there is none yet (or pass labels=)")
+        if not torch.is_tensor(lab) or lab.device != self.device or lab.dtype != torch.int32 or tuple(lab.shape) != (n,):
+            raise ValueError(f"labels must be an int32 tensor [{n}] on the session's device")
+        q = self._points("points", points)
+        r, cell = self._reach(max_distance)
+        return self._nearest(self._vertex_index(cell), q, r, lab.contiguous(), fill)
+
+    def import_labels(self, points, labels, max_distance=None, into="manual"):
+        """A labelling held on another point set brought into the session: every vertex of the scene takes the label of
+        its nearest row of ``points`` [k, 3] within ``max_distance`` (default ``voxel_size``); ``labels`` [k] integer ids
+        (numpy, or a tensor on any device).  The index over ``points`` lives for the call only.  ``into="manual"``: the
+        matched vertices go into the manual layer (``set_manual``: ids in 0..255, else ``ValueError`` and the layer as it
+        was); the layer's other vertices stay as they were, so ``corrected()`` shows the imported labels.
+        ``into="truth"``: the labels become the scene's ground truth (unmatched vertices 0) -- ``infer()`` then reports
+        ``miou`` -- which is allowed only while the click list is empty (``ValueError`` otherwise, nothing changed).
+        Returns the ``TransferResult`` of the scene's vertices."""
+        self._need_scene()
+        if into not in ("manual", "truth"):
+            raise ValueError("into must be 'manual' or 'truth'")
+        if into == "truth" and self._clicks:
+            raise ValueError("the ground truth can be replaced only while the click list is empty (reset() first)")
+        p = self._points("points", points)
+        lab = labels if torch.is_tensor(labels) else torch.as_tensor(np.asarray(labels))
+        if lab.dim() != 1 or lab.shape[0] != p.shape[0] or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+            raise ValueError(f"labels must be [{p.shape[0]}] integer ids, one per point")
+        lab = lab.to(self.device).to(torch.int32).contiguous()
+        r, cell = self._reach(max_distance)
+        index = V.point_index_create(p, cell)
+        try:
+            res = self._nearest(index, self.coords_full, r, lab, 0)
+        finally:
+            index.close()
+        if into == "manual":
+            on, obj = self.manual_labels()
+            hit = res.nearest >= 0
+            self.set_manual(on | hit.to(torch.uint8), torch.where(hit, res.labels, obj))
+        else:
+            self.labels_full_ori = res.labels
+            self.labels_qv_ori = self.labels_full_ori[self._unique_map]
+            self.new_labels = torch.zeros_like(self.labels_full_ori)
+        return res

@@ -1082,6 +1082,121 @@ def cull_points(xyz, normals, eye, mode, out=None, hidden=None, count=None):
     return out, hidden, count
 
 
+# ---- labels to and from another point set: an index over any point set, the bulk nearest query ---------------------------------
+TRANSFER_SUMMARY = np.dtype([("matched", "<i8"), ("unmatched", "<i8"), ("nonfinite", "<i8"), ("source_left_out", "<i8"),
+                             ("err", "<i4"), ("reserved_", "<i4")])
+assert C.sizeof(L.TransferSummary) == TRANSFER_SUMMARY.itemsize == 40
+TRANSFER_UNKEYABLE, TRANSFER_SORT_FAILED = L.A3D_TRANSFER_UNKEYABLE, L.A3D_TRANSFER_SORT_FAILED   # the bits of the error word
+POINT_INDEX_MAX_CELLS = 1 << 20                 # a source coordinate lies within this many cells of the origin
+
+
+def read_transfer_summary(host, check=True):
+    """The host copy of an ``a3d_transfer_summary`` (uint8 [40], or anything of those bytes) as a dict of Python ints:
+    ``matched``, ``unmatched`` (finite queries without a row in reach), ``nonfinite`` (queries), ``source_left_out`` (source
+    rows that are not finite), ``err``.  With ``check`` an index that left rows out because they cannot be keyed raises
+    ``ValueError`` (``TRANSFER_UNKEYABLE``: its answers ignore those rows) and one whose sort gave up ``RuntimeError``."""
+    s = _summary_ints(host, TRANSFER_SUMMARY)
+    if check and s["err"] & TRANSFER_UNKEYABLE:
+        raise ValueError(f"a source coordinate lies more than {POINT_INDEX_MAX_CELLS} cells of cell_size from the origin: such "
+                         "a point set cannot be indexed (a larger cell_size, or coordinates moved towards the origin)")
+    if check and s["err"]:
+        raise RuntimeError("a3d_point_index_create: the sort of the build gave up; the index is not usable")
+    return s
+
+
+def _positive_f32(name, value):
+    """``value`` rounded to fp32, as the library compares it; finite and > 0 there."""
+    with np.errstate(over="ignore"):
+        v = float(np.float32(value))
+    if not (np.isfinite(v) and v > 0.0):
+        raise ValueError(f"{name} must be finite and > 0 in fp32")
+    return v
+
+
+def point_index_workspace(n, device):
+    """The memory an index over n points lives in (``a3d_point_index_workspace_bytes``)."""
+    return _scratch(L.load().a3d_point_index_workspace_bytes(n), device, f"no point index for n={n}")
+
+
+class PointIndex:
+    """An ``a3d_point_index``: the handle, the workspace it lives in (kept alive here), ``n`` source rows, ``cell_size`` (the
+    fp32 value) and the device.  ``close()`` frees the handle and lets go of the workspace; a closed index is refused."""
+
+    def __init__(self, handle, workspace, n, cell_size, device):
+        self.handle, self.workspace, self.n, self.cell_size, self.device = handle, workspace, n, cell_size, device
+
+    def close(self):
+        if self.handle is not None:
+            L.load().a3d_point_index_destroy(self.handle)
+        self.handle = self.workspace = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def point_index_create(xyz, cell_size, workspace=None):
+    """``a3d_point_index_create``: a ``PointIndex`` over ``xyz`` fp32 [n, 3] (n >= 0) with cubic cells of ``cell_size`` (rounded
+    to fp32).  Rows that are not finite are left out and counted in every query's summary.  ``workspace``: uint8, 256-byte
+    aligned, ``point_index_workspace(n, device)`` or larger (allocated otherwise).  ``xyz`` is not needed after the call's
+    launches have run; nothing is synchronised."""
+    dev = _device("xyz", xyz)
+    xp = _ptr("xyz", xyz, F32, (None, 3), dev)
+    n = xyz.shape[0]
+    if n >= 1 << 31:
+        raise ValueError(f"xyz: {n} rows, the index takes fewer than 2^31")
+    cell = _positive_f32("cell_size", cell_size)
+    need = L.load().a3d_point_index_workspace_bytes(n)
+    if workspace is None:
+        workspace = point_index_workspace(n, dev)
+    wp = _ptr("workspace", workspace, U8, (None,), dev)
+    if workspace.shape[0] < need or workspace.data_ptr() % 256:
+        raise ValueError("workspace too small or not 256-byte aligned (point_index_workspace(n, device))")
+    handle = C.c_void_p()
+    L.check(L.load().a3d_point_index_create(xp, n, cell, wp, workspace.shape[0], L.stream(dev), C.byref(handle)),
+            "a3d_point_index_create")
+    return PointIndex(handle, workspace, n, cell, dev)
+
+
+def point_index_nearest(index, queries, max_distance, labels_src=None, fill=0, nearest=None, d2=None, labels=None, summary=None):
+    """``a3d_point_index_nearest``: for every row of ``queries`` fp32 [m, 3] the nearest source row of ``index`` within
+    ``max_distance`` (rounded to fp32; 0 < max_distance <= index.cell_size / 2), by the brute-force rule of the header: the
+    first arg-min of the fp32 distance among the finite rows in reach, -1 without one.  ``labels_src`` int32 [index.n]: the
+    labels to carry, gathered in the same kernel (``fill`` where nothing is in reach).  Outputs: a tensor of the caller's,
+    ``None`` = allocated; ``d2=False`` = not wanted; ``labels`` exists exactly with ``labels_src``.  Returns ``(nearest int32
+    [m], d2 fp32 [m] or None, labels int32 [m] or None, summary uint8 [40])`` on the device; ``read_transfer_summary`` decodes
+    the summary's host copy."""
+    if not isinstance(index, PointIndex) or index.handle is None:
+        raise ValueError("index must be an open PointIndex (point_index_create)")
+    dev = index.device
+    if not torch.is_tensor(queries) or queries.device != dev:
+        raise ValueError(f"queries must be a tensor on {dev}, the index's device")
+    qp = _ptr("queries", queries, F32, (None, 3), dev)
+    m = queries.shape[0]
+    if m >= 1 << 31:
+        raise ValueError(f"queries: {m} rows, a call takes fewer than 2^31")
+    r = _positive_f32("max_distance", max_distance)
+    if r > float(np.float32(0.5) * np.float32(index.cell_size)):
+        raise ValueError(f"max_distance={r} must not exceed half the index's cell_size={index.cell_size}")
+    fill = _int_in("fill", fill, -(1 << 31), (1 << 31) - 1)
+    lp = _ptr("labels_src", labels_src, I32, (index.n,), dev, optional=True)
+    if labels_src is None and labels is not None:
+        raise ValueError("labels is written only with labels_src")
+    nearest = _out("nearest", nearest, I32, (m,), dev)
+    d2 = None if d2 is False else _out("d2", d2, F32, (m,), dev)
+    labels = None if labels_src is None else _out("labels", labels, I32, (m,), dev)
+    summary = _summary(summary, TRANSFER_SUMMARY.itemsize, dev)
+    if labels_src is not None and lp is None:           # (no source rows: a pointer all the same, never followed)
+        lp = summary.data_ptr()
+    L.check(L.load().a3d_point_index_nearest(index.handle, qp, m, r, lp, fill, nearest.data_ptr() if m else None,
+                                             d2.data_ptr() if d2 is not None and m else None,
+                                             (labels.data_ptr() if m else summary.data_ptr()) if labels is not None else None,
+                                             summary.data_ptr(), L.stream(dev)), "a3d_point_index_nearest")
+    return nearest, d2, labels, summary
+
+
 # ---- correcting by hand: a screen region, the vertices seen inside it, the manual layer ----------------------------------------
 SELECT_SUMMARY = np.dtype([("selected", "<i8"), ("in_view", "<i8"), ("flags", "<i4"), ("reserved_", "<i4")])
 OVERLAY_SUMMARY = np.dtype([("changed", "<i8"), ("overridden", "<i8"), ("differing", "<i8"), ("err", "<i4"), ("reserved_", "<i4")])

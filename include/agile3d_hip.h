@@ -1420,6 +1420,58 @@ int    a3d_estimate_normals(const a3d_estimate_normals_args* args, void* stream)
 int    a3d_normals_solve(int64_t count, const int64_t* sum3, const int64_t* mom6, const double* origin, double quantum,
                          const double* viewpoint, float* out5);
 
+/* LABELS TO AND FROM ANOTHER POINT SET: an index over an arbitrary point set and the bulk, exact nearest-point query against
+ * it (csrc/session_transfer.hip).  a3d_nearest_rows scans every row for at most 64 queries a call, which is right for a click;
+ * this serves a million queries.  The reference has no counterpart.  The rule is a3d_nearest_rows' with a cutoff:
+ *
+ * THE RULE.  For query q take every source row p whose three coordinates are finite.  d2 = ((px-qx)^2 + (py-qy)^2) + (pz-qz)^2
+ * in fp32 from the differences, every operation rounded on its own (no fma contraction).  r2 = fl32(max_distance *
+ * max_distance), rounded once.  nearest_out[q] = the FIRST arg-min of d2 among the rows with d2 <= r2: ties go to the lowest
+ * source row, whichever cells the candidates sit in.  When no row qualifies, or q has a coordinate that is not finite:
+ * nearest_out[q] = -1 and d2_out[q] = +inf.  labels_out[q] = labels_src[nearest_out[q]], or fill without a match.
+ *
+ * a3d_point_index_create builds the index over xyz_dev fp32 [n][3] (0 <= n < 2^31) with cubic cells of cell_size (fp32, finite,
+ * > 0): the cell of a coordinate is floor(fl32(x / cell_size)).  A row with a coordinate that is not finite is left out and
+ * counted; a row with |floor(fl32(x / cell_size))| > 2^20 on some axis cannot be keyed: it is left out too and the build sets
+ * A3D_TRANSFER_UNKEYABLE, which every query's summary repeats -- such an index answers as if those rows were absent, so
+ * treat the bit as an error.  The index lives in the caller's workspace (a3d_point_index_workspace_bytes(n) bytes, 256-byte
+ * aligned; 0 for n < 0 or n >= 2^31), as an a3d_scene does: keep the workspace until a3d_point_index_destroy, which frees the
+ * host handle only.  xyz_dev is not needed after the build.  The build is a chain of launches on `stream` (one radix sort in
+ * its launch-chain form among them) and does not synchronise.
+ *
+ * a3d_point_index_nearest answers m queries (queries_dev fp32 [m][3], 0 <= m < 2^31) with 0 < max_distance <= cell_size / 2,
+ * both compared in fp32; anything else is A3D_ERR_INVALID.  Within that bound the 27 cells around a query's cell hold every
+ * row with d2 <= r2; where r2 is not a normal fp32 number (max_distance below 2^-63 or from 2^64 on) that
+ * argument fails and the call tests every indexed row instead: the same rule, without the index's speed.
+ * labels_src_dev int32 [n] may be NULL; labels_out_dev int32 [m] is given exactly when it is.  d2_out_dev fp32 [m] may be NULL.
+ * summary_dev (8-byte aligned, cleared by the call): matched queries; unmatched queries with finite coordinates; queries with a
+ * coordinate that is not finite (matched + unmatched + nonfinite = m); source rows left out as not finite; the error word.
+ * Integer sums, one atomic per workgroup and counter: two calls give the same bytes in every output.
+ * A3D_ERR_INVALID with nothing launched: no index, m out of range, m > 0 without queries_dev or nearest_out_dev, no
+ * summary_dev, labels_out_dev without labels_src_dev or the reverse, a max_distance outside (0, cell_size / 2] or NaN; for
+ * the build: n out of range, n > 0 without xyz_dev, a cell_size that is not finite and > 0, no or a misaligned workspace, no
+ * `out` (A3D_ERR_WORKSPACE for one that is too small).
+ * LIMITS: the nearest VERTEX, not the nearest point of a mesh's surface; one nearest row, no k-nearest vote; max_distance
+ * at most half a cell; one point set per index. */
+#define A3D_TRANSFER_UNKEYABLE   1   /* a source coordinate beyond 2^20 cells was left out */
+#define A3D_TRANSFER_SORT_FAILED 2   /* the build's sort gave up waiting (as A3D_ERR_HIP of a scene build): the index is not usable */
+typedef struct a3d_point_index a3d_point_index;
+typedef struct a3d_transfer_summary {
+  int64_t matched;                  /* queries with a row within max_distance */
+  int64_t unmatched;                /* finite queries without one */
+  int64_t nonfinite;                /* queries with a coordinate that is not finite */
+  int64_t source_left_out;          /* source rows left out of the index as not finite */
+  int32_t err;                      /* A3D_TRANSFER_UNKEYABLE | A3D_TRANSFER_SORT_FAILED */
+  int32_t reserved_;
+} a3d_transfer_summary;            /* 40 bytes */
+size_t a3d_point_index_workspace_bytes(int64_t n);
+int    a3d_point_index_create(const float* xyz_dev, int64_t n, float cell_size, void* workspace_dev, size_t workspace_bytes,
+                              void* stream, a3d_point_index** out);
+void   a3d_point_index_destroy(a3d_point_index* index);
+int    a3d_point_index_nearest(const a3d_point_index* index, const float* queries_dev, int64_t m, float max_distance,
+                               const int32_t* labels_src_dev, int32_t fill, int32_t* nearest_out_dev, float* d2_out_dev,
+                               int32_t* labels_out_dev, a3d_transfer_summary* summary_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
  * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a
