@@ -95,6 +95,8 @@ struct SkArgs {
   int prio;              // 1: static wave priority by occupancy layer (ticket / 256), see the kernel
   int nchunk2;           // FUSE: stages of the fused 1x1 projection per tile (cin2 / CH), run as offset 27 after the tile's own
   unsigned in2_row_bytes;
+  int ntab;              // LDS blocks for a tile's neighbour rows behind the weight ring: 2 (the next tile's rows are fetched a
+                         // tile ahead), 1, or 0 (no table, or no room: the rows are read in global memory)
   // STATS (training-mode BatchNorm): per 64-row tile and output column the sum of the tile's rows and the sum of their
   // squared deviations from the TILE mean, [n_tiles][2][stats_ld] -- what k_bn_combine merges into the batch statistics
   float* stats;
@@ -148,6 +150,20 @@ __device__ __forceinline__ void glds16_s(const float* sbase, unsigned voff, unsi
       : "memory");
 }
 
+// the same with a 64-bit per-lane address
+__device__ __forceinline__ void glds16_v(const void* src, unsigned lds_byte_addr) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(src), "s"(lds_byte_addr)
+      : "memory");
+}
+
 // s_waitcnt vmcnt(0) through the builtin: unlike an asm statement the compiler's wait-count pass models it, so it
 // knows every load it tracks (the A fragments) has landed and inserts no conservative vmcnt of its own in front of
 // the MFMAs -- which would also wait for the LDS-DMA pieces it cannot see.  simm16: vmcnt 0, expcnt 7, lgkmcnt 15.
@@ -176,8 +192,15 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
   constexpr int WF = NPIECE * 256;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* wring = (float*)smem;                            // [2][WF]
-  int* misc = (int*)(wring + 2 * WF);
   const unsigned ring_addr = (unsigned)(size_t)wring;
+  // behind the ring: a.ntab blocks [4 ceil(K / 4)][64] of neighbour rows, the table of one tile each (1 KB LDS-DMA pieces of
+  // four offsets x 64 rows; a tail piece repeats offset K - 1).  Not in the 64 x 96 build (sk_has_tab): three workgroups
+  // per CU of its 48 KB ring leave no room for a 3^3 block
+  constexpr bool kTab = !(BN == 64 && CH == 96);
+  int* const tab0 = (int*)(wring + 2 * WF);
+  const int ntab = kTab ? a.ntab : 0;
+  const int tabn = ((a.c.K + 3) & ~3) * kTile;
+  int* misc = tab0 + ntab * tabn;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -271,9 +294,32 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
   const int wrow = 16 * RG * wave + j;   // this lane's row inside the tile for its group 0 (group r: + 16 r)
 
   const int n_u = u_hi - u_lo + 1;
+  // order: the tile at the END of the share first (its part is published), the tile at the START last (it may wait)
+  auto tile_at = [&](int i) -> int { return n_u == 1 ? u_lo : (i == 0 ? u_hi : (i == n_u - 1 ? u_lo : u_lo + i)); };
+  // A tile's group masks and neighbour rows are requested ONE TILE AHEAD, beside the first stage of the tile before it (the
+  // masks into scalar registers, the K x 64 rows into the table block the current tile does not read): a tile boundary pays no
+  // chain of dependent round trips masks -> rows -> first fragments, and the stage loop reads its rows with ds_read_b32.
+  // Only a workgroup's first tile (and one behind a tile it skipped) waits for its own table.
+  static_assert(RG == 1, "four mask words and 64 table rows per tile");
+  uint32_t mk_nxt[4] = {0u, 0u, 0u, 0u};
+  int mk_u = -1;    // the tile whose masks are in mk_nxt
+  int tab_u = -1;   // the tile whose rows have landed in block tb ^ 1
+  int tb = 0;       // the block of the current tile
+  auto load_masks = [&](int uu, uint32_t (&m)[4]) {
+    const uint32_t* gp = a.c.gmask + (uu % T) * (kTile >> 4);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) m[q] = gp[q];
+  };
+  // this wave's pieces of tile uu's rows -> block blk (LDS-DMA: no register holds them; they count on vmcnt, and a reader
+  // is behind the issuing waves' vmcnt(0) and a barrier)
+  auto load_table = [&](int uu, int blk) {
+    const int* src = a.c.nbr + (size_t)(uu % T) * kTile + 4 * j;
+    const unsigned dst = ring_addr + (unsigned)(2 * WF + blk * tabn) * 4u;
+    for (int q = wave; 4 * q < K; q += NW)
+      glds16_v(src + (size_t)min(4 * q + g, K - 1) * a.c.nbr_stride, dst + (unsigned)q * 1024u);
+  };
   for (int it = 0; it < n_u; ++it) {
-    // order: the tile at the END of the share first (its part is published), the tile at the START last (it may wait)
-    const int u = n_u == 1 ? u_lo : (it == 0 ? u_hi : (it == n_u - 1 ? u_lo : u_lo + it));
+    const int u = tile_at(it);
     const int cb = u / T, t = u - cb * T;
     const int ct0 = cb * NCT;
     const int r0 = t * kTile;
@@ -281,14 +327,15 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
     // one of them gathers the zero row for it: rows are sorted by neighbour pattern, adjacent groups rarely differ)
     uint32_t un = K >= 32 ? 0xffffffffu : (1u << K) - 1u, gm = un;
     if (a.c.gmask) {
-      const uint32_t* gp = a.c.gmask + (r0 >> 4);
-      uint32_t o = 0;
+      uint32_t mk[4];
+      if (mk_u == u) {
 #pragma unroll
-      for (int q = 0; q < 4 * RG; ++q) o |= gp[q];
-      un &= o;
-      gm = 0;
-#pragma unroll
-      for (int r = 0; r < RG; ++r) gm |= gp[RG * wave + r];
+        for (int q = 0; q < 4; ++q) mk[q] = mk_nxt[q];
+      } else {
+        load_masks(u, mk);
+      }
+      un &= (mk[0] | mk[1]) | (mk[2] | mk[3]);
+      gm = wave == 0 ? mk[0] : wave == 1 ? mk[1] : wave == 2 ? mk[2] : mk[3];
     }
     un = __builtin_amdgcn_readfirstlane(un);
     gm = __builtin_amdgcn_readfirstlane(gm);
@@ -334,15 +381,48 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
       int rem = s1 - s0;
       const float* wbase = a.c.w + (size_t)ct0 * 256;
       const char* inb = (const char*)a.c.in;
-      // gather rows of offset kk for this lane's groups, straight from the neighbour table (requested one offset
-      // before the A loads that need them); a missing neighbour is the zero row
-      auto fetch_rows = [&](int kk, int (&rows)[RG]) {
-        const int kc = kk < K ? kk : 0;    // unconditional loads (no select behind them: the loop-carried register is
-                                           // the load's destination, nothing waits for it before its use a stage later);
-                                           // 32 = no further offset, 27 (FUSE) = the projection: no table row, entry unused
+      // the tile's rows: prefetched into the other block by the tile before, or fetched now (one round trip and a barrier)
+      if (kTab && ntab) {
+        if (tab_u == u) {
+          tb ^= 1;
+        } else {
+          load_table(u, tb);
+          wait_all_vmem();
+          __builtin_amdgcn_s_barrier();
+        }
+        tab_u = -1;
+      }
+      // gather rows of offset kk for this lane's groups: a ds_read_b32 of the tile's table block, requested a stage before
+      // the A loads that need them, into the ONE loop-carried register those loads read -- it counts on lgkmcnt, in order
+      // with the weight fragments' reads, and no wait on vmcnt belongs to it.  (As a global load requested an offset ahead
+      // into a second register it was drained by an s_waitcnt vmcnt(0) right behind its issue: hipcc's copy between the two
+      // loop-carried registers needs the value -- a round trip per offset in front of the stage's gathers and MFMAs.)
+      // Unconditional: 32 = no further offset, 27 (FUSE) = the projection, a layer without a table (it reads the ring):
+      // entry unused, the select sits at the use.  The one build without room for a block (kTab) reads the table in global
+      // memory when the offset changes.
+      const int* tabp = (ntab ? tab0 + tb * tabn : (const int*)wring) + wrow;
+      auto fetch_rows = [&](int kk, int cc, int (&rows)[RG]) {
+        const int kc = kk < K ? kk : 0;
+        if constexpr (kTab) {
 #pragma unroll
-        for (int r = 0; r < RG; ++r)
-          rows[r] = a.c.nbr ? a.c.nbr[(size_t)kc * a.c.nbr_stride + r0 + wrow + 16 * r] : min(r0 + wrow + 16 * r, a.c.n_in - 1);
+          for (int r = 0; r < RG; ++r) rows[r] = tabp[kc * kTile + 16 * r];
+        } else if (cc == 0 && a.c.nbr) {
+#pragma unroll
+          for (int r = 0; r < RG; ++r) rows[r] = a.c.nbr[(size_t)kc * a.c.nbr_stride + r0 + wrow + 16 * r];
+        }
+      };
+      // the next tile's masks and rows, requested behind the first stage's loads
+      auto request_next_tile = [&]() {
+        if (it + 1 >= n_u) return;
+        const int un1 = tile_at(it + 1);
+        if (a.c.gmask) {
+          load_masks(un1, mk_nxt);
+          mk_u = un1;
+        }
+        if (kTab && ntab == 2) {
+          load_table(un1, tb ^ 1);
+          tab_u = un1;
+        }
       };
       // stage (k, c): this lane's A fragments (for its groups that have k), this wave's weight pieces by LDS-DMA
       auto load_stage = [&](f32x4 (&A)[RG][NS], int kk, int cc, int slot, const int (&rows)[RG]) {
@@ -352,8 +432,10 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
         if ((gm >> kk) & 1u) {
 #pragma unroll
           for (int r = 0; r < RG; ++r) {
-            // (the select sits at the USE of the table entry requested a stage earlier, not behind its load)
-            const int row = proj ? min(r0 + wrow + 16 * r, a.c.n_out) : rows[r];   // n_out = the zero row of in2
+            // (the selects sit at the USE of the table entry requested a stage earlier, not behind its read)
+            const int row = proj        ? min(r0 + wrow + 16 * r, a.c.n_out)   // n_out = the zero row of in2
+                            : a.c.nbr ? rows[r]
+                                      : min(r0 + wrow + 16 * r, a.c.n_in - 1);
             const unsigned roff = (unsigned)row * row_bytes + lane_a_off;
 #pragma unroll
             for (int Sx = 0; Sx < NS; ++Sx) A[r][Sx] = *(const f32x4*)(ar + roff + 64 * Sx);
@@ -414,48 +496,50 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
           }
         }
       };
+      // the stage after (kk, cc) of the tile (offset 32: none)
+      auto advance = [&](int& kk, int& cc) {
+        if (cc + 1 < ((FUSE && kk == 27) ? nchunk2 : nchunk)) {
+          ++cc;
+        } else {
+          kk = next_k(kk);
+          cc = 0;
+        }
+      };
       f32x4 A0[RG][NS], A1[RG][NS];
-      int rows_cur[RG], rows_nxt[RG];
-      int k1 = next_k(k);
-      fetch_rows(k, rows_cur);
-      fetch_rows(k1, rows_nxt);
-      load_stage(A0, k, c, 0, rows_cur);
+      int rows[RG];      // of stage (kl, cl): the one fetched next
+      int kl = k, cl = c;
+      fetch_rows(kl, 0, rows);
+      load_stage(A0, kl, cl, 0, rows);
+      advance(kl, cl);
+      fetch_rows(kl, cl, rows);
+      request_next_tile();
       wait_all_vmem();
       __builtin_amdgcn_s_barrier();
       for (;;) {
-        int k2, c2;
-        // ---- even stage: multiply A0 / slot 0, fetch A1 / slot 1
-        if (c + 1 < ((FUSE && k == 27) ? nchunk2 : nchunk)) { k2 = k; c2 = c + 1; } else { k2 = k1; c2 = 0; }
+        // ---- even stage: multiply A0 / slot 0, fetch A1 / slot 1, then request the rows of the stage fetched next
+        const int ke = kl;
         if (rem > 1) {
-          if (k2 != k) {
-#pragma unroll
-            for (int r = 0; r < RG; ++r) rows_cur[r] = rows_nxt[r];
-            k1 = next_k(k2);
-            fetch_rows(k1, rows_nxt);
-          }
-          load_stage(A1, k2, c2, 1, rows_cur);
+          load_stage(A1, kl, cl, 1, rows);
+          advance(kl, cl);
+          fetch_rows(kl, cl, rows);
         }
         compute(A0, k, 0);
         wait_all_vmem();
         __builtin_amdgcn_s_barrier();
         if (--rem == 0) break;
-        k = k2; c = c2;
+        k = ke;
         // ---- odd stage: multiply A1 / slot 1, fetch A0 / slot 0
-        if (c + 1 < ((FUSE && k == 27) ? nchunk2 : nchunk)) { k2 = k; c2 = c + 1; } else { k2 = k1; c2 = 0; }
+        const int ko = kl;
         if (rem > 1) {
-          if (k2 != k) {
-#pragma unroll
-            for (int r = 0; r < RG; ++r) rows_cur[r] = rows_nxt[r];
-            k1 = next_k(k2);
-            fetch_rows(k1, rows_nxt);
-          }
-          load_stage(A0, k2, c2, 0, rows_cur);
+          load_stage(A0, kl, cl, 0, rows);
+          advance(kl, cl);
+          fetch_rows(kl, cl, rows);
         }
         compute(A1, k, 1);
         wait_all_vmem();
         __builtin_amdgcn_s_barrier();
         if (--rem == 0) break;
-        k = k2; c = c2;
+        k = ko;
       }
     }
 
@@ -1629,6 +1713,7 @@ struct ConvPlan {
   int D, P;            // k_conv_deep: ring slots, parts per unit
   int G, n_cblk, ntile, nchunk, nchunk2, ov;   // G = 0: plan_deep leaves the layer to the stream-K kernel
   bool handoff, prio;  // k_conv_sk: shares cut inside tiles; static wave priorities
+  int ntab;            // k_conv_sk: LDS blocks of neighbour rows (0, 1 or 2; their bytes are in lds)
   // would the stream-K kernel take the projection / the head into this op?  (Asked of its geometry whatever the family: a
   // projection that only the deep kernel could fuse still runs as two launches, as it always has.)
   bool fused_ok, head_ok;
@@ -1672,6 +1757,11 @@ static int sk_wgs_per_cu(int bn, int ch, int pair, size_t lds) {
   const int w = by_regs < by_lds ? by_regs : by_lds;
   return w < 1 ? 1 : (w > 4 ? 4 : w);
 }
+// one LDS block of a tile's neighbour rows: [4 ceil(K / 4)][64] ints, whole 1 KB LDS-DMA pieces
+static size_t sk_tab_bytes(int K) { return (size_t)((K + 3) / 4) * 1024; }
+// the 64 x 96 build reads the table in global memory: beside its 48 KB ring three workgroups per CU have no room for the
+// 7 KB block of a 3^3 map (the kernel's kTab)
+static bool sk_has_tab(int bn, int ch) { return !(bn == 64 && ch == 96); }
 // force_ch > 0: that stage width instead of sk_ch's choice (a fused projection whose input channels the preferred width does
 // not divide: the 32 -> 64 block of level 2 runs its 64 -> 64 conv with 32-channel stages)
 static ConvPlan plan_sk(int n_rows, int K, int cin, int cout, bool handoff, int force_ch = 0) {
@@ -1863,6 +1953,16 @@ static ConvPlan plan_conv(const ConvShape& s) {
   p.fused_ok = fused_ok, p.head_ok = head_ok;
   // training: the (last arriver's / owner's) epilogue writes the tile's BatchNorm partials, the four waves meet in LDS
   if (s.stats) p.lds += (size_t)8 * p.bn * 4;
+  // k_conv_sk keeps a tile's neighbour rows in LDS: two blocks (the next tile's rows arrive during the current tile) where
+  // the build keeps its resident workgroups, else one -- G, and with it the partition and every sum's order, stays what it
+  // was.  Two blocks everywhere but the STATS builds of the 96-column kernel at K = 27 (one); the 64 x 96 build has none
+  if (p.family == kConvSk && s.tables && sk_has_tab(p.bn, p.ch)) {
+    const int resident = sk_wgs_per_cu(p.bn, p.ch, p.pair, p.lds);
+    for (p.ntab = 2; p.ntab > 0; --p.ntab)
+      if (sk_wgs_per_cu(p.bn, p.ch, p.pair, p.lds + p.ntab * sk_tab_bytes(s.K)) == resident) break;
+    if (p.ntab == 0) p.ntab = 1;   // (no such build today: the kernel needs its block, whatever becomes of the residency)
+    p.lds += p.ntab * sk_tab_bytes(s.K);
+  }
   return p;
 }
 
@@ -2009,6 +2109,10 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
     set_error("spconv: hand-off workspace too small");
     return A3D_ERR_WORKSPACE;
   }
+  if (c.nbr && !c.gmask) {   // (the plan sizes the LDS blocks of the rows for an op with both)
+    set_error("spconv: a neighbour table without its group masks");
+    return A3D_ERR_INVALID;
+  }
   if (c.K > 1 && !pre64) {
     set_error("spconv: a gathered convolution needs the scene's tile prefix table");
     return A3D_ERR_INVALID;
@@ -2021,6 +2125,7 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
   if (p.handoff) a.ticket = state, a.fail = state + 1, a.flags = (unsigned*)(state + 2);
   a.slab = slab_ws;
   a.in_row_bytes = (unsigned)c.ldi * 4u, a.in2_row_bytes = (unsigned)c.ldi2 * 4u;
+  a.ntab = p.ntab;
   a.stats = stats, a.stats_ld = stats_ld;
   if (bw) {
     a.bw_y = bw->y, a.bw_raw = bw->raw, a.bw_mean = bw->mean, a.bw_rstd = bw->rstd;
