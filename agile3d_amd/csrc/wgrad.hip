@@ -17,7 +17,8 @@
 #include "common.h"
 #include <stdlib.h>
 #include <mutex>
-#include <unordered_map>
+#include <map>
+#include <tuple>
 #include <vector>
 
 namespace a3d {
@@ -25,6 +26,161 @@ namespace a3d {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(8)));
+
+// ---- planning: which build of k_wgrad an op runs, how its work is cut into items, and which kernel maps of a scene have
+// work lists.  Plain C++ from here to the end-of-planning mark (no HIP types; env_int is common.h's, A3D_NUM_LEVELS and the
+// A3D_OP_* codes are agile3d_hip.h's), so that the block compiles into a stand-alone host program that sweeps it
+// (tests/wgrad_plan_main.cpp, tests/test_wgrad_plan_host.py).
+
+// the test switches of the environment, read once per process
+struct WgradSwitches {
+  int seg;               // A3D_WGRAD_SEG > 0: a fixed segment length instead of the model's (the edge tests rely on it: tests/test_gpu_wgrad_edges.py)
+  bool wide;             // A3D_WGRAD_WIDE != 0: the pointer build on operands a buffer descriptor could span
+};
+inline WgradSwitches make_wgrad_switches(int seg, int wide) { return WgradSwitches{seg > 0 ? seg : 0, wide != 0}; }
+inline const WgradSwitches& wgrad_switches() {
+  static const WgradSwitches v = make_wgrad_switches(env_int("A3D_WGRAD_SEG", 0), env_int("A3D_WGRAD_WIDE", 0));
+  return v;
+}
+
+// The builds of k_wgrad: V(CX, CY) = channels per lane of x and of dy, {2, 4, 6, 8}^2 with at most 36 accumulator tiles per
+// lane.  wgrad_launch instantiates and names exactly these, and wgrad_plan chooses among exactly these.
+#define A3D_WGRAD_BUILDS(V) V(2, 2) V(2, 4) V(2, 6) V(2, 8) V(4, 2) V(4, 4) V(4, 6) V(4, 8) V(6, 2) V(6, 4) V(6, 6) V(8, 2) V(8, 4)
+#define A3D_WG_IS(CX_, CY_) || (cx == CX_ && cy == CY_)
+constexpr bool wgrad_has_build(int cx, int cy) { return false A3D_WGRAD_BUILDS(A3D_WG_IS); }
+#undef A3D_WG_IS
+
+// The kernel maps of a scene that have work lists, in the order of the lists, of their counts and of k_wgrad_lists' jobs
+// (one job per map and offset).  list_kind: 0 = 3^3, 1 = 2^3 stride 2, 2 = 2^3 transposed; level: the one that owns the
+// map's group masks; pos_above: the map's positions (output rows) are those of level + 1.
+struct WgradMap {
+  int list_kind, level, K;
+  bool pos_above;
+};
+constexpr WgradMap kWgradMaps[] = {
+    {0, 0, 27, false}, {0, 1, 27, false}, {0, 2, 27, false}, {0, 3, 27, false}, {0, 4, 27, false},
+    {1, 0, 8, true},   {1, 1, 8, true},   {1, 2, 8, true},   {1, 3, 8, true},
+    {2, 0, 8, false},  {2, 1, 8, false},  {2, 2, 8, false},  {2, 3, 8, false}};
+constexpr int kListMaps = (int)(sizeof(kWgradMaps) / sizeof(kWgradMaps[0]));
+constexpr int wgrad_jobs_before(int m) {     // jobs of the maps in front of map m
+  int jobs = 0;
+  for (int i = 0; i < m; ++i) jobs += kWgradMaps[i].K;
+  return jobs;
+}
+constexpr int kListJobs = wgrad_jobs_before(kListMaps);
+// the map of an op (A3D_OP_CONV3 / DOWN / UP on level_in; the transposed conv's map belongs to the FINE level); -1: the op
+// has none (another kind, or a level at which the kind does not exist)
+constexpr int wgrad_map_of(int op_kind, int level_in) {
+  const int lk = op_kind == A3D_OP_CONV3 ? 0 : op_kind == A3D_OP_DOWN ? 1 : op_kind == A3D_OP_UP ? 2 : -1;
+  const int level = op_kind == A3D_OP_UP ? level_in - 1 : level_in;
+  for (int m = 0; m < kListMaps; ++m)
+    if (kWgradMaps[m].list_kind == lk && kWgradMaps[m].level == level) return m;
+  return -1;
+}
+static_assert(A3D_NUM_LEVELS == 5 && kListMaps == 13 && kListJobs == 5 * 27 + 4 * 8 + 4 * 8, "3^3 maps of five levels, stride-2 and transposed maps of four");
+
+// Work items: offset k's groups (list[k * list_stride + i], i < cnt[k]; without a list: groups 0 .. cnt[0] - 1 of a 1x1 map)
+// are cut into segments of seg_len; segment s of offset k writes partial slot base[k] + s.  Workgroup b runs on XCD b % 8
+// (hardware) and takes item b / 8 of that XCD's items: offset k's segments seg_lo[k][x] .. seg_lo[k][x + 1] - 1 -- the
+// x-th eighth of its list, so an XCD's offsets work on about the same stretch of rows -- offset-major; xbase[x][k] =
+// items of XCD x before offset k.  Every XCD gets the same number of items +- K / 8.  The kernel reads the tables as they
+// stand here (WgradArgs::cut).
+struct WgradCut {
+  int seg_len;
+  int cnt[27];
+  int base[28];
+  int xbase[8][28];
+  int seg_lo[27][9];
+};
+struct WgradPlan {
+  int cx, cy, nblocks, slots, grid_items;     // grid_items: items of the fullest XCD
+  WgradCut cut;
+  size_t part_bytes;
+};
+
+// the segment tables of one segment length; returns the items of the fullest XCD
+inline int wgrad_cut(const int* cnt, int K, int seg_len, WgradPlan& p) {
+  WgradCut& c = p.cut;
+  c.seg_len = seg_len;
+  c.base[0] = 0;
+  for (int k = 0; k < 27; ++k) {
+    const int ns = k < K ? (cnt[k] + seg_len - 1) / seg_len : 0;
+    c.base[k + 1] = c.base[k] + ns;
+    // eighths of the list; the remainder ns % 8 goes to different XCDs for different offsets
+    for (int x = 0; x <= 8; ++x) c.seg_lo[k][x] = (int)(((long long)x * ns + (5 * k) % 8) / 8);
+  }
+  int most = 0;
+  for (int x = 0; x < 8; ++x) {
+    c.xbase[x][0] = 0;
+    for (int k = 0; k < 27; ++k) c.xbase[x][k + 1] = c.xbase[x][k] + (c.seg_lo[k][x + 1] - c.seg_lo[k][x]);
+    if (c.xbase[x][27] > most) most = c.xbase[x][27];
+  }
+  p.slots = c.base[27] > 0 ? c.base[27] : 1;
+  p.grid_items = most;
+  return most;
+}
+
+// counts: groups per offset (the scene's lists), nullptr: every one of the ngroups groups (1x1 maps).  Returns nullptr and
+// the plan, or why there is none.
+inline const char* wgrad_plan(int ngroups, int K, const int* counts, int cin, int cout, const WgradSwitches& sw, WgradPlan& p) {
+  if (cin % 32 || cout % 32 || cin < 32 || cout < 32) return "channels must be multiples of 32";
+  if (K > 27 || ngroups < 1) return "an empty map, or one of more than 27 offsets";
+  // the build with the most accumulator tiles whose channels per lane divide the 16-channel blocks of both sides
+  int best = 0;
+  const int cand[4] = {8, 6, 4, 2};
+  for (int ix = 0; ix < 4; ++ix)
+    for (int iy = 0; iy < 4; ++iy) {
+      const int cx = cand[ix], cy = cand[iy];
+      if ((cin / 16) % cx || (cout / 16) % cy || !wgrad_has_build(cx, cy)) continue;
+      if (cx * cy > best) best = cx * cy, p.cx = cx, p.cy = cy;
+    }
+  if (!best) return "no build of k_wgrad divides these channels";
+  p.nblocks = (cin / (16 * p.cx)) * (cout / (16 * p.cy));
+  // Work items of EQUAL size, the same number on every XCD.  Equal chunks of the ROWS per offset do not give that: rows are
+  // sorted by neighbour mask, so an offset's pairs cluster in some chunks and the (chunk, offset) items differed 0 .. 45
+  // groups, and a chunk's offsets went to one XCD whatever they held: the compute units stood idle a quarter of the
+  // level-0 launch (SQ_BUSY_CU_CYCLES), more on the small levels (level 4: five of eight XCDs had work at all).
+  // The segment length is chosen by a model of the launch: items go to the XCD's workgroup slots in rounds (equal items
+  // finish together), a slot's waves share their SIMD's matrix pipe with the other resident workgroups, every item pays a
+  // fixed prologue / fold / partial write and a pass of the reduce kernel.
+  int* cnt = p.cut.cnt;
+  int cmax = 0;
+  for (int k = 0; k < 27; ++k) {
+    cnt[k] = k < K ? (counts ? counts[k] : ngroups) : 0;
+    if (cnt[k] > cmax) cmax = cnt[k];
+  }
+  if (cmax < 1) cmax = 1;
+  const int regs = p.cx * p.cy * 4 + 4 * (p.cx + p.cy) + 24;                  // accumulators + four row buffers + the rest
+  const int occ = regs > 170 ? 2 : regs > 128 ? 3 : regs > 102 ? 4 : regs > 85 ? 5 : 6;   // workgroups per CU (512 registers per lane and SIMD)
+  const int slots_xcd = 32 * occ;
+  const double step_clk = 4.0 * p.cx * p.cy * 32.0;                            // one group through one wave's MFMAs
+  const double fixed_clk = 9000.0 + 40.0 * p.cx * p.cy;                        // prologue (three dependent fetches) + fold + partial
+  double best_cost = 0;
+  int best_seg = 0;
+  const int kMinSeg = 4, kMaxSlots = 2048;
+  for (int seg = kMinSeg; ; seg = seg + (seg + 7) / 8) {
+    if (seg > cmax) seg = cmax;
+    if (sw.seg > 0) seg = sw.seg < cmax ? sw.seg : cmax;
+    const int most = wgrad_cut(cnt, K, seg, p);
+    if (p.slots <= kMaxSlots || seg == cmax || sw.seg > 0) {
+      const long long wgs = (long long)most * p.nblocks;                       // workgroups of the fullest XCD
+      const int resident = wgs < slots_xcd ? (int)((wgs + 31) / 32) : occ;     // workgroups sharing a CU
+      const double rounds = (double)((wgs + slots_xcd - 1) / slots_xcd);
+      // one wave per SIMD keeps ~0.65 of the matrix pipe busy (it waits for its rows in between), r of them min(0.92, 0.65 r)
+      const double pipe = 0.65 * resident < 0.92 ? 0.65 * resident : 0.92;
+      const double item = ((seg + 3) / 4) * step_clk * resident / pipe + fixed_clk;
+      // a launch + the partials written and read again (measured ~1 TB/s each way next to the input-gradient convs), in clocks
+      const double reduce = 8000.0 + (double)p.slots * cin * cout * 4.0 / 200.0;
+      const double cost = rounds * item + reduce;
+      if (!best_seg || cost < best_cost) best_cost = cost, best_seg = seg;
+    }
+    if (seg >= cmax || sw.seg > 0) break;
+  }
+  wgrad_cut(cnt, K, best_seg, p);
+  p.part_bytes = (size_t)p.slots * cin * cout * sizeof(float);
+  return nullptr;
+}
+// ---- end of planning
 
 struct WgradArgs {
   const float* x;        // [n_in][ldx]
@@ -35,19 +191,10 @@ struct WgradArgs {
   const int* out_map;    // position -> output row (transposed conv: virtual rows), nullptr = identity
   int n_pos;             // positions (output rows of the kernel map)
   int K, cin, cout;
-  // work items: offset k's groups (list[k * list_stride + i], i < cnt[k]; nullptr: groups 0 .. cnt[0] - 1 of a 1x1 map) are
-  // cut into segments of seg_len; segment s of offset k writes partial slot base[k] + s.  Workgroup b runs on XCD b % 8
-  // (hardware) and takes item b / 8 of that XCD's items: offset k's segments seg_lo[k][x] .. seg_lo[k][x + 1] - 1 -- the
-  // x-th eighth of its list, so an XCD's offsets work on about the same stretch of rows -- offset-major; xbase[x][k] =
-  // items of XCD x before offset k.  The host makes the tables (wgrad_plan): every XCD gets the same number of items +- K / 8.
-  const int* list;
+  const int* list;       // [K][list_stride] the groups that have offset k, ascending; nullptr: every group (1x1 maps)
   int list_stride;
-  int seg_len;
-  int cnt[27];
-  int base[28];
-  int xbase[8][28];
-  int seg_lo[27][9];
-  float* part;           // [slots][cin][cout] in fragment layout
+  WgradCut cut;          // the plan's work items (wgrad_plan)
+  float* part;          // [slots][cin][cout] in fragment layout
   float* bias_part;      // BIAS builds (K = 1): [slots][cout] column sums of dy, the bias gradient of an nn.Linear
 };
 
@@ -143,16 +290,16 @@ __global__ void __launch_bounds__(256) k_wgrad(const WgradArgs a) {
   const int nbx = a.cin / (16 * CX);
   // workgroup id -> (XCD x, item i of x) -> (offset k, segment)
   const int xcd = blockIdx.x & 7, item = blockIdx.x >> 3;
-  if (item >= a.xbase[xcd][27]) return;
+  if (item >= a.cut.xbase[xcd][27]) return;
   int k = 0;
 #pragma unroll
-  for (int kk = 1; kk < 27; ++kk) k += item >= a.xbase[xcd][kk] ? 1 : 0;
-  const int seg = a.seg_lo[k][xcd] + (item - a.xbase[xcd][k]);
-  const int cnt = a.cnt[k];
-  const int slot = a.base[k] + seg;
+  for (int kk = 1; kk < 27; ++kk) k += item >= a.cut.xbase[xcd][kk] ? 1 : 0;
+  const int seg = a.cut.seg_lo[k][xcd] + (item - a.cut.xbase[xcd][k]);
+  const int cnt = a.cut.cnt[k];
+  const int slot = a.cut.base[k] + seg;
   const int bx = blockIdx.z % nbx, by = blockIdx.z / nbx;       // channel blocks
-  const int e_begin = seg * a.seg_len;
-  const int e_end = min(cnt, e_begin + a.seg_len);
+  const int e_begin = seg * a.cut.seg_len;
+  const int e_end = min(cnt, e_begin + a.cut.seg_len);
   const int* glist = a.list ? a.list + (size_t)k * a.list_stride : nullptr;
   f32x4 acc[CX][CY];
 #pragma unroll
@@ -440,114 +587,37 @@ __global__ void __launch_bounds__(64 * kRedLanes) k_wgrad_reduce_into(const floa
   *d = accumulate ? *d + s : s;
 }
 
-struct WgradPlan {
-  int cx, cy, nblocks, seg_len, slots, grid_items;     // grid_items: items of the fullest XCD
-  int cnt[27], base[28];
-  int xbase[8][28], seg_lo[27][9];
-  size_t part_bytes;
+// The plan of a (scene map, channel pair) is made once: the search over segment lengths costs the host 13-23 us, an
+// iteration asks ~110 times (each entry point twice: workspace size, then the launch).  serial = 0: a 1x1 map without a scene.
+using PlanKey = std::tuple<uint64_t, int, int, int, int, int>;      // serial, op kind * 16 + level_in, groups, K, cin, cout
+
+// One weight gradient: where its pairs come from -- a kernel map of a scene with its work lists, or the identity map of
+// n_pos rows (no tables, no lists) -- the entry point that asks (for messages), and what keys its plan.
+struct WgradOp {
+  const char* who;
+  uint64_t serial;       // the scene's; 0: no scene
+  int kind_level;        // op kind * 16 + level_in; 0 without a scene
+  const int* counts;     // groups per offset (host copy of the lists' counts); nullptr: every group
+  WgradArgs a;           // K, the row counts, the map's tables and lists; operands and plan are wgrad_run's to add
+  int ngroups() const { return (a.n_pos + 15) / 16; }
 };
 
-// the segment tables of one segment length; returns the items of the fullest XCD
-static int wgrad_cut(const int* cnt, int K, int seg_len, WgradPlan& p) {
-  p.seg_len = seg_len;
-  p.base[0] = 0;
-  for (int k = 0; k < 27; ++k) {
-    const int ns = k < K ? (cnt[k] + seg_len - 1) / seg_len : 0;
-    p.base[k + 1] = p.base[k] + ns;
-    // eighths of the list; the remainder ns % 8 goes to different XCDs for different offsets
-    for (int x = 0; x <= 8; ++x) p.seg_lo[k][x] = (int)(((long long)x * ns + (5 * k) % 8) / 8);
+// x^T dy of n rows (the linear entry points); false: n outside 1 .. 2^30
+static bool wgrad_identity_op(const char* who, int64_t n, WgradOp& op) {
+  if (n <= 0 || n > (int64_t)1 << 30) {
+    set_error("%s: the number of rows must be 1 .. 2^30 (got %lld)", who, (long long)n);
+    return false;
   }
-  int most = 0;
-  for (int x = 0; x < 8; ++x) {
-    p.xbase[x][0] = 0;
-    for (int k = 0; k < 27; ++k) p.xbase[x][k + 1] = p.xbase[x][k] + (p.seg_lo[k][x + 1] - p.seg_lo[k][x]);
-    if (p.xbase[x][27] > most) most = p.xbase[x][27];
-  }
-  p.slots = p.base[27] > 0 ? p.base[27] : 1;
-  p.grid_items = most;
-  return most;
-}
-
-// counts: groups per offset (the scene's lists), nullptr: every one of the ngroups groups (1x1 maps)
-static bool wgrad_plan(int ngroups, int K, const int* counts, int cin, int cout, WgradPlan& p) {
-  if (cin % 32 || cout % 32 || cin < 32 || cout < 32 || K > 27 || ngroups < 1) return false;
-  int best = 0;
-  const int cand[4] = {8, 6, 4, 2};
-  for (int ix = 0; ix < 4; ++ix)
-    for (int iy = 0; iy < 4; ++iy) {
-      const int cx = cand[ix], cy = cand[iy];
-      if ((cin / 16) % cx || (cout / 16) % cy || cx * cy > 36) continue;
-      if (cx * cy > best) best = cx * cy, p.cx = cx, p.cy = cy;
-    }
-  if (!best) return false;
-  p.nblocks = (cin / (16 * p.cx)) * (cout / (16 * p.cy));
-  // Work items of EQUAL size, the same number on every XCD.  Rounds 1-5 cut the ROWS into equal chunks per offset; rows are
-  // sorted by neighbour mask, so an offset's pairs cluster in some chunks and the (chunk, offset) items differed 0 .. 45
-  // groups, and a chunk's offsets went to one XCD whatever they held: the compute units stood idle a quarter of the
-  // level-0 launch (SQ_BUSY_CU_CYCLES), more on the small levels (level 4: five of eight XCDs had work at all).
-  // The segment length is chosen by a model of the launch: items go to the XCD's workgroup slots in rounds (equal items
-  // finish together), a slot's waves share their SIMD's matrix pipe with the other resident workgroups, every item pays a
-  // fixed prologue / fold / partial write and a pass of the reduce kernel.
-  static const int tgt_env = getenv("A3D_WGRAD_SEG") ? atoi(getenv("A3D_WGRAD_SEG")) : 0;     // a fixed segment length: the edge tests rely on it (tests/test_gpu_wgrad_edges.py)
-  long long total = 0;
-  int cmax = 0;
-  for (int k = 0; k < 27; ++k) {
-    p.cnt[k] = k < K ? (counts ? counts[k] : ngroups) : 0;
-    total += p.cnt[k];
-    if (p.cnt[k] > cmax) cmax = p.cnt[k];
-  }
-  if (cmax < 1) cmax = 1;
-  const int regs = p.cx * p.cy * 4 + 4 * (p.cx + p.cy) + 24;                  // accumulators + four row buffers + the rest
-  const int occ = regs > 170 ? 2 : regs > 128 ? 3 : regs > 102 ? 4 : regs > 85 ? 5 : 6;   // workgroups per CU (512 registers per lane and SIMD)
-  const int slots_xcd = 32 * occ;
-  const double step_clk = 4.0 * p.cx * p.cy * 32.0;                            // one group through one wave's MFMAs
-  const double fixed_clk = 9000.0 + 40.0 * p.cx * p.cy;                        // prologue (three dependent fetches) + fold + partial
-  double best_cost = 0;
-  int best_seg = 0;
-  const int kMinSeg = 4, kMaxSlots = 2048;
-  for (int seg = kMinSeg; ; seg = seg + (seg + 7) / 8) {
-    if (seg > cmax) seg = cmax;
-    if (tgt_env > 0) seg = tgt_env < cmax ? tgt_env : cmax;
-    const int most = wgrad_cut(p.cnt, K, seg, p);
-    if (p.slots <= kMaxSlots || seg == cmax || tgt_env > 0) {
-      const long long wgs = (long long)most * p.nblocks;                       // workgroups of the fullest XCD
-      const int resident = wgs < slots_xcd ? (int)((wgs + 31) / 32) : occ;     // workgroups sharing a CU
-      const double rounds = (double)((wgs + slots_xcd - 1) / slots_xcd);
-      // one wave per SIMD keeps ~0.65 of the matrix pipe busy (it waits for its rows in between), r of them min(0.92, 0.65 r)
-      const double pipe = 0.65 * resident < 0.92 ? 0.65 * resident : 0.92;
-      const double item = ((seg + 3) / 4) * step_clk * resident / pipe + fixed_clk;
-      // a launch + the partials written and read again (measured ~1 TB/s each way next to the input-gradient convs), in clocks
-      const double reduce = 8000.0 + (double)p.slots * cin * cout * 4.0 / 200.0;
-      const double cost = rounds * item + reduce;
-      if (!best_seg || cost < best_cost) best_cost = cost, best_seg = seg;
-    }
-    if (seg >= cmax || tgt_env > 0) break;
-  }
-  wgrad_cut(p.cnt, K, best_seg, p);
-  p.part_bytes = (size_t)p.slots * cin * cout * sizeof(float);
+  op = WgradOp{};
+  op.who = who, op.a.K = 1, op.a.n_in = op.a.n_out = op.a.n_pos = (int)n;
   return true;
 }
 
-// The plan of a (scene map, channel pair) is made once: the search over segment lengths costs the host 13-23 us, an
-// iteration asks ~110 times (each entry point twice: workspace size, then the launch).  serial = 0: a 1x1 map without a scene.
-struct PlanKey {
-  uint64_t serial;
-  int kind_level, ngroups, K, cin, cout;
-  bool operator==(const PlanKey& o) const {
-    return serial == o.serial && kind_level == o.kind_level && ngroups == o.ngroups && K == o.K && cin == o.cin && cout == o.cout;
-  }
-};
-struct PlanKeyHash {
-  size_t operator()(const PlanKey& k) const {
-    uint64_t h = k.serial * 0x9E3779B97F4A7C15ull;
-    for (int v : {k.kind_level, k.ngroups, k.K, k.cin, k.cout}) h = (h ^ (uint64_t)(uint32_t)v) * 0x100000001B3ull;
-    return (size_t)h;
-  }
-};
-static bool wgrad_plan_cached(uint64_t serial, int kind_level, int ngroups, int K, const int* counts, int cin, int cout, WgradPlan& p) {
+// the op's plan, from the cache; false (and the planner's reason as the error): there is none
+static bool wgrad_op_plan(const WgradOp& op, int cin, int cout, WgradPlan& p) {
   static std::mutex mu;
-  static std::unordered_map<PlanKey, WgradPlan, PlanKeyHash> cache;
-  const PlanKey key{serial, kind_level, ngroups, K, cin, cout};
+  static std::map<PlanKey, WgradPlan> cache;
+  const PlanKey key{op.serial, op.kind_level, op.ngroups(), op.a.K, cin, cout};
   {
     std::lock_guard<std::mutex> lock(mu);
     auto it = cache.find(key);
@@ -556,25 +626,25 @@ static bool wgrad_plan_cached(uint64_t serial, int kind_level, int ngroups, int 
       return true;
     }
   }
-  if (!wgrad_plan(ngroups, K, counts, cin, cout, p)) return false;
+  if (const char* why = wgrad_plan(op.ngroups(), op.a.K, op.counts, cin, cout, wgrad_switches(), p)) {
+    set_error("%s: %s (got %d -> %d) for %d offsets and %d groups", op.who, why, cin, cout, op.a.K, op.ngroups());
+    return false;
+  }
   std::lock_guard<std::mutex> lock(mu);
   if (cache.size() > 2048) cache.clear();      // scenes come and go (one per training iteration): the plans of dead ones are never asked for again
   cache.emplace(key, p);
   return true;
 }
 
-static void wgrad_fill(const WgradPlan& p, WgradArgs& a) {
-  a.seg_len = p.seg_len;
-  memcpy(a.cnt, p.cnt, sizeof(a.cnt));
-  memcpy(a.base, p.base, sizeof(a.base));
-  memcpy(a.xbase, p.xbase, sizeof(a.xbase));
-  memcpy(a.seg_lo, p.seg_lo, sizeof(a.seg_lo));
+// The workspace of a plan: the partials, then (bias: the linear entry point that also sums dy's columns) the bias partials.
+static size_t wgrad_bias_offset(const WgradPlan& p) { return align256(p.part_bytes); }
+static size_t wgrad_workspace(const WgradPlan& p, int cout, bool bias) {
+  return bias ? wgrad_bias_offset(p) + align256((size_t)p.slots * cout * sizeof(float)) : p.part_bytes;
 }
-static void wgrad_reduce_launch(const float* part, const WgradPlan& p, int K, int cin, int cout, float* dw, hipStream_t st) {
-  SlotBase sb;
-  memcpy(sb.base, p.base, sizeof(sb.base));
-  const unsigned units = (unsigned)(K * p.nblocks * p.cx * (p.cy > 4 ? 2 : 1));
-  k_wgrad_reduce<<<units, 64 * NW, 0, st>>>(part, sb, cin, cout, p.cx, p.cy, dw);
+// what a *_workspace_bytes entry point answers for the op: 0 (and the planner's reason as the error) without a plan
+static size_t wgrad_op_bytes(const WgradOp& op, int cin, int cout, bool bias) {
+  WgradPlan p;
+  return wgrad_op_plan(op, cin, cout, p) ? wgrad_workspace(p, cout, bias) + 256 : 0;
 }
 
 // a buffer descriptor spans < 4 GB and the "no pair" offset must lie past the end with room for a row's column offset
@@ -582,40 +652,63 @@ static bool wgrad_fits(const WgradArgs& a) {
   return (size_t)a.n_in * a.ldx * 4 <= (size_t)kNoRow && (size_t)a.n_out * a.ldy * 4 <= (size_t)kNoRow && a.cin <= 1024 && a.cout <= 1024;
 }
 
-template <int CX, int CY>
-static void wgrad_launch_one(const WgradArgs& a, dim3 grid, bool bias, bool wide, hipStream_t st) {
-  const size_t lds = (size_t)16 * CX * 16 * CY * sizeof(float);
-#define A3D_WG1(B_, W_)                                       \
-  {                                                           \
-    A3D_ALLOW_LDS(64 * 1024, (k_wgrad<CX, CY, B_, W_>));      \
-    k_wgrad<CX, CY, B_, W_><<<grid, 256, lds, st>>>(a);       \
-  }
-  if (bias) {
-    if (wide) A3D_WG1(true, true) else A3D_WG1(true, false)
-  } else {
-    if (wide) A3D_WG1(false, true) else A3D_WG1(false, false)
-  }
-#undef A3D_WG1
+template <int CX, int CY, bool BIAS, bool WIDE>
+static void wgrad_launch_one(const WgradArgs& a, dim3 grid, hipStream_t st) {
+  A3D_ALLOW_LDS(64 * 1024, (k_wgrad<CX, CY, BIAS, WIDE>));
+  k_wgrad<CX, CY, BIAS, WIDE><<<grid, 256, (size_t)16 * CX * 16 * CY * sizeof(float), st>>>(a);
 }
 
 // the kernel of the plan's channels-per-lane pair; false: there is none
 static bool wgrad_launch(const WgradArgs& a, const WgradPlan& p, dim3 grid, bool bias, hipStream_t st) {
-  static const bool force_wide = getenv("A3D_WGRAD_WIDE") && atoi(getenv("A3D_WGRAD_WIDE")) != 0;   // tests: the pointer build on small operands
-  const bool wide = force_wide || !wgrad_fits(a);
-#define A3D_WG(CX_, CY_)                                     \
-  if (p.cx == CX_ && p.cy == CY_) {                          \
-    wgrad_launch_one<CX_, CY_>(a, grid, bias, wide, st);     \
-    return true;                                             \
+  const bool wide = wgrad_switches().wide || !wgrad_fits(a);
+#define A3D_WG(CX_, CY_)                                                                                      \
+  if (p.cx == CX_ && p.cy == CY_) {                                                                           \
+    bias ? (wide ? wgrad_launch_one<CX_, CY_, true, true> : wgrad_launch_one<CX_, CY_, true, false>)(a, grid, st) \
+         : (wide ? wgrad_launch_one<CX_, CY_, false, true> : wgrad_launch_one<CX_, CY_, false, false>)(a, grid, st); \
+    return true;                                                                                              \
   }
-  A3D_WG(2, 2) A3D_WG(2, 4) A3D_WG(2, 6) A3D_WG(2, 8) A3D_WG(4, 2) A3D_WG(4, 4) A3D_WG(4, 6) A3D_WG(4, 8)
-  A3D_WG(6, 2) A3D_WG(6, 4) A3D_WG(6, 6) A3D_WG(8, 2) A3D_WG(8, 4)
+  A3D_WGRAD_BUILDS(A3D_WG)
 #undef A3D_WG
   return false;
 }
 
+// The partials of op's weight gradient, x^T dy per offset, into the workspace: the operand checks, the plan, the kernel's
+// arguments, the grid and the launch of k_wgrad.  bias_room: the workspace has the bias partials behind dW's; bias: the
+// BIAS build fills them with dy's column sums per slot (K = 1).  The caller's reducer turns p.slots partials into dW.
+static int wgrad_run(const WgradOp& op, const float* x, int ldx, const float* dy, int ldy, int cin, int cout, const float* dw,
+                     void* workspace, size_t workspace_bytes, bool bias_room, bool bias, hipStream_t st, WgradPlan& p) {
+  if (!x || !dy || !dw || !workspace || ldx < cin || ldy < cout || (ldx & 1) || (ldy & 1)) {
+    set_error("%s: bad arguments (a NULL pointer, or a leading dimension that is odd or below the channel count)", op.who);
+    return A3D_ERR_INVALID;
+  }
+  if (!wgrad_op_plan(op, cin, cout, p)) return A3D_ERR_INVALID;
+  const size_t need = wgrad_workspace(p, cout, bias_room);
+  if (workspace_bytes < need || ((uintptr_t)workspace & 15)) {
+    set_error("%s: workspace too small or misaligned (%zu < %zu)", op.who, workspace_bytes, need);
+    return A3D_ERR_WORKSPACE;
+  }
+  WgradArgs a = op.a;
+  a.x = x, a.dy = dy, a.ldx = ldx, a.ldy = ldy, a.cin = cin, a.cout = cout;
+  a.cut = p.cut;
+  a.part = (float*)workspace;
+  if (bias_room) a.bias_part = (float*)((char*)workspace + wgrad_bias_offset(p));
+  const dim3 grid((unsigned)(p.grid_items * 8), 1, p.nblocks);
+  if (!wgrad_launch(a, p, grid, bias, st)) {
+    set_error("%s: no kernel for %d x %d channels per lane", op.who, p.cx, p.cy);
+    return A3D_ERR_UNSUPPORTED;
+  }
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+static void wgrad_reduce_launch(const float* part, const WgradPlan& p, int K, int cin, int cout, float* dw, hipStream_t st) {
+  SlotBase sb;
+  memcpy(sb.base, p.cut.base, sizeof(sb.base));
+  const unsigned units = (unsigned)(K * p.nblocks * p.cx * (p.cy > 4 ? 2 : 1));
+  k_wgrad_reduce<<<units, 64 * NW, 0, st>>>(part, sb, cin, cout, p.cx, p.cy, dw);
+}
+
 // ---- the read-back of the work lists' counts: pinned buffer + event, pooled over the process (hipHostMalloc / hipEventCreate
 // cost more than the read-back they serve)
-constexpr int kListJobs = 5 * 27 + 4 * 8 + 4 * 8;
 struct ListReadback {
   int* counts = nullptr;      // pinned [kListJobs]
   hipEvent_t done = nullptr;
@@ -653,12 +746,8 @@ static int wgrad_lists_finish(a3d_scene* s) {
   if (!r) return A3D_OK;
   A3D_HIP_CHECK(hipEventSynchronize(r->done));
   int j = 0;
-  for (int kind = 0; kind < 3; ++kind)
-    for (int l = 0; l < A3D_NUM_LEVELS; ++l) {
-      if (kind > 0 && l >= A3D_NUM_LEVELS - 1) continue;
-      const int K = kind == 0 ? 27 : 8;
-      for (int k = 0; k < K; ++k) s->wg_count[kind][l][k] = r->counts[j++];
-    }
+  for (const WgradMap& m : kWgradMaps)
+    for (int k = 0; k < m.K; ++k) s->wg_count[m.list_kind][m.level][k] = r->counts[j++];
   s->wg_pending = nullptr;
   s->wg_ready = true;
   readback_put(r);
@@ -672,62 +761,48 @@ void wgrad_scene_release(a3d_scene* s) {
   readback_put(r);
 }
 
-static int wgrad_tables(const a3d_scene* s, int kind, int level_in, WgradArgs& a, const int** counts, int* ngroups) {
+// the op of a scene's kernel map: A3D_OP_CONV3 / DOWN / UP from level_in, or the 1x1 map of the level's rows (A3D_OP_LINEAR)
+static int wgrad_scene_op(const a3d_scene* s, int kind, int level_in, WgradOp& op) {
   if (!s || level_in < 0 || level_in >= A3D_NUM_LEVELS) {
     set_error("a3d_conv_wgrad: bad scene / level");
     return A3D_ERR_INVALID;
   }
-  a.tab = nullptr, a.out_map = nullptr, a.list = nullptr, a.list_stride = 0;
-  int lk = -1, ll = 0;       // list kind / owning level
-  switch (kind) {
-    case A3D_OP_CONV3:
-      a.K = 27, a.n_in = a.n_out = a.n_pos = s->lv[level_in].n;
-      a.tab = s->lv[level_in].nbr27, a.tab_stride = s->lv[level_in].npad;
-      lk = 0, ll = level_in;
-      break;
-    case A3D_OP_DOWN:
-      if (level_in >= A3D_NUM_LEVELS - 1) goto bad;
-      a.K = 8, a.n_in = s->lv[level_in].n, a.n_out = a.n_pos = s->lv[level_in + 1].n;
-      a.tab = s->lv[level_in].child8, a.tab_stride = s->lv[level_in + 1].npad;
-      lk = 1, ll = level_in;
-      break;
-    case A3D_OP_UP:
-      if (level_in < 1) goto bad;
-      a.K = 8, a.n_in = s->lv[level_in].n, a.n_out = a.n_pos = s->lv[level_in - 1].n;
-      a.tab = s->lv[level_in - 1].up8, a.tab_stride = s->lv[level_in - 1].npad;
-      a.out_map = s->lv[level_in - 1].up_rows;
-      lk = 2, ll = level_in - 1;
-      break;
-    case A3D_OP_LINEAR:
-      a.K = 1, a.n_in = a.n_out = a.n_pos = s->lv[level_in].n;
-      break;
-    default:
-    bad:
-      set_error("a3d_conv_wgrad: kind %d does not exist at level %d", kind, level_in);
-      return A3D_ERR_INVALID;
+  op = WgradOp{};
+  op.who = "a3d_conv_wgrad", op.serial = s->serial, op.kind_level = kind * 16 + level_in;
+  WgradArgs& a = op.a;
+  a.n_in = s->lv[level_in].n;
+  if (kind == A3D_OP_LINEAR) {
+    a.K = 1, a.n_out = a.n_pos = a.n_in;
+    return A3D_OK;
   }
-  *ngroups = (a.n_pos + 15) / 16;
-  *counts = nullptr;
-  if (lk >= 0) {
-    if (s->wg_pending) {                 // the lists were requested; their counts arrive now at the latest
-      const int rc = wgrad_lists_finish(const_cast<a3d_scene*>(s));
-      if (rc) return rc;
-    }
-    if (!s->wg_ready) {
-      set_error("a3d_conv_wgrad: the scene has no weight-gradient work lists (call a3d_scene_build_wgrad_lists once per scene)");
-      return A3D_ERR_INVALID;
-    }
-    a.list = s->wg_list[lk][ll], a.list_stride = s->wg_stride[lk][ll];
-    *counts = s->wg_count[lk][ll];
+  const int mi = wgrad_map_of(kind, level_in);
+  if (mi < 0) {
+    set_error("a3d_conv_wgrad: kind %d does not exist at level %d", kind, level_in);
+    return A3D_ERR_INVALID;
   }
+  const WgradMap& m = kWgradMaps[mi];
+  const Level& own = s->lv[m.level];
+  const Level& pos = s->lv[m.level + (m.pos_above ? 1 : 0)];
+  a.K = m.K, a.n_out = a.n_pos = pos.n;
+  a.tab = m.list_kind == 0 ? own.nbr27 : m.list_kind == 1 ? own.child8 : own.up8, a.tab_stride = pos.npad;
+  a.out_map = m.list_kind == 2 ? own.up_rows : nullptr;
+  if (s->wg_pending) {                 // the lists were requested; their counts arrive now at the latest
+    const int rc = wgrad_lists_finish(const_cast<a3d_scene*>(s));
+    if (rc) return rc;
+  }
+  if (!s->wg_ready) {
+    set_error("a3d_conv_wgrad: the scene has no weight-gradient work lists (call a3d_scene_build_wgrad_lists once per scene)");
+    return A3D_ERR_INVALID;
+  }
+  a.list = s->wg_list[m.list_kind][m.level], a.list_stride = s->wg_stride[m.list_kind][m.level];
+  op.counts = s->wg_count[m.list_kind][m.level];
   return A3D_OK;
 }
 
 // ---- the work lists: for every (map kind, level, offset k) the 16-position groups that have offset k, ascending.  One
 // workgroup per (kind, level, k) walks the level's group masks 1024 at a time (ballot + prefix inside the wave, the 16
 // waves' totals through LDS) and appends; the counts go to the host once per scene (the launch plan needs them).
-constexpr int kListMaps = 5 + 4 + 4;          // 3^3 maps of five levels, stride-2 and transposed maps of four
-struct ListSet {
+struct ListSet {                               // per map of kWgradMaps
   const uint32_t* gmask[kListMaps];
   int* list[kListMaps];                        // [K][stride]
   int ngroups[kListMaps], stride[kListMaps];
@@ -923,92 +998,6 @@ __global__ void __launch_bounds__(256) k_stem_wgrad_mfma(const Level lv, const f
 
 using namespace a3d;
 
-// dW [cin][cout] = x^T dy for plain row-major matrices of n rows (the nn.Linear layers of the decoder that run over all
-// points or over the queries: attention_block.py, agile3d.py:51-55): the 1x1 case of a3d_conv_wgrad without a scene
-extern "C" size_t a3d_linear_wgrad_workspace_bytes(int64_t n, int cin, int cout) {
-  WgradPlan p;
-  if (n <= 0 || n > (int64_t)1 << 30 || !wgrad_plan_cached(0, 0, (int)((n + 15) / 16), 1, nullptr, cin, cout, p)) {
-    set_error("a3d_linear_wgrad: channels must be multiples of 32 (got %d -> %d)", cin, cout);
-    return 0;
-  }
-  return p.part_bytes + 256;
-}
-extern "C" int a3d_linear_wgrad(const float* x_dev, int ldx, const float* dy_dev, int ldy, int64_t n, int cin, int cout,
-                                float* dw_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  WgradPlan p;
-  if (!x_dev || !dy_dev || !dw_dev || !workspace_dev || n <= 0 || n > (int64_t)1 << 30 || ldx < cin || ldy < cout ||
-      (ldx & 1) || (ldy & 1) || !wgrad_plan_cached(0, 0, (int)((n + 15) / 16), 1, nullptr, cin, cout, p)) {
-    set_error("a3d_linear_wgrad: bad arguments (channels multiples of 32, even leading dimensions)");
-    return A3D_ERR_INVALID;
-  }
-  if (workspace_bytes < p.part_bytes || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_linear_wgrad: workspace too small or misaligned");
-    return A3D_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  WgradArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x_dev, a.dy = dy_dev, a.ldx = ldx, a.ldy = ldy, a.cin = cin, a.cout = cout;
-  a.K = 1, a.n_in = a.n_out = a.n_pos = (int)n;
-  wgrad_fill(p, a);
-  a.part = (float*)workspace_dev;
-  const dim3 grid((unsigned)(p.grid_items * 8), 1, p.nblocks);
-  if (!wgrad_launch(a, p, grid, false, st)) {
-    set_error("a3d_linear_wgrad: no kernel for %d x %d channels per lane", p.cx, p.cy);
-    return A3D_ERR_UNSUPPORTED;
-  }
-  A3D_LAUNCH_CHECK();
-  wgrad_reduce_launch(a.part, p, 1, cin, cout, dw_dev, st);
-  A3D_LAUNCH_CHECK();
-  return A3D_OK;
-}
-
-// the same gradient written where the caller keeps it: dW as [cin][cout] or [cout][cin] (transposed = 1, nn.Linear.weight's
-// layout; a row slice of a packed in_proj matrix is such a block at an offset) with leading dimension ld_dw, assigned or
-// added (accumulate); db_dev != nullptr: the bias gradient (column sums of dy) from the SAME pass over dy -- what took a
-// transposing copy, a zero-filled full-size matrix + slice copy + add per in_proj slice and two column-sum launches per layer
-extern "C" size_t a3d_linear_wgrad_into_workspace_bytes(int64_t n, int cin, int cout) {
-  WgradPlan p;
-  if (n <= 0 || n > (int64_t)1 << 30 || !wgrad_plan_cached(0, 0, (int)((n + 15) / 16), 1, nullptr, cin, cout, p)) {
-    set_error("a3d_linear_wgrad_into: channels must be multiples of 32 (got %d -> %d)", cin, cout);
-    return 0;
-  }
-  return align256(p.part_bytes) + align256((size_t)p.slots * cout * sizeof(float)) + 256;
-}
-extern "C" int a3d_linear_wgrad_into(const float* x_dev, int ldx, const float* dy_dev, int ldy, int64_t n, int cin, int cout,
-                                     float* dw_dev, int ld_dw, int transposed, int accumulate, float* db_dev, int db_accumulate,
-                                     void* workspace_dev, size_t workspace_bytes, void* stream) {
-  WgradPlan p;
-  if (!x_dev || !dy_dev || !dw_dev || !workspace_dev || n <= 0 || n > (int64_t)1 << 30 || ldx < cin || ldy < cout ||
-      (ldx & 1) || (ldy & 1) || ld_dw < (transposed ? cin : cout) || !wgrad_plan_cached(0, 0, (int)((n + 15) / 16), 1, nullptr, cin, cout, p)) {
-    set_error("a3d_linear_wgrad_into: bad arguments (channels multiples of 32, even leading dimensions, ld_dw >= row length)");
-    return A3D_ERR_INVALID;
-  }
-  if (workspace_bytes < a3d_linear_wgrad_into_workspace_bytes(n, cin, cout) - 256 || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_linear_wgrad_into: workspace too small or misaligned");
-    return A3D_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  WgradArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x_dev, a.dy = dy_dev, a.ldx = ldx, a.ldy = ldy, a.cin = cin, a.cout = cout;
-  a.K = 1, a.n_in = a.n_out = a.n_pos = (int)n;
-  wgrad_fill(p, a);
-  a.part = (float*)workspace_dev;
-  a.bias_part = (float*)((char*)workspace_dev + align256(p.part_bytes));
-  const dim3 grid((unsigned)(p.grid_items * 8), 1, p.nblocks);
-  if (!wgrad_launch(a, p, grid, db_dev != nullptr, st)) {
-    set_error("a3d_linear_wgrad_into: no kernel for %d x %d channels per lane", p.cx, p.cy);
-    return A3D_ERR_UNSUPPORTED;
-  }
-  A3D_LAUNCH_CHECK();
-  const int all = cin * cout + (db_dev ? cout : 0);
-  k_wgrad_reduce_into<<<(unsigned)((all + 63) / 64), 64 * kRedLanes, 0, st>>>(a.part, a.bias_part, p.slots, cin, cout, p.cx, p.cy, dw_dev,
-                                                                            ld_dw, transposed, accumulate, db_dev, db_accumulate);
-  A3D_LAUNCH_CHECK();
-  return A3D_OK;
-}
-
 extern "C" size_t a3d_stem_wgrad_workspace_bytes(int kernel_volume) {
   if (kernel_volume != 125 && kernel_volume != 27) return 0;
   // the larger of the two paths: per-offset splits (hash / 3^3) or the matrix-core kernel's per-workgroup partials
@@ -1016,12 +1005,14 @@ extern "C" size_t a3d_stem_wgrad_workspace_bytes(int kernel_volume) {
   const size_t b = (size_t)kStemMfmaWgs * 384 * 32 * sizeof(float);
   return (a > b ? a : b) + 256;
 }
+// the matrix-core path's workspace: the workgroups' partials, then the colours in Morton order (16 bytes per level-0 row)
+static size_t stem_mfma_colours_offset() { return align256((size_t)kStemMfmaWgs * 384 * 32 * sizeof(float)); }
+static size_t stem_mfma_bytes(const Level& lv0) { return stem_mfma_colours_offset() + (size_t)lv0.npad * 16; }
 extern "C" size_t a3d_stem_wgrad_scene_workspace_bytes(const a3d_scene* s, int kernel_volume) {
   const size_t base = a3d_stem_wgrad_workspace_bytes(kernel_volume);
   if (!s || !base) return 0;
-  return align256((size_t)kStemMfmaWgs * 384 * 32 * sizeof(float)) + (size_t)s->lv[0].npad * 16 + 256 > base
-             ? align256((size_t)kStemMfmaWgs * 384 * 32 * sizeof(float)) + (size_t)s->lv[0].npad * 16 + 256
-             : base;
+  const size_t mfma = stem_mfma_bytes(s->lv[0]) + 256;
+  return mfma > base ? mfma : base;
 }
 // Morton-ordered colours for the matrix-core path (spconv.hip's k_gather_feats: feats4[f] = colours of Morton row f)
 __global__ void k_stem_gather_morton(const float* __restrict__ feats3, const int* __restrict__ orig_row, const int* __restrict__ perm,
@@ -1048,11 +1039,9 @@ extern "C" int a3d_stem_wgrad(const a3d_scene* s, const float* feats3_dev, const
   const int ks = kernel_volume == 125 ? 5 : 3;
   const int total = kernel_volume * 96;
   const Level& lv0 = s->lv[0];
-  const size_t part_bytes = align256((size_t)kStemMfmaWgs * 384 * 32 * sizeof(float));
-  if (ks == 5 && lv0.grid && lv0.n < (1 << 25) && workspace_bytes >= part_bytes + (size_t)lv0.npad * 16) {
-    // matrix-core path: colours in Morton order (behind the partials in the workspace: a3d_stem_wgrad_scene_workspace_bytes),
-    // one [384 x 32] accumulator per wave
-    f32x4* f4 = (f32x4*)((char*)workspace_dev + part_bytes);
+  if (ks == 5 && lv0.grid && lv0.n < (1 << 25) && workspace_bytes >= stem_mfma_bytes(lv0)) {
+    // matrix-core path (a workspace of a3d_stem_wgrad_scene_workspace_bytes has the room): one [384 x 32] accumulator per wave
+    f32x4* f4 = (f32x4*)((char*)workspace_dev + stem_mfma_colours_offset());
     k_stem_gather_morton<<<(lv0.n + 255) / 256, 256, 0, st>>>(feats3_dev, s->orig_row, lv0.perm, lv0.n, f4);
     const int steps = (lv0.n + 3) / 4;
     int wgs = (steps + 3) / 4;
@@ -1070,83 +1059,97 @@ extern "C" int a3d_stem_wgrad(const a3d_scene* s, const float* feats3_dev, const
   return A3D_OK;
 }
 
-extern "C" size_t a3d_conv_wgrad_workspace_bytes(const a3d_scene* s, int kind, int level_in, int cin, int cout) {
-  WgradArgs a;
-  const int* counts;
-  int ngroups;
-  if (wgrad_tables(s, kind, level_in, a, &counts, &ngroups) != A3D_OK) return 0;
-  WgradPlan p;
-  if (!wgrad_plan_cached(s->serial, kind * 16 + level_in, ngroups, a.K, counts, cin, cout, p)) {
-    set_error("a3d_conv_wgrad: channels must be multiples of 32 (got %d -> %d)", cin, cout);
-    return 0;
-  }
-  return p.part_bytes + 256;
-}
+// ---- the three entry points of k_wgrad: each names its op, asks for the plan's workspace or runs it (wgrad_run), and
+// launches its reducer
 
+// dW[k] of a scene's kernel map, [K][cin][cout]
+extern "C" size_t a3d_conv_wgrad_workspace_bytes(const a3d_scene* s, int kind, int level_in, int cin, int cout) {
+  WgradOp op;
+  return wgrad_scene_op(s, kind, level_in, op) == A3D_OK ? wgrad_op_bytes(op, cin, cout, false) : 0;
+}
 extern "C" int a3d_conv_wgrad(const a3d_scene* s, int kind, int level_in, const float* x_dev, int ldx,
                               const float* dy_dev, int ldy, int cin, int cout, float* dw_dev, void* workspace_dev,
                               size_t workspace_bytes, void* stream) {
-  WgradArgs a;
-  memset(&a, 0, sizeof(a));
-  const int* counts;
-  int ngroups;
-  int rc = wgrad_tables(s, kind, level_in, a, &counts, &ngroups);
-  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  WgradOp op;
   WgradPlan p;
-  if (!x_dev || !dy_dev || !dw_dev || !workspace_dev || ldx < cin || ldy < cout || (ldx & 1) || (ldy & 1) ||
-      !wgrad_plan_cached(s->serial, kind * 16 + level_in, ngroups, a.K, counts, cin, cout, p)) {
-    set_error("a3d_conv_wgrad: bad arguments (channels multiples of 32, even leading dimensions)");
+  int rc = wgrad_scene_op(s, kind, level_in, op);
+  if (rc == A3D_OK) rc = wgrad_run(op, x_dev, ldx, dy_dev, ldy, cin, cout, dw_dev, workspace_dev, workspace_bytes, false, false, st, p);
+  if (rc) return rc;
+  wgrad_reduce_launch((const float*)workspace_dev, p, op.a.K, cin, cout, dw_dev, st);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+// dW [cin][cout] = x^T dy for plain row-major matrices of n rows (the nn.Linear layers of the decoder that run over all
+// points or over the queries: attention_block.py, agile3d.py:51-55): the 1x1 case of a3d_conv_wgrad without a scene
+extern "C" size_t a3d_linear_wgrad_workspace_bytes(int64_t n, int cin, int cout) {
+  WgradOp op;
+  return wgrad_identity_op("a3d_linear_wgrad", n, op) ? wgrad_op_bytes(op, cin, cout, false) : 0;
+}
+extern "C" int a3d_linear_wgrad(const float* x_dev, int ldx, const float* dy_dev, int ldy, int64_t n, int cin, int cout,
+                                float* dw_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WgradOp op;
+  WgradPlan p;
+  if (!wgrad_identity_op("a3d_linear_wgrad", n, op)) return A3D_ERR_INVALID;
+  const int rc = wgrad_run(op, x_dev, ldx, dy_dev, ldy, cin, cout, dw_dev, workspace_dev, workspace_bytes, false, false, st, p);
+  if (rc) return rc;
+  wgrad_reduce_launch((const float*)workspace_dev, p, 1, cin, cout, dw_dev, st);
+  A3D_LAUNCH_CHECK();
+  return A3D_OK;
+}
+
+// the same gradient written where the caller keeps it: dW as [cin][cout] or [cout][cin] (transposed = 1, nn.Linear.weight's
+// layout; a row slice of a packed in_proj matrix is such a block at an offset) with leading dimension ld_dw, assigned or
+// added (accumulate); db_dev != nullptr: the bias gradient (column sums of dy) from the SAME pass over dy -- what took a
+// transposing copy, a zero-filled full-size matrix + slice copy + add per in_proj slice and two column-sum launches per layer
+extern "C" size_t a3d_linear_wgrad_into_workspace_bytes(int64_t n, int cin, int cout) {
+  WgradOp op;
+  return wgrad_identity_op("a3d_linear_wgrad_into", n, op) ? wgrad_op_bytes(op, cin, cout, true) : 0;
+}
+extern "C" int a3d_linear_wgrad_into(const float* x_dev, int ldx, const float* dy_dev, int ldy, int64_t n, int cin, int cout,
+                                     float* dw_dev, int ld_dw, int transposed, int accumulate, float* db_dev, int db_accumulate,
+                                     void* workspace_dev, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  WgradOp op;
+  WgradPlan p;
+  if (!wgrad_identity_op("a3d_linear_wgrad_into", n, op)) return A3D_ERR_INVALID;
+  if (ld_dw < (transposed ? cin : cout)) {
+    set_error("a3d_linear_wgrad_into: ld_dw %d is below the row length %d", ld_dw, transposed ? cin : cout);
     return A3D_ERR_INVALID;
   }
-  if (workspace_bytes < p.part_bytes || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_conv_wgrad: workspace too small or misaligned (%zu < %zu)", workspace_bytes, p.part_bytes);
-    return A3D_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  a.x = x_dev, a.dy = dy_dev, a.ldx = ldx, a.ldy = ldy, a.cin = cin, a.cout = cout;
-  wgrad_fill(p, a);
-  a.part = (float*)workspace_dev;
-  const dim3 grid((unsigned)(p.grid_items * 8), 1, p.nblocks);
-  if (!wgrad_launch(a, p, grid, false, st)) {
-    set_error("a3d_conv_wgrad: no kernel for %d x %d channels per lane", p.cx, p.cy);
-    return A3D_ERR_UNSUPPORTED;
-  }
-  A3D_LAUNCH_CHECK();
-  wgrad_reduce_launch(a.part, p, a.K, cin, cout, dw_dev, st);
+  const int rc = wgrad_run(op, x_dev, ldx, dy_dev, ldy, cin, cout, dw_dev, workspace_dev, workspace_bytes, true, db_dev != nullptr, st, p);
+  if (rc) return rc;
+  const int all = cin * cout + (db_dev ? cout : 0);
+  k_wgrad_reduce_into<<<(unsigned)((all + 63) / 64), 64 * kRedLanes, 0, st>>>(
+      (const float*)workspace_dev, (const float*)((char*)workspace_dev + wgrad_bias_offset(p)), p.slots, cin, cout, p.cx, p.cy, dw_dev,
+      ld_dw, transposed, accumulate, db_dev, db_accumulate);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
 
 // ---- the scene's weight-gradient work lists (once per scene, before the first a3d_conv_wgrad on it) ----------------------
-// the maps in (kind, level) order; lists packed behind one another with a stride of the level's group count
-static int wgrad_list_set(const a3d_scene* s, int* base_dev, ListSet* S, size_t* ints) {
-  int m = 0, nj = 0;
+// the lists of kWgradMaps' maps packed behind one another from base_dev (nullptr: sizes only), each [K][stride] with the
+// map's group count rounded up to 64 as stride; returns the ints of all of them.  The counts follow at the next 256 bytes.
+static size_t wgrad_list_set(const a3d_scene* s, int* base_dev, ListSet& S) {
   size_t off = 0;
-  for (int kind = 0; kind < 3; ++kind)
-    for (int l = 0; l < A3D_NUM_LEVELS; ++l) {
-      if (kind > 0 && l >= A3D_NUM_LEVELS - 1) continue;
-      const Level& lv = s->lv[l];
-      const int K = kind == 0 ? 27 : 8;
-      const int npos = kind == 1 ? s->lv[l + 1].n : lv.n;
-      const int ng = (npos + 15) / 16;
-      const int stride = (ng + 63) / 64 * 64;
-      if (S) {
-        S->gmask[m] = kind == 0 ? lv.gmask27 : kind == 1 ? lv.gmask_down : lv.gmask_up;
-        S->list[m] = base_dev + off;
-        S->ngroups[m] = ng, S->stride[m] = stride, S->first_job[m] = nj;
-      }
-      off += (size_t)K * stride;
-      nj += K, ++m;
-    }
-  if (S) S->first_job[m] = nj;
-  *ints = off;
-  return nj;
+  for (int m = 0; m < kListMaps; ++m) {
+    const WgradMap& map = kWgradMaps[m];
+    const Level& own = s->lv[map.level];
+    const int ng = (s->lv[map.level + (map.pos_above ? 1 : 0)].n + 15) / 16;
+    S.gmask[m] = map.list_kind == 0 ? own.gmask27 : map.list_kind == 1 ? own.gmask_down : own.gmask_up;
+    S.list[m] = base_dev ? base_dev + off : nullptr;
+    S.ngroups[m] = ng, S.stride[m] = (ng + 63) / 64 * 64, S.first_job[m] = wgrad_jobs_before(m);
+    off += (size_t)map.K * S.stride[m];
+  }
+  S.first_job[kListMaps] = kListJobs;
+  return off;
 }
 extern "C" size_t a3d_scene_wgrad_lists_bytes(const a3d_scene* s) {
   if (!s) return 0;
-  size_t ints;
-  wgrad_list_set(s, nullptr, nullptr, &ints);
-  return align256(ints * sizeof(int)) + align256(kListJobs * sizeof(int)) + 256;
+  ListSet S;
+  return align256(wgrad_list_set(s, nullptr, S) * sizeof(int)) + align256(kListJobs * sizeof(int)) + 256;
 }
 
 extern "C" int a3d_scene_build_wgrad_lists(a3d_scene* s, void* workspace_dev, size_t workspace_bytes, void* stream) {
@@ -1155,37 +1158,31 @@ extern "C" int a3d_scene_build_wgrad_lists(a3d_scene* s, void* workspace_dev, si
     return A3D_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  size_t ints;
   ListSet S;
-  int* base = (int*)workspace_dev;
-  const int nj = wgrad_list_set(s, base, &S, &ints);
+  const size_t ints = wgrad_list_set(s, (int*)workspace_dev, S);
   S.counts = (int*)((char*)workspace_dev + align256(ints * sizeof(int)));
   if (s->wg_pending) wgrad_scene_release(s);      // a second request: the first one's read-back is dropped
   s->wg_ready = false;
-  k_wgrad_lists<<<nj, 1024, 0, st>>>(S);
+  k_wgrad_lists<<<kListJobs, 1024, 0, st>>>(S);
   A3D_LAUNCH_CHECK();
   ListReadback* r = readback_get();
   if (!r) {
     set_error("a3d_scene_build_wgrad_lists: no pinned buffer / event for the read-back");
     return A3D_ERR_HIP;
   }
-  // no host round trip here (round 6, second half: the synchronisation stood between the scene build and the first conv
-  // of the training forward -- 0.4 ms of an idle device per iteration): the counts go to a pinned buffer behind an event
-  // that the first a3d_conv_wgrad / a3d_conv_wgrad_workspace_bytes on this scene waits for
-  if (hipMemcpyAsync(r->counts, S.counts, sizeof(int) * nj, hipMemcpyDeviceToHost, st) != hipSuccess ||
+  // no host round trip here (the synchronisation stood between the scene build and the first conv of the training
+  // forward -- 0.4 ms of an idle device per iteration): the counts go to a pinned buffer behind an event that the first
+  // a3d_conv_wgrad / a3d_conv_wgrad_workspace_bytes on this scene waits for
+  if (hipMemcpyAsync(r->counts, S.counts, sizeof(int) * kListJobs, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipEventRecord(r->done, st) != hipSuccess) {
     set_error("a3d_scene_build_wgrad_lists: %s", hipGetErrorString(hipGetLastError()));
     readback_put(r);
     return A3D_ERR_HIP;
   }
-  int m = 0;
-  for (int kind = 0; kind < 3; ++kind)
-    for (int l = 0; l < A3D_NUM_LEVELS; ++l) {
-      if (kind > 0 && l >= A3D_NUM_LEVELS - 1) continue;
-      s->wg_list[kind][l] = S.list[m];
-      s->wg_stride[kind][l] = S.stride[m];
-      ++m;
-    }
+  for (int m = 0; m < kListMaps; ++m) {
+    s->wg_list[kWgradMaps[m].list_kind][kWgradMaps[m].level] = S.list[m];
+    s->wg_stride[kWgradMaps[m].list_kind][kWgradMaps[m].level] = S.stride[m];
+  }
   s->wg_pending = r;
   return A3D_OK;
 }

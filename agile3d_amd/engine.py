@@ -66,10 +66,11 @@ class Scene:
         """The weight-gradient work lists on the host (tests / debugging; synchronises):
         ``{(kind, level): (lists [K, stride] int32, counts [K] int32)}`` for kind in (OP_CONV3, OP_DOWN, OP_UP), level = the
         level that owns the list (OP_UP: the FINE level, level_in - 1 of the op) -- ``lists[k, :counts[k]]`` are the ascending
-        16-position groups that have offset k.  The layout is the one wgrad_list_set (csrc/wgrad.hip) writes: the maps
-        behind one another in (kind, level) order -- 3^3 maps of the five levels, stride-2 and transposed maps of four --,
-        each [K][stride] ints with stride = ceil(ngroups / 64) * 64 and ngroups = ceil(positions / 16) (OP_DOWN: positions of
-        level + 1); the counts, one int per (map, offset) in the same order, start at byte align256(4 * ints)."""
+        16-position groups that have offset k.  The library states the layout once, as the table kWgradMaps of csrc/wgrad.hip
+        (walked by wgrad_list_set): the maps behind one another in the table's order, each [K][stride] ints with stride =
+        ceil(ngroups / 64) * 64 and ngroups = ceil(positions / 16) (pos_above: positions of level + 1); the counts, one int per
+        (map, offset) in the same order, start at byte align256(4 * ints).  The loop below restates that order on purpose: it
+        is the tests' independent statement of the layout."""
         self.prepare_wgrad()
         torch.cuda.current_stream(self.workspace.device).synchronize()
         raw = self._wgrad_lists.cpu().numpy()

@@ -43,19 +43,28 @@ def _scratch(nbytes):
 # ------------------------------------------------------------------------------------------------------------------
 # 1. a3d_linear_wgrad_into / a3d_linear_wgrad
 # ------------------------------------------------------------------------------------------------------------------
-# all 16 pairs of {32, 64, 96, 128}: the 13 instantiated channels-per-lane builds of k_wgrad (wgrad_plan):
-#   (32,32) 2x2  (32,64) 2x4  (32,96) 2x6  (32,128) 2x8  (64,32) 4x2  (64,64) 4x4  (64,96) 4x6  (64,128) 4x8  (96,32) 6x2
-#   (96,64) 6x4  (96,96) 6x6  (128,32) 8x2  (128,64) 8x4;   (96,128) 6x4, (128,96) 4x6 and (128,128) 8x4 with two channel
-#   blocks; the FFN shapes (128,1024) / (1024,128), 8x4 with sixteen.
+# all 16 pairs of {32, 64, 96, 128}: 13 of them select the 13 builds of k_wgrad, (96,128), (128,96) and (128,128) repeat a
+# build with two channel blocks, the FFN shapes (128,1024) / (1024,128) with sixteen -- the table is pinned by
+# test_wgrad_plan_host.py::test_the_build_table_of_the_gpu_modules
 PAIRS = [(ci, co) for ci in (32, 64, 96, 128) for co in (32, 64, 96, 128)] + [(128, 1024), (1024, 128)]
+BUILD_PAIRS = [p for p in PAIRS[:16] if p not in ((96, 128), (128, 96), (128, 128))]
 # one partial group, exactly one group, a group plus one row, fewer groups than the four waves, several segments
 ROW_EDGES = [(ci, co, n) for ci, co in ((128, 128), (96, 128)) for n in (1, 15, 16, 17, 63, 65, 4099)]
-WGRAD_CASES = [(ci, co, 1000) for ci, co in PAIRS] + ROW_EDGES
+# EXACT cases: x and dy are integers in [-3, 3], the seeded dW / db integers in [-8, 8], so every sum in any order is an integer
+# below 2^24 (the largest: 4099 x 9 + 8) and float32 arithmetic is exact: the assertion is bit equality with float64
+EXACT_CASES = ROW_EDGES + [(ci, co, 65) for ci, co in BUILD_PAIRS]
+WGRAD_CASES = ([pytest.param(ci, co, n, False, id=f"{ci}-{co}-{n}") for ci, co, n in [(ci, co, 1000) for ci, co in PAIRS] + ROW_EDGES] +
+               [pytest.param(ci, co, n, True, id=f"exact-{ci}-{co}-{n}") for ci, co, n in EXACT_CASES])
 LAYOUT_PAIRS = [(128, 128), (96, 64), (32, 96)]
 
 
-def _wgrad_inputs(cin, cout, n):
+def _wgrad_inputs(cin, cout, n, exact=False):
     g = torch.Generator().manual_seed(1000 * cin + cout + 7 * n)
+    if exact:
+        x, dy = (torch.randint(-3, 4, (n, c), generator=g).float() for c in (cin, cout))
+        old_w, old_b = torch.randint(-8, 9, (cin, cout), generator=g).float(), torch.randint(-8, 9, (cout,), generator=g).float()
+        assert n * 9 + 8 < 2 ** 24
+        return x, dy, old_w, old_b, x.double().t() @ dy.double(), dy.double().sum(0)
     x = torch.randn(n, cin, generator=g)
     dy = torch.randn(n, cout, generator=g)
     old_w = torch.randn(cin, cout, generator=g) * 3 + 0.5      # what an accumulating call finds ([cin, cout] orientation)
@@ -85,17 +94,18 @@ def _wgrad_plain(x, dy, n, cin, cout):
     return dw
 
 
-@pytest.mark.parametrize("cin,cout,n", WGRAD_CASES)
-def test_linear_wgrad_into_every_output_mode(cin, cout, n):
+@pytest.mark.parametrize("cin,cout,n,exact", WGRAD_CASES)
+def test_linear_wgrad_into_every_output_mode(cin, cout, n, exact):
     """dW = x^T dy and db = sum_rows dy against float64, for transposed x accumulate x db in {absent, assigned, added}.
     An assigning call finds NaN in its destination, an accumulating one seeded values (expected: old + new).  Bound: the
     project's linear-weight-gradient bound 2e-4 max(1, |ref|max), for db (a sum over the same n rows, produced by the same
-    pass) with its own reference's scale.  The plain a3d_linear_wgrad must agree with ``_into`` (transposed = 0,
-    accumulate = 0) within the same bound, and a repeated call must reproduce dW and db bit for bit."""
-    x, dy, old_w, old_b, ref_w, ref_b = _wgrad_inputs(cin, cout, n)
+    pass) with its own reference's scale; the EXACT cases (integer operands) allow no error at all, in both entry points and
+    every output mode.  The plain a3d_linear_wgrad must agree with ``_into`` (transposed = 0, accumulate = 0) within the same
+    bound, and a repeated call must reproduce dW and db bit for bit."""
+    x, dy, old_w, old_b, ref_w, ref_b = _wgrad_inputs(cin, cout, n, exact)
     xd, dyd = x.cuda(), dy.cuda()
-    tol_w = 2e-4 * max(1.0, ref_w.abs().max().item())
-    tol_b = 2e-4 * max(1.0, ref_b.abs().max().item())
+    tol_w = 0.0 if exact else 2e-4 * max(1.0, ref_w.abs().max().item())
+    tol_b = 0.0 if exact else 2e-4 * max(1.0, ref_b.abs().max().item())
     plain_into = None
     for transposed in (0, 1):
         for accumulate in (0, 1):

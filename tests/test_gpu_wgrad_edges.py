@@ -35,8 +35,8 @@ KIND_LEVELS = [(kind, lvl) for kind in KINDS for lvl in range(5)
                if not (kind == "down" and lvl == 4) and not (kind == "up" and lvl == 0)]
 WIDTHS_IN = [32, 64, 96, 128, 192, 256, 384]      # the forward suite's width sets (test_gpu_conv.py)
 WIDTHS_OUT = [32, 64, 96, 128, 256]
-# the 13 channels-per-lane builds of k_wgrad (table at the top of test_gpu_train_primitives.py): {32, 64, 96, 128}^2 without
-# (96, 128), (128, 96), (128, 128), which repeat 6x4, 4x6 and 8x4 with two channel blocks
+# the pairs that select the 13 channels-per-lane builds of k_wgrad: {32, 64, 96, 128}^2 without (96, 128), (128, 96), (128, 128),
+# which repeat a build with two channel blocks (pinned by test_wgrad_plan_host.py::test_the_build_table_of_the_gpu_modules)
 BUILD_PAIRS = [(ci, co) for ci in (32, 64, 96, 128) for co in (32, 64, 96, 128) if (ci, co) not in ((96, 128), (128, 96), (128, 128))]
 assert len(BUILD_PAIRS) == 13
 

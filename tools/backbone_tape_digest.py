@@ -5,7 +5,9 @@ backward -- the number of calls, and the sha256 of ``tape.output``, of every gra
 in ``relu_levels``.  Cases, all on one seeded 3000-voxel scene with seeded weights and d_output: the defaults,
 A3D_FUSE_BN_BWD=0, A3D_WGRAD_STREAM=0, a second tape on the same model after ``optim.WEIGHT_EPOCH`` moved (PackedWeights'
 one-launch ``refresh_all``), and ``sync_bn=True`` in a one-rank gloo group on a file store.  Last, the input convolution on
-its own (``backward.stem_forward``, ``train_backbone._run_stem`` before that existed) for kernel volumes 125 and 27.  Only
+its own (``backward.stem_forward``, ``train_backbone._run_stem`` before that existed) for kernel volumes 125 and 27, and the
+weight gradient's three entry points on seeded Gaussian operands (every op kind and level of the scene; the linear ones at
+1000 rows for 18 width pairs) through ``backward``'s wrappers.  Otherwise only
 BackboneTape's constructor, ``output``, ``relu_levels``, ``backward()`` and ``release()`` and setattr on the loaded library's
 symbols are used, so the same file runs on either commit:
   python tools/backbone_tape_digest.py [--json digests.json]"""
@@ -15,6 +17,7 @@ import lib_trace
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from agile3d_amd import backward as B
 from agile3d_amd import build_model, default_args, optim
+from agile3d_amd import lib as L
 from agile3d_amd import train_backbone as TB
 from agile3d_amd.engine import Scene
 from agile3d_amd.synthetic import make_scene
@@ -104,6 +107,27 @@ for kvol in (125, 27):
     torch.cuda.synchronize()
     digests[f"stem {kvol}"] = {"values": sha(y)}
     print(f"stem kernel volume {kvol} | shape {list(y.shape)} | sha256 {digests[f'stem {kvol}']['values']}", flush=True)
+
+# the three entry points of the weight gradient on seeded Gaussian operands: every op kind at every level it exists on, 64 -> 96
+# channels, and the linear entry points at n = 1000 for the 16 pairs of {32, 64, 96, 128} and the two FFN shapes
+d = digests["wgrad entry points"] = {}
+for kind, name in ((L.OP_CONV3, "conv3"), (L.OP_DOWN, "down"), (L.OP_UP, "up"), (L.OP_LINEAR, "linear")):
+    for lvl in range(5):
+        if (kind == L.OP_DOWN and lvl == 4) or (kind == L.OP_UP and lvl == 0):
+            continue
+        gw = torch.Generator().manual_seed(100 * kind + lvl)
+        x = torch.randn(scene.n[lvl], 64, generator=gw).cuda()
+        dy = torch.randn(scene.n[B.level_out(kind, lvl)], 96, generator=gw).cuda()
+        d[f"a3d_conv_wgrad {name} level {lvl}"] = sha(B.conv_weight_grad(scene, kind, lvl, x, dy))
+for cin, cout in [(ci, co) for ci in (32, 64, 96, 128) for co in (32, 64, 96, 128)] + [(128, 1024), (1024, 128)]:
+    gw = torch.Generator().manual_seed(cin * 2048 + cout)
+    x, dy = torch.randn(1000, cin, generator=gw).cuda(), torch.randn(1000, cout, generator=gw).cuda()
+    d[f"a3d_linear_wgrad {cin}->{cout}"] = sha(B.linear_weight_grad(x, dy))
+    dw, db = torch.zeros(cout, cin, device="cuda"), torch.zeros(cout, device="cuda")
+    B.linear_weight_grad_into(x, dy, dw, db=db)
+    d[f"a3d_linear_wgrad_into {cin}->{cout}"] = sha(torch.cat([dw.flatten(), db]))
+torch.cuda.synchronize()
+print(f"wgrad entry points | {len(d)} cases | sha256 {hashlib.sha256(''.join(d[k] for k in sorted(d)).encode()).hexdigest()}", flush=True)
 if args.json:
     with open(args.json, "w") as f:
         json.dump(digests, f, indent=1)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timing of the sparse-conv backward kernels (row f-2, first part) on the bench scene: input gradient (the forward
 kernel on the transposed map) and weight gradient (k_wgrad) per layer shape, algorithmic TFLOP/s = 2*pairs*Cin*Cout/t.
-Usage: python tools/backward_bench.py [--voxels N] [--batch B]"""
+Usage: python tools/backward_bench.py [--voxels N] [--batch B] [--host CALLS]"""
 import argparse
 import os
 import sys
@@ -35,8 +35,51 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def host_time(sc, calls):
+    """Host cost of one a3d_conv_wgrad_workspace_bytes + a3d_conv_wgrad pair with a warm plan cache: ``calls`` pairs per shape
+    of CASES back to back, timed by the host clock around the whole loop, one device synchronise after it (the launches queue
+    up behind the host; the figure is what the host spends per pair, launches included -- or, once the launch queue is full,
+    what the device needs per pair: the two times of the first line tell which).  Then the size queries alone, which launch
+    nothing: the op description and the plan-cache lookup."""
+    import time
+    lib = L.load()
+    sc.prepare_wgrad()
+    ops = []
+    for name, kind, lvl, cin, cout in CASES:
+        K = {L.OP_CONV3: 27, L.OP_DOWN: 8, L.OP_UP: 8, L.OP_LINEAR: 1}[kind]
+        x = torch.randn(sc.n[lvl], cin, device="cuda")
+        dy = torch.randn(sc.n[B.level_out(kind, lvl)], cout, device="cuda")
+        dw = torch.empty(K, cin, cout, device="cuda")
+        ws = torch.empty(lib.a3d_conv_wgrad_workspace_bytes(sc.handle, kind, lvl, cin, cout), dtype=torch.uint8, device="cuda")
+        ops.append((kind, lvl, cin, cout, L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(ws), ws.numel(), (x, dy, dw, ws)))
+    st = L.stream()
+
+    def loop(n):
+        for _ in range(n):
+            for kind, lvl, cin, cout, px, pdy, pdw, pws, nws, _keep in ops:
+                if lib.a3d_conv_wgrad_workspace_bytes(sc.handle, kind, lvl, cin, cout) != nws:
+                    raise RuntimeError("workspace size moved")
+                L.check(lib.a3d_conv_wgrad(sc.handle, kind, lvl, px, cin, pdy, cout, cin, cout, pdw, pws, nws, st), "a3d_conv_wgrad")
+    loop(2)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    loop(calls)
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    print(f"host: {calls * len(ops)} size + run pairs, {1e6 * (t1 - t0) / (calls * len(ops)):.2f} us per pair "
+          f"(until the last launch was queued; {1e3 * (time.perf_counter() - t0):.1f} ms until the device was idle)")
+    # where the two times agree the launch queue was full and the host waited for the device; the size query launches nothing
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        for kind, lvl, cin, cout, *_rest in ops:
+            lib.a3d_conv_wgrad_workspace_bytes(sc.handle, kind, lvl, cin, cout)
+    print(f"host: {calls * len(ops)} size queries alone, {1e6 * (time.perf_counter() - t0) / (calls * len(ops)):.3f} us each")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--host", type=int, default=0, metavar="CALLS",
+                    help="instead of the table: host time of CALLS a3d_conv_wgrad_workspace_bytes + a3d_conv_wgrad pairs per shape")
     ap.add_argument("--voxels", type=int, default=80_000)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--reps", type=int, default=10)
@@ -48,6 +91,9 @@ def main():
     coords = np.concatenate([make_scene(a.voxels, seed=b, batch_index=b)["coords"] for b in range(a.batch)])
     sc = Scene(torch.from_numpy(coords).cuda())
     print("levels", sc.n)
+    if a.host:
+        host_time(sc, a.host)
+        return a
     pairs3 = []
     for lvl in range(5):
         npad = (max(sc.n[lvl], 1) + 127) // 128 * 128
