@@ -28,6 +28,7 @@
 //     BatchNorm(eval) scale/shift, residual, ReLU and the channel-slice concat are 16-byte epilogue accesses.
 #include "common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace a3d {
 
@@ -64,6 +65,25 @@ struct ConvArgs {
   int head_ld, head_cout;
 };
 
+// The training operands of a launch: one spelling for k_conv_sk, k_conv_deep, k_conv_wl and the host-side plumbing (a null
+// pointer there: inference).
+// stats (STATS builds, training-mode BatchNorm): per block of output rows -- a 64-row tile, a 16-row group in k_conv_wl -- and
+// output column the sum of the block's rows and the sum of their squared deviations from the BLOCK mean,
+// [blocks][2][stats_ld] -- what k_bn_combine merges into the batch statistics.
+// bw.raw set (STATS == 2: an input-gradient conv whose output is the COMPLETE gradient dy of a BatchNorm(+ReLU) unit's output
+// y): the epilogue masks it (g = dy where y > 0), stores g, and writes per block the two column sums the BatchNorm backward
+// needs, stats[block][0][c] = sum g, stats[block][1][c] = sum g * xhat with xhat = (raw - mean) rstd -- no pass over dy, y and
+// raw for the sums afterwards
+struct BwArgs {
+  const float *y, *raw, *mean, *rstd;
+  int ldy, ldraw, relu;
+};
+struct TrainArgs {
+  BwArgs bw;
+  float* stats;
+  int stats_ld;
+};
+
 // ------------------------------------------------------------------------------ k_conv_sk
 // The convolution kernel:
 //   * a STATIC equal-share partition of the layer's work ("stream-K"): the (cout block, 64-row tile, offset, channel
@@ -97,23 +117,7 @@ struct SkArgs {
   unsigned in2_row_bytes;
   int ntab;              // LDS blocks for a tile's neighbour rows behind the weight ring: 2 (the next tile's rows are fetched a
                          // tile ahead), 1, or 0 (no table, or no room: the rows are read in global memory)
-  // STATS (training-mode BatchNorm): per 64-row tile and output column the sum of the tile's rows and the sum of their
-  // squared deviations from the TILE mean, [n_tiles][2][stats_ld] -- what k_bn_combine merges into the batch statistics
-  float* stats;
-  int stats_ld;
-  // STATS == 2 (input-gradient conv whose output is the COMPLETE gradient dy of a BatchNorm(+ReLU) unit's output y): the
-  // epilogue masks it (g = dy where y > 0), stores g, and writes per tile the two column sums the BatchNorm backward needs,
-  // stats[tile][0][c] = sum g, stats[tile][1][c] = sum g * xhat with xhat = (raw - mean) rstd -- no pass over dy, y and raw
-  // for the sums afterwards
-  const float* bw_y;
-  const float* bw_raw;
-  const float* bw_mean;
-  const float* bw_rstd;
-  int bw_ldy, bw_ldraw, bw_relu;
-};
-struct BwArgs {   // the same for k_conv_wl (and the host-side plumbing)
-  const float *y, *raw, *mean, *rstd;
-  int ldy, ldraw, relu;
+  TrainArgs tr;          // STATS builds: blocks = the 64-row tiles
 };
 
 // sum over the 16 lanes that share lane >> 4 (the 16 rows of an MFMA group), result in every lane; fixed order
@@ -168,6 +172,155 @@ __device__ __forceinline__ void glds16_v(const void* src, unsigned lds_byte_addr
 // knows every load it tracks (the A fragments) has landed and inserts no conservative vmcnt of its own in front of
 // the MFMAs -- which would also wait for the LDS-DMA pieces it cannot see.  simm16: vmcnt 0, expcnt 7, lgkmcnt 15.
 __device__ __forceinline__ void wait_all_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
+// ------------------------------------------------------------------------------ epilogues
+// The epilogues of k_conv_sk, k_conv_deep, k_conv_wl and k_dense, each written here once (k_conv_sk calls the STATS == 2 one and
+// tile_partials_out, and spells out its plain epilogue and its STATS == 1 statistics in the kernel: see there).  A lane holds acc[ct][0 .. 3] = four consecutive
+// columns, 16 ct + 4 g + (0 .. 3) of its column block, of ONE output row (g = lane >> 4; the row is j = lane & 15 of its wave's
+// 16-row group).  The kernels differ in how they find that row, so they pass the lane's row pointers (po, pr) at the lane's
+// first column, and ct0, the first 16-column tile of their column block (cb BN / 16; 0 in the kernels without column blocks): a
+// per-column operand is read at (ct0 + ct) 16 + 4 g -- a uniform base and a lane offset, spelled that way on purpose (one
+// vector index cb BN + 4 g moves the register counts of the builds: profiles/conv_epilogue_isa.txt).
+// k_bn_combine_tiles and bn_sums_from_partials merge the statistics without knowing which kernel wrote them: every order of
+// summation below is fixed.
+
+// the plain one: out = act(acc * scale + shift + res), 16-byte accesses.  RES_AHEAD: the residual's fragments are requested
+// before the column loop (the tile kernels; the persistent ones read them inside it: fewer registers beside their prefetched
+// rows)
+template <int NCT, bool RES_AHEAD>
+__device__ __forceinline__ void epilogue_row(const f32x4 (&acc)[NCT], float* po, const float* pr, const float* scale,
+                                             const float* shift, int ct0, int g, int relu) {
+  f32x4 rv[RES_AHEAD ? NCT : 1];
+  if constexpr (RES_AHEAD) {
+    if (pr) {
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) rv[ct] = *(const f32x4*)(pr + ct * 16);
+    }
+  }
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    f32x4 v = acc[ct];
+    if (scale) v *= *(const f32x4*)(scale + (ct0 + ct) * 16 + 4 * g);
+    if (shift) v += *(const f32x4*)(shift + (ct0 + ct) * 16 + 4 * g);
+    if (pr) v += RES_AHEAD ? rv[ct] : *(const f32x4*)(pr + ct * 16);
+    if (relu) {
+#pragma unroll
+      for (int tt = 0; tt < 4; ++tt) v[tt] = fmaxf(v[tt], 0.f);
+    }
+    *(f32x4*)(po + ct * 16) = v;
+  }
+}
+
+__device__ __forceinline__ f32x4 row16_sum4(f32x4 v) {
+#pragma unroll
+  for (int tt = 0; tt < 4; ++tt) v[tt] = row16_sum(v[tt]);
+  return v;
+}
+// STATS == 1, one column tile of a 16-row group: the column sums over the group's valid rows, and the sums of those rows'
+// squared deviations from the block mean tot * inv (BatchNorm statistics of the RAW output: the training path passes no scale /
+// shift / residual / ReLU)
+__device__ __forceinline__ f32x4 group_sum(f32x4 v, bool valid) { return row16_sum4(valid ? v : (f32x4){0.f, 0.f, 0.f, 0.f}); }
+__device__ __forceinline__ f32x4 group_sqdev(f32x4 v, f32x4 tot, float inv, bool valid) {
+  const f32x4 d = valid ? v - tot * inv : (f32x4){0.f, 0.f, 0.f, 0.f};
+  return row16_sum4(d * d);
+}
+
+// STATS == 2: a lane's row of the gradient buffer, of y and of raw at the lane's first column, the unit's mean and rstd
+struct BwRow {
+  bool valid;
+  float* po;
+  const float *pr, *py, *pw, *mean, *rstd;
+  int ct0, g, relu;
+};
+__device__ __forceinline__ BwRow bw_row(const ConvArgs& c, const BwArgs& bw, int myrow, int ct0, int g) {
+  BwRow r;
+  r.valid = myrow < c.n_out;
+  const int orow = r.valid ? (c.out_map ? c.out_map[myrow] : myrow) : 0;
+  r.po = c.out + (size_t)orow * c.ldo + ct0 * 16 + 4 * g;
+  r.pr = c.res ? c.res + (size_t)orow * c.ldr + ct0 * 16 + 4 * g : nullptr;
+  r.py = bw.y + (size_t)orow * bw.ldy + ct0 * 16 + 4 * g;
+  r.pw = bw.raw + (size_t)orow * bw.ldraw + ct0 * 16 + 4 * g;
+  r.mean = bw.mean, r.rstd = bw.rstd, r.ct0 = ct0, r.g = g, r.relu = bw.relu;
+  return r;
+}
+// ... one column tile of it: g = dy (+ the gradient already in the buffer) masked by y > 0, stored; s1, s2 = the sums of g
+// and g xhat over the valid rows of the lane's 16-row group
+__device__ __forceinline__ void bw_group(const BwRow& r, int ct, f32x4 v, f32x4& s1, f32x4& s2) {
+  if (r.pr) v += *(const f32x4*)(r.pr + ct * 16);
+  if (r.relu) {
+    const f32x4 yv = *(const f32x4*)(r.py + ct * 16);
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt) v[tt] = yv[tt] > 0.f ? v[tt] : 0.f;
+  }
+  const f32x4 xh = (*(const f32x4*)(r.pw + ct * 16) - *(const f32x4*)(r.mean + (r.ct0 + ct) * 16 + 4 * r.g)) *
+                   *(const f32x4*)(r.rstd + (r.ct0 + ct) * 16 + 4 * r.g);
+  if (r.valid) *(f32x4*)(r.po + ct * 16) = v;
+  s1 = r.valid ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
+  s2 = s1 * xh;
+  s1 = row16_sum4(s1), s2 = row16_sum4(s2);
+}
+
+// k_conv_wl's store of a group's two partials, column tile ct: stats[group][0 .. 1][16 ct + 4 g ..] (no LDS step)
+__device__ __forceinline__ void group_partials_out(const TrainArgs& tr, int group, int ct, int g, int j, f32x4 s1, f32x4 s2) {
+  if (j == 0) {
+    float* P = tr.stats + (size_t)group * 2 * tr.stats_ld + ct * 16 + 4 * g;
+    *(f32x4*)P = s1;
+    *(f32x4*)(P + tr.stats_ld) = s2;
+  }
+}
+
+// The 64-row tiles of k_conv_sk and k_conv_deep: four waves = four groups, which meet in sst [2][4][BN] of LDS (the kernels'
+// misc + 16).  Every wave has left its two partials per column there: stats[tile t][0 .. 1][cb BN + col] = ((a + b) + c) + d
+template <int BN>
+__device__ __forceinline__ void tile_partials_out(const float* sst, const TrainArgs& tr, int t, int cb, int tid) {
+  __syncthreads();
+  if (tid < BN) {
+    const float* s1p = sst + tid;
+    const float* s2p = sst + 4 * BN + tid;
+    float* P = tr.stats + (size_t)t * 2 * tr.stats_ld + cb * BN + tid;
+    P[0] = ((s1p[0] + s1p[BN]) + s1p[2 * BN]) + s1p[3 * BN];
+    P[tr.stats_ld] = ((s2p[0] + s2p[BN]) + s2p[2 * BN]) + s2p[3 * BN];
+  }
+}
+// STATS == 1 of a tile of cnt valid rows: the column sums (wave-level shuffles over the 16 rows of a group, the four waves
+// through LDS), then the squared deviations from the tile mean the same way (k_conv_deep; k_conv_sk keeps these statements in
+// the kernel and shares the pieces below and above them)
+template <int BN>
+__device__ __forceinline__ void tile_stats_forward(const f32x4 (&acc)[BN / 16], bool valid, int cnt, float* sst,
+                                                   const TrainArgs& tr, int t, int cb, int tid, int wave, int g, int j) {
+#pragma unroll
+  for (int ct = 0; ct < BN / 16; ++ct) {   // one column tile at a time (sched_barrier: no interleaving, four live temporaries)
+    const f32x4 sv = group_sum(acc[ct], valid);
+    if (j == 0) *(f32x4*)(sst + wave * BN + ct * 16 + 4 * g) = sv;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
+  const float inv = 1.f / (float)cnt;
+#pragma unroll
+  for (int ct = 0; ct < BN / 16; ++ct) {
+    const float* sp = sst + ct * 16 + 4 * g;
+    const f32x4 tot = ((*(const f32x4*)sp + *(const f32x4*)(sp + BN)) + *(const f32x4*)(sp + 2 * BN)) + *(const f32x4*)(sp + 3 * BN);
+    const f32x4 d = group_sqdev(acc[ct], tot, inv, valid);
+    if (j == 0) *(f32x4*)(sst + 4 * BN + wave * BN + ct * 16 + 4 * g) = d;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  tile_partials_out<BN>(sst, tr, t, cb, tid);
+}
+// STATS == 2 of a tile: g stored, the column sums of g and g xhat
+template <int BN>
+__device__ __forceinline__ void tile_stats_backward(const f32x4 (&acc)[BN / 16], const BwRow& r, float* sst,
+                                                    const TrainArgs& tr, int t, int cb, int tid, int wave, int j) {
+#pragma unroll
+  for (int ct = 0; ct < BN / 16; ++ct) {
+    f32x4 s1, s2;
+    bw_group(r, ct, acc[ct], s1, s2);
+    if (j == 0) {
+      *(f32x4*)(sst + wave * BN + ct * 16 + 4 * r.g) = s1;
+      *(f32x4*)(sst + 4 * BN + wave * BN + ct * 16 + 4 * r.g) = s2;
+    }
+  }
+  tile_partials_out<BN>(sst, tr, t, cb, tid);
+}
 
 // BN output columns, CH input channels per stage; PAIR (0 or 1): 1 = weight fragments two at a time (16 registers for the
 // B operand instead of 8 BN / 16: the low-register build, 3-4 workgroups per CU), 0 = all of a 16-channel step's fragments
@@ -596,11 +749,12 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
             for (int ct = 0; ct < NCT; ++ct) acc[0][ct] += pa[u][ct];
         }
       }
+      // the epilogues (above k_conv_sk): the tile's BatchNorm partials behind the weight ring, or the finished rows
+      const int myrow = r0 + wrow;
+      float* sst = (float*)(misc + 16);   // [2][4][BN]
       if constexpr (STATS == 1) {
-        // BatchNorm statistics of the RAW output (before scale / shift / residual / ReLU, which the training path does
-        // not pass): column sums over the tile's valid rows, then the squared deviations from the tile mean -- wave-level
-        // shuffles over the 16 rows of a group, the four waves through LDS behind the weight ring, fixed orders
-        float* sst = (float*)(misc + 16);   // [2][4][BN]
+        // tile_stats_forward<BN>, spelled out as it always stood here, for the reason given at the plain epilogue below: through
+        // the helper the ten STATS 1 builds of this kernel gain 2 registers or 8-12 bytes of scratch
         const bool valid = r0 + wrow < a.c.n_out;
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {   // one column tile at a time (sched_barrier: no interleaving, four live temporaries)
@@ -624,84 +778,43 @@ __global__ void __launch_bounds__(256, PAIR ? ((BN <= 96 && CH <= 32) ? 4 : 3) :
           if (j == 0) *(f32x4*)(sst + 4 * BN + wave * BN + ct * 16 + 4 * g) = d;
           __builtin_amdgcn_sched_barrier(0);
         }
-        __syncthreads();
-        if (tid < BN) {
-          const float* s1p = sst + tid;
-          const float* s2p = sst + 4 * BN + tid;
-          float* P = a.stats + (size_t)t * 2 * a.stats_ld + cb * BN + tid;
-          P[0] = ((s1p[0] + s1p[BN]) + s1p[2 * BN]) + s1p[3 * BN];
-          P[a.stats_ld] = ((s2p[0] + s2p[BN]) + s2p[2 * BN]) + s2p[3 * BN];
-        }
+        tile_partials_out<BN>(sst, a.tr, t, cb, tid);
       }
       if constexpr (STATS == 2) {
-        // dy = acc (+ the gradient already in the buffer) -> g = dy masked by (y > 0) -> stored; column sums of g and g xhat
-        // over the tile: shuffles over the 16 rows of a group, the four waves through LDS, fixed orders
-        float* sst = (float*)(misc + 16);   // [2][4][BN]
-        const int myrow = r0 + wrow;
-        const bool valid = myrow < a.c.n_out;
-        const int orow = valid ? (a.c.out_map ? a.c.out_map[myrow] : myrow) : 0;
-        float* po = a.c.out + (size_t)orow * a.c.ldo + ct0 * 16 + 4 * g;
-        const float* pr = a.c.res ? a.c.res + (size_t)orow * a.c.ldr + ct0 * 16 + 4 * g : nullptr;
-        const float* py = a.bw_y + (size_t)orow * a.bw_ldy + ct0 * 16 + 4 * g;
-        const float* pw = a.bw_raw + (size_t)orow * a.bw_ldraw + ct0 * 16 + 4 * g;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-          f32x4 v = acc[0][ct];
-          if (pr) v += *(const f32x4*)(pr + ct * 16);
-          if (a.bw_relu) {
-            const f32x4 yv = *(const f32x4*)(py + ct * 16);
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) v[tt] = yv[tt] > 0.f ? v[tt] : 0.f;
-          }
-          const f32x4 xh = (*(const f32x4*)(pw + ct * 16) - *(const f32x4*)(a.bw_mean + (ct0 + ct) * 16 + 4 * g)) *
-                           *(const f32x4*)(a.bw_rstd + (ct0 + ct) * 16 + 4 * g);
-          if (valid) *(f32x4*)(po + ct * 16) = v;
-          f32x4 s1 = valid ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
-          f32x4 s2 = s1 * xh;
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) s1[tt] = row16_sum(s1[tt]), s2[tt] = row16_sum(s2[tt]);
-          if (j == 0) {
-            *(f32x4*)(sst + wave * BN + ct * 16 + 4 * g) = s1;
-            *(f32x4*)(sst + 4 * BN + wave * BN + ct * 16 + 4 * g) = s2;
-          }
-        }
-        __syncthreads();
-        if (tid < BN) {
-          const float* s1p = sst + tid;
-          const float* s2p = sst + 4 * BN + tid;
-          float* P = a.stats + (size_t)t * 2 * a.stats_ld + cb * BN + tid;
-          P[0] = ((s1p[0] + s1p[BN]) + s1p[2 * BN]) + s1p[3 * BN];
-          P[a.stats_ld] = ((s2p[0] + s2p[BN]) + s2p[2 * BN]) + s2p[3 * BN];
-        }
+        tile_stats_backward<BN>(acc[0], bw_row(a.c, a.tr.bw, myrow, ct0, g), sst, a.tr, t, cb, tid, wave, j);
         __syncthreads();   // the scratch is rewritten by this workgroup's next owned tile
       } else {
+        // epilogue_row<NCT, true>, spelled out as it always stood here (HEAD keeps the finished row in acc): through the helper
+        // the same statements come out of hipcc with 11-35 registers fewer in every STATS 0 / 1 build of THIS kernel (200 -> 165
+        // in <128, 32, 0>) and other instructions; the issue that shared the epilogues held the builds to their registers, and
+        // these are the builds the step runs.  The helper shapes tried and their numbers: profiles/conv_epilogue_isa.txt
 #pragma unroll
-      for (int r = 0; r < RG; ++r) {
-        const int myrow = r0 + wrow + 16 * r;
-        if (myrow < a.c.n_out) {
-          const int orow = a.c.out_map ? a.c.out_map[myrow] : myrow;
-          float* po = a.c.out + (size_t)orow * a.c.ldo + ct0 * 16 + 4 * g;
-          const float* pr = a.c.res ? a.c.res + (size_t)orow * a.c.ldr + ct0 * 16 + 4 * g : nullptr;
-          f32x4 rv[NCT];
-          if (pr) {
+        for (int r = 0; r < RG; ++r) {
+          const int row = r0 + wrow + 16 * r;
+          if (row < a.c.n_out) {
+            const int orow = a.c.out_map ? a.c.out_map[row] : row;
+            float* po = a.c.out + (size_t)orow * a.c.ldo + ct0 * 16 + 4 * g;
+            const float* pr = a.c.res ? a.c.res + (size_t)orow * a.c.ldr + ct0 * 16 + 4 * g : nullptr;
+            f32x4 rv[NCT];
+            if (pr) {
 #pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) rv[ct] = *(const f32x4*)(pr + ct * 16);
-          }
-#pragma unroll
-          for (int ct = 0; ct < NCT; ++ct) {
-            f32x4 v = acc[r][ct];
-            if (a.c.scale) v *= *(const f32x4*)(a.c.scale + (ct0 + ct) * 16 + 4 * g);
-            if (a.c.shift) v += *(const f32x4*)(a.c.shift + (ct0 + ct) * 16 + 4 * g);
-            if (pr) v += rv[ct];
-            if (a.c.relu) {
-#pragma unroll
-              for (int tt = 0; tt < 4; ++tt) v[tt] = fmaxf(v[tt], 0.f);
+              for (int ct = 0; ct < NCT; ++ct) rv[ct] = *(const f32x4*)(pr + ct * 16);
             }
-            *(f32x4*)(po + ct * 16) = v;
-            if constexpr (HEAD) acc[r][ct] = v;   // the finished row stays in the accumulator registers for the head below
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+              f32x4 v = acc[r][ct];
+              if (a.c.scale) v *= *(const f32x4*)(a.c.scale + (ct0 + ct) * 16 + 4 * g);
+              if (a.c.shift) v += *(const f32x4*)(a.c.shift + (ct0 + ct) * 16 + 4 * g);
+              if (pr) v += rv[ct];
+              if (a.c.relu) {
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) v[tt] = fmaxf(v[tt], 0.f);
+              }
+              *(f32x4*)(po + ct * 16) = v;
+              if constexpr (HEAD) acc[r][ct] = v;   // the finished row stays in the accumulator registers for the head below
+            }
           }
         }
-      }
       }
       if constexpr (HEAD) {
         // second GEMM on the finished tile: pcd[row][16 c2 + 4 g + r] = sum over the BN channels.  The weight fragments come
@@ -782,11 +895,7 @@ struct DeepArgs {
   float* slab;         // [units * P][64 * BN]
   unsigned in_row_bytes, in2_row_bytes;
   unsigned long long* dbg;   // A3D_DEEP_DBG: [G][6] timestamps (100 MHz) of a workgroup's phases; nullptr otherwise
-  // STATS builds (training, as k_conv_sk's): per 64-row tile and column the BatchNorm partials [n_tiles][2][stats_ld];
-  // STATS == 2: the input-gradient conv's mask + sums (bw: y, raw, mean, rstd of the unit)
-  float* stats;
-  int stats_ld;
-  BwArgs bw;
+  TrainArgs tr;        // STATS builds, as k_conv_sk's: blocks = the 64-row tiles
 };
 
 template <int N>
@@ -1036,104 +1145,18 @@ __global__ void __launch_bounds__(256, 1) k_conv_deep(const DeepArgs a) {
     for (int ct = 0; ct < NCT; ++ct) acc[ct] = tot[ct];
   }
 
+  // the epilogues k_conv_sk has (above it): a tile's partials do not depend on which of the two kernels produced it beyond the
+  // rounding of the accumulators
   const int myrow = r0 + wrow;
-  if constexpr (STATS == 1) {
-    // BatchNorm statistics of the raw tile, exactly as k_conv_sk<..., STATS = 1> takes them (the same fixed orders: the
-    // partials of a tile do not depend on which kernel produced it beyond the rounding of the accumulators)
-    float* sst = (float*)(misc + 16);   // [2][4][BN]
-    const bool valid = myrow < a.c.n_out;
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-      f32x4 sv = valid ? acc[ct] : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) sv[tt] = row16_sum(sv[tt]);
-      if (j == 0) *(f32x4*)(sst + wave * BN + ct * 16 + 4 * g) = sv;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-    const float inv = 1.f / (float)min(64, a.c.n_out - r0);
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-      const float* sp = sst + ct * 16 + 4 * g;
-      const f32x4 tsum = ((*(const f32x4*)sp + *(const f32x4*)(sp + BN)) + *(const f32x4*)(sp + 2 * BN)) + *(const f32x4*)(sp + 3 * BN);
-      f32x4 dv = valid ? acc[ct] - tsum * inv : (f32x4){0.f, 0.f, 0.f, 0.f};
-      dv = dv * dv;
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) dv[tt] = row16_sum(dv[tt]);
-      if (j == 0) *(f32x4*)(sst + 4 * BN + wave * BN + ct * 16 + 4 * g) = dv;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-    if (tid < BN) {
-      const float* s1p = sst + tid;
-      const float* s2p = sst + 4 * BN + tid;
-      float* Pq = a.stats + (size_t)t * 2 * a.stats_ld + cb * BN + tid;
-      Pq[0] = ((s1p[0] + s1p[BN]) + s1p[2 * BN]) + s1p[3 * BN];
-      Pq[a.stats_ld] = ((s2p[0] + s2p[BN]) + s2p[2 * BN]) + s2p[3 * BN];
-    }
-  }
+  float* sst = (float*)(misc + 16);   // [2][4][BN]
+  if constexpr (STATS == 1) tile_stats_forward<BN>(acc, myrow < a.c.n_out, min(64, a.c.n_out - r0), sst, a.tr, t, cb, tid, wave, g, j);
   if constexpr (STATS == 2) {
-    // input-gradient conv: g = (dy (+ the gradient already in the buffer)) masked by y > 0, stored; tile sums of g and g xhat
-    float* sst = (float*)(misc + 16);   // [2][4][BN]
-    const bool valid = myrow < a.c.n_out;
-    const int orow = valid ? (a.c.out_map ? a.c.out_map[myrow] : myrow) : 0;
-    float* po = a.c.out + (size_t)orow * a.c.ldo + ct0 * 16 + 4 * g;
-    const float* pr = a.c.res ? a.c.res + (size_t)orow * a.c.ldr + ct0 * 16 + 4 * g : nullptr;
-    const float* py = a.bw.y + (size_t)orow * a.bw.ldy + ct0 * 16 + 4 * g;
-    const float* pw = a.bw.raw + (size_t)orow * a.bw.ldraw + ct0 * 16 + 4 * g;
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-      f32x4 v = acc[ct];
-      if (pr) v += *(const f32x4*)(pr + ct * 16);
-      if (a.bw.relu) {
-        const f32x4 yv = *(const f32x4*)(py + ct * 16);
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) v[tt] = yv[tt] > 0.f ? v[tt] : 0.f;
-      }
-      const f32x4 xh = (*(const f32x4*)(pw + ct * 16) - *(const f32x4*)(a.bw.mean + (ct0 + ct) * 16 + 4 * g)) *
-                       *(const f32x4*)(a.bw.rstd + (ct0 + ct) * 16 + 4 * g);
-      if (valid) *(f32x4*)(po + ct * 16) = v;
-      f32x4 s1 = valid ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
-      f32x4 s2 = s1 * xh;
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) s1[tt] = row16_sum(s1[tt]), s2[tt] = row16_sum(s2[tt]);
-      if (j == 0) {
-        *(f32x4*)(sst + wave * BN + ct * 16 + 4 * g) = s1;
-        *(f32x4*)(sst + 4 * BN + wave * BN + ct * 16 + 4 * g) = s2;
-      }
-    }
-    __syncthreads();
-    if (tid < BN) {
-      const float* s1p = sst + tid;
-      const float* s2p = sst + 4 * BN + tid;
-      float* Pq = a.stats + (size_t)t * 2 * a.stats_ld + cb * BN + tid;
-      Pq[0] = ((s1p[0] + s1p[BN]) + s1p[2 * BN]) + s1p[3 * BN];
-      Pq[a.stats_ld] = ((s2p[0] + s2p[BN]) + s2p[2 * BN]) + s2p[3 * BN];
-    }
-    stamp(5);
-    return;
-  }
-  if (myrow < a.c.n_out) {
+    tile_stats_backward<BN>(acc, bw_row(a.c, a.tr.bw, myrow, ct0, g), sst, a.tr, t, cb, tid, wave, j);
+  } else if (myrow < a.c.n_out) {
     const int orow = a.c.out_map ? a.c.out_map[myrow] : myrow;
-    float* po = a.c.out + (size_t)orow * a.c.ldo + ct0 * 16 + 4 * g;
-    const float* pr = a.c.res ? a.c.res + (size_t)orow * a.c.ldr + ct0 * 16 + 4 * g : nullptr;
-    f32x4 rv[NCT];
-    if (pr) {
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) rv[ct] = *(const f32x4*)(pr + ct * 16);
-    }
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-      f32x4 v = acc[ct];
-      if (a.c.scale) v *= *(const f32x4*)(a.c.scale + (ct0 + ct) * 16 + 4 * g);
-      if (a.c.shift) v += *(const f32x4*)(a.c.shift + (ct0 + ct) * 16 + 4 * g);
-      if (pr) v += rv[ct];
-      if (a.c.relu) {
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) v[tt] = fmaxf(v[tt], 0.f);
-      }
-      *(f32x4*)(po + ct * 16) = v;
-    }
+    epilogue_row<NCT, true>(acc, a.c.out + (size_t)orow * a.c.ldo + ct0 * 16 + 4 * g,
+                            a.c.res ? a.c.res + (size_t)orow * a.c.ldr + ct0 * 16 + 4 * g : nullptr, a.c.scale, a.c.shift, ct0, g,
+                            a.c.relu);
   }
   stamp(5);
 }
@@ -1149,10 +1172,10 @@ __global__ void __launch_bounds__(256, 1) k_conv_deep(const DeepArgs a) {
 // ahead, NS NCT ds_read_b128 + 4 NS NCT MFMAs.  Same summation order per output element as k_conv_sk run without
 // hand-offs (offsets ascending, channels ascending), so results are bit-identical to it.
 // STATS (training): every finished 16-row group also writes its BatchNorm partials (column sums, squared deviations from
-// the GROUP mean) to stats[group][2][stats_ld] -- a group belongs to one wave, so this needs no LDS and no barrier.
+// the GROUP mean; STATS == 2: the BatchNorm-backward sums) to tr.stats[group][2][stats_ld] -- a group belongs to one wave, so
+// this needs no LDS and no barrier.
 template <int NS, int NCT, int STATS = 0>
-__global__ void __launch_bounds__(1024) k_conv_wl(const ConvArgs c, int ngroups, float* stats = nullptr, int stats_ld = 0,
-                                                  const BwArgs bw = BwArgs()) {
+__global__ void __launch_bounds__(1024) k_conv_wl(const ConvArgs c, int ngroups, const TrainArgs tr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   f32x4* Wl = (f32x4*)smem;   // [K][NS][NCT][64]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1244,74 +1267,35 @@ __global__ void __launch_bounds__(1024) k_conv_wl(const ConvArgs c, int ngroups,
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ct][tt], A0[S][tt], acc[ct], 0, 0, 0);
     }
-    if (!v1 || g1 != g0) {   // last offset of group g0: epilogue (as k_conv_sk's)
+    if (!v1 || g1 != g0) {   // last offset of group g0: the epilogues above k_conv_sk, per group -- no LDS step, its own store
       const int myrow = g0 * 16 + j;
-      if constexpr (STATS == 2) {   // input-gradient conv: g = (dy (+ res)) masked by y > 0, stored; sums of g and g xhat per group
-        const bool valid = myrow < c.n_out;
-        const int orow = valid ? (c.out_map ? c.out_map[myrow] : myrow) : 0;
+      const bool valid = myrow < c.n_out;
+      if constexpr (STATS == 2) {
+        const BwRow r = bw_row(c, tr.bw, myrow, 0, g);
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
-          f32x4 v = acc[ct];
-          if (c.res) v += *(const f32x4*)(c.res + (size_t)orow * c.ldr + ct * 16 + 4 * g);
-          if (bw.relu) {
-            const f32x4 yv = *(const f32x4*)(bw.y + (size_t)orow * bw.ldy + ct * 16 + 4 * g);
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) v[tt] = yv[tt] > 0.f ? v[tt] : 0.f;
-          }
-          const f32x4 xh = (*(const f32x4*)(bw.raw + (size_t)orow * bw.ldraw + ct * 16 + 4 * g) - *(const f32x4*)(bw.mean + ct * 16 + 4 * g)) *
-                           *(const f32x4*)(bw.rstd + ct * 16 + 4 * g);
-          if (valid) *(f32x4*)(c.out + (size_t)orow * c.ldo + ct * 16 + 4 * g) = v;
-          f32x4 s1 = valid ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
-          f32x4 s2 = s1 * xh;
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) s1[tt] = row16_sum(s1[tt]), s2[tt] = row16_sum(s2[tt]);
-          if (j == 0) {
-            float* P = stats + (size_t)g0 * 2 * stats_ld + ct * 16 + 4 * g;
-            *(f32x4*)P = s1;
-            *(f32x4*)(P + stats_ld) = s2;
-          }
-          acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          f32x4 s1, s2;
+          bw_group(r, ct, acc[ct], s1, s2);
+          group_partials_out(tr, g0, ct, g, j, s1, s2);
         }
       } else {
-      if constexpr (STATS == 1) {
-        const bool valid = myrow < c.n_out;
-        const float inv = 1.f / (float)min(16, c.n_out - g0 * 16);
+        if constexpr (STATS == 1) {
+          const float inv = 1.f / (float)min(16, c.n_out - g0 * 16);
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-          f32x4 sv = valid ? acc[ct] : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) sv[tt] = row16_sum(sv[tt]);
-          f32x4 d = valid ? acc[ct] - sv * inv : (f32x4){0.f, 0.f, 0.f, 0.f};
-          d = d * d;
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) d[tt] = row16_sum(d[tt]);
-          if (j == 0) {
-            float* P = stats + (size_t)g0 * 2 * stats_ld + ct * 16 + 4 * g;
-            *(f32x4*)P = sv;
-            *(f32x4*)(P + stats_ld) = d;
+          for (int ct = 0; ct < NCT; ++ct) {
+            const f32x4 sv = group_sum(acc[ct], valid);
+            const f32x4 d = group_sqdev(acc[ct], sv, inv, valid);
+            group_partials_out(tr, g0, ct, g, j, sv, d);
           }
         }
-      }
-      if (myrow < c.n_out) {
-        const int orow = c.out_map ? c.out_map[myrow] : myrow;
-        float* po = c.out + (size_t)orow * c.ldo + 4 * g;
-        const float* pr = c.res ? c.res + (size_t)orow * c.ldr + 4 * g : nullptr;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-          f32x4 v = acc[ct];
-          if (c.scale) v *= *(const f32x4*)(c.scale + ct * 16 + 4 * g);
-          if (c.shift) v += *(const f32x4*)(c.shift + ct * 16 + 4 * g);
-          if (pr) v += *(const f32x4*)(pr + ct * 16);
-          if (c.relu) {
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) v[tt] = fmaxf(v[tt], 0.f);
-          }
-          *(f32x4*)(po + ct * 16) = v;
+        if (valid) {
+          const int orow = c.out_map ? c.out_map[myrow] : myrow;
+          epilogue_row<NCT, false>(acc, c.out + (size_t)orow * c.ldo + 4 * g, c.res ? c.res + (size_t)orow * c.ldr + 4 * g : nullptr,
+                                   c.scale, c.shift, 0, g, c.relu);
         }
       }
 #pragma unroll
       for (int ct = 0; ct < NCT; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      }
     }
 #pragma unroll
     for (int S = 0; S < NS; ++S) {
@@ -1326,8 +1310,20 @@ __global__ void __launch_bounds__(1024) k_conv_wl(const ConvArgs c, int ngroups,
   }
 }
 
+// The training mode of a launch, STATS of the kernels: 0 inference (no operands), 1 the BatchNorm-forward partials, 2 the
+// BatchNorm-backward sums (the operands name the unit's raw output).  by_stats: the build of a kernel for that mode,
+// pick(std::integral_constant<int, STATS>)
+static int train_mode(const TrainArgs* tr) { return !tr ? 0 : tr->bw.raw ? 2 : 1; }
+template <class Pick>
+static auto by_stats(const TrainArgs* tr, Pick pick) {
+  const int mode = train_mode(tr);
+  return mode == 2   ? pick(std::integral_constant<int, 2>())
+         : mode == 1 ? pick(std::integral_constant<int, 1>())
+                     : pick(std::integral_constant<int, 0>());
+}
+
 // the 32 -> 32 layers with a kernel map (plan_conv's family kConvWl)
-static int launch_conv_wl(const ConvArgs& c, hipStream_t st, float* stats = nullptr, int stats_ld = 0, const BwArgs* bw = nullptr) {
+static int launch_conv_wl(const ConvArgs& c, hipStream_t st, const TrainArgs* tr) {
   const int ngroups = (c.n_out + 15) / 16;
   const size_t lds = (size_t)c.K * c.cin * c.cout * 4;
   // one workgroup per CU; 16 waves when there are groups for them, never fewer than 4
@@ -1336,8 +1332,8 @@ static int launch_conv_wl(const ConvArgs& c, hipStream_t st, float* stats = null
   if ((long long)grid * nw > ngroups) grid = (ngroups + nw - 1) / nw;
   if (grid < 1) grid = 1;
   ProfScope ps(st, A3D_PROF_SPCONV, c.cout, c.K, c.cin, c.cout, c.n_out, c.tag_table, c.tag_level, 0);   // stage width 0: k_conv_wl
-  const auto kern = bw ? big_lds<k_conv_wl<2, 2, 2>>() : stats ? big_lds<k_conv_wl<2, 2, 1>>() : big_lds<k_conv_wl<2, 2>>();
-  kern<<<grid, 64 * nw, lds, st>>>(c, ngroups, stats, stats_ld, bw ? *bw : BwArgs());
+  const auto kern = by_stats(tr, [](auto S) { return big_lds<k_conv_wl<2, 2, decltype(S)::value>>(); });
+  kern<<<grid, 64 * nw, lds, st>>>(c, ngroups, tr ? *tr : TrainArgs());
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -1434,21 +1430,10 @@ __global__ void __launch_bounds__(768) k_dense(const float* __restrict__ X, int 
       }
     }
     // acc[ct][t] = Y[16 grp + j][16 ct + 4 g + t]
-    if (grp * 16 + j < n) {
+    if (grp * 16 + j < n) {   // the plain epilogue above k_conv_sk
       const int row = out_map ? out_map[grp * 16 + j] : grp * 16 + j;
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) {
-        const int col = 16 * ct + 4 * g;
-        f32x4 v = acc[ct];
-        if (scale) v *= *(const f32x4*)(scale + col);
-        if (shift) v += *(const f32x4*)(shift + col);
-        if (res) v += *(const f32x4*)(res + (size_t)row * ldr + col);
-        if (relu) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
-        }
-        *(f32x4*)(Y + (size_t)row * ldy + col) = v;
-      }
+      epilogue_row<NCT, false>(acc, Y + (size_t)row * ldy + 4 * g, res ? res + (size_t)row * ldr + 4 * g : nullptr, scale, shift, 0, g,
+                               relu);
     }
     grp = next;
   }
@@ -2034,22 +2019,21 @@ static void deep_dbg_report(const unsigned long long* dbg_buf, const ConvArgs& c
   fprintf(stderr, "\n");
 }
 
-static int launch_conv_deep(const ConvArgs& c, const ConvPlan& d, float* slab_ws, int* state, hipStream_t st, float* stats,
-                            int stats_ld, const BwArgs* bw) {
+static int launch_conv_deep(const ConvArgs& c, const ConvPlan& d, float* slab_ws, int* state, hipStream_t st,
+                            const TrainArgs* tr) {
   DeepArgs a;
   memset(&a, 0, sizeof(a));
   a.c = c;
   a.P = d.P, a.n_cblk = d.n_cblk, a.nchunk = d.nchunk, a.nchunk2 = d.nchunk2;
   a.cnt = state + 2, a.slab = slab_ws;
   a.in_row_bytes = (unsigned)c.ldi * 4u, a.in2_row_bytes = (unsigned)c.ldi2 * 4u;
-  a.stats = stats, a.stats_ld = stats_ld;
-  if (bw) a.bw = *bw;
+  if (tr) a.tr = *tr;
   // the kernel-volume field as k_conv_sk's (K | cin2 << 8); the column field carries 1000 + BN: "deep" in the layer tables
   ProfScope ps(st, A3D_PROF_SPCONV, 1000 + d.bn, c.K | (c.cin2 << 8), c.cin, c.cout, c.n_out, c.tag_table, c.tag_level, d.ch);
   a.dbg = deep_dbg_buffer();
   if (a.dbg) (void)hipMemsetAsync(a.dbg, 0, (size_t)kSkMaxG * 6 * 8, st);
-  const DeepKernel kern = bw ? deep_kernel<false, 2>(d) : stats ? deep_kernel<false, 1>(d)
-                          : c.cin2 > 0 ? deep_kernel<true, 0>(d) : deep_kernel<false, 0>(d);
+  const DeepKernel kern = c.cin2 > 0 ? deep_kernel<true, 0>(d)   // (never with training operands: launch_conv_sk)
+                                     : by_stats(tr, [&](auto S) { return deep_kernel<false, decltype(S)::value>(d); });
   if (!kern) {
     set_error("spconv: no deep kernel for BN %d CH %d", d.bn, d.ch);
     return A3D_ERR_UNSUPPORTED;
@@ -2075,15 +2059,15 @@ static ConvShape conv_shape(const ConvArgs& c, int stats, bool has_state, size_t
   return s;
 }
 
-// stats != nullptr (training): the kernel's epilogue also writes BatchNorm partials, [blocks][2][stats_ld] with
+// tr != nullptr (training): the kernel's epilogue also writes BatchNorm partials, tr->stats [blocks][2][stats_ld] with
 // *stats_rows rows per block (64: k_conv_sk / k_conv_deep tiles, 16: the groups of k_conv_wl); the op must carry no scale /
 // shift / residual
-// bw != nullptr (with stats): the BatchNorm-BACKWARD sums instead (STATS == 2: the op is an input-gradient conv, a residual =
-// the gradient already accumulated in the buffer is allowed)
+// train_mode(tr) == 2: the BatchNorm-BACKWARD sums instead (the op is an input-gradient conv, a residual = the gradient
+// already accumulated in the buffer is allowed)
 static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t slab_ws_floats, int* state,
-                          hipStream_t st, float* stats = nullptr, int stats_ld = 0, int* stats_rows = nullptr,
-                          const BwArgs* bw = nullptr) {
-  if (stats && (c.scale || c.shift || c.relu || c.cin2 > 0 || !stats_rows || (c.res && !bw))) {
+                          hipStream_t st, const TrainArgs* tr = nullptr, int* stats_rows = nullptr) {
+  const int mode = train_mode(tr);
+  if (tr && (!tr->stats || c.scale || c.shift || c.relu || c.cin2 > 0 || !stats_rows || (c.res && mode != 2))) {
     set_error("spconv: BatchNorm statistics are taken of a raw convolution (no epilogue, no fused projection)");
     return A3D_ERR_UNSUPPORTED;
   }
@@ -2099,12 +2083,12 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
     set_error("spconv: input of %d rows x %d floats exceeds the 4 GB gather window", c.n_in, c.ldi);
     return A3D_ERR_UNSUPPORTED;
   }
-  const ConvShape s = conv_shape(c, bw ? 2 : stats ? 1 : 0, state != nullptr, slab_ws_floats);
+  const ConvShape s = conv_shape(c, mode, state != nullptr, slab_ws_floats);
   const ConvPlan p = plan_conv(s);
-  if (stats) *stats_rows = p.family == kConvWl ? 16 : 64;
-  if (p.family == kConvWl) return launch_conv_wl(c, st, stats, stats_ld, bw);
+  if (tr) *stats_rows = p.family == kConvWl ? 16 : 64;
+  if (p.family == kConvWl) return launch_conv_wl(c, st, tr);
   c.n_tiles = p.ntile;
-  if (p.family == kConvDeep) return launch_conv_deep(c, p, slab_ws, state, st, stats, stats_ld, bw);
+  if (p.family == kConvDeep) return launch_conv_deep(c, p, slab_ws, state, st, tr);
   if (p.handoff && p.slab_floats > slab_ws_floats) {
     set_error("spconv: hand-off workspace too small");
     return A3D_ERR_WORKSPACE;
@@ -2126,11 +2110,7 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
   a.slab = slab_ws;
   a.in_row_bytes = (unsigned)c.ldi * 4u, a.in2_row_bytes = (unsigned)c.ldi2 * 4u;
   a.ntab = p.ntab;
-  a.stats = stats, a.stats_ld = stats_ld;
-  if (bw) {
-    a.bw_y = bw->y, a.bw_raw = bw->raw, a.bw_mean = bw->mean, a.bw_rstd = bw->rstd;
-    a.bw_ldy = bw->ldy, a.bw_ldraw = bw->ldraw, a.bw_relu = bw->relu;
-  }
+  if (tr) a.tr = *tr;
   // kernel-volume field: K, plus the fused projection's input channels in the bits above (cin2 << 8); last field: stage width
   // ... and a fused head's output columns above those (head_cout << 20)
   ProfScope ps(st, A3D_PROF_SPCONV, p.bn, c.K | (c.cin2 << 8) | (c.head_cout << 20), c.cin, c.cout, c.n_out, c.tag_table, c.tag_level,
@@ -2154,7 +2134,7 @@ static int launch_conv_sk(ConvArgs c, const int* pre64, float* slab_ws, size_t s
     }
     kern = big_lds<k_conv_sk<96, 32, 1, false, 0, true>>();
   } else {
-    kern = bw ? sk_kernel<false, 2>(p) : stats ? sk_kernel<false, 1>(p) : sk_kernel<false, 0>(p);
+    kern = by_stats(tr, [&](auto S) { return sk_kernel<false, decltype(S)::value>(p); });
     if (!kern) {
       set_error("spconv: no kernel for BN %d CH %d", p.bn, p.ch);
       return A3D_ERR_UNSUPPORTED;
@@ -2507,8 +2487,8 @@ extern "C" size_t a3d_conv_apply_workspace_bytes(const a3d_scene* s, int kind, i
 // shared body of a3d_conv_apply / a3d_conv_apply_acc / a3d_conv_bn_train_forward
 static int conv_apply_impl(const a3d_scene* s, int kind, int level_in, const float* x_dev, int ldx, int cin,
                            const float* w_packed_dev, int cout, float* y_dev, int ldy, int y_zero_row, const float* res_dev,
-                           int ldr, int* state_dev, float* stats, int stats_ld, int* stats_rows, void* workspace_dev,
-                           size_t workspace_bytes, hipStream_t st, const char* who, const BwArgs* bw = nullptr) {
+                           int ldr, int* state_dev, const TrainArgs* tr, int* stats_rows, void* workspace_dev,
+                           size_t workspace_bytes, hipStream_t st, const char* who) {
   if (!s || !x_dev || !w_packed_dev || !y_dev || level_in < 0 || level_in >= A3D_NUM_LEVELS || (ldx & 3) || (ldy & 3) ||
       ldx < cin || ldy < cout || (res_dev && ((ldr & 3) || ldr < cout))) {
     set_error("%s: bad arguments", who);
@@ -2541,14 +2521,14 @@ static int conv_apply_impl(const a3d_scene* s, int kind, int level_in, const flo
   float* slab = (float*)((char*)workspace_dev + align256((size_t)kMaxQueuesPerOp * 4));
   const size_t slab_floats = (workspace_bytes - align256((size_t)kMaxQueuesPerOp * 4)) / 4;
   if (!state_dev) A3D_HIP_CHECK(hipMemsetAsync(state, 0, (size_t)kMaxQueuesPerOp * 4, st));
-  return launch_conv_sk(a, pre, slab, slab_floats, state, st, stats, stats_ld, stats_rows, bw);
+  return launch_conv_sk(a, pre, slab, slab_floats, state, st, tr, stats_rows);
 }
 
 extern "C" int a3d_conv_apply(const a3d_scene* s, int kind, int level_in, const float* x_dev, int ldx, int cin,
                               const float* w_packed_dev, int cout, float* y_dev, int ldy, int y_zero_row,
                               void* workspace_dev, size_t workspace_bytes, void* stream) {
   return conv_apply_impl(s, kind, level_in, x_dev, ldx, cin, w_packed_dev, cout, y_dev, ldy, y_zero_row, nullptr, 0, nullptr,
-                         nullptr, 0, nullptr, workspace_dev, workspace_bytes, (hipStream_t)stream, "a3d_conv_apply");
+                         nullptr, nullptr, workspace_dev, workspace_bytes, (hipStream_t)stream, "a3d_conv_apply");
 }
 
 extern "C" size_t a3d_conv_state_bytes(void) { return (size_t)kMaxQueuesPerOp * 4; }
@@ -2564,7 +2544,7 @@ extern "C" int a3d_conv_apply_acc(const a3d_scene* s, int kind, int level_in, co
                                   const float* res_dev, int ldr, void* state_dev, void* workspace_dev,
                                   size_t workspace_bytes, void* stream) {
   return conv_apply_impl(s, kind, level_in, x_dev, ldx, cin, w_packed_dev, cout, y_dev, ldy, y_zero_row, res_dev, ldr,
-                         (int*)state_dev, nullptr, 0, nullptr, workspace_dev, workspace_bytes, (hipStream_t)stream,
+                         (int*)state_dev, nullptr, nullptr, workspace_dev, workspace_bytes, (hipStream_t)stream,
                          "a3d_conv_apply_acc");
 }
 
@@ -2584,12 +2564,13 @@ extern "C" int a3d_conv_dgrad_bn(const a3d_scene* s, int kind, int level_in, con
   hipStream_t st = (hipStream_t)stream;
   const size_t conv_bytes = align256(a3d_conv_apply_workspace_bytes(s, kind, level_in, cin, cout));
   float* partial = (float*)((char*)workspace_dev + conv_bytes);
-  BwArgs bw;
-  bw.y = y_dev, bw.raw = raw_dev, bw.mean = mean_dev, bw.rstd = rstd_dev, bw.ldy = ldy, bw.ldraw = ld_raw, bw.relu = relu;
+  TrainArgs tr;
+  tr.bw.y = y_dev, tr.bw.raw = raw_dev, tr.bw.mean = mean_dev, tr.bw.rstd = rstd_dev;
+  tr.bw.ldy = ldy, tr.bw.ldraw = ld_raw, tr.bw.relu = relu;
+  tr.stats = partial, tr.stats_ld = cout;
   int rows_per_block = 0;
   int rc = conv_apply_impl(s, kind, level_in, x_dev, ldx, cin, w_packed_dev, cout, g_dev, ldg, 1, acc ? g_dev : nullptr, ldg,
-                           (int*)state_dev, partial, cout, &rows_per_block, workspace_dev, conv_bytes, st, "a3d_conv_dgrad_bn",
-                           &bw);
+                           (int*)state_dev, &tr, &rows_per_block, workspace_dev, conv_bytes, st, "a3d_conv_dgrad_bn");
   if (rc != A3D_OK) return rc;
   const int lvl_out = level_out(kind, level_in);
   const int n = s->lv[lvl_out].n;
@@ -2619,10 +2600,11 @@ extern "C" int a3d_conv_bn_train_forward(const a3d_scene* s, int kind, int level
   hipStream_t st = (hipStream_t)stream;
   const size_t conv_bytes = align256(a3d_conv_apply_workspace_bytes(s, kind, level_in, cin, cout));
   float* partial = (float*)((char*)workspace_dev + conv_bytes);
+  TrainArgs tr = TrainArgs();   // no bw.raw: the forward partials
+  tr.stats = partial, tr.stats_ld = cout;
   int rows_per_block = 0;
   int rc = conv_apply_impl(s, kind, level_in, x_dev, ldx, cin, w_packed_dev, cout, raw_dev, ld_raw, 0, nullptr, 0,
-                           (int*)state_dev, partial, cout, &rows_per_block, workspace_dev, conv_bytes, st,
-                           "a3d_conv_bn_train_forward");
+                           (int*)state_dev, &tr, &rows_per_block, workspace_dev, conv_bytes, st, "a3d_conv_bn_train_forward");
   if (rc != A3D_OK) return rc;
   const int lvl_out = level_out(kind, level_in);
   const int n = s->lv[lvl_out].n;

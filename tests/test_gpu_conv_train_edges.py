@@ -6,7 +6,9 @@ build behind a3d_conv_bn_train_forward: its epilogue also writes, per 64-row til
 the sum of the tile's rows and their squared deviations from the tile mean, which k_bn_combine_tiles (bnorm.hip) merges.
 STATS = 2 is the build behind a3d_conv_dgrad_bn: its epilogue adds the gradient already in the buffer, masks by y > 0,
 stores g and writes per-tile sums of g and g * xhat, which bn_sums_from_partials folds (k_col_final below 64 blocks,
-k_col_final_tiles from 64 on).  These are separate code objects with their own epilogue code; plan_conv picks their class
+k_col_final_tiles from 64 on).  These are separate code objects, their epilogues compiled from one source: the helpers above
+k_conv_sk in spconv.hip, which k_conv_deep and k_conv_wl call for both builds and k_conv_sk for STATS = 2 and for the write of
+a tile's partials (its STATS = 1 statistics and its plain epilogue stand spelled out in the kernel); plan_conv picks their class
 exactly as it does for the inference build (test_conv_plan_classes.py holds that), so the class tables of conv_edge_cases.py
 apply, and the cases here are the ones of the forward module plus 63 / 64-block scenes and 1x1 rows.
 
