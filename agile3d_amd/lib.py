@@ -282,6 +282,35 @@ class TransferSummary(C.Structure):
                 ("err", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class PrototypesSummary(C.Structure):
+    """a3d_prototypes_summary: example rows summed, example rows left out (a channel beyond the fixed-point range or not finite),
+    the error word (A3D_MATCH_BAD_CLASS)."""
+    _fields_ = [("examples", C.c_int64), ("examples_left_out", C.c_int64), ("err", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class FeaturePrototypesArgs(C.Structure):
+    """a3d_feature_prototypes_args: the features and the example classes per row, the integer sums and counts per class, the
+    summary, the number of classes."""
+    _fields_ = [("feats_dev", C.c_void_p), ("classes_dev", C.c_void_p), ("n", C.c_int64), ("sums_dev", C.c_void_p),
+                ("count_dev", C.c_void_p), ("summary_dev", C.c_void_p), ("n_classes", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class MatchSummary(C.Structure):
+    """a3d_match_summary: matched voxels per class, rows with a channel that is not finite, the error word (A3D_MATCH_BAD_CLASS,
+    A3D_MATCH_BAD_INDEX, A3D_MATCH_BAD_PROTOTYPE)."""
+    _fields_ = [("matched", C.c_int64 * 256), ("rows_nonfinite", C.c_int64), ("err", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class FeatureMatchArgs(C.Structure):
+    """a3d_feature_match_args: the features, the prototypes and their classes, the optional candidate mask and lift
+    (inverse_map, n_full), the outputs per voxel and per vertex, the summary, and by value cos_min and k."""
+    _fields_ = [("feats_dev", C.c_void_p), ("n", C.c_int64), ("protos_dev", C.c_void_p), ("proto_class_dev", C.c_void_p),
+                ("candidate_dev", C.c_void_p), ("inverse_map_dev", C.c_void_p), ("n_full", C.c_int64),
+                ("match_qv_dev", C.c_void_p), ("best_qv_dev", C.c_void_p), ("score_qv_dev", C.c_void_p),
+                ("match_full_dev", C.c_void_p), ("score_full_dev", C.c_void_p), ("summary_dev", C.c_void_p),
+                ("cos_min", C.c_double), ("k", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class ObjectMoments(C.Structure):
     """a3d_object_moments: one object of a labelling -- vertices and voxels, the sums of the fixed-point coordinates (X, Y, Z)
     and of their products (XX, XY, XZ, YY, YZ, ZZ), the covered surface in thirds of area quanta, the exact fp32 box."""
@@ -381,6 +410,9 @@ A3D_MEASURE_BLOCK, A3D_MEASURE_CHUNK = 256, 1024
 A3D_GROW_MAX_STEPS, A3D_GROW_BAD_INDEX = 1024, 1
 A3D_NORMALS_RANGE, A3D_NORMALS_BAD_INDEX = 1, 2
 A3D_TRANSFER_UNKEYABLE, A3D_TRANSFER_SORT_FAILED = 1, 2
+A3D_MATCH_CHANNELS, A3D_MATCH_QUANTUM_BITS, A3D_MATCH_FIXED_BITS = 128, 20, 40
+A3D_MATCH_MAX_EXAMPLE_ROWS, A3D_MATCH_MAX_PROTOTYPES, A3D_MATCH_CHUNK = 1 << 22, 256, 16
+A3D_MATCH_BAD_CLASS, A3D_MATCH_BAD_INDEX, A3D_MATCH_BAD_PROTOTYPE = 1, 2, 4
 A3D_ERR_INVALID = -1
 A3D_ERR_WORKSPACE = -5
 PROF_DENSE = 11
@@ -592,6 +624,8 @@ SYMBOLS = {
     "a3d_point_index_destroy": (None, [C.c_void_p]),
     "a3d_point_index_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "a3d_feature_prototypes": (C.c_int, [C.POINTER(FeaturePrototypesArgs), C.c_void_p]),
+    "a3d_feature_match": (C.c_int, [C.POINTER(FeatureMatchArgs), C.c_void_p]),
     "a3d_cull_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "a3d_render_shade_lit_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Camera), C.c_float,

@@ -42,6 +42,9 @@ calls runs in ``libagile3d_hip.so`` (``csrc/session.hip``, ``csrc/clicks.hip``),
     labels on another point set         a3d_point_index_create / a3d_point_index_nearest  (nearest_vertices, transfer,
                                         import_labels: an index over any point set and the bulk exact nearest row within a
                                         reach -- labels to a high-resolution mesh, ground truth from one; a rule of ours)
+    more objects like this one          a3d_feature_prototypes / a3d_feature_match  (lookalikes, lookalike_at: one prototype per
+                                        example object from the backbone's features, the voxels within a cosine threshold of
+                                        one, their connected regions and a suggested click in each; a rule of ours)
 
 There is no CPU path: the model and the scene live on the GPU.
 
@@ -281,6 +284,25 @@ def rank_spots(records, max_spots=MAX_SPOTS):
         raise ValueError("max_spots must be an integer >= 0")
     order = sorted(range(len(records)), key=lambda k: (-int(records[k]["voxels"]), int(records[k]["root"])))
     return order[:int(max_spots)]
+
+
+def rank_candidates(clusters, spots, coords_row_lookup, max_candidates):
+    """The candidates of ``lookalikes()``, best first, from the records of the cluster search over the searched regions
+    (dicts with ``cluster_id``, ``row``, ``label`` = the region's pseudo id, ``error_size``; any order) and ``spots``, the
+    regions' ``a3d_label_pieces`` records in pseudo-id order (``spots[label - 1]``; ``key`` = the matched object): ranked by
+    ``error_size`` -- the depth of the region's deepest voxel -- largest first, equal depths in ascending cluster id, as
+    ``rank_suggestions`` ranks.  At most ``max_candidates`` entries ``{point, row, object, voxels, root, depth}``.  Pure
+    Python."""
+    if int(max_candidates) != max_candidates or max_candidates < 0:
+        raise ValueError("max_candidates must be an integer >= 0")
+    lookup = coords_row_lookup if callable(coords_row_lookup) else coords_row_lookup.__getitem__
+    ranked = sorted(sorted(clusters, key=lambda c: c["cluster_id"]), key=lambda c: c["error_size"], reverse=True)
+    out = []
+    for c in ranked[:int(max_candidates)]:
+        spot = spots[int(c["label"]) - 1]
+        out.append({"point": [float(x) for x in lookup(int(c["row"]))], "row": int(c["row"]), "object": int(spot["key"]),
+                    "voxels": int(spot["voxels"]), "root": int(spot["root"]), "depth": float(c["error_size"])})
+    return out
 
 
 class _Result:
@@ -543,6 +565,19 @@ class GuideResult(_Result):
 
     __slots__ = ("labels_qv", "runner_qv", "margin_qv", "margin_full", "colors", "object_voxels", "object_contested",
                  "least_confident", "n_contested", "suggestions", "threshold", "full_margin", "n_spots", "n_spots_searched")
+
+
+class LookalikeResult(_Result):
+    """What ``lookalikes()`` returns.  Device tensors: ``match_qv`` int32 [n_voxels] (the object a voxel looks like, -1: none),
+    ``score_qv`` fp32 [n_voxels] and ``score_full`` fp32 [n_full] (the cosine to the most similar prototype, passing or not; 0
+    where a voxel was no candidate), ``colors`` fp32 [n_full, 3] (the similarity view, for ``render(colors=)``).  Host:
+    ``candidates`` (``rank_candidates``: dicts ``{point, row, object, voxels, root, depth}``, best first), ``n_regions``
+    (matched regions of at least ``min_voxels``), ``n_regions_searched`` (those among them, at most ``MAX_SPOTS``, whose
+    deepest voxel was searched), ``prototypes`` (``{object: example voxels}``), ``examples_left_out``, ``rows_nonfinite``,
+    and ``cos_min``, ``min_voxels``, ``within``, ``connectivity`` as used."""
+
+    __slots__ = ("match_qv", "score_qv", "score_full", "colors", "candidates", "n_regions", "n_regions_searched", "prototypes",
+                 "examples_left_out", "rows_nonfinite", "cos_min", "min_voxels", "within", "connectivity")
 
 
 class SessionResult(_Result):
@@ -1642,12 +1677,17 @@ class InteractiveSession:
         key = torch.where(want != labels, want * 256 + labels, torch.full_like(labels, -1))
         piece_qv, _, recs, n_spots = self._label_pieces(key, 26)
         spots = [recs[k] for k in rank_spots(recs)]
-        table = torch.zeros(labels.numel() + 1, dtype=torch.int32, device=self.device)      # root row -> pseudo id; slot n: no piece
+        return torch.zeros_like(labels), self._spot_ids(piece_qv, spots), spots, n_spots
+
+    def _spot_ids(self, piece_qv, spots):
+        """int32 [n_voxels]: the pseudo id -- position in ``spots`` (records of ``a3d_label_pieces``) + 1 -- of the piece every
+        voxel lies in, 0 for a voxel of no piece or of one that is not among ``spots``: the wanted labels of the cluster search."""
+        n = piece_qv.numel()
+        table = torch.zeros(n + 1, dtype=torch.int32, device=self.device)                   # root row -> pseudo id; slot n: no piece
         if spots:
             roots = torch.tensor([int(r["root"]) for r in spots], dtype=torch.int64).to(self.device)
             table[roots] = torch.arange(1, len(spots) + 1, dtype=torch.int32, device=self.device)
-        pseudo = table[torch.where(piece_qv >= 0, piece_qv, torch.full_like(piece_qv, labels.numel())).long()].contiguous()
-        return torch.zeros_like(labels), pseudo, spots, n_spots
+        return table[torch.where(piece_qv >= 0, piece_qv, torch.full_like(piece_qv, n)).long()].contiguous()
 
     def pieces(self, connectivity=26, labels=None):
         """The connected PIECES of the session's current voxel labelling -- what ``preview()`` paints, so valid from
@@ -2304,6 +2344,126 @@ class InteractiveSession:
         row = self.inverse_map[vertex]
         both = torch.cat([normals.normals_full[vertex], normals.variation_qv[row].reshape(1)]).cpu().numpy()
         return both[:3].copy(), float(both[3])
+
+    # ------------------------------------------------------------------ more objects like this one
+    def _example_classes(self, obj, selection):
+        """``(classes int32 [n_voxels] on the device: the object a voxel is an example of, -1 for none; the object ids that
+        get a prototype)`` of ``lookalikes(obj=, selection=)``."""
+        labels, n_objects = self._labels_qv, len(self.click_idx) - 1
+        none = torch.full_like(labels, -1)
+        if selection is not None:
+            if obj is None:
+                raise ValueError("selection names the examples of ONE object: obj is missing")
+            obj = V._int_in("obj", obj, 1, 255)
+            sel = self._selection(selection)
+            hit = torch.zeros(labels.numel(), dtype=torch.int32, device=self.device).index_add_(0, self.inverse_map, sel.to(torch.int32))
+            return torch.where(hit > 0, torch.full_like(labels, obj), none), [obj]
+        if obj is None:
+            if n_objects == 0:
+                raise ValueError("lookalikes() needs an example: there is no object yet (click and infer(), or pass selection= with obj=)")
+            return torch.where(labels > 0, labels, none), list(range(1, n_objects + 1))
+        obj = V._int_in("obj", obj, 1, max(n_objects, 1), f"obj must be an existing object id 1 .. {n_objects}, or None (every object)")
+        if n_objects == 0:
+            raise ValueError("lookalikes() needs an example: there is no object yet (click and infer(), or pass selection= with obj=)")
+        return torch.where(labels == obj, labels, none), [obj]
+
+    def lookalikes(self, obj=None, selection=None, cos_min=0.9, min_voxels=8, within="background", connectivity=26,
+                   max_candidates=10, features=None):
+        """MORE OBJECTS LIKE THIS ONE, by the backbone's features: label one chair, ask for its lookalikes.  The EXAMPLES
+        are voxels of the current voxel labelling (what ``preview()`` paints): with ``obj=None`` every object 1..K that has
+        voxels gets a prototype, with ``obj=k`` that object alone; with ``selection`` (a ``SelectResult`` or a uint8 / bool
+        mask over the vertices) and ``obj=k`` the voxels of the selected vertices are the examples of object k, whatever the
+        labelling says.  No example voxel at all raises ``ValueError``.  An object's PROTOTYPE is the mean of its examples'
+        feature rows (``a3d_feature_prototypes``: integer sums in fixed point, so it depends on no order; ``view.
+        prototype_table``).  Every CANDIDATE voxel then takes the object whose prototype it is most similar to, provided the
+        cosine reaches ``cos_min`` (``a3d_feature_match``; the rule, reproducible to the bit, is stated in
+        include/agile3d_hip.h).  ``within="background"``: only voxels labelled 0 that are no example may match;
+        ``"all"``: every voxel, except that an example never matches its own object.
+
+        The matched voxels form REGIONS: connected pieces (``connectivity``, ``a3d_label_pieces``) of one matched object.
+        Regions below ``min_voxels`` voxels are dropped; the rest are ranked by size, ties to the lower root
+        (``rank_spots``), and for the first ``MAX_SPOTS`` = 255 the deepest voxel -- the one farthest from everything
+        outside the region -- is found by the click simulator's search (``a3d_click_clusters``), as ``guide(regions=
+        "connected")`` finds a spot's.  ``candidates`` holds one suggested click per searched region, deepest first
+        (``rank_candidates``), at most ``max_candidates``: ``ses.click(c["point"], new_id)`` takes a candidate as a NEW
+        object (or ``c["object"]`` to add it to the object it looks like).  ``colors`` is the similarity view: a matched
+        vertex's own colour faded towards its matched object's palette colour by the score (``own * (1 - s) + palette *
+        s``, s = the score clamped to [0, 1]); ``render(colors=res.colors)`` shows it as it is.
+
+        ``features``: fp32 [n_voxels, 128] on the device, used instead of the backbone's output (``ses._backbone[0].F``),
+        as ``infer(logits=)`` and ``patches(normals=)`` take theirs.  The default ``cos_min`` = 0.9 (and ``min_voxels`` = 8)
+        is this project's choice and is NOT tuned on real scans: how alike two chairs' features are depends on the
+        checkpoint.  Two library calls, the piece search and the cluster search; TWO host round trips, what ``guide(regions=
+        "connected")`` pays: the regions' records (with the summaries and the example counts), then the search's result --
+        one when no region is left to search.  The method reads the current labelling each call and changes no session
+        state.  Returns a ``LookalikeResult``."""
+        self._need_scene()
+        if within not in ("background", "all"):
+            raise ValueError('within must be "background" or "all"')
+        connectivity = V._connectivity(connectivity)
+        min_voxels = V._int_in("min_voxels", min_voxels, 1, (1 << 31) - 1)
+        max_candidates = V._int_in("max_candidates", max_candidates, 0, (1 << 31) - 1)
+        try:
+            cos_min = float(cos_min)
+        except (TypeError, ValueError):
+            raise ValueError("cos_min must be a finite number in [0, 1]") from None
+        if not 0.0 <= cos_min <= 1.0:
+            raise ValueError("cos_min must be a finite number in [0, 1]")
+        dev, labels = self.device, self._labels_qv
+        n = labels.numel()
+        feats = self._backbone[0].F if features is None else features
+        if not torch.is_tensor(feats) or feats.device != dev or feats.dtype != torch.float32 or tuple(feats.shape) != (n, V.MATCH_CHANNELS):
+            raise ValueError(f"features must be an fp32 tensor [{n}, {V.MATCH_CHANNELS}] on the session's device")
+        feats = feats.contiguous()
+        classes, ids = self._example_classes(obj, selection)
+        sums, count, proto_sum = V.feature_prototypes(feats, classes, n_classes=ids[-1] + 1)
+        id_rows = torch.tensor(ids, dtype=torch.int64).to(dev)
+        protos = V.prototype_table(sums, count)[id_rows].contiguous()
+        candidate = ((labels == 0) & (classes < 0)).to(torch.uint8) if within == "background" else None
+        match_qv, _, score_qv, match_full, score_full, match_sum = V.feature_match(
+            feats, protos, id_rows.to(torch.int32), cos_min, candidate=candidate, inverse_map=self.inverse_map)
+        if within == "all":                          # an example never matches its own object
+            match_qv = torch.where(match_qv == classes, torch.full_like(match_qv, -1), match_qv)
+            match_full = torch.where(match_full == classes[self.inverse_map], torch.full_like(match_full, -1), match_full)
+        piece_qv, _, recs, _, tail = self._label_pieces(
+            match_qv, connectivity, also=lambda *_: torch.cat([proto_sum, match_sum, count.view(torch.uint8)]))   # round trip 1
+        at = V.PROTOTYPES_SUMMARY.itemsize + V.MATCH_SUMMARY.itemsize
+        ps, ms = V.read_prototypes_summary(tail[:V.PROTOTYPES_SUMMARY.itemsize]), V.read_match_summary(tail[V.PROTOTYPES_SUMMARY.itemsize:at])
+        if ps["err"] or ms["err"]:
+            raise RuntimeError(f"lookalikes: labels, inverse_map or prototypes out of range (error words {ps['err']}, {ms['err']})")
+        per_class = tail[at:].view(np.int32)
+        prototypes = {k: int(per_class[k]) for k in ids if per_class[k] > 0}
+        if not prototypes:
+            raise ValueError("lookalikes() needs an example: no voxel of " + (f"object {ids[0]}" if len(ids) == 1 else "any object")
+                             + (" with features in range" if ps["examples_left_out"] else ""))
+        kept = [r for r in recs if int(r["voxels"]) >= min_voxels]
+        spots = [kept[k] for k in rank_spots(kept)]
+        clusters = []
+        if spots:
+            launched = K.launch_clusters(torch.zeros_like(labels), self._spot_ids(piece_qv, spots), self.raw_coords_qv)
+            try:
+                launched[1].copy_(launched[0], non_blocking=True)
+            finally:
+                torch.cuda.current_stream(dev).synchronize()      # round trip 2
+            clusters = K.read_clusters(launched[1].numpy(), bad_ids="a3d_click_clusters: labels outside 0 .. 255",
+                                       too_many="a3d_click_clusters: {} regions", whole_sample_ok=True)
+        own, s = self.colors_full, score_full.clamp(0.0, 1.0).unsqueeze(1)
+        colors = torch.where((match_full >= 0).unsqueeze(1), own * (1.0 - s) + self._palette_colors(match_full) * s, own)
+        return LookalikeResult(match_qv=match_qv, score_qv=score_qv, score_full=score_full, colors=colors,
+                               candidates=rank_candidates(clusters, spots, self._coords_qv_host, max_candidates),
+                               n_regions=len(kept), n_regions_searched=len(spots), prototypes=prototypes,
+                               examples_left_out=ps["examples_left_out"], rows_nonfinite=ms["rows_nonfinite"], cos_min=cos_min,
+                               min_voxels=min_voxels, within=within, connectivity=connectivity)
+
+    def lookalike_at(self, result, u, v, **kw):
+        """``lookalikes(obj=...)`` with the object under pixel ``(u, v)`` (column, row) of ``result`` as the example
+        (``object_at``: the labels of the last ``infer`` / ``preview``); ``kw`` are ``lookalikes``' other arguments.  A pixel
+        that shows the background or nothing raises ``ValueError``.  One small device-to-host copy more than ``lookalikes``."""
+        self._need_scene()
+        obj = self.object_at(result, u, v)
+        if not obj:
+            raise ValueError(f"pixel ({int(u)}, {int(v)}) shows " + ("nothing" if obj is None else "the background") + ": no object to look for")
+        return self.lookalikes(obj=obj, **kw)
 
     # ------------------------------------------------------------------ labels to and from another point set
     def _points(self, name, points):

@@ -1337,3 +1337,134 @@ def session_overlay(labels_in, manual_on, manual_obj, selected=None, op="none", 
     a.summary_dev = summary.data_ptr()
     L.check(L.load().a3d_session_overlay(C.byref(a), L.stream(dev)), "a3d_session_overlay")
     return labels_out, colors_out, summary
+
+
+# ---- more objects like this one: prototypes of example classes, the best prototype per voxel under a cosine threshold ---------
+PROTOTYPES_SUMMARY = np.dtype([("examples", "<i8"), ("examples_left_out", "<i8"), ("err", "<i4"), ("reserved_", "<i4")])
+MATCH_SUMMARY = np.dtype([("matched", "<i8", (L.A3D_MATCH_MAX_PROTOTYPES,)), ("rows_nonfinite", "<i8"), ("err", "<i4"),
+                          ("reserved_", "<i4")])
+assert C.sizeof(L.PrototypesSummary) == PROTOTYPES_SUMMARY.itemsize == 24
+assert C.sizeof(L.MatchSummary) == MATCH_SUMMARY.itemsize == 2064
+MATCH_CHANNELS, MATCH_MAX_PROTOTYPES = L.A3D_MATCH_CHANNELS, L.A3D_MATCH_MAX_PROTOTYPES
+MATCH_QUANTUM = 2.0 ** -L.A3D_MATCH_QUANTUM_BITS
+MATCH_BAD_CLASS, MATCH_BAD_INDEX, MATCH_BAD_PROTOTYPE = L.A3D_MATCH_BAD_CLASS, L.A3D_MATCH_BAD_INDEX, L.A3D_MATCH_BAD_PROTOTYPE
+
+
+def read_prototypes_summary(host):
+    """The host copy of an ``a3d_prototypes_summary`` (uint8 [24], or anything of those bytes) as a dict of Python ints:
+    ``examples``, ``examples_left_out``, ``err`` (bit ``MATCH_BAD_CLASS``)."""
+    return _summary_ints(host, PROTOTYPES_SUMMARY)
+
+
+def read_match_summary(host):
+    """The host copy of an ``a3d_match_summary`` (uint8 [2064], or anything of those bytes): ``matched`` (int64 [256], matched
+    voxels per class), ``rows_nonfinite`` and ``err`` (bits ``MATCH_BAD_CLASS``, ``MATCH_BAD_INDEX``, ``MATCH_BAD_PROTOTYPE``)."""
+    rec = _record(host, MATCH_SUMMARY)
+    return dict(matched=rec["matched"].astype(np.int64), rows_nonfinite=int(rec["rows_nonfinite"]), err=int(rec["err"]))
+
+
+def _features(name, feats, dev=None):
+    """(pointer, rows) of a feature table: fp32 [n, 128], contiguous, on the GPU (on ``dev`` when given)."""
+    dev = _device(name, feats) if dev is None else dev
+    return _ptr(name, feats, F32, (None, MATCH_CHANNELS), dev), feats.shape[0]
+
+
+def feature_prototypes(feats, classes, n_classes=MATCH_MAX_PROTOTYPES, sums=None, count=None, summary=None):
+    """``a3d_feature_prototypes``: the fixed-point sums of the example rows of ``feats`` fp32 [n, 128] per class -- ``classes``
+    int32 [n], -1 = no example, 0 .. n_classes-1 = the class; n < 2^22, 1 <= n_classes <= 256.  Returns ``(sums int64
+    [n_classes, 128], count int32 [n_classes], summary uint8 [24])`` on the device (the caller's tensors or new ones);
+    ``prototype_table`` turns the first two into prototypes, ``read_prototypes_summary`` decodes the summary's host copy."""
+    dev = _device("feats", feats)
+    a = L.FeaturePrototypesArgs()
+    a.feats_dev, a.n = _features("feats", feats)
+    if a.n >= L.A3D_MATCH_MAX_EXAMPLE_ROWS:
+        raise ValueError(f"feats: {a.n} rows, the prototypes take fewer than 2^22")
+    a.classes_dev = _ptr("classes", classes, I32, (a.n,), dev)
+    a.n_classes = _int_in("n_classes", n_classes, 1, MATCH_MAX_PROTOTYPES)
+    sums = _out("sums", sums, I64, (a.n_classes, MATCH_CHANNELS), dev)
+    count = _out("count", count, I32, (a.n_classes,), dev)
+    summary = _summary(summary, PROTOTYPES_SUMMARY.itemsize, dev)
+    a.sums_dev, a.count_dev, a.summary_dev = sums.data_ptr(), count.data_ptr(), summary.data_ptr()
+    L.check(L.load().a3d_feature_prototypes(C.byref(a), L.stream(dev)), "a3d_feature_prototypes")
+    return sums, count, summary
+
+
+def prototype_table(sums, count):
+    """The caller's step of the prototype rule: fp32 [n_classes, 128], row c = ``float32((float64(sums[c]) / float64(count[c]))
+    * 2^-20)`` -- int64 -> double to nearest even, one division, one exact scaling, one rounding, each an IEEE operation, so
+    numpy arrays (the host step; a numpy array comes back) and tensors on any device (a tensor there comes back, nothing is
+    synchronised) give the same bits.  A class with ``count == 0`` has no prototype: its row is ZERO, and a zero prototype
+    (``pp == 0``) takes part in no match.  ``sums`` int64 [n_classes, 128], ``count`` int32 [n_classes]."""
+    if torch.is_tensor(sums) != torch.is_tensor(count):
+        raise ValueError("sums and count must both be tensors or both be numpy arrays")
+    if torch.is_tensor(sums):
+        if sums.dtype is not I64 or sums.dim() != 2 or sums.shape[1] != MATCH_CHANNELS:
+            raise ValueError(f"sums must be an int64 [n_classes, {MATCH_CHANNELS}] tensor")
+        if count.dtype is not I32 or tuple(count.shape) != (sums.shape[0],) or count.device != sums.device:
+            raise ValueError(f"count must be an int32 [{sums.shape[0]}] tensor on sums' device")
+        has = (count > 0).unsqueeze(1)
+        mean = sums.to(torch.float64) / torch.where(has, count.unsqueeze(1), torch.ones_like(count.unsqueeze(1))).to(torch.float64)
+        return torch.where(has, (mean * MATCH_QUANTUM).to(torch.float32), torch.zeros((), dtype=torch.float32, device=sums.device))
+    s, c = np.asarray(sums), np.asarray(count)
+    if s.dtype != np.int64 or s.ndim != 2 or s.shape[1] != MATCH_CHANNELS:
+        raise ValueError(f"sums must be an int64 [n_classes, {MATCH_CHANNELS}] array")
+    if c.dtype != np.int32 or c.shape != (s.shape[0],):
+        raise ValueError(f"count must be an int32 [{s.shape[0]}] array")
+    has = (c > 0)[:, None]
+    mean = s.astype(np.float64) / np.where(has, c[:, None], 1).astype(np.float64)
+    return np.where(has, (mean * MATCH_QUANTUM).astype(np.float32), np.float32(0.0))
+
+
+def feature_match(feats, protos, proto_class, cos_min, candidate=None, inverse_map=None, match_qv=None, best_qv=None,
+                  score_qv=None, match_full=None, score_full=None, summary=None):
+    """``a3d_feature_match``: per row of ``feats`` fp32 [n, 128] the best of the prototypes ``protos`` fp32 [k, 128] (1 <= k <=
+    256; ``proto_class`` int32 [k], classes 0..255) whose cosine reaches ``cos_min`` (a finite number in [0, 1]), by the rule
+    of include/agile3d_hip.h.  ``candidate`` uint8 [n]: 0 = the voxel matches nothing (``None``: every voxel may).
+    ``inverse_map`` int64 [n_full]: also lift the match and the score to the vertices.  ``protos`` on the HOST (a numpy array
+    or a CPU tensor) are checked to be finite and uploaded; prototypes already on the device are the caller's word -- one that
+    is not finite takes part in nothing and sets ``MATCH_BAD_PROTOTYPE`` in the summary.  Outputs: the caller's tensors or new
+    ones.  Returns ``(match_qv int32 [n], best_qv int32 [n], score_qv fp32 [n], match_full int32 [n_full] or None, score_full
+    fp32 [n_full] or None, summary uint8 [2064])`` on the device; ``read_match_summary`` decodes the summary's host copy."""
+    dev = _device("feats", feats)
+    a = L.FeatureMatchArgs()
+    a.feats_dev, a.n = _features("feats", feats)
+    if a.n >= 1 << 31:
+        raise ValueError(f"feats: {a.n} rows, a call takes fewer than 2^31")
+    if not (torch.is_tensor(protos) and protos.device.type == "cuda"):
+        host = np.asarray(protos.numpy() if torch.is_tensor(protos) else protos)
+        if host.dtype != np.float32 or host.ndim != 2 or host.shape[1] != MATCH_CHANNELS:
+            raise ValueError(f"protos must be fp32 [k, {MATCH_CHANNELS}]")
+        if not np.isfinite(host).all():
+            raise ValueError("protos must be finite")
+        if not 1 <= host.shape[0] <= MATCH_MAX_PROTOTYPES:
+            raise ValueError(f"protos: k = {host.shape[0]} prototypes, a call takes 1 .. {MATCH_MAX_PROTOTYPES}")
+        protos = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+    a.protos_dev, a.k = _features("protos", protos, dev)
+    if not 1 <= a.k <= MATCH_MAX_PROTOTYPES:
+        raise ValueError(f"protos: k = {a.k} prototypes, a call takes 1 .. {MATCH_MAX_PROTOTYPES}")
+    a.proto_class_dev = _ptr("proto_class", proto_class, I32, (a.k,), dev)
+    try:
+        a.cos_min = float(cos_min)
+    except (TypeError, ValueError):
+        raise ValueError("cos_min must be a finite number in [0, 1]") from None
+    if not 0.0 <= a.cos_min <= 1.0:                     # (NaN fails both)
+        raise ValueError("cos_min must be a finite number in [0, 1]")
+    a.candidate_dev = _ptr("candidate", candidate, U8, (a.n,), dev, optional=True)
+    match_qv, best_qv = _out("match_qv", match_qv, I32, (a.n,), dev), _out("best_qv", best_qv, I32, (a.n,), dev)
+    score_qv = _out("score_qv", score_qv, F32, (a.n,), dev)
+    if a.n:
+        a.match_qv_dev, a.best_qv_dev, a.score_qv_dev = match_qv.data_ptr(), best_qv.data_ptr(), score_qv.data_ptr()
+    if inverse_map is not None:
+        _ptr("inverse_map", inverse_map, I64, (None,), dev)
+        a.n_full = inverse_map.shape[0]
+        if a.n_full >= 1 << 31:
+            raise ValueError(f"inverse_map: {a.n_full} rows, a call takes fewer than 2^31")
+        match_full, score_full = _out("match_full", match_full, I32, (a.n_full,), dev), _out("score_full", score_full, F32, (a.n_full,), dev)
+        if a.n_full:
+            a.inverse_map_dev, a.match_full_dev, a.score_full_dev = inverse_map.data_ptr(), match_full.data_ptr(), score_full.data_ptr()
+    elif match_full is not None or score_full is not None:
+        raise ValueError("match_full and score_full belong to the lift: inverse_map is missing")
+    summary = _summary(summary, MATCH_SUMMARY.itemsize, dev)
+    a.summary_dev = summary.data_ptr()
+    L.check(L.load().a3d_feature_match(C.byref(a), L.stream(dev)), "a3d_feature_match")
+    return match_qv, best_qv, score_qv, match_full, score_full, summary

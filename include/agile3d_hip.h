@@ -1472,6 +1472,108 @@ int    a3d_point_index_nearest(const a3d_point_index* index, const float* querie
                                const int32_t* labels_src_dev, int32_t fill, int32_t* nearest_out_dev, float* d2_out_dev,
                                int32_t* labels_out_dev, a3d_transfer_summary* summary_dev, void* stream);
 
+/* MORE OBJECTS LIKE THIS ONE: query by example on per-voxel features (csrc/session_match.hip) -- one prototype per example
+ * class, and per voxel the best prototype under a cosine threshold.  The features are the backbone's output, fp32 [n][128]
+ * (A3D_MATCH_CHANNELS).  The reference has no counterpart.  The rule is built so that every DECISION is reproducible to the
+ * bit by a plain restatement (tests/match_rule.py); only the displayed score carries a tolerance.
+ *
+ * THE RULE, PROTOTYPES (a3d_feature_prototypes).  classes_dev int32 [n]: -1 = the row is no example, 0 .. n_classes-1 = its
+ * class (1 <= n_classes <= 256); any other value sets A3D_MATCH_BAD_CLASS and the row is no example.  Every channel of an
+ * example row goes to fixed point, X = llrint(f / quantum) with quantum = 2^-20 (A3D_MATCH_QUANTUM_BITS; the quotient is
+ * exact, the rounding is to nearest even), accepted while |X| <= 2^40 (A3D_MATCH_FIXED_BITS).  A row with ANY channel beyond
+ * that or not finite is left out as a whole and counted in examples_left_out.  sums_dev int64 [n_classes][128] and count_dev
+ * int32 [n_classes] are the INTEGER sums of X and of 1 over the class's rows that count: they depend on no order.  The call
+ * refuses n >= 2^22 (A3D_MATCH_MAX_EXAMPLE_ROWS: count * 2^40 <= 2^62 fits int64).  sums, count and the summary are cleared by
+ * the call.  The prototype of class c is computed by the CALLER, in double and rounded once to fp32:
+ *     p_c[i] = (float)(((double)sums[c][i] / (double)count[c]) * quantum)
+ * (int64 -> double to nearest even, one division, one exact scaling, one rounding); a class with count 0 has no prototype.
+ * Prototypes are NOT normalised: their squared length enters the test below, which lets a threshold of exactly 1 be met
+ * exactly (a voxel that is a power of two times its prototype has dot * dot == nn * pp to the bit).
+ *
+ * THE RULE, MATCH (a3d_feature_match).  protos_dev fp32 [k][128] and proto_class_dev int32 [k] with 1 <= k <= 256
+ * (A3D_MATCH_MAX_PROTOTYPES), classes in 0..255; c2 = cos_min * cos_min for a double cos_min in [0, 1], rounded once.  All
+ * arithmetic is double.  With ONE accumulator each, starting at 0, channels ascending i = 0..127:
+ *     nn = sum f_i * f_i;      pp_c = sum p_ci * p_ci;      dot_c = sum f_i * p_ci
+ * Each product of two fp32 values is exact in double, so a fused multiply-add and a multiply then an add give the same bits;
+ * only the order of the additions matters, and it is fixed (no split across lanes, no matrix cores).
+ * A voxel CAN BE SCORED when all its channels are finite, nn > 0 and candidate_dev (uint8 [n], optional) is not 0 there; a
+ * prototype TAKES PART when 0 < pp_c < +inf (one with a channel that is not finite also sets A3D_MATCH_BAD_PROTOTYPE, one
+ * with a class outside 0..255 sets A3D_MATCH_BAD_CLASS and is not counted in the summary).  For a voxel that can be scored
+ * ONE SCAN runs over the prototypes that take part, c ascending, with d2_c = dot_c * dot_c:
+ *   best:  the first becomes the best; a later c replaces the best b when it BEATS it: with s = the sign of dot (-1, 0, 1),
+ *          s_c != s_b: s_c > s_b;  both > 0: d2_c * pp_b > d2_b * pp_c;  both < 0: d2_c * pp_b < d2_b * pp_c;  both 0: no.
+ *   match: c PASSES when dot_c > 0 and d2_c >= (c2 * (nn * pp_c)); the first that passes becomes the match; a later passing
+ *          c replaces the match m when d2_c * pp_m > d2_m * pp_c.
+ * Every multiplication is rounded on its own, with that parenthesisation; ties keep the lower index.  The comparison of
+ * rounded products is not transitive in the last bit, so the ORDER of the scan is part of the rule.
+ * OUTPUTS: match_qv_dev int32 [n] = proto_class of the match, -1 without one; best_qv_dev int32 [n] = the best's index, -1
+ * where the voxel cannot be scored or no prototype takes part; score_qv_dev fp32 [n] = (float)(dot_b / sqrt(nn * pp_b)) of the
+ * best b (double division and square root, one rounding to fp32), 0 where best is -1.  With inverse_map_dev int64 [n_full]:
+ * match_full_dev int32 [n_full] and score_full_dev fp32 [n_full] = the values of voxel inverse_map[j]; an index outside
+ * 0..n-1 sets A3D_MATCH_BAD_INDEX and is not followed (the two entries are not written).  The summary (8-byte aligned, cleared
+ * by the call): matched voxels per class, rows with a channel that is not finite (whatever candidate says), the error word.
+ * Integer sums, one atomic per workgroup and counter: two calls give the same bytes in every output.
+ *
+ * The library allocates nothing and does not synchronise; the stages are launches -- no grid barrier, no spin-wait.
+ * A3D_ERR_INVALID with nothing launched and nothing written: no arguments; n < 0 or too large (2^22 for the prototypes, 2^31
+ * for the match, also n_full); rows without feats_dev (or one that is not 16-byte aligned), classes_dev or the per-voxel
+ * outputs; no sums_dev, count_dev, summary_dev (or sums, summary not 8-byte aligned); n_classes outside 1..256; k outside
+ * 1..256; no protos_dev or proto_class_dev; cos_min outside [0, 1] or NaN; match_full_dev, score_full_dev or n_full > 0
+ * without inverse_map_dev, or inverse_map_dev with n_full > 0 and without both.
+ * LIMITS: one prototype per class, the mean -- an object whose parts look different is described badly by it; the features
+ * are whatever the backbone learnt: nothing here makes them discriminative. */
+#define A3D_MATCH_CHANNELS         128
+#define A3D_MATCH_QUANTUM_BITS     20        /* quantum = 2^-20 */
+#define A3D_MATCH_FIXED_BITS       40        /* |X| <= 2^40 */
+#define A3D_MATCH_MAX_EXAMPLE_ROWS (1 << 22) /* a3d_feature_prototypes: n below this */
+#define A3D_MATCH_MAX_PROTOTYPES   256       /* k, n_classes, and the classes counted */
+#define A3D_MATCH_CHUNK            16        /* prototypes the match kernel stages in LDS at a time (a kernel constant, for tests) */
+#define A3D_MATCH_BAD_CLASS        1
+#define A3D_MATCH_BAD_INDEX        2
+#define A3D_MATCH_BAD_PROTOTYPE    4
+typedef struct a3d_prototypes_summary {
+  int64_t examples;                 /* rows that were summed */
+  int64_t examples_left_out;        /* example rows left out: a channel beyond 2^40 quanta or not finite */
+  int32_t err;                      /* A3D_MATCH_BAD_CLASS */
+  int32_t reserved_;
+} a3d_prototypes_summary;          /* 24 bytes */
+typedef struct a3d_feature_prototypes_args {
+  const float*   feats_dev;         /* [n][128] */
+  const int32_t* classes_dev;       /* [n] */
+  int64_t        n;
+  int64_t*       sums_dev;          /* out [n_classes][128] */
+  int32_t*       count_dev;         /* out [n_classes] */
+  a3d_prototypes_summary* summary_dev;
+  int32_t        n_classes;
+  int32_t        reserved_;
+} a3d_feature_prototypes_args;     /* 56 bytes */
+typedef struct a3d_match_summary {
+  int64_t matched[A3D_MATCH_MAX_PROTOTYPES];   /* voxels whose match has this class */
+  int64_t rows_nonfinite;           /* rows with a channel that is not finite */
+  int32_t err;                      /* A3D_MATCH_BAD_CLASS | A3D_MATCH_BAD_INDEX | A3D_MATCH_BAD_PROTOTYPE */
+  int32_t reserved_;
+} a3d_match_summary;               /* 2064 bytes */
+typedef struct a3d_feature_match_args {
+  const float*   feats_dev;         /* [n][128] */
+  int64_t        n;
+  const float*   protos_dev;        /* [k][128] */
+  const int32_t* proto_class_dev;   /* [k] */
+  const uint8_t* candidate_dev;     /* [n] or NULL: every voxel */
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL: no lift */
+  int64_t        n_full;
+  int32_t*       match_qv_dev;      /* out [n] */
+  int32_t*       best_qv_dev;       /* out [n] */
+  float*         score_qv_dev;      /* out [n] */
+  int32_t*       match_full_dev;    /* out [n_full], with inverse_map_dev */
+  float*         score_full_dev;    /* out [n_full], with inverse_map_dev */
+  a3d_match_summary* summary_dev;
+  double         cos_min;
+  int32_t        k;
+  int32_t        reserved_;
+} a3d_feature_match_args;          /* 120 bytes */
+int    a3d_feature_prototypes(const a3d_feature_prototypes_args* args, void* stream);
+int    a3d_feature_match(const a3d_feature_match_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
  * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a
