@@ -24,15 +24,16 @@ def zmat(seed, sample, site, p, heads, rows, cols):
     return ops.dropout_mask(seed, sample, site, p, heads, rows, cols).cpu().double() * drop_scale(p)
 
 
-def mha_ref(q, k, v, w, mask, Z=None, per_head=False):
+def mha_ref(q, k, v, w, mask, Z=None, per_head=False, dtype=torch.float64):
     """softmax(q k^T / 4 + mask) (o Z) v per head (8 x 16) in float64 on the CPU, autograd for the loss sum(o * w):
     (o, dq, dk, dv).  ``per_head``: one head at a time (16-channel slices, written back), for the cases whose [8, Lq, Lk]
-    float64 matrices would take gigabytes."""
+    float64 matrices would take gigabytes.  ``dtype=torch.float32``: the same formula in plain float32, whose distance from
+    the float64 result is what the rounding of the scores alone costs (check_measured)."""
     Lq, Lk = q.shape[0], k.shape[0]
-    q64, k64, v64, w64 = (t.double() for t in (q, k, v, w))
+    q64, k64, v64, w64 = (t.to(dtype) for t in (q, k, v, w))
     blocked = mask.bool()[None] if mask is not None else None
-    o, dq = torch.empty(Lq, 128, dtype=torch.float64), torch.empty(Lq, 128, dtype=torch.float64)
-    dk, dv = torch.empty(Lk, 128, dtype=torch.float64), torch.empty(Lk, 128, dtype=torch.float64)
+    o, dq = torch.empty(Lq, 128, dtype=dtype), torch.empty(Lq, 128, dtype=dtype)
+    dk, dv = torch.empty(Lk, 128, dtype=dtype), torch.empty(Lk, 128, dtype=dtype)
     nh = 1 if per_head else 8
     for h0 in range(0, 8, nh):
         sl = slice(16 * h0, 16 * (h0 + nh))
@@ -42,7 +43,7 @@ def mha_ref(q, k, v, w, mask, Z=None, per_head=False):
             s = s.masked_fill(blocked, float("-inf"))
         p = torch.softmax(s, -1)
         if Z is not None:
-            p = p * Z[h0:h0 + nh]
+            p = p * Z[h0:h0 + nh].to(dtype)
         oh = torch.einsum("hij,jhd->ihd", p, vh.view(Lk, nh, 16)).reshape(Lq, 16 * nh)
         (oh * w64[:, sl]).sum().backward()
         o[:, sl], dq[:, sl], dk[:, sl], dv[:, sl] = oh.detach(), qh.grad, kh.grad, vh.grad
@@ -59,3 +60,22 @@ def check(tag, got, want, tol=TOL, names=("o", "dq", "dk", "dv")):
         errs.append((name, err, sc))
     for name, err, sc in errs:
         assert err <= tol * sc, (tag, name, err, sc)          # (a NaN fails: the comparison is False)
+
+
+def check_measured(tag, got, want, ref32, floor=TOL, factor=4.0, names=("o", "dq", "dk", "dv")):
+    """Scores far from zero: the float32 rounding of a score of 60 alone moves its weight by about 1e-5 relative, so the bar
+    is measured -- max|got - want| <= max(floor, factor * e32) * max|want| per output, e32 the distance of the plain float32
+    formula (``ref32``) from float64 (``want``); the factor is for another summation order and v_exp_f32 against expf.  Every
+    figure is printed before the first assertion; returns [(name, e32, kernel's figure)]."""
+    rows = []
+    for name, g, r, r32 in zip(names, got, want, ref32):
+        r = r.detach()
+        sc = max(1e-6, r.abs().max().item())
+        e32 = (r32.detach().double() - r).abs().max().item() / sc
+        err = (g.double().cpu() - r).abs().max().item() / sc
+        print(f"{tag} {name}: e32 {e32:.2e}, kernel {err:.2e} (scale {sc:.2e}), bar {max(floor, factor * e32):.2e}")
+        rows.append((name, e32, err))
+    for name, e32, err in rows:
+        assert factor * e32 <= 1e-3, (tag, name, e32, "too extreme an input for float32")
+        assert err <= max(floor, factor * e32), (tag, name, err, e32)      # (a NaN fails: the comparison is False)
+    return rows

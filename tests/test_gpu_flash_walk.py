@@ -7,11 +7,21 @@ reach, each against float64 autograd of the plain formula on the CPU:
     second chunk, the slab reduction over 256 slabs;
   * every build of the c2s forward (QT = 2, 4, 6, 8, 10, 14 query tiles) and its second launch for 225 .. 256 queries;
   * short sides: fewer keys than one chunk / one group, a single key, a single query, 256 keys on the short side of s2c;
-  * the decoder tape on a scene long enough to walk, flash against materialised scores.
+  * the decoder tape on a scene long enough to walk, flash against materialised scores;
+  * scores far from zero (test_scores_far_from_zero): q scaled so that q k^T / 4 spans +-50 instead of +-5, the long side
+    as drawn, sorted so that the running maximum climbs along the walk, sorted so that it falls, and one key 60 above every
+    other in the last chunk -- the online softmax's rescale by tens and the backward's recomputation from the saved
+    statistics.
 
 Every input is seeded; nothing is read from disk.  The bar is the one of the other flash tests: max|diff| <= 2e-5 of the
 reference's largest magnitude, per output.  Workspaces and outputs start out as NaN: a slab element that is read before
-the walk's first chunk wrote it, or an output row nothing writes, fails the comparison instead of passing on zeros."""
+the walk's first chunk wrote it, or an output row nothing writes, fails the comparison instead of passing on zeros.
+
+At |score| = 60 the float32 rounding of the score itself moves a weight by about 1e-5 relative, so the far-from-zero cases
+measure their bar: max(2e-5, 4 e32), e32 being the distance of the plain formula in float32 on the CPU from the float64
+result (attn_kit.check_measured).  Measured on an MI355X over the 22 cases, per output relative to the reference's largest
+magnitude: largest e32 3.9e-06 (s2c 16485x20 rising, dk), largest kernel figure 4.2e-06 (c2s 20x16485 peak, dq): 4 e32 never
+exceeded 2e-5, so every case was held to 2e-5."""
 import functools
 
 import pytest
@@ -19,7 +29,7 @@ import torch
 
 from agile3d_amd import decoder_ops as ops
 from agile3d_amd import lib as L
-from attn_kit import DEV, check as _check, mha_ref as _mha_ref, nan as _nan, poisoned as _workspace, zmat
+from attn_kit import DEV, check as _check, check_measured as _check_measured, mha_ref as _mha_ref, nan as _nan, poisoned as _workspace, zmat
 
 pytestmark = pytest.mark.gpu
 CHUNK = 64                 # points per chunk (kFlChunk)
@@ -205,6 +215,88 @@ def test_s2c_dropout_walk_and_widest_key_side(Lq, Lk):
     want = _mha_ref(q, k, v, w, None, Z)
     got = _flash_s2c(q, k, v, w, drop=L.Dropout(SEED, P_DROP, sample, site, 0))
     _check(f"flash s2c dropout {Lq}x{Lk}", got, want)
+
+
+# ---------------------------------------------------------------------------------------------------- scores far from zero
+SPAN, PEAK = 50.0, 60.0     # largest |score| of the scaled inputs (asserted within 40 .. 60); the peaked key's lead
+VALUE_SHAPES = [("c2s", 20, 16485), ("c2s", 225, 700), ("c2s", 20, 65), ("s2c", 16485, 20), ("s2c", 700, 256)]
+ORDERS = ("drawn", "rising", "falling", "peak")
+
+
+def _scores(q, k):
+    """float64 q k^T / 4 per head: [8, Lq, Lk]"""
+    return torch.einsum("ihd,jhd->hij", q.double().view(-1, 8, 16), k.double().view(-1, 8, 16)) / 4.0
+
+
+@functools.lru_cache(maxsize=None)
+def _value_case(side, Lq, Lk, order, drop):
+    """q (times c: the scores span +-SPAN), k, v, w, mask, Z, the float64 reference and the plain float32 one.
+    rising / falling: the long side -- the keys of c2s, the points of s2c -- sorted by head 0's score of query 0 (c2s) or
+    key 0 (s2c), so that a workgroup's running maximum climbs along its walk or is set by its first chunk; peak: one key --
+    in the last chunk of c2s, the last key of s2c -- whose score is at least PEAK above every other of its row.  In s2c only
+    every second point has that lead: where EVERY row is saturated (a weight of exactly 1.0) the true dq and dk are about
+    1e-26 and "relative to the reference's largest magnitude" means nothing -- the flash backward's dS = P (dP - o . do) then
+    keeps the float32 cancellation between dP and o . do, 2e-5 absolute on these operands, which the plain formula does not
+    have (measured: kernel 2.2e-5 absolute against a reference of 8e-27).  The saturated rows stay in the case, next to rows
+    that give the gradients a scale."""
+    seed = (Lq * 7 + Lk) if side == "c2s" else (Lq * 3 + Lk)
+    q, k, v, w = (t.clone() for t in _qkvw(Lq, Lk, seed))
+    q *= SPAN / _scores(q, k).abs().max().item()
+    walks = (Lk if side == "c2s" else Lq) > CAP * CHUNK
+    if order in ("rising", "falling"):
+        s0 = _scores(q, k)[0]
+        perm = torch.argsort(s0[0, :] if side == "c2s" else s0[:, 0], descending=order == "falling")
+        if side == "c2s":
+            k, v = k[perm].contiguous(), v[perm].contiguous()
+        else:
+            q, w = q[perm].contiguous(), w[perm].contiguous()
+    if order == "peak":
+        # channel 0 of every head: a for every query, 0 for every key but the peaked one (b): its score leads by a b / 4
+        # less what the other keys reach, the other scores lose one product of sixteen
+        row = Lk - 2 if side == "c2s" and (Lk - 1) % CHUNK else Lk - 1      # (not the last key where the chunk has another)
+        q[:, 0::16], k[:, 0::16] = 0.0, 0.0
+        s = _scores(q, k)
+        lead = (s.max(-1)[0] - s[:, :, row]).max().item() + PEAK + 0.01         # (+ 0.01: a and b are rounded to float32)
+        led = slice(None) if side == "c2s" else slice(1, None, 2)
+        q[led, 0::16], k[row, 0::16] = 2.0 * lead ** 0.5, 2.0 * lead ** 0.5
+        s = _scores(q, k)
+        others = torch.cat([s[:, :, :row], s[:, :, row + 1:]], -1)
+        assert (s[:, :, row] - others.max(-1)[0])[:, led].min().item() >= PEAK
+        assert side != "c2s" or row // CHUNK == (Lk - 1) // CHUNK
+    else:
+        top = _scores(q, k).abs().max().item()
+        assert 40.0 <= top <= 60.0, top
+    mask = None
+    if side == "c2s":
+        mask = _structured_mask(Lq, Lk, seed) if walks else _random_mask(Lq, Lk, seed)
+    Z = zmat(SEED, *drop, P_DROP, 8, Lq, Lk) if drop else None
+    want = _mha_ref(q, k, v, w, mask, Z, per_head=walks)
+    ref32 = _mha_ref(q, k, v, w, mask, Z, per_head=walks, dtype=torch.float32)
+    return q, k, v, w, mask, want, ref32
+
+
+_VALUE_CASES = [(side, Lq, Lk, order, None) for side, Lq, Lk in VALUE_SHAPES for order in ORDERS]
+_VALUE_CASES += [("c2s", 225, 700, "rising", (1, 8)), ("s2c", 700, 256, "rising", (2, 6))]      # the DROP builds: (sample, site)
+
+
+@pytest.mark.parametrize("side,Lq,Lk,order,drop", _VALUE_CASES,
+                         ids=[f"{s}-{a}x{b}-{o}{'-drop' if d else ''}" for s, a, b, o, d in _VALUE_CASES])
+def test_scores_far_from_zero(side, Lq, Lk, order, drop):
+    """The online softmax and the backward's recomputation from the saved statistics on scores of +-50 (the other cases:
+    about +-5): running maxima that climb by tens along a walk (rising), that the first chunk sets with everything after it
+    underflowing (falling), a key that leads by 60 in the last chunk (peak).  The bar is check_measured's."""
+    q, k, v, w, mask, want, ref32 = _value_case(side, Lq, Lk, order, drop)
+    d = L.Dropout(SEED, P_DROP, drop[0], drop[1], 0) if drop else None
+    if side == "c2s":
+        if Lk > CAP * CHUNK:
+            _assert_walks(ops.flash_c2s_workspace_bytes, Lk, Lq, None)
+        got = _flash_c2s(q, k, v, w, mask, drop=d)
+    else:
+        if Lq > CAP * CHUNK:
+            _assert_walks(ops.flash_s2c_workspace_bytes, Lq, None, Lk)
+        got = _flash_s2c(q, k, v, w, drop=d)
+    assert all(bool(torch.isfinite(g).all()) for g in got)
+    _check_measured(f"flash {side} values {Lq}x{Lk} {order}{' dropout' if drop else ''}", got, want, ref32)
 
 
 # ---------------------------------------------------------------------------------------------------- the tape

@@ -251,6 +251,90 @@ def test_softmax_cols_and_backward(Lq, Lk):
     _softmax_check(f"cols Lq={Lq} Lk={Lk}", S, dP, None, 1, ops.softmax_cols, ops.softmax_cols_backward)
 
 
+VALUE_FAMILIES = ("pm80", "peak60")
+
+
+def _far_from_zero(S, blocked, dim, family, seed):
+    """Scores of a peaked attention instead of 4 randn.  pm80: every entry within a few units of +80 or of -80 (half of the
+    softmax underflows to exactly 0); peak60: the LAST unblocked entry along ``dim`` 60 above the largest other one (its
+    weight is 1 to float32, every other one about e^-60)."""
+    g = torch.Generator().manual_seed(seed + 7)
+    opened = torch.ones_like(S, dtype=torch.bool) if blocked is None else ~blocked
+    if family == "pm80":
+        T = (torch.rand(S.shape, generator=g) < 0.5).float() * 160.0 - 80.0 + torch.randn(S.shape, generator=g)
+    else:
+        assert family == "peak60"
+        T = torch.randn(S.shape, generator=g) * 4
+        shape = [1] * S.dim()
+        shape[dim] = S.shape[dim]
+        last = (opened * torch.arange(S.shape[dim]).view(shape)).max(dim, keepdim=True)[1]
+        top = T.masked_fill(~opened, float("-inf")).max(dim, keepdim=True)[0]
+        T.scatter_(dim, last, top + 60.0)
+        assert bool(opened.gather(dim, last).all())
+    return T if blocked is None else T.masked_fill(blocked, float("-inf"))
+
+
+@pytest.mark.parametrize("family", VALUE_FAMILIES)
+@pytest.mark.parametrize("Lk", [129, 513])
+def test_softmax_rows_and_backward_far_from_zero(Lk, family):
+    """a3d_softmax_rows / _backward, masked, on both sides of the 512 switch, on the score families of ``_far_from_zero``
+    (the other cases: 4 randn).  Bound: ``_derived_bound``, as there.
+
+    Measured on an MI355X over the 4 cases: kernel error / float32-CPU error <= 1.06 (L = 513 pm80 backward: 7.1e-09 /
+    6.7e-09); peak60 is exact to the reference's 1.7e-32."""
+    S, dP, blocked = _softmax_inputs((24, Lk), 1, True, 31 * Lk + 1)
+    S = _far_from_zero(S, blocked, 1, family, 31 * Lk + 1)
+    _softmax_check(f"rows L={Lk} {family}", S, dP, blocked, 1, ops.softmax_rows, ops.softmax_rows_backward)
+
+
+@pytest.mark.parametrize("family", VALUE_FAMILIES)
+@pytest.mark.parametrize("Lq,Lk", [(20, 255), (3, 3000)])
+def test_softmax_cols_and_backward_far_from_zero(Lq, Lk, family):
+    """a3d_softmax_cols / _backward on the score families of ``_far_from_zero``.  Bound: ``_derived_bound``.
+
+    Measured on an MI355X over the 4 cases: kernel error / float32-CPU error <= 1.02 (Lq = 20, Lk = 255 pm80: 9.2e-08 /
+    9.1e-08)."""
+    S, dP, _ = _softmax_inputs((8, Lq, Lk), 1, False, 97 * Lq + Lk)
+    S = _far_from_zero(S, None, 1, family, 97 * Lq + Lk)
+    _softmax_check(f"cols Lq={Lq} Lk={Lk} {family}", S, dP, None, 1, ops.softmax_cols, ops.softmax_cols_backward)
+
+
+@pytest.mark.parametrize("family", VALUE_FAMILIES)
+@pytest.mark.parametrize("Lq,Lk,H,dh", [(20, 1500, 8, 16), (1500, 7, 8, 16)])
+def test_attn_scores_far_from_zero(Lq, Lk, H, dh, family):
+    """a3d_attn_scores (k_tr_scores_long by key and by query) on operands whose scores reach +-80 (pm80: q scaled), or
+    whose last key scores 60 above every other key of its row (peak60: channel 0 of every head is a for the queries, b for
+    that key and 0 for the others).  The bars of test_attn_scores_with_a_mask: 1e-4 absolute, blocked entries -inf.
+
+    Measured on an MI355X: max|diff| 1.1e-05 / 9.7e-06 (pm80), 2.1e-05 / 3.2e-05 (peak60, scores up to 71)."""
+    g = torch.Generator().manual_seed(Lq * 7 + Lk)
+    q, k = torch.randn(Lq, H * dh, generator=g), torch.randn(Lk, H * dh, generator=g)
+    mask = (torch.rand(Lq, Lk, generator=g) < 0.3)
+    scale = dh ** -0.5
+
+    def scores():
+        return scale * torch.einsum("ihd,jhd->hij", q.double().view(Lq, H, dh), k.double().view(Lk, H, dh))
+    if family == "pm80":
+        q *= 80.0 / scores().abs().max().item()
+        assert 79.0 <= scores().abs().max().item() <= 81.0
+    else:
+        q[:, 0::dh], k[:, 0::dh] = 0.0, 0.0
+        ref = scores()
+        lead = (ref.max(-1)[0] - ref[:, :, -1]).max().item() + 60.01
+        q[:, 0::dh], k[-1, 0::dh] = (lead / scale) ** 0.5, (lead / scale) ** 0.5
+        ref = scores()
+        assert (ref[:, :, -1] - ref[:, :, :-1].max(-1)[0]).min().item() >= 60.0
+    S = torch.full((H, Lq, Lk), NAN, device="cuda")
+    ops.attn_scores(q.cuda(), k.cuda(), scale, mask.to(torch.uint8).cuda(), out=S, heads=H)
+    ref = scores()
+    S = S.cpu()
+    blocked = mask.expand(H, Lq, Lk)
+    err = (S[~blocked].double() - ref[~blocked]).abs().max().item()
+    print(f"attn_scores {Lq}x{Lk} {family}: max|score| {ref.abs().max().item():.0f}, max|diff| {err:.2e}")
+    assert (S[blocked] == float("-inf")).all()
+    assert err <= 1e-4
+
+
 @pytest.mark.parametrize("Lq,Lk,H,dh", [(20, 20, 8, 16), (5, 300, 8, 16), (20, 1500, 8, 16), (1500, 7, 8, 16),
                                         (1100, 9, 1, 128)])
 def test_attn_scores_with_a_mask(Lq, Lk, H, dh):
