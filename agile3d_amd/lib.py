@@ -311,6 +311,38 @@ class FeatureMatchArgs(C.Structure):
                 ("cos_min", C.c_double), ("k", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class Plane(C.Structure):
+    """a3d_plane: one plane of a3d_find_planes -- the normal (canonical sign) and offset (``normal . p = offset`` in scene
+    coordinates), the inlier count, the peak's score and flat bin, the round, the integer sums of the final inliers (count, sum,
+    mom), the integer form ``N . X = off`` and the rms distance of the inliers."""
+    _fields_ = [("normal", C.c_float * 3), ("offset", C.c_float), ("inliers", C.c_int32), ("score", C.c_int32),
+                ("round", C.c_int32), ("bin", C.c_int32), ("count", C.c_int64), ("sum", C.c_int64 * 3), ("mom", C.c_int64 * 6),
+                ("off", C.c_int64), ("N", C.c_int32 * 3), ("rms", C.c_float)]
+
+
+class PlanesSummary(C.Structure):
+    """a3d_planes_summary: planes, rounds that passed the stop test, spent rounds, admitted rows, the rows left out per reason
+    (A3D_PLANES_OUT_*), the error word (A3D_PLANES_BAD_INDEX)."""
+    _fields_ = [("n_planes", C.c_int32), ("rounds", C.c_int32), ("spent", C.c_int32), ("admitted", C.c_int32),
+                ("left_out", C.c_int32 * 5), ("err", C.c_int32), ("reserved_", C.c_int32 * 2)]
+
+
+class PlanesOut(C.Structure):
+    """a3d_planes_out: the records in the order found, then the summary."""
+    _fields_ = [("plane", Plane * 16), ("summary", PlanesSummary)]
+
+
+class FindPlanesArgs(C.Structure):
+    """a3d_find_planes_args: the normals and positions per row, the optional candidate mask, the host's direction table, the
+    optional lift (inverse_map, n_full), the outputs, the workspace, and by value the fixed-point frame and the settings."""
+    _fields_ = [("normal_dev", C.c_void_p), ("pos_dev", C.c_void_p), ("candidate_dev", C.c_void_p), ("n", C.c_int64),
+                ("table_dev", C.c_void_p), ("inverse_map_dev", C.c_void_p), ("n_full", C.c_int64), ("plane_qv_dev", C.c_void_p),
+                ("plane_full_dev", C.c_void_p), ("out_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("origin", C.c_double * 3), ("quantum", C.c_double), ("cos_min", C.c_double),
+                ("bin_width", C.c_int64), ("dist_tol", C.c_int64), ("bits", C.c_int32), ("min_voxels", C.c_int32),
+                ("max_planes", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class ObjectMoments(C.Structure):
     """a3d_object_moments: one object of a labelling -- vertices and voxels, the sums of the fixed-point coordinates (X, Y, Z)
     and of their products (XX, XY, XZ, YY, YZ, ZZ), the covered surface in thirds of area quanta, the exact fp32 box."""
@@ -413,6 +445,10 @@ A3D_TRANSFER_UNKEYABLE, A3D_TRANSFER_SORT_FAILED = 1, 2
 A3D_MATCH_CHANNELS, A3D_MATCH_QUANTUM_BITS, A3D_MATCH_FIXED_BITS = 128, 20, 40
 A3D_MATCH_MAX_EXAMPLE_ROWS, A3D_MATCH_MAX_PROTOTYPES, A3D_MATCH_CHUNK = 1 << 22, 256, 16
 A3D_MATCH_BAD_CLASS, A3D_MATCH_BAD_INDEX, A3D_MATCH_BAD_PROTOTYPE = 1, 2, 4
+A3D_PLANES_MAX, A3D_PLANES_GRID, A3D_PLANES_BINS, A3D_PLANES_SCALE_BITS = 16, 16, 1024, 20
+(A3D_PLANES_OUT_CANDIDATE, A3D_PLANES_OUT_NONFINITE, A3D_PLANES_OUT_ZERO, A3D_PLANES_OUT_FRAME,
+ A3D_PLANES_OUT_BINS) = range(5)
+A3D_PLANES_BAD_INDEX = 1
 A3D_ERR_INVALID = -1
 A3D_ERR_WORKSPACE = -5
 PROF_DENSE = 11
@@ -626,6 +662,8 @@ SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "a3d_feature_prototypes": (C.c_int, [C.POINTER(FeaturePrototypesArgs), C.c_void_p]),
     "a3d_feature_match": (C.c_int, [C.POINTER(FeatureMatchArgs), C.c_void_p]),
+    "a3d_planes_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "a3d_find_planes": (C.c_int, [C.POINTER(FindPlanesArgs), C.c_void_p]),
     "a3d_cull_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "a3d_render_shade_lit_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Camera), C.c_float,

@@ -441,6 +441,103 @@ class NormalsResult(_Result):
     __slots__ = ("normals_full", "normals_qv", "variation_qv", "count_qv", "counted", "valid", "invalid", "err", "viewpoint")
 
 
+PLANE_KINDS = ("floor", "ceiling", "wall", "horizontal", "other")
+
+
+def _unit3(values, what):
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    if v.shape != (3,) or not np.isfinite(v).all() or not np.linalg.norm(v) > 0.0:
+        raise ValueError(f"{what} must be three finite numbers, not all zero")
+    return v / np.linalg.norm(v)
+
+
+def plane_kinds(normals, offsets, up=(0.0, 0.0, 1.0), normal_deg=20.0):
+    """The ``kind`` of every plane ``normal . p = offset`` (``normals`` [k, 3] unit vectors of either sign, ``offsets`` [k]),
+    pure numpy in float64: with ``c = normal . up`` (``up`` normalised here), a plane is a ``"wall"`` when its normal lies
+    within ``normal_deg`` of perpendicular to ``up`` (``|c| <= sin(normal_deg)``); it is LEVEL when its normal lies within
+    ``normal_deg`` of ``up`` or of ``-up`` (``|c| >= cos(normal_deg)``), and its height along ``up`` is ``offset / c``.  Of the
+    level planes the lowest is the ``"floor"``, the highest the ``"ceiling"`` (of equal heights the earlier plane), the rest are
+    ``"horizontal"``; a single level plane is the ``"floor"``.  Everything else is ``"other"``.  ``normal_deg`` in 0 .. 45
+    degrees (beyond, a plane could be both).  Returns a list of k strings."""
+    n = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    c0 = np.asarray(offsets, dtype=np.float64).reshape(-1)
+    deg = np.float64(normal_deg)
+    if len(c0) != len(n) or not (np.isfinite(deg) and 0.0 <= deg <= 45.0):
+        raise ValueError("one offset per normal, and normal_deg in 0 .. 45 degrees")
+    c = n @ _unit3(up, "up")
+    kinds = ["other"] * len(n)
+    level = np.flatnonzero(np.abs(c) >= np.cos(np.radians(deg)))
+    for k in np.flatnonzero(np.abs(c) <= np.sin(np.radians(deg))):
+        kinds[k] = "wall"
+    if len(level):
+        height = c0[level] / c[level]
+        for k in level:
+            kinds[k] = "horizontal"
+        lowest, highest = level[int(np.argmin(height))], level[int(np.argmax(height))]
+        if len(level) > 1 and highest != lowest:
+            kinds[highest] = "ceiling"
+        kinds[lowest] = "floor"
+    return kinds
+
+
+def upright_rotation(normal, up=(0.0, 0.0, 1.0)):
+    """The float64 3 x 3 rotation about ``normal x up`` that takes the direction of ``normal`` (either sign: the one nearer to
+    ``up``) to ``up`` -- Rodrigues' formula; the identity when they agree already."""
+    u, n = _unit3(up, "up"), _unit3(normal, "normal")
+    if n @ u < 0.0:
+        n = -n
+    axis, c = np.cross(n, u), float(n @ u)
+    K = np.array([[0.0, -axis[2], axis[1]], [axis[2], 0.0, -axis[0]], [-axis[1], axis[0], 0.0]])
+    return np.eye(3) + K + K @ K / (1.0 + c)
+
+
+class PlanesResult(_Result):
+    """What ``planes()`` returns.  Device tensors: ``plane_qv`` int32 [n_voxels] (the id of the voxel's plane, -1: none;
+    ``grow(..., within=r.plane_qv)`` stays on one plane) and ``plane_full`` int32 [n_full] (the same lifted to the vertices).
+    Host: ``records``, a numpy structured array (``view.PLANE``: normal with the canonical sign, offset -- ``normal . p =
+    offset`` in scene coordinates --, inliers, score, round, bin, the integer sums, N, off, rms) in the order found;
+    ``n_planes``; ``kinds``, one of ``PLANE_KINDS`` per plane (``plane_kinds``); ``floor`` and ``ceiling`` (plane ids or
+    ``None``) and ``walls`` (a list of ids); ``rounds``, ``spent``, ``admitted`` and ``left_out`` (a dict: the rows left out
+    per reason) from the call's summary; ``up`` (float64 [3], a unit vector) and ``normal_deg``, ``dist_tol``, ``min_voxels``,
+    ``max_planes``, ``within`` as used."""
+
+    __slots__ = ("plane_qv", "plane_full", "records", "n_planes", "kinds", "floor", "ceiling", "walls", "rounds", "spent",
+                 "admitted", "left_out", "up", "normal_deg", "dist_tol", "min_voxels", "max_planes", "within")
+
+    def _plane(self, k):
+        if isinstance(k, bool) or k is None or int(k) != k or not 0 <= k < self.n_planes:
+            raise ValueError(f"plane {k!r}: the result holds the planes 0 .. {self.n_planes - 1}")
+        return int(k)
+
+    def selection(self, k):
+        """uint8 [n_full] on the device: 1 = the vertex lies on plane ``k`` (``paint``, ``erase``, ``grow`` and ``shrink`` take
+        it as it is)."""
+        return (self.plane_full == self._plane(k)).to(torch.uint8)
+
+    def section(self, k, keep="above", margin=0.0, cull="none"):
+        """The ``Section`` of one plane along plane ``k``.  ``keep="above"`` keeps the side ``up`` points to -- of a wall, whose
+        normal is about perpendicular to ``up``, the side its recorded normal points to --, ``"below"`` the other.  ``margin``
+        (world units, finite) moves the cut INTO the kept side, so that the plane's own voxels go with what is cut away:
+        ``set_section(r.section(r.ceiling, "below", margin=0.05))`` cuts the ceiling off."""
+        if keep not in ("above", "below"):
+            raise ValueError('keep must be "above" or "below"')
+        m = float(margin)
+        if not np.isfinite(m):
+            raise ValueError("margin must be finite")
+        rec = self.records[self._plane(k)]
+        n, c = rec["normal"].astype(np.float64), float(rec["offset"])
+        if n @ self.up < 0.0 and self.kinds[int(k)] != "wall":
+            n, c = -n, -c
+        if keep == "below":
+            n, c = -n, -c
+        return Section([(n, c + m)], cull)
+
+    def upright(self):
+        """The float64 3 x 3 rotation that takes the floor's normal to ``up`` (``upright_rotation``): ``p @ R.T`` turns a tilted
+        scan upright.  The identity when there is no floor."""
+        return np.eye(3) if self.floor is None else upright_rotation(self.records["normal"][self.floor], self.up)
+
+
 _MAX_CULLED = 4                                 # culled copies of a cloud kept at a time (one per eye and mode)
 
 
@@ -2344,6 +2441,71 @@ class InteractiveSession:
         row = self.inverse_map[vertex]
         both = torch.cat([normals.normals_full[vertex], normals.variation_qv[row].reshape(1)]).cpu().numpy()
         return both[:3].copy(), float(both[3])
+
+    # ------------------------------------------------------------------ the planes a room is made of
+    def planes(self, normal_deg=20.0, dist_tol=None, min_voxels=200, max_planes=16, within="all", normals=None, up=(0, 0, 1)):
+        """The few global PLANES the scan is made of -- floor, ceiling, walls, table tops --, their equations and the voxels on
+        each (``a3d_find_planes``; the rule is stated in include/agile3d_hip.h).  Every voxel with a normal votes, in integers,
+        for one cell of a Hough array over (direction, offset); round by round the strongest cell seeds a plane, which is
+        fitted from exact integer sums, refitted twice from its inliers -- the voxels within ``dist_tol`` (world units;
+        ``None``: 1.5 voxels) whose normal lies within ``normal_deg`` degrees of the plane's -- and recorded when it holds at
+        least ``min_voxels`` voxels; at most ``max_planes`` (1 .. 16).  Unlike ``patches()``, which chains neighbours, a wall
+        behind a shelf is ONE plane, and every plane has an equation.  The offset bins are one voxel wide.
+        ``normals``: a ``NormalsResult``; ``None`` takes the one ``estimate_normals()`` left with a cloud -- a mesh keeps none,
+        so there it must be passed; with neither, ``ValueError``.  ``within``: ``"all"``, ``"label"`` (background voxels
+        only), an int32 tensor of keys over the voxels (keys >= 0 take part) or a uint8 / bool mask.  ``up`` names the
+        planes (``plane_kinds``) and plays no part in finding them.  Returns a ``PlanesResult``: ``selection(k)`` for
+        ``paint`` / ``grow``, ``section(k, ...)`` for ``set_section``, ``upright()`` for a tilted scan; ``grow(...,
+        within=r.plane_qv)`` stays on a plane, and ``pieces(labels=...)`` over ``plane_qv`` gives a plane's connected parts.
+        LIMITS: a direction cell is about 7 degrees wide; a plane whose normal lies on a cell border splits its votes and is
+        found later, not lost; a plane more than 512 voxels from the centre of the scene's box is left out; no curved
+        primitives.  The defaults (20 degrees, 1.5 voxels, 200 voxels) are this project's choice and are NOT tuned on real
+        scans.  One library call and ONE host round trip; no session state changes."""
+        self._need_scene()
+        n = self._labels_qv.numel()
+        up64 = _unit3(up, "up")
+        res = self._normals_last if normals is None and self.faces is None else normals
+        if res is None:
+            raise ValueError("no normals: call estimate_normals() first (on a mesh it keeps none with the scene: pass its result "
+                             "as normals=)")
+        if not isinstance(res, NormalsResult) or not torch.is_tensor(res.normals_qv) or res.normals_qv.device != self.device \
+                or tuple(res.normals_qv.shape) != (n, 3):
+            raise ValueError("normals must be a NormalsResult of this scene (estimate_normals())")
+        tol = 1.5 * self.voxel_size if dist_tol is None else dist_tol
+        kinds_deg = min(float(normal_deg), 45.0) if isinstance(normal_deg, (int, float)) else normal_deg
+        keys = self._grow_keys(within)
+        candidate = None
+        if keys is not None:
+            candidate = ((keys == 0) if isinstance(within, str) else (keys >= 0)).to(torch.uint8)
+        origin, quantum, bits = self._fixed_point_frame()
+        plane_qv, plane_full, out, _ = V.find_planes(
+            res.normals_qv.contiguous(), self.raw_coords_qv, origin, quantum, bits, offset_bin=self.voxel_size, normal_deg=normal_deg,
+            dist_tol=tol, min_voxels=min_voxels, max_planes=max_planes, candidate=candidate, inverse_map=self.inverse_map)
+        records, s = V.read_planes(out.cpu().numpy())                     # the one host round trip
+        if s["err"] & V.PLANES_BAD_INDEX:
+            raise RuntimeError("a3d_find_planes: inverse_map out of range")
+        kinds = plane_kinds(records["normal"], records["offset"], up64, kinds_deg)
+        first = lambda kind: kinds.index(kind) if kind in kinds else None
+        return PlanesResult(plane_qv=plane_qv, plane_full=plane_full, records=records, n_planes=s["n_planes"], kinds=kinds,
+                            floor=first("floor"), ceiling=first("ceiling"), walls=[k for k, x in enumerate(kinds) if x == "wall"],
+                            rounds=s["rounds"], spent=s["spent"], admitted=s["admitted"], left_out=s["left_out"], up=up64,
+                            normal_deg=float(normal_deg), dist_tol=float(tol), min_voxels=int(min_voxels),
+                            max_planes=int(max_planes), within=within if isinstance(within, str) else "keys")
+
+    def plane_at(self, result, u, v, planes=None):
+        """The id of the plane that pixel ``(u, v)`` (column, row) of ``result`` shows, or ``None`` where the pixel shows nothing
+        or its vertex lies on no plane -- resolved as ``piece_at`` resolves a vertex: the pixel's vertex on a cloud, the
+        heaviest corner of its face on a mesh.  ``planes``: a ``PlanesResult`` of this scene (default: ``planes()``, computed
+        here)."""
+        self._need_scene()
+        planes = self.planes() if planes is None else planes
+        if not isinstance(planes, PlanesResult) or tuple(planes.plane_full.shape) != (self.coords_full.shape[0],):
+            raise ValueError("the planes belong to another scene")
+        vertex = self._vertex_at(result, u, v)
+        if vertex < 0:
+            return None
+        k = int(planes.plane_full[vertex].cpu())
+        return k if k >= 0 else None
 
     # ------------------------------------------------------------------ more objects like this one
     def _example_classes(self, obj, selection):

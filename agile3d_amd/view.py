@@ -1468,3 +1468,131 @@ def feature_match(feats, protos, proto_class, cos_min, candidate=None, inverse_m
     a.summary_dev = summary.data_ptr()
     L.check(L.load().a3d_feature_match(C.byref(a), L.stream(dev)), "a3d_feature_match")
     return match_qv, best_qv, score_qv, match_full, score_full, summary
+
+
+# ---- the planes of a scan: Hough votes in integers, fits from integer sums ------------------------------------------------------
+PLANE = np.dtype([("normal", "<f4", (3,)), ("offset", "<f4"), ("inliers", "<i4"), ("score", "<i4"), ("round", "<i4"), ("bin", "<i4"),
+                  ("count", "<i8"), ("sum", "<i8", (3,)), ("mom", "<i8", (6,)), ("off", "<i8"), ("N", "<i4", (3,)), ("rms", "<f4")])
+PLANES_SUMMARY = np.dtype([("n_planes", "<i4"), ("rounds", "<i4"), ("spent", "<i4"), ("admitted", "<i4"), ("left_out", "<i4", (5,)),
+                           ("err", "<i4"), ("reserved_", "<i4", (2,))])
+PLANES_MAX, PLANES_GRID, PLANES_BINS = L.A3D_PLANES_MAX, L.A3D_PLANES_GRID, L.A3D_PLANES_BINS
+PLANES_SCALE = 1 << L.A3D_PLANES_SCALE_BITS     # table entries, N and the units of bin_width / dist_tol: 2^-20 (quanta)
+PLANES_MAX_UNITS = 1 << 44                      # the largest bin_width and dist_tol, in those units
+PLANES_OUT_BYTES = PLANES_MAX * PLANE.itemsize + PLANES_SUMMARY.itemsize
+PLANES_BAD_INDEX = L.A3D_PLANES_BAD_INDEX       # the bit of the summary's error word
+PLANES_LEFT_OUT = ("candidate", "nonfinite", "zero_normal", "frame", "bins")      # A3D_PLANES_OUT_*, in order
+assert C.sizeof(L.Plane) == PLANE.itemsize == 136 and C.sizeof(L.PlanesSummary) == PLANES_SUMMARY.itemsize == 48
+assert C.sizeof(L.PlanesOut) == PLANES_OUT_BYTES == 2224 and C.sizeof(L.FindPlanesArgs) == 168
+
+
+def read_planes(host):
+    """``(records, summary)`` of the host copy of an ``a3d_planes_out`` (uint8 [2224], or anything of those bytes): the
+    ``PLANE`` records of the planes found, in the order found (a copy), and the summary as a dict -- ``n_planes``, ``rounds``,
+    ``spent``, ``admitted``, ``left_out`` (a dict by ``PLANES_LEFT_OUT``), ``err`` (bit ``PLANES_BAD_INDEX``)."""
+    raw = np.ascontiguousarray(host).view(np.uint8).reshape(-1)[:PLANES_OUT_BYTES]
+    rec = raw[PLANES_MAX * PLANE.itemsize:].view(PLANES_SUMMARY)[0]
+    s = {k: int(rec[k]) for k in ("n_planes", "rounds", "spent", "admitted", "err")}
+    s["left_out"] = {name: int(v) for name, v in zip(PLANES_LEFT_OUT, rec["left_out"])}
+    return raw[:PLANES_MAX * PLANE.itemsize].view(PLANE)[:s["n_planes"]].copy(), s
+
+
+def planes_workspace(n, device):
+    """The scratch of ``find_planes`` for n rows (``a3d_planes_workspace_bytes``)."""
+    return _scratch(L.load().a3d_planes_workspace_bytes(n), device, f"no planes workspace for n={n}")
+
+
+def direction_table():
+    """The HOST's table of ``a3d_find_planes``, int32 [3 G G, 3] (numpy, G = 16): for cell ``(a G + iu) G + iv`` the unit vector
+    along ``e_a + u e_b + v e_c`` -- b, c = (a + 1, a + 2) mod 3, u = (2 iu + 1 - G) / G, v likewise -- computed in float64 and
+    rounded, ``llrint(component * 2^20)``.  The kernels read it and never normalise."""
+    G = PLANES_GRID
+    centre = (2.0 * np.arange(G) + 1.0 - G) / G
+    table = np.zeros((3, G, G, 3), np.float64)
+    for a in range(3):
+        table[a, :, :, a] = 1.0
+        table[a, :, :, (a + 1) % 3] = centre[:, None]
+        table[a, :, :, (a + 2) % 3] = centre[None, :]
+    table /= np.sqrt((table * table).sum(-1, keepdims=True))
+    return np.rint(table * float(PLANES_SCALE)).astype(np.int32).reshape(3 * G * G, 3)
+
+
+def planes_settings(quantum, offset_bin, normal_deg, dist_tol, min_voxels, max_planes):
+    """``(bin_width, dist_tol_units, cos_min, min_voxels, max_planes)`` as ``a3d_find_planes`` takes them, pure Python:
+    ``bin_width = llrint(offset_bin / quantum * 2^20)`` and ``dist_tol_units`` likewise (world units -> 2^-20 quanta, float64,
+    rounded once each), ``cos_min = cos(radians(normal_deg))`` in float64, rounded once.  ``ValueError`` for a bin of less
+    than one unit or more than 2^44, a tolerance that is negative or more than 2^44, an angle outside 0 .. 90 degrees,
+    ``min_voxels < 1`` or ``max_planes`` outside 1 .. 16."""
+    q = _power_of_two("quantum", quantum)
+    units = []
+    for name, value, lo in (("offset_bin", offset_bin, 1), ("dist_tol", dist_tol, 0)):
+        try:
+            x = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a finite number") from None
+        u = np.rint(np.float64(x) / np.float64(q) * np.float64(PLANES_SCALE)) if np.isfinite(x) else np.nan
+        if not lo <= u <= PLANES_MAX_UNITS:              # (a NaN fails both)
+            raise ValueError(f"{name}={value!r}: {lo} .. 2^44 units of quantum * 2^-20 are taken")
+        units.append(int(u))
+    try:
+        deg = float(normal_deg)
+    except (TypeError, ValueError):
+        raise ValueError("normal_deg must be an angle in 0 .. 90 degrees") from None
+    if not 0.0 <= deg <= 90.0:
+        raise ValueError("normal_deg must be an angle in 0 .. 90 degrees")
+    cos_min = min(max(float(np.cos(np.radians(np.float64(deg)))), 0.0), 1.0)
+    return (units[0], units[1], cos_min, _int_in("min_voxels", min_voxels, 1, (1 << 31) - 1),
+            _int_in("max_planes", max_planes, 1, PLANES_MAX))
+
+
+def find_planes(normals, positions, origin, quantum, bits=L.A3D_MEASURE_MAX_BITS, offset_bin=None, normal_deg=20.0, dist_tol=None,
+                min_voxels=200, max_planes=PLANES_MAX, candidate=None, inverse_map=None, table=None, plane_qv=None,
+                plane_full=None, out=None, workspace=None):
+    """``a3d_find_planes``: the global planes of the rows ``normals`` fp32 [n, 3] (zeros: no normal) at ``positions`` fp32
+    [n, 3], by the rule of include/agile3d_hip.h.  ``origin``, ``quantum``, ``bits``: the fixed-point frame of
+    ``measure_objects``.  ``offset_bin`` (the width of an offset bin) and ``dist_tol`` (the inlier distance) in world units --
+    both must be given: the session passes the voxel size and 1.5 voxels --, ``normal_deg`` in degrees, ``min_voxels`` (the
+    smallest recorded plane), ``max_planes`` 1 .. 16: see ``planes_settings``.  ``candidate`` uint8 [n]: 0 = the row takes no
+    part.  ``inverse_map`` int64 [n_full]: also lift the ids to the vertices (``plane_full=False``: not wanted, as without
+    a map).  ``table``: ``direction_table()`` on the device as int32 [768, 3] (``None``: uploaded here).  Outputs: the caller's
+    tensors or new ones.  Returns ``(plane_qv int32 [n], plane_full int32 [n_full] or None, out uint8 [2224], workspace)`` on the
+    device; ``read_planes`` decodes the host copy of ``out``."""
+    dev = _device("normals", normals)
+    a = L.FindPlanesArgs()
+    a.normal_dev = _ptr("normals", normals, F32, (None, 3), dev)
+    a.n = n = normals.shape[0]
+    a.pos_dev = _ptr("positions", positions, F32, (n, 3), dev)
+    a.candidate_dev = _ptr("candidate", candidate, U8, (n,), dev, optional=True)
+    a.bits = _int_in("bits", bits, 0, L.A3D_MEASURE_MAX_BITS)
+    if n >= 1 << 31 or n << (2 * a.bits) > 1 << 62:
+        raise ValueError(f"{n} rows at bits={a.bits}: the sums could overflow (n * 2^(2 bits) <= 2^62)")
+    a.origin[:] = _three_finite("origin", origin)
+    a.quantum = _power_of_two("quantum", quantum)
+    if offset_bin is None or dist_tol is None:
+        raise ValueError("offset_bin and dist_tol must be given (world units)")
+    a.bin_width, a.dist_tol, a.cos_min, a.min_voxels, a.max_planes = planes_settings(a.quantum, offset_bin, normal_deg, dist_tol,
+                                                                                      min_voxels, max_planes)
+    if table is None:
+        table = torch.from_numpy(direction_table()).to(dev)
+    a.table_dev = _ptr("table", table, I32, (3 * PLANES_GRID * PLANES_GRID, 3), dev)
+    plane_qv = _out("plane_qv", plane_qv, I32, (n,), dev)
+    a.plane_qv_dev = plane_qv.data_ptr() if n else None
+    if inverse_map is not None and plane_full is not False:
+        _ptr("inverse_map", inverse_map, I64, (None,), dev)
+        a.n_full = inverse_map.shape[0]
+        if a.n_full >= 1 << 31:
+            raise ValueError(f"inverse_map: {a.n_full} rows, a call takes fewer than 2^31")
+        plane_full = _out("plane_full", plane_full, I32, (a.n_full,), dev)
+        if a.n_full:
+            a.inverse_map_dev, a.plane_full_dev = inverse_map.data_ptr(), plane_full.data_ptr()
+    elif plane_full is not None and plane_full is not False:
+        raise ValueError("plane_full belongs to the lift: inverse_map is missing")
+    else:
+        plane_full = None
+    out = _summary(out, PLANES_OUT_BYTES, dev)
+    a.out_dev = out.data_ptr()
+    if workspace is None:
+        workspace = planes_workspace(n, dev)
+    _attach(a, workspace, dev, L.load().a3d_planes_workspace_bytes(n),
+            "workspace too small or not 256-byte aligned (planes_workspace(n, device))")
+    L.check(L.load().a3d_find_planes(C.byref(a), L.stream(dev)), "a3d_find_planes")
+    return plane_qv, plane_full, out, workspace

@@ -1574,6 +1574,136 @@ typedef struct a3d_feature_match_args {
 int    a3d_feature_prototypes(const a3d_feature_prototypes_args* args, void* stream);
 int    a3d_feature_match(const a3d_feature_match_args* args, void* stream);
 
+/* THE PLANES OF A SCAN: the few global planes a room is made of (floor, ceiling, walls, table tops), their equations, and
+ * which voxels lie on each (csrc/session_planes.hip).  The reference has no counterpart; THE RULE is this library's, restated in
+ * tests/planes_rule.py.  Hough votes are INTEGER counts (no order, no rounding); a plane is fitted from INTEGER sums by the
+ * solve of a3d_estimate_normals; every test a row passes or fails is exact.  Two calls give the same bytes in every output.
+ *
+ * a3d_find_planes.  Per row i of n: normal_dev fp32 [n][3] (zeros = no normal; the caller's word that it is a unit vector),
+ * pos_dev fp32 [n][3], optionally candidate_dev uint8 [n] (0 = the row takes no part).  origin, quantum, bits: the fixed-point
+ * frame of a3d_measure_objects (n 2^(2 bits) <= 2^62, n < 2^31).  table_dev int32 [3 G G][3], G = A3D_PLANES_GRID = 16: the
+ * HOST's table of cell-centre directions (below); the kernels never normalise.  By value: bin_width w >= 1 and dist_tol >= 0,
+ * int64 in units of 2^-20 quanta (the units of C . X); cos_min, a double in [0, 1]; min_voxels >= 1; max_planes in
+ * 1..A3D_PLANES_MAX.
+ *   ADMISSION, the first failing test names the reason the row is left out for (summary.left_out[reason]):
+ *     A3D_PLANES_OUT_CANDIDATE  candidate[i] == 0
+ *     A3D_PLANES_OUT_NONFINITE  a component of the normal or of the position is a NaN or an infinity
+ *     A3D_PLANES_OUT_ZERO       the normal is (+-0, +-0, +-0)
+ *     A3D_PLANES_OUT_FRAME      X_a = llrint(((double)p_a - origin[a]) / quantum) has |X_a| > 2^bits on some axis
+ *     A3D_PLANES_OUT_BINS       the offset bin k (below) lies outside 0..D-1
+ *   DIRECTION CELL.  a = the axis of the component of largest magnitude (of equals the lowest axis); if n_a < 0 the normal is
+ *   negated (its canonical sign); b = (a + 1) mod 3, c = (a + 2) mod 3.  With t_j = (j - G/2) / (G/2), j = 1..G-1 (dyadic):
+ *     iu = the number of j with (double)n_b >= t_j * (double)n_a;   iv likewise with n_c
+ *   (each product is exact in double, so the comparison is exact; no division).  cell = (a G + iu) G + iv.
+ *   THE TABLE, made on the host (view.direction_table): for cell (a, iu, iv) the unit vector along e_a + u e_b + v e_c with
+ *   u = (2 iu + 1 - G) / G, v likewise, in float64; table[cell][axis] = llrint(component * 2^20).
+ *   OFFSET BIN.  d = table[cell] . X, an exact int64;  k = floor(d / w) + D/2, D = A3D_PLANES_BINS = 1024 (floor division of
+ *   integers).  bin = cell D + k.  VOTES: H[bin] (int32, 3 G G D entries) counts the admitted rows of the bin.
+ *   ROUNDS, at most 2 max_planes.  The REMAINING rows are the admitted rows no earlier round removed.
+ *   1. PEAK.  score(bin) = H[bin - 1] + H[bin] + H[bin + 1], the neighbours taken inside the bin's direction cell only (0
+ *      beyond k = 0 and k = D-1).  The peak is the bin of the highest score, of equals the lowest bin.  If its score <
+ *      max(3, min_voxels / 4) (integer division) the call ENDS.  Votes are smoothed over OFFSET only: the offsets of
+ *      neighbouring direction cells are taken along different directions, and smoothing across them lets rows far away leak
+ *      into the seeds.
+ *   2. SEEDS: the remaining rows of the peak's cell with |k - k_peak| <= 1 (their number is the score).  cnt, sum[3], mom[6] =
+ *      the integer sums of 1, X, (XX, XY, XZ, YY, YZ, ZZ) over them.  FIT (below).
+ *   3. Twice: the INLIERS of the fit are found, their integer sums taken, and the plane is FITTED again from those.  Then the
+ *      FINAL inlier pass with the last fit: its count is the plane's inlier count, its sums go into the record.
+ *      FIT: stage B of a3d_estimate_normals on (cnt, sum, mom), no viewpoint: normal fp32 [3] with the canonical sign, or
+ *      invalid (cnt < 3, or a line).  N_a = llrint((double)normal_a * 2^20).  off, ONE int64, in integers only: with R_a =
+ *      floor(sum_a / cnt) and s_a = sum_a - cnt R_a (stage B's own recentring),
+ *          off = (N_0 R_0 + N_1 R_1 + N_2 R_2) + floor((N_0 s_0 + N_1 s_1 + N_2 s_2) / cnt)
+ *      -- N . (the mean of the rows), rounded down to a whole unit of 2^-20 quanta.  No double takes part.
+ *      INLIER: a remaining row with  |((double)normal_0 v_0 + (double)normal_1 v_1) + (double)normal_2 v_2| >= cos_min  (v the
+ *      row's normal; three exact products, one accumulator, axes ascending) and  |N . X - off| <= dist_tol  (exact int64).
+ *   4. RECORD.  If the final inlier count >= min_voxels the plane is recorded with the next id: plane_qv = id on its inliers,
+ *      their votes are subtracted from H and they leave the remaining rows.
+ *   5. SPENT.  Otherwise -- or when any fit of the round was invalid -- the round is spent: the SEEDS leave H and the remaining
+ *      rows, no plane is recorded, and the next round goes on (a column or a sphere does not stop the search).
+ *   The call ends as well once max_planes planes are recorded.
+ *   THE RECORD.  normal (the last fit), N, off, inliers, score (the peak's), bin (the peak's), round (0-based), cnt / sum /
+ *   mom of the final inliers, and
+ *     offset = (float)((((double)normal_0 origin_0 + (double)normal_1 origin_1) + (double)normal_2 origin_2)
+ *                      + (double)off * (quantum * 2^-20))          -- normal . p = offset in scene coordinates (a3d_section's form)
+ *     rms    = (float)(sqrt(E / (double)cnt) * (quantum * 2^-20)),  E = (double)hi * 2^64 + (double)lo of the EXACT 128-bit
+ *              integer  sum over the final inliers of (N . X - off)^2 = N^T mom N - 2 off (N . sum) + cnt off^2 = hi 2^64 + lo
+ *   every double operation rounded on its own, in the order written.
+ *   OUTPUTS.  plane_qv_dev int32 [n]: the id, -1 for no plane (every entry is written).  With inverse_map_dev int64 [n_full]:
+ *   plane_full_dev int32 [n_full], plane_full[j] = plane_qv[inverse_map[j]]; an index outside 0..n-1 sets A3D_PLANES_BAD_INDEX
+ *   and is not followed (the entry is not written).  out_dev (8-byte aligned, cleared by the call): A3D_PLANES_MAX records in
+ *   the order found, then the summary: planes, rounds (that passed the stop test) and spent rounds, admitted rows, the rows left
+ *   out per reason, the error word.  One copy to the host reads both.
+ *   The workspace: a3d_planes_workspace_bytes(n) bytes, 256-byte aligned.  The library allocates nothing and does not
+ *   synchronise; stages are launches -- no grid barrier, no spin-wait; a flag on the device turns the launches of the rounds
+ *   after the end into no-ops, so nothing is read back inside the call.
+ *   A3D_ERR_INVALID with nothing launched and nothing written: no arguments, n < 0 or beyond the bound, bits outside 0..20, a
+ *   quantum that is not a positive power of two, an origin that is not finite, bin_width < 1, dist_tol < 0, either beyond 2^44,
+ *   cos_min outside [0, 1], min_voxels < 1, max_planes outside 1..16, a missing normal_dev, pos_dev or plane_qv_dev (n > 0),
+ *   table_dev or out_dev, out_dev misaligned, n_full < 0 or >= 2^31, plane_full_dev / n_full without inverse_map_dev or
+ *   inverse_map_dev without plane_full_dev (n_full > 0), a workspace that is missing, too small or misaligned.
+ *   LIMITS: a direction cell is about 7 degrees wide and an offset bin one bin_width deep: a plane whose normal lies on a cell
+ *   border splits its votes and is found later, not lost; a plane more than D/2 bins from the origin of the frame along its
+ *   normal is left out; no curved primitives. */
+#define A3D_PLANES_MAX            16
+#define A3D_PLANES_GRID           16
+#define A3D_PLANES_BINS           1024
+#define A3D_PLANES_SCALE_BITS     20
+#define A3D_PLANES_OUT_CANDIDATE  0
+#define A3D_PLANES_OUT_NONFINITE  1
+#define A3D_PLANES_OUT_ZERO       2
+#define A3D_PLANES_OUT_FRAME      3
+#define A3D_PLANES_OUT_BINS       4
+#define A3D_PLANES_BAD_INDEX      1
+typedef struct a3d_plane {
+  float   normal[3];                /* the last fit, canonical sign */
+  float   offset;                   /* normal . p = offset in scene coordinates */
+  int32_t inliers;
+  int32_t score;                    /* the peak's */
+  int32_t round;
+  int32_t bin;                      /* the peak's flat bin index */
+  int64_t count;                    /* the final inliers: 1, X, (XX, XY, XZ, YY, YZ, ZZ) */
+  int64_t sum[3];
+  int64_t mom[6];
+  int64_t off;                      /* N . X = off */
+  int32_t N[3];
+  float   rms;
+} a3d_plane;                        /* 136 bytes */
+typedef struct a3d_planes_summary {
+  int32_t n_planes, rounds, spent, admitted;
+  int32_t left_out[5];              /* A3D_PLANES_OUT_* */
+  int32_t err;                      /* A3D_PLANES_BAD_INDEX */
+  int32_t reserved_[2];
+} a3d_planes_summary;               /* 48 bytes */
+typedef struct a3d_planes_out {
+  a3d_plane plane[A3D_PLANES_MAX];
+  a3d_planes_summary summary;
+} a3d_planes_out;                   /* 2224 bytes */
+typedef struct a3d_find_planes_args {
+  const float*   normal_dev;        /* [n][3] */
+  const float*   pos_dev;           /* [n][3] */
+  const uint8_t* candidate_dev;     /* [n] or NULL */
+  int64_t        n;
+  const int32_t* table_dev;         /* [3 G G][3] */
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL */
+  int64_t        n_full;
+  int32_t*       plane_qv_dev;      /* out [n] */
+  int32_t*       plane_full_dev;    /* out [n_full] or NULL */
+  a3d_planes_out* out_dev;
+  void*          workspace_dev;
+  size_t         workspace_bytes;
+  double         origin[3];
+  double         quantum;
+  double         cos_min;
+  int64_t        bin_width;
+  int64_t        dist_tol;
+  int32_t        bits;
+  int32_t        min_voxels;
+  int32_t        max_planes;
+  int32_t        reserved_;
+} a3d_find_planes_args;            /* 168 bytes */
+size_t a3d_planes_workspace_bytes(int64_t n);
+int    a3d_find_planes(const a3d_find_planes_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The session's view: id, depth and colour images of the scan for a pinhole camera (csrc/session.hip).
  * THE RULE: the image is, pixel by pixel, what the picks above return for the ray through that pixel's centre -- on a
