@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagile3d_hip.so")
-SOURCES = ["scene.hip", "radix.hip", "spconv.hip", "decoder.hip", "clicks.hip", "quantize.hip", "criterion.hip", "wgrad.hip", "bnorm.hip", "optim.hip", "attn_train.hip", "attn_flash.hip", "dropout.hip", "session.hip", "session_edit.hip", "session_guide.hip", "session_pieces.hip", "session_measure.hip", "session_region.hip", "session_grow.hip", "session_normals.hip", "session_transfer.hip", "session_match.hip", "session_planes.hip"]
+SOURCES = ["scene.hip", "radix.hip", "spconv.hip", "decoder.hip", "clicks.hip", "quantize.hip", "criterion.hip", "wgrad.hip", "bnorm.hip", "optim.hip", "attn_train.hip", "attn_flash.hip", "dropout.hip", "session.hip", "session_edit.hip", "session_guide.hip", "session_pieces.hip", "session_measure.hip", "session_region.hip", "session_grow.hip", "session_normals.hip", "session_transfer.hip", "session_match.hip", "session_planes.hip", "session_orient.hip"]
 
 
 STAMP = LIB + ".stamp"

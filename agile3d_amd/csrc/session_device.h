@@ -1,10 +1,12 @@
 // The small helpers every session_*.hip shares, one definition each: wave and workgroup reductions, the 64-bit counter add,
 // the fixed-point rule of a3d_measure_objects and a3d_estimate_normals, the finite test, and on the host the grid size, the
-// workspace carver and the check of a scene's level 0.  A new session file includes this header; it does not copy from it.
+// workspace carver, the offsets of a connectivity and the check of a scene's level 0.  A new session file includes this
+// header; it does not copy from it.
 #pragma once
 #include "common.h"
 
 #include <cmath>
+#include <cstdlib>
 
 namespace a3d {
 
@@ -92,6 +94,15 @@ struct Carver {
     return p;
   }
 };
+// the offsets a connectivity admits, bit k = offset (k % 3 - 1, (k / 3) % 3 - 1, k / 9 - 1)
+inline unsigned offset_mask(int connectivity) {
+  unsigned m = 0;
+  for (int k = 0; k < 27; ++k) {
+    const int l1 = std::abs(k % 3 - 1) + std::abs((k / 3) % 3 - 1) + std::abs(k / 9 - 1);
+    if (l1 >= 1 && (connectivity == 26 || (connectivity == 18 && l1 <= 2) || (connectivity == 6 && l1 == 1))) m |= 1u << k;
+  }
+  return m;
+}
 // Level 0 of the scene can be walked (the 27-neighbour table, the callers' rows) and has n rows.
 inline bool scene_walkable(const a3d_scene* s, long long n) {
   return s && s->lv[0].nbr27 && s->orig_row && s->n0 == s->lv[0].n && n == s->lv[0].n;

@@ -92,16 +92,6 @@ static PiecesWs carve_pieces(void* base, long long n, long long capacity, int n_
   return w;
 }
 
-// the offsets a connectivity admits, bit k = offset (k % 3 - 1, (k / 3) % 3 - 1, k / 9 - 1)
-static unsigned offset_mask(int connectivity) {
-  unsigned m = 0;
-  for (int k = 0; k < 27; ++k) {
-    const int l1 = abs(k % 3 - 1) + abs((k / 3) % 3 - 1) + abs(k / 9 - 1);
-    if (l1 >= 1 && (connectivity == 26 || (connectivity == 18 && l1 <= 2) || (connectivity == 6 && l1 == 1))) m |= 1u << k;
-  }
-  return m;
-}
-
 struct PiecesTab {
   const int32_t* nbr;        // [27][npad]
   const int32_t* orig;       // [n]

@@ -275,6 +275,27 @@ class EstimateNormalsArgs(C.Structure):
                 ("has_viewpoint", C.c_int32)]
 
 
+class OrientSummary(C.Structure):
+    """a3d_orient_summary: admitted rows, seeds, reached and unreached rows, flipped rows, conflicting edges, the largest dist,
+    whether the last sweep was quiet, the error word (A3D_ORIENT_BAD_INDEX, A3D_ORIENT_BAD_COMPONENT)."""
+    _fields_ = [("admitted", C.c_int64), ("seeds", C.c_int64), ("reached", C.c_int64), ("unreached", C.c_int64),
+                ("flipped", C.c_int64), ("conflicts", C.c_int64), ("max_dist", C.c_int32), ("converged", C.c_int32),
+                ("err", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class OrientNormalsArgs(C.Structure):
+    """a3d_orient_normals_args: the scene, the normals per voxel, the seeds of either mode (marks and flips; components and
+    positions), the lift (inverse_map, n_full), the optional outputs, the summary, the workspace, and by value the viewpoint,
+    the mode, the connectivity, the number of sweeps and whether the call resumes."""
+    _fields_ = [("scene", C.c_void_p), ("n", C.c_int64), ("normal_qv_dev", C.c_void_p), ("seed_qv_dev", C.c_void_p),
+                ("seed_flip_dev", C.c_void_p), ("component_qv_dev", C.c_void_p), ("position_qv_dev", C.c_void_p),
+                ("inverse_map_dev", C.c_void_p), ("n_full", C.c_int64), ("normal_out_qv_dev", C.c_void_p),
+                ("flipped_qv_dev", C.c_void_p), ("dist_qv_dev", C.c_void_p), ("owner_qv_dev", C.c_void_p),
+                ("normal_full_dev", C.c_void_p), ("summary_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("viewpoint", C.c_double * 3), ("mode", C.c_int32), ("connectivity", C.c_int32),
+                ("sweeps", C.c_int32), ("resume", C.c_int32)]
+
+
 class TransferSummary(C.Structure):
     """a3d_transfer_summary: matched, unmatched and non-finite queries, source rows left out as not finite, the error word
     (A3D_TRANSFER_UNKEYABLE, A3D_TRANSFER_SORT_FAILED)."""
@@ -441,6 +462,9 @@ A3D_MEASURE_MAX_BITS, A3D_MEASURE_MAX_Q, A3D_MEASURE_MAX_FACES = 20, 1 << 38, 1 
 A3D_MEASURE_BLOCK, A3D_MEASURE_CHUNK = 256, 1024
 A3D_GROW_MAX_STEPS, A3D_GROW_BAD_INDEX = 1024, 1
 A3D_NORMALS_RANGE, A3D_NORMALS_BAD_INDEX = 1, 2
+A3D_ORIENT_MAX_ROWS, A3D_ORIENT_MAX_SWEEPS = 1 << 21, 4096
+A3D_ORIENT_GIVEN, A3D_ORIENT_NEAREST = 0, 1
+A3D_ORIENT_BAD_INDEX, A3D_ORIENT_BAD_COMPONENT = 1, 2
 A3D_TRANSFER_UNKEYABLE, A3D_TRANSFER_SORT_FAILED = 1, 2
 A3D_MATCH_CHANNELS, A3D_MATCH_QUANTUM_BITS, A3D_MATCH_FIXED_BITS = 128, 20, 40
 A3D_MATCH_MAX_EXAMPLE_ROWS, A3D_MATCH_MAX_PROTOTYPES, A3D_MATCH_CHUNK = 1 << 22, 256, 16
@@ -654,6 +678,9 @@ SYMBOLS = {
     "a3d_estimate_normals": (C.c_int, [C.POINTER(EstimateNormalsArgs), C.c_void_p]),
     "a3d_normals_solve": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_double,
                                     C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "a3d_orient_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "a3d_orient_normals": (C.c_int, [C.POINTER(OrientNormalsArgs), C.c_void_p]),
+    "a3d_orient_edge": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "a3d_point_index_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "a3d_point_index_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p,
                                          C.POINTER(C.c_void_p)]),

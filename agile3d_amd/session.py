@@ -441,6 +441,20 @@ class NormalsResult(_Result):
     __slots__ = ("normals_full", "normals_qv", "variation_qv", "count_qv", "counted", "valid", "invalid", "err", "viewpoint")
 
 
+class OrientResult(_Result):
+    """What ``orient_normals()`` and ``orient_at()`` return.  Device tensors: ``normals_full`` fp32 [n_full, 3] and ``normals_qv``
+    fp32 [n_voxels, 3] (the input normals with the sign turned where ``flipped_qv`` is 1; every other byte as it was),
+    ``flipped_qv`` uint8 [n_voxels], ``dist_qv`` int32 [n_voxels] (the cost of the path from the seed, 1 .. 1024 an edge; -1: not
+    reached) and ``owner_qv`` int32 [n_voxels] (the voxel row of that seed).  Host, from ``a3d_orient_normals``' summary:
+    ``admitted`` (voxels with a normal), ``seeds``, ``reached``, ``unreached``, ``flipped``, ``conflicts`` (edges whose two
+    normals still disagree: where the regions of two seeds meet, or on a loop that cannot be oriented), ``max_dist``, ``err``;
+    ``launched``: the relaxation sweeps issued in all; ``connectivity`` as used; ``result``: the ``NormalsResult`` that now
+    holds these normals (what ``normal_at``, ``patches`` and ``planes`` take)."""
+
+    __slots__ = ("normals_full", "normals_qv", "flipped_qv", "dist_qv", "owner_qv", "admitted", "seeds", "reached", "unreached",
+                 "flipped", "conflicts", "max_dist", "err", "launched", "connectivity", "result")
+
+
 PLANE_KINDS = ("floor", "ceiling", "wall", "horizontal", "other")
 
 
@@ -2441,6 +2455,139 @@ class InteractiveSession:
         row = self.inverse_map[vertex]
         both = torch.cat([normals.normals_full[vertex], normals.variation_qv[row].reshape(1)]).cpu().numpy()
         return both[:3].copy(), float(both[3])
+
+    # ------------------------------------------------------------------ one sign for a whole surface
+    def _orient_source(self, normals):
+        res = self._normals_last if normals is None and self.faces is None else normals
+        if res is None:
+            raise ValueError("no normals: call estimate_normals() first (on a mesh it keeps none with the scene: pass its result "
+                             "as normals=)")
+        n = self.raw_coords_qv.shape[0]
+        if not isinstance(res, NormalsResult) or not torch.is_tensor(res.normals_qv) or res.normals_qv.device != self.device \
+                or tuple(res.normals_qv.shape) != (n, 3):
+            raise ValueError("normals must be a NormalsResult of this scene (estimate_normals())")
+        return res
+
+    def _orient_seeds(self, seeds):
+        """``seed_qv`` uint8 [n_voxels] of ``orient_normals(seeds=)`` other than ``"nearest"``."""
+        n = self.raw_coords_qv.shape[0]
+        if isinstance(seeds, (SelectResult, GrowResult, WandResult)):
+            seed_qv = torch.zeros(n, dtype=torch.uint8, device=self.device)
+            seed_qv[self.inverse_map[self._selection(seeds) != 0]] = 1
+            return seed_qv
+        if torch.is_tensor(seeds):
+            if seeds.device != self.device or seeds.dtype not in (torch.uint8, torch.bool) or tuple(seeds.shape) != (n,):
+                raise ValueError(f"a seed mask must be a uint8 / bool tensor [{n}] over the voxels on the session's device")
+            return (seeds != 0).to(torch.uint8)
+        try:
+            rows = [int(r) for r in seeds]
+        except (TypeError, ValueError):
+            raise ValueError('seeds must be "nearest", a SelectResult / GrowResult, a uint8 / bool mask over the voxels or a list '
+                             "of voxel rows") from None
+        if any(not 0 <= r < n for r in rows):
+            raise ValueError(f"seeds: a voxel row outside 0 .. {n - 1}")
+        seed_qv = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        if rows:
+            seed_qv[torch.tensor(rows, dtype=torch.int64).to(self.device)] = 1
+        return seed_qv
+
+    def _orient(self, src, connectivity, sweeps, **seeds):
+        """``a3d_orient_normals`` until it has converged: one library call and ONE host round trip (the summary) per batch of
+        ``sweeps``; then, on a cloud, the oriented normals become the scene's."""
+        n = self.raw_coords_qv.shape[0]
+        nrm = src.normals_qv.contiguous()
+        outs, launched, ws = None, 0, None
+        for batch in range(n // sweeps + 2):                            # (a path has fewer than n edges: n sweeps always suffice)
+            outs = V.orient_normals(self._scene_handle(), nrm, connectivity=connectivity, sweeps=sweeps, resume=batch > 0,
+                                    inverse_map=self.inverse_map, workspace=ws,
+                                    **(dict(zip(("normal_out_qv", "flipped_qv", "dist_qv", "owner_qv", "normal_full"), outs[:5]))
+                                       if outs else {}), **seeds)
+            ws = outs[6]
+            launched += sweeps
+            s = V.read_orient_summary(outs[5].cpu().numpy())            # the one host round trip of the batch
+            if s["err"] & V.ORIENT_BAD_INDEX:
+                raise RuntimeError("a3d_orient_normals: inverse_map out of range")
+            if s["converged"]:
+                break
+        else:
+            raise RuntimeError("a3d_orient_normals did not converge")
+        normal_qv, flipped_qv, dist_qv, owner_qv, normal_full = outs[:5]
+        kept = NormalsResult(normals_full=normal_full, normals_qv=normal_qv, variation_qv=src.variation_qv, count_qv=src.count_qv,
+                             counted=src.counted, valid=src.valid, invalid=src.invalid, err=src.err, viewpoint=src.viewpoint)
+        if self.faces is None:
+            self.normals, self._normals_last, self._culled = normal_full, kept, {}
+        return OrientResult(normals_full=normal_full, normals_qv=normal_qv, flipped_qv=flipped_qv, dist_qv=dist_qv,
+                            owner_qv=owner_qv, launched=launched, connectivity=connectivity, result=kept,
+                            **{k: s[k] for k in ("admitted", "seeds", "reached", "unreached", "flipped", "conflicts", "max_dist",
+                                                 "err")})
+
+    def orient_normals(self, seeds="nearest", viewpoint="centre", connectivity=26, normals=None, sweeps=512):
+        """Gives the normals ONE CONSISTENT SIGN per connected surface, by propagation (``a3d_orient_normals``; the rule is
+        stated in include/agile3d_hip.h).  ``estimate_normals()`` signs every voxel by one viewpoint, which is right for the
+        walls of a room seen from inside and wrong for the far sides of whatever stands in it.  Here a trusted sign starts
+        at SEED voxels and is carried from neighbour to neighbour (``connectivity`` 6, 18 or 26) along the cheapest path --
+        an edge costs 1 where the two normals are parallel and up to 1024 where they are perpendicular, so the sign travels
+        along smooth surface and crosses creases last -- and is turned wherever two neighbours disagree.
+        ``seeds="nearest"``: per connected component of the voxels that have a normal (``a3d_label_pieces``) the voxel
+        nearest to ``viewpoint`` -- a point, or ``"centre"``, the centre of the scene's box -- is the seed and is turned
+        towards it.  Or the seeds are voxels whose sign is TRUSTED AS IT STANDS: a ``SelectResult`` / ``GrowResult`` (the
+        voxels that hold a selected vertex), a uint8 / bool mask over the voxels, or a list of voxel rows; ``viewpoint`` then
+        plays no part.  ``normals``: a ``NormalsResult``; ``None`` takes the one ``estimate_normals()`` left with a cloud
+        (``ValueError`` when there is none, or when it belongs to another scene).
+        On a CLOUD the oriented normals replace ``ses.normals`` and the culled copies are dropped, exactly as a second
+        ``estimate_normals()`` does: ``render(lit=True)``, a ``Section`` with ``cull=`` and ``patches(oriented=True)`` see
+        them from then on.  On a MESH the result is returned and no session state changes.
+        ``sweeps`` (1 .. 4096) relaxation sweeps are launched per library call and the call is repeated, resuming, while it
+        has not converged: ``ceil(depth / sweeps)`` calls and as many host round trips (one summary each), where depth is
+        the largest number of edges on a seed's cheapest path -- one round trip on a room at the default.  The component
+        labelling of ``"nearest"`` adds none.  Returns an ``OrientResult``.
+        LIMITS: a shortest-path tree, not a minimum spanning tree; one normal per voxel, so a plate one voxel thick has one
+        side; the cost scale, the ``"nearest"`` seed and the 26-connectivity default are this project's choices and are NOT
+        tuned on real scans."""
+        self._need_scene()
+        connectivity = V._connectivity(connectivity)
+        sweeps = V._int_in("sweeps", sweeps, 1, V.ORIENT_MAX_SWEEPS)
+        src = self._orient_source(normals)
+        if isinstance(seeds, str):
+            if seeds != "nearest":
+                raise ValueError('seeds: the only name is "nearest"')
+            if isinstance(viewpoint, str):
+                if viewpoint != "centre":
+                    raise ValueError("viewpoint must be a point or 'centre'")
+                vp = np.array(self._fixed_point_frame()[0], np.float64)
+            else:
+                vp = np.asarray(viewpoint, dtype=np.float64).reshape(-1)
+                if vp.shape != (3,) or not np.isfinite(vp).all():
+                    raise ValueError("viewpoint must be three finite numbers or 'centre'")
+            nrm = src.normals_qv
+            has = torch.isfinite(nrm).all(1) & (nrm != 0).any(1)
+            comp = V.label_pieces(self._scene_handle(), has.to(torch.int32) - 1, connectivity,
+                                  records=torch.empty(V.PIECE.itemsize, dtype=torch.uint8, device=self.device))[0]
+            return self._orient(src, connectivity, sweeps, components=comp, positions=self.raw_coords_qv, viewpoint=vp)
+        return self._orient(src, connectivity, sweeps, seed_qv=self._orient_seeds(seeds))
+
+    def orient_at(self, result, u, v, normals=None, connectivity=26, sweeps=512):
+        """THIS SURFACE FACES ME: orients from the voxel of the vertex that pixel ``(u, v)`` (column, row) of ``result`` shows --
+        resolved as ``normal_at`` resolves it -- with its normal turned towards the camera's eye.  Only the voxels that seed
+        reaches change; every other voxel keeps its bytes.  Returns an ``OrientResult`` as ``orient_normals`` does (and
+        keeps it with a cloud in the same way), or ``None`` where the pixel shows nothing.  One small device-to-host copy,
+        then as ``orient_normals``."""
+        self._need_scene()
+        connectivity = V._connectivity(connectivity)
+        sweeps = V._int_in("sweeps", sweeps, 1, V.ORIENT_MAX_SWEEPS)
+        src = self._orient_source(normals)
+        vertex = self._vertex_at(result, u, v)
+        if vertex < 0:
+            return None
+        n = self.raw_coords_qv.shape[0]
+        row = self.inverse_map[vertex]
+        eye = torch.tensor([float(c) for c in result.camera.o[:]], dtype=torch.float64, device=self.device)
+        towards = (src.normals_qv[row].to(torch.float64) * (eye - self.coords_full[vertex].to(torch.float64))).sum()
+        seed_qv = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        seed_qv[row] = 1
+        seed_flip = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        seed_flip[row] = (towards < 0).to(torch.uint8)
+        return self._orient(src, connectivity, sweeps, seed_qv=seed_qv, seed_flip=seed_flip)
 
     # ------------------------------------------------------------------ the planes a room is made of
     def planes(self, normal_deg=20.0, dist_tol=None, min_voxels=200, max_planes=16, within="all", normals=None, up=(0, 0, 1)):

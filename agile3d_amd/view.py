@@ -1082,6 +1082,103 @@ def cull_points(xyz, normals, eye, mode, out=None, hidden=None, count=None):
     return out, hidden, count
 
 
+# ---- one sign for a whole surface: normals oriented by propagation ---------------------------------------------------------------
+ORIENT_SUMMARY = np.dtype([("admitted", "<i8"), ("seeds", "<i8"), ("reached", "<i8"), ("unreached", "<i8"), ("flipped", "<i8"),
+                           ("conflicts", "<i8"), ("max_dist", "<i4"), ("converged", "<i4"), ("err", "<i4"), ("reserved_", "<i4")])
+assert C.sizeof(L.OrientSummary) == ORIENT_SUMMARY.itemsize == 64
+assert C.sizeof(L.OrientNormalsArgs) == 176
+ORIENT_MAX_ROWS, ORIENT_MAX_SWEEPS = L.A3D_ORIENT_MAX_ROWS, L.A3D_ORIENT_MAX_SWEEPS
+ORIENT_BAD_INDEX, ORIENT_BAD_COMPONENT = L.A3D_ORIENT_BAD_INDEX, L.A3D_ORIENT_BAD_COMPONENT    # the bits of the error word
+ORIENT_MODES = {"given": L.A3D_ORIENT_GIVEN, "nearest": L.A3D_ORIENT_NEAREST}
+
+
+def read_orient_summary(host):
+    """The host copy of an ``a3d_orient_summary`` (uint8 [64], or anything of those bytes) as a dict of Python ints:
+    ``admitted``, ``seeds``, ``reached``, ``unreached``, ``flipped`` (voxels), ``conflicts`` (edges), ``max_dist``,
+    ``converged`` (1: the last sweep lowered nothing) and ``err`` (``ORIENT_BAD_INDEX``, ``ORIENT_BAD_COMPONENT``)."""
+    return _summary_ints(host, ORIENT_SUMMARY)
+
+
+def orient_workspace(n, device):
+    """The scratch of ``orient_normals`` for n voxels (``a3d_orient_workspace_bytes``; at most 2^21 voxels).  A call with
+    ``resume=True`` continues from what the call before left in it."""
+    return _scratch(L.load().a3d_orient_workspace_bytes(n), device, f"no orient workspace for n={n} (0 .. {ORIENT_MAX_ROWS})")
+
+
+def orient_edge(a, b):
+    """``a3d_orient_edge`` (host only, no GPU): ``(w, flip)`` of the edge between two voxels with the normals ``a`` and ``b``
+    (fp32 [3] each) -- the cost in 1 .. 1024 and whether the normals disagree (``dot < 0``) -- by the function the kernel calls.
+    NaNs and zeros are passed on as they are."""
+    ka, pa = _f32p("a", a, (3,))
+    kb, pb = _f32p("b", b, (3,))
+    w, flip = C.c_int32(0), C.c_int32(0)
+    L.check(L.load().a3d_orient_edge(pa, pb, C.byref(w), C.byref(flip)), "a3d_orient_edge")
+    return int(w.value), bool(flip.value)
+
+
+def orient_normals(scene, normals, seed_qv=None, seed_flip=None, components=None, positions=None, viewpoint=None, connectivity=26,
+                   sweeps=512, resume=False, inverse_map=None, n_full=None, normal_out_qv=None, flipped_qv=None, dist_qv=None,
+                   owner_qv=None, normal_full=None, summary=None, workspace=None):
+    """``a3d_orient_normals``: the ``normals`` fp32 [n, 3] of the voxels of ``scene`` (an ``engine.Scene``; n rows in the
+    caller's order) given one consistent sign by propagation from seed voxels along the edges between neighbours under
+    ``connectivity`` (the rule: include/agile3d_hip.h).  Seeds, one of two modes: ``seed_qv`` uint8 [n] marks voxels whose sign
+    is trusted (``seed_flip`` uint8 [n], optional: negate these first); or ``components`` int32 [n] (``label_pieces`` of the
+    rows with a normal), ``positions`` fp32 [n, 3] and ``viewpoint`` (three finite numbers): per component the voxel nearest to
+    the viewpoint is the seed and is turned towards it.  ``sweeps`` (1 .. 4096) relaxation sweeps are launched; with
+    ``resume`` the call continues from the state ``workspace`` holds (the same arguments otherwise).  The lift: ``inverse_map``
+    int64 [n_full], or ``n_full`` alone for the identity.  Outputs: a tensor of the caller's, ``None`` = allocated, ``False`` =
+    not wanted.  Returns ``(normal_out_qv fp32 [n, 3], flipped_qv uint8 [n], dist_qv int32 [n], owner_qv int32 [n],
+    normal_full fp32 [n_full, 3], summary uint8 [64], workspace)`` on the device, ``None`` for what was not wanted;
+    ``read_orient_summary`` decodes the summary's host copy -- while its ``converged`` is 0 the outputs are not final."""
+    connectivity = _connectivity(connectivity)
+    sweeps = _int_in("sweeps", sweeps, 1, ORIENT_MAX_SWEEPS)
+    handle, n = _scene_rows(scene)
+    if n > ORIENT_MAX_ROWS:
+        raise ValueError(f"{n} voxels: at most {ORIENT_MAX_ROWS} (2^21), so that every path cost fits 31 bits")
+    given = seed_qv is not None or seed_flip is not None
+    nearest = components is not None or positions is not None or viewpoint is not None
+    if given == nearest:
+        raise ValueError("seeds: either seed_qv (with seed_flip), or components, positions and viewpoint")
+    if given and seed_qv is None:
+        raise ValueError("seed_flip belongs to seed_qv, which is missing")
+    if nearest and (components is None or positions is None or viewpoint is None):
+        raise ValueError("the nearest seeds need components, positions and viewpoint, all three")
+    dev = _device("normals", normals)
+    a = L.OrientNormalsArgs()
+    a.scene, a.n = handle, n
+    a.normal_qv_dev = _ptr("normals", normals, F32, (n, 3), dev)
+    a.mode = L.A3D_ORIENT_GIVEN if given else L.A3D_ORIENT_NEAREST
+    a.seed_qv_dev = _ptr("seed_qv", seed_qv, U8, (n,), dev, optional=True)
+    a.seed_flip_dev = _ptr("seed_flip", seed_flip, U8, (n,), dev, optional=True)
+    a.component_qv_dev = _ptr("components", components, I32, (n,), dev, optional=True)
+    a.position_qv_dev = _ptr("positions", positions, F32, (n, 3), dev, optional=True)
+    if nearest:
+        a.viewpoint[:] = _three_finite("viewpoint", viewpoint)
+    a.connectivity, a.sweeps, a.resume = connectivity, sweeps, int(bool(resume))
+    if inverse_map is not None:
+        if n_full is not None and n_full != inverse_map.shape[0]:
+            raise ValueError("n_full must be the length of inverse_map")
+        n_full = inverse_map.shape[0]
+    n_full = _int_in("n_full", 0 if n_full is None else n_full, 0, (1 << 31) - 1, "n_full must be an integer in 0 .. 2^31 - 1")
+    a.n_full = n_full
+    a.inverse_map_dev = _ptr("inverse_map", inverse_map, I64, (n_full,), dev, optional=True)
+    outs = _wanted(a, dev, (("normal_out_qv", normal_out_qv, F32, (n, 3)), ("flipped_qv", flipped_qv, U8, (n,)),
+                            ("dist_qv", dist_qv, I32, (n,)), ("owner_qv", owner_qv, I32, (n,)),
+                            ("normal_full", normal_full, F32, (n_full, 3))))
+    if outs[0] is not None and outs[0].data_ptr() == normals.data_ptr():
+        raise ValueError("normal_out_qv must not be the input array")
+    summary = _summary(summary, ORIENT_SUMMARY.itemsize, dev)
+    a.summary_dev = summary.data_ptr()
+    if workspace is None:
+        if resume:
+            raise ValueError("resume continues from a workspace: pass the one the call before returned")
+        workspace = orient_workspace(n, dev)
+    _attach(a, workspace, dev, L.load().a3d_orient_workspace_bytes(n),
+            "workspace too small or not 256-byte aligned (orient_workspace(n, device))")
+    L.check(L.load().a3d_orient_normals(C.byref(a), L.stream(dev)), "a3d_orient_normals")
+    return (*outs, summary, workspace)
+
+
 # ---- labels to and from another point set: an index over any point set, the bulk nearest query ---------------------------------
 TRANSFER_SUMMARY = np.dtype([("matched", "<i8"), ("unmatched", "<i8"), ("nonfinite", "<i8"), ("source_left_out", "<i8"),
                              ("err", "<i4"), ("reserved_", "<i4")])

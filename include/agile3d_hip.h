@@ -1380,7 +1380,7 @@ int    a3d_object_extents(const a3d_extents_args* args, void* stream);
  *   two, an origin or (with has_viewpoint) a viewpoint that is not finite, no summary_dev, a workspace that is missing, too
  *   small or misaligned.
  *   LIMITS: all vertices of a voxel share one normal (shading is faceted at the voxel size); the sign is only as good as the
- *   viewpoint (no propagation between voxels). */
+ *   viewpoint (a3d_orient_normals, below, carries a sign from voxel to voxel). */
 #define A3D_NORMALS_RANGE     1
 #define A3D_NORMALS_BAD_INDEX 2
 typedef struct a3d_normals_summary {
@@ -1419,6 +1419,119 @@ int    a3d_estimate_normals(const a3d_estimate_normals_args* args, void* stream)
  * positive power of two. */
 int    a3d_normals_solve(int64_t count, const int64_t* sum3, const int64_t* mom6, const double* origin, double quantum,
                          const double* viewpoint, float* out5);
+
+/* ONE SIGN FOR A WHOLE SURFACE: the normals of a3d_estimate_normals oriented consistently by PROPAGATION from seed voxels over
+ * the adjacency of a3d_label_pieces (csrc/session_orient.hip).  The viewpoint sign is right for the walls of a room scanned
+ * from inside and wrong for the far sides of everything that stands in it; this call carries a trusted sign from a seed along
+ * the surface, flipping wherever two neighbouring normals disagree.  The rule is this library's: the reference's tool has no
+ * counterpart.  Everything but the edge function is an integer, and that function is one fixed sequence of fp32 operations.
+ *
+ * a3d_orient_normals.  scene, n = its level-0 size (rows in the CALLER's order), n <= A3D_ORIENT_MAX_ROWS = 2^21 (a path has
+ * fewer than n edges of cost <= 1024: every path cost fits 31 bits).  normal_qv_dev fp32 [n][3].
+ *   ADMITTED ROWS: a row whose three components are finite and not all zero (-0 is zero).  Any other row takes no part and
+ *   keeps its bytes.
+ *   EDGE: two admitted neighbours under the connectivity (6, 18 or 26, the offsets a3d_label_pieces admits; A3D_TAB_NBR27,
+ *   both ends through A3D_TAB_ORIGROW: never across batch samples).  For the normals a and b, in fp32, every operation
+ *   rounded on its own (no fma contraction), as NSIM above:
+ *       dot = (a0*b0 + a1*b1) + a2*b2
+ *       w = 1 + (int)floorf(1023.0f * fmaxf(1.0f - fabsf(dot), 0.0f))          an integer in 1 .. 1024 (a NaN dot gives 1)
+ *       flip = dot < 0
+ *   Both are symmetric bit for bit.  a3d_orient_edge(a, b, &w, &flip) is the same function on the host (HOST arrays of 3;
+ *   A3D_ERR_INVALID for a NULL pointer), so a test without a GPU holds the very function the kernel calls.
+ *   SEEDS, mode A3D_ORIENT_GIVEN: seed_qv_dev uint8 [n]; an admitted row with a non-zero entry is a seed whose sign is trusted
+ *   as it stands -- unless seed_flip_dev uint8 [n] (optional) holds a non-zero entry for it: then its normal is negated first.
+ *   SEEDS, mode A3D_ORIENT_NEAREST: component_qv_dev int32 [n] (< 0: in no component, else 0 .. n-1; a value >= n sets
+ *   A3D_ORIENT_BAD_COMPONENT and the row is in none), position_qv_dev fp32 [n][3], viewpoint (doubles, finite).  A CANDIDATE
+ *   is an admitted row in a component whose position is finite.  In double, every operation rounded on its own:
+ *       dx = (double)p_x - vp_x (dy, dz likewise);   d2 = (dx*dx + dy*dy) + dz*dz
+ *   Per component the seed is the candidate with the lexicographically least (d2, row) -- found without any dependence on
+ *   order: one pass of 64-bit atomicMin on the bit pattern of d2 (d2 >= +0 or +inf: the patterns order like the values), one
+ *   pass of atomicMin on the row among the candidates that hold that d2.  The seed's flip is g < 0 with
+ *       g = (n0*(vp0 - p0) + n1*(vp1 - p1)) + n2*(vp2 - p2)                      in double, n and p converted first
+ *   PHASE 1, distance and owner: the value of an admitted voxel v is the LEXICOGRAPHIC MINIMUM of (d, s) over the seeds s with a
+ *   path of edges to v, d = the sum of w along the path, s = the seed's caller row: dist[v] = d, owner[v] = s, -1 where there
+ *   is none.  There is no limit on d.  How: a3d_grow_voxels' method -- ONE word dist << 32 | owner, 64-bit atomicMin, only the
+ *   voxels lowered in the sweep before offer, a sweep that lowered anything raises a device flag and the next launch returns
+ *   at once when the flag is clear.  The fixed point is unique (the argument at a3d_grow_voxels), whatever order the
+ *   relaxations land in.  The call launches exactly `sweeps` (1 .. A3D_ORIENT_MAX_SWEEPS) sweep kernels; the summary's
+ *   `converged` is 1 when the last of them lowered nothing: then every output is the rule's.  When it is 0 the outputs are
+ *   a safe intermediate state and depend on timing: call again with resume = 1 and the SAME arguments and workspace, and the
+ *   call continues from the workspace's state (the edge table, the words, the front, the seeds' flips) instead of clearing
+ *   it; since the fixed point is unique, resuming gives the same bytes as one long call.  resume = 1 on a workspace no call
+ *   has filled for these arguments is undefined in its outputs (but stays inside its buffers).
+ *   The 27 (w, flip) words of every voxel are tabulated once (one kernel, 2 bytes a slot) and the sweeps read the table, not
+ *   the normals.
+ *   PHASE 2, parent: a pure function of phase 1.  A seed has none.  Any other reached voxel v takes the neighbour u at the
+ *   LOWEST offset slot k (0 .. 26, offset (k % 3 - 1, (k / 3) % 3 - 1, k / 9 - 1), among the admitted offsets) with
+ *   owner[u] == owner[v] and dist[u] + w(u, v) == dist[v]; edge_flip[v] = flip(u, v).  Such a u exists at the fixed point
+ *   (before it, a voxel without one is treated as a seed without a flip).  The parity of the path is NOT carried in the
+ *   relaxed word: XOR is not monotone, and a transient word of parity 0 could never be raised again.
+ *   PHASE 3, parity: parity[v] = the XOR of edge_flip along the parent chain, XOR the seed's flip.  Pointer jumping on two
+ *   buffers of (ancestor, parity), each round a launch that reads one and writes the other, ceil(log2(n)) rounds (a chain
+ *   has fewer than n edges).
+ *   OUTPUTS, all optional but the summary: normal_out_qv_dev fp32 [n][3] (the input with the sign bit of every component
+ *   flipped where parity == 1; the input's bytes elsewhere, rows not reached or not admitted included; it must not be the
+ *   input array), flipped_qv_dev uint8 [n] (the parity), dist_qv_dev and owner_qv_dev int32 [n], normal_full_dev fp32
+ *   [n_full][3] = the output normal of row inverse_map[i] (NULL map: the identity), (0, 0, 0) for a row outside 0..n-1, which
+ *   sets A3D_ORIENT_BAD_INDEX.  The summary (cleared by the call): admitted rows, seeds, reached and unreached (admitted)
+ *   rows, flipped rows, conflicts, the largest dist, converged, the error word.  CONFLICTS: the edges, each counted once,
+ *   whose two OUTPUT normals have dot < 0 (the dot above; negating a normal negates it exactly): they remain where the
+ *   regions of two seeds meet, and on a loop that cannot be oriented.  Integer sums and maxima, one atomic per workgroup and
+ *   counter.  Two calls give the same bytes in every output.
+ *   The workspace: a3d_orient_workspace_bytes(n) bytes (0 for n < 0 or n > 2^21), 256-byte aligned.  The library allocates
+ *   nothing, does not synchronise and reads nothing back; the phases are launches -- no grid barrier, no spin-wait.
+ *   A3D_ERR_INVALID with nothing launched and nothing written: no arguments, no scene, n != the scene's level-0 size or
+ *   n > 2^21, a connectivity other than 6 / 18 / 26, sweeps outside 1 .. 4096, a mode or a resume that is neither 0 nor 1, no
+ *   normal_qv_dev with n > 0, mode GIVEN without seed_qv_dev, mode NEAREST without component_qv_dev or position_qv_dev or with
+ *   a viewpoint that is not finite, no summary_dev, normal_out_qv_dev == normal_qv_dev, a workspace that is missing, too small
+ *   or misaligned, n_full < 0 or >= 2^31.
+ *   LIMITS: a shortest-path tree, not a minimum spanning tree; one normal per voxel, so a plate one voxel thick has one side;
+ *   the cost scale 1 .. 1024 is this library's choice and is not tuned on real scans. */
+#define A3D_ORIENT_MAX_ROWS   (1 << 21)
+#define A3D_ORIENT_MAX_SWEEPS 4096
+#define A3D_ORIENT_GIVEN      0
+#define A3D_ORIENT_NEAREST    1
+#define A3D_ORIENT_BAD_INDEX     1
+#define A3D_ORIENT_BAD_COMPONENT 2
+typedef struct a3d_orient_summary {
+  int64_t admitted;
+  int64_t seeds;
+  int64_t reached;                  /* voxels with dist >= 0, the seeds included */
+  int64_t unreached;                /* admitted voxels without a seed to reach them */
+  int64_t flipped;
+  int64_t conflicts;
+  int32_t max_dist;
+  int32_t converged;                /* 1: the last sweep lowered nothing */
+  int32_t err;                      /* A3D_ORIENT_BAD_INDEX | A3D_ORIENT_BAD_COMPONENT */
+  int32_t reserved_;
+} a3d_orient_summary;              /* 64 bytes */
+typedef struct a3d_orient_normals_args {
+  const a3d_scene* scene;
+  int64_t        n;
+  const float*   normal_qv_dev;     /* [n][3] */
+  const uint8_t* seed_qv_dev;       /* [n], mode GIVEN */
+  const uint8_t* seed_flip_dev;     /* [n] or NULL, mode GIVEN */
+  const int32_t* component_qv_dev;  /* [n], mode NEAREST */
+  const float*   position_qv_dev;   /* [n][3], mode NEAREST */
+  const int64_t* inverse_map_dev;   /* [n_full] or NULL: identity */
+  int64_t        n_full;
+  float*         normal_out_qv_dev; /* out [n][3] or NULL */
+  uint8_t*       flipped_qv_dev;    /* out [n] or NULL */
+  int32_t*       dist_qv_dev;       /* out [n] or NULL */
+  int32_t*       owner_qv_dev;      /* out [n] or NULL */
+  float*         normal_full_dev;   /* out [n_full][3] or NULL */
+  a3d_orient_summary* summary_dev;
+  void*          workspace_dev;
+  size_t         workspace_bytes;
+  double         viewpoint[3];      /* mode NEAREST */
+  int32_t        mode;              /* A3D_ORIENT_GIVEN, A3D_ORIENT_NEAREST */
+  int32_t        connectivity;
+  int32_t        sweeps;
+  int32_t        resume;
+} a3d_orient_normals_args;         /* 176 bytes */
+size_t a3d_orient_workspace_bytes(int64_t n);
+int    a3d_orient_normals(const a3d_orient_normals_args* args, void* stream);
+int    a3d_orient_edge(const float* a, const float* b, int32_t* w, int32_t* flip);
 
 /* LABELS TO AND FROM ANOTHER POINT SET: an index over an arbitrary point set and the bulk, exact nearest-point query against
  * it (csrc/session_transfer.hip).  a3d_nearest_rows scans every row for at most 64 queries a call, which is right for a click;
