@@ -1,13 +1,16 @@
 // libagile3d_hip -- BatchNorm in TRAINING mode over the [N, C] rows of a sparse tensor (ME.MinkowskiBatchNorm =
 // nn.BatchNorm1d over the concatenated rows of the batch, models/modules/common.py:22), forward and backward, with the
-// residual add and the ReLU of BasicBlock.forward (resnet_block.py:48-64) fused in.  Second kernel family of the
-// training path.  All of it is HBM-bound column statistics + element-wise work:
-//   forward : mean_c, var_c (two passes, like torch: the variance is taken around the mean), y = (x-mean) rstd g + b
-//             (+ res) (ReLU); running statistics updated with the unbiased variance
+// residual add and the ReLU of BasicBlock.forward (resnet_block.py:48-64) fused in; the same in pieces for statistics
+// that span the data-parallel ranks (SyncBN); the column sums of a matrix; LayerNorm over the channels of a row.  Second
+// kernel family of the training path.  All of it is HBM-bound statistics + element-wise work:
+//   forward : mean_c, var_c (the variance is taken around a mean, never as E[x^2] - E[x]^2: one sweep that gives every
+//             row block its own mean and M2, merged in fp64), y = (x-mean) rstd g + b (+ res) (ReLU); running statistics
+//             updated with the unbiased variance
 //   backward: g = dy (y > 0);  dbeta = sum g, dgamma = sum g xhat;  dx = gamma rstd (g - dbeta/N - xhat dgamma/N);
 //             the residual branch receives g
-// Column sums are two-stage and deterministic: row blocks -> partial[block][C] (fp32) -> one thread per column sums
-// the partials in block order in fp64.
+// Column reductions are two-stage and deterministic: row blocks -> partial[block][columns] (fp32) -> col_reduce: a
+// workgroup per 16 columns, its lanes take the blocks in strides and are folded in ascending order, all in fp64.
+// Order of the file: kernels, host helpers, entry points.
 #include "common.h"
 
 namespace a3d {
@@ -17,6 +20,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBnThreads = 192;     // divisible by C/4 for every channel count of the net (8..96 float4 columns)
 constexpr int kBnMaxBlocks = 1024;
 
+// the ReLU of the forward seen from the backward: the gradient passes where the OUTPUT y was positive
+__device__ __forceinline__ f32x4 relu_gate(f32x4 g, const f32x4 y) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) g[t] = y[t] > 0.f ? g[t] : 0.f;
+  return g;
+}
+
+// ---- first level: sums over the rows of a row block --------------------------------------------------------------
 // mode 0: sum x            mode 1: sum (x - m)^2
 // mode 2: two sums for the backward: g = dy * (y > 0 or 1), sum g and sum g * (x - m) * rstd   (out: [2][C])
 struct ColArgs {
@@ -59,11 +70,7 @@ __global__ void __launch_bounds__(kBnThreads) k_col_partial(const ColArgs a) {
         const f32x4 d = xv[u] - m;
         s0 += d * d;
       } else {
-        f32x4 g = gv[u];
-        if (a.relu) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) g[t] = yv[u][t] > 0.f ? g[t] : 0.f;
-        }
+        const f32x4 g = a.relu ? relu_gate(gv[u], yv[u]) : gv[u];
         s0 += g;
         s1 += g * ((xv[u] - m) * rs);
       }
@@ -123,12 +130,83 @@ __global__ void __launch_bounds__(kBnThreads) k_bn_block_stats(const ColArgs a) 
     *(f32x4*)(a.partial + (size_t)blockIdx.x * 2 * a.C + a.C + 4 * col) = s1;
   }
 }
-// The second level of the column reductions.  One thread per column walking up to 1024 block partials is a chain of a
-// thousand dependent L2 loads (38 us for a few KB of arithmetic; 130 of these launches per training iteration): a
-// 256-thread workgroup takes 16 consecutive columns, thread (bl, cc) folds the blocks bl, bl + 16, ... of column cc (64-byte
-// row segments per load), then one thread per column folds the 16 partial results in bl order -- fixed orders, fp64.
+
+// ---- second level: the block partials of a column, summed in fp64 ------------------------------------------------
+// One thread per column walking up to 1024 block partials is a chain of a thousand dependent L2 loads (38 us for a few KB
+// of arithmetic; 130 of these launches per training iteration).  So a workgroup takes kFinCols = 16 consecutive columns
+// with LANES block lanes each: lane bl sums the blocks bl, bl + LANES, ..., then thread c < 16 folds the LANES results of
+// its column in ascending lane order (col_fold) -- fixed orders.  Two geometries run:
+//   LANES = 16,  VEC = 1: 256 threads, thread (bl, cc) loads one float per block (64-byte row segments per load): the at
+//                         most 1024 row blocks of bn_blocks
+//   LANES = 256, VEC = 4: 1024 threads, thread (bl, q) loads the 16 bytes of column quad q per block: the MANY small
+//                         blocks of the conv epilogues (one per 64-row tile or 16-row group: 5 000 - 20 000 at 320 k
+//                         rows, 20 rounds per lane; 16 lanes per column walked 300+ blocks each)
+constexpr int kFinCols = 16, kFinLanes = 16, kFinTileLanes = 256;
+template <int LANES, int VEC>
+using FinShared = double[LANES][kFinCols + VEC / 4];      // (the 16-byte geometry pads its rows by one double)
+
+// -> in thread c < kFinCols the sum over the lanes, in lane order, of the s[] that belongs to column blockIdx.x * kFinCols + c
+template <int LANES, int VEC>
+__device__ __forceinline__ double col_fold(const double (&s)[VEC], FinShared<LANES, VEC>& sh) {
+  const int q = threadIdx.x % (kFinCols / VEC), bl = threadIdx.x / (kFinCols / VEC);
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) sh[bl][VEC * q + t] = s[t];
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x < kFinCols)
+    for (int k = 0; k < LANES; ++k) t += sh[k][threadIdx.x];
+  return t;
+}
+// -> in thread c < kFinCols the sum over the blocks of column blockIdx.x * kFinCols + c of partial [nblocks][stride]; columns
+// from ncol on are not read
+template <int LANES, int VEC>
+__device__ __forceinline__ double col_reduce(const float* __restrict__ partial, int nblocks, int stride, int ncol,
+                                             FinShared<LANES, VEC>& sh) {
+  const int q = threadIdx.x % (kFinCols / VEC), bl = threadIdx.x / (kFinCols / VEC);
+  const int c0 = blockIdx.x * kFinCols + VEC * q;
+  double s[VEC] = {};
+  if (c0 < ncol)
+    for (int b = bl; b < nblocks; b += LANES) {
+      if constexpr (VEC == 4) {
+        const f32x4 v = *(const f32x4*)(partial + (size_t)b * stride + c0);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) s[t] += (double)v[t];
+      } else {
+        s[0] += (double)partial[(size_t)b * stride + c0];
+      }
+    }
+  return col_fold<LANES, VEC>(s, sh);
+}
+
+// out[c] = the column sums of partial [nblocks][ncol], as fp64 or rounded to fp32 (launch: ceil(ncol / 16) workgroups of
+// 16 * LANES / VEC threads).  Three builds run: <16, 1, double>, <16, 1, float> (a3d_column_sums: one launch instead of
+// a sum + a conversion kernel) and <256, 4, double> (bn_sums_from_partials from 64 blocks on).
+template <int LANES, int VEC, typename OUT>
+__global__ void __launch_bounds__(kFinCols* LANES / VEC) k_col_final(const float* __restrict__ partial, int nblocks, int ncol, OUT* out) {
+  __shared__ FinShared<LANES, VEC> sh;
+  const double t = col_reduce<LANES, VEC>(partial, nblocks, ncol, ncol, sh);
+  const int c = blockIdx.x * kFinCols + threadIdx.x;
+  if (threadIdx.x < kFinCols && c < ncol) out[c] = (OUT)t;
+}
+
+// The end of the forward statistics of column c, from the merged (mean, M2 = sum of squared deviations, row count):
+// save_mean, save_rstd, and the running statistics moved towards the batch's with the UNBIASED variance, as torch does
+// (one row has none: the biased value, 0, takes its place).
+__device__ __forceinline__ void bn_write_stats(int c, double mean, double m2, double cnt, float eps, float momentum, float* mean_out,
+                                               float* rstd_out, float* running_mean, float* running_var) {
+  const float var = (float)(m2 / cnt);
+  mean_out[c] = (float)mean;
+  rstd_out[c] = 1.0f / sqrtf(var + eps);
+  if (running_mean) {
+    const float unbiased = cnt > 1.0 ? (float)(m2 / (cnt - 1.0)) : var;
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+  }
+}
+
+// The merge of k_bn_block_stats' partials in the 16-lane geometry above: thread (bl, cc) merges the blocks bl, bl + 16, ...
+// of column cc, then one thread per column merges the 16 triples in bl order -- fp64.
 // The partials are those of x - pivot (k_bn_block_stats: pivot = row 0 of x); the mean gets the pivot back.
-constexpr int kFinCols = 16, kFinLanes = 16;
 __global__ void __launch_bounds__(256) k_bn_combine(const float* __restrict__ partial, const float* __restrict__ pivot,
                                                     int nblocks, int rows_per_block, int n, int C, float eps, float* mean_out, float* rstd_out, float* running_mean,
                                                     float* running_var, float momentum) {
@@ -160,52 +238,27 @@ __global__ void __launch_bounds__(256) k_bn_combine(const float* __restrict__ pa
     m2 += s_m2[k][cc] + delta * delta * cnt * nb / tot;
     cnt = tot;
   }
-  mean += (double)pivot[c];
-  const float var = (float)(m2 / cnt);
-  mean_out[c] = (float)mean;
-  rstd_out[c] = 1.0f / sqrtf(var + eps);
-  if (running_mean) {
-    const float unbiased = cnt > 1.0 ? (float)(m2 / (cnt - 1.0)) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-  }
+  bn_write_stats(c, mean + (double)pivot[c], m2, cnt, eps, momentum, mean_out, rstd_out, running_mean, running_var);
 }
 
-// The same merge for MANY small blocks (the conv kernels' epilogues hand over one (sum, M2 around the block mean) pair per
-// 64-row tile or 16-row group: 5 000 - 20 000 blocks at 320 k rows) without a dependent chain of divisions: pass 1 sums the
-// block sums (fp64) -> the batch mean; pass 2 shifts every block's M2 to that mean with the exact identity
+// The same merge for the MANY small blocks of the conv kernels' epilogues (one (sum, M2 around the block mean) pair per
+// 64-row tile or 16-row group), in the 256-lane geometry and without a dependent chain of divisions: pass 1 sums the block
+// sums (col_reduce) -> the batch mean; pass 2 shifts every block's M2 to that mean with the exact identity
 //   sum (v - mean)^2 = M2_b + 2 (m_b - mean) (S_b - n_b m_b) + n_b (m_b - mean)^2        (m_b = the fp32 mean the block used)
-// 64 lanes per column, 16 columns per 1024-thread workgroup, every partial sum in a fixed order.
-constexpr int kFin2Lanes = 256;
+// and folds the lanes like pass 1.
 __global__ void __launch_bounds__(1024) k_bn_combine_tiles(const float* __restrict__ partial, int nblocks, int rows_per_block, int n,
                                                            int C, float eps, float* mean_out, float* rstd_out, float* running_mean,
                                                            float* running_var, float momentum) {
-  // thread (bl, q): block lane bl of 256, column quad q of the workgroup's 4 (16 columns per workgroup): one 16-byte load
-  // per block and thread, blocks bl, bl + 256, ... (20 rounds for the 5 000 tiles of a 320 k-row level)
-  __shared__ double sh[kFin2Lanes][kFinCols + 1];
+  __shared__ FinShared<kFinTileLanes, 4> sh;
   __shared__ double s_mean[kFinCols];
   const int q = threadIdx.x & 3, bl = threadIdx.x >> 2;
-  const int c0 = blockIdx.x * kFinCols + 4 * q;
-  const bool live = c0 < C;                          // C is a multiple of 4 (of 32)
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (live)
-    for (int b = bl; b < nblocks; b += kFin2Lanes) {
-      const f32x4 v = *(const f32x4*)(partial + (size_t)b * 2 * C + c0);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) s[t] += (double)v[t];
-    }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) sh[bl][4 * q + t] = s[t];
-  __syncthreads();
-  if (threadIdx.x < kFinCols) {
-    double t = 0.0;
-    for (int k = 0; k < kFin2Lanes; ++k) t += sh[k][threadIdx.x];
-    s_mean[threadIdx.x] = t / (double)n;
-  }
+  const int c0 = blockIdx.x * kFinCols + 4 * q;      // C is a multiple of 4 (of 32): a column quad is live or not as a whole
+  const double sum = col_reduce<kFinTileLanes, 4>(partial, nblocks, 2 * C, C, sh);
+  if (threadIdx.x < kFinCols) s_mean[threadIdx.x] = sum / (double)n;
   __syncthreads();
   double m2s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (live)
-    for (int b = bl; b < nblocks; b += kFin2Lanes) {
+  if (c0 < C)
+    for (int b = bl; b < nblocks; b += kFinTileLanes) {
       const int nbi = min(n, (b + 1) * rows_per_block) - b * rows_per_block;
       const f32x4 bsf = *(const f32x4*)(partial + (size_t)b * 2 * C + c0);
       const f32x4 bq = *(const f32x4*)(partial + (size_t)b * 2 * C + C + c0);
@@ -219,55 +272,14 @@ __global__ void __launch_bounds__(1024) k_bn_combine_tiles(const float* __restri
       }
     }
   __syncthreads();
-#pragma unroll
-  for (int t = 0; t < 4; ++t) sh[bl][4 * q + t] = m2s[t];
-  __syncthreads();
+  double m2 = col_fold<kFinTileLanes, 4>(m2s, sh);
   const int c = blockIdx.x * kFinCols + threadIdx.x;
   if (threadIdx.x >= kFinCols || c >= C) return;
-  double m2 = 0.0;
-  for (int k = 0; k < kFin2Lanes; ++k) m2 += sh[k][threadIdx.x];
   if (m2 < 0.0) m2 = 0.0;
-  const double cnt = (double)n, mean = s_mean[threadIdx.x];
-  const float var = (float)(m2 / cnt);
-  mean_out[c] = (float)mean;
-  rstd_out[c] = 1.0f / sqrtf(var + eps);
-  if (running_mean) {
-    const float unbiased = cnt > 1.0 ? (float)(m2 / (cnt - 1.0)) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-  }
+  bn_write_stats(c, s_mean[threadIdx.x], m2, (double)n, eps, momentum, mean_out, rstd_out, running_mean, running_var);
 }
 
-// column sums of the block partials, fp64: ncol = nsum * C columns of [nblocks][ncol] (launch: ceil(ncol / 16) x 256)
-__device__ __forceinline__ double col_final_sum(const float* __restrict__ partial, int nblocks, int ncol, int c, int bl, int cc,
-                                                double (*sh)[kFinCols]) {
-  double s = 0.0;
-  if (c < ncol)
-    for (int b = bl; b < nblocks; b += kFinLanes) s += (double)partial[(size_t)b * ncol + c];
-  sh[bl][cc] = s;
-  __syncthreads();
-  double t = 0.0;
-  if (bl == 0)
-    for (int k = 0; k < kFinLanes; ++k) t += sh[k][cc];
-  return t;
-}
-__global__ void __launch_bounds__(256) k_col_final(const float* __restrict__ partial, int nblocks, int nsum, int C, double* out) {
-  __shared__ double sh[kFinLanes][kFinCols];
-  const int cc = threadIdx.x % kFinCols, bl = threadIdx.x / kFinCols;
-  const int c = blockIdx.x * kFinCols + cc;
-  const double t = col_final_sum(partial, nblocks, nsum * C, c, bl, cc, sh);
-  if (bl == 0 && c < nsum * C) out[c] = t;
-}
-
-// the same sum written as fp32 (a3d_column_sums: one launch instead of k_col_final + a conversion kernel)
-__global__ void __launch_bounds__(256) k_col_final_f32(const float* __restrict__ partial, int nblocks, int C, float* out) {
-  __shared__ double sh[kFinLanes][kFinCols];
-  const int cc = threadIdx.x % kFinCols, bl = threadIdx.x / kFinCols;
-  const int c = blockIdx.x * kFinCols + cc;
-  const double t = col_final_sum(partial, nblocks, C, c, bl, cc, sh);
-  if (bl == 0 && c < C) out[c] = (float)t;
-}
-
+// a3d_bn_local_stats hands its mean to the second sweep in fp32 and to the caller in fp64
 __global__ void k_scale_f64(const double* in, int C, double f, double* out) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C) out[c] = in[c] * f;
@@ -276,19 +288,8 @@ __global__ void k_bn_mean(const double* sums, int C, double n, float* mean) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C) mean[c] = (float)(sums[c] / n);
 }
-__global__ void k_bn_rstd(const double* sq, int C, double n, float eps, float* rstd, const float* mean,
-                          float* running_mean, float* running_var, float momentum) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float var = (float)(sq[c] / n);
-  rstd[c] = 1.0f / sqrtf(var + eps);
-  if (running_mean) {
-    const float unbiased = n > 1.0 ? (float)(sq[c] / (n - 1.0)) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean[c];
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-  }
-}
 
+// ---- element-wise passes -------------------------------------------------------------------------------------------
 struct ApplyArgs {
   const float *x, *mean, *rstd, *gamma, *beta, *res;
   int ldx, ldr, ldy, n, C, relu;
@@ -333,11 +334,7 @@ __global__ void k_bn_bwd_apply(const BwdArgs a) {
   const int r = (int)(e / c4n), col = (int)(e % c4n);
   const f32x4 xv = *(const f32x4*)(a.x + (size_t)r * a.ldx + 4 * col);
   f32x4 g = *(const f32x4*)(a.dy + (size_t)r * a.lddy + 4 * col);
-  if (a.relu) {
-    const f32x4 yv = *(const f32x4*)(a.y + (size_t)r * a.ldy + 4 * col);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) g[t] = yv[t] > 0.f ? g[t] : 0.f;
-  }
+  if (a.relu) g = relu_gate(g, *(const f32x4*)(a.y + (size_t)r * a.ldy + 4 * col));
   if (a.dres) *(f32x4*)(a.dres + (size_t)r * a.lddres + 4 * col) = g;
   const f32x4 m = *(const f32x4*)(a.mean + 4 * col), rs = *(const f32x4*)(a.rstd + 4 * col);
   const f32x4 ga = *(const f32x4*)(a.gamma + 4 * col);
@@ -360,7 +357,7 @@ __global__ void k_bn_bwd_apply(const BwdArgs a) {
 }
 
 // ---- LayerNorm over the channels of every row (nn.LayerNorm(128) of the decoder: attention_block.py:38,98,155,
-// agile3d.py:137), forward and backward: one wave per row, lane = two channels at C = 128 (C <= 512: C / 64 per lane).
+// agile3d.py:137), forward and backward: one wave per row, lane = C / 64 channels (C <= 512).
 //   backward: gh = dy * gamma;  dx = rstd * (gh - mean(gh) - xhat * mean(gh * xhat));  dgamma = sum_rows dy * xhat,
 //             dbeta = sum_rows dy  (row-block partials -> k_col_final, deterministic)
 constexpr int kLnMaxPerLane = 8;
@@ -370,22 +367,29 @@ struct LnArgs {
   int ldx, ldy, n, C, rows_per_block;
   float eps;
 };
+__device__ __forceinline__ float ln64_sum(float v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// the wave loads row xrow (lane: channels lane, lane + 64, ...) into v -> the row's mean and rstd, two-pass
+__device__ __forceinline__ void ln_row_stats(const float* xrow, int lane, int per, int C, float eps, float (&v)[kLnMaxPerLane],
+                                             float& mean, float& rstd) {
+  float s = 0.f;
+  for (int i = 0; i < per; ++i) {
+    v[i] = xrow[lane + 64 * i];
+    s += v[i];
+  }
+  mean = ln64_sum(s) / (float)C;
+  float q = 0.f;
+  for (int i = 0; i < per; ++i) q += (v[i] - mean) * (v[i] - mean);
+  rstd = 1.0f / sqrtf(ln64_sum(q) / (float)C + eps);
+}
 __global__ void __launch_bounds__(256) k_ln_forward(const LnArgs a) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.n) return;
   const int per = a.C >> 6;
-  float v[kLnMaxPerLane];
-  float s = 0.f;
-  for (int i = 0; i < per; ++i) {
-    v[i] = a.x[(size_t)row * a.ldx + lane + 64 * i];
-    s += v[i];
-  }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  const float mean = s / (float)a.C;
-  float q = 0.f;
-  for (int i = 0; i < per; ++i) q += (v[i] - mean) * (v[i] - mean);
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-  const float rstd = 1.0f / sqrtf(q / (float)a.C + a.eps);
+  float v[kLnMaxPerLane], mean, rstd;
+  ln_row_stats(a.x + (size_t)row * a.ldx, lane, per, a.C, a.eps, v, mean, rstd);
   for (int i = 0; i < per; ++i) {
     const int c = lane + 64 * i;
     a.y[(size_t)row * a.ldy + c] = (v[i] - mean) * rstd * a.gamma[c] + a.beta[c];
@@ -399,19 +403,9 @@ __global__ void __launch_bounds__(256) k_ln_backward(const LnArgs a) {
   float dg[kLnMaxPerLane], db[kLnMaxPerLane], ga[kLnMaxPerLane];
   for (int i = 0; i < per; ++i) dg[i] = db[i] = 0.f, ga[i] = a.gamma[lane + 64 * i];
   for (int row = r0 + wave; row < r1; row += 4) {
-    float v[kLnMaxPerLane], g[kLnMaxPerLane];
-    float s = 0.f;
-    for (int i = 0; i < per; ++i) {
-      v[i] = a.x[(size_t)row * a.ldx + lane + 64 * i];
-      g[i] = a.dy[(size_t)row * a.ldy + lane + 64 * i];
-      s += v[i];
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s / (float)a.C;
-    float q = 0.f;
-    for (int i = 0; i < per; ++i) q += (v[i] - mean) * (v[i] - mean);
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    const float rstd = 1.0f / sqrtf(q / (float)a.C + a.eps);
+    float v[kLnMaxPerLane], g[kLnMaxPerLane], mean, rstd;
+    for (int i = 0; i < per; ++i) g[i] = a.dy[(size_t)row * a.ldy + lane + 64 * i];
+    ln_row_stats(a.x + (size_t)row * a.ldx, lane, per, a.C, a.eps, v, mean, rstd);
     float m1 = 0.f, m2 = 0.f;
     for (int i = 0; i < per; ++i) {
       v[i] = (v[i] - mean) * rstd;                  // xhat
@@ -421,11 +415,7 @@ __global__ void __launch_bounds__(256) k_ln_backward(const LnArgs a) {
       m1 += g[i];
       m2 += g[i] * v[i];
     }
-    for (int o = 32; o > 0; o >>= 1) {
-      m1 += __shfl_xor(m1, o, 64);
-      m2 += __shfl_xor(m2, o, 64);
-    }
-    m1 /= (float)a.C, m2 /= (float)a.C;
+    m1 = ln64_sum(m1) / (float)a.C, m2 = ln64_sum(m2) / (float)a.C;
     for (int i = 0; i < per; ++i) a.dx[(size_t)row * a.ldx + lane + 64 * i] = rstd * (g[i] - m1 - v[i] * m2);
   }
   for (int i = 0; i < per; ++i) {
@@ -450,17 +440,24 @@ __device__ __forceinline__ float ln16_sum(float v) {
   v += __shfl_xor(v, 8, 16);
   return v;
 }
+// a lane's eight channels, summed / multiplied and summed as a fixed tree (the tests pin values that depend on it)
+__device__ __forceinline__ float sum8(const f32x4 a, const f32x4 b) { return ((a[0] + a[1]) + (a[2] + a[3])) + ((b[0] + b[1]) + (b[2] + b[3])); }
+__device__ __forceinline__ float dot8(const f32x4 a0, const f32x4 a1, const f32x4 b0, const f32x4 b1) {
+  return ((a0[0] * b0[0] + a0[1] * b0[1]) + (a0[2] * b0[2] + a0[3] * b0[3])) + ((a1[0] * b1[0] + a1[1] * b1[1]) + (a1[2] * b1[2] + a1[3] * b1[3]));
+}
+// the row whose 16 lanes hold (v0, v1) -> d = v - mean(row) and the row's rstd
+__device__ __forceinline__ float ln128_row_stats(const f32x4 v0, const f32x4 v1, float eps, f32x4& d0, f32x4& d1) {
+  const float mean = ln16_sum(sum8(v0, v1)) * (1.f / 128.f);
+  d0 = v0 - mean, d1 = v1 - mean;
+  return 1.0f / sqrtf(ln16_sum(dot8(d0, d1, d0, d1)) * (1.f / 128.f) + eps);
+}
 __global__ void __launch_bounds__(256) k_ln_forward128(const LnArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane >> 4, j = lane & 15;
   const int row = blockIdx.x * 16 + wave * 4 + r;
   if (row >= a.n) return;
   const float* xp = a.x + (size_t)row * a.ldx + 8 * j;
-  const f32x4 v0 = *(const f32x4*)xp, v1 = *(const f32x4*)(xp + 4);
-  const float mean = ln16_sum(((v0[0] + v0[1]) + (v0[2] + v0[3])) + ((v1[0] + v1[1]) + (v1[2] + v1[3]))) * (1.f / 128.f);
-  const f32x4 d0 = v0 - mean, d1 = v1 - mean;
-  const float q = ln16_sum(((d0[0] * d0[0] + d0[1] * d0[1]) + (d0[2] * d0[2] + d0[3] * d0[3])) +
-                           ((d1[0] * d1[0] + d1[1] * d1[1]) + (d1[2] * d1[2] + d1[3] * d1[3])));
-  const float rstd = 1.0f / sqrtf(q * (1.f / 128.f) + a.eps);
+  f32x4 d0, d1;
+  const float rstd = ln128_row_stats(*(const f32x4*)xp, *(const f32x4*)(xp + 4), a.eps, d0, d1);
   const f32x4 g0 = *(const f32x4*)(a.gamma + 8 * j), g1 = *(const f32x4*)(a.gamma + 8 * j + 4);
   const f32x4 b0 = *(const f32x4*)(a.beta + 8 * j), b1 = *(const f32x4*)(a.beta + 8 * j + 4);
   float* yp = a.y + (size_t)row * a.ldy + 8 * j;
@@ -490,18 +487,14 @@ __global__ void __launch_bounds__(256) k_ln_backward128(const LnArgs a) {
     f32x4 v0 = nv0, v1 = nv1, g0 = ng0, g1 = ng1;
     if (!ok) v0 = v1 = g0 = g1 = (f32x4){0.f, 0.f, 0.f, 0.f};
     fetch(row + 16);
-    const float mean = ln16_sum(((v0[0] + v0[1]) + (v0[2] + v0[3])) + ((v1[0] + v1[1]) + (v1[2] + v1[3]))) * (1.f / 128.f);
-    f32x4 x0 = v0 - mean, x1 = v1 - mean;
-    const float q = ln16_sum(((x0[0] * x0[0] + x0[1] * x0[1]) + (x0[2] * x0[2] + x0[3] * x0[3])) +
-                             ((x1[0] * x1[0] + x1[1] * x1[1]) + (x1[2] * x1[2] + x1[3] * x1[3])));
-    const float rstd = 1.0f / sqrtf(q * (1.f / 128.f) + a.eps);
+    f32x4 x0, x1;
+    const float rstd = ln128_row_stats(v0, v1, a.eps, x0, x1);
     x0 = x0 * rstd, x1 = x1 * rstd;            // xhat
     dg0 += g0 * x0, dg1 += g1 * x1;
     db0 += g0, db1 += g1;
     g0 = g0 * ga0, g1 = g1 * ga1;              // gh
-    const float m1 = ln16_sum(((g0[0] + g0[1]) + (g0[2] + g0[3])) + ((g1[0] + g1[1]) + (g1[2] + g1[3]))) * (1.f / 128.f);
-    const float m2 = ln16_sum(((g0[0] * x0[0] + g0[1] * x0[1]) + (g0[2] * x0[2] + g0[3] * x0[3])) +
-                              ((g1[0] * x1[0] + g1[1] * x1[1]) + (g1[2] * x1[2] + g1[3] * x1[3]))) * (1.f / 128.f);
+    const float m1 = ln16_sum(sum8(g0, g1)) * (1.f / 128.f);
+    const float m2 = ln16_sum(dot8(g0, g1, x0, x1)) * (1.f / 128.f);
     if (ok) {
       float* dp = a.dx + (size_t)row * a.ldx + 8 * j;
       *(f32x4*)dp = rstd * (g0 - m1 - x0 * m2);
@@ -534,12 +527,98 @@ __global__ void k_ln_params(const double* sums, int C, float* dgamma, float* dbe
   if (c < C) dbeta[c] = (float)sums[c], dgamma[c] = (float)sums[C + c];
 }
 
+// ---- host helpers --------------------------------------------------------------------------------------------------
 static bool bn_shape_ok(int64_t n, int C, int ld0, int ld1, int ld2) {
   return n > 0 && n <= (int64_t)1 << 30 && C >= 32 && C % 32 == 0 && kBnThreads % (C / 4) == 0 && ld0 % 4 == 0 &&
          ld1 % 4 == 0 && ld2 % 4 == 0;
 }
-static int bn_blocks(int64_t n, int& rows_per_block);
-// BatchNorm(train) from the conv epilogues' block partials (spconv.hip: a3d_conv_bn_train_forward): merge + apply
+// the row blocks of the first-level kernels: 512 rows each, at most kBnMaxBlocks of them
+static int bn_blocks(int64_t n, int& rows_per_block) {
+  int blocks = (int)((n + 511) / 512);
+  if (blocks > kBnMaxBlocks) blocks = kBnMaxBlocks;
+  rows_per_block = (int)((n + blocks - 1) / blocks);
+  return (int)((n + rows_per_block - 1) / rows_per_block);
+}
+static unsigned fin_grid(int ncol) { return (unsigned)((ncol + kFinCols - 1) / kFinCols); }
+static unsigned elem_grid(int64_t n, int C) { return (unsigned)(((size_t)n * (C / 4) + 255) / 256); }
+
+// The workspace of a3d_bn_workspace_bytes: the first level's partials, then [2][C] fp64 sums, then [C] floats.
+struct BnWs { float* partial; double* sums; float* meanf; };
+static size_t bn_partial_bytes(int C) { return align256((size_t)kBnMaxBlocks * 2 * C * sizeof(float)); }
+static size_t bn_sums_bytes(int C) { return align256((size_t)2 * C * sizeof(double)); }
+// -> A3D_OK and the carve, or the workspace error of entry point `who`
+static int bn_carve(const char* who, void* workspace, size_t bytes, int64_t n, int C, BnWs& w, const char* hint = "") {
+  if (bytes < a3d_bn_workspace_bytes(n, C) || ((uintptr_t)workspace & 15)) {
+    set_error("%s: workspace too small or misaligned%s", who, hint);
+    return A3D_ERR_WORKSPACE;
+  }
+  w.partial = (float*)workspace;
+  w.sums = (double*)((char*)workspace + bn_partial_bytes(C));
+  w.meanf = (float*)((char*)w.sums + bn_sums_bytes(C));
+  return A3D_OK;
+}
+
+// One launcher per kernel family; none of them checks its arguments (the entry points do) or the launch (the entry points
+// end with A3D_LAUNCH_CHECK).
+// k_col_partial in `mode` (kColBlockStats: k_bn_block_stats) over x [n][C] -> the number of row blocks written to `partial`,
+// of *rows_per_block rows; `bw`: the operands of mode 2
+constexpr int kColBlockStats = -1;
+struct ColBwd {
+  const float *y, *dy, *rstd;
+  int ldy, lddy, relu;
+};
+static int col_partial(int mode, const float* x, int ldx, int64_t n, int C, const float* mean, const ColBwd* bw, float* partial,
+                       hipStream_t st, int* rows_per_block = nullptr) {
+  ColArgs c = {};
+  c.x = x, c.ldx = ldx, c.n = (int)n, c.C = C, c.mean = mean, c.mode = mode, c.partial = partial;
+  if (bw) c.y = bw->y, c.dy = bw->dy, c.rstd = bw->rstd, c.ldy = bw->ldy, c.lddy = bw->lddy, c.relu = bw->relu;
+  const int blocks = bn_blocks(n, c.rows_per_block);
+  if (rows_per_block) *rows_per_block = c.rows_per_block;
+  if (mode == kColBlockStats) k_bn_block_stats<<<blocks, kBnThreads, 0, st>>>(c);
+  else k_col_partial<<<blocks, kBnThreads, 0, st>>>(c);
+  return blocks;
+}
+// the first half of the backward: sums [2][C] (fp64) = sum g, sum g xhat over the n rows
+static void bn_backward_sums(const float* x, int ldx, const float* y, int ldy, const float* dy, int lddy, int64_t n, int C,
+                             const float* mean, const float* rstd, int relu, float* partial, double* sums, hipStream_t st) {
+  const ColBwd bw = {y, dy, rstd, ldy, lddy, relu};
+  const int blocks = col_partial(2, x, ldx, n, C, mean, &bw, partial, st);
+  k_col_final<kFinLanes, 1, double><<<fin_grid(2 * C), 256, 0, st>>>(partial, blocks, 2 * C, sums);
+}
+static void bn_apply(const float* x, int ldx, int64_t n, int C, const float* gamma, const float* beta, const float* mean,
+                     const float* rstd, const float* res, int ldr, int relu, float* y, int ldy, int zero_row, hipStream_t st) {
+  ApplyArgs a;
+  a.x = x, a.mean = mean, a.rstd = rstd, a.gamma = gamma, a.beta = beta, a.res = res;
+  a.ldx = ldx, a.ldr = ldr, a.ldy = ldy, a.n = (int)n, a.C = C, a.relu = relu, a.y = y, a.zero_row = zero_row;
+  k_bn_apply<<<elem_grid(n, C), 256, 0, st>>>(a);
+}
+// the second half of the backward: dx (and dres) from `sums` over n_stat rows, dgamma / dbeta = param_sums
+static void bn_bwd_apply(const float* x, int ldx, const float* y, int ldy, const float* dy, int lddy, int64_t n, int C,
+                         const float* gamma, const float* mean, const float* rstd, int relu, const double* sums, int64_t n_stat,
+                         const double* param_sums, float* dx, int lddx, float* dres, int lddres, float* dgamma, float* dbeta,
+                         int zero_row, hipStream_t st) {
+  BwdArgs b;
+  b.x = x, b.y = y, b.dy = dy, b.mean = mean, b.rstd = rstd, b.gamma = gamma;
+  b.sums = sums, b.param_sums = param_sums, b.n_stat = (double)n_stat, b.zero_row = zero_row;
+  b.ldx = ldx, b.ldy = ldy, b.lddy = lddy, b.lddx = lddx, b.lddres = lddres, b.n = (int)n, b.C = C;
+  b.relu = relu, b.dx = dx, b.dres = dres, b.dgamma = dgamma, b.dbeta = dbeta;
+  k_bn_bwd_apply<<<elem_grid(n, C), 256, 0, st>>>(b);
+}
+// dx and the row-block partials of dgamma / dbeta -> their column sums -> dgamma, dbeta
+static void ln_backward(const float* x, int ldx, const float* dy, int lddy, int64_t n, int C, const float* gamma, float eps,
+                        float* dx, float* dgamma, float* dbeta, const BnWs& w, hipStream_t st) {
+  LnArgs a = {};
+  a.x = x, a.dy = dy, a.gamma = gamma, a.dx = dx, a.partial = w.partial;
+  a.ldx = ldx, a.ldy = lddy, a.n = (int)n, a.C = C, a.eps = eps;
+  const int blocks = bn_blocks(n, a.rows_per_block);
+  if (C == 128 && !(ldx & 3) && !(lddy & 3)) k_ln_backward128<<<blocks, 256, 0, st>>>(a);
+  else k_ln_backward<<<blocks, 256, 0, st>>>(a);
+  k_col_final<kFinLanes, 1, double><<<fin_grid(2 * C), 256, 0, st>>>(w.partial, blocks, 2 * C, w.sums);
+  k_ln_params<<<(unsigned)((C + 255) / 256), 256, 0, st>>>(w.sums, C, dgamma, dbeta);
+}
+
+// ---- for the conv kernels' epilogues (spconv.hip) ------------------------------------------------------------------
+// BatchNorm(train) from the block partials of a3d_conv_bn_train_forward's epilogue: merge + apply
 int bn_finish_from_partials(const float* partial, int nblocks, int rows_per_block, const float* x, int ldx, int64_t n, int C,
                             const float* gamma, const float* beta, float eps, const float* res, int ldr, int relu, float* y,
                             int ldy, int y_zero_row, float* save_mean, float* save_rstd, float* running_mean,
@@ -550,62 +629,28 @@ int bn_finish_from_partials(const float* partial, int nblocks, int rows_per_bloc
     set_error("bn_finish_from_partials: bad arguments");
     return A3D_ERR_INVALID;
   }
-  k_bn_combine_tiles<<<(unsigned)((C + kFinCols - 1) / kFinCols), 1024, 0, st>>>(partial, nblocks, rows_per_block, (int)n, C, eps, save_mean,
-                                                                               save_rstd, running_mean, running_var, momentum);
-  ApplyArgs a;
-  a.x = x, a.mean = save_mean, a.rstd = save_rstd, a.gamma = gamma, a.beta = beta, a.res = res;
-  a.ldx = ldx, a.ldr = ldr, a.ldy = ldy, a.n = (int)n, a.C = C, a.relu = relu, a.y = y, a.zero_row = y_zero_row;
-  const size_t total = (size_t)n * (C / 4);
-  k_bn_apply<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a);
+  k_bn_combine_tiles<<<fin_grid(C), 1024, 0, st>>>(partial, nblocks, rows_per_block, (int)n, C, eps, save_mean, save_rstd,
+                                                    running_mean, running_var, momentum);
+  bn_apply(x, ldx, n, C, gamma, beta, save_mean, save_rstd, res, ldr, relu, y, ldy, y_zero_row, st);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
-// [blocks][2][C] fp32 partials (the input-gradient conv's epilogue) -> sums [2][C] fp64, blocks added in a fixed order
-// column sums of MANY block partials (one per 64-row tile or 16-row group of a conv epilogue): 256 block lanes x 4 column
-// quads per workgroup, one 16-byte load per block and thread (k_col_final's 16 lanes per column walked 300+ blocks each)
-__global__ void __launch_bounds__(1024) k_col_final_tiles(const float* __restrict__ partial, int nblocks, int ncol, double* out) {
-  __shared__ double sh[kFin2Lanes][kFinCols + 1];
-  const int q = threadIdx.x & 3, bl = threadIdx.x >> 2;
-  const int c0 = blockIdx.x * kFinCols + 4 * q;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (c0 < ncol)
-    for (int b = bl; b < nblocks; b += kFin2Lanes) {
-      const f32x4 v = *(const f32x4*)(partial + (size_t)b * ncol + c0);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) s[t] += (double)v[t];
-    }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) sh[bl][4 * q + t] = s[t];
-  __syncthreads();
-  const int c = blockIdx.x * kFinCols + threadIdx.x;
-  if (threadIdx.x >= kFinCols || c >= ncol) return;
-  double t = 0.0;
-  for (int k = 0; k < kFin2Lanes; ++k) t += sh[k][threadIdx.x];
-  out[c] = t;
-}
+// [blocks][2][C] fp32 partials (the epilogue of a3d_conv_dgrad_bn) -> sums [2][C] fp64, blocks added in a fixed order
 int bn_sums_from_partials(const float* partial, int nblocks, int C, double* sums, hipStream_t st) {
-  if (nblocks >= 64)
-    k_col_final_tiles<<<(unsigned)((2 * C + kFinCols - 1) / kFinCols), 1024, 0, st>>>(partial, nblocks, 2 * C, sums);
-  else
-    k_col_final<<<(unsigned)((2 * C + kFinCols - 1) / kFinCols), 256, 0, st>>>(partial, nblocks, 2, C, sums);
+  if (nblocks >= 64) k_col_final<kFinTileLanes, 4, double><<<fin_grid(2 * C), 1024, 0, st>>>(partial, nblocks, 2 * C, sums);
+  else k_col_final<kFinLanes, 1, double><<<fin_grid(2 * C), 256, 0, st>>>(partial, nblocks, 2 * C, sums);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
-}
-static int bn_blocks(int64_t n, int& rows_per_block) {
-  int blocks = (int)((n + 511) / 512);
-  if (blocks > kBnMaxBlocks) blocks = kBnMaxBlocks;
-  rows_per_block = (int)((n + blocks - 1) / blocks);
-  return (int)((n + rows_per_block - 1) / rows_per_block);
 }
 
 }  // namespace a3d
 
 using namespace a3d;
 
+// ---- entry points ------------------------------------------------------------------------------------------------------
 extern "C" size_t a3d_bn_workspace_bytes(int64_t n, int C) {
   if (n <= 0 || C <= 0) return 0;
-  return align256((size_t)kBnMaxBlocks * 2 * C * sizeof(float)) + align256((size_t)2 * C * sizeof(double)) +
-         align256((size_t)C * sizeof(float)) + 256;
+  return bn_partial_bytes(C) + bn_sums_bytes(C) + align256((size_t)C * sizeof(float)) + 256;
 }
 
 extern "C" int a3d_bn_train_forward(const float* x_dev, int ldx, int64_t n, int C, const float* gamma_dev,
@@ -618,28 +663,14 @@ extern "C" int a3d_bn_train_forward(const float* x_dev, int ldx, int64_t n, int 
     set_error("a3d_bn_train_forward: bad arguments (C a multiple of 32 dividing 768, leading dimensions multiples of 4)");
     return A3D_ERR_INVALID;
   }
-  if (workspace_bytes < a3d_bn_workspace_bytes(n, C) || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_bn_train_forward: workspace too small or misaligned");
-    return A3D_ERR_WORKSPACE;
-  }
+  BnWs w;
+  if (int rc = bn_carve("a3d_bn_train_forward", workspace_dev, workspace_bytes, n, C, w)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace_dev;
-  double* sums = (double*)((char*)workspace_dev + align256((size_t)kBnMaxBlocks * 2 * C * sizeof(float)));
-  ColArgs c;
-  memset(&c, 0, sizeof(c));
-  c.x = x_dev, c.ldx = ldx, c.n = (int)n, c.C = C, c.partial = partial;
-  const int blocks = bn_blocks(n, c.rows_per_block);
-  const unsigned cb = (unsigned)((2 * C + 255) / 256);
-  (void)sums;
-  (void)cb;
-  k_bn_block_stats<<<blocks, kBnThreads, 0, st>>>(c);
-  k_bn_combine<<<(unsigned)((C + kFinCols - 1) / kFinCols), 256, 0, st>>>(partial, x_dev, blocks, c.rows_per_block, (int)n, C, eps,
-                                                             save_mean_dev, save_rstd_dev, running_mean_dev, running_var_dev, momentum);
-  ApplyArgs a;
-  a.x = x_dev, a.mean = save_mean_dev, a.rstd = save_rstd_dev, a.gamma = gamma_dev, a.beta = beta_dev, a.res = res_dev;
-  a.ldx = ldx, a.ldr = ldr, a.ldy = ldy, a.n = (int)n, a.C = C, a.relu = relu, a.y = y_dev, a.zero_row = y_zero_row;
-  const size_t total = (size_t)n * (C / 4);
-  k_bn_apply<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a);
+  int rows_per_block;
+  const int blocks = col_partial(kColBlockStats, x_dev, ldx, n, C, nullptr, nullptr, w.partial, st, &rows_per_block);
+  k_bn_combine<<<fin_grid(C), 256, 0, st>>>(w.partial, x_dev, blocks, rows_per_block, (int)n, C, eps, save_mean_dev, save_rstd_dev,
+                                            running_mean_dev, running_var_dev, momentum);
+  bn_apply(x_dev, ldx, n, C, gamma_dev, beta_dev, save_mean_dev, save_rstd_dev, res_dev, ldr, relu, y_dev, ldy, y_zero_row, st);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -655,32 +686,17 @@ extern "C" int a3d_bn_train_backward(const float* x_dev, int ldx, const float* y
     set_error("a3d_bn_train_backward: bad arguments");
     return A3D_ERR_INVALID;
   }
-  if (workspace_bytes < a3d_bn_workspace_bytes(n, C) || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_bn_train_backward: workspace too small or misaligned");
-    return A3D_ERR_WORKSPACE;
-  }
+  BnWs w;
+  if (int rc = bn_carve("a3d_bn_train_backward", workspace_dev, workspace_bytes, n, C, w)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace_dev;
-  double* sums = (double*)((char*)workspace_dev + align256((size_t)kBnMaxBlocks * 2 * C * sizeof(float)));
-  ColArgs c;
-  memset(&c, 0, sizeof(c));
-  c.x = x_dev, c.y = y_dev, c.dy = dy_dev, c.mean = save_mean_dev, c.rstd = save_rstd_dev;
-  c.ldx = ldx, c.ldy = ldy, c.lddy = lddy, c.n = (int)n, c.C = C, c.relu = relu, c.mode = 2, c.partial = partial;
-  const int blocks = bn_blocks(n, c.rows_per_block);
-  k_col_partial<<<blocks, kBnThreads, 0, st>>>(c);
-  k_col_final<<<(unsigned)((2 * C + kFinCols - 1) / kFinCols), 256, 0, st>>>(partial, blocks, 2, C, sums);
-  BwdArgs b;
-  b.x = x_dev, b.y = y_dev, b.dy = dy_dev, b.mean = save_mean_dev, b.rstd = save_rstd_dev, b.gamma = gamma_dev;
-  b.sums = sums, b.param_sums = sums, b.n_stat = (double)n, b.zero_row = zero_row;
-  b.ldx = ldx, b.ldy = ldy, b.lddy = lddy, b.lddx = lddx, b.lddres = lddres, b.n = (int)n, b.C = C;
-  b.relu = relu, b.dx = dx_dev, b.dres = dres_dev, b.dgamma = dgamma_dev, b.dbeta = dbeta_dev;
-  const size_t total = (size_t)n * (C / 4);
-  k_bn_bwd_apply<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(b);
+  // a3d_bn_backward_sums, then a3d_bn_backward_apply with the statistics' rows = this call's rows
+  bn_backward_sums(x_dev, ldx, y_dev, ldy, dy_dev, lddy, n, C, save_mean_dev, save_rstd_dev, relu, w.partial, w.sums, st);
+  bn_bwd_apply(x_dev, ldx, y_dev, ldy, dy_dev, lddy, n, C, gamma_dev, save_mean_dev, save_rstd_dev, relu, w.sums, n, w.sums, dx_dev,
+               lddx, dres_dev, lddres, dgamma_dev, dbeta_dev, zero_row, st);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
 
-// column sums of a [n][C] matrix (bias gradient of lin_squeeze_head: sum over rows of dy)
 // ---- the same BatchNorm in pieces, for statistics that span the data-parallel ranks (SyncBN): the caller exchanges
 // the per-rank numbers (torch.distributed) between the calls.  Reference semantics: ME.MinkowskiBatchNorm normalises
 // over ALL rows of the batch on one device (models/modules/common.py:20-22); with one scene per rank the strict
@@ -696,28 +712,16 @@ extern "C" int a3d_bn_local_stats(const float* x_dev, int ldx, int64_t n, int C,
     set_error("a3d_bn_local_stats: bad arguments");
     return A3D_ERR_INVALID;
   }
-  if (workspace_bytes < a3d_bn_workspace_bytes(n, C) || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_bn_local_stats: workspace too small or misaligned");
-    return A3D_ERR_WORKSPACE;
-  }
+  BnWs w;
+  if (int rc = bn_carve("a3d_bn_local_stats", workspace_dev, workspace_bytes, n, C, w)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace_dev;
-  double* sums = (double*)((char*)workspace_dev + align256((size_t)kBnMaxBlocks * 2 * C * sizeof(float)));
-  float* meanf = (float*)((char*)sums + align256((size_t)2 * C * sizeof(double)));
-  ColArgs c;
-  memset(&c, 0, sizeof(c));
-  c.x = x_dev, c.ldx = ldx, c.n = (int)n, c.C = C, c.partial = partial;
-  const int blocks = bn_blocks(n, c.rows_per_block);
   const unsigned cb = (unsigned)((2 * C + 255) / 256);
-  c.mode = 0;
-  k_col_partial<<<blocks, kBnThreads, 0, st>>>(c);
-  const unsigned fb = (unsigned)((C + kFinCols - 1) / kFinCols);
-  k_col_final<<<fb, 256, 0, st>>>(partial, blocks, 1, C, sums);
-  k_bn_mean<<<cb, 256, 0, st>>>(sums, C, (double)n, meanf);
-  k_scale_f64<<<cb, 256, 0, st>>>(sums, C, 1.0 / (double)n, stats_dev);              // the mean in fp64
-  c.mode = 1, c.mean = meanf;
-  k_col_partial<<<blocks, kBnThreads, 0, st>>>(c);
-  k_col_final<<<fb, 256, 0, st>>>(partial, blocks, 1, C, stats_dev + C);
+  int blocks = col_partial(0, x_dev, ldx, n, C, nullptr, nullptr, w.partial, st);
+  k_col_final<kFinLanes, 1, double><<<fin_grid(C), 256, 0, st>>>(w.partial, blocks, C, w.sums);
+  k_bn_mean<<<cb, 256, 0, st>>>(w.sums, C, (double)n, w.meanf);
+  k_scale_f64<<<cb, 256, 0, st>>>(w.sums, C, 1.0 / (double)n, stats_dev);              // the mean in fp64
+  blocks = col_partial(1, x_dev, ldx, n, C, w.meanf, nullptr, w.partial, st);
+  k_col_final<kFinLanes, 1, double><<<fin_grid(C), 256, 0, st>>>(w.partial, blocks, C, stats_dev + C);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -729,11 +733,7 @@ extern "C" int a3d_bn_apply(const float* x_dev, int ldx, int64_t n, int C, const
     set_error("a3d_bn_apply: bad arguments");
     return A3D_ERR_INVALID;
   }
-  ApplyArgs a;
-  a.x = x_dev, a.mean = mean_dev, a.rstd = rstd_dev, a.gamma = gamma_dev, a.beta = beta_dev, a.res = res_dev;
-  a.ldx = ldx, a.ldr = ldr, a.ldy = ldy, a.n = (int)n, a.C = C, a.relu = relu, a.y = y_dev, a.zero_row = y_zero_row;
-  const size_t total = (size_t)n * (C / 4);
-  k_bn_apply<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
+  bn_apply(x_dev, ldx, n, C, gamma_dev, beta_dev, mean_dev, rstd_dev, res_dev, ldr, relu, y_dev, ldy, y_zero_row, (hipStream_t)stream);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -746,19 +746,9 @@ extern "C" int a3d_bn_backward_sums(const float* x_dev, int ldx, const float* y_
     set_error("a3d_bn_backward_sums: bad arguments");
     return A3D_ERR_INVALID;
   }
-  if (workspace_bytes < a3d_bn_workspace_bytes(n, C) || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_bn_backward_sums: workspace too small or misaligned");
-    return A3D_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace_dev;
-  ColArgs c;
-  memset(&c, 0, sizeof(c));
-  c.x = x_dev, c.y = y_dev, c.dy = dy_dev, c.mean = mean_dev, c.rstd = rstd_dev;
-  c.ldx = ldx, c.ldy = ldy, c.lddy = lddy, c.n = (int)n, c.C = C, c.relu = relu, c.mode = 2, c.partial = partial;
-  const int blocks = bn_blocks(n, c.rows_per_block);
-  k_col_partial<<<blocks, kBnThreads, 0, st>>>(c);
-  k_col_final<<<(unsigned)((2 * C + kFinCols - 1) / kFinCols), 256, 0, st>>>(partial, blocks, 2, C, sums_dev);
+  BnWs w;
+  if (int rc = bn_carve("a3d_bn_backward_sums", workspace_dev, workspace_bytes, n, C, w)) return rc;
+  bn_backward_sums(x_dev, ldx, y_dev, ldy, dy_dev, lddy, n, C, mean_dev, rstd_dev, relu, w.partial, sums_dev, (hipStream_t)stream);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -774,35 +764,24 @@ extern "C" int a3d_bn_backward_apply(const float* x_dev, int ldx, const float* y
     set_error("a3d_bn_backward_apply: bad arguments");
     return A3D_ERR_INVALID;
   }
-  BwdArgs b;
-  b.x = x_dev, b.y = y_dev, b.dy = dy_dev, b.mean = mean_dev, b.rstd = rstd_dev, b.gamma = gamma_dev;
-  b.sums = global_sums_dev, b.param_sums = local_sums_dev, b.n_stat = (double)n_global, b.zero_row = zero_row;
-  b.ldx = ldx, b.ldy = ldy, b.lddy = lddy, b.lddx = lddx, b.lddres = lddres, b.n = (int)n, b.C = C;
-  b.relu = relu, b.dx = dx_dev, b.dres = dres_dev, b.dgamma = dgamma_dev, b.dbeta = dbeta_dev;
-  const size_t total = (size_t)n * (C / 4);
-  k_bn_bwd_apply<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(b);
+  bn_bwd_apply(x_dev, ldx, y_dev, ldy, dy_dev, lddy, n, C, gamma_dev, mean_dev, rstd_dev, relu, global_sums_dev, n_global,
+               local_sums_dev, dx_dev, lddx, dres_dev, lddres, dgamma_dev, dbeta_dev, zero_row, (hipStream_t)stream);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
 
+// column sums of a [n][C] matrix (bias gradient of lin_squeeze_head: sum over rows of dy)
 extern "C" int a3d_column_sums(const float* x_dev, int ldx, int64_t n, int C, float* out_dev, void* workspace_dev,
                                size_t workspace_bytes, void* stream) {
   if (!x_dev || !out_dev || !workspace_dev || !bn_shape_ok(n, C, ldx, 4, 4)) {
     set_error("a3d_column_sums: bad arguments");
     return A3D_ERR_INVALID;
   }
-  if (workspace_bytes < a3d_bn_workspace_bytes(n, C) || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_column_sums: workspace too small or misaligned");
-    return A3D_ERR_WORKSPACE;
-  }
+  BnWs w;
+  if (int rc = bn_carve("a3d_column_sums", workspace_dev, workspace_bytes, n, C, w)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace_dev;
-  ColArgs c;
-  memset(&c, 0, sizeof(c));
-  c.x = x_dev, c.ldx = ldx, c.n = (int)n, c.C = C, c.partial = partial, c.mode = 0;
-  const int blocks = bn_blocks(n, c.rows_per_block);
-  k_col_partial<<<blocks, kBnThreads, 0, st>>>(c);
-  k_col_final_f32<<<(unsigned)((C + kFinCols - 1) / kFinCols), 256, 0, st>>>(partial, blocks, C, out_dev);
+  const int blocks = col_partial(0, x_dev, ldx, n, C, nullptr, nullptr, w.partial, st);
+  k_col_final<kFinLanes, 1, float><<<fin_grid(C), 256, 0, st>>>(w.partial, blocks, C, out_dev);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }
@@ -814,8 +793,7 @@ extern "C" int a3d_layernorm_forward(const float* x_dev, int ldx, int64_t n, int
     set_error("a3d_layernorm_forward: bad arguments (C a multiple of 64, <= 512)");
     return A3D_ERR_INVALID;
   }
-  LnArgs a;
-  memset(&a, 0, sizeof(a));
+  LnArgs a = {};
   a.x = x_dev, a.gamma = gamma_dev, a.beta = beta_dev, a.y = y_dev, a.ldx = ldx, a.ldy = ldy, a.n = (int)n, a.C = C, a.eps = eps;
   if (C == 128 && !(ldx & 3) && !(ldy & 3)) k_ln_forward128<<<(unsigned)((n + 15) / 16), 256, 0, (hipStream_t)stream>>>(a);
   else k_ln_forward<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(a);
@@ -831,22 +809,9 @@ extern "C" int a3d_layernorm_backward(const float* x_dev, int ldx, const float* 
     set_error("a3d_layernorm_backward: bad arguments (C a multiple of 64, <= 512; dx has the layout of x)");
     return A3D_ERR_INVALID;
   }
-  if (workspace_bytes < a3d_bn_workspace_bytes(n, C) || ((uintptr_t)workspace_dev & 15)) {
-    set_error("a3d_layernorm_backward: workspace too small or misaligned (a3d_bn_workspace_bytes)");
-    return A3D_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace_dev;
-  double* sums = (double*)((char*)workspace_dev + align256((size_t)kBnMaxBlocks * 2 * C * sizeof(float)));
-  LnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x_dev, a.dy = dy_dev, a.gamma = gamma_dev, a.dx = dx_dev, a.partial = partial;
-  a.ldx = ldx, a.ldy = lddy, a.n = (int)n, a.C = C, a.eps = eps;
-  const int blocks = bn_blocks(n, a.rows_per_block);
-  if (C == 128 && !(ldx & 3) && !(lddy & 3)) k_ln_backward128<<<blocks, 256, 0, st>>>(a);
-  else k_ln_backward<<<blocks, 256, 0, st>>>(a);
-  k_col_final<<<(unsigned)((2 * C + kFinCols - 1) / kFinCols), 256, 0, st>>>(partial, blocks, 2, C, sums);
-  k_ln_params<<<(unsigned)((C + 255) / 256), 256, 0, st>>>(sums, C, dgamma_dev, dbeta_dev);
+  BnWs w;
+  if (int rc = bn_carve("a3d_layernorm_backward", workspace_dev, workspace_bytes, n, C, w, " (a3d_bn_workspace_bytes)")) return rc;
+  ln_backward(x_dev, ldx, dy_dev, lddy, n, C, gamma_dev, eps, dx_dev, dgamma_dev, dbeta_dev, w, (hipStream_t)stream);
   A3D_LAUNCH_CHECK();
   return A3D_OK;
 }

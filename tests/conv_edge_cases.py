@@ -244,8 +244,8 @@ LINEAR_CASES = [
     (("s20000", "linear", 0, 32, 32, 0, 1), ("sk", 1, 32, 32, 0, 0, 0, 0)),   # G 315 P 0 tiles 315
     (("s20000", "linear", 0, 32, 32, 0, 0), ("sk", 1, 32, 32, 0, 0, 0, 0)),
 ]
-# 63 / 64 per-block partials: below 64 blocks bn_sums_from_partials folds them with k_col_final, from 64 on with
-# k_col_final_tiles (bnorm.hip).  64-row tiles of k_conv_sk / k_conv_deep on box4032 / box4096, 16-row groups of k_conv_wl
+# 63 / 64 per-block partials: below 64 blocks bn_sums_from_partials folds them with k_col_final<16, 1>, from 64 on with
+# k_col_final<256, 4> (bnorm.hip: 16 or 256 block lanes per column).  64-row tiles of k_conv_sk / k_conv_deep on box4032 / box4096, 16-row groups of k_conv_wl
 # on box1008 / box1024; level 0 only, not part of SMALL_SCENES / LARGE_SCENES (the reachability sweep keeps its meaning)
 TRAIN_BOX_CASES = [
     (("box1008", "conv3", 0, 32, 32, 0, 1), ("wl", 27)),

@@ -5,8 +5,8 @@ Every kernel family is compiled three times.  STATS = 0 is the inference build (
 build behind a3d_conv_bn_train_forward: its epilogue also writes, per 64-row tile (16-row group for k_conv_wl) and column,
 the sum of the tile's rows and their squared deviations from the tile mean, which k_bn_combine_tiles (bnorm.hip) merges.
 STATS = 2 is the build behind a3d_conv_dgrad_bn: its epilogue adds the gradient already in the buffer, masks by y > 0,
-stores g and writes per-tile sums of g and g * xhat, which bn_sums_from_partials folds (k_col_final below 64 blocks,
-k_col_final_tiles from 64 on).  These are separate code objects, their epilogues compiled from one source: the helpers above
+stores g and writes per-tile sums of g and g * xhat, which bn_sums_from_partials folds (k_col_final<16, 1> below 64 blocks,
+k_col_final<256, 4> from 64 on).  These are separate code objects, their epilogues compiled from one source: the helpers above
 k_conv_sk in spconv.hip, which k_conv_deep and k_conv_wl call for both builds and k_conv_sk for STATS = 2 and for the write of
 a tile's partials (its STATS = 1 statistics and its plain epilogue stand spelled out in the kernel); plan_conv picks their class
 exactly as it does for the inference build (test_conv_plan_classes.py holds that), so the class tables of conv_edge_cases.py

@@ -573,6 +573,107 @@ def test_batchnorm_zero_row_adds_one_zero_row_and_changes_nothing_else():
     assert torch.equal(dg0, dg1) and torch.equal(db0, db1)
 
 
+# the four SyncBN pieces on one GPU, no process group: two rows, one row past a 512-row block, three blocks + a one-row tail
+SYNCBN_CASES = [(n, C_) for C_ in (32, 96) for n in (2, 513, 1025)]
+# 4 x the largest error measured over SYNCBN_CASES (see the docstring below), relative to max(1, |ref|max)
+SYNCBN_MEAN_TOL, SYNCBN_M2_TOL = 4 * 6.326e-08, 4 * 1.409e-07
+
+
+def _syncbn_backward_apply(lib, x, y, dy, n, C_, gamma, mean, rstd, glob, n_global, local, zero_row):
+    """a3d_bn_backward_apply (ReLU on, residual gradient wanted) into NaN-filled outputs -> (dx, dres, dgamma, dbeta)."""
+    dx, dres = (torch.full((n + zero_row, C_), NAN, device="cuda") for _ in range(2))
+    dgamma, dbeta = torch.full((C_,), NAN, device="cuda"), torch.full((C_,), NAN, device="cuda")
+    L.check(lib.a3d_bn_backward_apply(_ptr(x), C_, _ptr(y), C_, _ptr(dy), C_, n, C_, _ptr(gamma), _ptr(mean), _ptr(rstd), 1,
+                                      _ptr(glob), n_global, _ptr(local), _ptr(dx), C_, _ptr(dres), C_, _ptr(dgamma),
+                                      _ptr(dbeta), zero_row, None), "a3d_bn_backward_apply")
+    return dx, dres, dgamma, dbeta
+
+
+@pytest.mark.parametrize("n,C_", SYNCBN_CASES)
+def test_syncbn_pieces_on_one_gpu(n, C_):
+    """a3d_bn_local_stats, a3d_bn_apply, a3d_bn_backward_sums and a3d_bn_backward_apply called through the library with
+    no process group (the two-rank run of test_gpu_distributed.py is the only other GPU test that reaches them), on
+    ``_bn_inputs``, with residual and ReLU.
+
+    Forward: local statistics, the host combination of bn_sync_forward for one rank, then a3d_bn_apply.  y against float64
+    batch_norm to the 2e-5 of test_batchnorm_training_at_row_block_edges.  stats[0:C] / stats[C:2C] against the float64
+    mean / sum of squared deviations: no project bound, so 4 x the largest error measured on an MI355X over these six
+    cases, relative to max(1, |ref|max) (the margin covers seed-to-seed variation of an fp32 block sum).  Measured:
+      (n, C)      mean       M2            (n, C)      mean       M2
+      (2, 32)     2.674e-08  6.849e-08     (2, 96)     5.099e-08  1.178e-07
+      (513, 32)   5.670e-08  1.409e-07     (513, 96)   6.326e-08  9.154e-08
+      (1025, 32)  5.007e-08  8.369e-08     (1025, 96)  5.545e-08  1.273e-07
+    so the bounds are 4 x 6.326e-08 for the mean and 4 x 1.409e-07 for the sum of squared deviations (``pytest -s`` prints
+    the figures).
+    Backward with n_global = n: dx, dres, dgamma and dbeta equal a3d_bn_train_backward's bit for bit (the same three
+    kernels in the same order).  Backward with n_global = 2 n and twice the local sums (two identical ranks): dx against
+    float64 gamma rstd (g - sum g / 2n - xhat sum g xhat / 2n) to the 5e-5 max(1, |dx|max) of the test above, dgamma /
+    dbeta the local sums.  zero_row = 1: row n of y, dx and dres is zero, the rows before it unchanged bit for bit."""
+    lib = L.load()
+    x, res, gamma, beta, _, _, dy = _bn_inputs(n, C_)
+    xd = x.double()
+    mean_ref = xd.mean(0)
+    m2_ref = ((xd - mean_ref) ** 2).sum(0)
+    y_ref = torch.relu(torch.nn.functional.batch_norm(xd, None, None, gamma.double(), beta.double(), training=True, eps=1e-5) +
+                       res.double())
+    x_d, res_d, dy_d, gam, bet = x.cuda(), res.cuda(), dy.cuda(), gamma.cuda(), beta.cuda()
+    nbytes = lib.a3d_bn_workspace_bytes(n, C_)
+
+    # forward
+    st = torch.full((2 * C_ + 1,), NAN, dtype=torch.float64, device="cuda")
+    ws = _scratch(nbytes)
+    L.check(lib.a3d_bn_local_stats(_ptr(x_d), C_, n, C_, _ptr(st), _ptr(ws), nbytes, None), "a3d_bn_local_stats")
+    e_mean = _err(st[:C_], mean_ref) / max(1.0, mean_ref.abs().max().item())
+    e_m2 = _err(st[C_:2 * C_], m2_ref) / max(1.0, m2_ref.abs().max().item())
+    print(f"[syncbn] n={n} C={C_}: local_stats mean error {e_mean:.3e}  M2 error {e_m2:.3e}  (relative to max(1, |ref|max))")
+    assert e_mean <= SYNCBN_MEAN_TOL and e_m2 <= SYNCBN_M2_TOL, (e_mean, e_m2)
+    st[2 * C_] = float(n)
+    allst = st[None]                                             # bn_sync_forward's combination, world = 1
+    cnt = allst[:, 2 * C_:2 * C_ + 1]
+    n_glob = cnt.sum()
+    mean = (allst[:, :C_] * cnt).sum(0) / n_glob
+    m2 = (allst[:, C_:2 * C_] + cnt * (allst[:, :C_] - mean) ** 2).sum(0)
+    mean_f = mean.to(torch.float32)
+    rstd = 1.0 / torch.sqrt((m2 / n_glob).to(torch.float32) + 1e-5)
+    ys = []
+    for zero_row in (0, 1):
+        y = torch.full((n + zero_row, C_), NAN, device="cuda")
+        L.check(lib.a3d_bn_apply(_ptr(x_d), C_, n, C_, _ptr(gam), _ptr(bet), _ptr(mean_f), _ptr(rstd), _ptr(res_d), C_, 1,
+                                 _ptr(y), C_, zero_row, None), "a3d_bn_apply")
+        ys.append(y)
+    y = ys[0]
+    assert _err(y, y_ref) <= 2e-5
+    assert (ys[1][n] == 0).all() and torch.equal(ys[1][:n], y)
+
+    # backward, n_global = n: the pieces against the one-call entry point
+    local = torch.full((2 * C_,), NAN, dtype=torch.float64, device="cuda")
+    ws = _scratch(nbytes)
+    L.check(lib.a3d_bn_backward_sums(_ptr(x_d), C_, _ptr(y), C_, _ptr(dy_d), C_, n, C_, _ptr(mean_f), _ptr(rstd), 1, _ptr(local),
+                                     _ptr(ws), nbytes, None), "a3d_bn_backward_sums")
+    pieces = _syncbn_backward_apply(lib, x_d, y, dy_d, n, C_, gam, mean_f, rstd, local, n, local, 0)
+    whole = [torch.full((n, C_), NAN, device="cuda") for _ in range(2)] + [torch.full((C_,), NAN, device="cuda") for _ in range(2)]
+    ws = _scratch(nbytes)
+    L.check(lib.a3d_bn_train_backward(_ptr(x_d), C_, _ptr(y), C_, _ptr(dy_d), C_, n, C_, _ptr(gam), _ptr(mean_f), _ptr(rstd), 1,
+                                      _ptr(whole[0]), C_, _ptr(whole[1]), C_, _ptr(whole[2]), _ptr(whole[3]), 0, _ptr(ws), nbytes,
+                                      None), "a3d_bn_train_backward")
+    for name, a, b in zip(("dx", "dres", "dgamma", "dbeta"), pieces, whole):
+        assert torch.equal(a, b), name
+    with_row = _syncbn_backward_apply(lib, x_d, y, dy_d, n, C_, gam, mean_f, rstd, local, n, local, 1)
+    for name, a, b in zip(("dx", "dres"), with_row, pieces):
+        assert (a[n] == 0).all() and torch.equal(a[:n], b), name
+    assert torch.equal(with_row[2], pieces[2]) and torch.equal(with_row[3], pieces[3])
+
+    # backward, n_global = 2 n: two identical ranks
+    dx2, dres2, dgamma2, dbeta2 = _syncbn_backward_apply(lib, x_d, y, dy_d, n, C_, gam, mean_f, rstd, 2.0 * local, 2 * n, local, 0)
+    rstd_ref = 1.0 / torch.sqrt(m2_ref / n + 1e-5)
+    g = dy.double() * (y_ref > 0)
+    xhat = (xd - mean_ref) * rstd_ref
+    dx_ref = gamma.double() * rstd_ref * (g - 2.0 * g.sum(0) / (2 * n) - xhat * (2.0 * (g * xhat).sum(0)) / (2 * n))
+    assert _err(dx2, dx_ref) <= 5e-5 * max(1.0, dx_ref.abs().max().item())
+    assert torch.equal(dres2, pieces[1])
+    assert torch.equal(dbeta2, local[:C_].float()) and torch.equal(dgamma2, local[C_:].float())
+
+
 @pytest.mark.parametrize("n", [1, 512, 513])
 def test_column_sums_at_row_block_edges(n):
     """a3d_column_sums against the float64 sum to the project's 1e-3, bit-equal when repeated."""
