@@ -108,7 +108,8 @@ __global__ void k_make_keys(const int32_t* __restrict__ coords4, int n, uint64_t
     vals[i] = i;
     if (b < 0 || b > 1022 || x < -lim || x >= lim || y < -lim || y >= lim || z < -lim || z >= lim) {
       atomicMin(&sizes_dev[5], A3D_ERR_COORD_RANGE);
-      keys[i] = 0;
+      keys[i] = kEmptyKey;   // the one key no voxel has (batch index 1023): head_flags does not count it as a duplicate
+                             // (0 is the key of (0, -2^17, -2^17, -2^17), and of every other refused row)
     } else {
       keys[i] = make_key(b, x, y, z, 0);
       lo[0] = hi[0] = x, lo[1] = hi[1] = y, lo[2] = hi[2] = z;
@@ -162,7 +163,7 @@ __device__ __forceinline__ bool head_flags(const uint64_t* __restrict__ keys, in
     const uint64_t k = keys[i], kp = i > 0 ? keys[i - 1] : 0;
 #pragma unroll
     for (int L = 1; L < A3D_NUM_LEVELS; ++L) f[L - 1] = (i == 0) || ((k >> (3 * L)) != (kp >> (3 * L)));
-    return i > 0 && k == kp;
+    return i > 0 && k == kp && k != kEmptyKey;   // rows refused by k_make_keys are reported as out of range, not as duplicates
   }
   return false;
 }
